@@ -1,6 +1,6 @@
 """Benchmark of the hot path: circuits/sec of one GNN train step on synthetic 100-qubit TFIM-Trotter graphs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -9,9 +9,11 @@ One step = device batch assembly -> forward -> MSE -> backward -> (gradient all-
 launched BEFORE this process makes any HIP call) and relays rank 0's line.  The corpus is 8 x batch x N circuits
 (">= 8 x batch"), sharded by circuit: rank r builds only its 1/N of the arena in its own HBM
 (``DataParallelShard.split`` balances node counts), so per-GPU work is fixed as N grows ("weak").
-Rank 0 prints ONE JSON line (contract in the task statement) carrying ``roofline`` (the CSR aggregation kernel,
-timed live with HIP events on the stream it runs on) and, at N=1, ``cpu_baseline`` (the CPU oracle on a bounded
-sample of the same workload), ``parity`` and ``accuracy``.
+Rank 0 prints ONE JSON line (contract in the task statement).  A plain run sets up, warms up, times exactly ``--steps``
+steps and prints it.  ``--full`` then also measures the host's enqueue time per step and ``roofline`` (the CSR aggregation
+kernel, timed live with HIP events on the stream it runs on) and, at N=1, ``cpu_baseline`` (the CPU oracle on a bounded
+sample of the same workload), ``parity``, ``accuracy`` and the other legs.  ``--dump-outputs DIR`` writes what the last
+timed step computed (``dump_outputs``).
 """
 import argparse
 import json
@@ -1303,17 +1305,20 @@ def headline_record(full):
     return rec
 
 
-def emit(full):
-    """stdout: ONE JSON line, the headline record (the task's contract: "rank 0 prints ONE JSON line").  The full record of
-    every leg lands in gpurun_out/bench_full.json (best effort: the directory may not be writable where the driver runs);
-    MLQEM_BENCH_FULL_STDOUT=1 also prints it as an EARLIER stdout line (scripts/refresh_profiles.sh reads it from there)."""
-    try:
-        os.makedirs(os.path.join(ROOT, os.path.dirname(FULL_RECORD)), exist_ok=True)
-        with open(os.path.join(ROOT, FULL_RECORD), "w") as fh:
-            json.dump(full, fh, indent=1)
-    except OSError as exc:
-        progress(f"could not write {FULL_RECORD}: {exc}")
+def emit(full, side_file=True):
+    """stdout: ONE JSON line, the headline record (the task's contract: "rank 0 prints ONE JSON line").  With ``side_file``
+    (``--full``) the full record of every leg lands in FULL_RECORD (best effort: the directory may not be writable where the
+    benchmark runs); MLQEM_BENCH_FULL_STDOUT=1 also prints it as an EARLIER stdout line (scripts/refresh_profiles.sh reads it from there)."""
+    if side_file:
+        try:
+            os.makedirs(os.path.join(ROOT, os.path.dirname(FULL_RECORD)), exist_ok=True)
+            with open(os.path.join(ROOT, FULL_RECORD), "w") as fh:
+                json.dump(full, fh, indent=1)
+        except OSError as exc:
+            progress(f"could not write {FULL_RECORD}: {exc}")
     head = headline_record(full)
+    if not side_file:
+        head.pop("full_record")
     text = json.dumps(head)
     if len(text) > HEADLINE_MAX_BYTES:          # never again a line the driver cannot parse: drop the optional scalars
         for k in list(FLAT_KEYS) + ["parity"]:
@@ -1322,6 +1327,16 @@ def emit(full):
     if os.environ.get("MLQEM_BENCH_FULL_STDOUT", "0") == "1":
         print(json.dumps(dict(full, record="full (every leg); the headline record is the next and last line")), flush=True)
     print(text, flush=True)
+
+
+def dump_outputs(out_dir, loss, trainer):
+    """``--dump-outputs``: what the last timed step hands its caller, as float32 ``out_dir/<name>.npy``: ``loss`` (that step's
+    MSE), ``params`` (every model parameter after that step's Adam update, flattened in parameter order) and ``grad`` (that
+    step's gradient in the same order; at N > 1 the all-reduced mean).  The corpus, the model and the batch order are seeded, so
+    two builds given the same arguments can be compared output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in (("loss", loss), ("params", trainer.flat_param), ("grad", trainer.flat_grad)):
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def spawn_ranks(n, argv):
@@ -1349,7 +1364,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=DEFAULT_BATCH, help="circuits per step per GPU")
     ap.add_argument("--n-j", type=int, default=0, help="J values per Trotter step count; 0 = 8 x batch x gpus / 10")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU legs (cpu_baseline, parity, accuracy, family_b)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the host enqueue time, the roofline leg and, at N = 1, every other leg "
+                         "(cpu_baseline, parity, accuracy, family_b, small_batch, mlp_head, configs, inference)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU legs (cpu_baseline, parity, accuracy, family_b) and the legs after them")
     ap.add_argument("--strong", action="store_true",
                     help="strong scaling: --batch is the GLOBAL number of circuits per step (each rank takes batch / gpus) and the corpus does "
                          "not grow with the number of GPUs; default: weak scaling (--batch circuits per step PER GPU)")
@@ -1445,6 +1465,8 @@ def main():
     elapsed = time.perf_counter() - t0
     per_step = np.array([marks[k].elapsed_time(marks[k + 1]) for k in range(args.steps)])
     loss = loss.clone()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, trainer)
     joined = 1
     dp_host_ms = None
     if distributed:
@@ -1460,19 +1482,19 @@ def main():
         torch.distributed.all_reduce(ones, op=torch.distributed.ReduceOp.SUM)
         elapsed, joined = t[0].item(), int(round(ones.item()))
 
-    # how long the HOST needs to enqueue one step (the step is device-bound only while this stays below ms_per_step): a few
-    # extra steps, timed up to the return of the last enqueue
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(4):
-        step()
-    host_ms = (time.perf_counter() - t1) / 4 * 1e3
-    torch.cuda.synchronize()
+    if args.full:
+        # how long the HOST needs to enqueue one step (the step is device-bound only while this stays below ms_per_step): a few
+        # extra steps, timed up to the return of the last enqueue
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(4):
+            step()
+        host_ms = (time.perf_counter() - t1) / 4 * 1e3
+        torch.cuda.synchronize()
 
     if rank == 0:
         total = args.batch * joined * args.steps
-        fixed = arena.batch(fixed_ids(n_local, args.batch))
-        progress(f"timed region done: {total / elapsed:.0f} circuits/s; roofline leg")
+        progress(f"timed region done: {total / elapsed:.0f} circuits/s")
         line = {
             "metric": "circuits/sec (GNN train step), 100q TFIM Trotter",
             "value": round(total / elapsed, 2), "unit": "circuits/s", "n_gpus": joined, "steps": args.steps,
@@ -1498,10 +1520,14 @@ def main():
             # the same percentiles as top-level numbers (a driver that keeps only scalar keys keeps these)
             "ms_per_step_p10": round(float(np.percentile(per_step, 10)), 3), "ms_per_step_p50": round(float(np.percentile(per_step, 50)), 3),
             "ms_per_step_p90": round(float(np.percentile(per_step, 90)), 3),
-            "final_loss": round(float(loss.item()), 6), "host_enqueue_ms_per_step": round(host_ms, 3),
-            "roofline": roofline_leg(fixed, arena if world == 1 else None, fixed_ids(n_local, args.batch), 100),
+            "final_loss": round(float(loss.item()), 6),
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            line["host_enqueue_ms_per_step"] = round(host_ms, 3)
+            progress("roofline leg")
+            fixed = arena.batch(fixed_ids(n_local, args.batch))
+            line["roofline"] = roofline_leg(fixed, arena if world == 1 else None, fixed_ids(n_local, args.batch), 100)
+        if args.full and world == 1 and not args.no_cpu_baseline:
             rep = local_ids[fixed_ids(n_local, args.batch)]
             progress("cpu_baseline leg")
             line["cpu_baseline"] = cpu_baseline_leg(corpus, rep, 100)
@@ -1519,7 +1545,7 @@ def main():
                 progress(f"{key} leg")
                 line[key] = leg(dev)
             progress("done")
-        emit(line)
+        emit(line, side_file=args.full)
     if distributed:
         torch.distributed.barrier()  # rank 0 is still in its roofline leg: leave together
         torch.distributed.destroy_process_group()

@@ -7,7 +7,7 @@ N=${1:-3}
 rm -f gpurun_out/pooled_grad_ab.txt
 for i in $(seq 1 $N); do
   for v in 0 1; do
-    MLQEM_POOLED_GRAD=$v timeout -k 10 300 python3 bench.py --steps 100 --no-cpu-baseline 2> /dev/null | tail -1 > /tmp/ab_line.json || exit 1
+    MLQEM_POOLED_GRAD=$v timeout -k 10 300 python3 bench.py --steps 100 --full --no-cpu-baseline 2> /dev/null | tail -1 > /tmp/ab_line.json || exit 1
     python3 - $v <<'PY' >> gpurun_out/pooled_grad_ab.txt
 import json, sys
 d = json.loads(open("/tmp/ab_line.json").read())

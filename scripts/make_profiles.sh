@@ -1,7 +1,7 @@
 #!/bin/bash
 # Regenerates the round's measurement artefacts on the GPU box (run through gpurun from the repo root):
-#   gpurun_out/bench_line.json, bench_full.json    one default `python bench.py` run: the headline line and every leg's record
-#   gpurun_out/bench_kernel_stats.csv              rocprofv3 --kernel-trace --stats of `bench.py --no-cpu-baseline`, SINGLE STREAM
+#   $OUT/bench_line.json, bench_full.json          one `python bench.py --full` run: the headline line and every leg's record
+#   $OUT/bench_kernel_stats.csv                    rocprofv3 --kernel-trace --stats of `bench.py --full --no-cpu-baseline`, SINGLE STREAM
 #                                                  (MLQEM_SINGLE_STREAM=1: kernels run one after the other, so a kernel's average
 #                                                  duration is its own) + the roofline leg's launches broken out of the trace
 #   gpurun_out/bench_kernel_stats_3streams.csv     the same command with the default three branch streams (kernels overlap:
@@ -14,7 +14,7 @@ OUT=$ROOT/gpurun_out
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 # the headline record (bench.py's one stdout line); the full record of every leg is written by bench.py to gpurun_out/bench_full.json
-timeout 900 python3 "$ROOT/bench.py" 2>/dev/null | grep '{"metric"' > "$OUT/bench_line.json"
+timeout 900 python3 "$ROOT/bench.py" --full 2>/dev/null | grep '{"metric"' > "$OUT/bench_line.json"
 # (the profiled --no-cpu-baseline runs below write their own, shorter, full records elsewhere)
 export MLQEM_BENCH_FULL_RECORD=gpurun_out/bench_full_profiled.json
 
@@ -39,7 +39,7 @@ tail = leg[-24:]   # the roofline leg runs last: 4 warm-up + 20 timed launches o
 same = [dur for _, dur, g in tail if g == tail[-1][2]]
 with open(out, "w") as fh:
     fh.write(f"# rocprofv3 --kernel-trace --stats summary (top 45 kernels by total time), {label}\n")
-    fh.write("# command: rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --no-cpu-baseline\n")
+    fh.write("# command: rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --no-cpu-baseline\n")
     fh.write("# bench line of the same (profiled) run: " + line + "\n")
     w = csv.writer(fh)
     for r in rows[:46]:
@@ -51,10 +51,10 @@ PY
 }
 
 export MLQEM_SINGLE_STREAM=1
-rm -rf /tmp/prof1 && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof1 -- python3 "$ROOT/bench.py" --no-cpu-baseline > /tmp/prof1.log 2>&1
+rm -rf /tmp/prof1 && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof1 -- python3 "$ROOT/bench.py" --full --no-cpu-baseline > /tmp/prof1.log 2>&1
 summarise /tmp/prof1 /tmp/prof1.log "$OUT/bench_kernel_stats.csv" "single stream (MLQEM_SINGLE_STREAM=1): per-kernel durations are the kernels' own"
 unset MLQEM_SINGLE_STREAM
-rm -rf /tmp/prof3 && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof3 -- python3 "$ROOT/bench.py" --no-cpu-baseline > /tmp/prof3.log 2>&1
+rm -rf /tmp/prof3 && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof3 -- python3 "$ROOT/bench.py" --full --no-cpu-baseline > /tmp/prof3.log 2>&1
 summarise /tmp/prof3 /tmp/prof3.log "$OUT/bench_kernel_stats_3streams.csv" "default three branch streams: kernels overlap, durations stretch each other (sum of kernel time > wall clock)"
 timeout 900 python3 "$ROOT/scripts/kernel_roofline.py" --out "$OUT/kernel_roofline.json" > "$OUT/kernel_roofline.txt" 2>&1
 echo "bench: $(cut -c1-160 "$OUT/bench_line.json")"

@@ -161,3 +161,44 @@ def test_headline_record_is_small_and_carries_the_contract_keys(capsys, tmp_path
     rec8 = bench.headline_record(multi)
     assert rec8["roofline"]["frac"] == 0.8451 and "alone" in rec8["roofline"]["basis"] and "cpu_baseline" not in rec8
     assert len(json.dumps(rec8)) < 8192
+
+
+def test_dump_outputs_writes_the_steps_arrays_as_float32(tmp_path):
+    """``--dump-outputs DIR``: the last timed step's loss, parameters and gradient as DIR/<name>.npy in float32."""
+    import types
+
+    import numpy as np
+    import torch
+
+    sys.path[:0] = [ROOT]
+    import bench
+
+    trainer = types.SimpleNamespace(flat_param=torch.arange(7, dtype=torch.float32), flat_grad=torch.full((7,), -0.5))
+    bench.dump_outputs(str(tmp_path / "out"), torch.tensor([1.25]), trainer)
+    got = {p.stem: np.load(p) for p in (tmp_path / "out").glob("*.npy")}
+    assert sorted(got) == ["grad", "loss", "params"]
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["loss"].tolist() == [1.25] and got["params"].tolist() == list(range(7)) and (got["grad"] == -0.5).all()
+
+
+def test_plain_run_emits_the_line_without_a_side_file(capsys, tmp_path, monkeypatch):
+    """A plain run (no ``--full``) prints the headline line and writes no full record beside it, nor points to one."""
+    import json
+
+    sys.path[:0] = [ROOT]
+    import bench
+
+    keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+            "dtype", "data", "config", "final_loss")
+    plain = {k: v for k, v in _canned_full_record().items() if k in keep}
+    monkeypatch.setattr(bench, "ROOT", str(tmp_path))
+    monkeypatch.delenv("MLQEM_BENCH_FULL_STDOUT", raising=False)
+    bench.emit(plain, side_file=False)
+    out = capsys.readouterr().out
+    assert out.count("\n") == 1
+    rec = json.loads(out)
+    assert "full_record" not in rec and "roofline" not in rec and "cpu_baseline" not in rec
+    assert {k: rec[k] for k in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype")} == \
+        {k: plain[k] for k in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype")}
+    assert not list(tmp_path.iterdir())
+

@@ -234,9 +234,11 @@ def test_fast_statement_path_equals_the_general_path(g1, lima_props, tmp_path):
     texts.append('OPENQASM 2.0;\nqreg verylongregister[4];\nsx verylongregister[3];\nx verylongregister[0];\nrz(0.5) verylongregister[1];\n')
     (tmp_path / "texts.json").write_text(json.dumps(texts))
     (tmp_path / "props.json").write_text(json.dumps(lima_props))
+    # the parent's sys.path and the script travel as files: on the command line they can exceed the kernel's limit on one argument
+    (tmp_path / "sys_path.json").write_text(json.dumps([p for p in sys.path if p]))
     script = (
         "import json, sys, numpy as np\n"
-        f"sys.path[:0] = {[p for p in sys.path if p]!r}\n"
+        f"sys.path[:0] = json.load(open({str(tmp_path / 'sys_path.json')!r}))\n"
         "from blackwater.data.native_encoder import NativeEncoder\n"
         f"texts = json.load(open({str(tmp_path / 'texts.json')!r}))\n"
         f"enc = NativeEncoder(json.load(open({str(tmp_path / 'props.json')!r})))\n"
@@ -248,11 +250,12 @@ def test_fast_statement_path_equals_the_general_path(g1, lima_props, tmp_path):
         "    except Exception as err:\n"
         "        out[f'err{k}'] = np.array(type(err).__name__ + ': ' + str(err))\n"
         "np.savez(sys.argv[1], **out)\n")
+    (tmp_path / "child.py").write_text(script)
     res = {}
     for mode in ("2", "1", "0"):
         path = tmp_path / f"out{mode}.npz"
         env = dict(os.environ, MLQEM_QASM_FAST=mode)
-        subprocess.run([sys.executable, "-c", script, str(path)], check=True, env=env, timeout=300)
+        subprocess.run([sys.executable, str(tmp_path / "child.py"), str(path)], check=True, env=env, timeout=300)
         res[mode] = dict(np.load(path))
     assert sorted(res["1"]) == sorted(res["0"]) == sorted(res["2"])
     assert any(k.startswith("err") for k in res["1"]) and any(k.startswith("x") for k in res["1"])

@@ -38,7 +38,7 @@ extern "C" {
 
 typedef void* mlqem_stream_t; /* hipStream_t */
 
-#define MLQEM_ABI_VERSION 42 /* bumped whenever a signature below changes; bindings compare it at load time */
+#define MLQEM_ABI_VERSION 43 /* bumped whenever a signature below changes; bindings compare it at load time */
 int mlqem_abi_version(void);
 const char* mlqem_error_string(int code);
 
@@ -544,8 +544,9 @@ int mlqem_pool_keep_ptr(const int32_t* graph_ptr, int64_t B, float ratio, int32_
  * max_graph_nodes: an upper bound on a graph's node count when the caller has one (0: none, N is used) -- it sizes the
  * index field of the sort key, and lets batches of large graphs (>= 1024 nodes on average) go through ONE device-wide radix
  * sort with the graph index in the key's top bits instead of a segmented sort that gives each graph to one workgroup.
- * slot (ABI 41; may be NULL): [N], mlqem_asap_slot_map's result for perm (slot[perm[p]] = p, -1 elsewhere) written by the same
- * launches -- every node is one of the sorted keys -- where the caller made it with a launch of its own. */
+ * slot (ABI 41; may be NULL): [N], slot[perm[p]] = p for the K kept centres, -1 elsewhere, written by the same launches (every
+ * node is one of the sorted keys).  ASAPooling's backward needs it (x_out = x'[perm] * fitness[perm], gnn.py:105-107,110-112)
+ * and the coarsening entry points below read it. */
 size_t mlqem_segment_topk_workspace_bytes(int64_t N, int64_t B);
 int mlqem_segment_topk(const float* fitness, const int32_t* graph_ptr, const int32_t* new_graph_ptr, int64_t N,
                        int64_t B, int64_t K, int64_t max_graph_nodes, int32_t* perm, int32_t* slot, void* workspace,
@@ -577,35 +578,7 @@ int mlqem_keys_to_edge_index(const uint64_t* keys, int64_t E, int64_t* edge_inde
 
 /* Coarsened connectivity of LARGE graphs (100-qubit circuits pool to thousands of clusters; their second pooling runs on
  * graphs with hub clusters of hundreds of neighbours, where the two-hop path above sorts ~50 candidate keys per distinct
- * edge).  One wave per cluster p builds the row's reach as bitsets in LDS -- nodes v in N+[N-[c_p]], then clusters
- * q = slot[w], w in N+[v] -- and the transposed row the same way from N-[N-[c_p]], so duplicates collapse without a sort or a
- * global atomic and rows come out in ascending order; both are kept as bit matrices [K][ceil(kmax / 32)] in the workspace.  Two calls, ONE host read between them:
- *   rows_count: slot[N], new_in_ptr[K + 1], new_out_ptr[K + 1]; the caller reads new_out_ptr[K] (the edge total E);
- *   rows_fill:  new_in_src[E], new_out_dst[E], new_out_eid[E] -- the arrays mlqem_csr_build yields from the two-hop path's
- *               edge list -- from the SAME workspace, untouched in between.
- * nmax / kmax: largest graph / largest pooled graph of the batch; nmax + 2 kmax + 96 <= mlqem_asap_coarsen_rows_max_bits()
- * (131 072: 64 KB of LDS for the four waves of a workgroup), else MLQEM_ERR_UNSUPPORTED.  Replaces the same
- * ASAPooling.forward lines as the entry points above (gnn.py:105-107,110-112). */
-size_t mlqem_asap_coarsen_rows_workspace_bytes(int64_t K, int kmax);
-
-/* slot[N] alone: slot[perm[p]] = p for the K kept centres, -1 elsewhere (every coarsening entry point writes it too).
- * ASAPooling's backward needs it (x_out = x'[perm] * fitness[perm], gnn.py:105-107,110-112) even when nobody reads the
- * coarsened connectivity -- the second pooling of every reference model is followed by global_mean_pool (gnn.py:112-114)
- * -- so the host can skip the coarsening and call only this. */
-int mlqem_asap_slot_map(const int32_t* perm, int64_t N, int64_t K, int32_t* slot, mlqem_stream_t stream);
-/* The same in ONE launch given the graphs' node ranges before / after pooling (ABI 40; graph g's centres are its own nodes). */
-int mlqem_asap_slot_map_graphs(const int32_t* perm, const int32_t* graph_ptr, const int32_t* new_graph_ptr, int64_t B, int64_t N,
-                               int64_t K, int32_t* slot, mlqem_stream_t stream);
-int mlqem_asap_coarsen_rows_max_bits(void);
-int mlqem_asap_coarsen_rows_count(const int32_t* in_ptr, const int32_t* in_src, const int32_t* out_ptr, const int32_t* out_dst,
-                                  const int32_t* graph_ptr, const int32_t* new_graph_ptr, const int32_t* perm, int64_t N,
-                                  int64_t K, int64_t B, int nmax, int kmax, int32_t* slot, int32_t* new_in_ptr,
-                                  int32_t* new_out_ptr, void* workspace, size_t workspace_bytes, mlqem_stream_t stream);
-int mlqem_asap_coarsen_rows_fill(const int32_t* new_graph_ptr, int64_t K, int64_t B, int kmax, const int32_t* new_in_ptr,
-                                 const int32_t* new_out_ptr, int32_t* new_in_src, int32_t* new_out_dst, int32_t* new_out_eid,
-                                 const void* workspace, size_t workspace_bytes, mlqem_stream_t stream);
-
-/* The same arrays from SORTED LISTS instead of bit matrices (round 4; the default for large graphs): nothing dense is written
+ * edge), from SORTED LISTS (round 4; the default for large graphs): nothing dense is written
  * to or read from global memory, and the three hops of a cluster's reach are split into per-NODE lists built once --
  * C(v): the kept centres among N+[v]; R(u) / R'(u): the C lists of N+[u] / N-[u] one after the other -- so that a hub's list
  * (a barrier: ~300 entries) is formed once and read, coalesced, by every cluster that contains the hub.  Persistent waves OR a
@@ -616,14 +589,14 @@ int mlqem_asap_coarsen_rows_fill(const int32_t* new_graph_ptr, int64_t K, int64_
  *   lists_caps:  totals[4] (device int64) = the totals of the row bounds (out, in) and of the per-node list sizes (out, in):
  *                `capacity` must cover all four when the caller has no structural bound of its own (one 32-byte read);
  *                workspace of mlqem_asap_coarsen_lists_workspace_bytes(N, K, 0, 0);
- *   lists_count: slot[N], new_in_ptr[K + 1], new_out_ptr[K + 1]; E = stored edges of the input structure (or a bound);
+ *   lists_count: new_in_ptr[K + 1], new_out_ptr[K + 1]; E = stored edges of the input structure (or a bound); slot[N] must
+ *                hold slot[perm[p]] = p, -1 elsewhere (mlqem_segment_topk writes it);
  *   lists_fill:  new_in_src / new_out_dst / new_out_eid, each holding edge_capacity entries (new_out_ptr[K] <= edge_capacity
  *                <= capacity), from the SAME workspace; new_out_eid may be NULL (no link pass: the recomputed backward forms
  *                need no out_eid); *overflow (device, may be NULL) = 1 if `capacity` was too small.
  * capacity < 2^32 (places inside the per-node records are 32 bits), else MLQEM_ERR_UNSUPPORTED.
  * kmax <= mlqem_asap_coarsen_lists_max_k() (65 535 clusters per pooled graph), else MLQEM_ERR_UNSUPPORTED.
- * ABI 41: slot_ready != 0: slot[] already holds mlqem_asap_slot_map's result (the caller made it for the backward: no fill, no map
- * launch here); new_loops (may be NULL): [K], zeroed (the coarsened graph lists no self-loops).
+ * new_loops (may be NULL): [K], zeroed (the coarsened graph lists no self-loops).
  * Replaces the same ASAPooling.forward lines (gnn.py:105-107,110-112; PyG semantics: SURVEY appendix B.2 step 7). */
 size_t mlqem_asap_coarsen_lists_workspace_bytes(int64_t N, int64_t K, int64_t E, int64_t capacity);
 int mlqem_asap_coarsen_lists_max_k(void);
@@ -632,7 +605,7 @@ int mlqem_asap_coarsen_lists_caps(const int32_t* in_ptr, const int32_t* in_src, 
                                   int64_t* totals, void* workspace, size_t workspace_bytes, mlqem_stream_t stream);
 int mlqem_asap_coarsen_lists_count(const int32_t* in_ptr, const int32_t* in_src, const int32_t* out_ptr, const int32_t* out_dst,
                                    const int32_t* graph_ptr, const int32_t* new_graph_ptr, const int32_t* perm, int64_t N,
-                                   int64_t K, int64_t B, int64_t E, int kmax, int64_t capacity, int32_t* slot, int slot_ready,
+                                   int64_t K, int64_t B, int64_t E, int kmax, int64_t capacity, const int32_t* slot,
                                    int32_t* new_in_ptr, int32_t* new_out_ptr, int32_t* new_loops, void* workspace, size_t workspace_bytes,
                                    mlqem_stream_t stream);
 int mlqem_asap_coarsen_lists_fill(int64_t N, int64_t K, int64_t E, int64_t capacity, const int32_t* new_in_ptr,
@@ -648,13 +621,13 @@ int mlqem_asap_coarsen_lists_fill(int64_t N, int64_t K, int64_t E, int64_t capac
  * ranges of the graphs before / after pooling; perm: the kept centres, graph by graph (mlqem_segment_topk); kmax >= the
  * largest k_g (host knows it: k_g = ceil(ratio * n_g); a bound will do).  new_in_src / new_out_dst / new_out_eid must hold
  * sum_g k_g (k_g - 1) entries; only the first new_in_ptr[K] are written.  new_loops[K] = 0 (no diagonal).
- * slot_ready (ABI 40): `slot` already holds mlqem_asap_slot_map(perm) -- the call then makes three launches (bit matrices, one
- * scan of both degree vectors, the fill) where ABI <= 39 made eleven. */
+ * slot: [N], slot[perm[p]] = p, -1 elsewhere (mlqem_segment_topk writes it).  Three launches: bit matrices, one scan of both
+ * degree vectors, the fill. */
 int mlqem_asap_coarsen_dense_max_k(void);
 size_t mlqem_asap_coarsen_dense_workspace_bytes(int64_t B, int64_t K, int kmax);
 int mlqem_asap_coarsen_dense(const int32_t* in_ptr, const int32_t* in_src, const int32_t* out_ptr, const int32_t* out_dst,
                              const int32_t* graph_ptr, const int32_t* new_graph_ptr, const int32_t* perm, int64_t N, int64_t K,
-                             int64_t B, int kmax, int32_t* slot, int slot_ready, int32_t* new_in_ptr, int32_t* new_in_src,
+                             int64_t B, int kmax, const int32_t* slot, int32_t* new_in_ptr, int32_t* new_in_src,
                              int32_t* new_out_ptr, int32_t* new_out_dst, int32_t* new_out_eid, int32_t* new_loops,
                              void* workspace, size_t workspace_bytes, mlqem_stream_t stream);
 
@@ -773,7 +746,7 @@ int mlqem_leconv_fitness_bwd_f32(const float* gfit, const float* fitness, const 
  * removed with ABI 39.)
  * ---------------------------------------------------------------------------------------------------- */
 /* order[new_graph_ptr[g] + r] = the cluster of graph g whose centre is the r-th kept node of the graph in node order
- * (= program order of a circuit); slot[] from mlqem_asap_slot_map.  One workgroup per graph. */
+ * (= program order of a circuit); slot[perm[p]] = p for the kept centres, -1 elsewhere.  One workgroup per graph. */
 int mlqem_tile_order_by_position(const int32_t* slot, const int32_t* graph_ptr, const int32_t* new_graph_ptr, int64_t num_graphs,
                                  int32_t* order, mlqem_stream_t stream);
 
@@ -834,24 +807,24 @@ int mlqem_dense_plan_build(const int32_t* ptr, const int32_t* idx, const int32_t
 /* 1 when the dense kernels serve this shape: one or two heads of at most 16 channels at a head pitch of 16 */
 int mlqem_dense_attention_supported(int H, int C, int head_pitch);
 /* mlqem_transformer_attention_train_f32 (pair-keyed dropout draws, no side table) with the rows of the plan's blocks on the matrix
- * cores: same arguments, outputs and statistics.  `parts` selects the launches of this call -- 1: the per-edge kernel over the rows
- * outside the blocks, 2: the block kernel (3: both) -- so that a caller may put the two, which touch disjoint rows, on two streams. */
+ * cores: same arguments, outputs and statistics.  Two launches: the per-edge kernel over the rows outside the blocks, then the block
+ * kernel. */
 int mlqem_dense_attention_train_f32(const float* qkvs, int64_t ld, const int32_t* in_ptr, const int32_t* in_src,
                                     const int32_t* loops, int64_t N, int64_t E, int H, int C, float drop_p, uint64_t seed,
                                     const uint64_t* seed_counter, int head_pitch, const int32_t* records, const int32_t* counter,
-                                    const uint8_t* row_flag, int64_t max_blocks, int parts, float* out, int64_t ldo,
+                                    const uint8_t* row_flag, int64_t max_blocks, float* out, int64_t ldo,
                                     float* attn_out, int64_t lda, float* stat_m, float* stat_den, mlqem_stream_t stream);
 /* mlqem_transformer_attention_bwd_f32 in its recomputing form (no out_eid, no per-edge buffers; edge_al: [4 N H] floats, 16-byte
- * aligned) with a plan of the in-CSR for the destination side and one of the out-CSR for the source side.  `parts`: 1 / 2 =
- * destination side per-edge rows / blocks, 4 / 8 = source side per-edge rows / blocks (15: all four, in that order).  The source
- * side reads what BOTH destination-side launches file in edge_al. */
+ * aligned) with a plan of the in-CSR for the destination side and one of the out-CSR for the source side.  Four launches, in this
+ * order: destination side per-edge rows, destination side blocks, source side per-edge rows, source side blocks.  The source side
+ * reads what BOTH destination-side launches file in edge_al. */
 int mlqem_dense_attention_bwd_f32(const float* qkvs, int64_t ld, const float* g, int64_t ldg, const float* attn_out, int64_t lda,
                                   const float* stat_m, const float* stat_den, const int32_t* in_ptr, const int32_t* in_src,
                                   const int32_t* out_ptr, const int32_t* out_dst, const int32_t* loops, int64_t N, int64_t E, int H,
                                   int C, float drop_p, uint64_t seed, const uint64_t* seed_counter, int head_pitch,
                                   const int32_t* in_records, const int32_t* in_counter, const uint8_t* in_flag, int64_t in_max_blocks,
                                   const int32_t* out_records, const int32_t* out_counter, const uint8_t* out_flag,
-                                  int64_t out_max_blocks, int parts, float* gqkvs, int64_t ldq, float* edge_al,
+                                  int64_t out_max_blocks, float* gqkvs, int64_t ldq, float* edge_al,
                                   mlqem_stream_t stream);
 
 /* ASAPooling's cluster sums over the same plans (csrc/dense_pool.hip; rows of at most 48 channels: mlqem_dense_pool_supported -- two or

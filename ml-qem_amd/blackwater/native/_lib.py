@@ -119,24 +119,18 @@ SIGNATURES = {
     "mlqem_sort_unique_u64_workspace_bytes": (_S, [_L]),
     "mlqem_sort_unique_u64": (_I, [_P, _L, _P, _P, _P, _S, _P]),
     "mlqem_keys_to_edge_index": (_I, [_P, _L, _P, _P]),
-    "mlqem_asap_coarsen_rows_workspace_bytes": (_S, [_L, _I]),
-    "mlqem_asap_coarsen_rows_max_bits": (_I, []),
-    "mlqem_asap_slot_map": (_I, [_P, _L, _L, _P, _P]),
     "mlqem_batch_norm_workspace_bytes": (_S, [_L, _I]),
     "mlqem_batch_norm_train_f32": (_I, [_P, _L, _L, _I, _P, _P, _F, _P, _L, _P, _P, _P, _P, _S, _P]),
     "mlqem_batch_norm_train_bwd_f32": (_I, [_P, _L, _P, _L, _L, _I, _P, _P, _P, _P, _L, _P, _P, _P, _S, _P]),
-    "mlqem_asap_coarsen_rows_count": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _I, _I, _P, _P, _P, _P, _S, _P]),
-    "mlqem_asap_coarsen_rows_fill": (_I, [_P, _L, _L, _I, _P, _P, _P, _P, _P, _P, _S, _P]),
     "mlqem_asap_coarsen_lists_workspace_bytes": (_S, [_L, _L, _L, _L]),
     "mlqem_asap_coarsen_lists_max_k": (_I, []),
     "mlqem_asap_coarsen_lists_caps": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _L, _P, _P, _S, _P]),
-    "mlqem_asap_coarsen_lists_count": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _L, _I, _L, _P, _I, _P, _P, _P, _P, _S, _P]),
+    "mlqem_asap_coarsen_lists_count": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _L, _I, _L, _P, _P, _P, _P, _P, _S, _P]),
     "mlqem_asap_coarsen_lists_fill": (_I, [_L, _L, _L, _L, _P, _P, _P, _P, _P, _L, _P, _P, _S, _P]),
     "mlqem_asap_coarsen_dense_max_k": (_I, []),
     "mlqem_asap_coarsen_dense_workspace_bytes": (_S, [_L, _L, _I]),
-    "mlqem_asap_coarsen_dense": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _S, _P]),
+    "mlqem_asap_coarsen_dense": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _S, _P]),
     "mlqem_gather_rows_f32": (_I, [_I, _P, _P, _P, _L, _P, _P]),
-    "mlqem_asap_slot_map_graphs": (_I, [_P, _P, _P, _L, _L, _L, _P, _P]),
     "mlqem_pad_head_rows_parts_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "mlqem_transformer_attention_train_f32": (_I, [_P, _L, _P, _P, _P, _L, _L, _I, _I, _F, _U, _P, _I, _P, _I, _P, _L, _P, _L, _P, _P, _P]),
     "mlqem_transformer_attention_bwd_f32": (_I, [_P, _L, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _I,
@@ -152,10 +146,10 @@ SIGNATURES = {
     "mlqem_dense_plan_max_blocks": (_L, [_L, _L]),
     "mlqem_dense_plan_build": (_I, [_P, _P, _P, _P, _P, _L, _L, _L, _P, _P, _P, _P, _P]),
     "mlqem_dense_attention_supported": (_I, [_I, _I, _I]),
-    "mlqem_dense_attention_train_f32": (_I, [_P, _L, _P, _P, _P, _L, _L, _I, _I, _F, _U, _P, _I, _P, _P, _P, _L, _I, _P, _L, _P, _L, _P,
+    "mlqem_dense_attention_train_f32": (_I, [_P, _L, _P, _P, _P, _L, _L, _I, _I, _F, _U, _P, _I, _P, _P, _P, _L, _P, _L, _P, _L, _P,
                                              _P, _P]),
     "mlqem_dense_attention_bwd_f32": (_I, [_P, _L, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _F, _U, _P, _I,
-                                           _P, _P, _P, _L, _P, _P, _P, _L, _I, _P, _L, _P, _P]),
+                                           _P, _P, _P, _L, _P, _P, _P, _L, _P, _L, _P, _P]),
     "mlqem_dense_pool_supported": (_I, [_I]),
     "mlqem_dense_softmax_aggregate_f32": (_I, [_P, _L, _P, _P, _P, _P, _F, _L, _I, _P, _P, _P, _L, _P, _L, _P, _P]),
     "mlqem_dense_leconv_fitness_bwd_f32": (_I, [_P, _P, _P, _P, _P, _L, _P, _P, _P, _L, _P, _P]),
@@ -188,7 +182,7 @@ SIGNATURES = {
 _lib = None
 ERR_UNSUPPORTED = -2   # MLQEM_ERR_UNSUPPORTED: a shape this kernel does not serve
 ERR_WORKSPACE = -4   # MLQEM_ERR_WORKSPACE: a caller-provided buffer is too small (the encoder then says what it needs)
-ABI_VERSION = 42   # MLQEM_ABI_VERSION of include/mlqem_hip.h; bumped whenever a signature changes
+ABI_VERSION = 43   # MLQEM_ABI_VERSION of include/mlqem_hip.h; bumped whenever a signature changes
 
 
 def load() -> ctypes.CDLL:

@@ -700,8 +700,7 @@ class _TransformerConv(Function):
         ell = struct.in_ell if struct.out_eid is not None else None
         if dense:
             out, attn, m, den = ops.dense_attention_train(qkvs, struct.in_ptr, struct.in_src, struct.loops, e, heads, channels,
-                                                         struct.dense_plan("in"), drop_p=drop_p, seed=seed, head_pitch=cp,
-                                                         side=_dense_side(w_used.device))
+                                                         struct.dense_plan("in"), drop_p=drop_p, seed=seed, head_pitch=cp)
         else:
             out, attn, m, den = ops.transformer_attention_train(qkvs, struct.in_ptr, struct.in_src, struct.loops, e, heads,
                                                                channels, drop_p, seed, pair_key=pair_key, ell=ell, head_pitch=cp)
@@ -725,7 +724,7 @@ class _TransformerConv(Function):
         if ctx.dense:
             st = ctx.struct
             gqkvs = ops.dense_attention_bwd(qkvs, g, attn, m, den, st, e, heads, channels, st.dense_plan("in"), st.dense_plan("out"),
-                                            drop_p=drop_p, seed=seed, head_pitch=cp, side=_dense_side(w.device))
+                                            drop_p=drop_p, seed=seed, head_pitch=cp)
         else:
             gqkvs = ops.transformer_attention_bwd(qkvs, g, attn, m, den, ctx.struct, e, heads, channels, drop_p, seed, pair_key=pair_key,
                                                   head_pitch=cp)
@@ -763,15 +762,6 @@ def _pad_heads(w, b, groups, channels, cp):
 # the long rows of ASAPooling's coarsened graphs as dense blocks: TransformerConv's edge softmax over them on the f32 matrix cores
 # (csrc/dense_block.hip); MLQEM_DENSE_BLOCKS=0: the per-edge kernels for every row (A/B runs, tests/test_gpu_dense_blocks.py)
 _DENSE_BLOCKS = os.environ.get("MLQEM_DENSE_BLOCKS", "1") == "1"
-# True: the per-edge kernel over the rows outside the blocks on a side stream, beside the block kernel (disjoint rows).  Measured on
-# 64 100-qubit circuits: slower -- eagerly 117.7 us against 109.4 on one stream (forward), 305.5 against 290.7 (backward); inside the
-# captured step 7.12 ms against 7.00 (scripts/family_b_step.py): the per-edge kernel's 11 k workgroups fill the chip either way, the
-# fork and the join cost more than the overlap returns.  Kept as a switch of the ops (tests/test_gpu_dense_blocks.py runs both).
-_DENSE_TWO_STREAMS = False
-
-
-def _dense_side(device):
-    return _branch_streams(device)[0] if _DENSE_TWO_STREAMS else None
 # channel pitch of a head inside q / k / v / skip in training (0: compact heads, the layout of rounds 1-3; the parity test of the two
 # layouts sets it)
 _ATTN_PITCH = 16
@@ -786,13 +776,12 @@ def transformer_conv(x, w, b, struct, heads, channels, drop_p=0.0, seed=0):
 
 
 # Which form of the coarsening S^T (A S) a pooling takes, by the batch's graph sizes: the sync-free dense form when every graph pools to
-# <= 512 clusters, the sorted-list form for larger graphs, the wave-per-cluster bit-matrix form when the lists would not fit 32-bit
-# places, the general two-hop path (four device->host size reads) otherwise.  All forms yield identical arrays; these module
+# <= 512 clusters, the sorted-list form for larger graphs, the general two-hop path (four device->host size reads) when the lists
+# would not fit 32-bit places or a pooled graph has more than 65 535 clusters.  All forms yield identical arrays; these module
 # attributes exist so that the tests can force one form and compare it with another (tests/test_gpu_family_b.py).
 _ASAP_DENSE = True
 # ASAPooling's forward on a graph of short rows as one fused pass (tests/test_gpu_family_b.py flips it: both forms, same results)
 _ASAP_FUSED = True
-_ASAP_ROWS = True
 _ASAP_LISTS = True
 # True: the list coarsening also links every out-entry to its in-CSR twin (out_eid; 0.55 ms for 64 100-qubit circuits) and the
 # backward kernels on the coarsened graph take the stored form; default: no out_eid, recomputed form
@@ -886,8 +875,7 @@ class _ASAPool(Function):
             # largest graph before / after pooling is known by a bound -- nothing here depends on the size SEQUENCE of the batch
             k_total, nmax, kmax = (int(v) for v in plan[0])
             new_ptr = ops.pool_keep_ptr(s.graph_ptr, s.num_graphs, ratio)
-            keep = {"b": s.num_graphs, "k": k_total, "kmax": kmax, "nmax": nmax}
-            sizes = None
+            keep = {"b": s.num_graphs, "k": k_total, "kmax": kmax}
             have = s.num_graphs > 0
         else:
             # k_g = ceil(ratio * n_g) evaluated in float32 like PyG's topk (float32 tensor times a python scalar)
@@ -902,29 +890,25 @@ class _ASAPool(Function):
         # ... with the backward's slot[] (cluster id of every kept centre, -1 elsewhere; the coarsenings read the same map) from the same launches
         perm, slot_fwd = ops.segment_topk(fitness, s.graph_ptr, new_ptr, n, s.num_graphs, k_total, max_graph_nodes=min(nmax, n), with_slot=True)
         x_out = ops.gather_scale_rows(x_new, perm, fitness)
-        use_dense, use_rows, use_lists, link = _ASAP_DENSE, _ASAP_ROWS, _ASAP_LISTS, _ASAP_LINK   # the switches as they stand now: build() may run later
+        use_dense, use_lists, link = _ASAP_DENSE, _ASAP_LISTS, _ASAP_LINK   # the switches as they stand now: build() may run later
 
         def build():
             dense_ok = use_dense and have and kmax <= ops.asap_dense_max_k()
             if dense_ok:
                 # small graphs: the pooled adjacency as per-graph bit matrices in LDS -- no device->host copy anywhere
                 csr, slot, cap = ops.asap_coarsen_dense(s.in_ptr, s.in_src, s.out_ptr, s.out_dst, s.graph_ptr, new_ptr, perm, n, keep,
-                                                        slot=slot_fwd)
+                                                        slot_fwd)
                 num_edges = cap     # an upper bound: the true count stays on the device (in_ptr[k_total])
             done = None
-            if not dense_ok and use_rows and use_lists and have and kmax <= ops.asap_lists_max_k():
+            if not dense_ok and use_lists and have and kmax <= ops.asap_lists_max_k():
                 # large graphs: per-node cluster lists, a thread per cluster gathers its candidates, persistent waves sort them through
                 # LDS bitsets; no host read when the structure carries a capacity.  None: too many candidates for this form
                 done = ops.asap_coarsen_lists(s.in_ptr, s.in_src, s.out_ptr, s.out_dst, s.graph_ptr, new_ptr, perm, n, s.edge_count(), keep,
-                                              capacity=getattr(s, "coarse_capacity", None), link=link, slot=slot_fwd)
+                                              slot_fwd, capacity=getattr(s, "coarse_capacity", None), link=link)
             if dense_ok:
                 pass
             elif done is not None:
                 csr, slot, num_edges = done
-            elif (use_rows and have and nmax + 2 * kmax + 96 <= ops.asap_rows_max_bits()):
-                # large graphs: one wave per cluster, bitsets in LDS, no sort; one 4-byte read (the edge total)
-                csr, slot, num_edges = ops.asap_coarsen_rows(s.in_ptr, s.in_src, s.out_ptr, s.out_dst, s.graph_ptr, new_ptr, perm,
-                                                             n, sizes, keep, capacity=getattr(s, "coarse_capacity", None))
             else:
                 ei, slot = ops.asap_coarsen(s.in_ptr, s.in_src, s.out_ptr, s.out_dst, perm, n, return_slot=True)
                 csr = ops.csr_build(ei, k_total)
@@ -938,7 +922,7 @@ class _ASAPool(Function):
         if plan:
             holder["structure"].pool_plan = plan[1:]             # the next pooling's level
             holder["structure"].num_real = s.num_real
-        if (_DENSE_BLOCKS and use_rows and use_lists and not link and have and ops.asap_dense_max_k() < kmax):
+        if (_DENSE_BLOCKS and use_lists and not link and have and ops.asap_dense_max_k() < kmax):
             # large graphs (the list coarsening's): clusters whose centres are close in program order share their neighbours, so
             # the layers that read this graph take its long rows 16 at a time in the order of their centres' node index
             def block_order(slot=slot, gptr=s.graph_ptr, b=s.num_graphs):

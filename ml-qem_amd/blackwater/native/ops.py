@@ -1401,7 +1401,7 @@ def pool_keep_ptr(graph_ptr, num_graphs, ratio):
 
 
 def segment_topk(fitness, graph_ptr, new_graph_ptr, num_nodes, num_graphs, k_total, max_graph_nodes=0, with_slot=False):
-    """perm [k_total] -- and, ``with_slot``, (perm, slot) with ``asap_slot_map``'s slot[N] from the same launches."""
+    """perm [k_total] -- and, ``with_slot``, (perm, slot) with slot[N] from the same launches: slot[perm[p]] = p, -1 elsewhere."""
     _vec(fitness, "fitness", num_nodes)
     _vec(graph_ptr, "graph_ptr", num_graphs + 1, torch.int32)
     _vec(new_graph_ptr, "new_graph_ptr", num_graphs + 1, torch.int32)
@@ -1490,79 +1490,40 @@ def _keep_info(keep_sizes):
     return b, k, (int(keep.max()) if b else 0), int((keep * (keep - 1)).sum())
 
 
-def asap_coarsen_dense(s_in_ptr, s_in_src, s_out_ptr, s_out_dst, graph_ptr, new_graph_ptr, perm, num_nodes, keep_sizes, slot=None):
+def asap_coarsen_dense(s_in_ptr, s_in_src, s_out_ptr, s_out_dst, graph_ptr, new_graph_ptr, perm, num_nodes, keep_sizes, slot):
     """Pooled structure arrays (in_ptr, in_src, out_ptr, out_dst, out_eid, loops, slot) and the capacity of the edge
     arrays, with NO device->host copy (mlqem_asap_coarsen_dense).  ``keep_sizes``: host array of k_g per graph (or bounds:
-    ``_keep_info``).  ``slot``: ``asap_slot_map(perm, num_nodes)`` when the caller has it already (two launches less)."""
+    ``_keep_info``).  ``slot``: [N], slot[perm[p]] = p, -1 elsewhere (``segment_topk(..., with_slot=True)``)."""
     b, k, kmax, cap = _keep_info(keep_sizes)
     dev = perm.device
     lib = _lib.load()
     mk = lambda n: torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-    ready = slot is not None
-    if ready:
-        _vec(slot, "slot", num_nodes, torch.int32)
+    _vec(slot, "slot", num_nodes, torch.int32)
     in_ptr, out_ptr, loops = mk(k + 1), mk(k + 1), mk(k)
-    slot = slot if ready else mk(num_nodes)
     in_src, out_dst, out_eid = mk(cap), mk(cap), mk(cap)
     need = lib.mlqem_asap_coarsen_dense_workspace_bytes(b, k, kmax)
     ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
     code = lib.mlqem_asap_coarsen_dense(_p(s_in_ptr), _p(s_in_src), _p(s_out_ptr), _p(s_out_dst), _p(graph_ptr), _p(new_graph_ptr),
-                                        _p(perm), num_nodes, k, b, kmax, _p(slot), 1 if ready else 0, _p(in_ptr), _p(in_src), _p(out_ptr),
+                                        _p(perm), num_nodes, k, b, kmax, _p(slot), _p(in_ptr), _p(in_src), _p(out_ptr),
                                         _p(out_dst), _p(out_eid), _p(loops), _p(ws), need, _stream())
     _lib.check(code, "mlqem_asap_coarsen_dense")
     return CsrArrays(in_ptr, in_src, out_ptr, out_dst, loops, out_eid), slot, cap
 
 
-def asap_coarsen_rows(s_in_ptr, s_in_src, s_out_ptr, s_out_dst, graph_ptr, new_graph_ptr, perm, num_nodes, graph_sizes, keep_sizes,
-                      capacity=None):
-    """The same pooled structure arrays for LARGE graphs (mlqem_asap_coarsen_rows_count / _fill: one wave per cluster, bitsets
-    in LDS, no sort): ONE 4-byte device->host read (the edge total) instead of the two-hop path's four reads and two
-    64-bit sorts -- and NONE when the caller knows an upper bound ``capacity`` on the edge total (GraphArena.coarse_capacity):
-    the edge arrays are then sized to it and the true total stays on the device (in_ptr[k]).  Returns (CsrArrays, slot,
-    number of edges or the capacity)."""
-    import numpy as np
-
-    b, k, kmax, _ = _keep_info(keep_sizes)
-    nmax = (int(keep_sizes["nmax"]) if isinstance(keep_sizes, dict) else int(np.asarray(graph_sizes).max())) if b else 0
-    dev = perm.device
-    lib = _lib.load()
-    mk = lambda n: torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-    slot, in_ptr, out_ptr = mk(num_nodes), mk(k + 1), mk(k + 1)
-    need = lib.mlqem_asap_coarsen_rows_workspace_bytes(k, kmax)
-    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-    code = lib.mlqem_asap_coarsen_rows_count(_p(s_in_ptr), _p(s_in_src), _p(s_out_ptr), _p(s_out_dst), _p(graph_ptr),
-                                             _p(new_graph_ptr), _p(perm), num_nodes, k, b, nmax, kmax, _p(slot), _p(in_ptr),
-                                             _p(out_ptr), _p(ws), need, _stream())
-    _lib.check(code, "mlqem_asap_coarsen_rows_count")
-    if capacity is None:
-        e = int(out_ptr[k].item()) if k > 0 else 0
-    else:
-        e = int(capacity) if k > 0 else 0
-    in_src, out_dst, out_eid = mk(e), mk(e), mk(e)
-    loops = torch.full((max(k, 1),), 0, dtype=torch.int32, device=dev)      # a fill kernel, not a memset node (the call may be captured)
-    if e > 0:
-        code = lib.mlqem_asap_coarsen_rows_fill(_p(new_graph_ptr), k, b, kmax, _p(in_ptr), _p(out_ptr), _p(in_src), _p(out_dst),
-                                                _p(out_eid), _p(ws), need, _stream())
-        _lib.check(code, "mlqem_asap_coarsen_rows_fill")
-    return CsrArrays(in_ptr, in_src[:e], out_ptr, out_dst[:e], loops[:k], out_eid[:e]), slot, e
-
-
-def asap_coarsen_lists(s_in_ptr, s_in_src, s_out_ptr, s_out_dst, graph_ptr, new_graph_ptr, perm, num_nodes, num_edges, keep_sizes,
-                       capacity=None, link=True, slot=None):
-    """The pooled structure arrays of ``asap_coarsen_rows`` from SORTED LISTS (mlqem_asap_coarsen_lists_*, round 4): per-node
+def asap_coarsen_lists(s_in_ptr, s_in_src, s_out_ptr, s_out_dst, graph_ptr, new_graph_ptr, perm, num_nodes, num_edges, keep_sizes, slot,
+                       capacity=None, link=True):
+    """The pooled structure arrays of ``asap_coarsen_dense`` for LARGE graphs, from SORTED LISTS (mlqem_asap_coarsen_lists_*): per-node
     cluster lists built once, one walk per cluster by persistent waves, nothing dense in global memory, the twin links by binary
     search.  ``num_edges``: stored edges of the input structure (or a bound).  ``capacity``: a bound on the four list totals and on
     the edge total (GraphArena.coarse_capacity); without it the totals are read back (one 32-byte device->host copy, then the
     4-byte edge total).  Returns (CsrArrays, slot, edge capacity), or None when the candidate lists would exceed
-    ``ASAP_LISTS_MAX_CAPACITY`` entries (the caller then takes another form).  ``slot``: ``asap_slot_map``'s result when the caller has
-    it (ASAPooling's autograd node makes it for its backward)."""
+    ``ASAP_LISTS_MAX_CAPACITY`` entries (the caller then takes the two-hop path).  ``slot``: [N], slot[perm[p]] = p, -1 elsewhere
+    (``segment_topk(..., with_slot=True)``)."""
     b, k, kmax, _ = _keep_info(keep_sizes)
     dev = perm.device
     lib = _lib.load()
     mk = lambda n: torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-    slot_ready = slot is not None
-    if not slot_ready:
-        slot = mk(num_nodes)
+    _vec(slot, "slot", num_nodes, torch.int32)
     in_ptr, out_ptr = mk(k + 1), mk(k + 1)
     exact = capacity is None
     if exact:
@@ -1580,14 +1541,14 @@ def asap_coarsen_lists(s_in_ptr, s_in_src, s_out_ptr, s_out_dst, graph_ptr, new_
         cap = int(capacity) if k > 0 else 0
     if cap >= ASAP_LISTS_MAX_CAPACITY:
         # a graph whose clusters have thousands of candidates each (the coarsening of an already coarsened graph: rows of hundreds of
-        # entries, three hops deep): the candidate lists would not fit 32-bit places -- the caller takes the bit-matrix form
+        # entries, three hops deep): the candidate lists would not fit 32-bit places -- the caller takes the two-hop path
         return None
     e = cap
     need = lib.mlqem_asap_coarsen_lists_workspace_bytes(num_nodes, k, int(num_edges), cap)
     ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
     loops = mk(k)                           # zeroed by the count pass (a kernel, not a memset node: the call may be captured)
     code = lib.mlqem_asap_coarsen_lists_count(_p(s_in_ptr), _p(s_in_src), _p(s_out_ptr), _p(s_out_dst), _p(graph_ptr), _p(new_graph_ptr),
-                                              _p(perm), num_nodes, k, b, int(num_edges), kmax, cap, _p(slot), 1 if slot_ready else 0,
+                                              _p(perm), num_nodes, k, b, int(num_edges), kmax, cap, _p(slot),
                                               _p(in_ptr), _p(out_ptr), _p(loops), _p(ws), need, _stream())
     _lib.check(code, "mlqem_asap_coarsen_lists_count")
     if exact and k > 0:
@@ -1679,24 +1640,6 @@ def batch_norm_train_bwd(dy, x, gamma, mean, invstd):
                                               _p(dx), _mat(dx, "dx"), _p(dgamma), _p(dbeta), _p(ws), need, _stream())
     _lib.check(code, "mlqem_batch_norm_train_bwd_f32")
     return dx, dgamma, dbeta
-
-
-def asap_slot_map(perm, num_nodes, graph_ptr=None, new_graph_ptr=None, num_graphs=0):
-    """slot[N]: cluster id of every kept centre (slot[perm[p]] = p), -1 elsewhere.  With the graphs' node ranges before / after the
-    pooling: one launch (a workgroup per graph) instead of a fill and a scatter."""
-    k = int(perm.shape[0])
-    slot = torch.empty(max(num_nodes, 1), dtype=torch.int32, device=perm.device)
-    if graph_ptr is not None and new_graph_ptr is not None and num_graphs > 0:
-        code = _lib.load().mlqem_asap_slot_map_graphs(_p(perm), _p(graph_ptr), _p(new_graph_ptr), int(num_graphs), num_nodes, k, _p(slot), _stream())
-        _lib.check(code, "mlqem_asap_slot_map_graphs")
-        return slot
-    code = _lib.load().mlqem_asap_slot_map(_p(perm), num_nodes, k, _p(slot), _stream())
-    _lib.check(code, "mlqem_asap_slot_map")
-    return slot
-
-
-def asap_rows_max_bits() -> int:
-    return int(_lib.load().mlqem_asap_coarsen_rows_max_bits())
 
 
 def asap_dense_max_k() -> int:
@@ -1939,44 +1882,24 @@ def dense_attention_supported(heads, channels, head_pitch) -> bool:
     return bool(_lib.load().mlqem_dense_attention_supported(heads, channels, head_pitch or channels))
 
 
-def _two_streams(first, second, side):
-    """``first()`` on a side stream while ``second()`` runs on the caller's: two launches that touch disjoint rows.  Joined before
-    returning (the caller's stream then holds both)."""
-    if side is None:
-        first()
-        second()
-        return
-    main = torch.cuda.current_stream()
-    side.wait_stream(main)
-    with torch.cuda.stream(side):
-        first()
-    second()
-    main.wait_stream(side)
-
-
-def dense_attention_train(qkvs, in_ptr, in_src, loops, num_edges, heads, channels, plan: DensePlan, drop_p=0.0, seed=0, head_pitch=16,
-                          side=None):
-    """``transformer_attention_train`` (pair-keyed draws) with the plan's rows on the matrix cores: (out, attn_out, m, den).
-    ``side``: a stream for the per-edge kernel over the rows outside the blocks, which then runs beside the block kernel."""
+def dense_attention_train(qkvs, in_ptr, in_src, loops, num_edges, heads, channels, plan: DensePlan, drop_p=0.0, seed=0, head_pitch=16):
+    """``transformer_attention_train`` (pair-keyed draws) with the plan's rows on the matrix cores: (out, attn_out, m, den)."""
     n, hc = qkvs.shape[0], heads * channels
     dev = qkvs.device
     out, attn = padded_empty(n, hc, dev), padded_empty(n, hc, dev)
     m = torch.empty((max(n, 1), heads), dtype=torch.float32, device=dev)
     den = torch.empty_like(m)
 
-    def call(parts):
-        code = _lib.load().mlqem_dense_attention_train_f32(
-            _p(qkvs), _mat(qkvs, "qkvs"), _p(in_ptr), _p(in_src), _p(loops), n, num_edges, heads, channels, float(drop_p),
-            int(seed) & 0xFFFFFFFFFFFFFFFF, _p(_seed_counter) if drop_p > 0 else None, int(head_pitch), *plan.args(), parts,
-            _p(out), _mat(out, "out"), _p(attn), _mat(attn, "attn"), _p(m), _p(den), _stream())
-        _lib.check(code, "mlqem_dense_attention_train_f32")
-
-    _two_streams(lambda: call(1), lambda: call(2), side)
+    code = _lib.load().mlqem_dense_attention_train_f32(
+        _p(qkvs), _mat(qkvs, "qkvs"), _p(in_ptr), _p(in_src), _p(loops), n, num_edges, heads, channels, float(drop_p),
+        int(seed) & 0xFFFFFFFFFFFFFFFF, _p(_seed_counter) if drop_p > 0 else None, int(head_pitch), *plan.args(),
+        _p(out), _mat(out, "out"), _p(attn), _mat(attn, "attn"), _p(m), _p(den), _stream())
+    _lib.check(code, "mlqem_dense_attention_train_f32")
     return out, attn, m, den
 
 
 def dense_attention_bwd(qkvs, g, attn, m, den, s, num_edges, heads, channels, plan_in: DensePlan, plan_out: DensePlan, drop_p=0.0, seed=0,
-                        head_pitch=16, side=None):
+                        head_pitch=16):
     """``transformer_attention_bwd`` (recomputing form) with the plans' rows on the matrix cores: the gradient of qkvs."""
     n = qkvs.shape[0]
     g = rowmajor(g)
@@ -1984,17 +1907,12 @@ def dense_attention_bwd(qkvs, g, attn, m, den, s, num_edges, heads, channels, pl
     gqkvs = padded_empty(n, 4 * heads * head_pitch, dev)
     al = torch.empty(4 * max(n, 1) * heads, dtype=torch.float32, device=dev)
 
-    def call(parts):
-        code = _lib.load().mlqem_dense_attention_bwd_f32(
-            _p(qkvs), _mat(qkvs, "qkvs"), _p(g), _mat(g, "g"), _p(attn), _mat(attn, "attn"), _p(m), _p(den), _p(s.in_ptr), _p(s.in_src),
-            _p(s.out_ptr), _p(s.out_dst), _p(s.loops), n, num_edges, heads, channels, float(drop_p), int(seed) & 0xFFFFFFFFFFFFFFFF,
-            _p(_seed_counter) if drop_p > 0 else None, int(head_pitch), *plan_in.args(), *plan_out.args(), parts, _p(gqkvs),
-            _mat(gqkvs, "gqkvs"), _p(al), _stream())
-        _lib.check(code, "mlqem_dense_attention_bwd_f32")
-
-    # the source side reads the records BOTH destination-side launches file: joined in between
-    _two_streams(lambda: call(1), lambda: call(2), side)
-    _two_streams(lambda: call(4), lambda: call(8), side)
+    code = _lib.load().mlqem_dense_attention_bwd_f32(
+        _p(qkvs), _mat(qkvs, "qkvs"), _p(g), _mat(g, "g"), _p(attn), _mat(attn, "attn"), _p(m), _p(den), _p(s.in_ptr), _p(s.in_src),
+        _p(s.out_ptr), _p(s.out_dst), _p(s.loops), n, num_edges, heads, channels, float(drop_p), int(seed) & 0xFFFFFFFFFFFFFFFF,
+        _p(_seed_counter) if drop_p > 0 else None, int(head_pitch), *plan_in.args(), *plan_out.args(), _p(gqkvs),
+        _mat(gqkvs, "gqkvs"), _p(al), _stream())
+    _lib.check(code, "mlqem_dense_attention_bwd_f32")
     return gqkvs
 
 

@@ -234,7 +234,7 @@ __global__ __launch_bounds__(kBlock) void topk_small_kernel(const float* __restr
     }
   }
   for (int r = tid; r < keep; r += kBlock) perm[k0 + r] = g0 + (int32_t)(0xFFFFFFFFu - (uint32_t)key[r]);
-  // slot[] (mlqem_asap_slot_map: the cluster of every kept centre, -1 elsewhere) from the same sorted keys: no launch of its own
+  // slot[] (slot[perm[p]] = p, -1 elsewhere) from the same sorted keys: no launch of its own
   if (slot)
     for (int r = tid; r < n; r += kBlock) slot[g0 + (int32_t)(0xFFFFFFFFu - (uint32_t)key[r])] = r < keep ? k0 + r : -1;
 }
@@ -273,7 +273,7 @@ __global__ __launch_bounds__(kBlock) void topk_rank_select_kernel(const uint64_t
   }
   const bool kept = rank < keep;
   if (kept) perm[new_gptr[g] + rank] = node;
-  // slot[] (mlqem_asap_slot_map: the cluster of every kept centre, -1 elsewhere): every node is one sorted key -- no launch of its own
+  // slot[] (slot[perm[p]] = p, -1 elsewhere): every node is one sorted key -- no launch of its own
   if (slot) slot[node] = kept ? new_gptr[g] + rank : -1;
 }
 
@@ -554,34 +554,11 @@ __global__ __launch_bounds__(kBlock) void coarsen_dense_fill_kernel(const DenseA
   }
 }
 
-// ------------------------------------------------------ coarsened connectivity, large graphs: one WAVE per cluster
+// ------------------------------------------------------ coarsened connectivity, large graphs: wave helpers
 // 100-qubit circuits pool to thousands of clusters per graph and their second pooling runs on graphs whose hub clusters
 // have hundreds of neighbours: the two-hop path above then enumerates ~50 candidates per distinct pair (147 M hop-1 and
 // 234 M hop-2 keys for eight circuits), sorts them as 64-bit keys (65 GB of buffers at 64 circuits) and reads four sizes
-// back.  Here a wave owns cluster p and keeps BITSETS in LDS: X (the graph's nodes, n_g bits) and Y, Z (the graph's
-// clusters, k_g bits each):
-//     X  = N+[N-[c_p]],  Y = { slot[w] : w in N+[X]  }      -- the clusters p points to   (row p of the pooled adjacency)
-//     X' = N-[N-[c_p]],  Z = { slot[w] : w in N+[X'] }      -- the clusters pointing to p (row p of its transpose)
-// Duplicates collapse in the LDS atomicOr, nothing is sorted, and a bitset is enumerated in ascending order -- which is the
-// order the CSR arrays want.  Both rows go to global bit matrices [K][Wk] with plain coalesced stores (the transpose used to
-// be filled with one global atomicOr per distinct edge into a zeroed matrix: 9.7 M random read-modify-writes for 64 circuits,
-// half of the kernel's time, plus the memset and a popcount pass).  Popcounts -> device scans -> the CSR pointers; a second
-// kernel lists rows / columns and links them (out_eid).  Graphs up to ~65 k nodes (64 KB of LDS per workgroup of four waves).
-struct RowsArgs {
-  const int32_t* in_ptr; const int32_t* in_src; const int32_t* out_ptr; const int32_t* out_dst;
-  const int32_t* gptr; const int32_t* new_gptr; const int32_t* perm; const int32_t* slot;
-  int B; int64_t K;
-  int Wn, Wk;                    // words of the node / cluster bitsets (batch maxima)
-  uint32_t* bm;                  // [K][Wk]: row p = clusters q (local index) with p -> q
-  uint64_t* bmT;                 // [K][Wk]: row q = sources p in the low word; high word = set bits of the row before this word
-  int32_t* outdeg; int32_t* indeg;   // [K + 1]
-};
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
+// back.  The list form below gives each cluster a wave instead; these are its wave-level building blocks.
 
 // exclusive prefix over the wave of a per-lane count
 __device__ __forceinline__ int wave_excl_scan(int v, int lane) {
@@ -620,158 +597,9 @@ __device__ __forceinline__ void wave_lds_only_sync() {
 
 constexpr int kRowsLight = 16;   // degree up to which a lane walks a node's edges alone
 
-// Every lane brings one node (or none); f(w) is called for the node itself and for every w in its neighbourhood in the CSR
-// (ptr, idx).  Nodes with few edges are walked by their lane; the others one after the other by the whole wave (coalesced reads
-// of their adjacency) -- a hub cluster's reach is a few nodes with hundreds of edges each, which one lane would walk for
-// hundreds of dependent round trips while 63 wait.
-template <typename F>
-__device__ __forceinline__ void visit_closed(const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx, bool has, int node,
-                                             int lane, F f) {
-  int eb = 0, ee = 0;
-  if (has) { eb = ptr[node]; ee = ptr[node + 1]; f(node); }
-  const bool heavy = has && ee - eb > kRowsLight;
-  if (has && !heavy)
-    for (int e = eb; e < ee; ++e) f(idx[e]);
-  unsigned long long todo = __ballot(heavy);
-  while (todo) {
-    const int owner = __ffsll((long long)todo) - 1;
-    todo &= todo - 1;
-    const int b = __shfl(eb, owner), e = __shfl(ee, owner);
-    for (int i = b + lane; i < e; i += 64) f(idx[i]);
-  }
-}
-
-// S = { slot[w] >= 0 : w in N+[v], v in X } without `self` (cluster bits, local to the graph); X: Wn words of node bits
-__device__ __forceinline__ void clusters_reached(const RowsArgs& a, const uint32_t* X, int Wn, uint32_t* S, int n0, int k0, int self,
-                                                 int lane) {
-  for (int w0 = 0; w0 < Wn; w0 += 64) {
-    const int wi = w0 + lane;
-    uint32_t bits = wi < Wn ? X[wi] : 0u;
-    while (__ballot(bits != 0u)) {                   // every lane offers its next node, if it has one left
-      const bool has = bits != 0u;
-      int v = 0;
-      if (has) { const int b = __ffs((int)bits) - 1; bits &= bits - 1; v = n0 + wi * 32 + b; }
-      visit_closed(a.out_ptr, a.out_dst, has, v, lane, [&](int w) {
-        const int q = a.slot[w];
-        if (q >= 0 && q != self) atomicOr(&S[(q - k0) >> 5], 1u << ((q - k0) & 31));
-      });
-    }
-  }
-}
-
-__global__ __launch_bounds__(kBlock) void coarsen_rows_kernel(const RowsArgs a) {
-  extern __shared__ uint32_t s_bits[];              // per wave: X [Wn], Y [Wk], Z [Wk]
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  uint32_t* X = s_bits + (size_t)wid * (a.Wn + 2 * a.Wk);
-  uint32_t* Y = X + a.Wn;
-  uint32_t* Z = Y + a.Wk;
-  const int64_t p = (int64_t)blockIdx.x * 4 + wid;
-  if (p >= a.K) return;                              // wave-uniform
-  const int c = a.perm[p];
-  int lo = 0, hi = a.B;                              // graph of cluster p: largest g with new_gptr[g] <= p
-  while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if ((int64_t)a.new_gptr[mid] <= p) lo = mid; else hi = mid; }
-  const int n0 = a.gptr[lo], k0 = a.new_gptr[lo];
-  // words of THIS graph's bitsets (the LDS regions and the rows of the bit matrices are laid out for the batch's largest
-  // graph; a batch mixes 2 k- and 20 k-node circuits, and every loop below runs over words, set or not)
-  const int Wn = (a.gptr[lo + 1] - n0 + 31) >> 5, Wk = (a.new_gptr[lo + 1] - k0 + 31) >> 5;
-  for (int i = lane; i < Wn; i += 64) X[i] = 0u;
-  for (int i = lane; i < Wk; i += 64) { Y[i] = 0u; Z[i] = 0u; }
-  wave_lds_sync();
-  const int ib = a.in_ptr[c], ie = a.in_ptr[c + 1];
-  // X = N+[N-[c]] (node bits, local to the graph)
-  for (int i0 = ib - 1; i0 < ie; i0 += 64) {         // index ib - 1 stands for c itself
-    const int i = i0 + lane;
-    const bool has = i < ie;
-    const int u = has ? (i < ib ? c : a.in_src[i]) : 0;
-    visit_closed(a.out_ptr, a.out_dst, has, u, lane, [&](int v) { atomicOr(&X[(v - n0) >> 5], 1u << ((v - n0) & 31)); });
-  }
-  wave_lds_sync();
-  clusters_reached(a, X, Wn, Y, n0, k0, (int)p, lane);
-  wave_lds_sync();
-  // X = N-[N-[c]]
-  for (int i = lane; i < Wn; i += 64) X[i] = 0u;
-  wave_lds_sync();
-  for (int i0 = ib - 1; i0 < ie; i0 += 64) {
-    const int i = i0 + lane;
-    const bool has = i < ie;
-    const int u = has ? (i < ib ? c : a.in_src[i]) : 0;
-    visit_closed(a.in_ptr, a.in_src, has, u, lane, [&](int v) { atomicOr(&X[(v - n0) >> 5], 1u << ((v - n0) & 31)); });
-  }
-  wave_lds_sync();
-  clusters_reached(a, X, Wn, Z, n0, k0, (int)p, lane);
-  wave_lds_sync();
-  int run_out = 0, run_in = 0;                         // set bits in the words before the current 64
-  for (int w0 = 0; w0 < Wk; w0 += 64) {                // words past Wk of row p stay unwritten: nobody reads them
-    const int wi = w0 + lane;
-    const uint32_t yb = wi < Wk ? Y[wi] : 0u, zb = wi < Wk ? Z[wi] : 0u;
-    const int cz = __popc(zb);
-    const int ex = wave_excl_scan(cz, lane);
-    if (wi < Wk) {
-      a.bm[p * a.Wk + wi] = yb;
-      a.bmT[p * a.Wk + wi] = (uint64_t)zb | ((uint64_t)(uint32_t)(run_in + ex) << 32);   // rank of the word's first bit inside the row
-    }
-    run_in += __shfl(ex + cz, 63);
-    run_out += wave_sum(__popc(yb));
-  }
-  if (lane == 0) { a.outdeg[p] = run_out; a.indeg[p] = run_in; }
-}
-
-__global__ __launch_bounds__(kBlock) void coarsen_rows_fill_kernel(const RowsArgs a, const int32_t* __restrict__ in_ptr_new,
-                                                                   const int32_t* __restrict__ out_ptr_new,
-                                                                   int32_t* __restrict__ in_src_new,
-                                                                   int32_t* __restrict__ out_dst_new,
-                                                                   int32_t* __restrict__ out_eid_new) {
-  const int lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= a.K) return;
-  int lo = 0, hi = a.B;
-  while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if ((int64_t)a.new_gptr[mid] <= r) lo = mid; else hi = mid; }
-  const int k0 = a.new_gptr[lo];
-  const int rl = (int)(r - k0);
-  const int Wk = (a.new_gptr[lo + 1] - k0 + 31) >> 5;   // words of this graph's rows (the count pass wrote no more)
-  // row r of the out-CSR: destinations ascending; each entry also learns where its twin lives in the in-CSR -- the rank of r in
-  // row q of the transpose (bits before word wq: the high half of that word; bits below r inside it).  All stores of this kernel are
-  // consecutive per row; what is random is one 8-byte and one 4-byte read per edge.
-  const int wq = rl >> 5;
-  const uint32_t below = (1u << (rl & 31)) - 1u;
-  int base = out_ptr_new[r];
-  for (int w0 = 0; w0 < Wk; w0 += 64) {
-    const int wi = w0 + lane;
-    uint32_t bits = wi < Wk ? a.bm[r * a.Wk + wi] : 0u;
-    const int n = __popc(bits);
-    const int ex = wave_excl_scan(n, lane);
-    int pos = base + ex;
-    while (bits) {
-      const int b = __ffs((int)bits) - 1;
-      bits &= bits - 1;
-      const int64_t q = (int64_t)k0 + wi * 32 + b;
-      const uint64_t t = a.bmT[q * a.Wk + wq];
-      out_dst_new[pos] = (int32_t)q;
-      out_eid_new[pos] = in_ptr_new[q] + (int)(t >> 32) + __popc((uint32_t)t & below);
-      ++pos;
-    }
-    base += __shfl(ex + n, 63);
-  }
-  // row r of the in-CSR: sources ascending
-  base = in_ptr_new[r];
-  for (int w0 = 0; w0 < Wk; w0 += 64) {
-    const int wi = w0 + lane;
-    uint32_t bits = wi < Wk ? (uint32_t)a.bmT[r * a.Wk + wi] : 0u;
-    const int n = __popc(bits);
-    const int ex = wave_excl_scan(n, lane);
-    int pos = base + ex;
-    while (bits) {
-      const int b = __ffs((int)bits) - 1;
-      bits &= bits - 1;
-      in_src_new[pos++] = k0 + wi * 32 + b;
-    }
-    base += __shfl(ex + n, 63);
-  }
-}
-
 // ------------------------------------------------------ coarsened connectivity, large graphs: SORTED LISTS, one walk (round 4)
-// The bit-matrix form above writes two dense [K][k_g / 32] matrices (0.93 GB for 64 100-qubit circuits, nearly all zeros) and
-// reads them back (1.36 GB) to list 9.7 M edges, and every cluster's wave walks three hops of dependent gathers (in_src ->
+// The bit-matrix form it replaced wrote two dense [K][k_g / 32] matrices (0.93 GB for 64 100-qubit circuits, nearly all zeros) and
+// read them back (1.36 GB) to list 9.7 M edges, and every cluster's wave walked three hops of dependent gathers (in_src ->
 // out_ptr -> out_dst -> slot: 112 M scattered cache accesses per 64 circuits, 72 % of its wave cycles parked on them).
 // This form splits the three hops into per-NODE lists that are built once, so that a cluster only ORs a few contiguous lists
 // into its LDS bitset -- and touches nothing dense in global memory:
@@ -785,7 +613,7 @@ __global__ __launch_bounds__(kBlock) void coarsen_rows_fill_kernel(const RowsArg
 //         words (ONE wave scan of packed counts per cluster) and cleared on the way; degrees -> device scans -> CSR pointers;
 //   copy  a 16-lane group per row moves its lists to their final place and notes every out-entry's row;
 //   link  a thread per out-entry p -> q finds its twin in q's in-row by binary search of p in q's sorted list (out_eid).
-// Same arrays as the bit-matrix form and the two-hop path (tests/test_gpu_family_b.py).
+// Same arrays as the two-hop path (tests/test_gpu_family_b.py).
 struct ListsArgs {
   const int32_t* in_ptr; const int32_t* in_src; const int32_t* out_ptr; const int32_t* out_dst;
   const int32_t* gptr; const int32_t* new_gptr; const int32_t* perm; const int32_t* slot;
@@ -1637,132 +1465,6 @@ extern "C" int mlqem_keys_to_edge_index(const uint64_t* keys, int64_t E, int64_t
   return launch_status();
 }
 
-static void rows_layout(int64_t K, int kmax, size_t& bm, size_t& deg) {
-  const size_t Wk = (size_t)(kmax + 31) / 32;
-  bm = ((size_t)K * Wk * sizeof(uint32_t) + 255) / 256 * 256;      // the transpose (bits + ranks, 8 bytes per word) takes 2 * bm
-  deg = ((size_t)(K + 1) * sizeof(int32_t) + 255) / 256 * 256;
-}
-
-extern "C" size_t mlqem_asap_coarsen_rows_workspace_bytes(int64_t K, int kmax) {
-  if (K < 0 || kmax < 0) return 0;
-  size_t bm, deg;
-  rows_layout(K, kmax, bm, deg);
-  return 3 * bm + 2 * deg + dense_scan_bytes(K);
-}
-
-// slot[] in ONE launch when the graphs' boundaries are at hand: workgroup g wipes its graph's nodes and, behind a barrier, files the
-// graph's kept centres (a graph's centres are its own nodes) -- a fill and a scatter launch before.
-__global__ __launch_bounds__(kBlock) void slot_map_graphs_kernel(const int32_t* __restrict__ perm, const int32_t* __restrict__ gptr,
-                                                                 const int32_t* __restrict__ new_gptr, int32_t* __restrict__ slot) {
-  const int g = blockIdx.x;
-  const int n0 = gptr[g], n1 = gptr[g + 1], k0 = new_gptr[g], k1 = new_gptr[g + 1];
-  for (int i = n0 + threadIdx.x; i < n1; i += kBlock) slot[i] = -1;
-  __syncthreads();
-  for (int p = k0 + threadIdx.x; p < k1; p += kBlock) slot[perm[p]] = p;
-}
-
-extern "C" int mlqem_asap_slot_map_graphs(const int32_t* perm, const int32_t* graph_ptr, const int32_t* new_graph_ptr, int64_t B, int64_t N,
-                                          int64_t K, int32_t* slot, mlqem_stream_t stream_) {
-  begin_launches();
-  hipStream_t stream = as_stream(stream_);
-  if (N < 0 || K < 0 || K > N || B < 0 || B > 0x7fffffffLL) return MLQEM_ERR_BAD_ARG;
-  if (N == 0 || B == 0) return MLQEM_OK;
-  if (!slot || !graph_ptr || !new_graph_ptr || (K > 0 && !perm)) return MLQEM_ERR_BAD_ARG;
-  if (N / B > 65536) {          // a few huge graphs: a workgroup per graph would walk its nodes alone -- the two-launch form
-    fill_i32(slot, -1, N, stream);
-    if (K > 0) hipLaunchKernelGGL(slot_map_kernel, dim3((unsigned)ceil_div(K, kBlock)), dim3(kBlock), 0, stream, perm, K, slot);
-    return launch_status();
-  }
-  hipLaunchKernelGGL(slot_map_graphs_kernel, dim3((unsigned)B), dim3(kBlock), 0, stream, perm, graph_ptr, new_graph_ptr, slot);
-  return launch_status();
-}
-
-extern "C" int mlqem_asap_slot_map(const int32_t* perm, int64_t N, int64_t K, int32_t* slot, mlqem_stream_t stream_) {
-  begin_launches();
-  hipStream_t stream = as_stream(stream_);
-  if (N < 0 || K < 0 || K > N) return MLQEM_ERR_BAD_ARG;
-  if (N == 0) return MLQEM_OK;
-  if (!slot || (K > 0 && !perm)) return MLQEM_ERR_BAD_ARG;
-  fill_i32(slot, -1, N, stream);
-  if (K > 0) hipLaunchKernelGGL(slot_map_kernel, dim3((unsigned)ceil_div(K, kBlock)), dim3(kBlock), 0, stream, perm, K, slot);
-  return launch_status();
-}
-
-extern "C" int mlqem_asap_coarsen_rows_max_bits(void) { return 64 * 1024 * 8 / 4; }   // (n_g + 2 k_g) bits per wave: 64 KB of LDS, four waves
-
-static bool rows_args(RowsArgs& a, const int32_t* in_ptr, const int32_t* in_src, const int32_t* out_ptr, const int32_t* out_dst,
-                      const int32_t* graph_ptr, const int32_t* new_graph_ptr, const int32_t* perm, const int32_t* slot,
-                      int64_t K, int64_t B, int nmax, int kmax, void* workspace) {
-  size_t bm, deg;
-  rows_layout(K, kmax, bm, deg);
-  char* ws = static_cast<char*>(workspace);
-  const int Wk = (kmax + 31) / 32;
-  a = RowsArgs{in_ptr, in_src, out_ptr, out_dst, graph_ptr, new_graph_ptr, perm, slot, (int)B, K, (nmax + 31) / 32, Wk,
-               reinterpret_cast<uint32_t*>(ws), reinterpret_cast<uint64_t*>(ws + bm), reinterpret_cast<int32_t*>(ws + 3 * bm),
-               reinterpret_cast<int32_t*>(ws + 3 * bm + deg)};
-  return true;
-}
-
-// Pass 1: slot[], the two bit matrices (kept in the workspace for pass 2) and both CSR pointer arrays; new_out_ptr[K] is the
-// edge total the caller reads to size the edge arrays.  nmax / kmax: largest graph / largest pooled graph of the batch.
-extern "C" int mlqem_asap_coarsen_rows_count(const int32_t* in_ptr, const int32_t* in_src, const int32_t* out_ptr,
-                                             const int32_t* out_dst, const int32_t* graph_ptr, const int32_t* new_graph_ptr,
-                                             const int32_t* perm, int64_t N, int64_t K, int64_t B, int nmax, int kmax,
-                                             int32_t* slot, int32_t* new_in_ptr, int32_t* new_out_ptr, void* workspace,
-                                             size_t workspace_bytes, mlqem_stream_t stream_) {
-  begin_launches();
-  hipStream_t stream = as_stream(stream_);
-  if (N < 0 || K < 0 || K > N || B < 0 || kmax < 0 || nmax < 0 || N >= 0x7fffffffLL) return MLQEM_ERR_BAD_ARG;
-  if (nmax + 2 * kmax + 96 > mlqem_asap_coarsen_rows_max_bits()) return MLQEM_ERR_UNSUPPORTED;
-  if (!slot || !new_in_ptr || !new_out_ptr) return MLQEM_ERR_BAD_ARG;
-  if (!workspace || workspace_bytes < mlqem_asap_coarsen_rows_workspace_bytes(K, kmax)) return MLQEM_ERR_WORKSPACE;
-  fill_i32(slot, -1, N, stream);
-  if (K == 0 || B == 0) {
-    fill_i32(new_in_ptr, 0, K + 1, stream);
-    fill_i32(new_out_ptr, 0, K + 1, stream);
-    return launch_status();
-  }
-  if (!in_ptr || !out_ptr || !graph_ptr || !new_graph_ptr || !perm) return MLQEM_ERR_BAD_ARG;
-  RowsArgs a;
-  rows_args(a, in_ptr, in_src, out_ptr, out_dst, graph_ptr, new_graph_ptr, perm, slot, K, B, nmax, kmax, workspace);
-  size_t bm, deg;
-  rows_layout(K, kmax, bm, deg);
-  fill_i32(a.outdeg + K, 0, 1, stream);
-  fill_i32(a.indeg + K, 0, 1, stream);
-  hipLaunchKernelGGL(slot_map_kernel, dim3((unsigned)ceil_div(K, kBlock)), dim3(kBlock), 0, stream, perm, K, slot);
-  const size_t lds = (size_t)4 * (a.Wn + 2 * a.Wk) * sizeof(uint32_t);
-  const unsigned grid = (unsigned)ceil_div(K, (int64_t)4);
-  hipLaunchKernelGGL(coarsen_rows_kernel, dim3(grid), dim3(kBlock), lds, stream, a);
-  void* temp = static_cast<char*>(workspace) + 3 * bm + 2 * deg;
-  size_t temp_bytes = dense_scan_bytes(K);
-  if (rocprim::exclusive_scan(temp, temp_bytes, a.outdeg, new_out_ptr, (int32_t)0, (size_t)(K + 1), rocprim::plus<int32_t>(),
-                              stream) != hipSuccess)
-    return MLQEM_ERR_LAUNCH;
-  if (rocprim::exclusive_scan(temp, temp_bytes, a.indeg, new_in_ptr, (int32_t)0, (size_t)(K + 1), rocprim::plus<int32_t>(),
-                              stream) != hipSuccess)
-    return MLQEM_ERR_LAUNCH;
-  return launch_status();
-}
-
-// Pass 2 (same workspace, untouched in between): the edge arrays, each sized new_out_ptr[K].
-extern "C" int mlqem_asap_coarsen_rows_fill(const int32_t* new_graph_ptr, int64_t K, int64_t B, int kmax, const int32_t* new_in_ptr,
-                                            const int32_t* new_out_ptr, int32_t* new_in_src, int32_t* new_out_dst,
-                                            int32_t* new_out_eid, const void* workspace, size_t workspace_bytes,
-                                            mlqem_stream_t stream_) {
-  begin_launches();
-  hipStream_t stream = as_stream(stream_);
-  if (K < 0 || B < 0 || kmax < 0) return MLQEM_ERR_BAD_ARG;
-  if (K == 0 || B == 0) return MLQEM_OK;
-  if (!new_graph_ptr || !new_in_ptr || !new_out_ptr || !new_in_src || !new_out_dst || !new_out_eid) return MLQEM_ERR_BAD_ARG;
-  if (!workspace || workspace_bytes < mlqem_asap_coarsen_rows_workspace_bytes(K, kmax)) return MLQEM_ERR_WORKSPACE;
-  RowsArgs a;
-  rows_args(a, nullptr, nullptr, nullptr, nullptr, nullptr, new_graph_ptr, nullptr, nullptr, K, B, 0, kmax,
-            const_cast<void*>(workspace));
-  hipLaunchKernelGGL(coarsen_rows_fill_kernel, dim3((unsigned)ceil_div(K, (int64_t)4)), dim3(kBlock), 0, stream, a, new_in_ptr,
-                     new_out_ptr, new_in_src, new_out_dst, new_out_eid);
-  return launch_status();
-}
-
 // ---- list form (round 4).  Workspace: h_out, h_in, roff_o, roff_i [N + 1] int64 | ccnt, rcnt_o, rcnt_i [N] | clist [E + N] |
 //      cap_o, cap_i, off_o, off_i [K + 1] int64 | outdeg, indeg [K + 1] | flag | scan temp | r_o, r_i, tmp_o, tmp_i [capacity]
 //      (rcnt_o + rcnt_i + ... : the per-node records rinfo [N][4] take the place of four count arrays)
@@ -1893,14 +1595,14 @@ extern "C" int mlqem_asap_coarsen_lists_caps(const int32_t* in_ptr, const int32_
   return launch_status();
 }
 
-// Pass 1: slot[], the per-node lists, the rows as sorted lists in the workspace, both CSR pointer arrays.  E: the number of stored
-// edges of the input structure (out_ptr[N]) or a bound on it.  `capacity`: entries each of the four list buffers holds -- a bound
-// on all four totals mlqem_asap_coarsen_lists_caps reports (GraphArena knows a structural one); a list that would leave its
-// buffer is dropped, nothing is written past one, and pass 2 reports it.
+// Pass 1 (slot[perm[p]] = p, -1 elsewhere, on entry): the per-node lists, the rows as sorted lists in the workspace, both CSR
+// pointer arrays.  E: the number of stored edges of the input structure (out_ptr[N]) or a bound on it.  `capacity`: entries each
+// of the four list buffers holds -- a bound on all four totals mlqem_asap_coarsen_lists_caps reports (GraphArena knows a structural
+// one); a list that would leave its buffer is dropped, nothing is written past one, and pass 2 reports it.
 extern "C" int mlqem_asap_coarsen_lists_count(const int32_t* in_ptr, const int32_t* in_src, const int32_t* out_ptr,
                                               const int32_t* out_dst, const int32_t* graph_ptr, const int32_t* new_graph_ptr,
                                               const int32_t* perm, int64_t N, int64_t K, int64_t B, int64_t E, int kmax, int64_t capacity,
-                                              int32_t* slot, int slot_ready, int32_t* new_in_ptr, int32_t* new_out_ptr, int32_t* new_loops,
+                                              const int32_t* slot, int32_t* new_in_ptr, int32_t* new_out_ptr, int32_t* new_loops,
                                               void* workspace, size_t workspace_bytes, mlqem_stream_t stream_) {
   begin_launches();
   hipStream_t stream = as_stream(stream_);
@@ -1909,7 +1611,6 @@ extern "C" int mlqem_asap_coarsen_lists_count(const int32_t* in_ptr, const int32
   if (!slot || !new_in_ptr || !new_out_ptr) return MLQEM_ERR_BAD_ARG;
   const ListsLayout l = lists_layout(N, K, E, capacity);
   if (!workspace || workspace_bytes < l.total) return MLQEM_ERR_WORKSPACE;
-  if (!slot_ready) fill_i32(slot, -1, N, stream);
   if (K == 0 || B == 0) {
     fill_i32(new_in_ptr, 0, K + 1, stream);
     fill_i32(new_out_ptr, 0, K + 1, stream);
@@ -1917,7 +1618,6 @@ extern "C" int mlqem_asap_coarsen_lists_count(const int32_t* in_ptr, const int32
   }
   if (!in_ptr || !out_ptr || !graph_ptr || !new_graph_ptr || !perm || (E > 0 && (!in_src || !out_dst))) return MLQEM_ERR_BAD_ARG;
   const ListsPointers q = lists_pointers(workspace, l);
-  if (!slot_ready) hipLaunchKernelGGL(slot_map_kernel, dim3((unsigned)ceil_div(K, kBlock)), dim3(kBlock), 0, stream, perm, K, slot);
   const int rc = lists_caps(in_ptr, in_src, out_ptr, out_dst, new_graph_ptr, perm, N, K, B, q, l, stream, new_loops);
   if (rc != MLQEM_OK) return rc;
   const unsigned node_blocks = (unsigned)ceil_div(N, (int64_t)kBlock);
@@ -1984,7 +1684,7 @@ extern "C" size_t mlqem_asap_coarsen_dense_workspace_bytes(int64_t B, int64_t K,
 
 extern "C" int mlqem_asap_coarsen_dense(const int32_t* in_ptr, const int32_t* in_src, const int32_t* out_ptr,
                                         const int32_t* out_dst, const int32_t* graph_ptr, const int32_t* new_graph_ptr,
-                                        const int32_t* perm, int64_t N, int64_t K, int64_t B, int kmax, int32_t* slot, int slot_ready,
+                                        const int32_t* perm, int64_t N, int64_t K, int64_t B, int kmax, const int32_t* slot,
                                         int32_t* new_in_ptr, int32_t* new_in_src, int32_t* new_out_ptr, int32_t* new_out_dst,
                                         int32_t* new_out_eid, int32_t* new_loops, void* workspace, size_t workspace_bytes,
                                         mlqem_stream_t stream_) {
@@ -1994,8 +1694,6 @@ extern "C" int mlqem_asap_coarsen_dense(const int32_t* in_ptr, const int32_t* in
   if (kmax > kDenseMaxK) return MLQEM_ERR_UNSUPPORTED;
   if (!slot || !new_in_ptr || !new_out_ptr) return MLQEM_ERR_BAD_ARG;
   if (!workspace || workspace_bytes < mlqem_asap_coarsen_dense_workspace_bytes(B, K, kmax)) return MLQEM_ERR_WORKSPACE;
-  // slot_ready: `slot` already holds mlqem_asap_slot_map(perm) (the pooling's forward made it for its backward): two launches less
-  if (!slot_ready) fill_i32(slot, -1, N, stream);
   if (K == 0 || B == 0) {
     fill_i32(new_in_ptr, 0, K + 1, stream);
     fill_i32(new_out_ptr, 0, K + 1, stream);
@@ -2011,7 +1709,6 @@ extern "C" int mlqem_asap_coarsen_dense(const int32_t* in_ptr, const int32_t* in
               reinterpret_cast<uint32_t*>(ws + bm), kmax, reinterpret_cast<int32_t*>(ws + 2 * bm), reinterpret_cast<int32_t*>(ws + 2 * bm + deg)};
   void* temp = ws + 2 * bm + 2 * deg;
   size_t temp_bytes = dense_scan_bytes(K);
-  if (!slot_ready) hipLaunchKernelGGL(slot_map_kernel, dim3((unsigned)ceil_div(K, kBlock)), dim3(kBlock), 0, stream, perm, K, slot);
   const size_t lds = (size_t)kmax * W * sizeof(uint32_t);      // one k x k bit matrix; the kernels hold two and three of them
   if (!ensure_dynamic_lds(coarsen_dense_bitmap_kernel, 2 * lds) || !ensure_dynamic_lds(coarsen_dense_fill_kernel, 3 * lds)) return MLQEM_ERR_LAUNCH;
   hipLaunchKernelGGL(coarsen_dense_bitmap_kernel, dim3((unsigned)B), dim3(kBlock), 2 * lds, stream, a);

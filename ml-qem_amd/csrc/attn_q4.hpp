@@ -62,17 +62,11 @@ __device__ __forceinline__ f4u load_channels(const float* __restrict__ p, int nv
   return v;
 }
 typedef float f3u __attribute__((ext_vector_type(3), aligned(4)));
-// MLQEM_ATTN_VSTORE=0 (compile time): one dword store per channel (A/B builds)
-#ifndef MLQEM_ATTN_VSTORE
-#define MLQEM_ATTN_VSTORE 1
-#endif
 // A lane's channels as ONE store: 16 bytes, or 12 from the last lane of a 15-channel head (the fourth float is the next head's
 // first channel, another lane's) -- two store instructions per wave and matrix instead of four that each touch every line.
 __device__ __forceinline__ void store_channels(float* __restrict__ p, const f4u& v, int nv) {
-#if MLQEM_ATTN_VSTORE
   if (nv == 4) { *reinterpret_cast<f4u*>(p) = v; return; }
   if (nv == 3) { *reinterpret_cast<f3u*>(p) = f3u{v.x, v.y, v.z}; return; }
-#endif
   if (nv > 0) p[0] = v.x;
   if (nv > 1) p[1] = v.y;
   if (nv > 2) p[2] = v.z;

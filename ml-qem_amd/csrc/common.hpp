@@ -26,12 +26,6 @@ inline int launch_status() {
 
 __host__ __device__ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-// A/B switch of an experiment in flight (scripts/ab_env.sh): read once per call site.  Settled switches become constants.
-inline int ab_env(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v && *v ? atoi(v) : dflt;
-}
-
 // Workgroups are dealt round-robin over the 8 XCDs (block b and b+8 share an L2).  Kernels that walk a
 // row range want each XCD to own one CONTIGUOUS slice of it, so that the window of source rows a tile
 // gathers from is already in that XCD's L2.  This is the bijective remap for any grid size.
@@ -45,17 +39,7 @@ __device__ __forceinline__ unsigned xcd_contiguous_block(unsigned b, unsigned nb
 // Block number of a ROW kernel (a block owns a run of consecutive rows): XCD-contiguous, so that the blocks resident on one XCD
 // walk neighbouring rows -- rows of the same graph, whose source rows are then in that XCD's 4 MB L2 (a pooled 100-qubit graph's
 // key + value rows are 1.4 MB; dealt round-robin every XCD sees every graph and the gathers go out to the Infinity Cache).
-// -DMLQEM_XCD_ROWS=0 compiles the plain numbering (A/B builds only).
-#ifndef MLQEM_XCD_ROWS
-#define MLQEM_XCD_ROWS 1
-#endif
-__device__ __forceinline__ unsigned row_block() {
-#if MLQEM_XCD_ROWS
-  return xcd_contiguous_block(blockIdx.x, gridDim.x);
-#else
-  return blockIdx.x;
-#endif
-}
+__device__ __forceinline__ unsigned row_block() { return xcd_contiguous_block(blockIdx.x, gridDim.x); }
 
 // Counter-based uniform in [0,1): one splitmix64 round over (seed, element index).
 __device__ __forceinline__ float uniform01(uint64_t seed, uint64_t idx) {

@@ -676,7 +676,7 @@ extern "C" int mlqem_dense_attention_supported(int H, int C, int head_pitch) { r
 extern "C" int mlqem_dense_attention_train_f32(const float* qkvs, int64_t ld, const int32_t* in_ptr, const int32_t* in_src,
                                                const int32_t* loops, int64_t N, int64_t E, int H, int C, float drop_p, uint64_t seed,
                                                const uint64_t* seed_counter, int head_pitch, const int32_t* records, const int32_t* counter,
-                                               const uint8_t* row_flag, int64_t max_blocks, int parts, float* out, int64_t ldo,
+                                               const uint8_t* row_flag, int64_t max_blocks, float* out, int64_t ldo,
                                                float* attn_out, int64_t lda, float* stat_m, float* stat_den, mlqem_stream_t stream) {
   begin_launches();
   if (!mlqem_dense_attention_supported(H, C, head_pitch)) return MLQEM_ERR_UNSUPPORTED;
@@ -689,13 +689,11 @@ extern "C" int mlqem_dense_attention_train_f32(const float* qkvs, int64_t ld, co
                 1, nullptr, head_pitch};
   a.skip = row_flag;
   const DensePlan p{records, counter, row_flag, max_blocks};
-  if (parts & 1) launch_attn_train_q4(a, as_stream(stream));
+  launch_attn_train_q4(a, as_stream(stream));        // the per-edge kernel over the rows outside the blocks, then the blocks
   const dim3 grid((unsigned)dense_grid(max_blocks));
-  if (parts & 2) {
-    if (H == 3) hipLaunchKernelGGL((dense_attn_fwd_kernel<3, true>), grid, dim3(kBlock), 0, as_stream(stream), a, p);
-    else if (H == 2) hipLaunchKernelGGL((dense_attn_fwd_kernel<2, true>), grid, dim3(kBlock), 0, as_stream(stream), a, p);
-    else hipLaunchKernelGGL((dense_attn_fwd_kernel<1, true>), grid, dim3(kBlock), 0, as_stream(stream), a, p);
-  }
+  if (H == 3) hipLaunchKernelGGL((dense_attn_fwd_kernel<3, true>), grid, dim3(kBlock), 0, as_stream(stream), a, p);
+  else if (H == 2) hipLaunchKernelGGL((dense_attn_fwd_kernel<2, true>), grid, dim3(kBlock), 0, as_stream(stream), a, p);
+  else hipLaunchKernelGGL((dense_attn_fwd_kernel<1, true>), grid, dim3(kBlock), 0, as_stream(stream), a, p);
   return launch_status();
 }
 
@@ -705,7 +703,7 @@ extern "C" int mlqem_dense_attention_bwd_f32(const float* qkvs, int64_t ld, cons
                                              int C, float drop_p, uint64_t seed, const uint64_t* seed_counter, int head_pitch,
                                              const int32_t* in_records, const int32_t* in_counter, const uint8_t* in_flag, int64_t in_max_blocks,
                                              const int32_t* out_records, const int32_t* out_counter, const uint8_t* out_flag,
-                                             int64_t out_max_blocks, int parts, float* gqkvs, int64_t ldq, float* edge_al,
+                                             int64_t out_max_blocks, float* gqkvs, int64_t ldq, float* edge_al,
                                              mlqem_stream_t stream) {
   begin_launches();
   if (!mlqem_dense_attention_supported(H, C, head_pitch)) return MLQEM_ERR_UNSUPPORTED;
@@ -723,20 +721,16 @@ extern "C" int mlqem_dense_attention_bwd_f32(const float* qkvs, int64_t ld, cons
   a.skip_src = out_flag;
   const DensePlan pin{in_records, in_counter, in_flag, in_max_blocks}, pout{out_records, out_counter, out_flag, out_max_blocks};
   const hipStream_t s = as_stream(stream);
-  // parts: 1 = destination side, per-edge rows; 2 = destination side, blocks; 4 = source side, per-edge rows; 8 = source side, blocks.
-  // The source side reads the records BOTH destination-side kernels file: a caller that spreads the parts over streams joins between.
-  if (parts & 1) launch_attn_bwd_dst_q4(a, s);
+  // destination side (per-edge rows, then blocks), then source side (per-edge rows, then blocks): the source side reads the records
+  // BOTH destination-side kernels file
+  launch_attn_bwd_dst_q4(a, s);
   const dim3 gin((unsigned)dense_grid(in_max_blocks)), gout((unsigned)dense_grid(out_max_blocks));
-  if (parts & 2) {
-    if (H == 3) hipLaunchKernelGGL(dense_attn_bwd_dst_kernel<3>, gin, dim3(kBlock), 0, s, a, pin);
-    else if (H == 2) hipLaunchKernelGGL(dense_attn_bwd_dst_kernel<2>, gin, dim3(kBlock), 0, s, a, pin);
-    else hipLaunchKernelGGL(dense_attn_bwd_dst_kernel<1>, gin, dim3(kBlock), 0, s, a, pin);
-  }
-  if (parts & 4) launch_attn_bwd_src_rc_q4(a, s);
-  if (parts & 8) {
-    if (H == 3) hipLaunchKernelGGL(dense_attn_bwd_src_kernel<3>, gout, dim3(kBlock), 0, s, a, pout);
-    else if (H == 2) hipLaunchKernelGGL(dense_attn_bwd_src_kernel<2>, gout, dim3(kBlock), 0, s, a, pout);
-    else hipLaunchKernelGGL(dense_attn_bwd_src_kernel<1>, gout, dim3(kBlock), 0, s, a, pout);
-  }
+  if (H == 3) hipLaunchKernelGGL(dense_attn_bwd_dst_kernel<3>, gin, dim3(kBlock), 0, s, a, pin);
+  else if (H == 2) hipLaunchKernelGGL(dense_attn_bwd_dst_kernel<2>, gin, dim3(kBlock), 0, s, a, pin);
+  else hipLaunchKernelGGL(dense_attn_bwd_dst_kernel<1>, gin, dim3(kBlock), 0, s, a, pin);
+  launch_attn_bwd_src_rc_q4(a, s);
+  if (H == 3) hipLaunchKernelGGL(dense_attn_bwd_src_kernel<3>, gout, dim3(kBlock), 0, s, a, pout);
+  else if (H == 2) hipLaunchKernelGGL(dense_attn_bwd_src_kernel<2>, gout, dim3(kBlock), 0, s, a, pout);
+  else hipLaunchKernelGGL(dense_attn_bwd_src_kernel<1>, gout, dim3(kBlock), 0, s, a, pout);
   return launch_status();
 }

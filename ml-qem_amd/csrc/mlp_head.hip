@@ -29,9 +29,7 @@ constexpr int kHeadH = MLQEM_MLP1_HIDDEN_PAD;   // columns of the stash (hidden 
 constexpr int kHeadMaxOut = MLQEM_MLP1_MAX_OUT;
 constexpr int kFwdThreads = 256;                // the waves of a workgroup share one W1 image in LDS
 constexpr int kBwdThreads = 256;
-#ifndef MLQEM_HEAD_BWD_KU
-#define MLQEM_HEAD_BWD_KU 8    // k-steps (of 4 rows) per iteration of the fp32 backward: one iteration = the prefetch distance; 8 spills (two register sets)
-#endif
+constexpr int kHeadBwdKU = 8;   // k-steps (of 4 rows) per iteration of the fp32 backward: one iteration = the prefetch distance; 8 spills (two register sets)
 
 struct Mlp1Args {
   const float* x; int64_t ldx; int64_t N; int I, H, O2;
@@ -873,7 +871,7 @@ extern "C" int mlqem_mlp1_backward(const float* gout, int64_t ldg, const float* 
     if (O2 == 1) hipLaunchKernelGGL(mlp1_bwd_bf16_kernel<1>, dim3(G), dim3(kBwdThreads), 0, s, a, cpw);
     else hipLaunchKernelGGL(mlp1_bwd_bf16_kernel<4>, dim3(G), dim3(kBwdThreads), 0, s, a, cpw);
   } else {
-    constexpr int KU = MLQEM_HEAD_BWD_KU;
+    constexpr int KU = kHeadBwdKU;
     // columns of [x | 1] as NG float4 groups of 64 and NS scalar fragments of 16
     const int ci = I + 1;
     const int ng = ci <= 112 ? 1 : 2, ns = ci <= 64 * ng ? 0 : 3;

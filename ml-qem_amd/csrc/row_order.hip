@@ -63,7 +63,7 @@ __device__ __forceinline__ int block_exclusive_scan(int v, int* tmp, int& tot) {
 
 // order[new_ptr[g] + r] = the cluster whose centre is the r-th kept node of graph g in NODE order (= program order: the encoder
 // numbers a circuit's operations in instruction order, blackwater/data/utils.py:198-389).  slot[v] = cluster id of a kept centre v,
-// -1 elsewhere (mlqem_asap_slot_map).  One workgroup per graph -- of 1024 threads, twelve nodes each: a 100-qubit circuit's 11 k nodes
+// -1 elsewhere (slot[perm[p]] = p).  One workgroup per graph -- of 1024 threads, twelve nodes each: a 100-qubit circuit's 11 k nodes
 // are ONE trip (load, scan, store); at 256 threads and eight nodes a trip the six trips, each waiting for its loads and two barriers,
 // were 22 us whatever the batch (64 workgroups on 256 compute units).
 constexpr int kOrderThreads = 1024;

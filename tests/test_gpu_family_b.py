@@ -390,8 +390,8 @@ def _pooled_levels(model, x, ei, batch_vec, b):
     return s1, s2, perm1, perm2, h2
 
 
-def test_wave_per_cluster_coarsening_equals_the_two_hop_path(golden_dir, g1):
-    """The large-graph form of ASAPooling's coarsening (one wave per cluster, LDS bitsets, one host read) against the
+def test_list_coarsening_equals_the_two_hop_path(golden_dir, g1):
+    """The large-graph form of ASAPooling's coarsening (sorted per-node lists, persistent waves, LDS bitsets) against the
     two-hop path (four reads, two 64-bit sorts): identical CSR arrays and out_eid at both pooling levels -- on the
     reference's small graphs (dense form switched off) and on 100-qubit circuits whose second pooling has hub clusters
     with hundreds of neighbours."""
@@ -414,28 +414,27 @@ def test_wave_per_cluster_coarsening_equals_the_two_hop_path(golden_dir, g1):
                   torch.from_numpy(np.repeat(np.arange(len(counts)), counts)).to(DEV), len(counts)))
     for model, x, ei, bv, b in cases:
         res = {}
-        # "lists": sorted lists from persistent waves (round 4, the default); "rows": dense bit matrices (round 3); "hop": two-hop
-        for mode, (rows, lists) in {"lists": (True, True), "rows": (True, False), "hop": (False, False)}.items():
-            F._ASAP_DENSE, F._ASAP_ROWS, F._ASAP_LISTS, keep_link = False, rows, lists, F._ASAP_LINK
+        # "lists": sorted lists from persistent waves (the default); "hop": two-hop
+        for mode, lists in {"lists": True, "hop": False}.items():
+            F._ASAP_DENSE, F._ASAP_LISTS, keep_link = False, lists, F._ASAP_LINK
             F._ASAP_LINK = True                    # out_eid is compared below (the default skips the link pass)
             try:
                 res[mode] = _pooled_levels(model, x, ei, bv, b)
                 for lvl in (0, 1):
                     res[mode][lvl].in_ptr          # the second level is deferred: build it under THIS mode's switches
             finally:
-                F._ASAP_DENSE, F._ASAP_ROWS, F._ASAP_LISTS, F._ASAP_LINK = True, True, True, keep_link
-        for mode in ("lists", "rows"):
-            for lvl in (0, 1):
-                a, c = res[mode][lvl], res["hop"][lvl]
-                e = int(c.in_ptr[c.num_nodes].item())
-                assert e == c.num_edges == a.num_edges and e > 0
-                assert torch.equal(a.in_ptr[:a.num_nodes + 1], c.in_ptr[:c.num_nodes + 1])
-                assert torch.equal(a.out_ptr[:a.num_nodes + 1], c.out_ptr[:c.num_nodes + 1])
-                assert torch.equal(a.in_src[:e], c.in_src[:e]) and torch.equal(a.out_dst[:e], c.out_dst[:e])
-                assert torch.equal(a.out_eid[:e], c.out_eid[:e])
-                assert not a.loops[:a.num_nodes].any()
-            assert torch.equal(res[mode][2], res["hop"][2]) and torch.equal(res[mode][3], res["hop"][3])
-            assert torch.equal(res[mode][4], res["hop"][4])
+                F._ASAP_DENSE, F._ASAP_LISTS, F._ASAP_LINK = True, True, keep_link
+        for lvl in (0, 1):
+            a, c = res["lists"][lvl], res["hop"][lvl]
+            e = int(c.in_ptr[c.num_nodes].item())
+            assert e == c.num_edges == a.num_edges and e > 0
+            assert torch.equal(a.in_ptr[:a.num_nodes + 1], c.in_ptr[:c.num_nodes + 1])
+            assert torch.equal(a.out_ptr[:a.num_nodes + 1], c.out_ptr[:c.num_nodes + 1])
+            assert torch.equal(a.in_src[:e], c.in_src[:e]) and torch.equal(a.out_dst[:e], c.out_dst[:e])
+            assert torch.equal(a.out_eid[:e], c.out_eid[:e])
+            assert not a.loops[:a.num_nodes].any()
+        assert torch.equal(res["lists"][2], res["hop"][2]) and torch.equal(res["lists"][3], res["hop"][3])
+        assert torch.equal(res["lists"][4], res["hop"][4])
 
 
 def test_list_coarsening_with_a_structural_capacity_equals_the_exact_one(golden_dir):
@@ -986,10 +985,11 @@ def test_family_b_with_and_without_the_fused_pooling_forward(g1):
         assert (ga[k] - gb[k]).abs().max().item() < 2e-4 * gmax, k
 
 
-def test_list_coarsening_equals_the_bit_matrix_form_on_a_64_circuit_batch():
+def test_list_coarsening_equals_the_two_hop_path_on_a_64_circuit_batch():
     """Scale matters to the persistent kernels of the list coarsening (batches of 64 clusters per wave, partial last batches, several
     batches per wave): the first pooling of 64 100-qubit circuits (363 k clusters, ~20 M coarsened edges) must give the arrays of the
-    round-3 bit-matrix form exactly.  (A variant of coarsen_unique_kernel passed every smaller comparison and failed this one.)"""
+    two-hop path exactly.  (A variant of coarsen_unique_kernel passed every smaller comparison and failed this one.)  Only the first
+    pooling: its input rows have 1-3 entries, so the two-hop path's candidate keys stay far below the second pooling's."""
     from blackwater.data.arena import GraphArena
     from blackwater.data.synthetic import TfimCorpus
     from blackwater.native import functional as F

@@ -38,7 +38,7 @@ extern "C" {
 
 typedef void* mlqem_stream_t; /* hipStream_t */
 
-#define MLQEM_ABI_VERSION 43 /* bumped whenever a signature below changes; bindings compare it at load time */
+#define MLQEM_ABI_VERSION 44 /* bumped whenever a signature below changes; bindings compare it at load time */
 int mlqem_abi_version(void);
 const char* mlqem_error_string(int code);
 
@@ -142,6 +142,29 @@ int mlqem_batch_norm_train_bwd_f32(const float* dy, int64_t ldg, const float* x,
                                    const float* gamma, const float* mean, const float* invstd, float* dx, int64_t lddx,
                                    float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
                                    mlqem_stream_t stream);
+
+/* BatchNorm1d with statistics shared by the ranks of a process group (torch.nn.SyncBatchNorm semantics, ABI 44): the bn1 / bn2 of a
+ * converted MLP2 / MLP3 under data parallelism (docs/tutorials/mlp.py:45-66,87-108).  The finish of the two calls above is split in
+ * two around ONE all-reduce(SUM) that the caller runs over a [world][2 C + 1] double buffer in which rank r filled row r (the other
+ * rows zero, so the sum is exact and every rank receives the same records bit for bit):
+ *   record    mode 0: [n_r | mean_r[C] | M2_r[C]] of this rank's rows x (per-workgroup sums shifted by row 0, finished in double).
+ *             mode 1: [n_r | sum dy[C] | sum dy xhat[C]] with xhat from the GLOBAL mean / invstd of the forward; this rank's
+ *             dgamma / dbeta (the local sums: the gradient all-reduce averages them like any parameter gradient).
+ *   train     records -> mean, biased var, invstd over the union of the ranks' rows (Chan's pairwise merge in rank order), y for
+ *             this rank's rows, and (running_mean / running_var / num_batches_tracked, each optional, both buffers or neither) the
+ *             running update with the global N: running_var <- (1 - momentum) running_var + momentum var N / (N - 1).
+ *   train_bwd records -> dx = gamma invstd (dy - sum_r dbeta_r / N - xhat sum_r dgamma_r / N) for this rank's rows.
+ * Same workspace as mlqem_batch_norm_train_f32 (C <= 256); deterministic, no atomics, no allocation, no host synchronisation. */
+int mlqem_batch_norm_sync_record_f32(int mode, const float* x, int64_t ldx, const float* dy, int64_t ldg, const float* mean,
+                                     const float* invstd, int64_t N, int C, double* record, float* dgamma, float* dbeta,
+                                     void* workspace, size_t workspace_bytes, mlqem_stream_t stream);
+int mlqem_batch_norm_sync_train_f32(const double* records, int world, const float* x, int64_t ldx, int64_t N, int C,
+                                    const float* gamma, const float* beta, float eps, float* y, int64_t ldy, float* mean, float* var,
+                                    float* invstd, float* running_mean, float* running_var, float momentum,
+                                    int64_t* num_batches_tracked, void* workspace, size_t workspace_bytes, mlqem_stream_t stream);
+int mlqem_batch_norm_sync_train_bwd_f32(const double* records, int world, const float* dy, int64_t ldg, const float* x, int64_t ldx,
+                                        int64_t N, int C, const float* gamma, const float* mean, const float* invstd, float* dx,
+                                        int64_t lddx, void* workspace, size_t workspace_bytes, mlqem_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------------
  * The two ends of a train step that are not model layers (docs/tutorials/__ml_models.py:100-187:
@@ -383,6 +406,32 @@ int mlqem_layer_rowdot_f32(const void* h, const float* w, const float* b, float*
                            mlqem_stream_t stream);
 int mlqem_layer_rowdot_bwd_f32(const float* g, int64_t ldg, const void* h, const float* w, void* gh, float gate_scale, float* gw,
                                float* gb, int64_t N, int C, int O, void* workspace, size_t workspace_bytes, mlqem_stream_t stream);
+
+/* Synced statistics for either storage of the pipeline (torch.nn.SyncBatchNorm semantics under data parallelism, ABI 44; the bn1 /
+ * bn2 of a converted MLP2 / MLP3, docs/tutorials/mlp.py:45-66,87-108): colstats' two stages with ONE all-reduce(SUM) of the caller
+ * in between, over a [world][2 C + 1] double buffer in which rank r filled row r (zeros elsewhere: exact in any order).
+ *   colstats_record_bf16 / _f32  mode 0: [n_r | mean_r[C] | M2_r[C]] of this rank's y (the shifted column sums, finished in
+ *               double).  mode 1: [n_r | sum gu[C] | sum gu xhat[C]] with colstats 1's gu and the GLOBAL mean / invstd; dbeta /
+ *               dgamma ([128], zeros beyond C) get this rank's sums (the parameter gradients: the gradient all-reduce averages them).
+ *               Arguments as colstats'; same workspace.
+ *   colstats_merge  records -> colstats' outputs, storage-independent ([128] each, zeros beyond C).  mode 0: o1..o5 = mean, biased
+ *               var, invstd, scale, shift over the union of the ranks' rows (Chan's pairwise merge in rank order) and the running
+ *               update with the global N (running_* / num_batches_tracked optional).  mode 1: o3..o5 = gs = gamma invstd,
+ *               k1 = sum_r dbeta_r / N, k2 = sum_r dgamma_r / N (o1 / o2 unused).
+ * The element-wise entry points (pointwise 0 / 1) consume the outputs unchanged.  Deterministic, no atomics, no allocation, no host
+ * synchronisation. */
+int mlqem_layer_colstats_record_bf16(int mode, const void* y, const void* g, const float* g32, int64_t ldg32, const float* scale,
+                                     const float* shift, const float* mean, const float* invstd, int relu, float drop_p, uint64_t seed,
+                                     const uint64_t* seed_counter, int64_t N, int C, double* record, float* dbeta, float* dgamma,
+                                     void* workspace, size_t workspace_bytes, mlqem_stream_t stream);
+int mlqem_layer_colstats_record_f32(int mode, const void* y, const void* g, const float* g32, int64_t ldg32, const float* scale,
+                                    const float* shift, const float* mean, const float* invstd, int relu, float drop_p, uint64_t seed,
+                                    const uint64_t* seed_counter, int64_t N, int C, double* record, float* dbeta, float* dgamma,
+                                    void* workspace, size_t workspace_bytes, mlqem_stream_t stream);
+int mlqem_layer_colstats_merge(int mode, const double* records, int world, int C, const float* gamma, const float* beta,
+                               const float* invstd, float eps, float* o1, float* o2, float* o3, float* o4, float* o5,
+                               float* running_mean, float* running_var, float momentum, int64_t* num_batches_tracked,
+                               mlqem_stream_t stream);
 
 /* Backward of a narrow hidden layer (I, O <= 12) in ONE pass over its operands:
  *   gx[n,:] = (x[n,:] > 0 ? gate_scale : 0) * (gy[n,:] @ W)   (gate != 0; plain gy @ W otherwise)      W: [O, I]

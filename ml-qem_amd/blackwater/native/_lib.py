@@ -92,6 +92,9 @@ SIGNATURES = {
     "mlqem_layer_wgrad_f32": (_I, [_P, _P, _L, _P, _P, _L, _I, _I, _P, _S, _P]),
     "mlqem_layer_rowdot_f32": (_I, [_P, _P, _P, _P, _L, _L, _I, _I, _P]),
     "mlqem_layer_rowdot_bwd_f32": (_I, [_P, _L, _P, _P, _P, _F, _P, _P, _L, _I, _I, _P, _S, _P]),
+    "mlqem_layer_colstats_record_bf16": (_I, [_I, _P, _P, _P, _L, _P, _P, _P, _P, _I, _F, _U, _P, _L, _I, _P, _P, _P, _P, _S, _P]),
+    "mlqem_layer_colstats_record_f32": (_I, [_I, _P, _P, _P, _L, _P, _P, _P, _P, _I, _F, _U, _P, _L, _I, _P, _P, _P, _P, _S, _P]),
+    "mlqem_layer_colstats_merge": (_I, [_I, _P, _I, _I, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P]),
     "mlqem_linear_bwd_fused_f32": (_I, [_P, _L, _P, _L, _P, _L, _P, _I, _F, _P, _L, _P, _P, _L, _I, _I, _P, _S, _P]),
     "mlqem_pooled_head_f32": (_I, [_P, _L, _I, _P, _L, _P]),
     "mlqem_pooled_head_bwd_f32": (_I, [_P, _P, _L, _L, _I, _P, _P, _P, _P, _P]),
@@ -122,6 +125,9 @@ SIGNATURES = {
     "mlqem_batch_norm_workspace_bytes": (_S, [_L, _I]),
     "mlqem_batch_norm_train_f32": (_I, [_P, _L, _L, _I, _P, _P, _F, _P, _L, _P, _P, _P, _P, _S, _P]),
     "mlqem_batch_norm_train_bwd_f32": (_I, [_P, _L, _P, _L, _L, _I, _P, _P, _P, _P, _L, _P, _P, _P, _S, _P]),
+    "mlqem_batch_norm_sync_record_f32": (_I, [_I, _P, _L, _P, _L, _P, _P, _L, _I, _P, _P, _P, _P, _S, _P]),
+    "mlqem_batch_norm_sync_train_f32": (_I, [_P, _I, _P, _L, _L, _I, _P, _P, _F, _P, _L, _P, _P, _P, _P, _P, _F, _P, _P, _S, _P]),
+    "mlqem_batch_norm_sync_train_bwd_f32": (_I, [_P, _I, _P, _L, _P, _L, _L, _I, _P, _P, _P, _P, _L, _P, _S, _P]),
     "mlqem_asap_coarsen_lists_workspace_bytes": (_S, [_L, _L, _L, _L]),
     "mlqem_asap_coarsen_lists_max_k": (_I, []),
     "mlqem_asap_coarsen_lists_caps": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _L, _P, _P, _S, _P]),
@@ -182,7 +188,7 @@ SIGNATURES = {
 _lib = None
 ERR_UNSUPPORTED = -2   # MLQEM_ERR_UNSUPPORTED: a shape this kernel does not serve
 ERR_WORKSPACE = -4   # MLQEM_ERR_WORKSPACE: a caller-provided buffer is too small (the encoder then says what it needs)
-ABI_VERSION = 43   # MLQEM_ABI_VERSION of include/mlqem_hip.h; bumped whenever a signature changes
+ABI_VERSION = 44   # MLQEM_ABI_VERSION of include/mlqem_hip.h; bumped whenever a signature changes
 
 
 def load() -> ctypes.CDLL:

@@ -156,6 +156,49 @@ def mlp1(x, w1, b1, w2, b2, mfma="f32"):
     return _MLP1.apply(x, w1, b1, w2, b2, mfma == "bf16")
 
 
+def sync_group(bn):
+    """The process group whose ranks share ``bn``'s batch statistics, or None (per-rank statistics, the default): ``bn.process_group``
+    (None means WORLD) when ``bn`` is a ``torch.nn.SyncBatchNorm``, torch.distributed is initialised and the group has more than
+    one rank."""
+    if not isinstance(bn, torch.nn.SyncBatchNorm):
+        return None
+    dist = torch.distributed
+    if not (dist.is_available() and dist.is_initialized()):
+        return None
+    group = bn.process_group if bn.process_group is not None else dist.group.WORLD
+    return group if dist.get_world_size(group) > 1 else None
+
+
+def _shared_records(group, width, device, fill):
+    """ONE collective per synced BatchNorm and direction: a zeroed float64 [world, width] buffer, this rank's record written into
+    its row by ``fill(row)``, all-reduced with SUM.  A sum of one value and zeros is exact in any order, so every rank receives
+    the same records bit for bit (gloo and RCCL alike) and computes the same statistics and running buffers."""
+    dist = torch.distributed
+    buf = torch.zeros((dist.get_world_size(group), width), dtype=torch.float64, device=device)
+    out = fill(buf[dist.get_rank(group)])
+    dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)
+    return buf, out
+
+
+def _colstats_fwd(y, gamma, beta, eps, n, c, running, group):
+    """layer_colstats_fwd, or with a process group its synced form: record -> all-reduce -> merge (statistics of all ranks' rows)."""
+    if group is None:
+        return ops.layer_colstats_fwd(y, gamma, beta, eps, n, c, running=running)
+    recs, _ = _shared_records(group, 2 * c + 1, y.device, lambda row: ops.layer_colstats_record(0, y, row, n, c))
+    return ops.layer_colstats_merge(0, recs, c, gamma, beta, eps, running=running)
+
+
+def _colstats_bwd(g, y, scale, shift, mean, invstd, gamma, drop_p, seed, n, c, group):
+    """layer_colstats_bwd (ReLU blocks), or with a process group its synced form: dbeta / dgamma stay this rank's sums, k1 / k2 are
+    the sums of all ranks over the global row count."""
+    if group is None:
+        return ops.layer_colstats_bwd(g, y, scale, shift, mean, invstd, gamma, True, drop_p, seed, n, c)
+    recs, (db, dg) = _shared_records(group, 2 * c + 1, y.device, lambda row: ops.layer_colstats_record(
+        1, y, row, n, c, g=g, scale=scale, shift=shift, mean=mean, invstd=invstd, relu=True, drop_p=drop_p, seed=seed))
+    gs, k1, k2 = ops.layer_colstats_merge(1, recs, c, gamma, invstd=invstd)
+    return db, dg, gs, k1, k2
+
+
 class _MLPTrunkBf16(Function):
     """MLP2 / MLP3 in training mode with bf16 storage (csrc/mlp_layers.hip): fc1 -> bn1 -> relu -> drop -> fc2 -> bn2 -> relu -> drop
     (+ residual) -> [fc3 -> relu -> drop -> fc4 | fc3], one autograd node.  Every activation it writes or saves is a [N, 128]
@@ -166,15 +209,16 @@ class _MLPTrunkBf16(Function):
     def forward(ctx, x, cfg, w1, b1, g1, be1, w2, b2, g2, be2, w3, b3, w4, b4, run1=None, run2=None):
         eps1, eps2, p_trunk, p_tail, seeds = cfg[:5]
         f32 = ctx.f32 = len(cfg) > 5 and bool(cfg[5])      # fp32 storage (mfma = "f32"): the same graph on the _f32 entry points
+        grp1, grp2 = cfg[6] if len(cfg) > 6 else (None, None)      # process groups of synced BatchNorms (None: per-rank statistics)
         gemm = ctx.gemm = (ops.layer_gemm_f32 if f32 else ops.layer_gemm_bf16)
         n, i = x.shape
         h = w1.shape[0]
         xin = x if x.dtype == torch.bfloat16 else ops._mlp1_x(x)
         y1 = gemm(xin, w1.contiguous(), b1)
-        m1, v1, is1, sc1, sh1 = ops.layer_colstats_fwd(y1, g1, be1, eps1, n, h, running=run1)
+        m1, v1, is1, sc1, sh1 = _colstats_fwd(y1, g1, be1, eps1, n, h, run1, grp1)
         x1 = ops.layer_act_bf16(y1, sc1, sh1, n, h, True, p_trunk, seeds[0])
         y2 = gemm(x1, w2.contiguous(), b2)
-        m2, v2, is2, sc2, sh2 = ops.layer_colstats_fwd(y2, g2, be2, eps2, n, h, running=run2)
+        m2, v2, is2, sc2, sh2 = _colstats_fwd(y2, g2, be2, eps2, n, h, run2, grp2)
         s = ops.layer_act_bf16(y2, sc2, sh2, n, h, True, p_trunk, seeds[1], res=x1)
         if w4 is None:                      # MLP2: out = fc3(s)
             out = ops.layer_rowdot_bf16(s, w3.contiguous(), b3, n)
@@ -195,6 +239,7 @@ class _MLPTrunkBf16(Function):
     def backward(ctx, gout, *_):
         xin, y1, x1, y2, s, y3, h3, w1, w2, w3, w4, g1, g2, m1, is1, sc1, sh1, m2, is2, sc2, sh2 = ctx.saved_tensors
         eps1, eps2, p_trunk, p_tail, seeds = ctx.cfg[:5]
+        grp1, grp2 = ctx.cfg[6] if len(ctx.cfg) > 6 else (None, None)
         n, i, h = ctx.dims
         gemm, wgrad = ctx.gemm, (ops.layer_wgrad_f32 if ctx.f32 else ops.layer_wgrad_bf16)
         gout = ops.rowmajor(gout)
@@ -212,12 +257,12 @@ class _MLPTrunkBf16(Function):
             gw3, gb3 = wgrad(dy3, s, h3w, h)
             gs = gemm(dy3, w3.contiguous(), transposed=True)
         # block 2: s = x1 + drop(relu(bn2(fc2 x1)))
-        db2, dg2, gs2, k1, k2 = ops.layer_colstats_bwd(gs, y2, sc2, sh2, m2, is2, g2, True, p_trunk, seeds[1], n, h)
+        db2, dg2, gs2, k1, k2 = _colstats_bwd(gs, y2, sc2, sh2, m2, is2, g2, p_trunk, seeds[1], n, h, grp2)
         dy2 = ops.layer_bwd_apply_bf16(gs, y2, sc2, sh2, m2, is2, gs2, k1, k2, n, h, True, p_trunk, seeds[1])
         gw2, gb2 = wgrad(dy2, x1, h, h)
         gx1 = gemm(dy2, w2.contiguous(), transposed=True, add=gs)       # + the residual path
         # block 1: x1 = drop(relu(bn1(fc1 x)))
-        db1, dg1, gs1, k1, k2 = ops.layer_colstats_bwd(gx1, y1, sc1, sh1, m1, is1, g1, True, p_trunk, seeds[0], n, h)
+        db1, dg1, gs1, k1, k2 = _colstats_bwd(gx1, y1, sc1, sh1, m1, is1, g1, p_trunk, seeds[0], n, h, grp1)
         dy1 = ops.layer_bwd_apply_bf16(gx1, y1, sc1, sh1, m1, is1, gs1, k1, k2, n, h, True, p_trunk, seeds[0])
         gw1, gb1 = wgrad(dy1, xin, h, i)
         if not ctx.x_needs_grad:
@@ -232,7 +277,12 @@ class _MLPTrunkBf16(Function):
 def mlp_trunk_bf16_ok(x, fc1, fc2, fc3, fc4, bn1, bn2) -> bool:
     """Whether the layer pipeline (csrc/mlp_layers.hip, either storage) takes this call: widths inside the kernels' limits, affine
     BatchNorm with a momentum."""
-    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and x.shape[0] >= 2):
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32):
+        return False
+    synced = [sync_group(bn) is not None for bn in (bn1, bn2)]
+    if any(synced) and x.shape[0] == 0:
+        raise ValueError("SyncBatchNorm: this rank holds no rows (every rank needs at least one)")
+    if x.shape[0] < (1 if all(synced) else 2):      # synced statistics need two rows over all ranks, not on each
         return False
     i, h = fc1.weight.shape[1], fc1.weight.shape[0]
     last = fc3 if fc4 is None else fc4
@@ -248,8 +298,12 @@ def mlp_trunk_bf16_ok(x, fc1, fc2, fc3, fc4, bn1, bn2) -> bool:
 
 def mlp_trunk_bf16(x, fc1, bn1, fc2, bn2, fc3, fc4, p_trunk, p_tail, seeds, f32=False):
     """Runs the block and updates the BatchNorm running statistics like torch (momentum, unbiased variance, batch counter).
-    ``f32``: fp32 storage and unrounded operands (mfma = "f32") instead of bfloat16."""
+    ``f32``: fp32 storage and unrounded operands (mfma = "f32") instead of bfloat16.  A ``torch.nn.SyncBatchNorm`` in a process group
+    of several ranks (``sync_group``) normalises with the statistics of all ranks' rows, forward and backward."""
     cfg = (float(bn1.eps), float(bn2.eps), float(p_trunk), float(p_tail), tuple(int(v) for v in seeds), bool(f32))
+    groups = (sync_group(bn1), sync_group(bn2))
+    if groups != (None, None):
+        cfg += (groups,)
     w4, b4 = (None, None) if fc4 is None else (fc4.weight, fc4.bias)
     # BatchNorm1d's buffer update rides in the statistics launches (running mean / unbiased variance / batch counter)
     runs = [((bn.running_mean, bn.running_var, float(bn.momentum), bn.num_batches_tracked)
@@ -295,13 +349,46 @@ class _BatchNormTrain(Function):
         return dx, dgamma, dbeta, None
 
 
+class _SyncBatchNormTrain(Function):
+    """``_BatchNormTrain`` with the statistics of every rank of ``group`` (torch.nn.SyncBatchNorm): column sums -> record -> one
+    all-reduce -> merge, in the forward and again in the backward.  The running buffers are updated by the forward's merge, with
+    the global row count."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps, running, group):
+        x = ops.rowmajor(x)
+        c = x.shape[1]
+        recs, _ = _shared_records(group, 2 * c + 1, x.device, lambda row: ops.batch_norm_sync_record(0, x, row))
+        y, mean, var, invstd = ops.batch_norm_sync_train(recs, x, gamma, beta, eps, running=running)
+        ctx.group = group
+        ctx.save_for_backward(x, gamma, mean, invstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, gamma, mean, invstd = ctx.saved_tensors
+        gy = ops.rowmajor(gy)
+        recs, (dgamma, dbeta) = _shared_records(ctx.group, 2 * x.shape[1] + 1, x.device,
+                                                lambda row: ops.batch_norm_sync_record(1, x, row, dy=gy, mean=mean, invstd=invstd))
+        dx = ops.batch_norm_sync_train_bwd(recs, gy, x, gamma, mean, invstd)
+        return dx, dgamma, dbeta, None, None, None
+
+
 def batch_norm_train(x, bn):
     """``bn(x)`` for a ``torch.nn.BatchNorm1d`` in training mode over [N, C] rows, running statistics updated as torch does
     (momentum, unbiased variance, num_batches_tracked).  Falls back to the module itself for what the kernels do not cover
-    (no affine parameters, cumulative-average momentum, C > 256, a single row)."""
+    (no affine parameters, cumulative-average momentum, C > 256, a single row).  A ``torch.nn.SyncBatchNorm`` in a process group
+    of several ranks (``sync_group``) gets the statistics of all ranks' rows (a single row per rank is then enough)."""
     n, c = x.shape
-    if bn.weight is None or bn.momentum is None or c > 256 or n < 2 or not x.is_cuda:
+    group = sync_group(bn)
+    if bn.weight is None or bn.momentum is None or c > 256 or not x.is_cuda or (n < 2 and group is None):
         return bn(x)
+    if group is not None:
+        if n == 0:
+            raise ValueError("SyncBatchNorm: this rank holds no rows (every rank needs at least one)")
+        runs = ((bn.running_mean, bn.running_var, float(bn.momentum), bn.num_batches_tracked)
+                if bn.track_running_stats and bn.running_mean is not None else None)
+        return _SyncBatchNormTrain.apply(x, bn.weight, bn.bias, float(bn.eps), runs, group)
     y, mean, var = _BatchNormTrain.apply(x, bn.weight, bn.bias, bn.eps)
     if bn.track_running_stats and bn.running_mean is not None:
         with torch.no_grad():

@@ -851,6 +851,43 @@ def layer_colstats_bwd(g, y, scale, shift, mean, invstd, gamma, relu, drop_p, se
     return o
 
 
+def layer_colstats_record(mode, y, record, n, c, g=None, scale=None, shift=None, mean=None, invstd=None, relu=True, drop_p=0.0, seed=0):
+    """This rank's record of a synced BatchNorm block (``record``: a float64 [2 c + 1] device view, written by the launch).  mode 0:
+    (n, mean, M2) of ``y``; mode 1: (n, sum gu, sum gu xhat) of the incoming gradient ``g`` with the global ``mean`` / ``invstd``,
+    and returns this rank's (dbeta, dgamma) ([128] each)."""
+    dev = y.device
+    ws, need = _layer_ws(dev)
+    if not (record.is_cuda and record.dtype == torch.float64 and record.is_contiguous() and record.numel() == 2 * c + 1):
+        raise ValueError("layer_colstats_record: record must be a contiguous float64 [2 c + 1] device tensor")
+    db = dg = None
+    ga = g32 = None
+    ld = 0
+    if mode == 1:
+        db, dg = torch.empty((2, LAYER_W), dtype=torch.float32, device=dev).unbind(0)
+        ga, g32, ld = _grad_operand(g, y, n, c)
+    name = "mlqem_layer_colstats_record_" + _sfx(y.dtype == torch.float32)
+    code = getattr(_lib.load(), name)(mode, _p(y), _p(ga), _p(g32), ld, _p(scale), _p(shift), _p(mean), _p(invstd), 1 if relu else 0,
+                                      *_seed_args(drop_p, seed), n, c, _p(record), _p(db), _p(dg), _p(ws), need, _stream())
+    _lib.check(code, name)
+    return db, dg
+
+
+def layer_colstats_merge(mode, records, c, gamma, beta=None, eps=0.0, invstd=None, running=None):
+    """The all-reduced records [world, 2 c + 1] of a synced block -> mode 0: (mean, var, invstd, scale, shift), the running buffers
+    (``running`` as in layer_colstats_fwd) updated with the global row count; mode 1: (gs, k1, k2).  Each [128], zeros beyond c."""
+    dev = records.device
+    if not (records.is_cuda and records.dtype == torch.float64 and records.is_contiguous() and records.dim() == 2
+            and records.shape[1] == 2 * c + 1):
+        raise ValueError("layer_colstats_merge: records must be a contiguous float64 [world, 2 c + 1] device tensor")
+    o = list(torch.empty((5 if mode == 0 else 3, LAYER_W), dtype=torch.float32, device=dev).unbind(0))
+    rm, rv, mo, nbt = running if running is not None else (None, None, 0.0, None)
+    outs = o if mode == 0 else [None, None] + o
+    code = _lib.load().mlqem_layer_colstats_merge(mode, _p(records), records.shape[0], c, _p(gamma), _p(beta), _p(invstd), float(eps),
+                                                  *[_p(t) for t in outs], _p(rm), _p(rv), float(mo), _p(nbt), _stream())
+    _lib.check(code, "mlqem_layer_colstats_merge")
+    return o
+
+
 def layer_act_bf16(y, scale, shift, n, c, relu=True, drop_p=0.0, seed=0, res=None):
     """drop(relu(y scale + shift)) (+ res) as a new activation in y's storage."""
     f32 = y.dtype == torch.float32
@@ -1640,6 +1677,58 @@ def batch_norm_train_bwd(dy, x, gamma, mean, invstd):
                                               _p(dx), _mat(dx, "dx"), _p(dgamma), _p(dbeta), _p(ws), need, _stream())
     _lib.check(code, "mlqem_batch_norm_train_bwd_f32")
     return dx, dgamma, dbeta
+
+
+def batch_norm_sync_record(mode, x, record, dy=None, mean=None, invstd=None):
+    """This rank's record of a synced BatchNorm1d (mlqem_batch_norm_sync_record_f32) into ``record`` (float64 [2 C + 1] on the
+    device).  mode 0: (n, mean, M2) of x; mode 1: (n, sum dy, sum dy xhat) with the global mean / invstd, and returns this rank's
+    (dgamma, dbeta)."""
+    n, c = x.shape
+    dev = x.device
+    if not (record.is_cuda and record.dtype == torch.float64 and record.is_contiguous() and record.numel() == 2 * c + 1):
+        raise ValueError("batch_norm_sync_record: record must be a contiguous float64 [2 C + 1] device tensor")
+    dgamma = dbeta = None
+    if mode == 1:
+        dgamma, dbeta = (torch.empty(c, dtype=torch.float32, device=dev) for _ in range(2))
+    lib = _lib.load()
+    need = lib.mlqem_batch_norm_workspace_bytes(n, c)
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    code = lib.mlqem_batch_norm_sync_record_f32(mode, _p(x), _mat(x, "x"), _p(dy), _mat(dy, "dy") if dy is not None else 0, _p(mean),
+                                                _p(invstd), n, c, _p(record), _p(dgamma), _p(dbeta), _p(ws), need, _stream())
+    _lib.check(code, "mlqem_batch_norm_sync_record_f32")
+    return dgamma, dbeta
+
+
+def batch_norm_sync_train(records, x, gamma, beta, eps, running=None):
+    """y, mean, biased var, invstd of x's rows under the statistics of all ranks (the all-reduced ``records`` [world, 2 C + 1]);
+    ``running`` = (running_mean, running_var, momentum, num_batches_tracked | None) is updated with the global row count."""
+    n, c = x.shape
+    dev = x.device
+    y = padded_empty(n, c, dev)
+    mean, var, invstd = (torch.empty(c, dtype=torch.float32, device=dev) for _ in range(3))
+    rm, rv, mo, nbt = running if running is not None else (None, None, 0.0, None)
+    lib = _lib.load()
+    need = lib.mlqem_batch_norm_workspace_bytes(n, c)
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    code = lib.mlqem_batch_norm_sync_train_f32(_p(records), records.shape[0], _p(x), _mat(x, "x"), n, c, _p(gamma), _p(beta), float(eps),
+                                               _p(y), _mat(y, "y"), _p(mean), _p(var), _p(invstd), _p(rm), _p(rv), float(mo), _p(nbt),
+                                               _p(ws), need, _stream())
+    _lib.check(code, "mlqem_batch_norm_sync_train_f32")
+    return y, mean, var, invstd
+
+
+def batch_norm_sync_train_bwd(records, dy, x, gamma, mean, invstd):
+    """dx of a synced BatchNorm1d from the all-reduced backward ``records`` [world, 2 C + 1]."""
+    n, c = x.shape
+    dev = x.device
+    dx = padded_empty(n, c, dev)
+    lib = _lib.load()
+    need = lib.mlqem_batch_norm_workspace_bytes(n, c)
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    code = lib.mlqem_batch_norm_sync_train_bwd_f32(_p(records), records.shape[0], _p(dy), _mat(dy, "dy"), _p(x), _mat(x, "x"), n, c,
+                                                   _p(gamma), _p(mean), _p(invstd), _p(dx), _mat(dx, "dx"), _p(ws), need, _stream())
+    _lib.check(code, "mlqem_batch_norm_sync_train_bwd_f32")
+    return dx
 
 
 def asap_dense_max_k() -> int:

@@ -8,10 +8,14 @@ their epilogues wherever the maths allows:
   over weights scaled by ``gamma / sqrt(running_var + eps)`` (folded on the fly from the live parameters: four [H]-sized
   ops instead of three [batch, H] passes);
 * train mode: BatchNorm needs the batch statistics of the GEMM output (``F.batch_norm_train``: the column reductions and
-  element-wise passes of csrc/bn.hip -- torch's kernels take 27 ms per layer and direction at 262 k rows; per-rank statistics
-  under data parallelism exactly like ``DistributedDataParallel`` without ``SyncBatchNorm``; running statistics are
-  broadcast from rank 0 once by ``Trainer``); ReLU, dropout and the residual add of the trunk are one fused launch
-  (``F.relu_dropout_add``), its mask keyed by torch's seed like every dropout of this build.
+  element-wise passes of csrc/bn.hip -- torch's kernels take 27 ms per layer and direction at 262 k rows); ReLU, dropout and
+  the residual add of the trunk are one fused launch (``F.relu_dropout_add``), its mask keyed by torch's seed like every
+  dropout of this build.  Under data parallelism each rank normalises with the statistics of its own rows by default, as
+  ``DistributedDataParallel`` does (running buffers broadcast from rank 0 once, by ``Trainer``).  After
+  ``torch.nn.SyncBatchNorm.convert_sync_batchnorm(model)`` -- before the trainer is built -- ``bn1`` / ``bn2`` use the statistics
+  of all ranks' rows, forward and backward, with torch's SyncBatchNorm semantics (``F.sync_group``: one all-reduce of per-rank
+  records per BatchNorm and direction, csrc/bn_sync.hpp), and every rank keeps the same running buffers.  State-dict keys do
+  not change.
 
 ``model.mfma = "bf16"`` (default ``"f32"``) sends the GEMMs -- forward, data gradient and weight gradient -- to the bf16
 matrix cores (v_mfma_f32_16x16x32_bf16): operands rounded to bf16, fp32 accumulation, fp32 master weights -- the "bf16 MFMA MLP

@@ -7,6 +7,11 @@ loss, batch 32 by default -- with three MI355X-side changes that do not alter th
 * the loss is accumulated on the device (the reference calls ``loss.item()`` every step: a host sync),
 * under ``torch.distributed`` each rank trains on its shard and gradients are averaged with ONE all-reduce
   over a flat fp32 buffer (RCCL over xGMI on MI355X, gloo in the CPU tests).
+
+BatchNorm heads (MLP2 / MLP3) normalise with per-rank batch statistics under data parallelism by default, as
+``DistributedDataParallel`` does.  ``model = torch.nn.SyncBatchNorm.convert_sync_batchnorm(model)`` -- run BEFORE the trainer is
+constructed, as with DDP -- gives them the statistics of all ranks' rows (one all-reduce per BatchNorm in the forward and one in
+the backward); such a step runs eagerly under data parallelism (see ``BucketedTrainer.eager_reason``).
 """
 from __future__ import annotations
 
@@ -457,7 +462,7 @@ class RowsTrainer(Trainer):
         tensor the next step of the same shape overwrites: read or clone it before stepping again)."""
         from .native import ops
 
-        if not self.graphs or self.distributed:      # under data parallelism the collective sits inside the step: eager
+        if not self.graphs or self.distributed:      # under data parallelism the collectives sit inside the step (a SyncBatchNorm's too): eager
             # the rows in the padded layout the captured step reads them in: the same kernels, the same sums, the same bits
             return self._step_on(self._Rows(ops._mlp1_x(x) if x.dtype == torch.float32 else x, y))
 
@@ -629,6 +634,15 @@ class BucketedTrainer(Trainer):
         self.split = bool(split_update) or self.distributed
         self.capture_collective = bool(capture_collective) and self.distributed and torch.distributed.get_backend() == "nccl"
         self.collective_in_graph, self.collective_capture_error = None, None
+        # A SyncBatchNorm head in a group of several ranks all-reduces its statistics inside the forward and the backward: such a step
+        # is not captured (collectives in the step graph are out of reach over gloo) and runs eagerly.  ``eager_reason`` says why a
+        # trainer with ``graphs=True`` steps eagerly (None: it captures).
+        from .native import functional as _F
+
+        self.eager_reason = None
+        if any(_F.sync_group(m) is not None for m in model.modules()):
+            self.eager_reason = "SyncBatchNorm: statistics all-reduced inside the forward and the backward"
+            self.collective_in_graph = False
         if not arena.filler_nodes:
             raise ValueError("BucketedTrainer needs an arena built with filler_nodes > 0")
         if node_quantum > arena.filler_nodes:
@@ -788,6 +802,8 @@ class BucketedTrainer(Trainer):
             eager = first_sight or len(self._entries) >= self.max_pattern_captures
         if self.graphs and entry is None and self.stable and len(self._entries) >= self.max_pattern_captures:
             eager = True                 # a rare bucket beyond the capture budget (each capture holds a graph and a pinned ring)
+        if self.eager_reason is not None:
+            eager = True
         if eager:
             packed = torch.from_numpy(host).to(self.flat_param.device, non_blocking=True)
             return self._step_on(packed, len(sel), nb, eb, sizes, real, cap, plan)

@@ -11,6 +11,7 @@
 // summed in a fixed order in double precision by a finish kernel, one wave per column: deterministic, no atomics) and an
 // element-wise pass.  torch's kernels for this shape (N = 262 144, C = 125) take 7 ms (Welford reduction) and 20 ms (backward)
 // on an MI355X -- 94 % of an MLP3 train step; these take 0.1-0.2 ms each, the time of their 2-3 passes over the matrix.
+#include "bn_sync.hpp"
 #include "common.hpp"
 
 namespace mlqem {
@@ -198,5 +199,80 @@ extern "C" int mlqem_batch_norm_train_bwd_f32(const float* dy, int64_t ldg, cons
                      invstd, 0.f, dbeta, dgamma, gs, k1, k2);
   hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3((unsigned)ceil_div(N * C, (int64_t)kBlock)), dim3(kBlock), 0, stream, dy, ldg,
                      x, ldx, mean, invstd, gs, k1, k2, N, C, dx, lddx);
+  return launch_status();
+}
+
+// ---- synced statistics (torch.nn.SyncBatchNorm over a process group; bn_sync.hpp): record -> the caller's all-reduce -> merge + apply
+
+// mode 0: this rank's forward record of x.  mode 1: its backward record of (dy, x) with the GLOBAL mean / invstd, and its local
+// dgamma / dbeta.  record: 2 C + 1 doubles.
+extern "C" int mlqem_batch_norm_sync_record_f32(int mode, const float* x, int64_t ldx, const float* dy, int64_t ldg, const float* mean,
+                                                const float* invstd, int64_t N, int C, double* record, float* dgamma, float* dbeta,
+                                                void* workspace, size_t workspace_bytes, mlqem_stream_t stream_) {
+  begin_launches();
+  hipStream_t stream = as_stream(stream_);
+  if ((mode != 0 && mode != 1) || N <= 0 || C <= 0 || ldx < C || !x || !record) return MLQEM_ERR_BAD_ARG;
+  if (C > kBnMaxChunks * kBnLanes) return MLQEM_ERR_UNSUPPORTED;
+  if (mode == 1 && (!dy || ldg < C || !mean || !invstd || !dgamma || !dbeta)) return MLQEM_ERR_BAD_ARG;
+  if (!workspace || workspace_bytes < mlqem_batch_norm_workspace_bytes(N, C)) return MLQEM_ERR_WORKSPACE;
+  const int nb = bn_blocks(N);
+  float* partial = static_cast<float*>(workspace);
+  const int64_t rpb = ceil_div(N, (int64_t)nb);
+  if (mode == 0) {
+    hipLaunchKernelGGL(bn_column_sums_kernel<0>, dim3((unsigned)nb), dim3(kBlock), 0, stream, x, ldx, (const float*)nullptr, (int64_t)0,
+                       (const float*)nullptr, (const float*)nullptr, N, C, rpb, partial);
+    hipLaunchKernelGGL(bn_sync_record_kernel<0>, dim3((unsigned)C), dim3(kSyncThreads), 0, stream, partial, nb, C, N, C,
+                       x /* the shift: row 0 */, record, (float*)nullptr, (float*)nullptr);
+  } else {
+    hipLaunchKernelGGL(bn_column_sums_kernel<1>, dim3((unsigned)nb), dim3(kBlock), 0, stream, dy, ldg, x, ldx, mean, invstd, N, C, rpb,
+                       partial);
+    hipLaunchKernelGGL(bn_sync_record_kernel<1>, dim3((unsigned)C), dim3(kSyncThreads), 0, stream, partial, nb, C, N, C,
+                       (const float*)nullptr, record, dbeta, dgamma);
+  }
+  return launch_status();
+}
+
+// records [world][2 C + 1] -> mean, var, invstd of the union of the ranks' rows, y = x scale + shift for this rank's rows, and the
+// running buffers (when given) updated with the global row count.
+extern "C" int mlqem_batch_norm_sync_train_f32(const double* records, int world, const float* x, int64_t ldx, int64_t N, int C,
+                                               const float* gamma, const float* beta, float eps, float* y, int64_t ldy, float* mean,
+                                               float* var, float* invstd, float* running_mean, float* running_var, float momentum,
+                                               int64_t* num_batches_tracked, void* workspace, size_t workspace_bytes,
+                                               mlqem_stream_t stream_) {
+  begin_launches();
+  hipStream_t stream = as_stream(stream_);
+  if (!records || world < 1 || N <= 0 || C <= 0 || ldx < C || ldy < C) return MLQEM_ERR_BAD_ARG;
+  if (C > kBnMaxChunks * kBnLanes) return MLQEM_ERR_UNSUPPORTED;
+  if (!x || !y || !mean || !var || !invstd || ((running_mean == nullptr) != (running_var == nullptr))) return MLQEM_ERR_BAD_ARG;
+  if (!workspace || workspace_bytes < mlqem_batch_norm_workspace_bytes(N, C)) return MLQEM_ERR_WORKSPACE;
+  float* scale = static_cast<float*>(workspace) + (size_t)bn_blocks(N) * 2 * C;
+  float* shift = scale + C;
+  hipLaunchKernelGGL(bn_sync_merge_kernel<0>, dim3((unsigned)ceil_div(C, (int64_t)kSyncThreads)), dim3(kSyncThreads), 0, stream, records,
+                     world, C, C, gamma, beta, (const float*)nullptr, eps, mean, var, invstd, scale, shift, running_mean, running_var,
+                     momentum, reinterpret_cast<long long*>(num_batches_tracked));
+  hipLaunchKernelGGL(bn_affine_kernel, dim3((unsigned)ceil_div(N * C, (int64_t)kBlock)), dim3(kBlock), 0, stream, x, ldx, scale, shift,
+                     N, C, y, ldy);
+  return launch_status();
+}
+
+// records [world][2 C + 1] of the backward -> dx = gamma invstd (dy - sum dbeta / N - xhat sum dgamma / N) for this rank's rows.
+extern "C" int mlqem_batch_norm_sync_train_bwd_f32(const double* records, int world, const float* dy, int64_t ldg, const float* x,
+                                                   int64_t ldx, int64_t N, int C, const float* gamma, const float* mean,
+                                                   const float* invstd, float* dx, int64_t lddx, void* workspace, size_t workspace_bytes,
+                                                   mlqem_stream_t stream_) {
+  begin_launches();
+  hipStream_t stream = as_stream(stream_);
+  if (!records || world < 1 || N <= 0 || C <= 0 || ldg < C || ldx < C || lddx < C) return MLQEM_ERR_BAD_ARG;
+  if (C > kBnMaxChunks * kBnLanes) return MLQEM_ERR_UNSUPPORTED;
+  if (!dy || !x || !mean || !invstd || !dx) return MLQEM_ERR_BAD_ARG;
+  if (!workspace || workspace_bytes < mlqem_batch_norm_workspace_bytes(N, C)) return MLQEM_ERR_WORKSPACE;
+  float* gs = static_cast<float*>(workspace) + (size_t)bn_blocks(N) * 2 * C;
+  float* k1 = gs + C;
+  float* k2 = k1 + C;
+  hipLaunchKernelGGL(bn_sync_merge_kernel<1>, dim3((unsigned)ceil_div(C, (int64_t)kSyncThreads)), dim3(kSyncThreads), 0, stream, records,
+                     world, C, C, gamma, (const float*)nullptr, invstd, 0.f, (float*)nullptr, (float*)nullptr, gs, k1, k2,
+                     (float*)nullptr, (float*)nullptr, 0.f, (long long*)nullptr);
+  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3((unsigned)ceil_div(N * C, (int64_t)kBlock)), dim3(kBlock), 0, stream, dy, ldg, x, ldx,
+                     mean, invstd, gs, k1, k2, N, C, dx, lddx);
   return launch_status();
 }

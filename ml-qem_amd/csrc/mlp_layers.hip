@@ -19,6 +19,7 @@
 // recomputes them, nothing is stored.
 #include <type_traits>
 
+#include "bn_sync.hpp"
 #include "common.hpp"
 
 namespace mlqem {
@@ -1336,6 +1337,29 @@ extern "C" int mlqem_layer_gemm_bf16(const void* x, int x_is_bf16, int64_t ldx, 
   return launch_layer_fwd<6, false>(a, workspace, s);
 }
 
+// Stage one of colstats / colstats_record: the per-workgroup column sums of mode 0 (y, shifted by row 0, which workgroup 0 files
+// behind the partials) or mode 1 (gu, gu xhat) into ``partial``.  Returns the number of workgroups.
+template <typename ST>
+static int layer_colsum(int mode, const void* y, const void* g, const float* g32, int64_t ldg32, const float* scale, const float* shift,
+                        const float* mean, const float* invstd, int relu, float drop_p, uint64_t seed, const uint64_t* seed_counter,
+                        int64_t N, int C, float* partial, hipStream_t s) {
+  int nb = colsum_blocks(N);
+  {   // a fixed partition of the rows over the workgroups: a whole number of resident rounds (the backward sums fit five workgroups
+      // per CU: 2048 of them ran as one round and a second one at 60 % of the occupancy)
+    static const int r0 = layer_resident(layer_colsum_kernel<0, ST>, 256, 0), r1 = layer_resident(layer_colsum_kernel<1, ST>, 256, 0);
+    const int res = mode == 0 ? r0 : r1;
+    if (nb > res) nb = nb / res * res;
+  }
+  ActArgs a{};
+  a.y = y; a.g = g; a.g32 = g32; a.ldg32 = ldg32;
+  a.scale = scale; a.shift = shift; a.mean = mean; a.invstd = invstd; a.partial = partial;
+  a.N = N; a.C = C; a.relu = relu; a.drop_p = drop_p; a.seed = seed; a.seed_counter = seed_counter;
+  a.rows_per_block = ceil_div(N, (int64_t)nb);
+  if (mode == 0) hipLaunchKernelGGL((layer_colsum_kernel<0, ST>), dim3(nb), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((layer_colsum_kernel<1, ST>), dim3(nb), dim3(256), 0, s, a);
+  return nb;
+}
+
 // mode 0: batch statistics of y -> mean, var, invstd, scale, shift (each [128]; gamma / beta [C]).
 // mode 1: backward sums from (g, y) -> dbeta, dgamma, gs, k1, k2.  g: bf16 [N,128], or fp32 [N, ldg32] when g32 != NULL.
 template <typename ST>
@@ -1350,26 +1374,15 @@ static int layer_colstats(int mode, const void* y, const void* g, const float* g
   if (mode == 0 ? !beta : (!scale || !shift || !mean || !invstd || (!g && !g32))) return MLQEM_ERR_BAD_ARG;
   if (!workspace || workspace_bytes < mlqem_layer_workspace_bytes()) return MLQEM_ERR_WORKSPACE;
   hipStream_t s = as_stream(stream);
-  int nb = colsum_blocks(N);
-  {   // a fixed partition of the rows over the workgroups: a whole number of resident rounds (the backward sums fit five workgroups
-      // per CU: 2048 of them ran as one round and a second one at 60 % of the occupancy)
-    static const int r0 = layer_resident(layer_colsum_kernel<0, ST>, 256, 0), r1 = layer_resident(layer_colsum_kernel<1, ST>, 256, 0);
-    const int res = mode == 0 ? r0 : r1;
-    if (nb > res) nb = nb / res * res;
-  }
-  ActArgs a{};
-  a.y = y; a.g = g; a.g32 = g32; a.ldg32 = ldg32;
-  a.scale = scale; a.shift = shift; a.mean = mean; a.invstd = invstd; a.partial = static_cast<float*>(workspace);
-  a.N = N; a.C = C; a.relu = relu; a.drop_p = drop_p; a.seed = seed; a.seed_counter = seed_counter;
-  a.rows_per_block = ceil_div(N, (int64_t)nb);
+  float* partial = static_cast<float*>(workspace);
   if (mode == 0) {
-    hipLaunchKernelGGL((layer_colsum_kernel<0, ST>), dim3(nb), dim3(256), 0, s, a);
+    const int nb = layer_colsum<ST>(0, y, g, g32, ldg32, scale, shift, mean, invstd, relu, drop_p, seed, seed_counter, N, C, partial, s);
     if ((running_mean == nullptr) != (running_var == nullptr) || (running_mean && N < 2)) return MLQEM_ERR_BAD_ARG;
-    hipLaunchKernelGGL(layer_finish_kernel<0>, dim3(kLW), dim3(kFinishThreads), 0, s, a.partial, nb, N, C, gamma, beta, (const float*)nullptr, eps,
+    hipLaunchKernelGGL(layer_finish_kernel<0>, dim3(kLW), dim3(kFinishThreads), 0, s, partial, nb, N, C, gamma, beta, (const float*)nullptr, eps,
                        o1, o2, o3, o4, o5, running_mean, running_var, momentum, reinterpret_cast<long long*>(num_batches_tracked));
   } else {
-    hipLaunchKernelGGL((layer_colsum_kernel<1, ST>), dim3(nb), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(layer_finish_kernel<1>, dim3(kLW), dim3(kFinishThreads), 0, s, a.partial, nb, N, C, gamma, (const float*)nullptr, invstd, 0.f,
+    const int nb = layer_colsum<ST>(1, y, g, g32, ldg32, scale, shift, mean, invstd, relu, drop_p, seed, seed_counter, N, C, partial, s);
+    hipLaunchKernelGGL(layer_finish_kernel<1>, dim3(kLW), dim3(kFinishThreads), 0, s, partial, nb, N, C, gamma, (const float*)nullptr, invstd, 0.f,
                        o1, o2, o3, o4, o5, (float*)nullptr, (float*)nullptr, 0.f, (long long*)nullptr);
   }
   return launch_status();
@@ -1387,6 +1400,61 @@ extern "C" int mlqem_layer_colstats_bf16(MLQEM_COLSTATS_ARGS) { return layer_col
 extern "C" int mlqem_layer_colstats_f32(MLQEM_COLSTATS_ARGS) { return layer_colstats<float>(MLQEM_COLSTATS_PASS); }
 #undef MLQEM_COLSTATS_ARGS
 #undef MLQEM_COLSTATS_PASS
+
+// Synced statistics (torch.nn.SyncBatchNorm over a process group; bn_sync.hpp): colstats' two stages with the caller's all-reduce of
+// the records in between.  record: this rank's 2 C + 1 doubles; mode 1 also writes its local dbeta / dgamma ([128], zeros beyond C).
+template <typename ST>
+static int layer_colstats_record(int mode, const void* y, const void* g, const float* g32, int64_t ldg32, const float* scale,
+                                 const float* shift, const float* mean, const float* invstd, int relu, float drop_p, uint64_t seed,
+                                 const uint64_t* seed_counter, int64_t N, int C, double* record, float* dbeta, float* dgamma,
+                                 void* workspace, size_t workspace_bytes, mlqem_stream_t stream) {
+  begin_launches();
+  if ((mode != 0 && mode != 1) || N <= 0 || C < 1 || C > kLW || !y || !record || drop_p < 0.f || drop_p >= 1.f) return MLQEM_ERR_BAD_ARG;
+  if (mode == 1 && (!scale || !shift || !mean || !invstd || (!g && !g32) || !dbeta || !dgamma)) return MLQEM_ERR_BAD_ARG;
+  if (!workspace || workspace_bytes < mlqem_layer_workspace_bytes()) return MLQEM_ERR_WORKSPACE;
+  hipStream_t s = as_stream(stream);
+  float* partial = static_cast<float*>(workspace);
+  const int nb = layer_colsum<ST>(mode, y, g, g32, ldg32, scale, shift, mean, invstd, relu, drop_p, seed, seed_counter, N, C, partial, s);
+  if (mode == 0)
+    hipLaunchKernelGGL(bn_sync_record_kernel<0>, dim3(kLW), dim3(kSyncThreads), 0, s, partial, nb, kLW, N, C,
+                       partial + (int64_t)nb * 2 * kLW /* the shift: row 0, filed behind the partials */, record, (float*)nullptr,
+                       (float*)nullptr);
+  else
+    hipLaunchKernelGGL(bn_sync_record_kernel<1>, dim3(kLW), dim3(kSyncThreads), 0, s, partial, nb, kLW, N, C, (const float*)nullptr, record,
+                       dbeta, dgamma);
+  return launch_status();
+}
+#define MLQEM_RECORD_ARGS                                                                                                           \
+  int mode, const void* y, const void* g, const float* g32, int64_t ldg32, const float* scale, const float* shift, const float* mean,  \
+      const float* invstd, int relu, float drop_p, uint64_t seed, const uint64_t* seed_counter, int64_t N, int C, double* record,       \
+      float* dbeta, float* dgamma, void* workspace, size_t workspace_bytes, mlqem_stream_t stream
+#define MLQEM_RECORD_PASS \
+  mode, y, g, g32, ldg32, scale, shift, mean, invstd, relu, drop_p, seed, seed_counter, N, C, record, dbeta, dgamma, workspace, workspace_bytes, stream
+extern "C" int mlqem_layer_colstats_record_bf16(MLQEM_RECORD_ARGS) { return layer_colstats_record<unsigned short>(MLQEM_RECORD_PASS); }
+extern "C" int mlqem_layer_colstats_record_f32(MLQEM_RECORD_ARGS) { return layer_colstats_record<float>(MLQEM_RECORD_PASS); }
+#undef MLQEM_RECORD_ARGS
+#undef MLQEM_RECORD_PASS
+
+// records [world][2 C + 1] -> colstats' outputs ([128] each, zeros beyond C), for either storage.  mode 0: o1..o5 = mean, var,
+// invstd, scale, shift and the running-buffer update with the global row count.  mode 1: o3..o5 = gs, k1, k2 (o1 / o2: unused).
+extern "C" int mlqem_layer_colstats_merge(int mode, const double* records, int world, int C, const float* gamma, const float* beta,
+                                          const float* invstd, float eps, float* o1, float* o2, float* o3, float* o4, float* o5,
+                                          float* running_mean, float* running_var, float momentum, int64_t* num_batches_tracked,
+                                          mlqem_stream_t stream) {
+  begin_launches();
+  if ((mode != 0 && mode != 1) || !records || world < 1 || C < 1 || C > kLW || !gamma || !o3 || !o4 || !o5) return MLQEM_ERR_BAD_ARG;
+  if (mode == 0 ? (!beta || !o1 || !o2 || (running_mean == nullptr) != (running_var == nullptr)) : !invstd) return MLQEM_ERR_BAD_ARG;
+  hipStream_t s = as_stream(stream);
+  if (mode == 0)
+    hipLaunchKernelGGL(bn_sync_merge_kernel<0>, dim3(ceil_div(kLW, kSyncThreads)), dim3(kSyncThreads), 0, s, records, world, C, kLW, gamma,
+                       beta, (const float*)nullptr, eps, o1, o2, o3, o4, o5, running_mean, running_var, momentum,
+                       reinterpret_cast<long long*>(num_batches_tracked));
+  else
+    hipLaunchKernelGGL(bn_sync_merge_kernel<1>, dim3(ceil_div(kLW, kSyncThreads)), dim3(kSyncThreads), 0, s, records, world, C, kLW, gamma,
+                       (const float*)nullptr, invstd, 0.f, (float*)nullptr, (float*)nullptr, o3, o4, o5, (float*)nullptr, (float*)nullptr,
+                       0.f, (long long*)nullptr);
+  return launch_status();
+}
 
 // op 0: out = drop(relu?(y scale + shift)) (+ res).   op 1: out = gs (gu - k1 - xhat k2), gu from (g | g32, y).
 template <typename ST>

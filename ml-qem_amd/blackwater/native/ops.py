@@ -207,7 +207,7 @@ def pooled_means(out, pool):
 # bits of a branch's last hidden activation come out of the aggregation launch that computes it (mlqem_csr_aggregate_pool_f32),
 # and the activation itself is never written: 6.75-6.80 against 6.97-7.09 ms per bench step on one box.  (With the activation
 # still stored the fused form was a wash: DESIGN.md section 3.)
-_POOL_FUSED = __import__("os").environ.get("MLQEM_POOL_FUSED", "1") != "0"
+_POOL_FUSED = os.environ.get("MLQEM_POOL_FUSED", "1") != "0"
 
 
 def _ell(ell, n):
@@ -1505,8 +1505,6 @@ def asap_coarsen(in_ptr, in_src, out_ptr, out_dst, perm, num_nodes, return_slot=
     _lib.check(code, "mlqem_asap_hop2_fill")
     uniq, e = _sort_unique(keys2, total2)
     del keys2
-    if os.environ.get("MLQEM_ASAP_DEBUG"):
-        print(f"asap_coarsen: N={num_nodes} k={k} hop1 candidates={total} distinct (p,v)={m} hop2 candidates={total2} edges={e}", flush=True)
     ei = torch.empty((2, e), dtype=torch.int64, device=dev)
     code = lib.mlqem_keys_to_edge_index(_p(uniq), e, _p(ei), _stream())
     _lib.check(code, "mlqem_keys_to_edge_index")

@@ -1559,14 +1559,6 @@ __global__ void lists_totals_kernel(const int64_t* __restrict__ off_o, const int
   if (threadIdx.x == 0 && blockIdx.x == 0) { totals[0] = off_o[K]; totals[1] = off_i[K]; totals[2] = roff_o[N]; totals[3] = roff_i[N]; }
 }
 
-int device_cus() {
-  int cus = 256, dev = 0;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-  }
-  return cus;
-}
 constexpr int kListsMaxLds = 160 * 1024;             // one workgroup may take a CU's whole LDS
 constexpr int kListsMaxK = 65535;                    // a row's two lengths travel as one packed int through the wave scan
 }  // namespace

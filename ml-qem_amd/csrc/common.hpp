@@ -131,6 +131,20 @@ template <class K> inline bool ensure_dynamic_lds(K kernel, size_t bytes) {
   if (bytes > 160 * 1024) return false;
   return ensure_dynamic_lds_impl(reinterpret_cast<const void*>(kernel), bytes);
 }
+// Compute units of the current device (256, an MI355X's, when the runtime will not say).
+inline int device_cus() {
+  int dev = 0, v = 0;
+  if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) return v;
+  return 256;
+}
+// Workgroups of `kernel` that are resident at once on the whole device (occupancy x compute units): the grid of a persistent
+// kernel.  fallback_per_cu stands in for the occupancy when the runtime will not say.  Callers keep the result (a `static const`
+// or a table of their own): the query is not for the launch path.
+template <class K> inline int resident_workgroups(K kernel, int threads, size_t lds, int fallback_per_cu) {
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds) != hipSuccess || per_cu < 1) per_cu = fallback_per_cu;
+  return per_cu * device_cus();
+}
 // Sum over the 16 lanes of an aligned lane group (all 16 must be active); every lane gets the total.  The attention
 // and pooling kernels give one group to a (row, head) or a row: lane l holds channels l, l + 16, ... so that a source row
 // is read with 64-byte coalesced loads and a dot product over the channels is four cross-lane adds in a fixed order.

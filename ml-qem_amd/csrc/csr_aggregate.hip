@@ -610,6 +610,14 @@ __global__ __launch_bounds__(kBlock) void ell_from_csr_kernel(const int32_t* __r
   reinterpret_cast<int2*>(ell)[i] = make_int2(s0, s1);
 }
 
+// Never launched: the 6-waves-per-SIMD sibling of the pooled kernel is instantiated because the compiler's output for the
+// launched one depends on it.  finish_row<4, false, true, true> is shared by every pooled instantiation; with callers of two
+// different waves-per-SIMD bounds LLVM leaves its by-reference arguments alone, with a single caller it promotes them before
+// inlining and the pooled kernel comes out five instructions longer (3514 -> 3519, same registers).  The 7-wave kernel was
+// tuned and measured as the compiler emits it with this sibling present; dropping the line is a code-generation change to be
+// measured on its own.
+template __global__ void csr_aggregate_ell_kernel<4, false, 2, true, 6, true>(const AggArgs, const PoolFuse);
+
 template <bool IS_MAX>
 static int launch_aggregate(AggArgs a, hipStream_t stream, const PoolFuse* pool = nullptr, int* rows_per_tile = nullptr) {
   const bool no_store = pool && pool->mask && !a.out;       // the pooled form with the gate bits: the activation itself is optional
@@ -633,11 +641,9 @@ static int launch_aggregate(AggArgs a, hipStream_t stream, const PoolFuse* pool 
   a.CV = (a.C + vec - 1) / vec;
   if (a.CV > kBlock) return MLQEM_ERR_UNSUPPORTED;
   // items per thread: measured best on MI355X (C = 10 and 22, 2.8M-node batch): 4 for the CSR walk (more loads in
-  // flight per thread outweigh 6 waves/SIMD), 2 for the ELL-assisted kernel (8 waves/SIMD).  MLQEM_AGG_IPT overrides.
-  constexpr int nt_env = 1;      // (was the A/B switch MLQEM_AGG_NT: settled)  // streaming stores (-8 % measured)
-  a.nt = nt_env;
-  constexpr int ipt_env = 0;      // (was the A/B switch MLQEM_AGG_IPT: settled)
-  const int ipt = ipt_env > 0 ? ipt_env : (a.ell ? 2 : 4);
+  // flight per thread outweigh 6 waves/SIMD), 2 for the ELL-assisted kernel (8 waves/SIMD).
+  a.nt = 1;       // streaming stores (-8 % measured)
+  const int ipt = a.ell ? 2 : 4;
   a.R = std::min(kRowsMax, kBlock * ipt / a.CV);
   const int64_t blocks = ceil_div(a.N, a.R);
   if (blocks > 0x7fffffffLL) return MLQEM_ERR_UNSUPPORTED;
@@ -651,33 +657,26 @@ static int launch_aggregate(AggArgs a, hipStream_t stream, const PoolFuse* pool 
   const bool epi = !IS_MAX && (a.z || a.bias || a.act || a.drop_p > 0.f);
   const PoolFuse no_pool{nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
   if (pool) {     // the pooled form exists for the shape the models launch it with: ELL side table, 16-byte rows, an epilogue
-    if (IS_MAX || !a.ell || vec != 4 || ipt != 2 || a.CV * 4 > kWave) return MLQEM_ERR_UNSUPPORTED;      // C <= 64: one wave holds a row of the tile
+    if (IS_MAX || !a.ell || vec != 4 || a.CV * 4 > kWave) return MLQEM_ERR_UNSUPPORTED;      // C <= 64: one wave holds a row of the tile
     if (rows_per_tile) *rows_per_tile = a.R;
     hipLaunchKernelGGL(tile_graph_kernel, dim3((unsigned)ceil_div((int64_t)std::max(pool->B, 1) * kGroup, kBlock)), dim3(kBlock), 0, stream, pool->gptr, pool->B,
                        a.R, (int64_t)grid.x, const_cast<int2*>(pool->tile_graph), pool->mask ? pool->tile_info : nullptr);
-    if constexpr (!IS_MAX) {
-      constexpr int pool_waves = 7;      // (was the A/B switch MLQEM_AGG_POOL_WAVES: settled)
-      if (pool_waves >= 7) hipLaunchKernelGGL((csr_aggregate_ell_kernel<4, false, 2, true, 7, true>), grid, block, 0, stream, a, *pool);
-      else hipLaunchKernelGGL((csr_aggregate_ell_kernel<4, false, 2, true, 6, true>), grid, block, 0, stream, a, *pool);
-    }
+    if constexpr (!IS_MAX) hipLaunchKernelGGL((csr_aggregate_ell_kernel<4, false, 2, true, 7, true>), grid, block, 0, stream, a, *pool);
     return launch_status();
   }
-  constexpr int epi_waves = 7;      // (was the A/B switch MLQEM_AGG_EPI_WAVES: settled)   // measured: 7 -> 304/351 us, 6 -> 341/385, 8 (spilling) -> 356/385 (GCN / Cheb forward)
-#define MLQEM_LAUNCH(V, P)                                                                                  \
-  do {                                                                                                      \
-    if (a.ell && epi && epi_waves == 8) hipLaunchKernelGGL((csr_aggregate_ell_kernel<V, IS_MAX, P, true, 8>), grid, block, 0, stream, a, no_pool);   \
-    else if (a.ell && epi && epi_waves == 7) hipLaunchKernelGGL((csr_aggregate_ell_kernel<V, IS_MAX, P, true, 7>), grid, block, 0, stream, a, no_pool);   \
-    else if (a.ell && epi) hipLaunchKernelGGL((csr_aggregate_ell_kernel<V, IS_MAX, P, true, 6>), grid, block, 0, stream, a, no_pool);   \
-    else if (a.ell) hipLaunchKernelGGL((csr_aggregate_ell_kernel<V, IS_MAX, P, false>), grid, block, 0, stream, a, no_pool);    \
-    else hipLaunchKernelGGL((csr_aggregate_kernel<V, IS_MAX, P>), grid, block, 0, stream, a);               \
+  // The epilogue form asks for 7 waves per SIMD; measured: 7 -> 304/351 us, 6 -> 341/385, 8 (spilling) -> 356/385 (GCN / Cheb forward).
+  // epi implies !IS_MAX, so that branch names the sum kernel outright.
+#define MLQEM_LAUNCH(V)                                                                                                            \
+  do {                                                                                                                             \
+    if (!a.ell) hipLaunchKernelGGL((csr_aggregate_kernel<V, IS_MAX, 4>), grid, block, 0, stream, a);                               \
+    else if (epi) hipLaunchKernelGGL((csr_aggregate_ell_kernel<V, false, 2, true, 7>), grid, block, 0, stream, a, no_pool);        \
+    else hipLaunchKernelGGL((csr_aggregate_ell_kernel<V, IS_MAX, 2, false>), grid, block, 0, stream, a, no_pool);                  \
   } while (0)
-#define MLQEM_BY_IPT(V) do { if (ipt == 1) MLQEM_LAUNCH(V, 1); else if (ipt == 2) MLQEM_LAUNCH(V, 2); else if (ipt == 8) MLQEM_LAUNCH(V, 8); else MLQEM_LAUNCH(V, 4); } while (0)
   switch (vec) {
-    case 4: MLQEM_BY_IPT(4); break;
-    case 2: MLQEM_BY_IPT(2); break;
-    default: MLQEM_BY_IPT(1); break;
+    case 4: MLQEM_LAUNCH(4); break;
+    case 2: MLQEM_LAUNCH(2); break;
+    default: MLQEM_LAUNCH(1); break;
   }
-#undef MLQEM_BY_IPT
 #undef MLQEM_LAUNCH
   return launch_status();
 }

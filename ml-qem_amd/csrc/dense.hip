@@ -834,7 +834,7 @@ constexpr int kWgradUnroll = 4;  // MFMA k-steps (of 4 rows) whose loads are iss
 
 // kU: k-steps per iteration.  The wide tile shapes (six output tiles: the seven first-layer gradient blocks in one pass)
 // can take kU = 2 (136 instead of 180 VGPRs: three waves per SIMD instead of two) -- measured SLOWER (1680 vs 1201 us on the
-// seven-block pass): the kernel lives on loads in flight per wave, so four stays the default (MLQEM_WGRAD_WIDE_U).
+// seven-block pass): the kernel lives on loads in flight per wave, so four stays the default.
 template <int OBT, int IBT, int kU = kWgradUnroll, bool PF = false>
 __global__ __launch_bounds__(kBlock) void wgrad_mfma_kernel(const WgradArgs a) {
   __shared__ f32x4 s_acc[4][kWave];   // the four waves' copies of ONE accumulator tile at a time (see the end)
@@ -1350,18 +1350,10 @@ static int resident_of(const void* kernel) {
   std::lock_guard<std::mutex> lock(mu);
   auto it = cache.find(kernel);
   if (it != cache.end()) return it->second;
-  int per_cu = 0, dev = 0, cus = 256;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, 0) != hipSuccess || per_cu < 1) per_cu = 2;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-  }
-  return cache[kernel] = per_cu * cus;
+  return cache[kernel] = resident_workgroups(kernel, kBlock, 0, 2);
 }
 template <typename K>
 static dim3 whole_rounds(K kernel, dim3 grid) {
-  constexpr int off = 0;      // (was the A/B switch MLQEM_WHOLE_ROUNDS: settled)
-  if (off) return grid;
   const int64_t per_round = std::max<int64_t>(1, resident_of(reinterpret_cast<const void*>(kernel)) / std::max(1u, grid.y));
   if ((int64_t)grid.x > per_round) grid.x = (unsigned)((int64_t)grid.x / per_round * per_round);
   return grid;
@@ -1426,24 +1418,16 @@ extern "C" int mlqem_linear_f32(const float* x, int64_t ldx, const float* w, int
   {
     // wide rows from narrow inputs, bias only (TransformerConv's q / k / v / skip projection): whole rows per wave through LDS
     const int c4 = (O + 3) / 4 * 4;
-    constexpr int rows_env = 1;      // (was the A/B switch MLQEM_LINEAR_ROWS: settled)
-    if (rows_env && !transposed && !accumulate && !gate && !rowscale && act == 0 && drop_p == 0.f && O >= 96 && O <= 192 && I <= 48 &&
+    if (!transposed && !accumulate && !gate && !rowscale && act == 0 && drop_p == 0.f && O >= 96 && O <= 192 && I <= 48 &&
         ldy == c4 && ldx % 4 == 0 && ldx >= (I + 3) / 4 * 4 && aligned_to(x, 16) && aligned_to(y, 16) && N >= 4096) {
       a.xrows = x_rows;
       const int nt = O <= 128 ? 8 : 12, g = I <= 32 ? 2 : 3;
       const int LS = c4 + (((c4 / 4) & 1) ? 0 : 4);          // an odd number of float4 per LDS row: 16-byte stores of 16 rows spread over the banks
       const size_t lds = ((size_t)4 * 16 * LS + (size_t)nt * 16) * sizeof(float);
-      int cus = 256, dev = 0;
-      if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-      }
       // persistent waves: exactly the workgroups that are resident at once (registers allow two per CU at twelve output tiles; three
       // were launched until round 4 -- the third ran alone after the others had finished: 166 us where 125 were due)
       auto go = [&](auto kernel) {
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, lds) != hipSuccess || per_cu < 1) per_cu = 2;
-        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)cus * per_cu, ceil_div(ceil_div(N, 16), 4)));
+        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(resident_workgroups(kernel, kBlock, lds, 2), ceil_div(ceil_div(N, 16), 4)));
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, a, LS);
       };
       const bool k24 = g == 2 && I > 16 && I <= 24 && ldx % 2 == 0;
@@ -1482,8 +1466,7 @@ extern "C" int mlqem_linear_f32(const float* x, int64_t ldx, const float* w, int
                     ldy >= c4o && aligned_to(x, 16) && aligned_to(y, 16) && !(transposed && (act || drop_p > 0.f)) &&
                     (!gate || (ldgate % 4 == 0 && ldgate >= c4o && aligned_to(gate, 16))) && !(transposed && rowscale) &&
                     !(act & ~1);
-  constexpr int lean_env = 1;      // (was the A/B switch MLQEM_LINEAR_LEAN: settled)
-  if (lean && lean_env) {
+  if (lean) {
     PartsArgs p{};
     p.xp[0] = x; p.ldx[0] = ldx; p.xn = 1; p.xw = c4i; p.xc = I;
     p.yp[0] = y; p.ldy[0] = ldy; p.yn = 1; p.yw = c4o; p.yc = O;
@@ -1509,11 +1492,9 @@ extern "C" int mlqem_linear_f32(const float* x, int64_t ldx, const float* w, int
     const int64_t tiles = ceil_div(N, 16);
     const unsigned gx = (unsigned)std::min<int64_t>(ceil_div(tiles, 4), 256 * 8);  // 4 waves per block
     dim3 grid(gx, (unsigned)ceil_div(ob, obt));
-    constexpr int v4_env = 1;      // (was the A/B switch MLQEM_LINEAR_V4: settled)
-    const bool padded = v4_form;
-    if (x_rows && !(v4_env && padded)) return MLQEM_ERR_UNSUPPORTED;   // the row map is carried by the lean and the 16-byte kernels only
+    if (x_rows && !v4_form) return MLQEM_ERR_UNSUPPORTED;   // the row map is carried by the lean and the 16-byte kernels only
     a.xrows = x_rows;
-    if (v4_env && padded) {  // padded activation rows on every operand: one 16-byte access path, no scalar tails
+    if (v4_form) {  // padded activation rows on every operand: one 16-byte access path, no scalar tails
       const int g = (I + 15) / 16;
       if (obt == 1) transposed ? launch_linear_v4<1, true>(a, g, grid, s) : launch_linear_v4<1, false>(a, g, grid, s);
       else if (obt == 2) transposed ? launch_linear_v4<2, true>(a, g, grid, s) : launch_linear_v4<2, false>(a, g, grid, s);
@@ -1556,44 +1537,29 @@ static bool launch_linear_parts(const PartsArgs& a, int g, int obt, dim3 grid, h
   return true;
 }
 
-// Workgroups of `kernel` that are resident at once on the whole device (occupancy x compute units).  The persistent
-// kernels below split their rows statically over the grid (deterministic partial sums), so a grid that is not a whole
-// number of resident rounds ends with a thin last round that runs at a fraction of the occupancy the kernel needs:
-// measured on the seven-block weight gradient, 3 workgroups per CU (= its occupancy) 1.01 ms, 4 per CU 1.47 ms.
-template <typename K>
-static int resident_workgroups(K kernel) {
-  int per_cu = 0, dev = 0, cus = 256;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, 0) != hipSuccess || per_cu < 1) per_cu = 2;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-  }
-  return per_cu * cus;
-}
+// The persistent kernels below take resident_workgroups (common.hpp; 2 per CU when the runtime will not say) as their grid.
+// They split their rows statically over the grid (deterministic partial sums), so a grid that is not a whole number of
+// resident rounds ends with a thin last round that runs at a fraction of the occupancy the kernel needs: measured on the
+// seven-block weight gradient, 3 workgroups per CU (= its occupancy) 1.01 ms, 4 per CU 1.47 ms.
 
 // Picks the tile shape and launches; `a` is complete except for the grid-related choices.
 static int run_linear_parts(PartsArgs& a, int transposed, hipStream_t s) {
   const int g = (a.I + 15) / 16, ob = (a.O + 15) / 16;
   if (g > 4 || ob > 16) return MLQEM_ERR_UNSUPPORTED;
-  constexpr int lds_env = 1;      // (was the A/B switch MLQEM_FANOUT_LDS: settled)
-  if (lds_env && !transposed && a.xn == 1 && a.yn >= 2 && a.yw <= 16 && !a.act && a.drop_p == 0.f && !a.gate) {
+  if (!transposed && a.xn == 1 && a.yn >= 2 && a.yw <= 16 && !a.act && a.drop_p == 0.f && !a.gate) {
     // several narrow output blocks from one read of x: weight fragments in LDS, one MFMA tile per block
     const int64_t tiles = ceil_div(a.N, 16);
-    constexpr int plain_env = 0;      // (was the A/B switch MLQEM_FANOUT_PLAIN: settled)
-    constexpr int grid_env = 0;      // (was the A/B switch MLQEM_FANOUT_GRID: settled)    // workgroups per CU; 0 = whole resident rounds
-    constexpr int rounds_env = 1;      // (was the A/B switch MLQEM_FANOUT_ROUNDS: settled)
-    a.plain_stores = plain_env;
-    constexpr int k24_env = 1;      // (was the A/B switch MLQEM_FANOUT_K24: settled)
-    const bool k24 = k24_env && g == 2 && a.xc <= 24 && a.ldx[0] % 2 == 0 && aligned_to(a.xp[0], 8);
+    a.plain_stores = 0;
+    const bool k24 = g == 2 && a.xc <= 24 && a.ldx[0] % 2 == 0 && aligned_to(a.xp[0], 8);
     int res = 0;
     switch (g) {
-      case 1: { static const int r = resident_workgroups(linear_fanout_lds_kernel<1>); res = r; break; }
-      case 2: { static const int r = resident_workgroups(linear_fanout_lds_kernel<2>), r24 = resident_workgroups(linear_fanout_lds_kernel<2, true>);
+      case 1: { static const int r = resident_workgroups(linear_fanout_lds_kernel<1>, kBlock, 0, 2); res = r; break; }
+      case 2: { static const int r = resident_workgroups(linear_fanout_lds_kernel<2>, kBlock, 0, 2), r24 = resident_workgroups(linear_fanout_lds_kernel<2, true>, kBlock, 0, 2);
                 res = k24 ? r24 : r; break; }
-      case 3: { static const int r = resident_workgroups(linear_fanout_lds_kernel<3>); res = r; break; }
-      default: { static const int r = resident_workgroups(linear_fanout_lds_kernel<4>); res = r; break; }
+      case 3: { static const int r = resident_workgroups(linear_fanout_lds_kernel<3>, kBlock, 0, 2); res = r; break; }
+      default: { static const int r = resident_workgroups(linear_fanout_lds_kernel<4>, kBlock, 0, 2); res = r; break; }
     }
-    dim3 grid((unsigned)std::min<int64_t>(ceil_div(tiles, 4), grid_env > 0 ? 256 * grid_env : res * rounds_env));
+    dim3 grid((unsigned)std::min<int64_t>(ceil_div(tiles, 4), res));      // one resident round
     switch (g) {
       case 1: hipLaunchKernelGGL(linear_fanout_lds_kernel<1>, grid, dim3(kBlock), 0, s, a); break;
       case 2:
@@ -1696,16 +1662,9 @@ extern "C" size_t mlqem_linear_wgrad_workspace_bytes(int I, int O) {
 }
 
 static int launch_wgrad(WgradArgs a, float* gw, float* gb, int accumulate, hipStream_t s) {
-  constexpr int wide_u = 4;      // (was the A/B switch MLQEM_WGRAD_WIDE_U: settled)   // measured on the 7-block pass: 4 -> 1201 us (180 VGPRs, 2 waves/SIMD), 2 -> 1680 us (136 VGPRs, 3 waves): loads in flight per wave matter more than occupancy
-  constexpr int wide_pf = 1;      // (was the A/B switch MLQEM_WGRAD_PF: settled)
-  const int ob_ = (a.O + 15) / 16, ib_ = (a.I + 1 + 15) / 16;
-  const bool wide = ob_ >= 4 && ob_ <= 6 && ib_ <= 2;
-  constexpr int pipe_env = 2;      // (was the A/B switch MLQEM_WGRAD_PIPE: settled)    // 0: wgrad_mfma_kernel, 1: KU = 4 (two waves per SIMD), 2: KU = 2 (three)
-  constexpr int wide6_env = 1;      // (was the A/B switch MLQEM_WGRAD_WIDE6: settled)
-  constexpr int pipe_grid = 0;      // (was the A/B switch MLQEM_WGRAD_GRID: settled)  // workgroups per CU; 0 = the resident count
   bool uniform_ld = true;
   for (int k = 1; k < a.gn; ++k) uniform_ld = uniform_ld && a.ldgy[k] == a.ldgy[0];
-  const int64_t iters = ceil_div(std::max<int64_t>(a.N, 1), 4 * (wide && wide_u == 2 ? 2 : kWgradUnroll));
+  const int64_t iters = ceil_div(std::max<int64_t>(a.N, 1), 4 * kWgradUnroll);
   int G = (int)std::max<int64_t>(1, std::min<int64_t>(kWgradBlocks, ceil_div(iters, 4)));
   // the workgroups walk the rows with stride gridDim.x and leave one partial each: a whole number of resident rounds (whole_rounds)
 #define MLQEM_WG(KERNEL, GY) { const dim3 gr = whole_rounds(KERNEL, dim3((unsigned)G, (unsigned)(GY))); G = (int)gr.x; hipLaunchKernelGGL(KERNEL, gr, dim3(kBlock), 0, s, a); }
@@ -1717,35 +1676,32 @@ static int launch_wgrad(WgradArgs a, float* gw, float* gb, int accumulate, hipSt
   } else if (ob == 3 && ib <= 2) {
     MLQEM_WG((wgrad_mfma_kernel<3, 2>), 1)
   } else if (ob == 4 && ib <= 2) {   // up to eight blocks (the three first layers of Family A share x): one pass
-    if (wide_u == 2) MLQEM_WG((wgrad_mfma_kernel<4, 2, 2>), 1)
-    else MLQEM_WG((wgrad_mfma_kernel<4, 2>), 1)
-  } else if (ob <= 6 && ib <= 2 && pipe_env && uniform_ld) {
-    // the first-layer blocks: software-pipelined form (see wgrad_pipe_kernel).  Blocks are 12 floats wide with 10 real columns:
-    // the MFMA rows take the REAL columns back to back (six blocks: 60 rows = four tiles instead of 72 = five; seven: five instead
+    // four k-steps in flight; measured on the 7-block pass: 4 -> 1201 us (180 VGPRs, 2 waves/SIMD), 2 -> 1680 us (136 VGPRs, 3 waves):
+    // loads in flight per wave matter more than occupancy
+    MLQEM_WG((wgrad_mfma_kernel<4, 2>), 1)
+  } else if (ob <= 6 && ib <= 2 && uniform_ld) {
+    // the first-layer blocks: software-pipelined form at KU = 2, three waves per SIMD (see wgrad_pipe_kernel).  Blocks are 12 floats
+    // wide with 10 real columns: the MFMA rows take the REAL columns back to back (six blocks: 60 rows = four tiles instead of 72 = five; seven: five instead
     // of six) -- fewer load instructions and a third fewer MFMAs for the same bytes; the second stage spreads them out again.
-    constexpr int pack_env = 1;      // (was the A/B switch MLQEM_WGRAD_PACK: settled)
     const int obp = (a.gn * a.gc + 15) / 16;
-    const bool pack = pack_env && a.gn > 1 && a.gc < a.gw && a.gw - a.gc <= a.gc && obp < ob && obp >= 4 && pipe_env == 2;
+    const bool pack = a.gn > 1 && a.gc < a.gw && a.gw - a.gc <= a.gc && obp < ob && obp >= 4;
     const int pw = a.gw, pc = a.gc;
     if (pack) { a.gw = a.gc; a.O = a.gn * a.gc; }
-    static const int res4p = resident_workgroups(wgrad_pipe_kernel<4, 2, 2, 2>), res5p = resident_workgroups(wgrad_pipe_kernel<5, 2, 2, 2>);
-    static const int res2 = resident_workgroups(wgrad_pipe_kernel<6, 2, 2, 2>), res4 = resident_workgroups(wgrad_pipe_kernel<6, 2, 4, 2>);
-    const int want = pipe_grid > 0 ? 256 * pipe_grid : (pack ? (obp == 4 ? res4p : res5p) : pipe_env == 2 ? res2 : res4);      // one resident round exactly
+    static const int res4p = resident_workgroups(wgrad_pipe_kernel<4, 2, 2, 2>, kBlock, 0, 2), res5p = resident_workgroups(wgrad_pipe_kernel<5, 2, 2, 2>, kBlock, 0, 2);
+    static const int res6 = resident_workgroups(wgrad_pipe_kernel<6, 2, 2, 2>, kBlock, 0, 2);
+    const int want = pack ? (obp == 4 ? res4p : res5p) : res6;      // one resident round exactly
     const int Gp = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(kWgradBlocks, want), ceil_div(ceil_div(a.N, 16), 4)));
     if (pack && obp == 4) hipLaunchKernelGGL((wgrad_pipe_kernel<4, 2, 2, 2>), dim3(Gp), dim3(kBlock), 0, s, a);
     else if (pack) hipLaunchKernelGGL((wgrad_pipe_kernel<5, 2, 2, 2>), dim3(Gp), dim3(kBlock), 0, s, a);
-    else if (pipe_env == 2) hipLaunchKernelGGL((wgrad_pipe_kernel<6, 2, 2, 2>), dim3(Gp), dim3(kBlock), 0, s, a);
-    else hipLaunchKernelGGL((wgrad_pipe_kernel<6, 2, 4, 2>), dim3(Gp), dim3(kBlock), 0, s, a);
+    else hipLaunchKernelGGL((wgrad_pipe_kernel<6, 2, 2, 2>), dim3(Gp), dim3(kBlock), 0, s, a);
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)ceil_div(a.O * (a.I + 1), kReducePairs)), dim3(kReducePairs * kReduceSlices), 0, s, a.partial,
                        Gp, a.I, a.O, gw, gb, accumulate, pack ? pw : 0, pack ? pc : 0);
     return launch_status();
-  } else if (ob <= 6 && ib <= 2) {
-    if (wide_u == 2) MLQEM_WG((wgrad_mfma_kernel<6, 2, 2>), 1)
-    else if (wide_pf) MLQEM_WG((wgrad_mfma_kernel<6, 2, kWgradUnroll, true>), 1)
-    else MLQEM_WG((wgrad_mfma_kernel<6, 2>), 1)
+  } else if (ob <= 6 && ib <= 2) {   // column blocks of differing leading dimensions: the prefetching form
+    MLQEM_WG((wgrad_mfma_kernel<6, 2, kWgradUnroll, true>), 1)
   } else if (ob == 1) {
     MLQEM_WG((wgrad_mfma_kernel<1, 4>), (unsigned)ceil_div(ib, 4))
-  } else if (ob > 6 && ib <= 2 && wide6_env) {
+  } else if (ob > 6 && ib <= 2) {
     // many outputs against a narrow x (Family B's first projection: gy[180]^T x[22]): six output tiles per workgroup -- a row's
     // gy is read as 384-byte pieces by ceil(ob / 6) workgroup columns instead of 128-byte pieces by ceil(ob / 2), and x is
     // re-read two times instead of six

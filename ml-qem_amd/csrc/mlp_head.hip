@@ -768,17 +768,6 @@ __global__ __launch_bounds__(kHeadReduceSlices * kWave) void mlp1_bwd_reduce_ker
   else gb2[c] = tot;
 }
 
-template <typename K>
-static int head_resident_workgroups(K kernel, int threads, size_t lds) {
-  int per_cu = 0, dev = 0, cus = 256;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-  }
-  return per_cu * cus;
-}
-
 constexpr int kHeadMaxBwdBlocks = 512;    // partial-sum slots of the backward workspace
 
 template <bool BF16, int G>
@@ -787,7 +776,7 @@ static int launch_head_fwd(Mlp1Args a, void* workspace, hipStream_t s) {
   void (*kernel)(Mlp1Args);
   if constexpr (BF16) kernel = mlp1_fwd_bf16_kernel<G>; else kernel = mlp1_fwd_f32_kernel<G>;
   if (!ensure_dynamic_lds(kernel, lds)) return MLQEM_ERR_LAUNCH;      // per device (common.hpp)
-  static const int res = head_resident_workgroups(kernel, kFwdThreads, lds);
+  static const int res = resident_workgroups(kernel, kFwdThreads, lds, 1);
   a.image = workspace;
   hipLaunchKernelGGL(mlp1_image_kernel<BF16>, dim3((unsigned)ceil_div(head_image_u32x4(G) * 4, 256)), dim3(256), 0, s, a, G,
                      static_cast<u32x4*>(workspace));
@@ -865,8 +854,8 @@ extern "C" int mlqem_mlp1_backward(const float* gout, int64_t ldg, const float* 
   if (N == 0) {
     G = 0;                                        // nothing to sum: the second stage writes zeros
   } else if (bf16) {
-    static const int res1 = head_resident_workgroups(mlp1_bwd_bf16_kernel<1>, kBwdThreads, 0);
-    static const int res4 = head_resident_workgroups(mlp1_bwd_bf16_kernel<4>, kBwdThreads, 0);
+    static const int res1 = resident_workgroups(mlp1_bwd_bf16_kernel<1>, kBwdThreads, 0, 1);
+    static const int res4 = resident_workgroups(mlp1_bwd_bf16_kernel<4>, kBwdThreads, 0, 1);
     G = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(O2 == 1 ? res1 : res4, kHeadMaxBwdBlocks), std::max<int64_t>(N / 32, 1)));
     if (O2 == 1) hipLaunchKernelGGL(mlp1_bwd_bf16_kernel<1>, dim3(G), dim3(kBwdThreads), 0, s, a, cpw);
     else hipLaunchKernelGGL(mlp1_bwd_bf16_kernel<4>, dim3(G), dim3(kBwdThreads), 0, s, a, cpw);
@@ -881,7 +870,7 @@ extern "C" int mlqem_mlp1_backward(const float* gout, int64_t ldg, const float* 
     static int res_of[2][2][2] = {};
     auto launch = [&](auto kernel) {
       int& res = res_of[O2 == 1 ? 0 : 1][ng - 1][ns ? 1 : 0];
-      if (res == 0) res = head_resident_workgroups(kernel, kBwdThreads, 0);
+      if (res == 0) res = resident_workgroups(kernel, kBwdThreads, 0, 1);
       G = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(res, kHeadMaxBwdBlocks), ceil_div(std::max<int64_t>(N / 4, 1), KU)));
       hipLaunchKernelGGL(kernel, dim3(G), dim3(kBwdThreads), 0, s, a);
     };

@@ -554,161 +554,23 @@ __global__ __launch_bounds__(kLayerThreads) void layer_wgrad_kernel(const WgradL
       for (int r = 0; r < 4; ++r) dst[((t * 4 + s4) * 4 + r) * kWave] = acc[t][s4][r];
 }
 
-// The same product for bf16 [N,128] inputs with the operands brought in by LDS DMA (global_load_lds_dwordx4: 64 lanes x 16 bytes
-// from per-lane global addresses into one contiguous KB of LDS, no registers in between).  The register-prefetch form above
-// holds ONE 32-row slab in flight per workgroup at one workgroup per CU (272 registers): 16 KB per CU against the ~40 KB the
-// memory system needs in flight per CU, 2.8 TB/s.  Here a workgroup keeps kDmaSlabs - 1 slabs (16 KB each: dY 8 KB | X 8 KB)
-// on their way in LDS, registers hold only the slab being multiplied (two workgroups per CU), and every wave reads the dY
-// slab the workgroup fetched ONCE instead of fetching it itself: 47 -> 35 us per launch (134 MB: 3.8 TB/s).
-//   DMA instruction i of a slab, issued by wave i / 2: lane (lq, lr) fetches bytes [16 lr, 16 lr + 16) of row 8 lq + i -> the
-//   consumer's load j = i of lane (lq, lr) is the linear read `region j + 16 lane`: no bank conflicts, no index arithmetic.
+// For bf16 [N,128] inputs the operands come in by LDS DMA (global_load_lds_dwordx4: 64 lanes x 16 bytes from per-lane global
+// addresses into one contiguous KB of LDS, no registers in between).  The register-prefetch form above holds ONE 32-row slab in
+// flight per workgroup at one workgroup per CU (272 registers): 16 KB per CU against the ~40 KB the memory system needs in flight
+// per CU, 2.8 TB/s.  With DMA a workgroup keeps a ring of slabs (16 KB each: dY 8 KB | X 8 KB) on their way in LDS, registers hold
+// only the slab being multiplied (two workgroups per CU), and every wave reads the dY slab the workgroup fetched ONCE instead of
+// fetching it itself: 47 -> 35 us per launch (134 MB: 3.8 TB/s) with the operands still transposed by v_perm; ring depths 2 to 5
+// measured the same there (34-35 us at 262 144 rows): in LDS the launch was bound by its instruction stream (32 MFMAs + ~100 vector
+// instructions per 32 rows and wave), not by latency any more, which is what the transposing reads below remove.
 //   One s_barrier per slab: a wave waits for its own DMAs of slab t (vmcnt), the barrier makes everybody's visible, and having
 //   passed it means everybody has finished READING slab t - 1, whose buffer the next DMA may overwrite.  The barrier is the
 //   raw instruction: __syncthreads() carries a release fence that waits for ALL outstanding DMAs (vmcnt(0)) -- the prefetch.
 constexpr int kDmaSlabBytes = 16384;
 
-template <int kDmaSlabs>
-__global__ __launch_bounds__(kLayerThreads, 2) void layer_wgrad_lds_kernel(const WgradLayerArgs a, int cpw) {
-  extern __shared__ __attribute__((aligned(16))) char s_dma[];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int lr = lane & 15, lq = lane >> 4;
-  const int col0 = 4 * (cpw * wid + lr);
-  const bool xlane = lr < cpw && col0 <= a.K;
-  const int colc = min(col0, kLW - 4);
-  const bool x_raw[4] = {col0 + 0 < a.K, col0 + 1 < a.K, col0 + 2 < a.K, col0 + 3 < a.K};
-  const float x_fill[4] = {xlane && col0 + 0 == a.K ? 1.f : 0.f, xlane && col0 + 1 == a.K ? 1.f : 0.f,
-                           xlane && col0 + 2 == a.K ? 1.f : 0.f, xlane && col0 + 3 == a.K ? 1.f : 0.f};
-  unsigned x_keep[4], x_or[4];                   // per column: keep the loaded pair of bf16 values, or replace it by 1.0 | 1.0 / by zeros
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    x_keep[c] = x_raw[c] ? 0xFFFFFFFFu : 0u;
-    x_or[c] = x_fill[c] != 0.f ? 0x3F803F80u : 0u;
-  }
-  f32x4 acc[8][4];
-#pragma unroll
-  for (int t = 0; t < 8; ++t)
-#pragma unroll
-    for (int s = 0; s < 4; ++s) acc[t][s] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int64_t n_slabs = a.N / 32;
-  const unsigned short* xb = static_cast<const unsigned short*>(a.x);
-  using lds_ptr = __attribute__((address_space(3))) void*;
-  auto issue = [&](int64_t s, int buf) {          // this wave's four DMA instructions of slab s (clamped: the counts stay uniform)
-    const int64_t r0 = 32 * min(s, n_slabs - 1);
-    char* base = s_dma + buf * kDmaSlabBytes;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int i = 2 * wid + q;
-      const int64_t off = (r0 + 8 * lq + i) * kLW + 8 * lr;
-      __builtin_amdgcn_global_load_lds(a.dy + off, (lds_ptr)(base + i * 1024), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(xb + off, (lds_ptr)(base + 8192 + i * 1024), 16, 0, 0);
-    }
-  };
-  // this lane's 8 bytes of an X row inside the region the DMA wrote: chunk colc / 8 of row-lane lq, half (colc % 8) / 4
-  const int x_off = 8192 + (lq * 16 + (colc >> 3)) * 16 + (colc & 7) * 2;
-  const int64_t G = gridDim.x;
-  if (n_slabs > 0) {
-#pragma unroll
-    for (int s = 0; s < kDmaSlabs - 1; ++s) issue(blockIdx.x + s * G, s);
-    int t = 0;
-    for (int64_t sl = blockIdx.x; sl < n_slabs; sl += G, ++t) {
-      __builtin_amdgcn_s_waitcnt(0x0F70 | (4 * (kDmaSlabs - 2)));      // vmcnt(4 (kDmaSlabs - 2)): this wave's parts of slab t are in LDS
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-      issue(sl + (kDmaSlabs - 1) * G, (t + kDmaSlabs - 1) % kDmaSlabs);
-      // The slab is read with ds_read instructions the compiler does not see as LDS loads: for a load it sees, its wait-count
-      // pass puts s_waitcnt vmcnt(0) in front (any LDS load may alias any pending LDS DMA), i.e. it waits for the slabs that
-      // were only just requested -- the whole prefetch.
-      const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)(s_dma) + (t % kDmaSlabs) * kDmaSlabBytes;
-      const unsigned ad_d = lds0 + lane * 16, ad_x = lds0 + x_off;
-      u32x4 dv[8];
-      uint2 xv[8];
-#define MLQEM_DS_READ(j)                                                                                         \
-      asm volatile("ds_read_b128 %0, %2 offset:" #j "*1024\n\tds_read_b64 %1, %3 offset:" #j "*1024"               \
-                   : "=&v"(dv[j]), "=&v"(xv[j]) : "v"(ad_d), "v"(ad_x));
-      MLQEM_DS_READ(0) MLQEM_DS_READ(1) MLQEM_DS_READ(2) MLQEM_DS_READ(3)
-      MLQEM_DS_READ(4) MLQEM_DS_READ(5) MLQEM_DS_READ(6) MLQEM_DS_READ(7)
-#undef MLQEM_DS_READ
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-      // B fragments: column c of this lane's four, rows 8 lq .. 8 lq + 7 -- the 16-bit field c of eight registers, gathered two
-      // rows at a time by v_perm, then (raw & keep) | fill: the ones column behind the last input (it makes the bias gradient)
-      // and the zero columns beyond it cost one v_and_or each instead of a round trip through fp32.
-      bf16x8 bx[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        unsigned w[4];
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-          const unsigned hi = c < 2 ? xv[2 * d + 1].x : xv[2 * d + 1].y, lo = c < 2 ? xv[2 * d].x : xv[2 * d].y;
-          const unsigned raw = __builtin_amdgcn_perm(hi, lo, (c & 1) ? 0x07060302u : 0x05040100u);
-          w[d] = (raw & x_keep[c]) | x_or[c];
-        }
-        const u32x4 v = {w[0], w[1], w[2], w[3]};
-        bx[c] = __builtin_bit_cast(bf16x8, v);
-      }
-#pragma unroll
-      for (int tt = 0; tt < 8; ++tt) {
-        const int c = tt >> 1;
-        unsigned ad[4];
-#pragma unroll
-        for (int d = 0; d < 4; ++d)
-          ad[d] = (tt & 1) ? __builtin_amdgcn_perm(vget(dv[2 * d + 1], c), vget(dv[2 * d], c), 0x07060302u)
-                           : __builtin_amdgcn_perm(vget(dv[2 * d + 1], c), vget(dv[2 * d], c), 0x05040100u);
-        const u32x4 av = {ad[0], ad[1], ad[2], ad[3]};
-        const bf16x8 af = __builtin_bit_cast(bf16x8, av);
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) acc[tt][s4] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bx[s4], acc[tt][s4], 0, 0, 0);
-      }
-    }
-    __builtin_amdgcn_s_waitcnt(0x0F70);             // vmcnt(0): the clamped DMAs of the last iterations land before the LDS is given back
-  }
-  if (blockIdx.x == 0 && (a.N & 31)) {              // the ragged tail: straight from memory, rows beyond N contribute nothing
-    u32x4 dv[8];
-    float xf[8][4];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int64_t row = 32 * n_slabs + 8 * lq + j;
-      const int64_t rc = min(row, a.N - 1);
-      const uint2 xq = *reinterpret_cast<const uint2*>(xb + rc * kLW + colc);
-      dv[j] = *reinterpret_cast<const u32x4*>(a.dy + rc * kLW + 8 * lr);
-      if (row >= a.N) dv[j] = u32x4{0u, 0u, 0u, 0u};
-      const float v[4] = {blo(xq.x), bhi(xq.x), blo(xq.y), bhi(xq.y)};
-#pragma unroll
-      for (int c = 0; c < 4; ++c) xf[j][c] = x_raw[c] ? v[c] : x_fill[c];
-    }
-    bf16x8 bx[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const u32x4 v = {lpack(xf[0][c], xf[1][c]), lpack(xf[2][c], xf[3][c]), lpack(xf[4][c], xf[5][c]), lpack(xf[6][c], xf[7][c])};
-      bx[c] = __builtin_bit_cast(bf16x8, v);
-    }
-#pragma unroll
-    for (int tt = 0; tt < 8; ++tt) {
-      const int c = tt >> 1;
-      unsigned ad[4];
-#pragma unroll
-      for (int d = 0; d < 4; ++d)
-        ad[d] = (tt & 1) ? __builtin_amdgcn_perm(vget(dv[2 * d + 1], c), vget(dv[2 * d], c), 0x07060302u)
-                         : __builtin_amdgcn_perm(vget(dv[2 * d + 1], c), vget(dv[2 * d], c), 0x05040100u);
-      const u32x4 av = {ad[0], ad[1], ad[2], ad[3]};
-      const bf16x8 af = __builtin_bit_cast(bf16x8, av);
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) acc[tt][s4] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bx[s4], acc[tt][s4], 0, 0, 0);
-    }
-  }
-  float* __restrict__ dst = a.partial + (int64_t)blockIdx.x * kLayerW1Floats + (wid * 32 * 4) * kWave + lane;
-#pragma unroll
-  for (int t = 0; t < 8; ++t)
-#pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) dst[((t * 4 + s4) * 4 + r) * kWave] = acc[t][s4][r];
-}
-
 // ---- the bf16 x bf16 weight gradient without a single transpose instruction: ds_read_b64_tr_b16 ------------------------------
 // Both MFMA operands of gW = dY^T X want, per lane, eight consecutive ROWS of one column -- the operands are row-major, so the
-// kernels above gather them with v_perm (48 per 32 rows and wave: the launch was bound by that instruction stream, not by
-// memory).  gfx950's transposing LDS read does the gather in the LDS crossbar: per 16-lane group it reads a 4-row x 16-column
+// kernel above gathers them with v_perm (48 per 32 rows and wave: with the operands in LDS the launch was bound by that
+// instruction stream, not by memory).  gfx950's transposing LDS read does the gather in the LDS crossbar: per 16-lane group it reads a 4-row x 16-column
 // block of 16-bit elements and hands lane i column i.  The slab image in LDS is what the DMA writes (lane-linear: region i = rows
 // {8 lq + i}, 256 B per row), with the 16-byte chunks of row r stored at position chunk ^ 2 g(r), g(r) = (r & 3) | ((r >> 3 & 1) << 2):
 // the eight rows one 32-lane half reads together (4 per 16-lane group) then sit on eight different 32-byte bank ranges and the
@@ -1269,23 +1131,12 @@ __global__ __launch_bounds__(16 * kWave) void layer_wgrad_f32_reduce_kernel(cons
   else if (gb) gb[o] = tot;
 }
 
-template <typename K>
-static int layer_resident(K kernel, int threads, size_t lds) {
-  int per_cu = 0, dev = 0, cus = 256;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-  }
-  return per_cu * cus;
-}
-
 template <int G2, bool IN_BF16>
 static int launch_layer_fwd(LayerArgs a, void* workspace, hipStream_t s) {
   const size_t lds = (size_t)layer_image_u32x4(G2) * sizeof(u32x4);
   auto kernel = layer_fwd_kernel<G2, IN_BF16>;
   if (!ensure_dynamic_lds(kernel, lds)) return MLQEM_ERR_LAUNCH;      // per device (common.hpp)
-  static const int res = layer_resident(kernel, kLayerThreads, lds);
+  static const int res = resident_workgroups(kernel, kLayerThreads, lds, 1);
   a.image = workspace;
   hipLaunchKernelGGL(layer_image_kernel, dim3((unsigned)ceil_div(layer_image_u32x4(G2) * 4, 256)), dim3(256), 0, s, a, G2, static_cast<u32x4*>(workspace));
   const int64_t tiles = ceil_div(a.N, 16);
@@ -1346,7 +1197,7 @@ static int layer_colsum(int mode, const void* y, const void* g, const float* g32
   int nb = colsum_blocks(N);
   {   // a fixed partition of the rows over the workgroups: a whole number of resident rounds (the backward sums fit five workgroups
       // per CU: 2048 of them ran as one round and a second one at 60 % of the occupancy)
-    static const int r0 = layer_resident(layer_colsum_kernel<0, ST>, 256, 0), r1 = layer_resident(layer_colsum_kernel<1, ST>, 256, 0);
+    static const int r0 = resident_workgroups(layer_colsum_kernel<0, ST>, 256, 0, 1), r1 = resident_workgroups(layer_colsum_kernel<1, ST>, 256, 0, 1);
     const int res = mode == 0 ? r0 : r1;
     if (nb > res) nb = nb / res * res;
   }
@@ -1500,33 +1351,19 @@ extern "C" int mlqem_layer_wgrad_bf16(const void* dy, const void* x, int x_is_bf
   const int chunks = (K + 1 + 3) / 4, cpw = (chunks + 3) / 4;
   int G = 0;
   if (N > 0) {
-    static const int r0 = layer_resident(layer_wgrad_kernel<false>, kLayerThreads, 0), r1 = layer_resident(layer_wgrad_kernel<true>, kLayerThreads, 0);
-    G = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(x_is_bf16 ? r1 : r0, kLayerMaxBlocks), std::max<int64_t>(N / 32, 1)));
-    constexpr int lds_form = 2;      // (was the A/B switch MLQEM_LAYER_WGRAD_LDS: settled)    // 0: register prefetch, 1: LDS DMA + v_perm, 2: LDS DMA + transposing reads
-    const bool dma_ok = aligned_to(dy, 16) && aligned_to(x, 16);      // the DMA forms move 16 bytes per lane
-    if (x_is_bf16 && lds_form == 2 && dma_ok) {    // the transposing-read form (default): see layer_wgrad_tr_kernel
+    if (x_is_bf16 && aligned_to(dy, 16) && aligned_to(x, 16)) {    // the transposing-read form (layer_wgrad_tr_kernel): its LDS DMA moves 16 bytes per lane
       const size_t lds = (size_t)kTrSlabs * kDmaSlabBytes;
       if (!ensure_dynamic_lds(layer_wgrad_tr_kernel, lds)) return MLQEM_ERR_LAUNCH;      // per device (common.hpp)
-      static const int rl = layer_resident(layer_wgrad_tr_kernel, kLayerThreads, lds);
+      static const int rl = resident_workgroups(layer_wgrad_tr_kernel, kLayerThreads, lds, 1);
       G = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(rl, kLayerMaxBlocks), std::max<int64_t>(N / 32, 1)));
       hipLaunchKernelGGL(layer_wgrad_tr_kernel, dim3(G), dim3(kLayerThreads), lds, s, a);
       hipLaunchKernelGGL(layer_wgrad_tr_reduce_kernel, dim3((unsigned)ceil_div(kLayerTrFloats, kWave)), dim3(16 * kWave), 0, s, a.partial, G, K, U, gw, gb);
       return launch_status();
     }
-    if (x_is_bf16 && lds_form && dma_ok) {
-      auto go = [&](auto kernel, int slabs) {
-        const size_t lds = (size_t)slabs * kDmaSlabBytes;
-        if (!ensure_dynamic_lds(kernel, lds)) return false;
-        const int rl = layer_resident(kernel, kLayerThreads, lds);
-        G = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(rl, kLayerMaxBlocks), std::max<int64_t>(N / 32, 1)));
-        hipLaunchKernelGGL(kernel, dim3(G), dim3(kLayerThreads), lds, s, a, cpw);
-        return true;
-      };
-      // depth 2, 3, 4 and 5 measure the same (34-35 us at 262 144 rows): with the operands in LDS the launch is bound by its
-      // instruction stream (32 MFMAs + ~100 vector instructions per 32 rows and wave: the 8 x 8 transposes of the 16-bit operands
-      // by v_perm), not by latency any more; ds_read_b64_tr_b16 on a swizzled image would remove the transposes
-      if (!go(layer_wgrad_lds_kernel<4>, 4)) return MLQEM_ERR_LAUNCH;
-    } else if (x_is_bf16) hipLaunchKernelGGL(layer_wgrad_kernel<true>, dim3(G), dim3(kLayerThreads), 0, s, a, cpw);
+    // fp32 x, or a bf16 x that is not 16-byte aligned: the register-prefetch form
+    static const int r0 = resident_workgroups(layer_wgrad_kernel<false>, kLayerThreads, 0, 1), r1 = resident_workgroups(layer_wgrad_kernel<true>, kLayerThreads, 0, 1);
+    G = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(x_is_bf16 ? r1 : r0, kLayerMaxBlocks), std::max<int64_t>(N / 32, 1)));
+    if (x_is_bf16) hipLaunchKernelGGL(layer_wgrad_kernel<true>, dim3(G), dim3(kLayerThreads), 0, s, a, cpw);
     else hipLaunchKernelGGL(layer_wgrad_kernel<false>, dim3(G), dim3(kLayerThreads), 0, s, a, cpw);
   }
   hipLaunchKernelGGL(layer_wgrad_reduce_kernel, dim3((unsigned)ceil_div(kLayerW1Floats, kWave)), dim3(kLayerReduceSlices * kWave), 0, s, a.partial, G, K, U, cpw, gw, gb);
@@ -1584,7 +1421,7 @@ static int launch_layer_fwd_f32(LayerF32Args a, void* workspace, hipStream_t s) 
   const size_t lds = (size_t)layer_f32_image_float4(NJ, NOB) * sizeof(float4);
   auto kernel = layer_fwd_f32_kernel<NJ, NOB>;
   if (!ensure_dynamic_lds(kernel, lds)) return MLQEM_ERR_LAUNCH;      // per device (common.hpp)
-  static const int res = layer_resident(kernel, kF32Threads, lds);
+  static const int res = resident_workgroups(kernel, kF32Threads, lds, 1);
   a.image = workspace;
   hipLaunchKernelGGL(layer_f32_image_kernel, dim3((unsigned)ceil_div(layer_f32_image_float4(NJ, NOB) * 4, 256)), dim3(256), 0, s, a, NJ, NOB,
                      static_cast<float4*>(workspace));
@@ -1628,28 +1465,14 @@ extern "C" int mlqem_layer_wgrad_f32(const float* dy, const float* x, int64_t ld
   WgradF32Args a{dy, x, ldx, N, K, NC, static_cast<float*>(workspace)};
   int G = 0;
   if (N > 0) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-      int v = 0;
-      if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
     // the partial sums of a workgroup are n_waves x 16 KB
     const int64_t cap = (int64_t)(mlqem_layer_workspace_bytes() / ((size_t)n_waves * kWgF32WaveFloats * sizeof(float)));
     // persistent workgroups: exactly as many as are resident at once (at 210 registers two waves share a SIMD: eight waves per CU)
-    constexpr int q_env = 8;      // (was the A/B switch MLQEM_LAYER_WGRAD_Q: settled)
-    const bool q4 = q_env == 4;
-    static int per_cu_of[8] = {};                    // by workgroup size (1..6 waves): asked of the runtime once, not per call
-    int per_cu = per_cu_of[n_waves & 7];
-    if (per_cu == 0) {
-      if ((q4 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, layer_wgrad_f32_kernel<4>, n_waves * kWave, 0)
-              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, layer_wgrad_f32_kernel<8>, n_waves * kWave, 0)) != hipSuccess || per_cu < 1)
-        per_cu = 1;
-      per_cu_of[n_waves & 7] = per_cu;
-    }
-    const int64_t want = (int64_t)cus * per_cu;
+    static int res_of[8] = {};                       // by workgroup size (1..6 waves): asked of the runtime once, not per call
+    int& want = res_of[n_waves & 7];
+    if (want == 0) want = resident_workgroups(layer_wgrad_f32_kernel<8>, n_waves * kWave, 0, 1);
     G = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(want, cap), std::max<int64_t>(N / 32, 1)));
-    if (q4) hipLaunchKernelGGL(layer_wgrad_f32_kernel<4>, dim3(G), dim3(n_waves * kWave), 0, s, a);
-    else hipLaunchKernelGGL(layer_wgrad_f32_kernel<8>, dim3(G), dim3(n_waves * kWave), 0, s, a);
+    hipLaunchKernelGGL(layer_wgrad_f32_kernel<8>, dim3(G), dim3(n_waves * kWave), 0, s, a);
   }
   hipLaunchKernelGGL(layer_wgrad_f32_reduce_kernel, dim3((unsigned)ceil_div(n_waves * kWgF32WaveFloats, kWave)), dim3(16 * kWave), 0, s,
                      a.partial, G, K, U, NC, n_waves, gw, gb);

@@ -31,5 +31,5 @@ torch.cuda.synchronize()
 us = beg.elapsed_time(end) * 1e3 / reps
 e = s.num_edges + n
 alg = 4 * (n + 1) + 4 * e + 4 * n + 4 * c * (e + n)
-print("nodes", n, "edges", s.num_edges, "C", c, "IPT", os.environ.get("MLQEM_AGG_IPT"), "ell", ELL is not None, "padded", PAD,  "us/launch %.1f" % us,
+print("nodes", n, "edges", s.num_edges, "C", c, "ell", ELL is not None, "padded", PAD,  "us/launch %.1f" % us,
       "alg GB/s %.0f" % (alg / us / 1e3))

@@ -38,7 +38,7 @@ extern "C" {
 
 typedef void* mlqem_stream_t; /* hipStream_t */
 
-#define MLQEM_ABI_VERSION 44 /* bumped whenever a signature below changes; bindings compare it at load time */
+#define MLQEM_ABI_VERSION 45 /* bumped whenever a signature below changes; bindings compare it at load time */
 int mlqem_abi_version(void);
 const char* mlqem_error_string(int code);
 
@@ -1025,6 +1025,39 @@ int mlqem_circuit_features_qasm(const char* qasm, const char* const* gate_names,
 int mlqem_circuit_features_qasm_batch(const char* const* qasm, int64_t count, const char* const* gate_names, int num_gates,
                                       const double* bin_edges, int num_edges, int threads, int64_t* gate_counts,
                                       int64_t* angle_hist, int64_t* failed);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Regression-forest inference (ABI 45).  Replaces model.predict(X) of a fitted scikit-learn RandomForestRegressor /
+ * ExtraTreesRegressor / DecisionTreeRegressor on encode_data rows (blackwater/library/learning/estimator.py:90-148
+ * ScikitLearningModelProcessor; docs/tutorials/vqe_rf*.py; docs/demos/demo1_rf_mimic_zne_100q_twirl.ipynb):
+ *
+ *   out[r, :] = (1 / T) * sum_{t = 0 .. T-1} values[tree_ptr[t] + leaf_t(x[r, :]), :]
+ *
+ * where leaf_t walks tree t from its root with the rule "go left iff x[r, feature] <= threshold".
+ *
+ * Node layout.  The nodes of tree t are nodes[tree_ptr[t] .. tree_ptr[t + 1]) in DEPTH-FIRST PRE-ORDER: node 0 is the root and
+ * the left child of node i is node i + 1, so a 16-byte record holds everything a step needs (one 16-byte load per level):
+ *   thr     the split threshold as float32, rounded TOWARD MINUS INFINITY from the model's float64 threshold.  For a float32 x,
+ *           x <= thr64  <=>  x <= thr32 (thr32 is the largest float32 not above thr64), so the fp32 compare takes scikit-learn's
+ *           branch on every input; round-to-nearest does not.
+ *   feature column of x the node splits on (0 .. F-1), or -1 for a leaf
+ *   right   index within the tree (pre-order numbering) of the right child; a leaf holds its own index
+ *   orig    index within the tree of this node IN THE CALLER'S ORIGINAL NUMBERING: what `leaf` reports (scikit-learn's
+ *           apply()) and the row of `values` a leaf reads -- values[(tree_ptr[t] + orig) * K + k] (float64) keeps the model's order.
+ * tree_ptr[T + 1] (int64, device): tree_ptr[0] = 0, strictly increasing (every tree has a root).
+ * The walk takes at most max_depth steps (the forest's recorded depth: root = depth 0), whatever the node table holds, and every
+ * index it forms from a node record is clamped to the tree / to F: a malformed table gives a wrong answer, never a spin or an
+ * out-of-range read.  x is float32 [n_rows, F] with row stride ldx >= F (columns beyond F are never read).  A NaN feature
+ * compares false and takes the RIGHT branch (scikit-learn without missing-value support does the same; the encoders emit none).
+ * The sum over trees is formed in float64 in tree order, by one thread per (row, output), and divided by T once: results are
+ * bit-identical from call to call and do not depend on n_rows or on how rows are tiled over workgroups.  No workspace.
+ * leaf (optional): int32 [n_rows, T].  Serves 1 <= K <= 16, 1 <= F <= 32767, T >= 1, trees of any size an int32 indexes
+ * (MLQEM_ERR_UNSUPPORTED beyond); n_rows == 0 returns MLQEM_OK without a launch.
+ * ---------------------------------------------------------------------------------------------------- */
+typedef struct mlqem_forest_node { float thr; int32_t feature; int32_t right; int32_t orig; } mlqem_forest_node;
+int mlqem_forest_predict_f32(const float* x, int64_t ldx, int64_t n_rows, int F, const mlqem_forest_node* nodes,
+                             const int64_t* tree_ptr, int T, const double* values, int K, int max_depth, double* out,
+                             int32_t* leaf, mlqem_stream_t stream);
 
 #ifdef __cplusplus
 }

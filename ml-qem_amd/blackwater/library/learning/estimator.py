@@ -2,8 +2,9 @@
 post-processed by a pluggable processor (reference: blackwater/library/learning/estimator.py:22-30,151-328).
 
 In scope: the decorator, the job wrapper, the processor protocol, ``TorchLearningModelProcessor``,
-``EmptyProcessor`` and ``ScikitLearningModelProcessor`` (the random-forest / OLS baselines: same feature rows, the
-model stays on the host CPU by design).  ``ZNEProcessor`` (runs extra noisy circuits
+``EmptyProcessor``, ``ScikitLearningModelProcessor`` (the random-forest / OLS baselines: same feature rows, the
+model stays on the host CPU by design) and ``ForestLearningModelProcessor`` (an addition: the
+same random forests scored on the device by the forest kernel, one launch per ``run()``).  ``ZNEProcessor`` (runs extra noisy circuits
 through a ZNE estimator; no model) is out of scope.
 """
 from __future__ import annotations
@@ -106,6 +107,63 @@ class ScikitLearningModelProcessor(LearningMethodEstimatorProcessor):
             output = float(np.ravel(self._model.predict(row.numpy()))[0])
             total = total + output * float(np.real(term.coeffs[0]))
         return total
+
+
+class ForestLearningModelProcessor(LearningMethodEstimatorProcessor):
+    """The random-forest mitigator of the reference's demos and VQE drivers (``ScikitLearningModelProcessor(rfr, backend)``,
+    reference :90-148) scored on the device: the same per-term ``encode_data`` rows, all (circuit, Pauli term) rows of a ``run()``
+    through ONE launch of the forest kernel (``blackwater.nn.ForestRegressor``), ``output[:, 0] * coeff`` summed per circuit.
+
+    ``model``: a fitted scikit-learn ``RandomForestRegressor`` / ``ExtraTreesRegressor`` / ``DecisionTreeRegressor`` (converted with
+    ``ForestRegressor.from_sklearn``) or a ``ForestRegressor``.  There is no host path: ``device`` must be a GPU."""
+
+    accepts_qasm_text = True     # process_batch scans OpenQASM text natively: PostProcessedJob hands text over unparsed
+
+    def __init__(self, model, backend, device="cuda"):
+        from ...nn.forest import ForestRegressor
+
+        if not isinstance(model, ForestRegressor):
+            model = ForestRegressor.from_sklearn(model)   # BlackwaterException for anything that is not a fitted regression forest
+        self._model = model.to(device)
+        self._device = torch.device(device)
+        self._backend = backend
+        self._properties = get_backend_properties_v1(backend)
+
+    def _score(self, rows: torch.Tensor) -> np.ndarray:
+        """First output of the forest for every row (float64, as scikit-learn's ``predict`` returns it)."""
+        out = self._model.predict(rows.to(self._device, dtype=torch.float32))
+        return out.reshape(rows.shape[0], -1)[:, 0].cpu().numpy()
+
+    def process(self, expectation_value, circuits, observables, parameter_values):
+        total = 0.0
+        for term in observables:
+            row, _ = encode_data(circuits=[circuits], properties=self._properties, ideal_exp_vals=[[0.0]],
+                                 noisy_exp_vals=[[expectation_value]], num_qubits=1,
+                                 meas_bases=encode_pauli_sum_op([(str(term.paulis[0]), 1.0)]), native=isinstance(circuits, str))
+            total = total + float(self._score(row)[0]) * float(np.real(term.coeffs[0]))
+        return total
+
+    def process_batch(self, expectation_values, circuits, observables, parameter_values):
+        """All (circuit, Pauli term) rows of one ``run()`` through ONE forest launch; results equal ``process`` applied circuit by
+        circuit (the same rows, the same per-circuit order of the sum)."""
+        rows, owners, coeffs, values, bases = [], [], [], [], []
+        for k, (value, circuit, obs) in enumerate(zip(expectation_values, circuits, observables)):
+            for term in obs:
+                rows.append(circuit)
+                owners.append(k)
+                coeffs.append(float(np.real(term.coeffs[0])))
+                values.append([float(value)])
+                bases.append(encode_pauli_sum_op([(str(term.paulis[0]), 1.0)])[0])
+        if not rows:
+            return [0.0] * len(circuits)
+        native = all(isinstance(c, str) for c in rows)
+        model_input, _ = encode_data(circuits=rows, properties=self._properties, ideal_exp_vals=[[0.0]] * len(rows),
+                                     noisy_exp_vals=values, num_qubits=1, meas_bases=bases, native=native)
+        out = self._score(model_input).tolist()
+        totals = [0.0] * len(circuits)
+        for k, o, c in zip(owners, out, coeffs):
+            totals[k] = totals[k] + o * c
+        return totals
 
 
 class EmptyProcessor(LearningMethodEstimatorProcessor):

@@ -2082,3 +2082,42 @@ def dense_segment_max_bwd_(gx, x, xmax, s, ties, gmax_rank1, plan_out: DensePlan
     _lib.check(code, "mlqem_dense_segment_max_bwd_f32")
     return gx
 
+
+
+FOREST_MAX_OUTPUTS = 16     # K the forest kernel serves
+FOREST_MAX_FEATURES = 32767
+
+
+def forest_predict(x, nodes, tree_ptr, values, max_depth, *, want_leaf=False, out=None, leaf_out=None):
+    """Regression-forest inference (mlqem_forest_predict_f32): ``(out, leaf)`` with ``out`` float64 [n, K] = the mean over trees
+    of the leaf values of every row of ``x`` (float32 [n, F], row stride >= F) and ``leaf`` int32 [n, T] (the leaf each tree
+    puts the row in, in the model's own node numbering; None unless ``want_leaf`` or ``leaf_out`` is given).
+
+    ``nodes``: int32 [N, 4] packed records (thr32 bits, feature, right, orig) in depth-first pre-order, ``tree_ptr``: int64
+    [T + 1], ``values``: float64 [N, K] in the model's node order -- the buffers of ``blackwater.nn.ForestRegressor``.
+    Nothing here waits for the device or reads a tensor's contents, and with ``out`` (and ``leaf_out``) given nothing is
+    allocated: the call can be captured in a hipGraph."""
+    ldx = _mat(x, "x")
+    n, f = int(x.shape[0]), int(x.shape[1])
+    _mat(nodes, "nodes", torch.int32)
+    _mat(values, "values", torch.float64)
+    if nodes.shape[1] != 4 or not nodes.is_contiguous() or not values.is_contiguous() or values.shape[0] != nodes.shape[0]:
+        raise ValueError(f"forest: want contiguous nodes [N, 4] and values [N, K], got {tuple(nodes.shape)} and {tuple(values.shape)}")
+    t = int(tree_ptr.shape[0]) - 1
+    _vec(tree_ptr, "tree_ptr", 2, torch.int64)
+    k = int(values.shape[1])
+    if any(b.device != x.device for b in (nodes, tree_ptr, values)):
+        raise ValueError(f"forest: x is on {x.device}, the forest on {nodes.device}")
+    if out is None:
+        out = torch.empty((n, k), dtype=torch.float64, device=x.device)
+    elif not out.is_cuda or out.dtype != torch.float64 or tuple(out.shape) != (n, k) or not out.is_contiguous():
+        raise ValueError(f"out: want contiguous float64 [{n}, {k}] on the device, got {tuple(out.shape)} {out.dtype}")
+    if leaf_out is None and want_leaf:
+        leaf_out = torch.empty((n, t), dtype=torch.int32, device=x.device)
+    elif leaf_out is not None and (not leaf_out.is_cuda or leaf_out.dtype != torch.int32 or tuple(leaf_out.shape) != (n, t)
+                                   or not leaf_out.is_contiguous()):
+        raise ValueError(f"leaf_out: want contiguous int32 [{n}, {t}] on the device, got {tuple(leaf_out.shape)} {leaf_out.dtype}")
+    code = _lib.load().mlqem_forest_predict_f32(_p(x), ldx, n, f, _p(nodes), _p(tree_ptr), t, _p(values), k, int(max_depth),
+                                                _p(out), _p(leaf_out), _stream())
+    _lib.check(code, "mlqem_forest_predict_f32")
+    return out, leaf_out

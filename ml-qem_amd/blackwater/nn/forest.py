@@ -1,0 +1,218 @@
+"""Regression forests on the device: ``ForestRegressor`` scores a fitted random forest with the native forest kernel.
+
+The reference's strongest mitigator is a scikit-learn ``RandomForestRegressor`` on ``encode_data`` rows
+(docs/tutorials/vqe_rf*.py, docs/demos/demo1_rf_mimic_zne_100q_twirl.ipynb; blackwater/library/learning/estimator.py:90-148
+calls ``model.predict`` once per Pauli term).  This module holds such a forest as registered buffers -- so ``.to(device)``,
+``state_dict()`` and ``load_state_dict(strict=True)`` work and a checkpoint depends neither on pickle nor on the scikit-learn
+version that fitted it -- and predicts with one launch of ``mlqem_forest_predict_f32`` for any number of rows.
+
+Buffers (include/mlqem_hip.h documents the node record):
+  ``nodes``     int32 [N, 4]: (threshold as float32 bits, feature or -1, right child, original index) per node, every tree in
+                depth-first pre-order (the left child of node i is node i + 1);
+  ``tree_ptr``  int64 [T + 1]: tree t owns nodes tree_ptr[t] .. tree_ptr[t + 1];
+  ``value``     float64 [N, K]: the trees' node values in the model's own node order;
+  ``meta``      int64 [2]: (number of features, maximum depth).
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from ..exception import BlackwaterException
+from ..native import ops
+
+TREE_LEAF = -1   # scikit-learn's marker in children_left / children_right
+
+
+def floor_to_float32(thr64: np.ndarray) -> np.ndarray:
+    """The largest float32 <= each float64 threshold.  scikit-learn compares a float32 feature with the float64 threshold; for a
+    float32 x, ``x <= thr64`` holds exactly when ``x <= floor_to_float32(thr64)`` (x is itself a float32 not above thr64, hence not
+    above the largest such; the converse because the rounded threshold is not above thr64).  Rounding to nearest moves rows that
+    sit on a split value to the other child."""
+    thr64 = np.asarray(thr64, dtype=np.float64)
+    with np.errstate(over="ignore"):
+        thr32 = thr64.astype(np.float32)
+    above = thr32.astype(np.float64) > thr64
+    thr32[above] = np.nextafter(thr32[above], np.float32(-np.inf))
+    return thr32
+
+
+def _pack(tree_ptr, feature, threshold, left, right, n_features):
+    """Validates the forest and returns (nodes int32 [N, 4], tree_ptr int64, max_depth).  Works on whole levels of all trees at once."""
+    tree_ptr = np.asarray(tree_ptr)
+    if tree_ptr.ndim != 1 or tree_ptr.size < 2 or not np.issubdtype(tree_ptr.dtype, np.integer):
+        raise ValueError("forest: tree_ptr must be a 1-D integer array with at least two entries")
+    tree_ptr = tree_ptr.astype(np.int64)
+    n = int(tree_ptr[-1])
+    counts = np.diff(tree_ptr)
+    if tree_ptr[0] != 0 or (counts < 1).any():
+        raise ValueError("forest: tree_ptr must start at 0 and increase strictly (every tree has a root)")
+    if counts.max() > 2**31 - 1:
+        raise ValueError("forest: a tree has more nodes than an int32 indexes")
+    arrays = {}
+    for name, a in (("feature", feature), ("threshold", threshold), ("left", left), ("right", right)):
+        a = np.asarray(a)
+        if a.shape != (n,):
+            raise ValueError(f"forest: {name} must have one entry per node ({n}), got shape {a.shape}")
+        if name != "threshold" and not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"forest: {name} must be an integer array")
+        arrays[name] = a.astype(np.float64 if name == "threshold" else np.int64)
+    feature, threshold, left, right = (arrays[k] for k in ("feature", "threshold", "left", "right"))
+    n_features = int(n_features)
+    if not 1 <= n_features <= ops.FOREST_MAX_FEATURES:
+        raise ValueError(f"forest: n_features must be in 1..{ops.FOREST_MAX_FEATURES}, got {n_features}")
+
+    offset = np.repeat(tree_ptr[:-1], counts)      # first node of the tree every node belongs to
+    size_of = np.repeat(counts, counts)
+    is_leaf = left == TREE_LEAF
+    if ((right == TREE_LEAF) != is_leaf).any():
+        raise ValueError("forest: a node has one child: left and right must both be -1 (a leaf) or both be nodes")
+    inner = np.flatnonzero(~is_leaf)
+    for name, child in (("left", left), ("right", right)):
+        bad = (child[inner] < 0) | (child[inner] >= size_of[inner])
+        if bad.any():
+            raise ValueError(f"forest: node {int(inner[bad][0])}: {name} child {int(child[inner[bad][0]])} is out of range")
+    bad = (feature[inner] < 0) | (feature[inner] >= n_features)
+    if bad.any():
+        raise ValueError(f"forest: node {int(inner[bad][0])} splits on feature {int(feature[inner[bad][0]])}, the rows have {n_features}")
+    if np.isnan(threshold[inner]).any():
+        raise ValueError("forest: a split threshold is NaN")
+    gleft, gright = offset[inner] + left[inner], offset[inner] + right[inner]
+    parents = np.bincount(np.concatenate([gleft, gright]), minlength=n)
+    if (parents > 1).any():
+        raise ValueError(f"forest: node {int(np.flatnonzero(parents > 1)[0])} has more than one parent")
+    if parents[tree_ptr[:-1]].any():
+        raise ValueError("forest: a root is some node's child (a cycle)")
+    # every node now has at most one parent and the roots none: level-by-level descent from the roots visits a node at most once
+    child_l, child_r = np.full(n, -1, np.int64), np.full(n, -1, np.int64)
+    child_l[inner], child_r[inner] = gleft, gright
+    levels, frontier, seen = [], tree_ptr[:-1].copy(), 0
+    while frontier.size:
+        levels.append(frontier)
+        seen += frontier.size
+        kids = np.concatenate([child_l[frontier], child_r[frontier]])
+        frontier = kids[kids >= 0]
+    if seen != n:
+        raise ValueError(f"forest: {n - seen} nodes cannot be reached from their root (a cycle or a detached subtree)")
+    max_depth = len(levels) - 1
+    size = np.ones(n, np.int64)                    # nodes of the subtree under each node, deepest level first
+    for lv in reversed(levels):
+        p = lv[child_l[lv] >= 0]
+        size[p] += size[child_l[p]] + size[child_r[p]]
+    pos = np.zeros(n, np.int64)                    # pre-order position within the tree
+    for lv in levels:
+        p = lv[child_l[lv] >= 0]
+        pos[child_l[p]] = pos[p] + 1
+        pos[child_r[p]] = pos[p] + 1 + size[child_l[p]]
+    dst = offset + pos
+    nodes = np.zeros((n, 4), np.int32)
+    thr32 = floor_to_float32(np.where(is_leaf, 0.0, threshold))
+    nodes[dst, 0] = thr32.view(np.int32)
+    nodes[dst, 1] = np.where(is_leaf, -1, feature)
+    nodes[dst, 2] = np.where(is_leaf, pos, pos[np.maximum(child_r, 0)])
+    nodes[dst, 3] = np.arange(n) - offset
+    return nodes, tree_ptr, max_depth
+
+
+class ForestRegressor(torch.nn.Module):
+    """A fitted regression forest (mean of T regression trees with K outputs) as a torch module on the native kernel.
+
+    Build one with ``from_sklearn``, ``from_arrays`` or ``from_state_dict``; both array constructors validate the forest on the
+    host (``ValueError``), so a malformed one never reaches the device."""
+
+    def __init__(self, nodes: torch.Tensor, tree_ptr: torch.Tensor, value: torch.Tensor, n_features: int, max_depth: int):
+        super().__init__()
+        self.register_buffer("nodes", nodes)
+        self.register_buffer("tree_ptr", tree_ptr)
+        self.register_buffer("value", value)
+        self.register_buffer("meta", torch.tensor([int(n_features), int(max_depth)], dtype=torch.int64))
+        self._set_meta()
+
+    def _set_meta(self):
+        self.n_features, self.max_depth = (int(v) for v in self.meta.tolist())   # host copies: predict() never reads a device value
+        self.n_trees, self.n_outputs = int(self.tree_ptr.shape[0]) - 1, int(self.value.shape[1])
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        super()._load_from_state_dict(*args, **kwargs)
+        self._set_meta()
+
+    @classmethod
+    def from_arrays(cls, tree_ptr, feature, threshold, left, right, value, n_features) -> "ForestRegressor":
+        """``tree_ptr`` [T + 1]; per node, concatenated over the trees: ``feature``, ``threshold`` (float64), ``left`` / ``right``
+        (child index WITHIN the tree, -1 for a leaf) and ``value`` [N, K] (or [N], or scikit-learn's [N, K, 1])."""
+        nodes, tree_ptr, max_depth = _pack(tree_ptr, feature, threshold, left, right, n_features)
+        value = np.asarray(value, dtype=np.float64)
+        n = nodes.shape[0]
+        if value.ndim == 3 and value.shape[2] == 1:
+            value = value[:, :, 0]
+        if value.ndim == 1:
+            value = value[:, None]
+        if value.ndim != 2 or value.shape[0] != n or not 1 <= value.shape[1] <= ops.FOREST_MAX_OUTPUTS:
+            raise ValueError(f"forest: value must be [{n}, K] with 1 <= K <= {ops.FOREST_MAX_OUTPUTS}, got shape {value.shape}")
+        return cls(torch.from_numpy(nodes), torch.from_numpy(tree_ptr), torch.from_numpy(np.ascontiguousarray(value)),
+                   n_features, max_depth)
+
+    @classmethod
+    def from_sklearn(cls, model) -> "ForestRegressor":
+        """From a fitted ``RandomForestRegressor``, ``ExtraTreesRegressor`` or ``DecisionTreeRegressor``."""
+        try:
+            from sklearn.ensemble import ExtraTreesRegressor, RandomForestRegressor
+            from sklearn.tree import DecisionTreeRegressor
+        except ImportError as exc:
+            raise BlackwaterException("ForestRegressor.from_sklearn needs scikit-learn; use from_arrays or from_state_dict") from exc
+        if isinstance(model, (RandomForestRegressor, ExtraTreesRegressor)):
+            if not hasattr(model, "estimators_"):
+                raise BlackwaterException(f"{type(model).__name__} is not fitted")
+            trees = [est.tree_ for est in model.estimators_]
+        elif isinstance(model, DecisionTreeRegressor):
+            if not hasattr(model, "tree_"):
+                raise BlackwaterException("DecisionTreeRegressor is not fitted")
+            trees = [model.tree_]
+        else:
+            raise BlackwaterException("ForestRegressor.from_sklearn takes a fitted RandomForestRegressor, ExtraTreesRegressor or "
+                                      f"DecisionTreeRegressor, got {type(model).__name__}")
+        tree_ptr = np.concatenate([[0], np.cumsum([t.node_count for t in trees])]).astype(np.int64)
+        cat = lambda name: np.concatenate([getattr(t, name) for t in trees])  # noqa: E731
+        return cls.from_arrays(tree_ptr, cat("feature"), cat("threshold"), cat("children_left"), cat("children_right"),
+                               cat("value"), int(model.n_features_in_))
+
+    @classmethod
+    def from_state_dict(cls, state_dict) -> "ForestRegressor":
+        """A module with buffers of the checkpoint's sizes, strict-loaded (buffer shapes depend on the forest, so there is no
+        forest-independent module to load into)."""
+        missing = [k for k in ("nodes", "tree_ptr", "value", "meta") if k not in state_dict]
+        if missing:
+            raise ValueError(f"forest checkpoint lacks {missing}")
+        nodes, tree_ptr, value, meta = (state_dict[k] for k in ("nodes", "tree_ptr", "value", "meta"))
+        if (nodes.dtype != torch.int32 or nodes.dim() != 2 or nodes.shape[1] != 4 or tree_ptr.dtype != torch.int64 or tree_ptr.dim() != 1
+                or tree_ptr.numel() < 2 or value.dtype != torch.float64 or value.dim() != 2 or value.shape[0] != nodes.shape[0]
+                or not 1 <= value.shape[1] <= ops.FOREST_MAX_OUTPUTS or meta.dtype != torch.int64 or tuple(meta.shape) != (2,)):
+            raise ValueError("forest checkpoint: buffers have the wrong dtype or shape")
+        counts = tree_ptr[1:] - tree_ptr[:-1]
+        if int(tree_ptr[0]) != 0 or int(tree_ptr[-1]) != nodes.shape[0] or bool((counts < 1).any()):
+            raise ValueError("forest checkpoint: tree_ptr does not partition the nodes")
+        f, depth = (int(v) for v in meta.tolist())
+        if not 1 <= f <= ops.FOREST_MAX_FEATURES or not 0 <= depth < nodes.shape[0]:
+            raise ValueError("forest checkpoint: meta (n_features, max_depth) is out of range")
+        module = cls(torch.empty_like(nodes, device="cpu"), torch.empty_like(tree_ptr, device="cpu"),
+                     torch.empty_like(value, device="cpu"), f, depth)
+        module.load_state_dict(state_dict, strict=True)
+        return module
+
+    def _run(self, x: torch.Tensor, want_leaf: bool):
+        if x.dim() != 2 or x.shape[1] != self.n_features:
+            raise ValueError(f"forest: want rows of {self.n_features} features, got {tuple(x.shape)}")
+        return ops.forest_predict(x, self.nodes, self.tree_ptr, self.value, self.max_depth, want_leaf=want_leaf)
+
+    def predict(self, x: torch.Tensor) -> torch.Tensor:
+        """float64 [n, K] ([n] when K == 1, as scikit-learn): the mean over the trees of each row's leaf values."""
+        out, _ = self._run(x, False)
+        return out[:, 0] if self.n_outputs == 1 else out
+
+    def apply(self, x: torch.Tensor) -> torch.Tensor:
+        """int32 [n, T]: the leaf every tree puts each row in, in the model's own node numbering (scikit-learn's ``apply``)."""
+        return self._run(x, True)[1]
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """float32 [n, K]: ``predict`` rounded, so the module composes with float32 torch code."""
+        return self._run(x, False)[0].to(torch.float32)

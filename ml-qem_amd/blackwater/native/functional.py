@@ -6,6 +6,7 @@ generic differentiable building blocks ``csr_aggregate``, ``linear`` and ``segme
 from __future__ import annotations
 
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -413,8 +414,9 @@ def relu_dropout_add(u, residual=None, drop_p=0.0, seed=0):
 
 
 def _mask_grad(g, y, drop_p):
-    """Gradient through the fused ReLU / dropout epilogue (the mask is read back from the saved output)."""
-    g = ops.rowmajor(g)
+    """Gradient through the fused ReLU / dropout epilogue (the mask is read back from the saved output); a pooled gradient that its
+    layer cannot compute inside an aggregation is written out first."""
+    g = ops.rowmajor(g.materialise() if isinstance(g, ops.PooledGrad) else g)
     if y is None:
         return g
     return ops.relu_dropout_bwd(g, y, 1.0 / (1.0 - drop_p) if drop_p > 0 else 1.0)
@@ -465,6 +467,15 @@ def _fan_in_t(gs, ws, i, w_minus=None, gate=None, gate_scale=1.0):
     return gx
 
 
+def _wgrad_blocks(gs, x, o):
+    """(gw [J, O, I], gb [J, O]) with gw[j] = gs[j]^T x and gb[j] = the column sums of gs[j] (the pass's ones column): ONE pass over x."""
+    nb, ow, i = len(gs), (o + 3) // 4 * 4, x.shape[1]
+    gw = torch.empty((nb * ow, i), dtype=torch.float32, device=x.device)
+    gb = torch.empty(nb * ow, dtype=torch.float32, device=x.device)
+    ops.linear_wgrad_parts(gs, x, gw, gb)
+    return gw.reshape(nb, ow, i)[:, :o], gb.reshape(nb, ow)[:, :o]
+
+
 class _ChebLayer(Function):
     """ChebConv (K = 2, 3) as ONE autograd node, evaluated PROJECT-FIRST (Clenshaw form).
 
@@ -475,65 +486,80 @@ class _ChebLayer(Function):
         b_1 = c_1 + 2 L^ c_2               aggregation at the OUTPUT width, "+ c_1" in its epilogue
         y   = act((c_0 - c_2) + L^ b_1 + b)     c_0 - c_2 = x (W_0 - W_2)^T: folded into the weights
 
-    so the aggregations move O instead of I columns (10 vs 22 in the first layer, 1 vs 10 in the second), and the
-    backward needs only x: g_b1 = L^T g, g_c2 = 2 L^T g_b1, then ONE weight-gradient pass x^T [g | g_b1 | g_c2] and ONE
-    GEMM gx = g (W_0 - W_2) + g_b1 W_1 + g_c2 W_2.  Same algebra as the reference, different fp32 rounding order
-    (covered by the 1e-5 parity tests)."""
+    so the aggregations move O instead of I columns (10 vs 22 in the first layer, 1 vs 10 in the second), and the backward needs only x: g_b1 = L^T g,
+    g_c2 = 2 L^T g_b1, then ONE weight-gradient pass x^T [g | g_b1 | g_c2] and ONE GEMM gx = g (W_0 - W_2) + g_b1 W_1 + g_c2 W_2.  Same algebra as the
+    reference, different fp32 rounding order (covered by the 1e-5 parity tests)."""
 
     @staticmethod
-    def forward(ctx, x, bias, struct: GraphStructure, relu, drop_p, seed, defer_mask, x_gate_scale, *ws, pre=None, pool=None):
-        s, k = struct, len(ws)
-        x = _padded_rows(ops.rowmajor(x))
-        o = ws[0].shape[0]
-        ow = (o + 3) // 4 * 4
-        ws = [w.contiguous() for w in ws]
-        w_minus = [ws[2], None, None] if k == 3 else None          # block 0 multiplies by W_0 - W_2
-        # pre: the projections c_k, already produced by a GEMM shared with other layers that read the same x
-        c = list(pre) if pre is not None else _fan_out(x, ws, [bias] + [None] * (k - 1), w_minus)
-        lap = dict(ell=s.in_ell, cscale=s.cheb_dinv, rscale=s.derived("cheb_neg"))
-        act = dict(relu=relu, drop_p=drop_p, seed=seed)
-        # pool: the pooled means of y from the launch that writes y (ops.csr_aggregate)
-        if k == 2:
-            y = ops.csr_aggregate(c[1], s.in_ptr, s.in_src, z=c[0], beta=1.0, out=c[0], pool=pool, **lap, **act)
-        else:
-            ops.csr_aggregate(c[2], s.in_ptr, s.in_src, alpha=2.0, z=c[1], beta=1.0, out=c[1], **lap)
-            y = ops.csr_aggregate(c[1], s.in_ptr, s.in_src, z=c[0], beta=1.0, out=c[0], pool=pool, **lap, **act)
-        ctx.struct, ctx.k, ctx.relu, ctx.drop_p, ctx.has_bias, ctx.dims = s, k, relu, drop_p, bias is not None, (o, ow)
-        ctx.x_gate_scale = x_gate_scale
-        ctx.save_for_backward(x, y if ((relu or drop_p > 0) and not defer_mask) else None, *ws)
+    def forward(ctx, x, bias, struct: GraphStructure, relu, drop_p, seed, defer_mask, x_gate_scale, *ws):
+        y, sv = _cheb_forward(x, ws, bias, struct, relu, drop_p, seed, defer_mask=defer_mask, x_gate_scale=x_gate_scale)
+        ctx.save_for_backward(sv.x, sv.y, *sv.ws)
+        ctx.rest = sv[3:]
         return y
 
     @staticmethod
-    def backward(ctx, g, blocks_only=False):
-        k, s, (o, ow) = ctx.k, ctx.struct, ctx.dims
+    def backward(ctx, g):
         x, y, *ws = ctx.saved_tensors
-        n, i = x.shape
-        lap_t = dict(ell=s.out_ell, cscale=s.derived("cheb_neg"), rscale=s.cheb_dinv)
-        if isinstance(g, ops.PooledGrad) and k >= 2 and y is None:      # the pooled gradient, computed inside its first aggregation
-            g1, g = ops.pooled_grad_aggregate(g, s.out_ptr, s.out_dst, s.out_ell, s.derived("cheb_neg"), rscale=s.cheb_dinv)
-            gs = [g, g1]
-        else:
-            if isinstance(g, ops.PooledGrad):
-                g = g.materialise()
-            g = _padded_rows(_mask_grad(g, y, ctx.drop_p))
-            gs = [g]
-            if k >= 2:
-                gs.append(ops.csr_aggregate(g, s.out_ptr, s.out_dst, **lap_t))
-        if k == 3:
-            gs.append(ops.csr_aggregate(gs[1], s.out_ptr, s.out_dst, alpha=2.0, **lap_t))
-        if blocks_only:     # the caller runs ONE weight-gradient pass over x for several layers (see cheb_grads_from_blocks)
-            return gs
-        gw = torch.empty((k * ow, i), dtype=torch.float32, device=x.device)
-        gb = torch.empty(k * ow, dtype=torch.float32, device=x.device)
-        ops.linear_wgrad_parts(gs, x, gw, gb)
-        gw = gw.reshape(k, ow, i)[:, :o]
-        gws = [gw[0], gw[1], gw[2] - gw[0]] if k == 3 else [gw[j] for j in range(k)]
-        gx = None
-        if ctx.needs_input_grad[0]:
-            gated = ctx.x_gate_scale is not None
-            gx = _fan_in_t(gs, ws, i, w_minus=[ws[2], None, None] if k == 3 else None, gate=x if gated else None,
-                           gate_scale=ctx.x_gate_scale if gated else 1.0)
-        return (gx, gb[:o] if ctx.has_bias else None, None, None, None, None, None, None, *gws)
+        r = _cheb_backward(_ChebSaved(x, y, ws, *ctx.rest), g, ctx.needs_input_grad[0])
+        return (r.x, r.b, None, None, None, None, None, None, *r.ws)
+
+
+# What a project-first layer keeps for its backward, and the gradients that backward returns.  The plain functions below know
+# nothing about autograd: the layer nodes put a record's tensors (its leading fields) through ctx.save_for_backward, _FamilyAGraph
+# keeps the records whole.  y: the layer's output as its ReLU / dropout mask, None without a mask or with a deferred one.
+_ChebSaved = namedtuple("_ChebSaved", "x y ws struct k drop_p has_bias o x_gate_scale")
+_ChebGrads = namedtuple("_ChebGrads", "x b ws")
+_SAGESaved = namedtuple("_SAGESaved", "x wl wr y struct drop_p has_bias o x_gate_scale")
+_SAGEGrads = namedtuple("_SAGEGrads", "x wl bl wr")
+_GCNSaved = namedtuple("_GCNSaved", "x w y struct drop_p x_gate_scale")
+_GCNGrads = namedtuple("_GCNGrads", "x w b x_colsum", defaults=(None,))    # x_colsum: x.sum(0), from the fused backward only
+
+
+def _x_gate(sv):     # gx takes the mask of the layer below when that layer deferred it (see "Mask hand-over")
+    return dict(gate=sv.x, gate_scale=sv.x_gate_scale) if sv.x_gate_scale is not None else dict(gate=None, gate_scale=1.0)
+
+
+def _cheb_forward(x, ws, bias, struct, relu, drop_p, seed, *, defer_mask, x_gate_scale, pre=None, pool=None):
+    """``_ChebLayer`` (K = 2, 3) -> (y, _ChebSaved).  pre: the projections c_k, already produced by a GEMM shared with other layers
+    that read the same x; pool: the pooled means of y from the launch that writes y (ops.csr_aggregate)."""
+    s, k = struct, len(ws)
+    x = _padded_rows(ops.rowmajor(x))
+    ws = [w.contiguous() for w in ws]
+    w_minus = [ws[2], None, None] if k == 3 else None          # block 0 multiplies by W_0 - W_2
+    c = list(pre) if pre is not None else _fan_out(x, ws, [bias] + [None] * (k - 1), w_minus)
+    lap = dict(ell=s.in_ell, cscale=s.cheb_dinv, rscale=s.derived("cheb_neg"))
+    act = dict(relu=relu, drop_p=drop_p, seed=seed)
+    if k == 2:
+        y = ops.csr_aggregate(c[1], s.in_ptr, s.in_src, z=c[0], beta=1.0, out=c[0], pool=pool, **lap, **act)
+    else:
+        ops.csr_aggregate(c[2], s.in_ptr, s.in_src, alpha=2.0, z=c[1], beta=1.0, out=c[1], **lap)
+        y = ops.csr_aggregate(c[1], s.in_ptr, s.in_src, z=c[0], beta=1.0, out=c[0], pool=pool, **lap, **act)
+    mask = y if ((relu or drop_p > 0) and not defer_mask) else None
+    return y, _ChebSaved(x, mask, ws, s, k, drop_p, bias is not None, ws[0].shape[0], x_gate_scale)
+
+
+def _cheb_grad_blocks(sv, g):
+    """[g, g_b1, (K = 3:) g_c2]: the gradient at y with the layer's mask applied, and the transposed aggregations of it."""
+    s = sv.struct
+    lap_t = dict(ell=s.out_ell, cscale=s.derived("cheb_neg"), rscale=s.cheb_dinv)
+    if isinstance(g, ops.PooledGrad) and sv.y is None:      # the pooled gradient, computed inside its first aggregation
+        g1, g = ops.pooled_grad_aggregate(g, s.out_ptr, s.out_dst, s.out_ell, s.derived("cheb_neg"), rscale=s.cheb_dinv)
+        gs = [g, g1]
+    else:
+        g = _padded_rows(_mask_grad(g, sv.y, sv.drop_p))
+        gs = [g, ops.csr_aggregate(g, s.out_ptr, s.out_dst, **lap_t)]
+    if sv.k == 3:
+        gs.append(ops.csr_aggregate(gs[1], s.out_ptr, s.out_dst, alpha=2.0, **lap_t))
+    return gs
+
+
+def _cheb_backward(sv, g, need_x):
+    gs = _cheb_grad_blocks(sv, g)
+    x, ws, k = sv.x, sv.ws, sv.k
+    gw, gb = _wgrad_blocks(gs, x, sv.o)
+    gws = [gw[0], gw[1], gw[2] - gw[0]] if k == 3 else [gw[0], gw[1]]
+    gx = _fan_in_t(gs, ws, x.shape[1], w_minus=[ws[2], None, None] if k == 3 else None, **_x_gate(sv)) if need_x else None
+    return _ChebGrads(gx, gb[0] if sv.has_bias else None, gws)
 
 
 class _ChebLayerRecurrence(Function):
@@ -600,48 +626,48 @@ def cheb_layer(x, ws, bias, struct, relu=False, drop_p=0.0, seed=0, defer_mask=F
 
 
 class _SAGELayer(Function):
-    """SAGEConv as ONE autograd node, PROJECT-FIRST: y = act(mean_in(x W_l^T) + x W_r^T + b) -- one GEMM produces both
-    projections from one read of x, the mean runs at the output width with "+ x W_r^T + b" in its epilogue (PyG
-    aggregates at the input width and projects afterwards: same algebra, different fp32 rounding order).
-    Backward: g_p = mean_in^T(g); one weight-gradient pass x^T [g_p | g]; gx = g_p W_l + g W_r in one GEMM."""
+    """SAGEConv as ONE autograd node, PROJECT-FIRST: y = act(mean_in(x W_l^T) + x W_r^T + b) -- one GEMM produces both projections from one read of x,
+    the mean runs at the output width with "+ x W_r^T + b" in its epilogue (PyG aggregates at the input width and projects afterwards: same algebra,
+    different fp32 rounding order). Backward: g_p = mean_in^T(g); one weight-gradient pass x^T [g_p | g]; gx = g_p W_l + g W_r in one GEMM."""
 
     @staticmethod
-    def forward(ctx, x, wl, bl, wr, struct: GraphStructure, relu, drop_p, seed, defer_mask, x_gate_scale, pre=None, pool=None):
-        s = struct
-        x = _padded_rows(ops.rowmajor(x))
-        o = wl.shape[0]
-        ow = (o + 3) // 4 * 4
-        wl, wr = wl.contiguous(), wr.contiguous()
-        p, r = pre if pre is not None else _fan_out(x, [wl, wr], [None, bl])   # the bias rides on the root term
-        y = ops.csr_aggregate(p, s.in_ptr, s.in_src, ell=s.in_ell, rscale=s.sage_rinv, dself=s.derived("sage_dself"),
-                              z=r, beta=1.0, relu=relu, drop_p=drop_p, seed=seed, out=r, pool=pool)
-        ctx.struct, ctx.relu, ctx.drop_p, ctx.has_bias, ctx.dims = s, relu, drop_p, bl is not None, (o, ow)
-        ctx.x_gate_scale = x_gate_scale
-        ctx.save_for_backward(x, wl, wr, y if ((relu or drop_p > 0) and not defer_mask) else None)
+    def forward(ctx, x, wl, bl, wr, struct: GraphStructure, relu, drop_p, seed, defer_mask, x_gate_scale):
+        y, sv = _sage_forward(x, wl, bl, wr, struct, relu, drop_p, seed, defer_mask=defer_mask, x_gate_scale=x_gate_scale)
+        ctx.save_for_backward(*sv[:4])
+        ctx.rest = sv[4:]
         return y
 
     @staticmethod
-    def backward(ctx, g, blocks_only=False):
-        x, wl, wr, y = ctx.saved_tensors
-        s, (o, ow) = ctx.struct, ctx.dims
-        n, i = x.shape
-        if isinstance(g, ops.PooledGrad) and y is None:
-            gp, g = ops.pooled_grad_aggregate(g, s.out_ptr, s.out_dst, s.out_ell, s.sage_rinv, dself=s.derived("sage_dself"))
-        else:
-            if isinstance(g, ops.PooledGrad):
-                g = g.materialise()
-            g = _padded_rows(_mask_grad(g, y, ctx.drop_p))
-            gp = ops.csr_aggregate(g, s.out_ptr, s.out_dst, ell=s.out_ell, cscale=s.sage_rinv, dself=s.derived("sage_dself"))
-        if blocks_only:
-            return [gp, g]
-        gw = torch.empty((2 * ow, i), dtype=torch.float32, device=x.device)
-        gb = torch.empty(2 * ow, dtype=torch.float32, device=x.device)
-        ops.linear_wgrad_parts([gp, g], x, gw, gb)
-        gx = None
-        if ctx.needs_input_grad[0]:
-            gated = ctx.x_gate_scale is not None
-            gx = _fan_in_t([gp, g], [wl, wr], i, gate=x if gated else None, gate_scale=ctx.x_gate_scale if gated else 1.0)
-        return gx, gw[:o], gb[ow:ow + o] if ctx.has_bias else None, gw[ow:ow + o], None, None, None, None, None, None
+    def backward(ctx, g):
+        r = _sage_backward(_SAGESaved(*ctx.saved_tensors, *ctx.rest), g, ctx.needs_input_grad[0])
+        return r.x, r.wl, r.bl, r.wr, None, None, None, None, None, None
+
+
+def _sage_forward(x, wl, bl, wr, struct, relu, drop_p, seed, *, defer_mask, x_gate_scale, pre=None, pool=None):
+    """``_SAGELayer`` -> (y, _SAGESaved).  pre: the two projections from a shared GEMM; pool: as in ``_cheb_forward``."""
+    s = struct
+    x, wl, wr = _padded_rows(ops.rowmajor(x)), wl.contiguous(), wr.contiguous()
+    p, r = pre if pre is not None else _fan_out(x, [wl, wr], [None, bl])   # the bias rides on the root term
+    y = ops.csr_aggregate(p, s.in_ptr, s.in_src, ell=s.in_ell, rscale=s.sage_rinv, dself=s.derived("sage_dself"),
+                          z=r, beta=1.0, relu=relu, drop_p=drop_p, seed=seed, out=r, pool=pool)
+    mask = y if ((relu or drop_p > 0) and not defer_mask) else None
+    return y, _SAGESaved(x, wl, wr, mask, s, drop_p, bl is not None, wl.shape[0], x_gate_scale)
+
+
+def _sage_grad_blocks(sv, g):
+    """[g_p, g]: the gradient at y with the layer's mask applied, and its transposed mean before it."""
+    s = sv.struct
+    if isinstance(g, ops.PooledGrad) and sv.y is None:
+        return list(ops.pooled_grad_aggregate(g, s.out_ptr, s.out_dst, s.out_ell, s.sage_rinv, dself=s.derived("sage_dself")))
+    g = _padded_rows(_mask_grad(g, sv.y, sv.drop_p))
+    return [ops.csr_aggregate(g, s.out_ptr, s.out_dst, ell=s.out_ell, cscale=s.sage_rinv, dself=s.derived("sage_dself")), g]
+
+
+def _sage_backward(sv, g, need_x):
+    gs = _sage_grad_blocks(sv, g)
+    gw, gb = _wgrad_blocks(gs, sv.x, sv.o)
+    gx = _fan_in_t(gs, [sv.wl, sv.wr], sv.x.shape[1], **_x_gate(sv)) if need_x else None
+    return _SAGEGrads(gx, gw[0], gb[1] if sv.has_bias else None, gw[1])
 
 
 def sage_layer(x, wl, bl, wr, struct, relu=False, drop_p=0.0, seed=0, defer_mask=False, x_gate_scale=None):
@@ -656,63 +682,63 @@ class _GCNLayer(Function):
     then the same symmetric-normalised aggregation on the transposed CSR, then the two GEMM gradients."""
 
     @staticmethod
-    def forward(ctx, x, w, bias, struct: GraphStructure, relu, drop_p, seed, defer_mask, x_gate_scale, pre=None, pool=None):
-        x = ops.rowmajor(x)
-        dinv = struct.gcn_dinv
-        h = pre if pre is not None else ops.linear(x, w.contiguous(), rowscale=dinv)
-        y = ops.csr_aggregate(h, struct.in_ptr, struct.in_src, ell=struct.in_ell, rscale=dinv, dself=dinv, bias=bias, relu=relu,
-                              drop_p=drop_p, seed=seed, pool=pool)
-        ctx.struct, ctx.relu, ctx.drop_p, ctx.x_gate_scale = struct, relu, drop_p, x_gate_scale
-        ctx.save_for_backward(x, w, y if ((relu or drop_p > 0) and not defer_mask) else None)
+    def forward(ctx, x, w, bias, struct: GraphStructure, relu, drop_p, seed, defer_mask, x_gate_scale):
+        y, sv = _gcn_forward(x, w, bias, struct, relu, drop_p, seed, defer_mask=defer_mask, x_gate_scale=x_gate_scale)
+        ctx.save_for_backward(*sv[:3])
+        ctx.rest = sv[3:]
         return y
 
     @staticmethod
-    def backward(ctx, g, blocks_only=False):
-        x, w, y = ctx.saved_tensors
-        s = ctx.struct
-        fused = (not blocks_only and ctx.needs_input_grad[0] and ctx.needs_input_grad[2] and ctx.x_gate_scale is not None
-                 and max(w.shape) <= 12)
-        if isinstance(g, ops.PooledGrad) and y is None:
-            # the fused backward below reads g only for the bias gradient: its column sums come from the bits, g is never written
-            pooled = g
-            gh, g = ops.pooled_grad_aggregate(pooled, s.out_ptr, s.out_dst, s.out_ell, s.gcn_dinv, rscale=s.gcn_dinv, dself=s.derived("gcn_dself"), want_g=not fused)
-            if fused and ops._fused_bwd_ok(gh, x):
-                gx, gw, _, ctx.gx_colsum = ops.linear_bwd_fused(gh, x, w.contiguous(), gate_scale=ctx.x_gate_scale)
-                return gx, gw, ops.pooled_grad_colsum(pooled), None, None, None, None, None, None
-            if g is None:
-                g = pooled.materialise()
-        else:
-            if isinstance(g, ops.PooledGrad):
-                g = g.materialise()
-            g = _mask_grad(g, y, ctx.drop_p)
-            gh = ops.csr_aggregate(g, s.out_ptr, s.out_dst, ell=s.out_ell, cscale=s.gcn_dinv, rscale=s.gcn_dinv,
-                                   dself=s.derived("gcn_dself"))
-        if blocks_only:
-            return [gh, _padded_rows(g)]
-        if (ctx.needs_input_grad[0] and ctx.needs_input_grad[2] and ctx.x_gate_scale is not None
-                and max(w.shape) <= 12 and ops._fused_bwd_ok(gh, g, x)):
-            # hidden layer of width <= 12 (conv2): gated data gradient, weight and bias gradient from ONE pass over gh, x, g
-            gx, gw, gb, ctx.gx_colsum = ops.linear_bwd_fused(gh, x, w.contiguous(), gb_src=g, gate_scale=ctx.x_gate_scale)
-            return gx, gw, gb, None, None, None, None, None, None
-        gx = None
-        if ctx.needs_input_grad[0]:
-            gated = ctx.x_gate_scale is not None
-            gx = ops.linear(gh, w.contiguous(), transposed=True, gate=x if gated else None,
-                            gate_scale=ctx.x_gate_scale if gated else 1.0)
-        gw = gb = None
-        if ctx.needs_input_grad[2]:
-            # the bias gradient sum_n g[n,:] is the ones-column of a weight-gradient pass: give that pass a second
-            # column block [gh | g] instead of sweeping g with a separate reduction
-            o, i = w.shape
-            ow = (o + 3) // 4 * 4
-            gw2 = torch.empty((2 * ow, i), dtype=torch.float32, device=x.device)
-            gb2 = torch.empty(2 * ow, dtype=torch.float32, device=x.device)
-            ops.linear_wgrad_parts([gh, g], x, gw2, gb2)
-            gw, gb = gw2[:o], gb2[ow:ow + o]
-        elif ctx.needs_input_grad[1]:
-            gw = torch.empty_like(w, memory_format=torch.contiguous_format)
-            ops.linear_wgrad(gh, x, gw, None)
-        return gx, gw, gb, None, None, None, None, None, None
+    def backward(ctx, g):
+        r = _gcn_backward(_GCNSaved(*ctx.saved_tensors, *ctx.rest), g, *ctx.needs_input_grad[:3])
+        return r.x, r.w, r.b, None, None, None, None, None, None
+
+
+def _gcn_forward(x, w, bias, struct, relu, drop_p, seed, *, defer_mask, x_gate_scale, pre=None, pool=None):
+    """``_GCNLayer`` -> (y, _GCNSaved).  pre: h' from a shared GEMM; pool: as in ``_cheb_forward``."""
+    x = ops.rowmajor(x)
+    dinv = struct.gcn_dinv
+    h = pre if pre is not None else ops.linear(x, w.contiguous(), rowscale=dinv)
+    y = ops.csr_aggregate(h, struct.in_ptr, struct.in_src, ell=struct.in_ell, rscale=dinv, dself=dinv, bias=bias, relu=relu,
+                          drop_p=drop_p, seed=seed, pool=pool)
+    return y, _GCNSaved(x, w, y if ((relu or drop_p > 0) and not defer_mask) else None, struct, drop_p, x_gate_scale)
+
+
+def _gcn_grad_blocks(sv, g, want_g=True):
+    """[gh, g]: the masked gradient at y, its transposed aggregation before it.  ``want_g=False``: a pooled gradient is not written (g None)."""
+    s = sv.struct
+    if isinstance(g, ops.PooledGrad) and sv.y is None:
+        return list(ops.pooled_grad_aggregate(g, s.out_ptr, s.out_dst, s.out_ell, s.gcn_dinv, rscale=s.gcn_dinv,
+                                              dself=s.derived("gcn_dself"), want_g=want_g))
+    g = _mask_grad(g, sv.y, sv.drop_p)
+    return [ops.csr_aggregate(g, s.out_ptr, s.out_dst, ell=s.out_ell, cscale=s.gcn_dinv, rscale=s.gcn_dinv, dself=s.derived("gcn_dself")), g]
+
+
+def _gcn_backward(sv, g, need_x, need_w, need_b):
+    x, w = sv.x, sv.w
+    # hidden layer of width <= 12 (conv2): gated data gradient, weight and bias gradient from ONE pass (ops.linear_bwd_fused)
+    fused = need_x and need_b and sv.x_gate_scale is not None and max(w.shape) <= 12
+    pooled = g if (isinstance(g, ops.PooledGrad) and sv.y is None) else None
+    gh, g = _gcn_grad_blocks(sv, g, want_g=not fused)
+    if pooled is not None:
+        # the fused backward reads g only for the bias gradient: its column sums come from the bits, g is never written
+        if fused and ops._fused_bwd_ok(gh, x):
+            gx, gw, _, colsum = ops.linear_bwd_fused(gh, x, w.contiguous(), gate_scale=sv.x_gate_scale)
+            return _GCNGrads(gx, gw, ops.pooled_grad_colsum(pooled), colsum)
+        if g is None:
+            g = pooled.materialise()
+    if fused and ops._fused_bwd_ok(gh, g, x):
+        return _GCNGrads(*ops.linear_bwd_fused(gh, x, w.contiguous(), gb_src=g, gate_scale=sv.x_gate_scale))
+    gx = ops.linear(gh, w.contiguous(), transposed=True, **_x_gate(sv)) if need_x else None
+    gw = gb = None
+    if need_b:
+        # the bias gradient sum_n g[n,:] as a second column block [gh | g] of the weight-gradient pass, not a separate reduction over g
+        gw2, gb2 = _wgrad_blocks([gh, g], x, w.shape[0])
+        gw, gb = gw2[0], gb2[1]
+    elif need_w:
+        gw = torch.empty_like(w, memory_format=torch.contiguous_format)
+        ops.linear_wgrad(gh, x, gw, None)
+    return _GCNGrads(gx, gw, gb)
 
 
 def gcn_layer(x, w, bias, struct, relu=False, drop_p=0.0, seed=0, defer_mask=False, x_gate_scale=None):
@@ -1091,23 +1117,19 @@ def asap_pool(x, mod, struct):
 
 
 # ------------------------------------------------------------------------------------------------------------------
-# Family A's graph part as ONE autograd node.  torch.autograd.Function.apply costs ~30 us of host time per node and
-# direction; the model has 7 conv layers + 3 pools, which made the host enqueue a train step in 2.0 ms (a batch of 32
-# small graphs is host-bound).  This node runs the very same layer code -- each layer's forward/backward static methods
-# are called with a private context object -- so the arithmetic and the launch sequence do not change.
+# Family A's graph part as ONE autograd node.  torch.autograd.Function.apply costs ~30 us of host time per node and direction; the model has 7 conv
+# layers + 3 pools, which made the host enqueue a train step in 2.0 ms (a batch of 32 small graphs is host-bound).  This node runs the very same layer
+# code -- the plain functions under the layer nodes (_gcn_forward, _cheb_grad_blocks, ...) -- so the arithmetic and the launch sequence do not change.
 _side_streams = {}
-
-
 _BRANCH_STREAMS_MIN_NODES = int(os.environ.get("MLQEM_BRANCH_STREAMS_MIN_NODES", "200000"))
 
 
 def _branch_streams(device, num_nodes=None):
-    """Two side streams per device for the Cheb and SAGE branches (created once).  ``MLQEM_SINGLE_STREAM=1`` keeps all
-    three branches on the caller's stream: kernels then run one after the other, which is what a per-kernel profile
-    needs (durations of overlapping kernels stretch each other; scripts/make_profiles.sh uses it for attribution).
-    A SMALL batch stays on one stream too: its kernels are launch latency, and the forks and joins of a three-stream graph cost
-    more than the branches' overlap returns (32 four-qubit circuits, captured: 0.245-0.279 ms on three streams, 0.199 on one;
-    2.4 M nodes: 1.48 against 1.75 ms the other way round; 11.3 M nodes: 5.86-6.0 against 6.03-6.13)."""
+    """Two side streams per device for the Cheb and SAGE branches (created once).  ``MLQEM_SINGLE_STREAM=1`` keeps all three branches on the caller's
+    stream: kernels then run one after the other, which is what a per-kernel profile needs (durations of overlapping kernels stretch each other;
+    scripts/make_profiles.sh uses it for attribution).  A SMALL batch stays on one stream too: its kernels are launch latency, and the forks and joins
+    of a three-stream graph cost more than the branches' overlap returns (32 four-qubit circuits, captured: 0.245-0.279 ms on three streams, 0.199 on
+    one; 2.4 M nodes: 1.48 against 1.75 ms the other way round; 11.3 M nodes: 5.86-6.0 against 6.03-6.13)."""
     if os.environ.get("MLQEM_SINGLE_STREAM", "0") == "1" or (num_nodes is not None and num_nodes < _BRANCH_STREAMS_MIN_NODES):
         cur = torch.cuda.current_stream(device)
         return (cur, cur)
@@ -1115,17 +1137,6 @@ def _branch_streams(device, num_nodes=None):
     if key not in _side_streams:
         _side_streams[key] = (torch.cuda.Stream(device=device), torch.cuda.Stream(device=device))
     return _side_streams[key]
-
-
-class _LayerCtx:
-    """The part of a torch.autograd.Function context the layer nodes use."""
-
-    def __init__(self, needs_input_grad):
-        self.needs_input_grad = needs_input_grad
-        self.saved_tensors = ()
-
-    def save_for_backward(self, *tensors):
-        self.saved_tensors = tensors
 
 
 class _FamilyAGraph(Function):
@@ -1142,19 +1153,15 @@ class _FamilyAGraph(Function):
         mean_pool(h W_0^T + (L^ h) W_1^T + b)    = mean(h) W_0^T + wmean_t(h) W_1^T + b   Cheb, K = 2
         mean_pool(M h W_l^T + b_l + h W_r^T)     = wmean_t(h) W_l^T + b_l + mean(h) W_r^T SAGE  (M = in-edge mean)
 
-    with wmean_t(h)[g] = (1/n_g) sum_{j in g} t_j h_j.  One pass over h (``ops.segment_pool``) replaces a [N,10] -> [N,1]
-    projection, a width-1 aggregation and a pool; the backward is one pass that writes gh = (g_mean + t g_wmean) / n_g
-    with the hidden layer's ReLU/dropout mask applied (``ops.segment_pool_bwd``), and the weight gradients are [B, 10]
-    matrix products.  Same algebra as the reference in a different fp32 summation order (1e-5 parity tests cover it);
-    the width-1 kernels this removes ran at 20-35 % of the HBM peak and took 29 % of the step."""
+    with wmean_t(h)[g] = (1/n_g) sum_{j in g} t_j h_j.  One pass over h (``ops.segment_pool``) replaces a [N,10] -> [N,1] projection, a width-1
+    aggregation and a pool; the backward is one pass that writes gh = (g_mean + t g_wmean) / n_g with the hidden layer's ReLU/dropout mask applied
+    (``ops.segment_pool_bwd``), and the weight gradients are [B, 10] matrix products.  Same algebra as the reference in a different fp32 summation
+    order (1e-5 parity tests cover it); the width-1 kernels this removes ran at 20-35 % of the HBM peak and took 29 % of the step."""
 
     @staticmethod
     def forward(ctx, x, struct: GraphStructure, p1, p2, seed, *prm):
         (g1w, g1b, g2w, g2b, g3w, g3b, c1w0, c1w1, c1w2, c1b, c2w0, c2w1, c2b, s1l, s1b, s1r, s2l, s2b, s2r) = prm
         k1, k2 = 1.0 / (1.0 - p1), 1.0 / (1.0 - p2)
-        T, Fa = True, False
-        mk = lambda n_in, x_grad: _LayerCtx((x_grad,) + (T,) * (n_in - 1))
-        L = ctx.layers = {}
         gptr, nb, n = struct.graph_ptr, struct.num_graphs, struct.num_nodes
         # The three branches are independent until the concatenation: each runs on its own HIP stream, so the tail of one
         # branch's kernels (hub-row waves keep a launch's last workgroups alive) is filled by the others' workgroups.
@@ -1172,34 +1179,30 @@ class _FamilyAGraph(Function):
         pre_g = pre_c = pre_s = None
         if fuse:
             xr = _padded_rows(ops.rowmajor(x))
-            o = g1w.shape[0]
-            blocks = [ops.padded_empty(xr.shape[0], o, x.device) for _ in range(6)]
+            blocks = [ops.padded_empty(xr.shape[0], g1w.shape[0], x.device) for _ in range(6)]
             ws6 = [w.contiguous() for w in (g1w, c1w0, c1w1, c1w2, s1l, s1r)]
-            ops.linear_parts([xr], ws6, blocks, w_minus=[None, ws6[3], None, None, None, None],
-                             biases=[None, c1b, None, None, None, s1b],
+            ops.linear_parts([xr], ws6, blocks, w_minus=[None, ws6[3], None, None, None, None], biases=[None, c1b, None, None, None, s1b],
                              rowscales=[struct.gcn_dinv, None, None, None, None, None])
             pre_g, pre_c, pre_s = blocks[0], blocks[1:4], blocks[4:6]
         for st in side:
             st.wait_stream(main)
-        # GCN branch: args (x, w, bias, struct, relu, drop_p, seed, defer_mask, x_gate_scale)
-        L["g1"] = mk(9, Fa); h = _GCNLayer.forward(L["g1"], x, g1w, g1b, struct, T, p1, seed + 1, T, None, pre=pre_g)
+        # every hidden layer defers its mask: conv2 gates conv1's gradient, the pools' backward those of the last hidden activations
+        h, g1 = _gcn_forward(x, g1w, g1b, struct, True, p1, seed + 1, defer_mask=True, x_gate_scale=None, pre=pre_g)
         # the pooled means of each branch's last hidden activation come out of the aggregation launch that writes it
         # (mlqem_csr_aggregate_pool_f32: the activation is not read a second time)
         # ... and since the backward reads that activation ONLY as the ReLU / dropout gate of the pool's gradient, the launch leaves
         # its sign bits (one byte per 16-byte slice) instead of the activation itself: h is never written, never read again
         pg = dict(graph_ptr=gptr, num_graphs=nb, weights=tg, mean=False, wmean=True, bits=True, store=False)
-        L["g2"] = mk(9, T); hg = _GCNLayer.forward(L["g2"], h, g2w, g2b, struct, T, p1, seed + 2, T, k1, pool=pg)
+        hg, g2 = _gcn_forward(h, g2w, g2b, struct, True, p1, seed + 2, defer_mask=True, x_gate_scale=k1, pool=pg)
         _, wg = ops.pooled_means(hg, pg)
         with torch.cuda.stream(side[0]):
-            # Cheb branch: args (x, bias, struct, relu, drop_p, seed, defer_mask, x_gate_scale, *ws)
             pc = dict(graph_ptr=gptr, num_graphs=nb, weights=tc, mean=True, wmean=True, bits=True, store=False)
-            L["c1"] = mk(11, Fa); hc = _ChebLayer.forward(L["c1"], x, c1b, struct, T, p2, seed + 3, T, None, c1w0, c1w1, c1w2,
-                                                          pre=pre_c, pool=pc)
+            hc, c1 = _cheb_forward(x, (c1w0, c1w1, c1w2), c1b, struct, True, p2, seed + 3, defer_mask=True, x_gate_scale=None,
+                                   pre=pre_c, pool=pc)
             mc, wc = ops.pooled_means(hc, pc)
         with torch.cuda.stream(side[1]):
-            # SAGE branch: args (x, wl, bl, wr, struct, relu, drop_p, seed, defer_mask, x_gate_scale)
             ps = dict(graph_ptr=gptr, num_graphs=nb, weights=ts, mean=True, wmean=True, bits=True, store=False)
-            L["s1"] = mk(10, Fa); hs = _SAGELayer.forward(L["s1"], x, s1l, s1b, s1r, struct, T, p2, seed + 4, T, None, pre=pre_s, pool=ps)
+            hs, s1 = _sage_forward(x, s1l, s1b, s1r, struct, True, p2, seed + 4, defer_mask=True, x_gate_scale=None, pre=pre_s, pool=ps)
             ms, ws = ops.pooled_means(hs, ps)
         for st, ts_ in zip(side, ((mc, wc), (ms, ws))):
             main.wait_stream(st)
@@ -1213,27 +1216,27 @@ class _FamilyAGraph(Function):
         out = ops.pooled_head(*ctx.head)
         # the gates of the three pooled activations: the activation itself, or its sign bits when the pooled launch left only those
         ctx.tail = (struct, k1, k2, hg, hc, hs)
+        # The layers' records as a plain attribute, their tensors NOT through ctx.save_for_backward: deliberate.  Wrapping a dozen tensors is
+        # host time of the kind this node exists to save; the price: no version check of x and the weights here (the layer nodes keep theirs)
+        ctx.layers = (g1, g2, c1, s1)
         ctx.gate_bits = (pg.get("out_bits"), pc.get("out_bits"), ps.get("out_bits"))
         return out
 
     @staticmethod
     def backward(ctx, g):
-        L = ctx.layers
+        (g1, g2, c1, s1), fuse = ctx.layers, ctx.fuse
         struct, k1, k2, hg, hc, hs = ctx.tail
         bg_, bc_, bs_ = ctx.gate_bits           # sign bits of the pooled activations (then hg / hc / hs are None: never written)
         gptr, n = struct.graph_ptr, struct.num_nodes
-        main = torch.cuda.current_stream(g.device)
-        side = ctx.side
+        main, side = torch.cuda.current_stream(g.device), ctx.side
         # the folded last convs first, on the compute stream: gradients of the five pooled matrices, five weight rows, three biases
         (ggw, gcm, gcw, gsw, gsm), gw5, gb3 = ops.pooled_head_bwd(ctx.head[0], ctx.head[1], g)
         g3wg, c2w0g, c2w1g, s2lg, s2rg = gw5[0:1], gw5[1:2], gw5[2:3], gw5[3:4], gw5[4:5]
         g3bg, c2bg, s2bg = gb3[0:1], gb3[1:2], gb3[2:3]
-        c_ = ggw.shape[1]
-        synth = (_POOLED_GRAD and n >= _POOLED_GRAD_MIN_NODES and ops.pooled_grad_supported(c_)
+        synth = (_POOLED_GRAD and n >= _POOLED_GRAD_MIN_NODES and ops.pooled_grad_supported(ggw.shape[1])
                  and struct.out_ell is not None)      # per branch: its gate bits exist
         for st in side:
             st.wait_stream(main)
-        # GCN branch, last layer first: pooled = wmean(h) W^T + b
 
         def pooled_grad(gm, gw, kind, gate, scale, bits):
             if synth and bits is not None:
@@ -1241,48 +1244,45 @@ class _FamilyAGraph(Function):
             return ops.segment_pool_bwd(gm, gw, gptr, n, weights=struct.colsum(kind), gate=gate if bits is None else None, gate_scale=scale,
                                         gate_bits=bits)
 
+        # GCN branch, last layer first: pooled = wmean(h) W^T + b
         t = pooled_grad(None, ggw, "gcn", hg, k1, bg_)
-        t, g2w, g2b = _GCNLayer.backward(L["g2"], t)[:3]
-        # conv1's bias gradient is the column sum of the gradient conv2's backward just wrote: taken there, the first-layer
-        # weight-gradient pass below reads six blocks instead of seven
-        g1b_cs = getattr(L["g2"], "gx_colsum", None)
-        fuse = ctx.fuse
+        r = _gcn_backward(g2, t, True, True, True)
+        # conv1's bias gradient is the column sum of the gradient conv2's backward just wrote: taken there (by the fused form, else
+        # None), the first-layer weight-gradient pass below reads six blocks instead of seven
+        g2w, g2b, g1b_cs = r.w, r.b, r.x_colsum
         if fuse:
-            bg = _GCNLayer.backward(L["g1"], t, blocks_only=True)            # [gh, g]
+            gh, t = _gcn_grad_blocks(g1, r.x)
+            bg = [gh, _padded_rows(t)]
         else:
-            _, g1w, g1b = _GCNLayer.backward(L["g1"], t)[:3]
+            r = _gcn_backward(g1, r.x, False, True, True)
+            g1w, g1b = r.w, r.b
         with torch.cuda.stream(side[0]):
             t = pooled_grad(gcm, gcw, "cheb", hc, k2, bc_)
             if fuse:
-                bc = _ChebLayer.backward(L["c1"], t, blocks_only=True)       # [g, g_b1, g_c2]
+                bc = _cheb_grad_blocks(c1, t)       # [g, g_b1, g_c2]
             else:
-                r = _ChebLayer.backward(L["c1"], t)
-                c1b, c1w0, c1w1, c1w2 = r[1], r[8], r[9], r[10]
+                r = _cheb_backward(c1, t, False)
+                c1b, (c1w0, c1w1, c1w2) = r.b, r.ws
         with torch.cuda.stream(side[1]):
             t = pooled_grad(gsm, gsw, "sage", hs, k2, bs_)
             if fuse:
-                bs = _SAGELayer.backward(L["s1"], t, blocks_only=True)       # [g_p, g]
+                bs = _sage_grad_blocks(s1, t)       # [g_p, g]
             else:
-                _, s1l, s1b, s1r = _SAGELayer.backward(L["s1"], t)[:4]
+                r = _sage_backward(s1, t, False)
+                s1l, s1b, s1r = r.wl, r.bl, r.wr
         for st in side:
             main.wait_stream(st)
         if fuse:
             # ONE pass over x for the weight gradients of all three first layers: x^T [gh | g || g | g_b1 | g_c2 || g_p | g];
             # the ones column of the pass yields the three bias gradients
-            x0 = L["g1"].saved_tensors[0]
-            o, i = L["g1"].saved_tensors[1].shape
-            ow = (o + 3) // 4 * 4
             for blk in bc + bs:
                 blk.record_stream(main)
             blks = ([bg[0]] if g1b_cs is not None else bg) + bc + bs
-            nb, k = len(blks), len(blks) - 5             # k: index of the first Cheb block
-            gwn = torch.empty((nb * ow, i), dtype=torch.float32, device=g.device)
-            gbn = torch.empty(nb * ow, dtype=torch.float32, device=g.device)
-            ops.linear_wgrad_parts(blks, x0, gwn, gbn)
-            gwn = gwn.reshape(nb, ow, i)[:, :o]
-            g1w, g1b = gwn[0], (g1b_cs[:o] if g1b_cs is not None else gbn[ow:ow + o])
-            c1w0, c1w1, c1w2, c1b = gwn[k], gwn[k + 1], gwn[k + 2] - gwn[k], gbn[k * ow:k * ow + o]
-            s1l, s1r, s1b = gwn[k + 3], gwn[k + 4], gbn[(k + 4) * ow:(k + 4) * ow + o]
+            k, o = len(blks) - 5, g1.w.shape[0]             # k: index of the first Cheb block
+            gwn, gbn = _wgrad_blocks(blks, g1.x, o)
+            g1w, g1b = gwn[0], (g1b_cs[:o] if g1b_cs is not None else gbn[1])
+            c1w0, c1w1, c1w2, c1b = gwn[k], gwn[k + 1], gwn[k + 2] - gwn[k], gbn[k]
+            s1l, s1r, s1b = gwn[k + 3], gwn[k + 4], gbn[k + 4]
         for t in (gcm, gcw, gsm, gsw):        # made on the compute stream, consumed by the side streams
             t.record_stream(side[0] if t is gcm or t is gcw else side[1])
         for t in (() if fuse else (c1b, c1w0, c1w1, c1w2, s1l, s1b, s1r)):

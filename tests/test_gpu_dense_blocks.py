@@ -1,7 +1,8 @@
 """Dense blocks (csrc/dense_block.hip; round 5): TransformerConv's edge softmax over the long rows of ASAPooling's coarsened graphs on
 the f32 matrix cores (docs/tutorials/gnn.py:80-91: the second TransformerConv of every reference GNN), against the per-edge kernels.
 
-The per-edge kernels are pinned to dense fp64 algebra and to the oracle (test_gpu_family_b.py); here the block forms must reproduce
+The per-edge kernels are pinned to fp64 algebra and to the oracle (TransformerConv's: test_gpu_family_b.py; ASAPooling's cluster sums,
+maxima and fitness with their backwards: test_gpu_asap_reference.py); here the block forms must reproduce
 them on graphs shaped like the coarsened ones -- long rows that share their sources, short rows between them, graphs of every size,
 with and without self entries, with dropout (keyed by (destination, head, source): the same draws in both forms) -- and the plan
 itself must list exactly the structure's entries.  Tolerance: 2e-5 of each result's scale (another fp32 summation order, exp2 on the

@@ -1,8 +1,9 @@
 """torch.autograd nodes over the native kernels.
 
-One node per conv layer (``_GCNLayer``, ``_ChebLayer``, ``_SAGELayer``, ``_TransformerConv``, ``_ASAPool``): its forward
-and backward are short, fixed sequences of launches with the element-wise work folded into kernel epilogues; plus the
-generic differentiable building blocks ``csr_aggregate``, ``linear`` and ``segment_mean``."""
+One node per conv layer (``_GCNLayer``, ``_ChebLayer``, ``_SAGELayer``, ``_TransformerConv``, ``_ASAPool``): a thin adapter over
+plain functions that know nothing about autograd (``_gcn_forward`` / ``_gcn_backward``, ..., ``_tconv_forward``, ``_asap_forward`` and
+its stages) -- short, fixed sequences of launches with the element-wise work folded into kernel epilogues; plus the generic
+differentiable building blocks ``csr_aggregate``, ``linear`` and ``segment_mean``."""
 from __future__ import annotations
 
 import os
@@ -768,108 +769,89 @@ class _TransformerConv(Function):
 
     @staticmethod
     def forward(ctx, x, struct: GraphStructure, heads, channels, drop_p, seed, *wb):
-        # wb = (w, b): the fused [4 H C, in] projection, or the reference's eight parameters (query, key, value, skip: weight, bias
-        # each) as they are -- their concatenation and the per-head padding then come from ONE launch (ops.pad_head_rows_parts)
-        # instead of two torch.cat and a padding launch
-        x = ops.rowmajor(x)        # a RowsOf (rows of the device-resident dataset) stays one: the projection reads through its row map
-        parts = len(wb) == 8
-        ctx.parts = parts
-        if parts:
-            ws_, bs_ = list(wb[0::2]), list(wb[1::2])
-            on_gpu = ws_[0].is_cuda
-            fused = lambda pitch: (ops.pad_head_rows_parts(ws_, bs_, heads, channels, pitch) if on_gpu
-                                   else _pad_heads(torch.cat(ws_, 0), torch.cat(bs_, 0), 4 * heads, channels, pitch))
-            w = None
-        else:
-            w, b = wb
-            w = w.contiguous()
-            on_gpu = w.is_cuda
-        e = struct.edge_count()
-        # a structure whose rows share their sources (ASAPooling's coarsened graphs of large circuits): its long rows as dense blocks,
-        # the edge softmax on the matrix cores (csrc/dense_block.hip)
-        dense = (_DENSE_BLOCKS and struct.blocked and on_gpu and struct.out_eid is None and channels < 16
-                 and ops.dense_attention_supported(heads, channels, 16))
-        if not any(ctx.needs_input_grad) and drop_p == 0.0:  # inference: no statistics kept
-            if parts:
-                w, b = fused(channels)
-            return ops.transformer_attention(ops.linear(x, w, b), struct.in_ptr, struct.in_src, struct.loops, heads, channels)
-        # Training: a head's channels at a pitch of 16 inside q / k / v / skip (the reference's 15: every gathered segment becomes an
-        # aligned 64-byte piece).  The projection writes that layout by itself when its weight and bias rows are padded the same way
-        # (zero rows: the pads of qkvs are zeros, the gradient of a pad row is exactly zero); w itself stays [4 H C, in].
-        cp = _ATTN_PITCH if (_ATTN_PITCH > channels and _ATTN_PITCH - channels < 4 and on_gpu) else 0
-        if dense:
-            cp = 16 if channels < 16 else 0
-        ctx.cp = cp
-        ctx.dense = dense
-        if parts:
-            w_used, b_used = fused(cp if cp else channels)
-        else:
-            w_used, b_used = _pad_heads(w, b, 4 * heads, channels, cp) if cp else (w, b)
-        qkvs = ops.linear(x, w_used, b_used)
-        # a structure without out_eid (ASAPooling's coarsened graphs: no parallel edges) takes the recomputed backward, whose dropout
-        # draws are keyed by (destination, head, source)
-        pair_key = struct.out_eid is None
-        # the side table of a graph of short rows (circuit DAGs: the arena builds it with the batch); a coarsened graph's rows are long
-        ell = struct.in_ell if struct.out_eid is not None else None
-        if dense:
-            out, attn, m, den = ops.dense_attention_train(qkvs, struct.in_ptr, struct.in_src, struct.loops, e, heads, channels,
-                                                         struct.dense_plan("in"), drop_p=drop_p, seed=seed, head_pitch=cp)
-        else:
-            out, attn, m, den = ops.transformer_attention_train(qkvs, struct.in_ptr, struct.in_src, struct.loops, e, heads,
-                                                               channels, drop_p, seed, pair_key=pair_key, ell=ell, head_pitch=cp)
-        ctx.struct, ctx.cfg = struct, (e, heads, channels, drop_p, seed, pair_key)
-        ctx.x_rows_of = isinstance(x, ops.RowsOf)
-        if ctx.x_rows_of:
-            ctx.save_for_backward(x.base, x.rows, w_used, qkvs, attn, m, den)
-        else:
-            ctx.save_for_backward(x, w_used, qkvs, attn, m, den)
+        train = any(ctx.needs_input_grad) or drop_p != 0.0      # inference otherwise: no statistics kept
+        out, sv = _tconv_forward(x, wb, struct, heads, channels, drop_p, seed, train)
+        if train:
+            ctx.x_rows_of = isinstance(sv.x, ops.RowsOf)
+            ctx.save_for_backward(*((sv.x.base, sv.x.rows) if ctx.x_rows_of else (sv.x,)), *sv[1:6])
+            ctx.rest = sv[6:]
         return out
 
     @staticmethod
     def backward(ctx, g):
-        if ctx.x_rows_of:
-            base, rows, w, qkvs, attn, m, den = ctx.saved_tensors
-            x = ops.RowsOf(base, rows)
-        else:
-            x, w, qkvs, attn, m, den = ctx.saved_tensors
-        e, heads, channels, drop_p, seed, pair_key = ctx.cfg
-        cp = ctx.cp
-        if ctx.dense:
-            st = ctx.struct
-            gqkvs = ops.dense_attention_bwd(qkvs, g, attn, m, den, st, e, heads, channels, st.dense_plan("in"), st.dense_plan("out"),
-                                            drop_p=drop_p, seed=seed, head_pitch=cp)
-        else:
-            gqkvs = ops.transformer_attention_bwd(qkvs, g, attn, m, den, ctx.struct, e, heads, channels, drop_p, seed, pair_key=pair_key,
-                                                  head_pitch=cp)
-        gx = ops.linear(gqkvs, w, transposed=True) if ctx.needs_input_grad[0] else None       # w: the (padded) weight the forward used
-        gw = torch.empty_like(w)
-        gb = torch.empty(w.shape[0], dtype=w.dtype, device=w.device)
-        ops.linear_wgrad(gqkvs, x, gw, gb)
-        if cp:                     # the real rows of the padded gradients
-            gw, gb = ops.unpad_head_rows(gw, gb, 4 * heads, channels, cp)
-        if ctx.parts:              # the four parameters' gradients: row blocks of the fused one
-            hc = heads * channels
-            grads = []
-            for k in range(4):
-                grads += [gw[k * hc:(k + 1) * hc], gb[k * hc:(k + 1) * hc]]
-            return (gx, None, None, None, None, None, *grads)
-        return gx, None, None, None, None, None, gw, gb
+        *xs, w, qkvs, attn, m, den = ctx.saved_tensors
+        x = ops.RowsOf(*xs) if ctx.x_rows_of else xs[0]
+        r = _tconv_backward(_TConvSaved(x, w, qkvs, attn, m, den, *ctx.rest), g, ctx.needs_input_grad[0])
+        return (r.x, None, None, None, None, None, *r.wb)
 
 
-def _pad_heads(w, b, groups, channels, cp):
-    """Weight and bias of a projection whose ``groups`` blocks of ``channels`` rows each are spread to a pitch of ``cp`` rows (zero
-    rows between: the projection then writes its output at that pitch, pads zero; the gradient of a pad row is exactly zero)."""
-    if cp <= channels:
-        return w, b
-    if w.is_cuda:
-        return ops.pad_head_rows(w, b, groups, channels, cp)
-    wp = w.new_zeros((groups * cp, w.shape[1]))
-    wp.view(groups, cp, -1)[:, :channels].copy_(w.view(groups, channels, -1))
-    bp = None
-    if b is not None:
-        bp = b.new_zeros(groups * cp)
-        bp.view(groups, cp)[:, :channels].copy_(b.view(groups, channels))
-    return wp, bp
+# What TransformerConv keeps for its backward (tensors first; x may be an ops.RowsOf, w is the (padded) weight the forward used), and
+# the gradients that backward returns -- wb: one per tensor of the forward's ``wb``, in its order.
+_TConvSaved = namedtuple("_TConvSaved", "x w qkvs attn m den struct e heads channels drop_p seed pair_key cp dense parts")
+_TConvGrads = namedtuple("_TConvGrads", "x wb")
+
+
+def _tconv_projection(wb, heads, channels, pitch):
+    """(w_used, b_used), a head's ``channels`` rows at a pitch of ``pitch`` rows, of wb = (w, b): the fused [4 H C, in] projection,
+    or of the reference's eight parameters (query, key, value, skip: weight, bias each) as they are -- their concatenation and the
+    per-head padding then come from ONE launch (ops.pad_head_rows_parts) instead of two torch.cat and a padding launch."""
+    if len(wb) == 8:
+        return ops.pad_head_rows_parts(list(wb[0::2]), list(wb[1::2]), heads, channels, pitch)
+    w, b = wb
+    w = w.contiguous()
+    return ops.pad_head_rows(w, b, 4 * heads, channels, pitch) if pitch > channels else (w, b)
+
+
+def _tconv_forward(x, wb, struct, heads, channels, drop_p, seed, train):
+    """``_TransformerConv`` -> (out, _TConvSaved); (out, None) for inference (``train`` false)."""
+    x = ops.rowmajor(x)        # a RowsOf (rows of the device-resident dataset) stays one: the projection reads through its row map
+    ops._x_operand(x)          # a host tensor is an error HERE, before anything is launched: there is no CPU path
+    e = struct.edge_count()
+    # a structure whose rows share their sources (ASAPooling's coarsened graphs of large circuits): its long rows as dense blocks,
+    # the edge softmax on the matrix cores (csrc/dense_block.hip)
+    dense = (_DENSE_BLOCKS and struct.blocked and struct.out_eid is None and channels < 16
+             and ops.dense_attention_supported(heads, channels, 16))
+    # Training: a head's channels at a pitch of 16 inside q / k / v / skip (the reference's 15: every gathered segment becomes an
+    # aligned 64-byte piece; the dense blocks need that pitch).  The projection writes that layout by itself when its weight and
+    # bias rows are padded the same way (zero rows: the pads of qkvs are zeros, the gradient of a pad row is exactly zero); w itself
+    # stays [4 H C, in].  Inference: compact heads.
+    cp = (16 if dense else (_ATTN_PITCH if 0 < _ATTN_PITCH - channels < 4 else 0)) if train else 0
+    w_used, b_used = _tconv_projection(wb, heads, channels, cp or channels)
+    qkvs = ops.linear(x, w_used, b_used)
+    if not train:
+        return ops.transformer_attention(qkvs, struct.in_ptr, struct.in_src, struct.loops, heads, channels), None
+    # a structure without out_eid (ASAPooling's coarsened graphs: no parallel edges) takes the recomputed backward, whose dropout
+    # draws are keyed by (destination, head, source)
+    pair_key = struct.out_eid is None
+    if dense:
+        out, attn, m, den = ops.dense_attention_train(qkvs, struct.in_ptr, struct.in_src, struct.loops, e, heads, channels,
+                                                     struct.dense_plan("in"), drop_p=drop_p, seed=seed, head_pitch=cp)
+    else:
+        # the side table of a graph of short rows (circuit DAGs: the arena builds it with the batch); a coarsened graph's rows are long
+        ell = struct.in_ell if struct.out_eid is not None else None
+        out, attn, m, den = ops.transformer_attention_train(qkvs, struct.in_ptr, struct.in_src, struct.loops, e, heads,
+                                                           channels, drop_p, seed, pair_key=pair_key, ell=ell, head_pitch=cp)
+    return out, _TConvSaved(x, w_used, qkvs, attn, m, den, struct, e, heads, channels, drop_p, seed, pair_key, cp, dense, len(wb) == 8)
+
+
+def _tconv_backward(sv, g, need_x):
+    st, w, heads, channels, cp = sv.struct, sv.w, sv.heads, sv.channels, sv.cp
+    if sv.dense:
+        gqkvs = ops.dense_attention_bwd(sv.qkvs, g, sv.attn, sv.m, sv.den, st, sv.e, heads, channels, st.dense_plan("in"), st.dense_plan("out"),
+                                        drop_p=sv.drop_p, seed=sv.seed, head_pitch=cp)
+    else:
+        gqkvs = ops.transformer_attention_bwd(sv.qkvs, g, sv.attn, sv.m, sv.den, st, sv.e, heads, channels, sv.drop_p, sv.seed,
+                                              pair_key=sv.pair_key, head_pitch=cp)
+    gx = ops.linear(gqkvs, w, transposed=True) if need_x else None
+    gw = torch.empty_like(w)
+    gb = torch.empty(w.shape[0], dtype=w.dtype, device=w.device)
+    ops.linear_wgrad(gqkvs, sv.x, gw, gb)
+    if cp:                     # the real rows of the padded gradients
+        gw, gb = ops.unpad_head_rows(gw, gb, 4 * heads, channels, cp)
+    if not sv.parts:
+        return _TConvGrads(gx, (gw, gb))
+    hc = heads * channels      # the four parameters' gradients: row blocks of the fused one
+    return _TConvGrads(gx, tuple(t[k * hc:(k + 1) * hc] for k in range(4) for t in (gw, gb)))
 
 
 # the long rows of ASAPooling's coarsened graphs as dense blocks: TransformerConv's edge softmax over them on the f32 matrix cores
@@ -943,168 +925,184 @@ class _ASAPool(Function):
     @staticmethod
     def forward(ctx, x, lin_w, lin_b, att_w, att_b, l1_w, l1_b, l2_w, l3_w, l3_b, struct: GraphStructure, ratio, slope,
                 holder):
-        s = struct
-        x = ops.rowmajor(x)
-        d, n = x.shape[1], s.num_nodes
-        # the parameters' small-tensor algebra in one launch (csrc/asap.hip asap_compose_kernel): the halves of att_w, LEConv's three
-        # one-wide projections as one [3, D] matrix (lin2 has no bias), and the query projection composed into the score projection
-        w_comp, b_comp, att_q, att_x, w3, b3 = ops.asap_compose(lin_w, lin_b, att_w, att_b, l1_w, l1_b, l2_w, l3_w, l3_b)
-        # the input graph's rows share their sources (it is itself a coarsened graph): its long rows as dense blocks
-        # (csrc/dense_pool.hip), on the same plans TransformerConv's edge softmax built on this graph
-        dense = _DENSE_BLOCKS and s.blocked and s.out_eid is None and ops.dense_pool_fits(x)
-        ctx.dense = dense
-        # ... or, a graph of short rows (the circuit DAGs: the arena hands their side table along): everything up to the fitness
-        # projections in one pass over the rows (csrc/attn.hip asap_scores_fused_kernel)
-        fused = _ASAP_FUSED and not dense and x.is_cuda and d <= 64 and s.in_ell is not None
-        stat = None
-        if fused:
-            xq_raw, a_dst, c_src, x_new, pqr = ops.asap_scores_fused(x, s.in_ptr, s.in_src, w_comp, b_comp, att_x, w3, b3, slope)
-            fitness = ops.leconv_fitness(pqr, s.in_ptr, s.in_src)
-        elif dense:
-            xq_raw = ops.dense_segment_max(x, s.in_ptr, s.in_src, s.dense_plan("in"))
-        else:
-            xq_raw = ops.csr_segment_max(x, s.in_ptr, s.in_src, ell=s.in_ell)
-        if not fused:
-            # ASAPooling's query x_q = lin(segmax) feeds ONLY the one-wide score a_i = att_q . x_q[i] + att_b (SURVEY appendix
-            # B.2 steps 2-3): a_i = (att_q W) . segmax[i] + (att_q . b + att_b) -- one row dot of the segment max against a composed
-            # 45-vector.  x_q [N, D] is never formed (a [N,D]x[D,D] GEMM forward; a data GEMM and a [D,D] weight-gradient pass
-            # backward), the gradients of lin follow from the composed vector's by the chain rule on D x D tensors
-            # (asap_compose above, asap_compose_bwd in the backward: deterministic, capturable).
-            # (one-wide and three-wide projections into COMPACT outputs: a [N, 1] matrix with a row pitch of one float is the vector the
-            # edge kernels take -- the padded default cost a strided copy per projection)
-            a_dst = ops.linear(xq_raw, w_comp, b_comp, out=torch.empty((n, 1), dtype=torch.float32, device=x.device))[:, 0]
-        if not fused:
-            c_src = ops.linear(x, att_x, out=torch.empty((n, 1), dtype=torch.float32, device=x.device))[:, 0]
-            if dense:
-                x_new, stat = ops.dense_softmax_aggregate(x, s.in_ptr, s.in_src, a_dst, c_src, slope, s.dense_plan("in"))
-            else:
-                x_new = ops.csr_softmax_aggregate(x, s.in_ptr, s.in_src, a_dst, c_src, slope)
-            fitness = ops.leconv_fitness(ops.linear(x_new, w3, b3, out=torch.empty((n, 3), dtype=torch.float32, device=x.device)), s.in_ptr, s.in_src,
-                                         long_rows=dense)      # (the coarsened graph: a 16-lane group per row)
-        plan = getattr(s, "pool_plan", None)
-        if plan:
-            # a size-stable batch (train.BucketedTrainer): the per-graph sizes stay on the device.  The pooled boundaries come from a
-            # launch, the number of kept nodes is a function of the bucket (the batch's filler graphs are sized for that), and the
-            # largest graph before / after pooling is known by a bound -- nothing here depends on the size SEQUENCE of the batch
-            k_total, nmax, kmax = (int(v) for v in plan[0])
-            new_ptr = ops.pool_keep_ptr(s.graph_ptr, s.num_graphs, ratio)
-            keep = {"b": s.num_graphs, "k": k_total, "kmax": kmax}
-            have = s.num_graphs > 0
-        else:
-            # k_g = ceil(ratio * n_g) evaluated in float32 like PyG's topk (float32 tensor times a python scalar)
-            sizes = np.asarray(s.graph_sizes, dtype=np.int64)
-            keep = np.ceil(sizes.astype(np.float32) * np.float32(ratio)).astype(np.int64)
-            new_ptr_host = np.zeros(len(keep) + 1, dtype=np.int64)
-            np.cumsum(keep, out=new_ptr_host[1:])
-            k_total = int(new_ptr_host[-1])
-            new_ptr = _device_ptr(new_ptr_host.astype(np.int32), x.device)
-            have = len(keep) > 0
-            nmax, kmax = (int(sizes.max()), int(keep.max())) if have else (0, 0)
-        # ... with the backward's slot[] (cluster id of every kept centre, -1 elsewhere; the coarsenings read the same map) from the same launches
-        perm, slot_fwd = ops.segment_topk(fitness, s.graph_ptr, new_ptr, n, s.num_graphs, k_total, max_graph_nodes=min(nmax, n), with_slot=True)
-        x_out = ops.gather_scale_rows(x_new, perm, fitness)
-        use_dense, use_lists, link = _ASAP_DENSE, _ASAP_LISTS, _ASAP_LINK   # the switches as they stand now: build() may run later
-
-        def build():
-            dense_ok = use_dense and have and kmax <= ops.asap_dense_max_k()
-            if dense_ok:
-                # small graphs: the pooled adjacency as per-graph bit matrices in LDS -- no device->host copy anywhere
-                csr, slot, cap = ops.asap_coarsen_dense(s.in_ptr, s.in_src, s.out_ptr, s.out_dst, s.graph_ptr, new_ptr, perm, n, keep,
-                                                        slot_fwd)
-                num_edges = cap     # an upper bound: the true count stays on the device (in_ptr[k_total])
-            done = None
-            if not dense_ok and use_lists and have and kmax <= ops.asap_lists_max_k():
-                # large graphs: per-node cluster lists, a thread per cluster gathers its candidates, persistent waves sort them through
-                # LDS bitsets; no host read when the structure carries a capacity.  None: too many candidates for this form
-                done = ops.asap_coarsen_lists(s.in_ptr, s.in_src, s.out_ptr, s.out_dst, s.graph_ptr, new_ptr, perm, n, s.edge_count(), keep,
-                                              slot_fwd, capacity=getattr(s, "coarse_capacity", None), link=link)
-            if dense_ok:
-                pass
-            elif done is not None:
-                csr, slot, num_edges = done
-            else:
-                ei, slot = ops.asap_coarsen(s.in_ptr, s.in_src, s.out_ptr, s.out_dst, perm, n, return_slot=True)
-                csr = ops.csr_build(ei, k_total)
-                num_edges = int(ei.shape[1])
-            return (csr[0], csr[1], csr[2], csr[3], csr[4], num_edges, csr.out_eid), slot
-
-        # the coarsened connectivity S^T A S waits until a layer reads it (GraphStructure.deferred); the backward's slot[] does not
-        # depend on it
-        slot = slot_fwd
-        holder["structure"] = GraphStructure.deferred(k_total, new_ptr, s.num_graphs, lambda: build()[0], graph_sizes=None if plan else keep)
-        if plan:
-            holder["structure"].pool_plan = plan[1:]             # the next pooling's level
-            holder["structure"].num_real = s.num_real
-        if (_DENSE_BLOCKS and use_lists and not link and have and ops.asap_dense_max_k() < kmax):
-            # large graphs (the list coarsening's): clusters whose centres are close in program order share their neighbours, so
-            # the layers that read this graph take its long rows 16 at a time in the order of their centres' node index
-            def block_order(slot=slot, gptr=s.graph_ptr, b=s.num_graphs):
-                # (a bound on the id range of one block's entries: its rows may straddle two graphs)
-                return ops.tile_order_by_position(slot, gptr, new_ptr, b, k_total), 2 * kmax + ops.ORDER_SPAN_SLACK
-
-            holder["structure"].set_block_order(block_order)
-        holder["perm"] = perm
-        ctx.struct, ctx.slope, ctx.d = s, slope, d
-        ctx.save_for_backward(x, xq_raw, w_comp, a_dst, c_src, x_new, fitness, slot, lin_w, att_w, w3, lin_b, stat if dense else None)
+        x_out, holder["structure"], holder["perm"], sv = _asap_forward(
+            x, (lin_w, lin_b, att_w, att_b, l1_w, l1_b, l2_w, l3_w, l3_b), struct, ratio, slope)
+        ctx.save_for_backward(*sv[:13])
+        ctx.rest = sv[13:]
         return x_out
 
     @staticmethod
     def backward(ctx, g_out):
-        x, xq_raw, w_comp, a_dst, c_src, x_new, fitness, slot, lin_w, att_w, w3, lin_b, dense_stat = ctx.saved_tensors
-        s, d = ctx.struct, ctx.d
-        e = s.edge_count()
-        dev = x.device
-        # x_out = x'[perm] * f[perm]: g_f = g_out . x' first (the fitness backward needs it), g_x' = g_out f + g_pqr W3 in one store after it
-        # (padded rows of at most 64 channels; otherwise g_x' = g_out f is stored with g_f and a [N,3]x[3,D] GEMM adds g_pqr W3 to it)
-        gfit = ops.gather_rows_dot(g_out, x_new, slot) if (x.is_cuda and _ASAP_FUSED) else None
-        split = gfit is not None
-        if not split:
-            gxnew, gfit = ops.gather_scale_rows_bwd(g_out, x_new, fitness, slot)
-        # f = sigmoid(LEConv(x')) on scalars pqr = x' W3^T + b3
-        if ctx.dense:        # the long rows of the coarsened graph: a wave each (the plan of the out-structure lists them)
-            gpqr = ops.dense_leconv_fitness_bwd(gfit, fitness, s.in_ptr, s.out_ptr, s.out_dst, s.dense_plan("out"))
-        else:
-            gpqr = ops.leconv_fitness_bwd(gfit, fitness, s.in_ptr, s.out_ptr, s.out_dst)
-        if split:
-            gxnew = ops.scatter_scale_rank(g_out, fitness, slot, gpqr, w3, x_new.shape[0], x_new.shape[1])
-        else:
-            ops.linear(gpqr, w3, transposed=True, out=gxnew, accumulate=True)
-        # x' = sum_e softmax(LeakyReLU(a_i + c_j)) x_j
-        # ... its destination-side walk also counts the ties of the segment max below (same x, same entries)
-        att_x = att_w[:, d:]                 # (a view: its one row is contiguous)
-        # c = x att_x^T: its gradient g_c (x) att_x rides in the source-side kernel's store of gx (it computes g_c itself) instead of
-        # being a read-modify-write pass over gx
-        dense = ctx.dense and ops.dense_pool_fits(gxnew, x_new, xq_raw)
-        fuse_max = False
-        if dense:
-            gx, g_a, g_c, ties = ops.dense_softmax_aggregate_bwd(x, x_new, gxnew, s, e, a_dst, c_src, ctx.slope, dense_stat, s.dense_plan("in"),
-                                                                 s.dense_plan("out"), xq_raw, gx_rank1=att_x[0])
-        else:
-            # the stored form (a graph with out_eid: the circuit DAGs) carries the segment max's backward in its source-side walk
-            fuse_max = _ASAP_FUSED and s.out_eid is not None and d <= 128
-            gx, g_a, g_c, ties = ops.csr_softmax_aggregate_bwd(x, x_new, gxnew, s, e, a_dst, c_src, ctx.slope, xmax=xq_raw, gx_rank1=att_x[0],
-                                                               fuse_max_col=w_comp[0].contiguous() if fuse_max else None)
-        # The three tiny weight gradients of the pooling in ONE pass over their operands (csrc/family_b_bwd.hip rank_grad_*: two
-        # launches where three linear_wgrad calls were six): gw3 [3, D] = gpqr^T x' and gb3 = its column sums (LEConv's projections);
-        # g_att_x [1, D] = g_c^T x (c = x att_x^T); g_w_comp [1, D] = g_a^T segmax and g_att_b = sum g_a -- a = xq_raw w_comp^T + b_comp
-        # with w_comp = att_q W, b_comp = att_q . b + att_b: the gradients of lin and of att's query half follow by the chain rule on
-        # D x D tensors (asap_compose_bwd); the segment max's gradient g_a (x) w_comp is formed inside its backward kernel
-        if x.is_cuda:
-            (gw3, gb3), (g_att_x, _), (g_w_comp, g_att_b) = ops.rank_grad([(gpqr, x_new), (g_c, x), (g_a, xq_raw)])
-        else:
-            gw3, gb3 = torch.empty_like(w3), torch.empty(3, dtype=torch.float32, device=dev)
-            ops.linear_wgrad(gpqr, x_new, gw3, gb3)
-            g_att_x = torch.empty((1, d), dtype=torch.float32, device=dev)
-            ops.linear_wgrad(g_c.unsqueeze(1), x, g_att_x, None)
-            g_w_comp, g_att_b = torch.empty_like(w_comp), torch.empty(1, dtype=torch.float32, device=dev)
-            ops.linear_wgrad(g_a.unsqueeze(1), xq_raw, g_w_comp, g_att_b)
-        if dense:
-            ops.dense_segment_max_bwd_(gx, x, xq_raw, s, ties, (g_a, w_comp[0].contiguous()), s.dense_plan("out"))
-        elif not fuse_max:
-            ops.csr_segment_max_bwd_(gx, x, xq_raw, None, s, ties=ties, gmax_rank1=(g_a, w_comp[0].contiguous()))
-        g_lin_w, g_lin_b, g_att_w = ops.asap_compose_bwd(g_w_comp, g_att_b, lin_w, lin_b, att_w, g_att_x)
-        return (gx, g_lin_w, g_lin_b, g_att_w, g_att_b, gw3[0:1], gb3[0:1], gw3[1:2], gw3[2:3], gb3[2:3],
-                None, None, None, None)
+        return (*_asap_backward(_AsapSaved(*ctx.saved_tensors, *ctx.rest), g_out), None, None, None, None)
+
+
+# The stages of ASAPooling below know nothing about autograd.  _AsapScores: what the score stage computed and the form it took
+# ("fused", "dense" or "edge"; stat: the dense form's softmax statistics, None otherwise).  _AsapKeep: the pooled batch's sizes --
+# on the host, or as bounds when the per-graph sizes stay on the device (then graph_sizes is None); bounds: what the coarsenings
+# size their arrays by (ops.KeepBounds), next_plan: the pool_plan of the pooled structure (None: it sizes from graph_sizes).
+# _AsapSaved: what the backward reads (its 13 tensors first); _AsapGrads: one gradient per parameter of ``_ASAPool.forward``, in order.
+_AsapScores = namedtuple("_AsapScores", "xq_raw a_dst c_src x_new fitness stat form")
+_AsapKeep = namedtuple("_AsapKeep", "new_ptr k_total nmax kmax have bounds graph_sizes next_plan")
+_AsapSaved = namedtuple("_AsapSaved", "x xq_raw w_comp a_dst c_src x_new fitness slot lin_w att_w w3 lin_b stat struct slope dense")
+_AsapGrads = namedtuple("_AsapGrads", "x lin_w lin_b att_w att_b l1_w l1_b l2_w l3_w l3_b")
+
+
+def _asap_scores(x, s, w_comp, b_comp, att_x, w3, b3, slope):
+    """x' (every node's attention-weighted neighbourhood) and its fitness, from the composed parameters -> _AsapScores."""
+    n, d = s.num_nodes, x.shape[1]
+    # "dense": the input graph's rows share their sources (it is itself a coarsened graph): its long rows as dense blocks
+    # (csrc/dense_pool.hip), on the same plans TransformerConv's edge softmax built on this graph
+    # "fused": a graph of short rows (the circuit DAGs: the arena hands their side table along): everything up to the fitness
+    # projections in one pass over the rows (csrc/attn.hip asap_scores_fused_kernel); "edge": the per-edge kernels
+    dense = _DENSE_BLOCKS and s.blocked and s.out_eid is None and ops.dense_pool_fits(x)
+    form = "dense" if dense else "fused" if (_ASAP_FUSED and d <= 64 and s.in_ell is not None) else "edge"
+    if form == "fused":
+        xq_raw, a_dst, c_src, x_new, pqr = ops.asap_scores_fused(x, s.in_ptr, s.in_src, w_comp, b_comp, att_x, w3, b3, slope)
+        return _AsapScores(xq_raw, a_dst, c_src, x_new, ops.leconv_fitness(pqr, s.in_ptr, s.in_src), None, form)
+    # ASAPooling's query x_q = lin(segmax) feeds ONLY the one-wide score a_i = att_q . x_q[i] + att_b (SURVEY appendix
+    # B.2 steps 2-3): a_i = (att_q W) . segmax[i] + (att_q . b + att_b) -- one row dot of the segment max against a composed
+    # 45-vector.  x_q [N, D] is never formed (a [N,D]x[D,D] GEMM forward; a data GEMM and a [D,D] weight-gradient pass
+    # backward), the gradients of lin follow from the composed vector's by the chain rule on D x D tensors
+    # (asap_compose in the forward, asap_compose_bwd in the backward: deterministic, capturable).
+    # (one-wide and three-wide projections into COMPACT outputs: a [N, 1] matrix with a row pitch of one float is the vector the
+    # edge kernels take -- the padded default cost a strided copy per projection)
+    compact = lambda width: torch.empty((n, width), dtype=torch.float32, device=x.device)
+    stat = None
+    if form == "dense":
+        xq_raw = ops.dense_segment_max(x, s.in_ptr, s.in_src, s.dense_plan("in"))
+        a_dst = ops.linear(xq_raw, w_comp, b_comp, out=compact(1))[:, 0]
+        c_src = ops.linear(x, att_x, out=compact(1))[:, 0]
+        x_new, stat = ops.dense_softmax_aggregate(x, s.in_ptr, s.in_src, a_dst, c_src, slope, s.dense_plan("in"))
+    else:
+        xq_raw = ops.csr_segment_max(x, s.in_ptr, s.in_src, ell=s.in_ell)
+        a_dst = ops.linear(xq_raw, w_comp, b_comp, out=compact(1))[:, 0]
+        c_src = ops.linear(x, att_x, out=compact(1))[:, 0]
+        x_new = ops.csr_softmax_aggregate(x, s.in_ptr, s.in_src, a_dst, c_src, slope)
+    fitness = ops.leconv_fitness(ops.linear(x_new, w3, b3, out=compact(3)), s.in_ptr, s.in_src,
+                                 long_rows=form == "dense")      # (the coarsened graph: a 16-lane group per row)
+    return _AsapScores(xq_raw, a_dst, c_src, x_new, fitness, stat, form)
+
+
+def _asap_keep_sizes(s, ratio, device):
+    """How many nodes of every graph the pooling keeps, and what follows from it -> _AsapKeep."""
+    plan = getattr(s, "pool_plan", None)
+    if plan:
+        # a size-stable batch (train.BucketedTrainer): the per-graph sizes stay on the device.  The pooled boundaries come from a
+        # launch, the number of kept nodes is a function of the bucket (the batch's filler graphs are sized for that), and the
+        # largest graph before / after pooling is known by a bound -- nothing here depends on the size SEQUENCE of the batch
+        k_total, nmax, kmax = (int(v) for v in plan[0])
+        new_ptr = ops.pool_keep_ptr(s.graph_ptr, s.num_graphs, ratio)
+        # (the dense coarsening's edge capacity: sum k_g (k_g - 1) <= k (kmax - 1))
+        bounds = ops.KeepBounds(s.num_graphs, k_total, kmax, k_total * max(kmax - 1, 0))
+        return _AsapKeep(new_ptr, k_total, nmax, kmax, s.num_graphs > 0, bounds, None, plan[1:])    # plan[1:]: the next pooling's level
+    # k_g = ceil(ratio * n_g) evaluated in float32 like PyG's topk (float32 tensor times a python scalar)
+    sizes = np.asarray(s.graph_sizes, dtype=np.int64)
+    keep = np.ceil(sizes.astype(np.float32) * np.float32(ratio)).astype(np.int64)
+    new_ptr_host = np.zeros(len(keep) + 1, dtype=np.int64)
+    np.cumsum(keep, out=new_ptr_host[1:])
+    new_ptr = _device_ptr(new_ptr_host.astype(np.int32), device)
+    bounds = ops._keep_info(keep)
+    return _AsapKeep(new_ptr, bounds.k, int(sizes.max()) if len(keep) else 0, bounds.kmax, len(keep) > 0, bounds, keep, None)
+
+
+def _asap_coarsen(s, keep, perm, slot, use_dense, use_lists, link):
+    """The connectivity S^T A S of the pooled graph, as ``GraphStructure.deferred`` takes it.  All three forms yield the same arrays."""
+    n = s.num_nodes
+    fields = lambda csr, num_edges: (csr[0], csr[1], csr[2], csr[3], csr[4], num_edges, csr.out_eid)
+    if use_dense and keep.have and keep.kmax <= ops.asap_dense_max_k():
+        # small graphs: the pooled adjacency as per-graph bit matrices in LDS -- no device->host copy anywhere
+        csr, _, cap = ops.asap_coarsen_dense(s.in_ptr, s.in_src, s.out_ptr, s.out_dst, s.graph_ptr, keep.new_ptr, perm, n, keep.bounds, slot)
+        return fields(csr, cap)     # an upper bound: the true count stays on the device (in_ptr[k_total])
+    if use_lists and keep.have and keep.kmax <= ops.asap_lists_max_k():
+        # large graphs: per-node cluster lists, a thread per cluster gathers its candidates, persistent waves sort them through
+        # LDS bitsets; no host read when the structure carries a capacity.  None: too many candidates for this form
+        done = ops.asap_coarsen_lists(s.in_ptr, s.in_src, s.out_ptr, s.out_dst, s.graph_ptr, keep.new_ptr, perm, n, s.edge_count(), keep.bounds,
+                                      slot, capacity=getattr(s, "coarse_capacity", None), link=link)
+        if done is not None:
+            return fields(done[0], done[2])
+    ei, _ = ops.asap_coarsen(s.in_ptr, s.in_src, s.out_ptr, s.out_dst, perm, n, return_slot=True)
+    return fields(ops.csr_build(ei, keep.k_total), int(ei.shape[1]))
+
+
+def _asap_forward(x, prm, s, ratio, slope):
+    """``_ASAPool`` -> (x_out, pooled structure, perm, _AsapSaved).  prm: the nine parameters in the node's order."""
+    x = ops.rowmajor(x)
+    ops._mat(x, "x")           # a host tensor is an error HERE, before anything is launched: there is no CPU path
+    lin_w, lin_b, att_w = prm[:3]
+    # the parameters' small-tensor algebra in one launch (csrc/asap.hip asap_compose_kernel): the halves of att_w, LEConv's three
+    # one-wide projections as one [3, D] matrix (lin2 has no bias), and the query projection composed into the score projection
+    w_comp, b_comp, _att_q, att_x, w3, b3 = ops.asap_compose(*prm)
+    sc = _asap_scores(x, s, w_comp, b_comp, att_x, w3, b3, slope)
+    keep = _asap_keep_sizes(s, ratio, x.device)
+    # ... with the backward's slot[] (cluster id of every kept centre, -1 elsewhere; the coarsenings read the same map) from the same launches
+    perm, slot = ops.segment_topk(sc.fitness, s.graph_ptr, keep.new_ptr, s.num_nodes, s.num_graphs, keep.k_total,
+                                  max_graph_nodes=min(keep.nmax, s.num_nodes), with_slot=True)
+    x_out = ops.gather_scale_rows(sc.x_new, perm, sc.fitness)
+    # the coarsened connectivity S^T A S waits until a layer reads it (GraphStructure.deferred); the backward's slot[] does not
+    # depend on it.  The switches as they stand now: the coarsening may run later
+    use_dense, use_lists, link = _ASAP_DENSE, _ASAP_LISTS, _ASAP_LINK
+    pooled = GraphStructure.deferred(keep.k_total, keep.new_ptr, s.num_graphs,
+                                     lambda: _asap_coarsen(s, keep, perm, slot, use_dense, use_lists, link), graph_sizes=keep.graph_sizes)
+    if keep.next_plan is not None:
+        pooled.pool_plan, pooled.num_real = keep.next_plan, s.num_real
+    if _DENSE_BLOCKS and use_lists and not link and keep.have and ops.asap_dense_max_k() < keep.kmax:
+        # large graphs (the list coarsening's): clusters whose centres are close in program order share their neighbours, so
+        # the layers that read this graph take its long rows 16 at a time in the order of their centres' node index
+        # (with it, a bound on the id range of one block's entries: its rows may straddle two graphs)
+        pooled.set_block_order(lambda: (ops.tile_order_by_position(slot, s.graph_ptr, keep.new_ptr, s.num_graphs, keep.k_total),
+                                        2 * keep.kmax + ops.ORDER_SPAN_SLACK))
+    return x_out, pooled, perm, _AsapSaved(x, sc.xq_raw, w_comp, sc.a_dst, sc.c_src, sc.x_new, sc.fitness, slot, lin_w, att_w, w3, lin_b,
+                                           sc.stat, s, slope, sc.form == "dense")
+
+
+def _asap_backward(sv, g_out):
+    x, xq_raw, w_comp, x_new, fitness, slot, w3 = sv.x, sv.xq_raw, sv.w_comp, sv.x_new, sv.fitness, sv.slot, sv.w3
+    s, d = sv.struct, x.shape[1]
+    e = s.edge_count()
+    # x_out = x'[perm] * f[perm]: g_f = g_out . x' first (the fitness backward needs it), g_x' = g_out f + g_pqr W3 in one store after it
+    # (padded rows of at most 64 channels; otherwise g_x' = g_out f is stored with g_f and a [N,3]x[3,D] GEMM adds g_pqr W3 to it)
+    gfit = ops.gather_rows_dot(g_out, x_new, slot) if _ASAP_FUSED else None
+    split = gfit is not None
+    if not split:
+        gxnew, gfit = ops.gather_scale_rows_bwd(g_out, x_new, fitness, slot)
+    # f = sigmoid(LEConv(x')) on scalars pqr = x' W3^T + b3
+    if sv.dense:        # the long rows of the coarsened graph: a wave each (the plan of the out-structure lists them)
+        gpqr = ops.dense_leconv_fitness_bwd(gfit, fitness, s.in_ptr, s.out_ptr, s.out_dst, s.dense_plan("out"))
+    else:
+        gpqr = ops.leconv_fitness_bwd(gfit, fitness, s.in_ptr, s.out_ptr, s.out_dst)
+    if split:
+        gxnew = ops.scatter_scale_rank(g_out, fitness, slot, gpqr, w3, x_new.shape[0], x_new.shape[1])
+    else:
+        ops.linear(gpqr, w3, transposed=True, out=gxnew, accumulate=True)
+    # x' = sum_e softmax(LeakyReLU(a_i + c_j)) x_j
+    # ... its destination-side walk also counts the ties of the segment max below (same x, same entries)
+    att_x = sv.att_w[:, d:]                 # (a view: its one row is contiguous)
+    # c = x att_x^T: its gradient g_c (x) att_x rides in the source-side kernel's store of gx (it computes g_c itself) instead of
+    # being a read-modify-write pass over gx
+    dense = sv.dense and ops.dense_pool_fits(gxnew, x_new, xq_raw)
+    fuse_max = False
+    if dense:
+        gx, g_a, g_c, ties = ops.dense_softmax_aggregate_bwd(x, x_new, gxnew, s, e, sv.a_dst, sv.c_src, sv.slope, sv.stat, s.dense_plan("in"),
+                                                             s.dense_plan("out"), xq_raw, gx_rank1=att_x[0])
+    else:
+        # the stored form (a graph with out_eid: the circuit DAGs) carries the segment max's backward in its source-side walk
+        fuse_max = _ASAP_FUSED and s.out_eid is not None and d <= 128
+        gx, g_a, g_c, ties = ops.csr_softmax_aggregate_bwd(x, x_new, gxnew, s, e, sv.a_dst, sv.c_src, sv.slope, xmax=xq_raw, gx_rank1=att_x[0],
+                                                           fuse_max_col=w_comp[0].contiguous() if fuse_max else None)
+    # The three tiny weight gradients of the pooling in ONE pass over their operands (csrc/family_b_bwd.hip rank_grad_*: two
+    # launches where three linear_wgrad calls were six): gw3 [3, D] = gpqr^T x' and gb3 = its column sums (LEConv's projections,
+    # rows lin1 | lin2 | lin3; lin2 has no bias); g_att_x [1, D] = g_c^T x (c = x att_x^T); g_w_comp [1, D] = g_a^T segmax and
+    # g_att_b = sum g_a -- a = xq_raw w_comp^T + b_comp with w_comp = att_q W, b_comp = att_q . b + att_b: the gradients of lin and of
+    # att's query half follow by the chain rule on D x D tensors (asap_compose_bwd); the segment max's gradient g_a (x) w_comp is
+    # formed inside its backward kernel
+    (gw3, gb3), (g_att_x, _), (g_w_comp, g_att_b) = ops.rank_grad([(gpqr, x_new), (g_c, x), (g_a, xq_raw)])
+    if dense:
+        ops.dense_segment_max_bwd_(gx, x, xq_raw, s, ties, (g_a, w_comp[0].contiguous()), s.dense_plan("out"))
+    elif not fuse_max:
+        ops.csr_segment_max_bwd_(gx, x, xq_raw, None, s, ties=ties, gmax_rank1=(g_a, w_comp[0].contiguous()))
+    g_lin_w, g_lin_b, g_att_w = ops.asap_compose_bwd(g_w_comp, g_att_b, sv.lin_w, sv.lin_b, sv.att_w, g_att_x)
+    return _AsapGrads(x=gx, lin_w=g_lin_w, lin_b=g_lin_b, att_w=g_att_w, att_b=g_att_b,
+                      l1_w=gw3[0:1], l1_b=gb3[0:1], l2_w=gw3[1:2], l3_w=gw3[2:3], l3_b=gb3[2:3])
 
 
 def asap_pool(x, mod, struct):

@@ -6,9 +6,10 @@ matching the CSR arrays) BEFORE launching -- a kernel that reads out of bounds c
 from __future__ import annotations
 
 import os
-
+from collections import namedtuple
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1511,24 +1512,24 @@ def asap_coarsen(in_ptr, in_src, out_ptr, out_dst, perm, num_nodes, return_slot=
     return (ei, slot) if return_slot else ei
 
 
-def _keep_info(keep_sizes):
-    """(B, k_total, kmax, dense edge capacity) of a pooled batch from the host array of its k_g -- or from BOUNDS, a dict with
-    ``b``, ``k`` (exact) and ``kmax`` (an upper bound on the largest k_g), when the per-graph sizes stay on the device (size-stable
-    captured steps): sum k_g (k_g - 1) <= k (kmax - 1)."""
-    import numpy as np
+# (B, k_total, kmax, dense edge capacity) of a pooled batch: what the coarsenings size their arrays by.  kmax may be an upper bound on
+# the largest k_g and cap on sum k_g (k_g - 1) when the per-graph sizes stay on the device (size-stable captured steps).
+KeepBounds = namedtuple("KeepBounds", "b k kmax cap")
 
-    if isinstance(keep_sizes, dict):
-        b, k, kmax = int(keep_sizes["b"]), int(keep_sizes["k"]), int(keep_sizes["kmax"])
-        return b, k, kmax, k * max(kmax - 1, 0)
+
+def _keep_info(keep_sizes) -> KeepBounds:
+    """``keep_sizes`` itself when it is a KeepBounds, else the exact bounds of the host array of the batch's k_g."""
+    if isinstance(keep_sizes, KeepBounds):
+        return keep_sizes
     keep = np.asarray(keep_sizes, dtype=np.int64)
     b, k = int(keep.shape[0]), int(keep.sum())
-    return b, k, (int(keep.max()) if b else 0), int((keep * (keep - 1)).sum())
+    return KeepBounds(b, k, (int(keep.max()) if b else 0), int((keep * (keep - 1)).sum()))
 
 
 def asap_coarsen_dense(s_in_ptr, s_in_src, s_out_ptr, s_out_dst, graph_ptr, new_graph_ptr, perm, num_nodes, keep_sizes, slot):
     """Pooled structure arrays (in_ptr, in_src, out_ptr, out_dst, out_eid, loops, slot) and the capacity of the edge
-    arrays, with NO device->host copy (mlqem_asap_coarsen_dense).  ``keep_sizes``: host array of k_g per graph (or bounds:
-    ``_keep_info``).  ``slot``: [N], slot[perm[p]] = p, -1 elsewhere (``segment_topk(..., with_slot=True)``)."""
+    arrays, with NO device->host copy (mlqem_asap_coarsen_dense).  ``keep_sizes``: host array of k_g per graph, or a
+    ``KeepBounds``.  ``slot``: [N], slot[perm[p]] = p, -1 elsewhere (``segment_topk(..., with_slot=True)``)."""
     b, k, kmax, cap = _keep_info(keep_sizes)
     dev = perm.device
     lib = _lib.load()

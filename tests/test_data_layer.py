@@ -145,3 +145,35 @@ def test_deferred_structure_builds_its_connectivity_on_first_use():
         pass
     else:
         raise AssertionError("unknown attributes must raise")
+
+
+def test_family_b_nodes_reject_host_tensors_before_any_launch(monkeypatch):
+    """TransformerConv and ASAPooling have no CPU path: a host tensor is a NativeLibraryError at the node's entry, and the native
+    library is never reached (a launch on host addresses would be a device memory fault, not an error message)."""
+    import torch
+
+    from blackwater.native import _lib
+    from blackwater.native import functional as F
+    from blackwater.native.structure import GraphStructure
+    from blackwater.nn.family_b import ASAPooling, TransformerConv
+
+    class LibraryReached(Exception):
+        pass
+
+    def load():
+        raise LibraryReached("the native library was reached with host tensors")
+
+    monkeypatch.setattr(_lib, "load", load)
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32)
+    # a path 0 -> 1 -> 2 -> 3, one graph
+    s = GraphStructure(4, i32([0, 0, 1, 2, 3]), i32([0, 1, 2]), i32([0, 1, 2, 3, 3]), i32([1, 2, 3]), i32([0, 0, 0, 0]), i32([0, 4]), 1,
+                       num_edges=3, graph_sizes=[4], out_eid=i32([0, 1, 2]))
+    x = torch.randn(4, 6)
+    with pytest.raises(_lib.NativeLibraryError):
+        F.asap_pool(x, ASAPooling(6), s)
+    with pytest.raises(_lib.NativeLibraryError):
+        TransformerConv(6, 3, heads=2).train()(x, s)
+    with pytest.raises(_lib.NativeLibraryError):
+        TransformerConv(6, 3, heads=2).eval()(x, s)
+    with pytest.raises(_lib.NativeLibraryError), torch.no_grad():
+        TransformerConv(6, 3, heads=2).eval()(x, s)

@@ -38,7 +38,7 @@ extern "C" {
 
 typedef void* mlqem_stream_t; /* hipStream_t */
 
-#define MLQEM_ABI_VERSION 45 /* bumped whenever a signature below changes; bindings compare it at load time */
+#define MLQEM_ABI_VERSION 46 /* bumped whenever a signature below changes; bindings compare it at load time */
 int mlqem_abi_version(void);
 const char* mlqem_error_string(int code);
 
@@ -1058,6 +1058,38 @@ typedef struct mlqem_forest_node { float thr; int32_t feature; int32_t right; in
 int mlqem_forest_predict_f32(const float* x, int64_t ldx, int64_t n_rows, int F, const mlqem_forest_node* nodes,
                              const int64_t* tree_ptr, int T, const double* values, int K, int max_depth, double* out,
                              int32_t* leaf, mlqem_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Linear least squares (ABI 46).  Replaces ols.fit(X, y) / ols.predict(X) of a scikit-learn LinearRegression (or Ridge) on
+ * encode_data rows (docs/tutorials/h12_ols.ipynb, h17_compare_over_steps.ipynb; ScikitLearningModelProcessor(ols, ...) in the VQE
+ * drivers).  The fit is one streaming pass over the rows on the device (the moments below) and a solve of at most 529 x 529 on the
+ * host (blackwater.nn.linear_model.solve_moments); scoring is one launch.
+ *
+ * mlqem_linreg_moments_f32: with A = [1 | x | y] (n_rows x D, D = 1 + F + K) writes moments = A^T A as float64 [D, D], both
+ * triangles filled: row 0 holds n, the column sums of x and the column sums of y.  x is float32 [n_rows, F] with row stride
+ * ldx >= F, y float32 [n_rows, K] with row stride ldy >= K; columns beyond F and K are never read.  The float32 inputs are
+ * widened to fp64 before they are multiplied, so every product is exact (24 + 24 bits <= 53) and only the summation rounds: an
+ * entry is within n 2^-53 sum|a_i b_i| of the exact one.
+ * Determinism: no atomics.  The rows are cut into chunks whose size is a function of (n_rows, F, K) alone, every chunk's partial
+ * sums go to `workspace` (mlqem_linreg_moments_workspace_bytes(n_rows, F, K) bytes, 16-byte aligned; MLQEM_ERR_WORKSPACE when
+ * smaller) and a final kernel adds them in chunk order and writes M[i, j] and M[j, i] from the same sum: results are bit-identical
+ * from call to call and exactly symmetric.
+ * accumulate != 0 adds to what `moments` holds (a streaming fit over shards; a sum over ranks later); accumulate == 0 overwrites.
+ * With n_rows == 0 the call writes zeros (accumulate == 0) or nothing (accumulate != 0) and launches no kernel.
+ * Serves 1 <= F <= 512 and 1 <= K <= 16 (MLQEM_ERR_UNSUPPORTED beyond).  Negative sizes, ldx < F and ldy < K give
+ * MLQEM_ERR_BAD_ARG; all arguments are checked before anything is launched.  Capturable in a hipGraph.
+ *
+ * mlqem_linreg_predict_f32: out[r, k] = intercept[k] + sum_j coef[k, j] * x[r, j], with coef float64 [K, F] (row-major,
+ * scikit-learn's coef_), intercept float64 [K] and out float64 [n_rows, K].  The sum is formed in fp64 with fused multiply-adds in
+ * column order j = 0 .. F-1, starting from the intercept, by one thread per row: results are bit-identical from call to call and do
+ * not depend on n_rows or on how rows are tiled over workgroups.  No workspace; capturable in a hipGraph; n_rows == 0 returns
+ * MLQEM_OK without a launch.  The same F and K limits.
+ * ---------------------------------------------------------------------------------------------------- */
+size_t mlqem_linreg_moments_workspace_bytes(int64_t n_rows, int F, int K);
+int mlqem_linreg_moments_f32(const float* x, int64_t ldx, const float* y, int64_t ldy, int64_t n_rows, int F, int K,
+                             double* moments, int accumulate, void* workspace, size_t workspace_bytes, mlqem_stream_t stream);
+int mlqem_linreg_predict_f32(const float* x, int64_t ldx, int64_t n_rows, int F, const double* coef, const double* intercept,
+                             int K, double* out, mlqem_stream_t stream);
 
 #ifdef __cplusplus
 }

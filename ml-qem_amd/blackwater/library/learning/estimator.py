@@ -3,8 +3,9 @@ post-processed by a pluggable processor (reference: blackwater/library/learning/
 
 In scope: the decorator, the job wrapper, the processor protocol, ``TorchLearningModelProcessor``,
 ``EmptyProcessor``, ``ScikitLearningModelProcessor`` (the random-forest / OLS baselines: same feature rows, the
-model stays on the host CPU by design) and ``ForestLearningModelProcessor`` (an addition: the
-same random forests scored on the device by the forest kernel, one launch per ``run()``).  ``ZNEProcessor`` (runs extra noisy circuits
+model stays on the host CPU), ``ForestLearningModelProcessor`` and ``LinearLearningModelProcessor``
+(additions: the same random forests and the same OLS / ridge models scored on the device by the forest and least-squares kernels,
+one launch per ``run()``).  ``ZNEProcessor`` (runs extra noisy circuits
 through a ZNE estimator; no model) is out of scope.
 """
 from __future__ import annotations
@@ -109,28 +110,16 @@ class ScikitLearningModelProcessor(LearningMethodEstimatorProcessor):
         return total
 
 
-class ForestLearningModelProcessor(LearningMethodEstimatorProcessor):
-    """The random-forest mitigator of the reference's demos and VQE drivers (``ScikitLearningModelProcessor(rfr, backend)``,
-    reference :90-148) scored on the device: the same per-term ``encode_data`` rows, all (circuit, Pauli term) rows of a ``run()``
-    through ONE launch of the forest kernel (``blackwater.nn.ForestRegressor``), ``output[:, 0] * coeff`` summed per circuit.
-
-    ``model``: a fitted scikit-learn ``RandomForestRegressor`` / ``ExtraTreesRegressor`` / ``DecisionTreeRegressor`` (converted with
-    ``ForestRegressor.from_sklearn``) or a ``ForestRegressor``.  There is no host path: ``device`` must be a GPU."""
+class _DeviceRegressorProcessor(LearningMethodEstimatorProcessor):
+    """What the device-side scikit-learn replacements share: the per-term ``encode_data`` rows of
+    ``ScikitLearningModelProcessor``, all (circuit, Pauli term) rows of a ``run()`` through ONE ``self._model.predict`` launch,
+    ``output[:, 0] * coeff`` summed per circuit.  Subclasses set ``_model`` (a module on ``_device``), ``_device``, ``_backend`` and
+    ``_properties``."""
 
     accepts_qasm_text = True     # process_batch scans OpenQASM text natively: PostProcessedJob hands text over unparsed
 
-    def __init__(self, model, backend, device="cuda"):
-        from ...nn.forest import ForestRegressor
-
-        if not isinstance(model, ForestRegressor):
-            model = ForestRegressor.from_sklearn(model)   # BlackwaterException for anything that is not a fitted regression forest
-        self._model = model.to(device)
-        self._device = torch.device(device)
-        self._backend = backend
-        self._properties = get_backend_properties_v1(backend)
-
     def _score(self, rows: torch.Tensor) -> np.ndarray:
-        """First output of the forest for every row (float64, as scikit-learn's ``predict`` returns it)."""
+        """First output of the model for every row (float64, as scikit-learn's ``predict`` returns it)."""
         out = self._model.predict(rows.to(self._device, dtype=torch.float32))
         return out.reshape(rows.shape[0], -1)[:, 0].cpu().numpy()
 
@@ -144,7 +133,7 @@ class ForestLearningModelProcessor(LearningMethodEstimatorProcessor):
         return total
 
     def process_batch(self, expectation_values, circuits, observables, parameter_values):
-        """All (circuit, Pauli term) rows of one ``run()`` through ONE forest launch; results equal ``process`` applied circuit by
+        """All (circuit, Pauli term) rows of one ``run()`` through ONE launch; results equal ``process`` applied circuit by
         circuit (the same rows, the same per-circuit order of the sum)."""
         rows, owners, coeffs, values, bases = [], [], [], [], []
         for k, (value, circuit, obs) in enumerate(zip(expectation_values, circuits, observables)):
@@ -164,6 +153,44 @@ class ForestLearningModelProcessor(LearningMethodEstimatorProcessor):
         for k, o, c in zip(owners, out, coeffs):
             totals[k] = totals[k] + o * c
         return totals
+
+
+class ForestLearningModelProcessor(_DeviceRegressorProcessor):
+    """The random-forest mitigator of the reference's demos and VQE drivers (``ScikitLearningModelProcessor(rfr, backend)``,
+    reference :90-148) scored on the device: the same per-term ``encode_data`` rows, all (circuit, Pauli term) rows of a ``run()``
+    through ONE launch of the forest kernel (``blackwater.nn.ForestRegressor``), ``output[:, 0] * coeff`` summed per circuit.
+
+    ``model``: a fitted scikit-learn ``RandomForestRegressor`` / ``ExtraTreesRegressor`` / ``DecisionTreeRegressor`` (converted with
+    ``ForestRegressor.from_sklearn``) or a ``ForestRegressor``.  There is no host path: ``device`` must be a GPU."""
+
+    def __init__(self, model, backend, device="cuda"):
+        from ...nn.forest import ForestRegressor
+
+        if not isinstance(model, ForestRegressor):
+            model = ForestRegressor.from_sklearn(model)   # BlackwaterException for anything that is not a fitted regression forest
+        self._model = model.to(device)
+        self._device = torch.device(device)
+        self._backend = backend
+        self._properties = get_backend_properties_v1(backend)
+
+
+class LinearLearningModelProcessor(_DeviceRegressorProcessor):
+    """The OLS mitigator of the reference's tutorials and VQE drivers (``ScikitLearningModelProcessor(ols, backend)``, reference
+    :90-148) scored on the device: the same per-term ``encode_data`` rows, all (circuit, Pauli term) rows of a ``run()`` through ONE
+    launch of the least-squares predict kernel (``blackwater.nn.LinearRegressor``), ``output[:, 0] * coeff`` summed per circuit.
+
+    ``model``: a fitted scikit-learn ``LinearRegression`` / ``Ridge`` (converted with ``LinearRegressor.from_sklearn``) or a
+    ``LinearRegressor`` (``LinearRegressor.fit`` fits one on the device).  There is no host path: ``device`` must be a GPU."""
+
+    def __init__(self, model, backend, device="cuda"):
+        from ...nn.linear_model import LinearRegressor
+
+        if not isinstance(model, LinearRegressor):
+            model = LinearRegressor.from_sklearn(model)   # BlackwaterException for anything that is not a fitted linear model
+        self._model = model.to(device)
+        self._device = torch.device(device)
+        self._backend = backend
+        self._properties = get_backend_properties_v1(backend)
 
 
 class EmptyProcessor(LearningMethodEstimatorProcessor):

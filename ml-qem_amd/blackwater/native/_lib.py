@@ -184,12 +184,15 @@ SIGNATURES = {
     "mlqem_circuit_features_qasm": (_I, [c_char_p, _P, _I, _P, _I, _P, _P]),
     "mlqem_circuit_features_qasm_batch": (_I, [_P, _L, _P, _I, _P, _I, _I, _P, _P, _P]),
     "mlqem_forest_predict_f32": (_I, [_P, _L, _L, _I, _P, _P, _I, _P, _I, _I, _P, _P, _P]),
+    "mlqem_linreg_moments_workspace_bytes": (_S, [_L, _I, _I]),
+    "mlqem_linreg_moments_f32": (_I, [_P, _L, _P, _L, _L, _I, _I, _P, _I, _P, _S, _P]),
+    "mlqem_linreg_predict_f32": (_I, [_P, _L, _L, _I, _P, _P, _I, _P, _P]),
 }
 
 _lib = None
 ERR_UNSUPPORTED = -2   # MLQEM_ERR_UNSUPPORTED: a shape this kernel does not serve
 ERR_WORKSPACE = -4   # MLQEM_ERR_WORKSPACE: a caller-provided buffer is too small (the encoder then says what it needs)
-ABI_VERSION = 45   # MLQEM_ABI_VERSION of include/mlqem_hip.h; bumped whenever a signature changes
+ABI_VERSION = 46   # MLQEM_ABI_VERSION of include/mlqem_hip.h; bumped whenever a signature changes
 
 
 def load() -> ctypes.CDLL:

@@ -2122,3 +2122,61 @@ def forest_predict(x, nodes, tree_ptr, values, max_depth, *, want_leaf=False, ou
                                                 _p(out), _p(leaf_out), _stream())
     _lib.check(code, "mlqem_forest_predict_f32")
     return out, leaf_out
+
+
+LINREG_MAX_FEATURES = 512   # F and K the least-squares kernels serve
+LINREG_MAX_OUTPUTS = 16
+
+
+def linreg_moments(x, y, *, out=None, accumulate=False):
+    """The fit's streaming pass (mlqem_linreg_moments_f32): float64 [D, D] = A^T A for A = [1 | x | y], D = 1 + F + K, both
+    triangles filled (row 0: n, the column sums of x, the column sums of y).  ``x``: float32 [n, F], ``y``: float32 [n, K], row
+    strides >= F and K (the columns beyond are never read).  Products of the widened float32 inputs are exact in fp64; only the
+    summation rounds, in an order fixed by (n, F, K): two calls give the same bits.
+
+    ``accumulate=True`` adds to what ``out`` holds (required then): a streaming fit over shards.  Nothing here waits for the
+    device or reads a tensor's contents; the workspace of the chunks' partial sums is allocated per call."""
+    ldx, ldy = _mat(x, "x"), _mat(y, "y")
+    n, f, k = int(x.shape[0]), int(x.shape[1]), int(y.shape[1])
+    if y.shape[0] != n or y.device != x.device:
+        raise ValueError(f"linreg: x is {tuple(x.shape)} on {x.device}, y {tuple(y.shape)} on {y.device}: want the same rows and device")
+    d = 1 + f + k
+    if out is None:
+        if accumulate:
+            raise ValueError("linreg: accumulate=True adds to `out`; give it")
+        out = torch.empty((d, d), dtype=torch.float64, device=x.device)
+    elif (not out.is_cuda or out.device != x.device or out.dtype != torch.float64 or tuple(out.shape) != (d, d)
+          or not out.is_contiguous()):
+        raise ValueError(f"out: want contiguous float64 [{d}, {d}] on {x.device}, got {tuple(out.shape)} {out.dtype} {out.device}")
+    lib = _lib.load()
+    need = int(lib.mlqem_linreg_moments_workspace_bytes(n, f, k)) if n > 0 else 0
+    work = torch.empty(need, dtype=torch.uint8, device=x.device) if need else None
+    code = lib.mlqem_linreg_moments_f32(_p(x), ldx, _p(y), ldy, n, f, k, _p(out), int(bool(accumulate)), _p(work), need, _stream())
+    _lib.check(code, "mlqem_linreg_moments_f32")
+    return out
+
+
+def linreg_predict(x, coef, intercept, *, out=None):
+    """Linear scoring (mlqem_linreg_predict_f32): float64 [n, K] with ``out[r, k] = intercept[k] + sum_j coef[k, j] x[r, j]``,
+    summed in fp64 in column order from the intercept.  ``x``: float32 [n, F] (row stride >= F), ``coef``: contiguous float64
+    [K, F], ``intercept``: float64 [K] -- the buffers of ``blackwater.nn.LinearRegressor``.  Nothing here waits for the device or
+    reads a tensor's contents, and with ``out`` given nothing is allocated: the call can be captured in a hipGraph."""
+    ldx = _mat(x, "x")
+    n, f = int(x.shape[0]), int(x.shape[1])
+    _mat(coef, "coef", torch.float64)
+    k = int(coef.shape[0])
+    if coef.shape[1] != f or not coef.is_contiguous():
+        raise ValueError(f"linreg: want contiguous coef [K, {f}] for rows of {f} features, got {tuple(coef.shape)}")
+    _vec(intercept, "intercept", k, torch.float64)
+    if intercept.shape[0] != k:
+        raise ValueError(f"linreg: intercept has {intercept.shape[0]} entries, coef {k} rows")
+    if coef.device != x.device or intercept.device != x.device:
+        raise ValueError(f"linreg: x is on {x.device}, the model on {coef.device}")
+    if out is None:
+        out = torch.empty((n, k), dtype=torch.float64, device=x.device)
+    elif (not out.is_cuda or out.device != x.device or out.dtype != torch.float64 or tuple(out.shape) != (n, k)
+          or not out.is_contiguous()):
+        raise ValueError(f"out: want contiguous float64 [{n}, {k}] on {x.device}, got {tuple(out.shape)} {out.dtype} {out.device}")
+    code = _lib.load().mlqem_linreg_predict_f32(_p(x), ldx, n, f, _p(coef), _p(intercept), k, _p(out), _stream())
+    _lib.check(code, "mlqem_linreg_predict_f32")
+    return out

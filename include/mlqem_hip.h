@@ -38,7 +38,7 @@ extern "C" {
 
 typedef void* mlqem_stream_t; /* hipStream_t */
 
-#define MLQEM_ABI_VERSION 46 /* bumped whenever a signature below changes; bindings compare it at load time */
+#define MLQEM_ABI_VERSION 47 /* bumped whenever a signature below changes; bindings compare it at load time */
 int mlqem_abi_version(void);
 const char* mlqem_error_string(int code);
 
@@ -1058,6 +1058,63 @@ typedef struct mlqem_forest_node { float thr; int32_t feature; int32_t right; in
 int mlqem_forest_predict_f32(const float* x, int64_t ldx, int64_t n_rows, int F, const mlqem_forest_node* nodes,
                              const int64_t* tree_ptr, int T, const double* values, int K, int max_depth, double* out,
                              int32_t* leaf, mlqem_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Growing a regression forest (ABI 47).  Replaces RandomForestRegressor(...).fit(X_train, y_train) with scikit-learn's defaults
+ * (docs/tutorials/vqe_rf*.py, both demos, h15 / h19 / h21 / h26 / h33 / h36): exact CART with squared error, the best splitter
+ * over all features, grown level by level for a chunk of Tc trees at once.  blackwater.native.ops.forest_fit drives it.
+ *
+ * The rule (scikit-learn 1.7's best splitter with the MSE criterion, restated).  A tree's rows are the rows with counts[t, r] > 0
+ * and its weights are the counts; a node's sample count is its number of DISTINCT in-bag rows (a bag handed over as sample
+ * weights).  With W = sum w, S_k = sum w y_k, Q = sum w sum_k y_k^2 over the node's rows: value = S / W, impurity =
+ * (Q / W - sum_k (S_k / W)^2) / K.  A node at depth d is a leaf when d >= max_depth, rows < min_samples_split,
+ * rows < 2 min_samples_leaf, impurity <= 2.220446049250313e-16, or it has no candidate.  A candidate of feature f separates
+ * positions p - 1 | p of the node's rows sorted by x[:, f]; it exists where v[p] > v[p - 1] + 1e-7f in float32 and both sides keep
+ * min_samples_leaf rows.  Its score is sum_k sl_k^2 / wl + sum_k (S_k - sl_k)^2 / (W - wl) with (wl, sl) the sums of the left
+ * side; the highest score wins, on equal scores the lowest feature and then the lowest position (scikit-learn draws the feature
+ * order at random).  Any candidate is taken, a zero-gain one included.  threshold = double(v[p - 1]) / 2 + double(v[p]) / 2,
+ * replaced by double(v[p - 1]) when that sum equals double(v[p]) or is infinite; rows with x[f] <= threshold go left.
+ *
+ * mlqem_forest_fit_state: the inputs and the workspace of one chunk of Tc trees, every pointer device memory of the caller.
+ *   x float32 [n, F] with row stride ldx >= F, finite; y float64 [n, K], finite; counts int32 [Tc, n] >= 0, every tree with a
+ *   positive one; order int32 [F, n]: order[f] = a STABLE argsort of x[:, f] (the same for every tree).
+ *   rows [2][Tc][F][n], segid [2][Tc][n], level [2][Tc][4], seg_i [2][Tc][n][4] (int32; level, seg_i 16-byte aligned): the
+ *   double-buffered row lists, per-position segment ids, (live segments, live positions, nodes so far, 0) per tree and
+ *   (first position, rows, node, feature whose list orders the sums) per live segment.  seg_stat float64 [Tc][n][K + 2] = (W, Q,
+ *   S[K]).  cand_score float64 / cand_pos int32 [Tc][F][n]: the best candidate per (tree, feature, segment), cand_pos = p or -1.
+ *   split_i int32 [Tc][n][4] (16-byte aligned) = (split feature or -1, first position in the next list, rows going left, left
+ *   child's segment) and split_thr float64 [Tc][n] per segment of the level.
+ *   Output, per tree at most 2 n - 1 nodes, node 0 the root, children appended level by level: node_i int32 [Tc][2n-1][4]
+ *   (16-byte aligned) = (feature or -2, left, right, rows; left = right = -1 for a leaf), node_thr float64 [Tc][2n-1],
+ *   node_value float64 [Tc][2n-1][K].  mlqem_forest_fit_tree_bytes(n, F, K) is the sum of these sizes for ONE tree.
+ *
+ * mlqem_forest_fit_init fills buffer 0 (the root's lists: `order` compacted to the in-bag rows, stable) and level / seg_i of the
+ * root.  Level d = 0, 1, ... is then mlqem_forest_fit_stats, _search, _select, _partition with level = d, in this order on one
+ * stream; they read buffer d & 1 and write the other.  After _select of level d, level[(d + 1) & 1][t] holds tree t's live
+ * segments of level d + 1 and its node count: the caller reads it and stops when no tree has a live segment (at most
+ * min(max_depth, n - 1) + 1 levels).  A tree without live segments costs nothing but its workgroups' first load.
+ *
+ * Determinism: no atomics.  Every sum is a segmented scan over 256-position tiles in list order with the running sums carried
+ * from tile to tile, so it depends on (n, F, K, counts) alone: two fits give the same bits, and so does any chunking of the trees
+ * (a tree reads no other tree's state).  Safety: every loop is bounded by n, F or K; every index read from the workspace is clamped
+ * before it addresses memory; no workgroup waits for another.  Serves 1 <= n <= 2^22, 1 <= F <= 32767, 1 <= K <= 16, Tc F < 2^31
+ * (MLQEM_ERR_UNSUPPORTED beyond); min_samples_split >= 2, min_samples_leaf >= 1, max_depth >= 0 and non-null, aligned buffers
+ * (MLQEM_ERR_BAD_ARG otherwise), all checked before a launch.  The node table is NOT validated here: ForestRegressor.fit passes it
+ * through the same host validation as from_arrays before mlqem_forest_predict_f32 sees it.
+ * ---------------------------------------------------------------------------------------------------- */
+typedef struct mlqem_forest_fit_state {
+  const float* x; int64_t ldx; const double* y; const int32_t* counts; const int32_t* order;
+  int64_t n; int32_t F, K, Tc, min_samples_split, min_samples_leaf, max_depth;
+  int32_t* rows; int32_t* segid; int32_t* level; int32_t* seg_i; double* seg_stat;
+  double* cand_score; int32_t* cand_pos; int32_t* split_i; double* split_thr;
+  int32_t* node_i; double* node_thr; double* node_value;
+} mlqem_forest_fit_state;
+size_t mlqem_forest_fit_tree_bytes(int64_t n, int F, int K);
+int mlqem_forest_fit_init(const mlqem_forest_fit_state* state, mlqem_stream_t stream);
+int mlqem_forest_fit_stats(const mlqem_forest_fit_state* state, int level, mlqem_stream_t stream);
+int mlqem_forest_fit_search(const mlqem_forest_fit_state* state, int level, mlqem_stream_t stream);
+int mlqem_forest_fit_select(const mlqem_forest_fit_state* state, int level, mlqem_stream_t stream);
+int mlqem_forest_fit_partition(const mlqem_forest_fit_state* state, int level, mlqem_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Linear least squares (ABI 46).  Replaces ols.fit(X, y) / ols.predict(X) of a scikit-learn LinearRegression (or Ridge) on

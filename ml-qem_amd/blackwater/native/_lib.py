@@ -43,6 +43,15 @@ class ColParts(ctypes.Structure):
                 ("reserved", ctypes.c_int32), ("ptr", c_void_p * MAX_COL_PARTS), ("ld", c_int64 * MAX_COL_PARTS)]
 
 
+class ForestFitState(ctypes.Structure):
+    """``mlqem_forest_fit_state``: the inputs and the workspace of one chunk of trees of a forest fit."""
+
+    _fields_ = ([("x", c_void_p), ("ldx", c_int64), ("y", c_void_p), ("counts", c_void_p), ("order", c_void_p), ("n", c_int64)]
+                + [(k, ctypes.c_int32) for k in ("F", "K", "Tc", "min_samples_split", "min_samples_leaf", "max_depth")]
+                + [(k, c_void_p) for k in ("rows", "segid", "level", "seg_i", "seg_stat", "cand_score", "cand_pos", "split_i",
+                                           "split_thr", "node_i", "node_thr", "node_value")])
+
+
 # name -> (restype, argtypes); kept in the order of include/mlqem_hip.h
 SIGNATURES = {
     "mlqem_abi_version": (_I, []),
@@ -184,6 +193,12 @@ SIGNATURES = {
     "mlqem_circuit_features_qasm": (_I, [c_char_p, _P, _I, _P, _I, _P, _P]),
     "mlqem_circuit_features_qasm_batch": (_I, [_P, _L, _P, _I, _P, _I, _I, _P, _P, _P]),
     "mlqem_forest_predict_f32": (_I, [_P, _L, _L, _I, _P, _P, _I, _P, _I, _I, _P, _P, _P]),
+    "mlqem_forest_fit_tree_bytes": (_S, [_L, _I, _I]),
+    "mlqem_forest_fit_init": (_I, [_P, _P]),
+    "mlqem_forest_fit_stats": (_I, [_P, _I, _P]),
+    "mlqem_forest_fit_search": (_I, [_P, _I, _P]),
+    "mlqem_forest_fit_select": (_I, [_P, _I, _P]),
+    "mlqem_forest_fit_partition": (_I, [_P, _I, _P]),
     "mlqem_linreg_moments_workspace_bytes": (_S, [_L, _I, _I]),
     "mlqem_linreg_moments_f32": (_I, [_P, _L, _P, _L, _L, _I, _I, _P, _I, _P, _S, _P]),
     "mlqem_linreg_predict_f32": (_I, [_P, _L, _L, _I, _P, _P, _I, _P, _P]),
@@ -192,7 +207,7 @@ SIGNATURES = {
 _lib = None
 ERR_UNSUPPORTED = -2   # MLQEM_ERR_UNSUPPORTED: a shape this kernel does not serve
 ERR_WORKSPACE = -4   # MLQEM_ERR_WORKSPACE: a caller-provided buffer is too small (the encoder then says what it needs)
-ABI_VERSION = 46   # MLQEM_ABI_VERSION of include/mlqem_hip.h; bumped whenever a signature changes
+ABI_VERSION = 47   # MLQEM_ABI_VERSION of include/mlqem_hip.h; bumped whenever a signature changes
 
 
 def load() -> ctypes.CDLL:

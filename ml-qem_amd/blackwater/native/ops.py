@@ -5,6 +5,7 @@ matching the CSR arrays) BEFORE launching -- a kernel that reads out of bounds c
 """
 from __future__ import annotations
 
+import ctypes
 import os
 from collections import namedtuple
 from typing import Optional
@@ -2122,6 +2123,112 @@ def forest_predict(x, nodes, tree_ptr, values, max_depth, *, want_leaf=False, ou
                                                 _p(out), _p(leaf_out), _stream())
     _lib.check(code, "mlqem_forest_predict_f32")
     return out, leaf_out
+
+
+FOREST_FIT_MAX_ROWS = 1 << 22   # n the fit kernels serve
+
+
+def forest_fit_tree_bytes(n, f, k):
+    """Workspace bytes of ONE tree of a forest fit on ``n`` rows of ``f`` features with ``k`` outputs (mlqem_forest_fit_tree_bytes)."""
+    return int(_lib.load().mlqem_forest_fit_tree_bytes(int(n), int(f), int(k)))
+
+
+def _forest_fit_run(lib, stream, x, y, counts, order, min_samples_split, min_samples_leaf, max_depth, tc, profile=None):
+    """The host loop of ``forest_fit`` for tensors that are already checked; every buffer is allocated on ``x.device``."""
+    n, f = int(x.shape[0]), int(x.shape[1])
+    k, t_all, dev = int(y.shape[1]), int(counts.shape[0]), x.device
+    nn = 2 * n - 1
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)      # noqa: E731
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)    # noqa: E731
+    buf = dict(rows=i32(2, tc, f, n), segid=i32(2, tc, n), level=i32(2, tc, 4), seg_i=i32(2, tc, n, 4), seg_stat=f64(tc, n, k + 2),
+               cand_score=f64(tc, f, n), cand_pos=i32(tc, f, n), split_i=i32(tc, n, 4), split_thr=f64(tc, n),
+               node_i=i32(tc, nn, 4), node_thr=f64(tc, nn), node_value=f64(tc, nn, k))
+    max_levels = min(max_depth, n - 1) + 1   # a node at depth max_depth, or one of a single row (depth <= n - 1), is a leaf
+    steps = (("stats", lib.mlqem_forest_fit_stats), ("search", lib.mlqem_forest_fit_search), ("select", lib.mlqem_forest_fit_select),
+             ("partition", lib.mlqem_forest_fit_partition))
+
+    def launch(name, fn, *args):
+        if profile is not None:
+            start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+        _lib.check(fn(*args), "mlqem_forest_fit_" + name)
+        if profile is not None:
+            end.record()
+            profile.setdefault(name, []).append((start, end))
+
+    node_i, node_thr, node_value, node_count, levels = [], [], [], [], 0
+    for t0 in range(0, t_all, tc):
+        c = min(tc, t_all - t0)   # the chunk's buffers are the first c trees' worth of every allocation
+        state = _lib.ForestFitState(x=_p(x), ldx=int(x.stride(0)) if n > 1 else f, y=_p(y), counts=_p(counts[t0:t0 + c]), order=_p(order),
+                                    n=n, F=f, K=k, Tc=c, min_samples_split=int(min_samples_split), min_samples_leaf=int(min_samples_leaf),
+                                    max_depth=int(max_depth), **{name: _p(t) for name, t in buf.items()})
+        ref = ctypes.byref(state)
+        launch("init", lib.mlqem_forest_fit_init, ref, stream)
+        flat_level = buf["level"].view(-1)
+        for d in range(max_levels):
+            for name, fn in steps[:3]:
+                launch(name, fn, ref, d, stream)
+            nxt = (d + 1) & 1
+            live = flat_level[nxt * c * 4:(nxt + 1) * c * 4].cpu().view(c, 4)   # the level's one read: live segments, nodes so far
+            levels = max(levels, d + 1)
+            if not bool(live[:, 0].any()):
+                break
+            launch("partition", steps[3][1], ref, d, stream)
+        else:
+            raise _lib.NativeLibraryError(f"forest_fit: live segments remain after {max_levels} levels")
+        count = live[:, 2].to(torch.int64)
+        if bool((count < 1).any()) or bool((count > nn).any()):
+            raise _lib.NativeLibraryError("forest_fit: a tree's node count is out of range")
+        keep = (torch.arange(nn)[None, :] < count[:, None]).to(dev)
+        node_i.append(buf["node_i"].view(-1)[:c * nn * 4].view(c, nn, 4)[keep].cpu())
+        node_thr.append(buf["node_thr"].view(-1)[:c * nn].view(c, nn)[keep].cpu())
+        node_value.append(buf["node_value"].view(-1)[:c * nn * k].view(c, nn, k)[keep].cpu())
+        node_count.append(count)
+    node_i = torch.cat(node_i).numpy()
+    tree_ptr = np.concatenate([[0], np.cumsum(torch.cat(node_count).numpy())]).astype(np.int64)
+    return dict(tree_ptr=tree_ptr, feature=node_i[:, 0].astype(np.int64), threshold=torch.cat(node_thr).numpy(),
+                left=node_i[:, 1].astype(np.int64), right=node_i[:, 2].astype(np.int64), value=torch.cat(node_value).numpy(),
+                n_node_samples=node_i[:, 3].astype(np.int64), levels=levels, trees_per_chunk=tc)
+
+
+def forest_fit(x, y, counts, *, min_samples_split=2, min_samples_leaf=1, max_depth=None, workspace_bytes=2 << 30, profile=None):
+    """Grows a regression forest on the device (mlqem_forest_fit_*; include/mlqem_hip.h states the rule): one exact CART tree with
+    squared error per row of ``counts``.  ``x``: float32 [n, F] (row stride >= F), ``y``: contiguous float64 [n, K], ``counts``:
+    contiguous int32 [T, n] -- how often each row is in each tree's bag -- all on one device; the VALUES (finite x and y, counts
+    >= 0 and not all zero in a tree) are the caller's to check, as ``blackwater.nn.ForestRegressor.fit`` does.
+
+    Returns host numpy arrays: ``tree_ptr`` int64 [T + 1] and, per node in the device's numbering (root 0, children appended level by
+    level), ``feature`` (-2 for a leaf), ``threshold`` float64, ``left`` / ``right`` (-1 for a leaf), ``value`` float64 [N, K],
+    ``n_node_samples`` (distinct in-bag rows); plus ``levels`` and ``trees_per_chunk``.  The node table comes straight from the
+    kernels: validate it (``ForestRegressor.from_arrays``) before it is scored.
+
+    Trees are grown in chunks sized so that a chunk's workspace fits ``workspace_bytes``; the forest does not depend on the chunking,
+    bit for bit.  One stable argsort per column is shared by all trees.  Every level costs four launches and one small read of the
+    device (the fit cannot be captured in a hipGraph).  ``profile``: a dict that collects (start, end) events per kernel name."""
+    ldx = _mat(x, "x")
+    n, f = int(x.shape[0]), int(x.shape[1])
+    _mat(y, "y", torch.float64)
+    _mat(counts, "counts", torch.int32)
+    k, t = int(y.shape[1]), int(counts.shape[0])
+    if y.shape[0] != n or counts.shape[1] != n or not y.is_contiguous() or not counts.is_contiguous():
+        raise ValueError(f"forest_fit: x is {tuple(x.shape)}: want contiguous y [{n}, K] and counts [T, {n}], got {tuple(y.shape)} and "
+                         f"{tuple(counts.shape)}")
+    if y.device != x.device or counts.device != x.device:
+        raise ValueError(f"forest_fit: x is on {x.device}, y on {y.device}, counts on {counts.device}")
+    if not (1 <= n <= FOREST_FIT_MAX_ROWS and 1 <= f <= FOREST_MAX_FEATURES and 1 <= k <= FOREST_MAX_OUTPUTS and t >= 1 and ldx >= f):
+        raise ValueError(f"forest_fit: want 1 <= n <= {FOREST_FIT_MAX_ROWS}, 1 <= F <= {FOREST_MAX_FEATURES}, 1 <= K <= "
+                         f"{FOREST_MAX_OUTPUTS} and a tree, got n {n}, F {f}, K {k}, T {t}")
+    if min_samples_split < 2 or min_samples_leaf < 1 or (max_depth is not None and max_depth < 0):
+        raise ValueError("forest_fit: want min_samples_split >= 2, min_samples_leaf >= 1 and max_depth >= 0 (or None)")
+    lib = _lib.load()
+    per_tree = int(lib.mlqem_forest_fit_tree_bytes(n, f, k))
+    tc = min(t, int(workspace_bytes) // per_tree, (2 ** 31 - 1) // f)
+    if tc < 1:
+        raise ValueError(f"forest_fit: one tree of {n} rows x {f} features x {k} outputs needs {per_tree} bytes of workspace, "
+                         f"workspace_bytes is {int(workspace_bytes)}")
+    order = torch.argsort(x.t(), dim=1, stable=True).to(torch.int32).contiguous()   # [F, n], once per fit
+    depth = 2 ** 31 - 1 if max_depth is None else min(int(max_depth), 2 ** 31 - 1)
+    return _forest_fit_run(lib, _stream(), x, y, counts, order, min_samples_split, min_samples_leaf, depth, tc, profile)
 
 
 LINREG_MAX_FEATURES = 512   # F and K the least-squares kernels serve

@@ -12,6 +12,9 @@ Buffers (include/mlqem_hip.h documents the node record):
   ``tree_ptr``  int64 [T + 1]: tree t owns nodes tree_ptr[t] .. tree_ptr[t + 1];
   ``value``     float64 [N, K]: the trees' node values in the model's own node order;
   ``meta``      int64 [2]: (number of features, maximum depth).
+
+``ForestRegressor.fit`` grows the forest on the device as well (exact CART, scikit-learn's defaults: the ``mlqem_forest_fit_*`` kernels),
+so the mitigator needs scikit-learn neither to be trained nor to be scored.
 """
 from __future__ import annotations
 
@@ -35,6 +38,15 @@ def floor_to_float32(thr64: np.ndarray) -> np.ndarray:
     above = thr32.astype(np.float64) > thr64
     thr32[above] = np.nextafter(thr32[above], np.float32(-np.inf))
     return thr32
+
+
+def bootstrap_counts(n: int, n_estimators: int, seed: int) -> torch.Tensor:
+    """int32 [n_estimators, n]: how often each of ``n`` rows is drawn into each tree's bag.  The generator is
+    ``numpy.random.default_rng(seed).integers(0, n, size=(n_estimators, n))`` (PCG64; row t holds tree t's n draws with replacement),
+    counted per tree -- every row of the result sums to ``n``.  These are not scikit-learn's bags."""
+    draws = np.random.default_rng(int(seed)).integers(0, int(n), size=(int(n_estimators), int(n)))
+    counts = np.stack([np.bincount(d, minlength=int(n)) for d in draws]).astype(np.int32)
+    return torch.from_numpy(counts)
 
 
 def _pack(tree_ptr, feature, threshold, left, right, n_features):
@@ -117,7 +129,7 @@ def _pack(tree_ptr, feature, threshold, left, right, n_features):
 class ForestRegressor(torch.nn.Module):
     """A fitted regression forest (mean of T regression trees with K outputs) as a torch module on the native kernel.
 
-    Build one with ``from_sklearn``, ``from_arrays`` or ``from_state_dict``; both array constructors validate the forest on the
+    Build one with ``fit``, ``from_sklearn``, ``from_arrays`` or ``from_state_dict``; both array constructors validate the forest on the
     host (``ValueError``), so a malformed one never reaches the device."""
 
     def __init__(self, nodes: torch.Tensor, tree_ptr: torch.Tensor, value: torch.Tensor, n_features: int, max_depth: int):
@@ -151,6 +163,72 @@ class ForestRegressor(torch.nn.Module):
             raise ValueError(f"forest: value must be [{n}, K] with 1 <= K <= {ops.FOREST_MAX_OUTPUTS}, got shape {value.shape}")
         return cls(torch.from_numpy(nodes), torch.from_numpy(tree_ptr), torch.from_numpy(np.ascontiguousarray(value)),
                    n_features, max_depth)
+
+    @classmethod
+    def fit(cls, x: torch.Tensor, y: torch.Tensor, *, n_estimators: int = 100, bootstrap: bool = True, max_depth=None,
+            min_samples_split: int = 2, min_samples_leaf: int = 1, seed: int = 0, sample_counts=None,
+            workspace_bytes: int = 2 << 30) -> "ForestRegressor":
+        """``RandomForestRegressor(n_estimators, ...).fit(x, y)`` with scikit-learn's defaults, grown on ``x.device``: exact CART with
+        squared error and the best split over ALL features, one tree per bag (include/mlqem_hip.h states the rule node by node).
+
+        ``x``: float32 [n, F] device tensor; ``y``: [n] or [n, K] on the same device, float32 or float64 (widened to float64 before
+        anything is multiplied).  ``sample_counts``: int32 [T, n], how often each row is in each tree's bag; when given it overrides
+        ``n_estimators``, ``bootstrap`` and ``seed``.  Otherwise ``bootstrap=False`` gives every tree every row once, and
+        ``bootstrap=True`` the counts of ``bootstrap_counts(n, n_estimators, seed)`` (numpy's ``default_rng(seed)``; not scikit-learn's
+        bags).  A node's sample count is its number of distinct in-bag rows, as in scikit-learn's forest.
+
+        Equal scores are broken by the lowest feature index, then the lowest position (scikit-learn: a random feature order), so a
+        tree equals scikit-learn's where no two candidates tie.  Two fits give the same buffers bit for bit, whatever
+        ``workspace_bytes`` (it bounds the fit's workspace: trees are grown in chunks that fit it).
+
+        Not supported: ``max_features`` below 1.0, criteria other than squared error, ``min_weight_fraction_leaf``, ``ccp_alpha``,
+        missing values, out-of-bag scores.  Every argument is checked on the host before anything is launched (``ValueError`` /
+        ``BlackwaterException``); the finished node table goes through the validation of ``from_arrays``."""
+        if not isinstance(x, torch.Tensor) or not isinstance(y, torch.Tensor):
+            raise ValueError("forest fit: x and y must be torch tensors")
+        if x.dim() != 2 or x.dtype != torch.float32:
+            raise ValueError(f"forest fit: x must be float32 [n, F], got {tuple(x.shape)} {x.dtype}")
+        n, f = int(x.shape[0]), int(x.shape[1])
+        if y.dim() not in (1, 2) or y.shape[0] != n or y.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"forest fit: y must be float32 or float64 [{n}] or [{n}, K], got {tuple(y.shape)} {y.dtype}")
+        k = 1 if y.dim() == 1 else int(y.shape[1])
+        if n < 1 or n > ops.FOREST_FIT_MAX_ROWS:
+            raise ValueError(f"forest fit: want 1 <= n <= {ops.FOREST_FIT_MAX_ROWS} rows, got {n}")
+        if not 1 <= k <= ops.FOREST_MAX_OUTPUTS:
+            raise ValueError(f"forest fit: want 1 <= K <= {ops.FOREST_MAX_OUTPUTS} outputs, got {k}")
+        if not 1 <= f <= ops.FOREST_MAX_FEATURES:
+            raise ValueError(f"forest fit: want 1 <= F <= {ops.FOREST_MAX_FEATURES} features, got {f}")
+        if min_samples_split < 2 or min_samples_leaf < 1 or (max_depth is not None and max_depth < 0):
+            raise ValueError("forest fit: want min_samples_split >= 2, min_samples_leaf >= 1 and max_depth >= 0 (or None), got "
+                             f"{min_samples_split}, {min_samples_leaf}, {max_depth}")
+        if sample_counts is None:
+            if n_estimators < 1:
+                raise ValueError(f"forest fit: n_estimators must be >= 1, got {n_estimators}")
+            counts = bootstrap_counts(n, n_estimators, seed) if bootstrap else torch.ones((int(n_estimators), n), dtype=torch.int32)
+        else:
+            counts = sample_counts
+            if not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or counts.dim() != 2 or counts.shape[0] < 1 \
+                    or counts.shape[1] != n:
+                raise ValueError(f"forest fit: sample_counts must be an int32 [T, {n}] tensor with T >= 1")
+            host = counts.cpu()
+            if bool((host < 0).any()):
+                raise ValueError("forest fit: sample_counts has a negative entry")
+            if bool((host.max(dim=1).values < 1).any()):
+                raise ValueError(f"forest fit: tree {int(torch.nonzero(host.max(dim=1).values < 1)[0])} has an empty bag")
+        if not x.is_cuda or y.device != x.device:
+            raise BlackwaterException(f"forest fit: x and y must live on one GPU (got {x.device} and {y.device}); there is no CPU path")
+        if f == 1 and n > 1 and x.stride(1) != 1:   # a [n, 1] view may carry any column stride
+            x = x.as_strided((n, 1), (x.stride(0), 1))
+        y64 = y.reshape(n, k).to(torch.float64).contiguous()
+        if not bool(torch.isfinite(x).all() & torch.isfinite(y64).all()):   # one reduction, one wait
+            raise ValueError("forest fit: x or y holds a NaN or an infinity")
+        grown = ops.forest_fit(x, y64, counts.to(x.device).contiguous(), min_samples_split=int(min_samples_split),
+                               min_samples_leaf=int(min_samples_leaf), max_depth=None if max_depth is None else int(max_depth),
+                               workspace_bytes=int(workspace_bytes))
+        forest = cls.from_arrays(*(grown[key] for key in ("tree_ptr", "feature", "threshold", "left", "right", "value")),
+                                 n_features=f).to(x.device)
+        forest.fit_info = {key: grown[key] for key in ("levels", "trees_per_chunk", "n_node_samples")}
+        return forest
 
     @classmethod
     def from_sklearn(cls, model) -> "ForestRegressor":

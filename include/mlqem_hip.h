@@ -38,7 +38,7 @@ extern "C" {
 
 typedef void* mlqem_stream_t; /* hipStream_t */
 
-#define MLQEM_ABI_VERSION 47 /* bumped whenever a signature below changes; bindings compare it at load time */
+#define MLQEM_ABI_VERSION 48 /* bumped whenever a signature below changes; bindings compare it at load time */
 int mlqem_abi_version(void);
 const char* mlqem_error_string(int code);
 
@@ -1058,6 +1058,29 @@ typedef struct mlqem_forest_node { float thr; int32_t feature; int32_t right; in
 int mlqem_forest_predict_f32(const float* x, int64_t ldx, int64_t n_rows, int F, const mlqem_forest_node* nodes,
                              const int64_t* tree_ptr, int T, const double* values, int K, int max_depth, double* out,
                              int32_t* leaf, mlqem_stream_t stream);
+
+/* Out-of-bag prediction (ABI 48).  Replaces the oob_prediction_ of RandomForestRegressor(oob_score=True): every row is scored by the
+ * trees whose bag does not hold it,
+ *
+ *   out[r, k] = (1 / n_oob[r]) * sum_{t : counts[t, r] == 0} values[(tree_ptr[t] + leaf_t(x[r, :])) * K + k]
+ *
+ * with n_oob[r] the number of such trees.  counts is int32 [T][ldc] with ldc >= n_rows (device): counts[t * ldc + r] == 0  <=>  tree
+ * t is out of bag for row r.  Any non-zero count means in bag; a count is never used as an index.  A row with n_oob[r] == 0 gets
+ * out[r, :] = 0.0 (scikit-learn's behaviour).  out is float64 [n_rows, K], n_oob int32 [n_rows], leaf (optional) int32 [n_rows, T]:
+ * the leaf in the model's numbering, or -1 for an in-bag pair.  Nodes, tree_ptr, values, x and max_depth are those of
+ * mlqem_forest_predict_f32, and it is the same kernel: an in-bag pair does not walk.
+ * The walk takes at most max_depth steps, whatever the node table holds, and every index it forms from a node record or from counts
+ * is clamped: a malformed table gives a wrong answer, never a spin or an out-of-range read.  Every load is unconditional on a clamped
+ * address and masked by a select, the counts load of a lane past the last row or the last tree included.
+ * The sum over trees is formed in float64 in tree order, by one thread per (row, output), and divided by n_oob[r] once: results are
+ * bit-identical from call to call and do not depend on n_rows, on how rows are tiled over workgroups (64, 16 or 4 rows) or on ldc.
+ * No atomics and no workspace.  With scikit-learn's own bags the result equals its oob_prediction_ bit for bit (it adds in estimator
+ * order as well).  Serves 1 <= K <= 16, 1 <= F <= 32767, T >= 1 (MLQEM_ERR_UNSUPPORTED beyond); counts and n_oob non-null and
+ * ldc >= n_rows besides the checks of mlqem_forest_predict_f32 (MLQEM_ERR_BAD_ARG); n_rows == 0 returns MLQEM_OK without a launch. */
+int mlqem_forest_predict_oob_f32(const float* x, int64_t ldx, int64_t n_rows, int F, const mlqem_forest_node* nodes,
+                                 const int64_t* tree_ptr, int T, const double* values, int K, int max_depth,
+                                 const int32_t* counts, int64_t ldc, double* out, int32_t* n_oob, int32_t* leaf,
+                                 mlqem_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Growing a regression forest (ABI 47).  Replaces RandomForestRegressor(...).fit(X_train, y_train) with scikit-learn's defaults

@@ -193,6 +193,7 @@ SIGNATURES = {
     "mlqem_circuit_features_qasm": (_I, [c_char_p, _P, _I, _P, _I, _P, _P]),
     "mlqem_circuit_features_qasm_batch": (_I, [_P, _L, _P, _I, _P, _I, _I, _P, _P, _P]),
     "mlqem_forest_predict_f32": (_I, [_P, _L, _L, _I, _P, _P, _I, _P, _I, _I, _P, _P, _P]),
+    "mlqem_forest_predict_oob_f32": (_I, [_P, _L, _L, _I, _P, _P, _I, _P, _I, _I, _P, _L, _P, _P, _P, _P]),
     "mlqem_forest_fit_tree_bytes": (_S, [_L, _I, _I]),
     "mlqem_forest_fit_init": (_I, [_P, _P]),
     "mlqem_forest_fit_stats": (_I, [_P, _I, _P]),
@@ -207,7 +208,7 @@ SIGNATURES = {
 _lib = None
 ERR_UNSUPPORTED = -2   # MLQEM_ERR_UNSUPPORTED: a shape this kernel does not serve
 ERR_WORKSPACE = -4   # MLQEM_ERR_WORKSPACE: a caller-provided buffer is too small (the encoder then says what it needs)
-ABI_VERSION = 47   # MLQEM_ABI_VERSION of include/mlqem_hip.h; bumped whenever a signature changes
+ABI_VERSION = 48   # MLQEM_ABI_VERSION of include/mlqem_hip.h; bumped whenever a signature changes
 
 
 def load() -> ctypes.CDLL:

@@ -2090,15 +2090,8 @@ FOREST_MAX_OUTPUTS = 16     # K the forest kernel serves
 FOREST_MAX_FEATURES = 32767
 
 
-def forest_predict(x, nodes, tree_ptr, values, max_depth, *, want_leaf=False, out=None, leaf_out=None):
-    """Regression-forest inference (mlqem_forest_predict_f32): ``(out, leaf)`` with ``out`` float64 [n, K] = the mean over trees
-    of the leaf values of every row of ``x`` (float32 [n, F], row stride >= F) and ``leaf`` int32 [n, T] (the leaf each tree
-    puts the row in, in the model's own node numbering; None unless ``want_leaf`` or ``leaf_out`` is given).
-
-    ``nodes``: int32 [N, 4] packed records (thr32 bits, feature, right, orig) in depth-first pre-order, ``tree_ptr``: int64
-    [T + 1], ``values``: float64 [N, K] in the model's node order -- the buffers of ``blackwater.nn.ForestRegressor``.
-    Nothing here waits for the device or reads a tensor's contents, and with ``out`` (and ``leaf_out``) given nothing is
-    allocated: the call can be captured in a hipGraph."""
+def _forest_checked(x, nodes, tree_ptr, values, want_leaf, out, leaf_out):
+    """The checks both forest entries share; allocates the outputs that were not given.  Returns (ldx, n, f, t, k, out, leaf_out)."""
     ldx = _mat(x, "x")
     n, f = int(x.shape[0]), int(x.shape[1])
     _mat(nodes, "nodes", torch.int32)
@@ -2119,10 +2112,48 @@ def forest_predict(x, nodes, tree_ptr, values, max_depth, *, want_leaf=False, ou
     elif leaf_out is not None and (not leaf_out.is_cuda or leaf_out.dtype != torch.int32 or tuple(leaf_out.shape) != (n, t)
                                    or not leaf_out.is_contiguous()):
         raise ValueError(f"leaf_out: want contiguous int32 [{n}, {t}] on the device, got {tuple(leaf_out.shape)} {leaf_out.dtype}")
+    return ldx, n, f, t, k, out, leaf_out
+
+
+def forest_predict(x, nodes, tree_ptr, values, max_depth, *, want_leaf=False, out=None, leaf_out=None):
+    """Regression-forest inference (mlqem_forest_predict_f32): ``(out, leaf)`` with ``out`` float64 [n, K] = the mean over trees
+    of the leaf values of every row of ``x`` (float32 [n, F], row stride >= F) and ``leaf`` int32 [n, T] (the leaf each tree
+    puts the row in, in the model's own node numbering; None unless ``want_leaf`` or ``leaf_out`` is given).
+
+    ``nodes``: int32 [N, 4] packed records (thr32 bits, feature, right, orig) in depth-first pre-order, ``tree_ptr``: int64
+    [T + 1], ``values``: float64 [N, K] in the model's node order -- the buffers of ``blackwater.nn.ForestRegressor``.
+    Nothing here waits for the device or reads a tensor's contents, and with ``out`` (and ``leaf_out``) given nothing is
+    allocated: the call can be captured in a hipGraph."""
+    ldx, n, f, t, k, out, leaf_out = _forest_checked(x, nodes, tree_ptr, values, want_leaf, out, leaf_out)
     code = _lib.load().mlqem_forest_predict_f32(_p(x), ldx, n, f, _p(nodes), _p(tree_ptr), t, _p(values), k, int(max_depth),
                                                 _p(out), _p(leaf_out), _stream())
     _lib.check(code, "mlqem_forest_predict_f32")
     return out, leaf_out
+
+
+def forest_predict_oob(x, nodes, tree_ptr, values, max_depth, counts, *, want_leaf=False, out=None, n_oob_out=None, leaf_out=None):
+    """Out-of-bag prediction (mlqem_forest_predict_oob_f32): ``(out, n_oob, leaf)``.  ``out`` float64 [n, K] is the mean of the leaf
+    values over the trees t with ``counts[t, r] == 0`` only, ``n_oob`` int32 [n] their number (a row without one gets 0.0) and
+    ``leaf`` int32 [n, T] the leaf of every out-of-bag pair and -1 for an in-bag one (None unless ``want_leaf`` or ``leaf_out``).
+
+    ``counts``: int32 [T, n] on ``x``'s device, how often each row is in each tree's bag; unit column stride and any row stride
+    >= n, so a column slice ``counts[:, a:b]`` goes in without a copy.  Everything else, and every check, is ``forest_predict``'s.
+    Nothing here waits for the device or reads a tensor's contents, and with ``out``, ``n_oob_out`` (and ``leaf_out``) given
+    nothing is allocated: the call can be captured in a hipGraph."""
+    ldx, n, f, t, k, out, leaf_out = _forest_checked(x, nodes, tree_ptr, values, want_leaf, out, leaf_out)
+    ldc = _mat(counts, "counts", torch.int32)
+    if tuple(counts.shape) != (t, n) or counts.device != x.device or ldc < n:
+        raise ValueError(f"counts: want int32 [{t}, {n}] on {x.device} with row stride >= {n}, got {tuple(counts.shape)} on "
+                         f"{counts.device} with strides {counts.stride()}")
+    if n_oob_out is None:
+        n_oob_out = torch.empty((n,), dtype=torch.int32, device=x.device)
+    elif n_oob_out.device != x.device or tuple(n_oob_out.shape) != (n,):
+        raise ValueError(f"n_oob_out: want int32 [{n}] on {x.device}, got {tuple(n_oob_out.shape)} on {n_oob_out.device}")
+    _vec(n_oob_out, "n_oob_out", n, torch.int32)
+    code = _lib.load().mlqem_forest_predict_oob_f32(_p(x), ldx, n, f, _p(nodes), _p(tree_ptr), t, _p(values), k, int(max_depth),
+                                                    _p(counts), ldc, _p(out), _p(n_oob_out), _p(leaf_out), _stream())
+    _lib.check(code, "mlqem_forest_predict_oob_f32")
+    return out, n_oob_out, leaf_out
 
 
 FOREST_FIT_MAX_ROWS = 1 << 22   # n the fit kernels serve

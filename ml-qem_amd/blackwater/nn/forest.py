@@ -14,9 +14,13 @@ Buffers (include/mlqem_hip.h documents the node record):
   ``meta``      int64 [2]: (number of features, maximum depth).
 
 ``ForestRegressor.fit`` grows the forest on the device as well (exact CART, scikit-learn's defaults: the ``mlqem_forest_fit_*`` kernels),
-so the mitigator needs scikit-learn neither to be trained nor to be scored.
+so the mitigator needs scikit-learn neither to be trained nor to be scored.  ``oob_predict`` scores every row with the trees whose
+bag does not hold it (``mlqem_forest_predict_oob_f32``, scikit-learn's ``oob_prediction_``); ``fit(oob_score=True)``, ``score`` and
+``oob_permutation_importance`` are built on it.
 """
 from __future__ import annotations
+
+import warnings
 
 import numpy as np
 import torch
@@ -47,6 +51,28 @@ def bootstrap_counts(n: int, n_estimators: int, seed: int) -> torch.Tensor:
     draws = np.random.default_rng(int(seed)).integers(0, int(n), size=(int(n_estimators), int(n)))
     counts = np.stack([np.bincount(d, minlength=int(n)) for d in draws]).astype(np.int32)
     return torch.from_numpy(counts)
+
+
+def r2_score(y: torch.Tensor, pred: torch.Tensor) -> torch.Tensor:
+    """scikit-learn's ``r2_score(y, pred)`` as a float64 scalar on ``y``'s device: per output 1 - sum (y - p)^2 / sum (y - mean y)^2
+    over ALL rows, a zero denominator giving 1.0 when the numerator is 0 as well and 0.0 otherwise; then the uniform mean over the
+    outputs.  ``y`` and ``pred`` are [n] or [n, K]; fewer than two rows give NaN."""
+    n = int(y.shape[0])
+    y = y.reshape(n, -1).to(torch.float64)
+    pred = pred.reshape(n, -1).to(torch.float64)
+    if y.shape != pred.shape:
+        raise ValueError(f"r2_score: y is {tuple(y.shape)}, the prediction {tuple(pred.shape)}")
+    if n < 2:
+        return torch.full((), float("nan"), dtype=torch.float64, device=y.device)
+    num = ((y - pred) ** 2).sum(dim=0)
+    den = ((y - y.mean(dim=0, keepdim=True)) ** 2).sum(dim=0)
+    ratio = 1.0 - num / torch.where(den != 0, den, torch.ones_like(den))
+    flat = torch.where(num != 0, torch.zeros_like(num), torch.ones_like(num))
+    return torch.where(den != 0, ratio, flat).mean()
+
+
+OOB_WARNING = ("Some inputs do not have OOB scores. This probably means too few trees were used to compute any reliable OOB "
+               "estimates.")   # scikit-learn's wording
 
 
 def _pack(tree_ptr, feature, threshold, left, right, n_features):
@@ -167,7 +193,7 @@ class ForestRegressor(torch.nn.Module):
     @classmethod
     def fit(cls, x: torch.Tensor, y: torch.Tensor, *, n_estimators: int = 100, bootstrap: bool = True, max_depth=None,
             min_samples_split: int = 2, min_samples_leaf: int = 1, seed: int = 0, sample_counts=None,
-            workspace_bytes: int = 2 << 30) -> "ForestRegressor":
+            workspace_bytes: int = 2 << 30, oob_score: bool = False) -> "ForestRegressor":
         """``RandomForestRegressor(n_estimators, ...).fit(x, y)`` with scikit-learn's defaults, grown on ``x.device``: exact CART with
         squared error and the best split over ALL features, one tree per bag (include/mlqem_hip.h states the rule node by node).
 
@@ -181,8 +207,14 @@ class ForestRegressor(torch.nn.Module):
         tree equals scikit-learn's where no two candidates tie.  Two fits give the same buffers bit for bit, whatever
         ``workspace_bytes`` (it bounds the fit's workspace: trees are grown in chunks that fit it).
 
+        ``oob_score=True`` (scikit-learn's): once the forest is built and validated, ``oob_predict`` runs on the training rows with
+        the fit's own counts and sets ``oob_prediction_`` (float64 [n] or [n, K], device), ``oob_count_`` (int32 [n], device: the trees
+        that left each row out) and ``oob_score_`` (a Python float: ``r2_score(y, oob_prediction_)``, a row without an out-of-bag tree
+        counting with its 0.0); the counts stay as ``fit_info["sample_counts"]``.  These are plain attributes, not buffers: the state
+        dict does not change.  It needs bags: with ``bootstrap=False`` and no ``sample_counts`` it is a ``ValueError``.
+
         Not supported: ``max_features`` below 1.0, criteria other than squared error, ``min_weight_fraction_leaf``, ``ccp_alpha``,
-        missing values, out-of-bag scores.  Every argument is checked on the host before anything is launched (``ValueError`` /
+        missing values.  Every argument is checked on the host before anything is launched (``ValueError`` /
         ``BlackwaterException``); the finished node table goes through the validation of ``from_arrays``."""
         if not isinstance(x, torch.Tensor) or not isinstance(y, torch.Tensor):
             raise ValueError("forest fit: x and y must be torch tensors")
@@ -204,6 +236,8 @@ class ForestRegressor(torch.nn.Module):
         if sample_counts is None:
             if n_estimators < 1:
                 raise ValueError(f"forest fit: n_estimators must be >= 1, got {n_estimators}")
+            if oob_score and not bootstrap:
+                raise ValueError("forest fit: out of bag estimation is only available with bootstrap=True or explicit sample_counts")
             counts = bootstrap_counts(n, n_estimators, seed) if bootstrap else torch.ones((int(n_estimators), n), dtype=torch.int32)
         else:
             counts = sample_counts
@@ -222,12 +256,20 @@ class ForestRegressor(torch.nn.Module):
         y64 = y.reshape(n, k).to(torch.float64).contiguous()
         if not bool(torch.isfinite(x).all() & torch.isfinite(y64).all()):   # one reduction, one wait
             raise ValueError("forest fit: x or y holds a NaN or an infinity")
-        grown = ops.forest_fit(x, y64, counts.to(x.device).contiguous(), min_samples_split=int(min_samples_split),
+        counts = counts.to(x.device).contiguous()
+        grown = ops.forest_fit(x, y64, counts, min_samples_split=int(min_samples_split),
                                min_samples_leaf=int(min_samples_leaf), max_depth=None if max_depth is None else int(max_depth),
                                workspace_bytes=int(workspace_bytes))
         forest = cls.from_arrays(*(grown[key] for key in ("tree_ptr", "feature", "threshold", "left", "right", "value")),
                                  n_features=f).to(x.device)
         forest.fit_info = {key: grown[key] for key in ("levels", "trees_per_chunk", "n_node_samples")}
+        if oob_score:
+            pred, n_oob = forest._oob_run(x, counts)
+            forest._warn_if_no_oob(n_oob)
+            forest.oob_prediction_ = pred[:, 0] if k == 1 else pred
+            forest.oob_count_ = n_oob
+            forest.oob_score_ = float(r2_score(y64, pred))
+            forest.fit_info["sample_counts"] = counts
         return forest
 
     @classmethod
@@ -294,3 +336,87 @@ class ForestRegressor(torch.nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """float32 [n, K]: ``predict`` rounded, so the module composes with float32 torch code."""
         return self._run(x, False)[0].to(torch.float32)
+
+    def score(self, x: torch.Tensor, y: torch.Tensor) -> float:
+        """R^2 of ``predict(x)`` against ``y`` ([n] or [n, K] on ``x``'s device): scikit-learn's ``score`` (see ``r2_score``)."""
+        pred = self._run(x, False)[0]
+        if not isinstance(y, torch.Tensor) or y.dim() not in (1, 2) or y.numel() != pred.numel() or y.shape[0] != pred.shape[0]:
+            raise ValueError(f"forest score: y must be a [{pred.shape[0]}] or [{pred.shape[0]}, {self.n_outputs}] tensor")
+        return float(r2_score(y.to(pred.device), pred))
+
+    # ---- out-of-bag estimates -------------------------------------------------------------------------------------------------
+    def _check_oob_args(self, x, sample_counts, what):
+        """Host-side validation of (x, sample_counts), before anything is launched."""
+        if not isinstance(x, torch.Tensor):
+            raise ValueError(f"forest {what}: x must be a torch tensor, got {type(x).__name__}")
+        if x.dim() != 2 or x.shape[1] != self.n_features or x.dtype != torch.float32:
+            raise ValueError(f"forest {what}: want float32 rows of {self.n_features} features, got {tuple(x.shape)} {x.dtype}")
+        n = int(x.shape[0])
+        c = sample_counts
+        if not isinstance(c, torch.Tensor) or c.dtype != torch.int32:
+            raise ValueError(f"forest {what}: sample_counts must be an int32 tensor, got "
+                             f"{c.dtype if isinstance(c, torch.Tensor) else type(c).__name__}")
+        if c.dim() != 2 or tuple(c.shape) != (self.n_trees, n):
+            raise ValueError(f"forest {what}: sample_counts must be [{self.n_trees}, {n}] (trees, rows of x), got {tuple(c.shape)}")
+        if c.numel() and bool((c.cpu() < 0).any()):
+            raise ValueError(f"forest {what}: sample_counts has a negative entry")
+
+    def _oob_run(self, x, counts, out=None, n_oob=None):
+        """(out float64 [n, K], n_oob int32 [n]) for arguments that are already checked."""
+        out, n_oob, _ = ops.forest_predict_oob(x, self.nodes, self.tree_ptr, self.value, self.max_depth, counts, out=out, n_oob_out=n_oob)
+        return out, n_oob
+
+    @staticmethod
+    def _warn_if_no_oob(n_oob):
+        if n_oob.numel() and bool((n_oob == 0).any()):
+            warnings.warn(OOB_WARNING, UserWarning, stacklevel=3)
+
+    def oob_predict(self, x: torch.Tensor, sample_counts: torch.Tensor, return_counts: bool = False):
+        """float64 [n, K] ([n] when K == 1, as ``predict``): every row scored by the trees that did not draw it -- the mean of the leaf
+        values over the trees t with ``sample_counts[t, r] == 0``, scikit-learn's ``oob_prediction_`` (bit for bit with its own bags).
+        ``sample_counts``: int32 [T, n], how often row r of ``x`` is in tree t's bag (``fit_info["sample_counts"]`` of a forest fitted
+        with ``oob_score=True``; for a scikit-learn forest the ``bincount`` of its ``_generate_sample_indices``); checked on the host
+        first (``ValueError``).  A row every tree drew gets 0.0 and one ``UserWarning`` is raised.  With ``return_counts`` the
+        result is ``(prediction, n_oob)``, ``n_oob`` int32 [n] the number of out-of-bag trees per row."""
+        self._check_oob_args(x, sample_counts, "oob_predict")
+        out, n_oob = self._oob_run(x, sample_counts.to(x.device))
+        self._warn_if_no_oob(n_oob)
+        out = out[:, 0] if self.n_outputs == 1 else out
+        return (out, n_oob) if return_counts else out
+
+    def oob_permutation_importance(self, x: torch.Tensor, y: torch.Tensor, sample_counts: torch.Tensor, n_repeats: int = 1,
+                                   seed: int = 0) -> np.ndarray:
+        """Breiman's permutation importance from out-of-bag predictions, float64 [F] on the host:
+        ``importance[f] = mean_j (mse(oob_predict(x with column f permuted by perm(f, j))) - mse(oob_predict(x)))`` with
+        ``perm(f, j) = numpy.random.default_rng([seed, f, j]).permutation(n)`` and ``mse`` the float64 mean of ``(y - P)^2`` over the rows
+        that have an out-of-bag tree and over the outputs (``ValueError`` if no row has one).  A feature no tree splits on scores
+        exactly 0.0.  One working copy of ``x`` is made; a column is swapped in and back per feature."""
+        self._check_oob_args(x, sample_counts, "oob_permutation_importance")
+        n, nf, k = int(x.shape[0]), self.n_features, self.n_outputs
+        if not isinstance(y, torch.Tensor) or y.dim() not in (1, 2) or y.shape[0] != n or y.numel() != n * k \
+                or y.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"forest oob_permutation_importance: y must be float32 or float64 [{n}] or [{n}, {k}]")
+        if int(n_repeats) < 1:
+            raise ValueError(f"forest oob_permutation_importance: n_repeats must be >= 1, got {n_repeats}")
+        counts = sample_counts.to(x.device)
+        y64 = y.to(x.device).reshape(n, k).to(torch.float64)
+        work = x.clone()
+        out, n_oob = self._oob_run(work, counts)
+        seen = (n_oob > 0).unsqueeze(1)
+        rows = int(seen.sum())
+        if rows == 0:
+            raise ValueError("forest oob_permutation_importance: no row has an out-of-bag tree")
+
+        def mse():
+            return torch.where(seen, (y64 - out) ** 2, 0.0).sum() / float(rows * k)
+
+        base = mse()
+        importance = torch.zeros(nf, dtype=torch.float64, device=x.device)
+        for f in range(nf):
+            for j in range(int(n_repeats)):
+                perm = torch.from_numpy(np.random.default_rng([int(seed), f, j]).permutation(n)).to(x.device)
+                work[:, f] = x[perm, f]
+                self._oob_run(work, counts, out=out, n_oob=n_oob)
+                importance[f] += mse() - base
+            work[:, f] = x[:, f]
+        return (importance / float(n_repeats)).cpu().numpy()

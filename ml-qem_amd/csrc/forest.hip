@@ -18,6 +18,12 @@
 // The leaves of the chunk go to LDS ([tree of chunk][row], 4 KB); after a barrier thread (row, k) adds their values in TREE ORDER into
 // a float64 register that lives across chunks.  The sum is therefore the same for every R and every n_rows, bit for bit, and there is
 // no floating-point atomic and no workspace.
+//
+// The out-of-bag entry (mlqem_forest_predict_oob_f32) is the same kernel with OOB = true: out[r, :] is the mean over the trees t with
+// counts[t, r] == 0 only.  A (row, tree) pair that is in the bag is "at a leaf" from step 0, so it never holds the wave's trip count
+// open, and its slot of the LDS leaf array holds -1; the accumulating thread reads `values` at a clamped index, selects 0.0 for such a
+// slot and counts its row's out-of-bag trees in an integer register, which divides the sum once.  The counts load is unconditional
+// on a clamped (tree, row) and masked by a select; with R = 64 a wave reads 64 consecutive counts of one tree.
 #include "common.hpp"
 
 namespace mlqem {
@@ -30,12 +36,14 @@ constexpr int kForestMaxAcc = 4;                     // (row, k) sums per thread
 
 typedef int forest_i4 __attribute__((ext_vector_type(4)));
 
-template <bool XLDS>
+template <bool XLDS, bool OOB>
 __global__ __launch_bounds__(kBlock) void forest_predict_kernel(const float* __restrict__ x, int64_t ldx, int64_t n_rows, int F,
                                                                 const forest_i4* __restrict__ nodes,
                                                                 const int64_t* __restrict__ tree_ptr, int T,
                                                                 const double* __restrict__ values, int K, int max_depth, int log_r,
-                                                                double* __restrict__ out, int32_t* __restrict__ leaf_out) {
+                                                                double* __restrict__ out, int32_t* __restrict__ leaf_out,
+                                                                const int32_t* __restrict__ counts, int64_t ldc,
+                                                                int32_t* __restrict__ n_oob) {
   extern __shared__ int forest_smem[];
   int* leaves = forest_smem;                                             // [4 S][R]
   float* xs = reinterpret_cast<float*>(forest_smem + kForestChunkItems);   // [R][F | 1] when XLDS
@@ -59,23 +67,33 @@ __global__ __launch_bounds__(kBlock) void forest_predict_kernel(const float* __r
   // the (row, k) sums this thread owns: item e = tid + 256 m of the R K items, k fastest
   int acc_row[kForestMaxAcc], acc_k[kForestMaxAcc];
   double acc[kForestMaxAcc];
+  int acc_n[kForestMaxAcc];   // OOB: the out-of-bag trees of the row so far
 #pragma unroll
   for (int m = 0; m < kForestMaxAcc; ++m) {
     const int e = tid + kBlock * m;
     acc_row[m] = e / K;
     acc_k[m] = e - acc_row[m] * K;
     acc[m] = 0.0;
+    acc_n[m] = 0;
   }
+  const int64_t crow = OOB ? min(row0 + row, n_rows - 1) : 0;   // the row whose counts this thread reads, clamped
 
   for (int t0 = 0; t0 < T; t0 += TC) {
     int64_t base[kForestWalks];
     int last[kForestWalks], at[kForestWalks];
+    bool in_bag[kForestWalks];
 #pragma unroll
     for (int j = 0; j < kForestWalks; ++j) {
       const int t = min(t0 + slot + S * j, T - 1);   // a slot past the last tree walks the last tree again: loads stay unconditional
       base[j] = tree_ptr[t];
       last[j] = max((int)(tree_ptr[t + 1] - base[j]) - 1, 0);
       at[j] = 0;
+      if (OOB) {   // any non-zero count is in the bag; so is a lane past the last row or the last tree (nothing of it is used)
+        const int32_t cnt = counts[(int64_t)t * ldc + crow];
+        in_bag[j] = (cnt != 0) | (t0 + slot + S * j >= T) | (row0 + row >= n_rows);
+      } else {
+        in_bag[j] = false;
+      }
     }
     for (int d = 0; d < max_depth; ++d) {
       forest_i4 nd[kForestWalks];
@@ -84,7 +102,7 @@ __global__ __launch_bounds__(kBlock) void forest_predict_kernel(const float* __r
       bool inner = false;
 #pragma unroll
       for (int j = 0; j < kForestWalks; ++j) {
-        const bool is_leaf = nd[j].y < 0;
+        const bool is_leaf = OOB ? (nd[j].y < 0) | in_bag[j] : nd[j].y < 0;
         const int f = min(max(nd[j].y, 0), F - 1);
         const float xv = xrow[f];
         const int child = xv <= __builtin_bit_cast(float, nd[j].x) ? at[j] + 1 : nd[j].z;
@@ -96,7 +114,8 @@ __global__ __launch_bounds__(kBlock) void forest_predict_kernel(const float* __r
 #pragma unroll
     for (int j = 0; j < kForestWalks; ++j) {
       const int orig = nodes[base[j] + at[j]].w;
-      leaves[(slot + S * j) * R + row] = (int)min((unsigned)orig, (unsigned)last[j]);
+      const int lf = (int)min((unsigned)orig, (unsigned)last[j]);
+      leaves[(slot + S * j) * R + row] = OOB && in_bag[j] ? -1 : lf;
     }
     __syncthreads();
 
@@ -109,10 +128,22 @@ __global__ __launch_bounds__(kBlock) void forest_predict_kernel(const float* __r
         for (; c + 4 <= tc; c += 4) {   // four gathers in flight, added in tree order
           double v[4];
 #pragma unroll
-          for (int u = 0; u < 4; ++u) v[u] = values[(tree_ptr[t0 + c + u] + leaves[(c + u) * R + r]) * K + k];
+          for (int u = 0; u < 4; ++u) {
+            const int lf = leaves[(c + u) * R + r];
+            v[u] = values[(tree_ptr[t0 + c + u] + (OOB ? max(lf, 0) : lf)) * K + k];
+            if (OOB) {
+              v[u] = lf < 0 ? 0.0 : v[u];
+              acc_n[m] += lf >= 0;
+            }
+          }
           acc[m] += v[0]; acc[m] += v[1]; acc[m] += v[2]; acc[m] += v[3];
         }
-        for (; c < tc; ++c) acc[m] += values[(tree_ptr[t0 + c] + leaves[c * R + r]) * K + k];
+        for (; c < tc; ++c) {
+          const int lf = leaves[c * R + r];
+          const double v = values[(tree_ptr[t0 + c] + (OOB ? max(lf, 0) : lf)) * K + k];
+          acc[m] += OOB && lf < 0 ? 0.0 : v;
+          if (OOB) acc_n[m] += lf >= 0;
+        }
       }
     }
     if (leaf_out) {
@@ -127,7 +158,14 @@ __global__ __launch_bounds__(kBlock) void forest_predict_kernel(const float* __r
 
 #pragma unroll
   for (int m = 0; m < kForestMaxAcc; ++m) {
-    if (tid + kBlock * m < R * K && row0 + acc_row[m] < n_rows) out[(row0 + acc_row[m]) * K + acc_k[m]] = acc[m] / (double)T;
+    if (tid + kBlock * m < R * K && row0 + acc_row[m] < n_rows) {
+      if (OOB) {   // a row no tree left out gets 0.0 (scikit-learn's oob_prediction_ does the same)
+        out[(row0 + acc_row[m]) * K + acc_k[m]] = acc_n[m] > 0 ? acc[m] / (double)max(acc_n[m], 1) : 0.0;
+        if (acc_k[m] == 0) n_oob[row0 + acc_row[m]] = acc_n[m];
+      } else {
+        out[(row0 + acc_row[m]) * K + acc_k[m]] = acc[m] / (double)T;
+      }
+    }
   }
 }
 
@@ -136,15 +174,18 @@ __global__ __launch_bounds__(kBlock) void forest_predict_kernel(const float* __r
 
 using namespace mlqem;
 
-extern "C" int mlqem_forest_predict_f32(const float* x, int64_t ldx, int64_t n_rows, int F, const mlqem_forest_node* nodes,
-                                        const int64_t* tree_ptr, int T, const double* values, int K, int max_depth, double* out,
-                                        int32_t* leaf, mlqem_stream_t stream) {
+namespace {
+
+// Both entries: the checks, the tile and the launch.  `oob` selects the instantiation that reads counts and writes n_oob.
+int forest_predict_launch(const float* x, int64_t ldx, int64_t n_rows, int F, const mlqem_forest_node* nodes, const int64_t* tree_ptr,
+                          int T, const double* values, int K, int max_depth, bool oob, const int32_t* counts, int64_t ldc, double* out,
+                          int32_t* n_oob, int32_t* leaf, mlqem_stream_t stream) {
   static_assert(sizeof(mlqem_forest_node) == 16, "one 16-byte load per node");
   begin_launches();
-  if (n_rows < 0 || F < 1 || T < 1 || K < 1 || max_depth < 0 || ldx < F) return MLQEM_ERR_BAD_ARG;
+  if (n_rows < 0 || F < 1 || T < 1 || K < 1 || max_depth < 0 || ldx < F || (oob && ldc < n_rows)) return MLQEM_ERR_BAD_ARG;
   if (K > 16 || F > 32767) return MLQEM_ERR_UNSUPPORTED;
   if (n_rows == 0) return MLQEM_OK;
-  if (!x || !nodes || !tree_ptr || !values || !out || !aligned_to(nodes, 16)) return MLQEM_ERR_BAD_ARG;
+  if (!x || !nodes || !tree_ptr || !values || !out || !aligned_to(nodes, 16) || (oob && (!counts || !n_oob))) return MLQEM_ERR_BAD_ARG;
   // rows per workgroup: 64 once that still makes >= 512 workgroups (two per compute unit), fewer rows and more tree slots below
   int log_r = n_rows >= 32768 ? 6 : n_rows >= 8192 ? 4 : 2;
   const size_t row_bytes = (size_t)(F | 1) * sizeof(float);
@@ -154,12 +195,24 @@ extern "C" int mlqem_forest_predict_f32(const float* x, int64_t ldx, int64_t n_r
   if (blocks > 0x7FFFFFFFll) return MLQEM_ERR_UNSUPPORTED;
   const size_t lds = kForestChunkItems * sizeof(int) + (x_lds ? (row_bytes << log_r) : 0);
   const forest_i4* nd = reinterpret_cast<const forest_i4*>(nodes);
-  if (x_lds) {
-    hipLaunchKernelGGL(forest_predict_kernel<true>, dim3((unsigned)blocks), dim3(kBlock), lds, as_stream(stream), x, ldx, n_rows, F, nd,
-                       tree_ptr, T, values, K, max_depth, log_r, out, leaf);
-  } else {
-    hipLaunchKernelGGL(forest_predict_kernel<false>, dim3((unsigned)blocks), dim3(kBlock), lds, as_stream(stream), x, ldx, n_rows, F, nd,
-                       tree_ptr, T, values, K, max_depth, log_r, out, leaf);
-  }
+  auto kernel = oob ? (x_lds ? forest_predict_kernel<true, true> : forest_predict_kernel<false, true>)
+                    : (x_lds ? forest_predict_kernel<true, false> : forest_predict_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kBlock), lds, as_stream(stream), x, ldx, n_rows, F, nd, tree_ptr, T, values, K,
+                     max_depth, log_r, out, leaf, counts, ldc, n_oob);
   return launch_status();
+}
+
+}  // namespace
+
+extern "C" int mlqem_forest_predict_f32(const float* x, int64_t ldx, int64_t n_rows, int F, const mlqem_forest_node* nodes,
+                                        const int64_t* tree_ptr, int T, const double* values, int K, int max_depth, double* out,
+                                        int32_t* leaf, mlqem_stream_t stream) {
+  return forest_predict_launch(x, ldx, n_rows, F, nodes, tree_ptr, T, values, K, max_depth, false, nullptr, 0, out, nullptr, leaf, stream);
+}
+
+extern "C" int mlqem_forest_predict_oob_f32(const float* x, int64_t ldx, int64_t n_rows, int F, const mlqem_forest_node* nodes,
+                                            const int64_t* tree_ptr, int T, const double* values, int K, int max_depth,
+                                            const int32_t* counts, int64_t ldc, double* out, int32_t* n_oob, int32_t* leaf,
+                                            mlqem_stream_t stream) {
+  return forest_predict_launch(x, ldx, n_rows, F, nodes, tree_ptr, T, values, K, max_depth, true, counts, ldc, out, n_oob, leaf, stream);
 }

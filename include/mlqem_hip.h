@@ -288,6 +288,36 @@ int mlqem_linear_parts_f32(const mlqem_col_parts* x, const float* const* w_block
                            const mlqem_col_parts* y, int64_t N, const float* gate, int64_t ldgate, float gate_scale,
                            const int32_t* x_rows, mlqem_stream_t stream);
 
+#define MLQEM_FANOUT_MAX_TABLES 3
+
+/* The fan-out over up to MLQEM_FANOUT_MAX_TABLES INPUT TABLES that share one row map: table[j] is [M, cols] in the padded row
+ * layout (ldt % 4 == 0, 16-byte aligned), row n of every input is row x_rows[n] of its table (x_rows == NULL: row n).  The tables
+ * are the node features x and products of a graph operator with them that are constants of the dataset (A^ x of GCNConv, L^ x of
+ * ChebConv), so that a first layer's aggregation of its projection becomes a projection of the aggregated input.  Output block k
+ * (y[k]: [N, out_cols], padded rows) is
+ *     Y_k = act((T[w_table[k]] (w[k] - w_minus[k])^T + T[w2_table[k]] (w2_scale[k] * w2[k])^T + bias[k]) * rowscale[k])
+ * with the second term, w_minus, bias and rowscale optional (NULL); weights [out_cols, cols] row-major as the layers store them.
+ * act[k] != 0: ReLU, then inverted dropout (drop_p > 0) with the mask of mlqem_csr_aggregate_f32's epilogue -- one hash per four
+ * columns keyed by n * out_cols + column, seed + *seed_counter * 0xD1B54A32D192ED03 (seed_counter may be NULL).  At most
+ * MLQEM_MAX_COL_PARTS blocks and as many terms in all; 17 <= cols <= 24, out_cols <= 16 (else MLQEM_ERR_UNSUPPORTED).  Blocks of
+ * one term carry the values mlqem_linear_parts_f32 writes for them, bit for bit. */
+typedef struct mlqem_fanout_tables {
+  int32_t n_tables, n_blocks, cols, out_cols;
+  const void* table[MLQEM_FANOUT_MAX_TABLES];
+  int64_t ldt[MLQEM_FANOUT_MAX_TABLES];
+  void* y[MLQEM_MAX_COL_PARTS];
+  int64_t ldy[MLQEM_MAX_COL_PARTS];
+  const float* w[MLQEM_MAX_COL_PARTS];
+  const float* w_minus[MLQEM_MAX_COL_PARTS];
+  const float* w2[MLQEM_MAX_COL_PARTS];
+  const float* bias[MLQEM_MAX_COL_PARTS];
+  const float* rowscale[MLQEM_MAX_COL_PARTS];
+  float w2_scale[MLQEM_MAX_COL_PARTS];
+  int32_t w_table[MLQEM_MAX_COL_PARTS], w2_table[MLQEM_MAX_COL_PARTS], act[MLQEM_MAX_COL_PARTS];
+} mlqem_fanout_tables;
+int mlqem_linear_fanout_tables_f32(const mlqem_fanout_tables* d, int64_t N, const int32_t* x_rows, float drop_p, uint64_t seed,
+                                   const uint64_t* seed_counter, mlqem_stream_t stream);
+
 size_t mlqem_linear_wgrad_workspace_bytes(int I, int O);
 
 /* gw[o,i] (+)= sum_n gy[n,o] * x[n,i] ;  gb[o] (+)= sum_n gy[n,o]  (gb may be NULL).  Matrix-core partial sums per

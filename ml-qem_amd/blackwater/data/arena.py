@@ -117,6 +117,7 @@ class GraphArena:
         self.nscal = nscal  # [N,6]: gcn_dinv, sage_rinv, cheb_dinv, then the column sums P^T 1 of the three convs (structure.colsum)
         self.y, self.noisy, self.depth, self.observable = y, noisy, depth, observable
         self.device = x.device
+        self._first_layer = {}   # kind -> [M, F] table of a graph operator applied to x (first_layer_table), built on first request
 
     def __len__(self):
         return len(self.node_counts) - (1 if self.filler_nodes else 0)
@@ -234,6 +235,31 @@ class GraphArena:
         return GraphArena.from_arrays(xs, eis, y, noisy, depth, obs, device=device)
 
     # ------------------------------------------------------------------------------------------------
+    def first_layer_table(self, kind: str, build: bool = True) -> Optional[torch.Tensor]:
+        """The product of a conv's graph operator with the node features, for the WHOLE arena, in the padded row layout of ``x``
+        (filler rows included): ``"gcn"``: A^ x = D^-1/2 (A + I) D^-1/2 x, ``"cheb"``: L^ x = -D^-1/2 A D^-1/2 x.  x and the graphs
+        never change, so a first layer reads rows of these tables through the batch's row map instead of aggregating its
+        projection in every step (native/functional._FamilyAGraph).  Built on first request by the aggregation kernel itself, over
+        the arena's own CSR -- a batch's rows keep their edge order, so a table row equals what ``ops.csr_aggregate`` gives on the
+        batch, bit for bit.  ``build=False``: None unless it exists already.  Not part of a checkpoint (two [M, F] fp32 tables)."""
+        if kind not in ("gcn", "cheb"):
+            raise KeyError(kind)
+        t = self._first_layer.get(kind)
+        if t is None and build:
+            m, f = self.x.shape
+            dinv = self.nscal[:, 0 if kind == "gcn" else 2].contiguous()
+            out = ops.padded_empty(m, f, self.device)
+            if kind == "gcn":
+                kw = dict(cscale=dinv, rscale=dinv, dself=dinv * dinv)
+            else:
+                kw = dict(cscale=dinv, rscale=-dinv)
+            t = self._first_layer[kind] = ops.csr_aggregate(self.x, self.in_ptr, self.in_src, ell=self.in_ell, out=out, **kw)
+        return t
+
+    def first_layer_bytes(self) -> int:
+        """Device bytes the tables built so far hold."""
+        return sum(int(t.stride(0)) * int(t.shape[0]) * 4 for t in self._first_layer.values())
+
     _DEVICE_ARRAYS = ("x", "nscal", "gptr", "in_ptr", "in_src", "out_ptr", "out_dst", "out_eid", "loops", "in_ell", "out_ell",
                       "y", "noisy", "depth", "observable")
 
@@ -244,6 +270,7 @@ class GraphArena:
         import copy
 
         grown = copy.copy(self)
+        grown._first_layer = {}
         grown._base = {}
         for name in self._DEVICE_ARRAYS:
             t = getattr(self, name)
@@ -277,6 +304,7 @@ class GraphArena:
             view.copy_(t)
             setattr(self, name, view)
         self.node_counts, self.edge_counts, self.coarse_caps = other.node_counts, other.edge_counts, other.coarse_caps
+        self._first_layer = {}          # tables of the graphs that were here
         return True
 
     def selection(self, graph_ids, bucket=None, filler_sizes=None):
@@ -359,7 +387,8 @@ class GraphArena:
         s.coarse_capacity = coarse_capacity
         s.pool_plan = pool_plan           # size-stable batch: graph_sizes is None and the poolings go by this plan
         s.num_real = num_real
-        nodes = ops.RowsOf(self.x, src_node[:nb])     # the feature rows stay in the arena
+        # the feature rows stay in the arena; the first-layer tables (first_layer_table) go along as siblings under the same row map
+        nodes = ops.RowsOf(self.x, src_node[:nb], siblings=self.first_layer_table)
         # the per-graph inputs in ONE launch (five torch gathers before: a captured step of 32 small circuits is ~80 launches of ~5 us)
         labels = (self.y, self.noisy, self.depth, self.observable)
         if all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape[0] > 0 and t[0].numel() > 0 for t in labels):

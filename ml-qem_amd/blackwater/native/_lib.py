@@ -43,6 +43,21 @@ class ColParts(ctypes.Structure):
                 ("reserved", ctypes.c_int32), ("ptr", c_void_p * MAX_COL_PARTS), ("ld", c_int64 * MAX_COL_PARTS)]
 
 
+MAX_FANOUT_TABLES = 3   # MLQEM_FANOUT_MAX_TABLES
+
+
+class FanoutTables(ctypes.Structure):
+    """``mlqem_fanout_tables``: input tables that share one row map, and the one- or two-term output blocks projected from them."""
+
+    _fields_ = [("n_tables", ctypes.c_int32), ("n_blocks", ctypes.c_int32), ("cols", ctypes.c_int32), ("out_cols", ctypes.c_int32),
+                ("table", c_void_p * MAX_FANOUT_TABLES), ("ldt", c_int64 * MAX_FANOUT_TABLES),
+                ("y", c_void_p * MAX_COL_PARTS), ("ldy", c_int64 * MAX_COL_PARTS), ("w", c_void_p * MAX_COL_PARTS),
+                ("w_minus", c_void_p * MAX_COL_PARTS), ("w2", c_void_p * MAX_COL_PARTS), ("bias", c_void_p * MAX_COL_PARTS),
+                ("rowscale", c_void_p * MAX_COL_PARTS), ("w2_scale", c_float * MAX_COL_PARTS),
+                ("w_table", ctypes.c_int32 * MAX_COL_PARTS), ("w2_table", ctypes.c_int32 * MAX_COL_PARTS),
+                ("act", ctypes.c_int32 * MAX_COL_PARTS)]
+
+
 class ForestFitState(ctypes.Structure):
     """``mlqem_forest_fit_state``: the inputs and the workspace of one chunk of trees of a forest fit."""
 
@@ -80,6 +95,7 @@ SIGNATURES = {
     "mlqem_linear_bf16_f32": (_I, [_P, _L, _P, _I, _P, _P, _L, _L, _I, _I, _I, _P]),
     "mlqem_linear_wgrad_bf16_f32": (_I, [_P, _L, _P, _L, _P, _P, _L, _I, _I, _I, _P, _S, _P]),
     "mlqem_linear_parts_f32": (_I, [_P, _P, _P, _I, _P, _P, _P, _L, _P, _L, _F, _P, _P]),
+    "mlqem_linear_fanout_tables_f32": (_I, [_P, _L, _P, _F, _U, _P, _P]),
     "mlqem_linear_wgrad_workspace_bytes": (_S, [_I, _I]),
     "mlqem_linear_wgrad_f32": (_I, [_P, _L, _P, _L, _P, _P, _L, _I, _I, _I, _P, _S, _P, _P]),
     "mlqem_linear_wgrad_parts_f32": (_I, [_P, _P, _L, _P, _P, _L, _I, _I, _P, _S, _P, _P]),

@@ -429,6 +429,11 @@ _POOLED_GRAD = os.environ.get("MLQEM_POOLED_GRAD", "1") != "0"
 # ... for batches of at least this many nodes: below, a step is a chain of launches of a few microseconds each and the computed form
 # has one more of them per branch than the written one (the reference's 32 four-qubit circuits per step: 0.222 -> 0.244 ms captured)
 _POOLED_GRAD_MIN_NODES = 1 << 16
+# MLQEM_TABLE_GCN=0 / MLQEM_TABLE_CHEB=0: a Family A first layer aggregates its projection in every step even where the batch's rows
+# come with the arena's table of the aggregated INPUT (A^ x / L^ x, data/arena.py first_layer_table) (A/B, one switch per table).
+# Default: conv1 and the inner hop of cheb_conv1 are projections of table rows (_FamilyAGraph).
+_TABLE_GCN = os.environ.get("MLQEM_TABLE_GCN", "1") != "0"
+_TABLE_CHEB = os.environ.get("MLQEM_TABLE_CHEB", "1") != "0"
 
 _PARTS_MAX_COLS = 64   # mlqem_linear_parts_f32 keeps the weight fragments of I <= 64 concatenated columns in registers
 
@@ -520,9 +525,10 @@ def _x_gate(sv):     # gx takes the mask of the layer below when that layer defe
     return dict(gate=sv.x, gate_scale=sv.x_gate_scale) if sv.x_gate_scale is not None else dict(gate=None, gate_scale=1.0)
 
 
-def _cheb_forward(x, ws, bias, struct, relu, drop_p, seed, *, defer_mask, x_gate_scale, pre=None, pool=None):
+def _cheb_forward(x, ws, bias, struct, relu, drop_p, seed, *, defer_mask, x_gate_scale, pre=None, pool=None, b1_ready=False):
     """``_ChebLayer`` (K = 2, 3) -> (y, _ChebSaved).  pre: the projections c_k, already produced by a GEMM shared with other layers
-    that read the same x; pool: the pooled means of y from the launch that writes y (ops.csr_aggregate)."""
+    that read the same x; pool: the pooled means of y from the launch that writes y (ops.csr_aggregate).  b1_ready (K = 3):
+    pre is (c_0 - c_2 + b, b_1) -- the inner hop came out of the GEMM as x W_1^T + (L^ x) (2 W_2)^T, nothing is left to aggregate for it."""
     s, k = struct, len(ws)
     x = _padded_rows(ops.rowmajor(x))
     ws = [w.contiguous() for w in ws]
@@ -530,7 +536,7 @@ def _cheb_forward(x, ws, bias, struct, relu, drop_p, seed, *, defer_mask, x_gate
     c = list(pre) if pre is not None else _fan_out(x, ws, [bias] + [None] * (k - 1), w_minus)
     lap = dict(ell=s.in_ell, cscale=s.cheb_dinv, rscale=s.derived("cheb_neg"))
     act = dict(relu=relu, drop_p=drop_p, seed=seed)
-    if k == 2:
+    if k == 2 or b1_ready:
         y = ops.csr_aggregate(c[1], s.in_ptr, s.in_src, z=c[0], beta=1.0, out=c[0], pool=pool, **lap, **act)
     else:
         ops.csr_aggregate(c[2], s.in_ptr, s.in_src, alpha=2.0, z=c[1], beta=1.0, out=c[1], **lap)
@@ -539,8 +545,9 @@ def _cheb_forward(x, ws, bias, struct, relu, drop_p, seed, *, defer_mask, x_gate
     return y, _ChebSaved(x, mask, ws, s, k, drop_p, bias is not None, ws[0].shape[0], x_gate_scale)
 
 
-def _cheb_grad_blocks(sv, g):
-    """[g, g_b1, (K = 3:) g_c2]: the gradient at y with the layer's mask applied, and the transposed aggregations of it."""
+def _cheb_grad_blocks(sv, g, tail=True):
+    """[g, g_b1, (K = 3:) g_c2]: the gradient at y with the layer's mask applied, and the transposed aggregations of it.
+    ``tail=False``: without g_c2 (its weight gradient is taken against L^ x instead: 2 g_b1^T (L^ x))."""
     s = sv.struct
     lap_t = dict(ell=s.out_ell, cscale=s.derived("cheb_neg"), rscale=s.cheb_dinv)
     if isinstance(g, ops.PooledGrad) and sv.y is None:      # the pooled gradient, computed inside its first aggregation
@@ -549,7 +556,7 @@ def _cheb_grad_blocks(sv, g):
     else:
         g = _padded_rows(_mask_grad(g, sv.y, sv.drop_p))
         gs = [g, ops.csr_aggregate(g, s.out_ptr, s.out_dst, **lap_t)]
-    if sv.k == 3:
+    if sv.k == 3 and tail:
         gs.append(ops.csr_aggregate(gs[1], s.out_ptr, s.out_dst, alpha=2.0, **lap_t))
     return gs
 
@@ -1157,7 +1164,7 @@ class _FamilyAGraph(Function):
     order (1e-5 parity tests cover it); the width-1 kernels this removes ran at 20-35 % of the HBM peak and took 29 % of the step."""
 
     @staticmethod
-    def forward(ctx, x, struct: GraphStructure, p1, p2, seed, *prm):
+    def forward(ctx, x, struct: GraphStructure, p1, p2, seed, tables, *prm):
         (g1w, g1b, g2w, g2b, g3w, g3b, c1w0, c1w1, c1w2, c1b, c2w0, c2w1, c2b, s1l, s1b, s1r, s2l, s2b, s2r) = prm
         k1, k2 = 1.0 / (1.0 - p1), 1.0 / (1.0 - p2)
         gptr, nb, n = struct.graph_ptr, struct.num_graphs, struct.num_nodes
@@ -1175,7 +1182,26 @@ class _FamilyAGraph(Function):
         # backward ONE weight-gradient pass over x serves all seven gradient blocks (see backward).
         fuse = ctx.fuse = x.shape[1] <= _PARTS_MAX_COLS and 6 * ((g1w.shape[0] + 3) // 4 * 4) <= 96
         pre_g = pre_c = pre_s = None
-        if fuse:
+        # Rows of an arena come with the arena's tables of A^ x and L^ x (constants of the dataset): A^ (x W^T) = (A^ x) W^T makes conv1
+        # a projection of table rows with its bias / ReLU / dropout epilogue, and the inner Clenshaw hop of cheb_conv1 is
+        # b_1 = x W_1^T + (L^ x)(2 W_2)^T -- neither is aggregated, forward or backward (their weight gradients are taken against
+        # the tables).  ``tables``: (A^ x rows, L^ x rows), each None where there is no table (family_a_graph).
+        tab_g, tab_c = tables if (fuse and 16 < x.shape[1] <= 24) else (None, None)
+        ctx.tables = (tab_g, tab_c)
+        if tab_g is not None or tab_c is not None:
+            xr = ops.rowmajor(x)
+            n_, o_ = xr.shape[0], g1w.shape[0]
+            tabs = [xr.base] + [t.base for t in (tab_g, tab_c) if t is not None]
+            ig, ic = (1 if tab_g is not None else None), (len(tabs) - 1 if tab_c is not None else None)
+            wg, w0, w1, w2, wl, wr = [w.contiguous() for w in (g1w, c1w0, c1w1, c1w2, s1l, s1r)]
+            blk = lambda **kw: dict(out=ops.padded_empty(n_, o_, x.device), **kw)
+            spec = [blk(table=ig, w=wg, bias=g1b, act=True) if ig is not None else blk(table=0, w=wg, rowscale=struct.gcn_dinv),
+                    blk(table=0, w=w0, w_minus=w2, bias=c1b)]
+            spec += [blk(table=0, w=w1, table2=ic, w2=w2, scale2=2.0)] if ic is not None else [blk(table=0, w=w1), blk(table=0, w=w2)]
+            spec += [blk(table=0, w=wl), blk(table=0, w=wr, bias=s1b)]
+            blocks = ops.linear_fanout_tables(tabs, xr.rows, n_, spec, drop_p=p1 if ig is not None else 0.0, seed=seed + 1)
+            pre_g, pre_c, pre_s = blocks[0], blocks[1:-2], blocks[-2:]
+        elif fuse:
             xr = _padded_rows(ops.rowmajor(x))
             blocks = [ops.padded_empty(xr.shape[0], g1w.shape[0], x.device) for _ in range(6)]
             ws6 = [w.contiguous() for w in (g1w, c1w0, c1w1, c1w2, s1l, s1r)]
@@ -1185,7 +1211,10 @@ class _FamilyAGraph(Function):
         for st in side:
             st.wait_stream(main)
         # every hidden layer defers its mask: conv2 gates conv1's gradient, the pools' backward those of the last hidden activations
-        h, g1 = _gcn_forward(x, g1w, g1b, struct, True, p1, seed + 1, defer_mask=True, x_gate_scale=None, pre=pre_g)
+        if tab_g is not None:       # conv1 is done: pre_g IS its activation
+            h, g1 = pre_g, _GCNSaved(ops.rowmajor(x), g1w, None, struct, p1, None)
+        else:
+            h, g1 = _gcn_forward(x, g1w, g1b, struct, True, p1, seed + 1, defer_mask=True, x_gate_scale=None, pre=pre_g)
         # the pooled means of each branch's last hidden activation come out of the aggregation launch that writes it
         # (mlqem_csr_aggregate_pool_f32: the activation is not read a second time)
         # ... and since the backward reads that activation ONLY as the ReLU / dropout gate of the pool's gradient, the launch leaves
@@ -1196,7 +1225,7 @@ class _FamilyAGraph(Function):
         with torch.cuda.stream(side[0]):
             pc = dict(graph_ptr=gptr, num_graphs=nb, weights=tc, mean=True, wmean=True, bits=True, store=False)
             hc, c1 = _cheb_forward(x, (c1w0, c1w1, c1w2), c1b, struct, True, p2, seed + 3, defer_mask=True, x_gate_scale=None,
-                                   pre=pre_c, pool=pc)
+                                   pre=pre_c, pool=pc, b1_ready=tab_c is not None)
             mc, wc = ops.pooled_means(hc, pc)
         with torch.cuda.stream(side[1]):
             ps = dict(graph_ptr=gptr, num_graphs=nb, weights=ts, mean=True, wmean=True, bits=True, store=False)
@@ -1207,8 +1236,9 @@ class _FamilyAGraph(Function):
             for t in ts_:
                 t.record_stream(main)
         if fuse:
-            for t in blocks[1:]:          # made on the compute stream, consumed by the side streams
-                t.record_stream(side[0] if t is not blocks[4] and t is not blocks[5] else side[1])
+            for branch, st in ((pre_c, side[0]), (pre_s, side[1])):          # made on the compute stream, consumed by the side streams
+                for t in branch:
+                    t.record_stream(st)
         # the three folded last convs: [wmean_g . W3 + b3 | mean_c . W0 + wmean_c . W1 + b | wmean_s . Wl + bl + mean_s . Wr]
         ctx.head = ([(wg, g3w, 0), (mc, c2w0, 1), (wc, c2w1, 1), (ws, s2l, 2), (ms, s2r, 2)], [g3b, c2b, s2b])
         out = ops.pooled_head(*ctx.head)
@@ -1248,16 +1278,30 @@ class _FamilyAGraph(Function):
         # conv1's bias gradient is the column sum of the gradient conv2's backward just wrote: taken there (by the fused form, else
         # None), the first-layer weight-gradient pass below reads six blocks instead of seven
         g2w, g2b, g1b_cs = r.w, r.b, r.x_colsum
-        if fuse:
+        tab_g, tab_c = ctx.tables
+        o = g1.w.shape[0]
+        new_gw = lambda: torch.empty((o, g1.x.shape[1]), dtype=torch.float32, device=g.device)
+        if tab_g is not None:
+            # conv1 = a projection of the A^ x rows: its weight gradient is gx^T (A^ x) with the gated gradient conv2's backward wrote,
+            # nothing is aggregated; enqueued here, it runs while the other branches are still in their aggregations
+            bg, g1w = [], new_gw()
+            g1b = None if g1b_cs is not None else torch.empty(o, dtype=torch.float32, device=g.device)
+            ops.linear_wgrad(_padded_rows(ops.rowmajor(r.x)), tab_g, g1w, g1b)
+        elif fuse:
             gh, t = _gcn_grad_blocks(g1, r.x)
             bg = [gh, _padded_rows(t)]
+            if g1b_cs is not None:
+                bg = bg[:1]
         else:
             r = _gcn_backward(g1, r.x, False, True, True)
             g1w, g1b = r.w, r.b
         with torch.cuda.stream(side[0]):
             t = pooled_grad(gcm, gcw, "cheb", hc, k2, bc_)
             if fuse:
-                bc = _cheb_grad_blocks(c1, t)       # [g, g_b1, g_c2]
+                bc = _cheb_grad_blocks(c1, t, tail=tab_c is None)       # [g, g_b1, g_c2]; with the L^ x table: [g, g_b1]
+                if tab_c is not None:                                   # ... and g_c2^T x = 2 g_b1^T (L^ x)
+                    gwl = new_gw()
+                    ops.linear_wgrad(bc[1], tab_c, gwl, None)
             else:
                 r = _cheb_backward(c1, t, False)
                 c1b, (c1w0, c1w1, c1w2) = r.b, r.ws
@@ -1275,20 +1319,33 @@ class _FamilyAGraph(Function):
             # the ones column of the pass yields the three bias gradients
             for blk in bc + bs:
                 blk.record_stream(main)
-            blks = ([bg[0]] if g1b_cs is not None else bg) + bc + bs
-            k, o = len(blks) - 5, g1.w.shape[0]             # k: index of the first Cheb block
-            gwn, gbn = _wgrad_blocks(blks, g1.x, o)
-            g1w, g1b = gwn[0], (g1b_cs[:o] if g1b_cs is not None else gbn[1])
-            c1w0, c1w1, c1w2, c1b = gwn[k], gwn[k + 1], gwn[k + 2] - gwn[k], gbn[k]
-            s1l, s1r, s1b = gwn[k + 3], gwn[k + 4], gbn[k + 4]
+            k, j = len(bg), len(bg) + len(bc)               # index of the first Cheb / SAGE block
+            gwn, gbn = _wgrad_blocks(bg + bc + bs, g1.x, o)
+            if tab_g is None:
+                g1w, g1b = gwn[0], (gbn[1] if g1b_cs is None else None)
+            if g1b_cs is not None:
+                g1b = g1b_cs[:o]
+            c1w0, c1w1, c1b = gwn[k], gwn[k + 1], gbn[k]
+            if tab_c is None:
+                c1w2 = gwn[k + 2] - gwn[k]
+            else:
+                gwl.record_stream(main)
+                c1w2 = torch.sub(gwl.mul_(2.0), gwn[k])
+            s1l, s1r, s1b = gwn[j], gwn[j + 1], gbn[j + 1]
         for t in (gcm, gcw, gsm, gsw):        # made on the compute stream, consumed by the side streams
             t.record_stream(side[0] if t is gcm or t is gcw else side[1])
         for t in (() if fuse else (c1b, c1w0, c1w1, c1w2, s1l, s1b, s1r)):
             t.record_stream(main)
-        return (None, None, None, None, None, g1w, g1b, g2w, g2b, g3wg, g3bg, c1w0, c1w1, c1w2, c1b, c2w0g, c2w1g, c2bg,
+        return (None, None, None, None, None, None, g1w, g1b, g2w, g2b, g3wg, g3bg, c1w0, c1w1, c1w2, c1b, c2w0g, c2w1g, c2bg,
                 s1l, s1b, s1r, s2lg, s2bg, s2rg)
 
 
 def family_a_graph(x, struct, p1, p2, seed, params):
-    """One-node form of Family A's three conv branches + pools; ``params`` as listed in ``_FamilyAGraph``."""
-    return _FamilyAGraph.apply(x, struct, p1, p2, seed, *params)
+    """One-node form of Family A's three conv branches + pools; ``params`` as listed in ``_FamilyAGraph``.  Rows of an arena
+    (``ops.RowsOf``) bring the arena's first-layer tables along: a call that trains builds them on first use, one that only predicts
+    (no gradient wanted) takes them if they exist -- nothing is built for an arena that never trains this model."""
+    tables = (None, None)
+    if isinstance(x, ops.RowsOf) and 16 < x.shape[1] <= 24 and params[0].shape[0] <= 16:      # what the fused first layer takes
+        build = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        tables = (x.sibling("gcn", build) if _TABLE_GCN else None, x.sibling("cheb", build) if _TABLE_CHEB else None)
+    return _FamilyAGraph.apply(x, struct, p1, p2, seed, tables, *params)

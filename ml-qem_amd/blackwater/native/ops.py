@@ -49,13 +49,21 @@ class RowsOf:
     requires_grad = False
     is_cuda = True
 
-    def __init__(self, base: torch.Tensor, rows: torch.Tensor):
+    def __init__(self, base: torch.Tensor, rows: torch.Tensor, siblings=None):
         if (not rows.is_cuda or rows.dtype != torch.int32 or rows.dim() != 1 or (rows.numel() > 1 and rows.stride(0) != 1)):
             raise ValueError("RowsOf: rows must be a contiguous 1-D int32 cuda tensor")
         _mat(base, "base")
         self.base, self.rows = base, rows
         self.shape = (int(rows.shape[0]), int(base.shape[1]))
         self.device, self.dtype = base.device, base.dtype
+        # siblings(kind, build) -> another [M, c] matrix in ``base``'s layout that ``rows`` indexes just the same, or None: what the
+        # owner of ``base`` derives from it once (GraphArena.first_layer_table: a graph operator applied to the node features)
+        self._siblings = siblings
+
+    def sibling(self, kind: str, build: bool = True):
+        """Rows ``rows`` of the owner's table ``kind`` as a ``RowsOf``; None when there is none (``build=False``: none YET)."""
+        t = None if self._siblings is None else self._siblings(kind, build)
+        return None if t is None else RowsOf(t, self.rows)
 
     def dim(self):
         return 2
@@ -597,6 +605,59 @@ def linear_parts(xs, ws, ys, *, w_minus=None, biases=None, rowscales=None, trans
                                               *_gate(gate, n, ys[0].shape[1], True), float(gate_scale), x_rows, _stream())
     _lib.check(code, "mlqem_linear_parts_f32")
     return ys
+
+
+def linear_fanout_tables(tables, rows, n, blocks, *, drop_p=0.0, seed=0):
+    """One launch for output blocks projected from up to three padded tables that share the row map ``rows`` (int32 [n] or None):
+    every entry of ``blocks`` is a dict with ``out`` (a ``padded_empty`` [n, O] buffer), ``table`` and ``w`` ([O, I]), and optionally
+    ``w_minus`` (subtracted from ``w``), ``table2`` / ``w2`` / ``scale2`` (a second term scale2 * T[table2] w2^T), ``bias``, ``rowscale``
+    and ``act`` (ReLU + dropout ``drop_p`` with the aggregation epilogue's mask for ``seed``): mlqem_linear_fanout_tables_f32."""
+    import ctypes as _ct
+
+    d = _lib.FanoutTables()
+    i, o = tables[0].shape[1], blocks[0]["out"].shape[1]
+    if not 1 <= len(tables) <= _lib.MAX_FANOUT_TABLES or not 1 <= len(blocks) <= _lib.MAX_COL_PARTS:
+        raise ValueError(f"linear_fanout_tables: 1..{_lib.MAX_FANOUT_TABLES} tables and 1..{_lib.MAX_COL_PARTS} blocks")
+    d.n_tables, d.n_blocks, d.cols, d.out_cols = len(tables), len(blocks), i, o
+    c4 = (i + 3) // 4 * 4
+    for j, t in enumerate(tables):
+        _mat(t, f"tables[{j}]")
+        ld = int(t.stride(0))                   # a one-row table still has to own its padding
+        if t.shape[1] != i or ld < c4 or ld % 4 or t.data_ptr() % 16:
+            raise ValueError(f"tables[{j}]: needs [M, {i}] in the padded row layout, got {tuple(t.shape)} with stride {ld}")
+        if rows is None and t.shape[0] < n:
+            raise ValueError(f"tables[{j}]: {t.shape[0]} rows for {n} outputs")
+        d.table[j], d.ldt[j] = t.data_ptr(), ld
+    if rows is not None:
+        _vec(rows, "rows", n, torch.int32)
+
+    def weight(w, name):
+        if w is None:
+            return None
+        if not w.is_cuda or w.dtype != torch.float32 or tuple(w.shape) != (o, i) or not w.is_contiguous():
+            raise ValueError(f"linear_fanout_tables: {name} must be a contiguous fp32 cuda tensor of shape {(o, i)}")
+        return w.data_ptr()
+
+    for k, b in enumerate(blocks):
+        out = b["out"]
+        _mat(out, f"blocks[{k}].out")
+        ld = int(out.stride(0))
+        if tuple(out.shape) != (n, o) or ld < (o + 3) // 4 * 4 or ld % 4 or out.data_ptr() % 16:
+            raise ValueError(f"blocks[{k}].out: needs a padded [{n}, {o}] buffer (ops.padded_empty)")
+        _vec(b.get("bias"), "bias", o)
+        _vec(b.get("rowscale"), "rowscale", n)
+        for key in ("table", "table2"):
+            if b.get(key) is not None and not 0 <= int(b[key]) < len(tables):
+                raise ValueError(f"blocks[{k}].{key}: no such table")
+        d.y[k], d.ldy[k] = out.data_ptr(), ld
+        d.w[k], d.w_minus[k], d.w_table[k] = weight(b["w"], "w"), weight(b.get("w_minus"), "w_minus"), int(b["table"])
+        d.w2[k] = weight(b.get("w2"), "w2")
+        d.w2_table[k], d.w2_scale[k] = int(b.get("table2") or 0), float(b.get("scale2", 1.0))
+        d.bias[k], d.rowscale[k], d.act[k] = _p(b.get("bias")), _p(b.get("rowscale")), 1 if b.get("act") else 0
+    code = _lib.load().mlqem_linear_fanout_tables_f32(_ct.addressof(d), n, _p(rows), float(drop_p), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                      _p(_seed_counter) if drop_p > 0 else None, _stream())
+    _lib.check(code, "mlqem_linear_fanout_tables_f32")
+    return [b["out"] for b in blocks]
 
 
 _wgrad_ws = {}   # (device, stream, bytes) -> partial-sum workspace: per stream, so concurrent streams never share one

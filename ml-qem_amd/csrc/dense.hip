@@ -785,6 +785,142 @@ __global__ __launch_bounds__(kBlock) void linear_fanout_lds_kernel(const PartsAr
   }
 }
 
+// The same fan-out over up to THREE input tables that share ONE row map (mlqem_linear_fanout_tables_f32): the node features x and
+// the per-arena products of a graph operator with them (A^ x for GCNConv, L^ x for ChebConv's inner Clenshaw hop).  Those products
+// are constants of the dataset, so a first layer that would aggregate its projection reads the aggregated INPUT instead:
+//     block k = act((T_a W_a^T  [+ T_b (s W_b)^T])  + bias) * rowscale          one or two terms, each from its own table
+// A term is one set of weight fragments in LDS (the scale s folded in where they are staged: a power of two is exact); a block with
+// one term runs the MFMA steps of linear_fanout_lds_kernel<2, true> in its order (bit-identical results).  ACT blocks apply ReLU
+// and inverted dropout with the mask the aggregation epilogue draws (dropout_keep over the lane's four columns, key row * yc +
+// column, seed + device step counter).  17-24 input columns (the K24 split); every load of a tile before its first store, the next
+// tile's rows of ALL tables prefetched, as above.
+constexpr int kFanTables = MLQEM_FANOUT_MAX_TABLES, kFanTerms = kMaxParts;
+
+struct FanTablesArgs {
+  const float* tab[kFanTables]; int64_t ldt[kFanTables]; int xc;
+  float* yp[kMaxParts]; int64_t ldy[kMaxParts]; int yn, yw, yc;
+  // term slots: slot k < yn is block k's first term, bslot[k] (or -1) its second
+  const float* tw[kFanTerms]; const float* twm[kFanTerms]; float tscale[kFanTerms]; int ttab[kFanTerms]; int nterms;
+  int bslot[kMaxParts];
+  const float* bk[kMaxParts]; const float* rsk[kMaxParts]; int actk[kMaxParts];
+  int64_t N; const int32_t* xrows;
+  float drop_p; uint64_t seed; const uint64_t* seed_counter;
+};
+
+template <int NT>
+__global__ __launch_bounds__(kBlock) void linear_fanout_tables_kernel(const FanTablesArgs a) {
+  __shared__ float4 s_w[kFanTerms][2][kWave];
+  __shared__ float s_b[kMaxParts][16];
+  const int tid = threadIdx.x;
+  for (int idx = tid; idx < a.nterms * 2 * kWave; idx += kBlock) {
+    const int term = idx / (2 * kWave), g = (idx / kWave) % 2, l = idx % kWave;
+    const int o = l & 15, lq = l >> 4;
+    float v[4];
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4) {
+      const int k = g == 1 ? (s4 < 2 ? 16 + 2 * lq + s4 : a.xc) : 4 * lq + s4;
+      float w = 0.f;
+      if (o < a.yc && k < a.xc) {
+        w = a.tw[term][(int64_t)o * a.xc + k];
+        if (a.twm[term]) w -= a.twm[term][(int64_t)o * a.xc + k];
+        w *= a.tscale[term];
+      }
+      v[s4] = w;
+    }
+    s_w[term][g][l] = make_float4(v[0], v[1], v[2], v[3]);
+  }
+  for (int idx = tid; idx < a.yn * 16; idx += kBlock) {
+    const int blk = idx >> 4, o = idx & 15;
+    s_b[blk][o] = (a.bk[blk] && o < a.yc) ? a.bk[blk][o] : 0.f;
+  }
+  __syncthreads();
+  const int lane = tid & 63;
+  const int wave = (blockIdx.x * kBlock + tid) >> 6;
+  const int n_waves = (gridDim.x * kBlock) >> 6;
+  const int lr = lane & 15, lq = lane >> 4;
+  const int live1 = min(2, max(0, a.xc - (16 + 2 * lq)));      // live columns of the lane's pair in the second k-group (the first is full: xc > 16)
+  const uint64_t seed = a.seed + (a.seed_counter ? *a.seed_counter * 0xD1B54A32D192ED03ull : 0ull);
+  const float keep_scale = 1.f / (1.f - a.drop_p);
+  const bool store_lane = 4 * lq < a.yw;
+  const int64_t n_tiles = ceil_div(a.N, 16);
+  auto load_x = [&](int64_t t, int xmap, float4 (&v0)[NT], float2 (&v1)[NT]) {
+    const int64_t r = min(t * 16 + lr, a.N - 1);
+    const int64_t xr = a.xrows ? (int64_t)xmap : r;
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+      const float* __restrict__ p = a.tab[j] + xr * a.ldt[j];
+      v0[j] = *reinterpret_cast<const float4*>(p + 4 * lq);
+      v1[j] = live1 ? *reinterpret_cast<const float2*>(p + 16 + 2 * lq) : make_float2(0.f, 0.f);
+    }
+  };
+  auto map_at = [&](int64_t t) {
+    const int64_t r = min(t * 16 + lr, a.N - 1);
+    return (a.xrows && t < n_tiles) ? a.xrows[r] : 0;
+  };
+  float4 av0[NT], an0[NT];
+  float2 av1[NT], an1[NT];
+  int xnext = map_at(wave + n_waves);
+  load_x(wave, map_at(wave), av0, av1);
+  for (int64_t t = wave; t < n_tiles; t += n_waves) {
+    const int64_t row = t * 16 + lr;
+    const bool row_ok = row < a.N;
+    float rsv[kMaxParts];
+#pragma unroll
+    for (int blk = 0; blk < kMaxParts; ++blk) rsv[blk] = (blk < a.yn && a.rsk[blk] && row_ok) ? a.rsk[blk][row] : 1.f;
+    const int xmap2 = map_at(t + 2 * n_waves);
+    load_x(t + n_waves, xnext, an0, an1);      // a tile beyond the end re-reads row N - 1 and is never used
+    xnext = xmap2;
+#pragma unroll
+    for (int j = 0; j < NT; ++j)
+      if (live1 < 2) av1[j].y = 0.f;           // padding may hold anything (NaN included): it must not reach the MFMA
+    auto steps = [&](int slot, const float4& x0, const float2& x1, f32x4 acc) {
+      const float4 w0 = s_w[slot][0][lane], w1 = s_w[slot][1][lane];
+      acc = mfma16x16x4(w0.x, x0.x, acc);
+      acc = mfma16x16x4(w0.y, x0.y, acc);
+      acc = mfma16x16x4(w0.z, x0.z, acc);
+      acc = mfma16x16x4(w0.w, x0.w, acc);
+      acc = mfma16x16x4(w1.x, x1.x, acc);
+      acc = mfma16x16x4(w1.y, x1.y, acc);
+      return acc;
+    };
+    // a term's table is workgroup-uniform: a branch per table with the operand registers named outright (a select over the register
+    // arrays becomes an indexed load, and the arrays then live in scratch memory)
+    auto term = [&](int slot, f32x4 acc) {
+      const int tb = a.ttab[slot];
+      if (NT > 2 && tb == 2) return steps(slot, av0[NT > 2 ? 2 : 0], av1[NT > 2 ? 2 : 0], acc);
+      if (NT > 1 && tb == 1) return steps(slot, av0[NT > 1 ? 1 : 0], av1[NT > 1 ? 1 : 0], acc);
+      return steps(slot, av0[0], av1[0], acc);
+    };
+#pragma unroll
+    for (int blk = 0; blk < kMaxParts; ++blk) {
+      if (blk >= a.yn) break;
+      const float rs = rsv[blk];
+      f32x4 acc = term(blk, f32x4{0.f, 0.f, 0.f, 0.f});
+      if (a.bslot[blk] >= 0) acc = term(a.bslot[blk], acc);
+      if (!row_ok || !store_lane) continue;
+      float v[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        v[r] = acc[r] + s_b[blk][4 * lq + r];
+        v[r] *= rs;                            // 1.0f where the block has no row scale: exact
+      }
+      if (a.actk[blk]) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
+        if (a.drop_p > 0.f) {
+          bool keep[4];
+          dropout_keep<4>(seed, (uint64_t)(row * a.yc + 4 * lq), a.drop_p, keep);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[r] = keep[r] ? v[r] * keep_scale : 0.f;
+        }
+      }
+      vstore_nt<4>(a.yp[blk] + row * a.ldy[blk] + 4 * lq, v);
+    }
+#pragma unroll
+    for (int j = 0; j < NT; ++j) { av0[j] = an0[j]; av1[j] = an1[j]; }
+  }
+}
+
 // Generic fallback (any I; used for I > 128): thread per (row, output); a block stages one chunk of `oc` outputs' weights
 // in LDS (blockIdx.y selects the chunk).
 template <bool TRANSPOSED>
@@ -1622,6 +1758,51 @@ extern "C" int mlqem_linear_parts_f32(const mlqem_col_parts* x, const float* con
   a.xrows = x_rows;
   a.plain_stores = y->cols > 16;
   return run_linear_parts(a, transposed, as_stream(stream));
+}
+
+extern "C" int mlqem_linear_fanout_tables_f32(const mlqem_fanout_tables* d, int64_t N, const int32_t* x_rows, float drop_p,
+                                              uint64_t seed, const uint64_t* seed_counter, mlqem_stream_t stream) {
+  begin_launches();
+  if (!d || N < 0 || drop_p < 0.f || drop_p >= 1.f) return MLQEM_ERR_BAD_ARG;
+  if (d->n_tables < 1 || d->n_tables > kFanTables || d->n_blocks < 1 || d->n_blocks > kMaxParts || d->cols < 1 || d->out_cols < 1)
+    return MLQEM_ERR_BAD_ARG;
+  if (d->cols <= 16 || d->cols > 24 || d->out_cols > 16) return MLQEM_ERR_UNSUPPORTED;      // the 16 + 8 column split, one MFMA tile per block
+  const int c4i = (d->cols + 3) / 4 * 4, c4o = (d->out_cols + 3) / 4 * 4;
+  FanTablesArgs a{};
+  for (int j = 0; j < d->n_tables; ++j) {
+    if (!d->table[j] || d->ldt[j] < c4i || d->ldt[j] % 4 || !aligned_to(d->table[j], 16)) return MLQEM_ERR_BAD_ARG;
+    a.tab[j] = static_cast<const float*>(d->table[j]); a.ldt[j] = d->ldt[j];
+  }
+  int nterms = d->n_blocks;
+  for (int k = 0; k < d->n_blocks; ++k) {
+    if (!d->y[k] || d->ldy[k] < c4o || d->ldy[k] % 4 || !aligned_to(d->y[k], 16) || !d->w[k]) return MLQEM_ERR_BAD_ARG;
+    if (d->w_table[k] < 0 || d->w_table[k] >= d->n_tables) return MLQEM_ERR_BAD_ARG;
+    a.yp[k] = static_cast<float*>(d->y[k]); a.ldy[k] = d->ldy[k];
+    a.tw[k] = d->w[k]; a.twm[k] = d->w_minus[k]; a.tscale[k] = 1.f; a.ttab[k] = d->w_table[k];
+    a.bk[k] = d->bias[k]; a.rsk[k] = d->rowscale[k]; a.actk[k] = d->act[k] ? 1 : 0;
+    a.bslot[k] = -1;
+    if (d->w2[k]) {
+      if (d->w2_table[k] < 0 || d->w2_table[k] >= d->n_tables) return MLQEM_ERR_BAD_ARG;
+      if (nterms >= kFanTerms) return MLQEM_ERR_UNSUPPORTED;
+      a.bslot[k] = nterms;
+      a.tw[nterms] = d->w2[k]; a.twm[nterms] = nullptr; a.tscale[nterms] = d->w2_scale[k]; a.ttab[nterms] = d->w2_table[k];
+      ++nterms;
+    }
+  }
+  if (N == 0) return MLQEM_OK;
+  a.nterms = nterms; a.xc = d->cols; a.yn = d->n_blocks; a.yw = c4o; a.yc = d->out_cols;
+  a.N = N; a.xrows = x_rows; a.drop_p = drop_p; a.seed = seed; a.seed_counter = drop_p > 0.f ? seed_counter : nullptr;
+  const int64_t tiles = ceil_div(N, 16);
+  hipStream_t s = as_stream(stream);
+  auto go = [&](void (*kernel)(const FanTablesArgs)) {
+    const int res = resident_of(reinterpret_cast<const void*>(kernel));
+    const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(tiles, 4), res)));      // one resident round
+    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, a);
+  };
+  if (d->n_tables == 1) go(linear_fanout_tables_kernel<1>);
+  else if (d->n_tables == 2) go(linear_fanout_tables_kernel<2>);
+  else go(linear_fanout_tables_kernel<3>);
+  return launch_status();
 }
 
 template <int OBT, bool TRANSPOSED>

@@ -1154,6 +1154,37 @@ int mlqem_forest_predict_oob_f32(const float* x, int64_t ldx, int64_t n_rows, in
  * (MLQEM_ERR_UNSUPPORTED beyond); min_samples_split >= 2, min_samples_leaf >= 1, max_depth >= 0 and non-null, aligned buffers
  * (MLQEM_ERR_BAD_ARG otherwise), all checked before a launch.  The node table is NOT validated here: ForestRegressor.fit passes it
  * through the same host validation as from_arrays before mlqem_forest_predict_f32 sees it.
+ *
+ * Feature subsets per node (max_features = m, 1 <= m <= F; an additive symbol, the ABI version is unchanged).  With m == F nothing
+ * above changes.  With m < F a node that meets no leaf condition searches a subset of the features:
+ *   1. Feature order.  The node has its own permutation pi of 0 .. F-1, a pure function of (seed, t, node, i): t the tree's index
+ *      in the WHOLE forest (tree_base + its index in the chunk), node the node's index within its tree in the numbering above (root
+ *      0, children appended level by level: the third field of a seg_i record).  All arithmetic is uint32:
+ *        mix(x):  x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16
+ *        key   =  mix(mix(mix(seed) ^ t) ^ node)
+ *        h     =  max(1, ceil(bit_length(F - 1) / 2));   mask = 2^h - 1;   D = 4^h        (F <= D <= 4 F)
+ *        E(v):    (L, R) = (v >> h, v & mask)
+ *                 for r = 0 .. 7:  (L, R) = (R, L ^ (mix(R ^ key ^ (r * 0x9e3779b9)) & mask))
+ *                 return (L << h) | R
+ *        pi(i) =  the first of E(i), E(E(i)), ... that is below F
+ *      E is a bijection of [0, D) (eight Feistel rounds; four leave pair frequencies visibly uneven at small F), so pi is a
+ *      bijection of [0, F) by cycle walking; the walk is bounded by D steps and its result clamped to F - 1.
+ *   2. Visited features.  The node visits pi(0), pi(1), ... and stops after c features, c the smallest count >= m for which a
+ *      visited feature has a candidate (cand_pos >= 0 for this tree, feature and segment).  If no feature has one the node is a leaf.
+ *   3. Winner.  Among the visited features the highest score wins; on equal scores the lowest feature index, then the lowest
+ *      position.  The threshold and everything downstream are unchanged.
+ * Deviation from scikit-learn: it keeps drawing while every visited feature is CONSTANT in the node; here a feature counts only
+ * once it has a CANDIDATE.  The two differ only with min_samples_leaf > 1, where scikit-learn may stop at a feature that varies but
+ * has no admissible split and this rule goes on drawing.  scikit-learn's random stream is not reproduced: the subsets, like the
+ * bags, are the project's own.
+ * mlqem_forest_fit_select_subset(state, level, max_features, seed, tree_base, stream) takes the place of mlqem_forest_fit_select in
+ * the level's sequence; tree_base is the forest index of the chunk's first tree.  One workgroup per tree, one thread per segment, the
+ * same leaf tests, threshold, node record and numbering scans as _select (one body serves both); the visit loop is bounded by F and
+ * the cycle walk by D, every feature index is clamped before it addresses cand_score / cand_pos, the loads are unconditional and
+ * masked (every lane runs to its wave's largest count), no atomics, no workgroup waits for another.  max_features >= F gives the
+ * bits of mlqem_forest_fit_select (it launches that kernel).  The checks of the other entries, and max_features >= 1, tree_base
+ * >= 0, level >= 0 (MLQEM_ERR_BAD_ARG), all before a launch.  _search and _partition still walk all F lists: in this layout a per-node
+ * subset cannot skip a list, so max_features buys variety between the trees, not time.
  * ---------------------------------------------------------------------------------------------------- */
 typedef struct mlqem_forest_fit_state {
   const float* x; int64_t ldx; const double* y; const int32_t* counts; const int32_t* order;
@@ -1167,6 +1198,8 @@ int mlqem_forest_fit_init(const mlqem_forest_fit_state* state, mlqem_stream_t st
 int mlqem_forest_fit_stats(const mlqem_forest_fit_state* state, int level, mlqem_stream_t stream);
 int mlqem_forest_fit_search(const mlqem_forest_fit_state* state, int level, mlqem_stream_t stream);
 int mlqem_forest_fit_select(const mlqem_forest_fit_state* state, int level, mlqem_stream_t stream);
+int mlqem_forest_fit_select_subset(const mlqem_forest_fit_state* state, int level, int max_features, uint32_t seed,
+                                   int64_t tree_base, mlqem_stream_t stream);
 int mlqem_forest_fit_partition(const mlqem_forest_fit_state* state, int level, mlqem_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------

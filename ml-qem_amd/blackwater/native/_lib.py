@@ -215,6 +215,7 @@ SIGNATURES = {
     "mlqem_forest_fit_stats": (_I, [_P, _I, _P]),
     "mlqem_forest_fit_search": (_I, [_P, _I, _P]),
     "mlqem_forest_fit_select": (_I, [_P, _I, _P]),
+    "mlqem_forest_fit_select_subset": (_I, [_P, _I, _I, ctypes.c_uint32, _L, _P]),
     "mlqem_forest_fit_partition": (_I, [_P, _I, _P]),
     "mlqem_linreg_moments_workspace_bytes": (_S, [_L, _I, _I]),
     "mlqem_linreg_moments_f32": (_I, [_P, _L, _P, _L, _L, _I, _I, _P, _I, _P, _S, _P]),

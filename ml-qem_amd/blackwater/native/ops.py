@@ -2225,8 +2225,9 @@ def forest_fit_tree_bytes(n, f, k):
     return int(_lib.load().mlqem_forest_fit_tree_bytes(int(n), int(f), int(k)))
 
 
-def _forest_fit_run(lib, stream, x, y, counts, order, min_samples_split, min_samples_leaf, max_depth, tc, profile=None):
-    """The host loop of ``forest_fit`` for tensors that are already checked; every buffer is allocated on ``x.device``."""
+def _forest_fit_run(lib, stream, x, y, counts, order, min_samples_split, min_samples_leaf, max_depth, tc, profile=None, subset=None):
+    """The host loop of ``forest_fit`` for tensors that are already checked; every buffer is allocated on ``x.device``.  ``subset``:
+    None, or (max_features, seed) for ``mlqem_forest_fit_select_subset`` in the place of ``mlqem_forest_fit_select``."""
     n, f = int(x.shape[0]), int(x.shape[1])
     k, t_all, dev = int(y.shape[1]), int(counts.shape[0]), x.device
     nn = 2 * n - 1
@@ -2258,8 +2259,12 @@ def _forest_fit_run(lib, stream, x, y, counts, order, min_samples_split, min_sam
         launch("init", lib.mlqem_forest_fit_init, ref, stream)
         flat_level = buf["level"].view(-1)
         for d in range(max_levels):
-            for name, fn in steps[:3]:
+            for name, fn in steps[:2]:
                 launch(name, fn, ref, d, stream)
+            if subset is None:
+                launch("select", steps[2][1], ref, d, stream)
+            else:   # the key of a node's feature order holds the tree's index in the whole forest: t0 + its index in the chunk
+                launch("select", lib.mlqem_forest_fit_select_subset, ref, d, subset[0], subset[1], t0, stream)
             nxt = (d + 1) & 1
             live = flat_level[nxt * c * 4:(nxt + 1) * c * 4].cpu().view(c, 4)   # the level's one read: live segments, nodes so far
             levels = max(levels, d + 1)
@@ -2283,7 +2288,8 @@ def _forest_fit_run(lib, stream, x, y, counts, order, min_samples_split, min_sam
                 n_node_samples=node_i[:, 3].astype(np.int64), levels=levels, trees_per_chunk=tc)
 
 
-def forest_fit(x, y, counts, *, min_samples_split=2, min_samples_leaf=1, max_depth=None, workspace_bytes=2 << 30, profile=None):
+def forest_fit(x, y, counts, *, min_samples_split=2, min_samples_leaf=1, max_depth=None, workspace_bytes=2 << 30, profile=None,
+               max_features=None, seed=0):
     """Grows a regression forest on the device (mlqem_forest_fit_*; include/mlqem_hip.h states the rule): one exact CART tree with
     squared error per row of ``counts``.  ``x``: float32 [n, F] (row stride >= F), ``y``: contiguous float64 [n, K], ``counts``:
     contiguous int32 [T, n] -- how often each row is in each tree's bag -- all on one device; the VALUES (finite x and y, counts
@@ -2293,6 +2299,10 @@ def forest_fit(x, y, counts, *, min_samples_split=2, min_samples_leaf=1, max_dep
     level), ``feature`` (-2 for a leaf), ``threshold`` float64, ``left`` / ``right`` (-1 for a leaf), ``value`` float64 [N, K],
     ``n_node_samples`` (distinct in-bag rows); plus ``levels`` and ``trees_per_chunk``.  The node table comes straight from the
     kernels: validate it (``ForestRegressor.from_arrays``) before it is scored.
+
+    ``max_features``: None or an int in [1, F].  None or F searches every feature at every node (``mlqem_forest_fit_select``, as
+    ever); a smaller one gives every node its own feature subset, a pure function of (``seed`` & 0xFFFFFFFF, tree, node)
+    (``mlqem_forest_fit_select_subset``; the header states the rule).  ``seed`` is read for nothing else.
 
     Trees are grown in chunks sized so that a chunk's workspace fits ``workspace_bytes``; the forest does not depend on the chunking,
     bit for bit.  One stable argsort per column is shared by all trees.  Every level costs four launches and one small read of the
@@ -2312,6 +2322,10 @@ def forest_fit(x, y, counts, *, min_samples_split=2, min_samples_leaf=1, max_dep
                          f"{FOREST_MAX_OUTPUTS} and a tree, got n {n}, F {f}, K {k}, T {t}")
     if min_samples_split < 2 or min_samples_leaf < 1 or (max_depth is not None and max_depth < 0):
         raise ValueError("forest_fit: want min_samples_split >= 2, min_samples_leaf >= 1 and max_depth >= 0 (or None)")
+    if max_features is not None and (isinstance(max_features, bool) or not isinstance(max_features, (int, np.integer))
+                                     or not 1 <= max_features <= f):
+        raise ValueError(f"forest_fit: max_features must be None or an int in 1..{f}, got {max_features!r}")
+    subset = None if max_features is None or int(max_features) == f else (int(max_features), int(seed) & 0xFFFFFFFF)
     lib = _lib.load()
     per_tree = int(lib.mlqem_forest_fit_tree_bytes(n, f, k))
     tc = min(t, int(workspace_bytes) // per_tree, (2 ** 31 - 1) // f)
@@ -2320,7 +2334,7 @@ def forest_fit(x, y, counts, *, min_samples_split=2, min_samples_leaf=1, max_dep
                          f"workspace_bytes is {int(workspace_bytes)}")
     order = torch.argsort(x.t(), dim=1, stable=True).to(torch.int32).contiguous()   # [F, n], once per fit
     depth = 2 ** 31 - 1 if max_depth is None else min(int(max_depth), 2 ** 31 - 1)
-    return _forest_fit_run(lib, _stream(), x, y, counts, order, min_samples_split, min_samples_leaf, depth, tc, profile)
+    return _forest_fit_run(lib, _stream(), x, y, counts, order, min_samples_split, min_samples_leaf, depth, tc, profile, subset)
 
 
 LINREG_MAX_FEATURES = 512   # F and K the least-squares kernels serve

@@ -75,6 +75,27 @@ OOB_WARNING = ("Some inputs do not have OOB scores. This probably means too few 
                "estimates.")   # scikit-learn's wording
 
 
+def resolve_max_features(max_features, n_features: int) -> int:
+    """scikit-learn's reading of ``max_features`` for ``n_features`` columns: an int is itself (1..F), a float in (0, 1] is
+    ``max(1, int(f * F))``, "sqrt" / "log2" are ``max(1, int(sqrt(F)))`` / ``max(1, int(log2(F)))``, None is F.  ``ValueError`` otherwise."""
+    f = int(n_features)
+    m = None
+    if max_features is None:
+        m = f
+    elif isinstance(max_features, bool):
+        pass
+    elif isinstance(max_features, (int, np.integer)):
+        m = int(max_features) if 1 <= max_features <= f else None
+    elif isinstance(max_features, (float, np.floating)):
+        m = max(1, int(max_features * f)) if 0.0 < max_features <= 1.0 else None
+    elif isinstance(max_features, str) and max_features in ("sqrt", "log2"):
+        m = max(1, int(np.sqrt(f) if max_features == "sqrt" else np.log2(f)))
+    if m is None:
+        raise ValueError(f"forest fit: max_features must be an int in 1..{f}, a float in (0, 1], \"sqrt\", \"log2\" or None, got "
+                         f"{max_features!r}")
+    return m
+
+
 def _pack(tree_ptr, feature, threshold, left, right, n_features):
     """Validates the forest and returns (nodes int32 [N, 4], tree_ptr int64, max_depth).  Works on whole levels of all trees at once."""
     tree_ptr = np.asarray(tree_ptr)
@@ -193,15 +214,16 @@ class ForestRegressor(torch.nn.Module):
     @classmethod
     def fit(cls, x: torch.Tensor, y: torch.Tensor, *, n_estimators: int = 100, bootstrap: bool = True, max_depth=None,
             min_samples_split: int = 2, min_samples_leaf: int = 1, seed: int = 0, sample_counts=None,
-            workspace_bytes: int = 2 << 30, oob_score: bool = False) -> "ForestRegressor":
+            workspace_bytes: int = 2 << 30, oob_score: bool = False, max_features=1.0, importances: bool = False) -> "ForestRegressor":
         """``RandomForestRegressor(n_estimators, ...).fit(x, y)`` with scikit-learn's defaults, grown on ``x.device``: exact CART with
-        squared error and the best split over ALL features, one tree per bag (include/mlqem_hip.h states the rule node by node).
+        squared error and the best split over the node's features, one tree per bag (include/mlqem_hip.h states the rule node by node).
 
         ``x``: float32 [n, F] device tensor; ``y``: [n] or [n, K] on the same device, float32 or float64 (widened to float64 before
         anything is multiplied).  ``sample_counts``: int32 [T, n], how often each row is in each tree's bag; when given it overrides
-        ``n_estimators``, ``bootstrap`` and ``seed``.  Otherwise ``bootstrap=False`` gives every tree every row once, and
-        ``bootstrap=True`` the counts of ``bootstrap_counts(n, n_estimators, seed)`` (numpy's ``default_rng(seed)``; not scikit-learn's
-        bags).  A node's sample count is its number of distinct in-bag rows, as in scikit-learn's forest.
+        ``n_estimators`` and ``bootstrap``, and ``seed`` is ignored for the bags (it still seeds the feature draws of ``max_features``).
+        Otherwise ``bootstrap=False`` gives every tree every row once, and ``bootstrap=True`` the counts of
+        ``bootstrap_counts(n, n_estimators, seed)`` (numpy's ``default_rng(seed)``; not scikit-learn's bags).  A node's sample count
+        is its number of distinct in-bag rows, as in scikit-learn's forest.
 
         Equal scores are broken by the lowest feature index, then the lowest position (scikit-learn: a random feature order), so a
         tree equals scikit-learn's where no two candidates tie.  Two fits give the same buffers bit for bit, whatever
@@ -213,9 +235,17 @@ class ForestRegressor(torch.nn.Module):
         counting with its 0.0); the counts stay as ``fit_info["sample_counts"]``.  These are plain attributes, not buffers: the state
         dict does not change.  It needs bags: with ``bootstrap=False`` and no ``sample_counts`` it is a ``ValueError``.
 
-        Not supported: ``max_features`` below 1.0, criteria other than squared error, ``min_weight_fraction_leaf``, ``ccp_alpha``,
-        missing values.  Every argument is checked on the host before anything is launched (``ValueError`` /
-        ``BlackwaterException``); the finished node table goes through the validation of ``from_arrays``."""
+        ``max_features`` (scikit-learn's: an int, a float in (0, 1], "sqrt", "log2", None; ``fit_info["max_features"]`` holds the
+        resolved m): with m < F every node visits its own feature order, a pure function of (``seed``, tree, node), until it has seen
+        m features and one with a candidate, and splits on the best of those (include/mlqem_hip.h has the rule and where it departs
+        from scikit-learn; the draws are not scikit-learn's).  1.0, None or F is the search over all features, bit for bit.
+
+        ``importances=True`` sets ``feature_importances_`` (float64 [F], host) to ``feature_importances(x, counts)`` of the fit's own
+        rows and bags; a plain attribute as well.
+
+        Not supported: criteria other than squared error, ``min_weight_fraction_leaf``, ``ccp_alpha``, missing values.  Every
+        argument is checked on the host before anything is launched (``ValueError`` / ``BlackwaterException``); the finished node
+        table goes through the validation of ``from_arrays``."""
         if not isinstance(x, torch.Tensor) or not isinstance(y, torch.Tensor):
             raise ValueError("forest fit: x and y must be torch tensors")
         if x.dim() != 2 or x.dtype != torch.float32:
@@ -233,6 +263,7 @@ class ForestRegressor(torch.nn.Module):
         if min_samples_split < 2 or min_samples_leaf < 1 or (max_depth is not None and max_depth < 0):
             raise ValueError("forest fit: want min_samples_split >= 2, min_samples_leaf >= 1 and max_depth >= 0 (or None), got "
                              f"{min_samples_split}, {min_samples_leaf}, {max_depth}")
+        m = resolve_max_features(max_features, f)
         if sample_counts is None:
             if n_estimators < 1:
                 raise ValueError(f"forest fit: n_estimators must be >= 1, got {n_estimators}")
@@ -259,10 +290,11 @@ class ForestRegressor(torch.nn.Module):
         counts = counts.to(x.device).contiguous()
         grown = ops.forest_fit(x, y64, counts, min_samples_split=int(min_samples_split),
                                min_samples_leaf=int(min_samples_leaf), max_depth=None if max_depth is None else int(max_depth),
-                               workspace_bytes=int(workspace_bytes))
+                               workspace_bytes=int(workspace_bytes), max_features=m, seed=int(seed))
         forest = cls.from_arrays(*(grown[key] for key in ("tree_ptr", "feature", "threshold", "left", "right", "value")),
                                  n_features=f).to(x.device)
         forest.fit_info = {key: grown[key] for key in ("levels", "trees_per_chunk", "n_node_samples")}
+        forest.fit_info["max_features"] = m
         if oob_score:
             pred, n_oob = forest._oob_run(x, counts)
             forest._warn_if_no_oob(n_oob)
@@ -270,6 +302,8 @@ class ForestRegressor(torch.nn.Module):
             forest.oob_count_ = n_oob
             forest.oob_score_ = float(r2_score(y64, pred))
             forest.fit_info["sample_counts"] = counts
+        if importances:
+            forest.feature_importances_ = forest._importances_run(x, counts)
         return forest
 
     @classmethod
@@ -343,6 +377,55 @@ class ForestRegressor(torch.nn.Module):
         if not isinstance(y, torch.Tensor) or y.dim() not in (1, 2) or y.numel() != pred.numel() or y.shape[0] != pred.shape[0]:
             raise ValueError(f"forest score: y must be a [{pred.shape[0]}] or [{pred.shape[0]}, {self.n_outputs}] tensor")
         return float(r2_score(y.to(pred.device), pred))
+
+    # ---- impurity importances --------------------------------------------------------------------------------------------------
+    def feature_importances(self, x: torch.Tensor, sample_counts: torch.Tensor) -> np.ndarray:
+        """scikit-learn's ``feature_importances_`` (mean decrease in impurity), float64 [F] on the host, from the training rows ``x``
+        and their bags ``sample_counts`` (int32 [T, n], as ``oob_predict`` takes them; checked on the host first).  The weight W of a
+        leaf is the sum of the counts of the rows ``apply`` puts there (integers: exact in any order), that of an inner node the sum
+        of its children's.  A split node i with children l, r and values v gains
+        ``(W_l sum_k v_l,k^2 + W_r sum_k v_r,k^2 - W_i sum_k v_i,k^2) / K`` -- its weighted impurity less its children's: a value is
+        the weighted mean of its node, so the sum w y^2 terms cancel.  Per tree the gains are added per feature and divided by their
+        sum (a tree of one node, or one whose gains sum to <= 0, is left out); the mean over the remaining trees is divided by its
+        sum once more.  All zeros if no tree remains."""
+        self._check_oob_args(x, sample_counts, "feature_importances")
+        return self._importances_run(x, sample_counts.to(x.device))
+
+    def _importances_run(self, x, counts, pairs_per_chunk: int = 1 << 24):
+        n, t, nf, k = int(x.shape[0]), self.n_trees, self.n_features, self.n_outputs
+        total = int(self.nodes.shape[0])
+        weight = torch.zeros(total, dtype=torch.float64, device=x.device)
+        first = self.tree_ptr[:-1].to(x.device)
+        step = max(1, pairs_per_chunk // t)
+        for r0 in range(0, n, step):
+            leaf = self.apply(x[r0:r0 + step]).to(torch.int64) + first[None, :]                 # [rows, T] in the value table's numbering
+            weight.index_add_(0, leaf.reshape(-1), counts[:, r0:r0 + step].t().to(torch.float64).reshape(-1))
+        nodes, tree_ptr = self.nodes.cpu().numpy(), self.tree_ptr.cpu().numpy()
+        offset = np.repeat(tree_ptr[:-1], np.diff(tree_ptr))
+        orig = offset + nodes[:, 3]
+        w = weight.cpu().numpy()[orig]                                                          # pre-order from here on
+        sq = (self.value.cpu().numpy() ** 2).sum(axis=1)[orig]
+        inner = nodes[:, 1] >= 0
+        at = np.arange(total)
+        left, right = np.where(inner, at + 1, -1), np.where(inner, offset + nodes[:, 2], -1)
+        levels, frontier = [], tree_ptr[:-1]
+        while frontier.size:
+            levels.append(frontier)
+            split = frontier[inner[frontier]]
+            frontier = np.concatenate([left[split], right[split]])
+        for lv in reversed(levels):                                                             # deepest level first
+            split = lv[inner[lv]]
+            w[split] = w[left[split]] + w[right[split]]
+        split = np.flatnonzero(inner)
+        gain = (w[left[split]] * sq[left[split]] + w[right[split]] * sq[right[split]] - w[split] * sq[split]) / float(k)
+        tree_of = np.searchsorted(tree_ptr, split, side="right") - 1
+        per_tree = np.bincount(tree_of * nf + nodes[split, 1], weights=gain, minlength=t * nf).reshape(t, nf)
+        sums = per_tree.sum(axis=1)
+        keep = (np.diff(tree_ptr) > 1) & (sums > 0.0)
+        if not keep.any():
+            return np.zeros(nf, np.float64)
+        mean = (per_tree[keep] / sums[keep, None]).mean(axis=0)
+        return mean / mean.sum()
 
     # ---- out-of-bag estimates -------------------------------------------------------------------------------------------------
     def _check_oob_args(self, x, sample_counts, what):

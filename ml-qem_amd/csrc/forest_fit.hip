@@ -13,17 +13,19 @@
 //                                               every position and reduces (score, position) per segment with a segmented max-scan
 //   select     (a workgroup per tree)           a thread per segment: leaf tests, argmax over the features in feature order, the
 //                                               threshold, the node record; children and their places in the next lists are numbered
-//                                               by exclusive scans in segment order
+//                                               by exclusive scans in segment order.  With max_features < F the argmax runs over
+//                                               the node's own feature subset instead (select_subset: the same body, a keyed
+//                                               permutation of the features per node, walked until m features and a candidate are seen)
 //   partition  (a workgroup per tree, feature)  stable partition of every split segment into its children (ranks by a segmented
 //                                               scan of the go-left flags); the rows of segments that became leaves are dropped
 // Row lists, segment ids and segment tables are double buffered (level & 1 reads, the other half is written).
 //
 // Every sum is a scan whose association depends on the tile size and the positions alone: no atomics, the same bits from call to
 // call and for every chunking (a tree never reads another tree's state).  Every loop's trip count comes from a launch argument (n,
-// F, K) or from a level counter clamped to n; every index read from a workspace buffer (row, segment, feature, node, position,
-// destination) is clamped before it addresses memory, so a corrupted workspace gives a wrong forest -- which the host validation
-// of the finished node table then sees -- never an out-of-range access.  Loads are unconditional on clamped indices and masked by
-// selects afterwards.  No workgroup waits for another.
+// F, K; the cycle walk of a feature permutation: 4^h <= 4 F) or from a level counter clamped to n; every index read from a
+// workspace buffer (row, segment, feature, node, position, destination) is clamped before it addresses memory, so a corrupted
+// workspace gives a wrong forest -- which the host validation of the finished node table then sees -- never an out-of-range
+// access.  Loads are unconditional on clamped indices and masked by selects afterwards.  No workgroup waits for another.
 #include <math.h>
 
 #include "common.hpp"
@@ -224,7 +226,41 @@ __global__ __launch_bounds__(kBlock) void fit_search_kernel(mlqem_forest_fit_sta
 }
 
 // ---- select: leaf or split, node records, the next level's segments ----------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void fit_select_kernel(mlqem_forest_fit_state s, int buf, int depth) {
+// The per-node feature order of max_features < F (include/mlqem_hip.h states the rule): a Feistel permutation of [0, 4^h) keyed by
+// (seed, forest tree, node), walked along its cycle until it lands below F.  All arithmetic is uint32.
+struct FitSubset { int m, h; uint32_t seed, tree_base; };
+
+__device__ __forceinline__ uint32_t fit_mix(uint32_t x) {
+  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+  return x;
+}
+
+__device__ __forceinline__ uint32_t fit_feistel(uint32_t v, uint32_t key, int h) {
+  const uint32_t mask = (1u << h) - 1u;
+  uint32_t l = v >> h, r = v & mask;
+#pragma unroll
+  for (uint32_t round = 0; round < 8; ++round) {
+    const uint32_t nr = l ^ (fit_mix(r ^ key ^ (round * 0x9e3779b9u)) & mask);
+    l = r;
+    r = nr;
+  }
+  return (l << h) | r;
+}
+
+// pi(i) of the node with this key: at most D = 4^h steps along the cycle of i (E is a bijection of [0, D) and i < F, so the cycle
+// returns below F), clamped to F - 1 whatever the arguments.  No memory is touched: the lane-varying trip count guards no load.
+__device__ __forceinline__ int fit_perm(uint32_t i, uint32_t key, int h, int F) {
+  const uint32_t D = 1u << (2 * h);
+  uint32_t v = fit_feistel(i & (D - 1u), key, h);
+  for (uint32_t step = 1; step < D && v >= (uint32_t)F; ++step) v = fit_feistel(v, key, h);
+  return (int)min(v, (uint32_t)(F - 1));
+}
+
+// One body for both kernels: kSubset = false searches every feature (fit_select_kernel), kSubset = true the node's own subset
+// (fit_select_subset_kernel); leaf tests, threshold, node record and the two numbering scans are the same code.  The state comes
+// by value, as the kernels get it: so the plain kernel compiles to the instructions it had before the body was shared.
+template <bool kSubset>
+__device__ __forceinline__ void fit_select_body(mlqem_forest_fit_state s, int buf, int depth, FitSubset sub) {
   __shared__ int sh_v[4], sh_f[4], sh_carry[2];
   const int tid = threadIdx.x, n = (int)s.n, K = s.K, F = s.F;
   const int t = blockIdx.x;
@@ -263,14 +299,37 @@ __global__ __launch_bounds__(kBlock) void fit_select_kernel(mlqem_forest_fit_sta
     bool leaf = depth >= s.max_depth || rows < s.min_samples_split || rows < 2 * s.min_samples_leaf || impurity <= kFitEps;
     double best = -INFINITY;
     int best_pos = -1, best_f = -1;
-    for (int f = 0; f < F; ++f) {   // feature order: on equal scores the lowest feature keeps the split
-      const size_t at = ((size_t)t * F + f) * n + sc;
-      const double score = s.cand_score[at];
-      const int pos = s.cand_pos[at];
-      const bool better = pos >= 0 && score > best;
-      best = better ? score : best;
-      best_pos = better ? pos : best_pos;
-      best_f = better ? f : best_f;
+    if constexpr (!kSubset) {
+      for (int f = 0; f < F; ++f) {   // feature order: on equal scores the lowest feature keeps the split
+        const size_t at = ((size_t)t * F + f) * n + sc;
+        const double score = s.cand_score[at];
+        const int pos = s.cand_pos[at];
+        const bool better = pos >= 0 && score > best;
+        best = better ? score : best;
+        best_pos = better ? pos : best_pos;
+        best_f = better ? f : best_f;
+      }
+    } else {
+      // The node visits pi(0), pi(1), ... and stops after the smallest count >= m at which a visited feature has a candidate.  Every
+      // lane runs to the largest count of its wave (the exit is a wave vote, so no load sits behind a lane-varying branch): a lane
+      // that is done keeps loading at its clamped address and masks what it read.  A lane that is a leaf anyway visits nothing.
+      const uint32_t key = fit_mix(fit_mix(fit_mix(sub.seed) ^ (sub.tree_base + (uint32_t)t)) ^ (uint32_t)node);
+      bool done = !valid || leaf;
+      int with_cand = 0;
+      for (int i = 0; i < F; ++i) {
+        if (__all(done)) break;
+        const int f = fit_perm((uint32_t)i, key, sub.h, F);
+        const size_t at = ((size_t)t * F + f) * n + sc;
+        const double score = s.cand_score[at];
+        const int pos = s.cand_pos[at];
+        const bool has = !done && pos >= 0;
+        const bool better = has && (score > best || (score == best && f < best_f));   // equal scores: the lowest feature
+        best = better ? score : best;
+        best_pos = better ? pos : best_pos;
+        best_f = better ? f : best_f;
+        with_cand += has ? 1 : 0;
+        done = done || (i + 1 >= sub.m && with_cand > 0);
+      }
     }
     leaf = leaf || best_f < 0 || rows < 2;
     const bool split = valid && !leaf;
@@ -301,6 +360,14 @@ __global__ __launch_bounds__(kBlock) void fit_select_kernel(mlqem_forest_fit_sta
     const int splits = fit_clamp(sh_carry[0], 0, (max_nodes - lv.nodes) / 2);
     *next_level = fit_i4{2 * splits, sh_carry[1], lv.nodes + 2 * splits, 0};
   }
+}
+
+__global__ __launch_bounds__(kBlock) void fit_select_kernel(mlqem_forest_fit_state s, int buf, int depth) {
+  fit_select_body<false>(s, buf, depth, FitSubset{});
+}
+
+__global__ __launch_bounds__(kBlock) void fit_select_subset_kernel(mlqem_forest_fit_state s, int buf, int depth, FitSubset sub) {
+  fit_select_body<true>(s, buf, depth, sub);
 }
 
 // ---- partition: the next level's row lists -----------------------------------------------------------------------------------------
@@ -401,6 +468,22 @@ extern "C" int mlqem_forest_fit_select(const mlqem_forest_fit_state* s, int leve
   if (const int code = fit_check(s)) return code;
   if (level < 0) return MLQEM_ERR_BAD_ARG;
   hipLaunchKernelGGL(fit_select_kernel, dim3((unsigned)s->Tc), dim3(kBlock), 0, as_stream(stream), *s, level & 1, level);
+  return launch_status();
+}
+
+extern "C" int mlqem_forest_fit_select_subset(const mlqem_forest_fit_state* s, int level, int max_features, uint32_t seed,
+                                              int64_t tree_base, mlqem_stream_t stream) {
+  begin_launches();
+  if (const int code = fit_check(s)) return code;
+  if (level < 0 || max_features < 1 || tree_base < 0) return MLQEM_ERR_BAD_ARG;
+  if (max_features >= s->F) {   // every feature is visited: the plain kernel, bit for bit
+    hipLaunchKernelGGL(fit_select_kernel, dim3((unsigned)s->Tc), dim3(kBlock), 0, as_stream(stream), *s, level & 1, level);
+    return launch_status();
+  }
+  int bits = 0;   // h = max(1, ceil(bit_length(F - 1) / 2)): F <= 4^h <= 4 F, and F <= 32767 keeps h <= 8
+  while (bits < 31 && ((s->F - 1) >> bits) != 0) ++bits;
+  const FitSubset sub{max_features, bits < 2 ? 1 : (bits + 1) / 2, seed, (uint32_t)tree_base};
+  hipLaunchKernelGGL(fit_select_subset_kernel, dim3((unsigned)s->Tc), dim3(kBlock), 0, as_stream(stream), *s, level & 1, level, sub);
   return launch_status();
 }
 

@@ -2,6 +2,7 @@
 ``RandomForestRegressor(n_estimators=T).fit`` on the same rows.
 
     python scripts/forest_fit_micro.py [--out profiles/forest_fit_micro.json] [--shapes demo1,demo2,g1,scale] [--quick]
+    python scripts/forest_fit_micro.py --max-features [--out profiles/forest_subset_micro.json] [--shapes ...] [--quick]
 
 Shapes (rows x F x K, T): demo1 100 x 170 x 1, 100; demo2 2 500 x 169 x 1, 100; the G1 regime 2 000 x 58 x 4, 300; one scale point
 100 000 x 58 x 4, 100.  Rows are seeded stand-ins for ``encode_data`` rows: the first half of the columns standard normal, the second
@@ -13,6 +14,11 @@ half small integer counts (duplicates everywhere); y is a smooth function of thr
   scikit     ``RandomForestRegressor(n_estimators=T, random_state=0, n_jobs=j).fit`` for j = 1 and 16 on the host clock, median of
              3 (one run where a run takes longer than 20 s).  At the scale point j = 1 is timed on T / 10 trees and scaled by 10
              (said so in the result): trees are independent, and a full run would take tens of minutes.
+
+``--max-features`` measures feature subsets per node instead (no scikit-learn run): per shape, ``fit(max_features=F)`` and
+``fit(max_features=max(1, F // 3))`` alternated in one process, 1 warm-up each, median of 5 rounds, then one fit each with device
+events around every launch.  ``search`` and ``partition`` walk all F lists either way, so no speed-up is expected; what is watched is
+the share of ``select``, whose loop over the features becomes the node's keyed permutation.  There is no threshold.
 """
 import argparse
 import json
@@ -84,13 +90,7 @@ def point(name, n, F, K, T):
          "levels": forest.fit_info["levels"], "nodes": int(forest.nodes.shape[0]), "max_depth": forest.max_depth,
          "trees_per_chunk": forest.fit_info["trees_per_chunk"], "workspace_bytes_per_tree": ops.forest_fit_tree_bytes(n, F, K)}
     p["workspace_bytes"] = p["workspace_bytes_per_tree"] * p["trees_per_chunk"] + 4 * F * n
-    profile = {}
-    ops.forest_fit(x_d, y_d, bootstrap_counts(n, T, 0).to(DEV), profile=profile)
-    torch.cuda.synchronize()
-    per_kernel = {k: sum(a.elapsed_time(b) for a, b in v) * 1e-3 for k, v in profile.items()}
-    total = sum(per_kernel.values())
-    p["kernels"] = {k: {"seconds": s, "launches": len(profile[k]), "share_of_kernel_time": s / total} for k, s in per_kernel.items()}
-    p["kernel_seconds"] = total
+    p.update(kernel_split(x_d, y_d, bootstrap_counts(n, T, 0).to(DEV)))
     if sklearn is not None:
         if n >= 50000:
             p["sklearn_seconds_1_job"] = 10.0 * sklearn_seconds(X, y, T // 10, 1)
@@ -106,22 +106,69 @@ def point(name, n, F, K, T):
     return p
 
 
+def kernel_split(x_d, y_d, counts, **kw):
+    profile = {}
+    ops.forest_fit(x_d, y_d, counts, profile=profile, **kw)
+    torch.cuda.synchronize()
+    per_kernel = {k: sum(a.elapsed_time(b) for a, b in v) * 1e-3 for k, v in profile.items()}
+    total = sum(per_kernel.values())
+    return {"kernel_seconds": total,
+            "kernels": {k: {"seconds": s, "launches": len(profile[k]), "share_of_kernel_time": s / total} for k, s in per_kernel.items()}}
+
+
+def subset_point(name, n, F, K, T):
+    """``max_features = F`` against ``max(1, F // 3)``: alternated end-to-end fits, then one profiled fit each."""
+    X, y = make_rows(n, F, K, seed=n + F)
+    x_d, y_d = torch.from_numpy(X).to(DEV), torch.from_numpy(y).to(DEV)
+    counts = bootstrap_counts(n, T, 0).to(DEV)
+    settings = {"all_features": F, "subset": max(1, F // 3)}
+    runs, forests = {k: [] for k in settings}, {}
+    for rnd in range(6):                       # round 0 warms both up
+        for key, m in settings.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            forests[key] = ForestRegressor.fit(x_d, y_d, n_estimators=T, seed=0, max_features=m)
+            torch.cuda.synchronize()
+            if rnd:
+                runs[key].append(time.perf_counter() - t0)
+    p = {"shape": name, "rows": n, "features": F, "outputs": K, "trees": T}
+    for key, m in settings.items():
+        forest = forests[key]
+        p[key] = {"max_features": m, "fit_end_to_end_seconds": statistics.median(runs[key]), "fit_runs_seconds": runs[key],
+                  "levels": forest.fit_info["levels"], "nodes": int(forest.nodes.shape[0]), "max_depth": forest.max_depth,
+                  **kernel_split(x_d, y_d, counts, max_features=m, seed=0)}
+    p["fit_ratio_subset_over_all"] = p["subset"]["fit_end_to_end_seconds"] / p["all_features"]["fit_end_to_end_seconds"]
+    print(json.dumps(p), flush=True)
+    return p
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "forest_fit_micro.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/forest_fit_micro.json, or profiles/forest_subset_micro.json with --max-features")
+    ap.add_argument("--max-features", action="store_true", help="measure max_features = F against max(1, F // 3) instead (no scikit-learn)")
     ap.add_argument("--shapes", default="demo1,demo2,g1,scale")
     ap.add_argument("--quick", action="store_true", help="a rehearsal: a tenth of the rows and trees, not a measurement")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "forest_subset_micro.json" if args.max_features else "forest_fit_micro.json")
     if not torch.cuda.is_available():
         sys.exit("forest_fit_micro: needs the GPU (there is no host path to time)")
     points = []
-    result = {"device": torch.cuda.get_device_name(0), "sklearn": None if sklearn is None else sklearn.__version__,
-              "method": "host clock around ForestRegressor.fit with a final device wait, 1 warm-up, median of 5; device events around "
-                        "every launch in one further fit; scikit-learn on the host clock, n_jobs 1 and 16, median of 3 (one run above 20 s)",
-              "quick": args.quick, "points": points}
+    if args.max_features:
+        result = {"device": torch.cuda.get_device_name(0),
+                  "method": "per shape: ForestRegressor.fit(max_features=F) and fit(max_features=max(1, F // 3)) alternated in one process, "
+                            "host clock with a final device wait, 1 warm-up each, median of 5; then one fit each through "
+                            "ops.forest_fit(profile=...) with device events around every launch",
+                  "quick": args.quick, "points": points}
+    else:
+        result = {"device": torch.cuda.get_device_name(0), "sklearn": None if sklearn is None else sklearn.__version__,
+                  "method": "host clock around ForestRegressor.fit with a final device wait, 1 warm-up, median of 5; device events around "
+                            "every launch in one further fit; scikit-learn on the host clock, n_jobs 1 and 16, median of 3 (one run above "
+                            "20 s)",
+                  "quick": args.quick, "points": points}
     for name in args.shapes.split(","):
         n, F, K, T = SHAPES[name]
-        points.append(point(name, *((max(n // 10, 10), F, K, max(T // 10, 2)) if args.quick else (n, F, K, T))))
+        points.append((subset_point if args.max_features else point)(name, *((max(n // 10, 10), F, K, max(T // 10, 2)) if args.quick else (n, F, K, T))))
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as fh:      # after every point: a long run that is cut short keeps what it measured
             json.dump(result, fh, indent=1)

@@ -1203,6 +1203,50 @@ int mlqem_forest_fit_select_subset(const mlqem_forest_fit_state* state, int leve
 int mlqem_forest_fit_partition(const mlqem_forest_fit_state* state, int level, mlqem_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Gradient-boosted regression trees, squared error (additive symbols, the ABI version is unchanged).  Replaces
+ * GradientBoostingRegressor(...).fit / .predict of scikit-learn on encode_data rows (the notebooks that build the random-forest
+ * mitigator import it in the same line: h15, h18, h19, h20, h21, h26, h33, h36, demo1, demo2).  blackwater.native.ops.boost_fit /
+ * boost_predict and blackwater.nn.BoostedRegressor drive them.  Both kernels are compiled without floating-point contraction: the
+ * contracts below are stated operation by operation.
+ *
+ * mlqem_boost_predict_f32 scores an ensemble stored as mlqem_forest_predict_f32 takes a forest with K = 1 (nodes in pre-order,
+ * tree_ptr, values float64 [N]; the walk, the clamps and the thr32 rule are those of the forest kernel):
+ *
+ *   out[r] = ((init + lr * v_0) + lr * v_1) + ... + lr * v_{n_stages-1},     v_t = values[tree_ptr[t] + leaf_t(x[r, :])]
+ *
+ * in stage order, one rounded multiply and one rounded add per stage in float64 -- scikit-learn's predict_stages, bit for bit.
+ * n_stages <= T (tree_ptr holds at least n_stages + 1 entries): a prefix of the ensemble scores without repacking.  staged
+ * (optional): float64 [n_stages][lds], lds >= n_rows, staged[t * lds + r] = the running sum of row r after stage t; the threads of a
+ * tile write consecutive rows.  One thread owns a row's sum; loads are unconditional on clamped indices; the walk's trip count is
+ * wave-uniform and at most max_depth; no atomics, no workspace; results are bit-identical across calls, n_rows and tile sizes (64, 16
+ * or 4 rows a workgroup); capturable in a hipGraph.  Serves 1 <= F <= 32767 (MLQEM_ERR_UNSUPPORTED beyond); n_stages >= 1, ldx >= F,
+ * lds >= n_rows with staged, non-null 16-byte aligned nodes (MLQEM_ERR_BAD_ARG); n_rows == 0 returns MLQEM_OK without a launch.
+ *
+ * mlqem_boost_update_f64 is the step between two stages of a fit.  It reads the stage's tree in the numbering of the fit workspace
+ * (mlqem_forest_fit_state with K = 1: node_i = (feature or -2, left, right, rows), node_thr, node_value; n_nodes entries, node 0 the
+ * root) and, one thread per row r of x (float32 [n_rows, F], row stride ldx):
+ *   leaf    walk from the root, "go left iff double(x[r, feature]) <= node_thr" (scikit-learn's compare), at most max_depth + 1
+ *           steps under a wave-uniform exit, every feature clamped to F and every child to n_nodes;
+ *   raw[r]   = raw[r] + lr * node_value[leaf]        (a rounded multiply, then a rounded add)
+ *   resid[r] = y[r] - raw[r]
+ * A tree of at most 511 nodes is staged in LDS, a larger one is read from global memory.  mask (int32 [n_rows] or null = every row):
+ * non-zero means the row is in the stage's bag.  The same launch writes ONE record of four float64 sums per workgroup of 256 rows,
+ * partial[block * 4 + (0..3)] = (sum over in-bag rows of resid^2 after the update, sum over out-of-bag rows of (y - raw)^2 before it,
+ * the same after it, the number of in-bag rows), each summed by a shuffle tree within a wave and then wave 0..3 in order: the same
+ * bits from call to call.  mlqem_boost_update_blocks(n_rows) is the number of records (ceil(n_rows / 256)); the caller adds them in
+ * block order.  No atomics, no workspace, no workgroup waits for another.  Serves n_rows <= 2^22, F <= 32767
+ * (MLQEM_ERR_UNSUPPORTED beyond); n_rows >= 1, n_nodes >= 1, max_depth >= 0, ldx >= F, non-null buffers and a 16-byte aligned node_i
+ * (MLQEM_ERR_BAD_ARG), all checked before the launch.
+ * ---------------------------------------------------------------------------------------------------- */
+int mlqem_boost_predict_f32(const float* x, int64_t ldx, int64_t n_rows, int F, const mlqem_forest_node* nodes,
+                            const int64_t* tree_ptr, int n_stages, const double* values, int max_depth, double init, double lr,
+                            double* out, double* staged, int64_t lds, mlqem_stream_t stream);
+int64_t mlqem_boost_update_blocks(int64_t n_rows);
+int mlqem_boost_update_f64(const float* x, int64_t ldx, int64_t n_rows, int F, const int32_t* node_i, const double* node_thr,
+                           const double* node_value, int n_nodes, int max_depth, double lr, const double* y, double* raw,
+                           double* resid, const int32_t* mask, double* partial, mlqem_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * Linear least squares (ABI 46).  Replaces ols.fit(X, y) / ols.predict(X) of a scikit-learn LinearRegression (or Ridge) on
  * encode_data rows (docs/tutorials/h12_ols.ipynb, h17_compare_over_steps.ipynb; ScikitLearningModelProcessor(ols, ...) in the VQE
  * drivers).  The fit is one streaming pass over the rows on the device (the moments below) and a solve of at most 529 x 529 on the

@@ -3,9 +3,9 @@ post-processed by a pluggable processor (reference: blackwater/library/learning/
 
 In scope: the decorator, the job wrapper, the processor protocol, ``TorchLearningModelProcessor``,
 ``EmptyProcessor``, ``ScikitLearningModelProcessor`` (the random-forest / OLS baselines: same feature rows, the
-model stays on the host CPU), ``ForestLearningModelProcessor`` and ``LinearLearningModelProcessor``
-(additions: the same random forests and the same OLS / ridge models scored on the device by the forest and least-squares kernels,
-one launch per ``run()``).  ``ZNEProcessor`` (runs extra noisy circuits
+model stays on the host CPU), ``ForestLearningModelProcessor``, ``BoostedLearningModelProcessor`` and
+``LinearLearningModelProcessor`` (additions: the same random forests, gradient-boosted trees and OLS / ridge models scored on the
+device by the forest, boosted-trees and least-squares kernels, one launch per ``run()``).  ``ZNEProcessor`` (runs extra noisy circuits
 through a ZNE estimator; no model) is out of scope.
 """
 from __future__ import annotations
@@ -187,6 +187,27 @@ class LinearLearningModelProcessor(_DeviceRegressorProcessor):
 
         if not isinstance(model, LinearRegressor):
             model = LinearRegressor.from_sklearn(model)   # BlackwaterException for anything that is not a fitted linear model
+        self._model = model.to(device)
+        self._device = torch.device(device)
+        self._backend = backend
+        self._properties = get_backend_properties_v1(backend)
+
+
+class BoostedLearningModelProcessor(_DeviceRegressorProcessor):
+    """A gradient-boosted mitigator (``ScikitLearningModelProcessor(GradientBoostingRegressor().fit(...), backend)``, reference
+    :90-148; the notebooks import it beside the random forest) scored on the device: the same per-term ``encode_data`` rows, all
+    (circuit, Pauli term) rows of a ``run()`` through ONE launch of the boosted-trees kernel (``blackwater.nn.BoostedRegressor``),
+    ``output * coeff`` summed per circuit.
+
+    ``model``: a fitted scikit-learn ``GradientBoostingRegressor`` with squared-error loss (converted with
+    ``BoostedRegressor.from_sklearn``) or a ``BoostedRegressor`` (``BoostedRegressor.fit`` fits one on the device).  There is no host
+    path: ``device`` must be a GPU."""
+
+    def __init__(self, model, backend, device="cuda"):
+        from ...nn.boost import BoostedRegressor
+
+        if not isinstance(model, BoostedRegressor):
+            model = BoostedRegressor.from_sklearn(model)   # BlackwaterException for anything that is not a fitted squared-error ensemble
         self._model = model.to(device)
         self._device = torch.device(device)
         self._backend = backend

@@ -217,6 +217,9 @@ SIGNATURES = {
     "mlqem_forest_fit_select": (_I, [_P, _I, _P]),
     "mlqem_forest_fit_select_subset": (_I, [_P, _I, _I, ctypes.c_uint32, _L, _P]),
     "mlqem_forest_fit_partition": (_I, [_P, _I, _P]),
+    "mlqem_boost_predict_f32": (_I, [_P, _L, _L, _I, _P, _P, _I, _P, _I, _D, _D, _P, _P, _L, _P]),
+    "mlqem_boost_update_blocks": (_L, [_L]),
+    "mlqem_boost_update_f64": (_I, [_P, _L, _L, _I, _P, _P, _P, _I, _I, _D, _P, _P, _P, _P, _P, _P]),
     "mlqem_linreg_moments_workspace_bytes": (_S, [_L, _I, _I]),
     "mlqem_linreg_moments_f32": (_I, [_P, _L, _P, _L, _L, _I, _I, _P, _I, _P, _S, _P]),
     "mlqem_linreg_predict_f32": (_I, [_P, _L, _L, _I, _P, _P, _I, _P, _P]),

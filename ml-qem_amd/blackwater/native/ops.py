@@ -2225,17 +2225,28 @@ def forest_fit_tree_bytes(n, f, k):
     return int(_lib.load().mlqem_forest_fit_tree_bytes(int(n), int(f), int(k)))
 
 
-def _forest_fit_run(lib, stream, x, y, counts, order, min_samples_split, min_samples_leaf, max_depth, tc, profile=None, subset=None):
-    """The host loop of ``forest_fit`` for tensors that are already checked; every buffer is allocated on ``x.device``.  ``subset``:
-    None, or (max_features, seed) for ``mlqem_forest_fit_select_subset`` in the place of ``mlqem_forest_fit_select``."""
-    n, f = int(x.shape[0]), int(x.shape[1])
-    k, t_all, dev = int(y.shape[1]), int(counts.shape[0]), x.device
+def _forest_fit_workspace(n, f, k, tc, dev):
+    """The workspace of ``tc`` trees of a fit on ``n`` rows x ``f`` features x ``k`` outputs (mlqem_forest_fit_state's buffers)."""
     nn = 2 * n - 1
     i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)      # noqa: E731
     f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)    # noqa: E731
-    buf = dict(rows=i32(2, tc, f, n), segid=i32(2, tc, n), level=i32(2, tc, 4), seg_i=i32(2, tc, n, 4), seg_stat=f64(tc, n, k + 2),
-               cand_score=f64(tc, f, n), cand_pos=i32(tc, f, n), split_i=i32(tc, n, 4), split_thr=f64(tc, n),
-               node_i=i32(tc, nn, 4), node_thr=f64(tc, nn), node_value=f64(tc, nn, k))
+    return dict(rows=i32(2, tc, f, n), segid=i32(2, tc, n), level=i32(2, tc, 4), seg_i=i32(2, tc, n, 4), seg_stat=f64(tc, n, k + 2),
+                cand_score=f64(tc, f, n), cand_pos=i32(tc, f, n), split_i=i32(tc, n, 4), split_thr=f64(tc, n),
+                node_i=i32(tc, nn, 4), node_thr=f64(tc, nn), node_value=f64(tc, nn, k))
+
+
+def _forest_fit_run(lib, stream, x, y, counts, order, min_samples_split, min_samples_leaf, max_depth, tc, profile=None, subset=None,
+                    buf=None, tree_base=0, finish=True):
+    """The host loop of ``forest_fit`` for tensors that are already checked; every buffer is allocated on ``x.device``.  ``subset``:
+    None, or (max_features, seed) for ``mlqem_forest_fit_select_subset`` in the place of ``mlqem_forest_fit_select``.  ``buf``: a
+    workspace of ``_forest_fit_workspace`` to grow in (allocated here when None).  ``tree_base``: the forest index of the first row
+    of ``counts`` (it keys the feature subsets).  ``finish=False`` (a stage of ``boost_fit``: one tree, its table stays on the device)
+    returns ``(node count, levels)`` and copies nothing but the levels' 16-byte reads."""
+    n, f = int(x.shape[0]), int(x.shape[1])
+    k, t_all, dev = int(y.shape[1]), int(counts.shape[0]), x.device
+    nn = 2 * n - 1
+    if buf is None:
+        buf = _forest_fit_workspace(n, f, k, tc, dev)
     max_levels = min(max_depth, n - 1) + 1   # a node at depth max_depth, or one of a single row (depth <= n - 1), is a leaf
     steps = (("stats", lib.mlqem_forest_fit_stats), ("search", lib.mlqem_forest_fit_search), ("select", lib.mlqem_forest_fit_select),
              ("partition", lib.mlqem_forest_fit_partition))
@@ -2264,7 +2275,7 @@ def _forest_fit_run(lib, stream, x, y, counts, order, min_samples_split, min_sam
             if subset is None:
                 launch("select", steps[2][1], ref, d, stream)
             else:   # the key of a node's feature order holds the tree's index in the whole forest: t0 + its index in the chunk
-                launch("select", lib.mlqem_forest_fit_select_subset, ref, d, subset[0], subset[1], t0, stream)
+                launch("select", lib.mlqem_forest_fit_select_subset, ref, d, subset[0], subset[1], tree_base + t0, stream)
             nxt = (d + 1) & 1
             live = flat_level[nxt * c * 4:(nxt + 1) * c * 4].cpu().view(c, 4)   # the level's one read: live segments, nodes so far
             levels = max(levels, d + 1)
@@ -2276,6 +2287,8 @@ def _forest_fit_run(lib, stream, x, y, counts, order, min_samples_split, min_sam
         count = live[:, 2].to(torch.int64)
         if bool((count < 1).any()) or bool((count > nn).any()):
             raise _lib.NativeLibraryError("forest_fit: a tree's node count is out of range")
+        if not finish:
+            return int(count[0]), levels
         keep = (torch.arange(nn)[None, :] < count[:, None]).to(dev)
         node_i.append(buf["node_i"].view(-1)[:c * nn * 4].view(c, nn, 4)[keep].cpu())
         node_thr.append(buf["node_thr"].view(-1)[:c * nn].view(c, nn)[keep].cpu())
@@ -2335,6 +2348,152 @@ def forest_fit(x, y, counts, *, min_samples_split=2, min_samples_leaf=1, max_dep
     order = torch.argsort(x.t(), dim=1, stable=True).to(torch.int32).contiguous()   # [F, n], once per fit
     depth = 2 ** 31 - 1 if max_depth is None else min(int(max_depth), 2 ** 31 - 1)
     return _forest_fit_run(lib, _stream(), x, y, counts, order, min_samples_split, min_samples_leaf, depth, tc, profile, subset)
+
+
+def boost_predict(x, nodes, tree_ptr, values, max_depth, init, lr, *, n_stages=None, staged=False, out=None, staged_out=None):
+    """Scores a gradient-boosted ensemble (mlqem_boost_predict_f32): ``(out, staged)`` with ``out`` float64 [n] =
+    ``((init + lr v_0) + lr v_1) + ...`` over the first ``n_stages`` trees (all T when None) in stage order, one rounded multiply and
+    one rounded add per stage, and ``staged`` float64 [n_stages, n] the running sum after every stage (None unless ``staged`` or
+    ``staged_out`` is given; ``staged_out`` may have any row stride >= n).
+
+    ``nodes``, ``tree_ptr``, ``values`` (float64 [N, 1]): the buffers of ``blackwater.nn.BoostedRegressor``, in the forest's format;
+    ``init`` and ``lr`` are host floats.  The checks and allocation rules are ``forest_predict``'s: nothing here waits for the device
+    or reads a tensor's contents, and with ``out`` (and ``staged_out``) given nothing is allocated: the call can be captured in a
+    hipGraph."""
+    ldx = _mat(x, "x")
+    n, f = int(x.shape[0]), int(x.shape[1])
+    _mat(nodes, "nodes", torch.int32)
+    if not values.is_cuda:
+        raise _lib.NativeLibraryError(f"values must live on the GPU (got {values.device}); there is no CPU path")
+    if (nodes.shape[1] != 4 or not nodes.is_contiguous() or values.dtype != torch.float64 or values.dim() != 2
+            or values.shape[0] != nodes.shape[0] or values.shape[1] != 1 or (values.shape[0] > 1 and values.stride(0) != 1)):
+        raise ValueError(f"boost: want contiguous int32 nodes [N, 4] and float64 values [N, 1], got {tuple(nodes.shape)} {nodes.dtype} "
+                         f"and {tuple(values.shape)} {values.dtype} (strides {values.stride()})")
+    t = int(tree_ptr.shape[0]) - 1
+    _vec(tree_ptr, "tree_ptr", 2, torch.int64)
+    if any(b.device != x.device for b in (nodes, tree_ptr, values)):
+        raise ValueError(f"boost: x is on {x.device}, the ensemble on {nodes.device}")
+    m = t if n_stages is None else n_stages
+    if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 1 <= m <= t:
+        raise ValueError(f"boost: n_stages must be an int in 1..{t}, got {n_stages!r}")
+    m = int(m)
+    if out is None:
+        out = torch.empty((n,), dtype=torch.float64, device=x.device)
+    elif not out.is_cuda or out.device != x.device or out.dtype != torch.float64 or tuple(out.shape) != (n,) or not out.is_contiguous():
+        raise ValueError(f"out: want contiguous float64 [{n}] on {x.device}, got {tuple(out.shape)} {out.dtype} {out.device}")
+    lds = n
+    if staged_out is None and staged:
+        staged_out = torch.empty((m, n), dtype=torch.float64, device=x.device)
+    elif staged_out is not None:
+        if (not staged_out.is_cuda or staged_out.device != x.device or staged_out.dtype != torch.float64
+                or tuple(staged_out.shape) != (m, n) or (n > 1 and staged_out.stride(1) != 1) or (m > 1 and staged_out.stride(0) < n)):
+            raise ValueError(f"staged_out: want float64 [{m}, {n}] on {x.device} with unit column stride and row stride >= {n}, got "
+                             f"{tuple(staged_out.shape)} {staged_out.dtype} {staged_out.device} strides {staged_out.stride()}")
+        lds = int(staged_out.stride(0)) if m > 1 else n
+    code = _lib.load().mlqem_boost_predict_f32(_p(x), ldx, n, f, _p(nodes), _p(tree_ptr), m, _p(values), int(max_depth), float(init),
+                                               float(lr), _p(out), _p(staged_out), lds, _stream())
+    _lib.check(code, "mlqem_boost_predict_f32")
+    return out, staged_out
+
+
+BOOST_MAX_DEPTH = 20   # the node store of a fit holds min(2 n - 1, 2^(max_depth + 1) - 1) records per stage
+
+
+def boost_fit(x, y, masks, *, learning_rate, max_depth, min_samples_split=2, min_samples_leaf=1, max_features=None, seed=0,
+              profile=None):
+    """Fits gradient-boosted regression trees with squared error on the device: stage t grows one exact CART tree
+    (mlqem_forest_fit_*, the rule of include/mlqem_hip.h with K = 1, Tc = 1) on the residuals ``y - raw`` with the rows of
+    ``masks[t]`` as its bag, then ``mlqem_boost_update_f64`` adds ``learning_rate * value[leaf]`` to ``raw`` of ALL rows, renews the
+    residuals and leaves the stage's loss sums in a per-stage record.  ``raw`` starts at the float64 mean of ``y``.
+
+    ``x``: float32 [n, F] (row stride >= F), ``y``: contiguous float64 [n], ``masks``: contiguous int32 [T, n] of 0 and 1, all on one
+    device; the VALUES (finite x and y, a non-empty bag per stage) are the caller's to check, as ``BoostedRegressor.fit`` does.
+    ``max_depth`` is an int in 1..BOOST_MAX_DEPTH: it sizes the node store.  ``max_features``, ``seed``: as ``forest_fit`` (the key of
+    a node's feature order holds the stage's index).
+
+    One stable argsort per column and one workspace serve every stage.  A stage's node table is copied device to device into a
+    [T, cap] store; the store and the loss records come to the host once, after the last stage.  Every level costs four launches
+    and one 16-byte read of the device, as in ``forest_fit``.  Returns the host arrays of ``forest_fit`` (``tree_ptr``, ``feature``,
+    ``threshold``, ``left``, ``right``, ``value`` [N, 1], ``n_node_samples``; validate them with ``BoostedRegressor.from_arrays``)
+    plus ``init`` (float), ``train_score`` float64 [T] (the mean squared residual over the stage's bag after its update),
+    ``oob_improvement`` float64 [T] (the mean squared residual over the rows outside the bag before the update less the one after it;
+    None when every bag is full) and ``levels`` (the most levels a stage took).  ``profile``: a dict that collects (start, end) events
+    per kernel name, ``update`` among them."""
+    ldx = _mat(x, "x")
+    n, f = int(x.shape[0]), int(x.shape[1])
+    _vec(y, "y", n, torch.float64)
+    _mat(masks, "masks", torch.int32)
+    t_all = int(masks.shape[0])
+    if y.shape[0] != n or masks.shape[1] != n or not masks.is_contiguous():
+        raise ValueError(f"boost_fit: x is {tuple(x.shape)}: want y [{n}] and contiguous masks [T, {n}], got {tuple(y.shape)} and "
+                         f"{tuple(masks.shape)}")
+    if y.device != x.device or masks.device != x.device:
+        raise ValueError(f"boost_fit: x is on {x.device}, y on {y.device}, masks on {masks.device}")
+    if not (1 <= n <= FOREST_FIT_MAX_ROWS and 1 <= f <= FOREST_MAX_FEATURES and t_all >= 1 and ldx >= f):
+        raise ValueError(f"boost_fit: want 1 <= n <= {FOREST_FIT_MAX_ROWS}, 1 <= F <= {FOREST_MAX_FEATURES} and a stage, got n {n}, "
+                         f"F {f}, T {t_all}")
+    if isinstance(max_depth, bool) or not isinstance(max_depth, (int, np.integer)) or not 1 <= max_depth <= BOOST_MAX_DEPTH:
+        raise ValueError(f"boost_fit: max_depth must be an int in 1..{BOOST_MAX_DEPTH}, got {max_depth!r}")
+    if min_samples_split < 2 or min_samples_leaf < 1:
+        raise ValueError("boost_fit: want min_samples_split >= 2 and min_samples_leaf >= 1")
+    if max_features is not None and (isinstance(max_features, bool) or not isinstance(max_features, (int, np.integer))
+                                     or not 1 <= max_features <= f):
+        raise ValueError(f"boost_fit: max_features must be None or an int in 1..{f}, got {max_features!r}")
+    subset = None if max_features is None or int(max_features) == f else (int(max_features), int(seed) & 0xFFFFFFFF)
+    lib, stream, dev = _lib.load(), _stream(), x.device
+    depth, lr = int(max_depth), float(learning_rate)
+    cap = min(2 * n - 1, 2 ** (depth + 1) - 1)
+    blocks = int(lib.mlqem_boost_update_blocks(n))
+    order = torch.argsort(x.t(), dim=1, stable=True).to(torch.int32).contiguous()   # [F, n], once per fit
+    buf = _forest_fit_workspace(n, f, 1, 1, dev)
+    store_i = torch.empty((t_all, cap, 4), dtype=torch.int32, device=dev)
+    store_thr = torch.empty((t_all, cap), dtype=torch.float64, device=dev)
+    store_val = torch.empty((t_all, cap), dtype=torch.float64, device=dev)
+    partial = torch.empty((t_all, blocks, 4), dtype=torch.float64, device=dev)
+    init = torch.mean(y)
+    raw = init.expand(n).contiguous()
+    resid = (y - raw).reshape(n, 1)
+    x_ld = int(x.stride(0)) if n > 1 else f
+    counts, levels = [], 0
+    for t in range(t_all):
+        count, lv = _forest_fit_run(lib, stream, x, resid, masks[t:t + 1], order, min_samples_split, min_samples_leaf, depth, 1, profile,
+                                    subset, buf=buf, tree_base=t, finish=False)
+        if count > cap:
+            raise _lib.NativeLibraryError(f"boost_fit: stage {t} has {count} nodes, a tree of depth {depth} at most {cap}")
+        store_i[t].copy_(buf["node_i"][0, :cap])
+        store_thr[t].copy_(buf["node_thr"][0, :cap])
+        store_val[t].copy_(buf["node_value"][0, :cap, 0])
+        if profile is not None:
+            start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+        code = lib.mlqem_boost_update_f64(_p(x), x_ld, n, f, _p(buf["node_i"]), _p(buf["node_thr"]), _p(buf["node_value"]), count, depth,
+                                          lr, _p(y), _p(raw), _p(resid), _p(masks[t]), _p(partial[t]), stream)
+        _lib.check(code, "mlqem_boost_update_f64")
+        if profile is not None:
+            end.record()
+            profile.setdefault("update", []).append((start, end))
+        counts.append(count)
+        levels = max(levels, lv)
+    # the one copy of the fit: node store, loss records and the mean
+    host_i, host_thr, host_val = store_i.cpu().numpy(), store_thr.cpu().numpy(), store_val.cpu().numpy()
+    records, init = partial.cpu().numpy(), float(init)
+    counts = np.asarray(counts, np.int64)
+    keep = np.arange(cap)[None, :] < counts[:, None]
+    node_i = host_i[keep]
+    sums = np.zeros((t_all, 4), np.float64)
+    for b in range(blocks):   # block order
+        sums = sums + records[:, b, :]
+    n_in = sums[:, 3]
+    if (n_in < 1).any() or (n_in > n).any():
+        raise _lib.NativeLibraryError("boost_fit: a stage's in-bag count is out of range")
+    n_out = float(n) - n_in
+    oob = None
+    if (n_out > 0).any():
+        oob = np.where(n_out > 0, (sums[:, 1] - sums[:, 2]) / np.maximum(n_out, 1.0), 0.0)
+    return dict(tree_ptr=np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), feature=node_i[:, 0].astype(np.int64),
+                threshold=host_thr[keep], left=node_i[:, 1].astype(np.int64), right=node_i[:, 2].astype(np.int64),
+                value=host_val[keep][:, None], n_node_samples=node_i[:, 3].astype(np.int64), init=init, train_score=sums[:, 0] / n_in,
+                oob_improvement=oob, levels=levels)
 
 
 LINREG_MAX_FEATURES = 512   # F and K the least-squares kernels serve

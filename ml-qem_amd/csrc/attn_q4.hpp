@@ -107,6 +107,7 @@ template <bool TRAIN, int LPH, bool FAST = false> __device__ __forceinline__ voi
   const int CP = a.CP > 0 ? a.CP : C, HP = H * CP;      // head pitch and part stride inside a qkvs row
   const int offp = h * CP + 4 * lq;                     // the lane's first channel inside a part of qkvs
   const bool roomy = CP - 4 * lq >= 4;                  // the lane's 16 bytes lie inside its head's slot (pads are zeros)
+  const bool kv_in_row = 2 * HP + offp + 4 <= 4 * HP;   // the lane's 16 bytes of the value part (hence of the key part) end inside the row
   const float scale = 1.0f / sqrtf((float)C);
   const float keep = 1.f / (1.f - a.drop_p);
   const uint64_t seed = a.seed + ((TRAIN && a.seed_counter) ? *a.seed_counter * 0xD1B54A32D192ED03ull : 0ull);
@@ -154,10 +155,18 @@ template <bool TRAIN, int LPH, bool FAST = false> __device__ __forceinline__ voi
     f4u kk[4], vv[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      if (FAST || (u < k && nv > 0)) {                   // uniform over the (row, head)'s lanes but for the channel-less ones
-        const float* __restrict__ kj = qkvs + (int64_t)ju[u] * ld + HP + offp;
+      const float* __restrict__ kj = qkvs + (int64_t)ju[u] * ld + HP + offp;
+      if constexpr (FAST) {
         kk[u] = *reinterpret_cast<const f4u*>(kj);       // inside the row: a key segment runs over into the value part at most,
         vv[u] = *reinterpret_cast<const f4u*>(kj + HP);  // a value segment into the skip part
+      } else if (u < k && nv > 0 && kv_in_row) {         // uniform over the (row, head)'s lanes but for the channel-less ones
+        kk[u] = *reinterpret_cast<const f4u*>(kj);       // inside the row, as above
+        vv[u] = *reinterpret_cast<const f4u*>(kj + HP);
+      } else if (u < k && nv > 0) {
+        // H C < 3: the value (and key) segment of the last head ends past the ROW -- in the next row, or past the buffer after the
+        // last one -- and what lies there need not be finite (0 * NaN would reach the score): the lane's own channels only
+        kk[u] = load_channels(kj, nv, false);
+        vv[u] = load_channels(kj + HP, nv, false);
       } else {
         kk[u] = f4u{0.f, 0.f, 0.f, 0.f};
         vv[u] = f4u{0.f, 0.f, 0.f, 0.f};

@@ -263,6 +263,7 @@ template <int LPH, bool FAST> __global__ __launch_bounds__(kBlock) void transfor
   const int off = h * C + 4 * lq;
   const int CP = a.CP > 0 ? a.CP : C, HP = H * CP, offp = h * CP + 4 * lq;      // head pitch / part stride / lane offset inside qkvs, gqkvs
   const int nvs = min(4, max(0, CP - 4 * lq));           // floats of the lane's slot: what it stores (pads come out zero)
+  const bool kv_in_row = 2 * HP + offp + 4 <= 4 * HP;    // the lane's 16 bytes of the value part (hence of the key part) end inside the row
   const float scale = 1.0f / sqrtf((float)C);
   const float keep = 1.f / (1.f - a.drop_p);
   const uint64_t seed = a.seed + (a.seed_counter ? *a.seed_counter * 0xD1B54A32D192ED03ull : 0ull);   // as the forward
@@ -312,10 +313,13 @@ template <int LPH, bool FAST> __global__ __launch_bounds__(kBlock) void transfor
     f4u kk[4], vv[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      if (FAST || (u < k && nv > 0)) {
-        const float* __restrict__ kj = qkvs + (int64_t)ju[u] * ld + HP + offp;
+      const float* __restrict__ kj = qkvs + (int64_t)ju[u] * ld + HP + offp;
+      if (FAST || (u < k && nv > 0 && kv_in_row)) {
         kk[u] = *reinterpret_cast<const f4u*>(kj);
         vv[u] = *reinterpret_cast<const f4u*>(kj + HP);
+      } else if (u < k && nv > 0) {                      // H C < 3: the segment ends past the row (attn_q4.hpp): the lane's own channels only
+        kk[u] = load_channels(kj, nv, false);
+        vv[u] = load_channels(kj + HP, nv, false);
       } else {
         kk[u] = f4u{0.f, 0.f, 0.f, 0.f};
         vv[u] = f4u{0.f, 0.f, 0.f, 0.f};
@@ -387,8 +391,8 @@ template <int LPH, bool FAST> __global__ __launch_bounds__(kBlock) void transfor
     kown = *reinterpret_cast<const f4u*>(rj + HP + offp);
     vown = *reinterpret_cast<const f4u*>(rj + 2 * HP + offp);
   } else {
-    kown = load_channels(rj + HP + offp, nv, true);                  // runs over into the value part at most
-    vown = load_channels(rj + 2 * HP + offp, nv, true);              // ... into the skip part
+    kown = load_channels(rj + HP + offp, nv, HP + offp + 4 <= 4 * HP);       // runs over into the value part at most
+    vown = load_channels(rj + 2 * HP + offp, nv, 2 * HP + offp + 4 <= 4 * HP);   // ... into the skip part (H C < 3: past the row)
   }
   const int n_self = a.loops ? a.loops[row] : 0;
   f4u gk = {0.f, 0.f, 0.f, 0.f}, gv = {0.f, 0.f, 0.f, 0.f};

@@ -1278,6 +1278,78 @@ int mlqem_linreg_moments_f32(const float* x, int64_t ldx, const float* y, int64_
 int mlqem_linreg_predict_f32(const float* x, int64_t ldx, int64_t n_rows, int F, const double* coef, const double* intercept,
                              int K, double* out, mlqem_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Exact simulation of small circuits, a batch per call (an additive symbol, the ABI version is unchanged).  Produces the labels the mitigators learn from: ideal expectation
+ * values from a state vector, noisy ones from a density matrix with depolarising and readout ops (the reference gets them from
+ * Aer: blackwater/data/generators/exp_val.py, data/utils.py create_estimator_meas_data).  blackwater.sim lowers circuits to this
+ * format (compile_programs) and blackwater.native.ops.sim_run calls it.
+ *
+ * State.  Complex float64 amplitudes (re, im) in LDS for the whole circuit, starting from |0..0>; nothing of it touches global
+ * memory.  mode 0: an n-qubit state vector, 2^n amplitudes, qubit q = index bit q (qubit 0 the least significant: qiskit's order).
+ * mode 1: an n-qubit density matrix as a 2n-bit vector, 4^n entries, entry rho[r, c] at index r | c << n.
+ * Cap: MLQEM_SIM_MAX_AMPS = 2 048 amplitudes (32 KB of LDS): n <= 11 in mode 0, n <= 5 in mode 1.  There is no global-memory path.
+ *
+ * circ    int32 [n_circuits][4], 16-byte aligned: (n_qubits, mode, r, 0).  The LAST r ops of the circuit are its readout ops:
+ *         norm is taken before them.
+ * op_ptr  int64 [n_circuits + 1]: circuit c owns ops[op_ptr[c] .. op_ptr[c + 1]).
+ * ops     mlqem_sim_op [n_ops], 16-byte aligned: (kind, q0, q1, param).  param is the index of the record's first float64 in
+ *         `params`.  A unitary in mode 1 acts as U on bit q and conj(U) on bit q + n from the ONE record.
+ *           kind                 qubits   params
+ *           MLQEM_SIM_OP_U1      q0       8: a 2x2 complex matrix, row-major, (re, im) per entry
+ *           MLQEM_SIM_OP_DIAG1   q0       4: diag(d0, d1), (re, im) each                    (rz, p, z, s, t and their inverses)
+ *           MLQEM_SIM_OP_CX      q0, q1   -   q0 controls, q1 is flipped
+ *           MLQEM_SIM_OP_CZ      q0, q1   -
+ *           MLQEM_SIM_OP_SWAP    q0, q1   -
+ *           MLQEM_SIM_OP_U2      q0, q1   32: a 4x4 complex matrix, row-major, basis index = bit(q0) + 2 bit(q1)   (ecr, rzz, ...)
+ *           MLQEM_SIM_OP_DEPOL1  q0       1: lambda.  rho -> (1 - lambda) rho + lambda Tr_q0(rho) (x) I/2, in closed form: entries
+ *                                         whose row and column bit of q0 differ scale by 1 - lambda, the others become
+ *                                         (1 - lambda) rho_ii + lambda/2 (rho_00 + rho_11).  Mode 1 only (ignored in mode 0).
+ *           MLQEM_SIM_OP_DEPOL2  q0, q1   1: lambda.  The same over both qubits, I/4 and lambda/4 times the sum of the four diagonal
+ *                                         entries of a 4x4 block.  Mode 1 only.
+ *           MLQEM_SIM_OP_READOUT q0       2: p01 = P(read 0 | prepared 1), p10 = P(read 1 | prepared 0).  The column-stochastic matrix
+ *                                         [[1 - p10, p01], [p10, 1 - p01]] on bit q0 of the DIAGONAL of rho; off-diagonal entries
+ *                                         are meaningless afterwards, so only I/Z terms may follow.  Mode 1 only.
+ *         An unknown kind is skipped.
+ * params  float64 [n_params], n_params >= 32, with 32 values of padding after the last record's (a record's read is clamped to
+ *         [0, n_params - 32]).
+ * term_ptr int64 [n_circuits + 1]; terms mlqem_sim_term [n_terms], 16-byte aligned: (xmask, zmask, ny, 0) of a Pauli string (bit q of
+ *         xmask: X or Y on qubit q; of zmask: Z or Y; ny = the number of Y); coeff float64 [n_terms], the real coefficients.
+ *         With P|j> = i^ny (-1)^popcount(j & zmask) |j ^ xmask>:
+ *           mode 0   <P> = Re sum_j i^ny (-1)^popcount(j & zmask) conj(psi[j ^ xmask]) psi[j]
+ *           mode 1   <P> = Re sum_j i^ny (-1)^popcount(j & zmask) rho[j, j ^ xmask]
+ * ids     int32 [n_wave + n_wg]: the circuits this call simulates.  The first n_wave have at most MLQEM_SIM_WAVE_AMPS = 256
+ *         amplitudes and run a wave per circuit (four circuits per 256-thread workgroup, each wave on its own 4 KB of LDS, no
+ *         workgroup barrier); the other n_wg have 512 .. 2 048 and run a workgroup per circuit (a barrier between passes).  At most
+ *         two launches.  A circuit whose amplitude count exceeds its variant's is simulated with n clamped to what fits.
+ * Outputs, float64: term_values [n_terms]; values [n_circuits] = sum coeff * term value, added in term order by one thread (0.0 for
+ *         a circuit without terms); norm [n_circuits] = <psi|psi> or Tr rho before the readout ops.  Only the entries of the
+ *         circuits in `ids` are written.
+ * Every sum is formed in a fixed order (lane-strided partial sums, a shuffle tree over the 64 lanes, then wave 0 .. 3): no atomics,
+ * and a circuit's results are the same bits alone or in any batch, from call to call.  Every index read from a record is clamped
+ * (qubits to n, offsets to their arrays, masks to n bits, amplitude indices to the state), so a malformed record computes
+ * garbage and faults nothing.  No workspace, no host read: capturable in a hipGraph.
+ * Negative sizes, n_wave + n_wg > n_circuits, n_params < 32, null or misaligned buffers: MLQEM_ERR_BAD_ARG; n_circuits or n_params
+ * over 2^31 - 1: MLQEM_ERR_UNSUPPORTED; all checked before anything is launched.  n_wave + n_wg == 0 returns MLQEM_OK without a
+ * launch.
+ * ---------------------------------------------------------------------------------------------------- */
+#define MLQEM_SIM_WAVE_AMPS 256
+#define MLQEM_SIM_MAX_AMPS 2048
+#define MLQEM_SIM_OP_U1 0
+#define MLQEM_SIM_OP_DIAG1 1
+#define MLQEM_SIM_OP_CX 2
+#define MLQEM_SIM_OP_CZ 3
+#define MLQEM_SIM_OP_SWAP 4
+#define MLQEM_SIM_OP_U2 5
+#define MLQEM_SIM_OP_DEPOL1 6
+#define MLQEM_SIM_OP_DEPOL2 7
+#define MLQEM_SIM_OP_READOUT 8
+typedef struct mlqem_sim_op { int32_t kind; int32_t q0; int32_t q1; int32_t param; } mlqem_sim_op;
+typedef struct mlqem_sim_term { int32_t xmask; int32_t zmask; int32_t ny; int32_t reserved; } mlqem_sim_term;
+int mlqem_sim_run_f64(int64_t n_circuits, const int32_t* circ, const int64_t* op_ptr, const mlqem_sim_op* ops, int64_t n_ops,
+                      const double* params, int64_t n_params, const int64_t* term_ptr, const mlqem_sim_term* terms,
+                      const double* coeff, int64_t n_terms, const int32_t* ids, int64_t n_wave, int64_t n_wg, double* term_values,
+                      double* values, double* norm, mlqem_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,12 +1,14 @@
 """Wire/disk record of one training example (reference: blackwater/data/generators/exp_val.py:31-89).
 
-``exp_value_generator`` of that file runs Aer simulations and is out of scope.
+``exp_value_generator`` of that file (:92-170) runs Aer; here it runs the batched simulator of ``blackwater.sim`` on the device:
+exact ideal values from state vectors, noisy ones from density matrices under the project's own depolarising noise model.
 """
 from __future__ import annotations
 
 from dataclasses import dataclass, asdict
-from typing import Any, Dict, List
+from typing import Any, Dict, Iterator, List
 
+import numpy as np
 import torch
 
 from ..graph import Data
@@ -56,3 +58,48 @@ class ExpValueEntry:
         for k, value in enumerate(self.noisy_exp_values):
             fields[f"noisy_{k}"] = torch.tensor([[value]], dtype=torch.float)
         return Data(**fields)
+
+
+def exp_value_generator(backend: Any, n_qubits: int, circuit_depth: int, pauli_terms: int, pauli_coeff: float = 1.0,
+                        max_entries: int = 1000, seed: int = 0, batch: int = 256, device="cuda") -> Iterator[ExpValueEntry]:
+    """Yields ``max_entries`` dataset entries of random circuits with simulated labels (reference: exp_val.py:92-170, which
+    transpiles ``qiskit.circuit.random.random_circuit`` and runs Aer twice per circuit).
+
+    Circuits: ``synthetic.random_circuit`` on ``n_qubits`` qubits in the backend's basis (its two-qubit gate is taken from the
+    calibration table), depth drawn in 1..``circuit_depth``.  Observable: ``generate_random_pauli_sum_op(n_qubits, pauli_terms,
+    pauli_coeff)``.  ``ideal_exp_value``: the exact value, state-vector mode.  ``noisy_exp_values``: ``[v]`` with v from the
+    density-matrix mode under ``NoiseModel.from_backend(backend, readout=False)`` -- the project's depolarising model, not Aer's.
+    Readout noise is OFF: random Pauli sums contain X and Y, and a readout op leaves only the diagonal of the density matrix
+    meaningful.  ``batch`` circuits are simulated per launch (two launches: ideal, noisy); entries are yielded one by one and are a
+    function of ``seed`` alone."""
+    from ... import sim
+    from ..synthetic import random_circuit
+    from ..utils import circuit_to_graph_data_json, encode_pauli_sum_op, generate_random_pauli_sum_op, get_backend_properties_v1
+
+    properties = get_backend_properties_v1(backend)
+    two_q = [g for g in properties["gates_set"] if g in ("cx", "ecr", "cz")]
+    if len(two_q) != 1:
+        raise ValueError(f"exp_value_generator: want one two-qubit basis gate among cx / ecr / cz, the backend has {two_q}")
+    if batch < 1:
+        raise ValueError(f"exp_value_generator: batch must be >= 1, got {batch}")
+    noise = sim.NoiseModel.from_backend(backend, readout=False)
+    rng = np.random.default_rng(seed)
+    done = 0
+    while done < max_entries:
+        count = min(int(batch), max_entries - done)
+        circuits, observables = [], []
+        for _ in range(count):
+            depth = int(rng.integers(1, circuit_depth + 1))
+            circuits.append(random_circuit(n_qubits, depth, int(rng.integers(0, 2 ** 31 - 1)), two_q=two_q[0]))
+            observables.append(generate_random_pauli_sum_op(n_qubits, pauli_terms, pauli_coeff, rng=rng))
+        ideal = _to_host(sim.expectation_values(circuits, observables, None, device)[0])
+        noisy = _to_host(sim.expectation_values(circuits, observables, noise, device)[0])
+        for k, (circuit, observable) in enumerate(zip(circuits, observables)):
+            graph = circuit_to_graph_data_json(circuit=circuit, properties=properties, use_qubit_features=True, use_gate_features=True)
+            yield ExpValueEntry(circuit_graph=graph, observable=encode_pauli_sum_op(observable), ideal_exp_value=float(ideal[k]),
+                                noisy_exp_values=[float(noisy[k])], circuit_depth=circuit.depth())
+        done += count
+
+
+def _to_host(values) -> np.ndarray:
+    return np.asarray(values.cpu() if hasattr(values, "cpu") else values, dtype=np.float64)

@@ -6,7 +6,8 @@ The circuit STRUCTURE is the reference's Trotterised transverse-field Ising laye
 repeated ``steps`` times, then ``measure_all``.  It is lowered with one fixed rule per gate to the basis
 {rz, sx, x, ecr|cx} so that op counts land near what the reference's transpiled circuits hold (100 qubits:
 ~2.0k ops and 198 two-qubit gates per step; measured there: 1,584 / 8,999 / 20,711 ops at 1 / 6 / 10 steps).
-Labels are synthetic: they only feed the loss and the MAE plumbing.
+Labels are synthetic by default (they only feed the loss and the MAE plumbing); ``encode_corpus(simulate=...)`` fills them with
+simulated values from ``blackwater.sim`` for circuits small enough to simulate exactly.
 """
 from __future__ import annotations
 
@@ -116,8 +117,12 @@ def pauli_twirl(circ: Circuit, seed: int, two_q=("cx", "ecr")) -> Circuit:
 
 
 def encode_corpus(circuits, nq: int, two_q: str = "cx", seed: int = 7, exp_value_size: int = 1,
-                  add_self_loops: bool = True) -> Dict[str, list]:
-    """Arena-ready arrays (same keys as :func:`tfim_corpus`) for arbitrary circuits, encoded by the native encoder."""
+                  add_self_loops: bool = True, simulate=None, device="cuda") -> Dict[str, list]:
+    """Arena-ready arrays (same keys as :func:`tfim_corpus`) for arbitrary circuits, encoded by the native encoder.
+
+    ``simulate=None``: synthetic labels (a uniform draw and a made-up decay).  ``simulate=`` a ``blackwater.sim.NoiseModel``: ``y``
+    and ``noisy`` of every circuit within the simulator's caps (5 qubits as a density matrix) are the exact and the noisy
+    ``<Z>`` of the circuit's observable qubit, simulated on ``device`` in two launches; larger circuits keep the synthetic labels."""
     from .circuit import circuit_to_qasm
     from .native_encoder import NativeEncoder
 
@@ -125,6 +130,7 @@ def encode_corpus(circuits, nq: int, two_q: str = "cx", seed: int = 7, exp_value
     enc = NativeEncoder(props)
     rng = np.random.default_rng(seed)
     xs, eis, ys, noisy, depth, obs = [], [], [], [], [], []
+    kept, z_qubits = [], []
     for circ in circuits:
         x, ei, _, d = enc.encode(circuit_to_qasm(circ))
         if add_self_loops:
@@ -142,6 +148,20 @@ def encode_corpus(circuits, nq: int, two_q: str = "cx", seed: int = 7, exp_value
         qz = int(rng.integers(0, nq))
         o[0, 1 + 4 * qz], o[0, 2 + 4 * qz] = 0.0, 1.0
         obs.append(o)
+        kept.append(circ)
+        z_qubits.append(qz)
+    if simulate is not None:
+        from .. import sim
+
+        inside = [k for k, circ in enumerate(kept) if 1 <= circ.num_qubits <= sim.MAX_QUBITS_DENSITY]
+        if inside:
+            labels = ["".join("Z" if q == z_qubits[k] else "I" for q in reversed(range(kept[k].num_qubits))) for k in inside]
+            batch = [kept[k] for k in inside]
+            exact = sim.expectation_values(batch, labels, None, device)[0].cpu().numpy()
+            under = sim.expectation_values(batch, labels, simulate, device)[0].cpu().numpy()
+            for j, k in enumerate(inside):
+                ys[k] = np.full(exp_value_size, exact[j])
+                noisy[k] = np.full(exp_value_size, under[j])
     return {"x": xs, "edge_index": eis, "y": np.asarray(ys, np.float32), "noisy": np.asarray(noisy, np.float32),
             "depth": np.asarray(depth, np.float32), "observable": np.asarray(obs, np.float32)}
 

@@ -2,8 +2,9 @@
 
 Mirrors the call surface of the reference's blackwater/data/utils.py for the functions on the path:
 ``get_backend_properties_v1`` (:139-175), ``circuit_to_graph_data_json`` (:198-389),
-``encode_pauli_sum_op`` (:447-474) and the legacy ``circuit_to_pyg_data`` (:52-123).  The Aer-backed label
-helpers of that file need a quantum simulator and are out of scope.
+``encode_pauli_sum_op`` (:447-474), ``generate_random_pauli_sum_op`` (:477-491) and the legacy ``circuit_to_pyg_data``
+(:52-123).  What the Aer-backed label helper of that file (``create_estimator_meas_data``) computes comes from
+``blackwater.sim.expectation_values`` on the device.
 
 The reference converts the circuit to a qiskit DAG and lists ``dag.edges()``.  No DAG library is used
 here: because a DAG built by appending ops has, per qubit wire, one chain in -> op -> ... -> op -> out,
@@ -14,7 +15,7 @@ from __future__ import annotations
 
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
-from .backends import pauli_terms
+from .backends import PauliObservable, pauli_terms
 from .circuit import Circuit
 
 ADDITIONAL_GATE_TYPES = ["barrier", "measure"]
@@ -235,3 +236,15 @@ def _op_to_op_edges_all_wires(circ: Circuit) -> List[List[int]]:
                 out_adj[last[w]].append(k)
             last[w] = k
     return [[s, d] for s in range(len(circ.ops)) for d in reversed(out_adj[s])]
+
+
+def generate_random_pauli_sum_op(n_qubits: int, size: int, coeff: Optional[float] = None, rng=None) -> PauliObservable:
+    """``size`` uniformly random Pauli strings on ``n_qubits`` qubits with coefficient ``coeff`` each, or (``coeff`` None or 0, as
+    in the reference) coefficients uniform in [-1, 1) (reference: utils.py:477-491, there with ``random_pauli_list`` and the global
+    numpy state).  ``rng``: a ``numpy.random.Generator`` or a seed; the result is a function of it alone."""
+    import numpy as np
+
+    rng = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
+    coeffs = [float(coeff)] * size if coeff else rng.uniform(-1.0, 1.0, size=size).tolist()
+    letters = rng.integers(0, 4, size=(size, n_qubits))
+    return PauliObservable([("".join("IXYZ"[c] for c in row), c0) for row, c0 in zip(letters, coeffs)])

@@ -2552,3 +2552,51 @@ def linreg_predict(x, coef, intercept, *, out=None):
     code = _lib.load().mlqem_linreg_predict_f32(_p(x), ldx, n, f, _p(coef), _p(intercept), k, _p(out), _stream())
     _lib.check(code, "mlqem_linreg_predict_f32")
     return out
+
+
+SIM_WAVE_AMPS = 256    # MLQEM_SIM_WAVE_AMPS: a wave per circuit up to here
+SIM_MAX_AMPS = 2048    # MLQEM_SIM_MAX_AMPS: a workgroup per circuit up to here; nothing beyond
+SIM_PARAM_PAD = 32     # float64 values of padding the parameter pool ends with
+
+
+def sim_run(circ, op_ptr, ops, params, term_ptr, terms, coeff, ids, n_wave, n_wg, *, term_values=None, values=None, norm=None):
+    """Simulates a batch of lowered circuits (mlqem_sim_run_f64): ``(values, term_values, norm)``, float64 [B], [n_terms], [B].
+
+    ``circ`` int32 [B, 4], ``op_ptr`` int64 [B + 1], ``ops`` int32 [n_ops, 4], ``params`` float64 [>= 32], ``term_ptr`` int64 [B + 1],
+    ``terms`` int32 [n_terms, 4], ``coeff`` float64 [n_terms], ``ids`` int32 [n_wave + n_wg]: the buffers of
+    ``blackwater.sim.SimBatch.to(device)``, in the layout of include/mlqem_hip.h.  ``n_wave`` / ``n_wg``: how many of ``ids`` run a
+    wave / a workgroup per circuit.  Shapes, dtypes and devices are checked here; the CONTENTS are ``compile_programs``' to
+    guarantee (the kernel clamps every index, so a malformed record computes garbage and faults nothing).  Nothing here waits for the
+    device or reads a tensor's contents, and with the three outputs given nothing is allocated: the call can be captured in a
+    hipGraph."""
+    for t, name, dtype, cols in ((circ, "circ", torch.int32, 4), (ops, "ops", torch.int32, 4), (terms, "terms", torch.int32, 4)):
+        if not t.is_cuda:
+            raise _lib.NativeLibraryError(f"{name} must live on the GPU (got {t.device}); there is no CPU path")
+        if t.dtype != dtype or t.dim() != 2 or t.shape[1] != cols or not t.is_contiguous():
+            raise ValueError(f"sim: want contiguous {dtype} {name} [., {cols}], got {tuple(t.shape)} {t.dtype}")
+    b, n_ops, n_terms = int(circ.shape[0]), int(ops.shape[0]), int(terms.shape[0])
+    _vec(op_ptr, "op_ptr", b + 1, torch.int64)
+    _vec(term_ptr, "term_ptr", b + 1, torch.int64)
+    _vec(params, "params", SIM_PARAM_PAD, torch.float64)
+    _vec(coeff, "coeff", n_terms, torch.float64)
+    n_wave, n_wg = int(n_wave), int(n_wg)
+    if n_wave < 0 or n_wg < 0 or n_wave + n_wg > b:
+        raise ValueError(f"sim: n_wave = {n_wave} and n_wg = {n_wg} must be >= 0 and add up to at most {b} circuits")
+    _vec(ids, "ids", n_wave + n_wg, torch.int32)
+    dev = circ.device
+    if any(t.device != dev for t in (op_ptr, ops, params, term_ptr, terms, coeff, ids)):
+        raise ValueError(f"sim: circ is on {dev}, another buffer is not")
+
+    def _out(t, name, n):
+        if t is None:
+            return torch.zeros((n,), dtype=torch.float64, device=dev)
+        if not t.is_cuda or t.device != dev or t.dtype != torch.float64 or tuple(t.shape) != (n,) or not t.is_contiguous():
+            raise ValueError(f"{name}: want contiguous float64 [{n}] on {dev}, got {tuple(t.shape)} {t.dtype} {t.device}")
+        return t
+
+    values, term_values, norm = _out(values, "values", b), _out(term_values, "term_values", n_terms), _out(norm, "norm", b)
+    code = _lib.load().mlqem_sim_run_f64(b, _p(circ), _p(op_ptr), _p(ops) if n_ops else None, n_ops, _p(params), int(params.shape[0]),
+                                         _p(term_ptr), _p(terms) if n_terms else None, _p(coeff) if n_terms else None, n_terms,
+                                         _p(ids), n_wave, n_wg, _p(term_values) if n_terms else None, _p(values), _p(norm), _stream())
+    _lib.check(code, "mlqem_sim_run_f64")
+    return values, term_values, norm

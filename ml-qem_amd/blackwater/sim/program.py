@@ -1,0 +1,358 @@
+"""Host side of the batched simulator: circuits -> the flat programs ``mlqem_sim_run_f64`` runs (include/mlqem_hip.h has the
+record layouts).  Nothing here touches the GPU.
+
+Conventions are qiskit's: qubit 0 is the least significant index bit, and the rightmost character of a Pauli label acts on qubit
+0.  Gate matrices are built with Python's float64 ``math`` functions.  Everything is validated here, before anything is launched:
+the kernel clamps what it reads, but a refused circuit must be refused by name, not simulated as something else.
+"""
+from __future__ import annotations
+
+import cmath
+import math
+from dataclasses import dataclass, field
+from typing import Any, Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from ..data.backends import PauliObservable, pauli_terms
+from ..data.circuit import Circuit
+
+WAVE_AMPS = 256     # MLQEM_SIM_WAVE_AMPS: a wave per circuit
+MAX_AMPS = 2048     # MLQEM_SIM_MAX_AMPS: a workgroup per circuit; the cap
+PARAM_PAD = 32      # float64 values of padding at the end of the parameter pool
+MAX_QUBITS_VECTOR = 11
+MAX_QUBITS_DENSITY = 5
+
+OP_U1, OP_DIAG1, OP_CX, OP_CZ, OP_SWAP, OP_U2, OP_DEPOL1, OP_DEPOL2, OP_READOUT = range(9)   # MLQEM_SIM_OP_*
+
+_N_PARAMS = {"id": 0, "x": 0, "y": 0, "z": 0, "h": 0, "s": 0, "sdg": 0, "t": 0, "tdg": 0, "sx": 0, "sxdg": 0, "rx": 1, "ry": 1,
+             "rz": 1, "p": 1, "u1": 1, "u2": 2, "u3": 3, "u": 3, "cx": 0, "cz": 0, "swap": 0, "ecr": 0, "rzz": 1}
+_TWO_QUBIT = {"cx", "cz", "swap", "ecr", "rzz"}
+SUPPORTED_GATES = tuple(_N_PARAMS)
+
+_R = math.sqrt(0.5)
+
+
+def _u3(theta: float, phi: float, lam: float) -> List[complex]:
+    c, s = math.cos(theta / 2), math.sin(theta / 2)
+    return [c, -cmath.exp(1j * lam) * s, cmath.exp(1j * phi) * s, cmath.exp(1j * (phi + lam)) * c]
+
+
+def _one_qubit(name: str, p: Tuple[float, ...]):
+    """(kind, complex entries): two phases for a diagonal gate, a row-major 2x2 matrix otherwise; None for ``id``."""
+    if name == "id":
+        return None
+    if name == "z":
+        return OP_DIAG1, [1.0, -1.0]
+    if name == "s":
+        return OP_DIAG1, [1.0, 1j]
+    if name == "sdg":
+        return OP_DIAG1, [1.0, -1j]
+    if name == "t":
+        return OP_DIAG1, [1.0, cmath.exp(0.25j * math.pi)]
+    if name == "tdg":
+        return OP_DIAG1, [1.0, cmath.exp(-0.25j * math.pi)]
+    if name == "rz":
+        return OP_DIAG1, [cmath.exp(-0.5j * p[0]), cmath.exp(0.5j * p[0])]
+    if name in ("p", "u1"):
+        return OP_DIAG1, [1.0, cmath.exp(1j * p[0])]
+    if name == "x":
+        return OP_U1, [0.0, 1.0, 1.0, 0.0]
+    if name == "y":
+        return OP_U1, [0.0, -1j, 1j, 0.0]
+    if name == "h":
+        return OP_U1, [_R, _R, _R, -_R]
+    if name == "sx":
+        return OP_U1, [0.5 + 0.5j, 0.5 - 0.5j, 0.5 - 0.5j, 0.5 + 0.5j]
+    if name == "sxdg":
+        return OP_U1, [0.5 - 0.5j, 0.5 + 0.5j, 0.5 + 0.5j, 0.5 - 0.5j]
+    if name == "rx":
+        c, s = math.cos(p[0] / 2), math.sin(p[0] / 2)
+        return OP_U1, [c, -1j * s, -1j * s, c]
+    if name == "ry":
+        c, s = math.cos(p[0] / 2), math.sin(p[0] / 2)
+        return OP_U1, [c, -s, s, c]
+    if name == "u2":
+        return OP_U1, _u3(math.pi / 2, p[0], p[1])
+    return OP_U1, _u3(p[0], p[1], p[2])   # u3, u
+
+
+def _two_qubit(name: str, p: Tuple[float, ...]):
+    """(kind, complex entries of a row-major 4x4 matrix over the basis index bit(q0) + 2 bit(q1), or [])."""
+    if name == "cx":
+        return OP_CX, []
+    if name == "cz":
+        return OP_CZ, []
+    if name == "swap":
+        return OP_SWAP, []
+    if name == "ecr":   # (IX - XY) / sqrt(2), the left factor on q1
+        r = _R
+        return OP_U2, [0, r, 0, 1j * r, r, 0, -1j * r, 0, 0, 1j * r, 0, r, -1j * r, 0, r, 0]
+    a, b = cmath.exp(-0.5j * p[0]), cmath.exp(0.5j * p[0])   # rzz
+    return OP_U2, [a, 0, 0, 0, 0, b, 0, 0, 0, 0, b, 0, 0, 0, 0, a]
+
+
+class NoiseModel:
+    """The project's OWN noise model for the density-matrix mode: a depolarising op after a gate and a readout op per measured
+    qubit.  It is NOT Aer's ``NoiseModel.from_backend``: no thermal relaxation, no gate times, no T1/T2 -- so the ``noisy``
+    arrays that the reference's datasets hold (made with Aer) are not reproduced by it.
+
+    ``gate_lambda``: ``{(name, (qubits...)): lambda}``, the depolarising parameter of
+    ``rho -> (1 - lambda) rho + lambda Tr_S(rho) (x) I/d`` applied after every such gate on its qubits S (d = 2 or 4);
+    ``readout``: ``{qubit: (p01, p10)}`` with p01 = P(read 0 | prepared 1) and p10 = P(read 1 | prepared 0).  Qubits are
+    indices inside their register (``Circuit.qubit_reg_index``), as calibration tables count them.  An empty model is the
+    noiseless density-matrix mode.  Subclasses may override :meth:`after_gate` / :meth:`readout_of`."""
+
+    def __init__(self, gate_lambda: Optional[Dict[Tuple[str, Tuple[int, ...]], float]] = None,
+                 readout: Optional[Dict[int, Tuple[float, float]]] = None, strict_two_qubit: bool = False, name: str = "custom"):
+        self.gate_lambda = dict(gate_lambda or {})
+        self.readout = dict(readout or {})
+        self.strict_two_qubit = bool(strict_two_qubit)
+        self.name = name
+        for key, lam in self.gate_lambda.items():
+            if not (math.isfinite(lam) and 0.0 <= lam <= 1.0):
+                raise ValueError(f"NoiseModel: depolarising parameter of {key} is {lam!r}, want 0 <= lambda <= 1")
+        for q, (p01, p10) in self.readout.items():
+            if not all(math.isfinite(v) and 0.0 <= v <= 1.0 for v in (p01, p10)):
+                raise ValueError(f"NoiseModel: readout probabilities of qubit {q} are {(p01, p10)!r}, want both in [0, 1]")
+
+    def after_gate(self, index: int, name: str, qubits: Tuple[int, ...]) -> Optional[float]:
+        """lambda of the depolarising op after op ``index`` (``name`` on register qubits ``qubits``), or None for none."""
+        lam = self.gate_lambda.get((name, tuple(qubits)))
+        if lam is None and self.strict_two_qubit and len(qubits) == 2:
+            raise ValueError(f"noise model {self.name!r} has no calibration entry for {name} on the qubit pair {tuple(qubits)}")
+        return lam if lam else None
+
+    def readout_of(self, qubit: int) -> Optional[Tuple[float, float]]:
+        return self.readout.get(qubit)
+
+    @property
+    def has_readout(self) -> bool:
+        return bool(self.readout)
+
+    @staticmethod
+    def from_backend(backend: Any, readout: bool = True) -> "NoiseModel":
+        """From the calibration table the data layer reads (``backend.properties()``): after every gate (name, qubits) with a
+        ``gate_error`` e > 0 a depolarising op with ``lambda = e d / (d - 1)`` (d = 2, 4: the relation between the average gate
+        infidelity and the depolarising parameter, so lambda = 2 e and 4 e / 3); per measured qubit a readout op from
+        ``prob_meas0_prep1`` / ``prob_meas1_prep0``, or from a symmetric ``readout_error`` when those are missing.  A two-qubit
+        gate without a calibration entry is refused when a circuit uses it.  Again: this is not Aer's model of the same name."""
+        props = backend.properties()
+        lam: Dict[Tuple[str, Tuple[int, ...]], float] = {}
+        for gate in props.gates:
+            qubits = tuple(int(q) for q in gate.qubits)
+            if len(qubits) not in (1, 2):
+                continue
+            err = next((float(p.value) for p in gate.parameters if p.name == "gate_error"), None)
+            if err is None:
+                continue
+            d = 2 ** len(qubits)
+            value = err * d / (d - 1)
+            if not (math.isfinite(value) and 0.0 <= value <= 1.0):
+                raise ValueError(f"NoiseModel.from_backend: gate_error {err!r} of {gate.gate} on {qubits} gives lambda = {value!r}, "
+                                 "want 0 <= lambda <= 1")
+            lam[(str(gate.gate), qubits)] = value
+        ro: Dict[int, Tuple[float, float]] = {}
+        if readout:
+            for q in range(len(props.qubits)):
+                qp = props.qubit_property(q)
+                sym = qp.get("readout_error", (0.0, None))[0]
+                p01 = qp.get("prob_meas0_prep1", (sym, None))[0]
+                p10 = qp.get("prob_meas1_prep0", (sym, None))[0]
+                ro[q] = (float(p01), float(p10))
+        name = backend.name() if callable(getattr(backend, "name", None)) else getattr(backend, "name", "backend")
+        return NoiseModel(lam, ro, strict_two_qubit=True, name=str(name))
+
+
+@dataclass
+class SimBatch:
+    """A lowered batch: the host arrays of ``mlqem_sim_run_f64`` plus what the host knows about every circuit."""
+
+    circ: np.ndarray        # int32 [B, 4]: n_qubits, mode (0 vector, 1 density), trailing readout ops, 0
+    op_ptr: np.ndarray      # int64 [B + 1]
+    ops: np.ndarray         # int32 [n_ops, 4]: kind, q0, q1, offset into params
+    params: np.ndarray      # float64 [n_params + 32]
+    term_ptr: np.ndarray    # int64 [B + 1]
+    terms: np.ndarray       # int32 [n_terms, 4]: xmask, zmask, number of Y, 0
+    coeff: np.ndarray       # float64 [n_terms]
+    ids: np.ndarray         # int32 [B]: the wave-per-circuit circuits first, then the workgroup-per-circuit ones
+    n_wave: int
+    n_wg: int
+    variant: List[str] = field(default_factory=list)            # "wave" | "workgroup" per circuit
+    measured: List[Dict[int, int]] = field(default_factory=list)   # classical bit -> qubit per circuit
+
+    def __len__(self) -> int:
+        return int(self.circ.shape[0])
+
+    @property
+    def op_counts(self) -> np.ndarray:
+        return np.diff(self.op_ptr)
+
+    def to(self, device) -> Dict[str, Any]:
+        """The arrays as tensors on ``device``, keyed as ``ops.sim_run`` names them."""
+        import torch
+
+        dev = torch.device(device)
+        out = {k: torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(dev)
+               for k in ("circ", "op_ptr", "ops", "params", "term_ptr", "terms", "coeff", "ids")}
+        out["n_wave"], out["n_wg"] = self.n_wave, self.n_wg
+        return out
+
+
+def _lower_terms(observable: Any, n: int, where: str):
+    rows, coeffs, has_xy = [], [], False
+    for label, coeff in pauli_terms(observable):
+        if len(label) != n:
+            raise ValueError(f"{where}: Pauli label {label!r} has {len(label)} characters, the circuit has {n} qubits")
+        c = complex(coeff)
+        if c.imag != 0.0 or not math.isfinite(c.real):
+            raise ValueError(f"{where}: coefficient {coeff!r} of {label!r} is not a finite real number")
+        xm = zm = ny = 0
+        for q, ch in enumerate(reversed(label)):
+            if ch == "X":
+                xm |= 1 << q
+            elif ch == "Z":
+                zm |= 1 << q
+            elif ch == "Y":
+                xm |= 1 << q
+                zm |= 1 << q
+                ny += 1
+            elif ch != "I":
+                raise ValueError(f"{where}: Pauli label {label!r} has the character {ch!r}, want only I, X, Y, Z")
+        has_xy = has_xy or xm != 0
+        rows.append((xm, zm, ny, 0))
+        coeffs.append(c.real)
+    return rows, coeffs, has_xy
+
+
+def compile_programs(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None) -> SimBatch:
+    """Lowers ``circuits`` (anything ``Circuit.from_any`` takes) with one observable each (anything ``pauli_terms`` takes) to one
+    :class:`SimBatch`.  ``noise=None``: state vectors (at most 11 qubits); a :class:`NoiseModel`: density matrices (at most 5
+    qubits) with its depolarising and readout ops.
+
+    Lowered: ``id x y z h s sdg t tdg sx sxdg rx ry rz p u1 u2 u3 u cx cz swap ecr rzz``; ``barrier`` is ignored; ``measure``
+    records classical bit -> qubit (and gets the qubit's readout op, after every other op).  Raises ``ValueError`` naming the
+    offender for: any other gate (opaque custom gates and ``reset`` included), a wrong parameter count, a gate on a qubit after
+    it was measured, a qubit index out of range, a two-qubit gate on one qubit twice, a non-finite angle, a Pauli label of the
+    wrong length or alphabet, a coefficient that is not real, a circuit over the amplitude cap of its mode, and readout noise
+    together with a term that contains X or Y (a readout op leaves only the diagonal of rho meaningful)."""
+    circuits, observables = list(circuits), list(observables)
+    if len(circuits) != len(observables):
+        raise ValueError(f"compile_programs: {len(circuits)} circuits but {len(observables)} observables")
+    density = noise is not None
+    cap_q = MAX_QUBITS_DENSITY if density else MAX_QUBITS_VECTOR
+    circ_rows, ops, params, op_ptr, term_rows, coeffs, term_ptr = [], [], [], [0], [], [], [0]
+    variant, measured_all = [], []
+
+    def emit(kind, q0, q1, values):
+        ops.append((kind, q0, q1, len(params)))
+        params.extend(values)
+
+    def emit_complex(kind, q0, q1, entries):
+        flat = []
+        for e in entries:
+            e = complex(e)
+            flat += [e.real, e.imag]
+        emit(kind, q0, q1, flat)
+
+    for k, (obj, obs) in enumerate(zip(circuits, observables)):
+        circ = Circuit.from_any(obj)
+        where = f"circuit {k}"
+        n = circ.num_qubits
+        amps = 4 ** n if density else 2 ** n
+        if n < 1 or amps > MAX_AMPS:
+            raise ValueError(f"{where}: {n} qubits need {amps} amplitudes as a {'density matrix' if density else 'state vector'}; "
+                             f"the cap is {MAX_AMPS} amplitudes ({cap_q} qubits in this mode) and at least 1 qubit")
+        measured: Dict[int, int] = {}
+        done = set()
+        for i, op in enumerate(circ.ops):
+            name = op.name
+            if name == "barrier":
+                continue
+            for q in op.qubits:
+                if not 0 <= q < n:
+                    raise ValueError(f"{where}: op {i} ({name}) acts on qubit {q}, the circuit has {n}")
+                if q in done:
+                    raise ValueError(f"{where}: op {i} ({name}) acts on qubit {q} after it was measured")
+            if name == "measure":
+                if len(op.qubits) != 1 or len(op.clbits) != 1:
+                    raise ValueError(f"{where}: op {i} (measure) wants one qubit and one classical bit")
+                measured[int(op.clbits[0])] = int(op.qubits[0])
+                done.add(op.qubits[0])
+                continue
+            if name not in _N_PARAMS:
+                raise ValueError(f"{where}: op {i} is {name!r}, which is not simulated (supported: {' '.join(SUPPORTED_GATES)})")
+            width = 2 if name in _TWO_QUBIT else 1
+            if len(op.qubits) != width or len(op.params) != _N_PARAMS[name]:
+                raise ValueError(f"{where}: op {i} ({name}) has {len(op.qubits)} qubits and {len(op.params)} parameters, want "
+                                 f"{width} and {_N_PARAMS[name]}")
+            p = tuple(float(v) for v in op.params)
+            if not all(math.isfinite(v) for v in p):
+                raise ValueError(f"{where}: op {i} ({name}) has the non-finite angle {p!r}")
+            if width == 2:
+                q0, q1 = op.qubits
+                if q0 == q1:
+                    raise ValueError(f"{where}: op {i} ({name}) names qubit {q0} twice")
+                kind, entries = _two_qubit(name, p)
+                emit_complex(kind, q0, q1, entries)
+            else:
+                q0, q1 = op.qubits[0], 0
+                lowered = _one_qubit(name, p)
+                if lowered is not None:
+                    emit_complex(lowered[0], q0, 0, lowered[1])
+            if density:
+                lam = noise.after_gate(i, name, tuple(circ.qubit_reg_index[q] for q in op.qubits))
+                if lam is not None:
+                    if not (math.isfinite(lam) and 0.0 <= lam <= 1.0):
+                        raise ValueError(f"{where}: op {i} ({name}): depolarising parameter {lam!r}, want 0 <= lambda <= 1")
+                    emit(OP_DEPOL2 if width == 2 else OP_DEPOL1, q0, q1, [float(lam)])
+        rows, cs, has_xy = _lower_terms(obs, n, where)
+        n_readout = 0
+        if density:
+            for q in sorted(set(measured.values())):
+                pr = noise.readout_of(circ.qubit_reg_index[q])
+                if pr is None:
+                    continue
+                if has_xy:
+                    raise ValueError(f"{where}: readout noise on qubit {q} cannot be combined with an observable that has X or Y "
+                                     "terms (a readout op leaves only the diagonal of the density matrix meaningful)")
+                emit(OP_READOUT, q, 0, [float(pr[0]), float(pr[1])])
+                n_readout += 1
+        circ_rows.append((n, 1 if density else 0, n_readout, 0))
+        op_ptr.append(len(ops))
+        term_rows += rows
+        coeffs += cs
+        term_ptr.append(len(term_rows))
+        variant.append("wave" if amps <= WAVE_AMPS else "workgroup")
+        measured_all.append(measured)
+
+    if len(params) + PARAM_PAD > 2 ** 31 - 1:
+        raise ValueError(f"compile_programs: {len(params)} gate parameters exceed the 2^31 - 1 a record can address; split the batch")
+    wave = [i for i, v in enumerate(variant) if v == "wave"]
+    wg = [i for i, v in enumerate(variant) if v != "wave"]
+    return SimBatch(
+        circ=np.asarray(circ_rows, dtype=np.int32).reshape(-1, 4),
+        op_ptr=np.asarray(op_ptr, dtype=np.int64),
+        ops=np.asarray(ops, dtype=np.int32).reshape(-1, 4),
+        params=np.asarray(params + [0.0] * PARAM_PAD, dtype=np.float64),
+        term_ptr=np.asarray(term_ptr, dtype=np.int64),
+        terms=np.asarray(term_rows, dtype=np.int32).reshape(-1, 4),
+        coeff=np.asarray(coeffs, dtype=np.float64),
+        ids=np.asarray(wave + wg, dtype=np.int32),
+        n_wave=len(wave), n_wg=len(wg), variant=variant, measured=measured_all)
+
+
+def measured_z(circuit: Any) -> PauliObservable:
+    """One single-Z term per classical bit, in classical-bit order: term k is Z on the qubit measured into classical bit k (what
+    the Ising datasets measure; their stored columns are ``-<Z>`` of classical bit 3 - k)."""
+    circ = Circuit.from_any(circuit)
+    where: Dict[int, int] = {}
+    for op in circ.ops:
+        if op.name == "measure":
+            where[int(op.clbits[0])] = int(op.qubits[0])
+    terms = []
+    for c in sorted(where):
+        label = ["I"] * circ.num_qubits
+        label[circ.num_qubits - 1 - where[c]] = "Z"
+        terms.append(("".join(label), 1.0))
+    return PauliObservable(terms)

@@ -1,0 +1,372 @@
+// Exact simulation of small circuits, a batch per launch (mlqem_sim_run_f64).  include/mlqem_hip.h has the contract and the record
+// layouts.
+//
+// A circuit's state lives in LDS from |0..0> to its last expectation value and never touches global memory: complex float64
+// amplitudes (re, im), either an n-qubit state vector (2^n entries) or an n-qubit density matrix kept as a 2n-bit vector (4^n entries,
+// index = row | col << n).  One code path serves both: an op acts on `nbits` index bits, and in density mode a unitary U on qubit q is
+// U on bit q followed by conj(U) on bit q + n, both from the one record.
+//
+// Two instantiations.  WG = false: a wave per circuit, four circuits per 256-thread workgroup, each wave owning a 4 KB slice (256
+// amplitudes: 8-qubit vectors, 4-qubit density matrices).  The op loops of the four waves have different trip counts, so nothing in
+// this variant is a workgroup barrier: a pass ends with a wavefront fence (LDS instructions of one wave execute in issue order; the
+// fence only keeps the compiler from moving them).  WG = true: a workgroup per circuit, 2 048 amplitudes = 32 KB (11-qubit vectors,
+// 5-qubit density matrices), a barrier after every pass.
+//
+// Passes.  Every op is one or two passes over the state; within a pass a thread owns disjoint entries, so passes need no ordering
+// inside.  Loads are unconditional on clamped indices (every index is also masked to the amplitude count, so a malformed record
+// computes garbage and faults nothing); only stores are predicated; trip counts depend on the amplitude count alone.
+//   pair       a 2x2 matrix on bit b: entries (i, i | 1 << b)                        general one-qubit gates, readout (on the diagonal)
+//   element    entry i times a factor of its own bits                                diagonal one-qubit gates, cz
+//   gather     v = state[perm(i)], fence, state[i] = v                               cx, swap (row and column bits in one go)
+//   quad       a 4x4 matrix on bits (a, b); the one-qubit depolarising map on (q, q + n)
+//   hex        the two-qubit depolarising map on (a, b, a + n, b + n): 16 entries, closed form
+// Expectation values are reduced in a fixed order: lane-strided partial sums, a shuffle tree, then the waves in order through LDS.
+#include "common.hpp"
+
+namespace mlqem {
+namespace {
+
+constexpr int kSimWaveAmps = MLQEM_SIM_WAVE_AMPS;   // 256: a wave's slice
+constexpr int kSimMaxAmps = MLQEM_SIM_MAX_AMPS;     // 2048: a workgroup's state, 32 KB
+constexpr int kSimParamPad = 32;                    // doubles the longest record reads (a 4x4 complex matrix)
+
+typedef double sim_c __attribute__((ext_vector_type(2)));   // (re, im): one 16-byte LDS access
+typedef int sim_i4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ sim_c cmul(sim_c a, sim_c b) { return sim_c{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
+__device__ __forceinline__ sim_c cmac(sim_c acc, sim_c a, sim_c b) {
+  return sim_c{acc.x + (a.x * b.x - a.y * b.y), acc.y + (a.x * b.y + a.y * b.x)};
+}
+// index g with a zero bit inserted at position b
+__device__ __forceinline__ int insert0(int g, int b) { return ((g >> b) << (b + 1)) | (g & ((1 << b) - 1)); }
+
+template <bool WG> __device__ __forceinline__ void sim_sync() {
+  if (WG) {
+    __syncthreads();
+  } else {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
+}
+
+__device__ __forceinline__ double sim_wave_sum(double v) {
+#pragma unroll
+  for (int d = kWave / 2; d >= 1; d >>= 1) v = v + __shfl_down(v, d, kWave);
+  return v;
+}
+
+template <bool WG> struct SimCtx {
+  static constexpr int T = WG ? kBlock : kWave;   // threads on one circuit
+  sim_c* st;
+  double* red;   // [2][4] wave sums of the workgroup variant
+  int tid, nbits, A;
+
+  // a 2x2 matrix on bit b of the first `bits` index bits; the entry of index i sits at i * mul, which lets the readout op walk the
+  // diagonal of a density matrix (mul = 1 + 2^n) with the same code
+  __device__ __forceinline__ void pair(int bits, int b, sim_c m00, sim_c m01, sim_c m10, sim_c m11, int mul) {
+    const int np = (1 << bits) >> 1;
+    for (int p0 = 0; p0 < np; p0 += T) {
+      const int p = p0 + tid;
+      const bool live = p < np;
+      const int i0 = (insert0(min(p, np - 1), b) * mul) & (A - 1), i1 = (i0 | ((1 << b) * mul)) & (A - 1);
+      const sim_c a0 = st[i0], a1 = st[i1];
+      const sim_c r0 = cmac(cmul(m00, a0), m01, a1), r1 = cmac(cmul(m10, a0), m11, a1);
+      if (live) {
+        st[i0] = r0;
+        st[i1] = r1;
+      }
+    }
+    sim_sync<WG>();
+  }
+
+  // a 4x4 matrix on bits (a, b), basis index = bit a + 2 bit b
+  __device__ __forceinline__ void quad(int a, int b, const double* m, bool conj) {
+    const double s = conj ? -1.0 : 1.0;
+    const int lo = min(a, b), hi = max(a, b), ng = A >> 2;
+    for (int g0 = 0; g0 < ng; g0 += T) {
+      const int g = g0 + tid;
+      const bool live = g < ng;
+      const int base = insert0(insert0(min(g, ng - 1), lo), hi);
+      int idx[4];
+      sim_c e[4], r[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        idx[k] = (base | ((k & 1) << a) | ((k >> 1) << b)) & (A - 1);
+        e[k] = st[idx[k]];
+      }
+#pragma unroll
+      for (int row = 0; row < 4; ++row) {
+        r[row] = cmul(sim_c{m[8 * row], s * m[8 * row + 1]}, e[0]);
+#pragma unroll
+        for (int col = 1; col < 4; ++col) r[row] = cmac(r[row], sim_c{m[8 * row + 2 * col], s * m[8 * row + 2 * col + 1]}, e[col]);
+      }
+      if (live) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) st[idx[k]] = r[k];
+      }
+    }
+    sim_sync<WG>();
+  }
+
+  // entry i times f(i)
+  template <class F> __device__ __forceinline__ void element(F&& factor) {
+    for (int i0 = 0; i0 < A; i0 += T) {
+      const int i = i0 + tid;
+      const bool live = i < A;
+      const int ic = i & (A - 1);
+      const sim_c v = cmul(st[ic], factor(ic));
+      if (live) st[ic] = v;
+    }
+    sim_sync<WG>();
+  }
+
+  // state[i] = old state[perm(i)]
+  template <class F> __device__ __forceinline__ void gather(F&& perm) {
+    constexpr int kMax = (WG ? kSimMaxAmps : kSimWaveAmps) / T;
+    sim_c v[kMax];
+#pragma unroll
+    for (int k = 0; k < kMax; ++k) v[k] = st[perm((k * T + tid) & (A - 1)) & (A - 1)];
+    sim_sync<WG>();
+#pragma unroll
+    for (int k = 0; k < kMax; ++k)
+      if (k * T + tid < A) st[k * T + tid] = v[k];
+    sim_sync<WG>();
+  }
+
+  // rho -> (1 - lam) rho + lam Tr_q(rho) (x) I/2 on qubit q of an n-qubit density matrix
+  __device__ __forceinline__ void depol1(int n, int q, double lam) {
+    const int ng = A >> 2, cb = q + n;
+    const double keep = 1.0 - lam, mix = 0.5 * lam;
+    for (int g0 = 0; g0 < ng; g0 += T) {
+      const int g = g0 + tid;
+      const bool live = g < ng;
+      const int base = insert0(insert0(min(g, ng - 1), q), cb);
+      const int i00 = base & (A - 1), i10 = (base | (1 << q)) & (A - 1), i01 = (base | (1 << cb)) & (A - 1),
+                i11 = (base | (1 << q) | (1 << cb)) & (A - 1);
+      const sim_c e00 = st[i00], e10 = st[i10], e01 = st[i01], e11 = st[i11];
+      const sim_c tr = e00 + e11;
+      if (live) {
+        st[i00] = keep * e00 + mix * tr;
+        st[i10] = keep * e10;
+        st[i01] = keep * e01;
+        st[i11] = keep * e11 + mix * tr;
+      }
+    }
+    sim_sync<WG>();
+  }
+
+  // the same over the pair (a, b): 4 x 4 blocks, the four diagonal entries share their sum
+  __device__ __forceinline__ void depol2(int n, int a, int b, double lam) {
+    const int lo = min(a, b), hi = max(a, b), ng = A >> 4;
+    const double keep = 1.0 - lam, mix = 0.25 * lam;
+    for (int g0 = 0; g0 < ng; g0 += T) {
+      const int g = g0 + tid;
+      const bool live = g < ng;
+      const int base = insert0(insert0(insert0(insert0(min(g, max(ng - 1, 0)), lo), hi), lo + n), hi + n);
+      int idx[16];
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        const int r = k & 3, c = k >> 2;
+        idx[k] = (base | ((r & 1) << lo) | ((r >> 1) << hi) | ((c & 1) << (lo + n)) | ((c >> 1) << (hi + n))) & (A - 1);
+      }
+      const sim_c tr = ((st[idx[0]] + st[idx[5]]) + st[idx[10]]) + st[idx[15]];
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        sim_c v = keep * st[idx[k]];
+        if ((k & 3) == (k >> 2)) v = v + mix * tr;
+        if (live) st[idx[k]] = v;
+      }
+    }
+    sim_sync<WG>();
+  }
+
+  // fixed-order sum of one double per thread: a shuffle tree, then wave 0 .. 3 in order.  Thread 0 holds the result (every thread of
+  // the workgroup variant does).  `slot` alternates between two sets of wave sums, so one barrier per reduction is enough.
+  __device__ __forceinline__ double reduce(double part, int slot) {
+    const double w = sim_wave_sum(part);
+    if (!WG) return w;
+    if ((tid & (kWave - 1)) == 0) red[slot * 4 + (tid >> 6)] = w;
+    __syncthreads();
+    return ((red[slot * 4] + red[slot * 4 + 1]) + red[slot * 4 + 2]) + red[slot * 4 + 3];
+  }
+};
+
+template <bool WG>
+__global__ __launch_bounds__(kBlock) void sim_kernel(int B, const sim_i4* __restrict__ circ, const int64_t* __restrict__ op_ptr,
+                                                     const sim_i4* __restrict__ ops, int64_t n_ops,
+                                                     const double* __restrict__ params, int64_t n_params,
+                                                     const int64_t* __restrict__ term_ptr, const sim_i4* __restrict__ terms,
+                                                     const double* __restrict__ coeff, int64_t n_terms,
+                                                     const int32_t* __restrict__ ids, int count, double* __restrict__ term_values,
+                                                     double* __restrict__ values, double* __restrict__ norm) {
+  __shared__ sim_c state[WG ? kSimMaxAmps : kBlock / kWave * kSimWaveAmps];
+  __shared__ double red[8];
+  SimCtx<WG> cx;
+  const int slot = WG ? (int)blockIdx.x : __builtin_amdgcn_readfirstlane((int)blockIdx.x * (kBlock / kWave) + ((int)threadIdx.x >> 6));
+  if (slot >= count) return;   // a wave of a partly filled workgroup: wave-uniform, and this variant has no workgroup barrier
+  cx.tid = WG ? (int)threadIdx.x : (int)threadIdx.x & (kWave - 1);
+  cx.st = WG ? state : state + ((int)threadIdx.x >> 6) * kSimWaveAmps;
+  cx.red = red;
+  const int tid = cx.tid;
+  const int c = __builtin_amdgcn_readfirstlane(min(max(ids[slot], 0), B - 1));
+  const sim_i4 info = circ[c];   // n_qubits, mode, trailing readout ops, reserved
+  const bool density = info.y != 0;
+  constexpr int kMaxBits = WG ? 11 : 8;
+  const int n = __builtin_amdgcn_readfirstlane(min(max(info.x, 1), density ? kMaxBits / 2 : kMaxBits));
+  const int nbits = density ? 2 * n : n, A = 1 << nbits;
+  cx.nbits = nbits;
+  cx.A = A;
+  const int64_t ob = min(max(op_ptr[c], (int64_t)0), n_ops), oe = min(max(op_ptr[c + 1], ob), n_ops);
+  const int n_op = __builtin_amdgcn_readfirstlane((int)min(oe - ob, (int64_t)0x7FFFFFFF));
+  const int n_main = n_op - min(max(info.z, 0), n_op);   // ops before the readout ops: Tr rho is taken there
+
+  for (int i = tid; i < A; i += cx.T) cx.st[i] = sim_c{i == 0 ? 1.0 : 0.0, 0.0};
+  sim_sync<WG>();
+
+  double nrm = 0.0;
+  for (int k = 0; k <= n_op; ++k) {
+    if (k == n_main) {   // <psi|psi> or Tr rho, before any readout op
+      double part = 0.0;
+      const int cnt = density ? 1 << n : A, mul = density ? (1 << n) + 1 : 1;
+      for (int i0 = 0; i0 < cnt; i0 += cx.T) {
+        const int i = i0 + tid;
+        const sim_c v = cx.st[((i & (cnt - 1)) * mul) & (A - 1)];
+        const double add = density ? v.x : v.x * v.x + v.y * v.y;
+        part = part + (i < cnt ? add : 0.0);
+      }
+      nrm = cx.reduce(part, 0);
+      if (WG) __syncthreads();   // red[0..3] is free again
+    }
+    if (k == n_op) break;
+    const sim_i4 op = ops[ob + k];   // kind, q0, q1, offset into params
+    const int kind = __builtin_amdgcn_readfirstlane(op.x);
+    const int q0 = __builtin_amdgcn_readfirstlane(min(max(op.y, 0), n - 1)), q1 = __builtin_amdgcn_readfirstlane(min(max(op.z, 0), n - 1));
+    const int64_t po = min((int64_t)max(op.w, 0), n_params - kSimParamPad);
+    const double* m = params + po;
+    switch (kind) {
+      case MLQEM_SIM_OP_U1:
+        cx.pair(nbits, q0, sim_c{m[0], m[1]}, sim_c{m[2], m[3]}, sim_c{m[4], m[5]}, sim_c{m[6], m[7]}, 1);
+        if (density) cx.pair(nbits, q0 + n, sim_c{m[0], -m[1]}, sim_c{m[2], -m[3]}, sim_c{m[4], -m[5]}, sim_c{m[6], -m[7]}, 1);
+        break;
+      case MLQEM_SIM_OP_DIAG1: {
+        const sim_c d0{m[0], m[1]}, d1{m[2], m[3]};
+        if (density) {
+          cx.element([&](int i) {   // d[row bit] conj(d[column bit])
+            const bool r = (i >> q0) & 1, cc = (i >> (q0 + n)) & 1;
+            return cmul(sim_c{r ? d1.x : d0.x, r ? d1.y : d0.y}, sim_c{cc ? d1.x : d0.x, cc ? -d1.y : -d0.y});
+          });
+        } else {
+          cx.element([&](int i) { return (i >> q0) & 1 ? d1 : d0; });
+        }
+        break;
+      }
+      case MLQEM_SIM_OP_CZ: {
+        const int mrow = (1 << q0) | (1 << q1), mcol = density ? mrow << n : 0;
+        cx.element([&](int i) {
+          const bool neg = ((i & mrow) == mrow) != (density && (i & mcol) == mcol);
+          return sim_c{neg ? -1.0 : 1.0, 0.0};
+        });
+        break;
+      }
+      case MLQEM_SIM_OP_CX:
+        cx.gather([&](int i) {
+          int j = i ^ (((i >> q0) & 1) << q1);
+          if (density) j ^= ((i >> (q0 + n)) & 1) << (q1 + n);
+          return j;
+        });
+        break;
+      case MLQEM_SIM_OP_SWAP:
+        cx.gather([&](int i) {
+          int j = i ^ ((((i >> q0) ^ (i >> q1)) & 1) * ((1 << q0) | (1 << q1)));
+          if (density) j ^= (((i >> (q0 + n)) ^ (i >> (q1 + n))) & 1) * (((1 << q0) | (1 << q1)) << n);
+          return j;
+        });
+        break;
+      case MLQEM_SIM_OP_U2:
+        cx.quad(q0, q1, m, false);
+        if (density) cx.quad(q0 + n, q1 + n, m, true);
+        break;
+      case MLQEM_SIM_OP_DEPOL1:
+        if (density) cx.depol1(n, q0, m[0]);
+        break;
+      case MLQEM_SIM_OP_DEPOL2:
+        if (density) cx.depol2(n, q0, q1, m[0]);
+        break;
+      case MLQEM_SIM_OP_READOUT:
+        if (density)   // [[1 - p10, p01], [p10, 1 - p01]] on bit q0 of the diagonal; m = (p01, p10)
+          cx.pair(n, q0, sim_c{1.0 - m[1], 0.0}, sim_c{m[0], 0.0}, sim_c{m[1], 0.0}, sim_c{1.0 - m[0], 0.0}, (1 << n) + 1);
+        break;
+      default:
+        break;
+    }
+  }
+
+  // Pauli terms: P|j> = i^ny (-1)^popcount(j & z) |j ^ x>
+  const int64_t tb = min(max(term_ptr[c], (int64_t)0), n_terms), te = min(max(term_ptr[c + 1], tb), n_terms);
+  const int n_term = __builtin_amdgcn_readfirstlane((int)min(te - tb, (int64_t)0x7FFFFFFF));
+  const int qmask = (1 << n) - 1, cnt = density ? 1 << n : A;
+  double total = 0.0;
+  for (int t = 0; t < n_term; ++t) {
+    const sim_i4 term = terms[tb + t];   // xmask, zmask, number of Y factors, reserved
+    const int xm = __builtin_amdgcn_readfirstlane(term.x & qmask), zm = __builtin_amdgcn_readfirstlane(term.y & qmask);
+    const int ny = __builtin_amdgcn_readfirstlane(term.z & 3);
+    double part = 0.0;
+    for (int i0 = 0; i0 < cnt; i0 += cx.T) {
+      const int i = i0 + tid, j = i & (cnt - 1);
+      sim_c v;
+      if (density) {
+        v = cx.st[(j | ((j ^ xm) << n)) & (A - 1)];                  // rho[j, j ^ x]
+      } else {
+        const sim_c a = cx.st[(j ^ xm) & (A - 1)], b = cx.st[j];     // conj(psi[j ^ x]) psi[j]
+        v = sim_c{a.x * b.x + a.y * b.y, a.x * b.y - a.y * b.x};
+      }
+      double re = ny == 0 ? v.x : ny == 1 ? -v.y : ny == 2 ? -v.x : v.y;   // Re(i^ny v)
+      re = __popc(j & zm) & 1 ? -re : re;
+      part = part + (i < cnt ? re : 0.0);
+    }
+    const double tv = cx.reduce(part, t & 1);
+    if (tid == 0) {
+      term_values[tb + t] = tv;
+      total = total + coeff[tb + t] * tv;
+    }
+  }
+  if (tid == 0) {
+    values[c] = total;
+    norm[c] = nrm;
+  }
+}
+
+}  // namespace
+}  // namespace mlqem
+
+using namespace mlqem;
+
+extern "C" int mlqem_sim_run_f64(int64_t n_circuits, const int32_t* circ, const int64_t* op_ptr, const mlqem_sim_op* ops, int64_t n_ops,
+                                 const double* params, int64_t n_params, const int64_t* term_ptr, const mlqem_sim_term* terms,
+                                 const double* coeff, int64_t n_terms, const int32_t* ids, int64_t n_wave, int64_t n_wg,
+                                 double* term_values, double* values, double* norm, mlqem_stream_t stream) {
+  static_assert(sizeof(mlqem_sim_op) == 16 && sizeof(mlqem_sim_term) == 16, "one 16-byte load per record");
+  begin_launches();
+  if (n_circuits < 0 || n_ops < 0 || n_terms < 0 || n_wave < 0 || n_wg < 0 || n_params < kSimParamPad) return MLQEM_ERR_BAD_ARG;
+  if (n_wave + n_wg > n_circuits) return MLQEM_ERR_BAD_ARG;
+  if (n_circuits > 0x7FFFFFFFll || n_params > 0x7FFFFFFFll) return MLQEM_ERR_UNSUPPORTED;
+  if (n_wave + n_wg == 0) return MLQEM_OK;
+  if (!circ || !op_ptr || !params || !term_ptr || !ids || !values || !norm || (n_ops > 0 && !ops) ||
+      (n_terms > 0 && (!terms || !coeff || !term_values)))
+    return MLQEM_ERR_BAD_ARG;
+  if (!aligned_to(circ, 16) || !aligned_to(ops, 16) || !aligned_to(terms, 16)) return MLQEM_ERR_BAD_ARG;
+  const sim_i4* ci = reinterpret_cast<const sim_i4*>(circ);
+  const sim_i4* oi = reinterpret_cast<const sim_i4*>(ops);
+  const sim_i4* ti = reinterpret_cast<const sim_i4*>(terms);
+  if (n_wave > 0) {
+    const int64_t blocks = ceil_div(n_wave, (int64_t)(kBlock / kWave));
+    hipLaunchKernelGGL(sim_kernel<false>, dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), (int)n_circuits, ci, op_ptr, oi,
+                       n_ops, params, n_params, term_ptr, ti, coeff, n_terms, ids, (int)n_wave, term_values, values, norm);
+  }
+  if (n_wg > 0) {
+    hipLaunchKernelGGL(sim_kernel<true>, dim3((unsigned)n_wg), dim3(kBlock), 0, as_stream(stream), (int)n_circuits, ci, op_ptr, oi,
+                       n_ops, params, n_params, term_ptr, ti, coeff, n_terms, ids + n_wave, (int)n_wg, term_values, values, norm);
+  }
+  return launch_status();
+}

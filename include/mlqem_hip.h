@@ -1350,6 +1350,52 @@ int mlqem_sim_run_f64(int64_t n_circuits, const int32_t* circ, const int64_t* op
                       const double* coeff, int64_t n_terms, const int32_t* ids, int64_t n_wave, int64_t n_wg, double* term_values,
                       double* values, double* norm, mlqem_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Zero-noise extrapolation on the simulator (two additive symbols, the ABI version is unchanged).  A folded circuit is the same
+ * records replayed in another order, some as their inverse, so the circuits are lowered ONCE (the buffers of mlqem_sim_run_f64 for
+ * n_circuits = B circuits) and every (circuit, noise factor) pair gets a SCHEDULE of 4 bytes per step.  blackwater.sim.zne builds
+ * the schedules (build_schedules) and blackwater.native.ops.sim_run_folded / zne_combine call these.
+ *
+ * mlqem_sim_run_folded_f64.  Run r = f * B + c is circuit c at noise factor f, 0 <= f < n_factors = F.
+ * sched_ptr int64 [F * B + 1]; sched int32 [n_sched]: run r owns sched[sched_ptr[r] .. sched_ptr[r + 1]).  An entry is
+ *         (k << 1) | dagger with k an op index RELATIVE to op_ptr[c].  The run starts from |0..0> and applies
+ *         ops[op_ptr[c] + k] for each entry in order; the LAST circ[c].r entries of a schedule are its readout ops, and norm is
+ *         taken before them; then the terms of circuit c are evaluated exactly as in mlqem_sim_run_f64.
+ *         dagger = 1 applies the record's inverse, formed from the ONE record by swapping and negating components only (no new
+ *         rounding: a run is bit-equal to mlqem_sim_run_f64 on a program whose records were expanded and conjugate-transposed
+ *         on the host):
+ *           U1, U2           the conjugate transpose of the record's matrix; in mode 1 the column bits get its conjugate, i.e. the
+ *                            transpose
+ *           DIAG1            conjugated phases
+ *           CX, CZ, SWAP     unchanged (self-inverse)
+ *           DEPOL*, READOUT  the flag is ignored
+ * ids     int32 [n_wave + n_wg]: RUN numbers; the wave / workgroup split is by the circuit's amplitude count, as above.
+ * Outputs, float64: term_values [F][n_terms], values [F][B], norm [F][B]; only the entries of the runs in `ids` are written.
+ * The contract of mlqem_sim_run_f64 holds for the new input too: k is clamped to the circuit's op range (a circuit without ops
+ * skips its entries), schedule offsets are clamped to n_sched, run numbers to F * B; an empty schedule leaves |0..0>; a malformed
+ * schedule computes garbage and faults nothing.  No atomics, no workspace, no host read: capturable in a hipGraph; a run's bits are
+ * the same alone, in any batch and from call to call.  The wave variant has no workgroup barrier, so the four runs of a workgroup
+ * may have schedules of any lengths.
+ * Negative sizes, n_factors < 1, n_wave + n_wg > F * B, n_params < 32, null or misaligned buffers: MLQEM_ERR_BAD_ARG; n_circuits,
+ * n_factors, F * B, n_params or n_sched over 2^31 - 1: MLQEM_ERR_UNSUPPORTED; all checked before anything is launched.
+ *
+ * mlqem_zne_combine_f64.  Polynomial extrapolation of exact values to zero noise is a weighted sum over the factors (the weights
+ * come from the host: blackwater.sim.zne, Extrapolator.weights).  term_values [F][n_terms], weights [F], term_ptr [B + 1], coeff
+ * [n_terms] ->  mitigated_terms [n_terms] = sum_f weights[f] * term_values[f][t], added in factor order (w0 * tv0, then one fused
+ * multiply-add per further factor);  mitigated_values [B] = sum_t coeff[t] * mitigated term t, added in term order by one thread
+ * per circuit (a fused multiply-add per term, from 0.0).  One launch, fixed order, no atomics, no workspace, no host read:
+ * capturable.  term_ptr is clamped to n_terms.  n_factors < 1, negative sizes or a null buffer that would be used:
+ * MLQEM_ERR_BAD_ARG; a size over 2^31 - 1: MLQEM_ERR_UNSUPPORTED.  n_circuits == 0 and n_terms == 0: MLQEM_OK without a launch.
+ * ---------------------------------------------------------------------------------------------------- */
+int mlqem_sim_run_folded_f64(int64_t n_circuits, int64_t n_factors, const int32_t* circ, const int64_t* op_ptr, const mlqem_sim_op* ops,
+                             int64_t n_ops, const double* params, int64_t n_params, const int64_t* term_ptr,
+                             const mlqem_sim_term* terms, const double* coeff, int64_t n_terms, const int64_t* sched_ptr,
+                             const int32_t* sched, int64_t n_sched, const int32_t* ids, int64_t n_wave, int64_t n_wg,
+                             double* term_values, double* values, double* norm, mlqem_stream_t stream);
+int mlqem_zne_combine_f64(int64_t n_factors, int64_t n_circuits, const double* term_values, const double* weights,
+                          const int64_t* term_ptr, const double* coeff, int64_t n_terms, double* mitigated_terms,
+                          double* mitigated_values, mlqem_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

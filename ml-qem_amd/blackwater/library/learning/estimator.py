@@ -5,8 +5,9 @@ In scope: the decorator, the job wrapper, the processor protocol, ``TorchLearnin
 ``EmptyProcessor``, ``ScikitLearningModelProcessor`` (the random-forest / OLS baselines: same feature rows, the
 model stays on the host CPU), ``ForestLearningModelProcessor``, ``BoostedLearningModelProcessor`` and
 ``LinearLearningModelProcessor`` (additions: the same random forests, gradient-boosted trees and OLS / ridge models scored on the
-device by the forest, boosted-trees and least-squares kernels, one launch per ``run()``).  ``ZNEProcessor`` (runs extra noisy circuits
-through a ZNE estimator; no model) is out of scope.
+device by the forest, boosted-trees and least-squares kernels, one launch per ``run()``) and ``ZNEProcessor`` (no model: it runs
+the circuits at amplified noise through a ZNE estimator, ``blackwater.zne.zne(cls)``, and extrapolates to zero noise; around
+``blackwater.sim.DeviceEstimator`` a whole ``run()`` is one fused launch, reference :33-86).
 """
 from __future__ import annotations
 
@@ -212,6 +213,45 @@ class BoostedLearningModelProcessor(_DeviceRegressorProcessor):
         self._device = torch.device(device)
         self._backend = backend
         self._properties = get_backend_properties_v1(backend)
+
+
+class ZNEProcessor(LearningMethodEstimatorProcessor):
+    """Zero-noise extrapolation as a processor (reference :33-86): the value handed in is ignored, the circuit is run again through
+    ``zne_estimator`` (an INSTANCE of a ``blackwater.zne.zne(cls)`` class) with ``zne_strategy`` and the extrapolated value is
+    returned.  ``process_batch`` sends all circuits of a ``run()`` through one ``zne_estimator.run``: around
+    ``blackwater.sim.DeviceEstimator`` that is one lowering and one fused launch for every (circuit, noise factor) pair.
+
+    Circuits arrive bound and on physical qubits, with observables as wide as the circuit (wrap with ``skip_transpile=True``).  The
+    reference transpiles at optimisation level 0, appends measurements and re-maps a 2-qubit observable onto 5 physical qubits
+    through the last two measurements, all hard-coded; none of that is reproduced here.  ``backend`` is kept for the reference's
+    constructor; ``shots``, when given, is passed on as a run option (the device estimator is exact and ignores it)."""
+
+    accepts_qasm_text = True     # the ZNE estimator takes OpenQASM text as it comes
+
+    def __init__(self, zne_estimator, zne_strategy, backend=None, shots=None):
+        if not hasattr(zne_estimator, "run"):
+            raise BlackwaterException("ZNEProcessor needs an estimator instance with .run(circuits, observables, zne_strategy=...)")
+        self._zne_estimator = zne_estimator
+        self._zne_strategy = zne_strategy
+        self._backend = backend
+        self._shots = shots
+
+    def _values(self, circuits, observables, parameter_values):
+        options = {"zne_strategy": self._zne_strategy}
+        if self._shots is not None:
+            options["shots"] = self._shots
+        job = self._zne_estimator.run(circuits, observables, parameter_values, **options)
+        return np.asarray(job.result().values, dtype=np.float64)
+
+    def process(self, expectation_value, circuits, observables, parameter_values):
+        return float(self._values([circuits], [observables], None)[0])
+
+    def process_batch(self, expectation_values, circuits, observables, parameter_values):
+        """All circuits of one ``run()`` through ONE ZNE run; results equal ``process`` applied circuit by circuit (a run's bits
+        do not depend on the batch).  The circuits arrive bound, so no parameter values are passed on."""
+        if not circuits:
+            return []
+        return self._values(list(circuits), list(observables), None).tolist()
 
 
 class EmptyProcessor(LearningMethodEstimatorProcessor):

@@ -224,6 +224,8 @@ SIGNATURES = {
     "mlqem_linreg_moments_f32": (_I, [_P, _L, _P, _L, _L, _I, _I, _P, _I, _P, _S, _P]),
     "mlqem_linreg_predict_f32": (_I, [_P, _L, _L, _I, _P, _P, _I, _P, _P]),
     "mlqem_sim_run_f64": (_I, [_L, _P, _P, _P, _L, _P, _L, _P, _P, _P, _L, _P, _L, _L, _P, _P, _P, _P]),
+    "mlqem_sim_run_folded_f64": (_I, [_L, _L, _P, _P, _P, _L, _P, _L, _P, _P, _P, _L, _P, _P, _L, _P, _L, _L, _P, _P, _P, _P]),
+    "mlqem_zne_combine_f64": (_I, [_L, _L, _P, _P, _P, _P, _L, _P, _P, _P]),
 }
 
 _lib = None

@@ -2600,3 +2600,84 @@ def sim_run(circ, op_ptr, ops, params, term_ptr, terms, coeff, ids, n_wave, n_wg
                                          _p(ids), n_wave, n_wg, _p(term_values) if n_terms else None, _p(values), _p(norm), _stream())
     _lib.check(code, "mlqem_sim_run_f64")
     return values, term_values, norm
+
+
+def _sim_out(t, name, shape, dev):
+    if t is None:
+        return torch.zeros(shape, dtype=torch.float64, device=dev)
+    if not t.is_cuda or t.device != dev or t.dtype != torch.float64 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{name}: want contiguous float64 {list(shape)} on {dev}, got {tuple(t.shape)} {t.dtype} {t.device}")
+    return t
+
+
+def sim_run_folded(circ, op_ptr, ops, params, term_ptr, terms, coeff, sched_ptr, sched, ids, n_wave, n_wg, n_factors, *,
+                   term_values=None, values=None, norm=None):
+    """Simulates every (circuit, noise factor) run of a lowered batch along its schedule (mlqem_sim_run_folded_f64):
+    ``(values, term_values, norm)``, float64 [F, B], [F, n_terms], [F, B].
+
+    The first seven buffers are those of :func:`sim_run` for the B circuits, lowered once.  ``sched_ptr`` int64 [F * B + 1] and
+    ``sched`` int32 [n_sched] hold one schedule per run ``r = f * B + c``: entries ``(k << 1) | dagger`` with ``k`` relative to the
+    circuit's first op (``blackwater.sim.zne.build_schedules`` makes them).  ``ids`` int32 [n_wave + n_wg] holds RUN numbers, the
+    wave-per-circuit runs first.  Shapes, dtypes and devices are checked here; the contents are the builder's to guarantee (the
+    kernel clamps every index: a malformed schedule computes garbage and faults nothing).  Nothing here waits for the device or
+    reads a tensor's contents, and with the three outputs given nothing is allocated: the call can be captured in a hipGraph."""
+    for t, name, dtype, cols in ((circ, "circ", torch.int32, 4), (ops, "ops", torch.int32, 4), (terms, "terms", torch.int32, 4)):
+        if not t.is_cuda:
+            raise _lib.NativeLibraryError(f"{name} must live on the GPU (got {t.device}); there is no CPU path")
+        if t.dtype != dtype or t.dim() != 2 or t.shape[1] != cols or not t.is_contiguous():
+            raise ValueError(f"sim: want contiguous {dtype} {name} [., {cols}], got {tuple(t.shape)} {t.dtype}")
+    b, n_ops, n_terms, f = int(circ.shape[0]), int(ops.shape[0]), int(terms.shape[0]), int(n_factors)
+    if f < 1:
+        raise ValueError(f"sim: n_factors = {f}, want at least 1")
+    _vec(op_ptr, "op_ptr", b + 1, torch.int64)
+    _vec(term_ptr, "term_ptr", b + 1, torch.int64)
+    _vec(params, "params", SIM_PARAM_PAD, torch.float64)
+    _vec(coeff, "coeff", n_terms, torch.float64)
+    _vec(sched_ptr, "sched_ptr", f * b + 1, torch.int64)
+    _vec(sched, "sched", 0, torch.int32)
+    if op_ptr.shape[0] != b + 1 or term_ptr.shape[0] != b + 1 or sched_ptr.shape[0] != f * b + 1 or coeff.shape[0] != n_terms:
+        raise ValueError(f"sim: want op_ptr and term_ptr [{b + 1}], sched_ptr [{f * b + 1}] and coeff [{n_terms}], got "
+                         f"{tuple(op_ptr.shape)}, {tuple(term_ptr.shape)}, {tuple(sched_ptr.shape)} and {tuple(coeff.shape)}")
+    n_wave, n_wg, n_sched = int(n_wave), int(n_wg), int(sched.shape[0])
+    if n_wave < 0 or n_wg < 0 or n_wave + n_wg > f * b:
+        raise ValueError(f"sim: n_wave = {n_wave} and n_wg = {n_wg} must be >= 0 and add up to at most {f * b} runs")
+    _vec(ids, "ids", n_wave + n_wg, torch.int32)
+    dev = circ.device
+    if any(t.device != dev for t in (op_ptr, ops, params, term_ptr, terms, coeff, sched_ptr, sched, ids)):
+        raise ValueError(f"sim: circ is on {dev}, another buffer is not")
+    values, term_values = _sim_out(values, "values", (f, b), dev), _sim_out(term_values, "term_values", (f, n_terms), dev)
+    norm = _sim_out(norm, "norm", (f, b), dev)
+    code = _lib.load().mlqem_sim_run_folded_f64(
+        b, f, _p(circ), _p(op_ptr), _p(ops) if n_ops else None, n_ops, _p(params), int(params.shape[0]), _p(term_ptr),
+        _p(terms) if n_terms else None, _p(coeff) if n_terms else None, n_terms, _p(sched_ptr), _p(sched) if n_sched else None, n_sched,
+        _p(ids), n_wave, n_wg, _p(term_values) if n_terms else None, _p(values), _p(norm), _stream())
+    _lib.check(code, "mlqem_sim_run_folded_f64")
+    return values, term_values, norm
+
+
+def zne_combine(term_values, weights, term_ptr, coeff, *, mitigated_terms=None, mitigated_values=None):
+    """The extrapolation to zero noise as a weighted sum (mlqem_zne_combine_f64): ``(mitigated_values, mitigated_terms)``, float64
+    [B] and [n_terms].  ``term_values`` float64 [F, n_terms] (from :func:`sim_run_folded`), ``weights`` float64 [F] (from an
+    extrapolator of ``blackwater.sim.zne``), ``term_ptr`` int64 [B + 1], ``coeff`` float64 [n_terms].  Every sum is formed in a fixed
+    order (factors, then terms); nothing here waits for the device, and with both outputs given nothing is allocated."""
+    if not term_values.is_cuda:
+        raise _lib.NativeLibraryError(f"term_values must live on the GPU (got {term_values.device}); there is no CPU path")
+    if term_values.dtype != torch.float64 or term_values.dim() != 2 or not term_values.is_contiguous() or term_values.shape[0] < 1:
+        raise ValueError(f"zne: want contiguous float64 term_values [F >= 1, n_terms], got {tuple(term_values.shape)} {term_values.dtype}")
+    f, n_terms = int(term_values.shape[0]), int(term_values.shape[1])
+    _vec(weights, "weights", f, torch.float64)
+    _vec(term_ptr, "term_ptr", 1, torch.int64)
+    _vec(coeff, "coeff", n_terms, torch.float64)
+    if weights.shape[0] != f or coeff.shape[0] != n_terms:
+        raise ValueError(f"zne: want weights [{f}] and coeff [{n_terms}], got {tuple(weights.shape)} and {tuple(coeff.shape)}")
+    b = int(term_ptr.shape[0]) - 1
+    dev = term_values.device
+    if any(t.device != dev for t in (weights, term_ptr, coeff)):
+        raise ValueError(f"zne: term_values is on {dev}, another buffer is not")
+    mitigated_terms = _sim_out(mitigated_terms, "mitigated_terms", (n_terms,), dev)
+    mitigated_values = _sim_out(mitigated_values, "mitigated_values", (b,), dev)
+    code = _lib.load().mlqem_zne_combine_f64(f, b, _p(term_values) if n_terms else None, _p(weights), _p(term_ptr),
+                                             _p(coeff) if n_terms else None, n_terms, _p(mitigated_terms) if n_terms else None,
+                                             _p(mitigated_values) if b else None, _stream())
+    _lib.check(code, "mlqem_zne_combine_f64")
+    return mitigated_values, mitigated_terms

@@ -1,8 +1,15 @@
 """Batched exact simulation of small circuits on the device: ideal (state vector) and noisy (density matrix) expectation values,
-the labels the mitigators learn from.  ``compile_programs`` / ``NoiseModel`` / ``measured_z`` run on the host alone."""
+the labels the mitigators learn from.  ``compile_programs`` / ``NoiseModel`` / ``measured_z`` run on the host alone.  ``blackwater.sim.zne`` (also ``blackwater.zne``) is
+zero-noise extrapolation on it; the ``zne(cls)`` decorator lives there, so that ``sim.zne`` stays the module."""
 from .program import (MAX_AMPS, MAX_QUBITS_DENSITY, MAX_QUBITS_VECTOR, SUPPORTED_GATES, WAVE_AMPS, NoiseModel, SimBatch,
                       compile_programs, measured_z)
 from .run import DeviceEstimator, SimulatedJob, expectation_values, run_batch
+from .zne import (CubicExtrapolator, CxAmplifier, GlobalFoldingAmplifier, LinearExtrapolator, LocalFoldingAmplifier,
+                  PolynomialExtrapolator, QuadraticExtrapolator, QuarticExtrapolator, RichardsonExtrapolator, Schedules,
+                  TwoQubitAmplifier, ZNEStrategy, build_schedules, fold_circuit, zne_expectation_values, zne_run)
 
 __all__ = ["MAX_AMPS", "MAX_QUBITS_DENSITY", "MAX_QUBITS_VECTOR", "SUPPORTED_GATES", "WAVE_AMPS", "NoiseModel", "SimBatch",
-           "compile_programs", "measured_z", "DeviceEstimator", "SimulatedJob", "expectation_values", "run_batch"]
+           "compile_programs", "measured_z", "DeviceEstimator", "SimulatedJob", "expectation_values", "run_batch",
+           "CubicExtrapolator", "CxAmplifier", "GlobalFoldingAmplifier", "LinearExtrapolator", "LocalFoldingAmplifier",
+           "PolynomialExtrapolator", "QuadraticExtrapolator", "QuarticExtrapolator", "RichardsonExtrapolator", "Schedules",
+           "TwoQubitAmplifier", "ZNEStrategy", "build_schedules", "fold_circuit", "zne_expectation_values", "zne_run"]

@@ -180,6 +180,13 @@ class SimBatch:
     n_wg: int
     variant: List[str] = field(default_factory=list)            # "wave" | "workgroup" per circuit
     measured: List[Dict[int, int]] = field(default_factory=list)   # classical bit -> qubit per circuit
+    # the record map of the source gates (barrier and measure are no gates): what blackwater.sim.zne folds.  Record indices are
+    # relative to op_ptr[c]; -1 = absent (``id`` has no gate record, a gate without noise no depolarising record)
+    gate_ptr: Optional[np.ndarray] = None      # int64 [B + 1]: circuit c owns gates gate_ptr[c] .. gate_ptr[c + 1]
+    gate_record: Optional[np.ndarray] = None   # int32 [n_gates]: the gate's own record
+    gate_noise: Optional[np.ndarray] = None    # int32 [n_gates]: the depolarising record after it
+    gate_name: Optional[np.ndarray] = None     # int16 [n_gates]: index of the gate's name in SUPPORTED_GATES
+    gate_op: Optional[np.ndarray] = None       # int32 [n_gates]: index of the gate in the circuit's op list
 
     def __len__(self) -> int:
         return int(self.circ.shape[0])
@@ -243,6 +250,8 @@ def compile_programs(circuits: Sequence[Any], observables: Sequence[Any], noise:
     cap_q = MAX_QUBITS_DENSITY if density else MAX_QUBITS_VECTOR
     circ_rows, ops, params, op_ptr, term_rows, coeffs, term_ptr = [], [], [], [0], [], [], [0]
     variant, measured_all = [], []
+    gate_ptr, gate_record, gate_noise, gate_name, gate_op = [0], [], [], [], []
+    name_id = {g: j for j, g in enumerate(SUPPORTED_GATES)}
 
     def emit(kind, q0, q1, values):
         ops.append((kind, q0, q1, len(params)))
@@ -289,23 +298,31 @@ def compile_programs(circuits: Sequence[Any], observables: Sequence[Any], noise:
             p = tuple(float(v) for v in op.params)
             if not all(math.isfinite(v) for v in p):
                 raise ValueError(f"{where}: op {i} ({name}) has the non-finite angle {p!r}")
+            first, rec, noi = op_ptr[-1], -1, -1
             if width == 2:
                 q0, q1 = op.qubits
                 if q0 == q1:
                     raise ValueError(f"{where}: op {i} ({name}) names qubit {q0} twice")
                 kind, entries = _two_qubit(name, p)
+                rec = len(ops) - first
                 emit_complex(kind, q0, q1, entries)
             else:
                 q0, q1 = op.qubits[0], 0
                 lowered = _one_qubit(name, p)
                 if lowered is not None:
+                    rec = len(ops) - first
                     emit_complex(lowered[0], q0, 0, lowered[1])
             if density:
                 lam = noise.after_gate(i, name, tuple(circ.qubit_reg_index[q] for q in op.qubits))
                 if lam is not None:
                     if not (math.isfinite(lam) and 0.0 <= lam <= 1.0):
                         raise ValueError(f"{where}: op {i} ({name}): depolarising parameter {lam!r}, want 0 <= lambda <= 1")
+                    noi = len(ops) - first
                     emit(OP_DEPOL2 if width == 2 else OP_DEPOL1, q0, q1, [float(lam)])
+            gate_record.append(rec)
+            gate_noise.append(noi)
+            gate_name.append(name_id[name])
+            gate_op.append(i)
         rows, cs, has_xy = _lower_terms(obs, n, where)
         n_readout = 0
         if density:
@@ -320,6 +337,7 @@ def compile_programs(circuits: Sequence[Any], observables: Sequence[Any], noise:
                 n_readout += 1
         circ_rows.append((n, 1 if density else 0, n_readout, 0))
         op_ptr.append(len(ops))
+        gate_ptr.append(len(gate_record))
         term_rows += rows
         coeffs += cs
         term_ptr.append(len(term_rows))
@@ -339,7 +357,10 @@ def compile_programs(circuits: Sequence[Any], observables: Sequence[Any], noise:
         terms=np.asarray(term_rows, dtype=np.int32).reshape(-1, 4),
         coeff=np.asarray(coeffs, dtype=np.float64),
         ids=np.asarray(wave + wg, dtype=np.int32),
-        n_wave=len(wave), n_wg=len(wg), variant=variant, measured=measured_all)
+        n_wave=len(wave), n_wg=len(wg), variant=variant, measured=measured_all,
+        gate_ptr=np.asarray(gate_ptr, dtype=np.int64), gate_record=np.asarray(gate_record, dtype=np.int32),
+        gate_noise=np.asarray(gate_noise, dtype=np.int32), gate_name=np.asarray(gate_name, dtype=np.int16),
+        gate_op=np.asarray(gate_op, dtype=np.int32))
 
 
 def measured_z(circuit: Any) -> PauliObservable:

@@ -1,0 +1,525 @@
+"""Zero-noise extrapolation on the batched simulator: noise amplification by gate folding, polynomial extrapolation to zero noise.
+
+A folded circuit is the circuit's own gate records replayed in another order, some of them as their inverse.  So the circuits are
+lowered ONCE (:func:`compile_programs`), every (circuit, noise factor) pair gets a *schedule* of 4 bytes per step
+(:func:`build_schedules`), one call simulates all of them (``ops.sim_run_folded``) and one more extrapolates (``ops.zne_combine``):
+:func:`zne_expectation_values`.  Names follow the ``zne`` prototype library the reference imports (``ZNEStrategy``,
+``LocalFoldingAmplifier``, ``LinearExtrapolator``, the ``zne(cls)`` decorator); that library is not a dependency, and the semantics
+are the ones written down here.
+
+The fold rule.  The foldable set G of a circuit is its gates that match the amplifier, in circuit order (``barrier`` and
+``measure`` are no gates); N = |G|.  For a noise factor lambda >= 1 (it may be fractional)::
+
+    m = floor(N (lambda - 1) / 2 + 1/2),    (k, s) = divmod(m, N)
+
+*Local* folding runs every gate g of G as g (g^-1 g)^k, and s of them once more: the first s of G, the last s, or
+``default_rng(random_seed).choice(N, s, replace=False)`` (a fresh generator per choice, so the choice depends on (seed, N, s) alone:
+the same alone and in any batch).  *Global* folding runs the whole circuit U as U (U^-1 U)^k and then L^-1 L for L = its last (or
+first) s gates.  N = 0 runs the circuit unchanged at every factor.  The achieved factor 1 + 2 m / N is reported; the extrapolation
+uses the REQUESTED factors, as the public ZNE libraries do.
+
+Noise under folding (a modelling choice).  A fold unit is a gate together with the depolarising op the noise model puts after it: a
+folded gate runs as G N G^-1 N G N, the inverse carrying the gate's OWN depolarising record (its name is not looked up again: for
+``sx`` a by-name rule would find no calibration entry for ``sxdg`` and amplify nothing).  Readout ops run once, after everything.
+
+Polynomial extrapolation of exact values is linear in them, so an extrapolator is a weight vector: ``weights(noise_factors)`` is
+``e_0^T V^+`` for the Vandermonde matrix V of the factors, in float64 on the host.  Exponential extrapolation and standard errors
+from shot noise are out of scope: the values are exact.
+"""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass, field
+from typing import Any, Iterable, List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+
+from ..data.circuit import Circuit, CircuitOp
+from ..library.primitives import make_estimator_result
+from .program import _TWO_QUBIT, SUPPORTED_GATES, NoiseModel, SimBatch, compile_programs
+
+_NOT_GATES = ("barrier", "measure")
+
+
+# ---- amplifiers ------------------------------------------------------------------------------------------------------------------
+def fold_counts(n_foldable: int, noise_factor: float) -> Tuple[int, int]:
+    """``(k, s)`` of the fold rule: every foldable gate is folded k times and s of them once more.  (0, 0) for N = 0."""
+    lam = float(noise_factor)
+    if not math.isfinite(lam) or lam < 1.0:
+        raise ValueError(f"noise factor {noise_factor!r}: want a finite number >= 1")
+    if n_foldable <= 0:
+        return 0, 0
+    return divmod(int(math.floor(n_foldable * (lam - 1.0) / 2.0 + 0.5)), int(n_foldable))
+
+
+def achieved_factor(n_foldable: int, noise_factor: float) -> float:
+    k, s = fold_counts(n_foldable, noise_factor)
+    return 1.0 + 2.0 * (k * n_foldable + s) / n_foldable if n_foldable > 0 else 1.0
+
+
+class _Amplifier:
+    kind = "local"
+    sub_folding_option = "from_first"
+    random_seed = None
+
+    def matches(self, name: str, n_qubits: int) -> bool:
+        raise NotImplementedError
+
+    def _extra(self, n: int, s: int) -> np.ndarray:
+        """Ranks (positions inside G) of the s gates that are folded once more."""
+        if self.sub_folding_option == "from_first":
+            return np.arange(s)
+        if self.sub_folding_option == "from_last":
+            return np.arange(n - s, n)
+        return np.sort(np.random.default_rng(self.random_seed).choice(n, size=s, replace=False))
+
+
+class LocalFoldingAmplifier(_Amplifier):
+    """Folds gates one by one.  ``gates_to_fold``: ``None`` (every gate), an int (gates on exactly that many qubits), a gate name, or
+    an iterable of names and ints."""
+
+    def __init__(self, gates_to_fold: Union[None, int, str, Iterable[Union[int, str]]] = None, sub_folding_option: str = "from_first",
+                 random_seed: Optional[int] = None):
+        if sub_folding_option not in ("from_first", "from_last", "random"):
+            raise ValueError(f"sub_folding_option {sub_folding_option!r}: want 'from_first', 'from_last' or 'random'")
+        if gates_to_fold is None:
+            self.gates_to_fold = None
+        else:
+            items = [gates_to_fold] if isinstance(gates_to_fold, (int, str)) else list(gates_to_fold)
+            for it in items:
+                if not isinstance(it, (int, str)) or isinstance(it, bool) or it in _NOT_GATES:
+                    raise ValueError(f"gates_to_fold: {it!r} is neither a gate name nor a number of qubits")
+            self.gates_to_fold = frozenset(items)
+        self.sub_folding_option, self.random_seed = sub_folding_option, random_seed
+
+    def matches(self, name, n_qubits):
+        if name in _NOT_GATES:
+            return False
+        return self.gates_to_fold is None or name in self.gates_to_fold or n_qubits in self.gates_to_fold
+
+    def __repr__(self):
+        g = None if self.gates_to_fold is None else sorted(self.gates_to_fold, key=str)
+        return f"{type(self).__name__}(gates_to_fold={g!r}, sub_folding_option={self.sub_folding_option!r})"
+
+
+class TwoQubitAmplifier(LocalFoldingAmplifier):
+    def __init__(self, sub_folding_option: str = "from_first", random_seed: Optional[int] = None):
+        super().__init__(2, sub_folding_option, random_seed)
+
+
+class CxAmplifier(LocalFoldingAmplifier):
+    def __init__(self, sub_folding_option: str = "from_first", random_seed: Optional[int] = None):
+        super().__init__("cx", sub_folding_option, random_seed)
+
+
+class GlobalFoldingAmplifier(_Amplifier):
+    """Folds the whole circuit: U (U^-1 U)^k, then L^-1 L for its last (``from_last``) or first (``from_first``) s gates."""
+
+    kind = "global"
+
+    def __init__(self, sub_folding_option: str = "from_last"):
+        if sub_folding_option not in ("from_first", "from_last"):
+            raise ValueError(f"sub_folding_option {sub_folding_option!r}: want 'from_last' or 'from_first'")
+        self.sub_folding_option = sub_folding_option
+
+    def matches(self, name, n_qubits):
+        return name not in _NOT_GATES
+
+    def __repr__(self):
+        return f"GlobalFoldingAmplifier(sub_folding_option={self.sub_folding_option!r})"
+
+
+def _within(counts: np.ndarray) -> np.ndarray:
+    """0 .. counts[j] - 1 for every j, concatenated."""
+    counts = np.asarray(counts, dtype=np.int64)
+    starts = np.cumsum(counts) - counts
+    return np.arange(int(counts.sum()), dtype=np.int64) - np.repeat(starts, counts)
+
+
+def _plan(amplifier: _Amplifier, gate_ptr: np.ndarray, mask: np.ndarray, noise_factor: float):
+    """The fold rule on a batch of gate lists (circuit c owns gates gate_ptr[c] .. gate_ptr[c + 1], ``mask`` marks the foldable
+    ones).  Returns ``(unit_gate, unit_dagger, slot, achieved)``: the fold units of all circuits in running order (a flat gate index
+    and whether it runs as its inverse), the gate after which a unit is placed when the circuit is written out, and the achieved
+    factor per circuit.  numpy throughout; Python touches a circuit only for a ``random`` choice."""
+    lam = float(noise_factor)
+    if not math.isfinite(lam) or lam < 1.0:
+        raise ValueError(f"noise factor {noise_factor!r}: want a finite number >= 1")
+    gate_ptr = np.asarray(gate_ptr, dtype=np.int64)
+    per = np.diff(gate_ptr)
+    n_circ, n_gates = per.shape[0], int(gate_ptr[-1])
+    owner = np.repeat(np.arange(n_circ, dtype=np.int64), per)
+    mask = np.asarray(mask, dtype=bool)
+    big_n = np.bincount(owner, weights=mask, minlength=n_circ).astype(np.int64)
+    m = np.floor(big_n * (lam - 1.0) / 2.0 + 0.5).astype(np.int64)
+    safe = np.maximum(big_n, 1)
+    k, s = m // safe, m % safe
+    achieved = np.where(big_n > 0, 1.0 + 2.0 * m / safe, 1.0)
+    if amplifier.kind == "local":
+        before = np.cumsum(mask) - mask                       # foldable gates before this one, over the whole batch
+        first = np.concatenate([[0], np.cumsum(big_n)[:-1]]) if n_circ else np.zeros(0, dtype=np.int64)
+        rank = before - first[owner]                          # position inside G
+        if amplifier.sub_folding_option == "from_first":
+            extra = rank < s[owner]
+        elif amplifier.sub_folding_option == "from_last":
+            extra = rank >= (big_n - s)[owner]
+        else:
+            extra = np.zeros(n_gates, dtype=bool)
+            where = np.flatnonzero(mask)
+            for c in np.flatnonzero(s > 0):
+                extra[where[first[c] + amplifier._extra(int(big_n[c]), int(s[c]))]] = True
+        folds = np.where(mask, k[owner] + extra, 0)
+        reps = 1 + 2 * folds
+        unit_gate = np.repeat(np.arange(n_gates, dtype=np.int64), reps)
+        unit_dagger = _within(reps) & 1
+        return unit_gate, unit_dagger, unit_gate, achieved
+    # global: big_n = per (every gate is foldable)
+    body = per * (1 + 2 * k)
+    total = body + 2 * s
+    j = _within(total)
+    own = np.repeat(np.arange(n_circ, dtype=np.int64), total)
+    n_o, s_o, body_o = np.maximum(per[own], 1), s[own], body[own]
+    p, i = j // n_o, j % n_o
+    pos = np.where(p & 1, n_o - 1 - i, i)
+    dag = p & 1
+    tail = j - body_o
+    lo = (per - s)[own] if amplifier.sub_folding_option == "from_last" else np.zeros_like(own)
+    in_tail, inverse = tail >= 0, tail < s_o
+    pos = np.where(in_tail, np.where(inverse, lo + s_o - 1 - tail, lo + tail - s_o), pos)
+    dag = np.where(in_tail, inverse.astype(np.int64), dag)
+    unit_gate = gate_ptr[own] + pos
+    slot = np.where(j < per[own], unit_gate, gate_ptr[own] + per[own] - 1)   # the extra passes go after the last gate
+    return unit_gate, dag, slot, achieved
+
+
+_SELF_INVERSE = {"id", "x", "y", "z", "h", "cx", "cz", "swap", "ecr"}
+_PAIRS = {"s": "sdg", "sdg": "s", "t": "tdg", "tdg": "t", "sx": "sxdg", "sxdg": "sx"}
+_NEGATED = {"rx", "ry", "rz", "p", "u1", "rzz"}
+
+
+def inverse_op(op: CircuitOp) -> CircuitOp:
+    """The inverse of a gate, by name: self-inverse gates; s/sdg, t/tdg, sx/sxdg; a negated angle for rx ry rz p u1 rzz;
+    u3(a, b, c)^-1 = u3(-a, -c, -b); u2(b, c) = u3(pi / 2, b, c)."""
+    name, p = op.name, tuple(float(v) for v in op.params)
+    if name in _SELF_INVERSE:
+        return CircuitOp(name, op.qubits, op.clbits, p)
+    if name in _PAIRS:
+        return CircuitOp(_PAIRS[name], op.qubits, op.clbits, p)
+    if name in _NEGATED and len(p) == 1:
+        return CircuitOp(name, op.qubits, op.clbits, (-p[0],))
+    if name in ("u3", "u") and len(p) == 3:
+        return CircuitOp(name, op.qubits, op.clbits, (-p[0], -p[2], -p[1]))
+    if name == "u2" and len(p) == 2:
+        return CircuitOp("u3", op.qubits, op.clbits, (-math.pi / 2, -p[1], -p[0]))
+    raise ValueError(f"fold_circuit: no inverse is known for the gate {name!r} with {len(p)} parameters")
+
+
+def fold_circuit(circuit: Any, noise_factor: float, amplifier: _Amplifier) -> Circuit:
+    """The folded circuit as IR, for use outside the simulator (``circuit_to_qasm``, the graph encoder, another estimator) and as
+    the written-out form of the fold rule.  Inverses are by name (:func:`inverse_op`); barriers and measures stay where they are;
+    the extra passes of a global fold follow the circuit's last gate."""
+    circ = Circuit.from_any(circuit)
+    gates = [i for i, op in enumerate(circ.ops) if op.name not in _NOT_GATES]
+    mask = np.asarray([amplifier.matches(circ.ops[i].name, len(circ.ops[i].qubits)) for i in gates], dtype=bool)
+    unit_gate, unit_dagger, slot, _ = _plan(amplifier, np.asarray([0, len(gates)]), mask, noise_factor)
+    placed: List[List[CircuitOp]] = [[] for _ in gates]
+    for g, d, at in zip(unit_gate.tolist(), unit_dagger.tolist(), slot.tolist()):
+        op = circ.ops[gates[g]]
+        placed[at].append(inverse_op(op) if d else op)
+    out, g = [], 0
+    for op in circ.ops:
+        if op.name in _NOT_GATES:
+            out.append(op)
+        else:
+            out += placed[g]
+            g += 1
+    return Circuit(circ.num_qubits, circ.num_clbits, out, list(circ.qubit_reg_index))
+
+
+# ---- schedules -------------------------------------------------------------------------------------------------------------------
+@dataclass
+class Schedules:
+    """The schedules of ``mlqem_sim_run_folded_f64`` for F noise factors over a lowered batch of B circuits."""
+
+    sched_ptr: np.ndarray     # int64 [F * B + 1]
+    sched: np.ndarray         # int32 [n_sched]: (k << 1) | dagger, k relative to the circuit's first record
+    ids: np.ndarray           # int32 [F * B]: run numbers f * B + c, the wave-per-circuit runs first
+    n_wave: int
+    n_wg: int
+    noise_factors: Tuple[float, ...]
+    achieved: np.ndarray      # float64 [F, B]: 1 + 2 m / N per run
+
+    def to(self, device):
+        import torch
+
+        dev = torch.device(device)
+        return {k: torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(dev) for k in ("sched_ptr", "sched", "ids")}
+
+
+def _name_table(amplifier: _Amplifier) -> np.ndarray:
+    return np.asarray([amplifier.matches(g, 2 if g in _TWO_QUBIT else 1) for g in SUPPORTED_GATES], dtype=bool)
+
+
+def build_schedules(batch: SimBatch, circuits: Optional[Sequence[Any]], noise_factors: Sequence[float], amplifier: _Amplifier) -> Schedules:
+    """One schedule per (noise factor, circuit) from the record map ``compile_programs`` keeps (``batch.gate_*``).  A fold unit is
+    the gate's record followed by its depolarising record (either may be absent); the circuit's readout records follow every
+    schedule once.  ``circuits`` are the lowered circuits (only their number is checked: the map has everything).  numpy
+    throughout: no Python per entry."""
+    if batch.gate_ptr is None:
+        raise ValueError("build_schedules: the batch carries no record map (it was not made by compile_programs)")
+    n_circ = len(batch)
+    if circuits is not None and len(circuits) != n_circ:
+        raise ValueError(f"build_schedules: {len(circuits)} circuits but a batch of {n_circ}")
+    factors = tuple(float(f) for f in noise_factors)
+    if not factors:
+        raise ValueError("build_schedules: no noise factor")
+    mask = _name_table(amplifier)[batch.gate_name.astype(np.int64)] if batch.gate_name.size else np.zeros(0, dtype=bool)
+    owner = np.repeat(np.arange(n_circ, dtype=np.int64), np.diff(batch.gate_ptr))
+    n_readout = np.minimum(batch.circ[:, 2].astype(np.int64), batch.op_counts) if n_circ else np.zeros(0, dtype=np.int64)
+    readout = ((np.repeat(batch.op_counts - n_readout, n_readout) + _within(n_readout)) << 1).astype(np.int32)
+    rec, noi = batch.gate_record.astype(np.int64), batch.gate_noise.astype(np.int64)
+    pieces, lengths, achieved = [], [], []
+    for lam in factors:
+        unit_gate, unit_dagger, _, ach = _plan(amplifier, batch.gate_ptr, mask, lam)
+        r, n = rec[unit_gate], noi[unit_gate]
+        entries = np.stack([np.where(r >= 0, (r << 1) | unit_dagger, -1), np.where(n >= 0, n << 1, -1)], axis=1)
+        valid = entries >= 0
+        body_len = np.bincount(owner[unit_gate], weights=valid.sum(axis=1), minlength=n_circ).astype(np.int64)
+        run_len = body_len + n_readout
+        start = np.cumsum(run_len) - run_len
+        piece = np.empty(int(run_len.sum()), dtype=np.int32)
+        piece[np.repeat(start, body_len) + _within(body_len)] = entries[valid]
+        piece[np.repeat(start + body_len, n_readout) + _within(n_readout)] = readout
+        pieces.append(piece)
+        lengths.append(run_len)
+        achieved.append(ach)
+    lengths = np.concatenate(lengths) if lengths else np.zeros(0, dtype=np.int64)
+    sched_ptr = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    if int(sched_ptr[-1]) > 2 ** 31 - 1 or len(factors) * n_circ > 2 ** 31 - 1:
+        raise ValueError(f"build_schedules: {int(sched_ptr[-1])} schedule entries over {len(factors) * n_circ} runs exceed the "
+                         "2^31 - 1 one call can take; split the batch")
+    base = np.arange(len(factors), dtype=np.int64)[:, None] * n_circ
+    wave = (base + batch.ids[:batch.n_wave].astype(np.int64)[None, :]).reshape(-1)
+    wg = (base + batch.ids[batch.n_wave:batch.n_wave + batch.n_wg].astype(np.int64)[None, :]).reshape(-1)
+    return Schedules(sched_ptr=sched_ptr, sched=np.concatenate(pieces) if pieces else np.zeros(0, dtype=np.int32),
+                     ids=np.concatenate([wave, wg]).astype(np.int32), n_wave=int(wave.size), n_wg=int(wg.size), noise_factors=factors,
+                     achieved=np.asarray(achieved, dtype=np.float64).reshape(len(factors), n_circ))
+
+
+# ---- extrapolators ---------------------------------------------------------------------------------------------------------------
+class PolynomialExtrapolator:
+    """Least-squares polynomial of ``degree`` through (noise factor, value), evaluated at zero noise."""
+
+    def __init__(self, degree: int):
+        if int(degree) != degree or degree < 1:
+            raise ValueError(f"PolynomialExtrapolator: degree {degree!r}, want an integer >= 1")
+        self.degree = int(degree)
+
+    def _degree_for(self, n_factors: int) -> int:
+        return self.degree
+
+    def weights(self, noise_factors: Sequence[float]) -> np.ndarray:
+        """float64 [F] with ``sum_f w[f] y[f]`` = the fitted polynomial at 0: ``e_0^T V^+``, V the Vandermonde matrix."""
+        x = np.asarray([float(f) for f in noise_factors], dtype=np.float64)
+        if x.ndim != 1 or not np.isfinite(x).all():
+            raise ValueError(f"noise factors {tuple(noise_factors)!r}: want finite numbers")
+        if (x < 1.0).any():
+            raise ValueError(f"noise factors {tuple(noise_factors)!r}: every factor must be >= 1")
+        if np.unique(x).size != x.size:
+            raise ValueError(f"noise factors {tuple(noise_factors)!r}: a factor is repeated")
+        degree = self._degree_for(x.size)
+        if x.size < degree + 1:
+            raise ValueError(f"{type(self).__name__}: degree {degree} needs at least {degree + 1} noise factors, got {x.size}")
+        v = np.vander(x, degree + 1, increasing=True)
+        if x.size == degree + 1:   # interpolation: V^T w = e_0 (exact for (1, 3) -> (1.5, -0.5))
+            e0 = np.zeros(degree + 1)
+            e0[0] = 1.0
+            return np.linalg.solve(v.T, e0)
+        return np.linalg.pinv(v)[0].copy()
+
+    def extrapolate(self, noise_factors: Sequence[float], values) -> np.ndarray:
+        """The weights applied along the first axis of ``values`` [F, ...], added in factor order."""
+        w, y = self.weights(noise_factors), np.asarray(values, dtype=np.float64)
+        if y.shape[0] != w.shape[0]:
+            raise ValueError(f"extrapolate: {y.shape[0]} rows of values for {w.shape[0]} noise factors")
+        out = w[0] * y[0]
+        for f in range(1, w.shape[0]):
+            out = out + w[f] * y[f]
+        return out
+
+    def __repr__(self):
+        return f"{type(self).__name__}()" if type(self) is not PolynomialExtrapolator else f"PolynomialExtrapolator({self.degree})"
+
+
+class LinearExtrapolator(PolynomialExtrapolator):
+    def __init__(self):
+        super().__init__(1)
+
+
+class QuadraticExtrapolator(PolynomialExtrapolator):
+    def __init__(self):
+        super().__init__(2)
+
+
+class CubicExtrapolator(PolynomialExtrapolator):
+    def __init__(self):
+        super().__init__(3)
+
+
+class QuarticExtrapolator(PolynomialExtrapolator):
+    def __init__(self):
+        super().__init__(4)
+
+
+class RichardsonExtrapolator(PolynomialExtrapolator):
+    """The interpolating polynomial through all F factors: degree F - 1."""
+
+    def __init__(self):
+        self.degree = 0
+
+    def _degree_for(self, n_factors):
+        if n_factors < 2:
+            raise ValueError(f"RichardsonExtrapolator: needs at least 2 noise factors, got {n_factors}")
+        return n_factors - 1
+
+
+@dataclass
+class ZNEStrategy:
+    """What the reference's tutorial uses by default: factors (1, 3), two-qubit local folding, a straight line."""
+
+    noise_factors: Tuple[float, ...] = (1, 3)
+    noise_amplifier: Any = field(default_factory=lambda: LocalFoldingAmplifier(gates_to_fold=2))
+    extrapolator: Any = field(default_factory=LinearExtrapolator)
+
+    def __post_init__(self):
+        self.noise_factors = tuple(self.noise_factors)
+        self.weights()   # refuses bad factors at construction
+
+    def weights(self) -> np.ndarray:
+        return self.extrapolator.weights(self.noise_factors)
+
+
+# ---- the fused path --------------------------------------------------------------------------------------------------------------
+@dataclass
+class ZNERun:
+    """Everything one fused ZNE call produced (tensors on the device) and what the host knew."""
+
+    mitigated_values: Any     # float64 [B]
+    mitigated_terms: Any      # float64 [n_terms]
+    term_ptr: Any             # int64 [B + 1]
+    values: Any               # float64 [F, B]: per noise factor
+    term_values: Any          # float64 [F, n_terms]
+    norm: Any                 # float64 [F, B]
+    batch: SimBatch
+    schedules: Schedules
+    weights: np.ndarray
+
+
+def zne_run(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None,
+            strategy: Optional[ZNEStrategy] = None, device="cuda") -> ZNERun:
+    """Lowers once, builds the schedules, simulates every (circuit, factor) run in one call and extrapolates in one more."""
+    import torch
+
+    from ..native import ops
+
+    strategy = strategy or ZNEStrategy()
+    weights = strategy.weights()
+    circuits = list(circuits)
+    batch = compile_programs(circuits, observables, noise)
+    sch = build_schedules(batch, circuits, strategy.noise_factors, strategy.noise_amplifier)
+    t, s = batch.to(device), sch.to(device)
+    values, term_values, norm = ops.sim_run_folded(t["circ"], t["op_ptr"], t["ops"], t["params"], t["term_ptr"], t["terms"], t["coeff"],
+                                                   s["sched_ptr"], s["sched"], s["ids"], sch.n_wave, sch.n_wg, len(sch.noise_factors))
+    w = torch.from_numpy(weights).to(values.device)
+    mitigated_values, mitigated_terms = ops.zne_combine(term_values, w, t["term_ptr"], t["coeff"])
+    return ZNERun(mitigated_values, mitigated_terms, t["term_ptr"], values, term_values, norm, batch, sch, weights)
+
+
+def zne_expectation_values(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None,
+                           strategy: Optional[ZNEStrategy] = None, device="cuda"):
+    """``(mitigated_values [B], mitigated_terms [n_terms], term_ptr [B + 1], per_factor_values [F, B])``, tensors on ``device``.
+    ``noise=None`` is allowed (state vectors up to 11 qubits): pointless as mitigation, every factor then gives the same value up
+    to rounding."""
+    run = zne_run(circuits, observables, noise, strategy, device)
+    return run.mitigated_values, run.mitigated_terms, run.term_ptr, run.values
+
+
+# ---- the decorator ---------------------------------------------------------------------------------------------------------------
+def _zne_metadata(strategy: ZNEStrategy, achieved: np.ndarray, per_factor: np.ndarray, k: int) -> dict:
+    return {"noise_factors": tuple(float(f) for f in strategy.noise_factors), "achieved_factors": tuple(float(a) for a in achieved[:, k]),
+            "values": tuple(float(v) for v in per_factor[:, k]), "noise_amplifier": repr(strategy.noise_amplifier),
+            "extrapolator": repr(strategy.extrapolator)}
+
+
+class ZNEJob:
+    """The job of a ``zne(cls)`` run.  The fused path has its values when it is built; the generic path combines the F * B values of
+    the wrapped estimator's job when ``result()`` is asked for."""
+
+    def __init__(self, strategy: ZNEStrategy, achieved: np.ndarray, n_circuits: int, job_id: str, values=None, per_factor=None,
+                 base_job=None):
+        self._strategy, self._achieved, self._n, self._job_id = strategy, achieved, n_circuits, job_id
+        self._values, self._per_factor, self._base_job = values, per_factor, base_job
+
+    def result(self):
+        meta = [{} for _ in range(self._n)]
+        if self._values is None:
+            base = self._base_job.result()
+            self._per_factor = np.asarray(base.values, dtype=np.float64).reshape(len(self._strategy.noise_factors), self._n)
+            self._values = np.asarray(self._strategy.extrapolator.extrapolate(self._strategy.noise_factors, self._per_factor))
+            meta = [dict(m) for m in list(base.metadata)[:self._n]] if len(base.metadata) >= self._n else meta
+        for k in range(self._n):
+            meta[k]["zne"] = _zne_metadata(self._strategy, self._achieved, self._per_factor, k)
+        return make_estimator_result(np.asarray(self._values, dtype=np.float64), meta)
+
+    def job_id(self) -> str:
+        return self._job_id
+
+    def status(self):
+        return "DONE" if self._base_job is None else self._base_job.status()
+
+    def submit(self):
+        return None if self._base_job is None else self._base_job.submit()
+
+    def cancel(self):
+        return False if self._base_job is None else self._base_job.cancel()
+
+
+def zne(cls):
+    """Decorator in the style of ``learning(...)`` / ``ngem(...)``: ``zne(Estimator)`` is an estimator class that accepts
+    ``zne_strategy=`` at construction and as a run option and returns zero-noise-extrapolated values;
+    ``result().metadata[k]["zne"]`` holds the requested and achieved factors and the per-factor values.
+
+    Around :class:`DeviceEstimator` it takes the fused path (:func:`zne_run`: one lowering, schedules, two calls).  Around any other
+    estimator class it folds the IR (:func:`fold_circuit`), submits the F * B circuits through the wrapped ``_run`` in one job and
+    combines with the same weights on the host; circuits must arrive bound there."""
+    from .run import DeviceEstimator
+
+    fused = isinstance(cls, type) and issubclass(cls, DeviceEstimator)
+
+    def __init__(self, *args, zne_strategy: Optional[ZNEStrategy] = None, **kwargs):
+        cls.__init__(self, *args, **kwargs)
+        self._zne_strategy = zne_strategy or ZNEStrategy()
+        self._zne_count = 0
+
+    def _run(self, circuits, observables, parameter_values, **run_options):
+        strategy = run_options.pop("zne_strategy", None) or self._zne_strategy
+        circuits, observables, parameter_values = list(circuits), list(observables), list(parameter_values)
+        self._zne_count += 1
+        if fused:
+            for k, p in enumerate(parameter_values):
+                if len(p):
+                    raise ValueError(f"{type(self).__name__}: circuit {k} comes with {len(p)} parameter values; circuits must arrive bound")
+            run = zne_run(circuits, observables, self._noise, strategy, self._device)
+            return ZNEJob(strategy, run.schedules.achieved, len(circuits), f"zne-sim-{self._zne_count}",
+                          values=run.mitigated_values.cpu().numpy(), per_factor=run.values.cpu().numpy())
+        parsed = [Circuit.from_any(c) for c in circuits]
+        folded, achieved = [], []
+        for lam in strategy.noise_factors:
+            folded += [fold_circuit(c, lam, strategy.noise_amplifier) for c in parsed]
+            achieved.append([achieved_factor(sum(strategy.noise_amplifier.matches(op.name, len(op.qubits)) for op in c.ops), lam)
+                             for c in parsed])
+        n_f = len(strategy.noise_factors)
+        base = cls._run(self, folded, observables * n_f, parameter_values * n_f, **run_options)
+        return ZNEJob(strategy, np.asarray(achieved, dtype=np.float64).reshape(n_f, len(parsed)), len(parsed),
+                      f"zne-{self._zne_count}", base_job=base)
+
+    return type(f"ZNE{cls.__name__}", (cls,), {"__init__": __init__, "_run": _run, "__doc__": cls.__doc__})

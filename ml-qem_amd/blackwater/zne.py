@@ -1,0 +1,8 @@
+"""Zero-noise extrapolation under the name the reference imports it by (``from zne import zne, ZNEStrategy``,
+``from zne.noise_amplification import LocalFoldingAmplifier``, ``from zne.extrapolation import LinearExtrapolator``): everything
+lives in :mod:`blackwater.sim.zne`."""
+from .sim.zne import *  # noqa: F401,F403
+from .sim.zne import (CubicExtrapolator, CxAmplifier, GlobalFoldingAmplifier, LinearExtrapolator, LocalFoldingAmplifier,  # noqa: F401
+                      PolynomialExtrapolator, QuadraticExtrapolator, QuarticExtrapolator, RichardsonExtrapolator, Schedules,
+                      TwoQubitAmplifier, ZNEJob, ZNERun, ZNEStrategy, achieved_factor, build_schedules, fold_circuit, fold_counts,
+                      inverse_op, zne, zne_expectation_values, zne_run)

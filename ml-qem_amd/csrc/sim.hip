@@ -21,6 +21,12 @@
 //   quad       a 4x4 matrix on bits (a, b); the one-qubit depolarising map on (q, q + n)
 //   hex        the two-qubit depolarising map on (a, b, a + n, b + n): 16 entries, closed form
 // Expectation values are reduced in a fixed order: lane-strided partial sums, a shuffle tree, then the waves in order through LDS.
+//
+// Folded runs (mlqem_sim_run_folded_f64) are two more instantiations of the same template: a run walks a schedule of
+// (op index << 1) | dagger entries over its circuit's records instead of the records in order, and a daggered entry applies the
+// record's inverse, formed by swapping and negating components as they are read (no arithmetic, so no new rounding).  The two
+// instantiations mlqem_sim_run_f64 launches compile to the instructions they had before the schedules existed.
+// mlqem_zne_combine_f64 is the weighted sum over the noise factors that extrapolates to zero noise.
 #include "common.hpp"
 
 namespace mlqem {
@@ -80,9 +86,10 @@ template <bool WG> struct SimCtx {
     sim_sync<WG>();
   }
 
-  // a 4x4 matrix on bits (a, b), basis index = bit a + 2 bit b
-  __device__ __forceinline__ void quad(int a, int b, const double* m, bool conj) {
+  // a 4x4 matrix on bits (a, b), basis index = bit a + 2 bit b; `tr` reads the record transposed (with conj: its inverse)
+  __device__ __forceinline__ void quad(int a, int b, const double* m, bool conj, bool tr = false) {
     const double s = conj ? -1.0 : 1.0;
+    const int rs = tr ? 2 : 8, cs = tr ? 8 : 2;   // strides of a row and of a column in the record
     const int lo = min(a, b), hi = max(a, b), ng = A >> 2;
     for (int g0 = 0; g0 < ng; g0 += T) {
       const int g = g0 + tid;
@@ -97,9 +104,9 @@ template <bool WG> struct SimCtx {
       }
 #pragma unroll
       for (int row = 0; row < 4; ++row) {
-        r[row] = cmul(sim_c{m[8 * row], s * m[8 * row + 1]}, e[0]);
+        r[row] = cmul(sim_c{m[rs * row], s * m[rs * row + 1]}, e[0]);
 #pragma unroll
-        for (int col = 1; col < 4; ++col) r[row] = cmac(r[row], sim_c{m[8 * row + 2 * col], s * m[8 * row + 2 * col + 1]}, e[col]);
+        for (int col = 1; col < 4; ++col) r[row] = cmac(r[row], sim_c{m[rs * row + cs * col], s * m[rs * row + cs * col + 1]}, e[col]);
       }
       if (live) {
 #pragma unroll
@@ -192,14 +199,20 @@ template <bool WG> struct SimCtx {
   }
 };
 
-template <bool WG>
+// FOLD = false: circuit ids[slot] runs its ops in order (mlqem_sim_run_f64).  FOLD = true: ids holds RUN numbers r = f * B + c, and
+// run r walks the schedule sched[sched_ptr[r] .. sched_ptr[r + 1]) of entries (k << 1) | dagger over circuit c's ops
+// (mlqem_sim_run_folded_f64); its outputs go to row f.  The four waves of a workgroup of the wave variant then have trip counts that
+// differ by the ratio of the noise factors: as before, nothing in that variant is a workgroup barrier.
+template <bool WG, bool FOLD>
 __global__ __launch_bounds__(kBlock) void sim_kernel(int B, const sim_i4* __restrict__ circ, const int64_t* __restrict__ op_ptr,
                                                      const sim_i4* __restrict__ ops, int64_t n_ops,
                                                      const double* __restrict__ params, int64_t n_params,
                                                      const int64_t* __restrict__ term_ptr, const sim_i4* __restrict__ terms,
                                                      const double* __restrict__ coeff, int64_t n_terms,
                                                      const int32_t* __restrict__ ids, int count, double* __restrict__ term_values,
-                                                     double* __restrict__ values, double* __restrict__ norm) {
+                                                     double* __restrict__ values, double* __restrict__ norm, int n_runs,
+                                                     const int64_t* __restrict__ sched_ptr, const int32_t* __restrict__ sched,
+                                                     int64_t n_sched) {
   __shared__ sim_c state[WG ? kSimMaxAmps : kBlock / kWave * kSimWaveAmps];
   __shared__ double red[8];
   SimCtx<WG> cx;
@@ -209,7 +222,9 @@ __global__ __launch_bounds__(kBlock) void sim_kernel(int B, const sim_i4* __rest
   cx.st = WG ? state : state + ((int)threadIdx.x >> 6) * kSimWaveAmps;
   cx.red = red;
   const int tid = cx.tid;
-  const int c = __builtin_amdgcn_readfirstlane(min(max(ids[slot], 0), B - 1));
+  const int run = FOLD ? __builtin_amdgcn_readfirstlane(min(max(ids[slot], 0), n_runs - 1)) : 0;
+  const int c = FOLD ? run % B : __builtin_amdgcn_readfirstlane(min(max(ids[slot], 0), B - 1));
+  const int row = FOLD ? run / B : 0;   // the noise factor's row of the outputs
   const sim_i4 info = circ[c];   // n_qubits, mode, trailing readout ops, reserved
   const bool density = info.y != 0;
   constexpr int kMaxBits = WG ? 11 : 8;
@@ -219,13 +234,20 @@ __global__ __launch_bounds__(kBlock) void sim_kernel(int B, const sim_i4* __rest
   cx.A = A;
   const int64_t ob = min(max(op_ptr[c], (int64_t)0), n_ops), oe = min(max(op_ptr[c + 1], ob), n_ops);
   const int n_op = __builtin_amdgcn_readfirstlane((int)min(oe - ob, (int64_t)0x7FFFFFFF));
-  const int n_main = n_op - min(max(info.z, 0), n_op);   // ops before the readout ops: Tr rho is taken there
+  int64_t sb = 0;
+  int n_step = n_op;   // steps this run takes: its ops, or the entries of its schedule
+  if (FOLD) {
+    sb = min(max(sched_ptr[run], (int64_t)0), n_sched);
+    const int64_t se = min(max(sched_ptr[run + 1], sb), n_sched);
+    n_step = __builtin_amdgcn_readfirstlane((int)min(se - sb, (int64_t)0x7FFFFFFF));
+  }
+  const int n_main = n_step - min(max(info.z, 0), n_step);   // steps before the readout ops: Tr rho is taken there
 
   for (int i = tid; i < A; i += cx.T) cx.st[i] = sim_c{i == 0 ? 1.0 : 0.0, 0.0};
   sim_sync<WG>();
 
   double nrm = 0.0;
-  for (int k = 0; k <= n_op; ++k) {
+  for (int k = 0; k <= n_step; ++k) {
     if (k == n_main) {   // <psi|psi> or Tr rho, before any readout op
       double part = 0.0;
       const int cnt = density ? 1 << n : A, mul = density ? (1 << n) + 1 : 1;
@@ -238,19 +260,35 @@ __global__ __launch_bounds__(kBlock) void sim_kernel(int B, const sim_i4* __rest
       nrm = cx.reduce(part, 0);
       if (WG) __syncthreads();   // red[0..3] is free again
     }
-    if (k == n_op) break;
-    const sim_i4 op = ops[ob + k];   // kind, q0, q1, offset into params
+    if (k == n_step) break;
+    int at = k;
+    bool dg = false;   // apply the inverse of the record
+    if (FOLD) {
+      if (n_op == 0) continue;   // nothing an entry could name (wave-uniform; workgroup-uniform in the workgroup variant)
+      const int entry = __builtin_amdgcn_readfirstlane(sched[sb + k]);
+      at = min(max(entry >> 1, 0), n_op - 1);
+      dg = entry & 1;
+    }
+    const sim_i4 op = ops[ob + at];   // kind, q0, q1, offset into params
     const int kind = __builtin_amdgcn_readfirstlane(op.x);
     const int q0 = __builtin_amdgcn_readfirstlane(min(max(op.y, 0), n - 1)), q1 = __builtin_amdgcn_readfirstlane(min(max(op.z, 0), n - 1));
     const int64_t po = min((int64_t)max(op.w, 0), n_params - kSimParamPad);
     const double* m = params + po;
     switch (kind) {
       case MLQEM_SIM_OP_U1:
+        if (FOLD) {   // the inverse swaps the off-diagonal entries and negates the imaginary parts: no arithmetic, no rounding
+          const int o01 = dg ? 4 : 2, o10 = dg ? 2 : 4;
+          const sim_c u00{m[0], dg ? -m[1] : m[1]}, u01{m[o01], dg ? -m[o01 + 1] : m[o01 + 1]},
+              u10{m[o10], dg ? -m[o10 + 1] : m[o10 + 1]}, u11{m[6], dg ? -m[7] : m[7]};
+          cx.pair(nbits, q0, u00, u01, u10, u11, 1);
+          if (density) cx.pair(nbits, q0 + n, sim_c{u00.x, -u00.y}, sim_c{u01.x, -u01.y}, sim_c{u10.x, -u10.y}, sim_c{u11.x, -u11.y}, 1);
+          break;
+        }
         cx.pair(nbits, q0, sim_c{m[0], m[1]}, sim_c{m[2], m[3]}, sim_c{m[4], m[5]}, sim_c{m[6], m[7]}, 1);
         if (density) cx.pair(nbits, q0 + n, sim_c{m[0], -m[1]}, sim_c{m[2], -m[3]}, sim_c{m[4], -m[5]}, sim_c{m[6], -m[7]}, 1);
         break;
       case MLQEM_SIM_OP_DIAG1: {
-        const sim_c d0{m[0], m[1]}, d1{m[2], m[3]};
+        const sim_c d0{m[0], dg ? -m[1] : m[1]}, d1{m[2], dg ? -m[3] : m[3]};
         if (density) {
           cx.element([&](int i) {   // d[row bit] conj(d[column bit])
             const bool r = (i >> q0) & 1, cc = (i >> (q0 + n)) & 1;
@@ -284,8 +322,8 @@ __global__ __launch_bounds__(kBlock) void sim_kernel(int B, const sim_i4* __rest
         });
         break;
       case MLQEM_SIM_OP_U2:
-        cx.quad(q0, q1, m, false);
-        if (density) cx.quad(q0 + n, q1 + n, m, true);
+        cx.quad(q0, q1, m, dg, dg);   // the inverse: the record read transposed and conjugated
+        if (density) cx.quad(q0 + n, q1 + n, m, !dg, dg);
         break;
       case MLQEM_SIM_OP_DEPOL1:
         if (density) cx.depol1(n, q0, m[0]);
@@ -327,13 +365,36 @@ __global__ __launch_bounds__(kBlock) void sim_kernel(int B, const sim_i4* __rest
     }
     const double tv = cx.reduce(part, t & 1);
     if (tid == 0) {
-      term_values[tb + t] = tv;
+      term_values[(FOLD ? (int64_t)row * n_terms : (int64_t)0) + tb + t] = tv;
       total = total + coeff[tb + t] * tv;
     }
   }
   if (tid == 0) {
-    values[c] = total;
-    norm[c] = nrm;
+    values[(FOLD ? (int64_t)row * B : (int64_t)0) + c] = total;
+    norm[(FOLD ? (int64_t)row * B : (int64_t)0) + c] = nrm;
+  }
+}
+
+// Zero-noise extrapolation of exact values is a weighted sum over the noise factors.  Thread i < n_terms writes mitigated term i;
+// thread c < B forms the same sums again for its own terms (the same operations in the same order, so the same bits) and adds
+// coeff * term in term order.  Every product is a fused multiply-add, written out so that the order is the source's.
+__device__ __forceinline__ double zne_term(const double* __restrict__ tv, const double* __restrict__ w, int F, int64_t n_terms, int64_t t) {
+  double acc = w[0] * tv[t];
+  for (int f = 1; f < F; ++f) acc = __builtin_fma(w[f], tv[(int64_t)f * n_terms + t], acc);
+  return acc;
+}
+
+__global__ __launch_bounds__(kBlock) void zne_combine_kernel(int F, const double* __restrict__ tv, const double* __restrict__ w,
+                                                             const int64_t* __restrict__ term_ptr, const double* __restrict__ coeff,
+                                                             int64_t n_terms, int64_t B, double* __restrict__ mterms,
+                                                             double* __restrict__ mvalues) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i < n_terms) mterms[i] = zne_term(tv, w, F, n_terms, i);
+  if (i < B) {
+    const int64_t tb = min(max(term_ptr[i], (int64_t)0), n_terms), te = min(max(term_ptr[i + 1], tb), n_terms);
+    double total = 0.0;
+    for (int64_t t = tb; t < te; ++t) total = __builtin_fma(coeff[t], zne_term(tv, w, F, n_terms, t), total);
+    mvalues[i] = total;
   }
 }
 
@@ -361,12 +422,66 @@ extern "C" int mlqem_sim_run_f64(int64_t n_circuits, const int32_t* circ, const 
   const sim_i4* ti = reinterpret_cast<const sim_i4*>(terms);
   if (n_wave > 0) {
     const int64_t blocks = ceil_div(n_wave, (int64_t)(kBlock / kWave));
-    hipLaunchKernelGGL(sim_kernel<false>, dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), (int)n_circuits, ci, op_ptr, oi,
-                       n_ops, params, n_params, term_ptr, ti, coeff, n_terms, ids, (int)n_wave, term_values, values, norm);
+    hipLaunchKernelGGL((sim_kernel<false, false>), dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), (int)n_circuits, ci, op_ptr,
+                       oi, n_ops, params, n_params, term_ptr, ti, coeff, n_terms, ids, (int)n_wave, term_values, values, norm, 0,
+                       (const int64_t*)nullptr, (const int32_t*)nullptr, (int64_t)0);
   }
   if (n_wg > 0) {
-    hipLaunchKernelGGL(sim_kernel<true>, dim3((unsigned)n_wg), dim3(kBlock), 0, as_stream(stream), (int)n_circuits, ci, op_ptr, oi,
-                       n_ops, params, n_params, term_ptr, ti, coeff, n_terms, ids + n_wave, (int)n_wg, term_values, values, norm);
+    hipLaunchKernelGGL((sim_kernel<true, false>), dim3((unsigned)n_wg), dim3(kBlock), 0, as_stream(stream), (int)n_circuits, ci, op_ptr,
+                       oi, n_ops, params, n_params, term_ptr, ti, coeff, n_terms, ids + n_wave, (int)n_wg, term_values, values, norm, 0,
+                       (const int64_t*)nullptr, (const int32_t*)nullptr, (int64_t)0);
   }
+  return launch_status();
+}
+
+extern "C" int mlqem_sim_run_folded_f64(int64_t n_circuits, int64_t n_factors, const int32_t* circ, const int64_t* op_ptr,
+                                        const mlqem_sim_op* ops, int64_t n_ops, const double* params, int64_t n_params,
+                                        const int64_t* term_ptr, const mlqem_sim_term* terms, const double* coeff, int64_t n_terms,
+                                        const int64_t* sched_ptr, const int32_t* sched, int64_t n_sched, const int32_t* ids,
+                                        int64_t n_wave, int64_t n_wg, double* term_values, double* values, double* norm,
+                                        mlqem_stream_t stream) {
+  begin_launches();
+  if (n_circuits < 0 || n_factors < 1 || n_ops < 0 || n_terms < 0 || n_sched < 0 || n_wave < 0 || n_wg < 0 || n_params < kSimParamPad)
+    return MLQEM_ERR_BAD_ARG;
+  if (n_circuits > 0x7FFFFFFFll || n_factors > 0x7FFFFFFFll || n_params > 0x7FFFFFFFll || n_sched > 0x7FFFFFFFll)
+    return MLQEM_ERR_UNSUPPORTED;
+  const int64_t n_runs = n_factors * n_circuits;   // both below 2^31: no overflow
+  if (n_runs > 0x7FFFFFFFll) return MLQEM_ERR_UNSUPPORTED;
+  if (n_wave + n_wg > n_runs) return MLQEM_ERR_BAD_ARG;
+  if (n_wave + n_wg == 0) return MLQEM_OK;
+  if (!circ || !op_ptr || !params || !term_ptr || !sched_ptr || !ids || !values || !norm || (n_ops > 0 && !ops) || (n_sched > 0 && !sched) ||
+      (n_terms > 0 && (!terms || !coeff || !term_values)))
+    return MLQEM_ERR_BAD_ARG;
+  if (!aligned_to(circ, 16) || !aligned_to(ops, 16) || !aligned_to(terms, 16) || !aligned_to(sched_ptr, 8) || !aligned_to(sched, 4))
+    return MLQEM_ERR_BAD_ARG;
+  const sim_i4* ci = reinterpret_cast<const sim_i4*>(circ);
+  const sim_i4* oi = reinterpret_cast<const sim_i4*>(ops);
+  const sim_i4* ti = reinterpret_cast<const sim_i4*>(terms);
+  if (n_wave > 0) {
+    const int64_t blocks = ceil_div(n_wave, (int64_t)(kBlock / kWave));
+    hipLaunchKernelGGL((sim_kernel<false, true>), dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), (int)n_circuits, ci, op_ptr,
+                       oi, n_ops, params, n_params, term_ptr, ti, coeff, n_terms, ids, (int)n_wave, term_values, values, norm,
+                       (int)n_runs, sched_ptr, sched, n_sched);
+  }
+  if (n_wg > 0) {
+    hipLaunchKernelGGL((sim_kernel<true, true>), dim3((unsigned)n_wg), dim3(kBlock), 0, as_stream(stream), (int)n_circuits, ci, op_ptr,
+                       oi, n_ops, params, n_params, term_ptr, ti, coeff, n_terms, ids + n_wave, (int)n_wg, term_values, values, norm,
+                       (int)n_runs, sched_ptr, sched, n_sched);
+  }
+  return launch_status();
+}
+
+extern "C" int mlqem_zne_combine_f64(int64_t n_factors, int64_t n_circuits, const double* term_values, const double* weights,
+                                     const int64_t* term_ptr, const double* coeff, int64_t n_terms, double* mitigated_terms,
+                                     double* mitigated_values, mlqem_stream_t stream) {
+  begin_launches();
+  if (n_factors < 1 || n_circuits < 0 || n_terms < 0) return MLQEM_ERR_BAD_ARG;
+  if (n_factors > 0x7FFFFFFFll || n_circuits > 0x7FFFFFFFll || n_terms > 0x7FFFFFFFll) return MLQEM_ERR_UNSUPPORTED;
+  if (n_circuits == 0 && n_terms == 0) return MLQEM_OK;
+  if (!weights || (n_circuits > 0 && (!term_ptr || !mitigated_values)) || (n_terms > 0 && (!term_values || !coeff || !mitigated_terms)))
+    return MLQEM_ERR_BAD_ARG;
+  const int64_t blocks = ceil_div(n_circuits > n_terms ? n_circuits : n_terms, (int64_t)kBlock);
+  hipLaunchKernelGGL(zne_combine_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), (int)n_factors, term_values, weights,
+                     term_ptr, coeff, n_terms, n_circuits, mitigated_terms, mitigated_values);
   return launch_status();
 }

@@ -318,6 +318,24 @@ typedef struct mlqem_fanout_tables {
 int mlqem_linear_fanout_tables_f32(const mlqem_fanout_tables* d, int64_t N, const int32_t* x_rows, float drop_p, uint64_t seed,
                                    const uint64_t* seed_counter, mlqem_stream_t stream);
 
+/* The same launch with a CHAINED projection on one of its blocks (an additive symbol, the ABI version is unchanged): after block
+ * `block`'s epilogue (bias, row scale, ReLU, dropout) the values a lane holds are the operand of a second product,
+ *     Y2 = (Y_block W2^T) * rowscale2            W2: [out_cols, d->out_cols] row-major, out_cols <= 12, rowscale2 optional (NULL)
+ * written to y ([N, out_cols], padded rows) by the same launch -- the layer above is projected from registers instead of from a
+ * second pass over Y_block (GCN conv2's dinv * (h1 W2^T) from conv1's activation).  Y_block and every other block carry the values
+ * of mlqem_linear_fanout_tables_f32, bit for bit; Y2 is the k-ordered fp32 chain over Y_block's d->out_cols columns.
+ * chain == NULL is mlqem_linear_fanout_tables_f32. */
+typedef struct mlqem_fanout_chain {
+  int32_t block, out_cols;
+  void* y;
+  int64_t ldy;
+  const float* w;
+  const float* rowscale;
+} mlqem_fanout_chain;
+int mlqem_linear_fanout_tables_chain_f32(const mlqem_fanout_tables* d, const mlqem_fanout_chain* chain, int64_t N,
+                                         const int32_t* x_rows, float drop_p, uint64_t seed, const uint64_t* seed_counter,
+                                         mlqem_stream_t stream);
+
 size_t mlqem_linear_wgrad_workspace_bytes(int I, int O);
 
 /* gw[o,i] (+)= sum_n gy[n,o] * x[n,i] ;  gb[o] (+)= sum_n gy[n,o]  (gb may be NULL).  Matrix-core partial sums per
@@ -477,6 +495,20 @@ int mlqem_layer_colstats_merge(int mode, const double* records, int world, int C
 int mlqem_linear_bwd_fused_f32(const float* gy, int64_t ldgy, const float* gb_src, int64_t ldgbs, const float* x, int64_t ldx,
                                const float* w, int gate, float gate_scale, float* gx, int64_t ldgx, float* gw2, float* gb2,
                                int64_t N, int I, int O, void* workspace, size_t workspace_bytes, mlqem_stream_t stream);
+
+/* mlqem_linear_bwd_fused_f32 that ALSO takes the weight gradient of the layer below against a table (additive symbols, the ABI
+ * version is unchanged): with row n of that layer's input being row table_rows[n] of table ([M, T], padded rows, 17 <= T <= 24;
+ * table_rows == NULL: row n),
+ *   gwt[0:I, 0:T] = gx^T table[table_rows]       (gwt: [I, T] row-major)
+ * from the gx tile the pass holds, so gx need not exist in memory: gx == NULL skips its store (GCN conv1 as a projection of the
+ * A^ x rows: conv2's backward leaves conv1's weight gradient, and the gated gradient between the two is never written or read).
+ * gx (where requested), gw2 and gb2 carry the values of mlqem_linear_bwd_fused_f32, bit for bit.
+ * workspace: mlqem_linear_bwd_fused_table_workspace_bytes(I, T). */
+size_t mlqem_linear_bwd_fused_table_workspace_bytes(int I, int T);
+int mlqem_linear_bwd_fused_table_f32(const float* gy, int64_t ldgy, const float* gb_src, int64_t ldgbs, const float* x, int64_t ldx,
+                                     const float* w, int gate, float gate_scale, float* gx, int64_t ldgx, float* gw2, float* gb2,
+                                     const float* table, int64_t ldt, const int32_t* table_rows, int T, float* gwt,
+                                     int64_t N, int I, int O, void* workspace, size_t workspace_bytes, mlqem_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Pooling over graphs.  Replaces global_mean_pool (docs/tutorials/gnn.py:114; 01_ngem.ipynb cell [9]).

@@ -58,6 +58,13 @@ class FanoutTables(ctypes.Structure):
                 ("act", ctypes.c_int32 * MAX_COL_PARTS)]
 
 
+class FanoutChain(ctypes.Structure):
+    """``mlqem_fanout_chain``: a second projection of one block's post-activation values, written by the fan-out's launch."""
+
+    _fields_ = [("block", ctypes.c_int32), ("out_cols", ctypes.c_int32), ("y", c_void_p), ("ldy", c_int64), ("w", c_void_p),
+                ("rowscale", c_void_p)]
+
+
 class ForestFitState(ctypes.Structure):
     """``mlqem_forest_fit_state``: the inputs and the workspace of one chunk of trees of a forest fit."""
 
@@ -96,6 +103,7 @@ SIGNATURES = {
     "mlqem_linear_wgrad_bf16_f32": (_I, [_P, _L, _P, _L, _P, _P, _L, _I, _I, _I, _P, _S, _P]),
     "mlqem_linear_parts_f32": (_I, [_P, _P, _P, _I, _P, _P, _P, _L, _P, _L, _F, _P, _P]),
     "mlqem_linear_fanout_tables_f32": (_I, [_P, _L, _P, _F, _U, _P, _P]),
+    "mlqem_linear_fanout_tables_chain_f32": (_I, [_P, _P, _L, _P, _F, _U, _P, _P]),
     "mlqem_linear_wgrad_workspace_bytes": (_S, [_I, _I]),
     "mlqem_linear_wgrad_f32": (_I, [_P, _L, _P, _L, _P, _P, _L, _I, _I, _I, _P, _S, _P, _P]),
     "mlqem_linear_wgrad_parts_f32": (_I, [_P, _P, _L, _P, _P, _L, _I, _I, _P, _S, _P, _P]),
@@ -121,6 +129,9 @@ SIGNATURES = {
     "mlqem_layer_colstats_record_f32": (_I, [_I, _P, _P, _P, _L, _P, _P, _P, _P, _I, _F, _U, _P, _L, _I, _P, _P, _P, _P, _S, _P]),
     "mlqem_layer_colstats_merge": (_I, [_I, _P, _I, _I, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P]),
     "mlqem_linear_bwd_fused_f32": (_I, [_P, _L, _P, _L, _P, _L, _P, _I, _F, _P, _L, _P, _P, _L, _I, _I, _P, _S, _P]),
+    "mlqem_linear_bwd_fused_table_workspace_bytes": (_S, [_I, _I]),
+    "mlqem_linear_bwd_fused_table_f32": (_I, [_P, _L, _P, _L, _P, _L, _P, _I, _F, _P, _L, _P, _P, _P, _L, _P, _I, _P, _L, _I, _I, _P, _S,
+                                              _P]),
     "mlqem_pooled_head_f32": (_I, [_P, _L, _I, _P, _L, _P]),
     "mlqem_pooled_head_bwd_f32": (_I, [_P, _P, _L, _L, _I, _P, _P, _P, _P, _P]),
     "mlqem_segment_pool_workspace_bytes": (_S, [_L, _L, _I]),

@@ -434,6 +434,12 @@ _POOLED_GRAD_MIN_NODES = 1 << 16
 # Default: conv1 and the inner hop of cheb_conv1 are projections of table rows (_FamilyAGraph).
 _TABLE_GCN = os.environ.get("MLQEM_TABLE_GCN", "1") != "0"
 _TABLE_CHEB = os.environ.get("MLQEM_TABLE_CHEB", "1") != "0"
+# MLQEM_GCN_CHAIN=0: conv2's projection dinv * (h1 W2^T) is a launch of its own again (linear_parts over h1) instead of a second MFMA
+# chain on the registers that hold h1 in the table fan-out.  MLQEM_GCN_TABLE_WGRAD=0: conv2's fused backward writes the gated gradient
+# and a weight-gradient launch reads it back against the A^ x rows, instead of taking conv1's weight gradient from the tile it holds.
+# Both need the A^ x table (MLQEM_TABLE_GCN) and a hidden width <= 12 (A/B, one switch per join).
+_GCN_CHAIN = os.environ.get("MLQEM_GCN_CHAIN", "1") != "0"
+_GCN_TABLE_WGRAD = os.environ.get("MLQEM_GCN_TABLE_WGRAD", "1") != "0"
 
 _PARTS_MAX_COLS = 64   # mlqem_linear_parts_f32 keeps the weight fragments of I <= 64 concatenated columns in registers
 
@@ -518,7 +524,8 @@ _ChebGrads = namedtuple("_ChebGrads", "x b ws")
 _SAGESaved = namedtuple("_SAGESaved", "x wl wr y struct drop_p has_bias o x_gate_scale")
 _SAGEGrads = namedtuple("_SAGEGrads", "x wl bl wr")
 _GCNSaved = namedtuple("_GCNSaved", "x w y struct drop_p x_gate_scale")
-_GCNGrads = namedtuple("_GCNGrads", "x w b x_colsum", defaults=(None,))    # x_colsum: x.sum(0), from the fused backward only
+# x_colsum: x.sum(0), from the fused backward only; below_w: the weight gradient of the layer below against its table (then x is None)
+_GCNGrads = namedtuple("_GCNGrads", "x w b x_colsum below_w", defaults=(None, None))
 
 
 def _x_gate(sv):     # gx takes the mask of the layer below when that layer deferred it (see "Mask hand-over")
@@ -722,7 +729,9 @@ def _gcn_grad_blocks(sv, g, want_g=True):
     return [ops.csr_aggregate(g, s.out_ptr, s.out_dst, ell=s.out_ell, cscale=s.gcn_dinv, rscale=s.gcn_dinv, dself=s.derived("gcn_dself")), g]
 
 
-def _gcn_backward(sv, g, need_x, need_w, need_b):
+def _gcn_backward(sv, g, need_x, need_w, need_b, below_table=None):
+    """below_table: the rows the layer below projects (conv1 from the A^ x table).  Where the fused form runs, it then takes that layer's
+    weight gradient too (``below_w``) and the data gradient is not written (``x`` None); elsewhere the argument changes nothing."""
     x, w = sv.x, sv.w
     # hidden layer of width <= 12 (conv2): gated data gradient, weight and bias gradient from ONE pass (ops.linear_bwd_fused)
     fused = need_x and need_b and sv.x_gate_scale is not None and max(w.shape) <= 12
@@ -731,11 +740,16 @@ def _gcn_backward(sv, g, need_x, need_w, need_b):
     if pooled is not None:
         # the fused backward reads g only for the bias gradient: its column sums come from the bits, g is never written
         if fused and ops._fused_bwd_ok(gh, x):
+            if below_table is not None:
+                _, gw, _, colsum, gwt = ops.linear_bwd_fused_table(gh, x, w.contiguous(), below_table, gate_scale=sv.x_gate_scale, want_gx=False)
+                return _GCNGrads(None, gw, ops.pooled_grad_colsum(pooled), colsum, gwt)
             gx, gw, _, colsum = ops.linear_bwd_fused(gh, x, w.contiguous(), gate_scale=sv.x_gate_scale)
             return _GCNGrads(gx, gw, ops.pooled_grad_colsum(pooled), colsum)
         if g is None:
             g = pooled.materialise()
     if fused and ops._fused_bwd_ok(gh, g, x):
+        if below_table is not None:
+            return _GCNGrads(*ops.linear_bwd_fused_table(gh, x, w.contiguous(), below_table, gb_src=g, gate_scale=sv.x_gate_scale, want_gx=False))
         return _GCNGrads(*ops.linear_bwd_fused(gh, x, w.contiguous(), gb_src=g, gate_scale=sv.x_gate_scale))
     gx = ops.linear(gh, w.contiguous(), transposed=True, **_x_gate(sv)) if need_x else None
     gw = gb = None
@@ -1181,7 +1195,7 @@ class _FamilyAGraph(Function):
         # three times (GCN: dinv * x W^T | Cheb: x (W_0 - W_2)^T + b, x W_1^T, x W_2^T | SAGE: x W_l^T, x W_r^T + b), and in the
         # backward ONE weight-gradient pass over x serves all seven gradient blocks (see backward).
         fuse = ctx.fuse = x.shape[1] <= _PARTS_MAX_COLS and 6 * ((g1w.shape[0] + 3) // 4 * 4) <= 96
-        pre_g = pre_c = pre_s = None
+        pre_g = pre_c = pre_s = pre_g2 = None
         # Rows of an arena come with the arena's tables of A^ x and L^ x (constants of the dataset): A^ (x W^T) = (A^ x) W^T makes conv1
         # a projection of table rows with its bias / ReLU / dropout epilogue, and the inner Clenshaw hop of cheb_conv1 is
         # b_1 = x W_1^T + (L^ x)(2 W_2)^T -- neither is aggregated, forward or backward (their weight gradients are taken against
@@ -1199,6 +1213,10 @@ class _FamilyAGraph(Function):
                     blk(table=0, w=w0, w_minus=w2, bias=c1b)]
             spec += [blk(table=0, w=w1, table2=ic, w2=w2, scale2=2.0)] if ic is not None else [blk(table=0, w=w1), blk(table=0, w=w2)]
             spec += [blk(table=0, w=wl), blk(table=0, w=wr, bias=s1b)]
+            if ig is not None and _GCN_CHAIN and max(g2w.shape) <= 12:
+                # conv2's projection dinv * (h1 W2^T) from the registers that hold h1: no pass of its own over h1
+                pre_g2 = ops.padded_empty(n_, g2w.shape[0], x.device)
+                spec[0]["chain"] = dict(out=pre_g2, w=g2w.contiguous(), rowscale=struct.gcn_dinv)
             blocks = ops.linear_fanout_tables(tabs, xr.rows, n_, spec, drop_p=p1 if ig is not None else 0.0, seed=seed + 1)
             pre_g, pre_c, pre_s = blocks[0], blocks[1:-2], blocks[-2:]
         elif fuse:
@@ -1220,7 +1238,7 @@ class _FamilyAGraph(Function):
         # ... and since the backward reads that activation ONLY as the ReLU / dropout gate of the pool's gradient, the launch leaves
         # its sign bits (one byte per 16-byte slice) instead of the activation itself: h is never written, never read again
         pg = dict(graph_ptr=gptr, num_graphs=nb, weights=tg, mean=False, wmean=True, bits=True, store=False)
-        hg, g2 = _gcn_forward(h, g2w, g2b, struct, True, p1, seed + 2, defer_mask=True, x_gate_scale=k1, pool=pg)
+        hg, g2 = _gcn_forward(h, g2w, g2b, struct, True, p1, seed + 2, defer_mask=True, x_gate_scale=k1, pre=pre_g2, pool=pg)
         _, wg = ops.pooled_means(hg, pg)
         with torch.cuda.stream(side[0]):
             pc = dict(graph_ptr=gptr, num_graphs=nb, weights=tc, mean=True, wmean=True, bits=True, store=False)
@@ -1274,14 +1292,17 @@ class _FamilyAGraph(Function):
 
         # GCN branch, last layer first: pooled = wmean(h) W^T + b
         t = pooled_grad(None, ggw, "gcn", hg, k1, bg_)
-        r = _gcn_backward(g2, t, True, True, True)
+        tab_g, tab_c = ctx.tables
+        # with the A^ x table conv1's weight gradient is gx^T (A^ x): taken inside conv2's fused backward from the gx tile it holds
+        r = _gcn_backward(g2, t, True, True, True, below_table=tab_g if _GCN_TABLE_WGRAD else None)
         # conv1's bias gradient is the column sum of the gradient conv2's backward just wrote: taken there (by the fused form, else
         # None), the first-layer weight-gradient pass below reads six blocks instead of seven
         g2w, g2b, g1b_cs = r.w, r.b, r.x_colsum
-        tab_g, tab_c = ctx.tables
         o = g1.w.shape[0]
         new_gw = lambda: torch.empty((o, g1.x.shape[1]), dtype=torch.float32, device=g.device)
-        if tab_g is not None:
+        if r.below_w is not None:
+            bg, g1w = [], r.below_w[:o]
+        elif tab_g is not None:
             # conv1 = a projection of the A^ x rows: its weight gradient is gx^T (A^ x) with the gated gradient conv2's backward wrote,
             # nothing is aggregated; enqueued here, it runs while the other branches are still in their aggregations
             bg, g1w = [], new_gw()

@@ -611,7 +611,10 @@ def linear_fanout_tables(tables, rows, n, blocks, *, drop_p=0.0, seed=0):
     """One launch for output blocks projected from up to three padded tables that share the row map ``rows`` (int32 [n] or None):
     every entry of ``blocks`` is a dict with ``out`` (a ``padded_empty`` [n, O] buffer), ``table`` and ``w`` ([O, I]), and optionally
     ``w_minus`` (subtracted from ``w``), ``table2`` / ``w2`` / ``scale2`` (a second term scale2 * T[table2] w2^T), ``bias``, ``rowscale``
-    and ``act`` (ReLU + dropout ``drop_p`` with the aggregation epilogue's mask for ``seed``): mlqem_linear_fanout_tables_f32."""
+    and ``act`` (ReLU + dropout ``drop_p`` with the aggregation epilogue's mask for ``seed``): mlqem_linear_fanout_tables_f32.
+    ``chain`` (one block of a launch at most): a dict with ``out`` (a ``padded_empty`` [n, O2 <= 12] buffer), ``w`` ([O2, O]) and
+    optionally ``rowscale``: out = (block's values @ w.T) * rowscale from the same launch (mlqem_linear_fanout_tables_chain_f32); the
+    blocks themselves carry the same values with or without it."""
     import ctypes as _ct
 
     d = _lib.FanoutTables()
@@ -654,9 +657,27 @@ def linear_fanout_tables(tables, rows, n, blocks, *, drop_p=0.0, seed=0):
         d.w2[k] = weight(b.get("w2"), "w2")
         d.w2_table[k], d.w2_scale[k] = int(b.get("table2") or 0), float(b.get("scale2", 1.0))
         d.bias[k], d.rowscale[k], d.act[k] = _p(b.get("bias")), _p(b.get("rowscale")), 1 if b.get("act") else 0
-    code = _lib.load().mlqem_linear_fanout_tables_f32(_ct.addressof(d), n, _p(rows), float(drop_p), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                                      _p(_seed_counter) if drop_p > 0 else None, _stream())
-    _lib.check(code, "mlqem_linear_fanout_tables_f32")
+    chains = [(k, b["chain"]) for k, b in enumerate(blocks) if b.get("chain") is not None]
+    tail = (n, _p(rows), float(drop_p), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(_seed_counter) if drop_p > 0 else None, _stream())
+    if not chains:
+        code = _lib.load().mlqem_linear_fanout_tables_f32(_ct.addressof(d), *tail)
+        _lib.check(code, "mlqem_linear_fanout_tables_f32")
+        return [b["out"] for b in blocks]
+    if len(chains) > 1:
+        raise ValueError("linear_fanout_tables: one chained block per launch")
+    k, c = chains[0]
+    out2, w2 = c["out"], c["w"]
+    _mat(out2, f"blocks[{k}].chain.out")
+    o2, ld2 = out2.shape[1], int(out2.stride(0))
+    if tuple(out2.shape) != (n, o2) or not 1 <= o2 <= 12 or ld2 < (o2 + 3) // 4 * 4 or ld2 % 4 or out2.data_ptr() % 16:
+        raise ValueError(f"blocks[{k}].chain.out: needs a padded [{n}, <= 12] buffer (ops.padded_empty)")
+    if not w2.is_cuda or w2.dtype != torch.float32 or tuple(w2.shape) != (o2, o) or not w2.is_contiguous():
+        raise ValueError(f"blocks[{k}].chain.w must be a contiguous fp32 cuda tensor of shape {(o2, o)}")
+    _vec(c.get("rowscale"), "chain.rowscale", n)
+    ch = _lib.FanoutChain()
+    ch.block, ch.out_cols, ch.y, ch.ldy, ch.w, ch.rowscale = k, o2, out2.data_ptr(), ld2, w2.data_ptr(), _p(c.get("rowscale"))
+    code = _lib.load().mlqem_linear_fanout_tables_chain_f32(_ct.addressof(d), _ct.addressof(ch), *tail)
+    _lib.check(code, "mlqem_linear_fanout_tables_chain_f32")
     return [b["out"] for b in blocks]
 
 
@@ -1050,6 +1071,36 @@ def linear_bwd_fused(gy, x, w, gb_src=None, gate_scale=None):
                                           _p(gb2), n, i, o, _p(ws), need, _stream())
     _lib.check(code, "mlqem_linear_bwd_fused_f32")
     return gx, gw2[:o], gb2[12:12 + o], gw2[24]
+
+
+def linear_bwd_fused_table(gy, x, w, table, gb_src=None, gate_scale=None, want_gx=True):
+    """``linear_bwd_fused`` plus the weight gradient of the layer BELOW where that layer projects rows of ``table`` (a ``RowsOf`` or a
+    padded [n, 17..24] matrix): (gx, gw, gb, gx_colsum, gx.T @ table).  ``want_gx=False``: gx is not written (None) -- nothing else
+    changes (mlqem_linear_bwd_fused_table_f32)."""
+    n, o = gy.shape
+    i = x.shape[1]
+    tt, ldt, tn, t_rows = _x_operand(table, "table")
+    tc = table.shape[1]
+    if tuple(w.shape) != (o, i) or not w.is_contiguous() or x.shape[0] != n or tn != n or (gb_src is not None and gb_src.shape != gy.shape):
+        raise ValueError("linear_bwd_fused_table: shape mismatch")
+    if not _fused_bwd_ok(gy, x, *([gb_src] if gb_src is not None else [])):
+        raise ValueError("linear_bwd_fused_table: operands must be 2-D fp32 matrices of <= 12 columns in the padded row layout")
+    ldt = int(tt.stride(0))                     # a one-row table still has to own its padding
+    if not 16 < tc <= 24 or ldt < (tc + 3) // 4 * 4 or ldt % 4 or tt.data_ptr() % 16:
+        raise ValueError(f"linear_bwd_fused_table: table needs 17..24 columns in the padded row layout, got {tuple(tt.shape)} with stride {ldt}")
+    gx = padded_empty(n, i, gy.device) if want_gx else None
+    gw2 = torch.empty((25, i), dtype=torch.float32, device=gy.device)
+    gb2 = torch.empty(25, dtype=torch.float32, device=gy.device)
+    gwt = torch.empty((i, tc), dtype=torch.float32, device=gy.device)
+    lib = _lib.load()
+    need = lib.mlqem_linear_bwd_fused_table_workspace_bytes(i, tc)
+    ws = _wgrad_workspace(gy.device, need)
+    ld = lambda t: int(t.stride(0))
+    code = lib.mlqem_linear_bwd_fused_table_f32(_p(gy), ld(gy), _p(gb_src), ld(gb_src) if gb_src is not None else 0, _p(x), ld(x), _p(w),
+                                                0 if gate_scale is None else 1, float(gate_scale or 1.0), _p(gx), ld(gx) if want_gx else 0,
+                                                _p(gw2), _p(gb2), _p(tt), ldt, t_rows, tc, _p(gwt), n, i, o, _p(ws), need, _stream())
+    _lib.check(code, "mlqem_linear_bwd_fused_table_f32")
+    return gx, gw2[:o], gb2[12:12 + o], gw2[24], gwt
 
 
 def _fused_bwd_ok(*mats):

@@ -805,13 +805,29 @@ struct FanTablesArgs {
   const float* bk[kMaxParts]; const float* rsk[kMaxParts]; int actk[kMaxParts];
   int64_t N; const int32_t* xrows;
   float drop_p; uint64_t seed; const uint64_t* seed_counter;
+  // the chained projection of block chain_blk (CHAIN kernels only): y2 = (Y_blk w2c^T) * rs2, y2c <= 12 real columns in rows of y2w
+  int chain_blk; float* y2; int64_t ldy2; const float* w2c; const float* rs2; int y2c, y2w;
 };
 
-template <int NT>
+// CHAIN: block chain_blk's post-activation values -- lane (lr, lq) ends its epilogue holding Y[row lr][4 lq .. + 3], which IS the B
+// operand layout of a second MFMA chain over k = the block's columns -- are projected once more from the registers that hold them
+// (weight fragment w2c[o][4 lq + s] staged like s_w) and written as a second output: the layer above needs no pass of its own over Y.
+template <int NT, bool CHAIN = false>
 __global__ __launch_bounds__(kBlock) void linear_fanout_tables_kernel(const FanTablesArgs a) {
   __shared__ float4 s_w[kFanTerms][2][kWave];
   __shared__ float s_b[kMaxParts][16];
+  __shared__ float4 s_w2[CHAIN ? kWave : 1];
   const int tid = threadIdx.x;
+  if (CHAIN && tid < kWave) {
+    const int o = tid & 15, lq = tid >> 4;
+    float v[4];
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4) {
+      const int k = 4 * lq + s4;
+      v[s4] = (o < a.y2c && k < a.yc) ? a.w2c[(int64_t)o * a.yc + k] : 0.f;
+    }
+    s_w2[tid] = make_float4(v[0], v[1], v[2], v[3]);
+  }
   for (int idx = tid; idx < a.nterms * 2 * kWave; idx += kBlock) {
     const int term = idx / (2 * kWave), g = (idx / kWave) % 2, l = idx % kWave;
     const int o = l & 15, lq = l >> 4;
@@ -867,6 +883,8 @@ __global__ __launch_bounds__(kBlock) void linear_fanout_tables_kernel(const FanT
     float rsv[kMaxParts];
 #pragma unroll
     for (int blk = 0; blk < kMaxParts; ++blk) rsv[blk] = (blk < a.yn && a.rsk[blk] && row_ok) ? a.rsk[blk][row] : 1.f;
+    float rs2 = 1.f;                           // the chain's row scale: a load like the others, before the tile's first store
+    if (CHAIN) rs2 = (a.rs2 && row_ok) ? a.rs2[row] : 1.f;
     const int xmap2 = map_at(t + 2 * n_waves);
     load_x(t + n_waves, xnext, an0, an1);      // a tile beyond the end re-reads row N - 1 and is never used
     xnext = xmap2;
@@ -897,7 +915,8 @@ __global__ __launch_bounds__(kBlock) void linear_fanout_tables_kernel(const FanT
       const float rs = rsv[blk];
       f32x4 acc = term(blk, f32x4{0.f, 0.f, 0.f, 0.f});
       if (a.bslot[blk] >= 0) acc = term(a.bslot[blk], acc);
-      if (!row_ok || !store_lane) continue;
+      const bool chained = CHAIN && blk == a.chain_blk;      // workgroup-uniform: the chain's MFMAs need the whole wave
+      if ((!row_ok || !store_lane) && !chained) continue;
       float v[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -914,7 +933,26 @@ __global__ __launch_bounds__(kBlock) void linear_fanout_tables_kernel(const FanT
           for (int r = 0; r < 4; ++r) v[r] = keep[r] ? v[r] * keep_scale : 0.f;
         }
       }
-      vstore_nt<4>(a.yp[blk] + row * a.ldy[blk] + 4 * lq, v);
+      if (!CHAIN || (row_ok && store_lane)) vstore_nt<4>(a.yp[blk] + row * a.ldy[blk] + 4 * lq, v);
+      if (chained) {
+        // columns >= yc are zero by construction (pad weights and bias are staged as zeros) unless a table held a non-finite
+        // value: nothing but zeros may reach the MFMA from there, whatever the lane computed (lanes beyond the block's width too)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (4 * lq + r >= a.yc) v[r] = 0.f;
+        const float4 w4 = s_w2[lane];
+        f32x4 acc2 = f32x4{0.f, 0.f, 0.f, 0.f};
+        acc2 = mfma16x16x4(w4.x, v[0], acc2);
+        acc2 = mfma16x16x4(w4.y, v[1], acc2);
+        acc2 = mfma16x16x4(w4.z, v[2], acc2);
+        acc2 = mfma16x16x4(w4.w, v[3], acc2);
+        if (row_ok && 4 * lq < a.y2w) {
+          float v2[4];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v2[r] = acc2[r] * rs2;
+          vstore_nt<4>(a.y2 + row * a.ldy2 + 4 * lq, v2);
+        }
+      }
     }
 #pragma unroll
     for (int j = 0; j < NT; ++j) { av0[j] = an0[j]; av1[j] = an1[j]; }
@@ -1234,11 +1272,25 @@ struct BwdFusedArgs {
   float gate_scale; int gate;
   float* gx; int64_t ldgx; float* partial;
   int64_t N; int I; int O;
+  int alias;                                // gb_src IS gy: one load, one accumulator (block 1 of the image repeats block 0)
+  // TABLE: the weight gradient of the layer below against rows of a table, gwt = gx^T tab[trows]
+  const float* tab; int64_t ldt; const int32_t* trows; int T; float* partial_t;
 };
 
+// gb_src == gy (the caller takes the bias gradient elsewhere, or it IS the column sum of gy): the tile is loaded once and the
+// second accumulator is not run -- its image, [gy^T x | sum gy], is the first accumulator's, bit for bit (same operands, same order).
+// TABLE: the layer below is a projection of table rows (GCN conv1 from the A^ x table), so its weight gradient gx^T tab[trows] is
+// taken here from the gated gx tile the wave holds: the 16 x 24 table tile of the wave's rows is fetched through the row map (whose
+// entries are requested a tile ahead of the rows: the table-row loads are then no dependent round trip) into LDS next to the others, the gx
+// tile is parked beside it, and two more accumulator tiles (table columns 0..15, 16..23) run over the wave's tiles with K = the
+// rows.  gx is then written only where the caller asks for it (a.gx != NULL).  Partials of those two tiles: [workgroup][i][T + 1]
+// (the last column a zero: the second stage's bias slot), same fixed-order second stage.
+template <bool TABLE>
 __global__ __launch_bounds__(kBlock) void linear_bwd_fused_kernel(const BwdFusedArgs a) {
   __shared__ float s_t[4][3][16][12];     // per wave: gy, x, gb_src tiles
   __shared__ f32x4 s_acc[4][kWave];
+  __shared__ float s_tab[TABLE ? 4 : 1][16][24];      // per wave: the table rows of the tile
+  __shared__ float s_gx[TABLE ? 4 : 1][16][12];       // per wave: the gated data gradient of the tile
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int wave = blockIdx.x * 4 + wid, n_waves = gridDim.x * 4;
   const int lr = lane & 15, lq = lane >> 4;
@@ -1255,23 +1307,61 @@ __global__ __launch_bounds__(kBlock) void linear_bwd_fused_kernel(const BwdFused
   const bool loader = lane < 48;
   float (*t_gy)[12] = s_t[wid][0];
   float (*t_x)[12] = s_t[wid][1];
-  float (*t_gb)[12] = s_t[wid][2];
+  float (*t_gb)[12] = a.alias ? s_t[wid][0] : s_t[wid][2];
+  float (*t_tab)[24] = s_tab[TABLE ? wid : 0];
+  float (*t_gx)[12] = s_gx[TABLE ? wid : 0];
+  f32x4 acc_t0 = f32x4{0.f, 0.f, 0.f, 0.f}, acc_t1 = f32x4{0.f, 0.f, 0.f, 0.f};
   const int64_t n_tiles = ceil_div(a.N, 16);
-  for (int64_t t = wave; t < n_tiles; t += n_waves) {
+  // lanes 0..15 hold the row-map entries of a tile's rows
+  auto map_at = [&](int64_t t) {
+    const int64_t r = min(t * 16 + (lane & 15), a.N - 1);
+    return (TABLE && a.trows && t < n_tiles) ? a.trows[r] : 0;
+  };
+  // a 16 x 24 tile is 96 float4: lane l takes pieces l and l + 64 (rows of 6 pieces; pieces beyond the padded width do not exist)
+  const int tp0r = lane / 6, tp0c = (lane - tp0r * 6) * 4, tp1r = (lane + 64) / 6, tp1c = (lane + 64 - tp1r * 6) * 4;
+  const int t4 = (a.T + 3) / 4 * 4;
+  // The operands of the NEXT tile are requested while this one is worked on (a wave then has two tiles of loads in flight; four waves
+  // per SIMD with one tile each left the launch a third short of the stream rate), and the row-map entries a tile earlier still, so
+  // that the table-row loads are no dependent round trip.  All of it is issued before this tile's gx store: a load behind a store can
+  // only be waited for by draining that store (one in-order vmcnt).  A tile beyond the end loads nothing.
+  float4 v0, v1, v2, q0, q1;
+  auto fetch = [&](int64_t t, int m) {
     const int64_t r0 = t * 16;
+    v0 = v1 = v2 = q0 = q1 = make_float4(0.f, 0.f, 0.f, 0.f);
     if (loader) {
       const int64_t r = r0 + tr;
-      float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0, v2 = v0;
       if (r < a.N) {   // 4-column chunks beyond a row's padded width do not exist in memory
         if (tc < (a.O + 3) / 4 * 4) {
           v0 = *reinterpret_cast<const float4*>(a.gy + r * a.ldgy + tc);
-          v2 = *reinterpret_cast<const float4*>(a.gbs + r * a.ldgbs + tc);
+          if (!a.alias) v2 = *reinterpret_cast<const float4*>(a.gbs + r * a.ldgbs + tc);
         }
         if (tc < (a.I + 3) / 4 * 4) v1 = *reinterpret_cast<const float4*>(a.x + r * a.ldx + tc);
       }
+    }
+    if (TABLE) {
+      const int64_t m0 = a.trows ? (int64_t)__shfl(m, tp0r) : r0 + tp0r;
+      const int64_t m1 = a.trows ? (int64_t)__shfl(m, tp1r & 15) : r0 + tp1r;
+      if (r0 + tp0r < a.N && tp0c < t4) q0 = *reinterpret_cast<const float4*>(a.tab + m0 * a.ldt + tp0c);
+      if (lane < 32 && r0 + tp1r < a.N && tp1c < t4) q1 = *reinterpret_cast<const float4*>(a.tab + m1 * a.ldt + tp1c);
+    }
+  };
+  fetch(wave, map_at(wave));
+  int mnext = map_at(wave + n_waves);
+  for (int64_t t = wave; t < n_tiles; t += n_waves) {
+    const int64_t r0 = t * 16;
+    if (loader) {
       *reinterpret_cast<float4*>(&t_gy[tr][tc]) = v0;
       *reinterpret_cast<float4*>(&t_x[tr][tc]) = v1;
-      *reinterpret_cast<float4*>(&t_gb[tr][tc]) = v2;
+      if (!a.alias) *reinterpret_cast<float4*>(&t_gb[tr][tc]) = v2;
+    }
+    if (TABLE) {
+      *reinterpret_cast<float4*>(&t_tab[tp0r][tp0c]) = q0;
+      if (lane < 32) *reinterpret_cast<float4*>(&t_tab[tp1r][tp1c]) = q1;
+    }
+    {
+      const int m2 = map_at(t + 2 * n_waves);
+      fetch(t + n_waves, mnext);
+      mnext = m2;
     }
     // data gradient: lane (row lr, quarter lq) feeds gy[lr][4 lq .. + 3] to four k-steps and ends with gx[lr][4 lq .. + 3]
     float4 b = make_float4(0.f, 0.f, 0.f, 0.f), xv = b;
@@ -1295,9 +1385,12 @@ __global__ __launch_bounds__(kBlock) void linear_bwd_fused_kernel(const BwdFused
         v[0] = xv.x > 0.f ? v[0] * a.gate_scale : 0.f; v[1] = xv.y > 0.f ? v[1] * a.gate_scale : 0.f;
         v[2] = xv.z > 0.f ? v[2] * a.gate_scale : 0.f; v[3] = xv.w > 0.f ? v[3] * a.gate_scale : 0.f;
       }
-      vstore_nt<4>(a.gx + (r0 + lr) * a.ldgx + 4 * lq, v);
+      if (!TABLE || a.gx) vstore_nt<4>(a.gx + (r0 + lr) * a.ldgx + 4 * lq, v);
 #pragma unroll
       for (int r = 0; r < 4; ++r) cs[r] += v[r];
+      if (TABLE) *reinterpret_cast<float4*>(&t_gx[lr][4 * lq]) = make_float4(v[0], v[1], v[2], v[3]);
+    } else if (TABLE && lq < 3) {             // rows beyond N and chunks beyond the width: zeros, whatever the region held
+      *reinterpret_cast<float4*>(&t_gx[lr][4 * lq]) = make_float4(0.f, 0.f, 0.f, 0.f);
     }
     // weight / bias gradients: A[m = o][k = row], B[k = row][n = i]; column I of B is the ones column
 #pragma unroll
@@ -1305,10 +1398,19 @@ __global__ __launch_bounds__(kBlock) void linear_bwd_fused_kernel(const BwdFused
       const int row = 4 * u + lq;
       const bool live = r0 + row < a.N;
       const float a1 = (lr < a.O) ? t_gy[row][lr < 12 ? lr : 0] : 0.f;
-      const float a2 = (lr < a.O) ? t_gb[row][lr < 12 ? lr : 0] : 0.f;
       const float bc = lr < a.I ? t_x[row][lr < 12 ? lr : 0] : ((lr == a.I && live) ? 1.f : 0.f);
       acc_w = mfma16x16x4(a1, bc, acc_w);
-      acc_b = mfma16x16x4(a2, bc, acc_b);
+      if (!a.alias) {
+        const float a2 = (lr < a.O) ? t_gb[row][lr < 12 ? lr : 0] : 0.f;
+        acc_b = mfma16x16x4(a2, bc, acc_b);
+      }
+      if (TABLE) {      // A[m = i][k = row] = gx[row][i], B[k = row][n = table column]; pads of either must not reach the MFMA
+        const float ag = lr < a.I ? t_gx[row][lr < 12 ? lr : 0] : 0.f;
+        const float b0 = t_tab[row][lr];
+        const float b1 = 16 + lr < a.T ? t_tab[row][lr < 8 ? 16 + lr : 16] : 0.f;
+        acc_t0 = mfma16x16x4(ag, b0, acc_t0);
+        acc_t1 = mfma16x16x4(ag, b1, acc_t1);
+      }
     }
   }
   // partials: [workgroup][(block * 12 + o) * (I + 1) + i], block 0 = gy rows, block 1 = gb_src rows (the layout of
@@ -1332,7 +1434,7 @@ __global__ __launch_bounds__(kBlock) void linear_bwd_fused_kernel(const BwdFused
     dst[24 * I1 + threadIdx.x] = threadIdx.x < a.I ? (s_cs[threadIdx.x] + s_cs[12 + threadIdx.x]) + (s_cs[24 + threadIdx.x] + s_cs[36 + threadIdx.x]) : 0.f;
 #pragma unroll
   for (int tile = 0; tile < 2; ++tile) {
-    s_acc[wid][lane] = tile == 0 ? acc_w : acc_b;
+    s_acc[wid][lane] = (tile == 0 || a.alias) ? acc_w : acc_b;
     __syncthreads();
     if (wid == 0) {
       f32x4 tt = s_acc[0][lane];
@@ -1345,6 +1447,26 @@ __global__ __launch_bounds__(kBlock) void linear_bwd_fused_kernel(const BwdFused
       }
     }
     __syncthreads();
+  }
+  if (TABLE) {
+    const int T1 = a.T + 1;
+    float* __restrict__ dst_t = a.partial_t + (int64_t)blockIdx.x * a.I * T1;
+#pragma unroll
+    for (int tile = 0; tile < 2; ++tile) {
+      s_acc[wid][lane] = tile == 0 ? acc_t0 : acc_t1;
+      __syncthreads();
+      if (wid == 0) {
+        f32x4 tt = s_acc[0][lane];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) tt += s_acc[w][lane];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int i = lq * 4 + r, c = tile * 16 + lr;
+          if (i < a.I && c < T1) dst_t[i * T1 + c] = c < a.T ? tt[r] : 0.f;
+        }
+      }
+      __syncthreads();
+    }
   }
 }
 
@@ -1760,8 +1882,8 @@ extern "C" int mlqem_linear_parts_f32(const mlqem_col_parts* x, const float* con
   return run_linear_parts(a, transposed, as_stream(stream));
 }
 
-extern "C" int mlqem_linear_fanout_tables_f32(const mlqem_fanout_tables* d, int64_t N, const int32_t* x_rows, float drop_p,
-                                              uint64_t seed, const uint64_t* seed_counter, mlqem_stream_t stream) {
+static int fanout_tables(const mlqem_fanout_tables* d, const mlqem_fanout_chain* chain, int64_t N, const int32_t* x_rows, float drop_p,
+                         uint64_t seed, const uint64_t* seed_counter, mlqem_stream_t stream) {
   begin_launches();
   if (!d || N < 0 || drop_p < 0.f || drop_p >= 1.f) return MLQEM_ERR_BAD_ARG;
   if (d->n_tables < 1 || d->n_tables > kFanTables || d->n_blocks < 1 || d->n_blocks > kMaxParts || d->cols < 1 || d->out_cols < 1)
@@ -1789,6 +1911,15 @@ extern "C" int mlqem_linear_fanout_tables_f32(const mlqem_fanout_tables* d, int6
       ++nterms;
     }
   }
+  a.chain_blk = -1;
+  if (chain) {
+    if (chain->block < 0 || chain->block >= d->n_blocks || chain->out_cols < 1 || !chain->y || !chain->w) return MLQEM_ERR_BAD_ARG;
+    if (chain->out_cols > 12) return MLQEM_ERR_UNSUPPORTED;
+    const int c4c = (chain->out_cols + 3) / 4 * 4;
+    if (chain->ldy < c4c || chain->ldy % 4 || !aligned_to(chain->y, 16)) return MLQEM_ERR_BAD_ARG;
+    a.chain_blk = chain->block; a.y2 = static_cast<float*>(chain->y); a.ldy2 = chain->ldy; a.w2c = chain->w; a.rs2 = chain->rowscale;
+    a.y2c = chain->out_cols; a.y2w = c4c;
+  }
   if (N == 0) return MLQEM_OK;
   a.nterms = nterms; a.xc = d->cols; a.yn = d->n_blocks; a.yw = c4o; a.yc = d->out_cols;
   a.N = N; a.xrows = x_rows; a.drop_p = drop_p; a.seed = seed; a.seed_counter = drop_p > 0.f ? seed_counter : nullptr;
@@ -1799,10 +1930,25 @@ extern "C" int mlqem_linear_fanout_tables_f32(const mlqem_fanout_tables* d, int6
     const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(tiles, 4), res)));      // one resident round
     hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, a);
   };
-  if (d->n_tables == 1) go(linear_fanout_tables_kernel<1>);
+  if (chain) {
+    if (d->n_tables == 1) go(linear_fanout_tables_kernel<1, true>);
+    else if (d->n_tables == 2) go(linear_fanout_tables_kernel<2, true>);
+    else go(linear_fanout_tables_kernel<3, true>);
+  } else if (d->n_tables == 1) go(linear_fanout_tables_kernel<1>);
   else if (d->n_tables == 2) go(linear_fanout_tables_kernel<2>);
   else go(linear_fanout_tables_kernel<3>);
   return launch_status();
+}
+
+extern "C" int mlqem_linear_fanout_tables_f32(const mlqem_fanout_tables* d, int64_t N, const int32_t* x_rows, float drop_p,
+                                              uint64_t seed, const uint64_t* seed_counter, mlqem_stream_t stream) {
+  return fanout_tables(d, nullptr, N, x_rows, drop_p, seed, seed_counter, stream);
+}
+
+extern "C" int mlqem_linear_fanout_tables_chain_f32(const mlqem_fanout_tables* d, const mlqem_fanout_chain* chain, int64_t N,
+                                                    const int32_t* x_rows, float drop_p, uint64_t seed, const uint64_t* seed_counter,
+                                                    mlqem_stream_t stream) {
+  return fanout_tables(d, chain, N, x_rows, drop_p, seed, seed_counter, stream);
 }
 
 template <int OBT, bool TRANSPOSED>
@@ -1950,26 +2096,63 @@ extern "C" int mlqem_linear_wgrad_bf16_f32(const float* gy, int64_t ldgy, const 
   return launch_status();
 }
 
-extern "C" int mlqem_linear_bwd_fused_f32(const float* gy, int64_t ldgy, const float* gb_src, int64_t ldgbs, const float* x,
-                                          int64_t ldx, const float* w, int gate, float gate_scale, float* gx, int64_t ldgx,
-                                          float* gw2, float* gb2, int64_t N, int I, int O, void* workspace,
-                                          size_t workspace_bytes, mlqem_stream_t stream) {
+static int bwd_fused(const float* gy, int64_t ldgy, const float* gb_src, int64_t ldgbs, const float* x, int64_t ldx, const float* w,
+                     int gate, float gate_scale, float* gx, int64_t ldgx, float* gw2, float* gb2, bool with_table, const float* table,
+                     int64_t ldt, const int32_t* table_rows, int T, float* gwt, int64_t N, int I, int O, void* workspace,
+                     size_t workspace_bytes, mlqem_stream_t stream) {
   begin_launches();
   if (N < 0 || I <= 0 || O <= 0 || !gw2 || !gb2) return MLQEM_ERR_BAD_ARG;
   if (I > 12 || O > 12) return MLQEM_ERR_UNSUPPORTED;
-  if (!workspace || workspace_bytes < mlqem_linear_wgrad_workspace_bytes(I, kBwdFusedRows)) return MLQEM_ERR_WORKSPACE;
-  if (N > 0 && (!gy || !x || !w || !gx)) return MLQEM_ERR_BAD_ARG;
+  if (with_table) {
+    if (!gwt || T < 1) return MLQEM_ERR_BAD_ARG;
+    if (T <= 16 || T > 24) return MLQEM_ERR_UNSUPPORTED;
+  }
+  const size_t need = with_table ? mlqem_linear_bwd_fused_table_workspace_bytes(I, T) : mlqem_linear_wgrad_workspace_bytes(I, kBwdFusedRows);
+  if (!workspace || workspace_bytes < need) return MLQEM_ERR_WORKSPACE;
+  if (N > 0 && (!gy || !x || !w || (!gx && !with_table) || (with_table && !table))) return MLQEM_ERR_BAD_ARG;
   if (!gb_src) { gb_src = gy; ldgbs = ldgy; }
   auto rows_ok = [](const float* p, int64_t ld, int cols) { return ld >= (cols + 3) / 4 * 4 && ld % 4 == 0 && aligned_to(p, 16); };
-  if (!rows_ok(gy, ldgy, O) || !rows_ok(gb_src, ldgbs, O) || !rows_ok(x, ldx, I) || !rows_ok(gx, ldgx, I)) return MLQEM_ERR_UNSUPPORTED;
+  if (!rows_ok(gy, ldgy, O) || !rows_ok(gb_src, ldgbs, O) || !rows_ok(x, ldx, I) || (gx && !rows_ok(gx, ldgx, I))) return MLQEM_ERR_UNSUPPORTED;
+  if (with_table && !rows_ok(table, ldt, T)) return MLQEM_ERR_UNSUPPORTED;
   hipStream_t s = as_stream(stream);
   const int64_t tiles = ceil_div(std::max<int64_t>(N, 1), 16);
   const int G = (int)std::max<int64_t>(1, std::min<int64_t>(kWgradBlocks * 2, ceil_div(tiles, 4)));
   BwdFusedArgs a{gy, ldgy, gb_src, ldgbs, x, ldx, w, gate_scale, gate, gx, ldgx, static_cast<float*>(workspace), N, I, O};
+  a.alias = (gb_src == gy && ldgbs == ldgy) ? 1 : 0;
   // the partial buffer is sized for kWgradBlocks workgroups of 25 x (I + 1) floats: cap the grid accordingly
   const int Gc = std::min(G, kWgradBlocks);
-  hipLaunchKernelGGL(linear_bwd_fused_kernel, dim3(Gc), dim3(kBlock), 0, s, a);
+  if (with_table) {
+    a.tab = table; a.ldt = ldt; a.trows = table_rows; a.T = T;
+    a.partial_t = a.partial + (size_t)kWgradBlocks * kBwdFusedRows * (I + 1);      // behind the gradient image's partials
+    hipLaunchKernelGGL(linear_bwd_fused_kernel<true>, dim3(Gc), dim3(kBlock), 0, s, a);
+  } else {
+    hipLaunchKernelGGL(linear_bwd_fused_kernel<false>, dim3(Gc), dim3(kBlock), 0, s, a);
+  }
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)ceil_div(kBwdFusedRows * (I + 1), kReducePairs)), dim3(kReducePairs * kReduceSlices), 0, s, a.partial, Gc, I,
                      kBwdFusedRows, gw2, gb2, 0, 0, 0);
+  if (with_table)     // [workgroup][I][T + 1] -> gwt [I, T]; the zero column is the second stage's bias slot, not written anywhere
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)ceil_div(I * (T + 1), kReducePairs)), dim3(kReducePairs * kReduceSlices), 0, s, a.partial_t, Gc, T,
+                       I, gwt, static_cast<float*>(nullptr), 0, 0, 0);
   return launch_status();
+}
+
+extern "C" int mlqem_linear_bwd_fused_f32(const float* gy, int64_t ldgy, const float* gb_src, int64_t ldgbs, const float* x,
+                                          int64_t ldx, const float* w, int gate, float gate_scale, float* gx, int64_t ldgx,
+                                          float* gw2, float* gb2, int64_t N, int I, int O, void* workspace,
+                                          size_t workspace_bytes, mlqem_stream_t stream) {
+  return bwd_fused(gy, ldgy, gb_src, ldgbs, x, ldx, w, gate, gate_scale, gx, ldgx, gw2, gb2, false, nullptr, 0, nullptr, 0, nullptr, N, I, O,
+                   workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t mlqem_linear_bwd_fused_table_workspace_bytes(int I, int T) {
+  return mlqem_linear_wgrad_workspace_bytes(I, kBwdFusedRows) + (size_t)kWgradBlocks * I * (T + 1) * sizeof(float);
+}
+
+extern "C" int mlqem_linear_bwd_fused_table_f32(const float* gy, int64_t ldgy, const float* gb_src, int64_t ldgbs, const float* x,
+                                                int64_t ldx, const float* w, int gate, float gate_scale, float* gx, int64_t ldgx,
+                                                float* gw2, float* gb2, const float* table, int64_t ldt, const int32_t* table_rows,
+                                                int T, float* gwt, int64_t N, int I, int O, void* workspace, size_t workspace_bytes,
+                                                mlqem_stream_t stream) {
+  return bwd_fused(gy, ldgy, gb_src, ldgbs, x, ldx, w, gate, gate_scale, gx, ldgx, gw2, gb2, true, table, ldt, table_rows, T, gwt, N, I, O,
+                   workspace, workspace_bytes, stream);
 }

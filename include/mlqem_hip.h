@@ -1322,7 +1322,8 @@ int mlqem_linreg_predict_f32(const float* x, int64_t ldx, int64_t n_rows, int F,
  * Cap: MLQEM_SIM_MAX_AMPS = 2 048 amplitudes (32 KB of LDS): n <= 11 in mode 0, n <= 5 in mode 1.  There is no global-memory path.
  *
  * circ    int32 [n_circuits][4], 16-byte aligned: (n_qubits, mode, r, 0).  The LAST r ops of the circuit are its readout ops:
- *         norm is taken before them.
+ *         norm is taken before them.  (The fourth field is 0 here; the measured entry points below read it as the number of
+ *         measurement-tail records that follow the readout ops.)
  * op_ptr  int64 [n_circuits + 1]: circuit c owns ops[op_ptr[c] .. op_ptr[c + 1]).
  * ops     mlqem_sim_op [n_ops], 16-byte aligned: (kind, q0, q1, param).  param is the index of the record's first float64 in
  *         `params`.  A unitary in mode 1 acts as U on bit q and conj(U) on bit q + n from the ONE record.
@@ -1427,6 +1428,86 @@ int mlqem_sim_run_folded_f64(int64_t n_circuits, int64_t n_factors, const int32_
 int mlqem_zne_combine_f64(int64_t n_factors, int64_t n_circuits, const double* term_values, const double* weights,
                           const int64_t* term_ptr, const double* coeff, int64_t n_terms, double* mitigated_terms,
                           double* mitigated_values, mlqem_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Measurement shots on the simulator (three additive symbols, the ABI version is unchanged).  After a circuit is simulated the
+ * device draws `shots` outcomes per measurement basis and returns the counts, the sampled Pauli-term estimates, the sampled
+ * observable values and their variances.  blackwater.sim lowers for it (compile_programs(..., shots=)) and
+ * blackwater.native.ops.sim_run_measured / sim_run_folded_measured / sim_sample call these.
+ *
+ * Groups.  The Pauli terms of a circuit are partitioned on the host into GROUPS of qubit-wise commuting terms, one measurement
+ * basis (Z, X or Y per qubit) each; circuit c owns groups group_ptr[c] .. group_ptr[c + 1] of n_groups, group g owns the 2^n
+ * entries prob_ptr[g] .. prob_ptr[g] + 2^n of a pool of n_outcomes (probs float64, counts int32; outcome j = the measured bit
+ * string as an integer, qubit 0 the least significant bit), and term_group int32 [n_terms] is a term's group COUNTED INSIDE ITS
+ * CIRCUIT.  group_ptr int64 [n_circuits + 1], prob_ptr int64 [n_groups + 1], group_circ int32 [n_groups] (the circuit of a group).
+ *
+ * Trailing ops.  circ[c] = (n_qubits, mode, r, m): the LAST r + m ops of a program (or entries of a schedule) are its r readout
+ * ops followed by a measurement tail of m records, and norm is taken before all of them.  The tail holds, per group: the basis
+ * rotations as ordinary noise-free MLQEM_SIM_OP_U1 records (H for X, H S^dagger for Y), one MLQEM_SIM_OP_MEASURE record, and the
+ * inverse rotations, so that the next group and the exact term values see the circuit's own state.  m is read by the measured
+ * entry points alone: mlqem_sim_run_f64 / mlqem_sim_run_folded_f64 ignore it and skip a MEASURE record as an unknown kind.
+ *
+ * MLQEM_SIM_OP_MEASURE (q0 = the group inside its circuit, q1 = 0, param = the group's number g in prob_ptr; it owns no float64).
+ * One pass that reads the state and leaves it unmodified: probs[prob_ptr[g] + j] = |psi_j|^2 (mode 0) or Re rho_jj (mode 1) for
+ * j < 2^n; a folded run writes row f of probs [F][n_outcomes].  Stores are predicated: a g outside the circuit's own groups, or a
+ * prob_ptr[g] with prob_ptr[g] < 0 or prob_ptr[g] + 2^n > n_outcomes, stores nothing (the index into prob_ptr is clamped).
+ *
+ * mlqem_sim_run_measured_f64 / mlqem_sim_run_folded_measured_f64: mlqem_sim_run_f64 / mlqem_sim_run_folded_f64 with the trailing-op
+ * rule above, the three group arguments and the output probs.  Everything else, checks and return codes included, is theirs;
+ * n_groups over 2^31 - 1: MLQEM_ERR_UNSUPPORTED; a null group_ptr, prob_ptr or (n_outcomes > 0) probs: MLQEM_ERR_BAD_ARG.
+ *
+ * mlqem_sim_sample_f64 samples EVERY (noise factor f, group g) pair of F x n_groups (F = n_factors = 1 for plain runs); run
+ * r = f * B + c.  units int32 [n_wave + n_wg] lists the pairs as f * n_groups + g, n_wave + n_wg = F * n_groups: the first n_wave
+ * have at most 256 outcomes and take a wave each (four per workgroup, no workgroup barrier), the others a workgroup each; the
+ * pair's CDF and counts live in LDS.  The split is the caller's to respect (blackwater.sim.SimBatch.sample_units makes it): n is
+ * clamped to the variant's cap (8 or 11 qubits), so a pair of more than 256 outcomes listed among the first n_wave samples the first
+ * 256 entries of its range only -- memory-safe garbage, MLQEM_OK, like every malformed input of this file.  Per pair, with M = 2^n outcomes and p = probs[f][prob_ptr[g] ..]:
+ *   1. p_j <- p_j if p_j > 0, else 0 (a NaN counts as 0).
+ *   2. The CDF, in an order that depends on M alone.  L = min(M, 8), C = M / L chunks of L consecutive outcomes.  Inside chunk k:
+ *      run_k[0] = p[k L], run_k[i] = run_k[i - 1] + p[k L + i].  tot[k] = run_k[L - 1].  before[0] = 0, before[k] = before[k - 1] +
+ *      tot[k - 1].  cdf[k L + i] = before[k] + run_k[i].  (float64 additions, exactly these, in this order; the CDF is
+ *      non-decreasing.)
+ *   3. Shot s < shots: Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter (s >> 1, the group inside its circuit,
+ *      run_key & 0xffffffff, run_key >> 32) gives x0 .. x3; an even s takes (a, b) = (x0, x1), an odd s (x2, x3);
+ *      u = ((a >> 5) 2^26 + (b >> 6)) 2^-53.  run_key = run_keys[r], int64 [F * B] from the host (by default r itself; a caller
+ *      passes its own so that a circuit draws the same shots alone and in a batch).
+ *   4. target = u * cdf[M - 1] (one rounded product);  j = min(#{i : cdf[i] <= target}, j_last),  j_last = #{i : cdf[i] < cdf[M - 1]}
+ *      (the second term keeps an outcome of probability 0 unreachable even when the product rounds up to the total).  Both
+ *      counts are binary searches in LDS.  counts[j] += 1: integer LDS atomics, order-independent.
+ *   5. counts[f][prob_ptr[g] + j] = the int32 counts (row f of [F][n_outcomes]; nothing is stored when the range leaves the pool,
+ *      and the loads of p are clamped to it).
+ *   6. For every term t of circuit c with term_group[t] == the group: S_t = sum_j counts_j (-1)^popcount(j & (xmask | zmask)), an
+ *      integer; term_values[f][t] = (double)S_t / (double)shots (one IEEE division: numpy gives the same bits).  The all-identity
+ *      term gives +1.
+ * Then one thread per run, terms in order, from 0.0: values[f][c] = fma(coeff_t, term_t, values), variance[f][c] = fma(coeff_t^2,
+ * fma(-term_t, term_t, 1), variance) -- sum coeff^2 (1 - term^2), the per-term variance an estimator reports; covariances between
+ * the terms of a group are not included.  At most three launches on the stream; no float atomics, no workspace, no host read:
+ * capturable.  Counts and estimates are the same bits alone, in any batch and from call to call for equal (seed, run key, group,
+ * probabilities).  Everything read from a buffer is clamped (unit numbers, circuits, n to the variant's cap, term ranges).
+ * shots outside 1 .. MLQEM_SIM_MAX_SHOTS = 2^20, negative sizes, n_factors < 1, n_wave + n_wg != F * n_groups, n_groups or
+ * n_outcomes < 1 with n_circuits > 0, a null or misaligned buffer: MLQEM_ERR_BAD_ARG; n_circuits, n_factors, n_groups, F * B or
+ * F * n_groups over 2^31 - 1: MLQEM_ERR_UNSUPPORTED; n_circuits == 0: MLQEM_OK without a launch.
+ * ---------------------------------------------------------------------------------------------------- */
+#define MLQEM_SIM_OP_MEASURE 9
+#define MLQEM_SIM_MAX_SHOTS 1048576
+int mlqem_sim_run_measured_f64(int64_t n_circuits, const int32_t* circ, const int64_t* op_ptr, const mlqem_sim_op* ops, int64_t n_ops,
+                               const double* params, int64_t n_params, const int64_t* term_ptr, const mlqem_sim_term* terms,
+                               const double* coeff, int64_t n_terms, const int64_t* group_ptr, const int64_t* prob_ptr,
+                               int64_t n_groups, int64_t n_outcomes, const int32_t* ids, int64_t n_wave, int64_t n_wg,
+                               double* term_values, double* values, double* norm, double* probs, mlqem_stream_t stream);
+int mlqem_sim_run_folded_measured_f64(int64_t n_circuits, int64_t n_factors, const int32_t* circ, const int64_t* op_ptr,
+                                      const mlqem_sim_op* ops, int64_t n_ops, const double* params, int64_t n_params,
+                                      const int64_t* term_ptr, const mlqem_sim_term* terms, const double* coeff, int64_t n_terms,
+                                      const int64_t* group_ptr, const int64_t* prob_ptr, int64_t n_groups, int64_t n_outcomes,
+                                      const int64_t* sched_ptr, const int32_t* sched, int64_t n_sched, const int32_t* ids,
+                                      int64_t n_wave, int64_t n_wg, double* term_values, double* values, double* norm, double* probs,
+                                      mlqem_stream_t stream);
+int mlqem_sim_sample_f64(int64_t n_circuits, int64_t n_factors, const int32_t* circ, const int64_t* term_ptr,
+                         const mlqem_sim_term* terms, const double* coeff, int64_t n_terms, const int64_t* group_ptr,
+                         const int32_t* term_group, const int64_t* prob_ptr, const int32_t* group_circ, int64_t n_groups,
+                         int64_t n_outcomes, const double* probs, const int64_t* run_keys, int64_t shots, uint64_t seed,
+                         const int32_t* units, int64_t n_wave, int64_t n_wg, int32_t* counts, double* term_values, double* values,
+                         double* variance, mlqem_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -6,7 +6,7 @@ exact ideal values from state vectors, noisy ones from density matrices under th
 from __future__ import annotations
 
 from dataclasses import dataclass, asdict
-from typing import Any, Dict, Iterator, List
+from typing import Any, Dict, Iterator, List, Optional
 
 import numpy as np
 import torch
@@ -61,7 +61,8 @@ class ExpValueEntry:
 
 
 def exp_value_generator(backend: Any, n_qubits: int, circuit_depth: int, pauli_terms: int, pauli_coeff: float = 1.0,
-                        max_entries: int = 1000, seed: int = 0, batch: int = 256, device="cuda") -> Iterator[ExpValueEntry]:
+                        max_entries: int = 1000, seed: int = 0, batch: int = 256, device="cuda", shots: Optional[int] = None,
+                        sample_ideal: bool = False) -> Iterator[ExpValueEntry]:
     """Yields ``max_entries`` dataset entries of random circuits with simulated labels (reference: exp_val.py:92-170, which
     transpiles ``qiskit.circuit.random.random_circuit`` and runs Aer twice per circuit).
 
@@ -71,7 +72,12 @@ def exp_value_generator(backend: Any, n_qubits: int, circuit_depth: int, pauli_t
     density-matrix mode under ``NoiseModel.from_backend(backend, readout=False)`` -- the project's depolarising model, not Aer's.
     Readout noise is OFF: random Pauli sums contain X and Y, and a readout op leaves only the diagonal of the density matrix
     meaningful.  ``batch`` circuits are simulated per launch (two launches: ideal, noisy); entries are yielded one by one and are a
-    function of ``seed`` alone."""
+    function of ``seed`` alone.
+
+    ``shots`` (default ``None``: exact labels): the noisy value is estimated from that many measurement outcomes per measurement
+    basis, drawn on the device (``sim.sample_expectation_values``; the reference's labels are 10 000-shot estimates), and with
+    ``sample_ideal=True`` the ideal one too.  The draws are keyed by ``seed`` and the entry's number, so an entry is still a
+    function of ``seed`` (and ``shots``) alone, whatever ``batch`` is."""
     from ... import sim
     from ..synthetic import random_circuit
     from ..utils import circuit_to_graph_data_json, encode_pauli_sum_op, generate_random_pauli_sum_op, get_backend_properties_v1
@@ -92,8 +98,16 @@ def exp_value_generator(backend: Any, n_qubits: int, circuit_depth: int, pauli_t
             depth = int(rng.integers(1, circuit_depth + 1))
             circuits.append(random_circuit(n_qubits, depth, int(rng.integers(0, 2 ** 31 - 1)), two_q=two_q[0]))
             observables.append(generate_random_pauli_sum_op(n_qubits, pauli_terms, pauli_coeff, rng=rng))
-        ideal = _to_host(sim.expectation_values(circuits, observables, None, device)[0])
-        noisy = _to_host(sim.expectation_values(circuits, observables, noise, device)[0])
+        if shots is None:
+            ideal = _to_host(sim.expectation_values(circuits, observables, None, device)[0])
+            noisy = _to_host(sim.expectation_values(circuits, observables, noise, device)[0])
+        else:
+            keys = np.arange(done, done + count, dtype=np.int64)   # the entry's number; the ideal launch draws with keys 2^40 further on
+            noisy = _to_host(sim.sample_expectation_values(circuits, observables, noise, shots=shots, seed=seed, run_keys=keys,
+                                                           device=device).values)
+            ideal = _to_host(sim.sample_expectation_values(circuits, observables, None, shots=shots, seed=seed, run_keys=keys + (1 << 40),
+                                                           device=device).values if sample_ideal
+                             else sim.expectation_values(circuits, observables, None, device)[0])
         for k, (circuit, observable) in enumerate(zip(circuits, observables)):
             graph = circuit_to_graph_data_json(circuit=circuit, properties=properties, use_qubit_features=True, use_gate_features=True)
             yield ExpValueEntry(circuit_graph=graph, observable=encode_pauli_sum_op(observable), ideal_exp_value=float(ideal[k]),

@@ -117,12 +117,14 @@ def pauli_twirl(circ: Circuit, seed: int, two_q=("cx", "ecr")) -> Circuit:
 
 
 def encode_corpus(circuits, nq: int, two_q: str = "cx", seed: int = 7, exp_value_size: int = 1,
-                  add_self_loops: bool = True, simulate=None, device="cuda") -> Dict[str, list]:
+                  add_self_loops: bool = True, simulate=None, device="cuda", shots=None, sample_ideal: bool = False) -> Dict[str, list]:
     """Arena-ready arrays (same keys as :func:`tfim_corpus`) for arbitrary circuits, encoded by the native encoder.
 
     ``simulate=None``: synthetic labels (a uniform draw and a made-up decay).  ``simulate=`` a ``blackwater.sim.NoiseModel``: ``y``
     and ``noisy`` of every circuit within the simulator's caps (5 qubits as a density matrix) are the exact and the noisy
-    ``<Z>`` of the circuit's observable qubit, simulated on ``device`` in two launches; larger circuits keep the synthetic labels."""
+    ``<Z>`` of the circuit's observable qubit, simulated on ``device`` in two launches; larger circuits keep the synthetic labels.
+    ``shots`` (with ``simulate``; default ``None``: exact): the noisy value is a ``shots``-shot estimate drawn on the device with
+    ``seed`` (``sim.sample_expectation_values``), and with ``sample_ideal=True`` the ideal one too."""
     from .circuit import circuit_to_qasm
     from .native_encoder import NativeEncoder
 
@@ -157,8 +159,16 @@ def encode_corpus(circuits, nq: int, two_q: str = "cx", seed: int = 7, exp_value
         if inside:
             labels = ["".join("Z" if q == z_qubits[k] else "I" for q in reversed(range(kept[k].num_qubits))) for k in inside]
             batch = [kept[k] for k in inside]
-            exact = sim.expectation_values(batch, labels, None, device)[0].cpu().numpy()
-            under = sim.expectation_values(batch, labels, simulate, device)[0].cpu().numpy()
+            if shots is None:
+                exact = sim.expectation_values(batch, labels, None, device)[0].cpu().numpy()
+                under = sim.expectation_values(batch, labels, simulate, device)[0].cpu().numpy()
+            else:
+                keys = np.asarray(inside, dtype=np.int64)   # the circuit's position in the corpus
+                under = sim.sample_expectation_values(batch, labels, simulate, shots=shots, seed=seed, run_keys=keys,
+                                                      device=device).values.cpu().numpy()
+                exact = (sim.sample_expectation_values(batch, labels, None, shots=shots, seed=seed, run_keys=keys + (1 << 40),
+                                                       device=device).values if sample_ideal
+                         else sim.expectation_values(batch, labels, None, device)[0]).cpu().numpy()
             for j, k in enumerate(inside):
                 ys[k] = np.full(exp_value_size, exact[j])
                 noisy[k] = np.full(exp_value_size, under[j])

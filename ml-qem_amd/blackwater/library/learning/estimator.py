@@ -224,7 +224,9 @@ class ZNEProcessor(LearningMethodEstimatorProcessor):
     Circuits arrive bound and on physical qubits, with observables as wide as the circuit (wrap with ``skip_transpile=True``).  The
     reference transpiles at optimisation level 0, appends measurements and re-maps a 2-qubit observable onto 5 physical qubits
     through the last two measurements, all hard-coded; none of that is reproduced here.  ``backend`` is kept for the reference's
-    constructor; ``shots``, when given, is passed on as a run option (the device estimator is exact and ignores it)."""
+    constructor; ``shots``, when given, is passed on as a run option: around ``blackwater.sim.DeviceEstimator`` every (circuit, noise
+    factor) run is then measured with that many shots per measurement basis and the SAMPLED values are extrapolated (the job's
+    metadata carries ``variance``, ``shots`` and ``std_error``); without it the values are exact."""
 
     accepts_qasm_text = True     # the ZNE estimator takes OpenQASM text as it comes
 

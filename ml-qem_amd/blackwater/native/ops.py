@@ -2732,3 +2732,141 @@ def zne_combine(term_values, weights, term_ptr, coeff, *, mitigated_terms=None, 
                                              _p(mitigated_values) if b else None, _stream())
     _lib.check(code, "mlqem_zne_combine_f64")
     return mitigated_values, mitigated_terms
+
+
+SIM_MAX_SHOTS = 2 ** 20   # MLQEM_SIM_MAX_SHOTS
+
+
+def _sim_common(circ, op_ptr, ops, params, term_ptr, terms, coeff, group_ptr, prob_ptr):
+    """The shape checks the measured simulator calls share; returns ``(B, n_ops, n_terms, n_groups, device)``."""
+    for t, name, dtype, cols in ((circ, "circ", torch.int32, 4), (ops, "ops", torch.int32, 4), (terms, "terms", torch.int32, 4)):
+        if not t.is_cuda:
+            raise _lib.NativeLibraryError(f"{name} must live on the GPU (got {t.device}); there is no CPU path")
+        if t.dtype != dtype or t.dim() != 2 or t.shape[1] != cols or not t.is_contiguous():
+            raise ValueError(f"sim: want contiguous {dtype} {name} [., {cols}], got {tuple(t.shape)} {t.dtype}")
+    b, n_ops, n_terms = int(circ.shape[0]), int(ops.shape[0]), int(terms.shape[0])
+    _vec(op_ptr, "op_ptr", b + 1, torch.int64)
+    _vec(term_ptr, "term_ptr", b + 1, torch.int64)
+    _vec(params, "params", SIM_PARAM_PAD, torch.float64)
+    _vec(coeff, "coeff", n_terms, torch.float64)
+    _vec(group_ptr, "group_ptr", b + 1, torch.int64)
+    _vec(prob_ptr, "prob_ptr", 1, torch.int64)
+    if op_ptr.shape[0] != b + 1 or term_ptr.shape[0] != b + 1 or group_ptr.shape[0] != b + 1 or coeff.shape[0] != n_terms:
+        raise ValueError(f"sim: want op_ptr, term_ptr and group_ptr [{b + 1}] and coeff [{n_terms}], got {tuple(op_ptr.shape)}, "
+                         f"{tuple(term_ptr.shape)}, {tuple(group_ptr.shape)} and {tuple(coeff.shape)}")
+    dev = circ.device
+    if any(t.device != dev for t in (op_ptr, ops, params, term_ptr, terms, coeff, group_ptr, prob_ptr)):
+        raise ValueError(f"sim: circ is on {dev}, another buffer is not")
+    return b, n_ops, n_terms, int(prob_ptr.shape[0]) - 1, dev
+
+
+def sim_run_measured(circ, op_ptr, ops, params, term_ptr, terms, coeff, group_ptr, prob_ptr, n_outcomes, ids, n_wave, n_wg, *,
+                     term_values=None, values=None, norm=None, probs=None):
+    """:func:`sim_run` on a batch lowered for measurement (``compile_programs(..., shots=)``; mlqem_sim_run_measured_f64):
+    ``(values, term_values, norm, probs)``.  ``probs`` float64 [n_outcomes] receives, per measurement group g, the outcome
+    probabilities of the circuit's final state in the group's basis at ``prob_ptr[g] ..``; ``values`` / ``term_values`` stay the
+    EXACT ones.  ``group_ptr`` int64 [B + 1], ``prob_ptr`` int64 [n_groups + 1], ``n_outcomes`` the size of the pool (a host int:
+    nothing here reads a tensor).  The other arguments and guarantees are :func:`sim_run`'s."""
+    b, n_ops, n_terms, n_groups, dev = _sim_common(circ, op_ptr, ops, params, term_ptr, terms, coeff, group_ptr, prob_ptr)
+    n_wave, n_wg, n_outcomes = int(n_wave), int(n_wg), int(n_outcomes)
+    if n_wave < 0 or n_wg < 0 or n_wave + n_wg > b:
+        raise ValueError(f"sim: n_wave = {n_wave} and n_wg = {n_wg} must be >= 0 and add up to at most {b} circuits")
+    if n_outcomes < 0:
+        raise ValueError(f"sim: n_outcomes = {n_outcomes}, want >= 0")
+    _vec(ids, "ids", n_wave + n_wg, torch.int32)
+    if ids.device != dev:
+        raise ValueError(f"sim: circ is on {dev}, ids is not")
+    values, term_values = _sim_out(values, "values", (b,), dev), _sim_out(term_values, "term_values", (n_terms,), dev)
+    norm, probs = _sim_out(norm, "norm", (b,), dev), _sim_out(probs, "probs", (n_outcomes,), dev)
+    code = _lib.load().mlqem_sim_run_measured_f64(
+        b, _p(circ), _p(op_ptr), _p(ops) if n_ops else None, n_ops, _p(params), int(params.shape[0]), _p(term_ptr),
+        _p(terms) if n_terms else None, _p(coeff) if n_terms else None, n_terms, _p(group_ptr), _p(prob_ptr), n_groups, n_outcomes,
+        _p(ids), n_wave, n_wg, _p(term_values) if n_terms else None, _p(values), _p(norm), _p(probs) if n_outcomes else None, _stream())
+    _lib.check(code, "mlqem_sim_run_measured_f64")
+    return values, term_values, norm, probs
+
+
+def sim_run_folded_measured(circ, op_ptr, ops, params, term_ptr, terms, coeff, group_ptr, prob_ptr, n_outcomes, sched_ptr, sched, ids,
+                            n_wave, n_wg, n_factors, *, term_values=None, values=None, norm=None, probs=None):
+    """:func:`sim_run_folded` on a batch lowered for measurement (mlqem_sim_run_folded_measured_f64): ``(values, term_values, norm,
+    probs)`` with ``probs`` float64 [F, n_outcomes], row f the probabilities of the runs at noise factor f.  The schedules must carry
+    the measurement tail (``build_schedules`` appends it to every run)."""
+    b, n_ops, n_terms, n_groups, dev = _sim_common(circ, op_ptr, ops, params, term_ptr, terms, coeff, group_ptr, prob_ptr)
+    f, n_wave, n_wg, n_outcomes = int(n_factors), int(n_wave), int(n_wg), int(n_outcomes)
+    if f < 1:
+        raise ValueError(f"sim: n_factors = {f}, want at least 1")
+    _vec(sched_ptr, "sched_ptr", f * b + 1, torch.int64)
+    _vec(sched, "sched", 0, torch.int32)
+    if sched_ptr.shape[0] != f * b + 1:
+        raise ValueError(f"sim: want sched_ptr [{f * b + 1}], got {tuple(sched_ptr.shape)}")
+    if n_wave < 0 or n_wg < 0 or n_wave + n_wg > f * b:
+        raise ValueError(f"sim: n_wave = {n_wave} and n_wg = {n_wg} must be >= 0 and add up to at most {f * b} runs")
+    if n_outcomes < 0:
+        raise ValueError(f"sim: n_outcomes = {n_outcomes}, want >= 0")
+    _vec(ids, "ids", n_wave + n_wg, torch.int32)
+    if any(t.device != dev for t in (sched_ptr, sched, ids)):
+        raise ValueError(f"sim: circ is on {dev}, another buffer is not")
+    n_sched = int(sched.shape[0])
+    values, term_values = _sim_out(values, "values", (f, b), dev), _sim_out(term_values, "term_values", (f, n_terms), dev)
+    norm, probs = _sim_out(norm, "norm", (f, b), dev), _sim_out(probs, "probs", (f, n_outcomes), dev)
+    code = _lib.load().mlqem_sim_run_folded_measured_f64(
+        b, f, _p(circ), _p(op_ptr), _p(ops) if n_ops else None, n_ops, _p(params), int(params.shape[0]), _p(term_ptr),
+        _p(terms) if n_terms else None, _p(coeff) if n_terms else None, n_terms, _p(group_ptr), _p(prob_ptr), n_groups, n_outcomes,
+        _p(sched_ptr), _p(sched) if n_sched else None, n_sched, _p(ids), n_wave, n_wg, _p(term_values) if n_terms else None, _p(values),
+        _p(norm), _p(probs) if n_outcomes else None, _stream())
+    _lib.check(code, "mlqem_sim_run_folded_measured_f64")
+    return values, term_values, norm, probs
+
+
+def sim_sample(circ, term_ptr, terms, coeff, group_ptr, term_group, prob_ptr, group_circ, probs, run_keys, shots, seed, units, n_wave,
+               n_wg, *, counts=None, term_values=None, values=None, variance=None):
+    """Draws ``shots`` measurement outcomes per (run, group) from ``probs`` (mlqem_sim_sample_f64): ``(values, variance, term_values,
+    counts)``.  ``probs`` float64 [n_outcomes] (plain runs) or [F, n_outcomes] (folded runs; every output then has the leading F)
+    as :func:`sim_run_measured` left them; ``run_keys`` int64 [F * B], the Philox counter words of every run; ``units`` int32
+    [F * n_groups] from ``SimBatch.sample_units`` with its ``n_wave`` / ``n_wg`` (the first ``n_wave`` units must be the groups of at
+    most 256 outcomes: the split is not checked here, that would read ``prob_ptr`` back; a group in the wrong part is sampled from
+    a clamped range, garbage and no fault); ``shots`` in 1 .. 2^20; ``seed`` in 0 .. 2^64 - 1.
+    ``counts`` int32 like ``probs``; ``term_values`` the sampled Pauli-term estimates, ``values`` / ``variance`` per run.  The rule
+    is written out in include/mlqem_hip.h; equal (seed, run key, group, probabilities) give equal counts.  Nothing here waits for
+    the device or reads a tensor, and with the four outputs given nothing is allocated: capturable."""
+    for t, name, cols in ((circ, "circ", 4), (terms, "terms", 4)):
+        if not t.is_cuda:
+            raise _lib.NativeLibraryError(f"{name} must live on the GPU (got {t.device}); there is no CPU path")
+        if t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != cols or not t.is_contiguous():
+            raise ValueError(f"sim: want contiguous torch.int32 {name} [., {cols}], got {tuple(t.shape)} {t.dtype}")
+    if not probs.is_cuda or probs.dtype != torch.float64 or probs.dim() not in (1, 2) or not probs.is_contiguous():
+        raise ValueError(f"sim: want contiguous float64 probs [n_outcomes] or [F, n_outcomes] on the GPU, got {tuple(probs.shape)} {probs.dtype}")
+    lead = tuple(probs.shape[:-1])
+    f, n_outcomes = (int(probs.shape[0]) if lead else 1), int(probs.shape[-1])
+    b, n_terms, n_groups = int(circ.shape[0]), int(terms.shape[0]), int(group_circ.shape[0])
+    shots, n_wave, n_wg, seed = int(shots), int(n_wave), int(n_wg), int(seed)
+    if not 1 <= shots <= SIM_MAX_SHOTS:
+        raise ValueError(f"sim: shots = {shots}, want 1 .. 2^20")
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError(f"sim: seed = {seed}, want 0 .. 2^64 - 1")
+    if f < 1 or n_wave < 0 or n_wg < 0 or n_wave + n_wg != f * n_groups:
+        raise ValueError(f"sim: n_wave = {n_wave} and n_wg = {n_wg} must be >= 0 and add up to the {f * n_groups} (factor, group) pairs")
+    _vec(term_ptr, "term_ptr", b + 1, torch.int64)
+    _vec(coeff, "coeff", n_terms, torch.float64)
+    _vec(group_ptr, "group_ptr", b + 1, torch.int64)
+    _vec(term_group, "term_group", n_terms, torch.int32)
+    _vec(prob_ptr, "prob_ptr", n_groups + 1, torch.int64)
+    _vec(group_circ, "group_circ", n_groups, torch.int32)
+    _vec(run_keys, "run_keys", f * b, torch.int64)
+    _vec(units, "units", n_wave + n_wg, torch.int32)
+    dev = circ.device
+    if any(t.device != dev for t in (term_ptr, terms, coeff, group_ptr, term_group, prob_ptr, group_circ, probs, run_keys, units)):
+        raise ValueError(f"sim: circ is on {dev}, another buffer is not")
+    if counts is None:
+        counts = torch.zeros(lead + (n_outcomes,), dtype=torch.int32, device=dev)
+    elif (not counts.is_cuda or counts.device != dev or counts.dtype != torch.int32 or tuple(counts.shape) != lead + (n_outcomes,)
+          or not counts.is_contiguous()):
+        raise ValueError(f"counts: want contiguous int32 {list(lead + (n_outcomes,))} on {dev}, got {tuple(counts.shape)} {counts.dtype}")
+    term_values = _sim_out(term_values, "term_values", lead + (n_terms,), dev)
+    values, variance = _sim_out(values, "values", lead + (b,), dev), _sim_out(variance, "variance", lead + (b,), dev)
+    code = _lib.load().mlqem_sim_sample_f64(
+        b, f, _p(circ), _p(term_ptr), _p(terms) if n_terms else None, _p(coeff) if n_terms else None, n_terms, _p(group_ptr),
+        _p(term_group) if n_terms else None, _p(prob_ptr), _p(group_circ), n_groups, n_outcomes, _p(probs), _p(run_keys), shots, seed,
+        _p(units), n_wave, n_wg, _p(counts), _p(term_values) if n_terms else None, _p(values), _p(variance), _stream())
+    _lib.check(code, "mlqem_sim_sample_f64")
+    return values, variance, term_values, counts

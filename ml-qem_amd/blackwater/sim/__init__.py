@@ -3,7 +3,9 @@ the labels the mitigators learn from.  ``compile_programs`` / ``NoiseModel`` / `
 zero-noise extrapolation on it; the ``zne(cls)`` decorator lives there, so that ``sim.zne`` stays the module."""
 from .program import (MAX_AMPS, MAX_QUBITS_DENSITY, MAX_QUBITS_VECTOR, SUPPORTED_GATES, WAVE_AMPS, NoiseModel, SimBatch,
                       compile_programs, measured_z)
-from .run import DeviceEstimator, SimulatedJob, expectation_values, run_batch
+from .program import MAX_SHOTS, measurement_groups
+from .run import (DeviceEstimator, SampleResult, SimulatedJob, counts_dicts, default_run_keys, expectation_values, run_batch,
+                  sample_batch, sample_expectation_values)
 from .zne import (CubicExtrapolator, CxAmplifier, GlobalFoldingAmplifier, LinearExtrapolator, LocalFoldingAmplifier,
                   PolynomialExtrapolator, QuadraticExtrapolator, QuarticExtrapolator, RichardsonExtrapolator, Schedules,
                   TwoQubitAmplifier, ZNEStrategy, build_schedules, fold_circuit, zne_expectation_values, zne_run)
@@ -12,4 +14,6 @@ __all__ = ["MAX_AMPS", "MAX_QUBITS_DENSITY", "MAX_QUBITS_VECTOR", "SUPPORTED_GAT
            "compile_programs", "measured_z", "DeviceEstimator", "SimulatedJob", "expectation_values", "run_batch",
            "CubicExtrapolator", "CxAmplifier", "GlobalFoldingAmplifier", "LinearExtrapolator", "LocalFoldingAmplifier",
            "PolynomialExtrapolator", "QuadraticExtrapolator", "QuarticExtrapolator", "RichardsonExtrapolator", "Schedules",
-           "TwoQubitAmplifier", "ZNEStrategy", "build_schedules", "fold_circuit", "zne_expectation_values", "zne_run"]
+           "TwoQubitAmplifier", "ZNEStrategy", "build_schedules", "fold_circuit", "zne_expectation_values", "zne_run",
+           "MAX_SHOTS", "measurement_groups", "SampleResult", "counts_dicts", "default_run_keys", "sample_batch",
+           "sample_expectation_values"]

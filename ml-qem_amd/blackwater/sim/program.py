@@ -23,7 +23,9 @@ PARAM_PAD = 32      # float64 values of padding at the end of the parameter pool
 MAX_QUBITS_VECTOR = 11
 MAX_QUBITS_DENSITY = 5
 
-OP_U1, OP_DIAG1, OP_CX, OP_CZ, OP_SWAP, OP_U2, OP_DEPOL1, OP_DEPOL2, OP_READOUT = range(9)   # MLQEM_SIM_OP_*
+MAX_SHOTS = 2 ** 20  # MLQEM_SIM_MAX_SHOTS: counts are int32 and a Philox counter word holds shot >> 1
+
+OP_U1, OP_DIAG1, OP_CX, OP_CZ, OP_SWAP, OP_U2, OP_DEPOL1, OP_DEPOL2, OP_READOUT, OP_MEASURE = range(10)   # MLQEM_SIM_OP_*
 
 _N_PARAMS = {"id": 0, "x": 0, "y": 0, "z": 0, "h": 0, "s": 0, "sdg": 0, "t": 0, "tdg": 0, "sx": 0, "sxdg": 0, "rx": 1, "ry": 1,
              "rz": 1, "p": 1, "u1": 1, "u2": 2, "u3": 3, "u": 3, "cx": 0, "cz": 0, "swap": 0, "ecr": 0, "rzz": 1}
@@ -168,7 +170,7 @@ class NoiseModel:
 class SimBatch:
     """A lowered batch: the host arrays of ``mlqem_sim_run_f64`` plus what the host knows about every circuit."""
 
-    circ: np.ndarray        # int32 [B, 4]: n_qubits, mode (0 vector, 1 density), trailing readout ops, 0
+    circ: np.ndarray        # int32 [B, 4]: n_qubits, mode (0 vector, 1 density), trailing readout ops, measurement-tail records
     op_ptr: np.ndarray      # int64 [B + 1]
     ops: np.ndarray         # int32 [n_ops, 4]: kind, q0, q1, offset into params
     params: np.ndarray      # float64 [n_params + 32]
@@ -187,6 +189,13 @@ class SimBatch:
     gate_noise: Optional[np.ndarray] = None    # int32 [n_gates]: the depolarising record after it
     gate_name: Optional[np.ndarray] = None     # int16 [n_gates]: index of the gate's name in SUPPORTED_GATES
     gate_op: Optional[np.ndarray] = None       # int32 [n_gates]: index of the gate in the circuit's op list
+    # measurement (``compile_programs(..., shots=)``): the groups of qubit-wise commuting terms, one measurement basis each
+    shots: Optional[int] = None
+    group_ptr: Optional[np.ndarray] = None     # int64 [B + 1]: circuit c owns groups group_ptr[c] .. group_ptr[c + 1]
+    term_group: Optional[np.ndarray] = None    # int32 [n_terms]: the term's group, counted inside its circuit
+    prob_ptr: Optional[np.ndarray] = None      # int64 [n_groups + 1]: offsets into the pool of sum 2^n outcomes
+    group_circ: Optional[np.ndarray] = None    # int32 [n_groups]: the circuit a group belongs to
+    group_basis: Optional[np.ndarray] = None   # int32 [n_groups, 2]: (qubits measured in X, qubits measured in Y); the rest in Z
 
     def __len__(self) -> int:
         return int(self.circ.shape[0])
@@ -203,7 +212,24 @@ class SimBatch:
         out = {k: torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(dev)
                for k in ("circ", "op_ptr", "ops", "params", "term_ptr", "terms", "coeff", "ids")}
         out["n_wave"], out["n_wg"] = self.n_wave, self.n_wg
+        if self.group_ptr is not None:
+            for k in ("group_ptr", "term_group", "prob_ptr", "group_circ"):
+                out[k] = torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(dev)
         return out
+
+    def sample_units(self, n_factors: int = 1):
+        """``(units int32 [F * n_groups], n_wave, n_wg)`` for ``ops.sim_sample``: every (noise factor, group) pair as
+        ``f * n_groups + g``, those of at most 256 outcomes (a wave each) first, then the others (a workgroup each)."""
+        if self.group_ptr is None:
+            raise ValueError("sample_units: the batch carries no measurement groups (compile_programs was called without shots)")
+        n_groups = int(self.group_circ.shape[0])
+        outcomes = np.diff(self.prob_ptr)
+        base = np.arange(int(n_factors), dtype=np.int64)[:, None] * n_groups
+        wave = (base + np.flatnonzero(outcomes <= WAVE_AMPS)[None, :]).reshape(-1)
+        wg = (base + np.flatnonzero(outcomes > WAVE_AMPS)[None, :]).reshape(-1)
+        if int(n_factors) * n_groups > 2 ** 31 - 1:
+            raise ValueError(f"sample_units: {int(n_factors) * n_groups} (factor, group) pairs exceed the 2^31 - 1 one call can take")
+        return np.concatenate([wave, wg]).astype(np.int32), int(wave.size), int(wg.size)
 
 
 def _lower_terms(observable: Any, n: int, where: str):
@@ -232,7 +258,50 @@ def _lower_terms(observable: Any, n: int, where: str):
     return rows, coeffs, has_xy
 
 
-def compile_programs(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None) -> SimBatch:
+def check_shots(shots: Any, who: str) -> int:
+    """``shots`` as an int in 1 .. 2^20, or a ``ValueError`` that names it."""
+    if isinstance(shots, bool) or not isinstance(shots, (int, np.integer)) or not 1 <= int(shots) <= MAX_SHOTS:
+        raise ValueError(f"{who}: shots = {shots!r}, want an int in 1 .. 2^20 = {MAX_SHOTS}")
+    return int(shots)
+
+
+def check_seed(seed: Any, who: str) -> int:
+    """``seed`` as an int reduced mod 2^64, or a ``ValueError`` that names it."""
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+        raise ValueError(f"{who}: seed = {seed!r}, want an int (it is reduced mod 2^64)")
+    return int(seed) % 2 ** 64
+
+
+def measurement_groups(term_rows: Sequence[Tuple[int, int, int, int]]):
+    """Greedy qubit-wise commuting groups of one circuit's lowered terms ``(xmask, zmask, ny, 0)``, in term order: a term joins the
+    first group whose basis agrees with it on every qubit where the term is not the identity (the group's basis is then extended by
+    the term's qubits), else it opens a new group.  Returns ``(term_group, bases)``: the group of every term and ``(x, y)`` per
+    group, the qubits measured in X and in Y (all others in Z).  A circuit without terms still gets one all-Z group."""
+    groups: List[List[int]] = []   # [x, y, z] masks of the qubits whose basis is fixed
+    term_group = []
+    for xm, zm, _, _ in term_rows:
+        tx, ty, tz = xm & ~zm, xm & zm, zm & ~xm
+        for g, (gx, gy, gz) in enumerate(groups):
+            if not (tx & (gy | gz) or ty & (gx | gz) or tz & (gx | gy)):
+                groups[g] = [gx | tx, gy | ty, gz | tz]
+                term_group.append(g)
+                break
+        else:
+            groups.append([tx, ty, tz])
+            term_group.append(len(groups) - 1)
+    if not groups:
+        groups.append([0, 0, 0])
+    return term_group, [(g[0], g[1]) for g in groups]
+
+
+# the basis changes of a measurement group, as noise-free U1 records: H for X; H S^dagger for Y, and its inverse S H
+_ROT_X = [_R, _R, _R, -_R]
+_ROT_Y = [_R, -1j * _R, _R, 1j * _R]
+_ROT_Y_INV = [_R, _R, 1j * _R, -1j * _R]
+
+
+def compile_programs(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None,
+                     shots: Optional[int] = None) -> SimBatch:
     """Lowers ``circuits`` (anything ``Circuit.from_any`` takes) with one observable each (anything ``pauli_terms`` takes) to one
     :class:`SimBatch`.  ``noise=None``: state vectors (at most 11 qubits); a :class:`NoiseModel`: density matrices (at most 5
     qubits) with its depolarising and readout ops.
@@ -242,8 +311,18 @@ def compile_programs(circuits: Sequence[Any], observables: Sequence[Any], noise:
     offender for: any other gate (opaque custom gates and ``reset`` included), a wrong parameter count, a gate on a qubit after
     it was measured, a qubit index out of range, a two-qubit gate on one qubit twice, a non-finite angle, a Pauli label of the
     wrong length or alphabet, a coefficient that is not real, a circuit over the amplitude cap of its mode, and readout noise
-    together with a term that contains X or Y (a readout op leaves only the diagonal of rho meaningful)."""
+    together with a term that contains X or Y (a readout op leaves only the diagonal of rho meaningful).
+
+    ``shots`` (an int in 1 .. 2^20; ``None``: the batch is what it always was): the batch is lowered for MEASUREMENT.  Every
+    circuit's terms are partitioned into groups (:func:`measurement_groups`), and after the circuit's ops and its readout ops
+    every group appends a tail to the program: its basis rotations as ``U1`` records (H for X, H S^dagger for Y, in qubit order),
+    one ``MEASURE`` record (q0: the group inside its circuit, param: the group's number in ``prob_ptr``), and the inverse
+    rotations, so that the next group and the exact term values see the circuit's own state.  ``circ[c, 3]`` counts these tail
+    records; ``norm`` is still taken before the readout ops.  Such a batch runs through ``ops.sim_run_measured`` /
+    ``ops.sim_run_folded_measured``; the plain entry points skip a MEASURE record and would misplace ``norm``."""
     circuits, observables = list(circuits), list(observables)
+    if shots is not None:
+        shots = check_shots(shots, "compile_programs")
     if len(circuits) != len(observables):
         raise ValueError(f"compile_programs: {len(circuits)} circuits but {len(observables)} observables")
     density = noise is not None
@@ -251,6 +330,7 @@ def compile_programs(circuits: Sequence[Any], observables: Sequence[Any], noise:
     circ_rows, ops, params, op_ptr, term_rows, coeffs, term_ptr = [], [], [], [0], [], [], [0]
     variant, measured_all = [], []
     gate_ptr, gate_record, gate_noise, gate_name, gate_op = [0], [], [], [], []
+    group_ptr, term_group, prob_ptr, group_circ, group_basis = [0], [], [0], [], []
     name_id = {g: j for j, g in enumerate(SUPPORTED_GATES)}
 
     def emit(kind, q0, q1, values):
@@ -335,7 +415,23 @@ def compile_programs(circuits: Sequence[Any], observables: Sequence[Any], noise:
                                      "terms (a readout op leaves only the diagonal of the density matrix meaningful)")
                 emit(OP_READOUT, q, 0, [float(pr[0]), float(pr[1])])
                 n_readout += 1
-        circ_rows.append((n, 1 if density else 0, n_readout, 0))
+        n_tail = 0
+        if shots is not None:
+            tg, bases = measurement_groups(rows)
+            for gl, (bx, by) in enumerate(bases):
+                qs = [q for q in range(n) if (bx | by) >> q & 1]
+                for q in qs:
+                    emit_complex(OP_U1, q, 0, _ROT_X if bx >> q & 1 else _ROT_Y)
+                ops.append((OP_MEASURE, gl, 0, len(group_circ)))
+                for q in reversed(qs):
+                    emit_complex(OP_U1, q, 0, _ROT_X if bx >> q & 1 else _ROT_Y_INV)
+                n_tail += 2 * len(qs) + 1
+                group_circ.append(k)
+                group_basis.append((bx, by))
+                prob_ptr.append(prob_ptr[-1] + 2 ** n)
+            term_group += tg
+            group_ptr.append(len(group_circ))
+        circ_rows.append((n, 1 if density else 0, n_readout, n_tail))
         op_ptr.append(len(ops))
         gate_ptr.append(len(gate_record))
         term_rows += rows
@@ -360,7 +456,11 @@ def compile_programs(circuits: Sequence[Any], observables: Sequence[Any], noise:
         n_wave=len(wave), n_wg=len(wg), variant=variant, measured=measured_all,
         gate_ptr=np.asarray(gate_ptr, dtype=np.int64), gate_record=np.asarray(gate_record, dtype=np.int32),
         gate_noise=np.asarray(gate_noise, dtype=np.int32), gate_name=np.asarray(gate_name, dtype=np.int16),
-        gate_op=np.asarray(gate_op, dtype=np.int32))
+        gate_op=np.asarray(gate_op, dtype=np.int32),
+        **({} if shots is None else dict(
+            shots=shots, group_ptr=np.asarray(group_ptr, dtype=np.int64), term_group=np.asarray(term_group, dtype=np.int32),
+            prob_ptr=np.asarray(prob_ptr, dtype=np.int64), group_circ=np.asarray(group_circ, dtype=np.int32),
+            group_basis=np.asarray(group_basis, dtype=np.int32).reshape(-1, 2))))
 
 
 def measured_z(circuit: Any) -> PauliObservable:

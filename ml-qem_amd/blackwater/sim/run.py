@@ -1,12 +1,14 @@
-"""Device side of the batched simulator: one call of ``mlqem_sim_run_f64`` per batch, and an Estimator-shaped primitive on it."""
+"""Device side of the batched simulator: one call of ``mlqem_sim_run_f64`` per batch, measurement shots on top of it
+(``mlqem_sim_run_measured_f64`` + ``mlqem_sim_sample_f64``), and an Estimator-shaped primitive on both."""
 from __future__ import annotations
 
-from typing import Any, Optional, Sequence
+from dataclasses import dataclass
+from typing import Any, Dict, List, Optional, Sequence
 
 import numpy as np
 
 from ..library.primitives import make_estimator_result
-from .program import NoiseModel, SimBatch, compile_programs
+from .program import NoiseModel, SimBatch, check_seed, check_shots, compile_programs
 
 
 def run_batch(batch: SimBatch, device="cuda"):
@@ -30,14 +32,106 @@ def expectation_values(circuits: Sequence[Any], observables: Sequence[Any], nois
     return values, term_values, torch.from_numpy(batch.term_ptr).to(values.device)
 
 
+@dataclass
+class SampleResult:
+    """What one sampled call produced: tensors on the device, CSR over ``term_ptr`` (terms of a circuit), ``group_ptr`` (measurement
+    groups of a circuit) and ``prob_ptr`` (the 2^n outcomes of a group; outcome j is the measured bit string as an integer, qubit 0
+    the least significant bit).  Folded runs carry a leading noise-factor axis on everything but the pointers."""
+
+    values: Any          # float64 [B]: sum coeff * sampled term estimate
+    variance: Any        # float64 [B]: sum coeff^2 (1 - estimate^2), per term: no covariances between the terms of a group
+    term_values: Any     # float64 [n_terms]: the sampled Pauli-term estimates
+    term_ptr: Any        # int64 [B + 1]
+    counts: Any          # int32 [n_outcomes]
+    prob_ptr: Any        # int64 [n_groups + 1]
+    group_ptr: Any       # int64 [B + 1]
+    probs: Any           # float64 [n_outcomes]: the exact outcome probabilities the counts were drawn from
+    shots: int = 0
+    seed: int = 0
+    exact_values: Any = None        # float64 [B]: the exact expectation values of the same launch
+    exact_term_values: Any = None   # float64 [n_terms]
+    norm: Any = None
+    batch: Optional[SimBatch] = None
+
+
+def default_run_keys(n_runs: int, offset: int = 0) -> np.ndarray:
+    """int64 [n_runs]: ``offset + r`` for run r = f * B + c, the counter words a run draws with unless the caller passes its own."""
+    return np.arange(int(n_runs), dtype=np.int64) + np.int64(offset)
+
+
+def _run_keys(run_keys, n_runs: int, who: str) -> np.ndarray:
+    if run_keys is None:
+        return default_run_keys(n_runs)
+    keys = np.asarray(run_keys)
+    if keys.shape != (n_runs,) or keys.dtype.kind not in "iu":
+        raise ValueError(f"{who}: run_keys must be {n_runs} integers (one per run), got shape {keys.shape} dtype {keys.dtype}")
+    return keys.astype(np.int64)
+
+
+def sample_batch(batch: SimBatch, seed: int = 0, run_keys=None, device="cuda") -> SampleResult:
+    """Simulates a batch lowered with ``shots`` and samples it: two calls (at most five launches), nothing read back."""
+    import torch
+
+    from ..native import ops
+
+    if batch.group_ptr is None:
+        raise ValueError("sample_batch: the batch was lowered without shots (compile_programs(..., shots=))")
+    seed = check_seed(seed, "sample_batch")
+    keys = torch.from_numpy(_run_keys(run_keys, len(batch), "sample_batch")).to(device)
+    t = batch.to(device)
+    units, n_wave, n_wg = batch.sample_units(1)
+    n_outcomes = int(batch.prob_ptr[-1])
+    values, term_values, norm, probs = ops.sim_run_measured(
+        t["circ"], t["op_ptr"], t["ops"], t["params"], t["term_ptr"], t["terms"], t["coeff"], t["group_ptr"], t["prob_ptr"], n_outcomes,
+        t["ids"], t["n_wave"], t["n_wg"])
+    s_values, variance, s_terms, counts = ops.sim_sample(
+        t["circ"], t["term_ptr"], t["terms"], t["coeff"], t["group_ptr"], t["term_group"], t["prob_ptr"], t["group_circ"], probs, keys,
+        batch.shots, seed, torch.from_numpy(units).to(keys.device), n_wave, n_wg)
+    return SampleResult(s_values, variance, s_terms, t["term_ptr"], counts, t["prob_ptr"], t["group_ptr"], probs, batch.shots, seed,
+                        values, term_values, norm, batch)
+
+
+def sample_expectation_values(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None, shots: int = None,
+                              seed: int = 0, run_keys=None, device="cuda") -> SampleResult:
+    """Expectation values estimated from ``shots`` measurement outcomes per measurement basis, drawn on the device.
+
+    The circuits are lowered with their terms partitioned into qubit-wise commuting groups (``compile_programs(..., shots=)``),
+    simulated exactly, and every group's outcome distribution is sampled ``shots`` times (a Philox4x32-10 stream per (seed, run
+    key, group, shot): include/mlqem_hip.h has the rule).  ``run_keys``: one integer per circuit, by default its position in the
+    batch; pass a circuit's batch key to draw the same shots for it alone.  Returns a :class:`SampleResult`."""
+    if shots is None:
+        raise ValueError("sample_expectation_values: shots is required (an int in 1 .. 2^20); expectation_values gives the exact values")
+    shots = check_shots(shots, "sample_expectation_values")
+    return sample_batch(compile_programs(circuits, observables, noise, shots=shots), seed, run_keys, device)
+
+
+def counts_dicts(result: SampleResult) -> List[List[Dict[str, int]]]:
+    """``{bitstring: count}`` per (circuit, group) of a plain (unfolded) result, outcomes with a count of 0 left out.  A bitstring
+    is qiskit's: n characters, qubit 0 the RIGHTMOST, so that ``int(bitstring, 2)`` is the outcome index -- the order
+    ``counts_to_feature_vector`` expects.  Reads the counts back from the device."""
+    counts = result.counts.cpu().numpy()
+    if counts.ndim != 1:
+        raise ValueError("counts_dicts: want the result of a plain run (folded runs carry a noise-factor axis: index it first)")
+    prob_ptr, group_ptr = result.prob_ptr.cpu().numpy(), result.group_ptr.cpu().numpy()
+    out = []
+    for c in range(len(group_ptr) - 1):
+        per = []
+        for g in range(int(group_ptr[c]), int(group_ptr[c + 1])):
+            b, e = int(prob_ptr[g]), int(prob_ptr[g + 1])
+            width = max((e - b).bit_length() - 1, 1)
+            per.append({format(j, f"0{width}b"): int(v) for j, v in enumerate(counts[b:e].tolist()) if v})
+        out.append(per)
+    return out
+
+
 class SimulatedJob:
     """The job of a :class:`DeviceEstimator` run: the values are already on the host when it is built."""
 
-    def __init__(self, values: np.ndarray, job_id: str):
-        self._values, self._job_id = values, job_id
+    def __init__(self, values: np.ndarray, job_id: str, metadata: Optional[List[dict]] = None):
+        self._values, self._job_id, self._metadata = values, job_id, metadata
 
     def result(self):
-        return make_estimator_result(self._values, [{} for _ in range(len(self._values))])
+        return make_estimator_result(self._values, self._metadata if self._metadata is not None else [{} for _ in range(len(self._values))])
 
     def job_id(self) -> str:
         return self._job_id
@@ -57,10 +151,18 @@ class DeviceEstimator:
     ``result().values[k]`` is the exact expectation value of ``observables[k]`` after ``circuits[k]`` (``noise=None``) or the one
     under ``noise`` (a :class:`NoiseModel`, density-matrix mode), ``metadata[k] = {}``.  It has the ``_run`` protocol the
     ``learning(...)`` and ``ngem(...)`` decorators patch.  Circuits arrive bound (QASM text, ``Circuit`` or a bound qiskit-like
-    circuit); non-empty ``parameter_values`` are refused.  There is no host path: ``device`` must be a GPU."""
+    circuit); non-empty ``parameter_values`` are refused.  There is no host path: ``device`` must be a GPU.
 
-    def __init__(self, noise: Optional[NoiseModel] = None, device="cuda"):
+    ``shots`` (constructor, or the ``shots=`` run option, which wins; ``None``: exact, as above): the values are estimated from that
+    many measurement outcomes per measurement basis (:func:`sample_expectation_values`) and ``metadata[k] = {"variance": v_k,
+    "shots": shots}``, as qiskit's estimators report.  ``seed`` (constructor or run option) keys the draws.  Successive ``run()``
+    calls of one estimator do not repeat their draws: circuit k of the estimator's j-th job (j = 1, 2, ...; exact jobs count too)
+    draws with the run key ``j * 2^32 + k``, so two estimators with one seed that are asked the same things agree."""
+
+    def __init__(self, noise: Optional[NoiseModel] = None, device="cuda", shots: Optional[int] = None, seed: int = 0):
         self._noise, self._device, self._count = noise, device, 0
+        self._shots = None if shots is None else check_shots(shots, "DeviceEstimator")
+        self._seed = check_seed(seed, "DeviceEstimator")
 
     def run(self, circuits, observables, parameter_values=None, **run_options):
         circuits, observables = list(circuits), list(observables)
@@ -72,6 +174,15 @@ class DeviceEstimator:
         for k, p in enumerate(parameter_values):
             if len(p):
                 raise ValueError(f"DeviceEstimator: circuit {k} comes with {len(p)} parameter values; circuits must arrive bound")
-        values, _, _ = expectation_values(circuits, observables, self._noise, self._device)
+        shots = run_options.pop("shots", self._shots)
+        seed = run_options.pop("seed", self._seed)
         self._count += 1
-        return SimulatedJob(values.cpu().numpy(), f"sim-{self._count}")
+        if shots is None:
+            values, _, _ = expectation_values(circuits, observables, self._noise, self._device)
+            return SimulatedJob(values.cpu().numpy(), f"sim-{self._count}")
+        shots, seed = check_shots(shots, "DeviceEstimator.run"), check_seed(seed, "DeviceEstimator.run")
+        res = sample_expectation_values(circuits, observables, self._noise, shots=shots, seed=seed,
+                                        run_keys=default_run_keys(len(circuits), self._count << 32), device=self._device)
+        variance = res.variance.cpu().numpy()
+        return SimulatedJob(res.values.cpu().numpy(), f"sim-{self._count}",
+                            [{"variance": float(v), "shots": shots} for v in variance])

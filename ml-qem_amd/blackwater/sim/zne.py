@@ -23,8 +23,13 @@ folded gate runs as G N G^-1 N G N, the inverse carrying the gate's OWN depolari
 ``sx`` a by-name rule would find no calibration entry for ``sxdg`` and amplify nothing).  Readout ops run once, after everything.
 
 Polynomial extrapolation of exact values is linear in them, so an extrapolator is a weight vector: ``weights(noise_factors)`` is
-``e_0^T V^+`` for the Vandermonde matrix V of the factors, in float64 on the host.  Exponential extrapolation and standard errors
-from shot noise are out of scope: the values are exact.
+``e_0^T V^+`` for the Vandermonde matrix V of the factors, in float64 on the host.  Exponential extrapolation is out of scope.
+
+Shots.  With ``shots=`` every (circuit, factor) run is measured (``ops.sim_run_folded_measured`` + ``ops.sim_sample``): per factor
+the sampled values and their variances; the mitigated value is sum_f w_f value_f through the same combine, and the mitigated
+variance is sum_f w_f^2 variance_f (the factors are sampled independently) -- the SAME ``mlqem_zne_combine_f64`` called with the
+squared weights on an identity term layout (one "term" per circuit with coefficient 1), not a kernel of its own.  The standard error
+of a mitigated value is sqrt(variance / shots).
 """
 from __future__ import annotations
 
@@ -36,7 +41,7 @@ import numpy as np
 
 from ..data.circuit import Circuit, CircuitOp
 from ..library.primitives import make_estimator_result
-from .program import _TWO_QUBIT, SUPPORTED_GATES, NoiseModel, SimBatch, compile_programs
+from .program import _TWO_QUBIT, SUPPORTED_GATES, NoiseModel, SimBatch, check_seed, check_shots, compile_programs
 
 _NOT_GATES = ("barrier", "measure")
 
@@ -274,7 +279,10 @@ def build_schedules(batch: SimBatch, circuits: Optional[Sequence[Any]], noise_fa
         raise ValueError("build_schedules: no noise factor")
     mask = _name_table(amplifier)[batch.gate_name.astype(np.int64)] if batch.gate_name.size else np.zeros(0, dtype=bool)
     owner = np.repeat(np.arange(n_circ, dtype=np.int64), np.diff(batch.gate_ptr))
-    n_readout = np.minimum(batch.circ[:, 2].astype(np.int64), batch.op_counts) if n_circ else np.zeros(0, dtype=np.int64)
+    # the trailing records of a program run once, in order, after every schedule: its readout ops and, in a batch lowered for
+    # measurement, the measurement tail (circ[:, 3] records: rotations / MEASURE / inverse rotations per group)
+    n_readout = (np.minimum(batch.circ[:, 2].astype(np.int64) + batch.circ[:, 3].astype(np.int64), batch.op_counts)
+                 if n_circ else np.zeros(0, dtype=np.int64))
     readout = ((np.repeat(batch.op_counts - n_readout, n_readout) + _within(n_readout)) << 1).astype(np.int32)
     rec, noi = batch.gate_record.astype(np.int64), batch.gate_noise.astype(np.int64)
     pieces, lengths, achieved = [], [], []
@@ -412,11 +420,20 @@ class ZNERun:
     batch: SimBatch
     schedules: Schedules
     weights: np.ndarray
+    # with shots: ``values`` / ``term_values`` and the mitigated ones above are the SAMPLED ones, and
+    shots: Optional[int] = None
+    variance: Any = None              # float64 [F, B]: per factor, sum coeff^2 (1 - estimate^2)
+    mitigated_variance: Any = None    # float64 [B]: sum_f w_f^2 variance_f
+    counts: Any = None                # int32 [F, n_outcomes]
+    probs: Any = None                 # float64 [F, n_outcomes]
+    exact_values: Any = None          # float64 [F, B]: the exact per-factor values of the same launch
 
 
 def zne_run(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None,
-            strategy: Optional[ZNEStrategy] = None, device="cuda") -> ZNERun:
-    """Lowers once, builds the schedules, simulates every (circuit, factor) run in one call and extrapolates in one more."""
+            strategy: Optional[ZNEStrategy] = None, device="cuda", shots: Optional[int] = None, seed: int = 0, run_keys=None) -> ZNERun:
+    """Lowers once, builds the schedules, simulates every (circuit, factor) run in one call and extrapolates in one more.  With
+    ``shots`` every run is also measured and the extrapolation is of the sampled values (see the module docstring); ``run_keys``:
+    one integer per run f * B + c (by default the run number)."""
     import torch
 
     from ..native import ops
@@ -424,6 +441,29 @@ def zne_run(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional
     strategy = strategy or ZNEStrategy()
     weights = strategy.weights()
     circuits = list(circuits)
+    if shots is not None:
+        from .run import _run_keys
+
+        shots, seed = check_shots(shots, "zne_run"), check_seed(seed, "zne_run")
+        batch = compile_programs(circuits, observables, noise, shots=shots)
+        sch = build_schedules(batch, circuits, strategy.noise_factors, strategy.noise_amplifier)
+        t, s = batch.to(device), sch.to(device)
+        n_f, n_circ = len(sch.noise_factors), len(batch)
+        keys = torch.from_numpy(_run_keys(run_keys, n_f * n_circ, "zne_run")).to(device)
+        units, u_wave, u_wg = batch.sample_units(n_f)
+        exact, _, norm, probs = ops.sim_run_folded_measured(
+            t["circ"], t["op_ptr"], t["ops"], t["params"], t["term_ptr"], t["terms"], t["coeff"], t["group_ptr"], t["prob_ptr"],
+            int(batch.prob_ptr[-1]), s["sched_ptr"], s["sched"], s["ids"], sch.n_wave, sch.n_wg, n_f)
+        values, variance, term_values, counts = ops.sim_sample(
+            t["circ"], t["term_ptr"], t["terms"], t["coeff"], t["group_ptr"], t["term_group"], t["prob_ptr"], t["group_circ"], probs,
+            keys, shots, seed, torch.from_numpy(units).to(keys.device), u_wave, u_wg)
+        w = torch.from_numpy(weights).to(values.device)
+        mitigated_values, mitigated_terms = ops.zne_combine(term_values, w, t["term_ptr"], t["coeff"])
+        # sum_f w_f^2 variance_f: the same combine, squared weights, one unit-coefficient "term" per circuit
+        _, mitigated_variance = ops.zne_combine(variance, torch.from_numpy(weights * weights).to(values.device), torch.arange(n_circ + 1, dtype=torch.int64, device=values.device),
+                                                torch.ones(n_circ, dtype=torch.float64, device=values.device))
+        return ZNERun(mitigated_values, mitigated_terms, t["term_ptr"], values, term_values, norm, batch, sch, weights, shots=shots,
+                      variance=variance, mitigated_variance=mitigated_variance, counts=counts, probs=probs, exact_values=exact)
     batch = compile_programs(circuits, observables, noise)
     sch = build_schedules(batch, circuits, strategy.noise_factors, strategy.noise_amplifier)
     t, s = batch.to(device), sch.to(device)
@@ -435,11 +475,12 @@ def zne_run(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional
 
 
 def zne_expectation_values(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None,
-                           strategy: Optional[ZNEStrategy] = None, device="cuda"):
+                           strategy: Optional[ZNEStrategy] = None, device="cuda", shots: Optional[int] = None, seed: int = 0):
     """``(mitigated_values [B], mitigated_terms [n_terms], term_ptr [B + 1], per_factor_values [F, B])``, tensors on ``device``.
     ``noise=None`` is allowed (state vectors up to 11 qubits): pointless as mitigation, every factor then gives the same value up
-    to rounding."""
-    run = zne_run(circuits, observables, noise, strategy, device)
+    to rounding.  With ``shots`` the same four tensors hold the SAMPLED values; :func:`zne_run` returns the variances, counts and
+    probabilities beside them (``ZNERun.mitigated_variance``, ``.variance``, ``.counts``, ``.probs``)."""
+    run = zne_run(circuits, observables, noise, strategy, device, shots=shots, seed=seed)
     return run.mitigated_values, run.mitigated_terms, run.term_ptr, run.values
 
 
@@ -455,9 +496,10 @@ class ZNEJob:
     the wrapped estimator's job when ``result()`` is asked for."""
 
     def __init__(self, strategy: ZNEStrategy, achieved: np.ndarray, n_circuits: int, job_id: str, values=None, per_factor=None,
-                 base_job=None):
+                 base_job=None, shots=None, variance=None, per_factor_variance=None):
         self._strategy, self._achieved, self._n, self._job_id = strategy, achieved, n_circuits, job_id
         self._values, self._per_factor, self._base_job = values, per_factor, base_job
+        self._shots, self._variance, self._per_factor_variance = shots, variance, per_factor_variance
 
     def result(self):
         meta = [{} for _ in range(self._n)]
@@ -468,6 +510,10 @@ class ZNEJob:
             meta = [dict(m) for m in list(base.metadata)[:self._n]] if len(base.metadata) >= self._n else meta
         for k in range(self._n):
             meta[k]["zne"] = _zne_metadata(self._strategy, self._achieved, self._per_factor, k)
+            if self._shots is not None:   # the fused path with shots: the error bar of the mitigated value
+                var = float(self._variance[k])
+                meta[k].update(variance=var, shots=int(self._shots), std_error=math.sqrt(max(var, 0.0) / self._shots))
+                meta[k]["zne"]["variances"] = tuple(float(v) for v in self._per_factor_variance[:, k])
         return make_estimator_result(np.asarray(self._values, dtype=np.float64), meta)
 
     def job_id(self) -> str:
@@ -486,7 +532,10 @@ class ZNEJob:
 def zne(cls):
     """Decorator in the style of ``learning(...)`` / ``ngem(...)``: ``zne(Estimator)`` is an estimator class that accepts
     ``zne_strategy=`` at construction and as a run option and returns zero-noise-extrapolated values;
-    ``result().metadata[k]["zne"]`` holds the requested and achieved factors and the per-factor values.
+    ``result().metadata[k]["zne"]`` holds the requested and achieved factors and the per-factor values.  Around
+    :class:`DeviceEstimator`, ``shots=`` (constructor or run option) measures every run: ``metadata[k]`` gains ``variance``
+    (sum_f w_f^2 variance_f), ``shots`` and ``std_error = sqrt(variance / shots)``, and ``metadata[k]["zne"]["variances"]`` the
+    per-factor variances.
 
     Around :class:`DeviceEstimator` it takes the fused path (:func:`zne_run`: one lowering, schedules, two calls).  Around any other
     estimator class it folds the IR (:func:`fold_circuit`), submits the F * B circuits through the wrapped ``_run`` in one job and
@@ -508,6 +557,13 @@ def zne(cls):
             for k, p in enumerate(parameter_values):
                 if len(p):
                     raise ValueError(f"{type(self).__name__}: circuit {k} comes with {len(p)} parameter values; circuits must arrive bound")
+            shots, seed = run_options.pop("shots", self._shots), run_options.pop("seed", self._seed)
+            if shots is not None:   # job j's run r draws with the key j * 2^32 + r: successive runs do not repeat their draws
+                keys = np.arange(len(strategy.noise_factors) * len(circuits), dtype=np.int64) + (np.int64(self._zne_count) << 32)
+                run = zne_run(circuits, observables, self._noise, strategy, self._device, shots=shots, seed=seed, run_keys=keys)
+                return ZNEJob(strategy, run.schedules.achieved, len(circuits), f"zne-sim-{self._zne_count}",
+                              values=run.mitigated_values.cpu().numpy(), per_factor=run.values.cpu().numpy(), shots=run.shots,
+                              variance=run.mitigated_variance.cpu().numpy(), per_factor_variance=run.variance.cpu().numpy())
             run = zne_run(circuits, observables, self._noise, strategy, self._device)
             return ZNEJob(strategy, run.schedules.achieved, len(circuits), f"zne-sim-{self._zne_count}",
                           values=run.mitigated_values.cpu().numpy(), per_factor=run.values.cpu().numpy())

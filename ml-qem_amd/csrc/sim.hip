@@ -27,6 +27,12 @@
 // record's inverse, formed by swapping and negating components as they are read (no arithmetic, so no new rounding).  The two
 // instantiations mlqem_sim_run_f64 launches compile to the instructions they had before the schedules existed.
 // mlqem_zne_combine_f64 is the weighted sum over the noise factors that extrapolates to zero noise.
+//
+// Measurement shots.  mlqem_sim_run_measured_f64 and its folded twin are four more instantiations (MEAS = true): a MEASURE record
+// stores the state's outcome probabilities, one pass that leaves the state as it is and ends in the barrier every pass ends in (the
+// next record writes the state).  mlqem_sim_sample_f64 is a kernel of its own (sample_kernel): it reads those probabilities from
+// global memory, keeps a CDF and the counts in LDS -- not the 32 KB state -- and draws the shots with Philox4x32-10;
+// sample_finish_kernel then adds up values and variances.
 #include "common.hpp"
 
 namespace mlqem {
@@ -203,7 +209,12 @@ template <bool WG> struct SimCtx {
 // run r walks the schedule sched[sched_ptr[r] .. sched_ptr[r + 1]) of entries (k << 1) | dagger over circuit c's ops
 // (mlqem_sim_run_folded_f64); its outputs go to row f.  The four waves of a workgroup of the wave variant then have trip counts that
 // differ by the ratio of the noise factors: as before, nothing in that variant is a workgroup barrier.
-template <bool WG, bool FOLD>
+//
+// MEAS = true (mlqem_sim_run_measured_f64 and its folded twin): the program ends with a measurement tail of circ[c].w records
+// (basis rotations / MEASURE / inverse rotations per group) after its readout ops, norm is taken before the readout ops AND the
+// tail, and a MEASURE record stores the state's outcome probabilities -- one pass that reads the state and leaves it as it is.  The
+// MEAS = false instantiations never read the five trailing arguments and compile to the instructions they had without them.
+template <bool WG, bool FOLD, bool MEAS = false>
 __global__ __launch_bounds__(kBlock) void sim_kernel(int B, const sim_i4* __restrict__ circ, const int64_t* __restrict__ op_ptr,
                                                      const sim_i4* __restrict__ ops, int64_t n_ops,
                                                      const double* __restrict__ params, int64_t n_params,
@@ -212,7 +223,9 @@ __global__ __launch_bounds__(kBlock) void sim_kernel(int B, const sim_i4* __rest
                                                      const int32_t* __restrict__ ids, int count, double* __restrict__ term_values,
                                                      double* __restrict__ values, double* __restrict__ norm, int n_runs,
                                                      const int64_t* __restrict__ sched_ptr, const int32_t* __restrict__ sched,
-                                                     int64_t n_sched) {
+                                                     int64_t n_sched, const int64_t* __restrict__ group_ptr = nullptr,
+                                                     const int64_t* __restrict__ prob_ptr = nullptr, int64_t n_groups = 0,
+                                                     int64_t n_outcomes = 0, double* __restrict__ probs = nullptr) {
   __shared__ sim_c state[WG ? kSimMaxAmps : kBlock / kWave * kSimWaveAmps];
   __shared__ double red[8];
   SimCtx<WG> cx;
@@ -241,7 +254,8 @@ __global__ __launch_bounds__(kBlock) void sim_kernel(int B, const sim_i4* __rest
     const int64_t se = min(max(sched_ptr[run + 1], sb), n_sched);
     n_step = __builtin_amdgcn_readfirstlane((int)min(se - sb, (int64_t)0x7FFFFFFF));
   }
-  const int n_main = n_step - min(max(info.z, 0), n_step);   // steps before the readout ops: Tr rho is taken there
+  // steps before the readout ops (and the measurement tail after them): Tr rho is taken there
+  const int n_main = n_step - min(min(max(info.z, 0), n_step) + (MEAS ? min(max(info.w, 0), n_step) : 0), n_step);
 
   for (int i = tid; i < A; i += cx.T) cx.st[i] = sim_c{i == 0 ? 1.0 : 0.0, 0.0};
   sim_sync<WG>();
@@ -274,6 +288,25 @@ __global__ __launch_bounds__(kBlock) void sim_kernel(int B, const sim_i4* __rest
     const int q0 = __builtin_amdgcn_readfirstlane(min(max(op.y, 0), n - 1)), q1 = __builtin_amdgcn_readfirstlane(min(max(op.z, 0), n - 1));
     const int64_t po = min((int64_t)max(op.w, 0), n_params - kSimParamPad);
     const double* m = params + po;
+    if constexpr (MEAS) {
+      if (kind == MLQEM_SIM_OP_MEASURE) {   // probabilities of the 2^n outcomes: |psi_j|^2, or Re rho_jj
+        const int64_t g = __builtin_amdgcn_readfirstlane(op.w);   // the group's number in prob_ptr
+        const int64_t gb = min(max(group_ptr[c], (int64_t)0), n_groups), ge = min(max(group_ptr[c + 1], gb), n_groups);
+        const int64_t pb = prob_ptr[min(max(g, (int64_t)0), n_groups)];   // prob_ptr has n_groups + 1 entries
+        const int M = 1 << n, mul = density ? M + 1 : 1;
+        // a slot that is not one of this circuit's groups, or a range that leaves the pool: the pass runs and stores nothing
+        const bool ok = g >= gb && g < ge && pb >= 0 && pb <= n_outcomes - M;
+        double* out = probs + (FOLD ? (int64_t)row * n_outcomes : (int64_t)0) + (ok ? pb : (int64_t)0);
+        for (int i0 = 0; i0 < M; i0 += cx.T) {
+          const int i = i0 + tid;
+          const sim_c v = cx.st[((i & (M - 1)) * mul) & (A - 1)];
+          const double pr = density ? v.x : v.x * v.x + v.y * v.y;
+          if (ok && i < M) out[i] = pr;
+        }
+        sim_sync<WG>();   // the next record may overwrite entries another wave of the workgroup has not read yet
+        continue;
+      }
+    }
     switch (kind) {
       case MLQEM_SIM_OP_U1:
         if (FOLD) {   // the inverse swaps the off-diagonal entries and negates the imaginary parts: no arithmetic, no rounding
@@ -398,6 +431,173 @@ __global__ __launch_bounds__(kBlock) void zne_combine_kernel(int F, const double
   }
 }
 
+// ---- measurement shots (mlqem_sim_sample_f64) ----------------------------------------------------------------------------------------
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11): ten rounds of two 32 x 32 -> 64 products,
+// the key bumped by the Weyl constants between rounds.
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                              uint32_t (&x)[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  x[0] = c0;
+  x[1] = c1;
+  x[2] = c2;
+  x[3] = c3;
+}
+
+__device__ __forceinline__ int sim_wave_sum_int(int v) {
+#pragma unroll
+  for (int d = kWave / 2; d >= 1; d >>= 1) v = v + __shfl_down(v, d, kWave);
+  return v;
+}
+
+// One (noise factor, group) pair per wave (WG = false: at most 256 outcomes, four pairs per workgroup, no workgroup barrier) or per
+// workgroup (WG = true: up to 2 048).  The pair's CDF (float64) and counts (int32) live in LDS; the probabilities come from global
+// memory, where a MEASURE record left them.  include/mlqem_hip.h states the CDF order and the sampling rule.
+template <bool WG>
+__global__ __launch_bounds__(kBlock) void sample_kernel(int B, int F, const sim_i4* __restrict__ circ, const int64_t* __restrict__ term_ptr,
+                                                        const sim_i4* __restrict__ terms, int64_t n_terms,
+                                                        const int64_t* __restrict__ group_ptr, const int32_t* __restrict__ term_group,
+                                                        const int64_t* __restrict__ prob_ptr, const int32_t* __restrict__ group_circ,
+                                                        int n_groups, int64_t n_outcomes, const double* __restrict__ probs,
+                                                        const int64_t* __restrict__ run_keys, int shots, uint32_t seed_lo,
+                                                        uint32_t seed_hi, const int32_t* __restrict__ units, int count,
+                                                        int32_t* __restrict__ counts, double* __restrict__ term_values) {
+  constexpr int T = WG ? kBlock : kWave;
+  constexpr int kMaxM = WG ? kSimMaxAmps : kSimWaveAmps, kPer = WG ? 1 : kBlock / kWave;
+  __shared__ double cdf_s[kPer * kMaxM];
+  __shared__ double tot_s[kPer * (kMaxM / 8)];
+  __shared__ int cnt_s[kPer * kMaxM];
+  __shared__ int red_s[kBlock / kWave];
+  const int slot = WG ? (int)blockIdx.x : __builtin_amdgcn_readfirstlane((int)blockIdx.x * (kBlock / kWave) + ((int)threadIdx.x >> 6));
+  if (slot >= count) return;   // wave-uniform; the wave variant has no workgroup barrier
+  const int tid = WG ? (int)threadIdx.x : (int)threadIdx.x & (kWave - 1);
+  const int part = WG ? 0 : (int)threadIdx.x >> 6;
+  double* cdf = cdf_s + part * kMaxM;
+  double* tot = tot_s + part * (kMaxM / 8);
+  int* cnt = cnt_s + part * kMaxM;
+
+  const int rg = __builtin_amdgcn_readfirstlane(min(max(units[slot], 0), F * n_groups - 1));   // f * n_groups + g, F * n_groups < 2^31
+  const int f = rg / n_groups, g = rg % n_groups;
+  const int c = __builtin_amdgcn_readfirstlane(min(max(group_circ[g], 0), B - 1));
+  const int n = __builtin_amdgcn_readfirstlane(min(max(circ[c].x, 1), WG ? 11 : 8));
+  const int M = 1 << n;
+  const int gl = g - (int)min(max(group_ptr[c], (int64_t)0), (int64_t)g);   // the group inside its circuit
+  const int64_t pb = prob_ptr[g];
+  const bool ok = pb >= 0 && pb <= n_outcomes - M;   // a range that leaves the pool: clamped loads, no store of counts
+  const int64_t base = ok ? pb : 0;
+  const double* p = probs + (int64_t)f * n_outcomes;
+
+  // CDF: chunks of 8 consecutive outcomes (one chunk of M when M < 8), each summed left to right; the chunk totals prefix-summed
+  // left to right; cdf[j] = (total of the chunks before j's) + (running sum inside j's chunk up to j)
+  const int L = min(M, 8), C = M / L;   // C <= 256 = T (workgroup), C <= 32 (wave)
+  double run[8];
+  {
+    const int k = min(tid, C - 1);
+    double acc = 0.0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const double v = p[min(base + k * L + min(i, L - 1), n_outcomes - 1)];
+      acc = acc + (i < L && v > 0.0 ? v : 0.0);   // p_j <- max(p_j, 0); a NaN counts as 0
+      run[i] = acc;
+    }
+    if (tid < C) tot[tid] = acc;
+  }
+  for (int j = tid; j < M; j += T) cnt[j] = 0;
+  sim_sync<WG>();
+  {
+    double before = 0.0;
+    for (int i = 0; i < C; ++i) {
+      const double t = tot[i];
+      before = i < tid ? before + t : before;
+    }
+    if (tid < C) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        if (i < L) cdf[tid * L + i] = before + run[i];
+    }
+  }
+  sim_sync<WG>();
+
+  const double total = cdf[M - 1];
+  int j_last = 0;   // #{i : cdf[i] < total}: an outcome of probability 0 at the end of the range is never drawn
+  for (int step = M >> 1; step >= 1; step >>= 1)
+    if (cdf[j_last + step - 1] < total) j_last += step;
+  const int64_t key = run_keys[(int64_t)f * B + c];
+  const uint32_t key_lo = (uint32_t)(uint64_t)key, key_hi = (uint32_t)((uint64_t)key >> 32);
+  const int n_pair = (shots + 1) >> 1;   // a Philox block serves shots 2 i (words 0, 1) and 2 i + 1 (words 2, 3)
+  for (int i0 = 0; i0 < n_pair; i0 += T) {
+    const int i = i0 + tid;
+    if (i < n_pair) {
+      uint32_t x[4];
+      philox4x32_10((uint32_t)i, (uint32_t)gl, key_lo, key_hi, seed_lo, seed_hi, x);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        if (2 * i + h < shots) {
+          // u = ((x0 >> 5) 2^26 + (x1 >> 6)) 2^-53: 53 bits, every step exact
+          const double u = ((double)(x[2 * h] >> 5) * 67108864.0 + (double)(x[2 * h + 1] >> 6)) * 0x1p-53;
+          const double target = u * total;
+          int j = 0;   // #{i : cdf[i] <= target}, capped at M - 1 and then at j_last
+          for (int step = M >> 1; step >= 1; step >>= 1)
+            if (cdf[j + step - 1] <= target) j += step;
+          atomicAdd(&cnt[min(j, j_last)], 1);
+        }
+      }
+    }
+  }
+  sim_sync<WG>();
+
+  if (ok)
+    for (int j = tid; j < M; j += T) counts[(int64_t)f * n_outcomes + pb + j] = cnt[j];
+
+  // the group's terms: S_t = sum_j counts_j (-1)^popcount(j & support_t), an integer; estimate = S_t / shots
+  const int64_t tb = min(max(term_ptr[c], (int64_t)0), n_terms), te = min(max(term_ptr[c + 1], tb), n_terms);
+  const int n_term = __builtin_amdgcn_readfirstlane((int)min(te - tb, (int64_t)0x7FFFFFFF));
+  const int qmask = M - 1;
+  for (int t = 0; t < n_term; ++t) {
+    if (__builtin_amdgcn_readfirstlane(term_group[tb + t]) != gl) continue;   // uniform over the wave / workgroup
+    const sim_i4 term = terms[tb + t];
+    const int support = __builtin_amdgcn_readfirstlane((term.x | term.y) & qmask);
+    int part_sum = 0;
+    for (int j = tid; j < M; j += T) part_sum += __popc(j & support) & 1 ? -cnt[j] : cnt[j];
+    int s = sim_wave_sum_int(part_sum);
+    if (WG) {
+      if ((tid & (kWave - 1)) == 0) red_s[tid >> 6] = s;
+      __syncthreads();
+      s = red_s[0] + red_s[1] + red_s[2] + red_s[3];
+      __syncthreads();   // red_s is free again
+    }
+    if (tid == 0) term_values[(int64_t)f * n_terms + tb + t] = (double)s / (double)shots;
+  }
+}
+
+// values and variances of the sampled runs: one thread per run r = f * B + c, terms in order, a fused multiply-add per term
+__global__ __launch_bounds__(kBlock) void sample_finish_kernel(int B, int64_t n_runs, const int64_t* __restrict__ term_ptr,
+                                                               const double* __restrict__ coeff, int64_t n_terms,
+                                                               const double* __restrict__ term_values, double* __restrict__ values,
+                                                               double* __restrict__ variance) {
+  const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (r >= n_runs) return;
+  const int64_t c = r % B, f = r / B;
+  const int64_t tb = min(max(term_ptr[c], (int64_t)0), n_terms), te = min(max(term_ptr[c + 1], tb), n_terms);
+  double val = 0.0, var = 0.0;
+  for (int64_t t = tb; t < te; ++t) {
+    const double tv = term_values[f * n_terms + t], cf = coeff[t];
+    val = __builtin_fma(cf, tv, val);
+    var = __builtin_fma(cf * cf, __builtin_fma(-tv, tv, 1.0), var);
+  }
+  values[r] = val;
+  variance[r] = var;
+}
+
 }  // namespace
 }  // namespace mlqem
 
@@ -483,5 +683,110 @@ extern "C" int mlqem_zne_combine_f64(int64_t n_factors, int64_t n_circuits, cons
   const int64_t blocks = ceil_div(n_circuits > n_terms ? n_circuits : n_terms, (int64_t)kBlock);
   hipLaunchKernelGGL(zne_combine_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), (int)n_factors, term_values, weights,
                      term_ptr, coeff, n_terms, n_circuits, mitigated_terms, mitigated_values);
+  return launch_status();
+}
+
+// The two measured entry points share their checks and launches: `sched_ptr == nullptr` is the plain run (n_factors = 1).
+static int sim_run_measured_impl(bool fold, int64_t n_circuits, int64_t n_factors, const int32_t* circ, const int64_t* op_ptr,
+                                 const mlqem_sim_op* ops, int64_t n_ops, const double* params, int64_t n_params, const int64_t* term_ptr,
+                                 const mlqem_sim_term* terms, const double* coeff, int64_t n_terms, const int64_t* group_ptr,
+                                 const int64_t* prob_ptr, int64_t n_groups, int64_t n_outcomes, const int64_t* sched_ptr,
+                                 const int32_t* sched, int64_t n_sched, const int32_t* ids, int64_t n_wave, int64_t n_wg,
+                                 double* term_values, double* values, double* norm, double* probs, mlqem_stream_t stream) {
+  begin_launches();
+  if (n_circuits < 0 || n_factors < 1 || n_ops < 0 || n_terms < 0 || n_sched < 0 || n_wave < 0 || n_wg < 0 || n_groups < 0 ||
+      n_outcomes < 0 || n_params < kSimParamPad)
+    return MLQEM_ERR_BAD_ARG;
+  if (n_circuits > 0x7FFFFFFFll || n_factors > 0x7FFFFFFFll || n_params > 0x7FFFFFFFll || n_sched > 0x7FFFFFFFll ||
+      n_groups > 0x7FFFFFFFll)
+    return MLQEM_ERR_UNSUPPORTED;
+  const int64_t n_runs = n_factors * n_circuits;   // both below 2^31: no overflow
+  if (n_runs > 0x7FFFFFFFll) return MLQEM_ERR_UNSUPPORTED;
+  if (n_wave + n_wg > n_runs) return MLQEM_ERR_BAD_ARG;
+  if (n_wave + n_wg == 0) return MLQEM_OK;
+  if (!circ || !op_ptr || !params || !term_ptr || !group_ptr || !prob_ptr || !ids || !values || !norm || (n_ops > 0 && !ops) ||
+      (fold && (!sched_ptr || (n_sched > 0 && !sched))) || (n_terms > 0 && (!terms || !coeff || !term_values)) || (n_outcomes > 0 && !probs))
+    return MLQEM_ERR_BAD_ARG;
+  if (!aligned_to(circ, 16) || !aligned_to(ops, 16) || !aligned_to(terms, 16) || !aligned_to(sched_ptr, 8) || !aligned_to(sched, 4) ||
+      !aligned_to(group_ptr, 8) || !aligned_to(prob_ptr, 8) || !aligned_to(probs, 8))
+    return MLQEM_ERR_BAD_ARG;
+  const sim_i4* ci = reinterpret_cast<const sim_i4*>(circ);
+  const sim_i4* oi = reinterpret_cast<const sim_i4*>(ops);
+  const sim_i4* ti = reinterpret_cast<const sim_i4*>(terms);
+  const dim3 wave_grid((unsigned)ceil_div(n_wave, (int64_t)(kBlock / kWave))), wg_grid((unsigned)n_wg);
+#define MLQEM_SIM_MEASURED_LAUNCH(WGV, FOLDV, GRID, IDS, COUNT)                                                                          \
+  hipLaunchKernelGGL((sim_kernel<WGV, FOLDV, true>), GRID, dim3(kBlock), 0, as_stream(stream), (int)n_circuits, ci, op_ptr, oi, n_ops,    \
+                     params, n_params, term_ptr, ti, coeff, n_terms, IDS, (int)(COUNT), term_values, values, norm, (int)n_runs, sched_ptr, \
+                     sched, n_sched, group_ptr, prob_ptr, n_groups, n_outcomes, probs)
+  if (n_wave > 0) {
+    if (fold) MLQEM_SIM_MEASURED_LAUNCH(false, true, wave_grid, ids, n_wave);
+    else MLQEM_SIM_MEASURED_LAUNCH(false, false, wave_grid, ids, n_wave);
+  }
+  if (n_wg > 0) {
+    if (fold) MLQEM_SIM_MEASURED_LAUNCH(true, true, wg_grid, ids + n_wave, n_wg);
+    else MLQEM_SIM_MEASURED_LAUNCH(true, false, wg_grid, ids + n_wave, n_wg);
+  }
+#undef MLQEM_SIM_MEASURED_LAUNCH
+  return launch_status();
+}
+
+extern "C" int mlqem_sim_run_measured_f64(int64_t n_circuits, const int32_t* circ, const int64_t* op_ptr, const mlqem_sim_op* ops,
+                                          int64_t n_ops, const double* params, int64_t n_params, const int64_t* term_ptr,
+                                          const mlqem_sim_term* terms, const double* coeff, int64_t n_terms, const int64_t* group_ptr,
+                                          const int64_t* prob_ptr, int64_t n_groups, int64_t n_outcomes, const int32_t* ids,
+                                          int64_t n_wave, int64_t n_wg, double* term_values, double* values, double* norm,
+                                          double* probs, mlqem_stream_t stream) {
+  return sim_run_measured_impl(false, n_circuits, 1, circ, op_ptr, ops, n_ops, params, n_params, term_ptr, terms, coeff, n_terms,
+                               group_ptr, prob_ptr, n_groups, n_outcomes, nullptr, nullptr, 0, ids, n_wave, n_wg, term_values, values,
+                               norm, probs, stream);
+}
+
+extern "C" int mlqem_sim_run_folded_measured_f64(int64_t n_circuits, int64_t n_factors, const int32_t* circ, const int64_t* op_ptr,
+                                                 const mlqem_sim_op* ops, int64_t n_ops, const double* params, int64_t n_params,
+                                                 const int64_t* term_ptr, const mlqem_sim_term* terms, const double* coeff,
+                                                 int64_t n_terms, const int64_t* group_ptr, const int64_t* prob_ptr, int64_t n_groups,
+                                                 int64_t n_outcomes, const int64_t* sched_ptr, const int32_t* sched, int64_t n_sched,
+                                                 const int32_t* ids, int64_t n_wave, int64_t n_wg, double* term_values, double* values,
+                                                 double* norm, double* probs, mlqem_stream_t stream) {
+  return sim_run_measured_impl(true, n_circuits, n_factors, circ, op_ptr, ops, n_ops, params, n_params, term_ptr, terms, coeff, n_terms,
+                               group_ptr, prob_ptr, n_groups, n_outcomes, sched_ptr, sched, n_sched, ids, n_wave, n_wg, term_values,
+                               values, norm, probs, stream);
+}
+
+extern "C" int mlqem_sim_sample_f64(int64_t n_circuits, int64_t n_factors, const int32_t* circ, const int64_t* term_ptr,
+                                    const mlqem_sim_term* terms, const double* coeff, int64_t n_terms, const int64_t* group_ptr,
+                                    const int32_t* term_group, const int64_t* prob_ptr, const int32_t* group_circ, int64_t n_groups,
+                                    int64_t n_outcomes, const double* probs, const int64_t* run_keys, int64_t shots, uint64_t seed,
+                                    const int32_t* units, int64_t n_wave, int64_t n_wg, int32_t* counts, double* term_values,
+                                    double* values, double* variance, mlqem_stream_t stream) {
+  begin_launches();
+  if (n_circuits < 0 || n_factors < 1 || n_terms < 0 || n_groups < 0 || n_outcomes < 0 || n_wave < 0 || n_wg < 0) return MLQEM_ERR_BAD_ARG;
+  if (shots < 1 || shots > MLQEM_SIM_MAX_SHOTS) return MLQEM_ERR_BAD_ARG;
+  if (n_circuits > 0x7FFFFFFFll || n_factors > 0x7FFFFFFFll || n_groups > 0x7FFFFFFFll) return MLQEM_ERR_UNSUPPORTED;
+  const int64_t n_runs = n_factors * n_circuits, n_units = n_factors * n_groups;   // factors below 2^31: no overflow
+  if (n_runs > 0x7FFFFFFFll || n_units > 0x7FFFFFFFll) return MLQEM_ERR_UNSUPPORTED;
+  if (n_wave + n_wg != n_units) return MLQEM_ERR_BAD_ARG;   // every (factor, group) pair is sampled: the values need all of them
+  if (n_circuits == 0) return MLQEM_OK;
+  if (n_groups < 1 || n_outcomes < 1) return MLQEM_ERR_BAD_ARG;   // a circuit has at least one group of at least two outcomes
+  if (!circ || !term_ptr || !group_ptr || !prob_ptr || !group_circ || !probs || !run_keys || !units || !counts || !values || !variance ||
+      (n_terms > 0 && (!terms || !coeff || !term_group || !term_values)))
+    return MLQEM_ERR_BAD_ARG;
+  if (!aligned_to(circ, 16) || !aligned_to(terms, 16) || !aligned_to(probs, 8) || !aligned_to(run_keys, 8)) return MLQEM_ERR_BAD_ARG;
+  const sim_i4* ci = reinterpret_cast<const sim_i4*>(circ);
+  const sim_i4* ti = reinterpret_cast<const sim_i4*>(terms);
+  const uint32_t seed_lo = (uint32_t)seed, seed_hi = (uint32_t)(seed >> 32);
+  if (n_wave > 0) {
+    const int64_t blocks = ceil_div(n_wave, (int64_t)(kBlock / kWave));
+    hipLaunchKernelGGL((sample_kernel<false>), dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), (int)n_circuits, (int)n_factors,
+                       ci, term_ptr, ti, n_terms, group_ptr, term_group, prob_ptr, group_circ, (int)n_groups, n_outcomes, probs, run_keys,
+                       (int)shots, seed_lo, seed_hi, units, (int)n_wave, counts, term_values);
+  }
+  if (n_wg > 0) {
+    hipLaunchKernelGGL((sample_kernel<true>), dim3((unsigned)n_wg), dim3(kBlock), 0, as_stream(stream), (int)n_circuits, (int)n_factors,
+                       ci, term_ptr, ti, n_terms, group_ptr, term_group, prob_ptr, group_circ, (int)n_groups, n_outcomes, probs, run_keys,
+                       (int)shots, seed_lo, seed_hi, units + n_wave, (int)n_wg, counts, term_values);
+  }
+  hipLaunchKernelGGL(sample_finish_kernel, dim3((unsigned)ceil_div(n_runs, (int64_t)kBlock)), dim3(kBlock), 0, as_stream(stream),
+                     (int)n_circuits, n_runs, term_ptr, coeff, n_terms, term_values, values, variance);
   return launch_status();
 }

@@ -4,6 +4,7 @@ arena, train the reference's Family A GNN with the reference's loop shape, repor
     python examples/train_family_a.py --qubits 12 --epochs 5                         # one GPU
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29511 \
         examples/train_family_a.py --qubits 100 --epochs 3                            # one rank per GPU, RCCL all-reduce
+    python examples/train_family_a.py --qubits 100 --epochs 3 --clifford-labels      # simulated labels on Clifford circuits
 
 Everything the reference does on the host per step (PyG DataLoader collate, loss.item()) happens on the device here;
 the host only draws graph ids.  See INTEGRATION.md for moving an existing ml-qem dataset (.json / .pk) into shards.
@@ -21,7 +22,8 @@ sys.path[:0] = [os.path.join(ROOT, "ml-qem_amd")]
 
 from blackwater.data.arena import GraphArena                      # noqa: E402
 from blackwater.data.shards import pack_graphs, write_shard       # noqa: E402
-from blackwater.data.synthetic import tfim_corpus                 # noqa: E402
+from blackwater.data.synthetic import (clifford_tfim_circuit, encode_corpus, random_clifford_circuit,  # noqa: E402
+                                       synthetic_backend, tfim_corpus)
 from blackwater.metrics.improvement_factor import mitigation_report  # noqa: E402
 from blackwater.nn import ExpValCircuitGraphModelA                # noqa: E402
 from blackwater.train import DataParallelShard, Trainer           # noqa: E402
@@ -35,6 +37,9 @@ def main():
     ap.add_argument("--epochs", type=int, default=5)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--shard-dir", default=None)
+    ap.add_argument("--clifford-labels", action="store_true",
+                    help="train on Clifford circuits (TFIM at multiples of pi / 2, and random Clifford layers) whose ideal and noisy "
+                         "labels are simulated exactly on the device under the synthetic backend's noise model, at any --qubits <= 512")
     args = ap.parse_args()
 
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -46,11 +51,21 @@ def main():
         torch.distributed.init_process_group(os.environ.get("MLQEM_BACKEND", "nccl"), device_id=dev)
 
     # 1. encode once (rank 0) into two shards; every rank then maps them and keeps its round-robin part
-    shard_dir = args.shard_dir or os.path.join(tempfile.gettempdir(), f"mlqem_example_{args.qubits}q")
+    shard_dir = args.shard_dir or os.path.join(tempfile.gettempdir(),
+                                               f"mlqem_example_{args.qubits}q" + ("_clifford" if args.clifford_labels else ""))
     paths = [os.path.join(shard_dir, f"part{k}.mlqs") for k in range(2)]
     if rank == 0 and not all(os.path.exists(p) for p in paths):
         os.makedirs(shard_dir, exist_ok=True)
-        c = tfim_corpus(args.qubits, list(range(1, args.steps + 1)), args.n_j, two_q="cx")
+        if args.clifford_labels:
+            from blackwater import sim
+
+            circuits = [clifford_tfim_circuit(args.qubits, s, kx, kz, two_q="cx")
+                        for s in range(1, args.steps + 1) for kx in range(4) for kz in range(4)]
+            circuits += [random_clifford_circuit(args.qubits, 2 + k % 8, k, two_q="cx", basis=True) for k in range(args.n_j)]
+            noise = sim.NoiseModel.from_backend(synthetic_backend(args.qubits, "cx"))
+            c = encode_corpus(circuits, args.qubits, two_q="cx", simulate=noise, device=dev, clifford=True)
+        else:
+            c = tfim_corpus(args.qubits, list(range(1, args.steps + 1)), args.n_j, two_q="cx")
         half = len(c["x"]) // 2
         for p, sl in zip(paths, (slice(0, half), slice(half, None))):
             write_shard(p, pack_graphs(c["x"][sl], c["edge_index"][sl], c["y"][sl], c["noisy"][sl], c["depth"][sl],

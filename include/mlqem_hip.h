@@ -1509,6 +1509,71 @@ int mlqem_sim_sample_f64(int64_t n_circuits, int64_t n_factors, const int32_t* c
                          const int32_t* units, int64_t n_wave, int64_t n_wg, int32_t* counts, double* term_values, double* values,
                          double* variance, mlqem_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Clifford circuits of up to MLQEM_CLIFFORD_MAX_QUBITS = 512 qubits, a batch per call (an additive symbol, the ABI version is
+ * unchanged).  A Pauli observable is carried BACKWARDS through a Clifford circuit as a Pauli, so its ideal value on |0..0> and its
+ * value under the project's depolarising model come from one walk over the records, in O(records) bit operations per (circuit,
+ * Pauli) pair: no state vector.  blackwater.sim.clifford lowers circuits to this format (compile_clifford) and
+ * blackwater.native.ops.clifford_run calls it.
+ *
+ * A UNIT is one (circuit, Pauli) pair.  Its Pauli is W = ceil(n / 32) x words followed by W z words in `masks` (bit q % 32 of word
+ * q / 32: x set for X or Y on qubit q, z set for Z or Y), i.e. the LETTER of qubit q is l = x | z << 1: I = 0, X = 1, Z = 2, Y = 3,
+ * where Y is the Hermitian Pauli Y itself (not i X Z), so the Pauli is (-1)^sign times the product of its letters and nothing else.
+ *
+ * n_qubits int32 [n_circuits]: clamped to 1 .. 512 (to 1 .. 128 for a unit among the first n_reg).
+ * op_ptr   int64 [n_circuits + 1]: circuit c owns ops[op_ptr[c] .. op_ptr[c + 1]), in circuit order.  A unit walks them from the
+ *          LAST to the FIRST.
+ * ops      mlqem_clifford_op [n_ops], 16-byte aligned: (head, a, b, c) with head = kind | q0 << 4 | q1 << 14 (kind 4 bits, qubits 10
+ *          bits each, clamped to n - 1).  With l0 / l1 the unit's letters at q0 / q1:
+ *            MLQEM_CLIFFORD_OP_C1      a one-qubit Clifford U.  a holds U^dagger P U for P = X, Z, Y (l0 = 1, 2, 3) as three 3-bit
+ *                                      fields, field l0 - 1 at bits 3 (l0 - 1) ..: new letter | s << 2.  l0 becomes the new
+ *                                      letter and sign ^= s; l0 = 0 stays.
+ *            MLQEM_CLIFFORD_OP_C2      a two-qubit Clifford.  With p = l0 | l1 << 2 (1 .. 15) and e = p - 1: the 4-bit field e of
+ *                                      the 64-bit word a | b << 32 is the image's p (new l0 | new l1 << 2), bit e of c its sign.
+ *                                      p = 0 stays.
+ *            MLQEM_CLIFFORD_OP_DEPOL1  a = index into `pool` of keep = 1 - lambda: factor *= keep if l0 != 0 (the adjoint of
+ *                                      rho -> (1 - lambda) rho + lambda Tr_q0(rho) (x) I/2 scales every Pauli that is not the
+ *                                      identity on q0 by 1 - lambda and leaves the others).
+ *            MLQEM_CLIFFORD_OP_DEPOL2  the same over q0 and q1: factor *= keep if l0 | l1 != 0.
+ *          An unknown kind is skipped.  Readout noise is no record: the host applies it to the observable (Z -> a Z + b I), which
+ *          is what `comb` below is for.
+ * pool     float64 [n_pool], n_pool >= MLQEM_CLIFFORD_PAD = 32 (an index is clamped to [0, n_pool - 1]).
+ * units    mlqem_clifford_unit [n_reg + n_lds], 16-byte aligned: (circuit, mask, ny, 0).  mask = index of the unit's first x word in
+ *          `masks` (every word index is clamped to [0, n_masks - 1]); ny = the number of Y letters, carried for the host (with
+ *          Hermitian letters the kernel has no use for it: a Pauli without x bits has no Y left).  The first n_reg units belong to
+ *          circuits of at most MLQEM_CLIFFORD_REG_QUBITS = 128 qubits and keep their eight words in registers; the other n_lds
+ *          keep up to 32 words in LDS (word w of lane t at w * 256 + t; 32 KB per 256-thread workgroup).  Units should be ordered
+ *          by circuit inside each part, so that the lanes of a wave load the same records.
+ * masks    uint32 [n_masks], n_masks >= 32.
+ * Per unit: factor = 1, sign = 0; after the walk  ideal = 0 if any x bit is left, else (-1)^sign;  noisy = ideal * factor, factor
+ * being multiplied up in walk order, one rounded product per record.  unit_ideal / unit_noisy float64 [n_reg + n_lds] receive them.
+ * term_ptr int64 [n_circuits + 1]; coeff float64 [n_terms]; comb_ptr int64 [n_terms + 1]; comb_unit int32 [n_comb] (clamped);
+ *          comb_weight float64 [n_comb][2]:  ideal_terms[t] = sum_j comb_weight[j][0] * unit_ideal[comb_unit[j]] and
+ *          noisy_terms[t] = sum_j comb_weight[j][1] * unit_noisy[comb_unit[j]] over j in [comb_ptr[t], comb_ptr[t + 1]), from 0.0 in
+ *          that order; ideal_values[c] / noisy_values[c] = sum_t coeff[t] * term, from 0.0 in term order (0.0 for a circuit without
+ *          terms).  Every product and every sum is rounded on its own (no fused multiply-add).
+ * No atomics, no workspace, no host read: capturable in a hipGraph, at most three launches, and a circuit's results are the same
+ * bits alone or in any batch.  Every value read from a record is clamped, so a malformed record computes garbage and faults
+ * nothing.  Negative sizes, n_pool or n_masks < 32, null or misaligned buffers, combine entries without units: MLQEM_ERR_BAD_ARG; a
+ * count over 2^31 - 1: MLQEM_ERR_UNSUPPORTED; all checked before anything is launched.  n_circuits == 0 returns MLQEM_OK without a
+ * launch.
+ * ---------------------------------------------------------------------------------------------------- */
+#define MLQEM_CLIFFORD_MAX_QUBITS 512
+#define MLQEM_CLIFFORD_REG_QUBITS 128
+#define MLQEM_CLIFFORD_PAD 32
+#define MLQEM_CLIFFORD_OP_C1 0
+#define MLQEM_CLIFFORD_OP_C2 1
+#define MLQEM_CLIFFORD_OP_DEPOL1 2
+#define MLQEM_CLIFFORD_OP_DEPOL2 3
+typedef struct mlqem_clifford_op { int32_t head; int32_t a; int32_t b; int32_t c; } mlqem_clifford_op;
+typedef struct mlqem_clifford_unit { int32_t circuit; int32_t mask; int32_t ny; int32_t reserved; } mlqem_clifford_unit;
+int mlqem_clifford_run_f64(int64_t n_circuits, const int32_t* n_qubits, const int64_t* op_ptr, const mlqem_clifford_op* ops,
+                           int64_t n_ops, const double* pool, int64_t n_pool, const mlqem_clifford_unit* units, int64_t n_reg,
+                           int64_t n_lds, const uint32_t* masks, int64_t n_masks, const int64_t* term_ptr, const double* coeff,
+                           int64_t n_terms, const int64_t* comb_ptr, const int32_t* comb_unit, const double* comb_weight,
+                           int64_t n_comb, double* unit_ideal, double* unit_noisy, double* ideal_terms, double* noisy_terms,
+                           double* ideal_values, double* noisy_values, mlqem_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,8 @@ repeated ``steps`` times, then ``measure_all``.  It is lowered with one fixed ru
 {rz, sx, x, ecr|cx} so that op counts land near what the reference's transpiled circuits hold (100 qubits:
 ~2.0k ops and 198 two-qubit gates per step; measured there: 1,584 / 8,999 / 20,711 ops at 1 / 6 / 10 steps).
 Labels are synthetic by default (they only feed the loss and the MAE plumbing); ``encode_corpus(simulate=...)`` fills them with
-simulated values from ``blackwater.sim`` for circuits small enough to simulate exactly.
+simulated values from ``blackwater.sim`` for circuits small enough to simulate exactly, and with ``clifford=True`` also for wider
+Clifford circuits (``clifford_tfim_circuit``, ``random_clifford_circuit``: up to 512 qubits).
 """
 from __future__ import annotations
 
@@ -23,8 +24,18 @@ from .utils import circuit_to_graph_data_json, get_backend_properties_v1
 
 def tfim_circuit(nq: int, steps: int, J: float, h: float = 0.66 * math.pi, dt: float = 0.5,
                  two_q: str = "ecr") -> Circuit:
+    return _tfim(nq, steps, 2 * h * dt, -2 * J * dt, two_q)
+
+
+def clifford_tfim_circuit(nq: int, steps: int, kx: int, kz: int, two_q: str = "ecr") -> Circuit:
+    """:func:`tfim_circuit` with the field rotation ``theta = kx pi / 2`` and the bond rotation ``phi = kz pi / 2`` (integers): every
+    gate is then a Clifford gate, so ``blackwater.sim.clifford_expectation_values`` gives its exact ideal and noisy values at any
+    width."""
+    return _tfim(nq, steps, int(kx) * math.pi / 2, int(kz) * math.pi / 2, two_q)
+
+
+def _tfim(nq: int, steps: int, theta: float, phi: float, two_q: str) -> Circuit:
     ops: List[CircuitOp] = []
-    theta, phi = 2 * h * dt, -2 * J * dt
     all_q = tuple(range(nq))
 
     def rx(q):
@@ -89,6 +100,39 @@ def random_circuit(nq: int, depth: int, seed: int, two_q: str = "cx", measure: b
     return Circuit(nq, nq if measure else 0, ops)
 
 
+_CLIFFORD_IN_BASIS = {"h": (("rz", math.pi / 2), ("sx", None), ("rz", math.pi / 2)), "s": (("rz", math.pi / 2),),
+                      "sdg": (("rz", -math.pi / 2),), "x": (("x", None),), "y": (("rz", math.pi), ("x", None)), "z": (("rz", math.pi),),
+                      "sx": (("sx", None),)}   # equal up to a global phase
+
+
+def random_clifford_circuit(nq: int, depth: int, seed: int, two_q: str = "cx", measure: bool = True, basis: bool = False) -> Circuit:
+    """Layers of random disjoint Clifford gates on a line, in the style of :func:`random_circuit`: walking the line, a pair of
+    neighbours gets ``two_q`` (either direction) with probability 0.35, otherwise the qubit gets one of h, s, sdg, x, y, z, sx or
+    stays idle in this layer, each with probability 1/8.  ``basis=True`` writes the same draws in the backend basis {rz, sx, x, two_q}
+    (h = rz sx rz, s = rz(pi / 2), y = x rz(pi), ...), which is what :func:`encode_corpus` and :func:`synthetic_backend` can encode."""
+    rng = np.random.default_rng(seed)
+    one = ("h", "s", "sdg", "x", "y", "z", "sx")
+    ops: List[CircuitOp] = []
+    for _ in range(depth):
+        q = 0
+        while q < nq:
+            if q + 1 < nq and rng.random() < 0.35:
+                a, b = (q, q + 1) if rng.random() < 0.5 else (q + 1, q)
+                ops.append(CircuitOp(two_q, (a, b)))
+                q += 2
+                continue
+            kind = int(rng.integers(0, len(one) + 1))
+            if kind < len(one) and basis:
+                ops.extend(CircuitOp(g, (q,), (), () if angle is None else (angle,)) for g, angle in _CLIFFORD_IN_BASIS[one[kind]])
+            elif kind < len(one):
+                ops.append(CircuitOp(one[kind], (q,)))
+            q += 1
+    if measure:
+        ops.append(CircuitOp("barrier", tuple(range(nq))))
+        ops.extend(CircuitOp("measure", (q,), (q,)) for q in range(nq))
+    return Circuit(nq, nq if measure else 0, ops)
+
+
 def pauli_twirl(circ: Circuit, seed: int, two_q=("cx", "ecr")) -> Circuit:
     """Random single-qubit Paulis (x, or rz(pi) for Z, or both for Y) before and after every two-qubit gate -- the
     structural effect of Pauli twirling on the circuit graph (cfg5 of BASELINE.json)."""
@@ -117,12 +161,15 @@ def pauli_twirl(circ: Circuit, seed: int, two_q=("cx", "ecr")) -> Circuit:
 
 
 def encode_corpus(circuits, nq: int, two_q: str = "cx", seed: int = 7, exp_value_size: int = 1,
-                  add_self_loops: bool = True, simulate=None, device="cuda", shots=None, sample_ideal: bool = False) -> Dict[str, list]:
+                  add_self_loops: bool = True, simulate=None, device="cuda", shots=None, sample_ideal: bool = False,
+                  clifford: bool = False) -> Dict[str, list]:
     """Arena-ready arrays (same keys as :func:`tfim_corpus`) for arbitrary circuits, encoded by the native encoder.
 
     ``simulate=None``: synthetic labels (a uniform draw and a made-up decay).  ``simulate=`` a ``blackwater.sim.NoiseModel``: ``y``
     and ``noisy`` of every circuit within the simulator's caps (5 qubits as a density matrix) are the exact and the noisy
-    ``<Z>`` of the circuit's observable qubit, simulated on ``device`` in two launches; larger circuits keep the synthetic labels.
+    ``<Z>`` of the circuit's observable qubit, simulated on ``device`` in two launches; larger circuits keep the synthetic labels,
+    unless ``clifford=True``: then every larger circuit that is a Clifford circuit of at most 512 qubits (``sim.is_clifford``) gets its
+    exact and noisy ``<Z>`` from ``sim.clifford_expectation_values``, in one call (exact values only: ``shots`` with it is refused).
     ``shots`` (with ``simulate``; default ``None``: exact): the noisy value is a ``shots``-shot estimate drawn on the device with
     ``seed`` (``sim.sample_expectation_values``), and with ``sample_ideal=True`` the ideal one too."""
     from .circuit import circuit_to_qasm
@@ -152,9 +199,22 @@ def encode_corpus(circuits, nq: int, two_q: str = "cx", seed: int = 7, exp_value
         obs.append(o)
         kept.append(circ)
         z_qubits.append(qz)
+    if clifford and simulate is None:
+        raise ValueError("encode_corpus: clifford=True fills simulated labels, so it needs simulate= (a noise model)")
+    if clifford and shots is not None:
+        raise ValueError("encode_corpus: clifford=True gives exact values only; shots are not drawn on the Clifford path")
     if simulate is not None:
         from .. import sim
 
+        wide = [k for k, circ in enumerate(kept) if clifford and sim.MAX_QUBITS_DENSITY < circ.num_qubits <= sim.MAX_QUBITS_CLIFFORD
+                and sim.is_clifford(circ)]
+        if wide:
+            labels = ["".join("Z" if q == z_qubits[k] else "I" for q in reversed(range(kept[k].num_qubits))) for k in wide]
+            under, _, _, exact, _ = sim.clifford_expectation_values([kept[k] for k in wide], labels, simulate, device, return_ideal=True)
+            under, exact = under.cpu().numpy(), exact.cpu().numpy()
+            for j, k in enumerate(wide):
+                ys[k] = np.full(exp_value_size, exact[j])
+                noisy[k] = np.full(exp_value_size, under[j])
         inside = [k for k, circ in enumerate(kept) if 1 <= circ.num_qubits <= sim.MAX_QUBITS_DENSITY]
         if inside:
             labels = ["".join("Z" if q == z_qubits[k] else "I" for q in reversed(range(kept[k].num_qubits))) for k in inside]

@@ -2870,3 +2870,59 @@ def sim_sample(circ, term_ptr, terms, coeff, group_ptr, term_group, prob_ptr, gr
         _p(units), n_wave, n_wg, _p(counts), _p(term_values) if n_terms else None, _p(values), _p(variance), _stream())
     _lib.check(code, "mlqem_sim_sample_f64")
     return values, variance, term_values, counts
+
+
+CLIFFORD_MAX_QUBITS = 512   # MLQEM_CLIFFORD_MAX_QUBITS
+CLIFFORD_REG_QUBITS = 128   # MLQEM_CLIFFORD_REG_QUBITS: units of circuits up to here keep their Pauli words in registers
+CLIFFORD_PAD = 32           # entries of padding `pool` and `masks` end with
+
+
+def clifford_run(n_qubits, op_ptr, ops, pool, units, n_reg, n_lds, masks, term_ptr, coeff, comb_ptr, comb_unit, comb_weight, *,
+                 unit_ideal=None, unit_noisy=None, ideal_terms=None, noisy_terms=None, ideal_values=None, noisy_values=None):
+    """Carries every unit's Pauli backwards through its Clifford circuit (mlqem_clifford_run_f64): ``(ideal_values, noisy_values,
+    ideal_terms, noisy_terms, unit_ideal, unit_noisy)``, float64 [B], [B], [n_terms], [n_terms], [n_units], [n_units].
+
+    ``n_qubits`` int32 [B], ``op_ptr`` int64 [B + 1], ``ops`` int32 [n_ops, 4], ``pool`` float64 [>= 32], ``units`` int32 [n_units,
+    4], ``masks`` int32 [>= 32] (the uint32 words), ``term_ptr`` int64 [B + 1], ``coeff`` float64 [n_terms], ``comb_ptr`` int64
+    [n_terms + 1], ``comb_unit`` int32 [n_comb], ``comb_weight`` float64 [n_comb, 2]: the buffers of
+    ``blackwater.sim.CliffordBatch.to(device)``, in the layout of include/mlqem_hip.h.  ``n_reg`` / ``n_lds``: how many of ``units``
+    (the first / the rest) keep their words in registers / in LDS.  Shapes, dtypes and devices are checked here; the CONTENTS are
+    ``compile_clifford``'s to guarantee (the kernel clamps every index).  Nothing here waits for the device or reads a tensor, and with
+    the six outputs given nothing is allocated: the call can be captured in a hipGraph."""
+    for t, name, cols in ((ops, "ops", 4), (units, "units", 4)):
+        if not t.is_cuda:
+            raise _lib.NativeLibraryError(f"{name} must live on the GPU (got {t.device}); there is no CPU path")
+        if t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != cols or not t.is_contiguous():
+            raise ValueError(f"clifford: want contiguous torch.int32 {name} [., {cols}], got {tuple(t.shape)} {t.dtype}")
+    b, n_ops, n_units = int(n_qubits.shape[0]), int(ops.shape[0]), int(units.shape[0])
+    n_terms, n_comb = int(coeff.shape[0]), int(comb_unit.shape[0])
+    n_reg, n_lds = int(n_reg), int(n_lds)
+    if n_reg < 0 or n_lds < 0 or n_reg + n_lds != n_units:
+        raise ValueError(f"clifford: n_reg = {n_reg} and n_lds = {n_lds} must be >= 0 and add up to the {n_units} units")
+    _vec(n_qubits, "n_qubits", b, torch.int32)
+    _vec(op_ptr, "op_ptr", b + 1, torch.int64)
+    _vec(term_ptr, "term_ptr", b + 1, torch.int64)
+    _vec(pool, "pool", CLIFFORD_PAD, torch.float64)
+    _vec(masks, "masks", CLIFFORD_PAD, torch.int32)
+    _vec(coeff, "coeff", n_terms, torch.float64)
+    _vec(comb_ptr, "comb_ptr", n_terms + 1, torch.int64)
+    _vec(comb_unit, "comb_unit", n_comb, torch.int32)
+    if (not comb_weight.is_cuda or comb_weight.dtype != torch.float64 or tuple(comb_weight.shape) != (n_comb, 2)
+            or not comb_weight.is_contiguous()):
+        raise ValueError(f"comb_weight: want contiguous float64 [{n_comb}, 2] on the GPU, got {tuple(comb_weight.shape)} {comb_weight.dtype}")
+    if n_comb and not n_units:
+        raise ValueError(f"clifford: {n_comb} combine entries but no unit")
+    dev = ops.device
+    if any(t.device != dev for t in (n_qubits, op_ptr, pool, units, masks, term_ptr, coeff, comb_ptr, comb_unit, comb_weight)):
+        raise ValueError(f"clifford: ops is on {dev}, another buffer is not")
+    unit_ideal, unit_noisy = _sim_out(unit_ideal, "unit_ideal", (n_units,), dev), _sim_out(unit_noisy, "unit_noisy", (n_units,), dev)
+    ideal_terms, noisy_terms = _sim_out(ideal_terms, "ideal_terms", (n_terms,), dev), _sim_out(noisy_terms, "noisy_terms", (n_terms,), dev)
+    ideal_values, noisy_values = _sim_out(ideal_values, "ideal_values", (b,), dev), _sim_out(noisy_values, "noisy_values", (b,), dev)
+    code = _lib.load().mlqem_clifford_run_f64(
+        b, _p(n_qubits), _p(op_ptr), _p(ops) if n_ops else None, n_ops, _p(pool), int(pool.shape[0]), _p(units) if n_units else None,
+        n_reg, n_lds, _p(masks), int(masks.shape[0]), _p(term_ptr), _p(coeff) if n_terms else None, n_terms, _p(comb_ptr),
+        _p(comb_unit) if n_comb else None, _p(comb_weight) if n_comb else None, n_comb, _p(unit_ideal) if n_units else None,
+        _p(unit_noisy) if n_units else None, _p(ideal_terms) if n_terms else None, _p(noisy_terms) if n_terms else None,
+        _p(ideal_values), _p(noisy_values), _stream())
+    _lib.check(code, "mlqem_clifford_run_f64")
+    return ideal_values, noisy_values, ideal_terms, noisy_terms, unit_ideal, unit_noisy

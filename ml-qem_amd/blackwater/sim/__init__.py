@@ -1,9 +1,13 @@
 """Batched exact simulation of small circuits on the device: ideal (state vector) and noisy (density matrix) expectation values,
 the labels the mitigators learn from.  ``compile_programs`` / ``NoiseModel`` / ``measured_z`` run on the host alone.  ``blackwater.sim.zne`` (also ``blackwater.zne``) is
-zero-noise extrapolation on it; the ``zne(cls)`` decorator lives there, so that ``sim.zne`` stays the module."""
+zero-noise extrapolation on it; the ``zne(cls)`` decorator lives there, so that ``sim.zne`` stays the module.
+``blackwater.sim.clifford`` is the path for wide circuits: Clifford circuits of up to 512 qubits, ideal and noisy, by carrying the
+observable backwards through the circuit (``compile_clifford`` / ``clifford_expectation_values``)."""
 from .program import (MAX_AMPS, MAX_QUBITS_DENSITY, MAX_QUBITS_VECTOR, SUPPORTED_GATES, WAVE_AMPS, NoiseModel, SimBatch,
                       compile_programs, measured_z)
 from .program import MAX_SHOTS, measurement_groups
+from .clifford import (MAX_QUBITS_CLIFFORD, CliffordBatch, clifford_expectation_values, compile_clifford, is_clifford,
+                       run_clifford)
 from .run import (DeviceEstimator, SampleResult, SimulatedJob, counts_dicts, default_run_keys, expectation_values, run_batch,
                   sample_batch, sample_expectation_values)
 from .zne import (CubicExtrapolator, CxAmplifier, GlobalFoldingAmplifier, LinearExtrapolator, LocalFoldingAmplifier,
@@ -16,4 +20,5 @@ __all__ = ["MAX_AMPS", "MAX_QUBITS_DENSITY", "MAX_QUBITS_VECTOR", "SUPPORTED_GAT
            "PolynomialExtrapolator", "QuadraticExtrapolator", "QuarticExtrapolator", "RichardsonExtrapolator", "Schedules",
            "TwoQubitAmplifier", "ZNEStrategy", "build_schedules", "fold_circuit", "zne_expectation_values", "zne_run",
            "MAX_SHOTS", "measurement_groups", "SampleResult", "counts_dicts", "default_run_keys", "sample_batch",
-           "sample_expectation_values"]
+           "sample_expectation_values", "MAX_QUBITS_CLIFFORD", "CliffordBatch", "clifford_expectation_values", "compile_clifford",
+           "is_clifford", "run_clifford"]

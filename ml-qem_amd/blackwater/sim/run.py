@@ -8,7 +8,9 @@ from typing import Any, Dict, List, Optional, Sequence
 import numpy as np
 
 from ..library.primitives import make_estimator_result
-from .program import NoiseModel, SimBatch, check_seed, check_shots, compile_programs
+from ..data.circuit import Circuit
+from .clifford import clifford_expectation_values, is_clifford
+from .program import MAX_QUBITS_DENSITY, MAX_QUBITS_VECTOR, NoiseModel, SimBatch, check_seed, check_shots, compile_programs
 
 
 def run_batch(batch: SimBatch, device="cuda"):
@@ -157,9 +159,20 @@ class DeviceEstimator:
     many measurement outcomes per measurement basis (:func:`sample_expectation_values`) and ``metadata[k] = {"variance": v_k,
     "shots": shots}``, as qiskit's estimators report.  ``seed`` (constructor or run option) keys the draws.  Successive ``run()``
     calls of one estimator do not repeat their draws: circuit k of the estimator's j-th job (j = 1, 2, ...; exact jobs count too)
-    draws with the run key ``j * 2^32 + k``, so two estimators with one seed that are asked the same things agree."""
+    draws with the run key ``j * 2^32 + k``, so two estimators with one seed that are asked the same things agree.
 
-    def __init__(self, noise: Optional[NoiseModel] = None, device="cuda", shots: Optional[int] = None, seed: int = 0):
+    ``method``: ``"exact"`` (the default: the state-vector / density-matrix simulator and its caps, as above); ``"clifford"``: the
+    Clifford path (:func:`clifford_expectation_values`: Clifford circuits of up to 512 qubits, exact under the same noise model);
+    ``"auto"``: the exact simulator when every circuit of a job fits its cap, else the Clifford path when every circuit is a Clifford
+    circuit, else a ``ValueError`` naming a circuit that is neither.  The Clifford path draws no shots: ``shots`` with it is refused."""
+
+    METHODS = ("exact", "clifford", "auto")
+
+    def __init__(self, noise: Optional[NoiseModel] = None, device="cuda", shots: Optional[int] = None, seed: int = 0,
+                 method: str = "exact"):
+        if method not in self.METHODS:
+            raise ValueError(f"DeviceEstimator: method = {method!r}, want one of {', '.join(self.METHODS)}")
+        self._method = method
         self._noise, self._device, self._count = noise, device, 0
         self._shots = None if shots is None else check_shots(shots, "DeviceEstimator")
         self._seed = check_seed(seed, "DeviceEstimator")
@@ -176,6 +189,13 @@ class DeviceEstimator:
                 raise ValueError(f"DeviceEstimator: circuit {k} comes with {len(p)} parameter values; circuits must arrive bound")
         shots = run_options.pop("shots", self._shots)
         seed = run_options.pop("seed", self._seed)
+        if self._method != "exact" and self._use_clifford(circuits):
+            if shots is not None:
+                raise ValueError("DeviceEstimator: shots are not drawn on the Clifford path (method='clifford', or 'auto' on circuits "
+                                 "over the exact simulator's cap); run it without shots")
+            self._count += 1
+            values = clifford_expectation_values(circuits, observables, self._noise, self._device)[0]
+            return SimulatedJob(values.cpu().numpy(), f"sim-{self._count}")
         self._count += 1
         if shots is None:
             values, _, _ = expectation_values(circuits, observables, self._noise, self._device)
@@ -186,3 +206,18 @@ class DeviceEstimator:
         variance = res.variance.cpu().numpy()
         return SimulatedJob(res.values.cpu().numpy(), f"sim-{self._count}",
                             [{"variance": float(v), "shots": shots} for v in variance])
+
+    def _use_clifford(self, circuits) -> bool:
+        if self._method == "clifford":
+            return True
+        cap = MAX_QUBITS_VECTOR if self._noise is None else MAX_QUBITS_DENSITY
+        parsed = [Circuit.from_any(c) for c in circuits]
+        over = [k for k, c in enumerate(parsed) if c.num_qubits > cap]
+        if not over:
+            return False
+        for k in over + [k for k in range(len(parsed)) if k not in over]:   # name a circuit that fits neither path first
+            if not is_clifford(parsed[k]):
+                raise ValueError(f"DeviceEstimator(method='auto'): circuit {over[0]} has {parsed[over[0]].num_qubits} qubits, over the "
+                                 f"exact simulator's cap of {cap} in this mode, so the job needs the Clifford path, and circuit {k} "
+                                 "is not a Clifford circuit")
+        return True

@@ -1574,6 +1574,60 @@ int mlqem_clifford_run_f64(int64_t n_circuits, const int32_t* n_qubits, const in
                            int64_t n_comb, double* unit_ideal, double* unit_noisy, double* ideal_terms, double* noisy_terms,
                            double* ideal_values, double* noisy_values, mlqem_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Zero-noise extrapolation at width (two additive symbols, the ABI version is unchanged).  A folded Clifford circuit is a Clifford
+ * circuit: the same records replayed in another order, some as their inverse, and the inverse of a conjugation table is the
+ * inverse of a signed permutation.  So the circuits are lowered ONCE (the buffers of mlqem_clifford_run_f64) and every (circuit,
+ * noise factor) pair gets a schedule in the format of mlqem_sim_run_folded_f64.  blackwater.sim.zne builds the schedules
+ * (build_clifford_schedules) and blackwater.native.ops.clifford_run_folded / zne_combine_exp call these.
+ *
+ * mlqem_clifford_run_folded_f64.  Run r = f * B + c is circuit c at noise factor f, 0 <= f < n_factors = F.
+ * sched_ptr int64 [F * B + 1]; sched int32 [n_sched]: run r owns sched[sched_ptr[r] .. sched_ptr[r + 1]).  An entry is
+ *         (k << 1) | dagger with k a record index RELATIVE to op_ptr[c].  The circuit of run r is ops[op_ptr[c] + k] for each entry
+ *         in order; a unit of circuit c walks the entries of run (f, c) from the LAST to the FIRST, exactly as
+ *         mlqem_clifford_run_f64 walks the records.  There are no trailing entries: readout is no record in this format.
+ *         dagger = 1 applies the record's inverse, formed from the ONE record as it is read (a run is bit-equal to
+ *         mlqem_clifford_run_f64 on a batch whose records were expanded and inverted on the host):
+ *           C1      with l0 != 0: j = the lowest of the three fields whose letter equals l0 (0 if none does); l0 becomes j + 1
+ *                   and sign ^= the sign bit of field j
+ *           C2      with p != 0: e = the lowest of the 16 nibbles of a | b << 32 that equals p, at most 14 (0 if none does); p
+ *                   becomes e + 1 and sign ^= bit e of c
+ *           DEPOL*  the flag is ignored
+ * Every index is clamped: k to the circuit's record range (a circuit without records skips its entries), schedule offsets to
+ * n_sched, the run number to F * B - 1, and what mlqem_clifford_run_f64 clamps; loads are unconditional, only the final stores
+ * are predicated; a malformed schedule or table computes garbage and faults nothing.
+ * Outputs, float64, row f for noise factor f: unit_ideal, unit_noisy [F][n_reg + n_lds]; ideal_terms, noisy_terms [F][n_terms];
+ * ideal_values, noisy_values [F][B], combined per factor exactly as in mlqem_clifford_run_f64.  Folding is the identity without
+ * noise, so the ideal rows are equal across factors for well-formed input.  At most three launches (the register walk over F *
+ * n_reg runs, the LDS walk over F * n_lds, the combine over F * B); no atomics, no workspace, no host read: capturable; a circuit's
+ * bits are the same alone, in any batch and from call to call.
+ * The checks of mlqem_clifford_run_f64, and: n_factors < 1, n_sched < 0, a null sched_ptr, a null sched with n_sched > 0:
+ * MLQEM_ERR_BAD_ARG; n_factors over 65535, n_sched, F * B or F * (n_reg + n_lds) over 2^31 - 1: MLQEM_ERR_UNSUPPORTED.
+ *
+ * mlqem_zne_combine_exp_f64.  Exponential extrapolation per Pauli term, with w [F] the weights of the straight-line fit (the
+ * degree-1 weights of mlqem_zne_combine_f64, from the host) and v_f = term_values[f][t]:
+ *   all v_f > 0 or all v_f < 0   mitigated term = sign * exp(S), S = w_0 ln|v_0|, then one fused multiply-add per further factor
+ *   all v_f == 0                 0
+ *   anything else                the linear sum of mlqem_zne_combine_f64 (the same operations), and fallback[t] = 1
+ * fallback int32 [n_terms] is 0 in the first two cases.  mitigated_values [B] = sum_t coeff[t] * mitigated term t, a fused
+ * multiply-add per term from 0.0 in term order, by one thread per circuit.  Under this noise model a Clifford Pauli's value at
+ * noise factor x is ideal * F1 * F2^x, which the first case recovers as ideal * F1.  It works on the term values of either
+ * folded simulator.  One launch, fixed order, no atomics, no workspace, no host read: capturable.  n_factors < 2, negative sizes
+ * or a null buffer that would be used: MLQEM_ERR_BAD_ARG; a size over 2^31 - 1: MLQEM_ERR_UNSUPPORTED; n_circuits == 0 and
+ * n_terms == 0: MLQEM_OK without a launch.
+ * ---------------------------------------------------------------------------------------------------- */
+int mlqem_clifford_run_folded_f64(int64_t n_circuits, int64_t n_factors, const int32_t* n_qubits, const int64_t* op_ptr,
+                                  const mlqem_clifford_op* ops, int64_t n_ops, const double* pool, int64_t n_pool,
+                                  const mlqem_clifford_unit* units, int64_t n_reg, int64_t n_lds, const uint32_t* masks,
+                                  int64_t n_masks, const int64_t* term_ptr, const double* coeff, int64_t n_terms,
+                                  const int64_t* comb_ptr, const int32_t* comb_unit, const double* comb_weight, int64_t n_comb,
+                                  const int64_t* sched_ptr, const int32_t* sched, int64_t n_sched, double* unit_ideal,
+                                  double* unit_noisy, double* ideal_terms, double* noisy_terms, double* ideal_values,
+                                  double* noisy_values, mlqem_stream_t stream);
+int mlqem_zne_combine_exp_f64(int64_t n_factors, int64_t n_circuits, const double* term_values, const double* weights,
+                              const int64_t* term_ptr, const double* coeff, int64_t n_terms, double* mitigated_terms,
+                              double* mitigated_values, int32_t* fallback, mlqem_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2877,18 +2877,8 @@ CLIFFORD_REG_QUBITS = 128   # MLQEM_CLIFFORD_REG_QUBITS: units of circuits up to
 CLIFFORD_PAD = 32           # entries of padding `pool` and `masks` end with
 
 
-def clifford_run(n_qubits, op_ptr, ops, pool, units, n_reg, n_lds, masks, term_ptr, coeff, comb_ptr, comb_unit, comb_weight, *,
-                 unit_ideal=None, unit_noisy=None, ideal_terms=None, noisy_terms=None, ideal_values=None, noisy_values=None):
-    """Carries every unit's Pauli backwards through its Clifford circuit (mlqem_clifford_run_f64): ``(ideal_values, noisy_values,
-    ideal_terms, noisy_terms, unit_ideal, unit_noisy)``, float64 [B], [B], [n_terms], [n_terms], [n_units], [n_units].
-
-    ``n_qubits`` int32 [B], ``op_ptr`` int64 [B + 1], ``ops`` int32 [n_ops, 4], ``pool`` float64 [>= 32], ``units`` int32 [n_units,
-    4], ``masks`` int32 [>= 32] (the uint32 words), ``term_ptr`` int64 [B + 1], ``coeff`` float64 [n_terms], ``comb_ptr`` int64
-    [n_terms + 1], ``comb_unit`` int32 [n_comb], ``comb_weight`` float64 [n_comb, 2]: the buffers of
-    ``blackwater.sim.CliffordBatch.to(device)``, in the layout of include/mlqem_hip.h.  ``n_reg`` / ``n_lds``: how many of ``units``
-    (the first / the rest) keep their words in registers / in LDS.  Shapes, dtypes and devices are checked here; the CONTENTS are
-    ``compile_clifford``'s to guarantee (the kernel clamps every index).  Nothing here waits for the device or reads a tensor, and with
-    the six outputs given nothing is allocated: the call can be captured in a hipGraph."""
+def _clifford_common(n_qubits, op_ptr, ops, pool, units, n_reg, n_lds, masks, term_ptr, coeff, comb_ptr, comb_unit, comb_weight):
+    """The checks the two Clifford calls share; returns ``(B, n_ops, n_units, n_terms, n_comb, n_reg, n_lds, device)``."""
     for t, name, cols in ((ops, "ops", 4), (units, "units", 4)):
         if not t.is_cuda:
             raise _lib.NativeLibraryError(f"{name} must live on the GPU (got {t.device}); there is no CPU path")
@@ -2915,6 +2905,23 @@ def clifford_run(n_qubits, op_ptr, ops, pool, units, n_reg, n_lds, masks, term_p
     dev = ops.device
     if any(t.device != dev for t in (n_qubits, op_ptr, pool, units, masks, term_ptr, coeff, comb_ptr, comb_unit, comb_weight)):
         raise ValueError(f"clifford: ops is on {dev}, another buffer is not")
+    return b, n_ops, n_units, n_terms, n_comb, n_reg, n_lds, dev
+
+
+def clifford_run(n_qubits, op_ptr, ops, pool, units, n_reg, n_lds, masks, term_ptr, coeff, comb_ptr, comb_unit, comb_weight, *,
+                 unit_ideal=None, unit_noisy=None, ideal_terms=None, noisy_terms=None, ideal_values=None, noisy_values=None):
+    """Carries every unit's Pauli backwards through its Clifford circuit (mlqem_clifford_run_f64): ``(ideal_values, noisy_values,
+    ideal_terms, noisy_terms, unit_ideal, unit_noisy)``, float64 [B], [B], [n_terms], [n_terms], [n_units], [n_units].
+
+    ``n_qubits`` int32 [B], ``op_ptr`` int64 [B + 1], ``ops`` int32 [n_ops, 4], ``pool`` float64 [>= 32], ``units`` int32 [n_units,
+    4], ``masks`` int32 [>= 32] (the uint32 words), ``term_ptr`` int64 [B + 1], ``coeff`` float64 [n_terms], ``comb_ptr`` int64
+    [n_terms + 1], ``comb_unit`` int32 [n_comb], ``comb_weight`` float64 [n_comb, 2]: the buffers of
+    ``blackwater.sim.CliffordBatch.to(device)``, in the layout of include/mlqem_hip.h.  ``n_reg`` / ``n_lds``: how many of ``units``
+    (the first / the rest) keep their words in registers / in LDS.  Shapes, dtypes and devices are checked here; the CONTENTS are
+    ``compile_clifford``'s to guarantee (the kernel clamps every index).  Nothing here waits for the device or reads a tensor, and with
+    the six outputs given nothing is allocated: the call can be captured in a hipGraph."""
+    b, n_ops, n_units, n_terms, n_comb, n_reg, n_lds, dev = _clifford_common(n_qubits, op_ptr, ops, pool, units, n_reg, n_lds, masks,
+                                                                             term_ptr, coeff, comb_ptr, comb_unit, comb_weight)
     unit_ideal, unit_noisy = _sim_out(unit_ideal, "unit_ideal", (n_units,), dev), _sim_out(unit_noisy, "unit_noisy", (n_units,), dev)
     ideal_terms, noisy_terms = _sim_out(ideal_terms, "ideal_terms", (n_terms,), dev), _sim_out(noisy_terms, "noisy_terms", (n_terms,), dev)
     ideal_values, noisy_values = _sim_out(ideal_values, "ideal_values", (b,), dev), _sim_out(noisy_values, "noisy_values", (b,), dev)
@@ -2926,3 +2933,77 @@ def clifford_run(n_qubits, op_ptr, ops, pool, units, n_reg, n_lds, masks, term_p
         _p(ideal_values), _p(noisy_values), _stream())
     _lib.check(code, "mlqem_clifford_run_f64")
     return ideal_values, noisy_values, ideal_terms, noisy_terms, unit_ideal, unit_noisy
+
+
+def clifford_run_folded(n_qubits, op_ptr, ops, pool, units, n_reg, n_lds, masks, term_ptr, coeff, comb_ptr, comb_unit, comb_weight,
+                        sched_ptr, sched, n_factors, *, unit_ideal=None, unit_noisy=None, ideal_terms=None, noisy_terms=None,
+                        ideal_values=None, noisy_values=None):
+    """Every (circuit, noise factor) run of a lowered Clifford batch along its schedule (mlqem_clifford_run_folded_f64):
+    ``(ideal_values, noisy_values, ideal_terms, noisy_terms, unit_ideal, unit_noisy)``, float64 [F, B], [F, B], [F, n_terms],
+    [F, n_terms], [F, n_units], [F, n_units].
+
+    The first thirteen arguments are those of :func:`clifford_run` for the B circuits, lowered once.  ``sched_ptr`` int64
+    [F * B + 1] and ``sched`` int32 [n_sched] hold one schedule per run ``r = f * B + c``: entries ``(k << 1) | dagger`` with ``k``
+    relative to the circuit's first record (``blackwater.sim.zne.build_clifford_schedules``); a daggered entry applies the inverse of
+    its record's table, formed on the device.  Shapes, dtypes and devices are checked here; the contents are the caller's (the
+    kernel clamps every index).  Nothing here waits for the device or reads a tensor, and with the six outputs given nothing is
+    allocated: the call can be captured in a hipGraph."""
+    b, n_ops, n_units, n_terms, n_comb, n_reg, n_lds, dev = _clifford_common(n_qubits, op_ptr, ops, pool, units, n_reg, n_lds, masks,
+                                                                             term_ptr, coeff, comb_ptr, comb_unit, comb_weight)
+    f = int(n_factors)
+    if f < 1:
+        raise ValueError(f"clifford: n_factors = {f}, want at least 1")
+    _vec(sched_ptr, "sched_ptr", f * b + 1, torch.int64)
+    _vec(sched, "sched", 0, torch.int32)
+    if sched_ptr.shape[0] != f * b + 1:
+        raise ValueError(f"clifford: want sched_ptr [{f * b + 1}], got {tuple(sched_ptr.shape)}")
+    if any(t.device != dev for t in (sched_ptr, sched)):
+        raise ValueError(f"clifford: ops is on {dev}, another buffer is not")
+    n_sched = int(sched.shape[0])
+    unit_ideal, unit_noisy = _sim_out(unit_ideal, "unit_ideal", (f, n_units), dev), _sim_out(unit_noisy, "unit_noisy", (f, n_units), dev)
+    ideal_terms = _sim_out(ideal_terms, "ideal_terms", (f, n_terms), dev)
+    noisy_terms = _sim_out(noisy_terms, "noisy_terms", (f, n_terms), dev)
+    ideal_values, noisy_values = _sim_out(ideal_values, "ideal_values", (f, b), dev), _sim_out(noisy_values, "noisy_values", (f, b), dev)
+    code = _lib.load().mlqem_clifford_run_folded_f64(
+        b, f, _p(n_qubits), _p(op_ptr), _p(ops) if n_ops else None, n_ops, _p(pool), int(pool.shape[0]),
+        _p(units) if n_units else None, n_reg, n_lds, _p(masks), int(masks.shape[0]), _p(term_ptr), _p(coeff) if n_terms else None,
+        n_terms, _p(comb_ptr), _p(comb_unit) if n_comb else None, _p(comb_weight) if n_comb else None, n_comb, _p(sched_ptr),
+        _p(sched) if n_sched else None, n_sched, _p(unit_ideal) if n_units else None, _p(unit_noisy) if n_units else None,
+        _p(ideal_terms) if n_terms else None, _p(noisy_terms) if n_terms else None, _p(ideal_values), _p(noisy_values), _stream())
+    _lib.check(code, "mlqem_clifford_run_folded_f64")
+    return ideal_values, noisy_values, ideal_terms, noisy_terms, unit_ideal, unit_noisy
+
+
+def zne_combine_exp(term_values, weights, term_ptr, coeff, *, mitigated_terms=None, mitigated_values=None, fallback=None):
+    """Exponential extrapolation to zero noise per Pauli term (mlqem_zne_combine_exp_f64): ``(mitigated_values, mitigated_terms,
+    fallback)``, float64 [B], float64 [n_terms] and int32 [n_terms].  ``term_values`` float64 [F >= 2, n_terms] from either folded
+    simulator (:func:`sim_run_folded`, :func:`clifford_run_folded`), ``weights`` float64 [F]: the straight-line weights
+    (``LinearExtrapolator().weights(noise_factors)``), ``term_ptr`` int64 [B + 1], ``coeff`` float64 [n_terms].  A term whose values
+    are all nonzero with one sign is ``sign * exp(sum_f w_f ln|v_f|)``; all zero: 0; anything else: the linear sum, and
+    ``fallback[t] = 1``.  Fixed order; nothing here waits for the device, and with the three outputs given nothing is allocated."""
+    if not term_values.is_cuda:
+        raise _lib.NativeLibraryError(f"term_values must live on the GPU (got {term_values.device}); there is no CPU path")
+    if term_values.dtype != torch.float64 or term_values.dim() != 2 or not term_values.is_contiguous() or term_values.shape[0] < 2:
+        raise ValueError(f"zne: want contiguous float64 term_values [F >= 2, n_terms], got {tuple(term_values.shape)} {term_values.dtype}")
+    f, n_terms = int(term_values.shape[0]), int(term_values.shape[1])
+    _vec(weights, "weights", f, torch.float64)
+    _vec(term_ptr, "term_ptr", 1, torch.int64)
+    _vec(coeff, "coeff", n_terms, torch.float64)
+    if weights.shape[0] != f or coeff.shape[0] != n_terms:
+        raise ValueError(f"zne: want weights [{f}] and coeff [{n_terms}], got {tuple(weights.shape)} and {tuple(coeff.shape)}")
+    b = int(term_ptr.shape[0]) - 1
+    dev = term_values.device
+    if any(t.device != dev for t in (weights, term_ptr, coeff)):
+        raise ValueError(f"zne: term_values is on {dev}, another buffer is not")
+    mitigated_terms = _sim_out(mitigated_terms, "mitigated_terms", (n_terms,), dev)
+    mitigated_values = _sim_out(mitigated_values, "mitigated_values", (b,), dev)
+    if fallback is None:
+        fallback = torch.zeros(n_terms, dtype=torch.int32, device=dev)
+    elif (not fallback.is_cuda or fallback.device != dev or fallback.dtype != torch.int32 or tuple(fallback.shape) != (n_terms,)
+          or not fallback.is_contiguous()):
+        raise ValueError(f"fallback: want contiguous int32 [{n_terms}] on {dev}, got {tuple(fallback.shape)} {fallback.dtype}")
+    code = _lib.load().mlqem_zne_combine_exp_f64(f, b, _p(term_values) if n_terms else None, _p(weights), _p(term_ptr),
+                                                 _p(coeff) if n_terms else None, n_terms, _p(mitigated_terms) if n_terms else None,
+                                                 _p(mitigated_values) if b else None, _p(fallback) if n_terms else None, _stream())
+    _lib.check(code, "mlqem_zne_combine_exp_f64")
+    return mitigated_values, mitigated_terms, fallback

@@ -2,17 +2,19 @@
 the labels the mitigators learn from.  ``compile_programs`` / ``NoiseModel`` / ``measured_z`` run on the host alone.  ``blackwater.sim.zne`` (also ``blackwater.zne``) is
 zero-noise extrapolation on it; the ``zne(cls)`` decorator lives there, so that ``sim.zne`` stays the module.
 ``blackwater.sim.clifford`` is the path for wide circuits: Clifford circuits of up to 512 qubits, ideal and noisy, by carrying the
-observable backwards through the circuit (``compile_clifford`` / ``clifford_expectation_values``)."""
+observable backwards through the circuit (``compile_clifford`` / ``clifford_expectation_values``); ``zne_run(..., method="clifford")``
+extrapolates there too (``build_clifford_schedules``, ``ExponentialExtrapolator``)."""
 from .program import (MAX_AMPS, MAX_QUBITS_DENSITY, MAX_QUBITS_VECTOR, SUPPORTED_GATES, WAVE_AMPS, NoiseModel, SimBatch,
                       compile_programs, measured_z)
 from .program import MAX_SHOTS, measurement_groups
-from .clifford import (MAX_QUBITS_CLIFFORD, CliffordBatch, clifford_expectation_values, compile_clifford, is_clifford,
-                       run_clifford)
+from .clifford import (MAX_QUBITS_CLIFFORD, CliffordBatch, clifford_expectation_values, compile_clifford, invert_table, is_clifford,
+                       run_clifford, run_clifford_folded)
 from .run import (DeviceEstimator, SampleResult, SimulatedJob, counts_dicts, default_run_keys, expectation_values, run_batch,
                   sample_batch, sample_expectation_values)
-from .zne import (CubicExtrapolator, CxAmplifier, GlobalFoldingAmplifier, LinearExtrapolator, LocalFoldingAmplifier,
+from .zne import (CubicExtrapolator, CxAmplifier, ExponentialExtrapolator, GlobalFoldingAmplifier, LinearExtrapolator, LocalFoldingAmplifier,
                   PolynomialExtrapolator, QuadraticExtrapolator, QuarticExtrapolator, RichardsonExtrapolator, Schedules,
-                  TwoQubitAmplifier, ZNEStrategy, build_schedules, fold_circuit, zne_expectation_values, zne_run)
+                  TwoQubitAmplifier, ZNEStrategy, build_clifford_schedules, build_schedules, fold_circuit, zne_expectation_values,
+                  zne_run)
 
 __all__ = ["MAX_AMPS", "MAX_QUBITS_DENSITY", "MAX_QUBITS_VECTOR", "SUPPORTED_GATES", "WAVE_AMPS", "NoiseModel", "SimBatch",
            "compile_programs", "measured_z", "DeviceEstimator", "SimulatedJob", "expectation_values", "run_batch",
@@ -21,4 +23,4 @@ __all__ = ["MAX_AMPS", "MAX_QUBITS_DENSITY", "MAX_QUBITS_VECTOR", "SUPPORTED_GAT
            "TwoQubitAmplifier", "ZNEStrategy", "build_schedules", "fold_circuit", "zne_expectation_values", "zne_run",
            "MAX_SHOTS", "measurement_groups", "SampleResult", "counts_dicts", "default_run_keys", "sample_batch",
            "sample_expectation_values", "MAX_QUBITS_CLIFFORD", "CliffordBatch", "clifford_expectation_values", "compile_clifford",
-           "is_clifford", "run_clifford"]
+           "is_clifford", "run_clifford", "ExponentialExtrapolator", "build_clifford_schedules", "invert_table", "run_clifford_folded"]

@@ -89,6 +89,34 @@ def pack_table(table: List[Tuple[int, int]]) -> Tuple[int, int, int]:
     return letters & 0xFFFFFFFF, letters >> 32, signs
 
 
+def invert_table(packed):
+    """The packed table of ``U P U^dagger`` from the packed table of ``U^dagger P U`` (what a daggered schedule entry applies): if
+    entry e maps p to (q, s), the inverse maps q to (p, s) -- the table is a signed permutation of the local Paulis.  ``"id"`` stays
+    ``"id"``.  A C1 table is told from a C2 table by its second word (a C2 table's letters fill it; a C1 table leaves it 0)."""
+    if isinstance(packed, str):
+        if packed != "id":
+            raise ValueError(f"invert_table: {packed!r} is no table")
+        return packed
+    a, b, c = (int(v) & 0xFFFFFFFF for v in packed)
+    if b == 0:   # C1: three 3-bit fields, letter | sign << 2
+        out: List[Optional[Tuple[int, int]]] = [None] * 3
+        for j in range(3):
+            field = a >> (3 * j) & 7
+            code, s = field & 3, field >> 2
+            if code == 0 or out[code - 1] is not None:
+                raise ValueError(f"invert_table: {tuple(packed)!r} is no permutation of the letters X, Z, Y")
+            out[code - 1] = (j + 1, s)
+        return pack_table(out)
+    letters = a | b << 32
+    out = [None] * 15
+    for e in range(15):
+        code, s = letters >> (4 * e) & 15, c >> e & 1
+        if code == 0 or out[code - 1] is not None:
+            raise ValueError(f"invert_table: {tuple(packed)!r} is no permutation of the 15 two-qubit Paulis")
+        out[code - 1] = (e + 1, s)
+    return pack_table(out)
+
+
 _TABLES: Dict[Tuple[str, Tuple[float, ...]], Optional[Tuple[int, int, int]]] = {}
 
 
@@ -139,6 +167,13 @@ class CliffordBatch:
     comb_ptr: np.ndarray      # int64 [n_terms + 1]
     comb_unit: np.ndarray     # int32 [n_comb]
     comb_weight: np.ndarray   # float64 [n_comb, 2]: (weight of the unit's ideal value, of its noisy value)
+    # the record map of the source gates, with the meaning it has in ``SimBatch``: what blackwater.sim.zne folds.  Record indices
+    # are relative to op_ptr[c]; -1 = absent (``id`` has no gate record, a gate without noise no depolarising record)
+    gate_ptr: Optional[np.ndarray] = None      # int64 [B + 1]: circuit c owns gates gate_ptr[c] .. gate_ptr[c + 1]
+    gate_record: Optional[np.ndarray] = None   # int32 [n_gates]: the gate's own record
+    gate_noise: Optional[np.ndarray] = None    # int32 [n_gates]: the depolarising record after it
+    gate_name: Optional[np.ndarray] = None     # int16 [n_gates]: index of the gate's name in SUPPORTED_GATES
+    gate_op: Optional[np.ndarray] = None       # int32 [n_gates]: index of the gate in the circuit's op list
 
     def __len__(self) -> int:
         return int(self.n_qubits.shape[0])
@@ -183,6 +218,8 @@ def compile_clifford(circuits: Sequence[Any], observables: Sequence[Any], noise:
     nq_all, op_ptr, flat_ops, pool = [], [0], [], []
     unit_circ, unit_ny, unit_mask, masks = [], [], [], []
     coeffs, term_ptr, comb_ptr, comb_unit, comb_weight = [], [0], [0], [], []
+    gate_ptr, gate_record, gate_noise, gate_name, gate_op = [0], [], [], [], []
+    name_id = {g: j for j, g in enumerate(SUPPORTED_GATES)}
 
     for k, (obj, obs) in enumerate(zip(circuits, observables)):
         circ = Circuit.from_any(obj)
@@ -227,7 +264,9 @@ def compile_clifford(circuits: Sequence[Any], observables: Sequence[Any], noise:
                 raise ValueError(f"{where}: op {i}: {shown} is not a Clifford gate (every U^dagger P U must be +-one Pauli to "
                                  f"{TABLE_TOL:g}); the Clifford path takes no other gate")
             qs = q0 << 4 | q1 << 14
+            rec = noi = -1
             if table != "id":
+                rec = n_rec
                 flat_ops += (CL_C2 | qs if width == 2 else CL_C1 | qs, table[0], table[1], table[2])
                 n_rec += 1
             if noise is not None:
@@ -235,9 +274,14 @@ def compile_clifford(circuits: Sequence[Any], observables: Sequence[Any], noise:
                 if lam is not None:
                     if not (math.isfinite(lam) and 0.0 <= lam <= 1.0):
                         raise ValueError(f"{where}: op {i} ({name}): depolarising parameter {lam!r}, want 0 <= lambda <= 1")
+                    noi = n_rec
                     flat_ops += (CL_DEPOL2 | qs if width == 2 else CL_DEPOL1 | qs, len(pool), 0, 0)
                     pool.append(1.0 - float(lam))
                     n_rec += 1
+            gate_record.append(rec)
+            gate_noise.append(noi)
+            gate_name.append(name_id[name])
+            gate_op.append(i)
         readout: Dict[int, Tuple[float, float]] = {}
         if noise is not None:
             for q in sorted(set(measured.values())):
@@ -297,6 +341,7 @@ def compile_clifford(circuits: Sequence[Any], observables: Sequence[Any], noise:
         nq_all.append(n)
         op_ptr.append(op_ptr[-1] + n_rec)
         term_ptr.append(len(coeffs))
+        gate_ptr.append(len(gate_record))
 
     if max(len(masks), len(pool), len(unit_circ)) + PAD > 2 ** 31 - 1:
         raise ValueError("compile_clifford: the batch exceeds the 2^31 - 1 entries one call can address; split it")
@@ -320,7 +365,10 @@ def compile_clifford(circuits: Sequence[Any], observables: Sequence[Any], noise:
         term_ptr=np.asarray(term_ptr, dtype=np.int64), coeff=np.asarray(coeffs, dtype=np.float64),
         comb_ptr=np.asarray(comb_ptr, dtype=np.int64),
         comb_unit=(place[np.asarray(comb_unit, dtype=np.int64)] if comb_unit else np.zeros(0, dtype=np.int64)).astype(np.int32),
-        comb_weight=np.asarray(comb_weight, dtype=np.float64).reshape(-1, 2))
+        comb_weight=np.asarray(comb_weight, dtype=np.float64).reshape(-1, 2),
+        gate_ptr=np.asarray(gate_ptr, dtype=np.int64), gate_record=np.asarray(gate_record, dtype=np.int32),
+        gate_noise=np.asarray(gate_noise, dtype=np.int32), gate_name=np.asarray(gate_name, dtype=np.int16),
+        gate_op=np.asarray(gate_op, dtype=np.int32))
 
 
 def run_clifford(batch: CliffordBatch, device="cuda"):
@@ -331,6 +379,17 @@ def run_clifford(batch: CliffordBatch, device="cuda"):
     t = batch.to(device)
     return ops.clifford_run(t["n_qubits"], t["op_ptr"], t["ops"], t["pool"], t["units"], t["n_reg"], t["n_lds"], t["masks"],
                             t["term_ptr"], t["coeff"], t["comb_ptr"], t["comb_unit"], t["comb_weight"])
+
+
+def run_clifford_folded(batch: CliffordBatch, schedules, device="cuda"):
+    """:func:`run_clifford` along the schedules of ``blackwater.sim.zne.build_clifford_schedules``: the same six tensors with a
+    leading noise-factor axis, from one call (``ops.clifford_run_folded``)."""
+    from ..native import ops
+
+    t, s = batch.to(device), schedules.to(device)
+    return ops.clifford_run_folded(t["n_qubits"], t["op_ptr"], t["ops"], t["pool"], t["units"], t["n_reg"], t["n_lds"], t["masks"],
+                                   t["term_ptr"], t["coeff"], t["comb_ptr"], t["comb_unit"], t["comb_weight"], s["sched_ptr"],
+                                   s["sched"], len(schedules.noise_factors))
 
 
 def clifford_expectation_values(circuits: Sequence[Any], observables: Sequence[Any], noise: Any = None, device="cuda",

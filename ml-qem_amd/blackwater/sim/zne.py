@@ -23,7 +23,19 @@ folded gate runs as G N G^-1 N G N, the inverse carrying the gate's OWN depolari
 ``sx`` a by-name rule would find no calibration entry for ``sxdg`` and amplify nothing).  Readout ops run once, after everything.
 
 Polynomial extrapolation of exact values is linear in them, so an extrapolator is a weight vector: ``weights(noise_factors)`` is
-``e_0^T V^+`` for the Vandermonde matrix V of the factors, in float64 on the host.  Exponential extrapolation is out of scope.
+``e_0^T V^+`` for the Vandermonde matrix V of the factors, in float64 on the host.
+
+Exponential extrapolation (:class:`ExponentialExtrapolator`) fits a straight line through (factor, ln|value|) per Pauli term and
+exponentiates its value at zero noise: ``sign * exp(sum_f w_f ln|v_f|)`` with the degree-1 weights w.  It is exact for a value of
+the form ``A * r^factor``, which is what a Clifford circuit's Pauli term is under this noise model (see below); a term whose values
+are all 0 stays 0, and a term with a zero among nonzeros or with mixed signs falls back to the straight line and is counted.
+
+At width.  ``method="clifford"`` (or ``"auto"``, by :class:`DeviceEstimator`'s rule) takes the same route on the Clifford path:
+:func:`compile_clifford` once, :func:`build_clifford_schedules`, ``ops.clifford_run_folded``, then one combine.  A Pauli carried
+backwards through a folded gate G N G^-1 N G N has the same support at the three N as at the one N of the unfolded gate (G^-1 undoes
+what G did to it), so a folded gate's keep factor is multiplied in 1 + 2 folds times: the noisy value at an achieved factor x of a
+circuit whose gates are all folded alike is ``ideal * F1 * F2^x``, F2 the product of the foldable gates' keeps that the unfolded walk
+met and F1 that of the others.
 
 Shots.  With ``shots=`` every (circuit, factor) run is measured (``ops.sim_run_folded_measured`` + ``ops.sim_sample``): per factor
 the sampled values and their variances; the mitigated value is sum_f w_f value_f through the same combine, and the mitigated
@@ -41,6 +53,7 @@ import numpy as np
 
 from ..data.circuit import Circuit, CircuitOp
 from ..library.primitives import make_estimator_result
+from .clifford import CliffordBatch, compile_clifford
 from .program import _TWO_QUBIT, SUPPORTED_GATES, NoiseModel, SimBatch, check_seed, check_shots, compile_programs
 
 _NOT_GATES = ("barrier", "measure")
@@ -264,6 +277,19 @@ def _name_table(amplifier: _Amplifier) -> np.ndarray:
     return np.asarray([amplifier.matches(g, 2 if g in _TWO_QUBIT else 1) for g in SUPPORTED_GATES], dtype=bool)
 
 
+def _fold_entries(amplifier: _Amplifier, gate_ptr: np.ndarray, mask: np.ndarray, rec: np.ndarray, noi: np.ndarray, owner: np.ndarray,
+                  n_circ: int, noise_factor: float):
+    """The fold units of one noise factor as schedule entries, shared by both record formats: ``(entries, body_len, achieved)``
+    with the entries of all circuits in running order (a unit's gate record with its dagger flag, then its depolarising record;
+    absent records left out) and their number per circuit."""
+    unit_gate, unit_dagger, _, ach = _plan(amplifier, gate_ptr, mask, noise_factor)
+    r, n = rec[unit_gate], noi[unit_gate]
+    entries = np.stack([np.where(r >= 0, (r << 1) | unit_dagger, -1), np.where(n >= 0, n << 1, -1)], axis=1)
+    valid = entries >= 0
+    body_len = np.bincount(owner[unit_gate], weights=valid.sum(axis=1), minlength=n_circ).astype(np.int64)
+    return entries[valid], body_len, ach
+
+
 def build_schedules(batch: SimBatch, circuits: Optional[Sequence[Any]], noise_factors: Sequence[float], amplifier: _Amplifier) -> Schedules:
     """One schedule per (noise factor, circuit) from the record map ``compile_programs`` keeps (``batch.gate_*``).  A fold unit is
     the gate's record followed by its depolarising record (either may be absent); the circuit's readout records follow every
@@ -287,15 +313,11 @@ def build_schedules(batch: SimBatch, circuits: Optional[Sequence[Any]], noise_fa
     rec, noi = batch.gate_record.astype(np.int64), batch.gate_noise.astype(np.int64)
     pieces, lengths, achieved = [], [], []
     for lam in factors:
-        unit_gate, unit_dagger, _, ach = _plan(amplifier, batch.gate_ptr, mask, lam)
-        r, n = rec[unit_gate], noi[unit_gate]
-        entries = np.stack([np.where(r >= 0, (r << 1) | unit_dagger, -1), np.where(n >= 0, n << 1, -1)], axis=1)
-        valid = entries >= 0
-        body_len = np.bincount(owner[unit_gate], weights=valid.sum(axis=1), minlength=n_circ).astype(np.int64)
+        body, body_len, ach = _fold_entries(amplifier, batch.gate_ptr, mask, rec, noi, owner, n_circ, lam)
         run_len = body_len + n_readout
         start = np.cumsum(run_len) - run_len
         piece = np.empty(int(run_len.sum()), dtype=np.int32)
-        piece[np.repeat(start, body_len) + _within(body_len)] = entries[valid]
+        piece[np.repeat(start, body_len) + _within(body_len)] = body
         piece[np.repeat(start + body_len, n_readout) + _within(n_readout)] = readout
         pieces.append(piece)
         lengths.append(run_len)
@@ -311,6 +333,34 @@ def build_schedules(batch: SimBatch, circuits: Optional[Sequence[Any]], noise_fa
     return Schedules(sched_ptr=sched_ptr, sched=np.concatenate(pieces) if pieces else np.zeros(0, dtype=np.int32),
                      ids=np.concatenate([wave, wg]).astype(np.int32), n_wave=int(wave.size), n_wg=int(wg.size), noise_factors=factors,
                      achieved=np.asarray(achieved, dtype=np.float64).reshape(len(factors), n_circ))
+
+
+def build_clifford_schedules(batch: CliffordBatch, noise_factors: Sequence[float], amplifier: _Amplifier) -> Schedules:
+    """:func:`build_schedules` for the Clifford format (``mlqem_clifford_run_folded_f64``): one schedule per (noise factor, circuit)
+    from the record map ``compile_clifford`` keeps.  A fold unit is the gate's record followed by its depolarising record (either
+    may be absent; the inverse carries the gate's own depolarising record); there are no trailing entries, readout being no record
+    in this format, and no run numbers (``ids`` is empty: every unit of the batch walks every factor).  numpy throughout."""
+    if batch.gate_ptr is None:
+        raise ValueError("build_clifford_schedules: the batch carries no record map (it was not made by compile_clifford)")
+    n_circ = len(batch)
+    factors = tuple(float(f) for f in noise_factors)
+    if not factors:
+        raise ValueError("build_clifford_schedules: no noise factor")
+    mask = _name_table(amplifier)[batch.gate_name.astype(np.int64)] if batch.gate_name.size else np.zeros(0, dtype=bool)
+    owner = np.repeat(np.arange(n_circ, dtype=np.int64), np.diff(batch.gate_ptr))
+    rec, noi = batch.gate_record.astype(np.int64), batch.gate_noise.astype(np.int64)
+    pieces, lengths, achieved = [], [], []
+    for lam in factors:
+        body, body_len, ach = _fold_entries(amplifier, batch.gate_ptr, mask, rec, noi, owner, n_circ, lam)
+        pieces.append(body.astype(np.int32))
+        lengths.append(body_len)
+        achieved.append(ach)
+    sched_ptr = np.concatenate([[0], np.cumsum(np.concatenate(lengths))]).astype(np.int64)
+    if int(sched_ptr[-1]) > 2 ** 31 - 1 or len(factors) * max(n_circ, len(batch.units)) > 2 ** 31 - 1:
+        raise ValueError(f"build_clifford_schedules: {int(sched_ptr[-1])} schedule entries over {len(factors) * n_circ} runs exceed "
+                         "the 2^31 - 1 one call can take; split the batch")
+    return Schedules(sched_ptr=sched_ptr, sched=np.concatenate(pieces), ids=np.zeros(0, dtype=np.int32), n_wave=0, n_wg=0,
+                     noise_factors=factors, achieved=np.asarray(achieved, dtype=np.float64).reshape(len(factors), n_circ))
 
 
 # ---- extrapolators ---------------------------------------------------------------------------------------------------------------
@@ -390,6 +440,56 @@ class RichardsonExtrapolator(PolynomialExtrapolator):
         return n_factors - 1
 
 
+class ExponentialExtrapolator:
+    """A straight line through (noise factor, ln|value|) per Pauli term, exponentiated at zero noise.  With w the degree-1
+    least-squares weights: all v_f nonzero with one sign -> ``sign * exp(sum_f w_f ln|v_f|)``; all v_f = 0 -> 0; anything else (a zero
+    among nonzeros, mixed signs: the model does not hold) -> the linear ``sum_f w_f v_f``, counted as a fallback.  Needs at least two
+    distinct factors.  The fused paths extrapolate per TERM on the device (``ops.zne_combine_exp``) and add ``coeff * term`` in term
+    order; the generic ``zne(cls)`` path has only the values and extrapolates those (:meth:`extrapolate`)."""
+
+    exponential = True
+
+    def weights(self, noise_factors: Sequence[float]) -> np.ndarray:
+        """The straight-line weights ``PolynomialExtrapolator(1).weights(noise_factors)`` (they refuse fewer than two factors, a
+        repeated factor and a factor below 1)."""
+        return PolynomialExtrapolator(1).weights(noise_factors)
+
+    def fit(self, noise_factors: Sequence[float], values) -> Tuple[np.ndarray, np.ndarray]:
+        """``(mitigated, fallback)`` along the first axis of ``values`` [F, ...]: float64 and bool arrays of the remaining shape.
+        Sums are formed in factor order."""
+        w, y = self.weights(noise_factors), np.asarray(values, dtype=np.float64)
+        if y.shape[0] != w.shape[0]:
+            raise ValueError(f"extrapolate: {y.shape[0]} rows of values for {w.shape[0]} noise factors")
+        pos, neg, zero = (y > 0).all(axis=0), (y < 0).all(axis=0), (y == 0).all(axis=0)
+        model = pos | neg
+        with np.errstate(divide="ignore", invalid="ignore"):
+            logs = np.log(np.abs(np.where(model, y, 1.0)))
+        s, lin = w[0] * logs[0], w[0] * y[0]
+        for f in range(1, w.shape[0]):
+            s, lin = s + w[f] * logs[f], lin + w[f] * y[f]
+        out = np.where(model, np.where(neg, -1.0, 1.0) * np.exp(s), np.where(zero, 0.0, lin))
+        return out, ~(model | zero)
+
+    def extrapolate(self, noise_factors: Sequence[float], values) -> np.ndarray:
+        return self.fit(noise_factors, values)[0]
+
+    def extrapolate_terms(self, noise_factors: Sequence[float], term_values, term_ptr, coeff):
+        """The host form of ``ops.zne_combine_exp``: ``(mitigated_values [B], mitigated_terms [n_terms], fallback [n_terms])`` from
+        ``term_values`` [F, n_terms]; the value of a circuit is ``sum coeff * term`` in term order."""
+        terms, fallback = self.fit(noise_factors, term_values)
+        term_ptr, coeff = np.asarray(term_ptr, dtype=np.int64), np.asarray(coeff, dtype=np.float64)
+        values = np.zeros(len(term_ptr) - 1, dtype=np.float64)
+        for c in range(len(values)):
+            total = np.float64(0.0)
+            for t in range(int(term_ptr[c]), int(term_ptr[c + 1])):
+                total = total + coeff[t] * terms[t]
+            values[c] = total
+        return values, terms, fallback.astype(np.int32)
+
+    def __repr__(self):
+        return "ExponentialExtrapolator()"
+
+
 @dataclass
 class ZNEStrategy:
     """What the reference's tutorial uses by default: factors (1, 3), two-qubit local folding, a straight line."""
@@ -416,8 +516,8 @@ class ZNERun:
     term_ptr: Any             # int64 [B + 1]
     values: Any               # float64 [F, B]: per noise factor
     term_values: Any          # float64 [F, n_terms]
-    norm: Any                 # float64 [F, B]
-    batch: SimBatch
+    norm: Any                 # float64 [F, B]; None on the Clifford path (a Pauli walk has no state to normalise)
+    batch: Any                # the SimBatch, or the CliffordBatch on the Clifford path
     schedules: Schedules
     weights: np.ndarray
     # with shots: ``values`` / ``term_values`` and the mitigated ones above are the SAMPLED ones, and
@@ -427,20 +527,64 @@ class ZNERun:
     counts: Any = None                # int32 [F, n_outcomes]
     probs: Any = None                 # float64 [F, n_outcomes]
     exact_values: Any = None          # float64 [F, B]: the exact per-factor values of the same launch
+    # on the Clifford path the walk gives the ideal values too (equal across factors: folding is the identity without noise)
+    ideal_values: Any = None          # float64 [B]
+    ideal_terms: Any = None           # float64 [n_terms]
+    # with ExponentialExtrapolator: int32 [n_terms], 1 where a term fell back to the straight line
+    fallback_terms: Any = None
 
 
-def zne_run(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None,
-            strategy: Optional[ZNEStrategy] = None, device="cuda", shots: Optional[int] = None, seed: int = 0, run_keys=None) -> ZNERun:
-    """Lowers once, builds the schedules, simulates every (circuit, factor) run in one call and extrapolates in one more.  With
-    ``shots`` every run is also measured and the extrapolation is of the sampled values (see the module docstring); ``run_keys``:
-    one integer per run f * B + c (by default the run number)."""
+_CLIFFORD_SHOTS = ("DeviceEstimator: shots are not drawn on the Clifford path (method='clifford', or 'auto' on circuits over the exact "
+                   "simulator's cap); run it without shots")
+
+
+def _combine(strategy: "ZNEStrategy", weights: np.ndarray, term_values, term_ptr, coeff):
+    """``(mitigated_values, mitigated_terms, fallback or None)`` by the strategy's extrapolator, in one launch."""
     import torch
 
     from ..native import ops
 
+    w = torch.from_numpy(weights).to(term_values.device)
+    if getattr(strategy.extrapolator, "exponential", False):
+        return ops.zne_combine_exp(term_values, w, term_ptr, coeff)
+    return ops.zne_combine(term_values, w, term_ptr, coeff) + (None,)
+
+
+def zne_run(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None,
+            strategy: Optional[ZNEStrategy] = None, device="cuda", shots: Optional[int] = None, seed: int = 0, run_keys=None,
+            method: str = "exact") -> ZNERun:
+    """Lowers once, builds the schedules, simulates every (circuit, factor) run in one call and extrapolates in one more.  With
+    ``shots`` every run is also measured and the extrapolation is of the sampled values (see the module docstring); ``run_keys``:
+    one integer per run f * B + c (by default the run number).  ``method``: ``"exact"`` (the default), ``"clifford"`` or ``"auto"``,
+    with :class:`DeviceEstimator`'s meaning and ``auto`` rule; on the Clifford path ``batch`` is the ``CliffordBatch``, ``norm`` is
+    None, ``ideal_values`` / ``ideal_terms`` come from the same call, and ``shots`` is refused."""
+    import torch
+
+    from ..native import ops
+    from .run import DeviceEstimator
+
     strategy = strategy or ZNEStrategy()
     weights = strategy.weights()
     circuits = list(circuits)
+    exponential = getattr(strategy.extrapolator, "exponential", False)
+    if shots is not None and exponential:
+        raise ValueError("ExponentialExtrapolator: shots= is not supported with it (the variance of a sampled value is not "
+                         "propagated through the exponential fit); use a polynomial extrapolator or run without shots")
+    if method not in DeviceEstimator.METHODS:
+        raise ValueError(f"zne_run: method = {method!r}, want one of {', '.join(DeviceEstimator.METHODS)}")
+    if method != "exact" and DeviceEstimator(noise, device, method=method)._use_clifford(circuits):
+        if shots is not None:
+            raise ValueError(_CLIFFORD_SHOTS)
+        batch = compile_clifford(circuits, observables, noise)
+        sch = build_clifford_schedules(batch, strategy.noise_factors, strategy.noise_amplifier)
+        t, s = batch.to(device), sch.to(device)
+        ideal_values, noisy_values, ideal_terms, noisy_terms, _, _ = ops.clifford_run_folded(
+            t["n_qubits"], t["op_ptr"], t["ops"], t["pool"], t["units"], t["n_reg"], t["n_lds"], t["masks"], t["term_ptr"], t["coeff"],
+            t["comb_ptr"], t["comb_unit"], t["comb_weight"], s["sched_ptr"], s["sched"], len(sch.noise_factors))
+        values, term_values = (ideal_values, ideal_terms) if noise is None else (noisy_values, noisy_terms)
+        mitigated_values, mitigated_terms, fallback = _combine(strategy, weights, term_values, t["term_ptr"], t["coeff"])
+        return ZNERun(mitigated_values, mitigated_terms, t["term_ptr"], values, term_values, None, batch, sch, weights,
+                      ideal_values=ideal_values[0], ideal_terms=ideal_terms[0], fallback_terms=fallback)
     if shots is not None:
         from .run import _run_keys
 
@@ -469,18 +613,20 @@ def zne_run(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional
     t, s = batch.to(device), sch.to(device)
     values, term_values, norm = ops.sim_run_folded(t["circ"], t["op_ptr"], t["ops"], t["params"], t["term_ptr"], t["terms"], t["coeff"],
                                                    s["sched_ptr"], s["sched"], s["ids"], sch.n_wave, sch.n_wg, len(sch.noise_factors))
-    w = torch.from_numpy(weights).to(values.device)
-    mitigated_values, mitigated_terms = ops.zne_combine(term_values, w, t["term_ptr"], t["coeff"])
-    return ZNERun(mitigated_values, mitigated_terms, t["term_ptr"], values, term_values, norm, batch, sch, weights)
+    mitigated_values, mitigated_terms, fallback = _combine(strategy, weights, term_values, t["term_ptr"], t["coeff"])
+    return ZNERun(mitigated_values, mitigated_terms, t["term_ptr"], values, term_values, norm, batch, sch, weights,
+                  fallback_terms=fallback)
 
 
 def zne_expectation_values(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None,
-                           strategy: Optional[ZNEStrategy] = None, device="cuda", shots: Optional[int] = None, seed: int = 0):
+                           strategy: Optional[ZNEStrategy] = None, device="cuda", shots: Optional[int] = None, seed: int = 0,
+                           method: str = "exact"):
     """``(mitigated_values [B], mitigated_terms [n_terms], term_ptr [B + 1], per_factor_values [F, B])``, tensors on ``device``.
     ``noise=None`` is allowed (state vectors up to 11 qubits): pointless as mitigation, every factor then gives the same value up
     to rounding.  With ``shots`` the same four tensors hold the SAMPLED values; :func:`zne_run` returns the variances, counts and
-    probabilities beside them (``ZNERun.mitigated_variance``, ``.variance``, ``.counts``, ``.probs``)."""
-    run = zne_run(circuits, observables, noise, strategy, device, shots=shots, seed=seed)
+    probabilities beside them (``ZNERun.mitigated_variance``, ``.variance``, ``.counts``, ``.probs``).  ``method`` as in
+    :func:`zne_run`: ``"clifford"`` / ``"auto"`` extrapolate Clifford circuits of up to 512 qubits."""
+    run = zne_run(circuits, observables, noise, strategy, device, shots=shots, seed=seed, method=method)
     return run.mitigated_values, run.mitigated_terms, run.term_ptr, run.values
 
 
@@ -496,10 +642,11 @@ class ZNEJob:
     the wrapped estimator's job when ``result()`` is asked for."""
 
     def __init__(self, strategy: ZNEStrategy, achieved: np.ndarray, n_circuits: int, job_id: str, values=None, per_factor=None,
-                 base_job=None, shots=None, variance=None, per_factor_variance=None):
+                 base_job=None, shots=None, variance=None, per_factor_variance=None, fallback=None):
         self._strategy, self._achieved, self._n, self._job_id = strategy, achieved, n_circuits, job_id
         self._values, self._per_factor, self._base_job = values, per_factor, base_job
         self._shots, self._variance, self._per_factor_variance = shots, variance, per_factor_variance
+        self._fallback = fallback   # with ExponentialExtrapolator on a fused path: per circuit, the terms that fell back
 
     def result(self):
         meta = [{} for _ in range(self._n)]
@@ -510,6 +657,8 @@ class ZNEJob:
             meta = [dict(m) for m in list(base.metadata)[:self._n]] if len(base.metadata) >= self._n else meta
         for k in range(self._n):
             meta[k]["zne"] = _zne_metadata(self._strategy, self._achieved, self._per_factor, k)
+            if self._fallback is not None:
+                meta[k]["zne"]["fallback_terms"] = int(self._fallback[k])
             if self._shots is not None:   # the fused path with shots: the error bar of the mitigated value
                 var = float(self._variance[k])
                 meta[k].update(variance=var, shots=int(self._shots), std_error=math.sqrt(max(var, 0.0) / self._shots))
@@ -537,7 +686,10 @@ def zne(cls):
     (sum_f w_f^2 variance_f), ``shots`` and ``std_error = sqrt(variance / shots)``, and ``metadata[k]["zne"]["variances"]`` the
     per-factor variances.
 
-    Around :class:`DeviceEstimator` it takes the fused path (:func:`zne_run`: one lowering, schedules, two calls).  Around any other
+    Around :class:`DeviceEstimator` it takes the fused path (:func:`zne_run`: one lowering, schedules, two calls) and follows the
+    estimator's ``method``: ``"clifford"`` (or ``"auto"`` on a job over the exact simulator's cap) extrapolates Clifford circuits of
+    up to 512 qubits, without shots.  With :class:`ExponentialExtrapolator` on a fused path ``metadata[k]["zne"]["fallback_terms"]``
+    counts the circuit's terms that fell back to the straight line.  Around any other
     estimator class it folds the IR (:func:`fold_circuit`), submits the F * B circuits through the wrapped ``_run`` in one job and
     combines with the same weights on the host; circuits must arrive bound there."""
     from .run import DeviceEstimator
@@ -558,15 +710,22 @@ def zne(cls):
                 if len(p):
                     raise ValueError(f"{type(self).__name__}: circuit {k} comes with {len(p)} parameter values; circuits must arrive bound")
             shots, seed = run_options.pop("shots", self._shots), run_options.pop("seed", self._seed)
+            if shots is not None and self._method != "exact" and self._use_clifford(circuits):
+                raise ValueError(_CLIFFORD_SHOTS)
             if shots is not None:   # job j's run r draws with the key j * 2^32 + r: successive runs do not repeat their draws
                 keys = np.arange(len(strategy.noise_factors) * len(circuits), dtype=np.int64) + (np.int64(self._zne_count) << 32)
-                run = zne_run(circuits, observables, self._noise, strategy, self._device, shots=shots, seed=seed, run_keys=keys)
+                run = zne_run(circuits, observables, self._noise, strategy, self._device, shots=shots, seed=seed, run_keys=keys,
+                              method=self._method)
                 return ZNEJob(strategy, run.schedules.achieved, len(circuits), f"zne-sim-{self._zne_count}",
                               values=run.mitigated_values.cpu().numpy(), per_factor=run.values.cpu().numpy(), shots=run.shots,
                               variance=run.mitigated_variance.cpu().numpy(), per_factor_variance=run.variance.cpu().numpy())
-            run = zne_run(circuits, observables, self._noise, strategy, self._device)
+            run = zne_run(circuits, observables, self._noise, strategy, self._device, method=self._method)
+            fallback = None
+            if run.fallback_terms is not None:
+                ptr, flags = run.term_ptr.cpu().numpy(), run.fallback_terms.cpu().numpy()
+                fallback = [int(flags[ptr[k]:ptr[k + 1]].sum()) for k in range(len(circuits))]
             return ZNEJob(strategy, run.schedules.achieved, len(circuits), f"zne-sim-{self._zne_count}",
-                          values=run.mitigated_values.cpu().numpy(), per_factor=run.values.cpu().numpy())
+                          values=run.mitigated_values.cpu().numpy(), per_factor=run.values.cpu().numpy(), fallback=fallback)
         parsed = [Circuit.from_any(c) for c in circuits]
         folded, achieved = [], []
         for lam in strategy.noise_factors:

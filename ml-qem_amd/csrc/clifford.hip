@@ -13,7 +13,11 @@
 //                 only ever touches its own column, so there is no barrier), 32 KB per workgroup.
 // Loads are unconditional on clamped indices and only the two final stores are predicated; a malformed record computes garbage and
 // reads nothing out of range.
-// combine_kernel: a wave per circuit.  Lanes stride over the circuit's terms, each adding weight * unit in `comb` order; after a
+// FOLD = true (mlqem_clifford_run_folded_f64, zero-noise extrapolation): a thread per (noise factor, unit) walks the SCHEDULE of
+// its (factor, circuit) run, entries (k << 1) | dagger naming the circuit's records; a daggered C1 / C2 record applies the inverse
+// table, found in the record as it is read (the table is a signed permutation: the entry that holds the current letters).  Three
+// dependent loads per entry (entry -> record -> pool value), the four of a chunk in flight together at each level.
+// combine_kernel: a wave per (circuit, noise factor).  Lanes stride over the circuit's terms, each adding weight * unit in `comb` order; after a
 // barrier lane 0 adds coeff * term in term order.  Products and sums are separately rounded (no contraction), so the host can repeat
 // them bit for bit.  No atomics, no workspace, nothing read back.
 #include "common.hpp"
@@ -68,18 +72,80 @@ template <> struct ClfWords<false> {
   }
 };
 
-template <bool REG>
+// The record a daggered schedule entry applies is the INVERSE table, formed as the record is read: the table is a signed
+// permutation of the local Paulis, so the image of p under the inverse is the entry whose letter field holds p, and its sign bit
+// is that entry's.  A table that holds p nowhere (malformed) gives entry 0; an index is never above the table's last entry.
+__device__ __forceinline__ uint32_t clf_find_c1(uint32_t tab, uint32_t a) {   // a = 1 .. 3
+  return (tab & 3u) == a ? 0u : ((tab >> 3) & 3u) == a ? 1u : ((tab >> 6) & 3u) == a ? 2u : 0u;
+}
+
+__device__ __forceinline__ uint32_t clf_find_c2(uint64_t tab, uint32_t pq) {   // pq = 1 .. 15
+  // the lowest zero nibble of tab ^ pq pq .. pq: below it no nibble is zero, so no borrow reaches it and the lowest flag is exact
+  const uint64_t x = tab ^ (0x1111111111111111ull * (uint64_t)pq);
+  const uint64_t zero = (x - 0x1111111111111111ull) & ~x & 0x8888888888888888ull;
+  const int at = __ffsll((unsigned long long)zero);   // 0 when there is none, else 4 e + 4
+  return at ? min((uint32_t)(at - 1) >> 2, 14u) : 0u;
+}
+
+// One record applied to the lane's Pauli (`dagger`: its inverse; only the FOLD instantiations look at the flag).  A function on
+// the words themselves, not a lambda around them: a closure holds the words' address, and the register instantiation's words then
+// live in scratch.
+template <bool REG, bool FOLD>
+__device__ __forceinline__ void clf_step(ClfWords<REG>& p, uint32_t& sign, double& factor, const int n, const clf_i4 rec,
+                                         const double keep, const bool dagger) {
+  const int kind = rec.x & 15;
+  const int q0 = min((rec.x >> 4) & 1023, n - 1), q1 = min((rec.x >> 14) & 1023, n - 1);
+  const int w0 = q0 >> 5, b0 = q0 & 31, w1 = q1 >> 5, b1 = q1 & 31;
+  const uint32_t a = ((p.getx(w0) >> b0) & 1u) | (((p.getz(w0) >> b0) & 1u) << 1);
+  const bool two = kind == MLQEM_CLIFFORD_OP_C2 || kind == MLQEM_CLIFFORD_OP_DEPOL2;
+  const uint32_t b = two ? ((p.getx(w1) >> b1) & 1u) | (((p.getz(w1) >> b1) & 1u) << 1) : 0u;
+  const uint32_t pq = a | (b << 2);
+  if (kind == MLQEM_CLIFFORD_OP_C1) {
+    uint32_t img = a ? ((uint32_t)rec.y >> (3 * (a ? a - 1 : 0u))) & 7u : 0u;   // letter | sign << 2; I stays I
+    if (FOLD && dagger) {
+      const uint32_t e = clf_find_c1((uint32_t)rec.y, a);
+      img = a ? (e + 1u) | ((((uint32_t)rec.y >> (3 * e + 2)) & 1u) << 2) : 0u;
+    }
+    const uint32_t d = (img & 3u) ^ a;
+    sign ^= img >> 2;
+    p.flip(w0, (d & 1u) << b0, (d >> 1) << b0);
+  } else if (kind == MLQEM_CLIFFORD_OP_C2) {
+    const uint64_t tab = (uint64_t)(uint32_t)rec.y | ((uint64_t)(uint32_t)rec.z << 32);
+    uint32_t e = pq ? pq - 1 : 0u;
+    uint32_t img = pq ? (uint32_t)(tab >> (4 * e)) & 15u : 0u;
+    if (FOLD && dagger) {
+      e = clf_find_c2(tab, pq);
+      img = pq ? e + 1u : 0u;
+    }
+    const uint32_t d = img ^ pq;
+    sign ^= pq ? ((uint32_t)rec.w >> e) & 1u : 0u;
+    p.flip(w0, (d & 1u) << b0, ((d >> 1) & 1u) << b0);
+    p.flip(w1, ((d >> 2) & 1u) << b1, ((d >> 3) & 1u) << b1);
+  } else if (kind == MLQEM_CLIFFORD_OP_DEPOL1 || kind == MLQEM_CLIFFORD_OP_DEPOL2) {
+    factor = pq ? factor * keep : factor;
+  }
+}
+
+// FOLD = false walks the circuit's records from the last to the first (mlqem_clifford_run_f64); FOLD = true walks the schedule of
+// run (f, circuit of the unit) from its last entry to its first (mlqem_clifford_run_folded_f64): slot = f * n_here + the unit's
+// place in this part, so the units of one circuit stay adjacent and the lanes of a wave still mostly load the same bytes.
+template <bool REG, bool FOLD>
 __global__ __launch_bounds__(kBlock) void walk_kernel(int n_circuits, const int32_t* __restrict__ n_qubits,
                                                       const int64_t* __restrict__ op_ptr, const clf_i4* __restrict__ ops, int64_t n_ops,
                                                       const double* __restrict__ pool, int64_t n_pool,
                                                       const clf_i4* __restrict__ units, int64_t first_unit, int64_t n_here,
                                                       const uint32_t* __restrict__ masks, int64_t n_masks,
-                                                      double* __restrict__ unit_ideal, double* __restrict__ unit_noisy) {
+                                                      double* __restrict__ unit_ideal, double* __restrict__ unit_noisy,
+                                                      int n_factors, int64_t n_units, const int64_t* __restrict__ sched_ptr,
+                                                      const int32_t* __restrict__ sched, int64_t n_sched) {
   constexpr int WCAP = REG ? kClfRegWords : kClfMaxWords;
   __shared__ uint32_t lds[REG ? 1 : 2 * kClfMaxWords * kBlock];
   const int64_t slot = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  const bool live = slot < n_here;
-  const int64_t u = first_unit + (live ? slot : n_here - 1);   // n_here >= 1: the launcher launches nothing otherwise
+  const int64_t n_slots = FOLD ? (int64_t)n_factors * n_here : n_here;
+  const bool live = slot < n_slots;
+  const int64_t at = live ? slot : n_slots - 1;   // n_here >= 1 (and n_factors >= 1): the launcher launches nothing otherwise
+  const int64_t fac = FOLD ? at / n_here : 0;
+  const int64_t u = first_unit + (FOLD ? at - fac * n_here : at);
   const clf_i4 unit = units[u];
   const int c = min(max(unit.x, 0), n_circuits - 1);
   const int n = min(max(n_qubits[c], 1), 32 * WCAP);
@@ -100,47 +166,52 @@ __global__ __launch_bounds__(kBlock) void walk_kernel(int n_circuits, const int3
   const int64_t ob = min(max(op_ptr[c], (int64_t)0), n_ops), oe = min(max(op_ptr[c + 1], ob), n_ops);
   uint32_t sign = 0;
   double factor = 1.0;
-  // kClfChunk records at a time: their loads, then the loads of the pool entries they name, are in flight together, so a lane waits
-  // for memory twice per chunk and not twice per record (the walk itself is a serial chain through the lane's words)
-  for (int64_t k = oe - 1; k >= ob; k -= kClfChunk) {
-    clf_i4 r[kClfChunk];
-    double keep[kClfChunk];
+  if constexpr (!FOLD) {
+    // kClfChunk records at a time: their loads, then the loads of the pool entries they name, are in flight together, so a lane
+    // waits for memory twice per chunk and not twice per record (the walk itself is a serial chain through the lane's words)
+    for (int64_t k = oe - 1; k >= ob; k -= kClfChunk) {
+      clf_i4 r[kClfChunk];
+      double keep[kClfChunk];
 #pragma unroll
-    for (int j = 0; j < kClfChunk; ++j) r[j] = ops[max(k - j, ob)];
+      for (int j = 0; j < kClfChunk; ++j) r[j] = ops[max(k - j, ob)];
 #pragma unroll
-    for (int j = 0; j < kClfChunk; ++j) keep[j] = pool[min(max((int64_t)r[j].y, (int64_t)0), n_pool - 1)];
+      for (int j = 0; j < kClfChunk; ++j) keep[j] = pool[min(max((int64_t)r[j].y, (int64_t)0), n_pool - 1)];
 #pragma unroll
-    for (int j = 0; j < kClfChunk; ++j) {
-      if (k - j < ob) break;
-      const int kind = r[j].x & 15;
-      const int q0 = min((r[j].x >> 4) & 1023, n - 1), q1 = min((r[j].x >> 14) & 1023, n - 1);
-      const int w0 = q0 >> 5, b0 = q0 & 31, w1 = q1 >> 5, b1 = q1 & 31;
-      const uint32_t a = ((p.getx(w0) >> b0) & 1u) | (((p.getz(w0) >> b0) & 1u) << 1);
-      const bool two = kind == MLQEM_CLIFFORD_OP_C2 || kind == MLQEM_CLIFFORD_OP_DEPOL2;
-      const uint32_t b = two ? ((p.getx(w1) >> b1) & 1u) | (((p.getz(w1) >> b1) & 1u) << 1) : 0u;
-      const uint32_t pq = a | (b << 2);
-      if (kind == MLQEM_CLIFFORD_OP_C1) {
-        const uint32_t img = a ? ((uint32_t)r[j].y >> (3 * (a ? a - 1 : 0u))) & 7u : 0u;   // letter | sign << 2; I stays I
-        const uint32_t d = (img & 3u) ^ a;
-        sign ^= img >> 2;
-        p.flip(w0, (d & 1u) << b0, (d >> 1) << b0);
-      } else if (kind == MLQEM_CLIFFORD_OP_C2) {
-        const uint32_t e = pq ? pq - 1 : 0u;
-        const uint64_t tab = (uint64_t)(uint32_t)r[j].y | ((uint64_t)(uint32_t)r[j].z << 32);
-        const uint32_t img = pq ? (uint32_t)(tab >> (4 * e)) & 15u : 0u;
-        const uint32_t d = img ^ pq;
-        sign ^= pq ? ((uint32_t)r[j].w >> e) & 1u : 0u;
-        p.flip(w0, (d & 1u) << b0, ((d >> 1) & 1u) << b0);
-        p.flip(w1, ((d >> 2) & 1u) << b1, ((d >> 3) & 1u) << b1);
-      } else if (kind == MLQEM_CLIFFORD_OP_DEPOL1 || kind == MLQEM_CLIFFORD_OP_DEPOL2) {
-        factor = pq ? factor * keep[j] : factor;
+      for (int j = 0; j < kClfChunk; ++j) {
+        if (k - j < ob) break;
+        clf_step<REG, FOLD>(p, sign, factor, n, r[j], keep[j], false);
+      }
+    }
+  } else {
+    // run r = f * B + c; a circuit without records skips its entries (so every record index below is inside [ob, oe - 1])
+    const int64_t n_runs = (int64_t)n_factors * n_circuits;
+    const int64_t run = min(max(fac * n_circuits + c, (int64_t)0), n_runs - 1);
+    const int64_t sb = min(max(sched_ptr[run], (int64_t)0), n_sched);
+    const int64_t se = oe > ob ? min(max(sched_ptr[run + 1], sb), n_sched) : sb;
+    const int64_t last = oe - ob - 1;
+    // three dependent loads per entry (entry -> record -> pool value); the four of a chunk are in flight together at each level
+    for (int64_t i = se - 1; i >= sb; i -= kClfChunk) {
+      int32_t e[kClfChunk];
+      clf_i4 r[kClfChunk];
+      double keep[kClfChunk];
+#pragma unroll
+      for (int j = 0; j < kClfChunk; ++j) e[j] = sched[max(i - j, sb)];
+#pragma unroll
+      for (int j = 0; j < kClfChunk; ++j) r[j] = ops[ob + min(max((int64_t)(e[j] >> 1), (int64_t)0), last)];
+#pragma unroll
+      for (int j = 0; j < kClfChunk; ++j) keep[j] = pool[min(max((int64_t)r[j].y, (int64_t)0), n_pool - 1)];
+#pragma unroll
+      for (int j = 0; j < kClfChunk; ++j) {
+        if (i - j < sb) break;
+        clf_step<REG, FOLD>(p, sign, factor, n, r[j], keep[j], (e[j] & 1) != 0);
       }
     }
   }
   const double ideal = p.any_x(W) ? 0.0 : (sign & 1u) ? -1.0 : 1.0;
   if (live) {
-    unit_ideal[u] = ideal;
-    unit_noisy[u] = ideal * factor;
+    const int64_t out = FOLD ? fac * n_units + u : u;
+    unit_ideal[out] = ideal;
+    unit_noisy[out] = ideal * factor;
   }
 }
 
@@ -154,6 +225,11 @@ __global__ __launch_bounds__(kWave) void combine_kernel(int n_circuits, const in
                                                         double* __restrict__ noisy_values) {
 #pragma clang fp contract(off)
   const int c = blockIdx.x;
+  const int64_t f = blockIdx.y;   // the noise factor: row f of every [F][.] buffer (0 for the unfolded run)
+  unit_ideal += f * n_units;
+  unit_noisy += f * n_units;
+  ideal_terms += f * n_terms;
+  noisy_terms += f * n_terms;
   const int64_t tb = min(max(term_ptr[c], (int64_t)0), n_terms), te = min(max(term_ptr[c + 1], tb), n_terms);
   for (int64_t t = tb + threadIdx.x; t < te; t += kWave) {
     const int64_t jb = min(max(comb_ptr[t], (int64_t)0), n_comb), je = min(max(comb_ptr[t + 1], jb), n_comb);
@@ -174,8 +250,8 @@ __global__ __launch_bounds__(kWave) void combine_kernel(int n_circuits, const in
       vi = vi + coeff[t] * ideal_terms[t];
       vn = vn + coeff[t] * noisy_terms[t];
     }
-    ideal_values[c] = vi;
-    noisy_values[c] = vn;
+    ideal_values[f * n_circuits + c] = vi;
+    noisy_values[f * n_circuits + c] = vn;
   }
 }
 
@@ -184,6 +260,64 @@ __global__ __launch_bounds__(kWave) void combine_kernel(int n_circuits, const in
 
 using namespace mlqem;
 
+// The two entry points share their checks and launches: `sched_ptr == nullptr` is the plain run (n_factors = 1).
+static int clifford_run_impl(bool fold, int64_t n_circuits, int64_t n_factors, const int32_t* n_qubits, const int64_t* op_ptr,
+                             const mlqem_clifford_op* ops, int64_t n_ops, const double* pool, int64_t n_pool,
+                             const mlqem_clifford_unit* units, int64_t n_reg, int64_t n_lds, const uint32_t* masks, int64_t n_masks,
+                             const int64_t* term_ptr, const double* coeff, int64_t n_terms, const int64_t* comb_ptr,
+                             const int32_t* comb_unit, const double* comb_weight, int64_t n_comb, const int64_t* sched_ptr,
+                             const int32_t* sched, int64_t n_sched, double* unit_ideal, double* unit_noisy, double* ideal_terms,
+                             double* noisy_terms, double* ideal_values, double* noisy_values, mlqem_stream_t stream) {
+  static_assert(sizeof(mlqem_clifford_op) == 16 && sizeof(mlqem_clifford_unit) == 16, "one 16-byte load per record");
+  begin_launches();
+  if (n_circuits < 0 || n_ops < 0 || n_terms < 0 || n_reg < 0 || n_lds < 0 || n_comb < 0 || n_pool < kClfPad || n_masks < kClfPad ||
+      n_factors < 1 || n_sched < 0)
+    return MLQEM_ERR_BAD_ARG;
+  const int64_t n_units = n_reg + n_lds;
+  if (n_circuits > 0x7FFFFFFFll || n_units > 0x7FFFFFFFll || n_pool > 0x7FFFFFFFll || n_masks > 0x7FFFFFFFll ||
+      n_factors > 0x7FFFFFFFll || n_sched > 0x7FFFFFFFll)
+    return MLQEM_ERR_UNSUPPORTED;
+  // grid.y carries the factor in the combine; F * B and F * units stay below 2^31 so that a block count fits a grid dimension
+  if (n_factors > 65535 || n_factors * n_circuits > 0x7FFFFFFFll || n_factors * n_units > 0x7FFFFFFFll) return MLQEM_ERR_UNSUPPORTED;
+  if (n_circuits == 0) return MLQEM_OK;
+  if (!n_qubits || !op_ptr || !pool || !masks || !term_ptr || !ideal_values || !noisy_values || (n_ops > 0 && !ops) ||
+      (n_units > 0 && (!units || !unit_ideal || !unit_noisy)) ||
+      (n_terms > 0 && (!coeff || !comb_ptr || !ideal_terms || !noisy_terms)) || (n_comb > 0 && (!comb_unit || !comb_weight)))
+    return MLQEM_ERR_BAD_ARG;
+  if (fold && (!sched_ptr || (n_sched > 0 && !sched))) return MLQEM_ERR_BAD_ARG;
+  if (n_comb > 0 && n_units == 0) return MLQEM_ERR_BAD_ARG;   // a combine entry needs a unit to name
+  if (!aligned_to(ops, 16) || !aligned_to(units, 16)) return MLQEM_ERR_BAD_ARG;
+  const clf_i4* oi = reinterpret_cast<const clf_i4*>(ops);
+  const clf_i4* ui = reinterpret_cast<const clf_i4*>(units);
+  const int F = (int)n_factors;
+  if (n_reg > 0) {
+    const dim3 grid((unsigned)ceil_div(n_factors * n_reg, (int64_t)kBlock));
+    if (fold)
+      hipLaunchKernelGGL((walk_kernel<true, true>), grid, dim3(kBlock), 0, as_stream(stream), (int)n_circuits, n_qubits, op_ptr, oi,
+                         n_ops, pool, n_pool, ui, (int64_t)0, n_reg, masks, n_masks, unit_ideal, unit_noisy, F, n_units, sched_ptr,
+                         sched, n_sched);
+    else
+      hipLaunchKernelGGL((walk_kernel<true, false>), grid, dim3(kBlock), 0, as_stream(stream), (int)n_circuits, n_qubits, op_ptr, oi,
+                         n_ops, pool, n_pool, ui, (int64_t)0, n_reg, masks, n_masks, unit_ideal, unit_noisy, F, n_units, sched_ptr,
+                         sched, n_sched);
+  }
+  if (n_lds > 0) {
+    const dim3 grid((unsigned)ceil_div(n_factors * n_lds, (int64_t)kBlock));
+    if (fold)
+      hipLaunchKernelGGL((walk_kernel<false, true>), grid, dim3(kBlock), 0, as_stream(stream), (int)n_circuits, n_qubits, op_ptr, oi,
+                         n_ops, pool, n_pool, ui, n_reg, n_lds, masks, n_masks, unit_ideal, unit_noisy, F, n_units, sched_ptr, sched,
+                         n_sched);
+    else
+      hipLaunchKernelGGL((walk_kernel<false, false>), grid, dim3(kBlock), 0, as_stream(stream), (int)n_circuits, n_qubits, op_ptr, oi,
+                         n_ops, pool, n_pool, ui, n_reg, n_lds, masks, n_masks, unit_ideal, unit_noisy, F, n_units, sched_ptr, sched,
+                         n_sched);
+  }
+  hipLaunchKernelGGL(combine_kernel, dim3((unsigned)n_circuits, (unsigned)n_factors), dim3(kWave), 0, as_stream(stream),
+                     (int)n_circuits, term_ptr, coeff, n_terms, comb_ptr, comb_unit, comb_weight, n_comb, unit_ideal, unit_noisy,
+                     n_units, ideal_terms, noisy_terms, ideal_values, noisy_values);
+  return launch_status();
+}
+
 extern "C" int mlqem_clifford_run_f64(int64_t n_circuits, const int32_t* n_qubits, const int64_t* op_ptr, const mlqem_clifford_op* ops,
                                       int64_t n_ops, const double* pool, int64_t n_pool, const mlqem_clifford_unit* units,
                                       int64_t n_reg, int64_t n_lds, const uint32_t* masks, int64_t n_masks, const int64_t* term_ptr,
@@ -191,34 +325,20 @@ extern "C" int mlqem_clifford_run_f64(int64_t n_circuits, const int32_t* n_qubit
                                       const double* comb_weight, int64_t n_comb, double* unit_ideal, double* unit_noisy,
                                       double* ideal_terms, double* noisy_terms, double* ideal_values, double* noisy_values,
                                       mlqem_stream_t stream) {
-  static_assert(sizeof(mlqem_clifford_op) == 16 && sizeof(mlqem_clifford_unit) == 16, "one 16-byte load per record");
-  begin_launches();
-  if (n_circuits < 0 || n_ops < 0 || n_terms < 0 || n_reg < 0 || n_lds < 0 || n_comb < 0 || n_pool < kClfPad || n_masks < kClfPad)
-    return MLQEM_ERR_BAD_ARG;
-  const int64_t n_units = n_reg + n_lds;
-  if (n_circuits > 0x7FFFFFFFll || n_units > 0x7FFFFFFFll || n_pool > 0x7FFFFFFFll || n_masks > 0x7FFFFFFFll)
-    return MLQEM_ERR_UNSUPPORTED;
-  if (n_circuits == 0) return MLQEM_OK;
-  if (!n_qubits || !op_ptr || !pool || !masks || !term_ptr || !ideal_values || !noisy_values || (n_ops > 0 && !ops) ||
-      (n_units > 0 && (!units || !unit_ideal || !unit_noisy)) ||
-      (n_terms > 0 && (!coeff || !comb_ptr || !ideal_terms || !noisy_terms)) || (n_comb > 0 && (!comb_unit || !comb_weight)))
-    return MLQEM_ERR_BAD_ARG;
-  if (n_comb > 0 && n_units == 0) return MLQEM_ERR_BAD_ARG;   // a combine entry needs a unit to name
-  if (!aligned_to(ops, 16) || !aligned_to(units, 16)) return MLQEM_ERR_BAD_ARG;
-  const clf_i4* oi = reinterpret_cast<const clf_i4*>(ops);
-  const clf_i4* ui = reinterpret_cast<const clf_i4*>(units);
-  if (n_reg > 0) {
-    hipLaunchKernelGGL((walk_kernel<true>), dim3((unsigned)ceil_div(n_reg, (int64_t)kBlock)), dim3(kBlock), 0, as_stream(stream),
-                       (int)n_circuits, n_qubits, op_ptr, oi, n_ops, pool, n_pool, ui, (int64_t)0, n_reg, masks, n_masks, unit_ideal,
-                       unit_noisy);
-  }
-  if (n_lds > 0) {
-    hipLaunchKernelGGL((walk_kernel<false>), dim3((unsigned)ceil_div(n_lds, (int64_t)kBlock)), dim3(kBlock), 0, as_stream(stream),
-                       (int)n_circuits, n_qubits, op_ptr, oi, n_ops, pool, n_pool, ui, n_reg, n_lds, masks, n_masks, unit_ideal,
-                       unit_noisy);
-  }
-  hipLaunchKernelGGL(combine_kernel, dim3((unsigned)n_circuits), dim3(kWave), 0, as_stream(stream), (int)n_circuits, term_ptr, coeff,
-                     n_terms, comb_ptr, comb_unit, comb_weight, n_comb, unit_ideal, unit_noisy, n_units, ideal_terms, noisy_terms,
-                     ideal_values, noisy_values);
-  return launch_status();
+  return clifford_run_impl(false, n_circuits, 1, n_qubits, op_ptr, ops, n_ops, pool, n_pool, units, n_reg, n_lds, masks, n_masks,
+                           term_ptr, coeff, n_terms, comb_ptr, comb_unit, comb_weight, n_comb, nullptr, nullptr, 0, unit_ideal,
+                           unit_noisy, ideal_terms, noisy_terms, ideal_values, noisy_values, stream);
+}
+
+extern "C" int mlqem_clifford_run_folded_f64(int64_t n_circuits, int64_t n_factors, const int32_t* n_qubits, const int64_t* op_ptr,
+                                             const mlqem_clifford_op* ops, int64_t n_ops, const double* pool, int64_t n_pool,
+                                             const mlqem_clifford_unit* units, int64_t n_reg, int64_t n_lds, const uint32_t* masks,
+                                             int64_t n_masks, const int64_t* term_ptr, const double* coeff, int64_t n_terms,
+                                             const int64_t* comb_ptr, const int32_t* comb_unit, const double* comb_weight,
+                                             int64_t n_comb, const int64_t* sched_ptr, const int32_t* sched, int64_t n_sched,
+                                             double* unit_ideal, double* unit_noisy, double* ideal_terms, double* noisy_terms,
+                                             double* ideal_values, double* noisy_values, mlqem_stream_t stream) {
+  return clifford_run_impl(true, n_circuits, n_factors, n_qubits, op_ptr, ops, n_ops, pool, n_pool, units, n_reg, n_lds, masks,
+                           n_masks, term_ptr, coeff, n_terms, comb_ptr, comb_unit, comb_weight, n_comb, sched_ptr, sched, n_sched,
+                           unit_ideal, unit_noisy, ideal_terms, noisy_terms, ideal_values, noisy_values, stream);
 }

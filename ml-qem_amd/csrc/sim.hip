@@ -431,6 +431,52 @@ __global__ __launch_bounds__(kBlock) void zne_combine_kernel(int F, const double
   }
 }
 
+// Exponential extrapolation (mlqem_zne_combine_exp_f64): a straight line through (factor, ln|value|), evaluated at zero noise and
+// exponentiated, where the term's values are all nonzero with one sign; 0 where they are all 0; the linear sum and a fallback flag
+// anywhere else (a zero among nonzeros, mixed signs, a NaN).  The same thread layout and fixed order as zne_combine_kernel.
+__device__ __forceinline__ double zne_exp_term(const double* __restrict__ tv, const double* __restrict__ w, int F, int64_t n_terms,
+                                               int64_t t, int& fallback) {
+  int pos = 0, neg = 0, zero = 0;
+  for (int f = 0; f < F; ++f) {
+    const double v = tv[(int64_t)f * n_terms + t];
+    pos += v > 0.0;
+    neg += v < 0.0;
+    zero += v == 0.0;
+  }
+  fallback = 0;
+  if (pos == F || neg == F) {
+    double acc = w[0] * log(fabs(tv[t]));
+    for (int f = 1; f < F; ++f) acc = __builtin_fma(w[f], log(fabs(tv[(int64_t)f * n_terms + t])), acc);
+    const double m = exp(acc);
+    return neg == F ? -m : m;
+  }
+  if (zero == F) return 0.0;
+  fallback = 1;
+  return zne_term(tv, w, F, n_terms, t);
+}
+
+__global__ __launch_bounds__(kBlock) void zne_combine_exp_kernel(int F, const double* __restrict__ tv, const double* __restrict__ w,
+                                                                 const int64_t* __restrict__ term_ptr,
+                                                                 const double* __restrict__ coeff, int64_t n_terms, int64_t B,
+                                                                 double* __restrict__ mterms, double* __restrict__ mvalues,
+                                                                 int32_t* __restrict__ fallback) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i < n_terms) {
+    int fb;
+    mterms[i] = zne_exp_term(tv, w, F, n_terms, i, fb);
+    fallback[i] = fb;
+  }
+  if (i < B) {
+    const int64_t tb = min(max(term_ptr[i], (int64_t)0), n_terms), te = min(max(term_ptr[i + 1], tb), n_terms);
+    double total = 0.0;
+    for (int64_t t = tb; t < te; ++t) {
+      int fb;
+      total = __builtin_fma(coeff[t], zne_exp_term(tv, w, F, n_terms, t, fb), total);
+    }
+    mvalues[i] = total;
+  }
+}
+
 // ---- measurement shots (mlqem_sim_sample_f64) ----------------------------------------------------------------------------------------
 // Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11): ten rounds of two 32 x 32 -> 64 products,
 // the key bumped by the Weyl constants between rounds.
@@ -683,6 +729,22 @@ extern "C" int mlqem_zne_combine_f64(int64_t n_factors, int64_t n_circuits, cons
   const int64_t blocks = ceil_div(n_circuits > n_terms ? n_circuits : n_terms, (int64_t)kBlock);
   hipLaunchKernelGGL(zne_combine_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), (int)n_factors, term_values, weights,
                      term_ptr, coeff, n_terms, n_circuits, mitigated_terms, mitigated_values);
+  return launch_status();
+}
+
+extern "C" int mlqem_zne_combine_exp_f64(int64_t n_factors, int64_t n_circuits, const double* term_values, const double* weights,
+                                         const int64_t* term_ptr, const double* coeff, int64_t n_terms, double* mitigated_terms,
+                                         double* mitigated_values, int32_t* fallback, mlqem_stream_t stream) {
+  begin_launches();
+  if (n_factors < 2 || n_circuits < 0 || n_terms < 0) return MLQEM_ERR_BAD_ARG;   // a line needs two points
+  if (n_factors > 0x7FFFFFFFll || n_circuits > 0x7FFFFFFFll || n_terms > 0x7FFFFFFFll) return MLQEM_ERR_UNSUPPORTED;
+  if (n_circuits == 0 && n_terms == 0) return MLQEM_OK;
+  if (!weights || (n_circuits > 0 && (!term_ptr || !mitigated_values)) ||
+      (n_terms > 0 && (!term_values || !coeff || !mitigated_terms || !fallback)))
+    return MLQEM_ERR_BAD_ARG;
+  const int64_t blocks = ceil_div(n_circuits > n_terms ? n_circuits : n_terms, (int64_t)kBlock);
+  hipLaunchKernelGGL(zne_combine_exp_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), (int)n_factors, term_values,
+                     weights, term_ptr, coeff, n_terms, n_circuits, mitigated_terms, mitigated_values, fallback);
   return launch_status();
 }
 

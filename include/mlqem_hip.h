@@ -1342,6 +1342,15 @@ int mlqem_linreg_predict_f32(const float* x, int64_t ldx, int64_t n_rows, int F,
  *           MLQEM_SIM_OP_READOUT q0       2: p01 = P(read 0 | prepared 1), p10 = P(read 1 | prepared 0).  The column-stochastic matrix
  *                                         [[1 - p10, p01], [p10, 1 - p01]] on bit q0 of the DIAGONAL of rho; off-diagonal entries
  *                                         are meaningless afterwards, so only I/Z terms may follow.  Mode 1 only.
+ *           MLQEM_SIM_OP_NOISE1  q0       4: lambda, g, c, p1.  One fused noise record: MLQEM_SIM_OP_DEPOL1's map with lambda, then
+ *                                         thermal relaxation of q0 on the same 2x2 block (e_rc: row bit r, column bit c of q0), with
+ *                                         tr = e00 + e11:  e00' = (1 - g) e00 + g (1 - p1) tr,  e11' = (1 - g) e11 + g p1 tr,
+ *                                         e01' = c e01,  e10' = c e10.  g = 1 - exp(-t/T1) is the reset probability, c = exp(-t/T2)
+ *                                         the factor of the coherences, p1 the excited-state population.  One pass.  lambda = 0
+ *                                         leaves the first part an exact identity, g = 0 and c = 1 the second.  Mode 1 only.
+ *           MLQEM_SIM_OP_NOISE2  q0, q1   7: lambda, (g, c, p1) of q0, (g, c, p1) of q1.  MLQEM_SIM_OP_DEPOL2's map with lambda, then
+ *                                         the relaxation map above on q0 and on q1, in one pass over the 4x4 blocks.  Mode 1 only.
+ *         The host keeps 0 <= g, p1 <= 1 and 0 <= c <= sqrt(1 - g) (complete positivity); the kernel uses the values as they are.
  *         An unknown kind is skipped.
  * params  float64 [n_params], n_params >= 32, with 32 values of padding after the last record's (a record's read is clamped to
  *         [0, n_params - 32]).
@@ -1376,6 +1385,10 @@ int mlqem_linreg_predict_f32(const float* x, int64_t ldx, int64_t n_rows, int F,
 #define MLQEM_SIM_OP_DEPOL1 6
 #define MLQEM_SIM_OP_DEPOL2 7
 #define MLQEM_SIM_OP_READOUT 8
+/* 9 is MLQEM_SIM_OP_MEASURE (below).  The two fused noise kinds were added without a change of any signature: a program lowered
+ * before them never contains them, and its results are the same bits. */
+#define MLQEM_SIM_OP_NOISE1 10
+#define MLQEM_SIM_OP_NOISE2 11
 typedef struct mlqem_sim_op { int32_t kind; int32_t q0; int32_t q1; int32_t param; } mlqem_sim_op;
 typedef struct mlqem_sim_term { int32_t xmask; int32_t zmask; int32_t ny; int32_t reserved; } mlqem_sim_term;
 int mlqem_sim_run_f64(int64_t n_circuits, const int32_t* circ, const int64_t* op_ptr, const mlqem_sim_op* ops, int64_t n_ops,
@@ -1401,7 +1414,7 @@ int mlqem_sim_run_f64(int64_t n_circuits, const int32_t* circ, const int64_t* op
  *                            transpose
  *           DIAG1            conjugated phases
  *           CX, CZ, SWAP     unchanged (self-inverse)
- *           DEPOL*, READOUT  the flag is ignored
+ *           DEPOL*, NOISE*, READOUT  the flag is ignored (a noise record is never inverted)
  * ids     int32 [n_wave + n_wg]: RUN numbers; the wave / workgroup split is by the circuit's amplitude count, as above.
  * Outputs, float64: term_values [F][n_terms], values [F][B], norm [F][B]; only the entries of the runs in `ids` are written.
  * The contract of mlqem_sim_run_f64 holds for the new input too: k is clamped to the circuit's op range (a circuit without ops

@@ -195,6 +195,15 @@ def _words(mask: int, w: int) -> List[int]:
     return [(mask >> (32 * j)) & 0xFFFFFFFF for j in range(w)]
 
 
+def refuse_non_pauli(noise: Any, who: str) -> None:
+    """``ValueError`` naming the model and the reason where ``noise`` has a part the Clifford path cannot carry: thermal
+    relaxation is no Pauli channel and a controlled rotation is no Clifford gate, so the walk would silently drop them."""
+    why = getattr(noise, "non_pauli", None)
+    if why:
+        raise ValueError(f"{who}: the noise model {getattr(noise, 'name', type(noise).__name__)!r} cannot run on the Clifford path: {why}; "
+                         "use the exact simulator (at most 5 qubits as a density matrix)")
+
+
 def compile_clifford(circuits: Sequence[Any], observables: Sequence[Any], noise: Any = None) -> CliffordBatch:
     """Lowers Clifford ``circuits`` (anything ``Circuit.from_any`` takes) with one observable each (anything ``pauli_terms`` takes,
     any Pauli string with a real coefficient) to one :class:`CliffordBatch`.  ``noise``: None, a ``NoiseModel`` or any object with
@@ -204,7 +213,7 @@ def compile_clifford(circuits: Sequence[Any], observables: Sequence[Any], noise:
     any angle that makes it a Clifford gate, and the refusals are ``compile_programs``': unknown gates, a wrong parameter count, a
     gate after a measurement, a qubit out of range, a two-qubit gate on one qubit twice, a non-finite angle, a label of the wrong
     length or alphabet, a coefficient that is not real.  Also refused, by name: a gate that is not a Clifford gate (``rz(0.3)``), a
-    circuit of more than 512 qubits, and, with non-trivial readout probabilities on a measured qubit, an observable with X or Y.
+    circuit of more than 512 qubits, a noise model with thermal relaxation or a coherent error (:func:`refuse_non_pauli`), and, with non-trivial readout probabilities on a measured qubit, an observable with X or Y.
 
     Records: ``id`` has none but keeps its depolarising record; a depolarising record holds the index of ``keep = 1 - lambda`` in
     ``pool``.  Readout is no record: every ``Z_q`` of a term on a measured qubit with probabilities (p01, p10) becomes
@@ -215,6 +224,8 @@ def compile_clifford(circuits: Sequence[Any], observables: Sequence[Any], noise:
     circuits, observables = list(circuits), list(observables)
     if len(circuits) != len(observables):
         raise ValueError(f"compile_clifford: {len(circuits)} circuits but {len(observables)} observables")
+    refuse_non_pauli(noise, "compile_clifford")
+    relaxation_after, coherent_after = getattr(noise, "relaxation_after", None), getattr(noise, "coherent_after", None)
     nq_all, op_ptr, flat_ops, pool = [], [0], [], []
     unit_circ, unit_ny, unit_mask, masks = [], [], [], []
     coeffs, term_ptr, comb_ptr, comb_unit, comb_weight = [], [0], [0], [], []
@@ -270,7 +281,13 @@ def compile_clifford(circuits: Sequence[Any], observables: Sequence[Any], noise:
                 flat_ops += (CL_C2 | qs if width == 2 else CL_C1 | qs, table[0], table[1], table[2])
                 n_rec += 1
             if noise is not None:
-                lam = noise.after_gate(i, name, tuple(circ.qubit_reg_index[q] for q in op.qubits))
+                reg = tuple(circ.qubit_reg_index[q] for q in op.qubits)
+                for hook, why in ((relaxation_after, "thermal relaxation, which is not a Pauli channel"),
+                                  (coherent_after, "a coherent error, which is not a Clifford gate")):
+                    if hook is not None and hook(i, name, reg) is not None:   # a duck-typed model that does not say non_pauli
+                        raise ValueError(f"{where}: op {i} ({name}): the noise model {getattr(noise, 'name', type(noise).__name__)!r} has "
+                                         f"{why}; the Clifford path cannot carry it")
+                lam = noise.after_gate(i, name, reg)
                 if lam is not None:
                     if not (math.isfinite(lam) and 0.0 <= lam <= 1.0):
                         raise ValueError(f"{where}: op {i} ({name}): depolarising parameter {lam!r}, want 0 <= lambda <= 1")

@@ -14,7 +14,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ..data.backends import PauliObservable, pauli_terms
+from ..data.backends import PauliObservable, _apply_unit_prefix, pauli_terms
 from ..data.circuit import Circuit
 
 WAVE_AMPS = 256     # MLQEM_SIM_WAVE_AMPS: a wave per circuit
@@ -26,6 +26,7 @@ MAX_QUBITS_DENSITY = 5
 MAX_SHOTS = 2 ** 20  # MLQEM_SIM_MAX_SHOTS: counts are int32 and a Philox counter word holds shot >> 1
 
 OP_U1, OP_DIAG1, OP_CX, OP_CZ, OP_SWAP, OP_U2, OP_DEPOL1, OP_DEPOL2, OP_READOUT, OP_MEASURE = range(10)   # MLQEM_SIM_OP_*
+OP_NOISE1, OP_NOISE2 = 10, 11   # the fused noise records: depolarising, then thermal relaxation of the gate's qubits
 
 _N_PARAMS = {"id": 0, "x": 0, "y": 0, "z": 0, "h": 0, "s": 0, "sdg": 0, "t": 0, "tdg": 0, "sx": 0, "sxdg": 0, "rx": 1, "ry": 1,
              "rz": 1, "p": 1, "u1": 1, "u2": 2, "u3": 3, "u": 3, "cx": 0, "cz": 0, "swap": 0, "ecr": 0, "rzz": 1}
@@ -94,19 +95,58 @@ def _two_qubit(name: str, p: Tuple[float, ...]):
     return OP_U2, [a, 0, 0, 0, 0, b, 0, 0, 0, 0, b, 0, 0, 0, 0, a]
 
 
+def _check_relaxation(key, triples, width: Optional[int] = None) -> Tuple[Tuple[float, float, float], ...]:
+    """One (g, c, p1) triple per qubit, or a ``ValueError`` that names ``key`` and the value that is out of range."""
+    out = tuple(tuple(float(v) for v in t) for t in triples)
+    if not out or any(len(t) != 3 for t in out) or len(out) > 2 or (width is not None and len(out) != width):
+        raise ValueError(f"NoiseModel: relaxation of {key} is {triples!r}, want one (g, c, p1) triple per qubit of the gate")
+    for g, c, p1 in out:
+        if not (math.isfinite(g) and 0.0 <= g <= 1.0):
+            raise ValueError(f"NoiseModel: relaxation of {key}: reset probability g = {g!r}, want 0 <= g <= 1")
+        if not (math.isfinite(p1) and 0.0 <= p1 <= 1.0):
+            raise ValueError(f"NoiseModel: relaxation of {key}: excited-state population p1 = {p1!r}, want 0 <= p1 <= 1")
+        if not (math.isfinite(c) and 0.0 <= c <= math.sqrt(1.0 - g)):
+            raise ValueError(f"NoiseModel: relaxation of {key}: coherence factor c = {c!r}, want 0 <= c <= sqrt(1 - g) = "
+                             f"{math.sqrt(1.0 - g)!r} (complete positivity: T2 <= 2 T1)")
+    return out
+
+
+def _check_coherent(key, matrix) -> np.ndarray:
+    """A 4x4 unitary (to 1e-12), or a ``ValueError`` that names ``key``."""
+    m = np.asarray(matrix, dtype=complex)
+    if m.shape != (4, 4) or not np.all(np.isfinite(m)):
+        raise ValueError(f"NoiseModel: coherent error of {key} has the shape {m.shape}, want a finite 4x4 matrix")
+    dev = float(np.abs(m.conj().T @ m - np.eye(4)).max())
+    if dev > 1e-12:
+        raise ValueError(f"NoiseModel: coherent error of {key} is not unitary: max |U^dagger U - 1| = {dev:.3e}, want <= 1e-12")
+    return m
+
+
 class NoiseModel:
-    """The project's OWN noise model for the density-matrix mode: a depolarising op after a gate and a readout op per measured
-    qubit.  It is NOT Aer's ``NoiseModel.from_backend``: no thermal relaxation, no gate times, no T1/T2 -- so the ``noisy``
-    arrays that the reference's datasets hold (made with Aer) are not reproduced by it.
+    """The noise model of the density-matrix mode.  After a gate come, in this order: an optional coherent error (a two-qubit
+    unitary), a depolarising op, and thermal relaxation of the gate's qubits; a readout op per measured qubit ends the circuit.
 
     ``gate_lambda``: ``{(name, (qubits...)): lambda}``, the depolarising parameter of
     ``rho -> (1 - lambda) rho + lambda Tr_S(rho) (x) I/d`` applied after every such gate on its qubits S (d = 2 or 4);
+    ``gate_relaxation``: ``{(name, (qubits...)): ((g, c, p1), ...)}``, one triple per qubit of the gate: the qubit is reset with
+    probability ``g = 1 - exp(-t / T1)`` (to |1> with probability p1, the excited-state population, else to |0>) and its
+    coherences shrink by ``c = exp(-t / T2)``; ``0 <= c <= sqrt(1 - g)`` keeps the map completely positive (T2 <= 2 T1);
+    ``gate_coherent``: ``{(name, (q0, q1)): 4x4 unitary}`` over the basis index bit(q0) + 2 bit(q1), applied right after the gate;
     ``readout``: ``{qubit: (p01, p10)}`` with p01 = P(read 0 | prepared 1) and p10 = P(read 1 | prepared 0).  Qubits are
     indices inside their register (``Circuit.qubit_reg_index``), as calibration tables count them.  An empty model is the
-    noiseless density-matrix mode.  Subclasses may override :meth:`after_gate` / :meth:`readout_of`."""
+    noiseless density-matrix mode.  Subclasses may override :meth:`after_gate` / :meth:`relaxation_after` /
+    :meth:`coherent_after` / :meth:`readout_of`; a duck-typed model may leave ``relaxation_after`` and ``coherent_after`` out.
+
+    :meth:`from_backend` has two forms.  The default is the project's own depolarising + readout model.  With
+    ``thermal_relaxation=True`` it restates the device model of Aer's ``NoiseModel.from_backend`` (gate times, T1, T2, the
+    depolarising part rebalanced against the relaxation part), and that form reproduces the ``noisy`` columns of the reference's
+    datasets within their shot noise (tests/test_relax_cpu.py) -- without readout noise, which those datasets
+    were evidently made without."""
 
     def __init__(self, gate_lambda: Optional[Dict[Tuple[str, Tuple[int, ...]], float]] = None,
-                 readout: Optional[Dict[int, Tuple[float, float]]] = None, strict_two_qubit: bool = False, name: str = "custom"):
+                 readout: Optional[Dict[int, Tuple[float, float]]] = None, strict_two_qubit: bool = False, name: str = "custom",
+                 gate_relaxation: Optional[Dict[Tuple[str, Tuple[int, ...]], Sequence[Tuple[float, float, float]]]] = None,
+                 gate_coherent: Optional[Dict[Tuple[str, Tuple[int, ...]], Any]] = None):
         self.gate_lambda = dict(gate_lambda or {})
         self.readout = dict(readout or {})
         self.strict_two_qubit = bool(strict_two_qubit)
@@ -117,13 +157,28 @@ class NoiseModel:
         for q, (p01, p10) in self.readout.items():
             if not all(math.isfinite(v) and 0.0 <= v <= 1.0 for v in (p01, p10)):
                 raise ValueError(f"NoiseModel: readout probabilities of qubit {q} are {(p01, p10)!r}, want both in [0, 1]")
+        self.gate_relaxation = {(str(k[0]), tuple(int(q) for q in k[1])): _check_relaxation(k, v, len(k[1]))
+                                for k, v in (gate_relaxation or {}).items()}
+        self.gate_coherent = {}
+        for k, v in (gate_coherent or {}).items():
+            if len(k[1]) != 2:
+                raise ValueError(f"NoiseModel: coherent error of {k}: want a two-qubit gate (a 4x4 unitary on its pair)")
+            self.gate_coherent[(str(k[0]), tuple(int(q) for q in k[1]))] = _check_coherent(k, v)
 
     def after_gate(self, index: int, name: str, qubits: Tuple[int, ...]) -> Optional[float]:
         """lambda of the depolarising op after op ``index`` (``name`` on register qubits ``qubits``), or None for none."""
         lam = self.gate_lambda.get((name, tuple(qubits)))
-        if lam is None and self.strict_two_qubit and len(qubits) == 2:
+        if lam is None and self.strict_two_qubit and len(qubits) == 2 and (name, tuple(qubits)) not in self.gate_relaxation:
             raise ValueError(f"noise model {self.name!r} has no calibration entry for {name} on the qubit pair {tuple(qubits)}")
         return lam if lam else None
+
+    def relaxation_after(self, index: int, name: str, qubits: Tuple[int, ...]):
+        """``((g, c, p1), ...)`` of the thermal relaxation after op ``index``, one triple per qubit, or None for none."""
+        return self.gate_relaxation.get((name, tuple(qubits)))
+
+    def coherent_after(self, index: int, name: str, qubits: Tuple[int, ...]):
+        """The 4x4 unitary applied right after op ``index`` (basis index bit(q0) + 2 bit(q1)), or None for none."""
+        return self.gate_coherent.get((name, tuple(qubits)))
 
     def readout_of(self, qubit: int) -> Optional[Tuple[float, float]]:
         return self.readout.get(qubit)
@@ -132,15 +187,42 @@ class NoiseModel:
     def has_readout(self) -> bool:
         return bool(self.readout)
 
+    @property
+    def non_pauli(self) -> Optional[str]:
+        """Why the model is no Pauli channel after Clifford gates (the Clifford path refuses it with these words), or None."""
+        if self.gate_relaxation:
+            return "it has thermal relaxation, which is not a Pauli channel"
+        if self.gate_coherent:
+            return "it has a coherent error (a controlled rotation), which is not a Clifford gate"
+        return None
+
     @staticmethod
-    def from_backend(backend: Any, readout: bool = True) -> "NoiseModel":
-        """From the calibration table the data layer reads (``backend.properties()``): after every gate (name, qubits) with a
-        ``gate_error`` e > 0 a depolarising op with ``lambda = e d / (d - 1)`` (d = 2, 4: the relation between the average gate
-        infidelity and the depolarising parameter, so lambda = 2 e and 4 e / 3); per measured qubit a readout op from
-        ``prob_meas0_prep1`` / ``prob_meas1_prep0``, or from a symmetric ``readout_error`` when those are missing.  A two-qubit
-        gate without a calibration entry is refused when a circuit uses it.  Again: this is not Aer's model of the same name."""
+    def from_backend(backend: Any, readout: bool = True, thermal_relaxation: bool = False,
+                     excited_state_population: float = 0.0) -> "NoiseModel":
+        """From the calibration table the data layer reads (``backend.properties()``).
+
+        Default (``thermal_relaxation=False``), the project's own model: after every gate (name, qubits) with a ``gate_error``
+        e > 0 a depolarising op with ``lambda = e d / (d - 1)`` (d = 2, 4: the relation between the average gate infidelity and
+        the depolarising parameter, so lambda = 2 e and 4 e / 3); per measured qubit a readout op from ``prob_meas0_prep1`` /
+        ``prob_meas1_prep0``, or from a symmetric ``readout_error`` when those are missing.  A two-qubit gate without a
+        calibration entry is refused when a circuit uses it.
+
+        ``thermal_relaxation=True`` restates the device model of Aer's ``NoiseModel.from_backend``.  A gate (name, qubits) with
+        ``gate_error`` e and ``gate_length`` t > 0 (units as the table gives them) relaxes each of its qubits with
+        ``g = 1 - exp(-t / T1)``, ``c = exp(-t / min(T2, 2 T1))`` and ``p1 = excited_state_population``.  That channel has the
+        process fidelity ``F_pro = prod_q (1 + 2 c_q + (1 - g_q)) / 4`` and the average gate fidelity
+        ``F = (d F_pro + 1) / (d + 1)``, d = 2^k.  Only where the calibrated error exceeds what relaxation already explains,
+        ``e > 1 - F``, a depolarising op precedes it, with ``lambda = d (min(e, d / (d + 1)) - (1 - F)) / (d F - 1)`` capped at
+        ``4^k / (4^k - 1)``, so that the composed channel has the calibrated infidelity (a table that would need lambda > 1 is
+        refused by name, as in the default form).  A gate with t = 0 or without a gate
+        length relaxes nothing (F = 1: lambda is the default form's).  Readout is as in the default form."""
         props = backend.properties()
+        p1 = float(excited_state_population)
+        if not (math.isfinite(p1) and 0.0 <= p1 <= 1.0):
+            raise ValueError(f"NoiseModel.from_backend: excited_state_population = {excited_state_population!r}, want 0 <= p1 <= 1")
         lam: Dict[Tuple[str, Tuple[int, ...]], float] = {}
+        relax: Dict[Tuple[str, Tuple[int, ...]], Tuple[Tuple[float, float, float], ...]] = {}
+        times = [props.qubit_property(q) for q in range(len(props.qubits))] if thermal_relaxation else []
         for gate in props.gates:
             qubits = tuple(int(q) for q in gate.qubits)
             if len(qubits) not in (1, 2):
@@ -149,11 +231,31 @@ class NoiseModel:
             if err is None:
                 continue
             d = 2 ** len(qubits)
-            value = err * d / (d - 1)
+            if thermal_relaxation:
+                t = next((_apply_unit_prefix(float(p.value), p.unit) for p in gate.parameters if p.name == "gate_length"), 0.0)
+                if not (math.isfinite(t) and t >= 0.0):
+                    raise ValueError(f"NoiseModel.from_backend: gate_length {t!r} of {gate.gate} on {qubits}, want a finite time >= 0")
+                f_pro, triples = 1.0, []
+                for q in qubits:
+                    t1, t2 = (times[q].get(k, (math.inf, None))[0] for k in ("T1", "T2"))
+                    if not (t1 > 0.0 and t2 > 0.0):
+                        raise ValueError(f"NoiseModel.from_backend: qubit {q} has T1 = {t1!r}, T2 = {t2!r}, want both > 0")
+                    g, c = 1.0 - math.exp(-t / t1), math.exp(-t / min(t2, 2.0 * t1))
+                    triples.append((g, c, p1))
+                    f_pro *= (1.0 + 2.0 * c + (1.0 - g)) / 4.0
+                if t > 0.0:
+                    relax[(str(gate.gate), qubits)] = tuple(triples)
+                fid = (d * f_pro + 1.0) / (d + 1.0)
+                value = 0.0
+                if err > 1.0 - fid:
+                    value = min(d * (min(err, d / (d + 1.0)) - (1.0 - fid)) / (d * fid - 1.0), d * d / (d * d - 1.0))
+            else:
+                value = err * d / (d - 1)
             if not (math.isfinite(value) and 0.0 <= value <= 1.0):
                 raise ValueError(f"NoiseModel.from_backend: gate_error {err!r} of {gate.gate} on {qubits} gives lambda = {value!r}, "
                                  "want 0 <= lambda <= 1")
-            lam[(str(gate.gate), qubits)] = value
+            if value or not thermal_relaxation:
+                lam[(str(gate.gate), qubits)] = value
         ro: Dict[int, Tuple[float, float]] = {}
         if readout:
             for q in range(len(props.qubits)):
@@ -163,7 +265,28 @@ class NoiseModel:
                 p10 = qp.get("prob_meas1_prep0", (sym, None))[0]
                 ro[q] = (float(p01), float(p10))
         name = backend.name() if callable(getattr(backend, "name", None)) else getattr(backend, "name", "backend")
-        return NoiseModel(lam, ro, strict_two_qubit=True, name=str(name))
+        return NoiseModel(lam, ro, strict_two_qubit=True, name=str(name), gate_relaxation=relax)
+
+    def with_cx_over_rotation(self, theta: float, uniform: bool = True, seed: Optional[int] = None) -> "NoiseModel":
+        """A new model in which every calibrated ``cx (control, target)`` over-rotates: a controlled-RX(theta), controlled on
+        the cx's control and acting on its target, follows the gate and precedes its depolarising and relaxation part (so the
+        gate acts as ``I (x) |0><0| + i RX(pi + theta) (x) |1><1|``, the over-rotated CNOT of the reference's noise study).
+        ``uniform=False`` draws one angle ``theta_pair ~ U(0, theta)`` per calibrated direction, in the order of the table, from
+        ``numpy.random.default_rng(seed)``: this model's own stream, not the global one the reference seeds, so its angles are
+        not the reference's.  Everything else is copied."""
+        theta = float(theta)
+        if not math.isfinite(theta):
+            raise ValueError(f"NoiseModel.with_cx_over_rotation: theta = {theta!r}, want a finite angle")
+        pairs = [k for k in dict.fromkeys(list(self.gate_lambda) + list(self.gate_relaxation)) if k[0] == "cx" and len(k[1]) == 2]
+        rng = None if uniform else np.random.default_rng(seed)
+        coherent = dict(self.gate_coherent)
+        for key in pairs:
+            th = theta if uniform else float(rng.uniform(0.0, 1.0)) * theta
+            c, s = math.cos(th / 2), math.sin(th / 2)
+            m = np.eye(4, dtype=complex)   # basis index bit(control) + 2 bit(target): the rotation acts where the control is 1
+            m[1, 1], m[1, 3], m[3, 1], m[3, 3] = c, -1j * s, -1j * s, c
+            coherent[key] = m
+        return NoiseModel(self.gate_lambda, self.readout, self.strict_two_qubit, self.name, self.gate_relaxation, coherent)
 
 
 @dataclass
@@ -186,9 +309,11 @@ class SimBatch:
     # relative to op_ptr[c]; -1 = absent (``id`` has no gate record, a gate without noise no depolarising record)
     gate_ptr: Optional[np.ndarray] = None      # int64 [B + 1]: circuit c owns gates gate_ptr[c] .. gate_ptr[c + 1]
     gate_record: Optional[np.ndarray] = None   # int32 [n_gates]: the gate's own record
-    gate_noise: Optional[np.ndarray] = None    # int32 [n_gates]: the depolarising record after it
+    gate_noise: Optional[np.ndarray] = None    # int32 [n_gates]: the first noise record after it
     gate_name: Optional[np.ndarray] = None     # int16 [n_gates]: index of the gate's name in SUPPORTED_GATES
     gate_op: Optional[np.ndarray] = None       # int32 [n_gates]: index of the gate in the circuit's op list
+    # noise records after the gate's own, from gate_noise on: 0, 1 (DEPOL* or NOISE*) or 2 (a coherent U2, then DEPOL* / NOISE*)
+    gate_noise_len: Optional[np.ndarray] = None   # int32 [n_gates]
     # measurement (``compile_programs(..., shots=)``): the groups of qubit-wise commuting terms, one measurement basis each
     shots: Optional[int] = None
     group_ptr: Optional[np.ndarray] = None     # int64 [B + 1]: circuit c owns groups group_ptr[c] .. group_ptr[c + 1]
@@ -304,7 +429,8 @@ def compile_programs(circuits: Sequence[Any], observables: Sequence[Any], noise:
                      shots: Optional[int] = None) -> SimBatch:
     """Lowers ``circuits`` (anything ``Circuit.from_any`` takes) with one observable each (anything ``pauli_terms`` takes) to one
     :class:`SimBatch`.  ``noise=None``: state vectors (at most 11 qubits); a :class:`NoiseModel`: density matrices (at most 5
-    qubits) with its depolarising and readout ops.
+    qubits) with its noise records (a depolarising record after a gate as ever; where the model has thermal relaxation for the gate,
+    one fused ``NOISE1`` / ``NOISE2`` record in its place; before either, a ``U2`` record where it has a coherent error) and readout ops.
 
     Lowered: ``id x y z h s sdg t tdg sx sxdg rx ry rz p u1 u2 u3 u cx cz swap ecr rzz``; ``barrier`` is ignored; ``measure``
     records classical bit -> qubit (and gets the qubit's readout op, after every other op).  Raises ``ValueError`` naming the
@@ -329,7 +455,9 @@ def compile_programs(circuits: Sequence[Any], observables: Sequence[Any], noise:
     cap_q = MAX_QUBITS_DENSITY if density else MAX_QUBITS_VECTOR
     circ_rows, ops, params, op_ptr, term_rows, coeffs, term_ptr = [], [], [], [0], [], [], [0]
     variant, measured_all = [], []
-    gate_ptr, gate_record, gate_noise, gate_name, gate_op = [0], [], [], [], []
+    gate_ptr, gate_record, gate_noise, gate_name, gate_op, gate_noise_len = [0], [], [], [], [], []
+    # optional hooks: a duck-typed model with after_gate / readout_of alone lowers as it always did
+    relaxation_after, coherent_after = getattr(noise, "relaxation_after", None), getattr(noise, "coherent_after", None)
     group_ptr, term_group, prob_ptr, group_circ, group_basis = [0], [], [0], [], []
     name_id = {g: j for j, g in enumerate(SUPPORTED_GATES)}
 
@@ -392,15 +520,32 @@ def compile_programs(circuits: Sequence[Any], observables: Sequence[Any], noise:
                 if lowered is not None:
                     rec = len(ops) - first
                     emit_complex(lowered[0], q0, 0, lowered[1])
+            n_noise = 0
             if density:
-                lam = noise.after_gate(i, name, tuple(circ.qubit_reg_index[q] for q in op.qubits))
-                if lam is not None:
-                    if not (math.isfinite(lam) and 0.0 <= lam <= 1.0):
-                        raise ValueError(f"{where}: op {i} ({name}): depolarising parameter {lam!r}, want 0 <= lambda <= 1")
+                reg = tuple(circ.qubit_reg_index[q] for q in op.qubits)
+                lam = noise.after_gate(i, name, reg)
+                if lam is not None and not (math.isfinite(lam) and 0.0 <= lam <= 1.0):
+                    raise ValueError(f"{where}: op {i} ({name}): depolarising parameter {lam!r}, want 0 <= lambda <= 1")
+                coherent = coherent_after(i, name, reg) if coherent_after is not None else None
+                relax = relaxation_after(i, name, reg) if relaxation_after is not None else None
+                if coherent is not None:   # the coherent error: an ordinary U2 record, counted among the gate's noise records
+                    if width != 2:
+                        raise ValueError(f"{where}: op {i} ({name}): a coherent error is a 4x4 unitary, the gate has one qubit")
                     noi = len(ops) - first
+                    emit_complex(OP_U2, q0, q1, _check_coherent((name, reg), coherent).reshape(-1))
+                    n_noise += 1
+                if relax is not None:      # one fused record: depolarising (lambda = 0: none), then relaxation
+                    relax = _check_relaxation((name, reg), relax, width)
+                    noi = len(ops) - first if noi < 0 else noi
+                    emit(OP_NOISE2 if width == 2 else OP_NOISE1, q0, q1, [float(lam or 0.0)] + [v for t in relax for v in t])
+                    n_noise += 1
+                elif lam is not None:
+                    noi = len(ops) - first if noi < 0 else noi
                     emit(OP_DEPOL2 if width == 2 else OP_DEPOL1, q0, q1, [float(lam)])
+                    n_noise += 1
             gate_record.append(rec)
             gate_noise.append(noi)
+            gate_noise_len.append(n_noise)
             gate_name.append(name_id[name])
             gate_op.append(i)
         rows, cs, has_xy = _lower_terms(obs, n, where)
@@ -456,7 +601,7 @@ def compile_programs(circuits: Sequence[Any], observables: Sequence[Any], noise:
         n_wave=len(wave), n_wg=len(wg), variant=variant, measured=measured_all,
         gate_ptr=np.asarray(gate_ptr, dtype=np.int64), gate_record=np.asarray(gate_record, dtype=np.int32),
         gate_noise=np.asarray(gate_noise, dtype=np.int32), gate_name=np.asarray(gate_name, dtype=np.int16),
-        gate_op=np.asarray(gate_op, dtype=np.int32),
+        gate_op=np.asarray(gate_op, dtype=np.int32), gate_noise_len=np.asarray(gate_noise_len, dtype=np.int32),
         **({} if shots is None else dict(
             shots=shots, group_ptr=np.asarray(group_ptr, dtype=np.int64), term_group=np.asarray(term_group, dtype=np.int32),
             prob_ptr=np.asarray(prob_ptr, dtype=np.int64), group_circ=np.asarray(group_circ, dtype=np.int32),

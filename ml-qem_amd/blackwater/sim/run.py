@@ -9,7 +9,7 @@ import numpy as np
 
 from ..library.primitives import make_estimator_result
 from ..data.circuit import Circuit
-from .clifford import clifford_expectation_values, is_clifford
+from .clifford import clifford_expectation_values, is_clifford, refuse_non_pauli
 from .program import MAX_QUBITS_DENSITY, MAX_QUBITS_VECTOR, NoiseModel, SimBatch, check_seed, check_shots, compile_programs
 
 
@@ -209,12 +209,15 @@ class DeviceEstimator:
 
     def _use_clifford(self, circuits) -> bool:
         if self._method == "clifford":
+            refuse_non_pauli(self._noise, "DeviceEstimator(method='clifford')")
             return True
         cap = MAX_QUBITS_VECTOR if self._noise is None else MAX_QUBITS_DENSITY
         parsed = [Circuit.from_any(c) for c in circuits]
         over = [k for k, c in enumerate(parsed) if c.num_qubits > cap]
         if not over:
             return False
+        refuse_non_pauli(self._noise, f"DeviceEstimator(method='auto'): circuit {over[0]} has {parsed[over[0]].num_qubits} qubits, over the "
+                                      f"exact simulator's cap of {cap} in this mode, so the job needs the Clifford path")
         for k in over + [k for k in range(len(parsed)) if k not in over]:   # name a circuit that fits neither path first
             if not is_clifford(parsed[k]):
                 raise ValueError(f"DeviceEstimator(method='auto'): circuit {over[0]} has {parsed[over[0]].num_qubits} qubits, over the "

@@ -53,7 +53,7 @@ import numpy as np
 
 from ..data.circuit import Circuit, CircuitOp
 from ..library.primitives import make_estimator_result
-from .clifford import CliffordBatch, compile_clifford
+from .clifford import CliffordBatch, compile_clifford, refuse_non_pauli
 from .program import _TWO_QUBIT, SUPPORTED_GATES, NoiseModel, SimBatch, check_seed, check_shots, compile_programs
 
 _NOT_GATES = ("barrier", "measure")
@@ -278,13 +278,17 @@ def _name_table(amplifier: _Amplifier) -> np.ndarray:
 
 
 def _fold_entries(amplifier: _Amplifier, gate_ptr: np.ndarray, mask: np.ndarray, rec: np.ndarray, noi: np.ndarray, owner: np.ndarray,
-                  n_circ: int, noise_factor: float):
+                  n_circ: int, noise_factor: float, noi_len: Optional[np.ndarray] = None):
     """The fold units of one noise factor as schedule entries, shared by both record formats: ``(entries, body_len, achieved)``
-    with the entries of all circuits in running order (a unit's gate record with its dagger flag, then its depolarising record;
-    absent records left out) and their number per circuit."""
+    with the entries of all circuits in running order (a unit's gate record with its dagger flag, then its noise records, never
+    inverted: one depolarising or fused noise record, after a coherent-error record where the model has one; absent records left
+    out) and their number per circuit.  ``noi_len`` counts a gate's noise records (None: one where ``noi`` names one)."""
     unit_gate, unit_dagger, _, ach = _plan(amplifier, gate_ptr, mask, noise_factor)
     r, n = rec[unit_gate], noi[unit_gate]
-    entries = np.stack([np.where(r >= 0, (r << 1) | unit_dagger, -1), np.where(n >= 0, n << 1, -1)], axis=1)
+    columns = [np.where(r >= 0, (r << 1) | unit_dagger, -1), np.where(n >= 0, n << 1, -1)]
+    if noi_len is not None and noi_len.size and int(noi_len.max()) > 1:
+        columns.append(np.where((n >= 0) & (noi_len[unit_gate] > 1), (n + 1) << 1, -1))
+    entries = np.stack(columns, axis=1)
     valid = entries >= 0
     body_len = np.bincount(owner[unit_gate], weights=valid.sum(axis=1), minlength=n_circ).astype(np.int64)
     return entries[valid], body_len, ach
@@ -292,8 +296,9 @@ def _fold_entries(amplifier: _Amplifier, gate_ptr: np.ndarray, mask: np.ndarray,
 
 def build_schedules(batch: SimBatch, circuits: Optional[Sequence[Any]], noise_factors: Sequence[float], amplifier: _Amplifier) -> Schedules:
     """One schedule per (noise factor, circuit) from the record map ``compile_programs`` keeps (``batch.gate_*``).  A fold unit is
-    the gate's record followed by its depolarising record (either may be absent); the circuit's readout records follow every
-    schedule once.  ``circuits`` are the lowered circuits (only their number is checked: the map has everything).  numpy
+    the gate's record, possibly inverted, followed by its ``gate_noise_len`` noise records, never inverted (either may be absent):
+    the inverse of a gate carries the gate's own coherent error and noise again, which is how an over-rotated ``cx`` behaves when
+    it is folded.  The circuit's readout records follow every schedule once.  ``circuits`` are the lowered circuits (only their number is checked: the map has everything).  numpy
     throughout: no Python per entry."""
     if batch.gate_ptr is None:
         raise ValueError("build_schedules: the batch carries no record map (it was not made by compile_programs)")
@@ -311,9 +316,12 @@ def build_schedules(batch: SimBatch, circuits: Optional[Sequence[Any]], noise_fa
                  if n_circ else np.zeros(0, dtype=np.int64))
     readout = ((np.repeat(batch.op_counts - n_readout, n_readout) + _within(n_readout)) << 1).astype(np.int32)
     rec, noi = batch.gate_record.astype(np.int64), batch.gate_noise.astype(np.int64)
+    noi_len = None if batch.gate_noise_len is None else batch.gate_noise_len.astype(np.int64)
+    if noi_len is not None and noi_len.size and (int(noi_len.min()) < 0 or int(noi_len.max()) > 2):
+        raise ValueError(f"build_schedules: gate_noise_len holds {int(noi_len.min())} .. {int(noi_len.max())}, want 0, 1 or 2")
     pieces, lengths, achieved = [], [], []
     for lam in factors:
-        body, body_len, ach = _fold_entries(amplifier, batch.gate_ptr, mask, rec, noi, owner, n_circ, lam)
+        body, body_len, ach = _fold_entries(amplifier, batch.gate_ptr, mask, rec, noi, owner, n_circ, lam, noi_len)
         run_len = body_len + n_readout
         start = np.cumsum(run_len) - run_len
         piece = np.empty(int(run_len.sum()), dtype=np.int32)
@@ -335,11 +343,14 @@ def build_schedules(batch: SimBatch, circuits: Optional[Sequence[Any]], noise_fa
                      achieved=np.asarray(achieved, dtype=np.float64).reshape(len(factors), n_circ))
 
 
-def build_clifford_schedules(batch: CliffordBatch, noise_factors: Sequence[float], amplifier: _Amplifier) -> Schedules:
+def build_clifford_schedules(batch: CliffordBatch, noise_factors: Sequence[float], amplifier: _Amplifier, noise: Any = None) -> Schedules:
     """:func:`build_schedules` for the Clifford format (``mlqem_clifford_run_folded_f64``): one schedule per (noise factor, circuit)
     from the record map ``compile_clifford`` keeps.  A fold unit is the gate's record followed by its depolarising record (either
     may be absent; the inverse carries the gate's own depolarising record); there are no trailing entries, readout being no record
-    in this format, and no run numbers (``ids`` is empty: every unit of the batch walks every factor).  numpy throughout."""
+    in this format, and no run numbers (``ids`` is empty: every unit of the batch walks every factor).  numpy throughout.
+    ``noise``: the model the batch was lowered under, if the caller has it; one with thermal relaxation or a coherent error is
+    refused by name here too (``compile_clifford`` refuses it first: such a batch holds none of its records)."""
+    refuse_non_pauli(noise, "build_clifford_schedules")
     if batch.gate_ptr is None:
         raise ValueError("build_clifford_schedules: the batch carries no record map (it was not made by compile_clifford)")
     n_circ = len(batch)
@@ -576,7 +587,7 @@ def zne_run(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional
         if shots is not None:
             raise ValueError(_CLIFFORD_SHOTS)
         batch = compile_clifford(circuits, observables, noise)
-        sch = build_clifford_schedules(batch, strategy.noise_factors, strategy.noise_amplifier)
+        sch = build_clifford_schedules(batch, strategy.noise_factors, strategy.noise_amplifier, noise)
         t, s = batch.to(device), sch.to(device)
         ideal_values, noisy_values, ideal_terms, noisy_terms, _, _ = ops.clifford_run_folded(
             t["n_qubits"], t["op_ptr"], t["ops"], t["pool"], t["units"], t["n_reg"], t["n_lds"], t["masks"], t["term_ptr"], t["coeff"],

@@ -20,6 +20,8 @@
 //   gather     v = state[perm(i)], fence, state[i] = v                               cx, swap (row and column bits in one go)
 //   quad       a 4x4 matrix on bits (a, b); the one-qubit depolarising map on (q, q + n)
 //   hex        the two-qubit depolarising map on (a, b, a + n, b + n): 16 entries, closed form
+//   noise      NOISE1 / NOISE2: the depolarising map followed by thermal relaxation of the gate's qubits, fused into one quad or
+//              hex pass (a thread of noise2 takes one of the four 4-entry parts of a 4 x 4 block, so it holds what quad holds)
 // Expectation values are reduced in a fixed order: lane-strided partial sums, a shuffle tree, then the waves in order through LDS.
 //
 // Folded runs (mlqem_sim_run_folded_f64) are two more instantiations of the same template: a run walks a schedule of
@@ -194,6 +196,96 @@ template <bool WG> struct SimCtx {
     sim_sync<WG>();
   }
 
+  // thermal relaxation of one qubit on the two diagonal entries (a = rho_00, b = rho_11) of its 2x2 block: the population g of the
+  // block's trace is reset, 1 - p1 of it to |0> and p1 to |1>.  g = 0 multiplies by 1.0 and adds 0.0 * tr: an exact identity.
+  template <class V> static __device__ __forceinline__ void relax_diag(V& a, V& b, double stay, double to0, double to1) {
+    const V tr = a + b;
+    a = stay * a + to0 * tr;
+    b = stay * b + to1 * tr;
+  }
+
+  // one fused noise record on qubit q: depol1's closed form with lam, then relaxation (g, c, p1) of the same 2x2 block -- the
+  // diagonal through relax_diag, the two coherences times c.  One read and one write of the state.
+  __device__ __forceinline__ void noise1(int n, int q, double lam, double g, double c, double p1) {
+    const int ng = A >> 2, cb = q + n;
+    const double keep = 1.0 - lam, mix = 0.5 * lam, stay = 1.0 - g, to0 = g * (1.0 - p1), to1 = g * p1;
+    for (int g0 = 0; g0 < ng; g0 += T) {
+      const int gi = g0 + tid;
+      const bool live = gi < ng;
+      const int base = insert0(insert0(min(gi, ng - 1), q), cb);
+      const int i00 = base & (A - 1), i10 = (base | (1 << q)) & (A - 1), i01 = (base | (1 << cb)) & (A - 1),
+                i11 = (base | (1 << q) | (1 << cb)) & (A - 1);
+      const sim_c e00 = st[i00], e10 = st[i10], e01 = st[i01], e11 = st[i11];
+      const sim_c tr = e00 + e11;
+      sim_c d00 = keep * e00 + mix * tr, d11 = keep * e11 + mix * tr;
+      relax_diag(d00, d11, stay, to0, to1);
+      if (live) {
+        st[i00] = d00;
+        st[i10] = c * (keep * e10);
+        st[i01] = c * (keep * e01);
+        st[i11] = d11;
+      }
+    }
+    sim_sync<WG>();
+  }
+
+  // the same over the gate's pair: depol2's closed form with lam, then relaxation (g, c, p1) of qubit a (m[1..3]) and of qubit b
+  // (m[4..6]).  Relaxation of one qubit acts inside a fixed value of the other qubit's row and column bits, and it mixes two
+  // entries only where its own row and column bit agree (the populations); where they differ (the coherences) it scales.  So the
+  // 16 entries (ra, rb, ca, cb) of a 4 x 4 block fall into four parts of four that never meet, by whether a's bits agree and
+  // whether b's do, and a thread takes one PART, not one block: four entries x[ja + 2 jb] in registers, as in noise1, and every
+  // lane busy.  In a part the step along ja is relax_diag -- with (1 - g, g (1 - p1), g p1) where a's bits agree and with
+  // (c, 0, 0) where they differ (c x + 0.0 * tr: the scaling) -- and the same along jb.  Only the part where both agree holds the
+  // block's diagonal: its own four entries are the trace, and the other parts add 0.0 times theirs.  Every entry is read once
+  // and written once by the thread that owns it.
+  __device__ __forceinline__ void noise2(int n, int a, int b, const double* m) {
+    const int lo = min(a, b), hi = max(a, b), nu = A >> 2;   // units: (block, part)
+    const int ra = 1 << a, rb = 1 << b, ca = 1 << (a + n), cb = 1 << (b + n);
+    for (int u0 = 0; u0 < nu; u0 += T) {
+      const int u = u0 + tid;
+      const bool live = u < nu;
+      const int uc = min(u, max(nu - 1, 0));
+      const bool off_a = uc & 1, off_b = uc & 2;   // the part: a's (b's) row and column bit differ
+      const int base = insert0(insert0(insert0(insert0(uc >> 2, lo), hi), lo + n), hi + n);
+      int idx[4];
+      sim_c x[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int ja = k & 1, jb = k >> 1;
+        const int bits_a = off_a ? (ja ? ca : ra) : (ja ? ra | ca : 0), bits_b = off_b ? (jb ? cb : rb) : (jb ? rb | cb : 0);
+        idx[k] = (base | bits_a | bits_b) & (A - 1);
+        x[k] = st[idx[k]];
+      }
+      const double lam = m[0], keep = 1.0 - lam, mix = off_a || off_b ? 0.0 : 0.25 * lam;
+      const double ga = m[1], stay_a = off_a ? m[2] : 1.0 - ga, to1_a = off_a ? 0.0 : ga * m[3], to0_a = off_a ? 0.0 : ga * (1.0 - m[3]);
+      const double gb = m[4], stay_b = off_b ? m[5] : 1.0 - gb, to1_b = off_b ? 0.0 : gb * m[6], to0_b = off_b ? 0.0 : gb * (1.0 - m[6]);
+      // the maps are real: the real parts, then the imaginary parts, each four doubles updated in place
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        double v0 = h ? x[0].y : x[0].x, v1 = h ? x[1].y : x[1].x, v2 = h ? x[2].y : x[2].x, v3 = h ? x[3].y : x[3].x;
+        const double tr = ((v0 + v1) + v2) + v3;
+        v0 = keep * v0 + mix * tr;
+        v1 = keep * v1 + mix * tr;
+        v2 = keep * v2 + mix * tr;
+        v3 = keep * v3 + mix * tr;
+        relax_diag(v0, v1, stay_a, to0_a, to1_a);
+        relax_diag(v2, v3, stay_a, to0_a, to1_a);
+        relax_diag(v0, v2, stay_b, to0_b, to1_b);
+        relax_diag(v1, v3, stay_b, to0_b, to1_b);
+        if (h) {
+          x[0].y = v0, x[1].y = v1, x[2].y = v2, x[3].y = v3;
+        } else {
+          x[0].x = v0, x[1].x = v1, x[2].x = v2, x[3].x = v3;
+        }
+      }
+      if (live) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) st[idx[k]] = x[k];
+      }
+    }
+    sim_sync<WG>();
+  }
+
   // fixed-order sum of one double per thread: a shuffle tree, then wave 0 .. 3 in order.  Thread 0 holds the result (every thread of
   // the workgroup variant does).  `slot` alternates between two sets of wave sums, so one barrier per reduction is enough.
   __device__ __forceinline__ double reduce(double part, int slot) {
@@ -214,8 +306,12 @@ template <bool WG> struct SimCtx {
 // (basis rotations / MEASURE / inverse rotations per group) after its readout ops, norm is taken before the readout ops AND the
 // tail, and a MEASURE record stores the state's outcome probabilities -- one pass that reads the state and leaves it as it is.  The
 // MEAS = false instantiations never read the five trailing arguments and compile to the instructions they had without them.
+//
+// Occupancy.  The wave variants are bound by registers (7 waves per SIMD plain, 6 folded), the workgroup variants by their 32 KB of
+// LDS (4).  amdgpu_waves_per_eu states those figures, so that a pass added to the switch cannot lower them unnoticed: the compiler
+// keeps each instantiation inside the register budget of its figure, and a pass that does not fit shows up as scratch.
 template <bool WG, bool FOLD, bool MEAS = false>
-__global__ __launch_bounds__(kBlock) void sim_kernel(int B, const sim_i4* __restrict__ circ, const int64_t* __restrict__ op_ptr,
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WG ? 4 : FOLD ? 6 : 7))) void sim_kernel(int B, const sim_i4* __restrict__ circ, const int64_t* __restrict__ op_ptr,
                                                      const sim_i4* __restrict__ ops, int64_t n_ops,
                                                      const double* __restrict__ params, int64_t n_params,
                                                      const int64_t* __restrict__ term_ptr, const sim_i4* __restrict__ terms,
@@ -367,6 +463,12 @@ __global__ __launch_bounds__(kBlock) void sim_kernel(int B, const sim_i4* __rest
       case MLQEM_SIM_OP_READOUT:
         if (density)   // [[1 - p10, p01], [p10, 1 - p01]] on bit q0 of the diagonal; m = (p01, p10)
           cx.pair(n, q0, sim_c{1.0 - m[1], 0.0}, sim_c{m[0], 0.0}, sim_c{m[1], 0.0}, sim_c{1.0 - m[0], 0.0}, (1 << n) + 1);
+        break;
+      case MLQEM_SIM_OP_NOISE1:   // never inverted: a schedule's dagger bit is ignored, as for the depolarising kinds
+        if (density) cx.noise1(n, q0, m[0], m[1], m[2], m[3]);
+        break;
+      case MLQEM_SIM_OP_NOISE2:
+        if (density) cx.noise2(n, q0, q1, m);
         break;
       default:
         break;

@@ -1523,6 +1523,86 @@ int mlqem_sim_sample_f64(int64_t n_circuits, int64_t n_factors, const int32_t* c
                          double* variance, mlqem_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Quantum trajectories on the simulator (an additive symbol, the ABI version is unchanged).  A noisy circuit of 6 .. 11 qubits has
+ * no density matrix that fits the 2 048-amplitude state, but its state VECTOR fits.  mlqem_sim_run_trajectories_f64 runs every
+ * circuit as T = `trajectories` pure-state trajectories: at every noise record it draws ONE Kraus operator and applies it, and the
+ * averages over the trajectories estimate the values under the noise model.  blackwater.sim lowers for it
+ * (compile_programs(..., trajectories=)) and blackwater.native.ops.sim_run_trajectories calls it.
+ *
+ * Input.  The buffers of mlqem_sim_run_f64, with the records density mode (mode 1) emits, and circ[c] = (n_qubits, 2, r, 0): mode 2,
+ * TRAJECTORY mode, n <= 11, the state a 2^n vector.  The kernels here do not read the mode field (the other entry points read
+ * mode != 0 as a density matrix, so the host refuses to hand them such a batch).  ids int32 [n_wave + n_wg] with
+ * n_wave + n_wg == n_circuits: every circuit is run; the first n_wave have at most 256 amplitudes.  run_keys int64 [n_circuits];
+ * seed uint64; 1 <= trajectories <= MLQEM_SIM_MAX_TRAJECTORIES = 2^20.
+ *
+ * Work unit: one (circuit, trajectory) pair; a wave per unit (four per workgroup, no workgroup barrier) where 2^n <= 256, else a
+ * workgroup per unit; the wave units of the batch come first (one launch each).  Unit u of a launch is trajectory u % T of the
+ * launch's circuit ids[u / T].  The rules of mlqem_sim_run_f64 hold: loads unconditional on clamped and masked indices, stores
+ * predicated, trip counts that depend on the amplitude count alone, a malformed record computes garbage and faults nothing.
+ *
+ * Records.  Record k of circuit c (k counted from op_ptr[c]), k < n_ops(c) - r:
+ *   U1, DIAG1, CX, CZ, SWAP, U2   as in mode 0 (a coherent error is an ordinary U2 record).
+ *   DEPOL1 (lambda) on q0.  lambda == 0: nothing.  Else one uniform u = U(k, 0).  w = lambda / 4; s_0 = 1 - 3 w; s_j = s_(j-1) + w.
+ *           The outcome is the first j in 0 .. 3 with s_j > u, else 3.  j = 0: identity, NO pass.  j = 1, 2, 3: the Pauli X, Y, Z
+ *           on q0, one pass.
+ *   DEPOL2 (lambda) on (q0, q1).  The same with w = lambda / 16, s_0 = 1 - 15 w, j in 0 .. 15.  The pair's code: j = l0 + 4 l1 with
+ *           the letter l0 on q0 and l1 on q1, letters 0 = I, 1 = X, 2 = Y, 3 = Z (j = 0 is the identity; j = 1 is X on q0; j = 4 is
+ *           X on q1; j = 15 is Z Z).
+ *           A Pauli string acts as P|i> = i^ny (-1)^popcount(i & z) |i ^ x> (x: the X and Y letters, z: the Z and Y letters, ny: the
+ *           number of Y): components are swapped and negated, nothing is rounded.  The probabilities do not depend on the state,
+ *           so no norm is computed.
+ *   Relaxation (g, c, p1) of ONE qubit q with sub-draw s.  One pass forms P0 and P1, the sums of |psi_i|^2 over the i with bit q
+ *           clear and set (lane-strided partial sums over the pairs (i, i | 1 << q) in pair order, the shuffle tree, the waves in
+ *           order: the reduction order of every sum here).  pa = P0 / (P0 + P1), pb = P1 / (P0 + P1).  c2 = c c,
+ *           d = max(0, (1 - g) - c2).  Six outcomes, in this order, with their probabilities:
+ *             0  K0  = diag(1, c)          (1 - p1) (pa + c2 pb)
+ *             1  K1  = sqrt(g) |0><1|      (1 - p1) (g pb)
+ *             2  K2  = sqrt(d) |1><1|      (1 - p1) (d pb)
+ *             3  K0' = diag(c, 1)          p1 (c2 pa + pb)
+ *             4  K1' = sqrt(g) |1><0|      p1 (g pa)
+ *             5  K2' = sqrt(d) |0><0|      p1 (d pa)
+ *           One uniform u = U(k, s); s_j = s_(j-1) + probability_j from s_(-1) = 0; the outcome is the first j with s_j > u, and
+ *           if rounding leaves none, the last j whose probability is > 0.  An outcome of probability exactly 0 is never chosen.
+ *           The state is multiplied by the operator over the square root of ITS OWN probability given the state (the weight
+ *           1 - p1 or p1 left out), a real 2x2 matrix on bit q, one pair pass: with t = 1 / sqrt(.),
+ *             0: diag(t, c t), t from pa + c2 pb      1: t |0><1|, t from pb      2: t |1><1|, t from pb
+ *             3: diag(c t, t), t from c2 pa + pb      4: t |1><0|, t from pa      5: t |0><0|, t from pa
+ *           (g and d cancel in the jumps).  <psi|psi> keeps its value up to rounding.  Averaged over u this is the map of
+ *           MLQEM_SIM_OP_NOISE1's relaxation part: populations (1 - g) rho + g tr (1 - p1, p1), coherences times c; completely
+ *           positive exactly where the host demands c <= sqrt(1 - g).
+ *   NOISE1 (lambda, g, c, p1) on q0.  DEPOL1's draw with sub-draw 0 (skipped at lambda == 0), then relaxation of q0, sub-draw 1.
+ *   NOISE2 (lambda, (g, c, p1) of q0, (g, c, p1) of q1).  DEPOL2's draw (sub-draw 0, skipped at lambda == 0), relaxation of q0
+ *           (sub-draw 1), relaxation of q1 (sub-draw 2); each step takes its populations from the state the step before left.
+ *   The LAST r records (READOUT: p01, p10 on q0) are not applied to the state.  They fill a table r[q] = (1 - 2 p10, -(1 - 2 p01)),
+ *           default (+1, -1).  Where r > 0, a term with xmask == 0 is  sum_i |psi_i|^2 prod_(q in zmask, ascending) r[q][bit q of i],
+ *           the exact expectation under the readout channel (no sampling); every other term, and every term where r == 0, is
+ *           mode 0's formula.  (The host refuses readout noise beside a term with X or Y.)
+ *
+ * Randomness.  U(k, s) of trajectory t: Philox4x32-10 with the key (seed & 0xffffffff, seed >> 32) and the counter
+ *   (k,  s << 24 | t,  run_key & 0xffffffff,  run_key >> 32),   run_key = run_keys[c], t < 2^20, s in {0, 1, 2};
+ * of its words x0 .. x3, u = ((x0 >> 5) 2^26 + (x1 >> 6)) 2^-53, as in mlqem_sim_sample_f64.  Every lane computes the same u, so
+ * every branch on a draw is uniform over the unit.  A trajectory therefore depends on (seed, run key, t, the circuit's records)
+ * alone: not on the batch, not on the unit's slot, not on T (the first T trajectories of a longer run are the same bits).
+ *
+ * Outputs, float64.  Per unit: traj_term_values [T][n_terms] (row t: the term values of trajectory t, mode 0's reduction) and
+ * traj_norm [T][n_circuits], <psi|psi> after the last record.  Then one finish launch, sums in trajectory order t = 0 .. T - 1 from
+ * 0.0: term_values [n_terms] = the mean (sum / T); term_std_error [n_terms] = sqrt(M2 / (T (T - 1))) with M2 = sum (x_t - mean)^2
+ * (a second pass, a fused multiply-add per trajectory), 0 at T == 1; values [n_circuits] and std_error [n_circuits] the same over
+ * the per-trajectory value v_t = sum coeff * term in term order (a fused multiply-add per term, from 0.0); norm [n_circuits] = the
+ * mean of traj_norm.  Values are NOT divided by the norm.  At most three launches; no atomics, no host read: capturable.
+ * Negative sizes, trajectories outside 1 .. 2^20, n_wave + n_wg != n_circuits, n_params < 32, a null or misaligned buffer:
+ * MLQEM_ERR_BAD_ARG; n_circuits, n_params, n_terms or n_circuits * trajectories over 2^31 - 1: MLQEM_ERR_UNSUPPORTED; all checked
+ * before anything is launched.  n_circuits == 0: MLQEM_OK without a launch.
+ * ---------------------------------------------------------------------------------------------------- */
+#define MLQEM_SIM_MAX_TRAJECTORIES 1048576
+int mlqem_sim_run_trajectories_f64(int64_t n_circuits, const int32_t* circ, const int64_t* op_ptr, const mlqem_sim_op* ops,
+                                   int64_t n_ops, const double* params, int64_t n_params, const int64_t* term_ptr,
+                                   const mlqem_sim_term* terms, const double* coeff, int64_t n_terms, const int32_t* ids,
+                                   int64_t n_wave, int64_t n_wg, const int64_t* run_keys, int64_t trajectories, uint64_t seed,
+                                   double* traj_term_values, double* traj_norm, double* term_values, double* term_std_error,
+                                   double* values, double* std_error, double* norm, mlqem_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * Clifford circuits of up to MLQEM_CLIFFORD_MAX_QUBITS = 512 qubits, a batch per call (an additive symbol, the ABI version is
  * unchanged).  A Pauli observable is carried BACKWARDS through a Clifford circuit as a Pauli, so its ideal value on |0..0> and its
  * value under the project's depolarising model come from one walk over the records, in O(records) bit operations per (circuit,

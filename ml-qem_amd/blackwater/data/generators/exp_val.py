@@ -62,7 +62,7 @@ class ExpValueEntry:
 
 def exp_value_generator(backend: Any, n_qubits: int, circuit_depth: int, pauli_terms: int, pauli_coeff: float = 1.0,
                         max_entries: int = 1000, seed: int = 0, batch: int = 256, device="cuda", shots: Optional[int] = None,
-                        sample_ideal: bool = False) -> Iterator[ExpValueEntry]:
+                        sample_ideal: bool = False, trajectories: Optional[int] = None) -> Iterator[ExpValueEntry]:
     """Yields ``max_entries`` dataset entries of random circuits with simulated labels (reference: exp_val.py:92-170, which
     transpiles ``qiskit.circuit.random.random_circuit`` and runs Aer twice per circuit).
 
@@ -77,7 +77,14 @@ def exp_value_generator(backend: Any, n_qubits: int, circuit_depth: int, pauli_t
     ``shots`` (default ``None``: exact labels): the noisy value is estimated from that many measurement outcomes per measurement
     basis, drawn on the device (``sim.sample_expectation_values``; the reference's labels are 10 000-shot estimates), and with
     ``sample_ideal=True`` the ideal one too.  The draws are keyed by ``seed`` and the entry's number, so an entry is still a
-    function of ``seed`` (and ``shots``) alone, whatever ``batch`` is."""
+    function of ``seed`` (and ``shots``) alone, whatever ``batch`` is.
+
+    ``trajectories`` (default ``None``): the noisy value is the mean over that many quantum trajectories
+    (``sim.trajectory_expectation_values``), which reaches ``n_qubits`` of 6 to 11 where the density-matrix mode stops at 5; the
+    ideal value stays the exact state-vector one.  The draws are keyed as the shots are, so an entry is a function of ``seed`` and
+    ``trajectories`` alone, whatever ``batch`` is.  ``trajectories`` together with ``shots`` is refused."""
+    if trajectories is not None and shots is not None:
+        raise ValueError("exp_value_generator: trajectories together with shots (shot sampling over trajectories is not supported)")
     from ... import sim
     from ..synthetic import random_circuit
     from ..utils import circuit_to_graph_data_json, encode_pauli_sum_op, generate_random_pauli_sum_op, get_backend_properties_v1
@@ -98,7 +105,12 @@ def exp_value_generator(backend: Any, n_qubits: int, circuit_depth: int, pauli_t
             depth = int(rng.integers(1, circuit_depth + 1))
             circuits.append(random_circuit(n_qubits, depth, int(rng.integers(0, 2 ** 31 - 1)), two_q=two_q[0]))
             observables.append(generate_random_pauli_sum_op(n_qubits, pauli_terms, pauli_coeff, rng=rng))
-        if shots is None:
+        if trajectories is not None:
+            keys = np.arange(done, done + count, dtype=np.int64)   # the entry's number, as on the shots path
+            ideal = _to_host(sim.expectation_values(circuits, observables, None, device)[0])
+            noisy = _to_host(sim.trajectory_expectation_values(circuits, observables, noise, trajectories=trajectories, seed=seed,
+                                                               run_keys=keys, device=device).values)
+        elif shots is None:
             ideal = _to_host(sim.expectation_values(circuits, observables, None, device)[0])
             noisy = _to_host(sim.expectation_values(circuits, observables, noise, device)[0])
         else:

@@ -162,7 +162,7 @@ def pauli_twirl(circ: Circuit, seed: int, two_q=("cx", "ecr")) -> Circuit:
 
 def encode_corpus(circuits, nq: int, two_q: str = "cx", seed: int = 7, exp_value_size: int = 1,
                   add_self_loops: bool = True, simulate=None, device="cuda", shots=None, sample_ideal: bool = False,
-                  clifford: bool = False) -> Dict[str, list]:
+                  clifford: bool = False, trajectories=None) -> Dict[str, list]:
     """Arena-ready arrays (same keys as :func:`tfim_corpus`) for arbitrary circuits, encoded by the native encoder.
 
     ``simulate=None``: synthetic labels (a uniform draw and a made-up decay).  ``simulate=`` a ``blackwater.sim.NoiseModel``: ``y``
@@ -171,7 +171,10 @@ def encode_corpus(circuits, nq: int, two_q: str = "cx", seed: int = 7, exp_value
     unless ``clifford=True``: then every larger circuit that is a Clifford circuit of at most 512 qubits (``sim.is_clifford``) gets its
     exact and noisy ``<Z>`` from ``sim.clifford_expectation_values``, in one call (exact values only: ``shots`` with it is refused).
     ``shots`` (with ``simulate``; default ``None``: exact): the noisy value is a ``shots``-shot estimate drawn on the device with
-    ``seed`` (``sim.sample_expectation_values``), and with ``sample_ideal=True`` the ideal one too."""
+    ``seed`` (``sim.sample_expectation_values``), and with ``sample_ideal=True`` the ideal one too.
+    ``trajectories`` (with ``simulate``; default ``None``): the noisy value is the mean over that many quantum trajectories
+    (``sim.trajectory_expectation_values``, keyed by ``seed`` and the circuit's position), and the cap of the simulated circuits
+    rises from 5 to 11 qubits; the ideal value stays the exact one.  ``trajectories`` together with ``shots`` is refused."""
     from .circuit import circuit_to_qasm
     from .native_encoder import NativeEncoder
 
@@ -203,10 +206,15 @@ def encode_corpus(circuits, nq: int, two_q: str = "cx", seed: int = 7, exp_value
         raise ValueError("encode_corpus: clifford=True fills simulated labels, so it needs simulate= (a noise model)")
     if clifford and shots is not None:
         raise ValueError("encode_corpus: clifford=True gives exact values only; shots are not drawn on the Clifford path")
+    if trajectories is not None and simulate is None:
+        raise ValueError("encode_corpus: trajectories fill simulated labels, so they need simulate= (a noise model)")
+    if trajectories is not None and shots is not None:
+        raise ValueError("encode_corpus: trajectories together with shots (shot sampling over trajectories is not supported)")
     if simulate is not None:
         from .. import sim
 
-        wide = [k for k, circ in enumerate(kept) if clifford and sim.MAX_QUBITS_DENSITY < circ.num_qubits <= sim.MAX_QUBITS_CLIFFORD
+        cap = sim.MAX_QUBITS_DENSITY if trajectories is None else sim.MAX_QUBITS_VECTOR
+        wide = [k for k, circ in enumerate(kept) if clifford and cap < circ.num_qubits <= sim.MAX_QUBITS_CLIFFORD
                 and sim.is_clifford(circ)]
         if wide:
             labels = ["".join("Z" if q == z_qubits[k] else "I" for q in reversed(range(kept[k].num_qubits))) for k in wide]
@@ -215,11 +223,16 @@ def encode_corpus(circuits, nq: int, two_q: str = "cx", seed: int = 7, exp_value
             for j, k in enumerate(wide):
                 ys[k] = np.full(exp_value_size, exact[j])
                 noisy[k] = np.full(exp_value_size, under[j])
-        inside = [k for k, circ in enumerate(kept) if 1 <= circ.num_qubits <= sim.MAX_QUBITS_DENSITY]
+        inside = [k for k, circ in enumerate(kept) if 1 <= circ.num_qubits <= cap]
         if inside:
             labels = ["".join("Z" if q == z_qubits[k] else "I" for q in reversed(range(kept[k].num_qubits))) for k in inside]
             batch = [kept[k] for k in inside]
-            if shots is None:
+            if trajectories is not None:
+                keys = np.asarray(inside, dtype=np.int64)   # the circuit's position in the corpus, as on the shots path
+                exact = sim.expectation_values(batch, labels, None, device)[0].cpu().numpy()
+                under = sim.trajectory_expectation_values(batch, labels, simulate, trajectories=trajectories, seed=seed, run_keys=keys,
+                                                          device=device).values.cpu().numpy()
+            elif shots is None:
                 exact = sim.expectation_values(batch, labels, None, device)[0].cpu().numpy()
                 under = sim.expectation_values(batch, labels, simulate, device)[0].cpu().numpy()
             else:

@@ -2872,6 +2872,61 @@ def sim_sample(circ, term_ptr, terms, coeff, group_ptr, term_group, prob_ptr, gr
     return values, variance, term_values, counts
 
 
+SIM_MAX_TRAJECTORIES = 2 ** 20   # MLQEM_SIM_MAX_TRAJECTORIES
+
+
+def sim_run_trajectories(circ, op_ptr, ops, params, term_ptr, terms, coeff, ids, n_wave, n_wg, run_keys, trajectories, seed, *,
+                         traj_term_values=None, traj_norm=None, term_values=None, term_std_error=None, values=None, std_error=None,
+                         norm=None):
+    """Runs every circuit of a batch lowered in trajectory mode (``compile_programs(..., trajectories=)``) as ``trajectories``
+    pure-state trajectories (mlqem_sim_run_trajectories_f64): ``(values, std_error, term_values, term_std_error, norm,
+    traj_term_values, traj_norm)``, float64 [B], [B], [n_terms], [n_terms], [B], [T, n_terms], [T, B].
+
+    The first eight buffers are :func:`sim_run`'s; ``n_wave + n_wg`` must be B (every circuit is run); ``run_keys`` int64 [B], the
+    Philox counter words of every circuit; ``trajectories`` in 1 .. 2^20; ``seed`` in 0 .. 2^64 - 1.  include/mlqem_hip.h states
+    the unravelling and the counter layout: a trajectory's bits depend on (seed, run key, trajectory, circuit) alone.  The means and
+    standard errors are formed on the device in trajectory order.  Nothing here waits for the device or reads a tensor, and with
+    the seven outputs given nothing is allocated: capturable.  There is no CPU path."""
+    for t, name, dtype, cols in ((circ, "circ", torch.int32, 4), (ops, "ops", torch.int32, 4), (terms, "terms", torch.int32, 4)):
+        if not t.is_cuda:
+            raise _lib.NativeLibraryError(f"{name} must live on the GPU (got {t.device}); there is no CPU path")
+        if t.dtype != dtype or t.dim() != 2 or t.shape[1] != cols or not t.is_contiguous():
+            raise ValueError(f"sim: want contiguous {dtype} {name} [., {cols}], got {tuple(t.shape)} {t.dtype}")
+    b, n_ops, n_terms = int(circ.shape[0]), int(ops.shape[0]), int(terms.shape[0])
+    n_wave, n_wg, n_traj, seed = int(n_wave), int(n_wg), int(trajectories), int(seed)
+    if not 1 <= n_traj <= SIM_MAX_TRAJECTORIES:
+        raise ValueError(f"sim: trajectories = {n_traj}, want 1 .. 2^20")
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError(f"sim: seed = {seed}, want 0 .. 2^64 - 1")
+    if n_wave < 0 or n_wg < 0 or n_wave + n_wg != b:
+        raise ValueError(f"sim: n_wave = {n_wave} and n_wg = {n_wg} must be >= 0 and add up to the {b} circuits")
+    if b * n_traj > 2 ** 31 - 1:
+        raise ValueError(f"sim: {b} circuits x {n_traj} trajectories exceed the 2^31 - 1 units one call can take; split the batch")
+    _vec(op_ptr, "op_ptr", b + 1, torch.int64)
+    _vec(term_ptr, "term_ptr", b + 1, torch.int64)
+    _vec(params, "params", SIM_PARAM_PAD, torch.float64)
+    _vec(coeff, "coeff", n_terms, torch.float64)
+    _vec(ids, "ids", b, torch.int32)
+    _vec(run_keys, "run_keys", b, torch.int64)
+    if op_ptr.shape[0] != b + 1 or term_ptr.shape[0] != b + 1 or coeff.shape[0] != n_terms or run_keys.shape[0] != b or ids.shape[0] != b:
+        raise ValueError(f"sim: want op_ptr and term_ptr [{b + 1}], coeff [{n_terms}], ids and run_keys [{b}], got {tuple(op_ptr.shape)}, "
+                         f"{tuple(term_ptr.shape)}, {tuple(coeff.shape)}, {tuple(ids.shape)} and {tuple(run_keys.shape)}")
+    dev = circ.device
+    if any(t.device != dev for t in (op_ptr, ops, params, term_ptr, terms, coeff, ids, run_keys)):
+        raise ValueError(f"sim: circ is on {dev}, another buffer is not")
+    traj_term_values = _sim_out(traj_term_values, "traj_term_values", (n_traj, n_terms), dev)
+    traj_norm = _sim_out(traj_norm, "traj_norm", (n_traj, b), dev)
+    term_values, term_std_error = _sim_out(term_values, "term_values", (n_terms,), dev), _sim_out(term_std_error, "term_std_error", (n_terms,), dev)
+    values, std_error, norm = _sim_out(values, "values", (b,), dev), _sim_out(std_error, "std_error", (b,), dev), _sim_out(norm, "norm", (b,), dev)
+    code = _lib.load().mlqem_sim_run_trajectories_f64(
+        b, _p(circ), _p(op_ptr), _p(ops) if n_ops else None, n_ops, _p(params), int(params.shape[0]), _p(term_ptr),
+        _p(terms) if n_terms else None, _p(coeff) if n_terms else None, n_terms, _p(ids), n_wave, n_wg, _p(run_keys), n_traj, seed,
+        _p(traj_term_values) if n_terms else None, _p(traj_norm), _p(term_values) if n_terms else None,
+        _p(term_std_error) if n_terms else None, _p(values), _p(std_error), _p(norm), _stream())
+    _lib.check(code, "mlqem_sim_run_trajectories_f64")
+    return values, std_error, term_values, term_std_error, norm, traj_term_values, traj_norm
+
+
 CLIFFORD_MAX_QUBITS = 512   # MLQEM_CLIFFORD_MAX_QUBITS
 CLIFFORD_REG_QUBITS = 128   # MLQEM_CLIFFORD_REG_QUBITS: units of circuits up to here keep their Pauli words in registers
 CLIFFORD_PAD = 32           # entries of padding `pool` and `masks` end with

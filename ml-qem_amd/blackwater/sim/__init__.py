@@ -1,16 +1,20 @@
 """Batched exact simulation of small circuits on the device: ideal (state vector) and noisy (density matrix) expectation values,
 the labels the mitigators learn from.  ``compile_programs`` / ``NoiseModel`` / ``measured_z`` run on the host alone.  ``blackwater.sim.zne`` (also ``blackwater.zne``) is
 zero-noise extrapolation on it; the ``zne(cls)`` decorator lives there, so that ``sim.zne`` stays the module.
+``run_trajectories`` / ``trajectory_expectation_values`` are the path for NOISY circuits of 6 to 11 qubits (any gate, any
+``NoiseModel``): pure-state quantum trajectories, a mean and its standard error.
 ``blackwater.sim.clifford`` is the path for wide circuits: Clifford circuits of up to 512 qubits, ideal and noisy, by carrying the
 observable backwards through the circuit (``compile_clifford`` / ``clifford_expectation_values``); ``zne_run(..., method="clifford")``
 extrapolates there too (``build_clifford_schedules``, ``ExponentialExtrapolator``)."""
 from .program import (MAX_AMPS, MAX_QUBITS_DENSITY, MAX_QUBITS_VECTOR, SUPPORTED_GATES, WAVE_AMPS, NoiseModel, SimBatch,
                       compile_programs, measured_z)
 from .program import MAX_SHOTS, measurement_groups
+from .program import MAX_TRAJECTORIES
 from .clifford import (MAX_QUBITS_CLIFFORD, CliffordBatch, clifford_expectation_values, compile_clifford, invert_table, is_clifford,
                        run_clifford, run_clifford_folded)
 from .run import (DeviceEstimator, SampleResult, SimulatedJob, counts_dicts, default_run_keys, expectation_values, run_batch,
                   sample_batch, sample_expectation_values)
+from .run import TrajectoryResult, run_trajectories, trajectory_expectation_values
 from .zne import (CubicExtrapolator, CxAmplifier, ExponentialExtrapolator, GlobalFoldingAmplifier, LinearExtrapolator, LocalFoldingAmplifier,
                   PolynomialExtrapolator, QuadraticExtrapolator, QuarticExtrapolator, RichardsonExtrapolator, Schedules,
                   TwoQubitAmplifier, ZNEStrategy, build_clifford_schedules, build_schedules, fold_circuit, zne_expectation_values,
@@ -23,4 +27,5 @@ __all__ = ["MAX_AMPS", "MAX_QUBITS_DENSITY", "MAX_QUBITS_VECTOR", "SUPPORTED_GAT
            "TwoQubitAmplifier", "ZNEStrategy", "build_schedules", "fold_circuit", "zne_expectation_values", "zne_run",
            "MAX_SHOTS", "measurement_groups", "SampleResult", "counts_dicts", "default_run_keys", "sample_batch",
            "sample_expectation_values", "MAX_QUBITS_CLIFFORD", "CliffordBatch", "clifford_expectation_values", "compile_clifford",
-           "is_clifford", "run_clifford", "ExponentialExtrapolator", "build_clifford_schedules", "invert_table", "run_clifford_folded"]
+           "is_clifford", "run_clifford", "ExponentialExtrapolator", "build_clifford_schedules", "invert_table", "run_clifford_folded",
+           "MAX_TRAJECTORIES", "TrajectoryResult", "run_trajectories", "trajectory_expectation_values"]

@@ -24,6 +24,8 @@ MAX_QUBITS_VECTOR = 11
 MAX_QUBITS_DENSITY = 5
 
 MAX_SHOTS = 2 ** 20  # MLQEM_SIM_MAX_SHOTS: counts are int32 and a Philox counter word holds shot >> 1
+MAX_TRAJECTORIES = 2 ** 20  # MLQEM_SIM_MAX_TRAJECTORIES: a Philox counter word holds sub-draw << 24 | trajectory
+MODE_TRAJECTORY = 2  # circ[c, 1] of a batch lowered for mlqem_sim_run_trajectories_f64
 
 OP_U1, OP_DIAG1, OP_CX, OP_CZ, OP_SWAP, OP_U2, OP_DEPOL1, OP_DEPOL2, OP_READOUT, OP_MEASURE = range(10)   # MLQEM_SIM_OP_*
 OP_NOISE1, OP_NOISE2 = 10, 11   # the fused noise records: depolarising, then thermal relaxation of the gate's qubits
@@ -241,6 +243,7 @@ class NoiseModel:
                     if not (t1 > 0.0 and t2 > 0.0):
                         raise ValueError(f"NoiseModel.from_backend: qubit {q} has T1 = {t1!r}, T2 = {t2!r}, want both > 0")
                     g, c = 1.0 - math.exp(-t / t1), math.exp(-t / min(t2, 2.0 * t1))
+                    c = min(c, math.sqrt(1.0 - g))   # T2 capped at 2 T1 is c = sqrt(1 - g) up to rounding: keep it inside
                     triples.append((g, c, p1))
                     f_pro *= (1.0 + 2.0 * c + (1.0 - g)) / 4.0
                 if t > 0.0:
@@ -293,7 +296,7 @@ class NoiseModel:
 class SimBatch:
     """A lowered batch: the host arrays of ``mlqem_sim_run_f64`` plus what the host knows about every circuit."""
 
-    circ: np.ndarray        # int32 [B, 4]: n_qubits, mode (0 vector, 1 density), trailing readout ops, measurement-tail records
+    circ: np.ndarray        # int32 [B, 4]: n_qubits, mode (0 vector, 1 density, 2 trajectory), trailing readout ops, measurement-tail records
     op_ptr: np.ndarray      # int64 [B + 1]
     ops: np.ndarray         # int32 [n_ops, 4]: kind, q0, q1, offset into params
     params: np.ndarray      # float64 [n_params + 32]
@@ -321,6 +324,16 @@ class SimBatch:
     prob_ptr: Optional[np.ndarray] = None      # int64 [n_groups + 1]: offsets into the pool of sum 2^n outcomes
     group_circ: Optional[np.ndarray] = None    # int32 [n_groups]: the circuit a group belongs to
     group_basis: Optional[np.ndarray] = None   # int32 [n_groups, 2]: (qubits measured in X, qubits measured in Y); the rest in Z
+    # quantum trajectories (``compile_programs(..., trajectories=)``): density mode's records on a state vector, mode 2.  Only
+    # ``blackwater.sim.run_trajectories`` runs such a batch; every other entry point refuses it (:meth:`refuse_trajectories`)
+    trajectories: Optional[int] = None
+
+    def refuse_trajectories(self, who: str) -> None:
+        """A ``ValueError`` when the batch was lowered in trajectory mode: the kernels behind ``who`` read mode != 0 as a density matrix."""
+        if self.trajectories is not None:
+            raise ValueError(f"{who}: the batch was lowered for quantum trajectories (compile_programs(..., trajectories="
+                             f"{self.trajectories})); only run_trajectories runs it (folded / ZNE runs and shot sampling over "
+                             "trajectories are not supported)")
 
     def __len__(self) -> int:
         return int(self.circ.shape[0])
@@ -390,6 +403,14 @@ def check_shots(shots: Any, who: str) -> int:
     return int(shots)
 
 
+def check_trajectories(trajectories: Any, who: str) -> int:
+    """``trajectories`` as an int in 1 .. 2^20, or a ``ValueError`` that names it."""
+    if (isinstance(trajectories, bool) or not isinstance(trajectories, (int, np.integer))
+            or not 1 <= int(trajectories) <= MAX_TRAJECTORIES):
+        raise ValueError(f"{who}: trajectories = {trajectories!r}, want an int in 1 .. 2^20 = {MAX_TRAJECTORIES}")
+    return int(trajectories)
+
+
 def check_seed(seed: Any, who: str) -> int:
     """``seed`` as an int reduced mod 2^64, or a ``ValueError`` that names it."""
     if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
@@ -426,7 +447,7 @@ _ROT_Y_INV = [_R, _R, 1j * _R, -1j * _R]
 
 
 def compile_programs(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None,
-                     shots: Optional[int] = None) -> SimBatch:
+                     shots: Optional[int] = None, trajectories: Optional[int] = None) -> SimBatch:
     """Lowers ``circuits`` (anything ``Circuit.from_any`` takes) with one observable each (anything ``pauli_terms`` takes) to one
     :class:`SimBatch`.  ``noise=None``: state vectors (at most 11 qubits); a :class:`NoiseModel`: density matrices (at most 5
     qubits) with its noise records (a depolarising record after a gate as ever; where the model has thermal relaxation for the gate,
@@ -445,14 +466,27 @@ def compile_programs(circuits: Sequence[Any], observables: Sequence[Any], noise:
     one ``MEASURE`` record (q0: the group inside its circuit, param: the group's number in ``prob_ptr``), and the inverse
     rotations, so that the next group and the exact term values see the circuit's own state.  ``circ[c, 3]`` counts these tail
     records; ``norm`` is still taken before the readout ops.  Such a batch runs through ``ops.sim_run_measured`` /
-    ``ops.sim_run_folded_measured``; the plain entry points skip a MEASURE record and would misplace ``norm``."""
+    ``ops.sim_run_folded_measured``; the plain entry points skip a MEASURE record and would misplace ``norm``.
+
+    ``trajectories`` (an int in 1 .. 2^20, with a noise model; ``None``: the batch is what it always was): the batch is lowered in
+    TRAJECTORY mode for ``blackwater.sim.run_trajectories``.  The records are the ones density mode emits, ``circ[c, 1] = 2``, and
+    the state is a vector: the cap is 2^n <= 2 048 amplitudes (11 qubits) and ``variant`` is chosen on 2^n.  Everything density
+    mode refuses is refused, and so are ``trajectories`` without a noise model and ``trajectories`` together with ``shots``."""
     circuits, observables = list(circuits), list(observables)
+    if trajectories is not None:
+        trajectories = check_trajectories(trajectories, "compile_programs")
+        if noise is None:
+            raise ValueError("compile_programs: trajectories without a noise model (a noiseless circuit has one trajectory: "
+                             "lower it without trajectories and run it as a state vector)")
+        if shots is not None:
+            raise ValueError("compile_programs: trajectories together with shots (shot sampling over trajectories is not supported)")
     if shots is not None:
         shots = check_shots(shots, "compile_programs")
     if len(circuits) != len(observables):
         raise ValueError(f"compile_programs: {len(circuits)} circuits but {len(observables)} observables")
-    density = noise is not None
-    cap_q = MAX_QUBITS_DENSITY if density else MAX_QUBITS_VECTOR
+    density = noise is not None   # the records of density mode; in trajectory mode they act on a state vector
+    matrix = density and trajectories is None
+    cap_q = MAX_QUBITS_DENSITY if matrix else MAX_QUBITS_VECTOR
     circ_rows, ops, params, op_ptr, term_rows, coeffs, term_ptr = [], [], [], [0], [], [], [0]
     variant, measured_all = [], []
     gate_ptr, gate_record, gate_noise, gate_name, gate_op, gate_noise_len = [0], [], [], [], [], []
@@ -476,9 +510,9 @@ def compile_programs(circuits: Sequence[Any], observables: Sequence[Any], noise:
         circ = Circuit.from_any(obj)
         where = f"circuit {k}"
         n = circ.num_qubits
-        amps = 4 ** n if density else 2 ** n
+        amps = 4 ** n if matrix else 2 ** n
         if n < 1 or amps > MAX_AMPS:
-            raise ValueError(f"{where}: {n} qubits need {amps} amplitudes as a {'density matrix' if density else 'state vector'}; "
+            raise ValueError(f"{where}: {n} qubits need {amps} amplitudes as a {'density matrix' if matrix else 'state vector'}; "
                              f"the cap is {MAX_AMPS} amplitudes ({cap_q} qubits in this mode) and at least 1 qubit")
         measured: Dict[int, int] = {}
         done = set()
@@ -557,7 +591,11 @@ def compile_programs(circuits: Sequence[Any], observables: Sequence[Any], noise:
                     continue
                 if has_xy:
                     raise ValueError(f"{where}: readout noise on qubit {q} cannot be combined with an observable that has X or Y "
-                                     "terms (a readout op leaves only the diagonal of the density matrix meaningful)")
+                                     "terms (a readout op leaves only the diagonal of the density matrix meaningful)"
+                                     if matrix else
+                                     f"{where}: readout noise on qubit {q} cannot be combined with an observable that has X or Y "
+                                     "terms (the readout channel of a trajectory acts on the outcome distribution, which has "
+                                     "only I / Z terms)")
                 emit(OP_READOUT, q, 0, [float(pr[0]), float(pr[1])])
                 n_readout += 1
         n_tail = 0
@@ -576,7 +614,7 @@ def compile_programs(circuits: Sequence[Any], observables: Sequence[Any], noise:
                 prob_ptr.append(prob_ptr[-1] + 2 ** n)
             term_group += tg
             group_ptr.append(len(group_circ))
-        circ_rows.append((n, 1 if density else 0, n_readout, n_tail))
+        circ_rows.append((n, (1 if matrix else MODE_TRAJECTORY) if density else 0, n_readout, n_tail))
         op_ptr.append(len(ops))
         gate_ptr.append(len(gate_record))
         term_rows += rows
@@ -602,6 +640,7 @@ def compile_programs(circuits: Sequence[Any], observables: Sequence[Any], noise:
         gate_ptr=np.asarray(gate_ptr, dtype=np.int64), gate_record=np.asarray(gate_record, dtype=np.int32),
         gate_noise=np.asarray(gate_noise, dtype=np.int32), gate_name=np.asarray(gate_name, dtype=np.int16),
         gate_op=np.asarray(gate_op, dtype=np.int32), gate_noise_len=np.asarray(gate_noise_len, dtype=np.int32),
+        trajectories=trajectories,
         **({} if shots is None else dict(
             shots=shots, group_ptr=np.asarray(group_ptr, dtype=np.int64), term_group=np.asarray(term_group, dtype=np.int32),
             prob_ptr=np.asarray(prob_ptr, dtype=np.int64), group_circ=np.asarray(group_circ, dtype=np.int32),

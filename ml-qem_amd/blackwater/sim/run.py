@@ -1,5 +1,6 @@
 """Device side of the batched simulator: one call of ``mlqem_sim_run_f64`` per batch, measurement shots on top of it
-(``mlqem_sim_run_measured_f64`` + ``mlqem_sim_sample_f64``), and an Estimator-shaped primitive on both."""
+(``mlqem_sim_run_measured_f64`` + ``mlqem_sim_sample_f64``), quantum trajectories for noisy circuits past the density-matrix cap
+(``mlqem_sim_run_trajectories_f64``), and an Estimator-shaped primitive on all three."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -10,13 +11,15 @@ import numpy as np
 from ..library.primitives import make_estimator_result
 from ..data.circuit import Circuit
 from .clifford import clifford_expectation_values, is_clifford, refuse_non_pauli
-from .program import MAX_QUBITS_DENSITY, MAX_QUBITS_VECTOR, NoiseModel, SimBatch, check_seed, check_shots, compile_programs
+from .program import (MAX_QUBITS_DENSITY, MAX_QUBITS_VECTOR, NoiseModel, SimBatch, check_seed, check_shots, check_trajectories,
+                      compile_programs)
 
 
 def run_batch(batch: SimBatch, device="cuda"):
     """``(values, term_values, norm)`` of a lowered batch: float64 tensors on ``device``."""
     from ..native import ops
 
+    batch.refuse_trajectories("run_batch")
     t = batch.to(device)
     return ops.sim_run(t["circ"], t["op_ptr"], t["ops"], t["params"], t["term_ptr"], t["terms"], t["coeff"], t["ids"],
                        t["n_wave"], t["n_wg"])
@@ -76,6 +79,7 @@ def sample_batch(batch: SimBatch, seed: int = 0, run_keys=None, device="cuda") -
 
     from ..native import ops
 
+    batch.refuse_trajectories("sample_batch")
     if batch.group_ptr is None:
         raise ValueError("sample_batch: the batch was lowered without shots (compile_programs(..., shots=))")
     seed = check_seed(seed, "sample_batch")
@@ -107,6 +111,104 @@ def sample_expectation_values(circuits: Sequence[Any], observables: Sequence[Any
     return sample_batch(compile_programs(circuits, observables, noise, shots=shots), seed, run_keys, device)
 
 
+@dataclass
+class TrajectoryResult:
+    """What one trajectory run produced: tensors on the device, the terms CSR over ``term_ptr``."""
+
+    values: Any            # float64 [B]: the mean over the trajectories of sum coeff * term
+    std_error: Any         # float64 [B]: sqrt(M2 / (T (T - 1))) of the per-trajectory values; 0 at T = 1
+    term_values: Any       # float64 [n_terms]: the mean of every Pauli term
+    term_std_error: Any    # float64 [n_terms]
+    norm: Any              # float64 [B]: the mean of <psi|psi> at the end of a trajectory (1 up to rounding)
+    term_ptr: Any          # int64 [B + 1]
+    trajectories: int = 0
+    seed: int = 0
+    traj_term_values: Any = None   # float64 [T, n_terms] with ``keep_trajectories``: row t holds trajectory t of every circuit
+    batch: Optional[SimBatch] = None
+
+
+TRAJECTORY_BUFFER_BYTES = 256 << 20   # the per-trajectory buffers of one call stay under this (``buffer_bytes=``)
+
+
+def _trajectory_chunks(batch: SimBatch, trajectories: int, buffer_bytes: int) -> List[range]:
+    """Contiguous ranges of circuits whose per-trajectory buffers (T x (terms + circuits) float64) fit ``buffer_bytes`` and whose
+    (circuit, trajectory) units fit one call; a range holds at least one circuit."""
+    budget = max(int(buffer_bytes) // (8 * trajectories), 1)          # term and norm columns per call
+    most = max((2 ** 31 - 1) // trajectories, 1)                      # circuits per call
+    chunks, lo = [], 0
+    n_circ = len(batch)
+    while lo < n_circ:
+        hi = lo + 1
+        while hi < n_circ and hi - lo < most and int(batch.term_ptr[hi + 1] - batch.term_ptr[lo]) + (hi + 1 - lo) <= budget:
+            hi += 1
+        chunks.append(range(lo, hi))
+        lo = hi
+    return chunks
+
+
+def run_trajectories(batch: SimBatch, seed: int = 0, run_keys=None, device="cuda", keep_trajectories: bool = False,
+                     buffer_bytes: int = TRAJECTORY_BUFFER_BYTES) -> TrajectoryResult:
+    """Runs a batch lowered with ``trajectories`` (``compile_programs(..., noise, trajectories=T)``): every circuit as T pure-state
+    trajectories on the device, one Kraus operator drawn at every noise record (include/mlqem_hip.h has the unravelling), and
+    the means and standard errors over them.  ``run_keys``: one integer per circuit, by default its position in the batch; a
+    trajectory's bits depend on (seed, run key, trajectory number, circuit) alone, so a circuit gives the same values alone and
+    in a batch, and the first T trajectories of a longer run are the same.  The batch is split by circuits so that the
+    per-trajectory buffers of a call stay under ``buffer_bytes``; the results do not depend on the split.
+    ``keep_trajectories``: also return ``traj_term_values`` [T, n_terms] (the whole buffer: it is then as large as it is)."""
+    import torch
+
+    from ..native import ops
+
+    if batch.trajectories is None:
+        raise ValueError("run_trajectories: the batch was lowered without trajectories (compile_programs(..., noise, trajectories=))")
+    n_traj = check_trajectories(batch.trajectories, "run_trajectories")
+    seed = check_seed(seed, "run_trajectories")
+    keys = _run_keys(run_keys, len(batch), "run_trajectories")
+    if int(buffer_bytes) < 1:
+        raise ValueError(f"run_trajectories: buffer_bytes = {buffer_bytes!r}, want a positive number of bytes")
+    dev = torch.device(device)
+
+    def up(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+    params, term_ptr = up(batch.params), up(batch.term_ptr)
+    out = {k: [] for k in ("values", "std_error", "term_values", "term_std_error", "norm", "traj")}
+    for chunk in _trajectory_chunks(batch, n_traj, buffer_bytes):
+        lo, hi = chunk.start, chunk.stop
+        ob, oe, tb, te = (int(v) for v in (batch.op_ptr[lo], batch.op_ptr[hi], batch.term_ptr[lo], batch.term_ptr[hi]))
+        wave = [k - lo for k in chunk if batch.variant[k] == "wave"]
+        wg = [k - lo for k in chunk if batch.variant[k] != "wave"]
+        values, std_error, term_values, term_std_error, norm, traj, _ = ops.sim_run_trajectories(
+            up(batch.circ[lo:hi]), up(batch.op_ptr[lo:hi + 1] - ob), up(batch.ops[ob:oe]), params, up(batch.term_ptr[lo:hi + 1] - tb),
+            up(batch.terms[tb:te]), up(batch.coeff[tb:te]), up(np.asarray(wave + wg, dtype=np.int32)), len(wave), len(wg),
+            up(keys[lo:hi]), n_traj, seed)
+        for k, v in zip(out, (values, std_error, term_values, term_std_error, norm, traj if keep_trajectories else None)):
+            out[k].append(v)
+
+    def cat(parts, dim=0):
+        return parts[0] if len(parts) == 1 else torch.cat(parts, dim=dim)
+
+    if not out["values"]:   # an empty batch
+        empty = torch.zeros(0, dtype=torch.float64, device=dev)
+        return TrajectoryResult(empty, empty.clone(), empty.clone(), empty.clone(), empty.clone(), term_ptr, n_traj, seed,
+                                torch.zeros((n_traj, 0), dtype=torch.float64, device=dev) if keep_trajectories else None, batch)
+    return TrajectoryResult(cat(out["values"]), cat(out["std_error"]), cat(out["term_values"]), cat(out["term_std_error"]),
+                            cat(out["norm"]), term_ptr, n_traj, seed, cat(out["traj"], 1) if keep_trajectories else None, batch)
+
+
+def trajectory_expectation_values(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None,
+                                  trajectories: int = None, seed: int = 0, run_keys=None, device="cuda") -> TrajectoryResult:
+    """Expectation values under ``noise`` estimated from ``trajectories`` pure-state trajectories per circuit, for noisy circuits
+    of up to 11 qubits, non-Clifford gates, thermal relaxation and coherent errors included (the density-matrix mode stops at 5
+    qubits).  Returns a :class:`TrajectoryResult`: the means and their standard errors.  See :func:`run_trajectories`."""
+    if trajectories is None:
+        raise ValueError("trajectory_expectation_values: trajectories is required (an int in 1 .. 2^20)")
+    trajectories = check_trajectories(trajectories, "trajectory_expectation_values")
+    if noise is None:
+        raise ValueError("trajectory_expectation_values: noise is required (a NoiseModel); expectation_values gives the noiseless values")
+    return run_trajectories(compile_programs(circuits, observables, noise, trajectories=trajectories), seed, run_keys, device)
+
+
 def counts_dicts(result: SampleResult) -> List[List[Dict[str, int]]]:
     """``{bitstring: count}`` per (circuit, group) of a plain (unfolded) result, outcomes with a count of 0 left out.  A bitstring
     is qiskit's: n characters, qubit 0 the RIGHTMOST, so that ``int(bitstring, 2)`` is the outcome index -- the order
@@ -124,6 +226,10 @@ def counts_dicts(result: SampleResult) -> List[List[Dict[str, int]]]:
             per.append({format(j, f"0{width}b"): int(v) for j, v in enumerate(counts[b:e].tolist()) if v})
         out.append(per)
     return out
+
+
+_TRAJECTORY_SHOTS = ("DeviceEstimator(method='trajectories'): shots= is not supported with it (shot sampling over trajectories is "
+                     "out of scope; the estimate's own standard error is in the metadata); run it without shots")
 
 
 class SimulatedJob:
@@ -164,15 +270,27 @@ class DeviceEstimator:
     ``method``: ``"exact"`` (the default: the state-vector / density-matrix simulator and its caps, as above); ``"clifford"``: the
     Clifford path (:func:`clifford_expectation_values`: Clifford circuits of up to 512 qubits, exact under the same noise model);
     ``"auto"``: the exact simulator when every circuit of a job fits its cap, else the Clifford path when every circuit is a Clifford
-    circuit, else a ``ValueError`` naming a circuit that is neither.  The Clifford path draws no shots: ``shots`` with it is refused."""
+    circuit, else a ``ValueError`` naming a circuit that is neither.  The Clifford path draws no shots: ``shots`` with it is refused.
+    ``"trajectories"``: quantum trajectories (:func:`trajectory_expectation_values`: noisy circuits of up to 11 qubits, any lowered
+    gate, any :class:`NoiseModel`); the values are means over ``trajectories`` (constructor; default 1 024) trajectories per circuit
+    and ``metadata[k] = {"std_error": e_k, "trajectories": T}``.  It needs a noise model and draws no shots: ``noise=None`` and
+    ``shots`` with it are refused.  Run keys are those of the shots path, so successive jobs do not repeat their draws.  ``"auto"``
+    never falls back to trajectories: an estimate with a standard error is chosen by name, not silently."""
 
-    METHODS = ("exact", "clifford", "auto")
+    METHODS = ("exact", "clifford", "auto", "trajectories")
 
     def __init__(self, noise: Optional[NoiseModel] = None, device="cuda", shots: Optional[int] = None, seed: int = 0,
-                 method: str = "exact"):
+                 method: str = "exact", trajectories: int = 1024):
         if method not in self.METHODS:
             raise ValueError(f"DeviceEstimator: method = {method!r}, want one of {', '.join(self.METHODS)}")
         self._method = method
+        self._trajectories = check_trajectories(trajectories, "DeviceEstimator")
+        if method == "trajectories":
+            if noise is None:
+                raise ValueError("DeviceEstimator(method='trajectories'): noise=None; trajectories unravel a noise model (the "
+                                 "noiseless values are method='exact')")
+            if shots is not None:
+                raise ValueError(_TRAJECTORY_SHOTS)
         self._noise, self._device, self._count = noise, device, 0
         self._shots = None if shots is None else check_shots(shots, "DeviceEstimator")
         self._seed = check_seed(seed, "DeviceEstimator")
@@ -189,6 +307,16 @@ class DeviceEstimator:
                 raise ValueError(f"DeviceEstimator: circuit {k} comes with {len(p)} parameter values; circuits must arrive bound")
         shots = run_options.pop("shots", self._shots)
         seed = run_options.pop("seed", self._seed)
+        if self._method == "trajectories":
+            if shots is not None:
+                raise ValueError(_TRAJECTORY_SHOTS)
+            self._count += 1
+            res = trajectory_expectation_values(circuits, observables, self._noise, trajectories=self._trajectories,
+                                                seed=check_seed(seed, "DeviceEstimator.run"),
+                                                run_keys=default_run_keys(len(circuits), self._count << 32), device=self._device)
+            std_error = res.std_error.cpu().numpy()
+            return SimulatedJob(res.values.cpu().numpy(), f"sim-{self._count}",
+                                [{"std_error": float(e), "trajectories": self._trajectories} for e in std_error])
         if self._method != "exact" and self._use_clifford(circuits):
             if shots is not None:
                 raise ValueError("DeviceEstimator: shots are not drawn on the Clifford path (method='clifford', or 'auto' on circuits "

@@ -300,6 +300,7 @@ def build_schedules(batch: SimBatch, circuits: Optional[Sequence[Any]], noise_fa
     the inverse of a gate carries the gate's own coherent error and noise again, which is how an over-rotated ``cx`` behaves when
     it is folded.  The circuit's readout records follow every schedule once.  ``circuits`` are the lowered circuits (only their number is checked: the map has everything).  numpy
     throughout: no Python per entry."""
+    batch.refuse_trajectories("build_schedules")
     if batch.gate_ptr is None:
         raise ValueError("build_schedules: the batch carries no record map (it was not made by compile_programs)")
     n_circ = len(batch)
@@ -581,6 +582,9 @@ def zne_run(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional
     if shots is not None and exponential:
         raise ValueError("ExponentialExtrapolator: shots= is not supported with it (the variance of a sampled value is not "
                          "propagated through the exponential fit); use a polynomial extrapolator or run without shots")
+    if method == "trajectories":
+        raise ValueError("zne_run: method = 'trajectories': folded / ZNE runs over quantum trajectories are not supported; "
+                         "want one of exact, clifford, auto")
     if method not in DeviceEstimator.METHODS:
         raise ValueError(f"zne_run: method = {method!r}, want one of {', '.join(DeviceEstimator.METHODS)}")
     if method != "exact" and DeviceEstimator(noise, device, method=method)._use_clifford(circuits):

@@ -1603,6 +1603,91 @@ int mlqem_sim_run_trajectories_f64(int64_t n_circuits, const int32_t* circ, cons
                                    double* values, double* std_error, double* norm, mlqem_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Parameter binding on the device (two additive symbols, the ABI version is unchanged).  One ansatz evaluated at many parameter
+ * vectors is ONE program and a table of float64: the circuit is lowered once as a TEMPLATE whose free angles stay in the records,
+ * and a RUN is (template, row of theta, shifted record).  blackwater.sim.compile_templates lowers templates to this format and
+ * blackwater.native.ops.sim_run_bound / sim_shift_combine call these; blackwater.sim.parameter_shift builds gradients on them.
+ *
+ * mlqem_sim_run_bound_f64.
+ * Input.  The buffers of mlqem_sim_run_f64 for n_templates templates, in which five more record kinds may appear.  The 16-byte
+ * record is unchanged and the kinds above keep their numbers, so a program without the new kinds is a program of mlqem_sim_run_f64.
+ *           kind                 qubits   params
+ *           MLQEM_SIM_OP_PRX     q0       3: parameter index (an exactly representable integer), scale, offset
+ *           MLQEM_SIM_OP_PRY     q0       3: the same
+ *           MLQEM_SIM_OP_PRZ     q0       3: the same
+ *           MLQEM_SIM_OP_PP      q0       3: the same
+ *           MLQEM_SIM_OP_PRZZ    q0, q1   3: the same
+ *         No ordinal is stored: q1 of the one-qubit kinds is 0 and the pool holds the three values alone (the trig table below is
+ *         indexed by the record's position in its circuit, which the kernel knows).
+ * theta   float64 [n_rows][ld_theta], ld_theta >= 1: the parameter rows.
+ * runs    int32 [n_runs][4], 16-byte aligned: (template c, theta row, shifted op or -1, 0).
+ * shift   float64 [n_runs].
+ * ids     int32 [n_wave + n_wg]: RUN numbers, the runs of templates with at most 256 amplitudes first (a wave each), then the others
+ *         (a workgroup each), as in mlqem_sim_run_f64.
+ * run_term_ptr int64 [n_runs + 1]: run r owns term_values[run_term_ptr[r] .. run_term_ptr[r + 1]), the terms of its template in
+ *         order.  n_out_terms = the length of term_values.
+ * form    MLQEM_SIM_BOUND_TABLE or MLQEM_SIM_BOUND_PLAIN: where the sin/cos of a parameterised record is computed (below).  Both
+ *         forms return the same bits.
+ * Run r simulates the records of template c = runs[r][0] with the row theta[runs[r][1]].  A parameterised record reads
+ *           phi = scale * theta[row][index] + offset,   and   phi = phi + shift[r]
+ *         if the record's index inside its circuit (0 for the circuit's first record) equals runs[r][2].  Every step is one
+ *         rounded float64 operation (a product, a sum, a sum: no fused multiply-add), so a host interpreter forms the same phi bit
+ *         for bit.  The gates, with (c, s) = (cos a, sin a) of a = 0.5 * phi (an exact product) for the first four kinds:
+ *           PRX   [[c, -i s], [-i s, c]]                        PRY   [[c, -s], [s, c]]
+ *           PRZ   diag(c - i s, c + i s)                        PRZZ  c - i s where bits q0 and q1 of the index agree, c + i s else
+ *           PP    diag(1, cos phi + i sin phi)
+ *         cos and sin are the device library's double-precision functions.  In mode 1 the gate acts as U on bits q and conj(U) on
+ *         bits q + n, as every unitary does; PRX and PRY are two pair passes there, the diagonal kinds one element pass in either
+ *         mode.
+ * Everything else is the contract of mlqem_sim_run_f64: the state stays in LDS from |0..0>; modes 0 and 1; a wave per run up to 256
+ * amplitudes without a workgroup barrier, a workgroup per run for 512 .. 2 048; loads unconditional on clamped and masked indices,
+ * stores predicated; fixed-order sums, no atomics, no workspace, no host read: capturable in a hipGraph; at most two launches.  The
+ * fixed kinds take the passes mlqem_sim_run_f64 takes, so a template without parameterised records gives its bits.  A run's bits
+ * depend on (records, theta row, shifted op, shift) alone, not on the other runs of the call.
+ * Clamps: a run number to [0, n_runs - 1]; the template to [0, n_templates - 1]; the row to [0, n_rows - 1]; the parameter index
+ * (converted towards zero) to [0, ld_theta - 1]; a shifted op outside [0, the circuit's record count) means "none"; run_term_ptr to
+ * [0, n_out_terms], and a term beyond the run's slice is computed and not stored; and what mlqem_sim_run_f64 clamps.
+ * The trig.  MLQEM_SIM_BOUND_TABLE: a table of (cos, sin) pairs in LDS for the current WINDOW of T consecutive records (T = 64 in the
+ * wave variant, 256 in the workgroup variant).  When the op loop enters a window, lane l forms the pair of record l of the window if
+ * that record is parameterised (a wave without one skips the trig), and the loop reads the pair when it reaches the record.
+ * MLQEM_SIM_BOUND_PLAIN: every lane computes the pair inside the op loop.
+ * Outputs, float64: term_values [n_out_terms]; values [n_runs] = sum coeff * term value in term order; norm [n_runs].  Only the
+ * entries of the runs in `ids` are written.
+ * The checks of mlqem_sim_run_f64 (with n_wave + n_wg > n_runs), and: a negative n_rows, ld_theta, n_runs or n_out_terms, an unknown
+ * form, with runs to do n_templates, n_rows or ld_theta < 1 or a null or misaligned theta, runs, shift or run_term_ptr:
+ * MLQEM_ERR_BAD_ARG; n_templates, n_params, n_runs, n_rows or ld_theta over 2^31 - 1: MLQEM_ERR_UNSUPPORTED; all before any launch.
+ * n_wave + n_wg == 0 returns MLQEM_OK without a launch.
+ *
+ * mlqem_sim_shift_combine_f64.  The parameter-shift rule: every parameterised gate is exp(-i a G) with G^2 = 1 up to a phase
+ * (a = phi / 2; PP is PRZ times a phase), so d<O>/d phi = (<O>(phi + pi/2) - <O>(phi - pi/2)) / 2 exactly, under any noise that
+ * does not depend on the angle.  With K shifted records per template (its OCCURRENCES, in circuit order), v_plus / v_minus float64
+ * [n_shifts = K][n_rows] the values of the runs shifted by +pi/2 / -pi/2 at occurrence k, scale float64 [K] the occurrence's scale,
+ * occ_ptr int64 [n_parameters + 1] and occ int32 [n_occ] the occurrences of every parameter (in circuit order; an entry is clamped to
+ * [0, K - 1]):
+ *           grad[b][p] = sum over j in [occ_ptr[p], occ_ptr[p + 1]) of (0.5 * scale[k]) * (v_plus[k][b] - v_minus[k][b]),  k = occ[j]
+ * by thread (b, p), from 0.0 in the order of j; 0.5 * scale is exact, the difference, the product and the sum are each one rounded
+ * float64 operation (no fused multiply-add).  grad float64 [n_rows][n_parameters].  One launch, no atomics, no workspace, no host
+ * read: the same bits from call to call, capturable.  Negative sizes, a null buffer that would be used, occurrences without shifts:
+ * MLQEM_ERR_BAD_ARG; a size over 2^31 - 1: MLQEM_ERR_UNSUPPORTED.  n_rows == 0 or n_parameters == 0: MLQEM_OK without a launch.
+ * ---------------------------------------------------------------------------------------------------- */
+#define MLQEM_SIM_OP_PRX 12
+#define MLQEM_SIM_OP_PRY 13
+#define MLQEM_SIM_OP_PRZ 14
+#define MLQEM_SIM_OP_PP 15
+#define MLQEM_SIM_OP_PRZZ 16
+#define MLQEM_SIM_BOUND_TABLE 0
+#define MLQEM_SIM_BOUND_PLAIN 1
+int mlqem_sim_run_bound_f64(int64_t n_templates, const int32_t* circ, const int64_t* op_ptr, const mlqem_sim_op* ops, int64_t n_ops,
+                            const double* params, int64_t n_params, const int64_t* term_ptr, const mlqem_sim_term* terms,
+                            const double* coeff, int64_t n_terms, const double* theta, int64_t n_rows, int64_t ld_theta,
+                            const int32_t* runs, int64_t n_runs, const double* shift, const int32_t* ids, int64_t n_wave,
+                            int64_t n_wg, const int64_t* run_term_ptr, int64_t n_out_terms, int32_t form, double* term_values,
+                            double* values, double* norm, mlqem_stream_t stream);
+int mlqem_sim_shift_combine_f64(int64_t n_rows, int64_t n_parameters, int64_t n_shifts, const int64_t* occ_ptr, const int32_t* occ,
+                                int64_t n_occ, const double* scale, const double* v_plus, const double* v_minus, double* grad,
+                                mlqem_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * Clifford circuits of up to MLQEM_CLIFFORD_MAX_QUBITS = 512 qubits, a batch per call (an additive symbol, the ABI version is
  * unchanged).  A Pauli observable is carried BACKWARDS through a Clifford circuit as a Pauli, so its ideal value on |0..0> and its
  * value under the project's depolarising model come from one walk over the records, in O(records) bit operations per (circuit,

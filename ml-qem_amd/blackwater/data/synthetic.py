@@ -72,6 +72,69 @@ def _tfim(nq: int, steps: int, theta: float, phi: float, two_q: str) -> Circuit:
     return Circuit(nq, nq, ops)
 
 
+def two_local(num_qubits: int, rotation_blocks=("ry",), entanglement_blocks="cz", entanglement: str = "full", reps: int = 3):
+    """qiskit's ``TwoLocal`` as a ``blackwater.sim.Template``: ``reps`` times a rotation layer and an entanglement layer, then a
+    final rotation layer.  Parameters are numbered as ``TwoLocal`` numbers them: layer-major, within a layer block-major, then by
+    qubit (an entanglement block with an angle, ``rzz``, by pair).  ``rotation_blocks``: names out of ``rx ry rz p``;
+    ``entanglement_blocks``: ``cx cz swap ecr`` (fixed) or ``rzz``; ``entanglement``: ``"full"`` (every pair i < j, in that order),
+    ``"linear"`` (i, i + 1) or a list of qubit pairs."""
+    from ..sim.template import Param, Template
+
+    rot = [rotation_blocks] if isinstance(rotation_blocks, str) else list(rotation_blocks)
+    ent = [entanglement_blocks] if isinstance(entanglement_blocks, str) else list(entanglement_blocks)
+    for name in rot:
+        if name not in ("rx", "ry", "rz", "p"):
+            raise ValueError(f"two_local: rotation block {name!r}, want one of rx ry rz p")
+    for name in ent:
+        if name not in ("cx", "cz", "swap", "ecr", "rzz"):
+            raise ValueError(f"two_local: entanglement block {name!r}, want one of cx cz swap ecr rzz")
+    if entanglement == "full":
+        pairs = [(i, j) for i in range(num_qubits) for j in range(i + 1, num_qubits)]
+    elif entanglement == "linear":
+        pairs = [(i, i + 1) for i in range(num_qubits - 1)]
+    elif isinstance(entanglement, (list, tuple)):   # explicit pairs, e.g. a device's coupling map
+        pairs = [(int(a), int(b)) for a, b in entanglement]
+    else:
+        raise ValueError(f"two_local: entanglement = {entanglement!r}, want 'full', 'linear' or a list of qubit pairs")
+    if num_qubits < 1 or reps < 0:
+        raise ValueError(f"two_local: num_qubits = {num_qubits}, reps = {reps}, want at least 1 qubit and reps >= 0")
+    ops: List[CircuitOp] = []
+    count = 0
+
+    def rotation_layer():
+        nonlocal count
+        for name in rot:
+            for q in range(num_qubits):
+                ops.append(CircuitOp(name, (q,), (), (Param(count),)))
+                count += 1
+
+    for _ in range(reps):
+        rotation_layer()
+        for name in ent:
+            for a, b in pairs:
+                if name == "rzz":
+                    ops.append(CircuitOp(name, (a, b), (), (Param(count),)))
+                    count += 1
+                else:
+                    ops.append(CircuitOp(name, (a, b)))
+    rotation_layer()
+    return Template(num_qubits, 0, ops, [], count)
+
+
+def tfim_template(num_qubits: int, steps: int):
+    """A Trotterised transverse-field Ising evolution as a ``blackwater.sim.Template`` with TWO parameters, each used by many gates:
+    per step ``rzz(2 theta[0])`` on every bond (i, i + 1) (theta[0] = J dt) and ``rx(2 theta[1])`` on every qubit (theta[1] = h dt)."""
+    from ..sim.template import Param, Template
+
+    ops: List[CircuitOp] = []
+    for _ in range(steps):
+        for q in range(num_qubits - 1):
+            ops.append(CircuitOp("rzz", (q, q + 1), (), (Param(0, 2.0),)))
+        for q in range(num_qubits):
+            ops.append(CircuitOp("rx", (q,), (), (Param(1, 2.0),)))
+    return Template(num_qubits, 0, ops, [], 2)
+
+
 def random_circuit(nq: int, depth: int, seed: int, two_q: str = "cx", measure: bool = True) -> Circuit:
     """Layers of random disjoint one- and two-qubit gates, like the reference's use of
     ``qiskit.circuit.random.random_circuit`` (blackwater/data/generators/exp_val.py:116-120), already in the backend

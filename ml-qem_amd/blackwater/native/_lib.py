@@ -243,6 +243,9 @@ SIGNATURES = {
     "mlqem_sim_sample_f64": (_I, [_L, _L, _P, _P, _P, _P, _L, _P, _P, _P, _P, _L, _L, _P, _P, _L, _U, _P, _L, _L, _P, _P, _P, _P, _P]),
     "mlqem_sim_run_trajectories_f64": (_I, [_L, _P, _P, _P, _L, _P, _L, _P, _P, _P, _L, _P, _L, _L, _P, _L, _U, _P, _P, _P, _P, _P, _P, _P,
                                             _P]),
+    "mlqem_sim_run_bound_f64": (_I, [_L, _P, _P, _P, _L, _P, _L, _P, _P, _P, _L, _P, _L, _L, _P, _L, _P, _P, _L, _L, _P, _L, ctypes.c_int32,
+                                     _P, _P, _P, _P]),
+    "mlqem_sim_shift_combine_f64": (_I, [_L, _L, _L, _P, _P, _L, _P, _P, _P, _P, _P]),
     "mlqem_clifford_run_f64": (_I, [_L, _P, _P, _P, _L, _P, _L, _P, _L, _L, _P, _L, _P, _P, _L, _P, _P, _P, _L, _P, _P, _P, _P, _P, _P,
                                     _P]),
     "mlqem_clifford_run_folded_f64": (_I, [_L, _L, _P, _P, _P, _L, _P, _L, _P, _L, _L, _P, _L, _P, _P, _L, _P, _P, _P, _L, _P, _P, _L,

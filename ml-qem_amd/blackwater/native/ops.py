@@ -2927,6 +2927,92 @@ def sim_run_trajectories(circ, op_ptr, ops, params, term_ptr, terms, coeff, ids,
     return values, std_error, term_values, term_std_error, norm, traj_term_values, traj_norm
 
 
+SIM_BOUND_TABLE, SIM_BOUND_PLAIN = 0, 1   # MLQEM_SIM_BOUND_TABLE / MLQEM_SIM_BOUND_PLAIN
+
+
+def sim_run_bound(circ, op_ptr, ops, params, term_ptr, terms, coeff, theta, runs, shift, ids, n_wave, n_wg, run_term_ptr, n_out_terms, *,
+                  form=SIM_BOUND_TABLE, term_values=None, values=None, norm=None):
+    """Simulates runs of lowered templates (``blackwater.sim.compile_templates``; mlqem_sim_run_bound_f64): ``(values,
+    term_values, norm)``, float64 [n_runs], [n_out_terms], [n_runs].
+
+    The first seven buffers are :func:`sim_run`'s for the templates.  ``theta`` contiguous float64 [n_rows >= 1, ld >= 1]: the
+    parameter rows; ``runs`` int32 [n_runs, 4]: (template, theta row, shifted op or -1, 0); ``shift`` float64 [n_runs]; ``ids``
+    int32 [n_wave + n_wg]: RUN numbers, the wave-per-run ones first; ``run_term_ptr`` int64 [n_runs + 1]: where a run's term values
+    go; ``n_out_terms`` the length of ``term_values`` (a host int: nothing here reads a tensor).  ``form``: the trig table in LDS
+    (``SIM_BOUND_TABLE``) or trig per record (``SIM_BOUND_PLAIN``); the same bits.  Shapes, dtypes and devices are checked here;
+    the contents are ``compile_templates``' to guarantee (the kernel clamps every index).  Nothing here waits for the device, and
+    with the three outputs given nothing is allocated: the call can be captured in a hipGraph.  There is no CPU path."""
+    for t, name, dtype, cols in ((circ, "circ", torch.int32, 4), (ops, "ops", torch.int32, 4), (terms, "terms", torch.int32, 4),
+                                 (runs, "runs", torch.int32, 4)):
+        if not t.is_cuda:
+            raise _lib.NativeLibraryError(f"{name} must live on the GPU (got {t.device}); there is no CPU path")
+        if t.dtype != dtype or t.dim() != 2 or t.shape[1] != cols or not t.is_contiguous():
+            raise ValueError(f"sim: want contiguous {dtype} {name} [., {cols}], got {tuple(t.shape)} {t.dtype}")
+    b, n_ops, n_terms, n_runs = int(circ.shape[0]), int(ops.shape[0]), int(terms.shape[0]), int(runs.shape[0])
+    if form not in (SIM_BOUND_TABLE, SIM_BOUND_PLAIN):
+        raise ValueError(f"sim: form = {form!r}, want SIM_BOUND_TABLE (0) or SIM_BOUND_PLAIN (1)")
+    if not theta.is_cuda or theta.dtype != torch.float64 or theta.dim() != 2 or not theta.is_contiguous() or theta.shape[0] < 1 or theta.shape[1] < 1:
+        raise ValueError(f"sim: want contiguous float64 theta [n_rows >= 1, ld >= 1] on the GPU, got {tuple(theta.shape)} {theta.dtype} {theta.device}")
+    _vec(op_ptr, "op_ptr", b + 1, torch.int64)
+    _vec(term_ptr, "term_ptr", b + 1, torch.int64)
+    _vec(params, "params", SIM_PARAM_PAD, torch.float64)
+    _vec(coeff, "coeff", n_terms, torch.float64)
+    _vec(shift, "shift", n_runs, torch.float64)
+    _vec(run_term_ptr, "run_term_ptr", n_runs + 1, torch.int64)
+    n_wave, n_wg, n_out = int(n_wave), int(n_wg), int(n_out_terms)
+    if n_wave < 0 or n_wg < 0 or n_wave + n_wg > n_runs:
+        raise ValueError(f"sim: n_wave = {n_wave} and n_wg = {n_wg} must be >= 0 and add up to at most {n_runs} runs")
+    if n_out < 0 or (n_wave + n_wg > 0 and b < 1):
+        raise ValueError(f"sim: n_out_terms = {n_out} must be >= 0, and runs need at least one template (got {b})")
+    _vec(ids, "ids", n_wave + n_wg, torch.int32)
+    if shift.shape[0] != n_runs or run_term_ptr.shape[0] != n_runs + 1 or op_ptr.shape[0] != b + 1 or term_ptr.shape[0] != b + 1:
+        raise ValueError(f"sim: want shift [{n_runs}], run_term_ptr [{n_runs + 1}], op_ptr and term_ptr [{b + 1}], got "
+                         f"{tuple(shift.shape)}, {tuple(run_term_ptr.shape)}, {tuple(op_ptr.shape)} and {tuple(term_ptr.shape)}")
+    dev = circ.device
+    if any(t.device != dev for t in (op_ptr, ops, params, term_ptr, terms, coeff, theta, runs, shift, ids, run_term_ptr)):
+        raise ValueError(f"sim: circ is on {dev}, another buffer is not")
+    values, norm = _sim_out(values, "values", (n_runs,), dev), _sim_out(norm, "norm", (n_runs,), dev)
+    term_values = _sim_out(term_values, "term_values", (n_out,), dev)
+    code = _lib.load().mlqem_sim_run_bound_f64(
+        b, _p(circ), _p(op_ptr), _p(ops) if n_ops else None, n_ops, _p(params), int(params.shape[0]), _p(term_ptr),
+        _p(terms) if n_terms else None, _p(coeff) if n_terms else None, n_terms, _p(theta), int(theta.shape[0]), int(theta.shape[1]),
+        _p(runs), n_runs, _p(shift), _p(ids), n_wave, n_wg, _p(run_term_ptr), n_out, int(form), _p(term_values) if n_out else None,
+        _p(values), _p(norm), _stream())
+    _lib.check(code, "mlqem_sim_run_bound_f64")
+    return values, term_values, norm
+
+
+def sim_shift_combine(v_plus, v_minus, occ_ptr, occ, scale, *, grad=None):
+    """The parameter-shift rule (mlqem_sim_shift_combine_f64): ``grad`` float64 [B, P] with ``grad[b, p] = sum_j (0.5 *
+    scale[k]) * (v_plus[k, b] - v_minus[k, b])``, ``k = occ[j]`` over ``j`` in ``occ_ptr[p] .. occ_ptr[p + 1]``, in that order, every
+    operation rounded on its own.  ``v_plus`` / ``v_minus`` contiguous float64 [K, B]: the values of the runs shifted by +pi/2 /
+    -pi/2 at occurrence k; ``scale`` float64 [K]; ``occ_ptr`` int64 [P + 1]; ``occ`` int32 [n_occ].  One launch, no atomics: the
+    same bits from call to call; with ``grad`` given nothing is allocated."""
+    for t, name in ((v_plus, "v_plus"), (v_minus, "v_minus")):
+        if not t.is_cuda:
+            raise _lib.NativeLibraryError(f"{name} must live on the GPU (got {t.device}); there is no CPU path")
+        if t.dtype != torch.float64 or t.dim() != 2 or not t.is_contiguous():
+            raise ValueError(f"shift: want contiguous float64 {name} [K, B], got {tuple(t.shape)} {t.dtype}")
+    if tuple(v_plus.shape) != tuple(v_minus.shape):
+        raise ValueError(f"shift: v_plus is {tuple(v_plus.shape)}, v_minus {tuple(v_minus.shape)}")
+    k, b = int(v_plus.shape[0]), int(v_plus.shape[1])
+    _vec(occ_ptr, "occ_ptr", 1, torch.int64)
+    _vec(occ, "occ", 0, torch.int32)
+    _vec(scale, "scale", k, torch.float64)
+    p, n_occ = int(occ_ptr.shape[0]) - 1, int(occ.shape[0])
+    if scale.shape[0] != k or (n_occ > 0 and k < 1):
+        raise ValueError(f"shift: want scale [{k}] and shifted values for the {n_occ} occurrences, got {tuple(scale.shape)} and K = {k}")
+    dev = v_plus.device
+    if any(t.device != dev for t in (v_minus, occ_ptr, occ, scale)):
+        raise ValueError(f"shift: v_plus is on {dev}, another buffer is not")
+    grad = _sim_out(grad, "grad", (b, p), dev)
+    code = _lib.load().mlqem_sim_shift_combine_f64(b, p, k, _p(occ_ptr), _p(occ) if n_occ else None, n_occ, _p(scale) if k else None,
+                                                   _p(v_plus) if k and b else None, _p(v_minus) if k and b else None,
+                                                   _p(grad) if b and p else None, _stream())
+    _lib.check(code, "mlqem_sim_shift_combine_f64")
+    return grad
+
+
 CLIFFORD_MAX_QUBITS = 512   # MLQEM_CLIFFORD_MAX_QUBITS
 CLIFFORD_REG_QUBITS = 128   # MLQEM_CLIFFORD_REG_QUBITS: units of circuits up to here keep their Pauli words in registers
 CLIFFORD_PAD = 32           # entries of padding `pool` and `masks` end with

@@ -13,6 +13,8 @@ from ..data.circuit import Circuit
 from .clifford import clifford_expectation_values, is_clifford, refuse_non_pauli
 from .program import (MAX_QUBITS_DENSITY, MAX_QUBITS_VECTOR, NoiseModel, SimBatch, check_seed, check_shots, check_trajectories,
                       compile_programs)
+from .bound import bound_expectation_values
+from .template import Template, has_free_parameters
 
 
 def run_batch(batch: SimBatch, device="cuda"):
@@ -259,7 +261,10 @@ class DeviceEstimator:
     ``result().values[k]`` is the exact expectation value of ``observables[k]`` after ``circuits[k]`` (``noise=None``) or the one
     under ``noise`` (a :class:`NoiseModel`, density-matrix mode), ``metadata[k] = {}``.  It has the ``_run`` protocol the
     ``learning(...)`` and ``ngem(...)`` decorators patch.  Circuits arrive bound (QASM text, ``Circuit`` or a bound qiskit-like
-    circuit); non-empty ``parameter_values`` are refused.  There is no host path: ``device`` must be a GPU.
+    circuit); non-empty ``parameter_values`` are refused for them.  A :class:`Template` (or a qiskit-like circuit with free
+    parameters) comes with its row of ``parameter_values`` and is bound on the device (:func:`bound_expectation_values`: one lowering
+    per distinct template, one run per row), under ``method="exact"`` and under ``"auto"`` within the cap; ``shots``, the other
+    methods and ``zne(DeviceEstimator)`` refuse a template by name.  There is no host path: ``device`` must be a GPU.
 
     ``shots`` (constructor, or the ``shots=`` run option, which wins; ``None``: exact, as above): the values are estimated from that
     many measurement outcomes per measurement basis (:func:`sample_expectation_values`) and ``metadata[k] = {"variance": v_k,
@@ -302,11 +307,14 @@ class DeviceEstimator:
         return self._run(circuits, observables, list(parameter_values), **run_options)
 
     def _run(self, circuits, observables, parameter_values, **run_options):
+        free = [has_free_parameters(c) for c in circuits]
         for k, p in enumerate(parameter_values):
-            if len(p):
+            if len(p) and not free[k]:
                 raise ValueError(f"DeviceEstimator: circuit {k} comes with {len(p)} parameter values; circuits must arrive bound")
         shots = run_options.pop("shots", self._shots)
         seed = run_options.pop("seed", self._seed)
+        if any(free):
+            return self._run_templates(circuits, observables, parameter_values, free.index(True), shots)
         if self._method == "trajectories":
             if shots is not None:
                 raise ValueError(_TRAJECTORY_SHOTS)
@@ -334,6 +342,31 @@ class DeviceEstimator:
         variance = res.variance.cpu().numpy()
         return SimulatedJob(res.values.cpu().numpy(), f"sim-{self._count}",
                             [{"variance": float(v), "shots": shots} for v in variance])
+
+    def _run_templates(self, circuits, observables, parameter_values, first: int, shots):
+        """A job with templates (or qiskit-like circuits with free parameters): the bound path, one lowering per distinct
+        (template, observable) pair and one run per row.  Everything that is not the exact simulator is refused by name."""
+        how = ("bind it first (Template.bind_parameters(values)) and pass the bound circuit, which takes that path as ever; "
+               "templates run on the exact simulator alone (method='exact', or 'auto' within its cap, without shots)")
+        if shots is not None:
+            raise ValueError(f"DeviceEstimator: circuit {first} is a template with free parameters and shots= is set: shots are not "
+                             f"drawn on the bound path; {how}")
+        if self._method in ("trajectories", "clifford"):
+            raise ValueError(f"DeviceEstimator(method={self._method!r}): circuit {first} is a template with free parameters; {how}")
+        templates = [Template.from_any(c) for c in circuits]
+        for k, (t, p) in enumerate(zip(templates, parameter_values)):
+            if len(p) != t.num_parameters:
+                raise ValueError(f"DeviceEstimator: circuit {k} comes with {len(p)} parameter values, the template has "
+                                 f"{t.num_parameters} parameters")
+        if self._method == "auto":
+            cap = MAX_QUBITS_VECTOR if self._noise is None else MAX_QUBITS_DENSITY
+            for k, t in enumerate(templates):
+                if t.num_qubits > cap:
+                    raise ValueError(f"DeviceEstimator(method='auto'): circuit {k} is a template of {t.num_qubits} qubits, over the "
+                                     f"exact simulator's cap of {cap} in this mode; {how}")
+        self._count += 1
+        values, _ = bound_expectation_values(list(circuits), list(observables), list(parameter_values), self._noise, self._device)
+        return SimulatedJob(values.cpu().numpy(), f"sim-{self._count}")
 
     def _use_clifford(self, circuits) -> bool:
         if self._method == "clifford":

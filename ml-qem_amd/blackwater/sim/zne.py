@@ -721,6 +721,12 @@ def zne(cls):
         circuits, observables, parameter_values = list(circuits), list(observables), list(parameter_values)
         self._zne_count += 1
         if fused:
+            from .template import has_free_parameters
+
+            for k, c in enumerate(circuits):
+                if has_free_parameters(c):
+                    raise ValueError(f"{type(self).__name__}: circuit {k} is a template with free parameters, which zne(DeviceEstimator) "
+                                     "does not fold; bind it first (Template.bind_parameters(values)) and pass the bound circuit")
             for k, p in enumerate(parameter_values):
                 if len(p):
                     raise ValueError(f"{type(self).__name__}: circuit {k} comes with {len(p)} parameter values; circuits must arrive bound")

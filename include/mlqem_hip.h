@@ -350,6 +350,41 @@ int mlqem_linear_wgrad_parts_f32(const mlqem_col_parts* gy, const float* x, int6
                                  int I, int accumulate, void* workspace, size_t workspace_bytes, const int32_t* x_rows,
                                  mlqem_stream_t stream);
 
+#define MLQEM_WGRAD_MAX_TABLES 4
+
+/* The weight gradients of TWO gradient blocks against up to MLQEM_WGRAD_MAX_TABLES tables that share one row map, in one pass
+ * (an additive symbol, the ABI version is unchanged): table[t] is [M, cols] in the padded row layout with the common leading
+ * dimension ldt, row n of every table is row rows[n] (rows == NULL: row n); 16 <= cols <= 31, out_cols <= 16 (else
+ * MLQEM_ERR_UNSUPPORTED).  image: [2][16][n_tables][32] floats,
+ *     image[b][o][t][i]    = sum_n g_b[n, o] * table[t][rows[n], i]      i < cols
+ *     image[b][o][t][cols] = sum_n g_b[n, o]                             (the ones column)
+ * every other entry 0 (a pair that pair_mask leaves out: all of its entries).  Pad columns of the tables and of the blocks are not read.  synth == 0: block b is the matrix g[b]
+ * ([N, out_cols], leading dimension ldg[b]).  synth != 0: block b is NOT read but computed per element, as
+ * mlqem_segment_pool_bwd_f32(gate_bits=) writes it -- gate_bits[b] (the buffer a pooled aggregation of N rows and out_cols columns
+ * left), weights[b], g_mean[b] / g_wmean[b] ([num_graphs, >= round_up(out_cols, 4)], either may be NULL), gate_scale[b], graph_ptr
+ * -- and the image is bit-equal to the one of the written matrices.  Matrix-core partial sums per workgroup over contiguous row
+ * ranges, then a fixed-order reduction: deterministic.  workspace: mlqem_linear_wgrad_tables_workspace_bytes(n_tables). */
+typedef struct mlqem_wgrad_tables {
+  int32_t n_tables, cols, out_cols, synth;
+  const void* table[MLQEM_WGRAD_MAX_TABLES];
+  int64_t ldt;
+  const float* g[2];
+  int64_t ldg[2];
+  const void* gate_bits[2];
+  const float* weights[2];
+  const float* g_mean[2];
+  int64_t ld_gmean[2];
+  const float* g_wmean[2];
+  int64_t ld_gwmean[2];
+  float gate_scale[2];
+  const int32_t* graph_ptr;
+  int64_t num_graphs;
+  uint32_t pair_mask; /* bit b * MLQEM_WGRAD_MAX_TABLES + t: the product of block b with table t is wanted; 0: all of them */
+} mlqem_wgrad_tables;
+size_t mlqem_linear_wgrad_tables_workspace_bytes(int n_tables);
+int mlqem_linear_wgrad_tables_f32(const mlqem_wgrad_tables* d, const int32_t* rows, int64_t N, float* image, void* workspace,
+                                  size_t workspace_bytes, mlqem_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * The MLP regressor as one forward and one backward launch.  Replaces MLP1.forward and its autograd
  * (docs/tutorials/mlp.py:18-30 == blackwater/library/learning/mlp.py: fc2(relu(fc1(x))); trained by h10_mlp.ipynb cells

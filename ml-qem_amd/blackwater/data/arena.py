@@ -118,6 +118,7 @@ class GraphArena:
         self.y, self.noisy, self.depth, self.observable = y, noisy, depth, observable
         self.device = x.device
         self._first_layer = {}   # kind -> [M, F] table of a graph operator applied to x (first_layer_table), built on first request
+        self._gradient_tables = {}   # ... and the ones only a first layer's backward reads (gradient_table)
 
     def __len__(self):
         return len(self.node_counts) - (1 if self.filler_nodes else 0)
@@ -260,6 +261,35 @@ class GraphArena:
         """Device bytes the tables built so far hold."""
         return sum(int(t.stride(0)) * int(t.shape[0]) * 4 for t in self._first_layer.values())
 
+    def gradient_table(self, kind: str, build: bool = True) -> Optional[torch.Tensor]:
+        """Two more products of a graph operator with the node features, in the layout of ``first_layer_table``, that only the BACKWARD
+        of a first layer reads: ``"cheb2"``: L^ (L^ x), ``"sage"``: M x, the in-edge mean with its self term (rscale = sage_rinv,
+        dself = loops * sage_rinv, as SAGEConv's aggregation takes them).  With g the gated gradient of the layer's output,
+        (L^T g)^T x = g^T (L^ x) and (M^T g)^T x = g^T (M x): the weight gradients of cheb_conv1 and sage_conv1 are products of g
+        with table rows, and g is never aggregated (native/functional._FamilyAGraph).  A store of its own: ``first_layer_bytes``
+        keeps counting the forward's tables only.  Built on first request, 96 bytes a row each; not part of a checkpoint."""
+        if kind not in ("cheb2", "sage"):
+            raise KeyError(kind)
+        t = self._gradient_tables.get(kind)
+        if t is None and build:
+            m, f = self.x.shape
+            out = ops.padded_empty(m, f, self.device)
+            if kind == "cheb2":
+                dinv = self.nscal[:, 2].contiguous()
+                src, kw = self.first_layer_table("cheb"), dict(cscale=dinv, rscale=-dinv)
+            else:
+                rinv = self.nscal[:, 1].contiguous()
+                src, kw = self.x, dict(rscale=rinv, dself=self.loops.to(torch.float32) * rinv)
+            t = self._gradient_tables[kind] = ops.csr_aggregate(src, self.in_ptr, self.in_src, ell=self.in_ell, out=out, **kw)
+        return t
+
+    def gradient_table_bytes(self) -> int:
+        """Device bytes the gradient tables built so far hold."""
+        return sum(int(t.stride(0)) * int(t.shape[0]) * 4 for t in self._gradient_tables.values())
+
+    def _sibling_table(self, kind: str, build: bool = True) -> Optional[torch.Tensor]:
+        return self.gradient_table(kind, build) if kind in ("cheb2", "sage") else self.first_layer_table(kind, build)
+
     _DEVICE_ARRAYS = ("x", "nscal", "gptr", "in_ptr", "in_src", "out_ptr", "out_dst", "out_eid", "loops", "in_ell", "out_ell",
                       "y", "noisy", "depth", "observable")
 
@@ -271,6 +301,7 @@ class GraphArena:
 
         grown = copy.copy(self)
         grown._first_layer = {}
+        grown._gradient_tables = {}
         grown._base = {}
         for name in self._DEVICE_ARRAYS:
             t = getattr(self, name)
@@ -305,6 +336,7 @@ class GraphArena:
             setattr(self, name, view)
         self.node_counts, self.edge_counts, self.coarse_caps = other.node_counts, other.edge_counts, other.coarse_caps
         self._first_layer = {}          # tables of the graphs that were here
+        self._gradient_tables = {}
         return True
 
     def selection(self, graph_ids, bucket=None, filler_sizes=None):
@@ -387,8 +419,9 @@ class GraphArena:
         s.coarse_capacity = coarse_capacity
         s.pool_plan = pool_plan           # size-stable batch: graph_sizes is None and the poolings go by this plan
         s.num_real = num_real
-        # the feature rows stay in the arena; the first-layer tables (first_layer_table) go along as siblings under the same row map
-        nodes = ops.RowsOf(self.x, src_node[:nb], siblings=self.first_layer_table)
+        # the feature rows stay in the arena; the first-layer tables (first_layer_table, gradient_table) go along as siblings under
+        # the same row map
+        nodes = ops.RowsOf(self.x, src_node[:nb], siblings=self._sibling_table)
         # the per-graph inputs in ONE launch (five torch gathers before: a captured step of 32 small circuits is ~80 launches of ~5 us)
         labels = (self.y, self.noisy, self.depth, self.observable)
         if all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape[0] > 0 and t[0].numel() > 0 for t in labels):

@@ -65,6 +65,19 @@ class FanoutChain(ctypes.Structure):
                 ("rowscale", c_void_p)]
 
 
+MAX_WGRAD_TABLES = 4    # MLQEM_WGRAD_MAX_TABLES
+
+
+class WgradTables(ctypes.Structure):
+    """``mlqem_wgrad_tables``: tables that share one row map, and the two gradient blocks (written, or the operands they are computed from)."""
+
+    _fields_ = [("n_tables", ctypes.c_int32), ("cols", ctypes.c_int32), ("out_cols", ctypes.c_int32), ("synth", ctypes.c_int32),
+                ("table", c_void_p * MAX_WGRAD_TABLES), ("ldt", c_int64), ("g", c_void_p * 2), ("ldg", c_int64 * 2),
+                ("gate_bits", c_void_p * 2), ("weights", c_void_p * 2), ("g_mean", c_void_p * 2), ("ld_gmean", c_int64 * 2),
+                ("g_wmean", c_void_p * 2), ("ld_gwmean", c_int64 * 2), ("gate_scale", c_float * 2), ("graph_ptr", c_void_p),
+                ("num_graphs", c_int64), ("pair_mask", ctypes.c_uint32)]
+
+
 class ForestFitState(ctypes.Structure):
     """``mlqem_forest_fit_state``: the inputs and the workspace of one chunk of trees of a forest fit."""
 
@@ -107,6 +120,8 @@ SIGNATURES = {
     "mlqem_linear_wgrad_workspace_bytes": (_S, [_I, _I]),
     "mlqem_linear_wgrad_f32": (_I, [_P, _L, _P, _L, _P, _P, _L, _I, _I, _I, _P, _S, _P, _P]),
     "mlqem_linear_wgrad_parts_f32": (_I, [_P, _P, _L, _P, _P, _L, _I, _I, _P, _S, _P, _P]),
+    "mlqem_linear_wgrad_tables_workspace_bytes": (_S, [_I]),
+    "mlqem_linear_wgrad_tables_f32": (_I, [_P, _P, _L, _P, _P, _S, _P]),
     "mlqem_mlp1_workspace_bytes": (_S, [_I, _I]),
     "mlqem_mlp1_forward": (_I, [_P, _L, _P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _I, _P, _L, _P, _L, _P, _S, _P]),
     "mlqem_mlp1_backward": (_I, [_P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P, _P, _S, _P]),

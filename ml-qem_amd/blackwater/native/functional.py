@@ -440,6 +440,14 @@ _TABLE_CHEB = os.environ.get("MLQEM_TABLE_CHEB", "1") != "0"
 # Both need the A^ x table (MLQEM_TABLE_GCN) and a hidden width <= 12 (A/B, one switch per join).
 _GCN_CHAIN = os.environ.get("MLQEM_GCN_CHAIN", "1") != "0"
 _GCN_TABLE_WGRAD = os.environ.get("MLQEM_GCN_TABLE_WGRAD", "1") != "0"
+# MLQEM_TABLE_GRAD=0: the backward of cheb_conv1 and sage_conv1 aggregates the pooled gradient (g_b1 = L^T g_c, g_p = M^T g_s) and takes
+# the weight gradients against x and L^ x (A/B).  Default: the graph operator sits on the constant side -- g_b1^T x = g_c^T (L^ x),
+# g_b1^T (L^ x) = g_c^T (L^ L^ x), g_p^T x = g_s^T (M x) -- so with the arena's tables of L^ L^ x and M x (data/arena.py gradient_table)
+# all first-layer gradients of the two branches are ONE pass of [g_c | g_s] over table rows (ops.linear_wgrad_tables), no aggregation.
+# MLQEM_TABLE_GRAD_SYNTH=0: that pass reads g_c and g_s as matrices written by ops.segment_pool_bwd instead of computing their
+# elements from the gate bits (A/B of the second stage).
+_TABLE_GRAD = os.environ.get("MLQEM_TABLE_GRAD", "1") != "0"
+_TABLE_GRAD_SYNTH = os.environ.get("MLQEM_TABLE_GRAD_SYNTH", "1") != "0"
 
 _PARTS_MAX_COLS = 64   # mlqem_linear_parts_f32 keeps the weight fragments of I <= 64 concatenated columns in registers
 
@@ -1200,8 +1208,11 @@ class _FamilyAGraph(Function):
         # a projection of table rows with its bias / ReLU / dropout epilogue, and the inner Clenshaw hop of cheb_conv1 is
         # b_1 = x W_1^T + (L^ x)(2 W_2)^T -- neither is aggregated, forward or backward (their weight gradients are taken against
         # the tables).  ``tables``: (A^ x rows, L^ x rows), each None where there is no table (family_a_graph).
-        tab_g, tab_c = tables if (fuse and 16 < x.shape[1] <= 24) else (None, None)
+        tab_g, tab_c, tab_c2, tab_s = tables if (fuse and 16 < x.shape[1] <= 24) else (None, None, None, None)
         ctx.tables = (tab_g, tab_c)
+        # the tables only the backward reads (L^ L^ x, M x: see backward); the forward is the same with and without them
+        ctx.grad_tables = (tab_c2, tab_s) if (tab_c is not None and tab_c2 is not None and tab_s is not None) else None
+        ctx.x_rows = x if ctx.grad_tables is not None else None
         if tab_g is not None or tab_c is not None:
             xr = ops.rowmajor(x)
             n_, o_ = xr.shape[0], g1w.shape[0]
@@ -1316,47 +1327,68 @@ class _FamilyAGraph(Function):
         else:
             r = _gcn_backward(g1, r.x, False, True, True)
             g1w, g1b = r.w, r.b
-        with torch.cuda.stream(side[0]):
-            t = pooled_grad(gcm, gcw, "cheb", hc, k2, bc_)
-            if fuse:
-                bc = _cheb_grad_blocks(c1, t, tail=tab_c is None)       # [g, g_b1, g_c2]; with the L^ x table: [g, g_b1]
-                if tab_c is not None:                                   # ... and g_c2^T x = 2 g_b1^T (L^ x)
-                    gwl = new_gw()
-                    ops.linear_wgrad(bc[1], tab_c, gwl, None)
-            else:
-                r = _cheb_backward(c1, t, False)
-                c1b, (c1w0, c1w1, c1w2) = r.b, r.ws
-        with torch.cuda.stream(side[1]):
-            t = pooled_grad(gsm, gsw, "sage", hs, k2, bs_)
-            if fuse:
-                bs = _sage_grad_blocks(s1, t)       # [g_p, g]
-            else:
-                r = _sage_backward(s1, t, False)
-                s1l, s1b, s1r = r.wl, r.bl, r.wr
+        # With the arena's tables of L^ L^ x and M x the graph operators of cheb_conv1 and sage_conv1 sit on the constant side of their
+        # weight gradients: g_b1^T x = g_c^T (L^ x), g_b1^T (L^ x) = g_c^T (L^ L^ x), g_p^T x = g_s^T (M x).  Neither pooled gradient is
+        # aggregated, and the seven gradients of the two first layers are one pass of [g_c | g_s] over the rows of four tables -- by
+        # default with g_c and g_s computed inside the pass from the gate bits (ops.PooledGrad), else written out first.
+        table_grad = fuse and _TABLE_GRAD and ctx.grad_tables is not None and synth and bc_ is not None and bs_ is not None
+        bc, bs = [], []
+        if table_grad:
+            # on the caller's stream, behind the GCN branch's backward (next to it on a side stream the step was slower: DESIGN.md section 9)
+            pooled = [pooled_grad(gcm, gcw, "cheb", hc, k2, bc_), pooled_grad(gsm, gsw, "sage", hs, k2, bs_)]
+            if not _TABLE_GRAD_SYNTH:
+                pooled = [t.materialise() for t in pooled]
+            xr, (tab_c2, tab_s) = ctx.x_rows, ctx.grad_tables
+            # the pairs the gradients need: g_c against x, L^ x, L^ L^ x and g_s against x, M x
+            gwt, gbt = ops.linear_wgrad_tables([xr.base, tab_c.base, tab_c2.base, tab_s.base], xr.rows, n, pooled,
+                                               pairs=((0, 0), (0, 1), (0, 2), (1, 0), (1, 3)))
+            c1w0, c1w1, c1b = gwt[0][0], gwt[0][1], gbt[0]
+            c1w2 = torch.sub(gwt[0][2] * 2.0, gwt[0][0])          # against T_2 = 2 L^ L^ x - x
+            s1l, s1r, s1b = gwt[1][3], gwt[1][0], gbt[1]
+        else:
+            with torch.cuda.stream(side[0]):
+                t = pooled_grad(gcm, gcw, "cheb", hc, k2, bc_)
+                if fuse:
+                    bc = _cheb_grad_blocks(c1, t, tail=tab_c is None)       # [g, g_b1, g_c2]; with the L^ x table: [g, g_b1]
+                    if tab_c is not None:                                   # ... and g_c2^T x = 2 g_b1^T (L^ x)
+                        gwl = new_gw()
+                        ops.linear_wgrad(bc[1], tab_c, gwl, None)
+                else:
+                    r = _cheb_backward(c1, t, False)
+                    c1b, (c1w0, c1w1, c1w2) = r.b, r.ws
+            with torch.cuda.stream(side[1]):
+                t = pooled_grad(gsm, gsw, "sage", hs, k2, bs_)
+                if fuse:
+                    bs = _sage_grad_blocks(s1, t)       # [g_p, g]
+                else:
+                    r = _sage_backward(s1, t, False)
+                    s1l, s1b, s1r = r.wl, r.bl, r.wr
         for st in side:
             main.wait_stream(st)
-        if fuse:
+        if fuse and (bg or not table_grad):
             # ONE pass over x for the weight gradients of all three first layers: x^T [gh | g || g | g_b1 | g_c2 || g_p | g];
-            # the ones column of the pass yields the three bias gradients
+            # the ones column of the pass yields the three bias gradients (with the gradient tables: the GCN blocks alone, if any)
             for blk in bc + bs:
                 blk.record_stream(main)
             k, j = len(bg), len(bg) + len(bc)               # index of the first Cheb / SAGE block
             gwn, gbn = _wgrad_blocks(bg + bc + bs, g1.x, o)
             if tab_g is None:
                 g1w, g1b = gwn[0], (gbn[1] if g1b_cs is None else None)
-            if g1b_cs is not None:
-                g1b = g1b_cs[:o]
-            c1w0, c1w1, c1b = gwn[k], gwn[k + 1], gbn[k]
-            if tab_c is None:
-                c1w2 = gwn[k + 2] - gwn[k]
-            else:
-                gwl.record_stream(main)
-                c1w2 = torch.sub(gwl.mul_(2.0), gwn[k])
-            s1l, s1r, s1b = gwn[j], gwn[j + 1], gbn[j + 1]
-        for t in (gcm, gcw, gsm, gsw):        # made on the compute stream, consumed by the side streams
-            t.record_stream(side[0] if t is gcm or t is gcw else side[1])
-        for t in (() if fuse else (c1b, c1w0, c1w1, c1w2, s1l, s1b, s1r)):
-            t.record_stream(main)
+            if not table_grad:
+                c1w0, c1w1, c1b = gwn[k], gwn[k + 1], gbn[k]
+                if tab_c is None:
+                    c1w2 = gwn[k + 2] - gwn[k]
+                else:
+                    gwl.record_stream(main)
+                    c1w2 = torch.sub(gwl.mul_(2.0), gwn[k])
+                s1l, s1r, s1b = gwn[j], gwn[j + 1], gbn[j + 1]
+        if fuse and g1b_cs is not None:
+            g1b = g1b_cs[:o]
+        if not table_grad:
+            for t in (gcm, gcw, gsm, gsw):        # made on the compute stream, consumed by the side streams
+                t.record_stream(side[0] if t is gcm or t is gcw else side[1])
+            for t in (() if fuse else (c1b, c1w0, c1w1, c1w2, s1l, s1b, s1r)):
+                t.record_stream(main)
         return (None, None, None, None, None, None, g1w, g1b, g2w, g2b, g3wg, g3bg, c1w0, c1w1, c1w2, c1b, c2w0g, c2w1g, c2bg,
                 s1l, s1b, s1r, s2lg, s2bg, s2rg)
 
@@ -1365,8 +1397,12 @@ def family_a_graph(x, struct, p1, p2, seed, params):
     """One-node form of Family A's three conv branches + pools; ``params`` as listed in ``_FamilyAGraph``.  Rows of an arena
     (``ops.RowsOf``) bring the arena's first-layer tables along: a call that trains builds them on first use, one that only predicts
     (no gradient wanted) takes them if they exist -- nothing is built for an arena that never trains this model."""
-    tables = (None, None)
+    tables = (None, None, None, None)
     if isinstance(x, ops.RowsOf) and 16 < x.shape[1] <= 24 and params[0].shape[0] <= 16:      # what the fused first layer takes
         build = torch.is_grad_enabled() and any(p.requires_grad for p in params)
-        tables = (x.sibling("gcn", build) if _TABLE_GCN else None, x.sibling("cheb", build) if _TABLE_CHEB else None)
+        # the tables of L^ L^ x and M x serve the backward alone, and only where it computes the pooled gradients (see backward)
+        grad = (build and _TABLE_GRAD and _TABLE_CHEB and _POOLED_GRAD and struct.num_nodes >= _POOLED_GRAD_MIN_NODES
+                and struct.out_ell is not None and ops.pooled_grad_supported(params[0].shape[0]))
+        tables = (x.sibling("gcn", build) if _TABLE_GCN else None, x.sibling("cheb", build) if _TABLE_CHEB else None,
+                  x.sibling("cheb2", True) if grad else None, x.sibling("sage", True) if grad else None)
     return _FamilyAGraph.apply(x, struct, p1, p2, seed, tables, *params)

@@ -727,6 +727,66 @@ def linear_wgrad(gy, x, gw, gb=None, accumulate=False):
     _lib.check(code, "mlqem_linear_wgrad_f32")
 
 
+def linear_wgrad_tables(tables, rows, n, blocks, pairs=None):
+    """(gw, gb) with gw[b][t] = blocks[b]^T tables[t][rows] ([O, I]) and gb[b] = the column sums of blocks[b] ([O]), for TWO gradient
+    blocks and up to four tables that share the row map ``rows`` (int32 [n] or None), in one pass: mlqem_linear_wgrad_tables_f32.
+    ``tables``: [M, I] fp32 in the padded row layout with one leading dimension (an arena's x and its tables), 16 <= I <= 31.
+    ``blocks``: two [n, O] matrices in the padded row layout, O <= 16 -- or two ``PooledGrad`` s, which are then not written out:
+    the pass computes their elements from the gate bits, the pool weights and the graphs' gradient rows (bit-equal to the pass over
+    ``materialise()``).  ``pairs``: the (block, table) products that are wanted (default: all); the others come out as zeros, and
+    so does the column sum of a block without a pair.  Deterministic; the k order is not ``linear_wgrad``'s (a wave walks a
+    contiguous range of rows)."""
+    import ctypes as _ct
+
+    if not 1 <= len(tables) <= _lib.MAX_WGRAD_TABLES or len(blocks) != 2:
+        raise ValueError(f"linear_wgrad_tables: 1..{_lib.MAX_WGRAD_TABLES} tables and two gradient blocks")
+    synth = isinstance(blocks[0], PooledGrad)
+    if synth != isinstance(blocks[1], PooledGrad):
+        raise ValueError("linear_wgrad_tables: both blocks written, or both PooledGrad")
+    i = tables[0].shape[1]
+    d = _lib.WgradTables()
+    ldt = _mat(tables[0], "tables[0]")
+    for j, t in enumerate(tables):
+        if t.shape != tables[0].shape or _mat(t, f"tables[{j}]") != ldt or ldt % 4 or t.data_ptr() % 16:
+            raise ValueError("linear_wgrad_tables: the tables must share one shape and the padded row layout")
+        d.table[j] = t.data_ptr()
+    if rows is None:
+        if tables[0].shape[0] < n:
+            raise ValueError("linear_wgrad_tables: fewer table rows than n")
+    else:
+        _vec(rows, "rows", n, torch.int32)
+    keep = []       # padded copies of the small per-graph gradients: alive until the launch is enqueued
+    if synth:
+        o = None
+        for b, pg in enumerate(blocks):
+            ref, nb, c, pn, gm, ldm, gw_, ldw = pg._operands()
+            if pn != n or (o is not None and c != o) or (b and (nb != d.num_graphs or pg.graph_ptr.data_ptr() != d.graph_ptr)):
+                raise ValueError("linear_wgrad_tables: the two PooledGrad blocks must share rows, columns and graphs")
+            o = c
+            keep += [gm, gw_]
+            d.gate_bits[b], d.weights[b], d.g_mean[b], d.ld_gmean[b] = _p(pg.gate_bits), _p(pg.weights), _p(gm), ldm
+            d.g_wmean[b], d.ld_gwmean[b], d.gate_scale[b] = _p(gw_), ldw, float(pg.gate_scale)
+            d.graph_ptr, d.num_graphs = _p(pg.graph_ptr), nb
+    else:
+        o = blocks[0].shape[1]
+        for b, g in enumerate(blocks):
+            if tuple(g.shape) != (n, o):
+                raise ValueError(f"linear_wgrad_tables: blocks must be [{n}, {o}]")
+            d.g[b], d.ldg[b] = _p(g), (_mat(g, f"blocks[{b}]") if n > 1 else (o + 3) // 4 * 4)
+    d.n_tables, d.cols, d.out_cols, d.synth, d.ldt = len(tables), i, o, 1 if synth else 0, ldt
+    d.pair_mask = 0 if pairs is None else sum(1 << (b * _lib.MAX_WGRAD_TABLES + t) for b, t in set(pairs))
+    lib = _lib.load()
+    need = lib.mlqem_linear_wgrad_tables_workspace_bytes(len(tables))
+    ws = _wgrad_workspace(tables[0].device, need)
+    img = torch.empty((2, 16, len(tables), 32), dtype=torch.float32, device=tables[0].device)
+    code = lib.mlqem_linear_wgrad_tables_f32(_ct.addressof(d), _p(rows), n, _p(img), _p(ws), need, _stream())
+    _lib.check(code, "mlqem_linear_wgrad_tables_f32")
+    del keep
+    gw = [[img[b, :o, t, :i] for t in range(len(tables))] for b in range(2)]
+    first = [min([t for bb, t in pairs if bb == b], default=0) if pairs is not None else 0 for b in range(2)]
+    return gw, [img[b, :o, first[b], i] for b in range(2)]
+
+
 MLP1_MAX_IN, MLP1_MAX_HIDDEN, MLP1_MAX_OUT = 175, 128, 4   # MLQEM_MLP1_MAX_IN / _HIDDEN_PAD / _MAX_OUT
 
 

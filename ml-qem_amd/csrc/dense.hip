@@ -1594,6 +1594,190 @@ __global__ __launch_bounds__(kReducePairs * kReduceSlices) void wgrad_reduce_ker
   }
 }
 
+// ----------------------------------------------------------- weight gradients of two gradient blocks against several tables
+// image[b][o][t][i] = sum_n g_b[n, o] * T_t[rows[n], i] for two gradient blocks (O <= 16 columns each) and NT tables that share
+// ONE row map (16 <= I <= 31 columns: two MFMA tiles a table, column I of each is the ones column -> the column sums of g_b):
+// wgrad_mfma_kernel with its x generalised to a list of bases.  The first-layer gradients of the Cheb and SAGE branches,
+// g_c^T [x | L^ x | L^ L^ x] and g_s^T [x | M x], are one pass with no transposed aggregation in front of it.  Only the pairs of
+// `pairs` are multiplied: all 16 MFMAs per four rows at NT = 4 are 0.59 ms of matrix pipe per 11.3 M rows beside ~1 ms of loads at
+// three waves per SIMD, and the five wanted pairs are 10 of them.
+// A wave takes `chunk` consecutive 16-row steps at a time -- by default ONE contiguous range (not every n_waves-th step as
+// wgrad_mfma_kernel: the k order differs from that kernel's; chunks of 16 / 64 / 256 steps measured 0.1 / 0.1 / 0.45 ms slower
+// per headline step) -- so that with SYNTH it walks the graphs in turn: the blocks are then not read but computed per element from the
+// 2-byte gate of the row, its pool weight and the graph's two gradient rows -- pool.hip pool_bwd_tiles_kernel's expression in its
+// order (pooled_grad.hip grad_value), bit-equal to the written matrix.  Partials per workgroup, fixed-order second stage.
+struct WgradTablesArgs {
+  const float* tab[MLQEM_WGRAD_MAX_TABLES]; int64_t ldt;
+  const int32_t* rows;                       // optional row map of the tables
+  const float* g[2]; int64_t ldg[2];         // the written blocks (!SYNTH)
+  const uint16_t* gate[2]; const float* wts[2]; const float* g0[2]; int64_t ldg0[2]; const float* g1[2]; int64_t ldg1[2];
+  float gscale[2]; const int32_t* gptr; int B;       // SYNTH: per block (node gates, pool weights, d mean, d weighted mean, gate scale)
+  float* partial;                            // [gridDim.x][2 * 16][NT * 32]
+  int64_t N; int I; int O;
+  int64_t chunk;
+  unsigned pairs;                            // bit b * NT + t: the product of block b with table t is wanted (workgroup-uniform)
+};
+
+template <int NT, bool SYNTH>
+// Pinned at three waves per SIMD: left alone, the computed form at NT = 4 takes 105 VGPRs + 64 accumulator registers (granule 8: 176 of
+// the 170 that three waves allow) and runs at TWO waves; pinned, both forms fit 162-167 unified registers without scratch
+// (1292 -> 1146 us on the headline pass, 5.02-5.08 -> 4.86-4.91 ms per step).
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3, 3))) void wgrad_tables_kernel(const WgradTablesArgs a) {
+  __shared__ f32x4 s_acc[4][kWave];
+  constexpr int kU = kWgradUnroll;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int lr = lane & 15, lq = lane >> 4;
+  const int64_t n_waves = (int64_t)gridDim.x * 4, wave = (int64_t)blockIdx.x * 4 + wid;
+  const int64_t n_iters = ceil_div(a.N, (int64_t)(4 * kU));
+  const int64_t chunk = a.chunk;                        // consecutive 16-row steps a wave takes before it jumps n_waves chunks on
+  const bool col_ok = lr < a.O;                         // the pad columns of a block are never read
+  const int i1 = 16 + lr;                               // this lane's column of a table's second tile
+  const bool hi_ok = i1 < a.I;
+  const float hi_fill = i1 == a.I ? 1.f : 0.f;          // column I: ones -> the column sums
+
+  f32x4 acc[2][NT][2];
+#pragma unroll
+  for (int b = 0; b < 2; ++b)
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[b][t][0] = acc[b][t][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // SYNTH: the graph of this lane's current row (its rows only grow), and this lane's column of the graph's gradient rows
+  int gr = 0, gend = 0;
+  float inv = 0.f, a0[2] = {0.f, 0.f}, a1[2] = {0.f, 0.f};
+  auto graph_rows = [&]() {
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      a0[b] = (col_ok && a.g0[b]) ? a.g0[b][(int64_t)gr * a.ldg0[b] + lr] : 0.f;
+      a1[b] = (col_ok && a.g1[b]) ? a.g1[b][(int64_t)gr * a.ldg1[b] + lr] : 0.f;
+    }
+  };
+
+  int xmap[kU];
+  auto fetch_map = [&](int64_t it) {      // one iteration ahead, as in wgrad_mfma_kernel: never in front of the operand loads
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const int64_t n = it * 4 * kU + u * 4 + lq;
+      xmap[u] = (a.rows && it < n_iters && n < a.N) ? a.rows[n] : 0;
+    }
+  };
+  fetch_map(wave * chunk);
+  for (int64_t c0 = wave * chunk; c0 < n_iters; c0 += n_waves * chunk) {
+    const int64_t c1 = min(n_iters, c0 + chunk);
+    if (SYNTH && c0 * 4 * kU + lq < a.N && c0 * 4 * kU + lq >= (int64_t)gend) {      // a chunk's first row: found by bisection
+      gr = graph_at(a.gptr, a.B, c0 * 4 * kU + lq);
+      gend = a.gptr[gr + 1];
+      inv = 1.f / (float)max(gend - a.gptr[gr], 1);
+      graph_rows();
+    }
+    for (int64_t it = c0; it < c1; ++it) {
+      float A[kU][2], Bv[kU][NT][2], tw[kU][2];
+      unsigned gt[kU][2];
+      int xcur[kU];
+#pragma unroll
+      for (int u = 0; u < kU; ++u) xcur[u] = xmap[u];
+      if (a.rows) fetch_map(it + 1 < c1 ? it + 1 : c0 + n_waves * chunk);
+#pragma unroll
+      for (int u = 0; u < kU; ++u) {
+        const int64_t n = it * 4 * kU + u * 4 + lq;
+        const bool ok = n < a.N;
+        const int64_t xn = a.rows ? (int64_t)xcur[u] : n;
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+          if (SYNTH) {
+            gt[u][b] = ok ? (unsigned)a.gate[b][n] : 0u;
+            tw[u][b] = (ok && a.wts[b]) ? a.wts[b][n] : (ok ? 1.f : 0.f);
+          } else {
+            A[u][b] = (ok && col_ok) ? a.g[b][n * a.ldg[b] + lr] : 0.f;
+          }
+        }
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          const float* __restrict__ row = a.tab[t] + xn * a.ldt;
+          Bv[u][t][0] = ok ? row[lr] : 0.f;
+          Bv[u][t][1] = ok ? (hi_ok ? row[i1] : hi_fill) : 0.f;
+        }
+      }
+      if (SYNTH) {
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+          const int64_t n = it * 4 * kU + u * 4 + lq;
+          if (n < a.N && n >= (int64_t)gend && gr + 1 < a.B) {      // the next graphs in turn (pooled_grad_colsum_kernel's walk)
+            int gbeg = gend;
+            do { ++gr; gbeg = gend; gend = a.gptr[gr + 1]; } while (n >= (int64_t)gend && gr + 1 < a.B);
+            inv = 1.f / (float)max(gend - gbeg, 1);
+            graph_rows();
+          }
+#pragma unroll
+          for (int b = 0; b < 2; ++b) {
+            const float uu = fmaf(tw[u][b], a1[b], a0[b]) * inv;
+            A[u][b] = (n < a.N && col_ok && (gt[u][b] >> lr & 1u)) ? uu * a.gscale[b] : 0.f;
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kU; ++u)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+          for (int t = 0; t < NT; ++t) {
+            if (!(a.pairs >> (b * NT + t) & 1u)) continue;      // the matrix pipe is NOT idle next to the loads: 64 MFMAs per 16 rows at NT = 4
+            acc[b][t][0] = mfma16x16x4(A[u][b], Bv[u][t][0], acc[b][t][0]);
+            acc[b][t][1] = mfma16x16x4(A[u][b], Bv[u][t][1], acc[b][t][1]);
+          }
+    }
+  }
+  // the four waves of the block add up through LDS in a fixed order, one accumulator tile at a time (as wgrad_mfma_kernel)
+  float* __restrict__ dst = a.partial + (int64_t)blockIdx.x * (2 * 16 * NT * 32);
+#pragma unroll
+  for (int b = 0; b < 2; ++b)
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        s_acc[wid][lane] = acc[b][t][h];
+        __syncthreads();
+        if (wid == 0) {
+          f32x4 s = s_acc[0][lane];
+#pragma unroll
+          for (int w = 1; w < 4; ++w) s += s_acc[w][lane];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) dst[((b * 16 + lq * 4 + r) * NT + t) * 32 + h * 16 + lr] = s[r];
+        }
+        __syncthreads();
+      }
+}
+
+// Stage 2 of wgrad_tables_kernel: wgrad_reduce_kernel's fixed-order sum over the G partials, the image written as it is laid out.
+__global__ __launch_bounds__(kReducePairs * kReduceSlices) void wgrad_tables_reduce_kernel(const float* __restrict__ partial, int G, int pairs,
+                                                                                          float* __restrict__ image) {
+  __shared__ float s[kReduceSlices][kReducePairs];
+  const int pl = threadIdx.x % kReducePairs, sl = threadIdx.x / kReducePairs;
+  const int p = blockIdx.x * kReducePairs + pl;
+  float t = 0.f;
+  if (p < pairs) {
+    const int per = (G + kReduceSlices - 1) / kReduceSlices;
+    const int g1 = min(G, (sl + 1) * per);
+    int g = sl * per;
+    float t1 = 0.f, t2 = 0.f, t3 = 0.f;
+    for (; g + 3 < g1; g += 4) {
+      t += partial[(int64_t)g * pairs + p];
+      t1 += partial[(int64_t)(g + 1) * pairs + p];
+      t2 += partial[(int64_t)(g + 2) * pairs + p];
+      t3 += partial[(int64_t)(g + 3) * pairs + p];
+    }
+    for (; g < g1; ++g) t += partial[(int64_t)g * pairs + p];
+    t = (t + t1) + (t2 + t3);
+  }
+  s[sl][pl] = t;
+  __syncthreads();
+  if (sl == 0 && p < pairs) {
+    float tot = 0.f;
+#pragma unroll
+    for (int k = 0; k < kReduceSlices; ++k) tot += s[k][pl];
+    image[p] = tot;
+  }
+}
+
 // Workgroups of the first stage (= partial sums per (o, i) pair).  1024 = 4 per CU: measured best on MI355X for the
 // 2.8M-row shapes (x[22]^T g[10]: 103 us at 512, 81 us at 1024, 94 us at 2048).
 constexpr int kWgradBlocks = 1024;
@@ -2074,6 +2258,84 @@ extern "C" int mlqem_linear_wgrad_parts_f32(const mlqem_col_parts* gy, const flo
   a.gn = gy->count; a.gw = gy->width; a.gc = gy->cols;
   a.x = x; a.ldx = ldx; a.xrows = x_rows; a.partial = static_cast<float*>(workspace); a.N = N; a.I = I; a.O = O;
   return launch_wgrad(a, gw, gb, accumulate, as_stream(stream));
+}
+
+namespace mlqem {
+int aggregate_pool_rows_per_tile(int C);      // csr_aggregate.hip: the tiling of the gate buffer a pooled aggregation leaves
+int aggregate_pool_mask_words();
+}  // namespace mlqem
+
+extern "C" size_t mlqem_linear_wgrad_tables_workspace_bytes(int n_tables) {
+  if (n_tables < 1 || n_tables > MLQEM_WGRAD_MAX_TABLES) return 0;
+  return (size_t)kWgradBlocks * 2 * 16 * n_tables * 32 * sizeof(float);
+}
+
+template <int NT>
+static int launch_wgrad_tables(const WgradTablesArgs& a, bool synth, unsigned mask, float* image, hipStream_t s) {
+  const int64_t iters = ceil_div(std::max<int64_t>(a.N, 1), 4 * kWgradUnroll);
+  // a wave walks ONE contiguous range of rows: a single resident round, at most kWgradBlocks partials
+  // ... of the SMALLER of the two forms' resident rounds: the grid fixes the order of the sums, and the computed form's image is
+  // promised bit-equal to the written form's at every size
+  const int res = std::min(resident_of(reinterpret_cast<const void*>(wgrad_tables_kernel<NT, true>)),
+                           resident_of(reinterpret_cast<const void*>(wgrad_tables_kernel<NT, false>)));
+  const int G = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(kWgradBlocks, res), ceil_div(iters, 4)));
+  WgradTablesArgs b = a;
+  b.pairs = 0;
+  for (int k = 0; k < 2; ++k)
+    for (int t = 0; t < NT; ++t)
+      if (mask == 0 || (mask >> (k * MLQEM_WGRAD_MAX_TABLES + t) & 1u)) b.pairs |= 1u << (k * NT + t);
+  b.chunk = std::max<int64_t>(1, ceil_div(iters, (int64_t)G * 4));      // one contiguous range per wave
+  if (synth) hipLaunchKernelGGL((wgrad_tables_kernel<NT, true>), dim3((unsigned)G), dim3(kBlock), 0, s, b);
+  else hipLaunchKernelGGL((wgrad_tables_kernel<NT, false>), dim3((unsigned)G), dim3(kBlock), 0, s, b);
+  const int pairs = 2 * 16 * NT * 32;
+  hipLaunchKernelGGL(wgrad_tables_reduce_kernel, dim3((unsigned)ceil_div(pairs, kReducePairs)), dim3(kReducePairs * kReduceSlices), 0, s, a.partial, G,
+                     pairs, image);
+  return launch_status();
+}
+
+extern "C" int mlqem_linear_wgrad_tables_f32(const mlqem_wgrad_tables* d, const int32_t* rows, int64_t N, float* image, void* workspace,
+                                             size_t workspace_bytes, mlqem_stream_t stream) {
+  begin_launches();
+  if (!d || N < 0 || N > 0x7fffffffLL || !image) return MLQEM_ERR_BAD_ARG;
+  if (d->n_tables < 1 || d->n_tables > MLQEM_WGRAD_MAX_TABLES || d->out_cols < 1 || d->cols < 1) return MLQEM_ERR_BAD_ARG;
+  if (d->cols < 16 || d->cols > 31 || d->out_cols > 16) return MLQEM_ERR_UNSUPPORTED;
+  if (!workspace || workspace_bytes < mlqem_linear_wgrad_tables_workspace_bytes(d->n_tables)) return MLQEM_ERR_WORKSPACE;
+  if (d->ldt < d->cols) return MLQEM_ERR_BAD_ARG;
+  WgradTablesArgs a{};
+  for (int t = 0; t < d->n_tables; ++t) {
+    if (N > 0 && !d->table[t]) return MLQEM_ERR_BAD_ARG;
+    a.tab[t] = static_cast<const float*>(d->table[t]);
+  }
+  a.ldt = d->ldt; a.rows = rows; a.partial = static_cast<float*>(workspace); a.N = N; a.I = d->cols; a.O = d->out_cols;
+  const bool synth = d->synth != 0;
+  const int c4 = (d->out_cols + 3) / 4 * 4;
+  for (int b = 0; b < 2; ++b) {
+    if (synth) {
+      if (d->num_graphs <= 0 || d->num_graphs > 0x7fffffffLL || !d->graph_ptr || !d->gate_bits[b] || (!d->g_mean[b] && !d->g_wmean[b]))
+        return MLQEM_ERR_BAD_ARG;
+      if ((d->g_mean[b] && d->ld_gmean[b] < c4) || (d->g_wmean[b] && (d->ld_gwmean[b] < c4 || !d->weights[b]))) return MLQEM_ERR_BAD_ARG;
+      if (!mlqem_pooled_grad_aggregate_supported(d->out_cols)) return MLQEM_ERR_UNSUPPORTED;
+      // the per-node section of the gate buffer, behind the tile records and the ballots (mlqem_csr_aggregate_pool_gate_bytes)
+      const int64_t tiles = ceil_div(std::max<int64_t>(N, 1), (int64_t)aggregate_pool_rows_per_tile(d->out_cols));
+      const int4* info = reinterpret_cast<const int4*>(d->gate_bits[b]);
+      const unsigned long long* words = reinterpret_cast<const unsigned long long*>(info + tiles);
+      a.gate[b] = reinterpret_cast<const uint16_t*>(words + tiles * aggregate_pool_mask_words());
+      a.wts[b] = d->g_wmean[b] ? d->weights[b] : nullptr;
+      a.g0[b] = d->g_mean[b]; a.ldg0[b] = d->ld_gmean[b]; a.g1[b] = d->g_wmean[b]; a.ldg1[b] = d->ld_gwmean[b];
+      a.gscale[b] = d->gate_scale[b];
+    } else {
+      if ((N > 0 && !d->g[b]) || d->ldg[b] < d->out_cols) return MLQEM_ERR_BAD_ARG;
+      a.g[b] = d->g[b]; a.ldg[b] = d->ldg[b];
+    }
+  }
+  a.gptr = d->graph_ptr; a.B = (int)d->num_graphs;
+  hipStream_t s = as_stream(stream);
+  switch (d->n_tables) {
+    case 1: return launch_wgrad_tables<1>(a, synth, d->pair_mask, image, s);
+    case 2: return launch_wgrad_tables<2>(a, synth, d->pair_mask, image, s);
+    case 3: return launch_wgrad_tables<3>(a, synth, d->pair_mask, image, s);
+    default: return launch_wgrad_tables<4>(a, synth, d->pair_mask, image, s);
+  }
 }
 
 extern "C" int mlqem_linear_wgrad_bf16_f32(const float* gy, int64_t ldgy, const float* x, int64_t ldx, float* gw, float* gb,

@@ -1841,6 +1841,95 @@ int mlqem_zne_combine_exp_f64(int64_t n_factors, int64_t n_circuits, const doubl
                               const int64_t* term_ptr, const double* coeff, int64_t n_terms, double* mitigated_terms,
                               double* mitigated_values, int32_t* fallback, mlqem_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Measurement shots at width: Pauli-frame sampling of Clifford circuits (an additive symbol, the ABI version is unchanged).  For a
+ * Clifford circuit under a Pauli noise model (depolarising records, readout flips) the outcome distribution is sampled EXACTLY from
+ * one reference outcome per (circuit, measurement basis) and one Pauli frame of 2 n bits per shot: no state vector, up to 512
+ * qubits.  blackwater.sim.frames lowers for it (compile_clifford_frames) and blackwater.native.ops.clifford_sample calls it.
+ *
+ * Input.  n_qubits, op_ptr, ops: the circuits in the record format of mlqem_clifford_run_f64 (circuit c IS run c).
+ * thresh   uint64 [n_thresh], n_thresh >= 32, 8-byte aligned: the integer pool BESIDE the float64 pool of the exact path -- entry i
+ *          is T = floor(lambda 2^60) of the depolarising record whose `a` is i (computed by the host with integers, exactly;
+ *          lambda = 1 gives 2^60, lambda = 0 gives 0), and a circuit with readout noise owns 2 n further entries (below).  An index
+ *          is clamped to [0, n_thresh - 1].
+ * ro_ptr   int64 [n_circuits]: -1, or the index in thresh of the circuit's readout table: entry 2 q is floor(p10 2^32) and entry
+ *          2 q + 1 is floor(p01 2^32) of qubit q (0 .. 2^32; both 0 for a qubit that is not measured or has no readout noise).
+ *          The convention is that of the exact path's Z -> a Z + b I with a = 1 - p01 - p10, b = p01 - p10:
+ *          p10 = P(read 1 | the bit is 0), p01 = P(read 0 | the bit is 1).
+ * Units.   One sampling unit is a (run, group) pair.  The terms of a circuit are partitioned into qubit-wise commuting GROUPS
+ *          (blackwater.sim.measurement_groups); circuit c owns groups group_ptr[c] .. group_ptr[c + 1] of n_groups (at least one,
+ *          at most MLQEM_CLIFFORD_MAX_GROUPS = 4 096 each), group_circ int32 [n_groups] is a group's circuit.  With W = ceil(n / 32):
+ *          group_mask int32 [n_groups] is the index in `masks` of the group's BASIS, W words bx then W words bz: the letter of
+ *          qubit q is bit q of bx | bit q of bz << 1 (X = 1, Z = 2, Y = 3; Z where no term touches the qubit).  There are no
+ *          rotation records: the basis enters through these masks alone.
+ * ids      int32 [n_reg + n_lds], n_reg + n_lds == n_groups: the groups, those of circuits of at most 128 qubits first (words in
+ *          registers), then the others (words in LDS at word * 256 + lane), as in mlqem_clifford_run_f64.
+ * masks    uint32 [n_masks], n_masks >= 32 (every index clamped).
+ * Terms.   term_ptr int64 [n_circuits + 1], coeff float64 [n_terms]; term_mask int32 [n_terms]: the index in `masks` of the term's
+ *          SUPPORT, W words (bit q set: the term is not the identity on q).  gterm_ptr int64 [n_groups + 1], gterm int32 [n_gterm]:
+ *          group g owns the terms gterm[gterm_ptr[g] .. gterm_ptr[g + 1]).
+ * run_keys int64 [n_circuits]; seed uint64; 1 <= shots <= MLQEM_SIM_MAX_SHOTS = 2^20; max_qubits in 1 .. 512: an upper bound of
+ *          every n_qubits[c] (n is clamped to it; it sizes the LDS of the reference kernel).
+ * Workspace and outputs, all written by the call:
+ *   rows      uint32 [n_rows]; row_ptr int64 [n_groups]: group g owns n rows of 2 W + 1 words from row_ptr[g].
+ *   reference uint32 [n_ref]; ref_ptr int64 [n_groups]: the W words of the group's reference outcome m at ref_ptr[g]
+ *             (ref_ptr[g] = the sum of W over the groups before g).
+ *   bits      uint32, or NULL (nothing is stored): shot s of group g owns the W words at ref_ptr[g] * shots + s * W, i.e. the CSR
+ *             pointer of the packed bits [shots][W] per unit is ref_ptr scaled by shots.  n_bits is its length.
+ *   term_sums int32 [n_terms]: S_t;  term_values float64 [n_terms];  values, variance float64 [n_circuits].
+ *
+ * The rule.
+ *   1. PULL-BACK.  For group g and qubit q < n: P_q = U^dagger B_q U, B_q the basis letter of q on q alone, by the backward walk
+ *      of mlqem_clifford_run_f64 from sign = 0 (noise records are ignored).  Row q of the group = its W x words, W z words and
+ *      the sign in one more word.
+ *   2. REFERENCE OUTCOME m.  Through q = 0 .. n - 1 in order, with a set of pivot rows keyed by the position of their lowest x
+ *      bit, each with a value bit v.  Start with row = P_q, acc = 0.  While the row has an x bit and a pivot exists for its lowest
+ *      one: row <- row * pivot, acc ^= v.  The product XORs the x and z words, and its sign is sign ^ sign_pivot ^ ((t >> 1) & 1),
+ *      t = sum over the qubits of the Aaronson-Gottesman exponent g(x1, z1, x2, z2) of (row, pivot): 0 for I; z2 - x2 for Y
+ *      (x1 z1 = 11); z2 (2 x2 - 1) for X (10); x2 (1 - 2 z2) for Z (01) -- an even number, as the rows commute.  If no x bit is
+ *      left the row is +-Z_T, which is +1 on |0..0>: m_q = sign ^ acc.  Otherwise m_q = 0 and the row becomes the pivot of its
+ *      lowest x bit with v = acc.
+ *   3. DRAWS.  Philox4x32-10 with the key (seed & 0xffffffff, seed >> 32) and the counter
+ *        (run_key & 0xffffffff,  run_key >> 32,  s | gl << 20,  domain << 30 | block),   run_key = run_keys[c],
+ *      s < 2^20 the shot, gl < 4 096 the group counted inside its circuit, domain 0 = initial z, 1 = noise, 2 = readout, block < 2^30.
+ *      A draw depends on (seed, run key, group, shot, domain, ordinal) alone: a circuit gives the same bits alone, in any batch,
+ *      for any grid and in a replayed graph.
+ *   4. FRAME of shot s.  x = 0; z word w = word w & 3 of block w >> 2 of domain 0, masked to n bits.  Then the records, first to
+ *      last; record i is counted from the circuit's first record:
+ *        C1 / C2   the frame's letters at the record's qubits are mapped through the INVERSE of the stored table, exactly as a
+ *                  daggered entry of mlqem_clifford_run_folded_f64 maps them, the sign ignored (U F U^dagger is wanted and the
+ *                  record stores U^dagger P U).
+ *        DEPOL1 / DEPOL2   v = word 2 (i & 1) | word 2 (i & 1) + 1 << 32 of block i >> 1 of domain 1.  The record is HIT iff
+ *                  v >> 4 < T (its upper 60 bits; T = 2^60 always hits, T = 0 never).  On a hit, letter v & 3 (bit 0: x, bit 1: z)
+ *                  is XORed into the frame at q0 and, for DEPOL2, letter (v >> 2) & 3 at q1: a Pauli drawn uniformly from all 4 or
+ *                  16, the identity included -- the channel whose adjoint scales a Pauli that is not the identity by 1 - lambda.
+ *                  (A block none of whose two records is a noise record is not computed; nothing else reads it.)
+ *   5. OUTCOME.  bits word w = (m ^ (x & bz) ^ (z & bx)) masked to n bits: bit q is m_q flipped iff the frame anticommutes with
+ *      B_q.  Then, in a circuit with ro_ptr >= 0, for q = 0 .. n - 1: u = word q & 3 of block q >> 2 of domain 2; bit q flips iff
+ *      u < the entry of ITS OWN value (entry 2 q for a 0, 2 q + 1 for a 1), compared as 64-bit integers, so 2^32 always flips.
+ *   6. ESTIMATES.  S_t = sum over the shots of (-1)^popcount(bits & support_t), an integer (wave-reduced, then integer atomics
+ *      into the zeroed buffer: order-independent); term_values[t] = (double)S_t / (double)shots; values and variance as in
+ *      mlqem_sim_sample_f64: one thread per circuit, terms in order from 0.0, values = fma(coeff, term, values), variance =
+ *      fma(coeff^2, fma(-term, term, 1), variance).
+ * Four kernels (the pull-back and the sampler, each in a register and an LDS instantiation; the reference; the finish) and one
+ * memset node on the stream, at most seven nodes; no float atomics, no host read: capturable.  Every index read from a buffer is
+ * clamped and only stores are predicated (a range that leaves its buffer stores nothing), so malformed input computes garbage and
+ * faults nothing.  Negative sizes, shots or max_qubits out of range, n_thresh or n_masks < 32, n_reg + n_lds != n_groups, circuits
+ * without a group, a null or misaligned buffer that would be used: MLQEM_ERR_BAD_ARG; a count over 2^31 - 1, n_groups *
+ * ceil(shots / 256) included: MLQEM_ERR_UNSUPPORTED; all checked before anything is launched.  n_circuits == 0: MLQEM_OK without
+ * a launch.
+ * ---------------------------------------------------------------------------------------------------- */
+#define MLQEM_CLIFFORD_MAX_GROUPS 4096
+int mlqem_clifford_sample_f64(int64_t n_circuits, const int32_t* n_qubits, const int64_t* op_ptr, const mlqem_clifford_op* ops,
+                              int64_t n_ops, const uint64_t* thresh, int64_t n_thresh, const int64_t* ro_ptr, const int64_t* group_ptr,
+                              const int32_t* group_circ, const int32_t* group_mask, int64_t n_groups, const int32_t* ids,
+                              int64_t n_reg, int64_t n_lds, const uint32_t* masks, int64_t n_masks, const int64_t* term_ptr,
+                              const double* coeff, const int32_t* term_mask, int64_t n_terms, const int64_t* gterm_ptr,
+                              const int32_t* gterm, int64_t n_gterm, const int64_t* run_keys, int64_t shots, uint64_t seed,
+                              int32_t max_qubits, const int64_t* row_ptr, uint32_t* rows, int64_t n_rows, const int64_t* ref_ptr,
+                              uint32_t* reference, int64_t n_ref, uint32_t* bits, int64_t n_bits, int32_t* term_sums,
+                              double* term_values, double* values, double* variance, mlqem_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,7 +62,8 @@ class ExpValueEntry:
 
 def exp_value_generator(backend: Any, n_qubits: int, circuit_depth: int, pauli_terms: int, pauli_coeff: float = 1.0,
                         max_entries: int = 1000, seed: int = 0, batch: int = 256, device="cuda", shots: Optional[int] = None,
-                        sample_ideal: bool = False, trajectories: Optional[int] = None) -> Iterator[ExpValueEntry]:
+                        sample_ideal: bool = False, trajectories: Optional[int] = None,
+                        frame_shots: Optional[int] = None) -> Iterator[ExpValueEntry]:
     """Yields ``max_entries`` dataset entries of random circuits with simulated labels (reference: exp_val.py:92-170, which
     transpiles ``qiskit.circuit.random.random_circuit`` and runs Aer twice per circuit).
 
@@ -82,11 +83,21 @@ def exp_value_generator(backend: Any, n_qubits: int, circuit_depth: int, pauli_t
     ``trajectories`` (default ``None``): the noisy value is the mean over that many quantum trajectories
     (``sim.trajectory_expectation_values``), which reaches ``n_qubits`` of 6 to 11 where the density-matrix mode stops at 5; the
     ideal value stays the exact state-vector one.  The draws are keyed as the shots are, so an entry is a function of ``seed`` and
-    ``trajectories`` alone, whatever ``batch`` is.  ``trajectories`` together with ``shots`` is refused."""
+    ``trajectories`` alone, whatever ``batch`` is.  ``trajectories`` together with ``shots`` is refused.
+
+    ``frame_shots`` (default ``None``): the circuits are Clifford circuits (``synthetic.random_clifford_circuit`` in the backend's
+    basis) of up to 512 qubits, the noisy value is a ``frame_shots``-shot estimate by Pauli-frame sampling
+    (``sim.sample_clifford_expectation_values``, keyed as the shots are) and the ideal value stays the exact one
+    (``sim.clifford_expectation_values``).  Together with ``shots`` or ``trajectories`` it is refused by name."""
     if trajectories is not None and shots is not None:
         raise ValueError("exp_value_generator: trajectories together with shots (shot sampling over trajectories is not supported)")
+    if frame_shots is not None and shots is not None:
+        raise ValueError("exp_value_generator: frame_shots together with shots (shots= samples the exact simulator, frame_shots= the "
+                         "Clifford path: choose one)")
+    if frame_shots is not None and trajectories is not None:
+        raise ValueError("exp_value_generator: frame_shots together with trajectories (choose one estimate of the noisy value)")
     from ... import sim
-    from ..synthetic import random_circuit
+    from ..synthetic import random_circuit, random_clifford_circuit
     from ..utils import circuit_to_graph_data_json, encode_pauli_sum_op, generate_random_pauli_sum_op, get_backend_properties_v1
 
     properties = get_backend_properties_v1(backend)
@@ -103,9 +114,16 @@ def exp_value_generator(backend: Any, n_qubits: int, circuit_depth: int, pauli_t
         circuits, observables = [], []
         for _ in range(count):
             depth = int(rng.integers(1, circuit_depth + 1))
-            circuits.append(random_circuit(n_qubits, depth, int(rng.integers(0, 2 ** 31 - 1)), two_q=two_q[0]))
+            circuit_seed = int(rng.integers(0, 2 ** 31 - 1))
+            circuits.append(random_circuit(n_qubits, depth, circuit_seed, two_q=two_q[0]) if frame_shots is None
+                            else random_clifford_circuit(n_qubits, depth, circuit_seed, two_q=two_q[0], measure=False, basis=True))
             observables.append(generate_random_pauli_sum_op(n_qubits, pauli_terms, pauli_coeff, rng=rng))
-        if trajectories is not None:
+        if frame_shots is not None:
+            keys = np.arange(done, done + count, dtype=np.int64)   # the entry's number, as on the shots path
+            ideal = _to_host(sim.clifford_expectation_values(circuits, observables, None, device)[0])
+            noisy = _to_host(sim.sample_clifford_expectation_values(circuits, observables, noise, shots=frame_shots, seed=seed,
+                                                                    run_keys=keys, device=device).values)
+        elif trajectories is not None:
             keys = np.arange(done, done + count, dtype=np.int64)   # the entry's number, as on the shots path
             ideal = _to_host(sim.expectation_values(circuits, observables, None, device)[0])
             noisy = _to_host(sim.trajectory_expectation_values(circuits, observables, noise, trajectories=trajectories, seed=seed,

@@ -225,7 +225,7 @@ def pauli_twirl(circ: Circuit, seed: int, two_q=("cx", "ecr")) -> Circuit:
 
 def encode_corpus(circuits, nq: int, two_q: str = "cx", seed: int = 7, exp_value_size: int = 1,
                   add_self_loops: bool = True, simulate=None, device="cuda", shots=None, sample_ideal: bool = False,
-                  clifford: bool = False, trajectories=None) -> Dict[str, list]:
+                  clifford: bool = False, trajectories=None, frame_shots=None) -> Dict[str, list]:
     """Arena-ready arrays (same keys as :func:`tfim_corpus`) for arbitrary circuits, encoded by the native encoder.
 
     ``simulate=None``: synthetic labels (a uniform draw and a made-up decay).  ``simulate=`` a ``blackwater.sim.NoiseModel``: ``y``
@@ -237,9 +237,22 @@ def encode_corpus(circuits, nq: int, two_q: str = "cx", seed: int = 7, exp_value
     ``seed`` (``sim.sample_expectation_values``), and with ``sample_ideal=True`` the ideal one too.
     ``trajectories`` (with ``simulate``; default ``None``): the noisy value is the mean over that many quantum trajectories
     (``sim.trajectory_expectation_values``, keyed by ``seed`` and the circuit's position), and the cap of the simulated circuits
-    rises from 5 to 11 qubits; the ideal value stays the exact one.  ``trajectories`` together with ``shots`` is refused."""
+    rises from 5 to 11 qubits; the ideal value stays the exact one.  ``trajectories`` together with ``shots`` is refused.
+    ``frame_shots`` (with ``simulate``; default ``None``): every circuit must be a Clifford circuit of at most 512 qubits, and its
+    noisy value is a ``frame_shots``-shot estimate by Pauli-frame sampling (``sim.sample_clifford_expectation_values``, keyed by
+    ``seed`` and the circuit's position); the ideal value stays the exact one (``sim.clifford_expectation_values``).  Together with
+    ``shots`` or ``trajectories``, without ``simulate`` or on a circuit that is no Clifford circuit it is refused by name."""
     from .circuit import circuit_to_qasm
     from .native_encoder import NativeEncoder
+
+    if frame_shots is not None:
+        if shots is not None:
+            raise ValueError("encode_corpus: frame_shots together with shots (shots= samples the exact simulator, frame_shots= the "
+                             "Clifford path: choose one)")
+        if trajectories is not None:
+            raise ValueError("encode_corpus: frame_shots together with trajectories (choose one estimate of the noisy value)")
+        if simulate is None:
+            raise ValueError("encode_corpus: frame_shots fills simulated labels, so it needs simulate= (a noise model)")
 
     props = get_backend_properties_v1(synthetic_backend(nq, two_q))
     enc = NativeEncoder(props)
@@ -273,7 +286,22 @@ def encode_corpus(circuits, nq: int, two_q: str = "cx", seed: int = 7, exp_value
         raise ValueError("encode_corpus: trajectories fill simulated labels, so they need simulate= (a noise model)")
     if trajectories is not None and shots is not None:
         raise ValueError("encode_corpus: trajectories together with shots (shot sampling over trajectories is not supported)")
-    if simulate is not None:
+    if frame_shots is not None:
+        from .. import sim
+
+        for k, circ in enumerate(kept):
+            if not (1 <= circ.num_qubits <= sim.MAX_QUBITS_CLIFFORD and sim.is_clifford(circ)):
+                raise ValueError(f"encode_corpus: frame_shots: circuit {k} is not a Clifford circuit of at most "
+                                 f"{sim.MAX_QUBITS_CLIFFORD} qubits; frame sampling takes no other")
+        labels = ["".join("Z" if q == z_qubits[k] else "I" for q in reversed(range(circ.num_qubits))) for k, circ in enumerate(kept)]
+        if kept:
+            exact = sim.clifford_expectation_values(kept, labels, None, device)[0].cpu().numpy()
+            under = sim.sample_clifford_expectation_values(kept, labels, simulate, shots=frame_shots, seed=seed,
+                                                           run_keys=np.arange(len(kept), dtype=np.int64), device=device).values.cpu().numpy()
+            for k in range(len(kept)):
+                ys[k] = np.full(exp_value_size, exact[k])
+                noisy[k] = np.full(exp_value_size, under[k])
+    elif simulate is not None:
         from .. import sim
 
         cap = sim.MAX_QUBITS_DENSITY if trajectories is None else sim.MAX_QUBITS_VECTOR

@@ -266,6 +266,8 @@ SIGNATURES = {
     "mlqem_clifford_run_folded_f64": (_I, [_L, _L, _P, _P, _P, _L, _P, _L, _P, _L, _L, _P, _L, _P, _P, _L, _P, _P, _P, _L, _P, _P, _L,
                                            _P, _P, _P, _P, _P, _P, _P]),
     "mlqem_zne_combine_exp_f64": (_I, [_L, _L, _P, _P, _P, _P, _L, _P, _P, _P, _P]),
+    "mlqem_clifford_sample_f64": (_I, [_L, _P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _L, _P, _L, _L, _P, _L, _P, _P, _P, _L, _P, _P, _L, _P,
+                                       _L, _U, ctypes.c_int32, _P, _P, _L, _P, _P, _L, _P, _L, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

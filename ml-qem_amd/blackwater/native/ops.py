@@ -3208,3 +3208,88 @@ def zne_combine_exp(term_values, weights, term_ptr, coeff, *, mitigated_terms=No
                                                  _p(mitigated_values) if b else None, _p(fallback) if n_terms else None, _stream())
     _lib.check(code, "mlqem_zne_combine_exp_f64")
     return mitigated_values, mitigated_terms, fallback
+
+
+CLIFFORD_MAX_GROUPS = 4096   # MLQEM_CLIFFORD_MAX_GROUPS
+
+
+def _int_out(t, name, n, dev):
+    if t is None:
+        return torch.zeros(n, dtype=torch.int32, device=dev)
+    if not t.is_cuda or t.device != dev or t.dtype != torch.int32 or tuple(t.shape) != (n,) or not t.is_contiguous():
+        raise ValueError(f"{name}: want contiguous int32 [{n}] on {dev}, got {tuple(t.shape)} {t.dtype} {t.device}")
+    return t
+
+
+def clifford_sample(n_qubits, op_ptr, ops, thresh, ro_ptr, group_ptr, group_circ, group_mask, ids, n_reg, n_lds, masks, term_ptr, coeff,
+                    term_mask, gterm_ptr, gterm, run_keys, shots, seed, max_qubits, row_ptr, n_rows, ref_ptr, n_ref, *,
+                    return_bits=False, rows=None, reference=None, bits=None, term_sums=None, term_values=None, values=None,
+                    variance=None):
+    """Draws ``shots`` measurement outcomes per (circuit, group) of a lowered Clifford batch by Pauli-frame sampling
+    (mlqem_clifford_sample_f64): ``(values, variance, term_values, term_sums, reference, bits)``, float64 [B], [B], [n_terms], int32
+    [n_terms], int32 [n_ref] (the packed reference outcomes) and int32 [n_ref * shots] (the packed shots; ``None`` unless
+    ``return_bits`` or ``bits`` is given).
+
+    The buffers are those of ``blackwater.sim.FrameBatch.to(device)``, in the layout of include/mlqem_hip.h: ``n_qubits`` int32 [B],
+    ``op_ptr`` int64 [B + 1], ``ops`` int32 [n_ops, 4], ``thresh`` int64 [>= 32] (the uint64 thresholds), ``ro_ptr`` int64 [B],
+    ``group_ptr`` int64 [B + 1], ``group_circ`` / ``group_mask`` / ``ids`` int32 [n_groups], ``masks`` int32 [>= 32], ``term_ptr`` int64
+    [B + 1], ``coeff`` float64 [n_terms], ``term_mask`` int32 [n_terms], ``gterm_ptr`` int64 [n_groups + 1], ``gterm`` int32 [n_gterm],
+    ``run_keys`` int64 [B], ``row_ptr`` int64 [n_groups], ``ref_ptr`` int64 [>= n_groups].  ``n_reg`` / ``n_lds``: how many of ``ids``
+    (the first / the rest) are groups of circuits of at most 128 qubits / of more; ``max_qubits``: the widest circuit; ``n_rows`` /
+    ``n_ref``: the lengths of the workspace ``rows`` and of ``reference``.  Shapes, dtypes and devices are checked here; the
+    CONTENTS are ``compile_clifford_frames``'s to guarantee (the kernels clamp every index).  Nothing here waits for the device or
+    reads a tensor, and with the buffers given nothing is allocated: the call can be captured in a hipGraph."""
+    if not ops.is_cuda:
+        raise _lib.NativeLibraryError(f"ops must live on the GPU (got {ops.device}); there is no CPU path")
+    if ops.dtype != torch.int32 or ops.dim() != 2 or ops.shape[1] != 4 or not ops.is_contiguous():
+        raise ValueError(f"clifford_sample: want contiguous torch.int32 ops [., 4], got {tuple(ops.shape)} {ops.dtype}")
+    b, n_ops, n_groups = int(n_qubits.shape[0]), int(ops.shape[0]), int(group_circ.shape[0])
+    n_terms, n_gterm = int(coeff.shape[0]), int(gterm.shape[0])
+    n_reg, n_lds, shots, seed, max_qubits, n_rows, n_ref = (int(v) for v in (n_reg, n_lds, shots, seed, max_qubits, n_rows, n_ref))
+    if n_reg < 0 or n_lds < 0 or n_reg + n_lds != n_groups:
+        raise ValueError(f"clifford_sample: n_reg = {n_reg} and n_lds = {n_lds} must be >= 0 and add up to the {n_groups} groups")
+    if not 1 <= shots <= SIM_MAX_SHOTS:
+        raise ValueError(f"clifford_sample: shots = {shots}, want 1 .. 2^20")
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError(f"clifford_sample: seed = {seed}, want 0 .. 2^64 - 1")
+    if not 1 <= max_qubits <= CLIFFORD_MAX_QUBITS:
+        raise ValueError(f"clifford_sample: max_qubits = {max_qubits}, want 1 .. {CLIFFORD_MAX_QUBITS}")
+    if b and (n_groups < 1 or n_rows < 1 or n_ref < 1):
+        raise ValueError(f"clifford_sample: {b} circuits but {n_groups} groups, {n_rows} row words, {n_ref} reference words")
+    _vec(n_qubits, "n_qubits", b, torch.int32)
+    _vec(op_ptr, "op_ptr", b + 1, torch.int64)
+    _vec(thresh, "thresh", CLIFFORD_PAD, torch.int64)
+    _vec(ro_ptr, "ro_ptr", b, torch.int64)
+    _vec(group_ptr, "group_ptr", b + 1, torch.int64)
+    _vec(group_circ, "group_circ", n_groups, torch.int32)
+    _vec(group_mask, "group_mask", n_groups, torch.int32)
+    _vec(ids, "ids", n_groups, torch.int32)
+    _vec(masks, "masks", CLIFFORD_PAD, torch.int32)
+    _vec(term_ptr, "term_ptr", b + 1, torch.int64)
+    _vec(coeff, "coeff", n_terms, torch.float64)
+    _vec(term_mask, "term_mask", n_terms, torch.int32)
+    _vec(gterm_ptr, "gterm_ptr", n_groups + 1, torch.int64)
+    _vec(gterm, "gterm", n_gterm, torch.int32)
+    _vec(run_keys, "run_keys", b, torch.int64)
+    _vec(row_ptr, "row_ptr", n_groups, torch.int64)
+    _vec(ref_ptr, "ref_ptr", n_groups, torch.int64)
+    dev = ops.device
+    if any(t.device != dev for t in (n_qubits, op_ptr, thresh, ro_ptr, group_ptr, group_circ, group_mask, ids, masks, term_ptr, coeff,
+                                     term_mask, gterm_ptr, gterm, run_keys, row_ptr, ref_ptr)):
+        raise ValueError(f"clifford_sample: ops is on {dev}, another buffer is not")
+    rows = _int_out(rows, "rows", n_rows, dev)
+    reference = _int_out(reference, "reference", n_ref, dev)
+    if bits is not None or return_bits:
+        bits = _int_out(bits, "bits", n_ref * shots, dev)
+    term_sums = _int_out(term_sums, "term_sums", n_terms, dev)
+    term_values = _sim_out(term_values, "term_values", (n_terms,), dev)
+    values, variance = _sim_out(values, "values", (b,), dev), _sim_out(variance, "variance", (b,), dev)
+    code = _lib.load().mlqem_clifford_sample_f64(
+        b, _p(n_qubits), _p(op_ptr), _p(ops) if n_ops else None, n_ops, _p(thresh), int(thresh.shape[0]), _p(ro_ptr), _p(group_ptr),
+        _p(group_circ), _p(group_mask), n_groups, _p(ids), n_reg, n_lds, _p(masks), int(masks.shape[0]), _p(term_ptr),
+        _p(coeff) if n_terms else None, _p(term_mask) if n_terms else None, n_terms, _p(gterm_ptr), _p(gterm) if n_gterm else None,
+        n_gterm, _p(run_keys), shots, seed, max_qubits, _p(row_ptr), _p(rows), n_rows, _p(ref_ptr), _p(reference), n_ref,
+        _p(bits) if bits is not None and bits.numel() else None, n_ref * shots if bits is not None else 0,
+        _p(term_sums) if n_terms else None, _p(term_values) if n_terms else None, _p(values), _p(variance), _stream())
+    _lib.check(code, "mlqem_clifford_sample_f64")
+    return values, variance, term_values, term_sums, reference, bits

@@ -6,6 +6,8 @@ zero-noise extrapolation on it; the ``zne(cls)`` decorator lives there, so that 
 ``blackwater.sim.clifford`` is the path for wide circuits: Clifford circuits of up to 512 qubits, ideal and noisy, by carrying the
 observable backwards through the circuit (``compile_clifford`` / ``clifford_expectation_values``); ``zne_run(..., method="clifford")``
 extrapolates there too (``build_clifford_schedules``, ``ExponentialExtrapolator``).
+``blackwater.sim.frames`` draws measurement SHOTS there: Pauli-frame sampling of Clifford circuits under the depolarising + readout
+model (``compile_clifford_frames`` / ``sample_clifford_expectation_values`` / ``frame_counts``), bit strings of up to 512 qubits.
 ``Template`` / ``Param`` / ``compile_templates`` are parameterised circuits: one template lowered once, bound on the device at many
 parameter vectors (``bound_expectation_values``), with exact gradients by the parameter-shift rule (``parameter_shift``)."""
 from .program import (MAX_AMPS, MAX_QUBITS_DENSITY, MAX_QUBITS_VECTOR, SUPPORTED_GATES, WAVE_AMPS, NoiseModel, SimBatch,
@@ -17,6 +19,8 @@ from .clifford import (MAX_QUBITS_CLIFFORD, CliffordBatch, clifford_expectation_
 from .run import (DeviceEstimator, SampleResult, SimulatedJob, counts_dicts, default_run_keys, expectation_values, run_batch,
                   sample_batch, sample_expectation_values)
 from .run import TrajectoryResult, run_trajectories, trajectory_expectation_values
+from .frames import (MAX_GROUPS, FrameBatch, FrameResult, compile_clifford_frames, frame_counts, run_clifford_frames,
+                     sample_clifford_expectation_values)
 from .template import BoundBatch, Param, Template, compile_templates
 from .bound import bound_expectation_values, parameter_shift, run_bound
 from .zne import (CubicExtrapolator, CxAmplifier, ExponentialExtrapolator, GlobalFoldingAmplifier, LinearExtrapolator, LocalFoldingAmplifier,
@@ -33,4 +37,6 @@ __all__ = ["MAX_AMPS", "MAX_QUBITS_DENSITY", "MAX_QUBITS_VECTOR", "SUPPORTED_GAT
            "sample_expectation_values", "MAX_QUBITS_CLIFFORD", "CliffordBatch", "clifford_expectation_values", "compile_clifford",
            "is_clifford", "run_clifford", "ExponentialExtrapolator", "build_clifford_schedules", "invert_table", "run_clifford_folded",
            "MAX_TRAJECTORIES", "TrajectoryResult", "run_trajectories", "trajectory_expectation_values",
+           "MAX_GROUPS", "FrameBatch", "FrameResult", "compile_clifford_frames", "frame_counts", "run_clifford_frames",
+           "sample_clifford_expectation_values",
            "BoundBatch", "Param", "Template", "compile_templates", "bound_expectation_values", "parameter_shift", "run_bound"]

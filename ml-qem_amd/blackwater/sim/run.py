@@ -11,6 +11,7 @@ import numpy as np
 from ..library.primitives import make_estimator_result
 from ..data.circuit import Circuit
 from .clifford import clifford_expectation_values, is_clifford, refuse_non_pauli
+from .frames import sample_clifford_expectation_values
 from .program import (MAX_QUBITS_DENSITY, MAX_QUBITS_VECTOR, NoiseModel, SimBatch, check_seed, check_shots, check_trajectories,
                       compile_programs)
 from .bound import bound_expectation_values
@@ -234,6 +235,10 @@ _TRAJECTORY_SHOTS = ("DeviceEstimator(method='trajectories'): shots= is not supp
                      "out of scope; the estimate's own standard error is in the metadata); run it without shots")
 
 
+_FRAMES_SHOTS = ("DeviceEstimator(method='frames'): shots=None; frame sampling draws measurement shots (pass shots=N; the exact "
+                 "values of Clifford circuits are method='clifford')")
+
+
 class SimulatedJob:
     """The job of a :class:`DeviceEstimator` run: the values are already on the host when it is built."""
 
@@ -280,15 +285,24 @@ class DeviceEstimator:
     gate, any :class:`NoiseModel`); the values are means over ``trajectories`` (constructor; default 1 024) trajectories per circuit
     and ``metadata[k] = {"std_error": e_k, "trajectories": T}``.  It needs a noise model and draws no shots: ``noise=None`` and
     ``shots`` with it are refused.  Run keys are those of the shots path, so successive jobs do not repeat their draws.  ``"auto"``
-    never falls back to trajectories: an estimate with a standard error is chosen by name, not silently."""
+    never falls back to trajectories: an estimate with a standard error is chosen by name, not silently.
+    ``"frames"``: measurement shots of Clifford circuits of up to 512 qubits by Pauli-frame sampling
+    (:func:`sample_clifford_expectation_values`), ideal or under a depolarising + readout model; it needs ``shots`` (``shots=None``
+    is refused by name, and so are templates), ``metadata[k] = {"variance": v_k, "shots": shots}`` and the run keys are those of the
+    shots path.  ``"auto"`` never picks it."""
 
     METHODS = ("exact", "clifford", "auto", "trajectories")
+    SAMPLED_METHODS = ("frames",)   # chosen by name alone; "auto" never picks one
 
     def __init__(self, noise: Optional[NoiseModel] = None, device="cuda", shots: Optional[int] = None, seed: int = 0,
                  method: str = "exact", trajectories: int = 1024):
-        if method not in self.METHODS:
-            raise ValueError(f"DeviceEstimator: method = {method!r}, want one of {', '.join(self.METHODS)}")
+        if method not in self.METHODS + self.SAMPLED_METHODS:
+            raise ValueError(f"DeviceEstimator: method = {method!r}, want one of {', '.join(self.METHODS + self.SAMPLED_METHODS)}")
         self._method = method
+        if method == "frames":
+            if shots is None:
+                raise ValueError(_FRAMES_SHOTS)
+            refuse_non_pauli(noise, "DeviceEstimator(method='frames')")
         self._trajectories = check_trajectories(trajectories, "DeviceEstimator")
         if method == "trajectories":
             if noise is None:
@@ -315,6 +329,15 @@ class DeviceEstimator:
         seed = run_options.pop("seed", self._seed)
         if any(free):
             return self._run_templates(circuits, observables, parameter_values, free.index(True), shots)
+        if self._method == "frames":
+            if shots is None:
+                raise ValueError(_FRAMES_SHOTS)
+            shots, seed = check_shots(shots, "DeviceEstimator.run"), check_seed(seed, "DeviceEstimator.run")
+            self._count += 1
+            res = sample_clifford_expectation_values(circuits, observables, self._noise, shots=shots, seed=seed,
+                                                     run_keys=default_run_keys(len(circuits), self._count << 32), device=self._device)
+            variance = res.variance.cpu().numpy()
+            return SimulatedJob(res.values.cpu().numpy(), f"sim-{self._count}", [{"variance": float(v), "shots": shots} for v in variance])
         if self._method == "trajectories":
             if shots is not None:
                 raise ValueError(_TRAJECTORY_SHOTS)
@@ -351,7 +374,7 @@ class DeviceEstimator:
         if shots is not None:
             raise ValueError(f"DeviceEstimator: circuit {first} is a template with free parameters and shots= is set: shots are not "
                              f"drawn on the bound path; {how}")
-        if self._method in ("trajectories", "clifford"):
+        if self._method in ("trajectories", "clifford", "frames"):
             raise ValueError(f"DeviceEstimator(method={self._method!r}): circuit {first} is a template with free parameters; {how}")
         templates = [Template.from_any(c) for c in circuits]
         for k, (t, p) in enumerate(zip(templates, parameter_values)):

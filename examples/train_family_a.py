@@ -5,6 +5,7 @@ arena, train the reference's Family A GNN with the reference's loop shape, repor
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29511 \
         examples/train_family_a.py --qubits 100 --epochs 3                            # one rank per GPU, RCCL all-reduce
     python examples/train_family_a.py --qubits 100 --epochs 3 --clifford-labels      # simulated labels on Clifford circuits
+    python examples/train_family_a.py --qubits 100 --steps 5 --mps-labels            # simulated labels on the TFIM circuits themselves
 
 Everything the reference does on the host per step (PyG DataLoader collate, loss.item()) happens on the device here;
 the host only draws graph ids.  See INTEGRATION.md for moving an existing ml-qem dataset (.json / .pk) into shards.
@@ -23,7 +24,7 @@ sys.path[:0] = [os.path.join(ROOT, "ml-qem_amd")]
 from blackwater.data.arena import GraphArena                      # noqa: E402
 from blackwater.data.shards import pack_graphs, write_shard       # noqa: E402
 from blackwater.data.synthetic import (clifford_tfim_circuit, encode_corpus, random_clifford_circuit,  # noqa: E402
-                                       synthetic_backend, tfim_corpus)
+                                       synthetic_backend, tfim_circuit, tfim_corpus)
 from blackwater.metrics.improvement_factor import mitigation_report  # noqa: E402
 from blackwater.nn import ExpValCircuitGraphModelA                # noqa: E402
 from blackwater.train import DataParallelShard, Trainer           # noqa: E402
@@ -40,7 +41,14 @@ def main():
     ap.add_argument("--clifford-labels", action="store_true",
                     help="train on Clifford circuits (TFIM at multiples of pi / 2, and random Clifford layers) whose ideal and noisy "
                          "labels are simulated exactly on the device under the synthetic backend's noise model, at any --qubits <= 512")
+    ap.add_argument("--mps-labels", action="store_true",
+                    help="train on the TFIM circuits themselves (J ~ U(0, 0.66 pi): not Clifford) with ideal and noisy labels simulated "
+                         "on the device as matrix-product states: exact through 5 Trotter steps at bond 32, certified-approximate beyond")
+    ap.add_argument("--mps-bond", type=int, default=32, help="the bond cap of --mps-labels (1 .. 32)")
+    ap.add_argument("--mps-trajectories", type=int, default=16, help="Pauli-insertion trajectories per noisy label of --mps-labels")
     args = ap.parse_args()
+    if args.clifford_labels and args.mps_labels:
+        ap.error("--clifford-labels and --mps-labels choose different circuits: pass one")
 
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -52,7 +60,8 @@ def main():
 
     # 1. encode once (rank 0) into two shards; every rank then maps them and keeps its round-robin part
     shard_dir = args.shard_dir or os.path.join(tempfile.gettempdir(),
-                                               f"mlqem_example_{args.qubits}q" + ("_clifford" if args.clifford_labels else ""))
+                                               f"mlqem_example_{args.qubits}q" + ("_clifford" if args.clifford_labels else "")
+                                               + (f"_mps{args.mps_bond}" if args.mps_labels else ""))
     paths = [os.path.join(shard_dir, f"part{k}.mlqs") for k in range(2)]
     if rank == 0 and not all(os.path.exists(p) for p in paths):
         os.makedirs(shard_dir, exist_ok=True)
@@ -64,6 +73,17 @@ def main():
             circuits += [random_clifford_circuit(args.qubits, 2 + k % 8, k, two_q="cx", basis=True) for k in range(args.n_j)]
             noise = sim.NoiseModel.from_backend(synthetic_backend(args.qubits, "cx"))
             c = encode_corpus(circuits, args.qubits, two_q="cx", simulate=noise, device=dev, clifford=True)
+        elif args.mps_labels:
+            from blackwater import sim
+
+            rng = np.random.default_rng(42)
+            circuits = [tfim_circuit(args.qubits, s, float(j), two_q="cx")
+                        for s in range(1, args.steps + 1) for j in rng.uniform(0.0, 0.66 * np.pi, size=args.n_j)]
+            noise = sim.NoiseModel.from_backend(synthetic_backend(args.qubits, "cx"))
+            c = encode_corpus(circuits, args.qubits, two_q="cx", simulate=noise, device=dev, mps_bond=args.mps_bond,
+                              trajectories=args.mps_trajectories)
+            print(f"MPS labels at bond {args.mps_bond}: the worst certificate of the corpus is B = {c['mps_error_bound']:.3e} "
+                  f"(every ideal label is within 2 B of the exact <Z>)")
         else:
             c = tfim_corpus(args.qubits, list(range(1, args.steps + 1)), args.n_j, two_q="cx")
         half = len(c["x"]) // 2

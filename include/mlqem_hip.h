@@ -1930,6 +1930,104 @@ int mlqem_clifford_sample_f64(int64_t n_circuits, const int32_t* n_qubits, const
                               uint32_t* reference, int64_t n_ref, uint32_t* bits, int64_t n_bits, int32_t* term_sums,
                               double* term_values, double* values, double* variance, mlqem_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Matrix-product-state simulation (four additive symbols, the ABI version is unchanged).  A circuit whose two-qubit gates all act
+ * on neighbours (q, q + 1) of a line is simulated as a matrix-product state (MPS) with bonds of at most max_bond <=
+ * MLQEM_MPS_MAX_BOND = 32: any gate angle, up to MLQEM_MPS_MAX_QUBITS = 512 qubits; exact while no bond needs more than
+ * max_bond, and with an a-priori certificate where it truncates.  With Pauli-insertion trajectories the same kernel gives values
+ * under a depolarising + readout model.  blackwater.sim.mps lowers for it (compile_mps) and blackwater.native.ops.sim_run_mps /
+ * sim_mps_finish call it.
+ *
+ * Input.  n_qubits int32 [B]; op_ptr int64 [B + 1]; ops mlqem_sim_op [n_ops] = (kind, site, orientation, offset into params);
+ * params float64 [n_params], the last 32 padding, as in mlqem_sim_run_f64; run_keys int64 [B].  Site = qubit index.  Kinds:
+ *   MLQEM_MPS_OP_U1     a 2x2 matrix (row-major, 4 complex = 8 float64) on the physical index of `site`.  No decomposition.
+ *   MLQEM_MPS_OP_U2     a 4x4 matrix (row-major, 16 complex) on the bond (site, site + 1).  orientation 0: its basis index is
+ *                       bit(site) + 2 bit(site + 1); orientation 1: bit(site + 1) + 2 bit(site) (a gate whose first qubit is the
+ *                       upper one).  A coherent error is such a record; the host may multiply a run of gates confined to one bond
+ *                       into one (ideal lowering only, never across a noise record).
+ *   MLQEM_MPS_OP_DEPOL1 (lambda) on `site`; MLQEM_MPS_OP_DEPOL2 (lambda) on the bond, orientation as above: q0 = site + orientation
+ *                       is the gate's first qubit, q1 the other.  The NOISE records of a circuit are numbered 0, 1, ... in record
+ *                       order (lambda == 0 records included).  Noise record i with lambda != 0 draws ONE uniform u (below).
+ *                       d = 2 or 4, m = d^2 - 1 = 3 or 15, w = lambda / 4 or lambda / 16 (lambda * 0.25, lambda * 0.0625);
+ *                       s_0 = 1 - m w (the product m w rounded, then the difference), s_j = s_(j-1) + w.  The outcome is the
+ *                       first j in 0 .. m with s_j > u, else m.  j = 0: nothing (probability 1 - lambda (d^2 - 1) / d^2).  Else
+ *                       j = l0 + 4 l1 with the letter l0 on q0 and l1 on q1 (DEPOL1: j = l0), letters 0 I, 1 X, 2 Y, 3 Z, each
+ *                       applied as a one-site 2x2 matrix of entries 0, +-1, +-i (nothing is rounded).  lambda == 0: no draw.
+ *   Any other kind is skipped; a two-site record of a one-qubit circuit is skipped.
+ * u of noise record i, trajectory t: Philox4x32-10 with the key (seed & 0xffffffff, seed >> 32) and the counter
+ *   (i, t, run_key & 0xffffffff, run_key >> 32), run_key = run_keys[c]; u = ((x0 >> 5) 2^26 + (x1 >> 6)) 2^-53.  A unit therefore
+ * depends on (seed, run key, t, the circuit's records, max_bond, cutoff) alone: the same bits alone, in any batch, in any split
+ * into calls, and in a replayed graph.  No atomics.
+ *
+ * State.  Site tensors A[q] of shape (chi_l, 2, chi_r), complex float64, |0..0> at the start (all bonds 1), and an orthogonality
+ * centre, site 0 at the start.  A U2 record on the bond (q, q + 1):
+ *   1. the centre moves to q, one site at a time, by the bond primitive below with the identity as the gate (to the right on the
+ *      bond (centre, centre + 1); to the left on (centre - 1, centre), decomposing the transpose);
+ *   2. theta[(l, s0), (s1, r)] = sum_m A[q][l, s0, m] A[q + 1][m, s1, r], then the 4x4 matrix on (s0, s1);
+ *   3. the columns of theta are orthogonalised by one-sided (Hestenes) Jacobi rotations: cyclic sweeps in the round-robin order
+ *      (C columns, C even: round r = 0 .. C - 2 pairs (r, C - 1) and ((r + p) mod (C - 1), (r - p) mod (C - 1)), p = 1 .. C / 2 - 1),
+ *      a pair (a, b) rotated where |a^dagger b|^2 > MLQEM_MPS_JACOBI_TOL2 |a|^2 |b|^2 and both |a|^2 and |b|^2 exceed
+ *      MLQEM_MPS_JACOBI_NULL = (64 u)^2 of theta's weight (a column below it is the rounding of the dot products; rotations would
+ *      only shrink it into the denormals and never end; with a cutoff below MLQEM_MPS_JACOBI_NULL the keep rule may keep such a
+ *      column as it is, so keep the cutoff above it), until a sweep rotates nothing or
+ *      MLQEM_MPS_SWEEPS sweeps are done (a decomposition whose last allowed sweep still rotated is counted in traj_stats as not
+ *      converged: its columns may be short of orthogonal, and so may everything after it); edge bonds (fewer rows than columns) are NOT transposed: their null columns come out with
+ *      norm (numerically) zero and the keep rule drops them;
+ *   4. sigma_j^2 = the squared norm of column j, sorted descending (ties: the lower column first); total = their sum in that order;
+ *   5. KEEP RULE: the longest prefix of at most max_bond columns (and at most min(rows, columns)) with sigma^2 > cutoff * total; at
+ *      least one;
+ *   6. eps = (sum of the dropped sigma^2, in sorted order) / total is added to `discarded` and sqrt(2 eps) to `error_bound`; the
+ *      kept part is rescaled by sqrt(total / kept) to the norm before truncation;
+ *   7. A[q] = the kept columns over their norms; 8. A[q + 1] = A[q]^dagger theta, with the theta of step 2, times the rescaling;
+ *   9. the centre is q + 1.  The leftward move decomposes theta^T the same way: A[q + 1] takes the orthonormal factor (as rows), A[q]
+ *      the other, and the centre is q.  A move is also a decomposition under the same keep rule, max_bond included: the cap
+ *      cannot bind there, since the bond a move crosses already has at most max_bond columns and the identity does not raise
+ *      theta's rank, so what a move drops is rounding, and it adds that eps to both sums.
+ * Certificate.  A truncation replaces the normalised state phi by phi', |phi - phi'| <= sqrt(2 eps); unitaries keep distances, so
+ * |psi_exact - psi_mps| <= B = sum sqrt(2 eps) = `error_bound`, and |<O>_exact - <O>_mps| <= 2 B sum|coeff|.  The default cutoff
+ * 1e-26 drops the numerically-zero columns of a rank-deficient theta (a cx on a product state); a decomposition that drops only
+ * such columns adds at most sqrt(2 * 2 max_bond * cutoff) to B, the floor under `error_bound`.
+ *
+ * mlqem_mps_run_f64 runs the units (circuit circ_first + u / traj_count, trajectory traj_first + u % traj_count), u < circ_count *
+ * traj_count, one workgroup each, into `workspace` (mlqem_mps_workspace_bytes(max_qubits, max_bond, units); max_qubits >= every
+ * circuit's width) and writes traj_stats [trajectories][B][MLQEM_MPS_STATS] = (discarded, error_bound, largest bond,
+ * decompositions, decompositions that did not converge within MLQEM_MPS_SWEEPS, most sweeps of one decomposition) of each.
+ * mlqem_mps_terms_f64 reads the same workspace.  Terms: term t of circuit term_circ[t] is the Pauli string letters[term_off[t] + q],
+ * q < n (uint8, 0 I, 1 X, 2 Y, 3 Z).  readout float64 [n_sites][2] holds (a, b) of site site_ptr[c] + q: (1, 0) without readout
+ * noise, (1 - p01 - p10, p01 - p10) for a measured qubit with it; a Z slot uses the diagonal operator a Z + b I, an I slot plain
+ * I: exact, no term is expanded (the host refuses X / Y beside readout noise).  One launch contracts E <- sum A[q]^dagger A[q] E
+ * per unit into traj_norm [trajectories][B]; a second, one workgroup per (unit, term of term_first .. term_first + term_count),
+ * contracts with the term's operators and writes traj_term_values [trajectories][n_terms] = that over the unit's norm.
+ * mlqem_mps_finish_f64 forms, in trajectory order as mlqem_sim_run_trajectories_f64 does: term_values / term_std_error [n_terms],
+ * values / std_error [B] (0 at one trajectory), norm, discarded and error_bound [B] (means) and bond int32 [B] (the maximum).
+ * Bad sizes, a null or misaligned buffer: MLQEM_ERR_BAD_ARG; a count over 2^31 - 1: MLQEM_ERR_UNSUPPORTED; a workspace that is too
+ * small: MLQEM_ERR_WORKSPACE; all before anything is launched.  No host read: capturable.
+ * ---------------------------------------------------------------------------------------------------- */
+#define MLQEM_MPS_MAX_BOND 32
+#define MLQEM_MPS_MAX_QUBITS 512
+#define MLQEM_MPS_SWEEPS 30
+#define MLQEM_MPS_STATS 6
+#define MLQEM_MPS_JACOBI_TOL2 1e-28
+#define MLQEM_MPS_JACOBI_NULL 5.048709793414476e-29
+#define MLQEM_MPS_OP_U1 0
+#define MLQEM_MPS_OP_U2 5
+#define MLQEM_MPS_OP_DEPOL1 6
+#define MLQEM_MPS_OP_DEPOL2 7
+size_t mlqem_mps_workspace_bytes(int64_t max_qubits, int64_t max_bond, int64_t n_units);
+int mlqem_mps_run_f64(int64_t n_circuits, const int32_t* n_qubits, const int64_t* op_ptr, const mlqem_sim_op* ops, int64_t n_ops,
+                      const double* params, int64_t n_params, const int64_t* run_keys, int64_t circ_first, int64_t circ_count,
+                      int64_t traj_first, int64_t traj_count, int64_t trajectories, uint64_t seed, int64_t max_bond, double cutoff,
+                      int64_t max_qubits, void* workspace, size_t workspace_bytes, double* traj_stats, mlqem_stream_t stream);
+int mlqem_mps_terms_f64(int64_t n_circuits, const int32_t* n_qubits, int64_t circ_first, int64_t circ_count, int64_t traj_first,
+                        int64_t traj_count, int64_t trajectories, int64_t max_bond, int64_t max_qubits, const void* workspace,
+                        size_t workspace_bytes, int64_t term_first, int64_t term_count, int64_t n_terms, const int32_t* term_circ,
+                        const int64_t* term_off, const uint8_t* letters, int64_t n_letters, const int64_t* site_ptr,
+                        const double* readout, int64_t n_sites, double* traj_term_values, double* traj_norm, mlqem_stream_t stream);
+int mlqem_mps_finish_f64(int64_t n_circuits, int64_t n_terms, int64_t trajectories, const int64_t* term_ptr, const double* coeff,
+                         const double* traj_term_values, const double* traj_norm, const double* traj_stats, double* term_values,
+                         double* term_std_error, double* values, double* std_error, double* norm, double* discarded,
+                         double* error_bound, int32_t* bond, mlqem_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

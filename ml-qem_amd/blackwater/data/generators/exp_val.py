@@ -63,7 +63,7 @@ class ExpValueEntry:
 def exp_value_generator(backend: Any, n_qubits: int, circuit_depth: int, pauli_terms: int, pauli_coeff: float = 1.0,
                         max_entries: int = 1000, seed: int = 0, batch: int = 256, device="cuda", shots: Optional[int] = None,
                         sample_ideal: bool = False, trajectories: Optional[int] = None,
-                        frame_shots: Optional[int] = None) -> Iterator[ExpValueEntry]:
+                        frame_shots: Optional[int] = None, mps_bond: Optional[int] = None) -> Iterator[ExpValueEntry]:
     """Yields ``max_entries`` dataset entries of random circuits with simulated labels (reference: exp_val.py:92-170, which
     transpiles ``qiskit.circuit.random.random_circuit`` and runs Aer twice per circuit).
 
@@ -88,7 +88,19 @@ def exp_value_generator(backend: Any, n_qubits: int, circuit_depth: int, pauli_t
     ``frame_shots`` (default ``None``): the circuits are Clifford circuits (``synthetic.random_clifford_circuit`` in the backend's
     basis) of up to 512 qubits, the noisy value is a ``frame_shots``-shot estimate by Pauli-frame sampling
     (``sim.sample_clifford_expectation_values``, keyed as the shots are) and the ideal value stays the exact one
-    (``sim.clifford_expectation_values``).  Together with ``shots`` or ``trajectories`` it is refused by name."""
+    (``sim.clifford_expectation_values``).  Together with ``shots`` or ``trajectories`` it is refused by name.
+
+    ``mps_bond`` (default ``None``; with ``trajectories``): both values come from the matrix-product-state path at that bond
+    (``sim.mps_expectation_values``: ``n_qubits`` up to 512, the circuits' two-qubit gates act on neighbours), the noisy one as
+    the mean over ``trajectories`` Pauli-insertion trajectories, keyed as the shots are.  Without ``trajectories``, or together
+    with ``shots`` or ``frame_shots``, it is refused by name."""
+    if mps_bond is not None:
+        if shots is not None or frame_shots is not None:
+            raise ValueError("exp_value_generator: mps_bond together with " + ("shots" if shots is not None else "frame_shots") +
+                             " (no shots are drawn from a matrix-product state: its noisy values are means over trajectories=)")
+        if trajectories is None:
+            raise ValueError("exp_value_generator: mps_bond without trajectories (the noisy value of the MPS path is a mean over "
+                             "trajectories: pass trajectories=T)")
     if trajectories is not None and shots is not None:
         raise ValueError("exp_value_generator: trajectories together with shots (shot sampling over trajectories is not supported)")
     if frame_shots is not None and shots is not None:
@@ -123,6 +135,11 @@ def exp_value_generator(backend: Any, n_qubits: int, circuit_depth: int, pauli_t
             ideal = _to_host(sim.clifford_expectation_values(circuits, observables, None, device)[0])
             noisy = _to_host(sim.sample_clifford_expectation_values(circuits, observables, noise, shots=frame_shots, seed=seed,
                                                                     run_keys=keys, device=device).values)
+        elif mps_bond is not None:
+            keys = np.arange(done, done + count, dtype=np.int64)   # the entry's number, as on the shots path
+            ideal = _to_host(sim.mps_expectation_values(circuits, observables, max_bond=mps_bond, device=device).values)
+            noisy = _to_host(sim.mps_expectation_values(circuits, observables, noise, max_bond=mps_bond, trajectories=trajectories,
+                                                        seed=seed, run_keys=keys, device=device).values)
         elif trajectories is not None:
             keys = np.arange(done, done + count, dtype=np.int64)   # the entry's number, as on the shots path
             ideal = _to_host(sim.expectation_values(circuits, observables, None, device)[0])

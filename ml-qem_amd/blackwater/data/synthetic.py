@@ -225,7 +225,7 @@ def pauli_twirl(circ: Circuit, seed: int, two_q=("cx", "ecr")) -> Circuit:
 
 def encode_corpus(circuits, nq: int, two_q: str = "cx", seed: int = 7, exp_value_size: int = 1,
                   add_self_loops: bool = True, simulate=None, device="cuda", shots=None, sample_ideal: bool = False,
-                  clifford: bool = False, trajectories=None, frame_shots=None) -> Dict[str, list]:
+                  clifford: bool = False, trajectories=None, frame_shots=None, mps_bond=None) -> Dict[str, list]:
     """Arena-ready arrays (same keys as :func:`tfim_corpus`) for arbitrary circuits, encoded by the native encoder.
 
     ``simulate=None``: synthetic labels (a uniform draw and a made-up decay).  ``simulate=`` a ``blackwater.sim.NoiseModel``: ``y``
@@ -241,7 +241,14 @@ def encode_corpus(circuits, nq: int, two_q: str = "cx", seed: int = 7, exp_value
     ``frame_shots`` (with ``simulate``; default ``None``): every circuit must be a Clifford circuit of at most 512 qubits, and its
     noisy value is a ``frame_shots``-shot estimate by Pauli-frame sampling (``sim.sample_clifford_expectation_values``, keyed by
     ``seed`` and the circuit's position); the ideal value stays the exact one (``sim.clifford_expectation_values``).  Together with
-    ``shots`` or ``trajectories``, without ``simulate`` or on a circuit that is no Clifford circuit it is refused by name."""
+    ``shots`` or ``trajectories``, without ``simulate`` or on a circuit that is no Clifford circuit it is refused by name.
+    ``mps_bond`` (with ``simulate``; default ``None``: as ever): every circuit wider than the exact caps (5 qubits, 11 with
+    ``trajectories``) whose two-qubit gates all act on neighbouring qubits (``sim.is_line_circuit``) gets its ideal ``<Z>`` from the
+    matrix-product-state path at that bond (``sim.mps_expectation_values``: exact while the bonds fit, certified beyond), and with
+    ``trajectories`` its noisy ``<Z>`` from that many MPS trajectories (keyed by ``seed`` and the circuit's position; without
+    ``trajectories`` its noisy label stays the synthetic one).  With ``clifford=True`` Clifford circuits keep going to the exact
+    Clifford path.  The result then has the key ``"mps_error_bound"``: the worst certificate B of those circuits (|<Z> - exact| <=
+    2 B; 0.0 where no circuit took the path).  Together with ``shots`` or ``frame_shots``, or without ``simulate``, it is refused."""
     from .circuit import circuit_to_qasm
     from .native_encoder import NativeEncoder
 
@@ -254,9 +261,20 @@ def encode_corpus(circuits, nq: int, two_q: str = "cx", seed: int = 7, exp_value
         if simulate is None:
             raise ValueError("encode_corpus: frame_shots fills simulated labels, so it needs simulate= (a noise model)")
 
+    if mps_bond is not None:
+        if shots is not None or frame_shots is not None:
+            raise ValueError("encode_corpus: mps_bond together with " + ("shots" if shots is not None else "frame_shots") +
+                             " (no shots are drawn from a matrix-product state: its noisy values are means over trajectories=)")
+        if simulate is None:
+            raise ValueError("encode_corpus: mps_bond fills simulated labels, so it needs simulate= (a noise model)")
+        from ..sim.mps import _check_bond
+
+        mps_bond = _check_bond(mps_bond, "encode_corpus")
+
     props = get_backend_properties_v1(synthetic_backend(nq, two_q))
     enc = NativeEncoder(props)
     rng = np.random.default_rng(seed)
+    mps_error_bound = 0.0
     xs, eis, ys, noisy, depth, obs = [], [], [], [], [], []
     kept, z_qubits = [], []
     for circ in circuits:
@@ -314,6 +332,20 @@ def encode_corpus(circuits, nq: int, two_q: str = "cx", seed: int = 7, exp_value
             for j, k in enumerate(wide):
                 ys[k] = np.full(exp_value_size, exact[j])
                 noisy[k] = np.full(exp_value_size, under[j])
+        line = [k for k, circ in enumerate(kept) if mps_bond is not None and k not in wide
+                and cap < circ.num_qubits <= sim.MAX_QUBITS_MPS and sim.is_line_circuit(circ)]
+        if line:
+            labels = ["".join("Z" if q == z_qubits[k] else "I" for q in reversed(range(kept[k].num_qubits))) for k in line]
+            res = sim.mps_expectation_values([kept[k] for k in line], labels, max_bond=mps_bond, device=device)
+            exact, mps_error_bound = res.values.cpu().numpy(), float(res.error_bound.max())
+            for j, k in enumerate(line):
+                ys[k] = np.full(exp_value_size, exact[j])
+            if trajectories is not None:
+                res = sim.mps_expectation_values([kept[k] for k in line], labels, simulate, max_bond=mps_bond, trajectories=trajectories,
+                                                 seed=seed, run_keys=np.asarray(line, dtype=np.int64), device=device)
+                under, mps_error_bound = res.values.cpu().numpy(), max(mps_error_bound, float(res.error_bound.max()))
+                for j, k in enumerate(line):
+                    noisy[k] = np.full(exp_value_size, under[j])
         inside = [k for k, circ in enumerate(kept) if 1 <= circ.num_qubits <= cap]
         if inside:
             labels = ["".join("Z" if q == z_qubits[k] else "I" for q in reversed(range(kept[k].num_qubits))) for k in inside]
@@ -336,8 +368,11 @@ def encode_corpus(circuits, nq: int, two_q: str = "cx", seed: int = 7, exp_value
             for j, k in enumerate(inside):
                 ys[k] = np.full(exp_value_size, exact[j])
                 noisy[k] = np.full(exp_value_size, under[j])
-    return {"x": xs, "edge_index": eis, "y": np.asarray(ys, np.float32), "noisy": np.asarray(noisy, np.float32),
-            "depth": np.asarray(depth, np.float32), "observable": np.asarray(obs, np.float32)}
+    out = {"x": xs, "edge_index": eis, "y": np.asarray(ys, np.float32), "noisy": np.asarray(noisy, np.float32),
+           "depth": np.asarray(depth, np.float32), "observable": np.asarray(obs, np.float32)}
+    if mps_bond is not None:
+        out["mps_error_bound"] = mps_error_bound
+    return out
 
 
 def synthetic_backend(nq: int, two_q: str = "ecr", seed: int = 0) -> StaticBackend:

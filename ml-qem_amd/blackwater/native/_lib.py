@@ -268,6 +268,10 @@ SIGNATURES = {
     "mlqem_zne_combine_exp_f64": (_I, [_L, _L, _P, _P, _P, _P, _L, _P, _P, _P, _P]),
     "mlqem_clifford_sample_f64": (_I, [_L, _P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _L, _P, _L, _L, _P, _L, _P, _P, _P, _L, _P, _P, _L, _P,
                                        _L, _U, ctypes.c_int32, _P, _P, _L, _P, _P, _L, _P, _L, _P, _P, _P, _P, _P]),
+    "mlqem_mps_workspace_bytes": (_S, [_L, _L, _L]),
+    "mlqem_mps_run_f64": (_I, [_L, _P, _P, _P, _L, _P, _L, _P, _L, _L, _L, _L, _L, _U, _L, _D, _L, _P, _S, _P, _P]),
+    "mlqem_mps_terms_f64": (_I, [_L, _P, _L, _L, _L, _L, _L, _L, _L, _P, _S, _L, _L, _L, _P, _P, _P, _L, _P, _P, _L, _P, _P, _P]),
+    "mlqem_mps_finish_f64": (_I, [_L, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -2987,6 +2987,108 @@ def sim_run_trajectories(circ, op_ptr, ops, params, term_ptr, terms, coeff, ids,
     return values, std_error, term_values, term_std_error, norm, traj_term_values, traj_norm
 
 
+MPS_MAX_BOND, MPS_MAX_QUBITS, MPS_STATS = 32, 512, 6   # MLQEM_MPS_MAX_BOND / MLQEM_MPS_MAX_QUBITS / MLQEM_MPS_STATS
+
+
+def mps_workspace_bytes(max_qubits: int, max_bond: int, n_units: int) -> int:
+    """Bytes of the site-tensor workspace of ``n_units`` (circuit, trajectory) units (mlqem_mps_workspace_bytes)."""
+    if not 1 <= int(max_qubits) <= MPS_MAX_QUBITS or not 1 <= int(max_bond) <= MPS_MAX_BOND or int(n_units) < 0:
+        raise ValueError(f"mps: max_qubits = {max_qubits}, max_bond = {max_bond}, n_units = {n_units}; want 1 .. {MPS_MAX_QUBITS}, "
+                         f"1 .. {MPS_MAX_BOND} and >= 0")
+    return int(_lib.load().mlqem_mps_workspace_bytes(int(max_qubits), int(max_bond), int(n_units)))
+
+
+def sim_run_mps(n_qubits, op_ptr, ops, params, run_keys, term_circ, term_off, letters, site_ptr, readout, circuits, terms, trajectories_range,
+                trajectories, seed, max_bond, cutoff, max_qubits, workspace, traj_term_values, traj_norm, traj_stats):
+    """Runs the (circuit, trajectory) units of one chunk of a batch lowered by ``blackwater.sim.compile_mps`` as matrix-product
+    states and contracts their Pauli terms (mlqem_mps_run_f64, then mlqem_mps_terms_f64): fills the chunk's part of
+    ``traj_term_values`` float64 [T, n_terms], ``traj_norm`` [T, B] and ``traj_stats`` [T, B, MPS_STATS] and returns them (``None``: allocated
+    here, zero outside the chunk).
+
+    ``n_qubits`` int32 [B], ``op_ptr`` int64 [B + 1], ``ops`` int32 [n_ops, 4], ``params`` float64 [>= 32], ``run_keys`` int64 [B],
+    ``term_circ`` int32 [n_terms], ``term_off`` int64 [n_terms], ``letters`` uint8 [n_letters], ``site_ptr`` int64 [B + 1],
+    ``readout`` float64 [n_sites, 2]: the WHOLE batch, in the layout of include/mlqem_hip.h.  ``circuits`` / ``terms`` /
+    ``trajectories_range``: ``(first, count)`` of the chunk (``terms`` must be the terms of ``circuits``); ``trajectories`` T;
+    ``workspace`` uint8 of at least :func:`mps_workspace_bytes` for the chunk's units.  Shapes, dtypes and devices are checked
+    here, the contents are the lowering's to guarantee (the kernels clamp every index).  Nothing here waits for the device or reads a
+    tensor, and with the three outputs given nothing is allocated: capturable.  There is no CPU path."""
+    for t, name, dtype, cols in ((ops, "ops", torch.int32, 4), (readout, "readout", torch.float64, 2)):
+        if not t.is_cuda:
+            raise _lib.NativeLibraryError(f"{name} must live on the GPU (got {t.device}); there is no CPU path")
+        if t.dtype != dtype or t.shape[-1] != cols or not t.is_contiguous():
+            raise ValueError(f"mps: want contiguous {dtype} {name} [..., {cols}], got {tuple(t.shape)} {t.dtype}")
+    b, n_ops, n_terms, n_traj, seed = int(n_qubits.shape[0]), int(ops.shape[0]), int(term_circ.shape[0]), int(trajectories), int(seed)
+    (c0, cn), (t0, tn), (j0, jn) = ((int(v) for v in pair) for pair in (circuits, terms, trajectories_range))
+    if not 1 <= n_traj <= SIM_MAX_TRAJECTORIES or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"mps: trajectories = {n_traj} and seed = {seed}, want 1 .. 2^20 and 0 .. 2^64 - 1")
+    if not (0 <= c0 and 1 <= cn and c0 + cn <= b and 0 <= t0 and 0 <= tn and t0 + tn <= n_terms and 0 <= j0 and 1 <= jn and j0 + jn <= n_traj):
+        raise ValueError(f"mps: the chunk (circuits {circuits}, terms {terms}, trajectories {trajectories_range}) does not lie inside "
+                         f"{b} circuits, {n_terms} terms and {n_traj} trajectories")
+    if cn * jn > 2 ** 31 - 1 or max(tn, 1) * jn > 2 ** 31 - 1:
+        raise ValueError(f"mps: {cn} circuits (or {tn} terms) x {jn} trajectories exceed the 2^31 - 1 units one call can take; split the chunk")
+    _vec(n_qubits, "n_qubits", b, torch.int32)
+    _vec(op_ptr, "op_ptr", b + 1, torch.int64)
+    _vec(params, "params", SIM_PARAM_PAD, torch.float64)
+    _vec(run_keys, "run_keys", b, torch.int64)
+    _vec(term_circ, "term_circ", n_terms, torch.int32)
+    _vec(term_off, "term_off", n_terms, torch.int64)
+    _vec(letters, "letters", 0, torch.uint8)
+    _vec(site_ptr, "site_ptr", b + 1, torch.int64)
+    _vec(workspace, "workspace", mps_workspace_bytes(max_qubits, max_bond, cn * jn), torch.uint8)
+    if op_ptr.shape[0] != b + 1 or site_ptr.shape[0] != b + 1 or run_keys.shape[0] != b or term_off.shape[0] != n_terms or readout.dim() != 2:
+        raise ValueError(f"mps: want op_ptr and site_ptr [{b + 1}], run_keys [{b}], term_off [{n_terms}] and readout [n_sites, 2], got "
+                         f"{tuple(op_ptr.shape)}, {tuple(site_ptr.shape)}, {tuple(run_keys.shape)}, {tuple(term_off.shape)}, {tuple(readout.shape)}")
+    dev = ops.device
+    traj_term_values = _sim_out(traj_term_values, "traj_term_values", (n_traj, n_terms), dev)
+    traj_norm, traj_stats = _sim_out(traj_norm, "traj_norm", (n_traj, b), dev), _sim_out(traj_stats, "traj_stats", (n_traj, b, MPS_STATS), dev)
+    if any(t.device != dev for t in (n_qubits, op_ptr, params, run_keys, term_circ, term_off, letters, site_ptr, readout, workspace)):
+        raise ValueError(f"mps: ops is on {dev}, another buffer is not")
+    lib, ws_bytes = _lib.load(), int(workspace.shape[0])
+    code = lib.mlqem_mps_run_f64(b, _p(n_qubits), _p(op_ptr), _p(ops) if n_ops else None, n_ops, _p(params), int(params.shape[0]),
+                                 _p(run_keys), c0, cn, j0, jn, n_traj, seed, int(max_bond), float(cutoff), int(max_qubits), _p(workspace),
+                                 ws_bytes, _p(traj_stats), _stream())
+    _lib.check(code, "mlqem_mps_run_f64")
+    code = lib.mlqem_mps_terms_f64(b, _p(n_qubits), c0, cn, j0, jn, n_traj, int(max_bond), int(max_qubits), _p(workspace), ws_bytes, t0, tn,
+                                   n_terms, _p(term_circ) if n_terms else None, _p(term_off) if n_terms else None,
+                                   _p(letters) if n_terms else None, int(letters.shape[0]), _p(site_ptr), _p(readout), int(readout.shape[0]),
+                                   _p(traj_term_values) if n_terms else None, _p(traj_norm), _stream())
+    _lib.check(code, "mlqem_mps_terms_f64")
+    return traj_term_values, traj_norm, traj_stats
+
+
+def sim_mps_finish(term_ptr, coeff, traj_term_values, traj_norm, traj_stats, *, out=None):
+    """Means and standard errors over the trajectories of an MPS run (mlqem_mps_finish_f64): a dict of ``term_values`` /
+    ``term_std_error`` float64 [n_terms], ``values`` / ``std_error`` / ``norm`` / ``discarded`` / ``error_bound`` float64 [B] and
+    ``bond`` int32 [B].  ``out``: the same dict from an earlier call, then nothing is allocated (capturable)."""
+    if not traj_norm.is_cuda:
+        raise _lib.NativeLibraryError(f"traj_norm must live on the GPU (got {traj_norm.device}); there is no CPU path")
+    if traj_norm.dtype != torch.float64 or traj_norm.dim() != 2 or not traj_norm.is_contiguous() or traj_norm.shape[0] < 1:
+        raise ValueError(f"mps: want contiguous float64 traj_norm [T >= 1, B], got {tuple(traj_norm.shape)} {traj_norm.dtype}")
+    n_traj, b, dev = int(traj_norm.shape[0]), int(traj_norm.shape[1]), traj_norm.device
+    n_terms = int(coeff.shape[0])
+    _vec(term_ptr, "term_ptr", b + 1, torch.int64)
+    _vec(coeff, "coeff", n_terms, torch.float64)
+    traj_term_values = _sim_out(traj_term_values, "traj_term_values", (n_traj, n_terms), dev)
+    traj_stats = _sim_out(traj_stats, "traj_stats", (n_traj, b, MPS_STATS), dev)
+    if term_ptr.device != dev or coeff.device != dev:
+        raise ValueError(f"mps: traj_norm is on {dev}, another buffer is not")
+    out = dict(out or {})
+    for k, n in (("term_values", n_terms), ("term_std_error", n_terms), ("values", b), ("std_error", b), ("norm", b), ("discarded", b),
+                 ("error_bound", b)):
+        out[k] = _sim_out(out.get(k), k, (n,), dev)
+    if out.get("bond") is None:
+        out["bond"] = torch.zeros((b,), dtype=torch.int32, device=dev)
+    bond = out["bond"]
+    if bond.device != dev or bond.dtype != torch.int32 or tuple(bond.shape) != (b,) or not bond.is_contiguous():
+        raise ValueError(f"bond: want contiguous int32 [{b}] on {dev}, got {tuple(bond.shape)} {bond.dtype} {bond.device}")
+    code = _lib.load().mlqem_mps_finish_f64(
+        b, n_terms, n_traj, _p(term_ptr), _p(coeff) if n_terms else None, _p(traj_term_values) if n_terms else None, _p(traj_norm),
+        _p(traj_stats), _p(out["term_values"]) if n_terms else None, _p(out["term_std_error"]) if n_terms else None, _p(out["values"]),
+        _p(out["std_error"]), _p(out["norm"]), _p(out["discarded"]), _p(out["error_bound"]), _p(bond), _stream())
+    _lib.check(code, "mlqem_mps_finish_f64")
+    return out
+
+
 SIM_BOUND_TABLE, SIM_BOUND_PLAIN = 0, 1   # MLQEM_SIM_BOUND_TABLE / MLQEM_SIM_BOUND_PLAIN
 
 

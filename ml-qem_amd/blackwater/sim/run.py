@@ -15,6 +15,7 @@ from .frames import sample_clifford_expectation_values
 from .program import (MAX_QUBITS_DENSITY, MAX_QUBITS_VECTOR, NoiseModel, SimBatch, check_seed, check_shots, check_trajectories,
                       compile_programs)
 from .bound import bound_expectation_values
+from .mps import DEFAULT_CUTOFF, MAX_BOND, _check_bond, _check_cutoff, mps_expectation_values
 from .template import Template, has_free_parameters
 
 
@@ -239,6 +240,10 @@ _FRAMES_SHOTS = ("DeviceEstimator(method='frames'): shots=None; frame sampling d
                  "values of Clifford circuits are method='clifford')")
 
 
+_MPS_SHOTS = ("DeviceEstimator(method='mps'): shots= is not supported with it (no shots are drawn from a matrix-product state; a "
+              "noisy estimate's own standard error is in the metadata); run it without shots")
+
+
 class SimulatedJob:
     """The job of a :class:`DeviceEstimator` run: the values are already on the host when it is built."""
 
@@ -289,16 +294,27 @@ class DeviceEstimator:
     ``"frames"``: measurement shots of Clifford circuits of up to 512 qubits by Pauli-frame sampling
     (:func:`sample_clifford_expectation_values`), ideal or under a depolarising + readout model; it needs ``shots`` (``shots=None``
     is refused by name, and so are templates), ``metadata[k] = {"variance": v_k, "shots": shots}`` and the run keys are those of the
-    shots path.  ``"auto"`` never picks it."""
+    shots path.  ``"auto"`` never picks it.
+    ``"mps"``: matrix-product states of bond at most ``max_bond`` (:func:`mps_expectation_values`: circuits of up to 512 qubits whose
+    two-qubit gates act on neighbours, any angle; ``cutoff`` is the relative weight below which a column is dropped).  Without
+    ``noise`` the values are the ideal ones and ``metadata[k] = {"truncation_error_bound": B_k, "max_bond": the largest bond
+    reached}`` with |value - exact| <= 2 B_k sum|coeff|; with ``noise`` (depolarising + readout, coherent errors) they are means over
+    ``trajectories`` trajectories and the metadata also has ``"std_error"`` and ``"trajectories"``.  ``shots`` with it is refused by
+    name, and so are templates.  ``"auto"`` never picks it."""
 
     METHODS = ("exact", "clifford", "auto", "trajectories")
     SAMPLED_METHODS = ("frames",)   # chosen by name alone; "auto" never picks one
+    WIDE_METHODS = ("mps",)         # chosen by name alone too
 
     def __init__(self, noise: Optional[NoiseModel] = None, device="cuda", shots: Optional[int] = None, seed: int = 0,
-                 method: str = "exact", trajectories: int = 1024):
-        if method not in self.METHODS + self.SAMPLED_METHODS:
-            raise ValueError(f"DeviceEstimator: method = {method!r}, want one of {', '.join(self.METHODS + self.SAMPLED_METHODS)}")
+                 method: str = "exact", trajectories: int = 1024, max_bond: int = MAX_BOND, cutoff: float = DEFAULT_CUTOFF):
+        methods = self.METHODS + self.SAMPLED_METHODS + self.WIDE_METHODS
+        if method not in methods:
+            raise ValueError(f"DeviceEstimator: method = {method!r}, want one of {', '.join(methods)}")
         self._method = method
+        self._max_bond, self._cutoff = _check_bond(max_bond, "DeviceEstimator"), _check_cutoff(cutoff, "DeviceEstimator")
+        if method == "mps" and shots is not None:
+            raise ValueError(_MPS_SHOTS)
         if method == "frames":
             if shots is None:
                 raise ValueError(_FRAMES_SHOTS)
@@ -338,6 +354,20 @@ class DeviceEstimator:
                                                      run_keys=default_run_keys(len(circuits), self._count << 32), device=self._device)
             variance = res.variance.cpu().numpy()
             return SimulatedJob(res.values.cpu().numpy(), f"sim-{self._count}", [{"variance": float(v), "shots": shots} for v in variance])
+        if self._method == "mps":
+            if shots is not None:
+                raise ValueError(_MPS_SHOTS)
+            self._count += 1
+            noisy = self._noise is not None
+            res = mps_expectation_values(circuits, observables, self._noise, max_bond=self._max_bond, cutoff=self._cutoff,
+                                         trajectories=self._trajectories if noisy else None, seed=check_seed(seed, "DeviceEstimator.run"),
+                                         run_keys=default_run_keys(len(circuits), self._count << 32), device=self._device)
+            metadata = [{"truncation_error_bound": float(b), "max_bond": int(k)}
+                        for b, k in zip(res.error_bound.cpu().numpy(), res.bond.cpu().numpy())]
+            if noisy:
+                for m, e in zip(metadata, res.std_error.cpu().numpy()):
+                    m.update(std_error=float(e), trajectories=self._trajectories)
+            return SimulatedJob(res.values.cpu().numpy(), f"sim-{self._count}", metadata)
         if self._method == "trajectories":
             if shots is not None:
                 raise ValueError(_TRAJECTORY_SHOTS)
@@ -374,7 +404,7 @@ class DeviceEstimator:
         if shots is not None:
             raise ValueError(f"DeviceEstimator: circuit {first} is a template with free parameters and shots= is set: shots are not "
                              f"drawn on the bound path; {how}")
-        if self._method in ("trajectories", "clifford", "frames"):
+        if self._method in ("trajectories", "clifford", "frames", "mps"):
             raise ValueError(f"DeviceEstimator(method={self._method!r}): circuit {first} is a template with free parameters; {how}")
         templates = [Template.from_any(c) for c in circuits]
         for k, (t, p) in enumerate(zip(templates, parameter_values)):

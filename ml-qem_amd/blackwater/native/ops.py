@@ -2668,6 +2668,67 @@ def linreg_predict(x, coef, intercept, *, out=None):
 SIM_WAVE_AMPS = 256    # MLQEM_SIM_WAVE_AMPS: a wave per circuit up to here
 SIM_MAX_AMPS = 2048    # MLQEM_SIM_MAX_AMPS: a workgroup per circuit up to here; nothing beyond
 SIM_PARAM_PAD = 32     # float64 values of padding the parameter pool ends with
+SIM_MAX_SHOTS = 2 ** 20          # MLQEM_SIM_MAX_SHOTS
+SIM_MAX_TRAJECTORIES = 2 ** 20   # MLQEM_SIM_MAX_TRAJECTORIES
+
+
+def _sim_batch(circ, op_ptr, ops, params, term_ptr, terms, coeff, records=()):
+    """The checks every simulator call makes of a lowered batch, the first seven buffers of :func:`sim_run`: the record matrices
+    (and the caller's further ``(tensor, name)`` ones in ``records``), the pointer vectors and one device for all of them.
+    Returns ``(B, n_ops, n_terms, device)``."""
+    for t, name in ((circ, "circ"), (ops, "ops"), (terms, "terms")) + tuple(records):
+        if not t.is_cuda:
+            raise _lib.NativeLibraryError(f"{name} must live on the GPU (got {t.device}); there is no CPU path")
+        if t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != 4 or not t.is_contiguous():
+            raise ValueError(f"sim: want contiguous {torch.int32} {name} [., 4], got {tuple(t.shape)} {t.dtype}")
+    b, n_ops, n_terms = int(circ.shape[0]), int(ops.shape[0]), int(terms.shape[0])
+    _vec(op_ptr, "op_ptr", b + 1, torch.int64)
+    _vec(term_ptr, "term_ptr", b + 1, torch.int64)
+    _vec(params, "params", SIM_PARAM_PAD, torch.float64)
+    _vec(coeff, "coeff", n_terms, torch.float64)
+    _sim_same_device(circ.device, op_ptr, ops, params, term_ptr, terms, coeff)
+    return b, n_ops, n_terms, circ.device
+
+
+def _sim_same_device(dev, *buffers):
+    if any(t.device != dev for t in buffers):
+        raise ValueError(f"sim: circ is on {dev}, another buffer is not")
+
+
+def _sim_units(ids, n_wave, n_wg, limit, what, exact=False):
+    """``(n_wave, n_wg)`` as ints: none negative, adding up to at most ``limit`` (``exact``: to it; ``what`` names what it counts),
+    and ``ids`` int32 with as many entries."""
+    n_wave, n_wg = int(n_wave), int(n_wg)
+    if n_wave < 0 or n_wg < 0 or (n_wave + n_wg != limit if exact else n_wave + n_wg > limit):
+        raise ValueError(f"sim: n_wave = {n_wave} and n_wg = {n_wg} must be >= 0 and add up to {'the' if exact else 'at most'} {limit} {what}")
+    _vec(ids, "ids", n_wave + n_wg, torch.int32)
+    return n_wave, n_wg
+
+
+def _sim_seed(seed):
+    if not 0 <= int(seed) < 2 ** 64:
+        raise ValueError(f"sim: seed = {int(seed)}, want 0 .. 2^64 - 1")
+    return int(seed)
+
+
+def _sim_shots(shots):
+    if not 1 <= int(shots) <= SIM_MAX_SHOTS:
+        raise ValueError(f"sim: shots = {int(shots)}, want 1 .. 2^20")
+    return int(shots)
+
+
+def _sim_trajectories(trajectories):
+    if not 1 <= int(trajectories) <= SIM_MAX_TRAJECTORIES:
+        raise ValueError(f"sim: trajectories = {int(trajectories)}, want 1 .. 2^20")
+    return int(trajectories)
+
+
+def _sim_out(t, name, shape, dev):
+    if t is None:
+        return torch.zeros(shape, dtype=torch.float64, device=dev)
+    if not t.is_cuda or t.device != dev or t.dtype != torch.float64 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{name}: want contiguous float64 {list(shape)} on {dev}, got {tuple(t.shape)} {t.dtype} {t.device}")
+    return t
 
 
 def sim_run(circ, op_ptr, ops, params, term_ptr, terms, coeff, ids, n_wave, n_wg, *, term_values=None, values=None, norm=None):
@@ -2680,45 +2741,16 @@ def sim_run(circ, op_ptr, ops, params, term_ptr, terms, coeff, ids, n_wave, n_wg
     guarantee (the kernel clamps every index, so a malformed record computes garbage and faults nothing).  Nothing here waits for the
     device or reads a tensor's contents, and with the three outputs given nothing is allocated: the call can be captured in a
     hipGraph."""
-    for t, name, dtype, cols in ((circ, "circ", torch.int32, 4), (ops, "ops", torch.int32, 4), (terms, "terms", torch.int32, 4)):
-        if not t.is_cuda:
-            raise _lib.NativeLibraryError(f"{name} must live on the GPU (got {t.device}); there is no CPU path")
-        if t.dtype != dtype or t.dim() != 2 or t.shape[1] != cols or not t.is_contiguous():
-            raise ValueError(f"sim: want contiguous {dtype} {name} [., {cols}], got {tuple(t.shape)} {t.dtype}")
-    b, n_ops, n_terms = int(circ.shape[0]), int(ops.shape[0]), int(terms.shape[0])
-    _vec(op_ptr, "op_ptr", b + 1, torch.int64)
-    _vec(term_ptr, "term_ptr", b + 1, torch.int64)
-    _vec(params, "params", SIM_PARAM_PAD, torch.float64)
-    _vec(coeff, "coeff", n_terms, torch.float64)
-    n_wave, n_wg = int(n_wave), int(n_wg)
-    if n_wave < 0 or n_wg < 0 or n_wave + n_wg > b:
-        raise ValueError(f"sim: n_wave = {n_wave} and n_wg = {n_wg} must be >= 0 and add up to at most {b} circuits")
-    _vec(ids, "ids", n_wave + n_wg, torch.int32)
-    dev = circ.device
-    if any(t.device != dev for t in (op_ptr, ops, params, term_ptr, terms, coeff, ids)):
-        raise ValueError(f"sim: circ is on {dev}, another buffer is not")
-
-    def _out(t, name, n):
-        if t is None:
-            return torch.zeros((n,), dtype=torch.float64, device=dev)
-        if not t.is_cuda or t.device != dev or t.dtype != torch.float64 or tuple(t.shape) != (n,) or not t.is_contiguous():
-            raise ValueError(f"{name}: want contiguous float64 [{n}] on {dev}, got {tuple(t.shape)} {t.dtype} {t.device}")
-        return t
-
-    values, term_values, norm = _out(values, "values", b), _out(term_values, "term_values", n_terms), _out(norm, "norm", b)
+    b, n_ops, n_terms, dev = _sim_batch(circ, op_ptr, ops, params, term_ptr, terms, coeff)
+    n_wave, n_wg = _sim_units(ids, n_wave, n_wg, b, "circuits")
+    _sim_same_device(dev, ids)
+    values, term_values = _sim_out(values, "values", (b,), dev), _sim_out(term_values, "term_values", (n_terms,), dev)
+    norm = _sim_out(norm, "norm", (b,), dev)
     code = _lib.load().mlqem_sim_run_f64(b, _p(circ), _p(op_ptr), _p(ops) if n_ops else None, n_ops, _p(params), int(params.shape[0]),
                                          _p(term_ptr), _p(terms) if n_terms else None, _p(coeff) if n_terms else None, n_terms,
                                          _p(ids), n_wave, n_wg, _p(term_values) if n_terms else None, _p(values), _p(norm), _stream())
     _lib.check(code, "mlqem_sim_run_f64")
     return values, term_values, norm
-
-
-def _sim_out(t, name, shape, dev):
-    if t is None:
-        return torch.zeros(shape, dtype=torch.float64, device=dev)
-    if not t.is_cuda or t.device != dev or t.dtype != torch.float64 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-        raise ValueError(f"{name}: want contiguous float64 {list(shape)} on {dev}, got {tuple(t.shape)} {t.dtype} {t.device}")
-    return t
 
 
 def sim_run_folded(circ, op_ptr, ops, params, term_ptr, terms, coeff, sched_ptr, sched, ids, n_wave, n_wg, n_factors, *,
@@ -2732,30 +2764,18 @@ def sim_run_folded(circ, op_ptr, ops, params, term_ptr, terms, coeff, sched_ptr,
     wave-per-circuit runs first.  Shapes, dtypes and devices are checked here; the contents are the builder's to guarantee (the
     kernel clamps every index: a malformed schedule computes garbage and faults nothing).  Nothing here waits for the device or
     reads a tensor's contents, and with the three outputs given nothing is allocated: the call can be captured in a hipGraph."""
-    for t, name, dtype, cols in ((circ, "circ", torch.int32, 4), (ops, "ops", torch.int32, 4), (terms, "terms", torch.int32, 4)):
-        if not t.is_cuda:
-            raise _lib.NativeLibraryError(f"{name} must live on the GPU (got {t.device}); there is no CPU path")
-        if t.dtype != dtype or t.dim() != 2 or t.shape[1] != cols or not t.is_contiguous():
-            raise ValueError(f"sim: want contiguous {dtype} {name} [., {cols}], got {tuple(t.shape)} {t.dtype}")
-    b, n_ops, n_terms, f = int(circ.shape[0]), int(ops.shape[0]), int(terms.shape[0]), int(n_factors)
+    b, n_ops, n_terms, dev = _sim_batch(circ, op_ptr, ops, params, term_ptr, terms, coeff)
+    f = int(n_factors)
     if f < 1:
         raise ValueError(f"sim: n_factors = {f}, want at least 1")
-    _vec(op_ptr, "op_ptr", b + 1, torch.int64)
-    _vec(term_ptr, "term_ptr", b + 1, torch.int64)
-    _vec(params, "params", SIM_PARAM_PAD, torch.float64)
-    _vec(coeff, "coeff", n_terms, torch.float64)
     _vec(sched_ptr, "sched_ptr", f * b + 1, torch.int64)
     _vec(sched, "sched", 0, torch.int32)
     if op_ptr.shape[0] != b + 1 or term_ptr.shape[0] != b + 1 or sched_ptr.shape[0] != f * b + 1 or coeff.shape[0] != n_terms:
         raise ValueError(f"sim: want op_ptr and term_ptr [{b + 1}], sched_ptr [{f * b + 1}] and coeff [{n_terms}], got "
                          f"{tuple(op_ptr.shape)}, {tuple(term_ptr.shape)}, {tuple(sched_ptr.shape)} and {tuple(coeff.shape)}")
-    n_wave, n_wg, n_sched = int(n_wave), int(n_wg), int(sched.shape[0])
-    if n_wave < 0 or n_wg < 0 or n_wave + n_wg > f * b:
-        raise ValueError(f"sim: n_wave = {n_wave} and n_wg = {n_wg} must be >= 0 and add up to at most {f * b} runs")
-    _vec(ids, "ids", n_wave + n_wg, torch.int32)
-    dev = circ.device
-    if any(t.device != dev for t in (op_ptr, ops, params, term_ptr, terms, coeff, sched_ptr, sched, ids)):
-        raise ValueError(f"sim: circ is on {dev}, another buffer is not")
+    n_wave, n_wg = _sim_units(ids, n_wave, n_wg, f * b, "runs")
+    _sim_same_device(dev, sched_ptr, sched, ids)
+    n_sched = int(sched.shape[0])
     values, term_values = _sim_out(values, "values", (f, b), dev), _sim_out(term_values, "term_values", (f, n_terms), dev)
     norm = _sim_out(norm, "norm", (f, b), dev)
     code = _lib.load().mlqem_sim_run_folded_f64(
@@ -2794,29 +2814,15 @@ def zne_combine(term_values, weights, term_ptr, coeff, *, mitigated_terms=None, 
     return mitigated_values, mitigated_terms
 
 
-SIM_MAX_SHOTS = 2 ** 20   # MLQEM_SIM_MAX_SHOTS
-
-
 def _sim_common(circ, op_ptr, ops, params, term_ptr, terms, coeff, group_ptr, prob_ptr):
-    """The shape checks the measured simulator calls share; returns ``(B, n_ops, n_terms, n_groups, device)``."""
-    for t, name, dtype, cols in ((circ, "circ", torch.int32, 4), (ops, "ops", torch.int32, 4), (terms, "terms", torch.int32, 4)):
-        if not t.is_cuda:
-            raise _lib.NativeLibraryError(f"{name} must live on the GPU (got {t.device}); there is no CPU path")
-        if t.dtype != dtype or t.dim() != 2 or t.shape[1] != cols or not t.is_contiguous():
-            raise ValueError(f"sim: want contiguous {dtype} {name} [., {cols}], got {tuple(t.shape)} {t.dtype}")
-    b, n_ops, n_terms = int(circ.shape[0]), int(ops.shape[0]), int(terms.shape[0])
-    _vec(op_ptr, "op_ptr", b + 1, torch.int64)
-    _vec(term_ptr, "term_ptr", b + 1, torch.int64)
-    _vec(params, "params", SIM_PARAM_PAD, torch.float64)
-    _vec(coeff, "coeff", n_terms, torch.float64)
+    """:func:`_sim_batch` and the two group pointers of the measured calls; returns ``(B, n_ops, n_terms, n_groups, device)``."""
+    b, n_ops, n_terms, dev = _sim_batch(circ, op_ptr, ops, params, term_ptr, terms, coeff)
     _vec(group_ptr, "group_ptr", b + 1, torch.int64)
     _vec(prob_ptr, "prob_ptr", 1, torch.int64)
     if op_ptr.shape[0] != b + 1 or term_ptr.shape[0] != b + 1 or group_ptr.shape[0] != b + 1 or coeff.shape[0] != n_terms:
         raise ValueError(f"sim: want op_ptr, term_ptr and group_ptr [{b + 1}] and coeff [{n_terms}], got {tuple(op_ptr.shape)}, "
                          f"{tuple(term_ptr.shape)}, {tuple(group_ptr.shape)} and {tuple(coeff.shape)}")
-    dev = circ.device
-    if any(t.device != dev for t in (op_ptr, ops, params, term_ptr, terms, coeff, group_ptr, prob_ptr)):
-        raise ValueError(f"sim: circ is on {dev}, another buffer is not")
+    _sim_same_device(dev, group_ptr, prob_ptr)
     return b, n_ops, n_terms, int(prob_ptr.shape[0]) - 1, dev
 
 
@@ -2828,12 +2834,10 @@ def sim_run_measured(circ, op_ptr, ops, params, term_ptr, terms, coeff, group_pt
     EXACT ones.  ``group_ptr`` int64 [B + 1], ``prob_ptr`` int64 [n_groups + 1], ``n_outcomes`` the size of the pool (a host int:
     nothing here reads a tensor).  The other arguments and guarantees are :func:`sim_run`'s."""
     b, n_ops, n_terms, n_groups, dev = _sim_common(circ, op_ptr, ops, params, term_ptr, terms, coeff, group_ptr, prob_ptr)
-    n_wave, n_wg, n_outcomes = int(n_wave), int(n_wg), int(n_outcomes)
-    if n_wave < 0 or n_wg < 0 or n_wave + n_wg > b:
-        raise ValueError(f"sim: n_wave = {n_wave} and n_wg = {n_wg} must be >= 0 and add up to at most {b} circuits")
+    n_outcomes = int(n_outcomes)
     if n_outcomes < 0:
         raise ValueError(f"sim: n_outcomes = {n_outcomes}, want >= 0")
-    _vec(ids, "ids", n_wave + n_wg, torch.int32)
+    n_wave, n_wg = _sim_units(ids, n_wave, n_wg, b, "circuits")
     if ids.device != dev:
         raise ValueError(f"sim: circ is on {dev}, ids is not")
     values, term_values = _sim_out(values, "values", (b,), dev), _sim_out(term_values, "term_values", (n_terms,), dev)
@@ -2852,20 +2856,18 @@ def sim_run_folded_measured(circ, op_ptr, ops, params, term_ptr, terms, coeff, g
     probs)`` with ``probs`` float64 [F, n_outcomes], row f the probabilities of the runs at noise factor f.  The schedules must carry
     the measurement tail (``build_schedules`` appends it to every run)."""
     b, n_ops, n_terms, n_groups, dev = _sim_common(circ, op_ptr, ops, params, term_ptr, terms, coeff, group_ptr, prob_ptr)
-    f, n_wave, n_wg, n_outcomes = int(n_factors), int(n_wave), int(n_wg), int(n_outcomes)
+    n_outcomes = int(n_outcomes)
+    if n_outcomes < 0:
+        raise ValueError(f"sim: n_outcomes = {n_outcomes}, want >= 0")
+    f = int(n_factors)
     if f < 1:
         raise ValueError(f"sim: n_factors = {f}, want at least 1")
     _vec(sched_ptr, "sched_ptr", f * b + 1, torch.int64)
     _vec(sched, "sched", 0, torch.int32)
     if sched_ptr.shape[0] != f * b + 1:
         raise ValueError(f"sim: want sched_ptr [{f * b + 1}], got {tuple(sched_ptr.shape)}")
-    if n_wave < 0 or n_wg < 0 or n_wave + n_wg > f * b:
-        raise ValueError(f"sim: n_wave = {n_wave} and n_wg = {n_wg} must be >= 0 and add up to at most {f * b} runs")
-    if n_outcomes < 0:
-        raise ValueError(f"sim: n_outcomes = {n_outcomes}, want >= 0")
-    _vec(ids, "ids", n_wave + n_wg, torch.int32)
-    if any(t.device != dev for t in (sched_ptr, sched, ids)):
-        raise ValueError(f"sim: circ is on {dev}, another buffer is not")
+    n_wave, n_wg = _sim_units(ids, n_wave, n_wg, f * b, "runs")
+    _sim_same_device(dev, sched_ptr, sched, ids)
     n_sched = int(sched.shape[0])
     values, term_values = _sim_out(values, "values", (f, b), dev), _sim_out(term_values, "term_values", (f, n_terms), dev)
     norm, probs = _sim_out(norm, "norm", (f, b), dev), _sim_out(probs, "probs", (f, n_outcomes), dev)
@@ -2899,11 +2901,7 @@ def sim_sample(circ, term_ptr, terms, coeff, group_ptr, term_group, prob_ptr, gr
     lead = tuple(probs.shape[:-1])
     f, n_outcomes = (int(probs.shape[0]) if lead else 1), int(probs.shape[-1])
     b, n_terms, n_groups = int(circ.shape[0]), int(terms.shape[0]), int(group_circ.shape[0])
-    shots, n_wave, n_wg, seed = int(shots), int(n_wave), int(n_wg), int(seed)
-    if not 1 <= shots <= SIM_MAX_SHOTS:
-        raise ValueError(f"sim: shots = {shots}, want 1 .. 2^20")
-    if not 0 <= seed < 2 ** 64:
-        raise ValueError(f"sim: seed = {seed}, want 0 .. 2^64 - 1")
+    shots, n_wave, n_wg, seed = _sim_shots(shots), int(n_wave), int(n_wg), _sim_seed(seed)
     if f < 1 or n_wave < 0 or n_wg < 0 or n_wave + n_wg != f * n_groups:
         raise ValueError(f"sim: n_wave = {n_wave} and n_wg = {n_wg} must be >= 0 and add up to the {f * n_groups} (factor, group) pairs")
     _vec(term_ptr, "term_ptr", b + 1, torch.int64)
@@ -2932,9 +2930,6 @@ def sim_sample(circ, term_ptr, terms, coeff, group_ptr, term_group, prob_ptr, gr
     return values, variance, term_values, counts
 
 
-SIM_MAX_TRAJECTORIES = 2 ** 20   # MLQEM_SIM_MAX_TRAJECTORIES
-
-
 def sim_run_trajectories(circ, op_ptr, ops, params, term_ptr, terms, coeff, ids, n_wave, n_wg, run_keys, trajectories, seed, *,
                          traj_term_values=None, traj_norm=None, term_values=None, term_std_error=None, values=None, std_error=None,
                          norm=None):
@@ -2947,33 +2942,16 @@ def sim_run_trajectories(circ, op_ptr, ops, params, term_ptr, terms, coeff, ids,
     the unravelling and the counter layout: a trajectory's bits depend on (seed, run key, trajectory, circuit) alone.  The means and
     standard errors are formed on the device in trajectory order.  Nothing here waits for the device or reads a tensor, and with
     the seven outputs given nothing is allocated: capturable.  There is no CPU path."""
-    for t, name, dtype, cols in ((circ, "circ", torch.int32, 4), (ops, "ops", torch.int32, 4), (terms, "terms", torch.int32, 4)):
-        if not t.is_cuda:
-            raise _lib.NativeLibraryError(f"{name} must live on the GPU (got {t.device}); there is no CPU path")
-        if t.dtype != dtype or t.dim() != 2 or t.shape[1] != cols or not t.is_contiguous():
-            raise ValueError(f"sim: want contiguous {dtype} {name} [., {cols}], got {tuple(t.shape)} {t.dtype}")
-    b, n_ops, n_terms = int(circ.shape[0]), int(ops.shape[0]), int(terms.shape[0])
-    n_wave, n_wg, n_traj, seed = int(n_wave), int(n_wg), int(trajectories), int(seed)
-    if not 1 <= n_traj <= SIM_MAX_TRAJECTORIES:
-        raise ValueError(f"sim: trajectories = {n_traj}, want 1 .. 2^20")
-    if not 0 <= seed < 2 ** 64:
-        raise ValueError(f"sim: seed = {seed}, want 0 .. 2^64 - 1")
-    if n_wave < 0 or n_wg < 0 or n_wave + n_wg != b:
-        raise ValueError(f"sim: n_wave = {n_wave} and n_wg = {n_wg} must be >= 0 and add up to the {b} circuits")
+    b, n_ops, n_terms, dev = _sim_batch(circ, op_ptr, ops, params, term_ptr, terms, coeff)
+    n_traj, seed = _sim_trajectories(trajectories), _sim_seed(seed)
+    n_wave, n_wg = _sim_units(ids, n_wave, n_wg, b, "circuits", exact=True)
     if b * n_traj > 2 ** 31 - 1:
         raise ValueError(f"sim: {b} circuits x {n_traj} trajectories exceed the 2^31 - 1 units one call can take; split the batch")
-    _vec(op_ptr, "op_ptr", b + 1, torch.int64)
-    _vec(term_ptr, "term_ptr", b + 1, torch.int64)
-    _vec(params, "params", SIM_PARAM_PAD, torch.float64)
-    _vec(coeff, "coeff", n_terms, torch.float64)
-    _vec(ids, "ids", b, torch.int32)
     _vec(run_keys, "run_keys", b, torch.int64)
     if op_ptr.shape[0] != b + 1 or term_ptr.shape[0] != b + 1 or coeff.shape[0] != n_terms or run_keys.shape[0] != b or ids.shape[0] != b:
         raise ValueError(f"sim: want op_ptr and term_ptr [{b + 1}], coeff [{n_terms}], ids and run_keys [{b}], got {tuple(op_ptr.shape)}, "
                          f"{tuple(term_ptr.shape)}, {tuple(coeff.shape)}, {tuple(ids.shape)} and {tuple(run_keys.shape)}")
-    dev = circ.device
-    if any(t.device != dev for t in (op_ptr, ops, params, term_ptr, terms, coeff, ids, run_keys)):
-        raise ValueError(f"sim: circ is on {dev}, another buffer is not")
+    _sim_same_device(dev, ids, run_keys)
     traj_term_values = _sim_out(traj_term_values, "traj_term_values", (n_traj, n_terms), dev)
     traj_norm = _sim_out(traj_norm, "traj_norm", (n_traj, b), dev)
     term_values, term_std_error = _sim_out(term_values, "term_values", (n_terms,), dev), _sim_out(term_std_error, "term_std_error", (n_terms,), dev)
@@ -3104,35 +3082,21 @@ def sim_run_bound(circ, op_ptr, ops, params, term_ptr, terms, coeff, theta, runs
     (``SIM_BOUND_TABLE``) or trig per record (``SIM_BOUND_PLAIN``); the same bits.  Shapes, dtypes and devices are checked here;
     the contents are ``compile_templates``' to guarantee (the kernel clamps every index).  Nothing here waits for the device, and
     with the three outputs given nothing is allocated: the call can be captured in a hipGraph.  There is no CPU path."""
-    for t, name, dtype, cols in ((circ, "circ", torch.int32, 4), (ops, "ops", torch.int32, 4), (terms, "terms", torch.int32, 4),
-                                 (runs, "runs", torch.int32, 4)):
-        if not t.is_cuda:
-            raise _lib.NativeLibraryError(f"{name} must live on the GPU (got {t.device}); there is no CPU path")
-        if t.dtype != dtype or t.dim() != 2 or t.shape[1] != cols or not t.is_contiguous():
-            raise ValueError(f"sim: want contiguous {dtype} {name} [., {cols}], got {tuple(t.shape)} {t.dtype}")
-    b, n_ops, n_terms, n_runs = int(circ.shape[0]), int(ops.shape[0]), int(terms.shape[0]), int(runs.shape[0])
+    b, n_ops, n_terms, dev = _sim_batch(circ, op_ptr, ops, params, term_ptr, terms, coeff, records=((runs, "runs"),))
+    n_runs, n_out = int(runs.shape[0]), int(n_out_terms)
     if form not in (SIM_BOUND_TABLE, SIM_BOUND_PLAIN):
         raise ValueError(f"sim: form = {form!r}, want SIM_BOUND_TABLE (0) or SIM_BOUND_PLAIN (1)")
     if not theta.is_cuda or theta.dtype != torch.float64 or theta.dim() != 2 or not theta.is_contiguous() or theta.shape[0] < 1 or theta.shape[1] < 1:
         raise ValueError(f"sim: want contiguous float64 theta [n_rows >= 1, ld >= 1] on the GPU, got {tuple(theta.shape)} {theta.dtype} {theta.device}")
-    _vec(op_ptr, "op_ptr", b + 1, torch.int64)
-    _vec(term_ptr, "term_ptr", b + 1, torch.int64)
-    _vec(params, "params", SIM_PARAM_PAD, torch.float64)
-    _vec(coeff, "coeff", n_terms, torch.float64)
     _vec(shift, "shift", n_runs, torch.float64)
     _vec(run_term_ptr, "run_term_ptr", n_runs + 1, torch.int64)
-    n_wave, n_wg, n_out = int(n_wave), int(n_wg), int(n_out_terms)
-    if n_wave < 0 or n_wg < 0 or n_wave + n_wg > n_runs:
-        raise ValueError(f"sim: n_wave = {n_wave} and n_wg = {n_wg} must be >= 0 and add up to at most {n_runs} runs")
+    n_wave, n_wg = _sim_units(ids, n_wave, n_wg, n_runs, "runs")
     if n_out < 0 or (n_wave + n_wg > 0 and b < 1):
         raise ValueError(f"sim: n_out_terms = {n_out} must be >= 0, and runs need at least one template (got {b})")
-    _vec(ids, "ids", n_wave + n_wg, torch.int32)
     if shift.shape[0] != n_runs or run_term_ptr.shape[0] != n_runs + 1 or op_ptr.shape[0] != b + 1 or term_ptr.shape[0] != b + 1:
         raise ValueError(f"sim: want shift [{n_runs}], run_term_ptr [{n_runs + 1}], op_ptr and term_ptr [{b + 1}], got "
                          f"{tuple(shift.shape)}, {tuple(run_term_ptr.shape)}, {tuple(op_ptr.shape)} and {tuple(term_ptr.shape)}")
-    dev = circ.device
-    if any(t.device != dev for t in (op_ptr, ops, params, term_ptr, terms, coeff, theta, runs, shift, ids, run_term_ptr)):
-        raise ValueError(f"sim: circ is on {dev}, another buffer is not")
+    _sim_same_device(dev, theta, runs, shift, ids, run_term_ptr)
     values, norm = _sim_out(values, "values", (n_runs,), dev), _sim_out(norm, "norm", (n_runs,), dev)
     term_values = _sim_out(term_values, "term_values", (n_out,), dev)
     code = _lib.load().mlqem_sim_run_bound_f64(

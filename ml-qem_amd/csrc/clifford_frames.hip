@@ -338,15 +338,11 @@ __global__ __launch_bounds__(kBlock) void frames_finish_kernel(int64_t n_circuit
   const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (c >= n_circuits) return;
   const int64_t tb = frm_clamp(term_ptr[c], (int64_t)0, n_terms), te = frm_clamp(term_ptr[c + 1], tb, n_terms);
-  double val = 0.0, var = 0.0;
-  for (int64_t t = tb; t < te; ++t) {
-    const double tv = (double)term_sums[t] / (double)shots, cf = coeff[t];
+  sample_value_variance(coeff, tb, te, values[c], variance[c], [&](int64_t t) {
+    const double tv = (double)term_sums[t] / (double)shots;
     term_values[t] = tv;
-    val = __builtin_fma(cf, tv, val);
-    var = __builtin_fma(cf * cf, __builtin_fma(-tv, tv, 1.0), var);
-  }
-  values[c] = val;
-  variance[c] = var;
+    return tv;
+  });
 }
 
 }  // namespace

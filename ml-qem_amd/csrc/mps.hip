@@ -455,8 +455,8 @@ __global__ __launch_bounds__(kBlock) void mps_terms_kernel(int B, const int32_t*
   }
 }
 
-// Means and standard errors over the trajectories, in trajectory order, as mlqem_sim_run_trajectories_f64 forms them; the
-// discarded weight and the certificate are means, the bond a maximum.
+// Means and standard errors over the trajectories, in trajectory order, from the functions mlqem_sim_run_trajectories_f64 forms
+// them with (sim_ctx.hpp); the discarded weight and the certificate are means, the bond a maximum.
 __global__ __launch_bounds__(kBlock) void mps_finish_kernel(int64_t B, int64_t n_terms, int T, const int64_t* __restrict__ term_ptr,
                                                             const double* __restrict__ coeff, const double* __restrict__ traj_terms,
                                                             const double* __restrict__ traj_norm, const double* __restrict__ traj_stats,
@@ -467,23 +467,15 @@ __global__ __launch_bounds__(kBlock) void mps_finish_kernel(int64_t B, int64_t n
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   const double count = (double)T, pairs = (double)T * (double)(T - 1);
   if (i < n_terms) {
-    double acc = 0.0, m2 = 0.0;
-    for (int t = 0; t < T; ++t) acc = acc + traj_terms[(int64_t)t * n_terms + i];
-    const double mean = acc / count;
-    for (int t = 0; t < T; ++t) {
-      const double d = traj_terms[(int64_t)t * n_terms + i] - mean;
-      m2 = __builtin_fma(d, d, m2);
-    }
-    term_values[i] = mean;
-    term_se[i] = T > 1 ? sqrt(m2 / pairs) : 0.0;
+    const TrajStat s = traj_term_stats(traj_terms, n_terms, T, i);
+    term_values[i] = s.mean;
+    term_se[i] = s.se;
   }
   if (i < B) {
     const int64_t tb = min(max(term_ptr[i], (int64_t)0), n_terms), te = min(max(term_ptr[i + 1], tb), n_terms);
     double acc = 0.0, nacc = 0.0, dacc = 0.0, bacc = 0.0, m2 = 0.0, most = 1.0;
     for (int t = 0; t < T; ++t) {
-      double v = 0.0;
-      for (int64_t k = tb; k < te; ++k) v = __builtin_fma(coeff[k], traj_terms[(int64_t)t * n_terms + k], v);
-      acc = acc + v;
+      acc = acc + traj_value(coeff, traj_terms, n_terms, t, tb, te);
       nacc = nacc + traj_norm[(int64_t)t * B + i];
       const double* s = traj_stats + ((int64_t)t * B + i) * kMpsStats;
       dacc = dacc + s[0];
@@ -492,9 +484,7 @@ __global__ __launch_bounds__(kBlock) void mps_finish_kernel(int64_t B, int64_t n
     }
     const double mean = acc / count;
     for (int t = 0; t < T; ++t) {
-      double v = 0.0;
-      for (int64_t k = tb; k < te; ++k) v = __builtin_fma(coeff[k], traj_terms[(int64_t)t * n_terms + k], v);
-      const double d = v - mean;
+      const double d = traj_value(coeff, traj_terms, n_terms, t, tb, te) - mean;
       m2 = __builtin_fma(d, d, m2);
     }
     values[i] = mean;

@@ -36,7 +36,8 @@
 // global memory, keeps a CDF and the counts in LDS -- not the 32 KB state -- and draws the shots with Philox4x32-10;
 // sample_finish_kernel then adds up values and variances.
 //
-// SimCtx (the passes), the state's types and Philox4x32-10 live in sim_ctx.hpp, which sim_traj.hip (quantum trajectories) shares.
+// SimCtx (the passes), the record decode, the norm pass, the switch over the record kinds, the state's types and Philox4x32-10
+// live in sim_ctx.hpp: sim_bound.hip (runs of templates) and sim_traj.hip (quantum trajectories) call the same copy.
 #include "sim_ctx.hpp"
 
 namespace mlqem {
@@ -70,11 +71,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WG ? 4 :
   __shared__ sim_c state[WG ? kSimMaxAmps : kBlock / kWave * kSimWaveAmps];
   __shared__ double red[8];
   SimCtx<WG> cx;
-  const int slot = WG ? (int)blockIdx.x : __builtin_amdgcn_readfirstlane((int)blockIdx.x * (kBlock / kWave) + ((int)threadIdx.x >> 6));
+  const int slot = cx.begin(state, red);
   if (slot >= count) return;   // a wave of a partly filled workgroup: wave-uniform, and this variant has no workgroup barrier
-  cx.tid = WG ? (int)threadIdx.x : (int)threadIdx.x & (kWave - 1);
-  cx.st = WG ? state : state + ((int)threadIdx.x >> 6) * kSimWaveAmps;
-  cx.red = red;
   const int tid = cx.tid;
   const int run = FOLD ? __builtin_amdgcn_readfirstlane(min(max(ids[slot], 0), n_runs - 1)) : 0;
   const int c = FOLD ? run % B : __builtin_amdgcn_readfirstlane(min(max(ids[slot], 0), B - 1));
@@ -104,15 +102,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WG ? 4 :
   double nrm = 0.0;
   for (int k = 0; k <= n_step; ++k) {
     if (k == n_main) {   // <psi|psi> or Tr rho, before any readout op
-      double part = 0.0;
-      const int cnt = density ? 1 << n : A, mul = density ? (1 << n) + 1 : 1;
-      for (int i0 = 0; i0 < cnt; i0 += cx.T) {
-        const int i = i0 + tid;
-        const sim_c v = cx.st[((i & (cnt - 1)) * mul) & (A - 1)];
-        const double add = density ? v.x : v.x * v.x + v.y * v.y;
-        part = part + (i < cnt ? add : 0.0);
-      }
-      nrm = cx.reduce(part, 0);
+      nrm = sim_norm(cx, n, density);
       if (WG) __syncthreads();   // red[0..3] is free again
     }
     if (k == n_step) break;
@@ -125,12 +115,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WG ? 4 :
       dg = entry & 1;
     }
     const sim_i4 op = ops[ob + at];   // kind, q0, q1, offset into params
-    const int kind = __builtin_amdgcn_readfirstlane(op.x);
-    const int q0 = __builtin_amdgcn_readfirstlane(min(max(op.y, 0), n - 1)), q1 = __builtin_amdgcn_readfirstlane(min(max(op.z, 0), n - 1));
-    const int64_t po = min((int64_t)max(op.w, 0), n_params - kSimParamPad);
-    const double* m = params + po;
+    const SimRec rec = sim_decode(op, n, params, n_params);
     if constexpr (MEAS) {
-      if (kind == MLQEM_SIM_OP_MEASURE) {   // probabilities of the 2^n outcomes: |psi_j|^2, or Re rho_jj
+      if (rec.kind == MLQEM_SIM_OP_MEASURE) {   // probabilities of the 2^n outcomes: |psi_j|^2, or Re rho_jj
         const int64_t g = __builtin_amdgcn_readfirstlane(op.w);   // the group's number in prob_ptr
         const int64_t gb = min(max(group_ptr[c], (int64_t)0), n_groups), ge = min(max(group_ptr[c + 1], gb), n_groups);
         const int64_t pb = prob_ptr[min(max(g, (int64_t)0), n_groups)];   // prob_ptr has n_groups + 1 entries
@@ -148,76 +135,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WG ? 4 :
         continue;
       }
     }
-    switch (kind) {
-      case MLQEM_SIM_OP_U1:
-        if (FOLD) {   // the inverse swaps the off-diagonal entries and negates the imaginary parts: no arithmetic, no rounding
-          const int o01 = dg ? 4 : 2, o10 = dg ? 2 : 4;
-          const sim_c u00{m[0], dg ? -m[1] : m[1]}, u01{m[o01], dg ? -m[o01 + 1] : m[o01 + 1]},
-              u10{m[o10], dg ? -m[o10 + 1] : m[o10 + 1]}, u11{m[6], dg ? -m[7] : m[7]};
-          cx.pair(nbits, q0, u00, u01, u10, u11, 1);
-          if (density) cx.pair(nbits, q0 + n, sim_c{u00.x, -u00.y}, sim_c{u01.x, -u01.y}, sim_c{u10.x, -u10.y}, sim_c{u11.x, -u11.y}, 1);
-          break;
-        }
-        cx.pair(nbits, q0, sim_c{m[0], m[1]}, sim_c{m[2], m[3]}, sim_c{m[4], m[5]}, sim_c{m[6], m[7]}, 1);
-        if (density) cx.pair(nbits, q0 + n, sim_c{m[0], -m[1]}, sim_c{m[2], -m[3]}, sim_c{m[4], -m[5]}, sim_c{m[6], -m[7]}, 1);
-        break;
-      case MLQEM_SIM_OP_DIAG1: {
-        const sim_c d0{m[0], dg ? -m[1] : m[1]}, d1{m[2], dg ? -m[3] : m[3]};
-        if (density) {
-          cx.element([&](int i) {   // d[row bit] conj(d[column bit])
-            const bool r = (i >> q0) & 1, cc = (i >> (q0 + n)) & 1;
-            return cmul(sim_c{r ? d1.x : d0.x, r ? d1.y : d0.y}, sim_c{cc ? d1.x : d0.x, cc ? -d1.y : -d0.y});
-          });
-        } else {
-          cx.element([&](int i) { return (i >> q0) & 1 ? d1 : d0; });
-        }
-        break;
-      }
-      case MLQEM_SIM_OP_CZ: {
-        const int mrow = (1 << q0) | (1 << q1), mcol = density ? mrow << n : 0;
-        cx.element([&](int i) {
-          const bool neg = ((i & mrow) == mrow) != (density && (i & mcol) == mcol);
-          return sim_c{neg ? -1.0 : 1.0, 0.0};
-        });
-        break;
-      }
-      case MLQEM_SIM_OP_CX:
-        cx.gather([&](int i) {
-          int j = i ^ (((i >> q0) & 1) << q1);
-          if (density) j ^= ((i >> (q0 + n)) & 1) << (q1 + n);
-          return j;
-        });
-        break;
-      case MLQEM_SIM_OP_SWAP:
-        cx.gather([&](int i) {
-          int j = i ^ ((((i >> q0) ^ (i >> q1)) & 1) * ((1 << q0) | (1 << q1)));
-          if (density) j ^= (((i >> (q0 + n)) ^ (i >> (q1 + n))) & 1) * (((1 << q0) | (1 << q1)) << n);
-          return j;
-        });
-        break;
-      case MLQEM_SIM_OP_U2:
-        cx.quad(q0, q1, m, dg, dg);   // the inverse: the record read transposed and conjugated
-        if (density) cx.quad(q0 + n, q1 + n, m, !dg, dg);
-        break;
-      case MLQEM_SIM_OP_DEPOL1:
-        if (density) cx.depol1(n, q0, m[0]);
-        break;
-      case MLQEM_SIM_OP_DEPOL2:
-        if (density) cx.depol2(n, q0, q1, m[0]);
-        break;
-      case MLQEM_SIM_OP_READOUT:
-        if (density)   // [[1 - p10, p01], [p10, 1 - p01]] on bit q0 of the diagonal; m = (p01, p10)
-          cx.pair(n, q0, sim_c{1.0 - m[1], 0.0}, sim_c{m[0], 0.0}, sim_c{m[1], 0.0}, sim_c{1.0 - m[0], 0.0}, (1 << n) + 1);
-        break;
-      case MLQEM_SIM_OP_NOISE1:   // never inverted: a schedule's dagger bit is ignored, as for the depolarising kinds
-        if (density) cx.noise1(n, q0, m[0], m[1], m[2], m[3]);
-        break;
-      case MLQEM_SIM_OP_NOISE2:
-        if (density) cx.noise2(n, q0, q1, m);
-        break;
-      default:
-        break;
-    }
+    sim_apply_fixed<FOLD>(cx, rec, n, density, dg);
   }
 
   // Pauli terms: P|j> = i^ny (-1)^popcount(j & z) |j ^ x>
@@ -460,14 +378,7 @@ __global__ __launch_bounds__(kBlock) void sample_finish_kernel(int B, int64_t n_
   if (r >= n_runs) return;
   const int64_t c = r % B, f = r / B;
   const int64_t tb = min(max(term_ptr[c], (int64_t)0), n_terms), te = min(max(term_ptr[c + 1], tb), n_terms);
-  double val = 0.0, var = 0.0;
-  for (int64_t t = tb; t < te; ++t) {
-    const double tv = term_values[f * n_terms + t], cf = coeff[t];
-    val = __builtin_fma(cf, tv, val);
-    var = __builtin_fma(cf * cf, __builtin_fma(-tv, tv, 1.0), var);
-  }
-  values[r] = val;
-  variance[r] = var;
+  sample_value_variance(coeff, tb, te, values[r], variance[r], [&](int64_t t) { return term_values[f * n_terms + t]; });
 }
 
 }  // namespace
@@ -479,30 +390,19 @@ extern "C" int mlqem_sim_run_f64(int64_t n_circuits, const int32_t* circ, const 
                                  const double* params, int64_t n_params, const int64_t* term_ptr, const mlqem_sim_term* terms,
                                  const double* coeff, int64_t n_terms, const int32_t* ids, int64_t n_wave, int64_t n_wg,
                                  double* term_values, double* values, double* norm, mlqem_stream_t stream) {
-  static_assert(sizeof(mlqem_sim_op) == 16 && sizeof(mlqem_sim_term) == 16, "one 16-byte load per record");
   begin_launches();
-  if (n_circuits < 0 || n_ops < 0 || n_terms < 0 || n_wave < 0 || n_wg < 0 || n_params < kSimParamPad) return MLQEM_ERR_BAD_ARG;
+  if (!sim_batch_sizes(n_circuits, n_ops, n_params, n_terms, n_wave, n_wg)) return MLQEM_ERR_BAD_ARG;
   if (n_wave + n_wg > n_circuits) return MLQEM_ERR_BAD_ARG;
   if (n_circuits > 0x7FFFFFFFll || n_params > 0x7FFFFFFFll) return MLQEM_ERR_UNSUPPORTED;
   if (n_wave + n_wg == 0) return MLQEM_OK;
-  if (!circ || !op_ptr || !params || !term_ptr || !ids || !values || !norm || (n_ops > 0 && !ops) ||
-      (n_terms > 0 && (!terms || !coeff || !term_values)))
-    return MLQEM_ERR_BAD_ARG;
-  if (!aligned_to(circ, 16) || !aligned_to(ops, 16) || !aligned_to(terms, 16)) return MLQEM_ERR_BAD_ARG;
-  const sim_i4* ci = reinterpret_cast<const sim_i4*>(circ);
-  const sim_i4* oi = reinterpret_cast<const sim_i4*>(ops);
-  const sim_i4* ti = reinterpret_cast<const sim_i4*>(terms);
-  if (n_wave > 0) {
-    const int64_t blocks = ceil_div(n_wave, (int64_t)(kBlock / kWave));
-    hipLaunchKernelGGL((sim_kernel<false, false>), dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), (int)n_circuits, ci, op_ptr,
-                       oi, n_ops, params, n_params, term_ptr, ti, coeff, n_terms, ids, (int)n_wave, term_values, values, norm, 0,
+  SimBatchPtrs b;
+  if (int code = sim_batch_buffers(circ, op_ptr, ops, n_ops, params, term_ptr, terms, coeff, n_terms, ids, b)) return code;
+  if (!values || !norm || (n_terms > 0 && !term_values)) return MLQEM_ERR_BAD_ARG;
+  sim_launch_pair(ids, n_wave, n_wg, 1, [&](auto wg, dim3 grid, const int32_t* id, int count) {
+    hipLaunchKernelGGL((sim_kernel<decltype(wg)::value, false>), grid, dim3(kBlock), 0, as_stream(stream), (int)n_circuits, b.circ, op_ptr,
+                       b.ops, n_ops, params, n_params, term_ptr, b.terms, coeff, n_terms, id, count, term_values, values, norm, 0,
                        (const int64_t*)nullptr, (const int32_t*)nullptr, (int64_t)0);
-  }
-  if (n_wg > 0) {
-    hipLaunchKernelGGL((sim_kernel<true, false>), dim3((unsigned)n_wg), dim3(kBlock), 0, as_stream(stream), (int)n_circuits, ci, op_ptr,
-                       oi, n_ops, params, n_params, term_ptr, ti, coeff, n_terms, ids + n_wave, (int)n_wg, term_values, values, norm, 0,
-                       (const int64_t*)nullptr, (const int32_t*)nullptr, (int64_t)0);
-  }
+  });
   return launch_status();
 }
 
@@ -513,33 +413,22 @@ extern "C" int mlqem_sim_run_folded_f64(int64_t n_circuits, int64_t n_factors, c
                                         int64_t n_wave, int64_t n_wg, double* term_values, double* values, double* norm,
                                         mlqem_stream_t stream) {
   begin_launches();
-  if (n_circuits < 0 || n_factors < 1 || n_ops < 0 || n_terms < 0 || n_sched < 0 || n_wave < 0 || n_wg < 0 || n_params < kSimParamPad)
-    return MLQEM_ERR_BAD_ARG;
+  if (!sim_batch_sizes(n_circuits, n_ops, n_params, n_terms, n_wave, n_wg) || n_factors < 1 || n_sched < 0) return MLQEM_ERR_BAD_ARG;
   if (n_circuits > 0x7FFFFFFFll || n_factors > 0x7FFFFFFFll || n_params > 0x7FFFFFFFll || n_sched > 0x7FFFFFFFll)
     return MLQEM_ERR_UNSUPPORTED;
   const int64_t n_runs = n_factors * n_circuits;   // both below 2^31: no overflow
   if (n_runs > 0x7FFFFFFFll) return MLQEM_ERR_UNSUPPORTED;
   if (n_wave + n_wg > n_runs) return MLQEM_ERR_BAD_ARG;
   if (n_wave + n_wg == 0) return MLQEM_OK;
-  if (!circ || !op_ptr || !params || !term_ptr || !sched_ptr || !ids || !values || !norm || (n_ops > 0 && !ops) || (n_sched > 0 && !sched) ||
-      (n_terms > 0 && (!terms || !coeff || !term_values)))
-    return MLQEM_ERR_BAD_ARG;
-  if (!aligned_to(circ, 16) || !aligned_to(ops, 16) || !aligned_to(terms, 16) || !aligned_to(sched_ptr, 8) || !aligned_to(sched, 4))
-    return MLQEM_ERR_BAD_ARG;
-  const sim_i4* ci = reinterpret_cast<const sim_i4*>(circ);
-  const sim_i4* oi = reinterpret_cast<const sim_i4*>(ops);
-  const sim_i4* ti = reinterpret_cast<const sim_i4*>(terms);
-  if (n_wave > 0) {
-    const int64_t blocks = ceil_div(n_wave, (int64_t)(kBlock / kWave));
-    hipLaunchKernelGGL((sim_kernel<false, true>), dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), (int)n_circuits, ci, op_ptr,
-                       oi, n_ops, params, n_params, term_ptr, ti, coeff, n_terms, ids, (int)n_wave, term_values, values, norm,
+  SimBatchPtrs b;
+  if (int code = sim_batch_buffers(circ, op_ptr, ops, n_ops, params, term_ptr, terms, coeff, n_terms, ids, b)) return code;
+  if (!sched_ptr || !values || !norm || (n_sched > 0 && !sched) || (n_terms > 0 && !term_values)) return MLQEM_ERR_BAD_ARG;
+  if (!aligned_to(sched_ptr, 8) || !aligned_to(sched, 4)) return MLQEM_ERR_BAD_ARG;
+  sim_launch_pair(ids, n_wave, n_wg, 1, [&](auto wg, dim3 grid, const int32_t* id, int count) {
+    hipLaunchKernelGGL((sim_kernel<decltype(wg)::value, true>), grid, dim3(kBlock), 0, as_stream(stream), (int)n_circuits, b.circ, op_ptr,
+                       b.ops, n_ops, params, n_params, term_ptr, b.terms, coeff, n_terms, id, count, term_values, values, norm,
                        (int)n_runs, sched_ptr, sched, n_sched);
-  }
-  if (n_wg > 0) {
-    hipLaunchKernelGGL((sim_kernel<true, true>), dim3((unsigned)n_wg), dim3(kBlock), 0, as_stream(stream), (int)n_circuits, ci, op_ptr,
-                       oi, n_ops, params, n_params, term_ptr, ti, coeff, n_terms, ids + n_wave, (int)n_wg, term_values, values, norm,
-                       (int)n_runs, sched_ptr, sched, n_sched);
-  }
+  });
   return launch_status();
 }
 
@@ -582,8 +471,7 @@ static int sim_run_measured_impl(bool fold, int64_t n_circuits, int64_t n_factor
                                  const int32_t* sched, int64_t n_sched, const int32_t* ids, int64_t n_wave, int64_t n_wg,
                                  double* term_values, double* values, double* norm, double* probs, mlqem_stream_t stream) {
   begin_launches();
-  if (n_circuits < 0 || n_factors < 1 || n_ops < 0 || n_terms < 0 || n_sched < 0 || n_wave < 0 || n_wg < 0 || n_groups < 0 ||
-      n_outcomes < 0 || n_params < kSimParamPad)
+  if (!sim_batch_sizes(n_circuits, n_ops, n_params, n_terms, n_wave, n_wg) || n_factors < 1 || n_sched < 0 || n_groups < 0 || n_outcomes < 0)
     return MLQEM_ERR_BAD_ARG;
   if (n_circuits > 0x7FFFFFFFll || n_factors > 0x7FFFFFFFll || n_params > 0x7FFFFFFFll || n_sched > 0x7FFFFFFFll ||
       n_groups > 0x7FFFFFFFll)
@@ -592,29 +480,19 @@ static int sim_run_measured_impl(bool fold, int64_t n_circuits, int64_t n_factor
   if (n_runs > 0x7FFFFFFFll) return MLQEM_ERR_UNSUPPORTED;
   if (n_wave + n_wg > n_runs) return MLQEM_ERR_BAD_ARG;
   if (n_wave + n_wg == 0) return MLQEM_OK;
-  if (!circ || !op_ptr || !params || !term_ptr || !group_ptr || !prob_ptr || !ids || !values || !norm || (n_ops > 0 && !ops) ||
-      (fold && (!sched_ptr || (n_sched > 0 && !sched))) || (n_terms > 0 && (!terms || !coeff || !term_values)) || (n_outcomes > 0 && !probs))
+  SimBatchPtrs b;
+  if (int code = sim_batch_buffers(circ, op_ptr, ops, n_ops, params, term_ptr, terms, coeff, n_terms, ids, b)) return code;
+  if (!group_ptr || !prob_ptr || !values || !norm || (fold && (!sched_ptr || (n_sched > 0 && !sched))) || (n_terms > 0 && !term_values) ||
+      (n_outcomes > 0 && !probs))
     return MLQEM_ERR_BAD_ARG;
-  if (!aligned_to(circ, 16) || !aligned_to(ops, 16) || !aligned_to(terms, 16) || !aligned_to(sched_ptr, 8) || !aligned_to(sched, 4) ||
-      !aligned_to(group_ptr, 8) || !aligned_to(prob_ptr, 8) || !aligned_to(probs, 8))
+  if (!aligned_to(sched_ptr, 8) || !aligned_to(sched, 4) || !aligned_to(group_ptr, 8) || !aligned_to(prob_ptr, 8) || !aligned_to(probs, 8))
     return MLQEM_ERR_BAD_ARG;
-  const sim_i4* ci = reinterpret_cast<const sim_i4*>(circ);
-  const sim_i4* oi = reinterpret_cast<const sim_i4*>(ops);
-  const sim_i4* ti = reinterpret_cast<const sim_i4*>(terms);
-  const dim3 wave_grid((unsigned)ceil_div(n_wave, (int64_t)(kBlock / kWave))), wg_grid((unsigned)n_wg);
-#define MLQEM_SIM_MEASURED_LAUNCH(WGV, FOLDV, GRID, IDS, COUNT)                                                                          \
-  hipLaunchKernelGGL((sim_kernel<WGV, FOLDV, true>), GRID, dim3(kBlock), 0, as_stream(stream), (int)n_circuits, ci, op_ptr, oi, n_ops,    \
-                     params, n_params, term_ptr, ti, coeff, n_terms, IDS, (int)(COUNT), term_values, values, norm, (int)n_runs, sched_ptr, \
-                     sched, n_sched, group_ptr, prob_ptr, n_groups, n_outcomes, probs)
-  if (n_wave > 0) {
-    if (fold) MLQEM_SIM_MEASURED_LAUNCH(false, true, wave_grid, ids, n_wave);
-    else MLQEM_SIM_MEASURED_LAUNCH(false, false, wave_grid, ids, n_wave);
-  }
-  if (n_wg > 0) {
-    if (fold) MLQEM_SIM_MEASURED_LAUNCH(true, true, wg_grid, ids + n_wave, n_wg);
-    else MLQEM_SIM_MEASURED_LAUNCH(true, false, wg_grid, ids + n_wave, n_wg);
-  }
-#undef MLQEM_SIM_MEASURED_LAUNCH
+  sim_launch_pair(ids, n_wave, n_wg, 1, [&](auto wg, dim3 grid, const int32_t* id, int count) {
+    auto kernel = fold ? sim_kernel<decltype(wg)::value, true, true> : sim_kernel<decltype(wg)::value, false, true>;
+    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, as_stream(stream), (int)n_circuits, b.circ, op_ptr, b.ops, n_ops, params, n_params,
+                       term_ptr, b.terms, coeff, n_terms, id, count, term_values, values, norm, (int)n_runs, sched_ptr, sched, n_sched,
+                       group_ptr, prob_ptr, n_groups, n_outcomes, probs);
+  });
   return launch_status();
 }
 
@@ -663,17 +541,11 @@ extern "C" int mlqem_sim_sample_f64(int64_t n_circuits, int64_t n_factors, const
   const sim_i4* ci = reinterpret_cast<const sim_i4*>(circ);
   const sim_i4* ti = reinterpret_cast<const sim_i4*>(terms);
   const uint32_t seed_lo = (uint32_t)seed, seed_hi = (uint32_t)(seed >> 32);
-  if (n_wave > 0) {
-    const int64_t blocks = ceil_div(n_wave, (int64_t)(kBlock / kWave));
-    hipLaunchKernelGGL((sample_kernel<false>), dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), (int)n_circuits, (int)n_factors,
-                       ci, term_ptr, ti, n_terms, group_ptr, term_group, prob_ptr, group_circ, (int)n_groups, n_outcomes, probs, run_keys,
-                       (int)shots, seed_lo, seed_hi, units, (int)n_wave, counts, term_values);
-  }
-  if (n_wg > 0) {
-    hipLaunchKernelGGL((sample_kernel<true>), dim3((unsigned)n_wg), dim3(kBlock), 0, as_stream(stream), (int)n_circuits, (int)n_factors,
-                       ci, term_ptr, ti, n_terms, group_ptr, term_group, prob_ptr, group_circ, (int)n_groups, n_outcomes, probs, run_keys,
-                       (int)shots, seed_lo, seed_hi, units + n_wave, (int)n_wg, counts, term_values);
-  }
+  sim_launch_pair(units, n_wave, n_wg, 1, [&](auto wg, dim3 grid, const int32_t* unit, int count) {
+    hipLaunchKernelGGL((sample_kernel<decltype(wg)::value>), grid, dim3(kBlock), 0, as_stream(stream), (int)n_circuits, (int)n_factors, ci,
+                       term_ptr, ti, n_terms, group_ptr, term_group, prob_ptr, group_circ, (int)n_groups, n_outcomes, probs, run_keys,
+                       (int)shots, seed_lo, seed_hi, unit, count, counts, term_values);
+  });
   hipLaunchKernelGGL(sample_finish_kernel, dim3((unsigned)ceil_div(n_runs, (int64_t)kBlock)), dim3(kBlock), 0, as_stream(stream),
                      (int)n_circuits, n_runs, term_ptr, coeff, n_terms, term_values, values, variance);
   return launch_status();

@@ -5,8 +5,10 @@
 // owns (parameter index, scale, offset) in the pool instead of a matrix.  A RUN is (template, row of theta, shifted record or -1):
 // thousands of bindings of one ansatz share one set of records and differ in a row of float64, and the 2 K shifted runs of a
 // parameter-shift gradient differ in 16 bytes each.  The kernel is sim_kernel's (sim.hip) with the run in the place of the circuit:
-// the same state in LDS, the same passes of SimCtx (sim_ctx.hpp) for the fixed kinds in the same order -- a template without
-// parameterised records gives the bits of mlqem_sim_run_f64 -- and the same fixed-order reductions.
+// the same state in LDS, and for everything but its own parameterised kinds it CALLS what sim_kernel calls -- the prologue, the
+// record decode, the norm pass, the switch over the fixed kinds (sim_apply_fixed with FOLD = false), one copy of each in sim_ctx.hpp;
+// the term loop is sim_kernel's text, kept here as a copy (sim_ctx.hpp says why).  So a template without parameterised records gives
+// the bits of mlqem_sim_run_f64, and a pass added to that switch is added here too.
 //
 // The matrices.  The angle of a record is uniform over the wave, and a double-precision sin/cos (the device library's: argument
 // reduction and two polynomials, some 150 instructions) is long next to a pass over 32 amplitudes.  Two forms, one switch (`form`):
@@ -55,11 +57,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WG ? 4 :
   __shared__ sim_c trig[TABLE ? kBlock : 1];   // the window's (cos, sin): 256 records of a workgroup's run, or 64 per wave
   __shared__ double red[8];
   SimCtx<WG> cx;
-  const int slot = WG ? (int)blockIdx.x : __builtin_amdgcn_readfirstlane((int)blockIdx.x * (kBlock / kWave) + ((int)threadIdx.x >> 6));
+  const int slot = cx.begin(state, red);
   if (slot >= count) return;   // a wave of a partly filled workgroup: wave-uniform, and this variant has no workgroup barrier
-  cx.tid = WG ? (int)threadIdx.x : (int)threadIdx.x & (kWave - 1);
-  cx.st = WG ? state : state + ((int)threadIdx.x >> 6) * kSimWaveAmps;
-  cx.red = red;
   const int tid = cx.tid;
   sim_c* tab = WG ? trig : trig + (TABLE ? ((int)threadIdx.x >> 6) * kWave : 0);
   const int run = __builtin_amdgcn_readfirstlane(min(max(ids[slot], 0), n_runs - 1));
@@ -87,15 +86,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WG ? 4 :
   double nrm = 0.0;
   for (int k = 0; k <= n_step; ++k) {
     if (k == n_main) {   // <psi|psi> or Tr rho, before any readout op
-      double part = 0.0;
-      const int cnt = density ? 1 << n : A, mul = density ? (1 << n) + 1 : 1;
-      for (int i0 = 0; i0 < cnt; i0 += cx.T) {
-        const int i = i0 + tid;
-        const sim_c v = cx.st[((i & (cnt - 1)) * mul) & (A - 1)];
-        const double add = density ? v.x : v.x * v.x + v.y * v.y;
-        part = part + (i < cnt ? add : 0.0);
-      }
-      nrm = cx.reduce(part, 0);
+      nrm = sim_norm(cx, n, density);
       if (WG) __syncthreads();   // red[0..3] is free again
     }
     if (k == n_step) break;
@@ -113,15 +104,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WG ? 4 :
         sim_sync<WG>();
       }
     }
-    const sim_i4 op = ops[ob + k];   // kind, q0, q1, offset into params
-    const int kind = __builtin_amdgcn_readfirstlane(op.x);
-    const int q0 = __builtin_amdgcn_readfirstlane(min(max(op.y, 0), n - 1)), q1 = __builtin_amdgcn_readfirstlane(min(max(op.z, 0), n - 1));
-    const int64_t po = min((int64_t)max(op.w, 0), n_params - kSimParamPad);
-    const double* m = params + po;
+    const SimRec rec = sim_decode(ops[ob + k], n, params, n_params);   // kind, q0, q1, offset into params
+    const int kind = rec.kind, q0 = rec.q0, q1 = rec.q1;
     if (bound_is_param(kind)) {   // uniform over the wave (and the workgroup)
       sim_c cs;
       if constexpr (TABLE) cs = tab[k & (cx.T - 1)];
-      else cs = bound_trig(kind, m, theta_row, ld_theta, k == sop, sh);
+      else cs = bound_trig(kind, rec.m, theta_row, ld_theta, k == sop, sh);
       const double co = cs.x, si = cs.y;
       if (kind == MLQEM_SIM_OP_PRX) {          // [[c, -is], [-is, c]]
         cx.pair(nbits, q0, sim_c{co, 0.0}, sim_c{0.0, -si}, sim_c{0.0, -si}, sim_c{co, 0.0}, 1);
@@ -153,68 +141,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WG ? 4 :
       }
       continue;
     }
-    switch (kind) {   // the fixed kinds: sim_kernel's passes, as sim_kernel takes them
-      case MLQEM_SIM_OP_U1:
-        cx.pair(nbits, q0, sim_c{m[0], m[1]}, sim_c{m[2], m[3]}, sim_c{m[4], m[5]}, sim_c{m[6], m[7]}, 1);
-        if (density) cx.pair(nbits, q0 + n, sim_c{m[0], -m[1]}, sim_c{m[2], -m[3]}, sim_c{m[4], -m[5]}, sim_c{m[6], -m[7]}, 1);
-        break;
-      case MLQEM_SIM_OP_DIAG1: {
-        const sim_c d0{m[0], m[1]}, d1{m[2], m[3]};
-        if (density) {
-          cx.element([&](int i) {   // d[row bit] conj(d[column bit])
-            const bool r = (i >> q0) & 1, cc = (i >> (q0 + n)) & 1;
-            return cmul(sim_c{r ? d1.x : d0.x, r ? d1.y : d0.y}, sim_c{cc ? d1.x : d0.x, cc ? -d1.y : -d0.y});
-          });
-        } else {
-          cx.element([&](int i) { return (i >> q0) & 1 ? d1 : d0; });
-        }
-        break;
-      }
-      case MLQEM_SIM_OP_CZ: {
-        const int mrow = (1 << q0) | (1 << q1), mcol = density ? mrow << n : 0;
-        cx.element([&](int i) {
-          const bool neg = ((i & mrow) == mrow) != (density && (i & mcol) == mcol);
-          return sim_c{neg ? -1.0 : 1.0, 0.0};
-        });
-        break;
-      }
-      case MLQEM_SIM_OP_CX:
-        cx.gather([&](int i) {
-          int j = i ^ (((i >> q0) & 1) << q1);
-          if (density) j ^= ((i >> (q0 + n)) & 1) << (q1 + n);
-          return j;
-        });
-        break;
-      case MLQEM_SIM_OP_SWAP:
-        cx.gather([&](int i) {
-          int j = i ^ ((((i >> q0) ^ (i >> q1)) & 1) * ((1 << q0) | (1 << q1)));
-          if (density) j ^= (((i >> (q0 + n)) ^ (i >> (q1 + n))) & 1) * (((1 << q0) | (1 << q1)) << n);
-          return j;
-        });
-        break;
-      case MLQEM_SIM_OP_U2:
-        cx.quad(q0, q1, m, false, false);
-        if (density) cx.quad(q0 + n, q1 + n, m, true, false);
-        break;
-      case MLQEM_SIM_OP_DEPOL1:
-        if (density) cx.depol1(n, q0, m[0]);
-        break;
-      case MLQEM_SIM_OP_DEPOL2:
-        if (density) cx.depol2(n, q0, q1, m[0]);
-        break;
-      case MLQEM_SIM_OP_READOUT:
-        if (density)   // [[1 - p10, p01], [p10, 1 - p01]] on bit q0 of the diagonal; m = (p01, p10)
-          cx.pair(n, q0, sim_c{1.0 - m[1], 0.0}, sim_c{m[0], 0.0}, sim_c{m[1], 0.0}, sim_c{1.0 - m[0], 0.0}, (1 << n) + 1);
-        break;
-      case MLQEM_SIM_OP_NOISE1:
-        if (density) cx.noise1(n, q0, m[0], m[1], m[2], m[3]);
-        break;
-      case MLQEM_SIM_OP_NOISE2:
-        if (density) cx.noise2(n, q0, q1, m);
-        break;
-      default:
-        break;
-    }
+    sim_apply_fixed<false>(cx, rec, n, density, false);   // the fixed kinds: sim_kernel's passes, from the text sim_kernel runs
   }
 
   // Pauli terms: P|j> = i^ny (-1)^popcount(j & z) |j ^ x>
@@ -291,38 +218,25 @@ extern "C" int mlqem_sim_run_bound_f64(int64_t n_templates, const int32_t* circ,
                                        int64_t n_out_terms, int32_t form, double* term_values, double* values, double* norm,
                                        mlqem_stream_t stream) {
   begin_launches();
-  if (n_templates < 0 || n_ops < 0 || n_terms < 0 || n_wave < 0 || n_wg < 0 || n_params < kSimParamPad || n_rows < 0 || ld_theta < 0 ||
-      n_runs < 0 || n_out_terms < 0 || (form != MLQEM_SIM_BOUND_TABLE && form != MLQEM_SIM_BOUND_PLAIN))
+  if (!sim_batch_sizes(n_templates, n_ops, n_params, n_terms, n_wave, n_wg) || n_rows < 0 || ld_theta < 0 || n_runs < 0 || n_out_terms < 0 ||
+      (form != MLQEM_SIM_BOUND_TABLE && form != MLQEM_SIM_BOUND_PLAIN))
     return MLQEM_ERR_BAD_ARG;
   if (n_wave + n_wg > n_runs) return MLQEM_ERR_BAD_ARG;
   if (n_templates > 0x7FFFFFFFll || n_params > 0x7FFFFFFFll || n_runs > 0x7FFFFFFFll || n_rows > 0x7FFFFFFFll || ld_theta > 0x7FFFFFFFll)
     return MLQEM_ERR_UNSUPPORTED;
   if (n_wave + n_wg == 0) return MLQEM_OK;
   if (n_templates < 1 || n_rows < 1 || ld_theta < 1) return MLQEM_ERR_BAD_ARG;   // a run names a template and a row of >= 1 value
-  if (!circ || !op_ptr || !params || !term_ptr || !theta || !runs || !shift || !ids || !run_term_ptr || !values || !norm ||
-      (n_ops > 0 && !ops) || (n_terms > 0 && (!terms || !coeff)) || (n_out_terms > 0 && !term_values))
-    return MLQEM_ERR_BAD_ARG;
-  if (!aligned_to(circ, 16) || !aligned_to(ops, 16) || !aligned_to(terms, 16) || !aligned_to(runs, 16) || !aligned_to(theta, 8) ||
-      !aligned_to(shift, 8) || !aligned_to(run_term_ptr, 8))
-    return MLQEM_ERR_BAD_ARG;
-  const sim_i4* ci = reinterpret_cast<const sim_i4*>(circ);
-  const sim_i4* oi = reinterpret_cast<const sim_i4*>(ops);
-  const sim_i4* ti = reinterpret_cast<const sim_i4*>(terms);
+  SimBatchPtrs b;
+  if (int code = sim_batch_buffers(circ, op_ptr, ops, n_ops, params, term_ptr, terms, coeff, n_terms, ids, b)) return code;
+  if (!theta || !runs || !shift || !run_term_ptr || !values || !norm || (n_out_terms > 0 && !term_values)) return MLQEM_ERR_BAD_ARG;
+  if (!aligned_to(runs, 16) || !aligned_to(theta, 8) || !aligned_to(shift, 8) || !aligned_to(run_term_ptr, 8)) return MLQEM_ERR_BAD_ARG;
   const sim_i4* ri = reinterpret_cast<const sim_i4*>(runs);
-  const dim3 wave_grid((unsigned)ceil_div(n_wave, (int64_t)(kBlock / kWave))), wg_grid((unsigned)n_wg);
-#define MLQEM_SIM_BOUND_LAUNCH(WGV, TABLEV, GRID, IDS, COUNT)                                                                           \
-  hipLaunchKernelGGL((bound_kernel<WGV, TABLEV>), GRID, dim3(kBlock), 0, as_stream(stream), (int)n_templates, ci, op_ptr, oi, n_ops,     \
-                     params, n_params, term_ptr, ti, coeff, n_terms, theta, (int)n_rows, (int)ld_theta, ri, (int)n_runs, shift, IDS,     \
-                     (int)(COUNT), run_term_ptr, n_out_terms, term_values, values, norm)
-  if (n_wave > 0) {
-    if (form == MLQEM_SIM_BOUND_TABLE) MLQEM_SIM_BOUND_LAUNCH(false, true, wave_grid, ids, n_wave);
-    else MLQEM_SIM_BOUND_LAUNCH(false, false, wave_grid, ids, n_wave);
-  }
-  if (n_wg > 0) {
-    if (form == MLQEM_SIM_BOUND_TABLE) MLQEM_SIM_BOUND_LAUNCH(true, true, wg_grid, ids + n_wave, n_wg);
-    else MLQEM_SIM_BOUND_LAUNCH(true, false, wg_grid, ids + n_wave, n_wg);
-  }
-#undef MLQEM_SIM_BOUND_LAUNCH
+  sim_launch_pair(ids, n_wave, n_wg, 1, [&](auto wg, dim3 grid, const int32_t* id, int count) {
+    auto kernel = form == MLQEM_SIM_BOUND_TABLE ? bound_kernel<decltype(wg)::value, true> : bound_kernel<decltype(wg)::value, false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, as_stream(stream), (int)n_templates, b.circ, op_ptr, b.ops, n_ops, params, n_params,
+                       term_ptr, b.terms, coeff, n_terms, theta, (int)n_rows, (int)ld_theta, ri, (int)n_runs, shift, id, count, run_term_ptr,
+                       n_out_terms, term_values, values, norm);
+  });
   return launch_status();
 }
 

@@ -1,8 +1,23 @@
-// What the simulator's kernels share (sim.hip: exact runs, folded runs, measurement shots; sim_traj.hip: quantum trajectories):
-// the LDS state's types, the passes of SimCtx and the Philox4x32-10 generator.  sim.hip's header comment states the rules of a
-// pass; everything here is in an unnamed namespace, so each translation unit has its own copy.
+// What the simulator's kernels share (sim.hip: exact runs, folded runs, measurement shots; sim_bound.hip: runs of templates;
+// sim_traj.hip: quantum trajectories; the finish kernels of mps.hip and clifford_frames.hip).  sim.hip's header comment states the
+// rules of a pass.  Here lives the ONE copy of
+//   the LDS state's types, the passes of SimCtx and its unit prologue (SimCtx::begin),
+//   the record decode (sim_decode), the <psi|psi> / Tr rho pass (sim_norm) and the switch over the fixed record kinds
+//   (sim_apply_fixed): sim_kernel and bound_kernel call them; traj_kernel keeps its own text of all four, which was faster
+//   (DESIGN.md 3.13), and the term loop stays in each kernel (see the note below the switch),
+//   a term's mean and standard error over trajectories and a trajectory's value (traj_term_stats, traj_value: traj_finish_kernel,
+//   mps_finish_kernel, which keep their own two passes over the trajectories around traj_value, with their other sums in them) and
+//   the value / variance sums of sampled runs (sample_value_variance: sample_finish_kernel, frames_finish_kernel),
+//   the Philox4x32-10 generator,
+//   and, for the host side of the entry points, the checks of a lowered batch's arguments (sim_batch_sizes, sim_batch_buffers) and the
+//   wave-grid / workgroup-grid launch pair (sim_launch_pair).
+// A record kind or a pass added to the switch reaches sim_kernel and bound_kernel: bound_kernel's promise of sim_kernel's bits for
+// a template without parameterised records rests on both calling the same text (and on its copy of the term loop).  Everything here is in an unnamed namespace, so each
+// translation unit has its own copy.
 #pragma once
 #include "common.hpp"
+
+#include <type_traits>
 
 namespace mlqem {
 namespace {
@@ -42,6 +57,16 @@ template <bool WG> struct SimCtx {
   sim_c* st;
   double* red;   // [2][4] wave sums of the workgroup variant
   int tid, nbits, A;
+
+  // The unit's number: the workgroup's (WG), or four waves a workgroup with the wave's own 4 KB slice of `state`.  The number is
+  // wave-uniform, so a kernel may return on it for a wave of a partly filled workgroup: the wave variant has no workgroup barrier.
+  __device__ __forceinline__ int begin(sim_c* state, double* red8) {
+    const int slot = WG ? (int)blockIdx.x : __builtin_amdgcn_readfirstlane((int)blockIdx.x * (kBlock / kWave) + ((int)threadIdx.x >> 6));
+    tid = WG ? (int)threadIdx.x : (int)threadIdx.x & (kWave - 1);
+    st = WG ? state : state + ((int)threadIdx.x >> 6) * kSimWaveAmps;
+    red = red8;
+    return slot;
+  }
 
   // a 2x2 matrix on bit b of the first `bits` index bits; the entry of index i sits at i * mul, which lets the readout op walk the
   // diagonal of a density matrix (mul = 1 + 2^n) with the same code
@@ -264,6 +289,157 @@ template <bool WG> struct SimCtx {
   }
 };
 
+// One record, decoded: kind, q0, q1 (clamped to the circuit's qubits) and its values in the pool (the offset clamped so that the
+// longest record stays inside the padding).  All four are wave-uniform.
+struct SimRec {
+  int kind, q0, q1;
+  const double* m;
+};
+
+__device__ __forceinline__ SimRec sim_decode(const sim_i4 op, int n, const double* __restrict__ params, int64_t n_params) {
+  const int kind = __builtin_amdgcn_readfirstlane(op.x);
+  const int q0 = __builtin_amdgcn_readfirstlane(min(max(op.y, 0), n - 1)), q1 = __builtin_amdgcn_readfirstlane(min(max(op.z, 0), n - 1));
+  const int64_t po = min((int64_t)max(op.w, 0), n_params - kSimParamPad);
+  return SimRec{kind, q0, q1, params + po};
+}
+
+// <psi|psi> or Tr rho, reduced in the fixed order through slot 0 of `red`: the caller of the workgroup variant follows it with a
+// barrier before red[0..3] is written again
+template <bool WG> __device__ __forceinline__ double sim_norm(SimCtx<WG>& cx, int n, bool density) {
+  const int A = cx.A, tid = cx.tid;
+  double part = 0.0;
+  const int cnt = density ? 1 << n : A, mul = density ? (1 << n) + 1 : 1;
+  for (int i0 = 0; i0 < cnt; i0 += cx.T) {
+    const int i = i0 + tid;
+    const sim_c v = cx.st[((i & (cnt - 1)) * mul) & (A - 1)];
+    const double add = density ? v.x : v.x * v.x + v.y * v.y;
+    part = part + (i < cnt ? add : 0.0);
+  }
+  return cx.reduce(part, 0);
+}
+
+// The fixed record kinds (U1 .. NOISE2) as passes over the state; `dg` applies the record's inverse (folded runs, FOLD = true).
+// A caller that passes `density = false` or `dg = false` as a literal compiles without the branches they guard.
+template <bool FOLD, bool WG> __device__ __forceinline__ void sim_apply_fixed(SimCtx<WG>& cx, const SimRec& rec, int n, bool density, bool dg) {
+  const int nbits = cx.nbits, kind = rec.kind, q0 = rec.q0, q1 = rec.q1;
+  const double* m = rec.m;
+  switch (kind) {
+    case MLQEM_SIM_OP_U1:
+      if (FOLD) {   // the inverse swaps the off-diagonal entries and negates the imaginary parts: no arithmetic, no rounding
+        const int o01 = dg ? 4 : 2, o10 = dg ? 2 : 4;
+        const sim_c u00{m[0], dg ? -m[1] : m[1]}, u01{m[o01], dg ? -m[o01 + 1] : m[o01 + 1]},
+            u10{m[o10], dg ? -m[o10 + 1] : m[o10 + 1]}, u11{m[6], dg ? -m[7] : m[7]};
+        cx.pair(nbits, q0, u00, u01, u10, u11, 1);
+        if (density) cx.pair(nbits, q0 + n, sim_c{u00.x, -u00.y}, sim_c{u01.x, -u01.y}, sim_c{u10.x, -u10.y}, sim_c{u11.x, -u11.y}, 1);
+        break;
+      }
+      cx.pair(nbits, q0, sim_c{m[0], m[1]}, sim_c{m[2], m[3]}, sim_c{m[4], m[5]}, sim_c{m[6], m[7]}, 1);
+      if (density) cx.pair(nbits, q0 + n, sim_c{m[0], -m[1]}, sim_c{m[2], -m[3]}, sim_c{m[4], -m[5]}, sim_c{m[6], -m[7]}, 1);
+      break;
+    case MLQEM_SIM_OP_DIAG1: {
+      const sim_c d0{m[0], dg ? -m[1] : m[1]}, d1{m[2], dg ? -m[3] : m[3]};
+      if (density) {
+        cx.element([&](int i) {   // d[row bit] conj(d[column bit])
+          const bool r = (i >> q0) & 1, cc = (i >> (q0 + n)) & 1;
+          return cmul(sim_c{r ? d1.x : d0.x, r ? d1.y : d0.y}, sim_c{cc ? d1.x : d0.x, cc ? -d1.y : -d0.y});
+        });
+      } else {
+        cx.element([&](int i) { return (i >> q0) & 1 ? d1 : d0; });
+      }
+      break;
+    }
+    case MLQEM_SIM_OP_CZ: {
+      const int mrow = (1 << q0) | (1 << q1), mcol = density ? mrow << n : 0;
+      cx.element([&](int i) {
+        const bool neg = ((i & mrow) == mrow) != (density && (i & mcol) == mcol);
+        return sim_c{neg ? -1.0 : 1.0, 0.0};
+      });
+      break;
+    }
+    case MLQEM_SIM_OP_CX:
+      cx.gather([&](int i) {
+        int j = i ^ (((i >> q0) & 1) << q1);
+        if (density) j ^= ((i >> (q0 + n)) & 1) << (q1 + n);
+        return j;
+      });
+      break;
+    case MLQEM_SIM_OP_SWAP:
+      cx.gather([&](int i) {
+        int j = i ^ ((((i >> q0) ^ (i >> q1)) & 1) * ((1 << q0) | (1 << q1)));
+        if (density) j ^= (((i >> (q0 + n)) ^ (i >> (q1 + n))) & 1) * (((1 << q0) | (1 << q1)) << n);
+        return j;
+      });
+      break;
+    case MLQEM_SIM_OP_U2:
+      cx.quad(q0, q1, m, dg, dg);   // the inverse: the record read transposed and conjugated
+      if (density) cx.quad(q0 + n, q1 + n, m, !dg, dg);
+      break;
+    case MLQEM_SIM_OP_DEPOL1:
+      if (density) cx.depol1(n, q0, m[0]);
+      break;
+    case MLQEM_SIM_OP_DEPOL2:
+      if (density) cx.depol2(n, q0, q1, m[0]);
+      break;
+    case MLQEM_SIM_OP_READOUT:
+      if (density)   // [[1 - p10, p01], [p10, 1 - p01]] on bit q0 of the diagonal; m = (p01, p10)
+        cx.pair(n, q0, sim_c{1.0 - m[1], 0.0}, sim_c{m[0], 0.0}, sim_c{m[1], 0.0}, sim_c{1.0 - m[0], 0.0}, (1 << n) + 1);
+      break;
+    case MLQEM_SIM_OP_NOISE1:   // never inverted: a schedule's dagger bit is ignored, as for the depolarising kinds
+      if (density) cx.noise1(n, q0, m[0], m[1], m[2], m[3]);
+      break;
+    case MLQEM_SIM_OP_NOISE2:
+      if (density) cx.noise2(n, q0, q1, m);
+      break;
+    default:
+      break;
+  }
+}
+
+// The Pauli-term loop that follows the passes is not here: each kernel keeps its own copy, because as a shared function it changed
+// the code the compiler emits for the passes of the workgroup variant and cost time (DESIGN.md 3.13 has the figures).
+
+// Mean and standard error sqrt(M2 / (T (T - 1))) (0 at T = 1) of term i over the T trajectories, in trajectory order: a sum, then
+// the squared deviations from the mean in a second pass, a fused multiply-add each
+struct TrajStat {
+  double mean, se;
+};
+
+__device__ __forceinline__ TrajStat traj_term_stats(const double* __restrict__ traj_terms, int64_t n_terms, int T, int64_t i) {
+  const double count = (double)T, pairs = (double)T * (double)(T - 1);   // the callers' own: one copy after inlining
+  double acc = 0.0, m2 = 0.0;
+  for (int t = 0; t < T; ++t) acc = acc + traj_terms[(int64_t)t * n_terms + i];
+  const double mean = acc / count;
+  for (int t = 0; t < T; ++t) {
+    const double d = traj_terms[(int64_t)t * n_terms + i] - mean;
+    m2 = __builtin_fma(d, d, m2);
+  }
+  return TrajStat{mean, T > 1 ? sqrt(m2 / pairs) : 0.0};
+}
+
+// One trajectory's value of a circuit: sum coeff * term over its terms tb .. te in term order, a fused multiply-add per term from
+// 0.0.  The finish kernels form it in both passes over the trajectories with these operations, so with the same bits.
+__device__ __forceinline__ double traj_value(const double* __restrict__ coeff, const double* __restrict__ traj_terms, int64_t n_terms, int t,
+                                             int64_t tb, int64_t te) {
+  double v = 0.0;
+  for (int64_t k = tb; k < te; ++k) v = __builtin_fma(coeff[k], traj_terms[(int64_t)t * n_terms + k], v);
+  return v;
+}
+
+// Value sum coeff * tv and variance sum coeff^2 (1 - tv^2) of one sampled run over its terms tb .. te, in term order, a fused
+// multiply-add per term; tv = estimate(t) is the term's sampled estimate
+template <class F>
+__device__ __forceinline__ void sample_value_variance(const double* __restrict__ coeff, int64_t tb, int64_t te, double& value, double& variance,
+                                                      F&& estimate) {
+  double val = 0.0, var = 0.0;
+  for (int64_t t = tb; t < te; ++t) {
+    const double tv = estimate(t), cf = coeff[t];
+    val = __builtin_fma(cf, tv, val);
+    var = __builtin_fma(cf * cf, __builtin_fma(-tv, tv, 1.0), var);
+  }
+  value = val;
+  variance = var;
+}
+
 // Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11): ten rounds of two 32 x 32 -> 64 products,
 // the key bumped by the Weyl constants between rounds.
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
@@ -283,6 +459,40 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
   x[1] = c1;
   x[2] = c2;
   x[3] = c3;
+}
+
+// ---- the host side of an entry point that takes a lowered batch ------------------------------------------------------------------------
+// An entry point checks in this order: sim_batch_sizes and its own sizes (MLQEM_ERR_BAD_ARG), its own limit on n_wave + n_wg and what
+// it does not support, the return of MLQEM_OK for a call without units (which may come with null buffers), then sim_batch_buffers
+// and its own buffers.  That is why the batch's checks are two functions: the first runs before that return, the second after it.
+
+// the counts of a lowered batch and of its units: none negative, and a pool that ends with its padding
+inline bool sim_batch_sizes(int64_t n_circuits, int64_t n_ops, int64_t n_params, int64_t n_terms, int64_t n_wave, int64_t n_wg) {
+  return n_circuits >= 0 && n_ops >= 0 && n_terms >= 0 && n_wave >= 0 && n_wg >= 0 && n_params >= kSimParamPad;
+}
+
+struct SimBatchPtrs {   // the three record arrays as the kernels read them: one 16-byte load per record
+  const sim_i4 *circ, *ops, *terms;
+};
+
+// The buffers of a lowered batch: MLQEM_ERR_BAD_ARG for a missing one (`ops`, and `terms` with `coeff`, may be null where their
+// count is 0) or a record array off its 16 bytes, else MLQEM_OK and the cast pointers.  `ids` is the call's list of units.
+inline int sim_batch_buffers(const int32_t* circ, const int64_t* op_ptr, const mlqem_sim_op* ops, int64_t n_ops, const double* params,
+                             const int64_t* term_ptr, const mlqem_sim_term* terms, const double* coeff, int64_t n_terms, const int32_t* ids,
+                             SimBatchPtrs& out) {
+  static_assert(sizeof(mlqem_sim_op) == 16 && sizeof(mlqem_sim_term) == 16, "one 16-byte load per record");
+  if (!circ || !op_ptr || !params || !term_ptr || !ids || (n_ops > 0 && !ops) || (n_terms > 0 && (!terms || !coeff))) return MLQEM_ERR_BAD_ARG;
+  if (!aligned_to(circ, 16) || !aligned_to(ops, 16) || !aligned_to(terms, 16)) return MLQEM_ERR_BAD_ARG;
+  out = SimBatchPtrs{reinterpret_cast<const sim_i4*>(circ), reinterpret_cast<const sim_i4*>(ops), reinterpret_cast<const sim_i4*>(terms)};
+  return MLQEM_OK;
+}
+
+// The launch pair of a call: the first n_wave of `ids` run a wave per unit, four units a workgroup, the other n_wg a workgroup per
+// unit; an id stands for `per_id` units (a circuit's trajectories).  launch(wg, grid, ids, count) launches the WG = wg.value
+// instantiation over `count` ids; a part without ids is not launched.
+template <class F> void sim_launch_pair(const int32_t* ids, int64_t n_wave, int64_t n_wg, int64_t per_id, F&& launch) {
+  if (n_wave > 0) launch(std::false_type{}, dim3((unsigned)ceil_div(n_wave * per_id, (int64_t)(kBlock / kWave))), ids, (int)n_wave);
+  if (n_wg > 0) launch(std::true_type{}, dim3((unsigned)(n_wg * per_id)), ids + n_wave, (int)n_wg);
 }
 
 }  // namespace

@@ -283,30 +283,20 @@ __global__ __launch_bounds__(kBlock) void traj_finish_kernel(int64_t B, int64_t 
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   const double count = (double)T, pairs = (double)T * (double)(T - 1);
   if (i < n_terms) {
-    double acc = 0.0, m2 = 0.0;
-    for (int t = 0; t < T; ++t) acc = acc + traj_terms[(int64_t)t * n_terms + i];
-    const double mean = acc / count;
-    for (int t = 0; t < T; ++t) {
-      const double d = traj_terms[(int64_t)t * n_terms + i] - mean;
-      m2 = __builtin_fma(d, d, m2);
-    }
-    term_values[i] = mean;
-    term_se[i] = T > 1 ? sqrt(m2 / pairs) : 0.0;
+    const TrajStat s = traj_term_stats(traj_terms, n_terms, T, i);
+    term_values[i] = s.mean;
+    term_se[i] = s.se;
   }
   if (i < B) {
     const int64_t tb = min(max(term_ptr[i], (int64_t)0), n_terms), te = min(max(term_ptr[i + 1], tb), n_terms);
     double acc = 0.0, nacc = 0.0, m2 = 0.0;
     for (int t = 0; t < T; ++t) {
-      double v = 0.0;
-      for (int64_t k = tb; k < te; ++k) v = __builtin_fma(coeff[k], traj_terms[(int64_t)t * n_terms + k], v);
-      acc = acc + v;
+      acc = acc + traj_value(coeff, traj_terms, n_terms, t, tb, te);
       nacc = nacc + traj_norm[(int64_t)t * B + i];
     }
     const double mean = acc / count;
     for (int t = 0; t < T; ++t) {
-      double v = 0.0;
-      for (int64_t k = tb; k < te; ++k) v = __builtin_fma(coeff[k], traj_terms[(int64_t)t * n_terms + k], v);
-      const double d = v - mean;
+      const double d = traj_value(coeff, traj_terms, n_terms, t, tb, te) - mean;
       m2 = __builtin_fma(d, d, m2);
     }
     values[i] = mean;
@@ -327,32 +317,24 @@ extern "C" int mlqem_sim_run_trajectories_f64(int64_t n_circuits, const int32_t*
                                               double* traj_term_values, double* traj_norm, double* term_values, double* term_std_error,
                                               double* values, double* std_error, double* norm, mlqem_stream_t stream) {
   begin_launches();
-  if (n_circuits < 0 || n_ops < 0 || n_terms < 0 || n_wave < 0 || n_wg < 0 || n_params < kSimParamPad) return MLQEM_ERR_BAD_ARG;
+  if (!sim_batch_sizes(n_circuits, n_ops, n_params, n_terms, n_wave, n_wg)) return MLQEM_ERR_BAD_ARG;
   if (trajectories < 1 || trajectories > MLQEM_SIM_MAX_TRAJECTORIES) return MLQEM_ERR_BAD_ARG;
   if (n_circuits > 0x7FFFFFFFll || n_params > 0x7FFFFFFFll || n_terms > 0x7FFFFFFFll) return MLQEM_ERR_UNSUPPORTED;
   if (n_circuits * trajectories > 0x7FFFFFFFll) return MLQEM_ERR_UNSUPPORTED;   // a unit's number is an int
   if (n_wave + n_wg != n_circuits) return MLQEM_ERR_BAD_ARG;   // the finish kernel reads every circuit's trajectories
   if (n_circuits == 0) return MLQEM_OK;
-  if (!circ || !op_ptr || !params || !term_ptr || !ids || !run_keys || !traj_norm || !values || !std_error || !norm || (n_ops > 0 && !ops) ||
-      (n_terms > 0 && (!terms || !coeff || !traj_term_values || !term_values || !term_std_error)))
+  SimBatchPtrs b;
+  if (int code = sim_batch_buffers(circ, op_ptr, ops, n_ops, params, term_ptr, terms, coeff, n_terms, ids, b)) return code;
+  if (!run_keys || !traj_norm || !values || !std_error || !norm || (n_terms > 0 && (!traj_term_values || !term_values || !term_std_error)))
     return MLQEM_ERR_BAD_ARG;
-  if (!aligned_to(circ, 16) || !aligned_to(ops, 16) || !aligned_to(terms, 16) || !aligned_to(run_keys, 8)) return MLQEM_ERR_BAD_ARG;
-  const sim_i4* ci = reinterpret_cast<const sim_i4*>(circ);
-  const sim_i4* oi = reinterpret_cast<const sim_i4*>(ops);
-  const sim_i4* ti = reinterpret_cast<const sim_i4*>(terms);
+  if (!aligned_to(run_keys, 8)) return MLQEM_ERR_BAD_ARG;
   const uint32_t seed_lo = (uint32_t)seed, seed_hi = (uint32_t)(seed >> 32);
   const int T = (int)trajectories;
-  if (n_wave > 0) {
-    const int64_t blocks = ceil_div(n_wave * trajectories, (int64_t)(kBlock / kWave));
-    hipLaunchKernelGGL((traj_kernel<false>), dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), (int)n_circuits, ci, op_ptr, oi,
-                       n_ops, params, n_params, term_ptr, ti, n_terms, ids, (int)n_wave, T, run_keys, seed_lo, seed_hi, traj_term_values,
+  sim_launch_pair(ids, n_wave, n_wg, trajectories, [&](auto wg, dim3 grid, const int32_t* id, int count) {
+    hipLaunchKernelGGL((traj_kernel<decltype(wg)::value>), grid, dim3(kBlock), 0, as_stream(stream), (int)n_circuits, b.circ, op_ptr, b.ops,
+                       n_ops, params, n_params, term_ptr, b.terms, n_terms, id, count, T, run_keys, seed_lo, seed_hi, traj_term_values,
                        traj_norm);
-  }
-  if (n_wg > 0) {
-    hipLaunchKernelGGL((traj_kernel<true>), dim3((unsigned)(n_wg * trajectories)), dim3(kBlock), 0, as_stream(stream), (int)n_circuits, ci,
-                       op_ptr, oi, n_ops, params, n_params, term_ptr, ti, n_terms, ids + n_wave, (int)n_wg, T, run_keys, seed_lo, seed_hi,
-                       traj_term_values, traj_norm);
-  }
+  });
   const int64_t rows = n_circuits > n_terms ? n_circuits : n_terms;
   hipLaunchKernelGGL(traj_finish_kernel, dim3((unsigned)ceil_div(rows, (int64_t)kBlock)), dim3(kBlock), 0, as_stream(stream), n_circuits,
                      n_terms, T, term_ptr, coeff, traj_term_values, traj_norm, term_values, term_std_error, values, std_error, norm);

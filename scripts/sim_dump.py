@@ -1,0 +1,139 @@
+"""Runs every case of the grids the simulator's GPU tests iterate and writes every output tensor to one .npz, so that two builds of
+the library can be compared bit for bit (MLQEM_LIB selects the build; compare the files array for array).
+
+    python scripts/sim_dump.py --out a.npz
+    MLQEM_LIB=/path/to/other/libmlqem_hip.so python scripts/sim_dump.py --out b.npz
+    python scripts/sim_dump.py --compare a.npz b.npz
+
+The grids: sim_cases (vector, density, depolarising, readout), relax_cases.grid, zne_cases (folded runs, one of them measured),
+shots_cases.batches at every shot count (measured runs + sampled counts), traj_cases.grid with the per-trajectory values,
+bound_cases.grid in both forms with every shifted run, mps_cases.grid through sim_mps_finish, clifford_frames_cases' grid.
+"""
+import argparse
+import dataclasses
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "ml-qem_amd"), os.path.join(ROOT, "tests")]
+import numpy as np  # noqa: E402
+
+DEV = "cuda:0"
+
+
+def compare(a, b):
+    x, y = np.load(a), np.load(b)
+    differ = [k for k in x.files if k not in y.files or x[k].dtype != y[k].dtype or x[k].shape != y[k].shape
+              or x[k].tobytes() != y[k].tobytes()]
+    differ += [k for k in y.files if k not in x.files]
+    print(f"{len(x.files)} arrays in {a}, {len(y.files)} in {b}, {len(differ)} differ")
+    for k in differ[:20]:
+        print("  differs:", k)
+    return 1 if differ else 0
+
+
+def dump(out):
+    import torch
+
+    import bound_cases as bc
+    import clifford_frames_cases as fc
+    import mps_cases as mc
+    import relax_cases as rc
+    import shots_cases as shc
+    import sim_cases as sc
+    import traj_cases as tc
+    import zne_cases as zc
+    from blackwater import sim
+    from blackwater.native import ops
+    from blackwater.sim import zne
+    from blackwater.sim.bound import run_bound, shift_runs
+
+    arrays = {}
+
+    def put(name, obj):
+        if torch.is_tensor(obj):
+            arrays[name] = obj.cpu().numpy()
+        elif dataclasses.is_dataclass(obj):
+            for f in dataclasses.fields(obj):
+                if f.name != "batch":
+                    put(f"{name}/{f.name}", getattr(obj, f.name))
+        elif isinstance(obj, dict):
+            for k, v in obj.items():
+                put(f"{name}/{k}", v)
+        elif isinstance(obj, (tuple, list)):
+            for k, v in enumerate(obj):
+                put(f"{name}/{k}", v)
+
+    def section(name):
+        print(f"{name}: {len(arrays)} arrays so far", flush=True)
+
+    def exact(name, circuits, observables, noise):
+        put(name, sim.run_batch(sim.compile_programs(circuits, observables, noise), DEV))
+
+    for n in (1, 2, 3, 8, 9, 11):
+        c = sc.random_program(n, 40, seed=0)
+        exact(f"sim/vector-n{n}", [c, c], [sc.term_set(n), sc.long_observable(n)], None)
+    for n in (1, 2, 4, 5):
+        obs = [sc.term_set(n), sc.long_observable(n)]
+        c = sc.random_program(n, 40, seed=1)
+        exact(f"sim/density-n{n}", [c, c], obs, sc.NoNoise())
+        c = sc.random_program(n, 40, seed=2)
+        exact(f"sim/depol-n{n}", [c, c], obs, sc.StepNoise(11))
+        c = sc.random_program(n, 40, seed=3, measure=True)
+        noise = sc.StepNoise(12, readout={q: (0.01 + 0.02 * q, 0.06 - 0.01 * q) for q in range(n)})
+        exact(f"sim/readout-n{n}", [c, c], [sc.term_set(n, alphabet="IZ"), sc.long_observable(n, alphabet="IZ")], noise)
+    section("relax")
+    for name, c, terms, noise in rc.grid():
+        exact(f"relax/{name}", [c], [list(terms)], noise)
+
+    def folded(name, c, terms, noise, desc, factors, **kw):
+        strategy = zne.ZNEStrategy(noise_factors=factors, noise_amplifier=zc.make_amplifier(desc), extrapolator=zne.PolynomialExtrapolator(1))
+        put(name, zne.zne_run([c], [terms], noise, strategy, DEV, **kw))
+
+    section("zne")
+    for name, n, desc, factors in zc.density_cases():
+        folded(f"zne/{name}", *zc.density_program(n), desc, factors)
+    for n in zc.VECTOR_N:
+        folded(f"zne/vector-n{n}", *zc.vector_program(n), None, zc.GLOBAL, (1, 3, 5))
+    for n in zc.READOUT_N:   # the two folds tests/test_gpu_zne.py runs on the readout programs
+        folded(f"zne/readout-n{n}-local", *zc.readout_program(n), zc.LOCAL_ALL, (1, 3))
+        folded(f"zne/readout-n{n}-global-partial", *zc.readout_program(n), zc.GLOBAL, zc.PARTIAL)
+    for n in (2, 5):
+        folded(f"zne/measured-n{n}", *zc.density_program(n), zc.LOCAL_ALL, (1, 3), shots=65, seed=7)
+    section("shots")
+    for name, (circuits, observables, noise, _) in shc.batches().items():
+        for shots in shc.SHOTS:
+            put(f"shots/{name}-{shots}", sim.sample_batch(sim.compile_programs(circuits, observables, noise, shots=shots), shc.seed_for(shots), None, DEV))
+    section("traj")
+    for case in tc.grid():
+        put(f"traj/{case['id']}", sim.run_trajectories(tc.lower(case), case["seed"], None, DEV, keep_trajectories=True))
+    section("bound")
+    for name, template, terms, noise, n_rows, span in bc.grid():
+        batch = sim.compile_templates([template], [terms], noise)
+        theta = bc.thetas(n_rows, template.num_parameters, span=span)
+        runs, shift, _ = shift_runs(batch, np.zeros(n_rows, dtype=np.int64))
+        for form, tag in ((ops.SIM_BOUND_TABLE, "table"), (ops.SIM_BOUND_PLAIN, "plain")):
+            put(f"bound/{name}-{tag}", run_bound(batch, theta, runs, shift, DEV, form=form))
+    section("mps")
+    for case in mc.grid():
+        put(f"mps/{case['id']}", sim.run_mps(mc.lower(case), case["seed"], None, DEV, keep_trajectories=True))
+    section("frames")
+    for kind, mixed in fc.GRID_COMBOS:
+        cases = [fc.grid_case(n, mixed) for n in fc.GRID_N]   # fc.grid_batch's lowering, without its host oracle
+        batch = sim.compile_clifford_frames([c for c, _ in cases], [t for _, t in cases], fc.GRID_NOISE[kind]())
+        for shots in fc.GRID_SHOTS:
+            put(f"frames/{kind}-{int(mixed)}-{shots}", sim.run_clifford_frames(batch, shots, fc.GRID_SEED, None, False, DEV))
+    torch.cuda.synchronize()
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    np.savez(out, **arrays)
+    print(f"wrote {len(arrays)} arrays to {out} with {os.environ.get('MLQEM_LIB') or 'the library of this tree'}")
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", help="the .npz to write (a few MB: keep it out of the repository)")
+    ap.add_argument("--compare", nargs=2, metavar=("A", "B"), help="compare two dumps array for array and exit (1: some differ)")
+    args = ap.parse_args()
+    if not args.compare and not args.out:
+        ap.error("give --out FILE to dump, or --compare A B")
+    sys.exit(compare(*args.compare) if args.compare else dump(args.out))

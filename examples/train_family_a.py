@@ -46,9 +46,14 @@ def main():
                          "on the device as matrix-product states: exact through 5 Trotter steps at bond 32, certified-approximate beyond")
     ap.add_argument("--mps-bond", type=int, default=32, help="the bond cap of --mps-labels (1 .. 32)")
     ap.add_argument("--mps-trajectories", type=int, default=16, help="Pauli-insertion trajectories per noisy label of --mps-labels")
+    ap.add_argument("--mps-shots", type=int, default=None, metavar="N",
+                    help="with --mps-labels: the noisy label is an N-shot estimate drawn from the matrix-product states (shot s from "
+                         "trajectory s mod --mps-trajectories), as the reference trains on estimates from finite counts")
     args = ap.parse_args()
     if args.clifford_labels and args.mps_labels:
         ap.error("--clifford-labels and --mps-labels choose different circuits: pass one")
+    if args.mps_shots is not None and not args.mps_labels:
+        ap.error("--mps-shots draws from the matrix-product states of --mps-labels: pass both")
 
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -61,7 +66,8 @@ def main():
     # 1. encode once (rank 0) into two shards; every rank then maps them and keeps its round-robin part
     shard_dir = args.shard_dir or os.path.join(tempfile.gettempdir(),
                                                f"mlqem_example_{args.qubits}q" + ("_clifford" if args.clifford_labels else "")
-                                               + (f"_mps{args.mps_bond}" if args.mps_labels else ""))
+                                               + (f"_mps{args.mps_bond}" if args.mps_labels else "")
+                                               + (f"_shots{args.mps_shots}" if args.mps_shots is not None else ""))
     paths = [os.path.join(shard_dir, f"part{k}.mlqs") for k in range(2)]
     if rank == 0 and not all(os.path.exists(p) for p in paths):
         os.makedirs(shard_dir, exist_ok=True)
@@ -81,7 +87,7 @@ def main():
                         for s in range(1, args.steps + 1) for j in rng.uniform(0.0, 0.66 * np.pi, size=args.n_j)]
             noise = sim.NoiseModel.from_backend(synthetic_backend(args.qubits, "cx"))
             c = encode_corpus(circuits, args.qubits, two_q="cx", simulate=noise, device=dev, mps_bond=args.mps_bond,
-                              trajectories=args.mps_trajectories)
+                              trajectories=args.mps_trajectories, mps_shots=args.mps_shots)
             print(f"MPS labels at bond {args.mps_bond}: the worst certificate of the corpus is B = {c['mps_error_bound']:.3e} "
                   f"(every ideal label is within 2 B of the exact <Z>)")
         else:

@@ -2028,6 +2028,63 @@ int mlqem_mps_finish_f64(int64_t n_circuits, int64_t n_terms, int64_t trajectori
                          double* term_std_error, double* values, double* std_error, double* norm, double* discarded,
                          double* error_bound, int32_t* bond, mlqem_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Shots from a matrix-product state (three additive symbols, the ABI version is unchanged): measurement outcomes of the state
+ * that mlqem_mps_run_f64 left in `workspace`, by perfect sampling.  blackwater.sim.mps lowers for it (compile_mps_shots) and
+ * blackwater.native.ops.mps_sample / mps_sample_finish call it.  The sampled distribution is that of the TRUNCATED state; its
+ * trace distance from the exact state's is at most the run's error_bound.
+ *
+ * mlqem_mps_sample_f64 takes one chunk of units exactly as mlqem_mps_terms_f64 does (after mlqem_mps_run_f64 on the same chunk and
+ * workspace) plus `sample_workspace` (mlqem_mps_sample_workspace_bytes(max_qubits, max_bond, units): n 2 chi^2 16 B per unit).
+ * It does not rely on the gauge (the orthogonality centre is not stored):
+ *   Environment pass, one workgroup per unit, right to left: R[n] = [1]; G[q][l, s, r'] = sum_r A[q][l, s, r] R[q + 1][r, r'] is
+ *   written to sample_workspace; R[q][l, l'] = sum_(s, r') G[q][l, s, r'] conj(A[q][l', s, r']).  Sums in index order, no atomics.
+ *   Sampling pass, one workgroup per (group of the chunk, trajectory of the chunk, block of MLQEM_MPS_SHOT_BLOCK = 16 of that
+ *   trajectory's shots).  Shot s < shots belongs to trajectory s mod trajectories (T = 1 without noise).  Its left vector v starts
+ *   as [1]; at site q = 0, 1, ..., n - 1: a[s, r] = sum_l v[l] A[q][l, s, r] and g[s, r] = sum_l v[l] G[q][l, s, r]; the group's
+ *   basis letter at the site mixes the physical index of both (0 I and 3 Z: nothing; 1 X: (a0 + a1) c, (a0 - a1) c; 2 Y:
+ *   (a0 - i a1) c, (a0 + i a1) c; c = 0.7071067811865476); the unnormalised weight of outcome b is p_b = sum_r Re(g[b, r]
+ *   conj(a[b, r])); one outcome b is drawn (below); v <- a[b, .] / sqrt(p_b), with the true outcome b, not the reported bit.
+ * DRAW CONTRACT.  Circuit c with run key k = run_keys[c], group g inside its circuit (g < MLQEM_MPS_MAX_GROUPS = 4 096), shot s,
+ * site q: Philox4x32-10 with the key (seed & 0xffffffff, seed >> 32) and the counter (0x80000000 | g << 9 | q, s, k & 0xffffffff,
+ * k >> 32) -- the top bit of the first word keeps these draws apart from the noise draws, whose counter is (record index,
+ * trajectory, key words).  u = ((x0 >> 5) 2^26 + (x1 >> 6)) 2^-53, u' the same from (x2, x3).  w_b = p_b where p_b > 0, else 0 (a
+ * NaN weight counts as 0); target = u * (w0 + w1), one rounded product of the rounded sum; b = 0 if target < w0 or not (w1 > 0),
+ * else 1: an outcome of weight zero is unreachable.  The reported bit is b xor (u' < flip[site_ptr[c] + q][b]); flip float64
+ * [n_sites][2] is (P(read 1 | 0), P(read 0 | 1)) of a measured qubit with readout noise and (0, 0) otherwise, so the mean of the
+ * reported Z is a <Z> + b of the readout table of mlqem_mps_terms_f64.  Bits are packed as mlqem_clifford_sample_f64 packs them:
+ * W = ceil(n / 32) uint32 words per (group, shot), bit q in word q >> 5, the words of global group G, shot s at bits[ref_ptr[G] *
+ * shots + s * W] (ref_ptr int64 [n_groups + 1], the running sum of W; bits may be null with n_bits = 0).  The bits of a (circuit,
+ * group, shot) depend on (seed, run key, group, shot, the circuit's records, max_bond, cutoff, trajectories) alone: the same
+ * alone, in any batch, under any split into chunks and in a replayed graph.
+ * Groups.  group_ptr int64 [B + 1] (a circuit's groups; max_groups is the largest count of one circuit), group_circ int32
+ * [n_groups], group_off int64 [n_groups]: the group's n basis letters basis[group_off[G] + q] (uint8: 0 / 3 Z basis, 1 X, 2 Y);
+ * the chunk's groups are group_first .. group_first + group_count (those of its circuits).  Terms: term t has the support
+ * masks[term_mask[t] + w], w < W; gterm_ptr int64 [n_groups + 1] / gterm int32 [n_terms] list the terms of a group.  S_t = sum_s
+ * (-1)^popcount(bits_s & support_t) is added with integer atomics into term_sums int32 [n_terms]; a call with traj_first == 0
+ * first zeroes term_sums[term_first .. term_first + term_count) (the terms of the chunk's circuits) on the stream, so the chunks
+ * of one circuit run in trajectory order.  No float atomics.
+ * mlqem_mps_sample_finish_f64 forms, with the expressions of mlqem_sim_sample_f64: term_values = (double)S_t / (double)shots,
+ * values = fma(coeff, term, values) in term order from 0.0, variance = fma(coeff^2, fma(-term, term, 1), variance).
+ * shots outside 1 .. MLQEM_SIM_MAX_SHOTS, bad sizes, a null or misaligned buffer: MLQEM_ERR_BAD_ARG; max_groups over 4 096 or a
+ * count over 2^31 - 1: MLQEM_ERR_UNSUPPORTED; a workspace that is too small: MLQEM_ERR_WORKSPACE; all before anything is
+ * launched.  No host read: capturable.  Every index read from a buffer is clamped: malformed input computes garbage.
+ * ---------------------------------------------------------------------------------------------------- */
+#define MLQEM_MPS_SHOT_BLOCK 16
+#define MLQEM_MPS_MAX_GROUPS 4096
+size_t mlqem_mps_sample_workspace_bytes(int64_t max_qubits, int64_t max_bond, int64_t n_units);
+int mlqem_mps_sample_f64(int64_t n_circuits, const int32_t* n_qubits, int64_t circ_first, int64_t circ_count, int64_t traj_first,
+                         int64_t traj_count, int64_t trajectories, int64_t max_bond, int64_t max_qubits, const void* workspace,
+                         size_t workspace_bytes, void* sample_workspace, size_t sample_workspace_bytes, int64_t group_first,
+                         int64_t group_count, int64_t n_groups, int64_t max_groups, const int64_t* group_ptr, const int32_t* group_circ,
+                         const int64_t* group_off, const uint8_t* basis, int64_t n_basis, const int64_t* site_ptr, const double* flip,
+                         int64_t n_sites, const int64_t* ref_ptr, const int64_t* gterm_ptr, const int32_t* gterm, int64_t term_first,
+                         int64_t term_count, int64_t n_terms, const int32_t* term_mask, const uint32_t* masks, int64_t n_masks,
+                         const int64_t* run_keys, int64_t shots, uint64_t seed, int32_t* term_sums, uint32_t* bits, int64_t n_bits,
+                         mlqem_stream_t stream);
+int mlqem_mps_sample_finish_f64(int64_t n_circuits, int64_t n_terms, int64_t shots, const int64_t* term_ptr, const double* coeff,
+                                const int32_t* term_sums, double* term_values, double* values, double* variance, mlqem_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

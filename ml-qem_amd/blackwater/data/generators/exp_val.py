@@ -63,7 +63,8 @@ class ExpValueEntry:
 def exp_value_generator(backend: Any, n_qubits: int, circuit_depth: int, pauli_terms: int, pauli_coeff: float = 1.0,
                         max_entries: int = 1000, seed: int = 0, batch: int = 256, device="cuda", shots: Optional[int] = None,
                         sample_ideal: bool = False, trajectories: Optional[int] = None,
-                        frame_shots: Optional[int] = None, mps_bond: Optional[int] = None) -> Iterator[ExpValueEntry]:
+                        frame_shots: Optional[int] = None, mps_bond: Optional[int] = None,
+                        mps_shots: Optional[int] = None) -> Iterator[ExpValueEntry]:
     """Yields ``max_entries`` dataset entries of random circuits with simulated labels (reference: exp_val.py:92-170, which
     transpiles ``qiskit.circuit.random.random_circuit`` and runs Aer twice per circuit).
 
@@ -93,7 +94,20 @@ def exp_value_generator(backend: Any, n_qubits: int, circuit_depth: int, pauli_t
     ``mps_bond`` (default ``None``; with ``trajectories``): both values come from the matrix-product-state path at that bond
     (``sim.mps_expectation_values``: ``n_qubits`` up to 512, the circuits' two-qubit gates act on neighbours), the noisy one as
     the mean over ``trajectories`` Pauli-insertion trajectories, keyed as the shots are.  Without ``trajectories``, or together
-    with ``shots`` or ``frame_shots``, it is refused by name."""
+    with ``shots`` or ``frame_shots``, it is refused by name.
+
+    ``mps_shots`` (default ``None``; with ``mps_bond`` and ``trajectories``): the noisy value becomes the ``mps_shots``-shot estimate
+    drawn from the matrix-product states (``sim.sample_mps_expectation_values``, shot s from trajectory s mod ``trajectories``, keyed as
+    the shots are); the ideal value stays the exact MPS value.  Without ``mps_bond``, or together with ``shots`` or ``frame_shots``,
+    it is refused by name."""
+    if mps_shots is not None:
+        if shots is not None or frame_shots is not None:
+            raise ValueError("exp_value_generator: mps_shots together with " + ("shots" if shots is not None else "frame_shots") +
+                             " (shots= samples the exact simulator, frame_shots= the Clifford path, mps_shots= the matrix-product "
+                             "states: choose one)")
+        if mps_bond is None:
+            raise ValueError("exp_value_generator: mps_shots without mps_bond (the shots are drawn from matrix-product states: pass "
+                             "mps_bond=chi)")
     if mps_bond is not None:
         if shots is not None or frame_shots is not None:
             raise ValueError("exp_value_generator: mps_bond together with " + ("shots" if shots is not None else "frame_shots") +
@@ -138,8 +152,13 @@ def exp_value_generator(backend: Any, n_qubits: int, circuit_depth: int, pauli_t
         elif mps_bond is not None:
             keys = np.arange(done, done + count, dtype=np.int64)   # the entry's number, as on the shots path
             ideal = _to_host(sim.mps_expectation_values(circuits, observables, max_bond=mps_bond, device=device).values)
-            noisy = _to_host(sim.mps_expectation_values(circuits, observables, noise, max_bond=mps_bond, trajectories=trajectories,
-                                                        seed=seed, run_keys=keys, device=device).values)
+            if mps_shots is not None:
+                noisy = _to_host(sim.sample_mps_expectation_values(circuits, observables, noise, shots=mps_shots, max_bond=mps_bond,
+                                                                   trajectories=trajectories, seed=seed, run_keys=keys,
+                                                                   device=device).values)
+            else:
+                noisy = _to_host(sim.mps_expectation_values(circuits, observables, noise, max_bond=mps_bond, trajectories=trajectories,
+                                                            seed=seed, run_keys=keys, device=device).values)
         elif trajectories is not None:
             keys = np.arange(done, done + count, dtype=np.int64)   # the entry's number, as on the shots path
             ideal = _to_host(sim.expectation_values(circuits, observables, None, device)[0])

@@ -225,7 +225,7 @@ def pauli_twirl(circ: Circuit, seed: int, two_q=("cx", "ecr")) -> Circuit:
 
 def encode_corpus(circuits, nq: int, two_q: str = "cx", seed: int = 7, exp_value_size: int = 1,
                   add_self_loops: bool = True, simulate=None, device="cuda", shots=None, sample_ideal: bool = False,
-                  clifford: bool = False, trajectories=None, frame_shots=None, mps_bond=None) -> Dict[str, list]:
+                  clifford: bool = False, trajectories=None, frame_shots=None, mps_bond=None, mps_shots=None) -> Dict[str, list]:
     """Arena-ready arrays (same keys as :func:`tfim_corpus`) for arbitrary circuits, encoded by the native encoder.
 
     ``simulate=None``: synthetic labels (a uniform draw and a made-up decay).  ``simulate=`` a ``blackwater.sim.NoiseModel``: ``y``
@@ -248,7 +248,11 @@ def encode_corpus(circuits, nq: int, two_q: str = "cx", seed: int = 7, exp_value
     ``trajectories`` its noisy ``<Z>`` from that many MPS trajectories (keyed by ``seed`` and the circuit's position; without
     ``trajectories`` its noisy label stays the synthetic one).  With ``clifford=True`` Clifford circuits keep going to the exact
     Clifford path.  The result then has the key ``"mps_error_bound"``: the worst certificate B of those circuits (|<Z> - exact| <=
-    2 B; 0.0 where no circuit took the path).  Together with ``shots`` or ``frame_shots``, or without ``simulate``, it is refused."""
+    2 B; 0.0 where no circuit took the path).  Together with ``shots`` or ``frame_shots``, or without ``simulate``, it is refused.
+    ``mps_shots`` (with ``mps_bond`` and ``trajectories``; default ``None``): the noisy ``<Z>`` of those circuits becomes the
+    ``mps_shots``-shot estimate drawn from their matrix-product states (``sim.sample_mps_expectation_values``: shot s from trajectory
+    s mod ``trajectories``, keyed by ``seed`` and the circuit's position); the ideal value stays the exact MPS value.  Without
+    ``mps_bond`` or ``trajectories``, or together with ``shots`` or ``frame_shots``, it is refused by name."""
     from .circuit import circuit_to_qasm
     from .native_encoder import NativeEncoder
 
@@ -261,6 +265,17 @@ def encode_corpus(circuits, nq: int, two_q: str = "cx", seed: int = 7, exp_value
         if simulate is None:
             raise ValueError("encode_corpus: frame_shots fills simulated labels, so it needs simulate= (a noise model)")
 
+    if mps_shots is not None:
+        if shots is not None or frame_shots is not None:
+            raise ValueError("encode_corpus: mps_shots together with " + ("shots" if shots is not None else "frame_shots") +
+                             " (shots= samples the exact simulator, frame_shots= the Clifford path, mps_shots= the matrix-product "
+                             "states: choose one)")
+        if mps_bond is None:
+            raise ValueError("encode_corpus: mps_shots without mps_bond (the shots are drawn from matrix-product states: pass "
+                             "mps_bond=chi)")
+        if trajectories is None:
+            raise ValueError("encode_corpus: mps_shots without trajectories (the noisy states are Pauli-insertion trajectories: pass "
+                             "trajectories=T, at most mps_shots)")
     if mps_bond is not None:
         if shots is not None or frame_shots is not None:
             raise ValueError("encode_corpus: mps_bond together with " + ("shots" if shots is not None else "frame_shots") +
@@ -341,8 +356,14 @@ def encode_corpus(circuits, nq: int, two_q: str = "cx", seed: int = 7, exp_value
             for j, k in enumerate(line):
                 ys[k] = np.full(exp_value_size, exact[j])
             if trajectories is not None:
-                res = sim.mps_expectation_values([kept[k] for k in line], labels, simulate, max_bond=mps_bond, trajectories=trajectories,
-                                                 seed=seed, run_keys=np.asarray(line, dtype=np.int64), device=device)
+                if mps_shots is not None:
+                    res = sim.sample_mps_expectation_values([kept[k] for k in line], labels, simulate, shots=mps_shots, max_bond=mps_bond,
+                                                            trajectories=trajectories, seed=seed,
+                                                            run_keys=np.asarray(line, dtype=np.int64), device=device)
+                else:
+                    res = sim.mps_expectation_values([kept[k] for k in line], labels, simulate, max_bond=mps_bond,
+                                                     trajectories=trajectories, seed=seed, run_keys=np.asarray(line, dtype=np.int64),
+                                                     device=device)
                 under, mps_error_bound = res.values.cpu().numpy(), max(mps_error_bound, float(res.error_bound.max()))
                 for j, k in enumerate(line):
                     noisy[k] = np.full(exp_value_size, under[j])

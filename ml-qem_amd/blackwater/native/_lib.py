@@ -272,6 +272,10 @@ SIGNATURES = {
     "mlqem_mps_run_f64": (_I, [_L, _P, _P, _P, _L, _P, _L, _P, _L, _L, _L, _L, _L, _U, _L, _D, _L, _P, _S, _P, _P]),
     "mlqem_mps_terms_f64": (_I, [_L, _P, _L, _L, _L, _L, _L, _L, _L, _P, _S, _L, _L, _L, _P, _P, _P, _L, _P, _P, _L, _P, _P, _P]),
     "mlqem_mps_finish_f64": (_I, [_L, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mlqem_mps_sample_workspace_bytes": (_S, [_L, _L, _L]),
+    "mlqem_mps_sample_f64": (_I, [_L, _P, _L, _L, _L, _L, _L, _L, _L, _P, _S, _P, _S, _L, _L, _L, _L, _P, _P, _P, _P, _L, _P, _P, _L, _P, _P,
+                                  _P, _L, _L, _L, _P, _P, _L, _P, _L, _U, _P, _P, _L, _P]),
+    "mlqem_mps_sample_finish_f64": (_I, [_L, _L, _L, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -3067,6 +3067,137 @@ def sim_mps_finish(term_ptr, coeff, traj_term_values, traj_norm, traj_stats, *, 
     return out
 
 
+MPS_SHOT_BLOCK, MPS_MAX_GROUPS = 16, 4096   # MLQEM_MPS_SHOT_BLOCK / MLQEM_MPS_MAX_GROUPS
+
+
+def mps_sample_workspace_bytes(max_qubits: int, max_bond: int, n_units: int) -> int:
+    """Bytes of the environment workspace of ``n_units`` (circuit, trajectory) units (mlqem_mps_sample_workspace_bytes)."""
+    if not 1 <= int(max_qubits) <= MPS_MAX_QUBITS or not 1 <= int(max_bond) <= MPS_MAX_BOND or int(n_units) < 0:
+        raise ValueError(f"mps: max_qubits = {max_qubits}, max_bond = {max_bond}, n_units = {n_units}; want 1 .. {MPS_MAX_QUBITS}, "
+                         f"1 .. {MPS_MAX_BOND} and >= 0")
+    return int(_lib.load().mlqem_mps_sample_workspace_bytes(int(max_qubits), int(max_bond), int(n_units)))
+
+
+def mps_run(n_qubits, op_ptr, ops, params, run_keys, circuits, trajectories_range, trajectories, seed, max_bond, cutoff, max_qubits,
+            workspace, traj_stats):
+    """The (circuit, trajectory) units of one chunk as matrix-product states (mlqem_mps_run_f64 alone: the site tensors stay in
+    ``workspace`` for :func:`mps_sample`).  Arguments as :func:`sim_run_mps` takes them; ``traj_stats`` float64 [T, B, MPS_STATS]."""
+    if not ops.is_cuda:
+        raise _lib.NativeLibraryError(f"ops must live on the GPU (got {ops.device}); there is no CPU path")
+    if ops.dtype != torch.int32 or ops.shape[-1] != 4 or not ops.is_contiguous():
+        raise ValueError(f"mps: want contiguous int32 ops [n_ops, 4], got {tuple(ops.shape)} {ops.dtype}")
+    b, n_ops, n_traj, seed = int(n_qubits.shape[0]), int(ops.shape[0]), int(trajectories), int(seed)
+    (c0, cn), (j0, jn) = ((int(v) for v in pair) for pair in (circuits, trajectories_range))
+    if not 1 <= n_traj <= SIM_MAX_TRAJECTORIES or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"mps: trajectories = {n_traj} and seed = {seed}, want 1 .. 2^20 and 0 .. 2^64 - 1")
+    if not (0 <= c0 and 1 <= cn and c0 + cn <= b and 0 <= j0 and 1 <= jn and j0 + jn <= n_traj) or cn * jn > 2 ** 31 - 1:
+        raise ValueError(f"mps: the chunk (circuits {circuits}, trajectories {trajectories_range}) does not lie inside {b} circuits and "
+                         f"{n_traj} trajectories, or exceeds the 2^31 - 1 units one call can take")
+    dev = ops.device
+    _vec(n_qubits, "n_qubits", b, torch.int32)
+    _vec(op_ptr, "op_ptr", b + 1, torch.int64)
+    _vec(params, "params", SIM_PARAM_PAD, torch.float64)
+    _vec(run_keys, "run_keys", b, torch.int64)
+    _vec(workspace, "workspace", mps_workspace_bytes(max_qubits, max_bond, cn * jn), torch.uint8)
+    traj_stats = _sim_out(traj_stats, "traj_stats", (n_traj, b, MPS_STATS), dev)
+    if op_ptr.shape[0] != b + 1 or run_keys.shape[0] != b or any(t.device != dev for t in (n_qubits, op_ptr, params, run_keys, workspace)):
+        raise ValueError(f"mps: want op_ptr [{b + 1}] and run_keys [{b}] on {dev}, got {tuple(op_ptr.shape)} and {tuple(run_keys.shape)}")
+    code = _lib.load().mlqem_mps_run_f64(b, _p(n_qubits), _p(op_ptr), _p(ops) if n_ops else None, n_ops, _p(params), int(params.shape[0]),
+                                         _p(run_keys), c0, cn, j0, jn, n_traj, seed, int(max_bond), float(cutoff), int(max_qubits),
+                                         _p(workspace), int(workspace.shape[0]), _p(traj_stats), _stream())
+    _lib.check(code, "mlqem_mps_run_f64")
+    return traj_stats
+
+
+def mps_sample(n_qubits, circuits, trajectories_range, trajectories, max_bond, max_qubits, workspace, sample_workspace, groups, max_groups,
+               group_ptr, group_circ, group_off, basis, site_ptr, flip, ref_ptr, gterm_ptr, gterm, terms, term_mask, masks, run_keys, shots,
+               seed, term_sums, bits=None):
+    """Measurement shots of the chunk whose site tensors :func:`mps_run` left in ``workspace`` (mlqem_mps_sample_f64): adds the chunk's
+    part of S_t to ``term_sums`` int32 [n_terms] (zeroed for the chunk's terms where the chunk starts at trajectory 0) and, with
+    ``bits`` int32 [n_ref * shots], writes the packed outcomes.
+
+    ``circuits`` / ``trajectories_range`` / ``groups`` / ``terms``: ``(first, count)`` of the chunk (the groups and terms of its
+    circuits); ``group_ptr`` int64 [B + 1], ``group_circ`` int32 [G], ``group_off`` int64 [G], ``basis`` uint8, ``site_ptr`` int64
+    [B + 1], ``flip`` float64 [n_sites, 2], ``ref_ptr`` / ``gterm_ptr`` int64 [G + 1], ``gterm`` / ``term_mask`` int32 [n_terms],
+    ``masks`` int32 (uint32 words), ``run_keys`` int64 [B]: the WHOLE batch, in the layout of include/mlqem_hip.h.  Shapes, dtypes and
+    devices are checked here, the contents are the lowering's to guarantee (the kernels clamp every index).  Nothing here waits
+    for the device or reads a tensor and nothing is allocated: capturable.  There is no CPU path."""
+    if not workspace.is_cuda:
+        raise _lib.NativeLibraryError(f"workspace must live on the GPU (got {workspace.device}); there is no CPU path")
+    b, n_groups, n_terms, n_traj, shots, seed = (int(n_qubits.shape[0]), int(group_circ.shape[0]), int(term_mask.shape[0]), int(trajectories),
+                                                 int(shots), int(seed))
+    (c0, cn), (j0, jn), (g0, gn), (t0, tn) = ((int(v) for v in pair) for pair in (circuits, trajectories_range, groups, terms))
+    if not 1 <= shots <= SIM_MAX_SHOTS or not 1 <= n_traj <= SIM_MAX_TRAJECTORIES or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"mps: shots = {shots}, trajectories = {n_traj} and seed = {seed}, want 1 .. 2^20, 1 .. 2^20 and 0 .. 2^64 - 1")
+    if not (0 <= c0 and 1 <= cn and c0 + cn <= b and 0 <= j0 and 1 <= jn and j0 + jn <= n_traj and 0 <= g0 and 1 <= gn and g0 + gn <= n_groups
+            and 0 <= t0 and 0 <= tn and t0 + tn <= n_terms):
+        raise ValueError(f"mps: the chunk (circuits {circuits}, trajectories {trajectories_range}, groups {groups}, terms {terms}) does not "
+                         f"lie inside {b} circuits, {n_traj} trajectories, {n_groups} groups and {n_terms} terms")
+    if not 1 <= int(max_groups) <= MPS_MAX_GROUPS:
+        raise ValueError(f"mps: {max_groups} measurement groups in one circuit, want 1 .. {MPS_MAX_GROUPS}")
+    dev = workspace.device
+    units = cn * jn
+    _vec(n_qubits, "n_qubits", b, torch.int32)
+    _vec(workspace, "workspace", mps_workspace_bytes(max_qubits, max_bond, units), torch.uint8)
+    _vec(sample_workspace, "sample_workspace", mps_sample_workspace_bytes(max_qubits, max_bond, units), torch.uint8)
+    _vec(group_ptr, "group_ptr", b + 1, torch.int64)
+    _vec(group_circ, "group_circ", n_groups, torch.int32)
+    _vec(group_off, "group_off", n_groups, torch.int64)
+    _vec(basis, "basis", 1, torch.uint8)
+    _vec(site_ptr, "site_ptr", b + 1, torch.int64)
+    _vec(ref_ptr, "ref_ptr", n_groups + 1, torch.int64)
+    _vec(gterm_ptr, "gterm_ptr", n_groups + 1, torch.int64)
+    _vec(gterm, "gterm", n_terms, torch.int32)
+    _vec(term_mask, "term_mask", n_terms, torch.int32)
+    _vec(masks, "masks", 1, torch.int32)
+    _vec(run_keys, "run_keys", b, torch.int64)
+    _vec(term_sums, "term_sums", n_terms, torch.int32)
+    if flip.dtype != torch.float64 or flip.dim() != 2 or flip.shape[-1] != 2 or not flip.is_contiguous() or flip.shape[0] < 1:
+        raise ValueError(f"mps: want contiguous float64 flip [n_sites >= 1, 2], got {tuple(flip.shape)} {flip.dtype}")
+    n_bits = 0
+    if bits is not None:
+        _vec(bits, "bits", 0, torch.int32)
+        n_bits = int(bits.shape[0])
+    if (group_ptr.shape[0] != b + 1 or site_ptr.shape[0] != b + 1 or group_off.shape[0] != n_groups or ref_ptr.shape[0] != n_groups + 1
+            or gterm_ptr.shape[0] != n_groups + 1 or gterm.shape[0] != n_terms or run_keys.shape[0] != b or term_sums.shape[0] != n_terms):
+        raise ValueError(f"mps: want group_ptr and site_ptr [{b + 1}], group_off [{n_groups}], ref_ptr and gterm_ptr [{n_groups + 1}], gterm "
+                         f"and term_sums [{n_terms}] and run_keys [{b}]")
+    others = [n_qubits, sample_workspace, group_ptr, group_circ, group_off, basis, site_ptr, flip, ref_ptr, gterm_ptr, gterm, term_mask, masks,
+              run_keys, term_sums] + ([] if bits is None else [bits])
+    if any(t.device != dev for t in others):
+        raise ValueError(f"mps: workspace is on {dev}, another buffer is not")
+    code = _lib.load().mlqem_mps_sample_f64(
+        b, _p(n_qubits), c0, cn, j0, jn, n_traj, int(max_bond), int(max_qubits), _p(workspace), int(workspace.shape[0]),
+        _p(sample_workspace), int(sample_workspace.shape[0]), g0, gn, n_groups, int(max_groups), _p(group_ptr), _p(group_circ),
+        _p(group_off), _p(basis), int(basis.shape[0]), _p(site_ptr), _p(flip), int(flip.shape[0]), _p(ref_ptr), _p(gterm_ptr),
+        _p(gterm) if n_terms else None, t0, tn, n_terms, _p(term_mask) if n_terms else None, _p(masks), int(masks.shape[0]), _p(run_keys),
+        shots, seed, _p(term_sums) if n_terms else None, _p(bits) if n_bits else None, n_bits, _stream())
+    _lib.check(code, "mlqem_mps_sample_f64")
+    return term_sums
+
+
+def mps_sample_finish(term_ptr, coeff, term_sums, shots, *, term_values=None, values=None, variance=None):
+    """``(values, variance, term_values)`` of a sampled MPS run from its ``term_sums`` (mlqem_mps_sample_finish_f64): term_values = S_t /
+    shots, values = sum coeff * term, variance = sum coeff^2 (1 - term^2).  With the outputs given nothing is allocated."""
+    if not term_ptr.is_cuda:
+        raise _lib.NativeLibraryError(f"term_ptr must live on the GPU (got {term_ptr.device}); there is no CPU path")
+    b, n_terms, shots, dev = int(term_ptr.shape[0]) - 1, int(coeff.shape[0]), int(shots), term_ptr.device
+    if not 1 <= shots <= SIM_MAX_SHOTS:
+        raise ValueError(f"mps: shots = {shots}, want 1 .. 2^20")
+    _vec(term_ptr, "term_ptr", 1, torch.int64)
+    _vec(coeff, "coeff", n_terms, torch.float64)
+    _vec(term_sums, "term_sums", n_terms, torch.int32)
+    if coeff.device != dev or term_sums.device != dev or term_sums.shape[0] != n_terms:
+        raise ValueError(f"mps: want coeff and term_sums [{n_terms}] on {dev}")
+    term_values = _sim_out(term_values, "term_values", (n_terms,), dev)
+    values, variance = _sim_out(values, "values", (b,), dev), _sim_out(variance, "variance", (b,), dev)
+    code = _lib.load().mlqem_mps_sample_finish_f64(b, n_terms, shots, _p(term_ptr), _p(coeff) if n_terms else None,
+                                                   _p(term_sums) if n_terms else None, _p(term_values) if n_terms else None, _p(values),
+                                                   _p(variance), _stream())
+    _lib.check(code, "mlqem_mps_sample_finish_f64")
+    return values, variance, term_values
+
+
 SIM_BOUND_TABLE, SIM_BOUND_PLAIN = 0, 1   # MLQEM_SIM_BOUND_TABLE / MLQEM_SIM_BOUND_PLAIN
 
 

@@ -11,7 +11,8 @@ model (``compile_clifford_frames`` / ``sample_clifford_expectation_values`` / ``
 ``Template`` / ``Param`` / ``compile_templates`` are parameterised circuits: one template lowered once, bound on the device at many
 parameter vectors (``bound_expectation_values``), with exact gradients by the parameter-shift rule (``parameter_shift``).
 ``blackwater.sim.mps`` is the path for wide circuits that are NOT Clifford circuits: matrix-product states of bond at most 32 for
-circuits on a line (``compile_mps`` / ``run_mps`` / ``mps_expectation_values``), exact while the bonds fit and certified beyond, ideal
+circuits on a line (``compile_mps`` / ``run_mps`` / ``mps_expectation_values``; measurement shots from the same states:
+``compile_mps_shots`` / ``run_mps_shots`` / ``sample_mps_expectation_values`` / ``mps_counts``), exact while the bonds fit and certified beyond, ideal
 and, by Pauli-insertion trajectories, under a depolarising + readout model."""
 from .program import (MAX_AMPS, MAX_QUBITS_DENSITY, MAX_QUBITS_VECTOR, SUPPORTED_GATES, WAVE_AMPS, NoiseModel, SimBatch,
                       compile_programs, measured_z)
@@ -26,8 +27,9 @@ from .frames import (MAX_GROUPS, FrameBatch, FrameResult, compile_clifford_frame
                      sample_clifford_expectation_values)
 from .template import BoundBatch, Param, Template, compile_templates
 from .bound import bound_expectation_values, parameter_shift, run_bound
-from .mps import (MAX_BOND, MAX_QUBITS_MPS, MPS_BUFFER_BYTES, MpsBatch, MpsResult, compile_mps, is_line_circuit, mps_expectation_values,
-                  run_mps)
+from .mps import (MAX_BOND, MAX_GROUPS_MPS, MAX_QUBITS_MPS, MPS_BUFFER_BYTES, MpsBatch, MpsResult, MpsShotsBatch, MpsShotsResult,
+                  compile_mps, compile_mps_shots, is_line_circuit, mps_counts, mps_expectation_values, run_mps, run_mps_shots,
+                  sample_mps_expectation_values)
 from .zne import (CubicExtrapolator, CxAmplifier, ExponentialExtrapolator, GlobalFoldingAmplifier, LinearExtrapolator, LocalFoldingAmplifier,
                   PolynomialExtrapolator, QuadraticExtrapolator, QuarticExtrapolator, RichardsonExtrapolator, Schedules,
                   TwoQubitAmplifier, ZNEStrategy, build_clifford_schedules, build_schedules, fold_circuit, zne_expectation_values,
@@ -45,5 +47,6 @@ __all__ = ["MAX_AMPS", "MAX_QUBITS_DENSITY", "MAX_QUBITS_VECTOR", "SUPPORTED_GAT
            "MAX_GROUPS", "FrameBatch", "FrameResult", "compile_clifford_frames", "frame_counts", "run_clifford_frames",
            "sample_clifford_expectation_values",
            "MAX_BOND", "MAX_QUBITS_MPS", "MPS_BUFFER_BYTES", "MpsBatch", "MpsResult", "compile_mps", "is_line_circuit",
-           "mps_expectation_values", "run_mps",
+           "mps_expectation_values", "run_mps", "MAX_GROUPS_MPS", "MpsShotsBatch", "MpsShotsResult", "compile_mps_shots", "mps_counts",
+           "run_mps_shots", "sample_mps_expectation_values",
            "BoundBatch", "Param", "Template", "compile_templates", "bound_expectation_values", "parameter_shift", "run_bound"]

@@ -7,6 +7,9 @@ bond needs more than ``max_bond`` (TFIM circuits: through 5 Trotter steps at bon
 beyond: ``error_bound`` B bounds the distance of the states, so |<O>_exact - <O>_mps| <= 2 B sum|coeff|.  With a depolarising +
 readout noise model and ``trajectories`` the same kernel gives noisy values: every depolarising record inserts one drawn Pauli
 string (its probabilities do not depend on the state), readout noise is folded into the measured operators.
+
+``compile_mps_shots`` / ``run_mps_shots`` / ``sample_mps_expectation_values`` draw measurement shots from the same states
+(``mlqem_mps_sample_f64``: perfect sampling, one sweep over the sites per shot), ``mps_counts`` gives the count dictionaries.
 """
 from __future__ import annotations
 
@@ -18,7 +21,7 @@ import numpy as np
 
 from ..data.circuit import Circuit
 from .program import (_N_PARAMS, _TWO_QUBIT, OP_DIAG1, PARAM_PAD, SUPPORTED_GATES, NoiseModel, _check_coherent, _lower_terms,
-                      _one_qubit, _two_qubit, check_seed, check_trajectories)
+                      _one_qubit, _two_qubit, check_seed, check_trajectories, measurement_groups)
 
 MAX_BOND = 32            # MLQEM_MPS_MAX_BOND: theta, (2 chi) x (2 chi) complex128 = 64 KiB, sits in LDS beside a second workgroup
 MAX_QUBITS_MPS = 512     # MLQEM_MPS_MAX_QUBITS
@@ -315,23 +318,27 @@ class MpsResult:
     batch: Optional[MpsBatch] = None
 
 
-def _mps_chunks(batch: MpsBatch, trajectories: int, buffer_bytes: int):
+def _mps_chunks(batch: MpsBatch, trajectories: int, buffer_bytes: int, unit_bytes=None):
     """``(circuit range, trajectory range)`` pairs whose site-tensor workspace (n * chi * 2 * chi * 16 B per unit, plus the stash)
     stays under ``buffer_bytes``: whole circuits with all their trajectories while they fit, else one circuit with a part of them.
-    A chunk holds at least one unit."""
+    A chunk holds at least one unit.  ``unit_bytes(width)``: the bytes of one unit where they are more than that workspace."""
     from ..native import ops
+
+    if unit_bytes is None:
+        def unit_bytes(width):
+            return ops.mps_workspace_bytes(width, batch.max_bond, 1)
 
     chunks, lo, b = [], 0, len(batch)
     while lo < b:
         hi, widest = lo + 1, int(batch.n_qubits[lo])
-        per = ops.mps_workspace_bytes(widest, batch.max_bond, 1)
+        per = unit_bytes(widest)
         if per * trajectories > buffer_bytes:
             step = max(int(buffer_bytes // per), 1)
             chunks += [(range(lo, hi), range(t0, min(t0 + step, trajectories))) for t0 in range(0, trajectories, step)]
         else:
             while hi < b:
                 wider = max(widest, int(batch.n_qubits[hi]))
-                if ops.mps_workspace_bytes(wider, batch.max_bond, 1) * trajectories * (hi + 1 - lo) > buffer_bytes:
+                if unit_bytes(wider) * trajectories * (hi + 1 - lo) > buffer_bytes:
                     break
                 widest, hi = wider, hi + 1
             chunks.append((range(lo, hi), range(0, trajectories)))
@@ -391,3 +398,237 @@ def mps_expectation_values(circuits: Sequence[Any], observables: Sequence[Any], 
     circuits of up to 512 qubits whose two-qubit gates act on neighbours, any angle.  ``noise`` + ``trajectories``: the values
     under a depolarising + readout model, as means over Pauli-insertion trajectories with their standard errors."""
     return run_mps(compile_mps(circuits, observables, noise, trajectories, max_bond, cutoff), seed, run_keys, device)
+
+
+# ---- shots ------------------------------------------------------------------------------------------------------------------------
+MAX_GROUPS_MPS = 4096    # MLQEM_MPS_MAX_GROUPS: measurement groups per circuit (12 bits of a Philox counter word)
+_PAD = 32
+
+
+def _mask_words(mask: int, w: int) -> List[int]:
+    return [(mask >> (32 * j)) & 0xFFFFFFFF for j in range(w)]
+
+
+@dataclass
+class MpsShotsBatch:
+    """A batch lowered for ``mlqem_mps_sample_f64``: ``mps`` is the same batch lowered by :func:`compile_mps` (its records, terms and
+    ``site_ptr`` are the ones used here), the rest are the measurement groups."""
+
+    mps: MpsBatch
+    group_ptr: np.ndarray    # int64 [B + 1]
+    group_circ: np.ndarray   # int32 [n_groups]
+    group_off: np.ndarray    # int64 [n_groups]: the group's first letter in ``basis``
+    basis: np.ndarray        # uint8 [n_basis + 32]: one letter per (group, site): 1 X, 2 Y, 3 Z (0: padding)
+    flip: np.ndarray         # float64 [n_sites, 2]: (P(read 1 | 0), P(read 0 | 1)) of every site; (0, 0) without readout noise
+    ref_ptr: np.ndarray      # int64 [n_groups + 1]: the group's W words of a shot; times shots, in ``bits``
+    gterm_ptr: np.ndarray    # int64 [n_groups + 1]
+    gterm: np.ndarray        # int32 [n_terms]: the terms by group
+    term_mask: np.ndarray    # int32 [n_terms]: the support in masks, W words
+    term_group: np.ndarray   # int32 [n_terms]: the term's group inside its circuit
+    masks: np.ndarray        # uint32 [n_masks + 32]
+    max_groups: int = 1
+
+    def __len__(self) -> int:
+        return len(self.mps)
+
+    @property
+    def n_qubits(self) -> np.ndarray:
+        return self.mps.n_qubits
+
+    @property
+    def trajectories(self) -> Optional[int]:
+        return self.mps.trajectories
+
+    def to(self, device) -> Dict[str, Any]:
+        import torch
+
+        dev = torch.device(device)
+        out = self.mps.to(dev)
+        for k in ("group_ptr", "group_circ", "group_off", "basis", "flip", "ref_ptr", "gterm_ptr", "gterm", "term_mask"):
+            out[k] = torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(dev)
+        out["masks"] = torch.from_numpy(np.ascontiguousarray(self.masks).view(np.int32)).to(dev)
+        return out
+
+
+def compile_mps_shots(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None,
+                      trajectories: Optional[int] = None, max_bond: int = MAX_BOND, cutoff: float = DEFAULT_CUTOFF) -> MpsShotsBatch:
+    """The lowering of :func:`compile_mps` plus the measurement groups of :func:`~blackwater.sim.measurement_groups`: one basis
+    letter per (group, site) (Z where no term of the group touches the site), the ``flip`` table of the measured qubits' readout
+    noise, a support mask per term and the group of each term.  What ``compile_mps`` refuses stays refused, by the same messages
+    (X or Y terms beside readout noise, thermal relaxation, gates on qubits that are no neighbours, ...); also refused: a circuit
+    whose terms need more than 4 096 measurement groups."""
+    circuits, observables = list(circuits), list(observables)
+    base = compile_mps(circuits, observables, noise, trajectories, max_bond, cutoff)   # every check and refusal
+    group_ptr, group_circ, group_off, basis, ref_ptr = [0], [], [], [], [0]
+    gterm_ptr, gterm, term_mask, term_group, masks, flip = [0], [], [], [], [], []
+    max_groups = 1
+    for k, (obj, obs) in enumerate(zip(circuits, observables)):
+        circ = Circuit.from_any(obj)
+        n = circ.num_qubits
+        w = (n + 31) // 32
+        rows, _, _ = _lower_terms(obs, n, f"circuit {k}")
+        first_term = len(term_mask)
+        for xm, zm, _, _ in rows:
+            term_mask.append(len(masks))
+            masks += _mask_words(xm | zm, w)
+        groups_of, bases = measurement_groups(rows)
+        if len(bases) > MAX_GROUPS_MPS:
+            raise ValueError(f"circuit {k}: its terms need {len(bases)} measurement groups; MPS sampling takes at most {MAX_GROUPS_MPS} "
+                             "per circuit (split the observable)")
+        max_groups = max(max_groups, len(bases))
+        term_group += groups_of
+        for g, (gx, gy) in enumerate(bases):
+            group_circ.append(k)
+            group_off.append(len(basis))
+            basis += [1 if gx >> q & 1 else 2 if gy >> q & 1 else 3 for q in range(n)]
+            members = [first_term + t for t, tg in enumerate(groups_of) if tg == g]
+            gterm += members
+            gterm_ptr.append(len(gterm))
+            ref_ptr.append(ref_ptr[-1] + w)
+        group_ptr.append(len(group_circ))
+        table = [[0.0, 0.0] for _ in range(n)]
+        if noise is not None:
+            for q in sorted(set(base.measured[k].values())):
+                pr = noise.readout_of(circ.qubit_reg_index[q])
+                if pr is not None:
+                    table[q] = [float(pr[1]), float(pr[0])]   # (p01, p10) -> (P(read 1 | 0), P(read 0 | 1))
+        flip += table
+    if len(masks) + _PAD > 2 ** 31 - 1 or len(basis) + _PAD > 2 ** 31 - 1:
+        raise ValueError("compile_mps_shots: the batch exceeds what one call can address; split it")
+    return MpsShotsBatch(
+        mps=base, group_ptr=np.asarray(group_ptr, dtype=np.int64), group_circ=np.asarray(group_circ, dtype=np.int32),
+        group_off=np.asarray(group_off, dtype=np.int64), basis=np.asarray(basis + [0] * _PAD, dtype=np.uint8),
+        flip=np.asarray(flip + [[0.0, 0.0]], dtype=np.float64).reshape(-1, 2), ref_ptr=np.asarray(ref_ptr, dtype=np.int64),
+        gterm_ptr=np.asarray(gterm_ptr, dtype=np.int64), gterm=np.asarray(gterm, dtype=np.int32),
+        term_mask=np.asarray(term_mask, dtype=np.int32), term_group=np.asarray(term_group, dtype=np.int32),
+        masks=np.asarray(masks + [0] * _PAD, dtype=np.uint32), max_groups=max_groups)
+
+
+@dataclass
+class MpsShotsResult:
+    """What one sampled MPS call produced: tensors on the device.  The fields of ``FrameResult`` (there is no reference outcome:
+    every shot is drawn from the state), plus the run's ``discarded``, ``error_bound`` and ``bond``.  ``bits`` are packed uint32 words
+    carried as int32, CSR over ``ref_ptr`` (the W = ceil(n / 32) words of a group; a group's bits are ``[shots, W]`` from
+    ``ref_ptr[g] * shots``).
+
+    ``variance`` is the per-shot variance sum coeff^2 (1 - estimate^2), as on the other sampled paths.  Under noise shot s comes
+    from trajectory s mod T: every shot is marginally a draw from the noisy distribution, but with T < shots the shots of one
+    trajectory share a noise realisation, so the standard error of the estimate also has the between-trajectory part that
+    ``mps_expectation_values(...).std_error`` reports; T = shots gives independent shots.  The sampled distribution is that of the
+    truncated state: its trace distance from the exact state's is at most ``error_bound``."""
+
+    values: Any          # float64 [B]: sum coeff * sampled term estimate
+    variance: Any        # float64 [B]: sum coeff^2 (1 - estimate^2)
+    term_values: Any     # float64 [n_terms]
+    term_ptr: Any        # int64 [B + 1]
+    term_sums: Any       # int32 [n_terms]: S_t = sum over the shots of (-1)^popcount(bits & support)
+    ref_ptr: Any         # int64 [n_groups + 1]
+    group_ptr: Any       # int64 [B + 1]
+    discarded: Any       # float64 [B] (mean over the trajectories)
+    error_bound: Any     # float64 [B] (mean over the trajectories)
+    bond: Any            # int32 [B]
+    bits: Any = None     # int32 [n_ref * shots], with return_bits
+    shots: int = 0
+    seed: int = 0
+    trajectories: Optional[int] = None
+    batch: Optional[MpsShotsBatch] = None
+
+
+def run_mps_shots(batch: MpsShotsBatch, shots: int, seed: int = 0, run_keys=None, return_bits: bool = False, device="cuda",
+                  buffer_bytes: int = None) -> MpsShotsResult:
+    """Samples ``shots`` outcomes of every (circuit, group) of a batch lowered by :func:`compile_mps_shots`.  Per chunk of (circuit,
+    trajectory) units the MPS is run and then sampled; ``buffer_bytes`` (default :data:`MPS_BUFFER_BYTES`) bounds the site-tensor
+    workspace and the environment workspace of a chunk together.  ``run_keys`` as in :func:`run_mps`; the bits of a (circuit,
+    group, shot) depend on (seed, run key, group, shot, the circuit's records, max_bond, cutoff, trajectories) alone.  Nothing is
+    read back."""
+    import torch
+
+    from ..native import ops
+    from .program import check_shots
+    from .run import _run_keys
+
+    shots, seed = check_shots(shots, "run_mps_shots"), check_seed(seed, "run_mps_shots")
+    mps = batch.mps
+    n_traj = 1 if mps.trajectories is None else check_trajectories(mps.trajectories, "run_mps_shots")
+    if n_traj > shots:
+        raise ValueError(f"run_mps_shots: trajectories = {n_traj} exceed shots = {shots} (shot s comes from trajectory s mod "
+                         "trajectories: the others would be simulated and never measured)")
+    keys = _run_keys(run_keys, len(batch), "run_mps_shots")
+    buffer_bytes = MPS_BUFFER_BYTES if buffer_bytes is None else int(buffer_bytes)
+    if buffer_bytes < 1:
+        raise ValueError(f"run_mps_shots: buffer_bytes = {buffer_bytes!r}, want a positive number of bytes")
+    dev = torch.device(device)
+    t = batch.to(dev)
+    b, n_terms = len(batch), int(mps.term_circ.shape[0])
+    zeros = lambda n, dtype=torch.float64: torch.zeros(n, dtype=dtype, device=dev)   # noqa: E731
+    if b == 0:
+        return MpsShotsResult(zeros(0), zeros(0), zeros(0), t["term_ptr"], zeros(0, torch.int32), t["ref_ptr"], t["group_ptr"], zeros(0),
+                              zeros(0), zeros(0, torch.int32), zeros(0, torch.int32) if return_bits else None, shots, seed,
+                              mps.trajectories, batch)
+    keys_t = torch.from_numpy(keys).to(dev)
+    traj_stats = zeros((n_traj, b, ops.MPS_STATS))
+    term_sums = zeros(n_terms, torch.int32)
+    bits = zeros(int(batch.ref_ptr[-1]) * shots, torch.int32) if return_bits else None
+
+    def unit_bytes(width):
+        return ops.mps_workspace_bytes(width, mps.max_bond, 1) + ops.mps_sample_workspace_bytes(width, mps.max_bond, 1)
+
+    chunks = _mps_chunks(mps, n_traj, buffer_bytes, unit_bytes)
+    widest = [int(mps.n_qubits[list(cr)].max()) for cr, _ in chunks]
+    workspace = torch.empty((max(ops.mps_workspace_bytes(w, mps.max_bond, len(cr) * len(tr)) for w, (cr, tr) in zip(widest, chunks)),),
+                            dtype=torch.uint8, device=dev)
+    env = torch.empty((max(ops.mps_sample_workspace_bytes(w, mps.max_bond, len(cr) * len(tr)) for w, (cr, tr) in zip(widest, chunks)),),
+                      dtype=torch.uint8, device=dev)
+    for w, (cr, tr) in zip(widest, chunks):
+        ops.mps_run(t["n_qubits"], t["op_ptr"], t["ops"], t["params"], keys_t, (cr.start, len(cr)), (tr.start, len(tr)), n_traj, seed,
+                    mps.max_bond, mps.cutoff, w, workspace, traj_stats)
+        g0, g1 = int(batch.group_ptr[cr.start]), int(batch.group_ptr[cr.stop])
+        t0, t1 = int(mps.term_ptr[cr.start]), int(mps.term_ptr[cr.stop])
+        ops.mps_sample(t["n_qubits"], (cr.start, len(cr)), (tr.start, len(tr)), n_traj, mps.max_bond, w, workspace, env, (g0, g1 - g0),
+                       batch.max_groups, t["group_ptr"], t["group_circ"], t["group_off"], t["basis"], t["site_ptr"], t["flip"], t["ref_ptr"],
+                       t["gterm_ptr"], t["gterm"], (t0, t1 - t0), t["term_mask"], t["masks"], keys_t, shots, seed, term_sums, bits)
+    stats = ops.sim_mps_finish(t["term_ptr"], t["coeff"], zeros((n_traj, n_terms)), zeros((n_traj, b)), traj_stats)
+    values, variance, term_values = ops.mps_sample_finish(t["term_ptr"], t["coeff"], term_sums, shots)
+    return MpsShotsResult(values, variance, term_values, t["term_ptr"], term_sums, t["ref_ptr"], t["group_ptr"], stats["discarded"],
+                          stats["error_bound"], stats["bond"], bits, shots, seed, mps.trajectories, batch)
+
+
+def sample_mps_expectation_values(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None, *,
+                                  shots: int = None, trajectories: Optional[int] = None, max_bond: int = MAX_BOND,
+                                  cutoff: float = DEFAULT_CUTOFF, seed: int = 0, run_keys=None, return_bits: bool = False,
+                                  device="cuda") -> MpsShotsResult:
+    """Expectation values of ``observables[k]`` after ``circuits[k]`` estimated from ``shots`` measurement outcomes per measurement
+    basis, drawn from the matrix-product state of bond at most ``max_bond``: circuits of up to 512 qubits whose two-qubit gates act on
+    neighbours, any angle; ideal, or under a depolarising + readout ``noise`` model with ``trajectories``.  The limit of every
+    estimate is the value :func:`mps_expectation_values` gives."""
+    from .program import check_shots
+
+    if shots is None:
+        raise ValueError("sample_mps_expectation_values: shots is required (an int in 1 .. 2^20); mps_expectation_values gives the "
+                         "values without shot noise")
+    shots = check_shots(shots, "sample_mps_expectation_values")
+    return run_mps_shots(compile_mps_shots(circuits, observables, noise, trajectories, max_bond, cutoff), shots, seed, run_keys,
+                         return_bits, device)
+
+
+def mps_counts(result: MpsShotsResult, k: int) -> List[Dict[str, int]]:
+    """``{bitstring: count}`` per measurement group of circuit ``k``: qiskit's strings, n characters, qubit 0 the RIGHTMOST -- what
+    ``cal_z_exp`` / ``counts_to_feature_vector`` take.  Needs ``return_bits=True``; reads that circuit's bits back from the device."""
+    if result.bits is None:
+        raise ValueError("mps_counts: the result has no bits (run it with return_bits=True)")
+    batch = result.batch
+    if not 0 <= k < len(batch):
+        raise ValueError(f"mps_counts: circuit {k} of {len(batch)}")
+    n, shots = int(batch.n_qubits[k]), result.shots
+    w = (n + 31) // 32
+    out = []
+    for g in range(int(batch.group_ptr[k]), int(batch.group_ptr[k + 1])):
+        b = int(batch.ref_ptr[g]) * shots
+        words = result.bits[b:b + shots * w].cpu().numpy().view(np.uint32).reshape(shots, w)
+        counts: Dict[str, int] = {}
+        rows, freq = np.unique(words, axis=0, return_counts=True)
+        for row, f in zip(rows, freq):
+            value = sum(int(v) << (32 * j) for j, v in enumerate(row.tolist()))
+            counts[format(value, f"0{n}b")] = int(f)
+        out.append(counts)
+    return out

@@ -15,7 +15,7 @@ from .frames import sample_clifford_expectation_values
 from .program import (MAX_QUBITS_DENSITY, MAX_QUBITS_VECTOR, NoiseModel, SimBatch, check_seed, check_shots, check_trajectories,
                       compile_programs)
 from .bound import bound_expectation_values
-from .mps import DEFAULT_CUTOFF, MAX_BOND, _check_bond, _check_cutoff, mps_expectation_values
+from .mps import DEFAULT_CUTOFF, MAX_BOND, _check_bond, _check_cutoff, mps_expectation_values, sample_mps_expectation_values
 from .template import Template, has_free_parameters
 
 
@@ -244,6 +244,10 @@ _MPS_SHOTS = ("DeviceEstimator(method='mps'): shots= is not supported with it (n
               "noisy estimate's own standard error is in the metadata); run it without shots")
 
 
+_MPS_SHOTS_NONE = ("DeviceEstimator(method='mps_shots'): shots=None; it draws measurement shots from a matrix-product state (pass "
+                   "shots=N; the values without shot noise are method='mps')")
+
+
 class SimulatedJob:
     """The job of a :class:`DeviceEstimator` run: the values are already on the host when it is built."""
 
@@ -300,21 +304,30 @@ class DeviceEstimator:
     ``noise`` the values are the ideal ones and ``metadata[k] = {"truncation_error_bound": B_k, "max_bond": the largest bond
     reached}`` with |value - exact| <= 2 B_k sum|coeff|; with ``noise`` (depolarising + readout, coherent errors) they are means over
     ``trajectories`` trajectories and the metadata also has ``"std_error"`` and ``"trajectories"``.  ``shots`` with it is refused by
-    name, and so are templates.  ``"auto"`` never picks it."""
+    name, and so are templates.  ``"auto"`` never picks it.
+    ``"mps_shots"``: measurement shots drawn from those matrix-product states (:func:`sample_mps_expectation_values`), ideal or with
+    ``noise`` and ``trajectories`` (shot s comes from trajectory s mod trajectories, so ``trajectories <= shots``); it needs ``shots``
+    (``shots=None`` is refused by name, and so are templates), ``metadata[k] = {"variance": v_k, "shots": shots,
+    "truncation_error_bound": B_k, "max_bond": the largest bond reached}`` plus ``"trajectories"`` under noise, and the run keys are
+    those of the shots path.  ``variance`` is the per-shot variance; with fewer trajectories than shots the estimate's standard
+    error also has a between-trajectory part (:class:`MpsShotsResult`).  ``"auto"`` never picks it."""
 
     METHODS = ("exact", "clifford", "auto", "trajectories")
     SAMPLED_METHODS = ("frames",)   # chosen by name alone; "auto" never picks one
     WIDE_METHODS = ("mps",)         # chosen by name alone too
+    WIDE_SAMPLED_METHODS = ("mps_shots",)   # shots at width from matrix-product states; by name alone
 
     def __init__(self, noise: Optional[NoiseModel] = None, device="cuda", shots: Optional[int] = None, seed: int = 0,
                  method: str = "exact", trajectories: int = 1024, max_bond: int = MAX_BOND, cutoff: float = DEFAULT_CUTOFF):
-        methods = self.METHODS + self.SAMPLED_METHODS + self.WIDE_METHODS
+        methods = self.METHODS + self.SAMPLED_METHODS + self.WIDE_METHODS + self.WIDE_SAMPLED_METHODS
         if method not in methods:
             raise ValueError(f"DeviceEstimator: method = {method!r}, want one of {', '.join(methods)}")
         self._method = method
         self._max_bond, self._cutoff = _check_bond(max_bond, "DeviceEstimator"), _check_cutoff(cutoff, "DeviceEstimator")
         if method == "mps" and shots is not None:
             raise ValueError(_MPS_SHOTS)
+        if method == "mps_shots" and shots is None:
+            raise ValueError(_MPS_SHOTS_NONE)
         if method == "frames":
             if shots is None:
                 raise ValueError(_FRAMES_SHOTS)
@@ -354,6 +367,21 @@ class DeviceEstimator:
                                                      run_keys=default_run_keys(len(circuits), self._count << 32), device=self._device)
             variance = res.variance.cpu().numpy()
             return SimulatedJob(res.values.cpu().numpy(), f"sim-{self._count}", [{"variance": float(v), "shots": shots} for v in variance])
+        if self._method == "mps_shots":
+            if shots is None:
+                raise ValueError(_MPS_SHOTS_NONE)
+            shots, seed = check_shots(shots, "DeviceEstimator.run"), check_seed(seed, "DeviceEstimator.run")
+            self._count += 1
+            noisy = self._noise is not None
+            res = sample_mps_expectation_values(circuits, observables, self._noise, shots=shots, max_bond=self._max_bond,
+                                                cutoff=self._cutoff, trajectories=self._trajectories if noisy else None, seed=seed,
+                                                run_keys=default_run_keys(len(circuits), self._count << 32), device=self._device)
+            metadata = [{"variance": float(v), "shots": shots, "truncation_error_bound": float(b), "max_bond": int(k)}
+                        for v, b, k in zip(res.variance.cpu().numpy(), res.error_bound.cpu().numpy(), res.bond.cpu().numpy())]
+            if noisy:
+                for m in metadata:
+                    m.update(trajectories=self._trajectories)
+            return SimulatedJob(res.values.cpu().numpy(), f"sim-{self._count}", metadata)
         if self._method == "mps":
             if shots is not None:
                 raise ValueError(_MPS_SHOTS)
@@ -404,7 +432,7 @@ class DeviceEstimator:
         if shots is not None:
             raise ValueError(f"DeviceEstimator: circuit {first} is a template with free parameters and shots= is set: shots are not "
                              f"drawn on the bound path; {how}")
-        if self._method in ("trajectories", "clifford", "frames", "mps"):
+        if self._method in ("trajectories", "clifford", "frames", "mps", "mps_shots"):
             raise ValueError(f"DeviceEstimator(method={self._method!r}): circuit {first} is a template with free parameters; {how}")
         templates = [Template.from_any(c) for c in circuits]
         for k, (t, p) in enumerate(zip(templates, parameter_values)):

@@ -1,5 +1,6 @@
 // Matrix-product-state simulation of circuits on a line, a batch per call (mlqem_mps_run_f64, mlqem_mps_terms_f64,
-// mlqem_mps_finish_f64).  include/mlqem_hip.h has the contract: the records, the keep rule, the certificate, the draws.
+// mlqem_mps_finish_f64), and measurement shots from the states it leaves (mlqem_mps_sample_f64, mlqem_mps_sample_finish_f64: the
+// kernels after mps_finish_kernel).  include/mlqem_hip.h has the contract: the records, the keep rule, the certificate, the draws.
 //
 // Work unit of the run kernel: one (circuit, trajectory) pair, a workgroup each.  The site tensors A[q] (chi_l x 2 x chi_r complex
 // float64, entry (l, s, r) at (l * 2 + s) * chi + r, chi = max_bond) live in the unit's slice of a global workspace; the bond sizes
@@ -496,6 +497,227 @@ __global__ __launch_bounds__(kBlock) void mps_finish_kernel(int64_t B, int64_t n
   }
 }
 
+// ---- shots (mlqem_mps_sample_f64, mlqem_mps_sample_finish_f64) ------------------------------------------------------------------------
+// Perfect sampling: the right environments once per unit, then one sweep over the sites per shot, each bit drawn from its
+// conditional probability.  Nothing here relies on the gauge: the weights are formed against the environments.
+constexpr int kMpsShotBlock = MLQEM_MPS_SHOT_BLOCK;                 // 16 shots a workgroup
+constexpr int kMpsWaveShots = kMpsShotBlock / (kBlock / kWave);     // 4 of them a wave, in registers side by side
+constexpr int kMpsMaxWords = (kMpsMaxQubits + 31) / 32;             // 16 words of packed bits a shot
+static_assert(kMpsWaveShots * (kBlock / kWave) == kMpsShotBlock && kWave == 2 * kMpsMaxBond, "a lane per (s, r), four shots a wave");
+
+__host__ __device__ inline int64_t mps_env_unit_bytes(int max_q, int chi) { return 16 * ((int64_t)max_q * 2 * chi * chi); }
+
+// the value lane `from` (a constant) holds, as a scalar
+template <int from> __device__ __forceinline__ double mps_lane(double v) {
+  const uint64_t b = __builtin_bit_cast(uint64_t, v);
+  const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)b, from), hi = __builtin_amdgcn_readlane((uint32_t)(b >> 32), from);
+  return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+// the sum over the lane's half of the wave (32 lanes), a butterfly in a fixed order: every lane of a half ends with the same bits
+__device__ __forceinline__ double mps_half_sum(double v) {
+#pragma unroll
+  for (int d = kMpsMaxBond / 2; d >= 1; d >>= 1) v = v + __shfl_xor(v, d, kWave);
+  return v;
+}
+__device__ __forceinline__ sim_c mps_other_half(sim_c v) { return sim_c{__shfl_xor(v.x, kMpsMaxBond, kWave), __shfl_xor(v.y, kMpsMaxBond, kWave)}; }
+// the physical components (v0, v1) of a lane pair in the basis of `letter` (1 X: (v0 +- v1) c, 2 Y: (v0 -+ i v1) c); `mine` is the
+// lane's own component, s its index
+__device__ __forceinline__ sim_c mps_mix(sim_c mine, int s, int letter) {
+  const sim_c other = mps_other_half(mine);
+  const sim_c v0 = s ? other : mine, v1 = s ? mine : other;
+  const sim_c w1 = letter == 2 ? sim_c{v1.y, -v1.x} : v1;   // -i v1 for Y
+  const sim_c r = s ? v0 - w1 : v0 + w1;
+  return 0.7071067811865476 * r;
+}
+
+// Right environments of one (circuit, trajectory) unit, a workgroup each, right to left: R[n] = [1], G[q][l, s, r'] = sum_r
+// A[q][l, s, r] R[q + 1][r, r'] (written to `env` in the layout of the site tensors), R[q][l, l'] = sum_(s, r') G[q][l, s, r']
+// conj(A[q][l', s, r']).  Every sum runs in index order.
+__global__ __launch_bounds__(kBlock) void mps_env_kernel(int B, const int32_t* __restrict__ n_qubits, int circ_first, int traj_count, int chi,
+                                                         int max_q, const char* __restrict__ workspace, char* __restrict__ env) {
+  __shared__ sim_c R[kMpsMaxBond * kMpsMaxBond];
+  __shared__ sim_c Gl[kMpsMaxBond * 2 * kMpsMaxBond];
+  const int tid = (int)threadIdx.x, unit = (int)blockIdx.x, cl = unit / traj_count;
+  const int c = min(max(circ_first + cl, 0), B - 1);
+  const int n = min(max(n_qubits[c], 1), max_q);
+  const char* base = workspace + (int64_t)unit * mps_unit_bytes(max_q, chi);
+  const int* gdims = reinterpret_cast<const int*>(base);
+  const sim_c* A = reinterpret_cast<const sim_c*>(base + mps_dims_bytes(max_q));
+  sim_c* G = reinterpret_cast<sim_c*>(env + (int64_t)unit * mps_env_unit_bytes(max_q, chi));
+  const int S = 2 * chi * chi;
+  if (tid == 0) R[0] = sim_c{1.0, 0.0};
+  __syncthreads();
+  for (int q = n - 1; q >= 0; --q) {
+    const int dl = min(max(gdims[q], 1), chi), dr = min(max(gdims[q + 1], 1), chi);
+    const sim_c* a = A + (int64_t)q * S;
+    sim_c* g = G + (int64_t)q * S;
+    const int items = dl * 2 * dr;
+    for (int it0 = 0; it0 < items; it0 += kBlock) {
+      const int it = it0 + tid, ic = min(it, items - 1);
+      const int row = ic / dr, rp = ic - row * dr;   // row = l * 2 + s
+      sim_c acc{0.0, 0.0};
+      for (int r = 0; r < dr; ++r) acc = cmac(acc, a[row * chi + r], R[r * kMpsMaxBond + rp]);
+      if (it < items) {
+        Gl[row * kMpsMaxBond + rp] = acc;
+        g[row * chi + rp] = acc;
+      }
+    }
+    __syncthreads();
+    for (int it0 = 0; it0 < dl * dl; it0 += kBlock) {   // R is read above only: the barrier before this loop frees it
+      const int it = it0 + tid, ic = min(it, dl * dl - 1);
+      const int l = ic / dl, lp = ic - l * dl;
+      sim_c acc{0.0, 0.0};
+      for (int s = 0; s < 2; ++s)
+        for (int rp = 0; rp < dr; ++rp) acc = cmac(acc, Gl[(l * 2 + s) * kMpsMaxBond + rp], cconj(a[(lp * 2 + s) * chi + rp]));
+      if (it < dl * dl) R[l * kMpsMaxBond + lp] = acc;
+    }
+    __syncthreads();
+  }
+}
+
+// One workgroup per (measurement group, trajectory of the chunk, block of kMpsShotBlock of that trajectory's shots).  The sites
+// run in the outer loop: A[q] and G[q] are staged into LDS once for the block, then every wave advances its four shots, lane =
+// (s, r): a = sum_l v[l] A[l, s, r], g = sum_l v[l] G[l, s, r], the basis letter mixes s, p_b = sum_r Re(g_b[r] conj(a_b[r])) over
+// the lane's half, the draw of include/mlqem_hip.h, v <- a_b / sqrt(p_b).  v (a row of V per shot) is read and written by its own
+// wave only.  A lane with r >= chi_r reads lane chi_r - 1's entries and adds nothing.
+__global__ __launch_bounds__(kBlock) void mps_sample_kernel(
+    int B, const int32_t* __restrict__ n_qubits, int circ_first, int circ_count, int traj_first, int traj_count, int T, int chi, int max_q,
+    const char* __restrict__ workspace, const char* __restrict__ env, int64_t group_first, int64_t n_groups,
+    const int64_t* __restrict__ group_ptr, const int32_t* __restrict__ group_circ, const int64_t* __restrict__ group_off,
+    const uint8_t* __restrict__ basis, int64_t n_basis, const int64_t* __restrict__ site_ptr, const double* __restrict__ flip,
+    int64_t n_sites, const int64_t* __restrict__ ref_ptr, const int64_t* __restrict__ gterm_ptr, const int32_t* __restrict__ gterm,
+    int64_t n_terms, const int32_t* __restrict__ term_mask, const uint32_t* __restrict__ masks, int64_t n_masks,
+    const int64_t* __restrict__ run_keys, int shots, int n_blocks, uint32_t seed_lo, uint32_t seed_hi, int32_t* __restrict__ term_sums,
+    uint32_t* __restrict__ bits, int64_t n_bits) {
+  __shared__ sim_c Al[kMpsMaxBond * 2 * kMpsMaxBond];
+  __shared__ sim_c Gl[kMpsMaxBond * 2 * kMpsMaxBond];
+  __shared__ sim_c V[kMpsShotBlock * kMpsMaxBond];
+  __shared__ uint32_t words[kMpsShotBlock * kMpsMaxWords];
+  const int tid = (int)threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
+  const int64_t rest = (int64_t)blockIdx.x / n_blocks;
+  const int sb = (int)((int64_t)blockIdx.x - rest * n_blocks), tl = (int)(rest % traj_count);
+  const int64_t g = min(max(group_first + rest / traj_count, (int64_t)0), n_groups - 1);
+  const int c = min(max(group_circ[g], circ_first), min(circ_first + circ_count, B) - 1);
+  const int traj = traj_first + tl, unit = (c - circ_first) * traj_count + tl;
+  const int n = min(max(n_qubits[c], 1), max_q), W = (n + 31) >> 5;
+  const int per = traj < shots ? (shots - traj + T - 1) / T : 0;   // the shots traj, traj + T, ... below `shots`
+  const int first = sb * kMpsShotBlock, count = min(max(per - first, 0), kMpsShotBlock);
+  if (count == 0) return;   // workgroup-uniform, before any barrier
+  const uint32_t glocal = (uint32_t)(g - min(max(group_ptr[c], (int64_t)0), g)) & (MLQEM_MPS_MAX_GROUPS - 1);
+  const int64_t key = run_keys[c];
+  const uint32_t key_lo = (uint32_t)(uint64_t)key, key_hi = (uint32_t)((uint64_t)key >> 32);
+  const int64_t lo = min(max(group_off[g], (int64_t)0), max(n_basis - n, (int64_t)0));
+  const int64_t sbase = min(max(site_ptr[c], (int64_t)0), max(n_sites - n, (int64_t)0));
+  const char* base = workspace + (int64_t)unit * mps_unit_bytes(max_q, chi);
+  const int* gdims = reinterpret_cast<const int*>(base);
+  const sim_c* A = reinterpret_cast<const sim_c*>(base + mps_dims_bytes(max_q));
+  const sim_c* G = reinterpret_cast<const sim_c*>(env + (int64_t)unit * mps_env_unit_bytes(max_q, chi));
+  const int S = 2 * chi * chi;
+  const int s = lane >> 5, r = lane & (kMpsMaxBond - 1);
+  if (tid < kMpsShotBlock) V[tid * kMpsMaxBond] = sim_c{1.0, 0.0};
+  uint32_t word[kMpsWaveShots];
+#pragma unroll
+  for (int j = 0; j < kMpsWaveShots; ++j) word[j] = 0u;
+  for (int q = 0; q < n; ++q) {
+    const int dl = min(max(gdims[q], 1), chi), dr = min(max(gdims[q + 1], 1), chi);
+    const sim_c* a = A + (int64_t)q * S;
+    const sim_c* gq = G + (int64_t)q * S;
+    __syncthreads();   // the last site's reads of Al and Gl are over (first site: V is set)
+    for (int it = tid; it < dl * 2 * chi; it += kBlock) {
+      Al[it] = a[it];
+      Gl[it] = gq[it];
+    }
+    __syncthreads();
+    const int letter = (int)(basis[min(lo + q, n_basis - 1)] & 3);
+    const int64_t sq = min(sbase + q, n_sites - 1);
+    const double flip0 = flip[2 * sq], flip1 = flip[2 * sq + 1];
+    const bool live = r < dr;
+    const int col = s * chi + min(r, dr - 1);
+    sim_c av[kMpsWaveShots], gv[kMpsWaveShots];
+#pragma unroll
+    for (int j = 0; j < kMpsWaveShots; ++j) av[j] = gv[j] = sim_c{0.0, 0.0};
+    for (int l = 0; l < dl; ++l) {
+      const sim_c ae = Al[l * 2 * chi + col], ge = Gl[l * 2 * chi + col];
+#pragma unroll
+      for (int j = 0; j < kMpsWaveShots; ++j) {
+        const sim_c v = V[(wave * kMpsWaveShots + j) * kMpsMaxBond + l];
+        av[j] = cmac(av[j], v, ae);
+        gv[j] = cmac(gv[j], v, ge);
+      }
+    }
+    if (letter == 1 || letter == 2) {   // workgroup-uniform
+#pragma unroll
+      for (int j = 0; j < kMpsWaveShots; ++j) {
+        av[j] = mps_mix(av[j], s, letter);
+        gv[j] = mps_mix(gv[j], s, letter);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kMpsWaveShots; ++j) {
+      const double sum = mps_half_sum(live ? gv[j].x * av[j].x + gv[j].y * av[j].y : 0.0);
+      const double p0 = mps_lane<0>(sum), p1 = mps_lane<kMpsMaxBond>(sum);
+      const double w0 = p0 > 0.0 ? p0 : 0.0, w1 = p1 > 0.0 ? p1 : 0.0;   // a NaN weight counts as 0
+      const int shot = traj + (first + wave * kMpsWaveShots + j) * T;
+      uint32_t x[4];
+      philox4x32_10(0x80000000u | (glocal << 9) | (uint32_t)q, (uint32_t)shot, key_lo, key_hi, seed_lo, seed_hi, x);
+      const double u = ((double)(x[0] >> 5) * 67108864.0 + (double)(x[1] >> 6)) * 0x1p-53;
+      const double u2 = ((double)(x[2] >> 5) * 67108864.0 + (double)(x[3] >> 6)) * 0x1p-53;
+      const double target = u * (w0 + w1);
+      const int b = __builtin_amdgcn_readfirstlane((target < w0 || !(w1 > 0.0)) ? 0 : 1);
+      const uint32_t reported = (uint32_t)b ^ (u2 < (b ? flip1 : flip0) ? 1u : 0u);
+      word[j] |= reported << (q & 31);
+      const double root = sqrt(b ? p1 : p0);
+      if (live && s == b) V[(wave * kMpsWaveShots + j) * kMpsMaxBond + r] = sim_c{av[j].x / root, av[j].y / root};
+    }
+    if ((q & 31) == 31 || q == n - 1) {
+#pragma unroll
+      for (int j = 0; j < kMpsWaveShots; ++j) {
+        if (lane == 0) words[(wave * kMpsWaveShots + j) * kMpsMaxWords + (q >> 5)] = word[j];
+        word[j] = 0u;
+      }
+    }
+  }
+  __syncthreads();
+  const int64_t rb = min(max(ref_ptr[g], (int64_t)0), (int64_t)0x7FFFFFFF) * shots;
+  if (bits != nullptr) {
+    for (int it = tid; it < count * W; it += kBlock) {
+      const int sh = it / W, w = it - sh * W;
+      const int64_t at = rb + (int64_t)(traj + (first + sh) * T) * W + w;
+      if (at < n_bits) bits[at] = words[sh * kMpsMaxWords + w];
+    }
+  }
+  // S_t of the group's terms over the block's shots: one integer atomic per (term, block)
+  const int64_t tb = min(max(gterm_ptr[g], (int64_t)0), n_terms), te = min(max(gterm_ptr[g + 1], tb), n_terms);
+  for (int64_t i0 = tb; i0 < te; i0 += kBlock) {
+    const int64_t i = i0 + tid;
+    const int t = min(max(gterm[min(i, n_terms - 1)], 0), (int)(n_terms - 1));
+    const int64_t tm = term_mask[t];
+    int sum = 0;
+    for (int sh = 0; sh < count; ++sh) {
+      uint32_t par = 0u;
+      for (int w = 0; w < W; ++w) par ^= words[sh * kMpsMaxWords + w] & masks[min(max(tm + w, (int64_t)0), n_masks - 1)];
+      sum += 1 - 2 * (int)(__popc(par) & 1);
+    }
+    if (i < te) atomicAdd(&term_sums[t], sum);
+  }
+}
+
+// term_values = S_t / shots, values and variance with the expressions of mlqem_sim_sample_f64 (sample_value_variance)
+__global__ __launch_bounds__(kBlock) void mps_sample_finish_kernel(int64_t n_circuits, const int64_t* __restrict__ term_ptr,
+                                                                   const double* __restrict__ coeff, int64_t n_terms,
+                                                                   const int32_t* __restrict__ term_sums, int shots,
+                                                                   double* __restrict__ term_values, double* __restrict__ values,
+                                                                   double* __restrict__ variance) {
+  const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (c >= n_circuits) return;
+  const int64_t tb = min(max(term_ptr[c], (int64_t)0), n_terms), te = min(max(term_ptr[c + 1], tb), n_terms);
+  sample_value_variance(coeff, tb, te, values[c], variance[c], [&](int64_t t) {
+    const double tv = (double)term_sums[t] / (double)shots;
+    term_values[t] = tv;
+    return tv;
+  });
+}
+
 bool mps_shape_ok(int64_t n_circuits, int64_t circ_first, int64_t circ_count, int64_t traj_first, int64_t traj_count, int64_t trajectories,
                   int64_t max_bond, int64_t max_qubits) {
   return n_circuits >= 1 && circ_first >= 0 && circ_count >= 1 && circ_first + circ_count <= n_circuits && traj_first >= 0 &&
@@ -579,5 +801,70 @@ extern "C" int mlqem_mps_finish_f64(int64_t n_circuits, int64_t n_terms, int64_t
   hipLaunchKernelGGL(mps_finish_kernel, dim3((unsigned)ceil_div(rows, (int64_t)kBlock)), dim3(kBlock), 0, as_stream(stream), n_circuits, n_terms,
                      (int)trajectories, term_ptr, coeff, traj_term_values, traj_norm, traj_stats, term_values, term_std_error, values,
                      std_error, norm, discarded, error_bound, bond);
+  return launch_status();
+}
+
+extern "C" size_t mlqem_mps_sample_workspace_bytes(int64_t max_qubits, int64_t max_bond, int64_t n_units) {
+  if (max_qubits < 1 || max_qubits > kMpsMaxQubits || max_bond < 1 || max_bond > kMpsMaxBond || n_units < 0) return 0;
+  return (size_t)(mps_env_unit_bytes((int)max_qubits, (int)max_bond) * n_units);
+}
+
+extern "C" int mlqem_mps_sample_f64(int64_t n_circuits, const int32_t* n_qubits, int64_t circ_first, int64_t circ_count, int64_t traj_first,
+                                    int64_t traj_count, int64_t trajectories, int64_t max_bond, int64_t max_qubits, const void* workspace,
+                                    size_t workspace_bytes, void* sample_workspace, size_t sample_workspace_bytes, int64_t group_first,
+                                    int64_t group_count, int64_t n_groups, int64_t max_groups, const int64_t* group_ptr,
+                                    const int32_t* group_circ, const int64_t* group_off, const uint8_t* basis, int64_t n_basis,
+                                    const int64_t* site_ptr, const double* flip, int64_t n_sites, const int64_t* ref_ptr,
+                                    const int64_t* gterm_ptr, const int32_t* gterm, int64_t term_first, int64_t term_count, int64_t n_terms,
+                                    const int32_t* term_mask, const uint32_t* masks, int64_t n_masks, const int64_t* run_keys, int64_t shots,
+                                    uint64_t seed, int32_t* term_sums, uint32_t* bits, int64_t n_bits, mlqem_stream_t stream) {
+  begin_launches();
+  if (n_circuits == 0) return MLQEM_OK;
+  if (shots < 1 || shots > MLQEM_SIM_MAX_SHOTS) return MLQEM_ERR_BAD_ARG;
+  if (!mps_shape_ok(n_circuits, circ_first, circ_count, traj_first, traj_count, trajectories, max_bond, max_qubits)) return MLQEM_ERR_BAD_ARG;
+  if (group_first < 0 || group_count < 1 || n_groups < 1 || group_first + group_count > n_groups || max_groups < 1 || n_basis < 1 ||
+      n_sites < 1 || term_first < 0 || term_count < 0 || n_terms < 0 || term_first + term_count > n_terms || n_masks < 0 || n_bits < 0)
+    return MLQEM_ERR_BAD_ARG;
+  if (max_groups > MLQEM_MPS_MAX_GROUPS) return MLQEM_ERR_UNSUPPORTED;
+  const int64_t per = (shots + trajectories - 1) / trajectories, n_blocks = (per + kMpsShotBlock - 1) / kMpsShotBlock;
+  if (n_circuits > 0x7FFFFFFFll || n_groups > 0x7FFFFFFFll || n_terms > 0x7FFFFFFFll || n_masks > 0x7FFFFFFFll ||
+      circ_count * traj_count > 0x7FFFFFFFll || group_count > 0x7FFFFFFFll / (traj_count * n_blocks))
+    return MLQEM_ERR_UNSUPPORTED;
+  if (!n_qubits || !workspace || !sample_workspace || !group_ptr || !group_circ || !group_off || !basis || !site_ptr || !flip || !ref_ptr ||
+      !gterm_ptr || !run_keys || (n_terms > 0 && (!gterm || !term_mask || !masks || !term_sums || n_masks < 1)) || (n_bits > 0 && !bits))
+    return MLQEM_ERR_BAD_ARG;
+  if (!aligned_to(workspace, 16) || !aligned_to(sample_workspace, 16) || !aligned_to(run_keys, 8) || !aligned_to(flip, 8))
+    return MLQEM_ERR_BAD_ARG;
+  const int64_t units = circ_count * traj_count;
+  if (workspace_bytes < mlqem_mps_workspace_bytes(max_qubits, max_bond, units) ||
+      sample_workspace_bytes < mlqem_mps_sample_workspace_bytes(max_qubits, max_bond, units))
+    return MLQEM_ERR_WORKSPACE;
+  const hipStream_t st = as_stream(stream);
+  const char* ws = static_cast<const char*>(workspace);
+  char* env = static_cast<char*>(sample_workspace);
+  // the chunk that holds a circuit's first trajectories zeroes its sums; the chunks of its other trajectories add to them
+  if (traj_first == 0 && term_count > 0 &&
+      hipMemsetAsync(term_sums + term_first, 0, (size_t)term_count * sizeof(int32_t), st) != hipSuccess)
+    return MLQEM_ERR_LAUNCH;
+  hipLaunchKernelGGL(mps_env_kernel, dim3((unsigned)units), dim3(kBlock), 0, st, (int)n_circuits, n_qubits, (int)circ_first, (int)traj_count,
+                     (int)max_bond, (int)max_qubits, ws, env);
+  hipLaunchKernelGGL(mps_sample_kernel, dim3((unsigned)(group_count * traj_count * n_blocks)), dim3(kBlock), 0, st, (int)n_circuits, n_qubits,
+                     (int)circ_first, (int)circ_count, (int)traj_first, (int)traj_count, (int)trajectories, (int)max_bond, (int)max_qubits, ws,
+                     env, group_first, n_groups, group_ptr, group_circ, group_off, basis, n_basis, site_ptr, flip, n_sites, ref_ptr, gterm_ptr,
+                     gterm, n_terms, term_mask, masks, n_masks, run_keys, (int)shots, (int)n_blocks, (uint32_t)seed, (uint32_t)(seed >> 32),
+                     term_sums, n_bits > 0 ? bits : nullptr, n_bits);
+  return launch_status();
+}
+
+extern "C" int mlqem_mps_sample_finish_f64(int64_t n_circuits, int64_t n_terms, int64_t shots, const int64_t* term_ptr, const double* coeff,
+                                           const int32_t* term_sums, double* term_values, double* values, double* variance,
+                                           mlqem_stream_t stream) {
+  begin_launches();
+  if (n_circuits < 0 || n_terms < 0 || shots < 1 || shots > MLQEM_SIM_MAX_SHOTS) return MLQEM_ERR_BAD_ARG;
+  if (n_circuits > 0x7FFFFFFFll || n_terms > 0x7FFFFFFFll) return MLQEM_ERR_UNSUPPORTED;
+  if (n_circuits == 0) return MLQEM_OK;
+  if (!term_ptr || !values || !variance || (n_terms > 0 && (!coeff || !term_sums || !term_values))) return MLQEM_ERR_BAD_ARG;
+  hipLaunchKernelGGL(mps_sample_finish_kernel, dim3((unsigned)ceil_div(n_circuits, (int64_t)kBlock)), dim3(kBlock), 0, as_stream(stream),
+                     n_circuits, term_ptr, coeff, n_terms, term_sums, (int)shots, term_values, values, variance);
   return launch_status();
 }

@@ -336,6 +336,55 @@ int mlqem_linear_fanout_tables_chain_f32(const mlqem_fanout_tables* d, const mlq
                                          const int32_t* x_rows, float drop_p, uint64_t seed, const uint64_t* seed_counter,
                                          mlqem_stream_t stream);
 
+#define MLQEM_FANOUT_POOL_MAX_TABLES 5
+#define MLQEM_FANOUT_POOL_MAX_TERMS 3
+#define MLQEM_FANOUT_POOL_BLOCKS 3
+
+/* The fan-out with POOLED blocks: up to MLQEM_FANOUT_POOL_MAX_TABLES tables that share one row map (layout and row map as in
+ * mlqem_fanout_tables), block k the sum of n_terms[k] <= MLQEM_FANOUT_POOL_MAX_TERMS projections
+ *     V_k = act_k(sum_t T[w_table[k][t]] (w_scale[k][t] * (w[k][t] - w_minus[k][t]))^T + bias[k]) * rowscale[k]
+ * with its OWN dropout probability drop_p[k] and seed seed[k] (mask and seed counter as in mlqem_linear_fanout_tables_f32).
+ * Block 0 is stored (y[0]) and may carry the chain of mlqem_linear_fanout_tables_chain_f32 (chain->block == 0, or chain == NULL): its
+ * values and the chain's are those of that entry point, bit for bit.  Blocks 1 and 2 are pooled: the launch leaves
+ *     out_mean[k][g] = (1/n_g) sum_{r in g} V_k[r]      out_wmean[k][g] = (1/n_g) sum_r pool_weights[k][r] V_k[r]     ([B, out_cols])
+ * over the row ranges graph_ptr[g] .. graph_ptr[g + 1] (graph_ptr[B] == N), and in gate_bits[k] the per-node sign bits of V_k in the
+ * per-node section of the gate buffer of mlqem_csr_aggregate_pool_f32 (mlqem_csr_aggregate_pool_gate_bytes(N, out_cols) bytes; 16 bits
+ * a node, bit 4 slice + v = V_k[node][4 slice + v] > 0).  The tile records and ballots of that buffer are NOT written: it serves the
+ * readers of the per-node section (mlqem_pooled_grad_*, mlqem_linear_wgrad_tables_f32), not mlqem_segment_pool_bwd_f32.  y[k] of a
+ * pooled block is optional: with it V_k is stored as well (tests; a pooled block's values otherwise never reach memory).
+ * The sums are deterministic and do not depend on the grid: a wave owns 256 consecutive rows at a time and leaves one partial per
+ * (tile, graph) in the workspace (pool layout), added in tile order by the pool's finish kernel.  max_groups > 0 caps the grid (tests).
+ * Exactly MLQEM_FANOUT_POOL_BLOCKS blocks (else MLQEM_ERR_UNSUPPORTED); 17 <= cols <= 24, out_cols <= 16; out_cols <= 12 with a chain. */
+typedef struct mlqem_fanout_pool {
+  int32_t n_tables, n_blocks, cols, out_cols;
+  const void* table[MLQEM_FANOUT_POOL_MAX_TABLES];
+  int64_t ldt[MLQEM_FANOUT_POOL_MAX_TABLES];
+  int32_t n_terms[MLQEM_FANOUT_POOL_BLOCKS];
+  int32_t max_groups;
+  const float* w[MLQEM_FANOUT_POOL_BLOCKS][MLQEM_FANOUT_POOL_MAX_TERMS];
+  const float* w_minus[MLQEM_FANOUT_POOL_BLOCKS][MLQEM_FANOUT_POOL_MAX_TERMS];
+  float w_scale[MLQEM_FANOUT_POOL_BLOCKS][MLQEM_FANOUT_POOL_MAX_TERMS];
+  int32_t w_table[MLQEM_FANOUT_POOL_BLOCKS][MLQEM_FANOUT_POOL_MAX_TERMS];
+  const float* bias[MLQEM_FANOUT_POOL_BLOCKS];
+  const float* rowscale[MLQEM_FANOUT_POOL_BLOCKS];
+  int32_t act[MLQEM_FANOUT_POOL_BLOCKS];
+  float drop_p[MLQEM_FANOUT_POOL_BLOCKS];
+  uint64_t seed[MLQEM_FANOUT_POOL_BLOCKS];
+  void* y[MLQEM_FANOUT_POOL_BLOCKS];
+  int64_t ldy[MLQEM_FANOUT_POOL_BLOCKS];
+  const float* pool_weights[MLQEM_FANOUT_POOL_BLOCKS];       /* entries 1 and 2 */
+  float* out_mean[MLQEM_FANOUT_POOL_BLOCKS];
+  int64_t ld_mean[MLQEM_FANOUT_POOL_BLOCKS];
+  float* out_wmean[MLQEM_FANOUT_POOL_BLOCKS];
+  int64_t ld_wmean[MLQEM_FANOUT_POOL_BLOCKS];
+  uint8_t* gate_bits[MLQEM_FANOUT_POOL_BLOCKS];
+  const int32_t* graph_ptr;
+  int64_t num_graphs;
+} mlqem_fanout_pool;
+size_t mlqem_linear_fanout_pool_workspace_bytes(int64_t N, int64_t B, int out_cols);
+int mlqem_linear_fanout_pool_f32(const mlqem_fanout_pool* d, const mlqem_fanout_chain* chain, int64_t N, const int32_t* x_rows,
+                                 const uint64_t* seed_counter, void* workspace, size_t workspace_bytes, mlqem_stream_t stream);
+
 size_t mlqem_linear_wgrad_workspace_bytes(int I, int O);
 
 /* gw[o,i] (+)= sum_n gy[n,o] * x[n,i] ;  gb[o] (+)= sum_n gy[n,o]  (gb may be NULL).  Matrix-core partial sums per

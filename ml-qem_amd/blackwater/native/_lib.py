@@ -65,6 +65,25 @@ class FanoutChain(ctypes.Structure):
                 ("rowscale", c_void_p)]
 
 
+FANOUT_POOL_MAX_TABLES, FANOUT_POOL_MAX_TERMS, FANOUT_POOL_BLOCKS = 5, 3, 3   # MLQEM_FANOUT_POOL_*
+
+
+class FanoutPool(ctypes.Structure):
+    """``mlqem_fanout_pool``: five tables, one stored (optionally chained) block and two pooled blocks of up to three terms each."""
+
+    _T = FANOUT_POOL_MAX_TERMS
+    _B = FANOUT_POOL_BLOCKS
+    _fields_ = [("n_tables", ctypes.c_int32), ("n_blocks", ctypes.c_int32), ("cols", ctypes.c_int32), ("out_cols", ctypes.c_int32),
+                ("table", c_void_p * FANOUT_POOL_MAX_TABLES), ("ldt", c_int64 * FANOUT_POOL_MAX_TABLES),
+                ("n_terms", ctypes.c_int32 * _B), ("max_groups", ctypes.c_int32),
+                ("w", (c_void_p * _T) * _B), ("w_minus", (c_void_p * _T) * _B), ("w_scale", (c_float * _T) * _B),
+                ("w_table", (ctypes.c_int32 * _T) * _B), ("bias", c_void_p * _B), ("rowscale", c_void_p * _B),
+                ("act", ctypes.c_int32 * _B), ("drop_p", c_float * _B), ("seed", c_uint64 * _B), ("y", c_void_p * _B),
+                ("ldy", c_int64 * _B), ("pool_weights", c_void_p * _B), ("out_mean", c_void_p * _B), ("ld_mean", c_int64 * _B),
+                ("out_wmean", c_void_p * _B), ("ld_wmean", c_int64 * _B), ("gate_bits", c_void_p * _B), ("graph_ptr", c_void_p),
+                ("num_graphs", c_int64)]
+
+
 MAX_WGRAD_TABLES = 4    # MLQEM_WGRAD_MAX_TABLES
 
 
@@ -117,6 +136,8 @@ SIGNATURES = {
     "mlqem_linear_parts_f32": (_I, [_P, _P, _P, _I, _P, _P, _P, _L, _P, _L, _F, _P, _P]),
     "mlqem_linear_fanout_tables_f32": (_I, [_P, _L, _P, _F, _U, _P, _P]),
     "mlqem_linear_fanout_tables_chain_f32": (_I, [_P, _P, _L, _P, _F, _U, _P, _P]),
+    "mlqem_linear_fanout_pool_workspace_bytes": (_S, [_L, _L, _I]),
+    "mlqem_linear_fanout_pool_f32": (_I, [_P, _P, _L, _P, _P, _P, _S, _P]),
     "mlqem_linear_wgrad_workspace_bytes": (_S, [_I, _I]),
     "mlqem_linear_wgrad_f32": (_I, [_P, _L, _P, _L, _P, _P, _L, _I, _I, _I, _P, _S, _P, _P]),
     "mlqem_linear_wgrad_parts_f32": (_I, [_P, _P, _L, _P, _P, _L, _I, _I, _P, _S, _P, _P]),

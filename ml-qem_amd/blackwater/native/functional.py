@@ -448,6 +448,14 @@ _GCN_TABLE_WGRAD = os.environ.get("MLQEM_GCN_TABLE_WGRAD", "1") != "0"
 # elements from the gate bits (A/B of the second stage).
 _TABLE_GRAD = os.environ.get("MLQEM_TABLE_GRAD", "1") != "0"
 _TABLE_GRAD_SYNTH = os.environ.get("MLQEM_TABLE_GRAD_SYNTH", "1") != "0"
+# MLQEM_TABLE_FWD=0: the forward of cheb_conv1 and sage_conv1 aggregates its projections (one pooled aggregation per branch) (A/B).
+# Default: where the backward above is the computed one (all four tables, MLQEM_TABLE_GRAD and MLQEM_TABLE_GRAD_SYNTH on), both layers
+# are projections of table rows -- y_c = x (W0 - W2)^T + (L^ x) W1^T + (L^ L^ x)(2 W2)^T + b, y_s = (M x) Wl^T + x Wr^T + b_l -- pooled inside
+# the fan-out launch (ops.linear_fanout_pool): nothing of either branch is aggregated or written per node but its gate bits.
+_TABLE_FWD = os.environ.get("MLQEM_TABLE_FWD", "1") != "0"
+# ... for batches of at least this many nodes.  A threshold of its own: the projection form is a reassociation of the forward, and small
+# batches (which gain nothing from it) are compared bit for bit across the backward's switches
+_TABLE_FWD_MIN_NODES = 1 << 16
 
 _PARTS_MAX_COLS = 64   # mlqem_linear_parts_f32 keeps the weight fragments of I <= 64 concatenated columns in registers
 
@@ -1213,6 +1221,37 @@ class _FamilyAGraph(Function):
         # the tables only the backward reads (L^ L^ x, M x: see backward); the forward is the same with and without them
         ctx.grad_tables = (tab_c2, tab_s) if (tab_c is not None and tab_c2 is not None and tab_s is not None) else None
         ctx.x_rows = x if ctx.grad_tables is not None else None
+        # With all four tables AND the computed backward (which reads of these two branches only gate bits, pool weights and pooled
+        # gradients) cheb_conv1 and sage_conv1 are projections of table rows too, pooled inside the fan-out's launch: see _TABLE_FWD
+        table_fwd = (_TABLE_FWD and n >= _TABLE_FWD_MIN_NODES and tab_g is not None and ctx.grad_tables is not None and _TABLE_GRAD
+                     and _TABLE_GRAD_SYNTH and _POOLED_GRAD and n >= _POOLED_GRAD_MIN_NODES and struct.out_ell is not None
+                     and max(g1w.shape[0], g2w.shape[0]) <= 12 and ops.pooled_grad_supported(g1w.shape[0]))
+        ctx.forked = not table_fwd
+        if table_fwd:
+            ctx.side = (main, main)                 # nothing runs beside the GCN branch, forward or backward: no fork, no join
+            xr = ops.rowmajor(x)
+            n_, o_ = xr.shape[0], g1w.shape[0]
+            tabs = [xr.base, tab_g.base, tab_c.base, tab_c2.base, tab_s.base]
+            wg, w0, w1, w2, wl, wr = [w.contiguous() for w in (g1w, c1w0, c1w1, c1w2, s1l, s1r)]
+            pre_g = ops.padded_empty(n_, o_, x.device)
+            spec = [dict(out=pre_g, terms=[dict(table=1, w=wg)], bias=g1b, act=True, drop_p=p1, seed=seed + 1),
+                    dict(terms=[dict(table=0, w=w0, w_minus=w2), dict(table=2, w=w1), dict(table=3, w=w2, scale=2.0)], bias=c1b,
+                         act=True, drop_p=p2, seed=seed + 3, weights=tc),
+                    dict(terms=[dict(table=4, w=wl), dict(table=0, w=wr)], bias=s1b, act=True, drop_p=p2, seed=seed + 4, weights=ts)]
+            if _GCN_CHAIN:
+                pre_g2 = ops.padded_empty(n_, g2w.shape[0], x.device)
+                spec[0]["chain"] = dict(out=pre_g2, w=g2w.contiguous(), rowscale=struct.gcn_dinv)
+            (mc, wc, bits_c), (ms, ws, bits_s) = ops.linear_fanout_pool(tabs, xr.rows, n_, spec, gptr, nb)
+            h, g1 = pre_g, _GCNSaved(ops.rowmajor(x), g1w, None, struct, p1, None)
+            pg = dict(graph_ptr=gptr, num_graphs=nb, weights=tg, mean=False, wmean=True, bits=True, store=False)
+            hg, g2 = _gcn_forward(h, g2w, g2b, struct, True, p1, seed + 2, defer_mask=True, x_gate_scale=k1, pre=pre_g2, pool=pg)
+            _, wg = ops.pooled_means(hg, pg)
+            ctx.head = ([(wg, g3w, 0), (mc, c2w0, 1), (wc, c2w1, 1), (ws, s2l, 2), (ms, s2r, 2)], [g3b, c2b, s2b])
+            out = ops.pooled_head(*ctx.head)
+            ctx.tail = (struct, k1, k2, hg, None, None)
+            ctx.layers = (g1, g2, None, None)
+            ctx.gate_bits = (pg.get("out_bits"), bits_c, bits_s)
+            return out
         if tab_g is not None or tab_c is not None:
             xr = ops.rowmajor(x)
             n_, o_ = xr.shape[0], g1w.shape[0]
@@ -1292,7 +1331,7 @@ class _FamilyAGraph(Function):
         g3bg, c2bg, s2bg = gb3[0:1], gb3[1:2], gb3[2:3]
         synth = (_POOLED_GRAD and n >= _POOLED_GRAD_MIN_NODES and ops.pooled_grad_supported(ggw.shape[1])
                  and struct.out_ell is not None)      # per branch: its gate bits exist
-        for st in side:
+        for st in (side if ctx.forked else ()):
             st.wait_stream(main)
 
         def pooled_grad(gm, gw, kind, gate, scale, bits):
@@ -1363,7 +1402,7 @@ class _FamilyAGraph(Function):
                 else:
                     r = _sage_backward(s1, t, False)
                     s1l, s1b, s1r = r.wl, r.bl, r.wr
-        for st in side:
+        for st in (side if ctx.forked else ()):
             main.wait_stream(st)
         if fuse and (bg or not table_grad):
             # ONE pass over x for the weight gradients of all three first layers: x^T [gh | g || g | g_b1 | g_c2 || g_p | g];
@@ -1401,8 +1440,9 @@ def family_a_graph(x, struct, p1, p2, seed, params):
     if isinstance(x, ops.RowsOf) and 16 < x.shape[1] <= 24 and params[0].shape[0] <= 16:      # what the fused first layer takes
         build = torch.is_grad_enabled() and any(p.requires_grad for p in params)
         # the tables of L^ L^ x and M x serve the backward alone, and only where it computes the pooled gradients (see backward)
-        grad = (build and _TABLE_GRAD and _TABLE_CHEB and _POOLED_GRAD and struct.num_nodes >= _POOLED_GRAD_MIN_NODES
+        # (a call that only predicts takes them where they exist: its forward is then the one the training steps ran, _TABLE_FWD)
+        grad = (_TABLE_GRAD and _TABLE_CHEB and _POOLED_GRAD and struct.num_nodes >= _POOLED_GRAD_MIN_NODES
                 and struct.out_ell is not None and ops.pooled_grad_supported(params[0].shape[0]))
         tables = (x.sibling("gcn", build) if _TABLE_GCN else None, x.sibling("cheb", build) if _TABLE_CHEB else None,
-                  x.sibling("cheb2", True) if grad else None, x.sibling("sage", True) if grad else None)
+                  x.sibling("cheb2", build) if grad else None, x.sibling("sage", build) if grad else None)
     return _FamilyAGraph.apply(x, struct, p1, p2, seed, tables, *params)

@@ -681,6 +681,110 @@ def linear_fanout_tables(tables, rows, n, blocks, *, drop_p=0.0, seed=0):
     return [b["out"] for b in blocks]
 
 
+def node_gates_only(bits) -> bool:
+    """Is ``bits`` a gate buffer of which only the per-node section was written (``linear_fanout_pool`` leaves such)?  It has the size
+    and layout of a pooled aggregation's buffer and serves ``PooledGrad``'s computed forms and ``pool_node_gates``; its tile ballots
+    were never written, so ``segment_pool_bwd(gate_bits=)`` refuses it."""
+    return bool(getattr(bits, "node_gates_only", False))
+
+
+def linear_fanout_pool(tables, rows, n, blocks, graph_ptr, num_graphs, *, max_groups=0):
+    """The table fan-out with two POOLED blocks (mlqem_linear_fanout_pool_f32): up to five padded tables that share the row map
+    ``rows``, and exactly three ``blocks``.  Every block is a dict with ``terms`` -- one to three dicts ``table``, ``w`` ([O, I]) and
+    optionally ``w_minus``, ``scale`` -- and optionally ``bias``, ``rowscale``, ``act`` (ReLU + dropout ``drop_p`` with the aggregation
+    epilogue's mask for ``seed``, both per block).  Block 0 is stored in its ``out`` and may carry a ``chain`` as in
+    ``linear_fanout_tables`` (same values, bit for bit).  Blocks 1 and 2 carry ``weights`` ([n] pool weights) and are not written
+    (unless they have an ``out``): -> [(mean, wmean, bits), (mean, wmean, bits)], the [B, O] pooled means over ``graph_ptr`` and a gate
+    buffer of which only the per-node section is written (``node_gates_only``).  ``max_groups``: a cap on the grid, for tests (the
+    results do not depend on it)."""
+    import ctypes as _ct
+
+    if not 1 <= len(tables) <= _lib.FANOUT_POOL_MAX_TABLES or len(blocks) != _lib.FANOUT_POOL_BLOCKS:
+        raise ValueError(f"linear_fanout_pool: 1..{_lib.FANOUT_POOL_MAX_TABLES} tables and exactly {_lib.FANOUT_POOL_BLOCKS} blocks")
+    d = _lib.FanoutPool()
+    i, o = tables[0].shape[1], blocks[0]["out"].shape[1]
+    dev = tables[0].device
+    d.n_tables, d.n_blocks, d.cols, d.out_cols, d.max_groups = len(tables), len(blocks), i, o, int(max_groups)
+    c4 = (i + 3) // 4 * 4
+    for j, t in enumerate(tables):
+        _mat(t, f"tables[{j}]")
+        ld = int(t.stride(0))
+        if t.shape[1] != i or ld < c4 or ld % 4 or t.data_ptr() % 16:
+            raise ValueError(f"tables[{j}]: needs [M, {i}] in the padded row layout, got {tuple(t.shape)} with stride {ld}")
+        if rows is None and t.shape[0] < n:
+            raise ValueError(f"tables[{j}]: {t.shape[0]} rows for {n} outputs")
+        d.table[j], d.ldt[j] = t.data_ptr(), ld
+    if rows is not None:
+        _vec(rows, "rows", n, torch.int32)
+    nb = int(num_graphs)
+    _vec(graph_ptr, "graph_ptr", nb + 1, torch.int32)
+    lib = _lib.load()
+    keep, pooled = [], []
+    for k, b in enumerate(blocks):
+        terms = b["terms"]
+        if not 1 <= len(terms) <= _lib.FANOUT_POOL_MAX_TERMS:
+            raise ValueError(f"blocks[{k}]: 1..{_lib.FANOUT_POOL_MAX_TERMS} terms")
+        d.n_terms[k] = len(terms)
+        for t, term in enumerate(terms):
+            for key in ("w", "w_minus"):
+                w = term.get(key)
+                if w is not None and (not w.is_cuda or w.dtype != torch.float32 or tuple(w.shape) != (o, i) or not w.is_contiguous()):
+                    raise ValueError(f"linear_fanout_pool: blocks[{k}].terms[{t}].{key} must be a contiguous fp32 cuda tensor of shape {(o, i)}")
+            if not 0 <= int(term["table"]) < len(tables):
+                raise ValueError(f"blocks[{k}].terms[{t}].table: no such table")
+            d.w[k][t], d.w_minus[k][t] = _p(term["w"]), _p(term.get("w_minus"))
+            d.w_scale[k][t], d.w_table[k][t] = float(term.get("scale", 1.0)), int(term["table"])
+        _vec(b.get("bias"), "bias", o)
+        _vec(b.get("rowscale"), "rowscale", n)
+        out = b.get("out")
+        if out is not None:
+            _mat(out, f"blocks[{k}].out")
+            ld = int(out.stride(0))
+            if tuple(out.shape) != (n, o) or ld < (o + 3) // 4 * 4 or ld % 4 or out.data_ptr() % 16:
+                raise ValueError(f"blocks[{k}].out: needs a padded [{n}, {o}] buffer (ops.padded_empty)")
+            d.y[k], d.ldy[k] = out.data_ptr(), ld
+        elif k == 0:
+            raise ValueError("linear_fanout_pool: blocks[0] is stored and needs an out buffer")
+        p = float(b.get("drop_p", 0.0))
+        if not 0.0 <= p < 1.0:
+            raise ValueError("linear_fanout_pool: drop_p must be in [0, 1)")
+        d.bias[k], d.rowscale[k], d.act[k] = _p(b.get("bias")), _p(b.get("rowscale")), 1 if b.get("act") else 0
+        d.drop_p[k], d.seed[k] = p, int(b.get("seed", 0)) & 0xFFFFFFFFFFFFFFFF
+        if k == 0:
+            continue
+        wts = b["weights"]
+        _vec(wts, "weights", n)
+        mean, wmean = padded_empty(nb, o, dev), padded_empty(nb, o, dev)
+        bits = torch.empty(lib.mlqem_csr_aggregate_pool_gate_bytes(n, o), dtype=torch.uint8, device=dev)
+        bits.node_gates_only = True
+        d.pool_weights[k], d.gate_bits[k] = wts.data_ptr(), bits.data_ptr()
+        d.out_mean[k], d.ld_mean[k] = mean.data_ptr(), _mat(mean, "mean")
+        d.out_wmean[k], d.ld_wmean[k] = wmean.data_ptr(), _mat(wmean, "wmean")
+        pooled.append((mean, wmean, bits))
+    d.graph_ptr, d.num_graphs = graph_ptr.data_ptr(), nb
+    ch, c = None, blocks[0].get("chain")
+    if any(b.get("chain") is not None for b in blocks[1:]):
+        raise ValueError("linear_fanout_pool: only block 0 may be chained")
+    if c is not None:
+        out2, w2 = c["out"], c["w"]
+        _mat(out2, "blocks[0].chain.out")
+        o2, ld2 = out2.shape[1], int(out2.stride(0))
+        if tuple(out2.shape) != (n, o2) or not 1 <= o2 <= 12 or ld2 < (o2 + 3) // 4 * 4 or ld2 % 4 or out2.data_ptr() % 16:
+            raise ValueError(f"blocks[0].chain.out: needs a padded [{n}, <= 12] buffer (ops.padded_empty)")
+        if not w2.is_cuda or w2.dtype != torch.float32 or tuple(w2.shape) != (o2, o) or not w2.is_contiguous():
+            raise ValueError(f"blocks[0].chain.w must be a contiguous fp32 cuda tensor of shape {(o2, o)}")
+        _vec(c.get("rowscale"), "chain.rowscale", n)
+        ch = _lib.FanoutChain()
+        ch.block, ch.out_cols, ch.y, ch.ldy, ch.w, ch.rowscale = 0, o2, out2.data_ptr(), ld2, w2.data_ptr(), _p(c.get("rowscale"))
+    need = lib.mlqem_linear_fanout_pool_workspace_bytes(n, nb, o)
+    ws = _wgrad_workspace(dev, need)
+    drops = any(b.get("act") and float(b.get("drop_p", 0.0)) > 0 for b in blocks)
+    code = lib.mlqem_linear_fanout_pool_f32(_ct.addressof(d), _ct.addressof(ch) if ch is not None else None, n, _p(rows),
+                                            _p(_seed_counter) if drops else None, _p(ws), need, _stream())
+    _lib.check(code, "mlqem_linear_fanout_pool_f32")
+    return pooled
+
+
 _wgrad_ws = {}   # (device, stream, bytes) -> partial-sum workspace: per stream, so concurrent streams never share one
 
 
@@ -1300,7 +1404,10 @@ def segment_pool_bwd(g_mean, g_wmean, graph_ptr, num_nodes, weights=None, gate=N
         raise ValueError("segment_pool_bwd: bad out shape")
     gp, gld = _gate(gate, num_nodes, c, False)
     if gate_bits is not None:      # the gate as sign bits (csr_aggregate(..., pool=) leaves them: tile records + per-wave ballots)
-        want = _lib.load().mlqem_csr_aggregate_pool_gate_bytes(num_nodes, c)
+        if node_gates_only(gate_bits):
+            raise ValueError("segment_pool_bwd: this gate buffer holds per-node gates only (linear_fanout_pool wrote no tile ballots): "
+                             "the pooled gradient of such a forward is computed (PooledGrad.aggregate, linear_wgrad_tables), not written")
+        want =_lib.load().mlqem_csr_aggregate_pool_gate_bytes(num_nodes, c)
         if gate is not None or gate_bits.dtype != torch.uint8 or not gate_bits.is_cuda or gate_bits.numel() != want \
                 or not gate_bits.is_contiguous():
             raise ValueError(f"segment_pool_bwd: gate_bits must be the contiguous uint8 cuda tensor of {want} bytes the pooled "

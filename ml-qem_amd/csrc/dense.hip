@@ -959,6 +959,264 @@ __global__ __launch_bounds__(kBlock) void linear_fanout_tables_kernel(const FanT
   }
 }
 
+// The table fan-out with POOLED blocks (mlqem_linear_fanout_pool_f32): five tables (x, A^ x, L^ x, L^ L^ x, M x), block 0 stored and
+// chained exactly as linear_fanout_tables_kernel<., true> does it (same staging, same MFMA step order, same epilogue: bit-identical
+// h1 and p2), blocks 1 and 2 -- cheb_conv1 and sage_conv1 as plain projections of table rows, up to three terms in one accumulator
+// chain -- reduced to what the model needs of them: the per-graph mean and weighted mean and the per-node gate bits.  Their values never
+// reach memory (unless a test asks for them).
+// Ownership is CONTIGUOUS: a wave takes kFanPoolRows consecutive rows (sixteen MFMA tiles) at a time, every lane keeps the running sums
+// of ITS row of those tiles for the graph the wave is in, and when the graph or the wave tile ends the sixteen row lanes are added by a
+// fixed xor tree and one partial per (wave tile, graph) goes to slot tile + graph (pool.hip's layout; pool_finish_tiles_kernel adds a
+// graph's slots in tile order).  No atomics, and the grid decides only WHO computes a tile, never what is added to what.  A 16-row
+// tile that holds a graph boundary walks its graphs one after the other with the rows of the others masked (graphs of one row work).
+// Resources (gfx950, -O3): see the launcher.
+constexpr int kFanPoolTables = MLQEM_FANOUT_POOL_MAX_TABLES, kFanPoolBlocks = MLQEM_FANOUT_POOL_BLOCKS;
+constexpr int kFanPoolSlots = 8, kFanPoolRows = 256, kFanPoolSub = kFanPoolRows / 16;
+
+struct FanPoolArgs {
+  const float* tab[kFanPoolTables]; int64_t ldt[kFanPoolTables]; int xc, yw, yc;
+  const float* tw[kFanPoolSlots]; const float* twm[kFanPoolSlots]; float tscale[kFanPoolSlots]; int ttab[kFanPoolSlots]; int nslots;
+  int tbeg[kFanPoolBlocks + 1];              // block k's terms are slots tbeg[k] .. tbeg[k + 1] - 1
+  float* yp[kFanPoolBlocks]; int64_t ldy[kFanPoolBlocks];      // block 0: required; pooled blocks: optional
+  const float* bk[kFanPoolBlocks]; const float* rsk[kFanPoolBlocks]; int actk[kFanPoolBlocks]; float dropk[kFanPoolBlocks];
+  uint64_t seedk[kFanPoolBlocks];
+  const float* pw[2]; float* ppart[2]; uint16_t* pgate[2];      // pooled block 1 + p: pool weights, partials, per-node gates
+  const int32_t* gptr; int B;
+  int64_t N; const int32_t* xrows; const uint64_t* seed_counter;
+  float* y2; int64_t ldy2; const float* w2c; const float* rs2; int y2c, y2w;      // the chain on block 0 (y2 == nullptr: none)
+};
+
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3, 3))) void linear_fanout_pool_kernel(const FanPoolArgs a) {
+  constexpr int NT = kFanPoolTables;
+  __shared__ float4 s_w[kFanPoolSlots][2][kWave];
+  __shared__ float s_b[kFanPoolBlocks][16];
+  __shared__ float4 s_w2[kWave];
+  const int tid = threadIdx.x;
+  const bool chain = a.y2 != nullptr;
+  if (tid < kWave) {
+    const int o = tid & 15, lq = tid >> 4;
+    float v[4];
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4) {
+      const int k = 4 * lq + s4;
+      v[s4] = (chain && o < a.y2c && k < a.yc) ? a.w2c[(int64_t)o * a.yc + k] : 0.f;
+    }
+    s_w2[tid] = make_float4(v[0], v[1], v[2], v[3]);
+  }
+  for (int idx = tid; idx < a.nslots * 2 * kWave; idx += kBlock) {
+    const int term = idx / (2 * kWave), g = (idx / kWave) % 2, l = idx % kWave;
+    const int o = l & 15, lq = l >> 4;
+    float v[4];
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4) {
+      const int k = g == 1 ? (s4 < 2 ? 16 + 2 * lq + s4 : a.xc) : 4 * lq + s4;
+      float w = 0.f;
+      if (o < a.yc && k < a.xc) {
+        w = a.tw[term][(int64_t)o * a.xc + k];
+        if (a.twm[term]) w -= a.twm[term][(int64_t)o * a.xc + k];
+        w *= a.tscale[term];
+      }
+      v[s4] = w;
+    }
+    s_w[term][g][l] = make_float4(v[0], v[1], v[2], v[3]);
+  }
+  for (int idx = tid; idx < kFanPoolBlocks * 16; idx += kBlock) {
+    const int blk = idx >> 4, o = idx & 15;
+    s_b[blk][o] = (a.bk[blk] && o < a.yc) ? a.bk[blk][o] : 0.f;
+  }
+  __syncthreads();
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * kBlock + tid) >> 6));
+  const int64_t n_waves = (gridDim.x * kBlock) >> 6;
+  const int lr = lane & 15, lq = lane >> 4;
+  const int live1 = min(2, max(0, a.xc - (16 + 2 * lq)));
+  const uint64_t ctr = a.seed_counter ? *a.seed_counter * 0xD1B54A32D192ED03ull : 0ull;
+  const bool store_lane = 4 * lq < a.yw;
+  const int64_t n_tiles = ceil_div(a.N, 16);
+  auto load_x = [&](int64_t t, int xmap, float4 (&v0)[NT], float2 (&v1)[NT]) {
+    const int64_t r = min(t * 16 + lr, a.N - 1);
+    const int64_t xr = a.xrows ? (int64_t)xmap : r;
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+      const float* __restrict__ p = a.tab[j] + xr * a.ldt[j];
+      v0[j] = *reinterpret_cast<const float4*>(p + 4 * lq);
+      v1[j] = live1 ? *reinterpret_cast<const float2*>(p + 16 + 2 * lq) : make_float2(0.f, 0.f);
+    }
+  };
+  auto map_at = [&](int64_t t) {
+    const int64_t r = min(t * 16 + lr, a.N - 1);
+    return (a.xrows && t < n_tiles) ? a.xrows[r] : 0;
+  };
+  // the wave's q-th 16-row tile: sixteen in a row, then the wave's next kFanPoolRows rows
+  auto tile_of = [&](int64_t q) { return ((int64_t)wave + (q / kFanPoolSub) * n_waves) * kFanPoolSub + (q % kFanPoolSub); };
+  float pm[2][4], pwm[2][4];                   // the running sums of the wave's current (tile, graph) segment, this lane's rows
+#pragma unroll
+  for (int p = 0; p < 2; ++p)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) pm[p][r] = pwm[p][r] = 0.f;
+  int g = 0; int64_t gend = 0; bool have = false;      // wave-uniform: the graph being summed, its end, whether the sums hold a row of it
+  auto flush = [&](int64_t wt) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      float t[8];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { t[r] = pm[p][r]; t[4 + r] = pwm[p][r]; pm[p][r] = pwm[p][r] = 0.f; }
+#pragma unroll
+      for (int v = 0; v < 8; ++v)
+#pragma unroll
+        for (int m = 1; m < 16; m <<= 1) t[v] += __shfl_xor(t[v], m);      // the sixteen row lanes of a column quarter: a fixed tree
+      if (lr == 0 && store_lane) {
+        float* dst = a.ppart[p] + ((wt + g) * 2) * a.yw + 4 * lq;
+        const float m4[4] = {t[0], t[1], t[2], t[3]}, w4[4] = {t[4], t[5], t[6], t[7]};
+        vstore<4>(dst, m4);
+        vstore<4>(dst + a.yw, w4);
+      }
+    }
+    have = false;
+  };
+  float4 av0[NT], an0[NT];
+  float2 av1[NT], an1[NT];
+  int64_t t = tile_of(0);
+  int xnext = map_at(tile_of(1));
+  load_x(t, map_at(t), av0, av1);
+  for (int64_t q = 0; t < n_tiles; ++q) {
+    const int64_t tn = tile_of(q + 1);
+    const int64_t row0 = t * 16, row = row0 + lr, rend = min(row0 + 16, a.N);
+    const int64_t wt = t / kFanPoolSub;
+    const bool row_ok = row < a.N;
+    // every load of the tile before its first store (see linear_fanout_lds_kernel): row scales, pool weights, then the prefetch
+    float rsv[kFanPoolBlocks], pwv[2], hv[2][4];
+#pragma unroll
+    for (int blk = 0; blk < kFanPoolBlocks; ++blk) rsv[blk] = (a.rsk[blk] && row_ok) ? a.rsk[blk][row] : 1.f;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) pwv[p] = (a.pw[p] && row_ok) ? a.pw[p][row] : 0.f;
+    const float rs2 = (chain && a.rs2 && row_ok) ? a.rs2[row] : 1.f;
+    const int xmap2 = map_at(tile_of(q + 2));
+    load_x(tn, xnext, an0, an1);               // a tile beyond the end re-reads a valid row and is never used
+    xnext = xmap2;
+    if (q % kFanPoolSub == 0) {                // a new wave tile: the graph of its first row (one search per kFanPoolRows rows)
+      g = graph_at(a.gptr, a.B, row0);
+      gend = a.gptr[g + 1];
+    }
+#pragma unroll
+    for (int j = 0; j < NT; ++j)
+      if (live1 < 2) av1[j].y = 0.f;           // padding may hold anything (NaN included): it must not reach the MFMA
+    auto steps = [&](int slot, const float4& x0, const float2& x1, f32x4 acc) {
+      const float4 w0 = s_w[slot][0][lane], w1 = s_w[slot][1][lane];
+      acc = mfma16x16x4(w0.x, x0.x, acc);
+      acc = mfma16x16x4(w0.y, x0.y, acc);
+      acc = mfma16x16x4(w0.z, x0.z, acc);
+      acc = mfma16x16x4(w0.w, x0.w, acc);
+      acc = mfma16x16x4(w1.x, x1.x, acc);
+      acc = mfma16x16x4(w1.y, x1.y, acc);
+      return acc;
+    };
+    // a term's table is workgroup-uniform: a branch per table with the operand registers named outright (see linear_fanout_tables_kernel)
+    auto term = [&](int slot, f32x4 acc) {
+      const int tb = a.ttab[slot];
+      if (tb == 4) return steps(slot, av0[4], av1[4], acc);
+      if (tb == 3) return steps(slot, av0[3], av1[3], acc);
+      if (tb == 2) return steps(slot, av0[2], av1[2], acc);
+      if (tb == 1) return steps(slot, av0[1], av1[1], acc);
+      return steps(slot, av0[0], av1[0], acc);
+    };
+#pragma unroll
+    for (int blk = 0; blk < kFanPoolBlocks; ++blk) {
+      f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+      const int s0 = a.tbeg[blk], cnt = a.tbeg[blk + 1] - s0;
+#pragma unroll
+      for (int k = 0; k < MLQEM_FANOUT_POOL_MAX_TERMS; ++k)
+        if (k < cnt) acc = term(s0 + k, acc);
+      float v[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        v[r] = acc[r] + s_b[blk][4 * lq + r];
+        v[r] *= rsv[blk];                      // 1.0f where the block has no row scale: exact
+      }
+      if (a.actk[blk]) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
+        const float drop_p = a.dropk[blk];
+        if (drop_p > 0.f) {
+          const float keep_scale = 1.f / (1.f - drop_p);
+          bool keep[4];
+          dropout_keep<4>(a.seedk[blk] + ctr, (uint64_t)(row * a.yc + 4 * lq), drop_p, keep);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[r] = keep[r] ? v[r] * keep_scale : 0.f;
+        }
+      }
+      if (a.yp[blk] && row_ok && store_lane) vstore_nt<4>(a.yp[blk] + row * a.ldy[blk] + 4 * lq, v);
+      if (blk == 0) {
+        if (chain) {                           // workgroup-uniform: the chain's MFMAs need the whole wave
+          // nothing but zeros may reach the MFMA from the columns >= yc (see linear_fanout_tables_kernel)
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            if (4 * lq + r >= a.yc) v[r] = 0.f;
+          const float4 w4 = s_w2[lane];
+          f32x4 acc2 = f32x4{0.f, 0.f, 0.f, 0.f};
+          acc2 = mfma16x16x4(w4.x, v[0], acc2);
+          acc2 = mfma16x16x4(w4.y, v[1], acc2);
+          acc2 = mfma16x16x4(w4.z, v[2], acc2);
+          acc2 = mfma16x16x4(w4.w, v[3], acc2);
+          if (row_ok && 4 * lq < a.y2w) {
+            float v2[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v2[r] = acc2[r] * rs2;
+            vstore_nt<4>(a.y2 + row * a.ldy2 + 4 * lq, v2);
+          }
+        }
+      } else {
+        const int p = blk - 1;
+        // the node's sixteen gate bits: this lane's four, the four column quarters of a row OR-ed together
+        unsigned bits = 0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bits |= ((4 * lq + r < a.yc && v[r] > 0.f) ? 1u : 0u) << (4 * lq + r);
+        bits |= (unsigned)__shfl_xor((int)bits, 16);
+        bits |= (unsigned)__shfl_xor((int)bits, 32);
+        if (lq == 0 && row_ok) a.pgate[p][row] = (uint16_t)bits;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (4 * lq + r >= a.yc || !row_ok) v[r] = 0.f;      // pad columns and rows beyond the end add nothing
+#pragma unroll
+        for (int r = 0; r < 4; ++r) hv[p][r] = v[r];          // summed below, both pooled blocks in one walk over the tile's graphs
+      }
+    }
+    // the pooled sums: rows [lo, min(gend, rend)) of the tile belong to the wave's graph g
+    if (rend <= gend) {                        // the whole tile inside one graph (wave-uniform)
+#pragma unroll
+      for (int p = 0; p < 2; ++p)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { pm[p][r] += hv[p][r]; pwm[p][r] = fmaf(pwv[p], hv[p][r], pwm[p][r]); }
+      have = true;
+    } else {
+      int64_t lo = row0;
+      while (true) {
+        const bool mine = row >= lo && row < gend;
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float x = mine ? hv[p][r] : 0.f;
+            pm[p][r] += x;
+            pwm[p][r] = fmaf(pwv[p], x, pwm[p][r]);
+          }
+        if (min(gend, rend) > lo) have = true;
+        if (gend >= rend) break;
+        if (have) flush(wt);                   // graph g ends inside this tile
+        lo = max(lo, gend);
+        ++g;
+        while (g < a.B && (int64_t)a.gptr[g + 1] <= lo) ++g;      // empty graphs
+        if (g >= a.B) { g = a.B - 1; gend = rend; break; }       // rows beyond graph_ptr[B] (the host checked: none) belong to no graph
+        gend = a.gptr[g + 1];
+      }
+    }
+    if (have && ((q + 1) % kFanPoolSub == 0 || tn >= n_tiles)) flush(wt);      // the wave tile ends
+#pragma unroll
+    for (int j = 0; j < NT; ++j) { av0[j] = an0[j]; av1[j] = an1[j]; }
+    t = tn;
+  }
+}
+
 // Generic fallback (any I; used for I > 128): thread per (row, output); a block stages one chunk of `oc` outputs' weights
 // in LDS (blockIdx.y selects the chunk).
 template <bool TRANSPOSED>
@@ -2133,6 +2391,95 @@ extern "C" int mlqem_linear_fanout_tables_chain_f32(const mlqem_fanout_tables* d
                                                     const int32_t* x_rows, float drop_p, uint64_t seed, const uint64_t* seed_counter,
                                                     mlqem_stream_t stream) {
   return fanout_tables(d, chain, N, x_rows, drop_p, seed, seed_counter, stream);
+}
+
+namespace mlqem {
+void launch_pool_finish_tiles(const float* partial, const int32_t* graph_ptr, int B, int C, int c4, int rows, float* out_mean,
+                              int64_t ld_mean, float* out_wmean, int64_t ld_wmean, hipStream_t s);      // pool.hip
+int aggregate_pool_rows_per_tile(int C);      // csr_aggregate.hip: the tiling of the gate buffer a pooled aggregation leaves
+int aggregate_pool_mask_words();
+}
+
+extern "C" size_t mlqem_linear_fanout_pool_workspace_bytes(int64_t N, int64_t B, int out_cols) {
+  if (N < 0 || B < 0 || out_cols <= 0) return 0;
+  const int64_t tiles = ceil_div(std::max<int64_t>(N, 1), kFanPoolRows);
+  return (size_t)2 * (size_t)(tiles + B) * 2 * ((out_cols + 3) / 4 * 4) * sizeof(float);       // the two pooled blocks' partials
+}
+
+// linear_fanout_pool_kernel on gfx950 (-O3, kernel-resource-usage): 161 VGPRs, no accumulator registers, no scratch, 17.6 KB LDS,
+// three waves per SIMD (pinned: amdgpu_waves_per_eu(3, 3)); 128 scalar registers of the argument block live in spare VGPR lanes.
+extern "C" int mlqem_linear_fanout_pool_f32(const mlqem_fanout_pool* d, const mlqem_fanout_chain* chain, int64_t N, const int32_t* x_rows,
+                                            const uint64_t* seed_counter, void* workspace, size_t workspace_bytes,
+                                            mlqem_stream_t stream) {
+  begin_launches();
+  if (!d || N < 0 || N > 0x7fffffffLL || d->num_graphs < 0 || d->num_graphs > 0x7fffffffLL) return MLQEM_ERR_BAD_ARG;
+  if (d->n_tables < 1 || d->n_tables > kFanPoolTables || d->n_blocks < 1 || d->cols < 1 || d->out_cols < 1) return MLQEM_ERR_BAD_ARG;
+  if (d->n_blocks != kFanPoolBlocks) return MLQEM_ERR_UNSUPPORTED;          // one stored block, two pooled ones
+  if (d->cols <= 16 || d->cols > 24 || d->out_cols > 16) return MLQEM_ERR_UNSUPPORTED;
+  const int c4i = (d->cols + 3) / 4 * 4, c4o = (d->out_cols + 3) / 4 * 4;
+  const int64_t B = d->num_graphs;
+  FanPoolArgs a{};
+  for (int j = 0; j < kFanPoolTables; ++j) {
+    const int jj = j < d->n_tables ? j : 0;       // a table the descriptor does not have: the first one again (no term names it)
+    if (!d->table[jj] || d->ldt[jj] < c4i || d->ldt[jj] % 4 || !aligned_to(d->table[jj], 16)) return MLQEM_ERR_BAD_ARG;
+    a.tab[j] = static_cast<const float*>(d->table[jj]); a.ldt[j] = d->ldt[jj];
+  }
+  int nslots = 0;
+  for (int k = 0; k < kFanPoolBlocks; ++k) {
+    if (d->n_terms[k] < 1 || d->n_terms[k] > MLQEM_FANOUT_POOL_MAX_TERMS) return MLQEM_ERR_BAD_ARG;
+    if (d->drop_p[k] < 0.f || d->drop_p[k] >= 1.f) return MLQEM_ERR_BAD_ARG;
+    a.tbeg[k] = nslots;
+    for (int t = 0; t < d->n_terms[k]; ++t) {
+      if (!d->w[k][t] || d->w_table[k][t] < 0 || d->w_table[k][t] >= d->n_tables) return MLQEM_ERR_BAD_ARG;
+      if (nslots >= kFanPoolSlots) return MLQEM_ERR_UNSUPPORTED;
+      a.tw[nslots] = d->w[k][t]; a.twm[nslots] = d->w_minus[k][t]; a.tscale[nslots] = d->w_scale[k][t]; a.ttab[nslots] = d->w_table[k][t];
+      ++nslots;
+    }
+    if (d->y[k] && (d->ldy[k] < c4o || d->ldy[k] % 4 || !aligned_to(d->y[k], 16))) return MLQEM_ERR_BAD_ARG;
+    a.yp[k] = static_cast<float*>(d->y[k]); a.ldy[k] = d->ldy[k];
+    a.bk[k] = d->bias[k]; a.rsk[k] = d->rowscale[k]; a.actk[k] = d->act[k] ? 1 : 0;
+    a.dropk[k] = d->act[k] ? d->drop_p[k] : 0.f; a.seedk[k] = d->seed[k];
+    if (k == 0) continue;
+    if (!d->gate_bits[k] || (!d->out_mean[k] && !d->out_wmean[k]) || (d->out_wmean[k] && !d->pool_weights[k])) return MLQEM_ERR_BAD_ARG;
+    if ((d->out_mean[k] && d->ld_mean[k] < d->out_cols) || (d->out_wmean[k] && d->ld_wmean[k] < d->out_cols)) return MLQEM_ERR_BAD_ARG;
+  }
+  a.tbeg[kFanPoolBlocks] = nslots;
+  if (!d->y[0]) return MLQEM_ERR_BAD_ARG;
+  if (chain) {
+    if (chain->block != 0 || chain->out_cols < 1 || !chain->y || !chain->w) return MLQEM_ERR_BAD_ARG;
+    if (chain->out_cols > 12 || d->out_cols > 12) return MLQEM_ERR_UNSUPPORTED;
+    const int c4c = (chain->out_cols + 3) / 4 * 4;
+    if (chain->ldy < c4c || chain->ldy % 4 || !aligned_to(chain->y, 16)) return MLQEM_ERR_BAD_ARG;
+    a.y2 = static_cast<float*>(chain->y); a.ldy2 = chain->ldy; a.w2c = chain->w; a.rs2 = chain->rowscale;
+    a.y2c = chain->out_cols; a.y2w = c4c;
+  }
+  if (B == 0 || N == 0) return N == 0 ? MLQEM_OK : MLQEM_ERR_BAD_ARG;
+  if (!d->graph_ptr) return MLQEM_ERR_BAD_ARG;
+  if (!workspace || workspace_bytes < mlqem_linear_fanout_pool_workspace_bytes(N, B, d->out_cols)) return MLQEM_ERR_WORKSPACE;
+  const int64_t wtiles = ceil_div(N, kFanPoolRows);
+  float* partial = static_cast<float*>(workspace);
+  const size_t per_block = (size_t)(wtiles + B) * 2 * c4o;
+  // the per-node section of the gate buffer (pool.hip mlqem_csr_aggregate_pool_gate_bytes: tile records and ballots come first)
+  const size_t gate_off = (size_t)ceil_div(N, mlqem::aggregate_pool_rows_per_tile(d->out_cols)) *
+                          (sizeof(int4) + (size_t)mlqem::aggregate_pool_mask_words() * sizeof(unsigned long long));
+  for (int p = 0; p < 2; ++p) {
+    a.pw[p] = d->pool_weights[1 + p];
+    a.ppart[p] = partial + p * per_block;
+    a.pgate[p] = reinterpret_cast<uint16_t*>(d->gate_bits[1 + p] + gate_off);
+  }
+  a.nslots = nslots; a.xc = d->cols; a.yw = c4o; a.yc = d->out_cols;
+  a.gptr = d->graph_ptr; a.B = (int)B;
+  a.N = N; a.xrows = x_rows;
+  a.seed_counter = (a.dropk[0] > 0.f || a.dropk[1] > 0.f || a.dropk[2] > 0.f) ? seed_counter : nullptr;
+  hipStream_t s = as_stream(stream);
+  const int res = resident_of(reinterpret_cast<const void*>(linear_fanout_pool_kernel));
+  int64_t groups = std::max<int64_t>(1, std::min<int64_t>(ceil_div(wtiles, 4), res));      // one resident round
+  if (d->max_groups > 0) groups = std::min<int64_t>(groups, d->max_groups);
+  hipLaunchKernelGGL(linear_fanout_pool_kernel, dim3((unsigned)groups), dim3(kBlock), 0, s, a);
+  for (int p = 0; p < 2; ++p)
+    mlqem::launch_pool_finish_tiles(a.ppart[p], d->graph_ptr, (int)B, d->out_cols, c4o, kFanPoolRows, d->out_mean[1 + p], d->ld_mean[1 + p],
+                                    d->out_wmean[1 + p], d->ld_wmean[1 + p], s);
+  return launch_status();
 }
 
 template <int OBT, bool TRANSPOSED>

@@ -503,6 +503,15 @@ extern "C" int mlqem_csr_aggregate_pool_f32(const float* x, int64_t ldx, const i
   return launch_status();
 }
 
+namespace mlqem {
+// The tile finish for another launcher's partials in this layout (dense.hip: the pooled fan-out's 256-row wave tiles); 2 c4 <= 32.
+void launch_pool_finish_tiles(const float* partial, const int32_t* graph_ptr, int B, int C, int c4, int rows, float* out_mean,
+                              int64_t ld_mean, float* out_wmean, int64_t ld_wmean, hipStream_t s) {
+  hipLaunchKernelGGL(pool_finish_tiles_kernel, dim3((unsigned)B), dim3(kBlock), 0, s, partial, graph_ptr, C, c4, rows, out_mean, ld_mean,
+                     out_wmean, ld_wmean);
+}
+}  // namespace mlqem
+
 extern "C" int mlqem_segment_pool_bwd_f32(const float* g_mean, int64_t ld_gmean, const float* g_wmean, int64_t ld_gwmean,
                                           const float* weights, const int32_t* graph_ptr, int64_t N, int64_t B, int C,
                                           const float* gate, int64_t ldgate, float gate_scale, const uint8_t* gate_bits, float* gx,

@@ -2051,6 +2051,32 @@ int mlqem_clifford_sample_f64(int64_t n_circuits, const int32_t* n_qubits, const
  * values / std_error [B] (0 at one trajectory), norm, discarded and error_bound [B] (means) and bond int32 [B] (the maximum).
  * Bad sizes, a null or misaligned buffer: MLQEM_ERR_BAD_ARG; a count over 2^31 - 1: MLQEM_ERR_UNSUPPORTED; a workspace that is too
  * small: MLQEM_ERR_WORKSPACE; all before anything is launched.  No host read: capturable.
+ *
+ * mlqem_mps_run_folded_f64 (zero-noise extrapolation on this path; an additive symbol, the ABI version is unchanged).  The B
+ * circuits are lowered ONCE -- n_qubits, op_ptr, ops and params are those of mlqem_mps_run_f64 and are not replicated per factor --
+ * and every (circuit, noise factor) pair gets a schedule in the format of mlqem_sim_run_folded_f64: run r = f * B + c is circuit c
+ * at noise factor f, 0 <= f < n_factors = F; sched_ptr int64 [F * B + 1]; run r owns sched[sched_ptr[r] .. sched_ptr[r + 1]), int32
+ * entries (k << 1) | dagger with k a record index RELATIVE to op_ptr[c].  blackwater.sim.zne builds them (build_mps_schedules).
+ *   Units.  Unit u < run_count * traj_count is (run run_first + u / traj_count, trajectory traj_first + u % traj_count), one
+ *     workgroup each; its slice of `workspace` has the layout of mlqem_mps_run_f64's, so mlqem_mps_terms_f64 and
+ *     mlqem_mps_finish_f64 read it unchanged when they are called with the F * B runs as a batch of F * B circuits (the per-circuit
+ *     arrays n_qubits, term_circ, term_off, site_ptr, term_ptr and coeff tiled F times on the host; letters and readout shared
+ *     through the offsets).
+ *   Daggers.  dagger = 1 on a U1 / U2 entry applies the conjugate transpose of the record's matrix, formed while the record is
+ *     read by swapping indices and flipping the sign of the imaginary parts (a multiplication by -1.0: no rounding); the record's
+ *     orientation is unchanged.  On DEPOL1 / DEPOL2 the bit is ignored: a noise record is never inverted.  A coherent-error U2 must
+ *     never be scheduled with the bit set; the host guarantees that, the kernel does not check it.
+ *   Draws.  The noise index of the draw contract is the ORDINAL of the noise entry as this run executes it (0, 1, 2, ...: an entry
+ *     that is scheduled three times draws three times), and the key is run_keys[r], int64 [F * B].  With these two rules a run
+ *     equals, bit for bit, mlqem_mps_run_f64 on the program obtained by writing its schedule out (daggered matrices
+ *     conjugate-transposed on the host), under the same key.
+ *   traj_stats is [trajectories][F * B][MLQEM_MPS_STATS], a row per run.
+ *   Clamping.  Schedule offsets are clamped to n_sched, k to the circuit's records (a circuit without records skips its
+ *     entries), run numbers to F * B; an empty schedule leaves |0..0>; a malformed schedule computes garbage inside the unit's own
+ *     slice and faults nothing.
+ * Bad sizes (n_factors < 1, n_sched < 0, a run or trajectory range outside F * B runs and `trajectories`), a null or misaligned
+ * buffer: MLQEM_ERR_BAD_ARG; F * B, n_params, n_sched or run_count * traj_count over 2^31 - 1: MLQEM_ERR_UNSUPPORTED; a workspace
+ * that is too small: MLQEM_ERR_WORKSPACE; all before anything is launched.  No host read: capturable.
  * ---------------------------------------------------------------------------------------------------- */
 #define MLQEM_MPS_MAX_BOND 32
 #define MLQEM_MPS_MAX_QUBITS 512
@@ -2067,6 +2093,12 @@ int mlqem_mps_run_f64(int64_t n_circuits, const int32_t* n_qubits, const int64_t
                       const double* params, int64_t n_params, const int64_t* run_keys, int64_t circ_first, int64_t circ_count,
                       int64_t traj_first, int64_t traj_count, int64_t trajectories, uint64_t seed, int64_t max_bond, double cutoff,
                       int64_t max_qubits, void* workspace, size_t workspace_bytes, double* traj_stats, mlqem_stream_t stream);
+int mlqem_mps_run_folded_f64(int64_t n_circuits, int64_t n_factors, const int32_t* n_qubits, const int64_t* op_ptr,
+                             const mlqem_sim_op* ops, int64_t n_ops, const double* params, int64_t n_params, const int64_t* sched_ptr,
+                             const int32_t* sched, int64_t n_sched, const int64_t* run_keys, int64_t run_first, int64_t run_count,
+                             int64_t traj_first, int64_t traj_count, int64_t trajectories, uint64_t seed, int64_t max_bond,
+                             double cutoff, int64_t max_qubits, void* workspace, size_t workspace_bytes, double* traj_stats,
+                             mlqem_stream_t stream);
 int mlqem_mps_terms_f64(int64_t n_circuits, const int32_t* n_qubits, int64_t circ_first, int64_t circ_count, int64_t traj_first,
                         int64_t traj_count, int64_t trajectories, int64_t max_bond, int64_t max_qubits, const void* workspace,
                         size_t workspace_bytes, int64_t term_first, int64_t term_count, int64_t n_terms, const int32_t* term_circ,

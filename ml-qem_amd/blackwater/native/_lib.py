@@ -291,6 +291,7 @@ SIGNATURES = {
                                        _L, _U, ctypes.c_int32, _P, _P, _L, _P, _P, _L, _P, _L, _P, _P, _P, _P, _P]),
     "mlqem_mps_workspace_bytes": (_S, [_L, _L, _L]),
     "mlqem_mps_run_f64": (_I, [_L, _P, _P, _P, _L, _P, _L, _P, _L, _L, _L, _L, _L, _U, _L, _D, _L, _P, _S, _P, _P]),
+    "mlqem_mps_run_folded_f64": (_I, [_L, _L, _P, _P, _P, _L, _P, _L, _P, _P, _L, _P, _L, _L, _L, _L, _L, _U, _L, _D, _L, _P, _S, _P, _P]),
     "mlqem_mps_terms_f64": (_I, [_L, _P, _L, _L, _L, _L, _L, _L, _L, _P, _S, _L, _L, _L, _P, _P, _P, _L, _P, _P, _L, _P, _P, _P]),
     "mlqem_mps_finish_f64": (_I, [_L, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mlqem_mps_sample_workspace_bytes": (_S, [_L, _L, _L]),

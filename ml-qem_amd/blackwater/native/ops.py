@@ -3141,6 +3141,79 @@ def sim_run_mps(n_qubits, op_ptr, ops, params, run_keys, term_circ, term_off, le
     return traj_term_values, traj_norm, traj_stats
 
 
+def sim_run_mps_folded(n_qubits, op_ptr, ops, params, sched_ptr, sched, n_factors, run_keys, run_qubits, term_circ, term_off, letters,
+                       site_ptr, readout, runs, terms, trajectories_range, trajectories, seed, max_bond, cutoff, max_qubits, workspace,
+                       traj_term_values, traj_norm, traj_stats):
+    """Runs the (run, trajectory) units of one chunk of the F * B folded runs of a batch lowered ONCE by ``blackwater.sim.compile_mps``
+    and contracts their Pauli terms (mlqem_mps_run_folded_f64, then mlqem_mps_terms_f64 on the runs as a batch of F * B circuits):
+    fills the chunk's part of ``traj_term_values`` float64 [T, F * n_terms], ``traj_norm`` [T, F * B] and ``traj_stats``
+    [T, F * B, MPS_STATS] and returns them (``None``: allocated here, zero outside the chunk).
+
+    ``n_qubits`` int32 [B], ``op_ptr`` int64 [B + 1], ``ops`` int32 [n_ops, 4], ``params`` float64 [>= 32]: the B circuits, not
+    replicated.  ``sched_ptr`` int64 [F * B + 1] and ``sched`` int32 [n_sched]: one schedule per run ``r = f * B + c``, entries
+    ``(k << 1) | dagger`` (``blackwater.sim.zne.build_mps_schedules`` makes them).  ``run_keys`` int64 [F * B].  The terms side is
+    per RUN, tiled on the host: ``run_qubits`` int32 [F * B], ``term_circ`` int32 [F * n_terms] (run numbers), ``term_off`` int64
+    [F * n_terms], ``site_ptr`` int64 [F * B + 1]; ``letters`` and ``readout`` are the batch's own, shared through the offsets.
+    ``runs`` / ``terms`` / ``trajectories_range``: ``(first, count)`` of the chunk (``terms`` must be the tiled terms of ``runs``).
+    Shapes, dtypes and devices are checked here, the contents are the builders' to guarantee (the kernels clamp every index).
+    Nothing here waits for the device or reads a tensor, and with the three outputs given nothing is allocated: capturable."""
+    for t, name, dtype, cols in ((ops, "ops", torch.int32, 4), (readout, "readout", torch.float64, 2)):
+        if not t.is_cuda:
+            raise _lib.NativeLibraryError(f"{name} must live on the GPU (got {t.device}); there is no CPU path")
+        if t.dtype != dtype or t.dim() != 2 or t.shape[-1] != cols or not t.is_contiguous():
+            raise ValueError(f"mps: want contiguous {dtype} {name} [., {cols}], got {tuple(t.shape)} {t.dtype}")
+    b, n_ops, f = int(n_qubits.shape[0]), int(ops.shape[0]), int(n_factors)
+    if f < 1:
+        raise ValueError(f"mps: n_factors = {f}, want at least 1")
+    n_runs, n_terms = f * b, int(term_circ.shape[0])
+    n_traj, seed = _sim_trajectories(trajectories), _sim_seed(seed)
+    (r0, rn), (t0, tn), (j0, jn) = ((int(v) for v in pair) for pair in (runs, terms, trajectories_range))
+    if not (0 <= r0 and 1 <= rn and r0 + rn <= n_runs and 0 <= t0 and 0 <= tn and t0 + tn <= n_terms and 0 <= j0 and 1 <= jn and j0 + jn <= n_traj):
+        raise ValueError(f"mps: the chunk (runs {runs}, terms {terms}, trajectories {trajectories_range}) does not lie inside "
+                         f"{n_runs} runs, {n_terms} terms and {n_traj} trajectories")
+    if rn * jn > 2 ** 31 - 1 or max(tn, 1) * jn > 2 ** 31 - 1:
+        raise ValueError(f"mps: {rn} runs (or {tn} terms) x {jn} trajectories exceed the 2^31 - 1 units one call can take; split the chunk")
+    _vec(n_qubits, "n_qubits", b, torch.int32)
+    _vec(op_ptr, "op_ptr", b + 1, torch.int64)
+    _vec(params, "params", SIM_PARAM_PAD, torch.float64)
+    _vec(sched_ptr, "sched_ptr", 1, torch.int64)
+    _vec(sched, "sched", 0, torch.int32)
+    _vec(run_keys, "run_keys", 0, torch.int64)
+    if sched_ptr.shape[0] != n_runs + 1:
+        raise ValueError(f"mps: sched_ptr has {int(sched_ptr.shape[0])} entries, want {n_runs + 1} (one schedule per run f * B + c of "
+                         f"{f} factors x {b} circuits, and the end)")
+    if run_keys.shape[0] != n_runs:
+        raise ValueError(f"mps: run_keys has {int(run_keys.shape[0])} entries, want {n_runs} (one key per run f * B + c of {f} factors x "
+                         f"{b} circuits)")
+    _vec(run_qubits, "run_qubits", n_runs, torch.int32)
+    _vec(term_circ, "term_circ", n_terms, torch.int32)
+    _vec(term_off, "term_off", n_terms, torch.int64)
+    _vec(letters, "letters", 0, torch.uint8)
+    _vec(site_ptr, "site_ptr", n_runs + 1, torch.int64)
+    _vec(workspace, "workspace", mps_workspace_bytes(max_qubits, max_bond, rn * jn), torch.uint8)
+    if op_ptr.shape[0] != b + 1 or run_qubits.shape[0] != n_runs or site_ptr.shape[0] != n_runs + 1 or term_off.shape[0] != n_terms:
+        raise ValueError(f"mps: want op_ptr [{b + 1}], run_qubits [{n_runs}], site_ptr [{n_runs + 1}] and term_off [{n_terms}], got "
+                         f"{tuple(op_ptr.shape)}, {tuple(run_qubits.shape)}, {tuple(site_ptr.shape)} and {tuple(term_off.shape)}")
+    dev = ops.device
+    traj_term_values = _sim_out(traj_term_values, "traj_term_values", (n_traj, n_terms), dev)
+    traj_norm = _sim_out(traj_norm, "traj_norm", (n_traj, n_runs), dev)
+    traj_stats = _sim_out(traj_stats, "traj_stats", (n_traj, n_runs, MPS_STATS), dev)
+    if any(t.device != dev for t in (n_qubits, op_ptr, params, sched_ptr, sched, run_keys, run_qubits, term_circ, term_off, letters, site_ptr,
+                                     readout, workspace)):
+        raise ValueError(f"mps: ops is on {dev}, another buffer is not")
+    lib, ws_bytes, n_sched = _lib.load(), int(workspace.shape[0]), int(sched.shape[0])
+    code = lib.mlqem_mps_run_folded_f64(b, f, _p(n_qubits), _p(op_ptr), _p(ops) if n_ops else None, n_ops, _p(params), int(params.shape[0]),
+                                        _p(sched_ptr), _p(sched) if n_sched else None, n_sched, _p(run_keys), r0, rn, j0, jn, n_traj, seed,
+                                        int(max_bond), float(cutoff), int(max_qubits), _p(workspace), ws_bytes, _p(traj_stats), _stream())
+    _lib.check(code, "mlqem_mps_run_folded_f64")
+    code = lib.mlqem_mps_terms_f64(n_runs, _p(run_qubits), r0, rn, j0, jn, n_traj, int(max_bond), int(max_qubits), _p(workspace), ws_bytes,
+                                   t0, tn, n_terms, _p(term_circ) if n_terms else None, _p(term_off) if n_terms else None,
+                                   _p(letters) if n_terms else None, int(letters.shape[0]), _p(site_ptr), _p(readout), int(readout.shape[0]),
+                                   _p(traj_term_values) if n_terms else None, _p(traj_norm), _stream())
+    _lib.check(code, "mlqem_mps_terms_f64")
+    return traj_term_values, traj_norm, traj_stats
+
+
 def sim_mps_finish(term_ptr, coeff, traj_term_values, traj_norm, traj_stats, *, out=None):
     """Means and standard errors over the trajectories of an MPS run (mlqem_mps_finish_f64): a dict of ``term_values`` /
     ``term_std_error`` float64 [n_terms], ``values`` / ``std_error`` / ``norm`` / ``discarded`` / ``error_bound`` float64 [B] and

@@ -32,8 +32,8 @@ from .mps import (MAX_BOND, MAX_GROUPS_MPS, MAX_QUBITS_MPS, MPS_BUFFER_BYTES, Mp
                   sample_mps_expectation_values)
 from .zne import (CubicExtrapolator, CxAmplifier, ExponentialExtrapolator, GlobalFoldingAmplifier, LinearExtrapolator, LocalFoldingAmplifier,
                   PolynomialExtrapolator, QuadraticExtrapolator, QuarticExtrapolator, RichardsonExtrapolator, Schedules,
-                  TwoQubitAmplifier, ZNEStrategy, build_clifford_schedules, build_schedules, fold_circuit, zne_expectation_values,
-                  zne_run)
+                  TwoQubitAmplifier, ZNEStrategy, build_clifford_schedules, build_mps_schedules, build_schedules, fold_circuit,
+                  run_mps_folded, zne_expectation_values, zne_run)
 
 __all__ = ["MAX_AMPS", "MAX_QUBITS_DENSITY", "MAX_QUBITS_VECTOR", "SUPPORTED_GATES", "WAVE_AMPS", "NoiseModel", "SimBatch",
            "compile_programs", "measured_z", "DeviceEstimator", "SimulatedJob", "expectation_values", "run_batch",
@@ -48,5 +48,5 @@ __all__ = ["MAX_AMPS", "MAX_QUBITS_DENSITY", "MAX_QUBITS_VECTOR", "SUPPORTED_GAT
            "sample_clifford_expectation_values",
            "MAX_BOND", "MAX_QUBITS_MPS", "MPS_BUFFER_BYTES", "MpsBatch", "MpsResult", "compile_mps", "is_line_circuit",
            "mps_expectation_values", "run_mps", "MAX_GROUPS_MPS", "MpsShotsBatch", "MpsShotsResult", "compile_mps_shots", "mps_counts",
-           "run_mps_shots", "sample_mps_expectation_values",
+           "run_mps_shots", "sample_mps_expectation_values", "build_mps_schedules", "run_mps_folded",
            "BoundBatch", "Param", "Template", "compile_templates", "bound_expectation_values", "parameter_shift", "run_bound"]

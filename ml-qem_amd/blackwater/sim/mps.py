@@ -88,6 +88,14 @@ class MpsBatch:
     n_noise: List[int] = field(default_factory=list)       # noise records per circuit
     abs_coeff: List[float] = field(default_factory=list)   # sum |coeff| per circuit
     measured: List[Dict[int, int]] = field(default_factory=list)
+    # the record map of the noisy lowering, with ``SimBatch``'s meaning (record numbers are relative to the circuit's first record,
+    # -1: none); ``blackwater.sim.zne.build_mps_schedules`` folds over it.  The ideal lowering fuses gates into bond records, so it
+    # has no fold units and keeps no map (None)
+    gate_ptr: Optional[np.ndarray] = None         # int64 [B + 1]: circuit c owns gates gate_ptr[c] .. gate_ptr[c + 1]
+    gate_name: Optional[np.ndarray] = None        # int16 [n_gates]: index of the gate's name in SUPPORTED_GATES
+    gate_record: Optional[np.ndarray] = None      # int32 [n_gates]: the gate's own U1 / U2 record
+    gate_noise: Optional[np.ndarray] = None       # int32 [n_gates]: the first noise record after it
+    gate_noise_len: Optional[np.ndarray] = None   # int32 [n_gates]: 0, 1 (DEPOL*) or 2 (a coherent U2, then DEPOL*)
 
     def __len__(self) -> int:
         return int(self.n_qubits.shape[0])
@@ -150,6 +158,8 @@ def compile_mps(circuits: Sequence[Any], observables: Sequence[Any], noise: Opti
     ops, params, op_ptr = [], [], [0]
     term_circ, term_off, letters, coeffs, term_ptr = [], [], [], [], [0]
     site_ptr, readout, n_noise_all, abs_coeff, measured_all, n_qubits = [0], [], [], [], [], []
+    gate_ptr, gate_name, gate_record, gate_noise, gate_noise_len = [0], [], [], [], []
+    name_id = {g: j for j, g in enumerate(SUPPORTED_GATES)}
 
     def emit(kind, site, orient, values):
         ops.append((kind, site, orient, len(params)))
@@ -200,6 +210,7 @@ def compile_mps(circuits: Sequence[Any], observables: Sequence[Any], noise: Opti
             p = tuple(float(v) for v in op.params)
             if not all(math.isfinite(v) for v in p):
                 raise ValueError(f"{where}: op {i} ({name}) has the non-finite angle {p!r}")
+            first, rec, noi, noi_len = op_ptr[-1], -1, -1, 0
             if width == 2:
                 q0, q1 = op.qubits
                 if q0 == q1:
@@ -210,6 +221,7 @@ def compile_mps(circuits: Sequence[Any], observables: Sequence[Any], noise: Opti
                 lower, orient = min(q0, q1), int(q0 > q1)
                 m = _matrix4(name, p)
                 if noisy:
+                    rec = len(ops) - first
                     emit_matrix(OP_MPS_U2, lower, orient, m)
                 else:
                     for other in (lower - 1, lower + 1):
@@ -225,6 +237,7 @@ def compile_mps(circuits: Sequence[Any], observables: Sequence[Any], noise: Opti
                 m = _matrix2(name, p)
                 if m is not None:
                     if noisy:
+                        rec = len(ops) - first
                         emit_matrix(OP_MPS_U1, q0, 0, m)
                     else:
                         site = q0 if q0 in open_bond else q0 - 1 if q0 - 1 in open_bond else None
@@ -246,13 +259,21 @@ def compile_mps(circuits: Sequence[Any], observables: Sequence[Any], noise: Opti
                 if coherent is not None:
                     if width != 2:
                         raise ValueError(f"{where}: op {i} ({name}): a coherent error is a 4x4 unitary, the gate has one qubit")
+                    noi = len(ops) - first
                     emit_matrix(OP_MPS_U2, min(op.qubits), int(op.qubits[0] > op.qubits[1]), _check_coherent((name, reg), coherent))
+                    noi_len += 1
                 if lam is not None:
+                    noi = len(ops) - first if noi < 0 else noi
+                    noi_len += 1
                     if width == 2:
                         emit(OP_MPS_DEPOL2, min(op.qubits), int(op.qubits[0] > op.qubits[1]), [float(lam)])
                     else:
                         emit(OP_MPS_DEPOL1, op.qubits[0], 0, [float(lam)])
                     n_noise += 1
+                gate_name.append(name_id[name])
+                gate_record.append(rec)
+                gate_noise.append(noi)
+                gate_noise_len.append(noi_len)
         for site in sorted(open_bond):
             flush(site)
         for q in sorted(pending):
@@ -285,6 +306,7 @@ def compile_mps(circuits: Sequence[Any], observables: Sequence[Any], noise: Opti
         abs_coeff.append(float(sum(abs(c) for c in cs)))
         measured_all.append(measured)
         n_qubits.append(n)
+        gate_ptr.append(len(gate_record))
 
     if len(params) + PARAM_PAD > 2 ** 31 - 1:
         raise ValueError(f"compile_mps: {len(params)} gate parameters exceed the 2^31 - 1 a record can address; split the batch")
@@ -295,7 +317,11 @@ def compile_mps(circuits: Sequence[Any], observables: Sequence[Any], noise: Opti
         term_off=np.asarray(term_off, dtype=np.int64), letters=np.asarray(letters + [0], dtype=np.uint8),
         coeff=np.asarray(coeffs, dtype=np.float64), site_ptr=np.asarray(site_ptr, dtype=np.int64),
         readout=np.asarray(readout + [[1.0, 0.0]], dtype=np.float64).reshape(-1, 2), max_bond=max_bond, cutoff=cutoff,
-        trajectories=trajectories, n_noise=n_noise_all, abs_coeff=abs_coeff, measured=measured_all)
+        trajectories=trajectories, n_noise=n_noise_all, abs_coeff=abs_coeff, measured=measured_all,
+        gate_ptr=np.asarray(gate_ptr, dtype=np.int64) if noisy else None, gate_name=np.asarray(gate_name, dtype=np.int16) if noisy else None,
+        gate_record=np.asarray(gate_record, dtype=np.int32) if noisy else None,
+        gate_noise=np.asarray(gate_noise, dtype=np.int32) if noisy else None,
+        gate_noise_len=np.asarray(gate_noise_len, dtype=np.int32) if noisy else None)
 
 
 @dataclass

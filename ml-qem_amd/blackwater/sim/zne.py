@@ -37,6 +37,12 @@ what G did to it), so a folded gate's keep factor is multiplied in 1 + 2 folds t
 circuit whose gates are all folded alike is ``ideal * F1 * F2^x``, F2 the product of the foldable gates' keeps that the unfolded walk
 met and F1 that of the others.
 
+Wide circuits at any angle.  ``method="mps"`` (by name alone) folds on matrix-product states: ``compile_mps`` with a noise model and
+``trajectories`` once, :func:`build_mps_schedules` from the record map it keeps, every (run, trajectory) unit through
+``ops.sim_run_mps_folded`` (:func:`run_mps_folded`), then the terms, finish and combine kernels with the F * B runs taken as a batch
+of F * B circuits.  The per-factor values are means over Pauli-insertion trajectories, so the result carries their standard errors
+and sqrt(sum_f w_f^2 se_f^2) for the mitigated value (polynomial extrapolators), and every run's truncation certificate.
+
 Shots.  With ``shots=`` every (circuit, factor) run is measured (``ops.sim_run_folded_measured`` + ``ops.sim_sample``): per factor
 the sampled values and their variances; the mitigated value is sum_f w_f value_f through the same combine, and the mitigated
 variance is sum_f w_f^2 variance_f (the factors are sampled independently) -- the SAME ``mlqem_zne_combine_f64`` called with the
@@ -375,6 +381,40 @@ def build_clifford_schedules(batch: CliffordBatch, noise_factors: Sequence[float
                      noise_factors=factors, achieved=np.asarray(achieved, dtype=np.float64).reshape(len(factors), n_circ))
 
 
+def build_mps_schedules(batch: Any, noise_factors: Sequence[float], amplifier: _Amplifier) -> Schedules:
+    """:func:`build_schedules` for the matrix-product-state format (``mlqem_mps_run_folded_f64``): one schedule per (noise factor,
+    circuit) from the record map the noisy lowering of ``compile_mps`` keeps.  A fold unit is the gate's ``U1`` / ``U2`` record,
+    possibly daggered, followed by its ``gate_noise_len`` noise records, never daggered: a coherent-error ``U2`` where the model has
+    one, then the ``DEPOL`` record (the inverse of a gate carries the gate's own coherent error and noise again).  There are no
+    trailing entries, readout being a table in this format, and no run numbers (``ids`` is empty: every (run, trajectory) unit is
+    a workgroup).  numpy throughout."""
+    if getattr(batch, "gate_ptr", None) is None:
+        raise ValueError("build_mps_schedules: the batch carries no record map: the ideal lowering of compile_mps fuses gates into "
+                         "bond records and has no fold units; ZNE on this path needs noise and trajectories "
+                         "(compile_mps(circuits, observables, noise, trajectories=T))")
+    n_circ = len(batch)
+    factors = tuple(float(f) for f in noise_factors)
+    if not factors:
+        raise ValueError("build_mps_schedules: no noise factor")
+    mask = _name_table(amplifier)[batch.gate_name.astype(np.int64)] if batch.gate_name.size else np.zeros(0, dtype=bool)
+    owner = np.repeat(np.arange(n_circ, dtype=np.int64), np.diff(batch.gate_ptr))
+    rec, noi, noi_len = (getattr(batch, k).astype(np.int64) for k in ("gate_record", "gate_noise", "gate_noise_len"))
+    if noi_len.size and (int(noi_len.min()) < 0 or int(noi_len.max()) > 2):
+        raise ValueError(f"build_mps_schedules: gate_noise_len holds {int(noi_len.min())} .. {int(noi_len.max())}, want 0, 1 or 2")
+    pieces, lengths, achieved = [], [], []
+    for lam in factors:
+        body, body_len, ach = _fold_entries(amplifier, batch.gate_ptr, mask, rec, noi, owner, n_circ, lam, noi_len)
+        pieces.append(body.astype(np.int32))
+        lengths.append(body_len)
+        achieved.append(ach)
+    sched_ptr = np.concatenate([[0], np.cumsum(np.concatenate(lengths))]).astype(np.int64)
+    if int(sched_ptr[-1]) > 2 ** 31 - 1 or len(factors) * n_circ > 2 ** 31 - 1:
+        raise ValueError(f"build_mps_schedules: {int(sched_ptr[-1])} schedule entries over {len(factors) * n_circ} runs exceed the "
+                         "2^31 - 1 one call can take; split the batch")
+    return Schedules(sched_ptr=sched_ptr, sched=np.concatenate(pieces), ids=np.zeros(0, dtype=np.int32), n_wave=0, n_wg=0,
+                     noise_factors=factors, achieved=np.asarray(achieved, dtype=np.float64).reshape(len(factors), n_circ))
+
+
 # ---- extrapolators ---------------------------------------------------------------------------------------------------------------
 class PolynomialExtrapolator:
     """Least-squares polynomial of ``degree`` through (noise factor, value), evaluated at zero noise."""
@@ -544,6 +584,17 @@ class ZNERun:
     ideal_terms: Any = None           # float64 [n_terms]
     # with ExponentialExtrapolator: int32 [n_terms], 1 where a term fell back to the straight line
     fallback_terms: Any = None
+    # on the MPS path (``method="mps"``): every value is a mean over ``trajectories`` Pauli-insertion trajectories per run, ``batch``
+    # is the ``MpsBatch`` and ``norm`` [F, B] the mean <psi|psi>
+    std_error: Any = None             # float64 [F, B]: the standard error of ``values``
+    term_std_error: Any = None        # float64 [F, n_terms]
+    mitigated_std_error: Any = None   # float64 [B]: sqrt(sum_f w_f^2 std_error_f^2); None with ExponentialExtrapolator
+    error_bound: Any = None           # float64 [F, B]: the truncation certificate of every run (mean over its trajectories)
+    discarded: Any = None             # float64 [F, B]
+    bond: Any = None                  # int32 [F, B]: the largest bond a run reached
+    trajectories: Optional[int] = None
+    traj_term_values: Any = None      # float64 [T, F * n_terms] with ``keep_trajectories``
+    traj_stats: Any = None            # float64 [T, F * B, 6] with it: MpsResult.traj_stats per run
 
 
 _CLIFFORD_SHOTS = ("DeviceEstimator: shots are not drawn on the Clifford path (method='clifford', or 'auto' on circuits over the exact "
@@ -562,14 +613,132 @@ def _combine(strategy: "ZNEStrategy", weights: np.ndarray, term_values, term_ptr
     return ops.zne_combine(term_values, w, term_ptr, coeff) + (None,)
 
 
+def tile_mps_runs(batch: Any, n_factors: int) -> dict:
+    """The terms side of an ``MpsBatch`` for its F * B folded runs taken as a batch of F * B circuits (what ``mlqem_mps_terms_f64`` and
+    ``mlqem_mps_finish_f64`` are given): ``run_qubits`` [F * B], ``term_circ`` [F * n_terms] (run numbers), ``term_off``
+    [F * n_terms], ``site_ptr`` [F * B + 1], ``term_ptr`` [F * B + 1] and ``coeff`` [F * n_terms] as host arrays.  ``letters`` and
+    ``readout`` are not tiled: every factor's offsets point into the batch's own."""
+    f, b, n_terms = int(n_factors), len(batch), int(batch.term_circ.shape[0])
+    rows = np.arange(f, dtype=np.int64)[:, None]
+    return {"run_qubits": np.tile(batch.n_qubits, f).astype(np.int32),
+            "term_circ": (batch.term_circ.astype(np.int64)[None, :] + rows * b).reshape(-1).astype(np.int32),
+            "term_off": np.tile(batch.term_off, f).astype(np.int64),
+            "site_ptr": np.concatenate([np.tile(batch.site_ptr[:-1], f), batch.site_ptr[-1:]]).astype(np.int64),
+            "term_ptr": np.concatenate([(batch.term_ptr[None, :-1] + rows * n_terms).reshape(-1), [f * n_terms]]).astype(np.int64),
+            "coeff": np.tile(batch.coeff, f).astype(np.float64)}
+
+
+def run_mps_folded(batch: Any, schedules: Schedules, seed: int = 0, run_keys=None, device="cuda", keep_trajectories: bool = False,
+                   buffer_bytes: Optional[int] = None):
+    """Runs the F * B folded runs of a batch lowered once by ``compile_mps`` (with noise and trajectories) along ``schedules``
+    (:func:`build_mps_schedules`) on the device.  Returns an :class:`~blackwater.sim.mps.MpsResult` over the runs taken as a batch of
+    F * B circuits, run r = f * B + c: ``values`` / ``norm`` / ``std_error`` / ``discarded`` / ``error_bound`` / ``bond`` [F * B],
+    ``term_values`` / ``term_std_error`` [F * n_terms], ``term_ptr`` [F * B + 1] (tiled), ``batch`` the unreplicated batch.
+    ``run_keys``: one integer per run, by default the run number; a unit's bits depend on (seed, run key, trajectory number, the
+    run's schedule and records) alone.  The (run, trajectory) units are split into launches so that the site-tensor workspace stays
+    under ``buffer_bytes`` (default :data:`~blackwater.sim.mps.MPS_BUFFER_BYTES`), as :func:`~blackwater.sim.mps.run_mps` splits."""
+    import dataclasses
+
+    import torch
+
+    from ..native import ops
+    from .mps import MPS_BUFFER_BYTES, MpsResult, _mps_chunks
+    from .program import check_trajectories
+    from .run import _run_keys
+
+    if batch.trajectories is None:
+        raise ValueError("run_mps_folded: the batch was lowered without trajectories; ZNE on this path needs noise and trajectories "
+                         "(compile_mps(circuits, observables, noise, trajectories=T))")
+    n_traj, seed = check_trajectories(batch.trajectories, "run_mps_folded"), check_seed(seed, "run_mps_folded")
+    n_f, b, n_terms = len(schedules.noise_factors), len(batch), int(batch.term_circ.shape[0])
+    n_runs = n_f * b
+    if schedules.sched_ptr.shape[0] != n_runs + 1:
+        raise ValueError(f"run_mps_folded: the schedules hold {schedules.sched_ptr.shape[0] - 1} runs, the batch has {n_f} factors x {b} "
+                         "circuits")
+    keys = _run_keys(run_keys, n_runs, "run_mps_folded")
+    buffer_bytes = MPS_BUFFER_BYTES if buffer_bytes is None else int(buffer_bytes)
+    if buffer_bytes < 1:
+        raise ValueError(f"run_mps_folded: buffer_bytes = {buffer_bytes!r}, want a positive number of bytes")
+    dev = torch.device(device)
+    tiled = tile_mps_runs(batch, n_f)
+    t, s = batch.to(dev), schedules.to(dev)
+    r = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in tiled.items()}
+    keys_t = torch.from_numpy(keys).to(dev)
+    traj_terms = torch.zeros((n_traj, n_f * n_terms), dtype=torch.float64, device=dev)
+    traj_norm = torch.zeros((n_traj, n_runs), dtype=torch.float64, device=dev)
+    traj_stats = torch.zeros((n_traj, n_runs, ops.MPS_STATS), dtype=torch.float64, device=dev)
+    if n_runs:
+        runs = dataclasses.replace(batch, n_qubits=tiled["run_qubits"])   # the F * B runs as what _mps_chunks splits
+        chunks = _mps_chunks(runs, n_traj, buffer_bytes)
+        widest = [int(tiled["run_qubits"][list(rr)].max()) for rr, _ in chunks]
+        workspace = torch.empty((max(ops.mps_workspace_bytes(w, batch.max_bond, len(rr) * len(tr)) for w, (rr, tr) in zip(widest, chunks)),),
+                                dtype=torch.uint8, device=dev)
+        for w, (rr, tr) in zip(widest, chunks):
+            t0, t1 = int(tiled["term_ptr"][rr.start]), int(tiled["term_ptr"][rr.stop])
+            ops.sim_run_mps_folded(t["n_qubits"], t["op_ptr"], t["ops"], t["params"], s["sched_ptr"], s["sched"], n_f, keys_t,
+                                   r["run_qubits"], r["term_circ"], r["term_off"], t["letters"], r["site_ptr"], t["readout"],
+                                   (rr.start, len(rr)), (t0, t1 - t0), (tr.start, len(tr)), n_traj, seed, batch.max_bond, batch.cutoff, w,
+                                   workspace, traj_terms, traj_norm, traj_stats)
+    out = ops.sim_mps_finish(r["term_ptr"], r["coeff"], traj_terms, traj_norm, traj_stats)
+    return MpsResult(out["values"], out["term_values"], out["norm"], r["term_ptr"], out["discarded"], out["error_bound"], out["bond"],
+                     out["std_error"], out["term_std_error"], n_traj, seed, traj_terms if keep_trajectories else None,
+                     traj_stats if keep_trajectories else None, batch)
+
+
+def _zne_run_mps(circuits, observables, noise, strategy, weights, device, shots, seed, run_keys, trajectories, max_bond, cutoff,
+                 buffer_bytes, keep_trajectories) -> ZNERun:
+    import torch
+
+    from ..native import ops
+    from .mps import DEFAULT_CUTOFF, MAX_BOND, compile_mps
+    from .program import check_trajectories
+
+    if shots is not None:
+        raise ValueError("zne_run(method='mps'): shots= is not supported with it (no shots are drawn from folded matrix-product-state "
+                         "runs; the sampled values of an unfolded circuit are DeviceEstimator(method='mps_shots') / "
+                         "sample_mps_expectation_values)")
+    if noise is None or trajectories is None:
+        raise ValueError("zne_run(method='mps'): ZNE on the matrix-product-state path needs noise and trajectories (a noise model and "
+                         "trajectories=T: the noisy lowering keeps the gate records that are folded; the ideal one fuses them)")
+    n_traj = check_trajectories(trajectories, "zne_run")
+    batch = compile_mps(circuits, observables, noise, n_traj, MAX_BOND if max_bond is None else max_bond,
+                        DEFAULT_CUTOFF if cutoff is None else cutoff)
+    sch = build_mps_schedules(batch, strategy.noise_factors, strategy.noise_amplifier)
+    n_f, b, n_terms = len(sch.noise_factors), len(batch), int(batch.term_circ.shape[0])
+    res = run_mps_folded(batch, sch, seed, run_keys, device, keep_trajectories, buffer_bytes)
+    dev = res.values.device
+    term_ptr, coeff = (torch.from_numpy(np.ascontiguousarray(v)).to(dev) for v in (batch.term_ptr, batch.coeff))
+    term_values = res.term_values.reshape(n_f, n_terms)
+    mitigated_values, mitigated_terms, fallback = _combine(strategy, weights, term_values, term_ptr, coeff)
+    std_error = res.std_error.reshape(n_f, b)
+    mitigated_std_error = None
+    if not getattr(strategy.extrapolator, "exponential", False):
+        # sqrt(sum_f w_f^2 se_f^2): the combine on the squared errors, squared weights, one unit-coefficient "term" per circuit
+        _, var = ops.zne_combine((std_error * std_error).contiguous(), torch.from_numpy(weights * weights).to(dev),
+                                 torch.arange(b + 1, dtype=torch.int64, device=dev), torch.ones(b, dtype=torch.float64, device=dev))
+        mitigated_std_error = torch.sqrt(var)
+    return ZNERun(mitigated_values, mitigated_terms, term_ptr, res.values.reshape(n_f, b), term_values, res.norm.reshape(n_f, b), batch,
+                  sch, weights, fallback_terms=fallback, std_error=std_error, term_std_error=res.term_std_error.reshape(n_f, n_terms),
+                  mitigated_std_error=mitigated_std_error, error_bound=res.error_bound.reshape(n_f, b),
+                  discarded=res.discarded.reshape(n_f, b), bond=res.bond.reshape(n_f, b), trajectories=n_traj,
+                  traj_term_values=res.traj_term_values, traj_stats=res.traj_stats)
+
+
 def zne_run(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None,
             strategy: Optional[ZNEStrategy] = None, device="cuda", shots: Optional[int] = None, seed: int = 0, run_keys=None,
-            method: str = "exact") -> ZNERun:
+            method: str = "exact", trajectories: Optional[int] = None, max_bond: Optional[int] = None, cutoff: Optional[float] = None,
+            buffer_bytes: Optional[int] = None, keep_trajectories: bool = False) -> ZNERun:
     """Lowers once, builds the schedules, simulates every (circuit, factor) run in one call and extrapolates in one more.  With
     ``shots`` every run is also measured and the extrapolation is of the sampled values (see the module docstring); ``run_keys``:
     one integer per run f * B + c (by default the run number).  ``method``: ``"exact"`` (the default), ``"clifford"`` or ``"auto"``,
     with :class:`DeviceEstimator`'s meaning and ``auto`` rule; on the Clifford path ``batch`` is the ``CliffordBatch``, ``norm`` is
-    None, ``ideal_values`` / ``ideal_terms`` come from the same call, and ``shots`` is refused."""
+    None, ``ideal_values`` / ``ideal_terms`` come from the same call, and ``shots`` is refused.
+
+    ``method="mps"`` (by name alone; ``auto`` never picks it) folds wide circuits at any angle on matrix-product states: needs
+    ``noise`` and ``trajectories=T``; ``max_bond`` / ``cutoff`` / ``buffer_bytes`` as in :func:`~blackwater.sim.mps.run_mps`.  One
+    lowering, :func:`build_mps_schedules`, then every (run, trajectory) unit through ``ops.sim_run_mps_folded`` in chunks that keep
+    the site-tensor workspace under ``buffer_bytes``, one finish over the F * B runs and the combine.  The per-factor values are
+    means over the trajectories; :class:`ZNERun` carries their standard errors, the truncation certificates and the bonds."""
     import torch
 
     from ..native import ops
@@ -584,9 +753,15 @@ def zne_run(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional
                          "propagated through the exponential fit); use a polynomial extrapolator or run without shots")
     if method == "trajectories":
         raise ValueError("zne_run: method = 'trajectories': folded / ZNE runs over quantum trajectories are not supported; "
-                         "want one of exact, clifford, auto")
+                         "want one of exact, clifford, auto, mps")
+    if method == "mps":
+        return _zne_run_mps(circuits, observables, noise, strategy, weights, device, shots, seed, run_keys, trajectories, max_bond, cutoff,
+                            buffer_bytes, keep_trajectories)
+    if trajectories is not None or max_bond is not None or cutoff is not None or buffer_bytes is not None or keep_trajectories:
+        raise ValueError(f"zne_run: trajectories=, max_bond=, cutoff=, buffer_bytes= and keep_trajectories= belong to method='mps', "
+                         f"not to method = {method!r}")
     if method not in DeviceEstimator.METHODS:
-        raise ValueError(f"zne_run: method = {method!r}, want one of {', '.join(DeviceEstimator.METHODS)}")
+        raise ValueError(f"zne_run: method = {method!r}, want one of {', '.join(DeviceEstimator.METHODS + ('mps',))}")
     if method != "exact" and DeviceEstimator(noise, device, method=method)._use_clifford(circuits):
         if shots is not None:
             raise ValueError(_CLIFFORD_SHOTS)
@@ -657,11 +832,13 @@ class ZNEJob:
     the wrapped estimator's job when ``result()`` is asked for."""
 
     def __init__(self, strategy: ZNEStrategy, achieved: np.ndarray, n_circuits: int, job_id: str, values=None, per_factor=None,
-                 base_job=None, shots=None, variance=None, per_factor_variance=None, fallback=None):
+                 base_job=None, shots=None, variance=None, per_factor_variance=None, fallback=None, metadata=None, zne_metadata=None):
         self._strategy, self._achieved, self._n, self._job_id = strategy, achieved, n_circuits, job_id
         self._values, self._per_factor, self._base_job = values, per_factor, base_job
         self._shots, self._variance, self._per_factor_variance = shots, variance, per_factor_variance
         self._fallback = fallback   # with ExponentialExtrapolator on a fused path: per circuit, the terms that fell back
+        # the MPS path: per circuit, what goes into metadata[k] and into metadata[k]["zne"]
+        self._metadata, self._zne_metadata = metadata, zne_metadata
 
     def result(self):
         meta = [{} for _ in range(self._n)]
@@ -674,6 +851,9 @@ class ZNEJob:
             meta[k]["zne"] = _zne_metadata(self._strategy, self._achieved, self._per_factor, k)
             if self._fallback is not None:
                 meta[k]["zne"]["fallback_terms"] = int(self._fallback[k])
+            if self._metadata is not None:
+                meta[k].update(self._metadata[k])
+                meta[k]["zne"].update(self._zne_metadata[k])
             if self._shots is not None:   # the fused path with shots: the error bar of the mitigated value
                 var = float(self._variance[k])
                 meta[k].update(variance=var, shots=int(self._shots), std_error=math.sqrt(max(var, 0.0) / self._shots))
@@ -703,7 +883,11 @@ def zne(cls):
 
     Around :class:`DeviceEstimator` it takes the fused path (:func:`zne_run`: one lowering, schedules, two calls) and follows the
     estimator's ``method``: ``"clifford"`` (or ``"auto"`` on a job over the exact simulator's cap) extrapolates Clifford circuits of
-    up to 512 qubits, without shots.  With :class:`ExponentialExtrapolator` on a fused path ``metadata[k]["zne"]["fallback_terms"]``
+    up to 512 qubits, without shots; ``"mps"`` (with ``trajectories=``, ``max_bond=``, ``cutoff=``) folds circuits on a line at any
+    angle on matrix-product states: for polynomial extrapolators ``metadata[k]`` gains ``std_error``, ``trajectories`` and
+    ``truncation_error_bound`` = sum_f |w_f| B_f (|mitigated - exact ZNE| <= 2 * that * sum|coeff|), and ``metadata[k]["zne"]`` the
+    per-factor ``std_errors`` and ``truncation_error_bounds``; with :class:`ExponentialExtrapolator` ``std_error`` and
+    ``truncation_error_bound`` are omitted.  With :class:`ExponentialExtrapolator` on a fused path ``metadata[k]["zne"]["fallback_terms"]``
     counts the circuit's terms that fell back to the straight line.  Around any other
     estimator class it folds the IR (:func:`fold_circuit`), submits the F * B circuits through the wrapped ``_run`` in one job and
     combines with the same weights on the host; circuits must arrive bound there."""
@@ -731,6 +915,29 @@ def zne(cls):
                 if len(p):
                     raise ValueError(f"{type(self).__name__}: circuit {k} comes with {len(p)} parameter values; circuits must arrive bound")
             shots, seed = run_options.pop("shots", self._shots), run_options.pop("seed", self._seed)
+            if self._method == "mps":   # job j's run r draws with the key j * 2^32 + r, as on the shots path
+                n_f, n = len(strategy.noise_factors), len(circuits)
+                keys = np.arange(n_f * n, dtype=np.int64) + (np.int64(self._zne_count) << 32)
+                run = zne_run(circuits, observables, self._noise, strategy, self._device, shots=shots, seed=seed, run_keys=keys,
+                              method="mps", trajectories=None if self._noise is None else self._trajectories, max_bond=self._max_bond,
+                              cutoff=self._cutoff)
+                se, bound = run.std_error.cpu().numpy(), run.error_bound.cpu().numpy()
+                polynomial = run.mitigated_std_error is not None
+                mse = run.mitigated_std_error.cpu().numpy() if polynomial else None
+                metadata, zne_metadata = [], []
+                for k in range(n):
+                    m = {"trajectories": run.trajectories}
+                    if polynomial:   # |mitigated - exact ZNE| <= 2 * truncation_error_bound * sum|coeff|
+                        m.update(std_error=float(mse[k]), truncation_error_bound=float(np.abs(run.weights) @ bound[:, k]))
+                    metadata.append(m)
+                    zne_metadata.append({"std_errors": tuple(float(v) for v in se[:, k]),
+                                         "truncation_error_bounds": tuple(float(v) for v in bound[:, k])})
+                fallback = None
+                if run.fallback_terms is not None:
+                    ptr, flags = run.term_ptr.cpu().numpy(), run.fallback_terms.cpu().numpy()
+                    fallback = [int(flags[ptr[k]:ptr[k + 1]].sum()) for k in range(n)]
+                return ZNEJob(strategy, run.schedules.achieved, n, f"zne-sim-{self._zne_count}", values=run.mitigated_values.cpu().numpy(),
+                              per_factor=run.values.cpu().numpy(), fallback=fallback, metadata=metadata, zne_metadata=zne_metadata)
             if shots is not None and self._method != "exact" and self._use_clifford(circuits):
                 raise ValueError(_CLIFFORD_SHOTS)
             if shots is not None:   # job j's run r draws with the key j * 2^32 + r: successive runs do not repeat their draws

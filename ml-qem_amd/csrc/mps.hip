@@ -1,6 +1,7 @@
 // Matrix-product-state simulation of circuits on a line, a batch per call (mlqem_mps_run_f64, mlqem_mps_terms_f64,
-// mlqem_mps_finish_f64), and measurement shots from the states it leaves (mlqem_mps_sample_f64, mlqem_mps_sample_finish_f64: the
-// kernels after mps_finish_kernel).  include/mlqem_hip.h has the contract: the records, the keep rule, the certificate, the draws.
+// mlqem_mps_finish_f64; mlqem_mps_run_folded_f64 walks a fold schedule over the same records: zero-noise extrapolation), and
+// measurement shots from the states it leaves (mlqem_mps_sample_f64, mlqem_mps_sample_finish_f64: the kernels after
+// mps_finish_kernel).  include/mlqem_hip.h has the contract: the records, the keep rule, the certificate, the draws.
 //
 // Work unit of the run kernel: one (circuit, trajectory) pair, a workgroup each.  The site tensors A[q] (chi_l x 2 x chi_r complex
 // float64, entry (l, s, r) at (l * 2 + s) * chi + r, chi = max_bond) live in the unit's slice of a global workspace; the bond sizes
@@ -82,8 +83,9 @@ struct MpsState {
   // The bond primitive on sites (q, q + 1): theta = A[q] A[q + 1], the 4x4 matrix g (null: none; `orient`: its basis index is
   // bit(q + 1) + 2 bit(q), else bit(q) + 2 bit(q + 1)), the decomposition, the keep rule.  left = false: A[q] takes the orthonormal
   // columns and the centre ends on q + 1; left = true: theta is decomposed transposed, A[q + 1] takes orthonormal rows and the
-  // centre ends on q.
-  __device__ __forceinline__ void bond_op(int q, const double* g, int orient, bool left) {
+  // centre ends on q.  FOLD with `dagger`: g's conjugate transpose, read from the same record by swapped strides and a flipped sign.
+  template <bool FOLD = false>
+  __device__ __forceinline__ void bond_op(int q, const double* g, int orient, bool left, int dagger = 0) {
     const int dl = dims[q], dm = dims[q + 1], dr = dims[q + 2];
     sim_c* aq = A + (int64_t)q * S;
     sim_c* aq1 = aq + S;
@@ -102,6 +104,8 @@ struct MpsState {
       }
       sim_c o[4] = {t[0], t[1], t[2], t[3]};
       if (g != nullptr) {
+        const int rs = FOLD && dagger ? 2 : 8, cs = FOLD && dagger ? 8 : 2;   // strides of a row and of a column in the record
+        const double sg = FOLD && dagger ? -1.0 : 1.0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const int gk = orient ? ((k & 1) << 1) | (k >> 1) : k;
@@ -109,7 +113,11 @@ struct MpsState {
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             const int gj = orient ? ((j & 1) << 1) | (j >> 1) : j;
-            acc = cmac(acc, sim_c{g[8 * gk + 2 * gj], g[8 * gk + 2 * gj + 1]}, t[j]);
+            if constexpr (FOLD) {
+              acc = cmac(acc, sim_c{g[rs * gk + cs * gj], sg * g[rs * gk + cs * gj + 1]}, t[j]);
+            } else {
+              acc = cmac(acc, sim_c{g[8 * gk + 2 * gj], g[8 * gk + 2 * gj + 1]}, t[j]);
+            }
           }
           o[k] = acc;
         }
@@ -272,18 +280,27 @@ __device__ __forceinline__ int mps_draw(int index, int traj, uint32_t key_lo, ui
   return __builtin_amdgcn_readfirstlane(code);
 }
 
+// FOLD = false: circuit circ_first + cl runs its records in order (mlqem_mps_run_f64).  FOLD = true (mlqem_mps_run_folded_f64):
+// `circ_first` counts RUNS r = f * B + c, and run r walks the schedule sched[sched_ptr[r] .. sched_ptr[r + 1]) of entries
+// (k << 1) | dagger over circuit c's records; run_keys and traj_stats have one row per run.  The noise index counts the noise
+// entries as the run executes them, so a run draws what the plain kernel draws on the schedule written out.
+template <bool FOLD>
 __global__ __launch_bounds__(kBlock) void mps_run_kernel(int B, const int32_t* __restrict__ n_qubits, const int64_t* __restrict__ op_ptr,
                                                          const sim_i4* __restrict__ ops, int64_t n_ops, const double* __restrict__ params,
                                                          int64_t n_params, const int64_t* __restrict__ run_keys, int circ_first, int traj_first,
                                                          int traj_count, uint32_t seed_lo, uint32_t seed_hi, int chi, double cutoff,
-                                                         int max_q, char* __restrict__ workspace, double* __restrict__ traj_stats) {
+                                                         int max_q, char* __restrict__ workspace, double* __restrict__ traj_stats,
+                                                         int n_runs, const int64_t* __restrict__ sched_ptr, const int32_t* __restrict__ sched,
+                                                         int64_t n_sched) {
   __shared__ sim_c th[kMpsCols * kMpsCols];
   __shared__ double sig[kMpsCols];
   __shared__ int perm[kMpsCols];
   __shared__ int dims[kMpsMaxQubits + 2];
   __shared__ int flag;
   const int unit = (int)blockIdx.x, cl = unit / traj_count, tl = unit - cl * traj_count;
-  const int c = min(max(circ_first + cl, 0), B - 1), traj = traj_first + tl;
+  const int run = FOLD ? min(max(circ_first + cl, 0), n_runs - 1) : 0;
+  const int c = FOLD ? run % B : min(max(circ_first + cl, 0), B - 1), traj = traj_first + tl;
+  const int row = FOLD ? run : c, rows = FOLD ? n_runs : B;   // of run_keys and traj_stats
   const int n = min(max(n_qubits[c], 1), max_q);
   const int tid = (int)threadIdx.x;
   char* base = workspace + (int64_t)unit * mps_unit_bytes(max_q, chi);
@@ -316,12 +333,25 @@ __global__ __launch_bounds__(kBlock) void mps_run_kernel(int B, const int32_t* _
   __syncthreads();
 
   const int64_t ob = min(max(op_ptr[c], (int64_t)0), n_ops), oe = min(max(op_ptr[c + 1], ob), n_ops);
-  const int n_step = (int)min(oe - ob, (int64_t)0x7FFFFFFF);
-  const int64_t key = run_keys[c];
+  const int n_op = (int)min(oe - ob, (int64_t)0x7FFFFFFF);
+  int64_t sb = 0;
+  int n_step = n_op;   // steps this run takes: its records, or the entries of its schedule
+  if (FOLD) {
+    sb = min(max(sched_ptr[run], (int64_t)0), n_sched);
+    const int64_t se = min(max(sched_ptr[run + 1], sb), n_sched);
+    n_step = n_op > 0 ? (int)min(se - sb, (int64_t)0x7FFFFFFF) : 0;   // a circuit without records skips its entries
+  }
+  const int64_t key = run_keys[row];
   const uint32_t key_lo = (uint32_t)(uint64_t)key, key_hi = (uint32_t)((uint64_t)key >> 32);
   int centre = 0, noise_index = 0;
   for (int k = 0; k < n_step; ++k) {
-    const sim_i4 op = ops[ob + k];   // kind, site, orientation, offset into params
+    int at = k, dg = 0;   // dg: apply the record's conjugate transpose
+    if (FOLD) {
+      const int entry = __builtin_amdgcn_readfirstlane(sched[sb + k]);
+      at = min(max(entry >> 1, 0), n_op - 1);
+      dg = entry & 1;
+    }
+    const sim_i4 op = ops[ob + at];   // kind, site, orientation, offset into params
     const int kind = __builtin_amdgcn_readfirstlane(op.x);
     const int orient = __builtin_amdgcn_readfirstlane(op.z) & 1;
     const int64_t po = min((int64_t)max(op.w, 0), n_params - kSimParamPad);
@@ -329,7 +359,13 @@ __global__ __launch_bounds__(kBlock) void mps_run_kernel(int B, const int32_t* _
     if (kind == MLQEM_MPS_OP_U1 || kind == MLQEM_MPS_OP_DEPOL1) {
       const int q = __builtin_amdgcn_readfirstlane(min(max(op.y, 0), n - 1));
       if (kind == MLQEM_MPS_OP_U1) {
-        st.one_site(q, sim_c{m[0], m[1]}, sim_c{m[2], m[3]}, sim_c{m[4], m[5]}, sim_c{m[6], m[7]});
+        if constexpr (FOLD) {   // the off-diagonal entries swapped and every imaginary part times -1 where daggered
+          const int i01 = dg ? 4 : 2, i10 = dg ? 2 : 4;
+          const double sg = dg ? -1.0 : 1.0;
+          st.one_site(q, sim_c{m[0], sg * m[1]}, sim_c{m[i01], sg * m[i01 + 1]}, sim_c{m[i10], sg * m[i10 + 1]}, sim_c{m[6], sg * m[7]});
+        } else {
+          st.one_site(q, sim_c{m[0], m[1]}, sim_c{m[2], m[3]}, sim_c{m[4], m[5]}, sim_c{m[6], m[7]});
+        }
       } else {
         st.pauli(q, mps_draw(noise_index, traj, key_lo, key_hi, seed_lo, seed_hi, false, m[0]));
         ++noise_index;
@@ -338,14 +374,14 @@ __global__ __launch_bounds__(kBlock) void mps_run_kernel(int B, const int32_t* _
       const int q = __builtin_amdgcn_readfirstlane(min(max(op.y, 0), n - 2));
       if (kind == MLQEM_MPS_OP_U2) {
         while (centre < q) {
-          st.bond_op(centre, nullptr, 0, false);
+          st.template bond_op<FOLD>(centre, nullptr, 0, false);
           ++centre;
         }
         while (centre > q) {
-          st.bond_op(centre - 1, nullptr, 0, true);
+          st.template bond_op<FOLD>(centre - 1, nullptr, 0, true);
           --centre;
         }
-        st.bond_op(q, m, orient, false);
+        st.template bond_op<FOLD>(q, m, orient, false, dg);
         centre = q + 1;
       } else {
         const int code = mps_draw(noise_index, traj, key_lo, key_hi, seed_lo, seed_hi, true, m[0]);
@@ -358,7 +394,7 @@ __global__ __launch_bounds__(kBlock) void mps_run_kernel(int B, const int32_t* _
   int* gdims = reinterpret_cast<int*>(base);
   for (int q = tid; q <= n; q += kBlock) gdims[q] = dims[q];
   if (tid == 0) {
-    double* out = traj_stats + ((int64_t)traj * B + c) * kMpsStats;
+    double* out = traj_stats + ((int64_t)traj * rows + row) * kMpsStats;
     out[0] = st.discarded;
     out[1] = st.bound;
     out[2] = (double)st.bond;
@@ -747,10 +783,38 @@ extern "C" int mlqem_mps_run_f64(int64_t n_circuits, const int32_t* n_qubits, co
   if (!n_qubits || !op_ptr || !params || !run_keys || !workspace || !traj_stats || (n_ops > 0 && !ops)) return MLQEM_ERR_BAD_ARG;
   if (!aligned_to(ops, 16) || !aligned_to(workspace, 16) || !aligned_to(run_keys, 8)) return MLQEM_ERR_BAD_ARG;
   if (workspace_bytes < mlqem_mps_workspace_bytes(max_qubits, max_bond, circ_count * traj_count)) return MLQEM_ERR_WORKSPACE;
-  hipLaunchKernelGGL(mps_run_kernel, dim3((unsigned)(circ_count * traj_count)), dim3(kBlock), 0, as_stream(stream), (int)n_circuits, n_qubits,
-                     op_ptr, reinterpret_cast<const sim_i4*>(ops), n_ops, params, n_params, run_keys, (int)circ_first, (int)traj_first,
-                     (int)traj_count, (uint32_t)seed, (uint32_t)(seed >> 32), (int)max_bond, cutoff, (int)max_qubits,
-                     static_cast<char*>(workspace), traj_stats);
+  hipLaunchKernelGGL((mps_run_kernel<false>), dim3((unsigned)(circ_count * traj_count)), dim3(kBlock), 0, as_stream(stream), (int)n_circuits,
+                     n_qubits, op_ptr, reinterpret_cast<const sim_i4*>(ops), n_ops, params, n_params, run_keys, (int)circ_first,
+                     (int)traj_first, (int)traj_count, (uint32_t)seed, (uint32_t)(seed >> 32), (int)max_bond, cutoff, (int)max_qubits,
+                     static_cast<char*>(workspace), traj_stats, 0, (const int64_t*)nullptr, (const int32_t*)nullptr, (int64_t)0);
+  return launch_status();
+}
+
+extern "C" int mlqem_mps_run_folded_f64(int64_t n_circuits, int64_t n_factors, const int32_t* n_qubits, const int64_t* op_ptr,
+                                        const mlqem_sim_op* ops, int64_t n_ops, const double* params, int64_t n_params,
+                                        const int64_t* sched_ptr, const int32_t* sched, int64_t n_sched, const int64_t* run_keys,
+                                        int64_t run_first, int64_t run_count, int64_t traj_first, int64_t traj_count, int64_t trajectories,
+                                        uint64_t seed, int64_t max_bond, double cutoff, int64_t max_qubits, void* workspace,
+                                        size_t workspace_bytes, double* traj_stats, mlqem_stream_t stream) {
+  begin_launches();
+  if (n_circuits == 0) return MLQEM_OK;
+  if (n_ops < 0 || n_params < kSimParamPad || n_sched < 0 || n_factors < 1 || n_circuits < 1 || !(cutoff >= 0.0) || !(cutoff < 1.0))
+    return MLQEM_ERR_BAD_ARG;
+  if (n_circuits > 0x7FFFFFFFll || n_factors > 0x7FFFFFFFll || n_circuits * n_factors > 0x7FFFFFFFll || n_params > 0x7FFFFFFFll ||
+      n_sched > 0x7FFFFFFFll)
+    return MLQEM_ERR_UNSUPPORTED;
+  const int64_t n_runs = n_circuits * n_factors;
+  if (!mps_shape_ok(n_runs, run_first, run_count, traj_first, traj_count, trajectories, max_bond, max_qubits)) return MLQEM_ERR_BAD_ARG;
+  if (run_count * traj_count > 0x7FFFFFFFll) return MLQEM_ERR_UNSUPPORTED;
+  if (!n_qubits || !op_ptr || !params || !sched_ptr || !run_keys || !workspace || !traj_stats || (n_ops > 0 && !ops) || (n_sched > 0 && !sched))
+    return MLQEM_ERR_BAD_ARG;
+  if (!aligned_to(ops, 16) || !aligned_to(workspace, 16) || !aligned_to(run_keys, 8) || !aligned_to(sched_ptr, 8) || !aligned_to(sched, 4))
+    return MLQEM_ERR_BAD_ARG;
+  if (workspace_bytes < mlqem_mps_workspace_bytes(max_qubits, max_bond, run_count * traj_count)) return MLQEM_ERR_WORKSPACE;
+  hipLaunchKernelGGL((mps_run_kernel<true>), dim3((unsigned)(run_count * traj_count)), dim3(kBlock), 0, as_stream(stream), (int)n_circuits,
+                     n_qubits, op_ptr, reinterpret_cast<const sim_i4*>(ops), n_ops, params, n_params, run_keys, (int)run_first,
+                     (int)traj_first, (int)traj_count, (uint32_t)seed, (uint32_t)(seed >> 32), (int)max_bond, cutoff, (int)max_qubits,
+                     static_cast<char*>(workspace), traj_stats, (int)n_runs, sched_ptr, sched, n_sched);
   return launch_status();
 }
 

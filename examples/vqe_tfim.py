@@ -2,6 +2,7 @@
 circuit evaluation on the GPU (a script, not a driver: DESIGN.md 8 keeps VQE drivers out of scope).
 
     python examples/vqe_tfim.py [--steps 60] [--lr 0.2]
+    python examples/vqe_tfim.py --qubits 100 --mps [--max-bond 16] [--steps 40] [--lr 0.05]
 
 H = -J sum_i Z_i Z_{i+1} - h sum_i X_i.  The ansatz is ``two_local(4, ry, cx on the lima fixture's coupled pairs, reps=2)``, one
 template lowered once; a step is ONE ``parameter_shift`` call (the energy and its 12 exact partial derivatives from 25 runs).
@@ -12,6 +13,11 @@ Twice from the same fixed start:
               processor takes single-Pauli observables), with a linear mitigator fitted on the ansatz at 256 random parameter
               vectors (noisy term value -> ideal term value; both from ``bound_expectation_values``).
 The energy of every step is printed beside numpy's exact ground energy.
+
+``--qubits N --mps`` descends the same energy AT WIDTH: the ansatz is ``two_local(N, ry, cx on the line, reps=2)``, lowered once
+by ``compile_mps_templates``, and a step is one ``parameter_shift(..., method="mps")`` call: the 3 N parameters' 2 * 3 N shifted
+copies are bound on the device and run as matrix-product states of bond at most ``--max-bond``.  Noiseless only; the exact ground
+energy is printed beside it up to 12 qubits, the energy per site beyond.
 """
 import argparse
 import os
@@ -34,22 +40,23 @@ DEV = "cuda:0"
 N, J, H_FIELD = 4, 1.0, 0.7
 
 
-def hamiltonian():
+def hamiltonian(n=N):
     terms = []
-    for i in range(N - 1):
-        label = ["I"] * N
-        label[N - 1 - i] = label[N - 2 - i] = "Z"
+    for i in range(n - 1):
+        label = ["I"] * n
+        label[n - 1 - i] = label[n - 2 - i] = "Z"
         terms.append(("".join(label), -J))
-    for i in range(N):
-        label = ["I"] * N
-        label[N - 1 - i] = "X"
+    for i in range(n):
+        label = ["I"] * n
+        label[n - 1 - i] = "X"
         terms.append(("".join(label), -H_FIELD))
     return terms
 
 
 def exact_ground_energy(terms):
     pauli = {"I": np.eye(2), "X": np.array([[0, 1], [1, 0]]), "Z": np.diag([1.0, -1.0])}
-    h = np.zeros((2 ** N, 2 ** N))
+    n = len(terms[0][0])
+    h = np.zeros((2 ** n, 2 ** n))
     for label, coeff in terms:
         m = np.eye(1)
         for ch in label:
@@ -86,11 +93,35 @@ def descend(ansatz, terms, noise, start, steps, lr, report):
     return theta
 
 
+def descend_mps(n, steps, lr, max_bond):
+    """The descent at width: one lowering, every step one bind launch per chunk and the MPS kernels."""
+    ansatz = two_local(n, rotation_blocks=("ry",), entanglement_blocks="cx", entanglement="linear", reps=2)
+    terms = hamiltonian(n)
+    ground = exact_ground_energy(terms) if n <= 12 else None
+    theta = np.random.default_rng(7).uniform(-0.5, 0.5, size=ansatz.num_parameters)
+    print(f"{n} qubits, {ansatz.num_parameters} parameters, {len(terms)} Pauli terms, bond <= {max_bond}"
+          + (f"; exact ground energy {ground:+.6f}" if ground is not None else ""))
+    print("mps: step  energy  " + ("(energy - ground)" if ground is not None else "energy per site"))
+    for step in range(steps):
+        values, grads = sim.parameter_shift(ansatz, terms, theta[None, :], None, DEV, method="mps", max_bond=max_bond)
+        e = float(values[0])
+        print(f"  {step:3d}  {e:+.6f}  {e - ground if ground is not None else e / n:+.6f}")
+        theta = theta - lr * grads[0].cpu().numpy()
+    torch.cuda.synchronize()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--lr", type=float, default=0.2)
+    ap.add_argument("--qubits", type=int, default=N)
+    ap.add_argument("--mps", action="store_true", help="descend on matrix-product states (parameter_shift(method='mps')): any width up to 512")
+    ap.add_argument("--max-bond", type=int, default=16)
     a = ap.parse_args()
+    if a.mps:
+        return descend_mps(a.qubits, a.steps, a.lr, a.max_bond)
+    if a.qubits != N:
+        ap.error(f"--qubits {a.qubits} needs --mps: the exact simulator's descent below is written for {N} qubits")
     backend = StaticBackend.from_json(os.path.join(ROOT, "tests", "golden", "fake_lima_backend_props.json"))
     noise = sim.NoiseModel.from_backend(backend)
     ansatz = two_local(N, rotation_blocks=("ry",), entanglement_blocks="cx", entanglement=[(0, 1), (1, 2), (1, 3)], reps=2)

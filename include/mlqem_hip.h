@@ -2166,6 +2166,62 @@ int mlqem_mps_sample_f64(int64_t n_circuits, const int32_t* n_qubits, int64_t ci
 int mlqem_mps_sample_finish_f64(int64_t n_circuits, int64_t n_terms, int64_t shots, const int64_t* term_ptr, const double* coeff,
                                 const int32_t* term_sums, double* term_values, double* values, double* variance, mlqem_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Parameter binding for matrix-product states (one additive symbol, the ABI version is unchanged).  Templates are lowered ONCE
+ * (blackwater.sim.compile_mps_templates): op_ptr int64 [C + 1], ops [n_ops] and params [n_params] are those of mlqem_mps_run_f64
+ * with a template per circuit (the matrix of a parameterised record stands at the placeholder angle 0 and is not read), and
+ * pool_ptr int64 [C + 1] names template c's slice params[pool_ptr[c] .. pool_ptr[c + 1]).  mlqem_mps_bind_f64 writes, on the
+ * device, the batch that the lowering of the R = n_runs BOUND COPIES would have produced; mlqem_mps_run_f64, _run_folded_f64,
+ * _terms_f64, _finish_f64 and _sample_f64 then run on it unchanged.
+ * FACTOR PROGRAM.  Record j (global) owns the factors fac_ptr[j] .. fac_ptr[j + 1] (fac_ptr int64 [n_ops + 1]); none: the
+ * record is copied.  With factors (U1 and U2 records only) its matrix is F_k ... F_2 F_1, d x d with d = 2 (U1) or 4 (U2: over
+ * bit(lower site) + 2 bit(upper site), orientation 0).  fac int32 [n_fac][4] = (kind, slot, parameter, offset), fac_val float64
+ * [n_fac][2] = (scale, offset):
+ *   kind MLQEM_MPS_FACTOR_FIXED: the d x d matrix fpool[offset ..], row-major (re, im), 8 or 32 float64 (fpool float64 [n_fpool],
+ *     n_fpool >= 32: the padding the longest read needs) -- the host product of a maximal run of consecutive fixed gates;
+ *   kind MLQEM_SIM_OP_PRX / PRY / PRZ / PP / PRZZ: a PARAM factor on slot 0 (the lower site; the site of a U1 record), 1 (the
+ *     upper site) or 2 (the bond: PRZZ).
+ * RUNS.  runs int32 [R][4] = (template, theta row, shifted occurrence or -1, reserved) and shift float64 [R], as in
+ * mlqem_sim_run_bound_f64; theta float64 [n_rows][ld_theta].  An occurrence is a PARAM factor: template c owns the occurrences
+ * occ_ptr[c] .. occ_ptr[c + 1] (int64 [C + 1]), in circuit order, occ int32 [n_occ][2] = (record relative to op_ptr[c], factor
+ * inside the record); the run's third entry counts from occ_ptr[c], and one outside the template's occurrences is none.
+ * OUTPUT.  Run r gets the records out_ops[out_op_ptr[r] + k] = (kind, site, orientation, P) for the template's records k, with
+ * P = out_pool_ptr[r] + (the template's offset - pool_ptr[c]), and the slice of out_pool that starts at out_pool_ptr[r]
+ * (out_op_ptr, out_pool_ptr int64 [R]: the running sums of the templates' record and value counts, the caller's; n_out_pool
+ * counts 32 values of padding at the end, as `params` does).  max_records: the largest record count of a template that a run
+ * names (the launch's second grid dimension is sized by it; records past it are still reached).
+ * ARITHMETIC CONTRACT (tests/mps_bound_cases.bind_host follows it operation by operation).  phi = scale * theta[row][parameter]
+ * + offset, then + shift[r] if this factor is the run's shifted occurrence: a product and one or two sums, each rounded on its
+ * own (the file is compiled under `#pragma clang fp contract(off)`: no fma).  (co, si) = (cos, sin)(0.5 * phi) -- an exact product
+ * -- for PRX, PRY, PRZ, PRZZ and (cos, sin)(phi) for PP, as the fixed gates of blackwater/sim/program.py define them.  The
+ * factors' matrices: PRX [[co, -i si], [-i si, co]], PRY [[co, -si], [si, co]], PRZ diag(co - i si, co + i si), PP diag(1, co +
+ * i si) on the slot's bit of the row index; PRZZ the diagonal with co - i si where the two bits are equal and co + i si where
+ * they differ.  M = F_1 (a PARAM factor written out as its d x d matrix, zeros exact), then M <- F M for each further factor:
+ *   FIXED   (F M)[i][j] = sum over k = 0 .. d - 1, ascending, of F[i][k] M[k][j], the first product as it is, each further one
+ *           added to the sum;
+ *   PRX/PRY (G M)[i][j] = g[b][0] M[i0][j] + g[b][1] M[i1][j], b the slot's bit of i, i0 / i1 = i with that bit clear / set:
+ *           applied as its 2x2, never as a 4x4 with zeros;
+ *   diagonal kinds  (D M)[i][j] = D[i] M[i][j].
+ *   A complex product is (a.re b.re - a.im b.im, a.re b.im + a.im b.re), four products, then one difference and one sum; a sum
+ *   of complex numbers is one sum per part.  No contraction anywhere.
+ * Records without factors, and DEPOL1 / DEPOL2 records, are copied bit for bit.  No atomics, no cross-run data: a run's slice
+ * of out_pool and its rows of out_ops depend on (template, theta row, shift) alone -- the same alone, in any batch, under any
+ * split into calls and in a replayed graph.  Sixteen lanes form one record, lane e its entry e (csrc/mps_bind.hip says why).
+ * Every index read from a buffer is clamped (template, row, parameter, record and factor ranges, pool offsets: an offset is
+ * clamped to [0, n - 32] of its pool, so a matrix always fits): malformed input computes garbage, never reads or writes outside a
+ * buffer.  A negative size, n_params / n_fpool / n_out_pool < 32, a null or misaligned buffer (ops, fac, runs, out_ops: 16 B;
+ * float64 buffers: 8 B), n_templates / n_rows / ld_theta < 1 with runs: MLQEM_ERR_BAD_ARG; a count over 2^31 - 1:
+ * MLQEM_ERR_UNSUPPORTED; all before anything is launched.  n_runs == 0 or max_records == 0: MLQEM_OK, nothing is written.
+ * No host read: capturable, on one stream with the run that follows.
+ * ---------------------------------------------------------------------------------------------------- */
+#define MLQEM_MPS_FACTOR_FIXED 0
+int mlqem_mps_bind_f64(int64_t n_templates, const int64_t* op_ptr, const mlqem_sim_op* ops, int64_t n_ops, const double* params,
+                       int64_t n_params, const int64_t* pool_ptr, const int64_t* fac_ptr, const int32_t* fac, const double* fac_val,
+                       int64_t n_fac, const double* fpool, int64_t n_fpool, const int64_t* occ_ptr, const int32_t* occ, int64_t n_occ,
+                       const double* theta, int64_t n_rows, int64_t ld_theta, const int32_t* runs, const double* shift, int64_t n_runs,
+                       int64_t max_records, const int64_t* out_op_ptr, const int64_t* out_pool_ptr, mlqem_sim_op* out_ops,
+                       int64_t n_out_ops, double* out_pool, int64_t n_out_pool, mlqem_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

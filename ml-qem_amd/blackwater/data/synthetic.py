@@ -34,7 +34,22 @@ def clifford_tfim_circuit(nq: int, steps: int, kx: int, kz: int, two_q: str = "e
     return _tfim(nq, steps, int(kx) * math.pi / 2, int(kz) * math.pi / 2, two_q)
 
 
+def tfim_circuit_template(nq: int, steps: int, two_q: str = "cx"):
+    """The op sequence of :func:`tfim_circuit` as a ``blackwater.sim.Template`` with TWO parameters on its two ``rz`` angles:
+    theta[0] is the field rotation (``rz(theta[0] + pi)`` between the ``sx`` of every ``rx``), theta[1] the bond rotation.  The
+    offsets are those of ``tfim_circuit``, so ``bind_parameters([2 h dt, -2 J dt]).ops == tfim_circuit(nq, steps, J, h, dt, two_q).ops``
+    exactly.  Its two-qubit gates act on neighbours: the matrix-product-state path binds it at any width up to 512 qubits."""
+    from ..sim.template import Param, Template
+
+    return Template(nq, nq, _tfim_ops(nq, steps, Param(0), Param(1), two_q), [], 2)
+
+
 def _tfim(nq: int, steps: int, theta: float, phi: float, two_q: str) -> Circuit:
+    return Circuit(nq, nq, _tfim_ops(nq, steps, theta, phi, two_q))
+
+
+def _tfim_ops(nq: int, steps: int, theta, phi, two_q: str) -> List[CircuitOp]:
+    """``theta`` / ``phi``: floats, or ``Param``s (``theta + pi`` is then a ``Param`` with the offset pi)."""
     ops: List[CircuitOp] = []
     all_q = tuple(range(nq))
 
@@ -69,7 +84,7 @@ def _tfim(nq: int, steps: int, theta: float, phi: float, two_q: str) -> Circuit:
         ops.append(CircuitOp("barrier", all_q))
     ops.append(CircuitOp("barrier", all_q))
     ops.extend(CircuitOp("measure", (q,), (q,)) for q in all_q)
-    return Circuit(nq, nq, ops)
+    return ops
 
 
 def two_local(num_qubits: int, rotation_blocks=("ry",), entanglement_blocks="cz", entanglement: str = "full", reps: int = 3):

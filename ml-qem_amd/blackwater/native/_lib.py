@@ -298,6 +298,8 @@ SIGNATURES = {
     "mlqem_mps_sample_f64": (_I, [_L, _P, _L, _L, _L, _L, _L, _L, _L, _P, _S, _P, _S, _L, _L, _L, _L, _P, _P, _P, _P, _L, _P, _P, _L, _P, _P,
                                   _P, _L, _L, _L, _P, _P, _L, _P, _L, _U, _P, _P, _L, _P]),
     "mlqem_mps_sample_finish_f64": (_I, [_L, _L, _L, _P, _P, _P, _P, _P, _P, _P]),
+    "mlqem_mps_bind_f64": (_I, [_L, _P, _P, _L, _P, _L, _P, _P, _P, _P, _L, _P, _L, _P, _P, _L, _P, _L, _L, _P, _P, _L, _L, _P, _P, _P, _L,
+                                _P, _L, _P]),
 }
 
 _lib = None

@@ -3450,6 +3450,56 @@ def sim_shift_combine(v_plus, v_minus, occ_ptr, occ, scale, *, grad=None):
     return grad
 
 
+def mps_bind(op_ptr, ops, params, pool_ptr, fac_ptr, fac, fac_val, fpool, occ_ptr, occ, theta, runs, shift, max_records, out_op_ptr,
+             out_pool_ptr, out_ops, out_pool):
+    """Binds runs of templates lowered by ``blackwater.sim.compile_mps_templates`` (mlqem_mps_bind_f64): fills ``out_ops`` int32
+    [n_out_ops, 4] and ``out_pool`` float64 [>= 32] with the records and the parameter pool of the bound copies, for
+    :func:`sim_run_mps` to run, and returns them.
+
+    ``op_ptr`` int64 [C + 1], ``ops`` int32 [n_ops, 4], ``params`` float64 [>= 32], ``pool_ptr`` int64 [C + 1], ``fac_ptr`` int64
+    [n_ops + 1], ``fac`` int32 [n_fac, 4], ``fac_val`` float64 [n_fac, 2], ``fpool`` float64 [>= 32], ``occ_ptr`` int64 [C + 1],
+    ``occ`` int32 [n_occ, 2]: the lowered templates.  ``theta`` contiguous float64 [n_rows >= 1, ld >= 1]; ``runs`` int32 [R, 4]:
+    (template, theta row, shifted occurrence or -1, 0); ``shift`` float64 [R]; ``out_op_ptr`` / ``out_pool_ptr`` int64 [>= R]: where
+    a run's records and values go; ``max_records`` (a host int): the largest record count of a template.  Shapes, dtypes and
+    devices are checked here; the contents are the lowering's to guarantee (the kernel clamps every index).  Nothing here waits
+    for the device, reads a tensor or allocates: capturable.  There is no CPU path."""
+    for t, name, dtype, cols in ((ops, "ops", torch.int32, 4), (fac, "fac", torch.int32, 4), (runs, "runs", torch.int32, 4),
+                                 (out_ops, "out_ops", torch.int32, 4), (fac_val, "fac_val", torch.float64, 2), (occ, "occ", torch.int32, 2),
+                                 (theta, "theta", torch.float64, None)):
+        if not t.is_cuda:
+            raise _lib.NativeLibraryError(f"{name} must live on the GPU (got {t.device}); there is no CPU path")
+        if t.dtype != dtype or t.dim() != 2 or (cols is not None and t.shape[1] != cols) or not t.is_contiguous():
+            raise ValueError(f"mps_bind: want contiguous {dtype} {name} [., {cols or 'ld'}], got {tuple(t.shape)} {t.dtype}")
+    c, n_ops, n_fac, n_occ, n_runs = int(op_ptr.shape[0]) - 1, int(ops.shape[0]), int(fac.shape[0]), int(occ.shape[0]), int(runs.shape[0])
+    if theta.shape[0] < 1 or theta.shape[1] < 1 or c < 0 or int(max_records) < 0:
+        raise ValueError(f"mps_bind: theta is {tuple(theta.shape)}, want [n_rows >= 1, ld >= 1]; op_ptr has {c + 1} entries; max_records = "
+                         f"{max_records}")
+    _vec(op_ptr, "op_ptr", 1, torch.int64)
+    _vec(pool_ptr, "pool_ptr", c + 1, torch.int64)
+    _vec(fac_ptr, "fac_ptr", n_ops + 1, torch.int64)
+    _vec(occ_ptr, "occ_ptr", c + 1, torch.int64)
+    _vec(params, "params", SIM_PARAM_PAD, torch.float64)
+    _vec(fpool, "fpool", SIM_PARAM_PAD, torch.float64)
+    _vec(shift, "shift", n_runs, torch.float64)
+    _vec(out_op_ptr, "out_op_ptr", n_runs, torch.int64)
+    _vec(out_pool_ptr, "out_pool_ptr", n_runs, torch.int64)
+    _vec(out_pool, "out_pool", SIM_PARAM_PAD, torch.float64)
+    if fac_val.shape[0] < n_fac:
+        raise ValueError(f"mps_bind: fac_val has {int(fac_val.shape[0])} rows, fac {n_fac}")
+    dev = ops.device
+    if any(t.device != dev for t in (op_ptr, params, pool_ptr, fac_ptr, fac, fac_val, fpool, occ_ptr, occ, theta, runs, shift, out_op_ptr,
+                                     out_pool_ptr, out_ops, out_pool)):
+        raise ValueError(f"mps_bind: ops is on {dev}, another buffer is not")
+    code = _lib.load().mlqem_mps_bind_f64(
+        c, _p(op_ptr), _p(ops) if n_ops else None, n_ops, _p(params), int(params.shape[0]), _p(pool_ptr), _p(fac_ptr),
+        _p(fac) if n_fac else None, _p(fac_val) if n_fac else None, n_fac, _p(fpool), int(fpool.shape[0]), _p(occ_ptr),
+        _p(occ) if n_occ else None, n_occ, _p(theta), int(theta.shape[0]), int(theta.shape[1]), _p(runs), _p(shift), n_runs,
+        int(max_records), _p(out_op_ptr), _p(out_pool_ptr), _p(out_ops) if out_ops.shape[0] else None, int(out_ops.shape[0]),
+        _p(out_pool), int(out_pool.shape[0]), _stream())
+    _lib.check(code, "mlqem_mps_bind_f64")
+    return out_ops, out_pool
+
+
 CLIFFORD_MAX_QUBITS = 512   # MLQEM_CLIFFORD_MAX_QUBITS
 CLIFFORD_REG_QUBITS = 128   # MLQEM_CLIFFORD_REG_QUBITS: units of circuits up to here keep their Pauli words in registers
 CLIFFORD_PAD = 32           # entries of padding `pool` and `masks` end with

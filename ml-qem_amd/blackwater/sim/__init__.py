@@ -13,7 +13,9 @@ parameter vectors (``bound_expectation_values``), with exact gradients by the pa
 ``blackwater.sim.mps`` is the path for wide circuits that are NOT Clifford circuits: matrix-product states of bond at most 32 for
 circuits on a line (``compile_mps`` / ``run_mps`` / ``mps_expectation_values``; measurement shots from the same states:
 ``compile_mps_shots`` / ``run_mps_shots`` / ``sample_mps_expectation_values`` / ``mps_counts``), exact while the bonds fit and certified beyond, ideal
-and, by Pauli-insertion trajectories, under a depolarising + readout model."""
+and, by Pauli-insertion trajectories, under a depolarising + readout model.  Templates run there too: ``compile_mps_templates`` lowers
+an ansatz of up to 512 qubits once, ``run_mps_bound`` / ``bound_mps_expectation_values`` bind it on the device for every parameter row
+and ``parameter_shift(..., method="mps")`` gives its gradients."""
 from .program import (MAX_AMPS, MAX_QUBITS_DENSITY, MAX_QUBITS_VECTOR, SUPPORTED_GATES, WAVE_AMPS, NoiseModel, SimBatch,
                       compile_programs, measured_z)
 from .program import MAX_SHOTS, measurement_groups
@@ -30,6 +32,7 @@ from .bound import bound_expectation_values, parameter_shift, run_bound
 from .mps import (MAX_BOND, MAX_GROUPS_MPS, MAX_QUBITS_MPS, MPS_BUFFER_BYTES, MpsBatch, MpsResult, MpsShotsBatch, MpsShotsResult,
                   compile_mps, compile_mps_shots, is_line_circuit, mps_counts, mps_expectation_values, run_mps, run_mps_shots,
                   sample_mps_expectation_values)
+from .mps import MpsBoundBatch, MpsBoundRun, bound_mps_expectation_values, compile_mps_templates, run_mps_bound
 from .zne import (CubicExtrapolator, CxAmplifier, ExponentialExtrapolator, GlobalFoldingAmplifier, LinearExtrapolator, LocalFoldingAmplifier,
                   PolynomialExtrapolator, QuadraticExtrapolator, QuarticExtrapolator, RichardsonExtrapolator, Schedules,
                   TwoQubitAmplifier, ZNEStrategy, build_clifford_schedules, build_mps_schedules, build_schedules, fold_circuit,
@@ -49,4 +52,5 @@ __all__ = ["MAX_AMPS", "MAX_QUBITS_DENSITY", "MAX_QUBITS_VECTOR", "SUPPORTED_GAT
            "MAX_BOND", "MAX_QUBITS_MPS", "MPS_BUFFER_BYTES", "MpsBatch", "MpsResult", "compile_mps", "is_line_circuit",
            "mps_expectation_values", "run_mps", "MAX_GROUPS_MPS", "MpsShotsBatch", "MpsShotsResult", "compile_mps_shots", "mps_counts",
            "run_mps_shots", "sample_mps_expectation_values", "build_mps_schedules", "run_mps_folded",
-           "BoundBatch", "Param", "Template", "compile_templates", "bound_expectation_values", "parameter_shift", "run_bound"]
+           "BoundBatch", "Param", "Template", "compile_templates", "bound_expectation_values", "parameter_shift", "run_bound",
+           "MpsBoundBatch", "MpsBoundRun", "bound_mps_expectation_values", "compile_mps_templates", "run_mps_bound"]

@@ -142,8 +142,15 @@ def shift_runs(batch: BoundBatch, pair: np.ndarray) -> Tuple[np.ndarray, np.ndar
 
 
 def parameter_shift(template, observable, parameter_values, noise: Optional[NoiseModel] = None, device="cuda",
-                    buffer_bytes: int = BOUND_BUFFER_BYTES):
+                    buffer_bytes: Optional[int] = None, method: str = "exact", trajectories: Optional[int] = None, max_bond: Optional[int] = None,
+                    cutoff: Optional[float] = None, seed: int = 0, run_keys=None):
     """Values and exact gradients by the parameter-shift rule: ``(values [B], gradients [B, P])``, float64 tensors on ``device``.
+
+    ``method="exact"`` (the default) runs the exact simulator, as described below.  ``method="mps"`` runs the same rule on
+    matrix-product states (:func:`blackwater.sim.mps.mps_parameter_shift`: templates of up to 512 qubits whose two-qubit gates
+    act on neighbours; ``max_bond``, ``cutoff``, and under ``noise`` ``trajectories``, ``seed`` and one run key per ROW:
+    every run of a row draws the row's Pauli insertions, so the rule is exact for that trajectory set).  Those options are
+    refused under ``"exact"``.
 
     Every parameterised gate is a rotation exp(-i phi G / 2) with G^2 = 1 (``p`` up to a phase), so ``d<O>/d phi = (<O>(phi + pi/2)
     - <O>(phi - pi/2)) / 2`` exactly, under noise too (the noise does not depend on the angle), and a parameter's derivative is the
@@ -154,6 +161,17 @@ def parameter_shift(template, observable, parameter_values, noise: Optional[Nois
 
     from ..native import ops
 
+    if method == "mps":
+        from .mps import DEFAULT_CUTOFF, MAX_BOND, mps_parameter_shift
+
+        return mps_parameter_shift(template, observable, parameter_values, noise, trajectories, MAX_BOND if max_bond is None else max_bond,
+                                   DEFAULT_CUTOFF if cutoff is None else cutoff, seed, run_keys, device, buffer_bytes)
+    if method != "exact":
+        raise ValueError(f"parameter_shift: method = {method!r}, want 'exact' or 'mps'")
+    if trajectories is not None or max_bond is not None or cutoff is not None or run_keys is not None:
+        raise ValueError("parameter_shift: trajectories, max_bond, cutoff and run_keys belong to method='mps'; the exact simulator "
+                         "takes none of them")
+    buffer_bytes = BOUND_BUFFER_BYTES if buffer_bytes is None else buffer_bytes
     tpls, obss, pair, theta, n_rows = _pairs(template, observable, parameter_values, "parameter_shift")
     batch = compile_templates(tpls, obss, noise)
     runs, shift, groups = shift_runs(batch, pair)

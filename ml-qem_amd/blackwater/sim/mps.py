@@ -127,64 +127,141 @@ def _check_cutoff(cutoff: Any, who: str) -> float:
     return float(cutoff)
 
 
-def compile_mps(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None,
-                trajectories: Optional[int] = None, max_bond: int = MAX_BOND, cutoff: float = DEFAULT_CUTOFF) -> MpsBatch:
-    """Lowers ``circuits`` with one observable each to one :class:`MpsBatch`.  Site = qubit index.
+FACTOR_FIXED = 0   # MLQEM_MPS_FACTOR_FIXED; a PARAM factor carries its MLQEM_SIM_OP_P* kind (12 .. 16)
+SLOT_LOWER, SLOT_UPPER, SLOT_BOND = 0, 1, 2   # what a PARAM factor of a U2 record acts on (a U1 record: SLOT_LOWER)
 
-    ``noise=None`` (ideal): one ``U2`` record per bond visit -- a run of gates confined to one bond (its one-qubit gates included)
-    is multiplied into a single 4x4 matrix over bit(lower) + 2 bit(upper) -- and one ``U1`` record per qubit whose last one-qubit
-    gates no bond absorbed.  With ``noise`` and ``trajectories``: nothing is fused; one ``U1`` record per one-qubit gate, one ``U2``
-    per two-qubit gate (the gate's own matrix and its orientation), a ``U2`` for a coherent error, and a ``DEPOL1`` / ``DEPOL2``
-    record per depolarising op; readout noise of measured qubits goes into the ``readout`` table.
 
-    Raises ``ValueError`` naming the offender for what ``compile_programs`` refuses (unknown gates, parameter counts, qubits out of
-    range or used after their measurement, non-finite angles, malformed terms) and for: a two-qubit gate on qubits that are no
-    neighbours, ``max_bond`` outside 1 .. 32, ``noise`` without ``trajectories`` or the reverse, a model with thermal relaxation,
-    readout noise together with an X / Y term, a circuit over 512 qubits."""
-    circuits, observables = list(circuits), list(observables)
-    max_bond, cutoff = _check_bond(max_bond, "compile_mps"), _check_cutoff(cutoff, "compile_mps")
-    if trajectories is not None:
-        trajectories = check_trajectories(trajectories, "compile_mps")
-        if noise is None:
-            raise ValueError("compile_mps: trajectories without a noise model (a noiseless circuit has one trajectory: lower it "
-                             "without trajectories)")
-    elif noise is not None:
-        raise ValueError("compile_mps: noise without trajectories (the MPS path unravels a noise model into Pauli-insertion "
-                         "trajectories: pass trajectories=T)")
-    if len(circuits) != len(observables):
-        raise ValueError(f"compile_mps: {len(circuits)} circuits but {len(observables)} observables")
-    noisy = noise is not None
-    relaxation_after, coherent_after = getattr(noise, "relaxation_after", None), getattr(noise, "coherent_after", None)
-    ops, params, op_ptr = [], [], [0]
-    term_circ, term_off, letters, coeffs, term_ptr = [], [], [], [], [0]
-    site_ptr, readout, n_noise_all, abs_coeff, measured_all, n_qubits = [0], [], [], [], [], []
-    gate_ptr, gate_name, gate_record, gate_noise, gate_noise_len = [0], [], [], [], []
-    name_id = {g: j for j, g in enumerate(SUPPORTED_GATES)}
+class _Chain:
+    """The matrix of one record as the product F_k ... F_2 F_1: a FIXED factor is a numpy matrix (consecutive fixed gates are
+    multiplied into one, by the operations ``compile_mps`` has always done), a PARAM factor the list [kind, slot, Param,
+    occurrence].  A chain without a PARAM factor has exactly one factor: the record's host matrix."""
 
-    def emit(kind, site, orient, values):
-        ops.append((kind, site, orient, len(params)))
-        params.extend(values)
+    __slots__ = ("factors", "trivial", "gates")
 
-    def emit_matrix(kind, site, orient, m):
+    def __init__(self, first: Optional[np.ndarray] = None, trivial: bool = False, gates: int = 1):
+        self.factors: List[Any] = [] if first is None else [first]
+        self.trivial = trivial   # the only factor is the identity of a bond that absorbed no pending gate
+        self.gates = gates if first is not None else 0   # gates multiplied into the record (what its rounding grows with)
+
+    def fixed(self, m: np.ndarray) -> None:
+        if self.factors and isinstance(self.factors[-1], np.ndarray):
+            self.factors[-1] = m @ self.factors[-1]
+        else:
+            self.factors.append(m)
+        self.trivial = False
+        self.gates += 1
+
+    def param(self, kind: int, slot: int, par: Any, occ: int) -> None:
+        if self.trivial:
+            self.factors, self.trivial = [], False
+        self.factors.append([kind, slot, par, occ])
+        self.gates += 1
+
+    @property
+    def parameterised(self) -> bool:
+        return any(not isinstance(f, np.ndarray) for f in self.factors)
+
+    def placeholder(self, dim: int) -> np.ndarray:
+        """The product with every free parameter at 0."""
+        m = np.eye(dim, dtype=complex)
+        for f in self.factors:
+            m = (f if isinstance(f, np.ndarray) else param_matrix(f[0], f[1], dim, f[2].value(_Zeros()))) @ m
+        return m
+
+
+class _Zeros:
+    def __getitem__(self, index):
+        return 0.0
+
+
+_PARAM_NAME = {12: "rx", 13: "ry", 14: "rz", 15: "p", 16: "rzz"}   # MLQEM_SIM_OP_PRX .. PRZZ
+
+
+def param_matrix(kind: int, slot: int, dim: int, phi: float) -> np.ndarray:
+    """The matrix of a PARAM factor at the angle ``phi``, from ``program``'s tables: 2x2 (``dim`` 2), or 4x4 over bit(lower) + 2
+    bit(upper) with the gate on ``slot``."""
+    if kind == 16:
+        return _matrix4("rzz", (phi,))
+    g = _matrix2(_PARAM_NAME[kind], (phi,))
+    if dim == 2:
+        return g
+    return np.kron(np.eye(2), g) if slot == SLOT_LOWER else np.kron(g, np.eye(2))
+
+
+class _Lowering:
+    """The per-circuit loop of :func:`compile_mps`, shared with :func:`compile_mps_templates`: every check, refusal, fusion
+    decision and noise record of the MPS lowering lives here and nowhere else.  ``add`` lowers one circuit; with ``free`` (the
+    ``Param`` of every op of a template, or None) it also keeps, for every record whose matrix depends on a parameter, the factor
+    program of the record and the occurrences of the parameters."""
+
+    def __init__(self, who, circuits, observables, noise, trajectories, max_bond, cutoff):
+        self.who = who
+        self.circuits, self.observables = list(circuits), list(observables)
+        self.max_bond, self.cutoff = _check_bond(max_bond, who), _check_cutoff(cutoff, who)
+        if trajectories is not None:
+            trajectories = check_trajectories(trajectories, who)
+            if noise is None:
+                raise ValueError(f"{who}: trajectories without a noise model (a noiseless circuit has one trajectory: lower it "
+                                 "without trajectories)")
+        elif noise is not None:
+            raise ValueError(f"{who}: noise without trajectories (the MPS path unravels a noise model into Pauli-insertion "
+                             "trajectories: pass trajectories=T)")
+        if len(self.circuits) != len(self.observables):
+            raise ValueError(f"{who}: {len(self.circuits)} circuits but {len(self.observables)} observables")
+        self.noise, self.trajectories, self.noisy = noise, trajectories, noise is not None
+        self.ops, self.params, self.op_ptr = [], [], [0]
+        self.term_circ, self.term_off, self.letters, self.coeffs, self.term_ptr = [], [], [], [], [0]
+        self.site_ptr, self.readout, self.n_noise_all, self.abs_coeff, self.measured_all, self.n_qubits = [0], [], [], [], [], []
+        self.gate_ptr, self.gate_name, self.gate_record, self.gate_noise, self.gate_noise_len = [0], [], [], [], []
+        self.name_id = {g: j for j, g in enumerate(SUPPORTED_GATES)}
+        # the factor programs (templates): global record index -> its chain; the occurrences [record, factor, parameter, scale] with
+        # the record relative to its circuit's first, in circuit order; pool_ptr: a circuit's slice of ``params``
+        self.chains: Dict[int, _Chain] = {}
+        self.occ: List[List[Any]] = []
+        self.occ_ptr, self.pool_ptr = [0], [0]
+
+    def emit(self, kind, site, orient, values):
+        self.ops.append((kind, site, orient, len(self.params)))
+        self.params.extend(values)
+
+    def emit_matrix(self, kind, site, orient, m, chain: Optional[_Chain] = None):
+        if chain is not None and chain.parameterised:
+            self.chains[len(self.ops)] = chain
+            for j, f in enumerate(chain.factors):
+                if not isinstance(f, np.ndarray):
+                    self.occ[f[3]][0], self.occ[f[3]][1] = len(self.ops) - self.op_ptr[-1], j
         flat = []
         for e in np.asarray(m, dtype=complex).reshape(-1):
             flat += [float(e.real), float(e.imag)]
-        emit(kind, site, orient, flat)
+        self.emit(kind, site, orient, flat)
 
-    for k, (obj, obs) in enumerate(zip(circuits, observables)):
-        circ = Circuit.from_any(obj)
+    def emit_chain(self, kind, site, chain: _Chain):
+        dim = 4 if kind == OP_MPS_U2 else 2
+        self.emit_matrix(kind, site, 0, chain.placeholder(dim) if chain.parameterised else chain.factors[0], chain)
+
+    def add(self, k: int, circ: Circuit, obs: Any, free: Optional[Sequence[Any]] = None) -> None:
+        from .template import PARAM_KIND
+
+        noise, noisy = self.noise, self.noisy
+        relaxation_after, coherent_after = getattr(noise, "relaxation_after", None), getattr(noise, "coherent_after", None)
+        ops, op_ptr = self.ops, self.op_ptr
+        emit, emit_matrix = self.emit, self.emit_matrix
         where = f"circuit {k}"
         n = circ.num_qubits
         if not 1 <= n <= MAX_QUBITS_MPS:
             raise ValueError(f"{where}: {n} qubits; the MPS path takes 1 .. {MAX_QUBITS_MPS}")
         measured: Dict[int, int] = {}
         done = set()
-        pending: Dict[int, np.ndarray] = {}    # ideal lowering: one-qubit matrices no record has absorbed yet
-        open_bond: Dict[int, np.ndarray] = {}  # ideal lowering: lower site -> the 4x4 matrix accumulated on its bond
+        pending: Dict[int, _Chain] = {}    # ideal lowering: the one-qubit gates no record has absorbed yet
+        open_bond: Dict[int, _Chain] = {}  # ideal lowering: lower site -> the gates accumulated on its bond
         n_noise = 0
 
         def flush(site):
-            emit_matrix(OP_MPS_U2, site, 0, open_bond.pop(site))
+            self.emit_chain(OP_MPS_U2, site, open_bond.pop(site))
+
+        def occurrence(par):
+            self.occ.append([-1, -1, par.index, par.scale])
+            return len(self.occ) - 1
 
         for i, op in enumerate(circ.ops):
             name = op.name
@@ -210,6 +287,7 @@ def compile_mps(circuits: Sequence[Any], observables: Sequence[Any], noise: Opti
             p = tuple(float(v) for v in op.params)
             if not all(math.isfinite(v) for v in p):
                 raise ValueError(f"{where}: op {i} ({name}) has the non-finite angle {p!r}")
+            par = free[i] if free is not None else None   # the gate's free parameter: its matrix is a PARAM factor
             first, rec, noi, noi_len = op_ptr[-1], -1, -1, 0
             if width == 2:
                 q0, q1 = op.qubits
@@ -222,30 +300,46 @@ def compile_mps(circuits: Sequence[Any], observables: Sequence[Any], noise: Opti
                 m = _matrix4(name, p)
                 if noisy:
                     rec = len(ops) - first
-                    emit_matrix(OP_MPS_U2, lower, orient, m)
+                    chain = None
+                    if par is not None:
+                        chain = _Chain()
+                        chain.param(PARAM_KIND[name], SLOT_BOND, par, occurrence(par))
+                    emit_matrix(OP_MPS_U2, lower, orient, m, chain)
                 else:
                     for other in (lower - 1, lower + 1):
                         if other in open_bond:
                             flush(other)
-                    m = _to_lower_basis(m, orient)
-                    before = open_bond.get(lower)
-                    if before is None:
-                        before = np.kron(pending.pop(lower + 1, np.eye(2)), pending.pop(lower, np.eye(2))).astype(complex)
-                    open_bond[lower] = m @ before
+                    chain = open_bond.get(lower)
+                    if chain is None:
+                        chain = open_bond[lower] = self._open(pending.pop(lower + 1, None), pending.pop(lower, None))
+                    if par is None:
+                        chain.fixed(_to_lower_basis(m, orient))
+                    else:
+                        chain.param(PARAM_KIND[name], SLOT_BOND, par, occurrence(par))
             else:
                 q0 = op.qubits[0]
                 m = _matrix2(name, p)
                 if m is not None:
                     if noisy:
                         rec = len(ops) - first
-                        emit_matrix(OP_MPS_U1, q0, 0, m)
+                        chain = None
+                        if par is not None:
+                            chain = _Chain()
+                            chain.param(PARAM_KIND[name], SLOT_LOWER, par, occurrence(par))
+                        emit_matrix(OP_MPS_U1, q0, 0, m, chain)
                     else:
                         site = q0 if q0 in open_bond else q0 - 1 if q0 - 1 in open_bond else None
                         if site is None:
-                            pending[q0] = m @ pending[q0] if q0 in pending else m
+                            if par is not None:
+                                pending.setdefault(q0, _Chain()).param(PARAM_KIND[name], SLOT_LOWER, par, occurrence(par))
+                            elif q0 in pending:
+                                pending[q0].fixed(m)
+                            else:
+                                pending[q0] = _Chain(m)
+                        elif par is not None:
+                            open_bond[site].param(PARAM_KIND[name], SLOT_LOWER if site == q0 else SLOT_UPPER, par, occurrence(par))
                         else:
-                            full = np.kron(np.eye(2), m) if site == q0 else np.kron(m, np.eye(2))
-                            open_bond[site] = full @ open_bond[site]
+                            open_bond[site].fixed(np.kron(np.eye(2), m) if site == q0 else np.kron(m, np.eye(2)))
             if noisy:
                 reg = tuple(circ.qubit_reg_index[q] for q in op.qubits)
                 lam = noise.after_gate(i, name, reg)
@@ -270,14 +364,14 @@ def compile_mps(circuits: Sequence[Any], observables: Sequence[Any], noise: Opti
                     else:
                         emit(OP_MPS_DEPOL1, op.qubits[0], 0, [float(lam)])
                     n_noise += 1
-                gate_name.append(name_id[name])
-                gate_record.append(rec)
-                gate_noise.append(noi)
-                gate_noise_len.append(noi_len)
+                self.gate_name.append(self.name_id[name])
+                self.gate_record.append(rec)
+                self.gate_noise.append(noi)
+                self.gate_noise_len.append(noi_len)
         for site in sorted(open_bond):
             flush(site)
         for q in sorted(pending):
-            emit_matrix(OP_MPS_U1, q, 0, pending[q])
+            self.emit_chain(OP_MPS_U1, q, pending[q])
 
         rows, cs, has_xy = _lower_terms(obs, n, where)
         table = [[1.0, 0.0] for _ in range(n)]
@@ -293,35 +387,155 @@ def compile_mps(circuits: Sequence[Any], observables: Sequence[Any], noise: Opti
                 p01, p10 = float(pr[0]), float(pr[1])
                 table[q] = [1.0 - p01 - p10, p01 - p10]
         for xm, zm, _, _ in rows:
-            term_circ.append(k)
-            term_off.append(len(letters))
-            letters += [(1 if xm >> q & 1 else 0) * (2 if zm >> q & 1 else 1) + (3 if zm >> q & 1 and not xm >> q & 1 else 0)
-                        for q in range(n)]
-        coeffs += cs
-        term_ptr.append(len(term_circ))
-        readout += table
-        site_ptr.append(len(readout))
+            self.term_circ.append(k)
+            self.term_off.append(len(self.letters))
+            self.letters += [(1 if xm >> q & 1 else 0) * (2 if zm >> q & 1 else 1) + (3 if zm >> q & 1 and not xm >> q & 1 else 0)
+                             for q in range(n)]
+        self.coeffs += cs
+        self.term_ptr.append(len(self.term_circ))
+        self.readout += table
+        self.site_ptr.append(len(self.readout))
         op_ptr.append(len(ops))
-        n_noise_all.append(n_noise)
-        abs_coeff.append(float(sum(abs(c) for c in cs)))
-        measured_all.append(measured)
-        n_qubits.append(n)
-        gate_ptr.append(len(gate_record))
+        self.n_noise_all.append(n_noise)
+        self.abs_coeff.append(float(sum(abs(c) for c in cs)))
+        self.measured_all.append(measured)
+        self.n_qubits.append(n)
+        self.gate_ptr.append(len(self.gate_record))
+        self.occ_ptr.append(len(self.occ))
+        self.pool_ptr.append(len(self.params))
 
-    if len(params) + PARAM_PAD > 2 ** 31 - 1:
-        raise ValueError(f"compile_mps: {len(params)} gate parameters exceed the 2^31 - 1 a record can address; split the batch")
-    return MpsBatch(
-        n_qubits=np.asarray(n_qubits, dtype=np.int32), op_ptr=np.asarray(op_ptr, dtype=np.int64),
-        ops=np.asarray(ops, dtype=np.int32).reshape(-1, 4), params=np.asarray(params + [0.0] * PARAM_PAD, dtype=np.float64),
-        term_ptr=np.asarray(term_ptr, dtype=np.int64), term_circ=np.asarray(term_circ, dtype=np.int32),
-        term_off=np.asarray(term_off, dtype=np.int64), letters=np.asarray(letters + [0], dtype=np.uint8),
-        coeff=np.asarray(coeffs, dtype=np.float64), site_ptr=np.asarray(site_ptr, dtype=np.int64),
-        readout=np.asarray(readout + [[1.0, 0.0]], dtype=np.float64).reshape(-1, 2), max_bond=max_bond, cutoff=cutoff,
-        trajectories=trajectories, n_noise=n_noise_all, abs_coeff=abs_coeff, measured=measured_all,
-        gate_ptr=np.asarray(gate_ptr, dtype=np.int64) if noisy else None, gate_name=np.asarray(gate_name, dtype=np.int16) if noisy else None,
-        gate_record=np.asarray(gate_record, dtype=np.int32) if noisy else None,
-        gate_noise=np.asarray(gate_noise, dtype=np.int32) if noisy else None,
-        gate_noise_len=np.asarray(gate_noise_len, dtype=np.int32) if noisy else None)
+    @staticmethod
+    def _open(upper: Optional[_Chain], lower: Optional[_Chain]) -> _Chain:
+        """The chain of a bond that opens: the pending one-qubit gates of its two sites.  Fixed ones enter as their ``kron``; a
+        pending PARAM factor moves onto its slot, the fixed factors around it as ``kron`` with the identity (lower site first: the
+        two sites commute)."""
+        if not (upper is not None and upper.parameterised) and not (lower is not None and lower.parameterised):
+            first = np.kron(upper.factors[0] if upper is not None else np.eye(2), lower.factors[0] if lower is not None else np.eye(2))
+            return _Chain(first.astype(complex), trivial=upper is None and lower is None,
+                          gates=sum(ch.gates for ch in (upper, lower) if ch is not None))
+        chain = _Chain()
+        for src, slot in ((lower, SLOT_LOWER), (upper, SLOT_UPPER)):
+            for f in (src.factors if src is not None else ()):
+                if isinstance(f, np.ndarray):
+                    chain.fixed((np.kron(np.eye(2), f) if slot == SLOT_LOWER else np.kron(f, np.eye(2))).astype(complex))
+                else:
+                    f[1] = slot
+                    chain.factors.append(f)
+        chain.gates = sum(ch.gates for ch in (upper, lower) if ch is not None)
+        return chain
+
+    def fields(self) -> Dict[str, Any]:
+        """The fields of the :class:`MpsBatch`."""
+        noisy, params = self.noisy, self.params
+        if len(params) + PARAM_PAD > 2 ** 31 - 1:
+            raise ValueError(f"{self.who}: {len(params)} gate parameters exceed the 2^31 - 1 a record can address; split the batch")
+        return dict(
+            n_qubits=np.asarray(self.n_qubits, dtype=np.int32), op_ptr=np.asarray(self.op_ptr, dtype=np.int64),
+            ops=np.asarray(self.ops, dtype=np.int32).reshape(-1, 4), params=np.asarray(params + [0.0] * PARAM_PAD, dtype=np.float64),
+            term_ptr=np.asarray(self.term_ptr, dtype=np.int64), term_circ=np.asarray(self.term_circ, dtype=np.int32),
+            term_off=np.asarray(self.term_off, dtype=np.int64), letters=np.asarray(self.letters + [0], dtype=np.uint8),
+            coeff=np.asarray(self.coeffs, dtype=np.float64), site_ptr=np.asarray(self.site_ptr, dtype=np.int64),
+            readout=np.asarray(self.readout + [[1.0, 0.0]], dtype=np.float64).reshape(-1, 2), max_bond=self.max_bond, cutoff=self.cutoff,
+            trajectories=self.trajectories, n_noise=self.n_noise_all, abs_coeff=self.abs_coeff, measured=self.measured_all,
+            gate_ptr=np.asarray(self.gate_ptr, dtype=np.int64) if noisy else None,
+            gate_name=np.asarray(self.gate_name, dtype=np.int16) if noisy else None,
+            gate_record=np.asarray(self.gate_record, dtype=np.int32) if noisy else None,
+            gate_noise=np.asarray(self.gate_noise, dtype=np.int32) if noisy else None,
+            gate_noise_len=np.asarray(self.gate_noise_len, dtype=np.int32) if noisy else None)
+
+
+def compile_mps(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None,
+                trajectories: Optional[int] = None, max_bond: int = MAX_BOND, cutoff: float = DEFAULT_CUTOFF) -> MpsBatch:
+    """Lowers ``circuits`` with one observable each to one :class:`MpsBatch`.  Site = qubit index.
+
+    ``noise=None`` (ideal): one ``U2`` record per bond visit -- a run of gates confined to one bond (its one-qubit gates included)
+    is multiplied into a single 4x4 matrix over bit(lower) + 2 bit(upper) -- and one ``U1`` record per qubit whose last one-qubit
+    gates no bond absorbed.  With ``noise`` and ``trajectories``: nothing is fused; one ``U1`` record per one-qubit gate, one ``U2``
+    per two-qubit gate (the gate's own matrix and its orientation), a ``U2`` for a coherent error, and a ``DEPOL1`` / ``DEPOL2``
+    record per depolarising op; readout noise of measured qubits goes into the ``readout`` table.
+
+    Raises ``ValueError`` naming the offender for what ``compile_programs`` refuses (unknown gates, parameter counts, qubits out of
+    range or used after their measurement, non-finite angles, malformed terms) and for: a two-qubit gate on qubits that are no
+    neighbours, ``max_bond`` outside 1 .. 32, ``noise`` without ``trajectories`` or the reverse, a model with thermal relaxation,
+    readout noise together with an X / Y term, a circuit over 512 qubits."""
+    low = _Lowering("compile_mps", circuits, observables, noise, trajectories, max_bond, cutoff)
+    for k, (obj, obs) in enumerate(zip(low.circuits, low.observables)):
+        low.add(k, Circuit.from_any(obj), obs)
+    return MpsBatch(**low.fields())
+
+
+@dataclass
+class MpsBoundBatch(MpsBatch):
+    """Templates lowered for ``mlqem_mps_bind_f64``: the arrays of an :class:`MpsBatch` (a template per "circuit", the matrices of
+    parameterised records at the placeholder angle 0), the factor programs of the parameterised records and what the host knows
+    about the parameters."""
+
+    pool_ptr: Optional[np.ndarray] = None     # int64 [C + 1]: template c owns params[pool_ptr[c] .. pool_ptr[c + 1])
+    # the factor CSR over the RECORDS: record j owns factors fac_ptr[j] .. fac_ptr[j + 1] (none: its host matrix is copied)
+    fac_ptr: Optional[np.ndarray] = None      # int64 [n_ops + 1]
+    fac: Optional[np.ndarray] = None          # int32 [n_fac + 1, 4]: kind (0 FIXED, 12 .. 16 PRX PRY PRZ PP PRZZ), slot, parameter, offset into fpool
+    fac_val: Optional[np.ndarray] = None      # float64 [n_fac + 1, 2]: (scale, offset) of a PARAM factor
+    fpool: Optional[np.ndarray] = None        # float64 [n + 32]: the FIXED factors, 32 (U2) or 8 (U1) float64 each, row-major (re, im)
+    rec_gates: Optional[np.ndarray] = None    # int32 [n_ops]: the gates multiplied into a parameterised record (0: a copied record)
+    num_parameters: Optional[np.ndarray] = None   # int32 [C]: the length of a parameter row of template c
+    # the OCCURRENCES: every PARAM factor in circuit order -- what a parameter-shift gradient shifts
+    occ_ptr: Optional[np.ndarray] = None      # int64 [C + 1]
+    occ: Optional[np.ndarray] = None          # int32 [n_occ + 1, 2]: (record relative to op_ptr[c], factor inside the record)
+    occ_param: Optional[np.ndarray] = None    # int32 [n_occ]
+    occ_scale: Optional[np.ndarray] = None    # float64 [n_occ]
+
+
+def compile_mps_templates(templates: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None,
+                          trajectories: Optional[int] = None, max_bond: int = MAX_BOND, cutoff: float = DEFAULT_CUTOFF) -> MpsBoundBatch:
+    """Lowers ``templates`` (anything ``Template.from_any`` takes) with one observable each ONCE, by the rules of
+    :func:`compile_mps` (the same loop: its refusals, caps, fusion decisions and noise records; the free angles stand at 0 where
+    a rule wants a number, and no rule looks at an angle, so the records' kinds, sites, orientations and order are those of every
+    bound copy).  A record whose matrix depends on a parameter also gets its FACTOR PROGRAM: the matrix is F_k ... F_2 F_1 with
+    FIXED factors (the host product of a maximal run of consecutive fixed gates, the ``kron`` of the pending one-qubit matrices a
+    bond absorbs included) and PARAM factors (kind, slot, parameter, scale, offset); ``mlqem_mps_bind_f64`` forms it per run on
+    the device.  The noisy lowering fuses nothing: a parameterised record there has exactly one PARAM factor.  A template without
+    parameters lowers to the arrays ``compile_mps`` gives."""
+    from .template import Template
+
+    templates = [Template.from_any(t) for t in templates]
+    low = _Lowering("compile_mps_templates", templates, observables, noise, trajectories, max_bond, cutoff)
+    for k, (t, obs) in enumerate(zip(templates, low.observables)):
+        low.add(k, t.placeholder(), obs, [_free_parameter(op) for op in t.ops])
+    fields = low.fields()
+    n_ops = int(fields["ops"].shape[0])
+    fac_ptr, fac, fac_val, fpool = [0], [], [], []
+    for j in range(n_ops):
+        chain = low.chains.get(j)
+        for f in (chain.factors if chain is not None else ()):
+            if isinstance(f, np.ndarray):
+                fac.append((FACTOR_FIXED, 0, 0, len(fpool)))
+                fac_val.append((0.0, 0.0))
+                for e in f.reshape(-1):
+                    fpool += [float(e.real), float(e.imag)]
+            else:
+                kind, slot, par, _ = f
+                fac.append((kind, slot, par.index, 0))
+                fac_val.append((par.scale, par.offset))
+        fac_ptr.append(len(fac))
+    if len(fpool) + PARAM_PAD > 2 ** 31 - 1 or len(fac) > 2 ** 31 - 2:
+        raise ValueError("compile_mps_templates: the factor programs exceed the 2^31 - 1 entries a record can address; split the batch")
+    occ = low.occ
+    return MpsBoundBatch(
+        **fields, pool_ptr=np.asarray(low.pool_ptr, dtype=np.int64), fac_ptr=np.asarray(fac_ptr, dtype=np.int64),
+        fac=np.asarray(fac + [(0, 0, 0, 0)], dtype=np.int32).reshape(-1, 4),
+        fac_val=np.asarray(fac_val + [(0.0, 0.0)], dtype=np.float64).reshape(-1, 2),
+        fpool=np.asarray(fpool + [0.0] * PARAM_PAD, dtype=np.float64),
+        rec_gates=np.asarray([low.chains[j].gates if j in low.chains else 0 for j in range(n_ops)], dtype=np.int32),
+        num_parameters=np.asarray([t.num_parameters for t in templates], dtype=np.int32),
+        occ_ptr=np.asarray(low.occ_ptr, dtype=np.int64),
+        occ=np.asarray([(o[0], o[1]) for o in occ] + [(-1, -1)], dtype=np.int32).reshape(-1, 2),
+        occ_param=np.asarray([o[2] for o in occ], dtype=np.int32), occ_scale=np.asarray([o[3] for o in occ], dtype=np.float64))
+
+
+def _free_parameter(op) -> Any:
+    from .template import Param
+
+    return op.params[0] if op.params and isinstance(op.params[0], Param) else None
 
 
 @dataclass
@@ -426,8 +640,296 @@ def mps_expectation_values(circuits: Sequence[Any], observables: Sequence[Any], 
     return run_mps(compile_mps(circuits, observables, noise, trajectories, max_bond, cutoff), seed, run_keys, device)
 
 
+# ---- templates: bound on the device ---------------------------------------------------------------------------------------------------
+MPS_POOL_ENTRIES = 2 ** 31 - 1 - PARAM_PAD   # float64 values of bound records one launch can address
+
+
+class _RunWidths:
+    """What :func:`_mps_chunks` reads of a batch, for the runs of templates."""
+
+    def __init__(self, n_qubits, max_bond):
+        self.n_qubits, self.max_bond = n_qubits, max_bond
+
+    def __len__(self):
+        return int(self.n_qubits.shape[0])
+
+
+class MpsBoundRun:
+    """The runs ``(template, theta row, shifted occurrence or -1)`` of a batch lowered by :func:`compile_mps_templates`, prepared
+    for the device: every table is uploaded and every buffer allocated here, so that :meth:`launch` only enqueues kernels (per
+    chunk ``mlqem_mps_bind_f64``, ``mlqem_mps_run_f64`` and ``mlqem_mps_terms_f64``, then ``mlqem_mps_finish_f64``) on the current
+    stream and can be captured in a graph and replayed.  :func:`run_mps_bound` is the one-call form."""
+
+    def __init__(self, batch: "MpsBoundBatch", theta, runs=None, shift=None, seed: int = 0, run_keys=None, device="cuda",
+                 buffer_bytes: int = None, pool_entries: int = MPS_POOL_ENTRIES):
+        import torch
+
+        from ..native import ops
+        from .run import _run_keys
+
+        who = "run_mps_bound"
+        self.batch, self.seed = batch, check_seed(seed, who)
+        self.n_traj = 1 if batch.trajectories is None else check_trajectories(batch.trajectories, who)
+        buffer_bytes = MPS_BUFFER_BYTES if buffer_bytes is None else int(buffer_bytes)
+        if buffer_bytes < 1:
+            raise ValueError(f"{who}: buffer_bytes = {buffer_bytes!r}, want a positive number of bytes")
+        dev = self.dev = torch.device(device)
+        is_tensor = isinstance(theta, torch.Tensor)
+        n_rows = int(theta.shape[0]) if (is_tensor and theta.dim() == 2) else None
+        if not is_tensor:
+            theta = np.asarray(theta, dtype=np.float64)
+            theta = theta.reshape(1, -1) if theta.ndim < 2 else theta
+            if theta.ndim != 2:
+                raise ValueError(f"{who}: the parameter rows have the shape {theta.shape}, want [n_rows, P]")
+            n_rows = int(theta.shape[0])
+            if theta.shape[1] == 0:
+                theta = np.zeros((max(n_rows, 1), 1), dtype=np.float64)
+        elif n_rows is None or theta.dtype != torch.float64:
+            raise ValueError(f"{who}: a tensor of parameter rows must be float64 [n_rows, P], got {tuple(theta.shape)} {theta.dtype}")
+        c = len(batch)
+        if runs is None:
+            if c != 1 and c != n_rows:
+                raise ValueError(f"{who}: {n_rows} parameter rows for {c} templates; pass runs= (template, row, shifted occurrence)")
+            runs = np.zeros((n_rows, 4), dtype=np.int32)
+            runs[:, 0], runs[:, 1], runs[:, 2] = (0 if c == 1 else np.arange(n_rows)), np.arange(n_rows), -1
+        runs = np.ascontiguousarray(runs, dtype=np.int32).reshape(-1, 4)
+        r = self.n_runs = int(runs.shape[0])
+        shift = np.zeros(r) if shift is None else np.ascontiguousarray(shift, dtype=np.float64).reshape(-1)
+        if shift.shape[0] != r:
+            raise ValueError(f"{who}: {r} runs but {shift.shape[0]} shifts")
+        if r and (c < 1 or n_rows < 1 or runs[:, 0].min() < 0 or runs[:, 0].max() >= c or runs[:, 1].min() < 0 or runs[:, 1].max() >= n_rows):
+            raise ValueError(f"{who}: a run names a template outside 0 .. {c - 1} or a parameter row outside 0 .. {n_rows - 1}")
+        if r and theta.shape[1] < int(batch.num_parameters[np.unique(runs[:, 0])].max()):
+            raise ValueError(f"{who}: the parameter rows have {int(theta.shape[1])} values, a template has "
+                             f"{int(batch.num_parameters[np.unique(runs[:, 0])].max())} parameters")
+        keys = _run_keys(run_keys, r, who)
+        tpl = runs[:, 0].astype(np.int64)
+        count = lambda ptr: np.diff(ptr)[tpl] if r else np.zeros(0, dtype=np.int64)   # noqa: E731
+        rec_n, pool_n, term_n = count(batch.op_ptr), count(batch.pool_ptr), count(batch.term_ptr)
+        cum = lambda v: np.concatenate([[0], np.cumsum(v)]).astype(np.int64)   # noqa: E731
+        run_op, run_pool, self.run_term_ptr = cum(rec_n), cum(pool_n), cum(term_n)
+        n_terms = int(self.run_term_ptr[-1])
+        self.term_run = np.repeat(np.arange(r, dtype=np.int64), term_n)
+        self.term_pos = np.arange(n_terms, dtype=np.int64) - np.repeat(self.run_term_ptr[:-1], term_n)
+        term_src = np.repeat(batch.term_ptr[tpl], term_n) + self.term_pos if r else np.zeros(0, dtype=np.int64)
+        widths = batch.n_qubits[tpl] if r else np.zeros(0, dtype=np.int32)
+        if np.any(pool_n > pool_entries):
+            raise ValueError(f"{who}: one bound copy holds {int(pool_n.max())} gate parameters, over the {pool_entries} a launch addresses")
+        # chunks: by the workspace budget, as run_mps splits circuits, and by the pool entries a record can address
+        chunks = []
+        for cr, tr in (_mps_chunks(_RunWidths(widths, batch.max_bond), self.n_traj, buffer_bytes) if r else []):
+            lo = cr.start
+            while lo < cr.stop:
+                hi = lo + 1
+                while hi < cr.stop and run_pool[hi + 1] - run_pool[lo] <= pool_entries:
+                    hi += 1
+                chunks.append((range(lo, hi), tr))
+                lo = hi
+        self.chunks = chunks
+
+        def up(a):
+            return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+        self.tpl = {k: up(getattr(batch, k)) for k in ("op_ptr", "ops", "params", "pool_ptr", "fac_ptr", "fac", "fac_val", "fpool",
+                                                       "occ_ptr", "occ", "letters", "readout")}
+        self.theta = theta.to(dev).contiguous() if is_tensor else up(theta)
+        self.runs, self.shift, self.keys, self.widths = up(runs), up(shift), up(keys), up(widths.astype(np.int32))
+        self.term_off, self.coeff = up(batch.term_off[term_src]), up(batch.coeff[term_src])
+        self.site_ptr = up(np.concatenate([batch.site_ptr[tpl], batch.site_ptr[-1:]]).astype(np.int64))
+        self.term_ptr = up(self.run_term_ptr)
+        # per chunk, relative to its first run: op_ptr [n + 1], out_pool_ptr [n + 1] and the run of each of its terms
+        rel_op, rel_pool, rel_term, self.where = [], [], [], []
+        for cr, _ in chunks:
+            self.where.append((sum(len(a) for a in rel_op), sum(len(a) for a in rel_term)))
+            rel_op.append(run_op[cr.start:cr.stop + 1] - run_op[cr.start])
+            rel_pool.append(run_pool[cr.start:cr.stop + 1] - run_pool[cr.start])
+            rel_term.append(self.term_run[self.run_term_ptr[cr.start]:self.run_term_ptr[cr.stop]] - cr.start)
+        cat = lambda parts, dtype: up(np.concatenate(parts).astype(dtype) if parts else np.zeros(0, dtype=dtype))   # noqa: E731
+        self.rel_op, self.rel_pool, self.rel_term = cat(rel_op, np.int64), cat(rel_pool, np.int64), cat(rel_term, np.int32)
+        self.sizes = [(int(run_op[cr.stop] - run_op[cr.start]), int(run_pool[cr.stop] - run_pool[cr.start]),
+                       int(self.run_term_ptr[cr.stop] - self.run_term_ptr[cr.start]), int(rec_n[cr.start:cr.stop].max()),
+                       int(widths[cr.start:cr.stop].max())) for cr, _ in chunks]
+        zeros = lambda shape, dtype=torch.float64: torch.zeros(shape, dtype=dtype, device=dev)   # noqa: E731
+        self.out_ops = zeros((max([s[0] for s in self.sizes] + [1]), 4), torch.int32)
+        self.out_pool = zeros(max([s[1] for s in self.sizes] + [0]) + PARAM_PAD)
+        t = self.n_traj
+        self.traj_terms, self.traj_norm, self.traj_stats = zeros((t, n_terms)), zeros((t, r)), zeros((t, r, ops.MPS_STATS))
+        units = max([len(cr) for cr, _ in chunks] + [1])
+        self.loc_terms, self.loc_norm = zeros(t * max([s[2] for s in self.sizes] + [1])), zeros(t * units)
+        self.loc_stats = zeros(t * units * ops.MPS_STATS)
+        need = max([ops.mps_workspace_bytes(s[4], batch.max_bond, len(cr) * len(tr)) for s, (cr, tr) in zip(self.sizes, chunks)] + [16])
+        self.workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+        self.out = {k: zeros(n) for k, n in (("term_values", n_terms), ("term_std_error", n_terms), ("values", r), ("std_error", r),
+                                             ("norm", r), ("discarded", r), ("error_bound", r))}
+        self.out["bond"] = zeros(r, torch.int32)
+
+    def launch(self) -> None:
+        """Enqueues the bind and run kernels of every chunk and the finish kernel.  No host read, no allocation, no upload."""
+        from ..native import ops
+
+        t, b, n_traj = self.tpl, self.batch, self.n_traj
+        for (cr, tr), (n_ops, n_pool, n_terms, max_rec, widest), (op_at, term_at) in zip(self.chunks, self.sizes, self.where):
+            lo, hi, n = cr.start, cr.stop, len(cr)
+            t0 = int(self.run_term_ptr[lo])
+            out_ops, out_pool = self.out_ops[:max(n_ops, 1)], self.out_pool[:n_pool + PARAM_PAD]
+            op_ptr, pool_ptr = self.rel_op[op_at:op_at + n + 1], self.rel_pool[op_at:op_at + n + 1]
+            ops.mps_bind(t["op_ptr"], t["ops"], t["params"], t["pool_ptr"], t["fac_ptr"], t["fac"], t["fac_val"], t["fpool"], t["occ_ptr"],
+                         t["occ"], self.theta, self.runs[lo:hi], self.shift[lo:hi], max_rec, op_ptr, pool_ptr, out_ops, out_pool)
+            loc_terms = self.loc_terms[:n_traj * n_terms].view(n_traj, n_terms)
+            loc_norm = self.loc_norm[:n_traj * n].view(n_traj, n)
+            loc_stats = self.loc_stats[:n_traj * n * ops.MPS_STATS].view(n_traj, n, ops.MPS_STATS)
+            ops.sim_run_mps(self.widths[lo:hi], op_ptr, out_ops, out_pool, self.keys[lo:hi], self.rel_term[term_at:term_at + n_terms],
+                            self.term_off[t0:t0 + n_terms], t["letters"], self.site_ptr[lo:hi + 1], t["readout"], (0, n), (0, n_terms),
+                            (tr.start, len(tr)), n_traj, self.seed, b.max_bond, b.cutoff, widest, self.workspace, loc_terms, loc_norm,
+                            loc_stats)
+            ts = slice(tr.start, tr.stop)
+            self.traj_terms[ts, t0:t0 + n_terms].copy_(loc_terms[ts])
+            self.traj_norm[ts, lo:hi].copy_(loc_norm[ts])
+            self.traj_stats[ts, lo:hi].copy_(loc_stats[ts])
+        if self.n_runs:
+            ops.sim_mps_finish(self.term_ptr, self.coeff, self.traj_terms, self.traj_norm, self.traj_stats, out=self.out)
+
+    def bound_batch(self, chunk: int = 0):
+        """Reads chunk ``chunk``'s bound records back as a plain :class:`MpsBatch` (after :meth:`launch`, before another chunk's bind
+        overwrites them: with one chunk, any time): what ``compile_mps`` of the bound copies would have lowered, for ``run_mps``."""
+        (cr, _), (n_ops, n_pool, n_terms, _, _), (op_at, term_at) = self.chunks[chunk], self.sizes[chunk], self.where[chunk]
+        lo, n, t0, b = cr.start, len(cr), int(self.run_term_ptr[cr.start]), self.batch
+        host = lambda x: x.cpu().numpy()   # noqa: E731
+        site = host(self.site_ptr[lo:cr.stop + 1])
+        return MpsBatch(
+            n_qubits=host(self.widths[lo:cr.stop]), op_ptr=host(self.rel_op[op_at:op_at + n + 1]), ops=host(self.out_ops[:n_ops]),
+            params=host(self.out_pool[:n_pool + PARAM_PAD]), term_ptr=self.run_term_ptr[lo:cr.stop + 1] - t0,
+            term_circ=host(self.rel_term[term_at:term_at + n_terms]), term_off=host(self.term_off[t0:t0 + n_terms]), letters=b.letters,
+            coeff=host(self.coeff[t0:t0 + n_terms]), site_ptr=site, readout=b.readout, max_bond=b.max_bond, cutoff=b.cutoff,
+            trajectories=b.trajectories)
+
+    def result(self, keep_trajectories: bool = False) -> MpsResult:
+        out, b = self.out, self.batch
+        noisy = b.trajectories is not None
+        return MpsResult(out["values"], out["term_values"], out["norm"], self.term_ptr, out["discarded"], out["error_bound"], out["bond"],
+                         out["std_error"] if noisy else None, out["term_std_error"] if noisy else None, b.trajectories, self.seed,
+                         self.traj_terms if keep_trajectories else None, self.traj_stats if keep_trajectories else None, b)
+
+
+def run_mps_bound(batch: MpsBoundBatch, rows, runs=None, shift=None, seed: int = 0, run_keys=None, device="cuda",
+                  keep_trajectories: bool = False, buffer_bytes: int = None) -> MpsResult:
+    """Runs templates lowered by :func:`compile_mps_templates`, bound on the device.  ``rows``: float64 [n_rows, P] (numpy, or a
+    tensor on the device); ``runs`` int32 [R, 4] = (template, row, shifted occurrence or -1, 0) with ``shift`` float64 [R] (default:
+    row r is one unshifted run of template r, or of the only template).  ``mlqem_mps_bind_f64`` writes the records and the
+    parameter pool of the R bound copies, the MPS kernels run them as they run any batch; both go on one stream
+    (:class:`MpsBoundRun` is the capturable form).  ``run_keys``: one integer per RUN, by default its position.  The runs are split
+    so that the site-tensor workspace of a launch stays under ``buffer_bytes`` and its pool under 2^31 - 1 entries; a run's bits
+    depend on (template, row, shift, seed, run key) alone, not on the split.  The result's CSR (``term_ptr``) is over the runs;
+    ``result.batch`` is the template batch."""
+    plan = MpsBoundRun(batch, rows, runs, shift, seed, run_keys, device, buffer_bytes)
+    plan.launch()
+    return plan.result(keep_trajectories)
+
+
+def _mps_pairs(template, observable, rows, noise, trajectories, max_bond, cutoff, who):
+    from .bound import _pairs
+
+    tpls, obss, pair, theta, n_rows = _pairs(template, observable, rows, who)
+    return compile_mps_templates(tpls, obss, noise, trajectories, max_bond, cutoff), pair, theta, n_rows
+
+
+def bound_mps_expectation_values(template, observable, rows, noise: Optional[NoiseModel] = None, trajectories: Optional[int] = None,
+                                 max_bond: int = MAX_BOND, cutoff: float = DEFAULT_CUTOFF, seed: int = 0, run_keys=None, device="cuda",
+                                 buffer_bytes: int = None, return_result: bool = False):
+    """Expectation values of one template of up to 512 qubits (two-qubit gates on neighbours) at many parameter vectors by
+    matrix-product states: ``(values [B], term_values [B, T])``, float64 tensors on ``device``; with ``return_result`` also the
+    :class:`MpsResult` over the B rows (``error_bound``, ``bond``, ``std_error``, ...: what :func:`mps_expectation_values` reports).
+    ``template`` / ``observable``: single objects with ``rows`` [B, P], or equal-length lists with one row per pair (T is then the
+    largest term count, rows padded with zeros).  Equal (template object, observable) pairs are lowered once
+    (:func:`compile_mps_templates`); nothing is bound or lowered per row on the host.  ``noise`` + ``trajectories`` as in
+    :func:`mps_expectation_values`."""
+    import torch
+
+    batch, pair, theta, n_rows = _mps_pairs(template, observable, rows, noise, trajectories, max_bond, cutoff, "bound_mps_expectation_values")
+    runs = np.zeros((n_rows, 4), dtype=np.int32)
+    runs[:, 0], runs[:, 1], runs[:, 2] = pair, np.arange(n_rows), -1
+    plan = MpsBoundRun(batch, theta, runs, None, seed, run_keys, device, buffer_bytes)
+    plan.launch()
+    res = plan.result()
+    width = int(np.diff(batch.term_ptr).max()) if len(batch) else 0
+    term_values = torch.zeros((n_rows, width), dtype=torch.float64, device=plan.dev)
+    if res.term_values.numel():
+        term_values[torch.from_numpy(plan.term_run).to(plan.dev), torch.from_numpy(plan.term_pos).to(plan.dev)] = res.term_values
+    return (res.values, term_values, res) if return_result else (res.values, term_values)
+
+
+def mps_parameter_shift(template, observable, rows, noise: Optional[NoiseModel] = None, trajectories: Optional[int] = None,
+                        max_bond: int = MAX_BOND, cutoff: float = DEFAULT_CUTOFF, seed: int = 0, run_keys=None, device="cuda",
+                        buffer_bytes: int = None):
+    """``parameter_shift(..., method="mps")``: values and parameter-shift gradients ``(values [B], gradients [B, P])`` from
+    matrix-product states.  One bind launch (per chunk) covers the B unshifted and the 2 K B shifted runs (K occurrences), the MPS
+    kernels follow, ``mlqem_sim_shift_combine_f64`` combines.  Under noise every run of a row uses the ROW's run key: the Pauli
+    insertions are drawn from (seed, key, trajectory, noise record) and not from an angle, so the + and - runs share their
+    insertions with the unshifted run, and the rule is exact for the mean over that trajectory set (each trajectory is a circuit
+    of rotations and fixed Pauli gates).  With truncation (a bond over ``max_bond``) the rule differentiates the truncated values
+    only up to their certificates."""
+    import torch
+
+    from ..native import ops
+    from .run import _run_keys
+
+    batch, pair, theta, n_rows = _mps_pairs(template, observable, rows, noise, trajectories, max_bond, cutoff, "parameter_shift")
+    runs, shift, groups = mps_shift_runs(batch, pair)
+    row_keys = _run_keys(run_keys, n_rows, "parameter_shift")
+    plan = MpsBoundRun(batch, theta, runs, shift, seed, row_keys[runs[:, 1]] if runs.shape[0] else None, device, buffer_bytes)
+    plan.launch()
+    all_values, dev = plan.result().values, plan.dev
+    width = int(batch.num_parameters.max()) if len(batch) else 0
+    values = torch.zeros(n_rows, dtype=torch.float64, device=dev)
+    grads = torch.zeros((n_rows, width), dtype=torch.float64, device=dev)
+
+    def up(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+    for c, rws, at, k in groups:
+        b, p = int(rws.size), int(batch.num_parameters[c])
+        ob = int(batch.occ_ptr[c])
+        par = batch.occ_param[ob:ob + k]
+        order = np.argsort(par, kind="stable").astype(np.int32)   # a parameter's occurrences, in circuit order
+        occ_ptr = np.concatenate([[0], np.cumsum(np.bincount(par, minlength=p))]).astype(np.int64)
+        v = all_values[at:at + b * (1 + 2 * k)]
+        g = ops.sim_shift_combine(v[b:b + k * b].reshape(k, b), v[b + k * b:].reshape(k, b), up(occ_ptr), up(order),
+                                  up(batch.occ_scale[ob:ob + k]))
+        idx = up(rws)
+        values[idx] = v[:b]
+        grads[idx, :p] = g
+    return values, grads
+
+
+def mps_shift_runs(batch: MpsBoundBatch, pair: np.ndarray):
+    """The runs of a parameter-shift gradient, as ``blackwater.sim.bound.shift_runs`` lays them out: per template c with rows ``R``
+    (B_c of them) and K_c occurrences, B_c unshifted runs, then K_c x B_c runs shifted by +pi/2 (occurrence-major), then as many
+    by -pi/2.  The shifted entry of a run is the OCCURRENCE number.  Returns ``(runs, shift, groups)``, ``groups = [(c, rows, first
+    run, K_c)]``."""
+    runs, shift, groups, at = [], [], [], 0
+    for c in range(len(batch)):
+        rows = np.flatnonzero(pair == c)
+        if rows.size == 0:
+            continue
+        k, b = int(batch.occ_ptr[c + 1] - batch.occ_ptr[c]), int(rows.size)
+        block = np.zeros((b * (1 + 2 * k), 4), dtype=np.int32)
+        block[:, 0] = c
+        block[:, 1] = np.tile(rows, 1 + 2 * k)
+        block[:b, 2] = -1
+        block[b:, 2] = np.tile(np.repeat(np.arange(k), b), 2)
+        sh = np.zeros(block.shape[0], dtype=np.float64)
+        sh[b:b + k * b], sh[b + k * b:] = 0.5 * math.pi, -0.5 * math.pi
+        runs.append(block)
+        shift.append(sh)
+        groups.append((c, rows, at, k))
+        at += block.shape[0]
+    if not runs:
+        return np.zeros((0, 4), dtype=np.int32), np.zeros(0), groups
+    return np.concatenate(runs), np.concatenate(shift), groups
+
+
 # ---- shots ------------------------------------------------------------------------------------------------------------------------
-MAX_GROUPS_MPS = 4096    # MLQEM_MPS_MAX_GROUPS: measurement groups per circuit (12 bits of a Philox counter word)
+MAX_GROUPS_MPS = 4096   # MLQEM_MPS_MAX_GROUPS: measurement groups per circuit (12 bits of a Philox counter word)
 _PAD = 32
 
 

@@ -15,7 +15,8 @@ from .frames import sample_clifford_expectation_values
 from .program import (MAX_QUBITS_DENSITY, MAX_QUBITS_VECTOR, NoiseModel, SimBatch, check_seed, check_shots, check_trajectories,
                       compile_programs)
 from .bound import bound_expectation_values
-from .mps import DEFAULT_CUTOFF, MAX_BOND, _check_bond, _check_cutoff, mps_expectation_values, sample_mps_expectation_values
+from .mps import (DEFAULT_CUTOFF, MAX_BOND, _check_bond, _check_cutoff, bound_mps_expectation_values, mps_expectation_values,
+                  sample_mps_expectation_values)
 from .template import Template, has_free_parameters
 
 
@@ -277,8 +278,9 @@ class DeviceEstimator:
     ``learning(...)`` and ``ngem(...)`` decorators patch.  Circuits arrive bound (QASM text, ``Circuit`` or a bound qiskit-like
     circuit); non-empty ``parameter_values`` are refused for them.  A :class:`Template` (or a qiskit-like circuit with free
     parameters) comes with its row of ``parameter_values`` and is bound on the device (:func:`bound_expectation_values`: one lowering
-    per distinct template, one run per row), under ``method="exact"`` and under ``"auto"`` within the cap; ``shots``, the other
-    methods and ``zne(DeviceEstimator)`` refuse a template by name.  There is no host path: ``device`` must be a GPU.
+    per distinct template, one run per row), under ``method="exact"``, under ``"auto"`` within the cap and, at width, under
+    ``"mps"``; ``shots``, the other methods and ``zne(DeviceEstimator)`` refuse a template by name.  There is no host path:
+    ``device`` must be a GPU.
 
     ``shots`` (constructor, or the ``shots=`` run option, which wins; ``None``: exact, as above): the values are estimated from that
     many measurement outcomes per measurement basis (:func:`sample_expectation_values`) and ``metadata[k] = {"variance": v_k,
@@ -304,7 +306,8 @@ class DeviceEstimator:
     ``noise`` the values are the ideal ones and ``metadata[k] = {"truncation_error_bound": B_k, "max_bond": the largest bond
     reached}`` with |value - exact| <= 2 B_k sum|coeff|; with ``noise`` (depolarising + readout, coherent errors) they are means over
     ``trajectories`` trajectories and the metadata also has ``"std_error"`` and ``"trajectories"``.  ``shots`` with it is refused by
-    name, and so are templates.  ``"auto"`` never picks it.
+    name.  Templates run here too, bound on the device (:func:`bound_mps_expectation_values`), with the same job ids, run keys and
+    metadata.  ``"auto"`` never picks it.
     ``"mps_shots"``: measurement shots drawn from those matrix-product states (:func:`sample_mps_expectation_values`), ideal or with
     ``noise`` and ``trajectories`` (shot s comes from trajectory s mod trajectories, so ``trajectories <= shots``); it needs ``shots``
     (``shots=None`` is refused by name, and so are templates), ``metadata[k] = {"variance": v_k, "shots": shots,
@@ -357,7 +360,7 @@ class DeviceEstimator:
         shots = run_options.pop("shots", self._shots)
         seed = run_options.pop("seed", self._seed)
         if any(free):
-            return self._run_templates(circuits, observables, parameter_values, free.index(True), shots)
+            return self._run_templates(circuits, observables, parameter_values, free.index(True), shots, seed)
         if self._method == "frames":
             if shots is None:
                 raise ValueError(_FRAMES_SHOTS)
@@ -424,21 +427,36 @@ class DeviceEstimator:
         return SimulatedJob(res.values.cpu().numpy(), f"sim-{self._count}",
                             [{"variance": float(v), "shots": shots} for v in variance])
 
-    def _run_templates(self, circuits, observables, parameter_values, first: int, shots):
+    def _run_templates(self, circuits, observables, parameter_values, first: int, shots, seed=0):
         """A job with templates (or qiskit-like circuits with free parameters): the bound path, one lowering per distinct
-        (template, observable) pair and one run per row.  Everything that is not the exact simulator is refused by name."""
+        (template, observable) pair and one run per row -- on the exact simulator, or under ``method="mps"`` on matrix-product
+        states (:func:`bound_mps_expectation_values`).  Everything else is refused by name."""
         how = ("bind it first (Template.bind_parameters(values)) and pass the bound circuit, which takes that path as ever; "
-               "templates run on the exact simulator alone (method='exact', or 'auto' within its cap, without shots)")
+               "templates run on the exact simulator (method='exact', or 'auto' within its cap) and on matrix-product states "
+               "(method='mps'), without shots")
         if shots is not None:
             raise ValueError(f"DeviceEstimator: circuit {first} is a template with free parameters and shots= is set: shots are not "
                              f"drawn on the bound path; {how}")
-        if self._method in ("trajectories", "clifford", "frames", "mps", "mps_shots"):
+        if self._method in ("trajectories", "clifford", "frames", "mps_shots"):
             raise ValueError(f"DeviceEstimator(method={self._method!r}): circuit {first} is a template with free parameters; {how}")
         templates = [Template.from_any(c) for c in circuits]
         for k, (t, p) in enumerate(zip(templates, parameter_values)):
             if len(p) != t.num_parameters:
                 raise ValueError(f"DeviceEstimator: circuit {k} comes with {len(p)} parameter values, the template has "
                                  f"{t.num_parameters} parameters")
+        if self._method == "mps":
+            self._count += 1
+            noisy = self._noise is not None
+            values, _, res = bound_mps_expectation_values(
+                list(circuits), list(observables), list(parameter_values), self._noise, self._trajectories if noisy else None,
+                self._max_bond, self._cutoff, check_seed(seed, "DeviceEstimator.run"), default_run_keys(len(circuits), self._count << 32),
+                self._device, return_result=True)
+            metadata = [{"truncation_error_bound": float(b), "max_bond": int(k)}
+                        for b, k in zip(res.error_bound.cpu().numpy(), res.bond.cpu().numpy())]
+            if noisy:
+                for m, e in zip(metadata, res.std_error.cpu().numpy()):
+                    m.update(std_error=float(e), trajectories=self._trajectories)
+            return SimulatedJob(values.cpu().numpy(), f"sim-{self._count}", metadata)
         if self._method == "auto":
             cap = MAX_QUBITS_VECTOR if self._noise is None else MAX_QUBITS_DENSITY
             for k, t in enumerate(templates):

@@ -49,11 +49,17 @@ def main():
     ap.add_argument("--mps-shots", type=int, default=None, metavar="N",
                     help="with --mps-labels: the noisy label is an N-shot estimate drawn from the matrix-product states (shot s from "
                          "trajectory s mod --mps-trajectories), as the reference trains on estimates from finite counts")
+    ap.add_argument("--mps-relaxation", action="store_true",
+                    help="with --mps-labels: the noisy labels are taken under the device model with thermal relaxation "
+                         "(NoiseModel.from_backend(..., thermal_relaxation=True): T1, T2 and gate times of the synthetic backend), "
+                         "unravelled into quantum jumps on the matrix-product states; about twice the decompositions")
     args = ap.parse_args()
     if args.clifford_labels and args.mps_labels:
         ap.error("--clifford-labels and --mps-labels choose different circuits: pass one")
     if args.mps_shots is not None and not args.mps_labels:
         ap.error("--mps-shots draws from the matrix-product states of --mps-labels: pass both")
+    if args.mps_relaxation and not args.mps_labels:
+        ap.error("--mps-relaxation changes the noise model of --mps-labels: pass both")
 
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -67,7 +73,8 @@ def main():
     shard_dir = args.shard_dir or os.path.join(tempfile.gettempdir(),
                                                f"mlqem_example_{args.qubits}q" + ("_clifford" if args.clifford_labels else "")
                                                + (f"_mps{args.mps_bond}" if args.mps_labels else "")
-                                               + (f"_shots{args.mps_shots}" if args.mps_shots is not None else ""))
+                                               + (f"_shots{args.mps_shots}" if args.mps_shots is not None else "")
+                                               + ("_relax" if args.mps_relaxation else ""))
     paths = [os.path.join(shard_dir, f"part{k}.mlqs") for k in range(2)]
     if rank == 0 and not all(os.path.exists(p) for p in paths):
         os.makedirs(shard_dir, exist_ok=True)
@@ -85,9 +92,9 @@ def main():
             rng = np.random.default_rng(42)
             circuits = [tfim_circuit(args.qubits, s, float(j), two_q="cx")
                         for s in range(1, args.steps + 1) for j in rng.uniform(0.0, 0.66 * np.pi, size=args.n_j)]
-            noise = sim.NoiseModel.from_backend(synthetic_backend(args.qubits, "cx"))
+            noise = sim.NoiseModel.from_backend(synthetic_backend(args.qubits, "cx"), thermal_relaxation=args.mps_relaxation)
             c = encode_corpus(circuits, args.qubits, two_q="cx", simulate=noise, device=dev, mps_bond=args.mps_bond,
-                              trajectories=args.mps_trajectories, mps_shots=args.mps_shots)
+                              trajectories=args.mps_trajectories, mps_shots=args.mps_shots, mps_relaxation=args.mps_relaxation)
             print(f"MPS labels at bond {args.mps_bond}: the worst certificate of the corpus is B = {c['mps_error_bound']:.3e} "
                   f"(every ideal label is within 2 B of the exact <Z>)")
         else:

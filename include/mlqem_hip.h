@@ -2002,9 +2002,35 @@ int mlqem_clifford_sample_f64(int64_t n_circuits, const int32_t* n_qubits, const
  *                       first j in 0 .. m with s_j > u, else m.  j = 0: nothing (probability 1 - lambda (d^2 - 1) / d^2).  Else
  *                       j = l0 + 4 l1 with the letter l0 on q0 and l1 on q1 (DEPOL1: j = l0), letters 0 I, 1 X, 2 Y, 3 Z, each
  *                       applied as a one-site 2x2 matrix of entries 0, +-1, +-i (nothing is rounded).  lambda == 0: no draw.
+ *   MLQEM_MPS_OP_NOISE1 (lambda, g, c, p1) on `site`; MLQEM_MPS_OP_NOISE2 (lambda, (g, c, p1) of q0, (g, c, p1) of q1) on the bond,
+ *                       orientation and q0 = site + orientation as for DEPOL2; numbered as their MLQEM_SIM_OP_* twins.  Thermal
+ *                       relaxation as quantum jumps (mlqem_mps_run_f64 only: the folded kernel skips them, the host refuses
+ *                       them there).  A NOISE record is ONE noise record for the index i, lambda == 0 included.  Inside it:
+ *                       first DEPOL1's / DEPOL2's draw with lambda (sub-draw 0; skipped at lambda == 0), then one RELAXATION
+ *                       per qubit.  NOISE2: the SITE order of its two relaxations is fixed by the centre: where the centre is
+ *                       <= site the lower site goes first, else the upper one (right after a U2 on the bond the centre is on
+ *                       site + 1, so the upper site costs no move and the lower one leftward move).  The sub-draw number and
+ *                       the triple follow the GATE's qubit -- 1 for q0, 2 for q1 -- not that order.  Relaxations of different
+ *                       qubits commute as channels, so the average over the draws is the map of MLQEM_SIM_OP_NOISE2 in either
+ *                       order (each step takes its populations from the state the step before left).
+ *                       RELAXATION (g, c, p1) of qubit q with sub-draw s:
+ *                       1. the centre moves to q, one site at a time, by the two loops of a U2 record (one qubit: no move);
+ *                       2. P_s = sum_(l, r) |A[q][l, s, r]|^2, s = 0, 1, reduced in this order: thread j of 256 adds the entries
+ *                          (l, r) = l * chi_r + r = j, j + 256, ... in that order from 0.0; the shuffle tree over a wave's 64
+ *                          lanes (v += the lane 32, 16, 8, 4, 2, 1 above); the four waves in order ((w0 + w1) + w2) + w3.
+ *                          pa = P0 / (P0 + P1), pb = P1 / (P0 + P1), c2 = c c, d = max(0, (1 - g) - c2);
+ *                       3. the six outcomes, their probabilities, the uniform u = U(i, s) against their running sum and the
+ *                          selection rule are those of mlqem_sim_run_trajectories_f64 (Relaxation, above): the first j with
+ *                          s_j > u, else the last j of probability > 0; an outcome of probability exactly 0 is never chosen;
+ *                       4. the chosen operator over the root of its own state-given probability, the real 2x2 matrix with the
+ *                          factor t = 1 / sqrt(.) tabulated there, is applied to the physical index of A[q].
+ *                       Because q holds the centre the other sites stay orthonormal: the state stays canonical, and normalised
+ *                       up to rounding.  The applied matrix has operator norm t (c <= 1), and `error_bound` <- t * `error_bound`
+ *                       after each relaxation; `discarded` is left alone (see Certificate).
  *   Any other kind is skipped; a two-site record of a one-qubit circuit is skipped.
- * u of noise record i, trajectory t: Philox4x32-10 with the key (seed & 0xffffffff, seed >> 32) and the counter
- *   (i, t, run_key & 0xffffffff, run_key >> 32), run_key = run_keys[c]; u = ((x0 >> 5) 2^26 + (x1 >> 6)) 2^-53.  A unit therefore
+ * u of noise record i, sub-draw s, trajectory t: Philox4x32-10 with the key (seed & 0xffffffff, seed >> 32) and the counter
+ *   (i, s << 24 | t, run_key & 0xffffffff, run_key >> 32), run_key = run_keys[c], t < 2^20; s = 0 for every depolarising draw (the
+ *   DEPOL records' bits are what they were), 1 / 2 for the relaxations; u = ((x0 >> 5) 2^26 + (x1 >> 6)) 2^-53.  A unit therefore
  * depends on (seed, run key, t, the circuit's records, max_bond, cutoff) alone: the same bits alone, in any batch, in any split
  * into calls, and in a replayed graph.  No atomics.
  *
@@ -2036,6 +2062,12 @@ int mlqem_clifford_sample_f64(int64_t n_circuits, const int32_t* n_qubits, const
  * |psi_exact - psi_mps| <= B = sum sqrt(2 eps) = `error_bound`, and |<O>_exact - <O>_mps| <= 2 B sum|coeff|.  The default cutoff
  * 1e-26 drops the numerically-zero columns of a rank-deficient theta (a cx on a product state); a decomposition that drops only
  * such columns adds at most sqrt(2 * 2 max_bond * cutoff) to B, the floor under `error_bound`.
+ *   With NOISE records: a relaxation applies M = K / sqrt(p), |M| = t, which is no unitary: |M x - M y| <= t |x - y|, hence
+ * B <- t B.  B then bounds |psi~ - psi_mps| where psi~ is the exact vector carried through the SAME operators M (the ones this
+ * trajectory drew, with the MPS's normalisers sqrt(p)); psi~ is not normalised, | |psi~| - 1 | <= B, so its normalised form is
+ * within 2 B of psi_mps and |<O>_exact - <O>_mps| <= 4 B sum|coeff| for that trajectory (2 B in the unitary case).  The bound is
+ * CONDITIONAL on the operators drawn: the exact state would have drawn them with other probabilities, so it is no bound on the
+ * channel average.  Where the bond cap never cuts, B stays at the cutoff's floor (times the t's) and nothing changes.
  *
  * mlqem_mps_run_f64 runs the units (circuit circ_first + u / traj_count, trajectory traj_first + u % traj_count), u < circ_count *
  * traj_count, one workgroup each, into `workspace` (mlqem_mps_workspace_bytes(max_qubits, max_bond, units); max_qubits >= every
@@ -2088,6 +2120,8 @@ int mlqem_clifford_sample_f64(int64_t n_circuits, const int32_t* n_qubits, const
 #define MLQEM_MPS_OP_U2 5
 #define MLQEM_MPS_OP_DEPOL1 6
 #define MLQEM_MPS_OP_DEPOL2 7
+#define MLQEM_MPS_OP_NOISE1 10
+#define MLQEM_MPS_OP_NOISE2 11
 size_t mlqem_mps_workspace_bytes(int64_t max_qubits, int64_t max_bond, int64_t n_units);
 int mlqem_mps_run_f64(int64_t n_circuits, const int32_t* n_qubits, const int64_t* op_ptr, const mlqem_sim_op* ops, int64_t n_ops,
                       const double* params, int64_t n_params, const int64_t* run_keys, int64_t circ_first, int64_t circ_count,

@@ -64,7 +64,7 @@ def exp_value_generator(backend: Any, n_qubits: int, circuit_depth: int, pauli_t
                         max_entries: int = 1000, seed: int = 0, batch: int = 256, device="cuda", shots: Optional[int] = None,
                         sample_ideal: bool = False, trajectories: Optional[int] = None,
                         frame_shots: Optional[int] = None, mps_bond: Optional[int] = None,
-                        mps_shots: Optional[int] = None) -> Iterator[ExpValueEntry]:
+                        mps_shots: Optional[int] = None, mps_relaxation: bool = False) -> Iterator[ExpValueEntry]:
     """Yields ``max_entries`` dataset entries of random circuits with simulated labels (reference: exp_val.py:92-170, which
     transpiles ``qiskit.circuit.random.random_circuit`` and runs Aer twice per circuit).
 
@@ -99,7 +99,16 @@ def exp_value_generator(backend: Any, n_qubits: int, circuit_depth: int, pauli_t
     ``mps_shots`` (default ``None``; with ``mps_bond`` and ``trajectories``): the noisy value becomes the ``mps_shots``-shot estimate
     drawn from the matrix-product states (``sim.sample_mps_expectation_values``, shot s from trajectory s mod ``trajectories``, keyed as
     the shots are); the ideal value stays the exact MPS value.  Without ``mps_bond``, or together with ``shots`` or ``frame_shots``,
-    it is refused by name."""
+    it is refused by name.
+
+    ``mps_relaxation`` (default ``False``; with ``mps_bond``): the noisy value is taken under
+    ``NoiseModel.from_backend(backend, readout=False, thermal_relaxation=True)`` -- Aer's device model restated -- which the MPS
+    path unravels into quantum jumps (``thermal_relaxation=True`` there).  Without ``mps_bond`` it is refused by name."""
+    if not isinstance(mps_relaxation, bool):
+        raise ValueError(f"exp_value_generator: mps_relaxation = {mps_relaxation!r}, want True or False")
+    if mps_relaxation and mps_bond is None:
+        raise ValueError("exp_value_generator: mps_relaxation without mps_bond (thermal relaxation is unravelled on the "
+                         "matrix-product-state path: pass mps_bond=chi)")
     if mps_shots is not None:
         if shots is not None or frame_shots is not None:
             raise ValueError("exp_value_generator: mps_shots together with " + ("shots" if shots is not None else "frame_shots") +
@@ -132,7 +141,7 @@ def exp_value_generator(backend: Any, n_qubits: int, circuit_depth: int, pauli_t
         raise ValueError(f"exp_value_generator: want one two-qubit basis gate among cx / ecr / cz, the backend has {two_q}")
     if batch < 1:
         raise ValueError(f"exp_value_generator: batch must be >= 1, got {batch}")
-    noise = sim.NoiseModel.from_backend(backend, readout=False)
+    noise = sim.NoiseModel.from_backend(backend, readout=False, thermal_relaxation=mps_relaxation)
     rng = np.random.default_rng(seed)
     done = 0
     while done < max_entries:
@@ -155,10 +164,11 @@ def exp_value_generator(backend: Any, n_qubits: int, circuit_depth: int, pauli_t
             if mps_shots is not None:
                 noisy = _to_host(sim.sample_mps_expectation_values(circuits, observables, noise, shots=mps_shots, max_bond=mps_bond,
                                                                    trajectories=trajectories, seed=seed, run_keys=keys,
-                                                                   device=device).values)
+                                                                   device=device, thermal_relaxation=mps_relaxation).values)
             else:
                 noisy = _to_host(sim.mps_expectation_values(circuits, observables, noise, max_bond=mps_bond, trajectories=trajectories,
-                                                            seed=seed, run_keys=keys, device=device).values)
+                                                            seed=seed, run_keys=keys, device=device,
+                                                            thermal_relaxation=mps_relaxation).values)
         elif trajectories is not None:
             keys = np.arange(done, done + count, dtype=np.int64)   # the entry's number, as on the shots path
             ideal = _to_host(sim.expectation_values(circuits, observables, None, device)[0])

@@ -6,7 +6,11 @@
 bond needs more than ``max_bond`` (TFIM circuits: through 5 Trotter steps at bond 32) and come with an a-priori certificate
 beyond: ``error_bound`` B bounds the distance of the states, so |<O>_exact - <O>_mps| <= 2 B sum|coeff|.  With a depolarising +
 readout noise model and ``trajectories`` the same kernel gives noisy values: every depolarising record inserts one drawn Pauli
-string (its probabilities do not depend on the state), readout noise is folded into the measured operators.
+string (its probabilities do not depend on the state), readout noise is folded into the measured operators.  With
+``thermal_relaxation=True`` a model with thermal relaxation (``NoiseModel.from_backend(..., thermal_relaxation=True)``) is taken too:
+a ``NOISE1`` / ``NOISE2`` record per relaxed gate, unravelled into quantum jumps at the orthogonality centre; ``error_bound`` is then
+a per-trajectory certificate, conditional on the jumps drawn, with the constant 4 in the place of 2.  Templates and folded runs
+refuse such a model by name.
 
 ``compile_mps_shots`` / ``run_mps_shots`` / ``sample_mps_expectation_values`` draw measurement shots from the same states
 (``mlqem_mps_sample_f64``: perfect sampling, one sweep over the sites per shot), ``mps_counts`` gives the count dictionaries.
@@ -20,14 +24,15 @@ from typing import Any, Dict, List, Optional, Sequence
 import numpy as np
 
 from ..data.circuit import Circuit
-from .program import (_N_PARAMS, _TWO_QUBIT, OP_DIAG1, PARAM_PAD, SUPPORTED_GATES, NoiseModel, _check_coherent, _lower_terms,
-                      _one_qubit, _two_qubit, check_seed, check_trajectories, measurement_groups)
+from .program import (_N_PARAMS, _TWO_QUBIT, OP_DIAG1, PARAM_PAD, SUPPORTED_GATES, NoiseModel, _check_coherent, _check_relaxation,
+                      _lower_terms, _one_qubit, _two_qubit, check_seed, check_trajectories, measurement_groups)
 
 MAX_BOND = 32            # MLQEM_MPS_MAX_BOND: theta, (2 chi) x (2 chi) complex128 = 64 KiB, sits in LDS beside a second workgroup
 MAX_QUBITS_MPS = 512     # MLQEM_MPS_MAX_QUBITS
 MPS_BUFFER_BYTES = 4 << 30   # the site-tensor workspace of one launch stays under this (``buffer_bytes=``): 1 300 units of 100 qubits
 DEFAULT_CUTOFF = 1e-26   # relative weight below which a column is dropped: the numerically-zero columns of a rank-deficient theta
 OP_MPS_U1, OP_MPS_U2, OP_MPS_DEPOL1, OP_MPS_DEPOL2 = 0, 5, 6, 7   # MLQEM_MPS_OP_*
+OP_MPS_NOISE1, OP_MPS_NOISE2 = 10, 11   # depolarising, then thermal relaxation of the gate's qubits (thermal_relaxation=True)
 
 _PERMUTATION = {"cx": (0, 3, 2, 1), "swap": (0, 2, 1, 3)}   # column j of the matrix has its 1 in row _PERMUTATION[name][j]
 
@@ -95,7 +100,7 @@ class MpsBatch:
     gate_name: Optional[np.ndarray] = None        # int16 [n_gates]: index of the gate's name in SUPPORTED_GATES
     gate_record: Optional[np.ndarray] = None      # int32 [n_gates]: the gate's own U1 / U2 record
     gate_noise: Optional[np.ndarray] = None       # int32 [n_gates]: the first noise record after it
-    gate_noise_len: Optional[np.ndarray] = None   # int32 [n_gates]: 0, 1 (DEPOL*) or 2 (a coherent U2, then DEPOL*)
+    gate_noise_len: Optional[np.ndarray] = None   # int32 [n_gates]: 0, 1 (DEPOL* / NOISE*) or 2 (a coherent U2, then DEPOL* / NOISE*)
 
     def __len__(self) -> int:
         return int(self.n_qubits.shape[0])
@@ -113,6 +118,17 @@ def is_line_circuit(circuit: Any) -> bool:
     """Whether every two-qubit gate of the circuit acts on neighbouring qubits (q, q + 1), in either order."""
     return all(len(op.qubits) != 2 or op.name in ("barrier", "measure") or abs(op.qubits[0] - op.qubits[1]) == 1
                for op in Circuit.from_any(circuit).ops)
+
+
+def refuse_relaxation_records(batch: Any, who: str) -> None:
+    """Raises where a batch holds a ``NOISE1`` / ``NOISE2`` record (``compile_mps(..., thermal_relaxation=True)``, or built by
+    hand): the folded kernel and the bind kernel do not run them."""
+    kinds = np.asarray(batch.ops).reshape(-1, 4)[:, 0]
+    hit = np.flatnonzero((kinds == OP_MPS_NOISE1) | (kinds == OP_MPS_NOISE2))
+    if hit.size:
+        raise ValueError(f"{who}: record {int(hit[0])} of the batch is a thermal-relaxation record (NOISE1 / NOISE2, "
+                         "compile_mps(..., thermal_relaxation=True)); folded runs and templates on the matrix-product-state path "
+                         "take depolarising + readout models only (relaxation there is not built: run_mps runs such a batch)")
 
 
 def _check_bond(max_bond: Any, who: str) -> int:
@@ -194,8 +210,11 @@ class _Lowering:
     ``Param`` of every op of a template, or None) it also keeps, for every record whose matrix depends on a parameter, the factor
     program of the record and the occurrences of the parameters."""
 
-    def __init__(self, who, circuits, observables, noise, trajectories, max_bond, cutoff):
+    def __init__(self, who, circuits, observables, noise, trajectories, max_bond, cutoff, thermal_relaxation=False):
         self.who = who
+        if not isinstance(thermal_relaxation, (bool, np.bool_)):
+            raise ValueError(f"{who}: thermal_relaxation = {thermal_relaxation!r}, want True or False")
+        self.relaxation = bool(thermal_relaxation)
         self.circuits, self.observables = list(circuits), list(observables)
         self.max_bond, self.cutoff = _check_bond(max_bond, who), _check_cutoff(cutoff, who)
         if trajectories is not None:
@@ -346,17 +365,30 @@ class _Lowering:
                 if lam is not None and not (math.isfinite(lam) and 0.0 <= lam <= 1.0):
                     raise ValueError(f"{where}: op {i} ({name}): depolarising parameter {lam!r}, want 0 <= lambda <= 1")
                 coherent = coherent_after(i, name, reg) if coherent_after is not None else None
-                if relaxation_after is not None and relaxation_after(i, name, reg) is not None:
+                relax = relaxation_after(i, name, reg) if relaxation_after is not None else None
+                if relax is not None and not self.relaxation:
                     raise ValueError(f"{where}: op {i} ({name}): the noise model has thermal relaxation, whose jump probabilities "
                                      "depend on the state; the MPS path takes depolarising + readout models (and coherent two-qubit "
-                                     "errors) only")
+                                     "errors) only, unless thermal_relaxation=True is passed (quantum jumps at the orthogonality "
+                                     "centre, which then moves to every relaxed qubit: about twice the decompositions; not "
+                                     "for templates or folded runs)")
                 if coherent is not None:
                     if width != 2:
                         raise ValueError(f"{where}: op {i} ({name}): a coherent error is a 4x4 unitary, the gate has one qubit")
                     noi = len(ops) - first
                     emit_matrix(OP_MPS_U2, min(op.qubits), int(op.qubits[0] > op.qubits[1]), _check_coherent((name, reg), coherent))
                     noi_len += 1
-                if lam is not None:
+                if relax is not None:      # one fused record: depolarising (lambda = 0: none), then relaxation
+                    relax = _check_relaxation((name, reg), relax, width)
+                    noi = len(ops) - first if noi < 0 else noi
+                    noi_len += 1
+                    values = [float(lam or 0.0)] + [v for t in relax for v in t]
+                    if width == 2:
+                        emit(OP_MPS_NOISE2, min(op.qubits), int(op.qubits[0] > op.qubits[1]), values)
+                    else:
+                        emit(OP_MPS_NOISE1, op.qubits[0], 0, values)
+                    n_noise += 1
+                elif lam is not None:
                     noi = len(ops) - first if noi < 0 else noi
                     noi_len += 1
                     if width == 2:
@@ -445,7 +477,8 @@ class _Lowering:
 
 
 def compile_mps(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None,
-                trajectories: Optional[int] = None, max_bond: int = MAX_BOND, cutoff: float = DEFAULT_CUTOFF) -> MpsBatch:
+                trajectories: Optional[int] = None, max_bond: int = MAX_BOND, cutoff: float = DEFAULT_CUTOFF,
+                thermal_relaxation: bool = False) -> MpsBatch:
     """Lowers ``circuits`` with one observable each to one :class:`MpsBatch`.  Site = qubit index.
 
     ``noise=None`` (ideal): one ``U2`` record per bond visit -- a run of gates confined to one bond (its one-qubit gates included)
@@ -454,11 +487,19 @@ def compile_mps(circuits: Sequence[Any], observables: Sequence[Any], noise: Opti
     per two-qubit gate (the gate's own matrix and its orientation), a ``U2`` for a coherent error, and a ``DEPOL1`` / ``DEPOL2``
     record per depolarising op; readout noise of measured qubits goes into the ``readout`` table.
 
+    ``thermal_relaxation=True`` takes a model with thermal relaxation (``NoiseModel.from_backend(..., thermal_relaxation=True)``):
+    a gate with relaxation gets ONE ``NOISE1`` / ``NOISE2`` record (lambda or 0, then the checked (g, c, p1) triples, as
+    ``compile_programs`` emits them) in the place of its ``DEPOL`` record, and the kernel unravels it into quantum jumps applied at
+    the orthogonality centre, which moves to every relaxed qubit (about twice the decompositions).  ``error_bound`` is then a
+    per-trajectory certificate, conditional on the jumps drawn: |<O>_exact - <O>_mps| <= 4 B sum|coeff| for the exact vector
+    carried through the same operators (include/mlqem_hip.h).  Such a batch is refused by ``compile_mps_templates`` (the keyword
+    does not exist there) and by the folded runs of ``blackwater.sim.zne``.
+
     Raises ``ValueError`` naming the offender for what ``compile_programs`` refuses (unknown gates, parameter counts, qubits out of
     range or used after their measurement, non-finite angles, malformed terms) and for: a two-qubit gate on qubits that are no
-    neighbours, ``max_bond`` outside 1 .. 32, ``noise`` without ``trajectories`` or the reverse, a model with thermal relaxation,
-    readout noise together with an X / Y term, a circuit over 512 qubits."""
-    low = _Lowering("compile_mps", circuits, observables, noise, trajectories, max_bond, cutoff)
+    neighbours, ``max_bond`` outside 1 .. 32, ``noise`` without ``trajectories`` or the reverse, a model with thermal relaxation
+    without ``thermal_relaxation=True``, readout noise together with an X / Y term, a circuit over 512 qubits."""
+    low = _Lowering("compile_mps", circuits, observables, noise, trajectories, max_bond, cutoff, thermal_relaxation)
     for k, (obj, obs) in enumerate(zip(low.circuits, low.observables)):
         low.add(k, Circuit.from_any(obj), obs)
     return MpsBatch(**low.fields())
@@ -494,7 +535,8 @@ def compile_mps_templates(templates: Sequence[Any], observables: Sequence[Any], 
     FIXED factors (the host product of a maximal run of consecutive fixed gates, the ``kron`` of the pending one-qubit matrices a
     bond absorbs included) and PARAM factors (kind, slot, parameter, scale, offset); ``mlqem_mps_bind_f64`` forms it per run on
     the device.  The noisy lowering fuses nothing: a parameterised record there has exactly one PARAM factor.  A template without
-    parameters lowers to the arrays ``compile_mps`` gives."""
+    parameters lowers to the arrays ``compile_mps`` gives.  A model with thermal relaxation is refused by name: there is no
+    ``thermal_relaxation`` keyword here, and ``run_mps_bound`` refuses a batch that holds a ``NOISE1`` / ``NOISE2`` record."""
     from .template import Template
 
     templates = [Template.from_any(t) for t in templates]
@@ -633,11 +675,12 @@ def run_mps(batch: MpsBatch, seed: int = 0, run_keys=None, device="cuda", keep_t
 
 def mps_expectation_values(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None,
                            max_bond: int = MAX_BOND, cutoff: float = DEFAULT_CUTOFF, trajectories: Optional[int] = None, seed: int = 0,
-                           run_keys=None, device="cuda") -> MpsResult:
+                           run_keys=None, device="cuda", thermal_relaxation: bool = False) -> MpsResult:
     """Expectation values of ``observables[k]`` after ``circuits[k]`` by matrix-product states of bond at most ``max_bond``:
     circuits of up to 512 qubits whose two-qubit gates act on neighbours, any angle.  ``noise`` + ``trajectories``: the values
-    under a depolarising + readout model, as means over Pauli-insertion trajectories with their standard errors."""
-    return run_mps(compile_mps(circuits, observables, noise, trajectories, max_bond, cutoff), seed, run_keys, device)
+    under a depolarising + readout model, as means over Pauli-insertion trajectories with their standard errors; with
+    ``thermal_relaxation=True`` also under a model with thermal relaxation (quantum jumps, :func:`compile_mps`)."""
+    return run_mps(compile_mps(circuits, observables, noise, trajectories, max_bond, cutoff, thermal_relaxation), seed, run_keys, device)
 
 
 # ---- templates: bound on the device ---------------------------------------------------------------------------------------------------
@@ -669,6 +712,7 @@ class MpsBoundRun:
 
         who = "run_mps_bound"
         self.batch, self.seed = batch, check_seed(seed, who)
+        refuse_relaxation_records(batch, who)
         self.n_traj = 1 if batch.trajectories is None else check_trajectories(batch.trajectories, who)
         buffer_bytes = MPS_BUFFER_BYTES if buffer_bytes is None else int(buffer_bytes)
         if buffer_bytes < 1:
@@ -979,14 +1023,15 @@ class MpsShotsBatch:
 
 
 def compile_mps_shots(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None,
-                      trajectories: Optional[int] = None, max_bond: int = MAX_BOND, cutoff: float = DEFAULT_CUTOFF) -> MpsShotsBatch:
+                      trajectories: Optional[int] = None, max_bond: int = MAX_BOND, cutoff: float = DEFAULT_CUTOFF,
+                      thermal_relaxation: bool = False) -> MpsShotsBatch:
     """The lowering of :func:`compile_mps` plus the measurement groups of :func:`~blackwater.sim.measurement_groups`: one basis
     letter per (group, site) (Z where no term of the group touches the site), the ``flip`` table of the measured qubits' readout
     noise, a support mask per term and the group of each term.  What ``compile_mps`` refuses stays refused, by the same messages
-    (X or Y terms beside readout noise, thermal relaxation, gates on qubits that are no neighbours, ...); also refused: a circuit
-    whose terms need more than 4 096 measurement groups."""
+    (X or Y terms beside readout noise, thermal relaxation without ``thermal_relaxation=True``, gates on qubits that are no
+    neighbours, ...); also refused: a circuit whose terms need more than 4 096 measurement groups."""
     circuits, observables = list(circuits), list(observables)
-    base = compile_mps(circuits, observables, noise, trajectories, max_bond, cutoff)   # every check and refusal
+    base = compile_mps(circuits, observables, noise, trajectories, max_bond, cutoff, thermal_relaxation)   # every check and refusal
     group_ptr, group_circ, group_off, basis, ref_ptr = [0], [], [], [], [0]
     gterm_ptr, gterm, term_mask, term_group, masks, flip = [0], [], [], [], [], []
     max_groups = 1
@@ -1124,18 +1169,19 @@ def run_mps_shots(batch: MpsShotsBatch, shots: int, seed: int = 0, run_keys=None
 def sample_mps_expectation_values(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None, *,
                                   shots: int = None, trajectories: Optional[int] = None, max_bond: int = MAX_BOND,
                                   cutoff: float = DEFAULT_CUTOFF, seed: int = 0, run_keys=None, return_bits: bool = False,
-                                  device="cuda") -> MpsShotsResult:
+                                  device="cuda", thermal_relaxation: bool = False) -> MpsShotsResult:
     """Expectation values of ``observables[k]`` after ``circuits[k]`` estimated from ``shots`` measurement outcomes per measurement
     basis, drawn from the matrix-product state of bond at most ``max_bond``: circuits of up to 512 qubits whose two-qubit gates act on
-    neighbours, any angle; ideal, or under a depolarising + readout ``noise`` model with ``trajectories``.  The limit of every
-    estimate is the value :func:`mps_expectation_values` gives."""
+    neighbours, any angle; ideal, or under a depolarising + readout ``noise`` model with ``trajectories`` (one with thermal
+    relaxation: ``thermal_relaxation=True``).  The limit of every estimate is the value :func:`mps_expectation_values` gives."""
     from .program import check_shots
 
     if shots is None:
         raise ValueError("sample_mps_expectation_values: shots is required (an int in 1 .. 2^20); mps_expectation_values gives the "
                          "values without shot noise")
     shots = check_shots(shots, "sample_mps_expectation_values")
-    return run_mps_shots(compile_mps_shots(circuits, observables, noise, trajectories, max_bond, cutoff), shots, seed, run_keys,
+    return run_mps_shots(compile_mps_shots(circuits, observables, noise, trajectories, max_bond, cutoff, thermal_relaxation), shots, seed,
+                         run_keys,
                          return_bits, device)
 
 

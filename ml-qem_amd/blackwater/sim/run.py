@@ -307,7 +307,10 @@ class DeviceEstimator:
     reached}`` with |value - exact| <= 2 B_k sum|coeff|; with ``noise`` (depolarising + readout, coherent errors) they are means over
     ``trajectories`` trajectories and the metadata also has ``"std_error"`` and ``"trajectories"``.  ``shots`` with it is refused by
     name.  Templates run here too, bound on the device (:func:`bound_mps_expectation_values`), with the same job ids, run keys and
-    metadata.  ``"auto"`` never picks it.
+    metadata.  ``"auto"`` never picks it.  ``thermal_relaxation=True`` (``"mps"`` and ``"mps_shots"`` alone) takes a model with
+    thermal relaxation (:func:`compile_mps`: quantum jumps at the orthogonality centre); the metadata keys are the same, and
+    ``truncation_error_bound`` is then the mean of per-trajectory certificates, each conditional on the jumps drawn (|value - exact|
+    <= 4 B sum|coeff| per trajectory).  Templates with it are refused by name.
     ``"mps_shots"``: measurement shots drawn from those matrix-product states (:func:`sample_mps_expectation_values`), ideal or with
     ``noise`` and ``trajectories`` (shot s comes from trajectory s mod trajectories, so ``trajectories <= shots``); it needs ``shots``
     (``shots=None`` is refused by name, and so are templates), ``metadata[k] = {"variance": v_k, "shots": shots,
@@ -321,12 +324,19 @@ class DeviceEstimator:
     WIDE_SAMPLED_METHODS = ("mps_shots",)   # shots at width from matrix-product states; by name alone
 
     def __init__(self, noise: Optional[NoiseModel] = None, device="cuda", shots: Optional[int] = None, seed: int = 0,
-                 method: str = "exact", trajectories: int = 1024, max_bond: int = MAX_BOND, cutoff: float = DEFAULT_CUTOFF):
+                 method: str = "exact", trajectories: int = 1024, max_bond: int = MAX_BOND, cutoff: float = DEFAULT_CUTOFF,
+                 thermal_relaxation: bool = False):
         methods = self.METHODS + self.SAMPLED_METHODS + self.WIDE_METHODS + self.WIDE_SAMPLED_METHODS
         if method not in methods:
             raise ValueError(f"DeviceEstimator: method = {method!r}, want one of {', '.join(methods)}")
         self._method = method
         self._max_bond, self._cutoff = _check_bond(max_bond, "DeviceEstimator"), _check_cutoff(cutoff, "DeviceEstimator")
+        if not isinstance(thermal_relaxation, bool):
+            raise ValueError(f"DeviceEstimator: thermal_relaxation = {thermal_relaxation!r}, want True or False")
+        if thermal_relaxation and method not in self.WIDE_METHODS + self.WIDE_SAMPLED_METHODS:
+            raise ValueError(f"DeviceEstimator(method={method!r}): thermal_relaxation=True belongs to method='mps' and 'mps_shots' (the "
+                             "exact and trajectory paths take a model with thermal relaxation as it is)")
+        self._relaxation = thermal_relaxation
         if method == "mps" and shots is not None:
             raise ValueError(_MPS_SHOTS)
         if method == "mps_shots" and shots is None:
@@ -378,7 +388,8 @@ class DeviceEstimator:
             noisy = self._noise is not None
             res = sample_mps_expectation_values(circuits, observables, self._noise, shots=shots, max_bond=self._max_bond,
                                                 cutoff=self._cutoff, trajectories=self._trajectories if noisy else None, seed=seed,
-                                                run_keys=default_run_keys(len(circuits), self._count << 32), device=self._device)
+                                                run_keys=default_run_keys(len(circuits), self._count << 32), device=self._device,
+                                                thermal_relaxation=self._relaxation)
             metadata = [{"variance": float(v), "shots": shots, "truncation_error_bound": float(b), "max_bond": int(k)}
                         for v, b, k in zip(res.variance.cpu().numpy(), res.error_bound.cpu().numpy(), res.bond.cpu().numpy())]
             if noisy:
@@ -392,7 +403,8 @@ class DeviceEstimator:
             noisy = self._noise is not None
             res = mps_expectation_values(circuits, observables, self._noise, max_bond=self._max_bond, cutoff=self._cutoff,
                                          trajectories=self._trajectories if noisy else None, seed=check_seed(seed, "DeviceEstimator.run"),
-                                         run_keys=default_run_keys(len(circuits), self._count << 32), device=self._device)
+                                         run_keys=default_run_keys(len(circuits), self._count << 32), device=self._device,
+                                         thermal_relaxation=self._relaxation)
             metadata = [{"truncation_error_bound": float(b), "max_bond": int(k)}
                         for b, k in zip(res.error_bound.cpu().numpy(), res.bond.cpu().numpy())]
             if noisy:
@@ -445,6 +457,9 @@ class DeviceEstimator:
                 raise ValueError(f"DeviceEstimator: circuit {k} comes with {len(p)} parameter values, the template has "
                                  f"{t.num_parameters} parameters")
         if self._method == "mps":
+            if self._relaxation:
+                raise ValueError(f"DeviceEstimator(method='mps', thermal_relaxation=True): circuit {first} is a template with free "
+                                 "parameters; thermal relaxation on templates is not built (bind the circuit first)")
             self._count += 1
             noisy = self._noise is not None
             values, _, res = bound_mps_expectation_values(

@@ -385,13 +385,17 @@ def build_mps_schedules(batch: Any, noise_factors: Sequence[float], amplifier: _
     """:func:`build_schedules` for the matrix-product-state format (``mlqem_mps_run_folded_f64``): one schedule per (noise factor,
     circuit) from the record map the noisy lowering of ``compile_mps`` keeps.  A fold unit is the gate's ``U1`` / ``U2`` record,
     possibly daggered, followed by its ``gate_noise_len`` noise records, never daggered: a coherent-error ``U2`` where the model has
-    one, then the ``DEPOL`` record (the inverse of a gate carries the gate's own coherent error and noise again).  There are no
+    one, then the ``DEPOL`` record (the inverse of a gate carries the gate's own coherent error and noise again).  A batch that
+    holds a thermal-relaxation record (``NOISE1`` / ``NOISE2``) is refused by name, here and in :func:`run_mps_folded`.  There are no
     trailing entries, readout being a table in this format, and no run numbers (``ids`` is empty: every (run, trajectory) unit is
     a workgroup).  numpy throughout."""
     if getattr(batch, "gate_ptr", None) is None:
         raise ValueError("build_mps_schedules: the batch carries no record map: the ideal lowering of compile_mps fuses gates into "
                          "bond records and has no fold units; ZNE on this path needs noise and trajectories "
                          "(compile_mps(circuits, observables, noise, trajectories=T))")
+    from .mps import refuse_relaxation_records
+
+    refuse_relaxation_records(batch, "build_mps_schedules")
     n_circ = len(batch)
     factors = tuple(float(f) for f in noise_factors)
     if not factors:
@@ -642,10 +646,11 @@ def run_mps_folded(batch: Any, schedules: Schedules, seed: int = 0, run_keys=Non
     import torch
 
     from ..native import ops
-    from .mps import MPS_BUFFER_BYTES, MpsResult, _mps_chunks
+    from .mps import MPS_BUFFER_BYTES, MpsResult, _mps_chunks, refuse_relaxation_records
     from .program import check_trajectories
     from .run import _run_keys
 
+    refuse_relaxation_records(batch, "run_mps_folded")
     if batch.trajectories is None:
         raise ValueError("run_mps_folded: the batch was lowered without trajectories; ZNE on this path needs noise and trajectories "
                          "(compile_mps(circuits, observables, noise, trajectories=T))")
@@ -738,7 +743,8 @@ def zne_run(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional
     ``noise`` and ``trajectories=T``; ``max_bond`` / ``cutoff`` / ``buffer_bytes`` as in :func:`~blackwater.sim.mps.run_mps`.  One
     lowering, :func:`build_mps_schedules`, then every (run, trajectory) unit through ``ops.sim_run_mps_folded`` in chunks that keep
     the site-tensor workspace under ``buffer_bytes``, one finish over the F * B runs and the combine.  The per-factor values are
-    means over the trajectories; :class:`ZNERun` carries their standard errors, the truncation certificates and the bonds."""
+    means over the trajectories; :class:`ZNERun` carries their standard errors, the truncation certificates and the bonds.  A
+    model with thermal relaxation is refused by name (folded runs do not take the ``thermal_relaxation=True`` of ``compile_mps``)."""
     import torch
 
     from ..native import ops

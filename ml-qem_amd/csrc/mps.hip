@@ -15,6 +15,8 @@
 // of anything that is kept below the cutoff.  Moving the orthogonality centre is the same primitive with the identity as the
 // gate (the keep rule with its cap included: a move cannot raise a bond above chi, so the cap never binds there); to the left it
 // runs on theta transposed.  A decomposition that still rotates in its last allowed sweep is counted in the unit's stats.
+// Thermal relaxation (the NOISE1 / NOISE2 records, plain runs only) is a quantum jump on one site: its Kraus operator is no unitary,
+// so the centre is moved to the qubit first, where the populations are a plain sum over that site's tensor (MpsState::relax).
 //
 // LDS: theta at chi = 32 is 64 x 64 x 16 B = 64 KiB, plus 3 KiB of tables: two workgroups a CU on the 160 KiB of gfx950.
 //
@@ -78,6 +80,51 @@ struct MpsState {
     if (letter == 1) one_site(q, o, p, p, o);
     if (letter == 2) one_site(q, o, ni, pi, o);
     if (letter == 3) one_site(q, p, o, o, n);
+  }
+
+  // Thermal relaxation (g, c, p1) of site q, which HOLDS THE ORTHOGONALITY CENTRE (the caller moved it there), with the uniform u:
+  // the populations P_s = sum_(l, r) |A[q][l, s, r]|^2 (a thread's entries in stride order, the shuffle tree, the four waves in
+  // order by every thread: the same bits everywhere), the six outcomes of the trajectory contract against their running sum, the
+  // chosen operator over the root of its own state-given probability as a real 2x2 matrix of norm t.  Every barrier here is
+  // reached by the whole workgroup: the trip count depends on the bond sizes alone and the outcome is the same in every thread.
+  __device__ __forceinline__ void relax(int q, double g, double c, double p1, double u) {
+    const int dl = dims[q], dr = dims[q + 1], items = dl * dr;
+    const sim_c* a = A + (int64_t)q * S;
+    double s0 = 0.0, s1 = 0.0;
+    for (int it0 = 0; it0 < items; it0 += kBlock) {
+      const int it = it0 + tid, ic = min(it, items - 1);
+      const int l = ic / dr, r = ic - l * dr;
+      const sim_c a0 = a[(l * 2) * chi + r], a1 = a[(l * 2 + 1) * chi + r];
+      s0 = s0 + (it < items ? norm2(a0) : 0.0);
+      s1 = s1 + (it < items ? norm2(a1) : 0.0);
+    }
+    s0 = mps_sum(s0);
+    s1 = mps_sum(s1);
+    if (lane == 0) {
+      sig[wave] = s0;
+      sig[kBlock / kWave + wave] = s1;
+    }
+    __syncthreads();   // sig is free here: bond_op and one_site end with a barrier, and the next writer stands behind one_site's
+    const double P0 = ((sig[0] + sig[1]) + sig[2]) + sig[3], P1 = ((sig[4] + sig[5]) + sig[6]) + sig[7];
+    const double sum = P0 + P1, pa = P0 / sum, pb = P1 / sum;
+    const double c2 = c * c, d = fmax(0.0, (1.0 - g) - c2), w0 = 1.0 - p1;
+    const double k0 = pa + c2 * pb, k3 = c2 * pa + pb;
+    const double pr[6] = {w0 * k0, w0 * (g * pb), w0 * (d * pb), p1 * k3, p1 * (g * pa), p1 * (d * pa)};
+    double run = 0.0;
+    int pick = -1, last = -1;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      run = run + pr[j];
+      if (pick < 0 && run > u) pick = j;
+      if (pr[j] > 0.0) last = j;
+    }
+    pick = __builtin_amdgcn_readfirstlane(pick >= 0 ? pick : max(last, 0));
+    const double den = pick == 0 ? k0 : pick == 3 ? k3 : (pick == 1 || pick == 2) ? pb : pa;
+    const double t = 1.0 / sqrt(den);   // the operator norm of what is applied (c <= 1)
+    const double m00 = pick == 0 || pick == 5 ? t : pick == 3 ? c * t : 0.0, m01 = pick == 1 ? t : 0.0, m10 = pick == 4 ? t : 0.0,
+                 m11 = pick == 3 || pick == 2 ? t : pick == 0 ? c * t : 0.0;
+    one_site(q, sim_c{m00, 0.0}, sim_c{m01, 0.0}, sim_c{m10, 0.0}, sim_c{m11, 0.0});
+    bound = t * bound;   // the certificate scales with the operator; `discarded` stays the sum of the eps
   }
 
   // The bond primitive on sites (q, q + 1): theta = A[q] A[q + 1], the 4x4 matrix g (null: none; `orient`: its basis index is
@@ -280,6 +327,14 @@ __device__ __forceinline__ int mps_draw(int index, int traj, uint32_t key_lo, ui
   return __builtin_amdgcn_readfirstlane(code);
 }
 
+// the uniform of sub-draw `sub` (1: the relaxation of the gate's first qubit, 2: of its second) of noise record `index`
+__device__ __forceinline__ double mps_uniform(int index, int sub, int traj, uint32_t key_lo, uint32_t key_hi, uint32_t seed_lo,
+                                              uint32_t seed_hi) {
+  uint32_t x[4];
+  philox4x32_10((uint32_t)index, ((uint32_t)sub << 24) | (uint32_t)traj, key_lo, key_hi, seed_lo, seed_hi, x);
+  return ((double)(x[0] >> 5) * 67108864.0 + (double)(x[1] >> 6)) * 0x1p-53;
+}
+
 // FOLD = false: circuit circ_first + cl runs its records in order (mlqem_mps_run_f64).  FOLD = true (mlqem_mps_run_folded_f64):
 // `circ_first` counts RUNS r = f * B + c, and run r walks the schedule sched[sched_ptr[r] .. sched_ptr[r + 1]) of entries
 // (k << 1) | dagger over circuit c's records; run_keys and traj_stats have one row per run.  The noise index counts the noise
@@ -388,6 +443,39 @@ __global__ __launch_bounds__(kBlock) void mps_run_kernel(int B, const int32_t* _
         ++noise_index;
         st.pauli(orient ? q + 1 : q, code & 3);    // the letter of the gate's first qubit
         st.pauli(orient ? q : q + 1, code >> 2);   // and of its second
+      }
+    } else if (kind == MLQEM_MPS_OP_NOISE1 || (kind == MLQEM_MPS_OP_NOISE2 && n >= 2)) {
+      if constexpr (!FOLD) {   // the host refuses these kinds on folded runs: the folded kernel skips them as any unknown kind
+        // the centre to site `to`, one site at a time: the two loops of a U2 record
+        auto move_to = [&](int to) {
+          while (centre < to) {
+            st.template bond_op<false>(centre, nullptr, 0, false);
+            ++centre;
+          }
+          while (centre > to) {
+            st.template bond_op<false>(centre - 1, nullptr, 0, true);
+            --centre;
+          }
+        };
+        // one record, one noise index: the depolarising draw of DEPOL1 / DEPOL2 (sub-draw 0), then one relaxation per qubit.  On a
+        // pair the SITE order follows the centre (the lower site first where the centre is at or below it, else the upper one:
+        // after a U2 the centre is on the upper site, which then costs no move); the sub-draw and the triple follow the GATE's
+        // qubit: the site q + orient is q0 (sub-draw 1, m[1 .. 3]), the other q1 (sub-draw 2, m[4 .. 6])
+        const int two = kind == MLQEM_MPS_OP_NOISE2 ? 1 : 0;
+        const int q = __builtin_amdgcn_readfirstlane(min(max(op.y, 0), n - 1 - two));
+        const int code = mps_draw(noise_index, traj, key_lo, key_hi, seed_lo, seed_hi, two != 0, m[0]);
+        st.pauli(two && orient ? q + 1 : q, code & 3);
+        st.pauli(orient ? q : q + 1, two ? code >> 2 : 0);
+        const int upper_first = two && centre > q ? 1 : 0;   // workgroup-uniform, as the centre is
+#pragma unroll 1
+        for (int step = 0; step <= two; ++step) {
+          const int up = two ? step ^ upper_first : 0;   // this step's site is q + up
+          const int second = two ? up ^ orient : 0;      // 0: the gate's q0, 1: its q1
+          move_to(q + up);
+          st.relax(q + up, m[1 + 3 * second], m[2 + 3 * second], m[3 + 3 * second],
+                   mps_uniform(noise_index, 1 + second, traj, key_lo, key_hi, seed_lo, seed_hi));
+        }
+        ++noise_index;
       }
     }
   }

@@ -53,6 +53,9 @@ def main():
                     help="with --mps-labels: the noisy labels are taken under the device model with thermal relaxation "
                          "(NoiseModel.from_backend(..., thermal_relaxation=True): T1, T2 and gate times of the synthetic backend), "
                          "unravelled into quantum jumps on the matrix-product states; about twice the decompositions")
+    ap.add_argument("--mps-twirl", action="store_true",
+                    help="with --mps-labels: the noisy labels are taken with every cx Pauli-twirled on the device, one draw per "
+                         "trajectory and gate (the circuits are lowered once), as the reference's twirled ZNE labels are")
     args = ap.parse_args()
     if args.clifford_labels and args.mps_labels:
         ap.error("--clifford-labels and --mps-labels choose different circuits: pass one")
@@ -60,6 +63,8 @@ def main():
         ap.error("--mps-shots draws from the matrix-product states of --mps-labels: pass both")
     if args.mps_relaxation and not args.mps_labels:
         ap.error("--mps-relaxation changes the noise model of --mps-labels: pass both")
+    if args.mps_twirl and not args.mps_labels:
+        ap.error("--mps-twirl twirls the gates of --mps-labels: pass both")
 
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -74,7 +79,7 @@ def main():
                                                f"mlqem_example_{args.qubits}q" + ("_clifford" if args.clifford_labels else "")
                                                + (f"_mps{args.mps_bond}" if args.mps_labels else "")
                                                + (f"_shots{args.mps_shots}" if args.mps_shots is not None else "")
-                                               + ("_relax" if args.mps_relaxation else ""))
+                                               + ("_relax" if args.mps_relaxation else "") + ("_twirl" if args.mps_twirl else ""))
     paths = [os.path.join(shard_dir, f"part{k}.mlqs") for k in range(2)]
     if rank == 0 and not all(os.path.exists(p) for p in paths):
         os.makedirs(shard_dir, exist_ok=True)
@@ -94,7 +99,8 @@ def main():
                         for s in range(1, args.steps + 1) for j in rng.uniform(0.0, 0.66 * np.pi, size=args.n_j)]
             noise = sim.NoiseModel.from_backend(synthetic_backend(args.qubits, "cx"), thermal_relaxation=args.mps_relaxation)
             c = encode_corpus(circuits, args.qubits, two_q="cx", simulate=noise, device=dev, mps_bond=args.mps_bond,
-                              trajectories=args.mps_trajectories, mps_shots=args.mps_shots, mps_relaxation=args.mps_relaxation)
+                              trajectories=args.mps_trajectories, mps_shots=args.mps_shots, mps_relaxation=args.mps_relaxation,
+                              mps_twirl=args.mps_twirl or None)
             print(f"MPS labels at bond {args.mps_bond}: the worst certificate of the corpus is B = {c['mps_error_bound']:.3e} "
                   f"(every ideal label is within 2 B of the exact <Z>)")
         else:

@@ -2027,6 +2027,25 @@ int mlqem_clifford_sample_f64(int64_t n_circuits, const int32_t* n_qubits, const
  *                       Because q holds the centre the other sites stay orthonormal: the state stays canonical, and normalised
  *                       up to rounding.  The applied matrix has operator norm t (c <= 1), and `error_bound` <- t * `error_bound`
  *                       after each relaxation; `discarded` is left alone (see Certificate).
+ *   MLQEM_MPS_OP_TWIRL_OPEN / MLQEM_MPS_OP_TWIRL_CLOSE on the bond, orientation and q0 = site + orientation as for DEPOL2 (both
+ *                       kernels): a Pauli twirl of what stands between them, drawn per (run, trajectory).  The unit keeps a TWIRL
+ *                       INDEX j, 0 at its start, beside and independent of the noise index, and the code of its latest OPEN (0
+ *                       before the first).  OPEN reads no params: it draws code = x0 >> 28 (0 .. 15, uniform, the all-identity
+ *                       code 0 included) of Philox4x32-10 at the counter (j, 3 << 24 | t, run_key & 0xffffffff, run_key >> 32)
+ *                       under the seed's key (sub-draw 3: the depolarising draw is 0, the relaxations 1 and 2, so no other draw
+ *                       changes and j may equal a noise index), and applies the letter code & 3 on q0, then code >> 2 on q1,
+ *                       as DEPOL2 applies its letters (identity letters: nothing).  An integer: no threshold to sit near.
+ *                       CLOSE reads table[0 .. 15] (16 float64; entry c: the code of the pair P' with P' ~ G P_c G^dagger for the
+ *                       ideal gate G, signs and phases dropped -- a trajectory is a pure state), applies the letters of
+ *                       table[code of the latest OPEN], the entry clamped to 0 .. 15, in the same order, then ++j.  j therefore
+ *                       counts the CLOSE records AS EXECUTED: every pass of a folded gate draws its own twirl.  Twirls are
+ *                       one-site unitaries: no decomposition, no centre move, nothing added to `discarded` or `error_bound`.
+ *                       A dagger bit on either kind is ignored (the host never sets it).  The site is clamped to n - 2; both
+ *                       kinds do nothing where n < 2.  A twirled program equals, bit for bit and per trajectory, the program in
+ *                       which every OPEN / CLOSE is written out as the U1 records of its two letters (q0's, then q1's, identity
+ *                       letters left out, entries 0, +-1, +-i), and the folded contract below extends to the two kinds verbatim.
+ *                       mlqem_mps_bind_f64 does not know them (it copies ONE value of a kind it does not know): the host refuses
+ *                       such a batch there.
  *   Any other kind is skipped; a two-site record of a one-qubit circuit is skipped.
  * u of noise record i, sub-draw s, trajectory t: Philox4x32-10 with the key (seed & 0xffffffff, seed >> 32) and the counter
  *   (i, s << 24 | t, run_key & 0xffffffff, run_key >> 32), run_key = run_keys[c], t < 2^20; s = 0 for every depolarising draw (the
@@ -2101,7 +2120,8 @@ int mlqem_clifford_sample_f64(int64_t n_circuits, const int32_t* n_qubits, const
  *   Draws.  The noise index of the draw contract is the ORDINAL of the noise entry as this run executes it (0, 1, 2, ...: an entry
  *     that is scheduled three times draws three times), and the key is run_keys[r], int64 [F * B].  With these two rules a run
  *     equals, bit for bit, mlqem_mps_run_f64 on the program obtained by writing its schedule out (daggered matrices
- *     conjugate-transposed on the host), under the same key.
+ *     conjugate-transposed on the host), under the same key.  The twirl index follows the same rule: it is the ordinal of the
+ *     TWIRL_CLOSE entry as this run executes it, so a fold unit OPEN, gate | dagger, noise records, CLOSE draws a twirl per pass.
  *   traj_stats is [trajectories][F * B][MLQEM_MPS_STATS], a row per run.
  *   Clamping.  Schedule offsets are clamped to n_sched, k to the circuit's records (a circuit without records skips its
  *     entries), run numbers to F * B; an empty schedule leaves |0..0>; a malformed schedule computes garbage inside the unit's own
@@ -2122,6 +2142,8 @@ int mlqem_clifford_sample_f64(int64_t n_circuits, const int32_t* n_qubits, const
 #define MLQEM_MPS_OP_DEPOL2 7
 #define MLQEM_MPS_OP_NOISE1 10
 #define MLQEM_MPS_OP_NOISE2 11
+#define MLQEM_MPS_OP_TWIRL_OPEN 17  /* free in the MLQEM_SIM_OP_* space too (12 .. 16 are the parameterised kinds) */
+#define MLQEM_MPS_OP_TWIRL_CLOSE 18
 size_t mlqem_mps_workspace_bytes(int64_t max_qubits, int64_t max_bond, int64_t n_units);
 int mlqem_mps_run_f64(int64_t n_circuits, const int32_t* n_qubits, const int64_t* op_ptr, const mlqem_sim_op* ops, int64_t n_ops,
                       const double* params, int64_t n_params, const int64_t* run_keys, int64_t circ_first, int64_t circ_count,

@@ -64,7 +64,8 @@ def exp_value_generator(backend: Any, n_qubits: int, circuit_depth: int, pauli_t
                         max_entries: int = 1000, seed: int = 0, batch: int = 256, device="cuda", shots: Optional[int] = None,
                         sample_ideal: bool = False, trajectories: Optional[int] = None,
                         frame_shots: Optional[int] = None, mps_bond: Optional[int] = None,
-                        mps_shots: Optional[int] = None, mps_relaxation: bool = False) -> Iterator[ExpValueEntry]:
+                        mps_shots: Optional[int] = None, mps_relaxation: bool = False,
+                        mps_twirl: Any = None) -> Iterator[ExpValueEntry]:
     """Yields ``max_entries`` dataset entries of random circuits with simulated labels (reference: exp_val.py:92-170, which
     transpiles ``qiskit.circuit.random.random_circuit`` and runs Aer twice per circuit).
 
@@ -103,7 +104,14 @@ def exp_value_generator(backend: Any, n_qubits: int, circuit_depth: int, pauli_t
 
     ``mps_relaxation`` (default ``False``; with ``mps_bond``): the noisy value is taken under
     ``NoiseModel.from_backend(backend, readout=False, thermal_relaxation=True)`` -- Aer's device model restated -- which the MPS
-    path unravels into quantum jumps (``thermal_relaxation=True`` there).  Without ``mps_bond`` it is refused by name."""
+    path unravels into quantum jumps (``thermal_relaxation=True`` there).  Without ``mps_bond`` it is refused by name.
+
+    ``mps_twirl`` (default ``None``; with ``mps_bond``; ``True`` or gate names): the noisy value is taken with the two-qubit gates
+    Pauli-twirled on the device (``pauli_twirl=`` there: one draw per trajectory and gate).  Without ``mps_bond`` it is refused by
+    name."""
+    if mps_twirl is not None and mps_twirl is not False and mps_bond is None:
+        raise ValueError("exp_value_generator: mps_twirl without mps_bond (the twirl is drawn per trajectory on the "
+                         "matrix-product-state path: pass mps_bond=chi)")
     if not isinstance(mps_relaxation, bool):
         raise ValueError(f"exp_value_generator: mps_relaxation = {mps_relaxation!r}, want True or False")
     if mps_relaxation and mps_bond is None:
@@ -164,11 +172,12 @@ def exp_value_generator(backend: Any, n_qubits: int, circuit_depth: int, pauli_t
             if mps_shots is not None:
                 noisy = _to_host(sim.sample_mps_expectation_values(circuits, observables, noise, shots=mps_shots, max_bond=mps_bond,
                                                                    trajectories=trajectories, seed=seed, run_keys=keys,
-                                                                   device=device, thermal_relaxation=mps_relaxation).values)
+                                                                   device=device, thermal_relaxation=mps_relaxation,
+                                                                   pauli_twirl=mps_twirl).values)
             else:
                 noisy = _to_host(sim.mps_expectation_values(circuits, observables, noise, max_bond=mps_bond, trajectories=trajectories,
                                                             seed=seed, run_keys=keys, device=device,
-                                                            thermal_relaxation=mps_relaxation).values)
+                                                            thermal_relaxation=mps_relaxation, pauli_twirl=mps_twirl).values)
         elif trajectories is not None:
             keys = np.arange(done, done + count, dtype=np.int64)   # the entry's number, as on the shots path
             ideal = _to_host(sim.expectation_values(circuits, observables, None, device)[0])

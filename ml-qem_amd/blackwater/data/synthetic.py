@@ -241,7 +241,7 @@ def pauli_twirl(circ: Circuit, seed: int, two_q=("cx", "ecr")) -> Circuit:
 def encode_corpus(circuits, nq: int, two_q: str = "cx", seed: int = 7, exp_value_size: int = 1,
                   add_self_loops: bool = True, simulate=None, device="cuda", shots=None, sample_ideal: bool = False,
                   clifford: bool = False, trajectories=None, frame_shots=None, mps_bond=None, mps_shots=None,
-                  mps_relaxation: bool = False) -> Dict[str, list]:
+                  mps_relaxation: bool = False, mps_twirl=None) -> Dict[str, list]:
     """Arena-ready arrays (same keys as :func:`tfim_corpus`) for arbitrary circuits, encoded by the native encoder.
 
     ``simulate=None``: synthetic labels (a uniform draw and a made-up decay).  ``simulate=`` a ``blackwater.sim.NoiseModel``: ``y``
@@ -273,7 +273,10 @@ def encode_corpus(circuits, nq: int, two_q: str = "cx", seed: int = 7, exp_value
     (``NoiseModel.from_backend(..., thermal_relaxation=True)``), which the MPS path then unravels into quantum jumps
     (``sim.mps_expectation_values(..., thermal_relaxation=True)``; the centre moves to every relaxed qubit).  ``"mps_error_bound"``
     is then the mean of per-trajectory certificates, each conditional on the jumps drawn (|<Z> - exact| <= 4 B per trajectory).
-    Without ``mps_bond`` it is refused by name."""
+    Without ``mps_bond`` it is refused by name.
+    ``mps_twirl`` (with ``mps_bond``; default ``None``; ``True`` or gate names): the noisy MPS values are taken with the two-qubit
+    gates Pauli-twirled on the device (``sim.mps_expectation_values(..., pauli_twirl=)``: one draw per trajectory and gate, the
+    circuits lowered once).  Without ``mps_bond`` it is refused by name."""
     from .circuit import circuit_to_qasm
     from .native_encoder import NativeEncoder
 
@@ -301,6 +304,9 @@ def encode_corpus(circuits, nq: int, two_q: str = "cx", seed: int = 7, exp_value
         raise ValueError(f"encode_corpus: mps_relaxation = {mps_relaxation!r}, want True or False")
     if mps_relaxation and mps_bond is None:
         raise ValueError("encode_corpus: mps_relaxation without mps_bond (thermal relaxation is unravelled on the matrix-product-state "
+                         "path: pass mps_bond=chi)")
+    if mps_twirl is not None and mps_twirl is not False and mps_bond is None:
+        raise ValueError("encode_corpus: mps_twirl without mps_bond (the twirl is drawn per trajectory on the matrix-product-state "
                          "path: pass mps_bond=chi)")
     if mps_bond is not None:
         if shots is not None or frame_shots is not None:
@@ -386,11 +392,11 @@ def encode_corpus(circuits, nq: int, two_q: str = "cx", seed: int = 7, exp_value
                     res = sim.sample_mps_expectation_values([kept[k] for k in line], labels, simulate, shots=mps_shots, max_bond=mps_bond,
                                                             trajectories=trajectories, seed=seed,
                                                             run_keys=np.asarray(line, dtype=np.int64), device=device,
-                                                            thermal_relaxation=mps_relaxation)
+                                                            thermal_relaxation=mps_relaxation, pauli_twirl=mps_twirl)
                 else:
                     res = sim.mps_expectation_values([kept[k] for k in line], labels, simulate, max_bond=mps_bond,
                                                      trajectories=trajectories, seed=seed, run_keys=np.asarray(line, dtype=np.int64),
-                                                     device=device, thermal_relaxation=mps_relaxation)
+                                                     device=device, thermal_relaxation=mps_relaxation, pauli_twirl=mps_twirl)
                 under, mps_error_bound = res.values.cpu().numpy(), max(mps_error_bound, float(res.error_bound.max()))
                 for j, k in enumerate(line):
                     noisy[k] = np.full(exp_value_size, under[j])

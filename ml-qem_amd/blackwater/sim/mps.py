@@ -10,7 +10,9 @@ string (its probabilities do not depend on the state), readout noise is folded i
 ``thermal_relaxation=True`` a model with thermal relaxation (``NoiseModel.from_backend(..., thermal_relaxation=True)``) is taken too:
 a ``NOISE1`` / ``NOISE2`` record per relaxed gate, unravelled into quantum jumps at the orthogonality centre; ``error_bound`` is then
 a per-trajectory certificate, conditional on the jumps drawn, with the constant 4 in the place of 2.  Templates and folded runs
-refuse such a model by name.
+refuse such a model by name.  With ``pauli_twirl=`` (noisy lowering) the two-qubit gates cx, cz, ecr, swap are Pauli-twirled on the
+device: ``TWIRL_OPEN`` / ``TWIRL_CLOSE`` records around the gate and its noise, one draw of 16 Pauli pairs per (run, trajectory) and
+gate, the circuits lowered once; plain runs, shots and folded runs take such a batch, templates refuse it by name.
 
 ``compile_mps_shots`` / ``run_mps_shots`` / ``sample_mps_expectation_values`` draw measurement shots from the same states
 (``mlqem_mps_sample_f64``: perfect sampling, one sweep over the sites per shot), ``mps_counts`` gives the count dictionaries.
@@ -33,6 +35,9 @@ MPS_BUFFER_BYTES = 4 << 30   # the site-tensor workspace of one launch stays und
 DEFAULT_CUTOFF = 1e-26   # relative weight below which a column is dropped: the numerically-zero columns of a rank-deficient theta
 OP_MPS_U1, OP_MPS_U2, OP_MPS_DEPOL1, OP_MPS_DEPOL2 = 0, 5, 6, 7   # MLQEM_MPS_OP_*
 OP_MPS_NOISE1, OP_MPS_NOISE2 = 10, 11   # depolarising, then thermal relaxation of the gate's qubits (thermal_relaxation=True)
+OP_MPS_TWIRL_OPEN, OP_MPS_TWIRL_CLOSE = 17, 18   # a Pauli twirl around a two-qubit gate and its noise (pauli_twirl=)
+TWIRL_GATES = ("cx", "cz", "ecr", "swap")   # the self-inverse two-qubit Cliffords: one table serves the gate and its dagger
+TWIRL_DEFAULT = ("cx", "cz", "ecr")         # what pauli_twirl=True twirls
 
 _PERMUTATION = {"cx": (0, 3, 2, 1), "swap": (0, 2, 1, 3)}   # column j of the matrix has its 1 in row _PERMUTATION[name][j]
 
@@ -101,6 +106,9 @@ class MpsBatch:
     gate_record: Optional[np.ndarray] = None      # int32 [n_gates]: the gate's own U1 / U2 record
     gate_noise: Optional[np.ndarray] = None       # int32 [n_gates]: the first noise record after it
     gate_noise_len: Optional[np.ndarray] = None   # int32 [n_gates]: 0, 1 (DEPOL* / NOISE*) or 2 (a coherent U2, then DEPOL* / NOISE*)
+    # with ``pauli_twirl=`` (else None): the TWIRL_OPEN record before a twirled gate and the TWIRL_CLOSE record after its noise
+    gate_twirl_open: Optional[np.ndarray] = None    # int32 [n_gates]
+    gate_twirl_close: Optional[np.ndarray] = None   # int32 [n_gates]
 
     def __len__(self) -> int:
         return int(self.n_qubits.shape[0])
@@ -129,6 +137,62 @@ def refuse_relaxation_records(batch: Any, who: str) -> None:
         raise ValueError(f"{who}: record {int(hit[0])} of the batch is a thermal-relaxation record (NOISE1 / NOISE2, "
                          "compile_mps(..., thermal_relaxation=True)); folded runs and templates on the matrix-product-state path "
                          "take depolarising + readout models only (relaxation there is not built: run_mps runs such a batch)")
+
+
+def refuse_twirl_records(batch: Any, who: str) -> None:
+    """Raises where a batch holds a ``TWIRL_OPEN`` / ``TWIRL_CLOSE`` record (``compile_mps(..., pauli_twirl=)``, or built by hand):
+    the bind kernel copies one value of a kind it does not know, and a ``TWIRL_CLOSE`` record has a table of 16."""
+    kinds = np.asarray(batch.ops).reshape(-1, 4)[:, 0]
+    hit = np.flatnonzero((kinds == OP_MPS_TWIRL_OPEN) | (kinds == OP_MPS_TWIRL_CLOSE))
+    if hit.size:
+        raise ValueError(f"{who}: record {int(hit[0])} of the batch is a Pauli-twirl record (TWIRL_OPEN / TWIRL_CLOSE, "
+                         "compile_mps(..., pauli_twirl=)); templates on the matrix-product-state path do not take twirled "
+                         "batches (mlqem_mps_bind_f64 copies one value of a record it does not know, a TWIRL_CLOSE table has 16: "
+                         "not built; run_mps and run_mps_folded run such a batch)")
+
+
+def _check_twirl(pauli_twirl: Any, who: str) -> tuple:
+    """The names ``pauli_twirl=`` asks to twirl, in the order of :data:`TWIRL_GATES`: () for ``False`` / ``None``."""
+    if pauli_twirl is None or pauli_twirl is False or (isinstance(pauli_twirl, np.bool_) and not pauli_twirl):
+        return ()
+    if pauli_twirl is True or isinstance(pauli_twirl, np.bool_):
+        return TWIRL_DEFAULT
+    if isinstance(pauli_twirl, str):
+        pauli_twirl = (pauli_twirl,)
+    try:
+        names = [g for g in pauli_twirl]
+    except TypeError:
+        names = None
+    if names is None or not names or not all(isinstance(g, str) for g in names):
+        raise ValueError(f"{who}: pauli_twirl = {pauli_twirl!r}, want True, False or a sequence of gate names from "
+                         f"{' '.join(TWIRL_GATES)}")
+    for g in names:
+        if g not in TWIRL_GATES:
+            raise ValueError(f"{who}: pauli_twirl names {g!r}; only the self-inverse two-qubit Clifford gates {' '.join(TWIRL_GATES)} "
+                             "are twirled (folding a gate with G^dagger = G needs one table)")
+    return tuple(g for g in TWIRL_GATES if g in names)
+
+
+_MPS_TO_CLIFFORD = (0, 1, 3, 2)   # a letter 0 I, 1 X, 2 Y, 3 Z of this path as a letter of ``clifford`` (0 I, 1 X, 2 Z, 3 Y), and back
+
+
+def _swap_yz(code: int) -> int:
+    return _MPS_TO_CLIFFORD[code & 3] | _MPS_TO_CLIFFORD[code >> 2] << 2
+
+
+def twirl_table(name: str) -> List[int]:
+    """``table[code]`` of a ``TWIRL_CLOSE`` record: the code (letter ``& 3`` on q0, ``>> 2`` on q1; 0 I, 1 X, 2 Y, 3 Z) of the pair
+    P' with P' ~ G P G^dagger for the gate's own matrix G, signs dropped.  Over the gate's (q0, q1): no orientation enters."""
+    from .clifford import conjugation_table
+
+    if name not in TWIRL_GATES:
+        raise ValueError(f"twirl_table: {name!r} is not one of {' '.join(TWIRL_GATES)}")
+    g = _matrix4(name, ())
+    back, forth = conjugation_table(g), conjugation_table(g.conj().T)   # G^dagger P G and G P G^dagger
+    assert back is not None and back == forth, f"{name} is not a self-inverse Clifford gate"
+    table = [0] + [_swap_yz(forth[_swap_yz(code) - 1][0]) for code in range(1, 16)]
+    assert sorted(table) == list(range(16))
+    return table
 
 
 def _check_bond(max_bond: Any, who: str) -> int:
@@ -210,8 +274,13 @@ class _Lowering:
     ``Param`` of every op of a template, or None) it also keeps, for every record whose matrix depends on a parameter, the factor
     program of the record and the occurrences of the parameters."""
 
-    def __init__(self, who, circuits, observables, noise, trajectories, max_bond, cutoff, thermal_relaxation=False):
+    def __init__(self, who, circuits, observables, noise, trajectories, max_bond, cutoff, thermal_relaxation=False, pauli_twirl=None):
         self.who = who
+        self.twirl = _check_twirl(pauli_twirl, who)
+        if self.twirl and (noise is None or trajectories is None):
+            raise ValueError(f"{who}: pauli_twirl on the ideal lowering (gates are fused into bond records there, and a twirl of an "
+                             "ideal gate changes nothing: twirling needs noise= and trajectories=)")
+        self.twirl_tables = {g: [float(v) for v in twirl_table(g)] for g in self.twirl}
         if not isinstance(thermal_relaxation, (bool, np.bool_)):
             raise ValueError(f"{who}: thermal_relaxation = {thermal_relaxation!r}, want True or False")
         self.relaxation = bool(thermal_relaxation)
@@ -232,6 +301,7 @@ class _Lowering:
         self.term_circ, self.term_off, self.letters, self.coeffs, self.term_ptr = [], [], [], [], [0]
         self.site_ptr, self.readout, self.n_noise_all, self.abs_coeff, self.measured_all, self.n_qubits = [0], [], [], [], [], []
         self.gate_ptr, self.gate_name, self.gate_record, self.gate_noise, self.gate_noise_len = [0], [], [], [], []
+        self.gate_twirl_open, self.gate_twirl_close = [], []
         self.name_id = {g: j for j, g in enumerate(SUPPORTED_GATES)}
         # the factor programs (templates): global record index -> its chain; the occurrences [record, factor, parameter, scale] with
         # the record relative to its circuit's first, in circuit order; pool_ptr: a circuit's slice of ``params``
@@ -308,6 +378,7 @@ class _Lowering:
                 raise ValueError(f"{where}: op {i} ({name}) has the non-finite angle {p!r}")
             par = free[i] if free is not None else None   # the gate's free parameter: its matrix is a PARAM factor
             first, rec, noi, noi_len = op_ptr[-1], -1, -1, 0
+            t_open = t_close = -1
             if width == 2:
                 q0, q1 = op.qubits
                 if q0 == q1:
@@ -318,6 +389,9 @@ class _Lowering:
                 lower, orient = min(q0, q1), int(q0 > q1)
                 m = _matrix4(name, p)
                 if noisy:
+                    if name in self.twirl_tables:   # OPEN, the gate, its noise, CLOSE: the twirl acts on the noisy gate as a whole
+                        t_open = len(ops) - first
+                        emit(OP_MPS_TWIRL_OPEN, lower, orient, [])
                     rec = len(ops) - first
                     chain = None
                     if par is not None:
@@ -396,6 +470,11 @@ class _Lowering:
                     else:
                         emit(OP_MPS_DEPOL1, op.qubits[0], 0, [float(lam)])
                     n_noise += 1
+                if t_open >= 0:
+                    t_close = len(ops) - first
+                    emit(OP_MPS_TWIRL_CLOSE, min(op.qubits), int(op.qubits[0] > op.qubits[1]), self.twirl_tables[name])
+                self.gate_twirl_open.append(t_open)
+                self.gate_twirl_close.append(t_close)
                 self.gate_name.append(self.name_id[name])
                 self.gate_record.append(rec)
                 self.gate_noise.append(noi)
@@ -473,12 +552,14 @@ class _Lowering:
             gate_name=np.asarray(self.gate_name, dtype=np.int16) if noisy else None,
             gate_record=np.asarray(self.gate_record, dtype=np.int32) if noisy else None,
             gate_noise=np.asarray(self.gate_noise, dtype=np.int32) if noisy else None,
-            gate_noise_len=np.asarray(self.gate_noise_len, dtype=np.int32) if noisy else None)
+            gate_noise_len=np.asarray(self.gate_noise_len, dtype=np.int32) if noisy else None,
+            gate_twirl_open=np.asarray(self.gate_twirl_open, dtype=np.int32) if self.twirl else None,
+            gate_twirl_close=np.asarray(self.gate_twirl_close, dtype=np.int32) if self.twirl else None)
 
 
 def compile_mps(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None,
                 trajectories: Optional[int] = None, max_bond: int = MAX_BOND, cutoff: float = DEFAULT_CUTOFF,
-                thermal_relaxation: bool = False) -> MpsBatch:
+                thermal_relaxation: bool = False, pauli_twirl: Any = None) -> MpsBatch:
     """Lowers ``circuits`` with one observable each to one :class:`MpsBatch`.  Site = qubit index.
 
     ``noise=None`` (ideal): one ``U2`` record per bond visit -- a run of gates confined to one bond (its one-qubit gates included)
@@ -495,11 +576,18 @@ def compile_mps(circuits: Sequence[Any], observables: Sequence[Any], noise: Opti
     carried through the same operators (include/mlqem_hip.h).  Such a batch is refused by ``compile_mps_templates`` (the keyword
     does not exist there) and by the folded runs of ``blackwater.sim.zne``.
 
+    ``pauli_twirl`` (noisy lowering only; ``True``: cx, cz and ecr; or names from cx, cz, ecr, swap) wraps every such gate into
+    ``TWIRL_OPEN``, the gate's ``U2``, its coherent-error ``U2`` and ``DEPOL2`` / ``NOISE2`` where the model has them,
+    ``TWIRL_CLOSE`` (the table of :func:`twirl_table`): the device draws one of the 16 Pauli pairs per (run, trajectory) and gate,
+    applies it before and its image under the ideal gate after, P' (Lambda G) P = (P' Lambda P') G -- the circuits are lowered
+    once, and the mean over the trajectories is the value under the twirled noise.  ``n_noise`` does not count twirl records;
+    ``gate_twirl_open`` / ``gate_twirl_close`` locate them.  ``run_mps_bound`` refuses such a batch.
+
     Raises ``ValueError`` naming the offender for what ``compile_programs`` refuses (unknown gates, parameter counts, qubits out of
     range or used after their measurement, non-finite angles, malformed terms) and for: a two-qubit gate on qubits that are no
     neighbours, ``max_bond`` outside 1 .. 32, ``noise`` without ``trajectories`` or the reverse, a model with thermal relaxation
     without ``thermal_relaxation=True``, readout noise together with an X / Y term, a circuit over 512 qubits."""
-    low = _Lowering("compile_mps", circuits, observables, noise, trajectories, max_bond, cutoff, thermal_relaxation)
+    low = _Lowering("compile_mps", circuits, observables, noise, trajectories, max_bond, cutoff, thermal_relaxation, pauli_twirl)
     for k, (obj, obs) in enumerate(zip(low.circuits, low.observables)):
         low.add(k, Circuit.from_any(obj), obs)
     return MpsBatch(**low.fields())
@@ -675,12 +763,14 @@ def run_mps(batch: MpsBatch, seed: int = 0, run_keys=None, device="cuda", keep_t
 
 def mps_expectation_values(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None,
                            max_bond: int = MAX_BOND, cutoff: float = DEFAULT_CUTOFF, trajectories: Optional[int] = None, seed: int = 0,
-                           run_keys=None, device="cuda", thermal_relaxation: bool = False) -> MpsResult:
+                           run_keys=None, device="cuda", thermal_relaxation: bool = False, pauli_twirl: Any = None) -> MpsResult:
     """Expectation values of ``observables[k]`` after ``circuits[k]`` by matrix-product states of bond at most ``max_bond``:
     circuits of up to 512 qubits whose two-qubit gates act on neighbours, any angle.  ``noise`` + ``trajectories``: the values
     under a depolarising + readout model, as means over Pauli-insertion trajectories with their standard errors; with
-    ``thermal_relaxation=True`` also under a model with thermal relaxation (quantum jumps, :func:`compile_mps`)."""
-    return run_mps(compile_mps(circuits, observables, noise, trajectories, max_bond, cutoff, thermal_relaxation), seed, run_keys, device)
+    ``thermal_relaxation=True`` also under a model with thermal relaxation (quantum jumps, :func:`compile_mps`);
+    ``pauli_twirl`` twirls the named two-qubit gates on the device (:func:`compile_mps`)."""
+    return run_mps(compile_mps(circuits, observables, noise, trajectories, max_bond, cutoff, thermal_relaxation, pauli_twirl), seed,
+                   run_keys, device)
 
 
 # ---- templates: bound on the device ---------------------------------------------------------------------------------------------------
@@ -713,6 +803,7 @@ class MpsBoundRun:
         who = "run_mps_bound"
         self.batch, self.seed = batch, check_seed(seed, who)
         refuse_relaxation_records(batch, who)
+        refuse_twirl_records(batch, who)
         self.n_traj = 1 if batch.trajectories is None else check_trajectories(batch.trajectories, who)
         buffer_bytes = MPS_BUFFER_BYTES if buffer_bytes is None else int(buffer_bytes)
         if buffer_bytes < 1:
@@ -1024,14 +1115,15 @@ class MpsShotsBatch:
 
 def compile_mps_shots(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None,
                       trajectories: Optional[int] = None, max_bond: int = MAX_BOND, cutoff: float = DEFAULT_CUTOFF,
-                      thermal_relaxation: bool = False) -> MpsShotsBatch:
+                      thermal_relaxation: bool = False, pauli_twirl: Any = None) -> MpsShotsBatch:
     """The lowering of :func:`compile_mps` plus the measurement groups of :func:`~blackwater.sim.measurement_groups`: one basis
     letter per (group, site) (Z where no term of the group touches the site), the ``flip`` table of the measured qubits' readout
     noise, a support mask per term and the group of each term.  What ``compile_mps`` refuses stays refused, by the same messages
     (X or Y terms beside readout noise, thermal relaxation without ``thermal_relaxation=True``, gates on qubits that are no
-    neighbours, ...); also refused: a circuit whose terms need more than 4 096 measurement groups."""
+    neighbours, ...); also refused: a circuit whose terms need more than 4 096 measurement groups.  ``pauli_twirl`` is
+    ``compile_mps``'s: the shots of a trajectory are drawn from its twirled state."""
     circuits, observables = list(circuits), list(observables)
-    base = compile_mps(circuits, observables, noise, trajectories, max_bond, cutoff, thermal_relaxation)   # every check and refusal
+    base = compile_mps(circuits, observables, noise, trajectories, max_bond, cutoff, thermal_relaxation, pauli_twirl)   # every check and refusal
     group_ptr, group_circ, group_off, basis, ref_ptr = [0], [], [], [], [0]
     gterm_ptr, gterm, term_mask, term_group, masks, flip = [0], [], [], [], [], []
     max_groups = 1
@@ -1169,20 +1261,20 @@ def run_mps_shots(batch: MpsShotsBatch, shots: int, seed: int = 0, run_keys=None
 def sample_mps_expectation_values(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None, *,
                                   shots: int = None, trajectories: Optional[int] = None, max_bond: int = MAX_BOND,
                                   cutoff: float = DEFAULT_CUTOFF, seed: int = 0, run_keys=None, return_bits: bool = False,
-                                  device="cuda", thermal_relaxation: bool = False) -> MpsShotsResult:
+                                  device="cuda", thermal_relaxation: bool = False, pauli_twirl: Any = None) -> MpsShotsResult:
     """Expectation values of ``observables[k]`` after ``circuits[k]`` estimated from ``shots`` measurement outcomes per measurement
     basis, drawn from the matrix-product state of bond at most ``max_bond``: circuits of up to 512 qubits whose two-qubit gates act on
     neighbours, any angle; ideal, or under a depolarising + readout ``noise`` model with ``trajectories`` (one with thermal
-    relaxation: ``thermal_relaxation=True``).  The limit of every estimate is the value :func:`mps_expectation_values` gives."""
+    relaxation: ``thermal_relaxation=True``; ``pauli_twirl``: :func:`compile_mps`).  The limit of every estimate is the value
+    :func:`mps_expectation_values` gives."""
     from .program import check_shots
 
     if shots is None:
         raise ValueError("sample_mps_expectation_values: shots is required (an int in 1 .. 2^20); mps_expectation_values gives the "
                          "values without shot noise")
     shots = check_shots(shots, "sample_mps_expectation_values")
-    return run_mps_shots(compile_mps_shots(circuits, observables, noise, trajectories, max_bond, cutoff, thermal_relaxation), shots, seed,
-                         run_keys,
-                         return_bits, device)
+    return run_mps_shots(compile_mps_shots(circuits, observables, noise, trajectories, max_bond, cutoff, thermal_relaxation, pauli_twirl),
+                         shots, seed, run_keys, return_bits, device)
 
 
 def mps_counts(result: MpsShotsResult, k: int) -> List[Dict[str, int]]:

@@ -15,7 +15,7 @@ from .frames import sample_clifford_expectation_values
 from .program import (MAX_QUBITS_DENSITY, MAX_QUBITS_VECTOR, NoiseModel, SimBatch, check_seed, check_shots, check_trajectories,
                       compile_programs)
 from .bound import bound_expectation_values
-from .mps import (DEFAULT_CUTOFF, MAX_BOND, _check_bond, _check_cutoff, bound_mps_expectation_values, mps_expectation_values,
+from .mps import (DEFAULT_CUTOFF, MAX_BOND, _check_bond, _check_cutoff, _check_twirl, bound_mps_expectation_values, mps_expectation_values,
                   sample_mps_expectation_values)
 from .template import Template, has_free_parameters
 
@@ -310,7 +310,9 @@ class DeviceEstimator:
     metadata.  ``"auto"`` never picks it.  ``thermal_relaxation=True`` (``"mps"`` and ``"mps_shots"`` alone) takes a model with
     thermal relaxation (:func:`compile_mps`: quantum jumps at the orthogonality centre); the metadata keys are the same, and
     ``truncation_error_bound`` is then the mean of per-trajectory certificates, each conditional on the jumps drawn (|value - exact|
-    <= 4 B sum|coeff| per trajectory).  Templates with it are refused by name.
+    <= 4 B sum|coeff| per trajectory).  Templates with it are refused by name.  ``pauli_twirl`` (``"mps"`` and ``"mps_shots"``
+    alone, with ``noise``; ``True`` or gate names, :func:`compile_mps`) twirls the two-qubit gates on the device, one draw per
+    trajectory and gate; ``zne(DeviceEstimator)`` passes it on to the folded runs.  The metadata keys are unchanged.
     ``"mps_shots"``: measurement shots drawn from those matrix-product states (:func:`sample_mps_expectation_values`), ideal or with
     ``noise`` and ``trajectories`` (shot s comes from trajectory s mod trajectories, so ``trajectories <= shots``); it needs ``shots``
     (``shots=None`` is refused by name, and so are templates), ``metadata[k] = {"variance": v_k, "shots": shots,
@@ -325,7 +327,7 @@ class DeviceEstimator:
 
     def __init__(self, noise: Optional[NoiseModel] = None, device="cuda", shots: Optional[int] = None, seed: int = 0,
                  method: str = "exact", trajectories: int = 1024, max_bond: int = MAX_BOND, cutoff: float = DEFAULT_CUTOFF,
-                 thermal_relaxation: bool = False):
+                 thermal_relaxation: bool = False, pauli_twirl: Any = None):
         methods = self.METHODS + self.SAMPLED_METHODS + self.WIDE_METHODS + self.WIDE_SAMPLED_METHODS
         if method not in methods:
             raise ValueError(f"DeviceEstimator: method = {method!r}, want one of {', '.join(methods)}")
@@ -337,6 +339,10 @@ class DeviceEstimator:
             raise ValueError(f"DeviceEstimator(method={method!r}): thermal_relaxation=True belongs to method='mps' and 'mps_shots' (the "
                              "exact and trajectory paths take a model with thermal relaxation as it is)")
         self._relaxation = thermal_relaxation
+        self._twirl = _check_twirl(pauli_twirl, "DeviceEstimator") or None
+        if self._twirl and method not in self.WIDE_METHODS + self.WIDE_SAMPLED_METHODS:
+            raise ValueError(f"DeviceEstimator(method={method!r}): pauli_twirl= belongs to method='mps' and 'mps_shots' (the twirl is "
+                             "drawn per trajectory on the matrix-product-state path)")
         if method == "mps" and shots is not None:
             raise ValueError(_MPS_SHOTS)
         if method == "mps_shots" and shots is None:
@@ -389,7 +395,7 @@ class DeviceEstimator:
             res = sample_mps_expectation_values(circuits, observables, self._noise, shots=shots, max_bond=self._max_bond,
                                                 cutoff=self._cutoff, trajectories=self._trajectories if noisy else None, seed=seed,
                                                 run_keys=default_run_keys(len(circuits), self._count << 32), device=self._device,
-                                                thermal_relaxation=self._relaxation)
+                                                thermal_relaxation=self._relaxation, pauli_twirl=self._twirl)
             metadata = [{"variance": float(v), "shots": shots, "truncation_error_bound": float(b), "max_bond": int(k)}
                         for v, b, k in zip(res.variance.cpu().numpy(), res.error_bound.cpu().numpy(), res.bond.cpu().numpy())]
             if noisy:
@@ -404,7 +410,7 @@ class DeviceEstimator:
             res = mps_expectation_values(circuits, observables, self._noise, max_bond=self._max_bond, cutoff=self._cutoff,
                                          trajectories=self._trajectories if noisy else None, seed=check_seed(seed, "DeviceEstimator.run"),
                                          run_keys=default_run_keys(len(circuits), self._count << 32), device=self._device,
-                                         thermal_relaxation=self._relaxation)
+                                         thermal_relaxation=self._relaxation, pauli_twirl=self._twirl)
             metadata = [{"truncation_error_bound": float(b), "max_bond": int(k)}
                         for b, k in zip(res.error_bound.cpu().numpy(), res.bond.cpu().numpy())]
             if noisy:
@@ -460,6 +466,10 @@ class DeviceEstimator:
             if self._relaxation:
                 raise ValueError(f"DeviceEstimator(method='mps', thermal_relaxation=True): circuit {first} is a template with free "
                                  "parameters; thermal relaxation on templates is not built (bind the circuit first)")
+            if self._twirl:
+                raise ValueError(f"DeviceEstimator(method='mps', pauli_twirl=): circuit {first} is a template with free parameters; "
+                                 "twirled templates are not built (mlqem_mps_bind_f64 does not know the twirl records: bind the "
+                                 "circuit first)")
             self._count += 1
             noisy = self._noise is not None
             values, _, res = bound_mps_expectation_values(

@@ -284,16 +284,23 @@ def _name_table(amplifier: _Amplifier) -> np.ndarray:
 
 
 def _fold_entries(amplifier: _Amplifier, gate_ptr: np.ndarray, mask: np.ndarray, rec: np.ndarray, noi: np.ndarray, owner: np.ndarray,
-                  n_circ: int, noise_factor: float, noi_len: Optional[np.ndarray] = None):
+                  n_circ: int, noise_factor: float, noi_len: Optional[np.ndarray] = None, pre: Optional[np.ndarray] = None,
+                  post: Optional[np.ndarray] = None):
     """The fold units of one noise factor as schedule entries, shared by both record formats: ``(entries, body_len, achieved)``
     with the entries of all circuits in running order (a unit's gate record with its dagger flag, then its noise records, never
     inverted: one depolarising or fused noise record, after a coherent-error record where the model has one; absent records left
-    out) and their number per circuit.  ``noi_len`` counts a gate's noise records (None: one where ``noi`` names one)."""
+    out) and their number per circuit.  ``noi_len`` counts a gate's noise records (None: one where ``noi`` names one).  ``pre`` /
+    ``post`` (the matrix-product-state format's twirl records; -1: none): a record per gate that every pass of the unit runs
+    before its gate record and after its noise records, never inverted.  Without them the entries are what they always were."""
     unit_gate, unit_dagger, _, ach = _plan(amplifier, gate_ptr, mask, noise_factor)
     r, n = rec[unit_gate], noi[unit_gate]
     columns = [np.where(r >= 0, (r << 1) | unit_dagger, -1), np.where(n >= 0, n << 1, -1)]
     if noi_len is not None and noi_len.size and int(noi_len.max()) > 1:
         columns.append(np.where((n >= 0) & (noi_len[unit_gate] > 1), (n + 1) << 1, -1))
+    if pre is not None:
+        columns.insert(0, np.where(pre[unit_gate] >= 0, pre[unit_gate] << 1, -1))
+    if post is not None:
+        columns.append(np.where(post[unit_gate] >= 0, post[unit_gate] << 1, -1))
     entries = np.stack(columns, axis=1)
     valid = entries >= 0
     body_len = np.bincount(owner[unit_gate], weights=valid.sum(axis=1), minlength=n_circ).astype(np.int64)
@@ -385,7 +392,9 @@ def build_mps_schedules(batch: Any, noise_factors: Sequence[float], amplifier: _
     """:func:`build_schedules` for the matrix-product-state format (``mlqem_mps_run_folded_f64``): one schedule per (noise factor,
     circuit) from the record map the noisy lowering of ``compile_mps`` keeps.  A fold unit is the gate's ``U1`` / ``U2`` record,
     possibly daggered, followed by its ``gate_noise_len`` noise records, never daggered: a coherent-error ``U2`` where the model has
-    one, then the ``DEPOL`` record (the inverse of a gate carries the gate's own coherent error and noise again).  A batch that
+    one, then the ``DEPOL`` record (the inverse of a gate carries the gate's own coherent error and noise again).  In a batch
+    lowered with ``pauli_twirl=`` a twirled gate's unit is ``TWIRL_OPEN``, gate | dagger, noise records, ``TWIRL_CLOSE``: every pass
+    draws its own twirl (the gates that are twirled are self-inverse, so one table closes the gate and its dagger).  A batch that
     holds a thermal-relaxation record (``NOISE1`` / ``NOISE2``) is refused by name, here and in :func:`run_mps_folded`.  There are no
     trailing entries, readout being a table in this format, and no run numbers (``ids`` is empty: every (run, trajectory) unit is
     a workgroup).  numpy throughout."""
@@ -405,9 +414,11 @@ def build_mps_schedules(batch: Any, noise_factors: Sequence[float], amplifier: _
     rec, noi, noi_len = (getattr(batch, k).astype(np.int64) for k in ("gate_record", "gate_noise", "gate_noise_len"))
     if noi_len.size and (int(noi_len.min()) < 0 or int(noi_len.max()) > 2):
         raise ValueError(f"build_mps_schedules: gate_noise_len holds {int(noi_len.min())} .. {int(noi_len.max())}, want 0, 1 or 2")
+    t_open, t_close = getattr(batch, "gate_twirl_open", None), getattr(batch, "gate_twirl_close", None)
+    twirl = {} if t_open is None or t_close is None else dict(pre=t_open.astype(np.int64), post=t_close.astype(np.int64))
     pieces, lengths, achieved = [], [], []
     for lam in factors:
-        body, body_len, ach = _fold_entries(amplifier, batch.gate_ptr, mask, rec, noi, owner, n_circ, lam, noi_len)
+        body, body_len, ach = _fold_entries(amplifier, batch.gate_ptr, mask, rec, noi, owner, n_circ, lam, noi_len, **twirl)
         pieces.append(body.astype(np.int32))
         lengths.append(body_len)
         achieved.append(ach)
@@ -691,7 +702,7 @@ def run_mps_folded(batch: Any, schedules: Schedules, seed: int = 0, run_keys=Non
 
 
 def _zne_run_mps(circuits, observables, noise, strategy, weights, device, shots, seed, run_keys, trajectories, max_bond, cutoff,
-                 buffer_bytes, keep_trajectories) -> ZNERun:
+                 buffer_bytes, keep_trajectories, pauli_twirl=None) -> ZNERun:
     import torch
 
     from ..native import ops
@@ -707,7 +718,7 @@ def _zne_run_mps(circuits, observables, noise, strategy, weights, device, shots,
                          "trajectories=T: the noisy lowering keeps the gate records that are folded; the ideal one fuses them)")
     n_traj = check_trajectories(trajectories, "zne_run")
     batch = compile_mps(circuits, observables, noise, n_traj, MAX_BOND if max_bond is None else max_bond,
-                        DEFAULT_CUTOFF if cutoff is None else cutoff)
+                        DEFAULT_CUTOFF if cutoff is None else cutoff, pauli_twirl=pauli_twirl)
     sch = build_mps_schedules(batch, strategy.noise_factors, strategy.noise_amplifier)
     n_f, b, n_terms = len(sch.noise_factors), len(batch), int(batch.term_circ.shape[0])
     res = run_mps_folded(batch, sch, seed, run_keys, device, keep_trajectories, buffer_bytes)
@@ -732,7 +743,7 @@ def _zne_run_mps(circuits, observables, noise, strategy, weights, device, shots,
 def zne_run(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None,
             strategy: Optional[ZNEStrategy] = None, device="cuda", shots: Optional[int] = None, seed: int = 0, run_keys=None,
             method: str = "exact", trajectories: Optional[int] = None, max_bond: Optional[int] = None, cutoff: Optional[float] = None,
-            buffer_bytes: Optional[int] = None, keep_trajectories: bool = False) -> ZNERun:
+            buffer_bytes: Optional[int] = None, keep_trajectories: bool = False, pauli_twirl: Any = None) -> ZNERun:
     """Lowers once, builds the schedules, simulates every (circuit, factor) run in one call and extrapolates in one more.  With
     ``shots`` every run is also measured and the extrapolation is of the sampled values (see the module docstring); ``run_keys``:
     one integer per run f * B + c (by default the run number).  ``method``: ``"exact"`` (the default), ``"clifford"`` or ``"auto"``,
@@ -744,7 +755,9 @@ def zne_run(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional
     lowering, :func:`build_mps_schedules`, then every (run, trajectory) unit through ``ops.sim_run_mps_folded`` in chunks that keep
     the site-tensor workspace under ``buffer_bytes``, one finish over the F * B runs and the combine.  The per-factor values are
     means over the trajectories; :class:`ZNERun` carries their standard errors, the truncation certificates and the bonds.  A
-    model with thermal relaxation is refused by name (folded runs do not take the ``thermal_relaxation=True`` of ``compile_mps``)."""
+    model with thermal relaxation is refused by name (folded runs do not take the ``thermal_relaxation=True`` of ``compile_mps``).
+    ``pauli_twirl`` (``method="mps"`` alone) is ``compile_mps``'s: every pass of a folded gate draws its own twirl on the device, which
+    turns a coherent gate error into the Pauli channel the extrapolators assume."""
     import torch
 
     from ..native import ops
@@ -762,7 +775,10 @@ def zne_run(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional
                          "want one of exact, clifford, auto, mps")
     if method == "mps":
         return _zne_run_mps(circuits, observables, noise, strategy, weights, device, shots, seed, run_keys, trajectories, max_bond, cutoff,
-                            buffer_bytes, keep_trajectories)
+                            buffer_bytes, keep_trajectories, pauli_twirl)
+    if pauli_twirl is not None and pauli_twirl is not False:
+        raise ValueError(f"zne_run: pauli_twirl= belongs to method='mps' (the twirl is drawn per trajectory on the matrix-product-state "
+                         f"path), not to method = {method!r}")
     if trajectories is not None or max_bond is not None or cutoff is not None or buffer_bytes is not None or keep_trajectories:
         raise ValueError(f"zne_run: trajectories=, max_bond=, cutoff=, buffer_bytes= and keep_trajectories= belong to method='mps', "
                          f"not to method = {method!r}")
@@ -926,7 +942,7 @@ def zne(cls):
                 keys = np.arange(n_f * n, dtype=np.int64) + (np.int64(self._zne_count) << 32)
                 run = zne_run(circuits, observables, self._noise, strategy, self._device, shots=shots, seed=seed, run_keys=keys,
                               method="mps", trajectories=None if self._noise is None else self._trajectories, max_bond=self._max_bond,
-                              cutoff=self._cutoff)
+                              cutoff=self._cutoff, pauli_twirl=getattr(self, "_twirl", None))
                 se, bound = run.std_error.cpu().numpy(), run.error_bound.cpu().numpy()
                 polynomial = run.mitigated_std_error is not None
                 mse = run.mitigated_std_error.cpu().numpy() if polynomial else None

@@ -17,6 +17,8 @@
 // runs on theta transposed.  A decomposition that still rotates in its last allowed sweep is counted in the unit's stats.
 // Thermal relaxation (the NOISE1 / NOISE2 records, plain runs only) is a quantum jump on one site: its Kraus operator is no unitary,
 // so the centre is moved to the qubit first, where the populations are a plain sum over that site's tensor (MpsState::relax).
+// A Pauli twirl (the TWIRL_OPEN / TWIRL_CLOSE records, plain and folded runs) is two one-site letters before a gate and their
+// image under the ideal gate after its noise, drawn per unit: no decomposition, no move of the centre, nothing in the certificate.
 //
 // LDS: theta at chi = 32 is 64 x 64 x 16 B = 64 KiB, plus 3 KiB of tables: two workgroups a CU on the 160 KiB of gfx950.
 //
@@ -335,6 +337,13 @@ __device__ __forceinline__ double mps_uniform(int index, int sub, int traj, uint
   return ((double)(x[0] >> 5) * 67108864.0 + (double)(x[1] >> 6)) * 0x1p-53;
 }
 
+// the code 0 .. 15 of twirl `index` (sub-draw 3): the top four bits of the first word, so a host reproduces it as an integer
+__device__ __forceinline__ int mps_twirl_draw(int index, int traj, uint32_t key_lo, uint32_t key_hi, uint32_t seed_lo, uint32_t seed_hi) {
+  uint32_t x[4];
+  philox4x32_10((uint32_t)index, (3u << 24) | (uint32_t)traj, key_lo, key_hi, seed_lo, seed_hi, x);
+  return __builtin_amdgcn_readfirstlane((int)(x[0] >> 28));
+}
+
 // FOLD = false: circuit circ_first + cl runs its records in order (mlqem_mps_run_f64).  FOLD = true (mlqem_mps_run_folded_f64):
 // `circ_first` counts RUNS r = f * B + c, and run r walks the schedule sched[sched_ptr[r] .. sched_ptr[r + 1]) of entries
 // (k << 1) | dagger over circuit c's records; run_keys and traj_stats have one row per run.  The noise index counts the noise
@@ -399,6 +408,7 @@ __global__ __launch_bounds__(kBlock) void mps_run_kernel(int B, const int32_t* _
   const int64_t key = run_keys[row];
   const uint32_t key_lo = (uint32_t)(uint64_t)key, key_hi = (uint32_t)((uint64_t)key >> 32);
   int centre = 0, noise_index = 0;
+  int twirl_index = 0, twirl_code = 0;   // the TWIRL_CLOSE entries executed so far, the code of the latest TWIRL_OPEN: scalars
   for (int k = 0; k < n_step; ++k) {
     int at = k, dg = 0;   // dg: apply the record's conjugate transpose
     if (FOLD) {
@@ -444,6 +454,20 @@ __global__ __launch_bounds__(kBlock) void mps_run_kernel(int B, const int32_t* _
         st.pauli(orient ? q + 1 : q, code & 3);    // the letter of the gate's first qubit
         st.pauli(orient ? q : q + 1, code >> 2);   // and of its second
       }
+    } else if ((kind == MLQEM_MPS_OP_TWIRL_OPEN || kind == MLQEM_MPS_OP_TWIRL_CLOSE) && n >= 2) {
+      // a Pauli twirl around a gate and its noise: OPEN draws the pair, CLOSE applies its image under the ideal gate from the
+      // record's table.  Kind, code and index are workgroup-uniform, so `pauli` (whose one_site ends in a barrier) is reached by
+      // every thread alike; a dagger bit is ignored, no centre moves, nothing enters the certificate
+      const int q = __builtin_amdgcn_readfirstlane(min(max(op.y, 0), n - 2));
+      int code;
+      if (kind == MLQEM_MPS_OP_TWIRL_OPEN) {
+        code = twirl_code = mps_twirl_draw(twirl_index, traj, key_lo, key_hi, seed_lo, seed_hi);
+      } else {
+        code = __builtin_amdgcn_readfirstlane((int)fmin(fmax(m[twirl_code], 0.0), 15.0));   // a NaN entry: 0
+        ++twirl_index;
+      }
+      st.pauli(orient ? q + 1 : q, code & 3);
+      st.pauli(orient ? q : q + 1, code >> 2);
     } else if (kind == MLQEM_MPS_OP_NOISE1 || (kind == MLQEM_MPS_OP_NOISE2 && n >= 2)) {
       if constexpr (!FOLD) {   // the host refuses these kinds on folded runs: the folded kernel skips them as any unknown kind
         // the centre to site `to`, one site at a time: the two loops of a U2 record

@@ -3075,12 +3075,129 @@ def sim_run_trajectories(circ, op_ptr, ops, params, term_ptr, terms, coeff, ids,
 MPS_MAX_BOND, MPS_MAX_QUBITS, MPS_STATS = 32, 512, 6   # MLQEM_MPS_MAX_BOND / MLQEM_MPS_MAX_QUBITS / MLQEM_MPS_STATS
 
 
-def mps_workspace_bytes(max_qubits: int, max_bond: int, n_units: int) -> int:
-    """Bytes of the site-tensor workspace of ``n_units`` (circuit, trajectory) units (mlqem_mps_workspace_bytes)."""
+def _mps_sizes(max_qubits, max_bond, n_units):
     if not 1 <= int(max_qubits) <= MPS_MAX_QUBITS or not 1 <= int(max_bond) <= MPS_MAX_BOND or int(n_units) < 0:
         raise ValueError(f"mps: max_qubits = {max_qubits}, max_bond = {max_bond}, n_units = {n_units}; want 1 .. {MPS_MAX_QUBITS}, "
                          f"1 .. {MPS_MAX_BOND} and >= 0")
-    return int(_lib.load().mlqem_mps_workspace_bytes(int(max_qubits), int(max_bond), int(n_units)))
+    return int(max_qubits), int(max_bond), int(n_units)
+
+
+def mps_workspace_bytes(max_qubits: int, max_bond: int, n_units: int) -> int:
+    """Bytes of the site-tensor workspace of ``n_units`` (circuit, trajectory) units (mlqem_mps_workspace_bytes)."""
+    return int(_lib.load().mlqem_mps_workspace_bytes(*_mps_sizes(max_qubits, max_bond, n_units)))
+
+
+def _mps_matrix(t, name, dtype, cols):
+    """``t`` is a contiguous ``dtype`` matrix [., cols] on the GPU."""
+    if not t.is_cuda:
+        raise _lib.NativeLibraryError(f"{name} must live on the GPU (got {t.device}); there is no CPU path")
+    if t.dtype != dtype or t.dim() != 2 or t.shape[1] != cols or not t.is_contiguous():
+        raise ValueError(f"mps: want contiguous {dtype} {name} [., {cols}], got {tuple(t.shape)} {t.dtype}")
+
+
+def _mps_same_device(first, name, *buffers):
+    if any(t.device != first.device for t in buffers if t is not None):
+        raise ValueError(f"mps: {name} is on {first.device}, another buffer is not")
+
+
+def _mps_vecs(*wanted):
+    """Every ``(vector, name, dtype, n)`` is a contiguous 1-D ``dtype`` tensor on the GPU with exactly ``n`` entries."""
+    for t, name, dtype, n in wanted:
+        _vec(t, name, 0, dtype)
+        if t.shape[0] != n:
+            raise ValueError(f"mps: {name} has {int(t.shape[0])} entries, want {n}")
+
+
+def _mps_ranges(trajectories_range, n_traj, *ranges):
+    """The ``(first, count)`` pairs of a chunk as ints, the trajectories' first.  Every ``(what, pair, total, least count, capped)``
+    of ``ranges`` lies inside its total, as the trajectories (at least one) lie inside ``n_traj``, and a capped one times the chunk's
+    trajectories stays within the 2^31 - 1 units one call takes."""
+    out = []
+    for what, pair, total, least, capped in (("trajectories", trajectories_range, n_traj, 1, False),) + ranges:
+        first, count = (int(v) for v in pair)
+        if first < 0 or count < least or first + count > total:
+            raise ValueError(f"mps: the chunk's {what} {(first, count)} (first, count) do not lie inside the {total} {what} there are")
+        if capped and max(count, 1) * out[0][1] > 2 ** 31 - 1:
+            raise ValueError(f"mps: {count} {what} x {out[0][1]} trajectories exceed the 2^31 - 1 units one call can take; split the chunk")
+        out.append((first, count))
+    return out
+
+
+def _mps_run_checked(n_qubits, op_ptr, ops, params, run_keys, units, n_units, trajectories_range, trajectories, seed, max_bond, max_qubits,
+                     workspace, traj_stats):
+    """What :func:`mps_run` and :func:`mps_run_folded` check alike: the B circuits' records, one key and one ``traj_stats`` row for
+    each of the ``n_units`` circuits or runs, the chunk ``units = (what, (first, count))`` of them and its workspace.  Returns
+    ``(B, n_ops, first unit, units, first trajectory, trajectories of the chunk, T, seed)`` and ``traj_stats``."""
+    _mps_matrix(ops, "ops", torch.int32, 4)
+    b, n_traj, seed = int(n_qubits.shape[0]), _sim_trajectories(trajectories), _sim_seed(seed)
+    (j0, jn), (u0, un) = _mps_ranges(trajectories_range, n_traj, units + (n_units, 1, True))
+    _mps_vecs((n_qubits, "n_qubits", torch.int32, b), (op_ptr, "op_ptr", torch.int64, b + 1), (run_keys, "run_keys", torch.int64, n_units))
+    _vec(params, "params", SIM_PARAM_PAD, torch.float64)
+    _vec(workspace, "workspace", mps_workspace_bytes(max_qubits, max_bond, un * jn), torch.uint8)
+    traj_stats = _sim_out(traj_stats, "traj_stats", (n_traj, n_units, MPS_STATS), ops.device)
+    _mps_same_device(ops, "ops", n_qubits, op_ptr, params, run_keys, workspace)
+    return (b, int(ops.shape[0]), u0, un, j0, jn, n_traj, seed), traj_stats
+
+
+def mps_run(n_qubits, op_ptr, ops, params, run_keys, circuits, trajectories_range, trajectories, seed, max_bond, cutoff, max_qubits,
+            workspace, traj_stats):
+    """The (circuit, trajectory) units of one chunk as matrix-product states (mlqem_mps_run_f64 alone: the site tensors stay in
+    ``workspace`` for :func:`mps_terms` or :func:`mps_sample`).  Arguments as :func:`sim_run_mps` takes them; ``traj_stats`` float64
+    [T, B, MPS_STATS]."""
+    (b, n_ops, c0, cn, j0, jn, n_traj, seed), traj_stats = _mps_run_checked(
+        n_qubits, op_ptr, ops, params, run_keys, ("circuits", circuits), int(n_qubits.shape[0]), trajectories_range, trajectories, seed,
+        max_bond, max_qubits, workspace, traj_stats)
+    code = _lib.load().mlqem_mps_run_f64(b, _p(n_qubits), _p(op_ptr), _p(ops) if n_ops else None, n_ops, _p(params), int(params.shape[0]),
+                                         _p(run_keys), c0, cn, j0, jn, n_traj, seed, int(max_bond), float(cutoff), int(max_qubits),
+                                         _p(workspace), int(workspace.shape[0]), _p(traj_stats), _stream())
+    _lib.check(code, "mlqem_mps_run_f64")
+    return traj_stats
+
+
+def mps_run_folded(n_qubits, op_ptr, ops, params, sched_ptr, sched, n_factors, run_keys, runs, trajectories_range, trajectories, seed,
+                   max_bond, cutoff, max_qubits, workspace, traj_stats):
+    """The (run, trajectory) units of one chunk of the F * B folded runs as matrix-product states (mlqem_mps_run_folded_f64 alone).
+    Arguments as :func:`sim_run_mps_folded` takes them; ``traj_stats`` float64 [T, F * B, MPS_STATS]."""
+    f = int(n_factors)
+    if f < 1:
+        raise ValueError(f"mps: n_factors = {f}, want at least 1")
+    n_runs = f * int(n_qubits.shape[0])   # run f * B + c of F factors x B circuits: one schedule and one key each
+    (b, n_ops, r0, rn, j0, jn, n_traj, seed), traj_stats = _mps_run_checked(
+        n_qubits, op_ptr, ops, params, run_keys, ("runs", runs), n_runs, trajectories_range, trajectories, seed, max_bond, max_qubits,
+        workspace, traj_stats)
+    _mps_vecs((sched_ptr, "sched_ptr", torch.int64, n_runs + 1), (sched, "sched", torch.int32, int(sched.shape[0])))
+    _mps_same_device(ops, "ops", sched_ptr, sched)
+    n_sched = int(sched.shape[0])
+    code = _lib.load().mlqem_mps_run_folded_f64(
+        b, f, _p(n_qubits), _p(op_ptr), _p(ops) if n_ops else None, n_ops, _p(params), int(params.shape[0]), _p(sched_ptr),
+        _p(sched) if n_sched else None, n_sched, _p(run_keys), r0, rn, j0, jn, n_traj, seed, int(max_bond), float(cutoff), int(max_qubits),
+        _p(workspace), int(workspace.shape[0]), _p(traj_stats), _stream())
+    _lib.check(code, "mlqem_mps_run_folded_f64")
+    return traj_stats
+
+
+def mps_terms(n_qubits, circuits, trajectories_range, trajectories, max_bond, max_qubits, workspace, term_circ, term_off, letters, site_ptr,
+              readout, terms, traj_term_values, traj_norm):
+    """The Pauli terms and the norms of the chunk whose site tensors :func:`mps_run` or :func:`mps_run_folded` left in ``workspace``
+    (mlqem_mps_terms_f64): fills the chunk's part of ``traj_term_values`` float64 [T, n_terms] and ``traj_norm`` [T, B] and returns
+    them (``None``: allocated here).  ``n_qubits`` int32 [B] and ``site_ptr`` int64 [B + 1] are per circuit, or per run with
+    ``circuits`` the chunk's runs; the other arguments as :func:`sim_run_mps` takes them."""
+    _mps_matrix(readout, "readout", torch.float64, 2)
+    b, n_terms, n_traj = int(n_qubits.shape[0]), int(term_circ.shape[0]), _sim_trajectories(trajectories)
+    (j0, jn), (c0, cn), (t0, tn) = _mps_ranges(trajectories_range, n_traj, ("circuits", circuits, b, 1, True), ("terms", terms, n_terms, 0, True))
+    _mps_vecs((n_qubits, "n_qubits", torch.int32, b), (term_circ, "term_circ", torch.int32, n_terms),
+              (term_off, "term_off", torch.int64, n_terms), (site_ptr, "site_ptr", torch.int64, b + 1))
+    _vec(letters, "letters", 0, torch.uint8)
+    _vec(workspace, "workspace", mps_workspace_bytes(max_qubits, max_bond, cn * jn), torch.uint8)
+    traj_term_values = _sim_out(traj_term_values, "traj_term_values", (n_traj, n_terms), readout.device)
+    traj_norm = _sim_out(traj_norm, "traj_norm", (n_traj, b), readout.device)
+    _mps_same_device(readout, "readout", n_qubits, term_circ, term_off, letters, site_ptr, workspace)
+    code = _lib.load().mlqem_mps_terms_f64(
+        b, _p(n_qubits), c0, cn, j0, jn, n_traj, int(max_bond), int(max_qubits), _p(workspace), int(workspace.shape[0]), t0, tn, n_terms,
+        _p(term_circ) if n_terms else None, _p(term_off) if n_terms else None, _p(letters) if n_terms else None, int(letters.shape[0]),
+        _p(site_ptr), _p(readout), int(readout.shape[0]), _p(traj_term_values) if n_terms else None, _p(traj_norm), _stream())
+    _lib.check(code, "mlqem_mps_terms_f64")
+    return traj_term_values, traj_norm
 
 
 def sim_run_mps(n_qubits, op_ptr, ops, params, run_keys, term_circ, term_off, letters, site_ptr, readout, circuits, terms, trajectories_range,
@@ -3097,47 +3214,10 @@ def sim_run_mps(n_qubits, op_ptr, ops, params, run_keys, term_circ, term_off, le
     ``workspace`` uint8 of at least :func:`mps_workspace_bytes` for the chunk's units.  Shapes, dtypes and devices are checked
     here, the contents are the lowering's to guarantee (the kernels clamp every index).  Nothing here waits for the device or reads a
     tensor, and with the three outputs given nothing is allocated: capturable.  There is no CPU path."""
-    for t, name, dtype, cols in ((ops, "ops", torch.int32, 4), (readout, "readout", torch.float64, 2)):
-        if not t.is_cuda:
-            raise _lib.NativeLibraryError(f"{name} must live on the GPU (got {t.device}); there is no CPU path")
-        if t.dtype != dtype or t.shape[-1] != cols or not t.is_contiguous():
-            raise ValueError(f"mps: want contiguous {dtype} {name} [..., {cols}], got {tuple(t.shape)} {t.dtype}")
-    b, n_ops, n_terms, n_traj, seed = int(n_qubits.shape[0]), int(ops.shape[0]), int(term_circ.shape[0]), int(trajectories), int(seed)
-    (c0, cn), (t0, tn), (j0, jn) = ((int(v) for v in pair) for pair in (circuits, terms, trajectories_range))
-    if not 1 <= n_traj <= SIM_MAX_TRAJECTORIES or not 0 <= seed < 2 ** 64:
-        raise ValueError(f"mps: trajectories = {n_traj} and seed = {seed}, want 1 .. 2^20 and 0 .. 2^64 - 1")
-    if not (0 <= c0 and 1 <= cn and c0 + cn <= b and 0 <= t0 and 0 <= tn and t0 + tn <= n_terms and 0 <= j0 and 1 <= jn and j0 + jn <= n_traj):
-        raise ValueError(f"mps: the chunk (circuits {circuits}, terms {terms}, trajectories {trajectories_range}) does not lie inside "
-                         f"{b} circuits, {n_terms} terms and {n_traj} trajectories")
-    if cn * jn > 2 ** 31 - 1 or max(tn, 1) * jn > 2 ** 31 - 1:
-        raise ValueError(f"mps: {cn} circuits (or {tn} terms) x {jn} trajectories exceed the 2^31 - 1 units one call can take; split the chunk")
-    _vec(n_qubits, "n_qubits", b, torch.int32)
-    _vec(op_ptr, "op_ptr", b + 1, torch.int64)
-    _vec(params, "params", SIM_PARAM_PAD, torch.float64)
-    _vec(run_keys, "run_keys", b, torch.int64)
-    _vec(term_circ, "term_circ", n_terms, torch.int32)
-    _vec(term_off, "term_off", n_terms, torch.int64)
-    _vec(letters, "letters", 0, torch.uint8)
-    _vec(site_ptr, "site_ptr", b + 1, torch.int64)
-    _vec(workspace, "workspace", mps_workspace_bytes(max_qubits, max_bond, cn * jn), torch.uint8)
-    if op_ptr.shape[0] != b + 1 or site_ptr.shape[0] != b + 1 or run_keys.shape[0] != b or term_off.shape[0] != n_terms or readout.dim() != 2:
-        raise ValueError(f"mps: want op_ptr and site_ptr [{b + 1}], run_keys [{b}], term_off [{n_terms}] and readout [n_sites, 2], got "
-                         f"{tuple(op_ptr.shape)}, {tuple(site_ptr.shape)}, {tuple(run_keys.shape)}, {tuple(term_off.shape)}, {tuple(readout.shape)}")
-    dev = ops.device
-    traj_term_values = _sim_out(traj_term_values, "traj_term_values", (n_traj, n_terms), dev)
-    traj_norm, traj_stats = _sim_out(traj_norm, "traj_norm", (n_traj, b), dev), _sim_out(traj_stats, "traj_stats", (n_traj, b, MPS_STATS), dev)
-    if any(t.device != dev for t in (n_qubits, op_ptr, params, run_keys, term_circ, term_off, letters, site_ptr, readout, workspace)):
-        raise ValueError(f"mps: ops is on {dev}, another buffer is not")
-    lib, ws_bytes = _lib.load(), int(workspace.shape[0])
-    code = lib.mlqem_mps_run_f64(b, _p(n_qubits), _p(op_ptr), _p(ops) if n_ops else None, n_ops, _p(params), int(params.shape[0]),
-                                 _p(run_keys), c0, cn, j0, jn, n_traj, seed, int(max_bond), float(cutoff), int(max_qubits), _p(workspace),
-                                 ws_bytes, _p(traj_stats), _stream())
-    _lib.check(code, "mlqem_mps_run_f64")
-    code = lib.mlqem_mps_terms_f64(b, _p(n_qubits), c0, cn, j0, jn, n_traj, int(max_bond), int(max_qubits), _p(workspace), ws_bytes, t0, tn,
-                                   n_terms, _p(term_circ) if n_terms else None, _p(term_off) if n_terms else None,
-                                   _p(letters) if n_terms else None, int(letters.shape[0]), _p(site_ptr), _p(readout), int(readout.shape[0]),
-                                   _p(traj_term_values) if n_terms else None, _p(traj_norm), _stream())
-    _lib.check(code, "mlqem_mps_terms_f64")
+    traj_stats = mps_run(n_qubits, op_ptr, ops, params, run_keys, circuits, trajectories_range, trajectories, seed, max_bond, cutoff,
+                         max_qubits, workspace, traj_stats)
+    traj_term_values, traj_norm = mps_terms(n_qubits, circuits, trajectories_range, trajectories, max_bond, max_qubits, workspace, term_circ,
+                                            term_off, letters, site_ptr, readout, terms, traj_term_values, traj_norm)
     return traj_term_values, traj_norm, traj_stats
 
 
@@ -3157,60 +3237,11 @@ def sim_run_mps_folded(n_qubits, op_ptr, ops, params, sched_ptr, sched, n_factor
     ``runs`` / ``terms`` / ``trajectories_range``: ``(first, count)`` of the chunk (``terms`` must be the tiled terms of ``runs``).
     Shapes, dtypes and devices are checked here, the contents are the builders' to guarantee (the kernels clamp every index).
     Nothing here waits for the device or reads a tensor, and with the three outputs given nothing is allocated: capturable."""
-    for t, name, dtype, cols in ((ops, "ops", torch.int32, 4), (readout, "readout", torch.float64, 2)):
-        if not t.is_cuda:
-            raise _lib.NativeLibraryError(f"{name} must live on the GPU (got {t.device}); there is no CPU path")
-        if t.dtype != dtype or t.dim() != 2 or t.shape[-1] != cols or not t.is_contiguous():
-            raise ValueError(f"mps: want contiguous {dtype} {name} [., {cols}], got {tuple(t.shape)} {t.dtype}")
-    b, n_ops, f = int(n_qubits.shape[0]), int(ops.shape[0]), int(n_factors)
-    if f < 1:
-        raise ValueError(f"mps: n_factors = {f}, want at least 1")
-    n_runs, n_terms = f * b, int(term_circ.shape[0])
-    n_traj, seed = _sim_trajectories(trajectories), _sim_seed(seed)
-    (r0, rn), (t0, tn), (j0, jn) = ((int(v) for v in pair) for pair in (runs, terms, trajectories_range))
-    if not (0 <= r0 and 1 <= rn and r0 + rn <= n_runs and 0 <= t0 and 0 <= tn and t0 + tn <= n_terms and 0 <= j0 and 1 <= jn and j0 + jn <= n_traj):
-        raise ValueError(f"mps: the chunk (runs {runs}, terms {terms}, trajectories {trajectories_range}) does not lie inside "
-                         f"{n_runs} runs, {n_terms} terms and {n_traj} trajectories")
-    if rn * jn > 2 ** 31 - 1 or max(tn, 1) * jn > 2 ** 31 - 1:
-        raise ValueError(f"mps: {rn} runs (or {tn} terms) x {jn} trajectories exceed the 2^31 - 1 units one call can take; split the chunk")
-    _vec(n_qubits, "n_qubits", b, torch.int32)
-    _vec(op_ptr, "op_ptr", b + 1, torch.int64)
-    _vec(params, "params", SIM_PARAM_PAD, torch.float64)
-    _vec(sched_ptr, "sched_ptr", 1, torch.int64)
-    _vec(sched, "sched", 0, torch.int32)
-    _vec(run_keys, "run_keys", 0, torch.int64)
-    if sched_ptr.shape[0] != n_runs + 1:
-        raise ValueError(f"mps: sched_ptr has {int(sched_ptr.shape[0])} entries, want {n_runs + 1} (one schedule per run f * B + c of "
-                         f"{f} factors x {b} circuits, and the end)")
-    if run_keys.shape[0] != n_runs:
-        raise ValueError(f"mps: run_keys has {int(run_keys.shape[0])} entries, want {n_runs} (one key per run f * B + c of {f} factors x "
-                         f"{b} circuits)")
-    _vec(run_qubits, "run_qubits", n_runs, torch.int32)
-    _vec(term_circ, "term_circ", n_terms, torch.int32)
-    _vec(term_off, "term_off", n_terms, torch.int64)
-    _vec(letters, "letters", 0, torch.uint8)
-    _vec(site_ptr, "site_ptr", n_runs + 1, torch.int64)
-    _vec(workspace, "workspace", mps_workspace_bytes(max_qubits, max_bond, rn * jn), torch.uint8)
-    if op_ptr.shape[0] != b + 1 or run_qubits.shape[0] != n_runs or site_ptr.shape[0] != n_runs + 1 or term_off.shape[0] != n_terms:
-        raise ValueError(f"mps: want op_ptr [{b + 1}], run_qubits [{n_runs}], site_ptr [{n_runs + 1}] and term_off [{n_terms}], got "
-                         f"{tuple(op_ptr.shape)}, {tuple(run_qubits.shape)}, {tuple(site_ptr.shape)} and {tuple(term_off.shape)}")
-    dev = ops.device
-    traj_term_values = _sim_out(traj_term_values, "traj_term_values", (n_traj, n_terms), dev)
-    traj_norm = _sim_out(traj_norm, "traj_norm", (n_traj, n_runs), dev)
-    traj_stats = _sim_out(traj_stats, "traj_stats", (n_traj, n_runs, MPS_STATS), dev)
-    if any(t.device != dev for t in (n_qubits, op_ptr, params, sched_ptr, sched, run_keys, run_qubits, term_circ, term_off, letters, site_ptr,
-                                     readout, workspace)):
-        raise ValueError(f"mps: ops is on {dev}, another buffer is not")
-    lib, ws_bytes, n_sched = _lib.load(), int(workspace.shape[0]), int(sched.shape[0])
-    code = lib.mlqem_mps_run_folded_f64(b, f, _p(n_qubits), _p(op_ptr), _p(ops) if n_ops else None, n_ops, _p(params), int(params.shape[0]),
-                                        _p(sched_ptr), _p(sched) if n_sched else None, n_sched, _p(run_keys), r0, rn, j0, jn, n_traj, seed,
-                                        int(max_bond), float(cutoff), int(max_qubits), _p(workspace), ws_bytes, _p(traj_stats), _stream())
-    _lib.check(code, "mlqem_mps_run_folded_f64")
-    code = lib.mlqem_mps_terms_f64(n_runs, _p(run_qubits), r0, rn, j0, jn, n_traj, int(max_bond), int(max_qubits), _p(workspace), ws_bytes,
-                                   t0, tn, n_terms, _p(term_circ) if n_terms else None, _p(term_off) if n_terms else None,
-                                   _p(letters) if n_terms else None, int(letters.shape[0]), _p(site_ptr), _p(readout), int(readout.shape[0]),
-                                   _p(traj_term_values) if n_terms else None, _p(traj_norm), _stream())
-    _lib.check(code, "mlqem_mps_terms_f64")
+    traj_stats = mps_run_folded(n_qubits, op_ptr, ops, params, sched_ptr, sched, n_factors, run_keys, runs, trajectories_range, trajectories,
+                                seed, max_bond, cutoff, max_qubits, workspace, traj_stats)
+    _mps_vecs((run_qubits, "run_qubits", torch.int32, int(n_factors) * int(n_qubits.shape[0])))
+    traj_term_values, traj_norm = mps_terms(run_qubits, runs, trajectories_range, trajectories, max_bond, max_qubits, workspace, term_circ,
+                                            term_off, letters, site_ptr, readout, terms, traj_term_values, traj_norm)
     return traj_term_values, traj_norm, traj_stats
 
 
@@ -3252,41 +3283,7 @@ MPS_SHOT_BLOCK, MPS_MAX_GROUPS = 16, 4096   # MLQEM_MPS_SHOT_BLOCK / MLQEM_MPS_M
 
 def mps_sample_workspace_bytes(max_qubits: int, max_bond: int, n_units: int) -> int:
     """Bytes of the environment workspace of ``n_units`` (circuit, trajectory) units (mlqem_mps_sample_workspace_bytes)."""
-    if not 1 <= int(max_qubits) <= MPS_MAX_QUBITS or not 1 <= int(max_bond) <= MPS_MAX_BOND or int(n_units) < 0:
-        raise ValueError(f"mps: max_qubits = {max_qubits}, max_bond = {max_bond}, n_units = {n_units}; want 1 .. {MPS_MAX_QUBITS}, "
-                         f"1 .. {MPS_MAX_BOND} and >= 0")
-    return int(_lib.load().mlqem_mps_sample_workspace_bytes(int(max_qubits), int(max_bond), int(n_units)))
-
-
-def mps_run(n_qubits, op_ptr, ops, params, run_keys, circuits, trajectories_range, trajectories, seed, max_bond, cutoff, max_qubits,
-            workspace, traj_stats):
-    """The (circuit, trajectory) units of one chunk as matrix-product states (mlqem_mps_run_f64 alone: the site tensors stay in
-    ``workspace`` for :func:`mps_sample`).  Arguments as :func:`sim_run_mps` takes them; ``traj_stats`` float64 [T, B, MPS_STATS]."""
-    if not ops.is_cuda:
-        raise _lib.NativeLibraryError(f"ops must live on the GPU (got {ops.device}); there is no CPU path")
-    if ops.dtype != torch.int32 or ops.shape[-1] != 4 or not ops.is_contiguous():
-        raise ValueError(f"mps: want contiguous int32 ops [n_ops, 4], got {tuple(ops.shape)} {ops.dtype}")
-    b, n_ops, n_traj, seed = int(n_qubits.shape[0]), int(ops.shape[0]), int(trajectories), int(seed)
-    (c0, cn), (j0, jn) = ((int(v) for v in pair) for pair in (circuits, trajectories_range))
-    if not 1 <= n_traj <= SIM_MAX_TRAJECTORIES or not 0 <= seed < 2 ** 64:
-        raise ValueError(f"mps: trajectories = {n_traj} and seed = {seed}, want 1 .. 2^20 and 0 .. 2^64 - 1")
-    if not (0 <= c0 and 1 <= cn and c0 + cn <= b and 0 <= j0 and 1 <= jn and j0 + jn <= n_traj) or cn * jn > 2 ** 31 - 1:
-        raise ValueError(f"mps: the chunk (circuits {circuits}, trajectories {trajectories_range}) does not lie inside {b} circuits and "
-                         f"{n_traj} trajectories, or exceeds the 2^31 - 1 units one call can take")
-    dev = ops.device
-    _vec(n_qubits, "n_qubits", b, torch.int32)
-    _vec(op_ptr, "op_ptr", b + 1, torch.int64)
-    _vec(params, "params", SIM_PARAM_PAD, torch.float64)
-    _vec(run_keys, "run_keys", b, torch.int64)
-    _vec(workspace, "workspace", mps_workspace_bytes(max_qubits, max_bond, cn * jn), torch.uint8)
-    traj_stats = _sim_out(traj_stats, "traj_stats", (n_traj, b, MPS_STATS), dev)
-    if op_ptr.shape[0] != b + 1 or run_keys.shape[0] != b or any(t.device != dev for t in (n_qubits, op_ptr, params, run_keys, workspace)):
-        raise ValueError(f"mps: want op_ptr [{b + 1}] and run_keys [{b}] on {dev}, got {tuple(op_ptr.shape)} and {tuple(run_keys.shape)}")
-    code = _lib.load().mlqem_mps_run_f64(b, _p(n_qubits), _p(op_ptr), _p(ops) if n_ops else None, n_ops, _p(params), int(params.shape[0]),
-                                         _p(run_keys), c0, cn, j0, jn, n_traj, seed, int(max_bond), float(cutoff), int(max_qubits),
-                                         _p(workspace), int(workspace.shape[0]), _p(traj_stats), _stream())
-    _lib.check(code, "mlqem_mps_run_f64")
-    return traj_stats
+    return int(_lib.load().mlqem_mps_sample_workspace_bytes(*_mps_sizes(max_qubits, max_bond, n_units)))
 
 
 def mps_sample(n_qubits, circuits, trajectories_range, trajectories, max_bond, max_qubits, workspace, sample_workspace, groups, max_groups,
@@ -3304,48 +3301,29 @@ def mps_sample(n_qubits, circuits, trajectories_range, trajectories, max_bond, m
     for the device or reads a tensor and nothing is allocated: capturable.  There is no CPU path."""
     if not workspace.is_cuda:
         raise _lib.NativeLibraryError(f"workspace must live on the GPU (got {workspace.device}); there is no CPU path")
-    b, n_groups, n_terms, n_traj, shots, seed = (int(n_qubits.shape[0]), int(group_circ.shape[0]), int(term_mask.shape[0]), int(trajectories),
-                                                 int(shots), int(seed))
-    (c0, cn), (j0, jn), (g0, gn), (t0, tn) = ((int(v) for v in pair) for pair in (circuits, trajectories_range, groups, terms))
-    if not 1 <= shots <= SIM_MAX_SHOTS or not 1 <= n_traj <= SIM_MAX_TRAJECTORIES or not 0 <= seed < 2 ** 64:
-        raise ValueError(f"mps: shots = {shots}, trajectories = {n_traj} and seed = {seed}, want 1 .. 2^20, 1 .. 2^20 and 0 .. 2^64 - 1")
-    if not (0 <= c0 and 1 <= cn and c0 + cn <= b and 0 <= j0 and 1 <= jn and j0 + jn <= n_traj and 0 <= g0 and 1 <= gn and g0 + gn <= n_groups
-            and 0 <= t0 and 0 <= tn and t0 + tn <= n_terms):
-        raise ValueError(f"mps: the chunk (circuits {circuits}, trajectories {trajectories_range}, groups {groups}, terms {terms}) does not "
-                         f"lie inside {b} circuits, {n_traj} trajectories, {n_groups} groups and {n_terms} terms")
+    b, n_groups, n_terms = int(n_qubits.shape[0]), int(group_circ.shape[0]), int(term_mask.shape[0])
+    shots, n_traj, seed = _sim_shots(shots), _sim_trajectories(trajectories), _sim_seed(seed)
+    (j0, jn), (c0, cn), (g0, gn), (t0, tn) = _mps_ranges(trajectories_range, n_traj, ("circuits", circuits, b, 1, False),
+                                                         ("groups", groups, n_groups, 1, False), ("terms", terms, n_terms, 0, False))
     if not 1 <= int(max_groups) <= MPS_MAX_GROUPS:
         raise ValueError(f"mps: {max_groups} measurement groups in one circuit, want 1 .. {MPS_MAX_GROUPS}")
-    dev = workspace.device
     units = cn * jn
     _vec(n_qubits, "n_qubits", b, torch.int32)
     _vec(workspace, "workspace", mps_workspace_bytes(max_qubits, max_bond, units), torch.uint8)
     _vec(sample_workspace, "sample_workspace", mps_sample_workspace_bytes(max_qubits, max_bond, units), torch.uint8)
-    _vec(group_ptr, "group_ptr", b + 1, torch.int64)
-    _vec(group_circ, "group_circ", n_groups, torch.int32)
-    _vec(group_off, "group_off", n_groups, torch.int64)
+    _mps_vecs((group_ptr, "group_ptr", torch.int64, b + 1), (group_circ, "group_circ", torch.int32, n_groups),
+              (group_off, "group_off", torch.int64, n_groups), (site_ptr, "site_ptr", torch.int64, b + 1),
+              (ref_ptr, "ref_ptr", torch.int64, n_groups + 1), (gterm_ptr, "gterm_ptr", torch.int64, n_groups + 1),
+              (gterm, "gterm", torch.int32, n_terms), (term_mask, "term_mask", torch.int32, n_terms), (run_keys, "run_keys", torch.int64, b),
+              (term_sums, "term_sums", torch.int32, n_terms))
     _vec(basis, "basis", 1, torch.uint8)
-    _vec(site_ptr, "site_ptr", b + 1, torch.int64)
-    _vec(ref_ptr, "ref_ptr", n_groups + 1, torch.int64)
-    _vec(gterm_ptr, "gterm_ptr", n_groups + 1, torch.int64)
-    _vec(gterm, "gterm", n_terms, torch.int32)
-    _vec(term_mask, "term_mask", n_terms, torch.int32)
     _vec(masks, "masks", 1, torch.int32)
-    _vec(run_keys, "run_keys", b, torch.int64)
-    _vec(term_sums, "term_sums", n_terms, torch.int32)
+    _vec(bits, "bits", 0, torch.int32)
     if flip.dtype != torch.float64 or flip.dim() != 2 or flip.shape[-1] != 2 or not flip.is_contiguous() or flip.shape[0] < 1:
         raise ValueError(f"mps: want contiguous float64 flip [n_sites >= 1, 2], got {tuple(flip.shape)} {flip.dtype}")
-    n_bits = 0
-    if bits is not None:
-        _vec(bits, "bits", 0, torch.int32)
-        n_bits = int(bits.shape[0])
-    if (group_ptr.shape[0] != b + 1 or site_ptr.shape[0] != b + 1 or group_off.shape[0] != n_groups or ref_ptr.shape[0] != n_groups + 1
-            or gterm_ptr.shape[0] != n_groups + 1 or gterm.shape[0] != n_terms or run_keys.shape[0] != b or term_sums.shape[0] != n_terms):
-        raise ValueError(f"mps: want group_ptr and site_ptr [{b + 1}], group_off [{n_groups}], ref_ptr and gterm_ptr [{n_groups + 1}], gterm "
-                         f"and term_sums [{n_terms}] and run_keys [{b}]")
-    others = [n_qubits, sample_workspace, group_ptr, group_circ, group_off, basis, site_ptr, flip, ref_ptr, gterm_ptr, gterm, term_mask, masks,
-              run_keys, term_sums] + ([] if bits is None else [bits])
-    if any(t.device != dev for t in others):
-        raise ValueError(f"mps: workspace is on {dev}, another buffer is not")
+    n_bits = 0 if bits is None else int(bits.shape[0])
+    _mps_same_device(workspace, "workspace", n_qubits, sample_workspace, group_ptr, group_circ, group_off, basis, site_ptr, flip, ref_ptr,
+                     gterm_ptr, gterm, term_mask, masks, run_keys, term_sums, bits)
     code = _lib.load().mlqem_mps_sample_f64(
         b, _p(n_qubits), c0, cn, j0, jn, n_traj, int(max_bond), int(max_qubits), _p(workspace), int(workspace.shape[0]),
         _p(sample_workspace), int(sample_workspace.shape[0]), g0, gn, n_groups, int(max_groups), _p(group_ptr), _p(group_circ),

@@ -19,6 +19,7 @@ gate, the circuits lowered once; plain runs, shots and folded runs take such a b
 """
 from __future__ import annotations
 
+import functools
 import math
 from dataclasses import dataclass, field
 from typing import Any, Dict, List, Optional, Sequence
@@ -128,27 +129,29 @@ def is_line_circuit(circuit: Any) -> bool:
                for op in Circuit.from_any(circuit).ops)
 
 
+def refuse_records(batch: Any, who: str, kinds: Sequence[int], text: str) -> None:
+    """Raises, naming the first one, where a batch holds a record of one of ``kinds``: ``text`` says what it is and who takes it."""
+    hit = np.flatnonzero(np.isin(np.asarray(batch.ops).reshape(-1, 4)[:, 0], kinds))
+    if hit.size:
+        raise ValueError(f"{who}: record {int(hit[0])} of the batch is {text}")
+
+
 def refuse_relaxation_records(batch: Any, who: str) -> None:
     """Raises where a batch holds a ``NOISE1`` / ``NOISE2`` record (``compile_mps(..., thermal_relaxation=True)``, or built by
     hand): the folded kernel and the bind kernel do not run them."""
-    kinds = np.asarray(batch.ops).reshape(-1, 4)[:, 0]
-    hit = np.flatnonzero((kinds == OP_MPS_NOISE1) | (kinds == OP_MPS_NOISE2))
-    if hit.size:
-        raise ValueError(f"{who}: record {int(hit[0])} of the batch is a thermal-relaxation record (NOISE1 / NOISE2, "
-                         "compile_mps(..., thermal_relaxation=True)); folded runs and templates on the matrix-product-state path "
-                         "take depolarising + readout models only (relaxation there is not built: run_mps runs such a batch)")
+    refuse_records(batch, who, (OP_MPS_NOISE1, OP_MPS_NOISE2),
+                   "a thermal-relaxation record (NOISE1 / NOISE2, compile_mps(..., thermal_relaxation=True)); folded runs and templates on "
+                   "the matrix-product-state path take depolarising + readout models only (relaxation there is not built: run_mps runs "
+                   "such a batch)")
 
 
 def refuse_twirl_records(batch: Any, who: str) -> None:
     """Raises where a batch holds a ``TWIRL_OPEN`` / ``TWIRL_CLOSE`` record (``compile_mps(..., pauli_twirl=)``, or built by hand):
     the bind kernel copies one value of a kind it does not know, and a ``TWIRL_CLOSE`` record has a table of 16."""
-    kinds = np.asarray(batch.ops).reshape(-1, 4)[:, 0]
-    hit = np.flatnonzero((kinds == OP_MPS_TWIRL_OPEN) | (kinds == OP_MPS_TWIRL_CLOSE))
-    if hit.size:
-        raise ValueError(f"{who}: record {int(hit[0])} of the batch is a Pauli-twirl record (TWIRL_OPEN / TWIRL_CLOSE, "
-                         "compile_mps(..., pauli_twirl=)); templates on the matrix-product-state path do not take twirled "
-                         "batches (mlqem_mps_bind_f64 copies one value of a record it does not know, a TWIRL_CLOSE table has 16: "
-                         "not built; run_mps and run_mps_folded run such a batch)")
+    refuse_records(batch, who, (OP_MPS_TWIRL_OPEN, OP_MPS_TWIRL_CLOSE),
+                   "a Pauli-twirl record (TWIRL_OPEN / TWIRL_CLOSE, compile_mps(..., pauli_twirl=)); templates on the "
+                   "matrix-product-state path do not take twirled batches (mlqem_mps_bind_f64 copies one value of a record it does not "
+                   "know, a TWIRL_CLOSE table has 16: not built; run_mps and run_mps_folded run such a batch)")
 
 
 def _check_twirl(pauli_twirl: Any, who: str) -> tuple:
@@ -688,32 +691,67 @@ class MpsResult:
     batch: Optional[MpsBatch] = None
 
 
-def _mps_chunks(batch: MpsBatch, trajectories: int, buffer_bytes: int, unit_bytes=None):
-    """``(circuit range, trajectory range)`` pairs whose site-tensor workspace (n * chi * 2 * chi * 16 B per unit, plus the stash)
-    stays under ``buffer_bytes``: whole circuits with all their trajectories while they fit, else one circuit with a part of them.
-    A chunk holds at least one unit.  ``unit_bytes(width)``: the bytes of one unit where they are more than that workspace."""
+def _upload(array, dev):
+    import torch
+
+    return torch.from_numpy(np.ascontiguousarray(array)).to(dev)
+
+
+def _mps_chunks(widths, max_bond: int, trajectories: int, buffer_bytes: int, unit_bytes=None):
+    """``(unit range, trajectory range)`` pairs over the circuits (or runs) of the widths ``widths`` whose site-tensor workspace
+    (n * chi * 2 * chi * 16 B per unit, plus the stash) stays under ``buffer_bytes``: whole circuits with all their trajectories
+    while they fit, else one circuit with a part of them.  A chunk holds at least one unit.  ``unit_bytes(width)``: the bytes of
+    one unit where they are more than that workspace."""
     from ..native import ops
 
     if unit_bytes is None:
         def unit_bytes(width):
-            return ops.mps_workspace_bytes(width, batch.max_bond, 1)
+            return ops.mps_workspace_bytes(width, max_bond, 1)
 
-    chunks, lo, b = [], 0, len(batch)
+    unit_bytes = functools.lru_cache(maxsize=None)(unit_bytes)   # a batch has few distinct widths and many circuits
+    chunks, lo, b = [], 0, len(widths)
     while lo < b:
-        hi, widest = lo + 1, int(batch.n_qubits[lo])
+        hi, widest = lo + 1, int(widths[lo])
         per = unit_bytes(widest)
         if per * trajectories > buffer_bytes:
             step = max(int(buffer_bytes // per), 1)
             chunks += [(range(lo, hi), range(t0, min(t0 + step, trajectories))) for t0 in range(0, trajectories, step)]
         else:
             while hi < b:
-                wider = max(widest, int(batch.n_qubits[hi]))
+                wider = max(widest, int(widths[hi]))
                 if unit_bytes(wider) * trajectories * (hi + 1 - lo) > buffer_bytes:
                     break
                 widest, hi = wider, hi + 1
             chunks.append((range(lo, hi), range(0, trajectories)))
         lo = hi
     return chunks
+
+
+def _mps_plan(widths, max_bond: int, n_traj: int, buffer_bytes, who: str, dev, shots: bool = False):
+    """The launches of a chunked driver: ``(chunks, workspace, environment workspace or None)``.  ``chunks``: ``(unit range,
+    trajectory range, widest circuit)`` triples of :func:`_mps_chunks` under ``buffer_bytes`` (``None``: :data:`MPS_BUFFER_BYTES`;
+    with ``shots`` a unit counts its environment workspace too); the workspaces are sized to the largest chunk."""
+    import torch
+
+    from ..native import ops
+
+    buffer_bytes = MPS_BUFFER_BYTES if buffer_bytes is None else int(buffer_bytes)
+    if buffer_bytes < 1:
+        raise ValueError(f"{who}: buffer_bytes = {buffer_bytes!r}, want a positive number of bytes")
+    sizes = (ops.mps_workspace_bytes, ops.mps_sample_workspace_bytes) if shots else (ops.mps_workspace_bytes,)
+    chunks = [(ur, tr, int(widths[ur.start:ur.stop].max()))
+              for ur, tr in _mps_chunks(widths, max_bond, n_traj, buffer_bytes, lambda width: sum(f(width, max_bond, 1) for f in sizes))]
+    buffers = [torch.empty((max([f(w, max_bond, len(ur) * len(tr)) for ur, tr, w in chunks] + [16]),), dtype=torch.uint8, device=dev)
+               for f in sizes]
+    return chunks, buffers[0], buffers[1] if shots else None
+
+
+def _mps_result(out, term_ptr, batch, seed, traj_terms, traj_stats, keep: bool, noisy: bool) -> MpsResult:
+    """The :class:`MpsResult` of ``sim_mps_finish``'s dict ``out``: standard errors where ``noisy``, the per-trajectory arrays where
+    ``keep``."""
+    return MpsResult(out["values"], out["term_values"], out["norm"], term_ptr, out["discarded"], out["error_bound"], out["bond"],
+                     out["std_error"] if noisy else None, out["term_std_error"] if noisy else None, batch.trajectories, seed,
+                     traj_terms if keep else None, traj_stats if keep else None, batch)
 
 
 def run_mps(batch: MpsBatch, seed: int = 0, run_keys=None, device="cuda", keep_trajectories: bool = False,
@@ -730,35 +768,26 @@ def run_mps(batch: MpsBatch, seed: int = 0, run_keys=None, device="cuda", keep_t
     seed = check_seed(seed, "run_mps")
     n_traj = 1 if batch.trajectories is None else check_trajectories(batch.trajectories, "run_mps")
     keys = _run_keys(run_keys, len(batch), "run_mps")
-    buffer_bytes = MPS_BUFFER_BYTES if buffer_bytes is None else int(buffer_bytes)
-    if buffer_bytes < 1:
-        raise ValueError(f"run_mps: buffer_bytes = {buffer_bytes!r}, want a positive number of bytes")
     dev = torch.device(device)
+    chunks, workspace, _ = _mps_plan(batch.n_qubits, batch.max_bond, n_traj, buffer_bytes, "run_mps", dev)
     t = batch.to(dev)
-    b, n_terms = len(batch), int(batch.term_circ.shape[0])
+    b, n_terms, noisy = len(batch), int(batch.term_circ.shape[0]), batch.trajectories is not None
     if b == 0:
-        empty = torch.zeros(0, dtype=torch.float64, device=dev)
-        return MpsResult(empty, empty.clone(), empty.clone(), t["term_ptr"], empty.clone(), empty.clone(),
-                         torch.zeros(0, dtype=torch.int32, device=dev), None if batch.trajectories is None else empty.clone(),
-                         None if batch.trajectories is None else empty.clone(), batch.trajectories, seed, None, None, batch)
-    keys_t = torch.from_numpy(keys).to(dev)
+        empty = {k: torch.zeros(0, dtype=torch.float64, device=dev)
+                 for k in ("values", "term_values", "norm", "discarded", "error_bound", "std_error", "term_std_error")}
+        empty["bond"] = torch.zeros(0, dtype=torch.int32, device=dev)
+        return _mps_result(empty, t["term_ptr"], batch, seed, None, None, False, noisy)
+    keys_t = _upload(keys, dev)
     traj_terms = torch.zeros((n_traj, n_terms), dtype=torch.float64, device=dev)
     traj_norm = torch.zeros((n_traj, b), dtype=torch.float64, device=dev)
     traj_stats = torch.zeros((n_traj, b, ops.MPS_STATS), dtype=torch.float64, device=dev)
-    chunks = _mps_chunks(batch, n_traj, buffer_bytes)
-    need = max(ops.mps_workspace_bytes(int(batch.n_qubits[list(cr)].max()), batch.max_bond, len(cr) * len(tr)) for cr, tr in chunks)
-    workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
-    for cr, tr in chunks:
+    for cr, tr, widest in chunks:
         ops.sim_run_mps(t["n_qubits"], t["op_ptr"], t["ops"], t["params"], keys_t, t["term_circ"], t["term_off"], t["letters"],
                         t["site_ptr"], t["readout"], (cr.start, len(cr)),
                         (int(batch.term_ptr[cr.start]), int(batch.term_ptr[cr.stop] - batch.term_ptr[cr.start])), (tr.start, len(tr)),
-                        n_traj, seed, batch.max_bond, batch.cutoff, int(batch.n_qubits[list(cr)].max()), workspace, traj_terms, traj_norm,
-                        traj_stats)
+                        n_traj, seed, batch.max_bond, batch.cutoff, widest, workspace, traj_terms, traj_norm, traj_stats)
     out = ops.sim_mps_finish(t["term_ptr"], t["coeff"], traj_terms, traj_norm, traj_stats)
-    noisy = batch.trajectories is not None
-    return MpsResult(out["values"], out["term_values"], out["norm"], t["term_ptr"], out["discarded"], out["error_bound"], out["bond"],
-                     out["std_error"] if noisy else None, out["term_std_error"] if noisy else None, batch.trajectories, seed,
-                     traj_terms if keep_trajectories else None, traj_stats if keep_trajectories else None, batch)
+    return _mps_result(out, t["term_ptr"], batch, seed, traj_terms, traj_stats, keep_trajectories, noisy)
 
 
 def mps_expectation_values(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None,
@@ -775,16 +804,6 @@ def mps_expectation_values(circuits: Sequence[Any], observables: Sequence[Any], 
 
 # ---- templates: bound on the device ---------------------------------------------------------------------------------------------------
 MPS_POOL_ENTRIES = 2 ** 31 - 1 - PARAM_PAD   # float64 values of bound records one launch can address
-
-
-class _RunWidths:
-    """What :func:`_mps_chunks` reads of a batch, for the runs of templates."""
-
-    def __init__(self, n_qubits, max_bond):
-        self.n_qubits, self.max_bond = n_qubits, max_bond
-
-    def __len__(self):
-        return int(self.n_qubits.shape[0])
 
 
 class MpsBoundRun:
@@ -805,9 +824,6 @@ class MpsBoundRun:
         refuse_relaxation_records(batch, who)
         refuse_twirl_records(batch, who)
         self.n_traj = 1 if batch.trajectories is None else check_trajectories(batch.trajectories, who)
-        buffer_bytes = MPS_BUFFER_BYTES if buffer_bytes is None else int(buffer_bytes)
-        if buffer_bytes < 1:
-            raise ValueError(f"{who}: buffer_bytes = {buffer_bytes!r}, want a positive number of bytes")
         dev = self.dev = torch.device(device)
         is_tensor = isinstance(theta, torch.Tensor)
         n_rows = int(theta.shape[0]) if (is_tensor and theta.dim() == 2) else None
@@ -851,8 +867,9 @@ class MpsBoundRun:
         if np.any(pool_n > pool_entries):
             raise ValueError(f"{who}: one bound copy holds {int(pool_n.max())} gate parameters, over the {pool_entries} a launch addresses")
         # chunks: by the workspace budget, as run_mps splits circuits, and by the pool entries a record can address
+        plan, self.workspace, _ = _mps_plan(widths, batch.max_bond, self.n_traj, buffer_bytes, who, dev)
         chunks = []
-        for cr, tr in (_mps_chunks(_RunWidths(widths, batch.max_bond), self.n_traj, buffer_bytes) if r else []):
+        for cr, tr, _ in plan:
             lo = cr.start
             while lo < cr.stop:
                 hi = lo + 1
@@ -861,17 +878,14 @@ class MpsBoundRun:
                 chunks.append((range(lo, hi), tr))
                 lo = hi
         self.chunks = chunks
-
-        def up(a):
-            return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-        self.tpl = {k: up(getattr(batch, k)) for k in ("op_ptr", "ops", "params", "pool_ptr", "fac_ptr", "fac", "fac_val", "fpool",
-                                                       "occ_ptr", "occ", "letters", "readout")}
-        self.theta = theta.to(dev).contiguous() if is_tensor else up(theta)
-        self.runs, self.shift, self.keys, self.widths = up(runs), up(shift), up(keys), up(widths.astype(np.int32))
-        self.term_off, self.coeff = up(batch.term_off[term_src]), up(batch.coeff[term_src])
-        self.site_ptr = up(np.concatenate([batch.site_ptr[tpl], batch.site_ptr[-1:]]).astype(np.int64))
-        self.term_ptr = up(self.run_term_ptr)
+        self.tpl = {k: _upload(getattr(batch, k), dev) for k in ("op_ptr", "ops", "params", "pool_ptr", "fac_ptr", "fac", "fac_val", "fpool",
+                                                                 "occ_ptr", "occ", "letters", "readout")}
+        self.theta = theta.to(dev).contiguous() if is_tensor else _upload(theta, dev)
+        self.runs, self.shift, self.keys = _upload(runs, dev), _upload(shift, dev), _upload(keys, dev)
+        self.widths = _upload(widths.astype(np.int32), dev)
+        self.term_off, self.coeff = _upload(batch.term_off[term_src], dev), _upload(batch.coeff[term_src], dev)
+        self.site_ptr = _upload(np.concatenate([batch.site_ptr[tpl], batch.site_ptr[-1:]]).astype(np.int64), dev)
+        self.term_ptr = _upload(self.run_term_ptr, dev)
         # per chunk, relative to its first run: op_ptr [n + 1], out_pool_ptr [n + 1] and the run of each of its terms
         rel_op, rel_pool, rel_term, self.where = [], [], [], []
         for cr, _ in chunks:
@@ -879,7 +893,7 @@ class MpsBoundRun:
             rel_op.append(run_op[cr.start:cr.stop + 1] - run_op[cr.start])
             rel_pool.append(run_pool[cr.start:cr.stop + 1] - run_pool[cr.start])
             rel_term.append(self.term_run[self.run_term_ptr[cr.start]:self.run_term_ptr[cr.stop]] - cr.start)
-        cat = lambda parts, dtype: up(np.concatenate(parts).astype(dtype) if parts else np.zeros(0, dtype=dtype))   # noqa: E731
+        cat = lambda parts, dtype: _upload(np.concatenate(parts).astype(dtype) if parts else np.zeros(0, dtype=dtype), dev)   # noqa: E731
         self.rel_op, self.rel_pool, self.rel_term = cat(rel_op, np.int64), cat(rel_pool, np.int64), cat(rel_term, np.int32)
         self.sizes = [(int(run_op[cr.stop] - run_op[cr.start]), int(run_pool[cr.stop] - run_pool[cr.start]),
                        int(self.run_term_ptr[cr.stop] - self.run_term_ptr[cr.start]), int(rec_n[cr.start:cr.stop].max()),
@@ -892,8 +906,6 @@ class MpsBoundRun:
         units = max([len(cr) for cr, _ in chunks] + [1])
         self.loc_terms, self.loc_norm = zeros(t * max([s[2] for s in self.sizes] + [1])), zeros(t * units)
         self.loc_stats = zeros(t * units * ops.MPS_STATS)
-        need = max([ops.mps_workspace_bytes(s[4], batch.max_bond, len(cr) * len(tr)) for s, (cr, tr) in zip(self.sizes, chunks)] + [16])
-        self.workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
         self.out = {k: zeros(n) for k, n in (("term_values", n_terms), ("term_std_error", n_terms), ("values", r), ("std_error", r),
                                              ("norm", r), ("discarded", r), ("error_bound", r))}
         self.out["bond"] = zeros(r, torch.int32)
@@ -939,11 +951,8 @@ class MpsBoundRun:
             trajectories=b.trajectories)
 
     def result(self, keep_trajectories: bool = False) -> MpsResult:
-        out, b = self.out, self.batch
-        noisy = b.trajectories is not None
-        return MpsResult(out["values"], out["term_values"], out["norm"], self.term_ptr, out["discarded"], out["error_bound"], out["bond"],
-                         out["std_error"] if noisy else None, out["term_std_error"] if noisy else None, b.trajectories, self.seed,
-                         self.traj_terms if keep_trajectories else None, self.traj_stats if keep_trajectories else None, b)
+        return _mps_result(self.out, self.term_ptr, self.batch, self.seed, self.traj_terms, self.traj_stats, keep_trajectories,
+                           self.batch.trajectories is not None)
 
 
 def run_mps_bound(batch: MpsBoundBatch, rows, runs=None, shift=None, seed: int = 0, run_keys=None, device="cuda",
@@ -1017,10 +1026,6 @@ def mps_parameter_shift(template, observable, rows, noise: Optional[NoiseModel] 
     width = int(batch.num_parameters.max()) if len(batch) else 0
     values = torch.zeros(n_rows, dtype=torch.float64, device=dev)
     grads = torch.zeros((n_rows, width), dtype=torch.float64, device=dev)
-
-    def up(a):
-        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
     for c, rws, at, k in groups:
         b, p = int(rws.size), int(batch.num_parameters[c])
         ob = int(batch.occ_ptr[c])
@@ -1028,9 +1033,9 @@ def mps_parameter_shift(template, observable, rows, noise: Optional[NoiseModel] 
         order = np.argsort(par, kind="stable").astype(np.int32)   # a parameter's occurrences, in circuit order
         occ_ptr = np.concatenate([[0], np.cumsum(np.bincount(par, minlength=p))]).astype(np.int64)
         v = all_values[at:at + b * (1 + 2 * k)]
-        g = ops.sim_shift_combine(v[b:b + k * b].reshape(k, b), v[b + k * b:].reshape(k, b), up(occ_ptr), up(order),
-                                  up(batch.occ_scale[ob:ob + k]))
-        idx = up(rws)
+        g = ops.sim_shift_combine(v[b:b + k * b].reshape(k, b), v[b + k * b:].reshape(k, b), _upload(occ_ptr, dev), _upload(order, dev),
+                                  _upload(batch.occ_scale[ob:ob + k], dev))
+        idx = _upload(rws, dev)
         values[idx] = v[:b]
         grads[idx, :p] = g
     return values, grads
@@ -1219,10 +1224,8 @@ def run_mps_shots(batch: MpsShotsBatch, shots: int, seed: int = 0, run_keys=None
         raise ValueError(f"run_mps_shots: trajectories = {n_traj} exceed shots = {shots} (shot s comes from trajectory s mod "
                          "trajectories: the others would be simulated and never measured)")
     keys = _run_keys(run_keys, len(batch), "run_mps_shots")
-    buffer_bytes = MPS_BUFFER_BYTES if buffer_bytes is None else int(buffer_bytes)
-    if buffer_bytes < 1:
-        raise ValueError(f"run_mps_shots: buffer_bytes = {buffer_bytes!r}, want a positive number of bytes")
     dev = torch.device(device)
+    chunks, workspace, env = _mps_plan(mps.n_qubits, mps.max_bond, n_traj, buffer_bytes, "run_mps_shots", dev, shots=True)
     t = batch.to(dev)
     b, n_terms = len(batch), int(mps.term_circ.shape[0])
     zeros = lambda n, dtype=torch.float64: torch.zeros(n, dtype=dtype, device=dev)   # noqa: E731
@@ -1230,21 +1233,11 @@ def run_mps_shots(batch: MpsShotsBatch, shots: int, seed: int = 0, run_keys=None
         return MpsShotsResult(zeros(0), zeros(0), zeros(0), t["term_ptr"], zeros(0, torch.int32), t["ref_ptr"], t["group_ptr"], zeros(0),
                               zeros(0), zeros(0, torch.int32), zeros(0, torch.int32) if return_bits else None, shots, seed,
                               mps.trajectories, batch)
-    keys_t = torch.from_numpy(keys).to(dev)
+    keys_t = _upload(keys, dev)
     traj_stats = zeros((n_traj, b, ops.MPS_STATS))
     term_sums = zeros(n_terms, torch.int32)
     bits = zeros(int(batch.ref_ptr[-1]) * shots, torch.int32) if return_bits else None
-
-    def unit_bytes(width):
-        return ops.mps_workspace_bytes(width, mps.max_bond, 1) + ops.mps_sample_workspace_bytes(width, mps.max_bond, 1)
-
-    chunks = _mps_chunks(mps, n_traj, buffer_bytes, unit_bytes)
-    widest = [int(mps.n_qubits[list(cr)].max()) for cr, _ in chunks]
-    workspace = torch.empty((max(ops.mps_workspace_bytes(w, mps.max_bond, len(cr) * len(tr)) for w, (cr, tr) in zip(widest, chunks)),),
-                            dtype=torch.uint8, device=dev)
-    env = torch.empty((max(ops.mps_sample_workspace_bytes(w, mps.max_bond, len(cr) * len(tr)) for w, (cr, tr) in zip(widest, chunks)),),
-                      dtype=torch.uint8, device=dev)
-    for w, (cr, tr) in zip(widest, chunks):
+    for cr, tr, w in chunks:
         ops.mps_run(t["n_qubits"], t["op_ptr"], t["ops"], t["params"], keys_t, (cr.start, len(cr)), (tr.start, len(tr)), n_traj, seed,
                     mps.max_bond, mps.cutoff, w, workspace, traj_stats)
         g0, g1 = int(batch.group_ptr[cr.start]), int(batch.group_ptr[cr.stop])

@@ -652,12 +652,10 @@ def run_mps_folded(batch: Any, schedules: Schedules, seed: int = 0, run_keys=Non
     ``run_keys``: one integer per run, by default the run number; a unit's bits depend on (seed, run key, trajectory number, the
     run's schedule and records) alone.  The (run, trajectory) units are split into launches so that the site-tensor workspace stays
     under ``buffer_bytes`` (default :data:`~blackwater.sim.mps.MPS_BUFFER_BYTES`), as :func:`~blackwater.sim.mps.run_mps` splits."""
-    import dataclasses
-
     import torch
 
     from ..native import ops
-    from .mps import MPS_BUFFER_BYTES, MpsResult, _mps_chunks, refuse_relaxation_records
+    from .mps import _mps_plan, _mps_result, _upload, refuse_relaxation_records
     from .program import check_trajectories
     from .run import _run_keys
 
@@ -672,33 +670,23 @@ def run_mps_folded(batch: Any, schedules: Schedules, seed: int = 0, run_keys=Non
         raise ValueError(f"run_mps_folded: the schedules hold {schedules.sched_ptr.shape[0] - 1} runs, the batch has {n_f} factors x {b} "
                          "circuits")
     keys = _run_keys(run_keys, n_runs, "run_mps_folded")
-    buffer_bytes = MPS_BUFFER_BYTES if buffer_bytes is None else int(buffer_bytes)
-    if buffer_bytes < 1:
-        raise ValueError(f"run_mps_folded: buffer_bytes = {buffer_bytes!r}, want a positive number of bytes")
     dev = torch.device(device)
     tiled = tile_mps_runs(batch, n_f)
+    chunks, workspace, _ = _mps_plan(tiled["run_qubits"], batch.max_bond, n_traj, buffer_bytes, "run_mps_folded", dev)
     t, s = batch.to(dev), schedules.to(dev)
-    r = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in tiled.items()}
-    keys_t = torch.from_numpy(keys).to(dev)
+    r = {k: _upload(v, dev) for k, v in tiled.items()}
+    keys_t = _upload(keys, dev)
     traj_terms = torch.zeros((n_traj, n_f * n_terms), dtype=torch.float64, device=dev)
     traj_norm = torch.zeros((n_traj, n_runs), dtype=torch.float64, device=dev)
     traj_stats = torch.zeros((n_traj, n_runs, ops.MPS_STATS), dtype=torch.float64, device=dev)
-    if n_runs:
-        runs = dataclasses.replace(batch, n_qubits=tiled["run_qubits"])   # the F * B runs as what _mps_chunks splits
-        chunks = _mps_chunks(runs, n_traj, buffer_bytes)
-        widest = [int(tiled["run_qubits"][list(rr)].max()) for rr, _ in chunks]
-        workspace = torch.empty((max(ops.mps_workspace_bytes(w, batch.max_bond, len(rr) * len(tr)) for w, (rr, tr) in zip(widest, chunks)),),
-                                dtype=torch.uint8, device=dev)
-        for w, (rr, tr) in zip(widest, chunks):
-            t0, t1 = int(tiled["term_ptr"][rr.start]), int(tiled["term_ptr"][rr.stop])
-            ops.sim_run_mps_folded(t["n_qubits"], t["op_ptr"], t["ops"], t["params"], s["sched_ptr"], s["sched"], n_f, keys_t,
-                                   r["run_qubits"], r["term_circ"], r["term_off"], t["letters"], r["site_ptr"], t["readout"],
-                                   (rr.start, len(rr)), (t0, t1 - t0), (tr.start, len(tr)), n_traj, seed, batch.max_bond, batch.cutoff, w,
-                                   workspace, traj_terms, traj_norm, traj_stats)
+    for rr, tr, w in chunks:
+        t0, t1 = int(tiled["term_ptr"][rr.start]), int(tiled["term_ptr"][rr.stop])
+        ops.sim_run_mps_folded(t["n_qubits"], t["op_ptr"], t["ops"], t["params"], s["sched_ptr"], s["sched"], n_f, keys_t,
+                               r["run_qubits"], r["term_circ"], r["term_off"], t["letters"], r["site_ptr"], t["readout"],
+                               (rr.start, len(rr)), (t0, t1 - t0), (tr.start, len(tr)), n_traj, seed, batch.max_bond, batch.cutoff, w,
+                               workspace, traj_terms, traj_norm, traj_stats)
     out = ops.sim_mps_finish(r["term_ptr"], r["coeff"], traj_terms, traj_norm, traj_stats)
-    return MpsResult(out["values"], out["term_values"], out["norm"], r["term_ptr"], out["discarded"], out["error_bound"], out["bond"],
-                     out["std_error"], out["term_std_error"], n_traj, seed, traj_terms if keep_trajectories else None,
-                     traj_stats if keep_trajectories else None, batch)
+    return _mps_result(out, r["term_ptr"], batch, seed, traj_terms, traj_stats, keep_trajectories, True)
 
 
 def _zne_run_mps(circuits, observables, noise, strategy, weights, device, shots, seed, run_keys, trajectories, max_bond, cutoff,

@@ -49,7 +49,7 @@ def sampling_alone(batch, shot_counts, seed=1):
     def unit_bytes(width):
         return ops.mps_workspace_bytes(width, mps.max_bond, 1) + ops.mps_sample_workspace_bytes(width, mps.max_bond, 1)
 
-    chunks = _mps_chunks(mps, n_traj, MPS_BUFFER_BYTES, unit_bytes)
+    chunks = _mps_chunks(mps.n_qubits, mps.max_bond, n_traj, MPS_BUFFER_BYTES, unit_bytes)
     units = max(len(cr) * len(tr) for cr, tr in chunks)
     width = int(mps.n_qubits.max())
     workspace = torch.empty(ops.mps_workspace_bytes(width, mps.max_bond, units), dtype=torch.uint8, device=DEV)

@@ -7,7 +7,14 @@ the library can be compared bit for bit (MLQEM_LIB selects the build; compare th
 
 The grids: sim_cases (vector, density, depolarising, readout), relax_cases.grid, zne_cases (folded runs, one of them measured),
 shots_cases.batches at every shot count (measured runs + sampled counts), traj_cases.grid with the per-trajectory values,
-bound_cases.grid in both forms with every shifted run, mps_cases.grid through sim_mps_finish, clifford_frames_cases' grid.
+bound_cases.grid in both forms with every shifted run, clifford_frames_cases' grid, and the matrix-product-state drivers: mps_cases.grid
+and mps_relax_cases.grid through run_mps, mps_shots_cases.grid through run_mps_shots with the bits, mps_zne_cases.grid through
+run_mps_folded, mps_bound_cases.grid through run_mps_bound (plain and shifted runs), mps_twirl_cases.grid through run_mps and
+run_mps_folded -- each once at the default buffer_bytes and once at the workspace of ONE unit of the case's widest circuit, which
+splits every circuit's trajectories over launches.
+
+--package-root DIR imports blackwater from another tree (a worktree of another commit, built in place) while the case modules
+stay this tree's: the MPS sections call only entry points of blackwater.sim.
 """
 import argparse
 import dataclasses
@@ -15,7 +22,8 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "ml-qem_amd"), os.path.join(ROOT, "tests")]
+PACKAGE_ROOT = os.path.abspath(sys.argv[sys.argv.index("--package-root") + 1]) if "--package-root" in sys.argv[:-1] else ROOT
+sys.path[:0] = [PACKAGE_ROOT, os.path.join(PACKAGE_ROOT, "ml-qem_amd"), os.path.join(ROOT, "tests")]
 import numpy as np  # noqa: E402
 
 DEV = "cuda:0"
@@ -37,7 +45,12 @@ def dump(out):
 
     import bound_cases as bc
     import clifford_frames_cases as fc
+    import mps_bound_cases as mbc
     import mps_cases as mc
+    import mps_relax_cases as mr
+    import mps_shots_cases as ms
+    import mps_twirl_cases as mt
+    import mps_zne_cases as mz
     import relax_cases as rc
     import shots_cases as shc
     import sim_cases as sc
@@ -47,6 +60,7 @@ def dump(out):
     from blackwater.native import ops
     from blackwater.sim import zne
     from blackwater.sim.bound import run_bound, shift_runs
+    from blackwater.sim.mps import mps_shift_runs
 
     arrays = {}
 
@@ -114,9 +128,42 @@ def dump(out):
         runs, shift, _ = shift_runs(batch, np.zeros(n_rows, dtype=np.int64))
         for form, tag in ((ops.SIM_BOUND_TABLE, "table"), (ops.SIM_BOUND_PLAIN, "plain")):
             put(f"bound/{name}-{tag}", run_bound(batch, theta, runs, shift, DEV, form=form))
+
+    def split(name, batch, run):
+        """``run(buffer_bytes)`` at the default budget and at one unit of the batch's widest circuit."""
+        put(name, run(None))
+        put(f"{name}/split", run(ops.mps_workspace_bytes(int(batch.n_qubits.max()), batch.max_bond, 1)))
+
     section("mps")
     for case in mc.grid():
-        put(f"mps/{case['id']}", sim.run_mps(mc.lower(case), case["seed"], None, DEV, keep_trajectories=True))
+        batch = mc.lower(case)
+        split(f"mps/{case['id']}", batch, lambda bb: sim.run_mps(batch, case["seed"], None, DEV, True, bb))
+    section("mps_relax")
+    for cid, case in mr.grid().items():
+        batch = mr.lower(cid)
+        split(f"mps_relax/{cid}", batch, lambda bb: sim.run_mps(batch, case["seed"], None, DEV, True, bb))
+    section("mps_shots")
+    for cid, case in ms.grid().items():
+        batch = ms.lower(cid)
+        split(f"mps_shots/{cid}", batch.mps, lambda bb: sim.run_mps_shots(batch, case["shots"], case["seed"], None, True, DEV, bb))
+    section("mps_zne")
+    for case in mz.grid():
+        batch, sch = mz.lowered(case["id"])
+        split(f"mps_zne/{case['id']}", batch, lambda bb: zne.run_mps_folded(batch, sch, case["seed"], None, DEV, True, bb))
+    section("mps_bound")
+    for case in mbc.grid():
+        batch = mbc.lower(case["id"])
+        shifted, shift, _ = mps_shift_runs(batch, case["pair"])
+        for tag, runs, sh in (("plain", mbc.plain_runs(case), None), ("shifted", shifted, shift)):
+            split(f"mps_bound/{case['id']}-{tag}", batch,
+                  lambda bb: sim.run_mps_bound(batch, case["rows"], runs, sh, case["seed"], None, DEV, True, bb))
+    section("mps_twirl")
+    for cid, case in mt.grid().items():
+        batch = mt.lower(cid)
+        split(f"mps_twirl/{cid}", batch, lambda bb: sim.run_mps(batch, case["seed"], None, DEV, True, bb))
+        if not case["relaxation"]:   # folded runs refuse relaxation records
+            sch = zne.build_mps_schedules(batch, mt.FOLD_FACTORS, zc.make_amplifier(zc.LOCAL_2Q))
+            split(f"mps_twirl/{cid}-folded", batch, lambda bb: zne.run_mps_folded(batch, sch, case["seed"], None, DEV, True, bb))
     section("frames")
     for kind, mixed in fc.GRID_COMBOS:
         cases = [fc.grid_case(n, mixed) for n in fc.GRID_N]   # fc.grid_batch's lowering, without its host oracle
@@ -126,12 +173,13 @@ def dump(out):
     torch.cuda.synchronize()
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     np.savez(out, **arrays)
-    print(f"wrote {len(arrays)} arrays to {out} with {os.environ.get('MLQEM_LIB') or 'the library of this tree'}")
+    print(f"wrote {len(arrays)} arrays to {out} with {os.environ.get('MLQEM_LIB') or f'the library of {PACKAGE_ROOT}'}")
 
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", help="the .npz to write (a few MB: keep it out of the repository)")
+    ap.add_argument("--package-root", metavar="DIR", help="import blackwater from this tree (default: the script's own)")
     ap.add_argument("--compare", nargs=2, metavar=("A", "B"), help="compare two dumps array for array and exit (1: some differ)")
     args = ap.parse_args()
     if not args.compare and not args.out:

@@ -5,7 +5,11 @@ only; the Philox uniforms are ``traj_cases.uniforms``, the dense oracles ``sim_c
 Interpreter.  ``interpret`` follows the contract of include/mlqem_hip.h record by record on a batch lowered by ``compile_mps``: the
 centre moves, theta, the 4x4 matrix, a decomposition, the KEEP RULE (descending, at most max_bond columns with sigma^2 > cutoff *
 total, at least one), eps and sqrt(2 eps), the rescaling, A[q + 1] = A[q]^dagger theta; the depolarising draw against the running sum
-s_0 = 1 - m w, s_j = s_(j-1) + w; the terms by the left-to-right contraction over the norm.  The decomposition is LAPACK's SVD
+s_0 = 1 - m w, s_j = s_(j-1) + w (sub-draw 0); for NOISE1 / NOISE2 then per qubit the move of the centre, the populations of the
+centre's tensor, the six outcomes against their running sum (the first above u, else the last of non-zero probability), the
+chosen operator over the root of its own state-given probability, and ``error_bound`` <- t ``error_bound``; the terms by the
+left-to-right contraction over the norm (``contract_terms``).  It is the one host interpreter of the MPS record format: the
+relaxation, shots, folded, bound and twirled cases all run it.  The decomposition is LAPACK's SVD
 (``method="lapack"``) or ``jacobi_columns`` (``method="jacobi"``), a plain numpy one-sided Jacobi written independently of the kernel
 (another pair order, the circle method on a rotating list; its own threshold).
 
@@ -42,6 +46,7 @@ CUT_FACTOR = 2.0
 MARGIN = 1e-12
 FACTOR = 16
 _LETTER = (np.eye(2, dtype=complex), sc.X, sc.Y, sc.Z)
+KIND_U1, KIND_U2, KIND_DEPOL1, KIND_DEPOL2, KIND_NOISE1, KIND_NOISE2 = 0, 5, 6, 7, 10, 11
 
 
 def jacobi_columns(m, tol=1e-15, sweeps=60):
@@ -96,31 +101,84 @@ def decompose(m, method):
     return q, sig2
 
 
+class NeedOutcome(Exception):
+    """``forced`` ran out: ``probs`` are the probabilities of the pending draw's outcomes."""
+
+    def __init__(self, probs):
+        super().__init__("forced outcomes exhausted")
+        self.probs = [float(p) for p in probs]
+
+
+def relax_probabilities(p0, p1_pop, g, c, p1):
+    """``(pr [6], den [6])`` of the trajectory contract: the outcome probabilities and each operator's own state-given
+    probability (the weight 1 - p1 or p1, and g or d of a jump, left out), from the populations P0, P1."""
+    total = p0 + p1_pop
+    pa, pb = p0 / total, p1_pop / total
+    c2 = c * c
+    d, w0 = max(0.0, (1.0 - g) - c2), 1.0 - p1
+    k0, k3 = pa + c2 * pb, c2 * pa + pb
+    return [w0 * k0, w0 * (g * pb), w0 * (d * pb), p1 * k3, p1 * (g * pa), p1 * (d * pa)], [k0, pb, pb, k3, pa, pa]
+
+
+def relax_matrix(pick, c, t):
+    """The real 2x2 matrix of outcome ``pick`` with the factor ``t``, as the trajectory contract tabulates it."""
+    return np.array({0: [[t, 0.0], [0.0, c * t]], 1: [[0.0, t], [0.0, 0.0]], 2: [[0.0, 0.0], [0.0, t]],
+                     3: [[c * t, 0.0], [0.0, t]], 4: [[0.0, 0.0], [t, 0.0]], 5: [[t, 0.0], [0.0, 0.0]]}[pick], dtype=complex)
+
+
+def contract(batch, c, tensors, letters):
+    """<letters> of circuit ``c``'s site tensors by the left-to-right contraction, NOT over the norm (``letters`` None: the norm)."""
+    n = int(batch.n_qubits[c])
+    ro = batch.readout[int(batch.site_ptr[c]):int(batch.site_ptr[c]) + n]
+    e = np.ones((1, 1), dtype=complex)
+    for q in range(n):
+        letter = int(letters[q]) if letters is not None else 0
+        o = np.diag([ro[q, 0] + ro[q, 1], ro[q, 1] - ro[q, 0]]).astype(complex) if letter == 3 else _LETTER[letter]
+        f = np.einsum("pl,lsr->psr", e, tensors[q])
+        e = np.einsum("ptq,ts,psr->qr", tensors[q].conj(), o, f)
+    return float(e[0, 0].real)
+
+
+def contract_terms(batch, c, tensors):
+    """The circuit's term values from site tensors, over the norm."""
+    n, norm = int(batch.n_qubits[c]), contract(batch, c, tensors, None)
+    return np.array([contract(batch, c, tensors, batch.letters[int(batch.term_off[t]):int(batch.term_off[t]) + n]) / norm
+                     for t in range(int(batch.term_ptr[c]), int(batch.term_ptr[c + 1]))])
+
+
 def interpret(batch, c, method="lapack", trajectory=0, seed=0, run_key=None, forced=None):
-    """Circuit ``c`` of an ``MpsBatch`` as one unit (trajectory number ``trajectory``): a dict of ``terms`` [n_terms], ``value``,
-    ``norm``, ``discarded``, ``error_bound``, ``bond``, ``n_dec`` (decompositions), ``n_free`` (those at which the bond cap dropped no
-    column), ``floor_d`` / ``floor_b`` (``stat_floor``), ``gap`` (smallest relative gap over the cuts at which the bond cap dropped a column, one with sigma^2 > cutoff *
-    total; inf without one), ``drop`` (largest relative weight of a dropped column), ``margin``
-    (smallest |u - threshold|), ``prob`` (the probability of the drawn outcomes).  ``forced``: the outcome of every noise record
-    instead of a draw (the enumeration of tests/test_mps_cpu.py)."""
+    """Circuit ``c`` of an ``MpsBatch`` as one unit (trajectory number ``trajectory``), all six record kinds: a dict of ``terms``
+    [n_terms], ``value``, ``norm``, ``discarded``, ``error_bound``, ``bond``, ``n_dec`` (decompositions), ``n_free`` (those at which the
+    bond cap dropped no column), ``floor_d`` / ``floor_b`` (``stat_floor``), ``gap`` (smallest relative gap over the cuts at which the
+    bond cap dropped a column, one with sigma^2 > cutoff * total; inf without one), ``drop`` (largest relative weight of a dropped
+    column), ``cut_margin``, ``margin`` (smallest |u - threshold| over every draw), ``prob`` (of the outcomes taken, drawn or forced),
+    ``min_prob`` (the smallest state-given probability of a chosen relaxation operator: t = 1 / sqrt of it), ``outcomes`` (what
+    was taken, in draw order), ``operators`` (every matrix applied, in order, with its sites: what
+    ``mps_relax_cases.dense_replay`` carries a dense vector through) and ``tensors`` (the site tensors).
+
+    ``forced``: the outcomes of the draws in the order they are taken (a depolarising draw at lambda != 0, then every relaxation),
+    instead of uniforms; a ``forced`` that runs out raises ``NeedOutcome`` with the probabilities of the pending draw, which is
+    how ``mps_relax_cases.enumerate_paths`` walks the tree of outcomes and prunes the zero-probability ones."""
     n, chi, cutoff = int(batch.n_qubits[c]), int(batch.max_bond), float(batch.cutoff)
     run_key = c if run_key is None else run_key
     a = [np.array([1.0, 0.0], dtype=complex).reshape(1, 2, 1) for _ in range(n)]
-    out = {"discarded": 0.0, "error_bound": 0.0, "bond": 1, "n_dec": 0, "n_free": 0, "floor_d": 0.0, "floor_b": 0.0, "gap": math.inf, "drop": 0.0, "margin": math.inf, "prob": 1.0,
-           "cut_margin": math.inf}
-    state = {"centre": 0, "noise": 0}
+    out = {"discarded": 0.0, "error_bound": 0.0, "bond": 1, "n_dec": 0, "n_free": 0, "floor_d": 0.0, "floor_b": 0.0, "gap": math.inf,
+           "drop": 0.0, "margin": math.inf, "prob": 1.0, "cut_margin": math.inf, "min_prob": math.inf, "outcomes": [], "operators": []}
+    state = {"centre": 0, "noise": 0, "taken": 0}
 
     def cplx(po, count):
         v = batch.params[po:po + 2 * count]
         return v[0::2] + 1j * v[1::2]
 
     def one_site(q, m):
+        out["operators"].append(((q,), np.array(m, dtype=complex)))
         a[q] = np.einsum("ts,lsr->ltr", m, a[q])
 
     def bond_op(q, g, left):
         dl, dr = a[q].shape[0], a[q + 1].shape[2]
         theta = np.einsum("lsm,mtr->lstr", a[q], a[q + 1])
-        if g is not None:   # g over bit(q) + 2 bit(q + 1): g4[s1', s0', s1, s0]
+        if g is not None:   # g over bit(q) + 2 bit(q + 1)
+            out["operators"].append(((q, q + 1), np.array(g, dtype=complex)))
             theta = np.einsum("badc,lcdr->labr", g.reshape(2, 2, 2, 2), theta)
         m = theta.reshape(2 * dl, 2 * dr)
         if left:
@@ -144,8 +202,8 @@ def interpret(batch, c, method="lapack", trajectory=0, seed=0, run_key=None, for
         out["error_bound"] += math.sqrt(2.0 * eps)
         out["bond"] = max(out["bond"], k)
         out["n_dec"] += 1
-        capped = k < len(sig2) and bool(sig2[k] > cutoff * total)   # the bond cap dropped a column, not the cutoff
-        if not capped:   # only the cutoff dropped columns here: each holds at most cutoff of the weight, and that is all one knows
+        capped = k < len(sig2) and bool(sig2[k] > cutoff * total)
+        if not capped:
             out["n_free"] += 1
             out["floor_d"] += (len(sig2) - k) * cutoff
             out["floor_b"] += math.sqrt(2.0 * (len(sig2) - k) * cutoff)
@@ -166,74 +224,113 @@ def interpret(batch, c, method="lapack", trajectory=0, seed=0, run_key=None, for
             a[q] = qk.reshape(dl, 2, k)
             a[q + 1] = p.reshape(k, 2, dr)
 
-    def draw(two, lam):
-        index = state["noise"]
-        state["noise"] += 1
+    def move_to(q):
+        while state["centre"] < q:
+            bond_op(state["centre"], None, False)
+            state["centre"] += 1
+        while state["centre"] > q:
+            bond_op(state["centre"] - 1, None, True)
+            state["centre"] -= 1
+
+    def take(probs):
+        """The next forced outcome, or NeedOutcome."""
+        if state["taken"] >= len(forced):
+            raise NeedOutcome(probs)
+        pick = int(forced[state["taken"]])
+        state["taken"] += 1
+        return pick
+
+    def depolarise(index, two, lam):
+        if lam == 0.0:
+            return 0
         m = 15 if two else 3
         w = lam * 0.0625 if two else lam * 0.25
         first = 1.0 - float(m) * w
         if forced is not None:
-            code = int(forced[index])
-            out["prob"] *= first if code == 0 else w
-            return code
-        if lam == 0.0:
-            return 0
-        u = float(tc.uniforms(index, 0, trajectory, 1, seed, run_key)[0])
-        run, code = first, 0
-        out["margin"] = min(out["margin"], abs(u - run))
-        while code < m and not run > u:
-            run = run + w
-            code += 1
-            if code < m:
-                out["margin"] = min(out["margin"], abs(u - run))
+            code = take([first] + [w] * m)
+        else:
+            u = float(tc.uniforms(index, 0, trajectory, 1, seed, run_key)[0])
+            run, code = first, 0
+            out["margin"] = min(out["margin"], abs(u - run))
+            while code < m and not run > u:
+                run = run + w
+                code += 1
+                if code < m:
+                    out["margin"] = min(out["margin"], abs(u - run))
+        out["prob"] *= first if code == 0 else w
+        out["outcomes"].append(code)
         return code
 
+    def relax(index, sub, q, g, c_, p1):
+        move_to(q)
+        w = np.abs(a[q]) ** 2
+        pr, den = relax_probabilities(float(w[:, 0, :].sum()), float(w[:, 1, :].sum()), g, c_, p1)
+        if forced is not None:
+            pick = take(pr)
+            assert pr[pick] > 0.0, "a forced outcome of probability 0"
+        else:
+            u = float(tc.uniforms(index, sub, trajectory, 1, seed, run_key)[0])
+            run, pick, last = 0.0, -1, -1
+            for j in range(6):
+                run = run + pr[j]
+                if pick < 0 and run > u:
+                    pick = j
+                if pr[j] > 0.0:
+                    last = j
+                if j < 5:   # the last sum is 1 up to rounding: no threshold, the rule falls back to `last`
+                    out["margin"] = min(out["margin"], abs(u - run))
+            pick = pick if pick >= 0 else max(last, 0)
+        t = 1.0 / math.sqrt(den[pick])
+        one_site(q, relax_matrix(pick, c_, t))
+        out["error_bound"] *= t
+        out["floor_b"] *= t
+        out["prob"] *= pr[pick]
+        out["min_prob"] = min(out["min_prob"], den[pick])
+        out["outcomes"].append(pick)
+
     for kind, site, orient, po in batch.ops[int(batch.op_ptr[c]):int(batch.op_ptr[c + 1])].tolist():
-        if kind == 0:
+        if kind == KIND_U1:
             one_site(site, cplx(po, 4).reshape(2, 2))
-        elif kind == 5 and n >= 2:
-            while state["centre"] < site:
-                bond_op(state["centre"], None, False)
-                state["centre"] += 1
-            while state["centre"] > site:
-                bond_op(state["centre"] - 1, None, True)
-                state["centre"] -= 1
+        elif kind == KIND_U2 and n >= 2:
+            move_to(site)
             g = cplx(po, 16).reshape(4, 4)
             if orient:
                 flip = [0, 2, 1, 3]
                 g = g[np.ix_(flip, flip)]
             bond_op(site, g, False)
             state["centre"] = site + 1
-        elif kind == 6:
-            code = draw(False, float(batch.params[po]))
+        elif kind in (KIND_DEPOL1, KIND_NOISE1):
+            index = state["noise"]
+            state["noise"] += 1
+            code = depolarise(index, False, float(batch.params[po]))
             if code:
                 one_site(site, _LETTER[code])
-        elif kind == 7 and n >= 2:
-            code = draw(True, float(batch.params[po]))
+            if kind == KIND_NOISE1:
+                relax(index, 1, site, *(float(v) for v in batch.params[po + 1:po + 4]))
+        elif kind in (KIND_DEPOL2, KIND_NOISE2) and n >= 2:
+            index = state["noise"]
+            state["noise"] += 1
+            code = depolarise(index, True, float(batch.params[po]))
             q0, q1 = (site + 1, site) if orient else (site, site + 1)
             if code & 3:
                 one_site(q0, _LETTER[code & 3])
             if code >> 2:
                 one_site(q1, _LETTER[code >> 2])
+            if kind == KIND_NOISE2:   # the site order follows the centre, the sub-draw and the triple the gate's qubit
+                order = (site, site + 1) if state["centre"] <= site else (site + 1, site)
+                for q in order:
+                    second = int(q != q0)
+                    relax(index, 1 + second, q, *(float(v) for v in batch.params[po + 1 + 3 * second:po + 4 + 3 * second]))
+    if forced is not None:
+        assert state["taken"] == len(forced), "more forced outcomes than draws"
 
-    ro = batch.readout[int(batch.site_ptr[c]):int(batch.site_ptr[c]) + n]
-
-    def contract(letters):
-        e = np.ones((1, 1), dtype=complex)
-        for q in range(n):
-            letter = int(letters[q]) if letters is not None else 0
-            o = np.diag([ro[q, 0] + ro[q, 1], ro[q, 1] - ro[q, 0]]).astype(complex) if letter == 3 else _LETTER[letter]
-            f = np.einsum("pl,lsr->psr", e, a[q])
-            e = np.einsum("ptq,ts,psr->qr", a[q].conj(), o, f)
-        return float(e[0, 0].real)
-
-    norm = contract(None)
+    norm = contract(batch, c, a, None)
     tb, te = int(batch.term_ptr[c]), int(batch.term_ptr[c + 1])
-    terms = np.array([contract(batch.letters[int(batch.term_off[t]):int(batch.term_off[t]) + n]) / norm for t in range(tb, te)])
+    terms = contract_terms(batch, c, a)
     value = 0.0
     for cf, t in zip(batch.coeff[tb:te], terms):
         value = value + float(cf) * float(t)
-    out.update(terms=terms, value=value, norm=norm, n=n, abs_coeff=float(np.abs(batch.coeff[tb:te]).sum()))
+    out.update(terms=terms, value=value, norm=norm, n=n, abs_coeff=float(np.abs(batch.coeff[tb:te]).sum()), tensors=a)
     return out
 
 

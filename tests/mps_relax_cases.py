@@ -1,19 +1,7 @@
-"""The interpreter, the measured tolerance table and the cases of thermal relaxation on matrix-product states (the NOISE1 / NOISE2
-records of mlqem_mps_run_f64), shared by tests/test_mps_relax_cpu.py and tests/test_gpu_mps_relax.py (no test in here).  numpy only.
-
-Interpreter.  ``mps_cases.interpret`` is a closure over the four old kinds, so ``interpret`` here follows the FULL record format of
-include/mlqem_hip.h on its own: U1, U2 (the centre's moves, theta, the decomposition of ``mps_cases.decompose``, ``lapack`` or
-``jacobi``, the keep rule, eps, the rescaling), DEPOL1 / DEPOL2, and NOISE1 / NOISE2: the depolarising draw with sub-draw 0, then per
-qubit the move of the centre, the populations of the centre's tensor, the six outcomes against their running sum (the first above
-u, else the last of non-zero probability), the chosen operator over the root of its own state-given probability, and
-``error_bound`` <- t ``error_bound``.  ``forced``: the outcomes of the draws in the order they are taken (a depolarising draw at
-lambda != 0, then every relaxation), instead of uniforms; a ``forced`` that runs out raises ``NeedOutcome`` with the probabilities
-of the pending draw, which is how ``enumerate_paths`` walks the tree of outcomes and prunes the zero-probability ones.
-
-Reports besides the terms: ``prob`` (of the outcomes taken), ``margin`` (smallest |u - threshold| over every draw), ``gap`` and
-``cut_margin`` (as in ``mps_cases``), ``min_prob`` (the smallest state-given probability of a chosen relaxation operator: t =
-1 / sqrt of it), ``outcomes`` (what was taken, in draw order), ``operators`` (every matrix applied, in order, with its sites: what
-``dense_replay`` carries a dense vector through) and ``tensors``.
+"""The enumeration of outcomes, the dense replay, the measured tolerance table and the cases of thermal relaxation on matrix-product
+states (the NOISE1 / NOISE2 records of mlqem_mps_run_f64), shared by tests/test_mps_relax_cpu.py and tests/test_gpu_mps_relax.py (no
+test in here).  numpy only.  The interpreter is ``mps_cases.interpret``, which follows the full record format; ``enumerate_paths``
+walks its tree of outcomes through ``forced=`` and ``NeedOutcome``, ``dense_replay`` carries a dense vector through its ``operators``.
 
 Tolerance, as for the other MPS cases: FACTOR = 16 x the measured difference of the interpreter's two
 decompositions on the case, floored at ``sim_cases.term_bound`` of its widest circuit (the 40-qubit case: the measurement alone).
@@ -32,225 +20,11 @@ import mps_cases as mc
 import relax_cases as rc
 import sim_cases as sc
 import traj_cases as tc
+from mps_cases import KIND_DEPOL1, KIND_DEPOL2, KIND_NOISE1, KIND_NOISE2, NeedOutcome
 
 U = sc.U
 MARGIN, MIN_GAP, CUT_FACTOR, FACTOR = mc.MARGIN, mc.MIN_GAP, mc.CUT_FACTOR, mc.FACTOR
 MIN_PROB = 1e-3
-KIND_U1, KIND_U2, KIND_DEPOL1, KIND_DEPOL2, KIND_NOISE1, KIND_NOISE2 = 0, 5, 6, 7, 10, 11
-_LETTER = (np.eye(2, dtype=complex), sc.X, sc.Y, sc.Z)
-
-
-class NeedOutcome(Exception):
-    """``forced`` ran out: ``probs`` are the probabilities of the pending draw's outcomes."""
-
-    def __init__(self, probs):
-        super().__init__("forced outcomes exhausted")
-        self.probs = [float(p) for p in probs]
-
-
-def relax_probabilities(p0, p1_pop, g, c, p1):
-    """``(pr [6], den [6])`` of the trajectory contract: the outcome probabilities and each operator's own state-given
-    probability (the weight 1 - p1 or p1, and g or d of a jump, left out), from the populations P0, P1."""
-    total = p0 + p1_pop
-    pa, pb = p0 / total, p1_pop / total
-    c2 = c * c
-    d, w0 = max(0.0, (1.0 - g) - c2), 1.0 - p1
-    k0, k3 = pa + c2 * pb, c2 * pa + pb
-    return [w0 * k0, w0 * (g * pb), w0 * (d * pb), p1 * k3, p1 * (g * pa), p1 * (d * pa)], [k0, pb, pb, k3, pa, pa]
-
-
-def relax_matrix(pick, c, t):
-    """The real 2x2 matrix of outcome ``pick`` with the factor ``t``, as the trajectory contract tabulates it."""
-    return np.array({0: [[t, 0.0], [0.0, c * t]], 1: [[0.0, t], [0.0, 0.0]], 2: [[0.0, 0.0], [0.0, t]],
-                     3: [[c * t, 0.0], [0.0, t]], 4: [[0.0, 0.0], [t, 0.0]], 5: [[t, 0.0], [0.0, 0.0]]}[pick], dtype=complex)
-
-
-def interpret(batch, c, method="lapack", trajectory=0, seed=0, run_key=None, forced=None):
-    """Circuit ``c`` of an ``MpsBatch`` as one unit: the dict of ``mps_cases.interpret`` plus what the module docstring lists."""
-    n, chi, cutoff = int(batch.n_qubits[c]), int(batch.max_bond), float(batch.cutoff)
-    run_key = c if run_key is None else run_key
-    a = [np.array([1.0, 0.0], dtype=complex).reshape(1, 2, 1) for _ in range(n)]
-    out = {"discarded": 0.0, "error_bound": 0.0, "bond": 1, "n_dec": 0, "n_free": 0, "floor_d": 0.0, "floor_b": 0.0, "gap": math.inf,
-           "drop": 0.0, "margin": math.inf, "prob": 1.0, "cut_margin": math.inf, "min_prob": math.inf, "outcomes": [], "operators": []}
-    state = {"centre": 0, "noise": 0, "taken": 0}
-
-    def cplx(po, count):
-        v = batch.params[po:po + 2 * count]
-        return v[0::2] + 1j * v[1::2]
-
-    def one_site(q, m):
-        out["operators"].append(((q,), np.array(m, dtype=complex)))
-        a[q] = np.einsum("ts,lsr->ltr", m, a[q])
-
-    def bond_op(q, g, left):
-        dl, dr = a[q].shape[0], a[q + 1].shape[2]
-        theta = np.einsum("lsm,mtr->lstr", a[q], a[q + 1])
-        if g is not None:   # g over bit(q) + 2 bit(q + 1)
-            out["operators"].append(((q, q + 1), np.array(g, dtype=complex)))
-            theta = np.einsum("badc,lcdr->labr", g.reshape(2, 2, 2, 2), theta)
-        m = theta.reshape(2 * dl, 2 * dr)
-        if left:
-            m = m.T
-        q_full, sig2 = mc.decompose(m, method)
-        total = 0.0
-        for s2 in sig2:
-            total = total + float(s2)
-        k = 0
-        for r in range(min(min(m.shape), chi)):
-            if not sig2[r] > cutoff * total:
-                break
-            k = r + 1
-        k = max(k, 1)
-        kept = float(np.sum(sig2[:k]))
-        dropped = 0.0
-        for s2 in sig2[k:]:
-            dropped = dropped + float(s2)
-        eps = dropped / total
-        out["discarded"] += eps
-        out["error_bound"] += math.sqrt(2.0 * eps)
-        out["bond"] = max(out["bond"], k)
-        out["n_dec"] += 1
-        capped = k < len(sig2) and bool(sig2[k] > cutoff * total)
-        if not capped:
-            out["n_free"] += 1
-            out["floor_d"] += (len(sig2) - k) * cutoff
-            out["floor_b"] += math.sqrt(2.0 * (len(sig2) - k) * cutoff)
-        live = sig2[sig2 > 0.0] / (cutoff * total) if cutoff > 0.0 else np.zeros(0)
-        if live.size:
-            out["cut_margin"] = min(out["cut_margin"], float(np.min(np.abs(np.log(live)))))
-        if k < len(sig2):
-            out["drop"] = max(out["drop"], float(sig2[k]) / total)
-            if capped:
-                sigma = np.sqrt(sig2)
-                out["gap"] = min(out["gap"], float((sigma[k - 1] - sigma[k]) / sigma[0]))
-        qk = q_full[:, :k]
-        p = (qk.conj().T @ m) * math.sqrt(total / kept)
-        if left:
-            a[q + 1] = qk.T.reshape(k, 2, dr)
-            a[q] = p.T.reshape(dl, 2, k)
-        else:
-            a[q] = qk.reshape(dl, 2, k)
-            a[q + 1] = p.reshape(k, 2, dr)
-
-    def move_to(q):
-        while state["centre"] < q:
-            bond_op(state["centre"], None, False)
-            state["centre"] += 1
-        while state["centre"] > q:
-            bond_op(state["centre"] - 1, None, True)
-            state["centre"] -= 1
-
-    def take(probs):
-        """The next forced outcome, or NeedOutcome."""
-        if state["taken"] >= len(forced):
-            raise NeedOutcome(probs)
-        pick = int(forced[state["taken"]])
-        state["taken"] += 1
-        return pick
-
-    def depolarise(index, two, lam):
-        if lam == 0.0:
-            return 0
-        m = 15 if two else 3
-        w = lam * 0.0625 if two else lam * 0.25
-        first = 1.0 - float(m) * w
-        if forced is not None:
-            code = take([first] + [w] * m)
-        else:
-            u = float(tc.uniforms(index, 0, trajectory, 1, seed, run_key)[0])
-            run, code = first, 0
-            out["margin"] = min(out["margin"], abs(u - run))
-            while code < m and not run > u:
-                run = run + w
-                code += 1
-                if code < m:
-                    out["margin"] = min(out["margin"], abs(u - run))
-        out["prob"] *= first if code == 0 else w
-        out["outcomes"].append(code)
-        return code
-
-    def relax(index, sub, q, g, c_, p1):
-        move_to(q)
-        w = np.abs(a[q]) ** 2
-        pr, den = relax_probabilities(float(w[:, 0, :].sum()), float(w[:, 1, :].sum()), g, c_, p1)
-        if forced is not None:
-            pick = take(pr)
-            assert pr[pick] > 0.0, "a forced outcome of probability 0"
-        else:
-            u = float(tc.uniforms(index, sub, trajectory, 1, seed, run_key)[0])
-            run, pick, last = 0.0, -1, -1
-            for j in range(6):
-                run = run + pr[j]
-                if pick < 0 and run > u:
-                    pick = j
-                if pr[j] > 0.0:
-                    last = j
-                if j < 5:   # the last sum is 1 up to rounding: no threshold, the rule falls back to `last`
-                    out["margin"] = min(out["margin"], abs(u - run))
-            pick = pick if pick >= 0 else max(last, 0)
-        t = 1.0 / math.sqrt(den[pick])
-        one_site(q, relax_matrix(pick, c_, t))
-        out["error_bound"] *= t
-        out["floor_b"] *= t
-        out["prob"] *= pr[pick]
-        out["min_prob"] = min(out["min_prob"], den[pick])
-        out["outcomes"].append(pick)
-
-    for kind, site, orient, po in batch.ops[int(batch.op_ptr[c]):int(batch.op_ptr[c + 1])].tolist():
-        if kind == KIND_U1:
-            one_site(site, cplx(po, 4).reshape(2, 2))
-        elif kind == KIND_U2 and n >= 2:
-            move_to(site)
-            g = cplx(po, 16).reshape(4, 4)
-            if orient:
-                flip = [0, 2, 1, 3]
-                g = g[np.ix_(flip, flip)]
-            bond_op(site, g, False)
-            state["centre"] = site + 1
-        elif kind in (KIND_DEPOL1, KIND_NOISE1):
-            index = state["noise"]
-            state["noise"] += 1
-            code = depolarise(index, False, float(batch.params[po]))
-            if code:
-                one_site(site, _LETTER[code])
-            if kind == KIND_NOISE1:
-                relax(index, 1, site, *(float(v) for v in batch.params[po + 1:po + 4]))
-        elif kind in (KIND_DEPOL2, KIND_NOISE2) and n >= 2:
-            index = state["noise"]
-            state["noise"] += 1
-            code = depolarise(index, True, float(batch.params[po]))
-            q0, q1 = (site + 1, site) if orient else (site, site + 1)
-            if code & 3:
-                one_site(q0, _LETTER[code & 3])
-            if code >> 2:
-                one_site(q1, _LETTER[code >> 2])
-            if kind == KIND_NOISE2:   # the site order follows the centre, the sub-draw and the triple the gate's qubit
-                order = (site, site + 1) if state["centre"] <= site else (site + 1, site)
-                for q in order:
-                    second = int(q != q0)
-                    relax(index, 1 + second, q, *(float(v) for v in batch.params[po + 1 + 3 * second:po + 4 + 3 * second]))
-    if forced is not None:
-        assert state["taken"] == len(forced), "more forced outcomes than draws"
-
-    ro = batch.readout[int(batch.site_ptr[c]):int(batch.site_ptr[c]) + n]
-
-    def contract(letters):
-        e = np.ones((1, 1), dtype=complex)
-        for q in range(n):
-            letter = int(letters[q]) if letters is not None else 0
-            o = np.diag([ro[q, 0] + ro[q, 1], ro[q, 1] - ro[q, 0]]).astype(complex) if letter == 3 else _LETTER[letter]
-            f = np.einsum("pl,lsr->psr", e, a[q])
-            e = np.einsum("ptq,ts,psr->qr", a[q].conj(), o, f)
-        return float(e[0, 0].real)
-
-    norm = contract(None)
-    tb, te = int(batch.term_ptr[c]), int(batch.term_ptr[c + 1])
-    terms = np.array([contract(batch.letters[int(batch.term_off[t]):int(batch.term_off[t]) + n]) / norm for t in range(tb, te)])
-    value = 0.0
-    for cf, t in zip(batch.coeff[tb:te], terms):
-        value = value + float(cf) * float(t)
-    out.update(terms=terms, value=value, norm=norm, n=n, abs_coeff=float(np.abs(batch.coeff[tb:te]).sum()), tensors=a)
-    return out
 
 
 def enumerate_paths(batch, c, method="lapack"):
@@ -260,7 +34,7 @@ def enumerate_paths(batch, c, method="lapack"):
 
     def walk(prefix):
         try:
-            res = interpret(batch, c, method, forced=prefix)
+            res = mc.interpret(batch, c, method, forced=prefix)
         except NeedOutcome as need:
             return sum(walk(prefix + [j]) if p > 0.0 else _unpruned(batch, c, len(prefix) + 1) for j, p in enumerate(need.probs))
         paths.append((res["prob"], res["terms"], tuple(res["outcomes"])))
@@ -382,7 +156,7 @@ def lower(case_id, trajectories=None):
 def reference(case_id, method="lapack"):
     """``[circuit][trajectory]`` of interpreter results (run key = the circuit's position), computed once."""
     c, batch = case(case_id), lower(case_id)
-    return [[interpret(batch, j, method, t, c["seed"]) for t in range(c["trajectories"])] for j in range(len(batch))]
+    return [[mc.interpret(batch, j, method, t, c["seed"]) for t in range(c["trajectories"])] for j in range(len(batch))]
 
 
 def measured_difference(case_id):
@@ -434,7 +208,7 @@ def stat_case():
 def stat_reference():
     """``(terms [T, n_terms] of the interpreter, the density-matrix oracle's term values)``."""
     circ, obs, batch = stat_case()
-    rows = np.stack([interpret(batch, 0, "lapack", t, STAT["seed"])["terms"] for t in range(STAT["trajectories"])])
+    rows = np.stack([mc.interpret(batch, 0, "lapack", t, STAT["seed"])["terms"] for t in range(STAT["trajectories"])])
     return rows, rc.simulate(circ, obs, model(STAT["noise"]))[1]
 
 
@@ -458,7 +232,7 @@ def shots_reference(method="lapack"):
 
     _, _, batch = shots_case()
     mps, shots, seed, n_traj, n = batch.mps, SHOTS["shots"], SHOTS["seed"], SHOTS["trajectories"], SHOTS["n"]
-    units = [interpret(mps, 0, method, t, seed)["tensors"] for t in range(n_traj)]
+    units = [mc.interpret(mps, 0, method, t, seed)["tensors"] for t in range(n_traj)]
     flip = batch.flip[:n]
     res = {"bits": [], "probs": [], "margin": math.inf, "flip_margin": math.inf}
     for g in range(int(batch.group_ptr[0]), int(batch.group_ptr[1])):

@@ -1,11 +1,8 @@
 """The oracles, the measured margins and the case grid of the matrix-product-state sampler (mlqem_mps_sample_f64), shared by
 tests/test_mps_shots_cpu.py and tests/test_gpu_mps_shots.py (no test in here).  numpy only.
 
-Oracle (a), ``reference`` (``sweep`` per group and trajectory): the draw contract of include/mlqem_hip.h followed on the host, on site
-tensors of the host's own.
-``tensors`` restates the record loop of ``mps_cases.interpret`` (same ``decompose``, same keep rule, same noise draws) and returns
-the tensors; tests/test_mps_shots_cpu.py asserts that they give ``mps_cases.interpret``'s term values.  Both decompositions, ``lapack``
-and ``jacobi``.  The environments and the sweep are plain einsums, not the kernel's loops: another order of the same arithmetic.
+Oracle (a), ``reference`` (``sweep`` per group and trajectory): the draw contract of include/mlqem_hip.h followed on the host, on the
+site tensors of the host's own interpreter (``mps_cases.interpret(...)["tensors"]``).  Both decompositions, ``lapack`` and ``jacobi``.  The environments and the sweep are plain einsums, not the kernel's loops: another order of the same arithmetic.
 
 Oracle (b), ``dense_shots``: for an ideal circuit within the dense cap, a sampler that never builds an MPS.  The state vector (the
 gates of ``sim_cases``), rotated into the group's basis, and every conditional weight as a marginal sum of |amplitude|^2 over the
@@ -27,127 +24,11 @@ import numpy as np
 
 import mps_cases as mc
 import sim_cases as sc
-import traj_cases as tc
 from shots_cases import philox4x32_10
 
 FACTOR = 16
 FLOOR = 1e-12
 C = 0.7071067811865476
-_LETTER = (np.eye(2, dtype=complex), sc.X, sc.Y, sc.Z)
-
-
-# ---- the site tensors of the interpreter -----------------------------------------------------------------------------------------------
-def tensors(batch, c, method="lapack", trajectory=0, seed=0, run_key=None):
-    """``(a, stats)``: the site tensors [(chi_l, 2, chi_r)] of circuit ``c`` of an ``MpsBatch`` after its records, and discarded /
-    error_bound / bond, record by record as ``mps_cases.interpret`` runs them."""
-    n, chi, cutoff = int(batch.n_qubits[c]), int(batch.max_bond), float(batch.cutoff)
-    run_key = c if run_key is None else run_key
-    a = [np.array([1.0, 0.0], dtype=complex).reshape(1, 2, 1) for _ in range(n)]
-    stats = {"discarded": 0.0, "error_bound": 0.0, "bond": 1}
-    state = {"centre": 0, "noise": 0}
-
-    def cplx(po, count):
-        v = batch.params[po:po + 2 * count]
-        return v[0::2] + 1j * v[1::2]
-
-    def one_site(q, m):
-        a[q] = np.einsum("ts,lsr->ltr", m, a[q])
-
-    def bond_op(q, g, left):
-        dl, dr = a[q].shape[0], a[q + 1].shape[2]
-        theta = np.einsum("lsm,mtr->lstr", a[q], a[q + 1])
-        if g is not None:
-            theta = np.einsum("badc,lcdr->labr", g.reshape(2, 2, 2, 2), theta)
-        m = theta.reshape(2 * dl, 2 * dr)
-        if left:
-            m = m.T
-        q_full, sig2 = mc.decompose(m, method)
-        total = 0.0
-        for s2 in sig2:
-            total = total + float(s2)
-        k = 0
-        for r in range(min(min(m.shape), chi)):
-            if not sig2[r] > cutoff * total:
-                break
-            k = r + 1
-        k = max(k, 1)
-        kept = float(np.sum(sig2[:k]))
-        dropped = 0.0
-        for s2 in sig2[k:]:
-            dropped = dropped + float(s2)
-        eps = dropped / total
-        stats["discarded"] += eps
-        stats["error_bound"] += math.sqrt(2.0 * eps)
-        stats["bond"] = max(stats["bond"], k)
-        qk = q_full[:, :k]
-        p = (qk.conj().T @ m) * math.sqrt(total / kept)
-        if left:
-            a[q + 1] = qk.T.reshape(k, 2, dr)
-            a[q] = p.T.reshape(dl, 2, k)
-        else:
-            a[q] = qk.reshape(dl, 2, k)
-            a[q + 1] = p.reshape(k, 2, dr)
-
-    def draw(two, lam):
-        index = state["noise"]
-        state["noise"] += 1
-        if lam == 0.0:
-            return 0
-        m = 15 if two else 3
-        w = lam * 0.0625 if two else lam * 0.25
-        u = float(tc.uniforms(index, 0, trajectory, 1, seed, run_key)[0])
-        run, code = 1.0 - float(m) * w, 0
-        while code < m and not run > u:
-            run = run + w
-            code += 1
-        return code
-
-    for kind, site, orient, po in batch.ops[int(batch.op_ptr[c]):int(batch.op_ptr[c + 1])].tolist():
-        if kind == 0:
-            one_site(site, cplx(po, 4).reshape(2, 2))
-        elif kind == 5 and n >= 2:
-            while state["centre"] < site:
-                bond_op(state["centre"], None, False)
-                state["centre"] += 1
-            while state["centre"] > site:
-                bond_op(state["centre"] - 1, None, True)
-                state["centre"] -= 1
-            g = cplx(po, 16).reshape(4, 4)
-            if orient:
-                flip = [0, 2, 1, 3]
-                g = g[np.ix_(flip, flip)]
-            bond_op(site, g, False)
-            state["centre"] = site + 1
-        elif kind == 6:
-            code = draw(False, float(batch.params[po]))
-            if code:
-                one_site(site, _LETTER[code])
-        elif kind == 7 and n >= 2:
-            code = draw(True, float(batch.params[po]))
-            q0, q1 = (site + 1, site) if orient else (site, site + 1)
-            if code & 3:
-                one_site(q0, _LETTER[code & 3])
-            if code >> 2:
-                one_site(q1, _LETTER[code >> 2])
-    return a, stats
-
-
-def contract_terms(batch, c, a):
-    """The circuit's term values from site tensors, as ``mps_cases.interpret`` contracts them (over the norm)."""
-    n = int(batch.n_qubits[c])
-    ro = batch.readout[int(batch.site_ptr[c]):int(batch.site_ptr[c]) + n]
-
-    def contract(letters):
-        e = np.ones((1, 1), dtype=complex)
-        for q in range(n):
-            letter = int(letters[q]) if letters is not None else 0
-            o = np.diag([ro[q, 0] + ro[q, 1], ro[q, 1] - ro[q, 0]]).astype(complex) if letter == 3 else _LETTER[letter]
-            e = np.einsum("ptq,ts,psr->qr", a[q].conj(), o, np.einsum("pl,lsr->psr", e, a[q]))
-        return float(e[0, 0].real)
-
-    norm = contract(None)
-    return np.array([contract(batch.letters[int(batch.term_off[t]):int(batch.term_off[t]) + n]) / norm
-                     for t in range(int(batch.term_ptr[c]), int(batch.term_ptr[c + 1]))])
 
 
 # ---- the draws -------------------------------------------------------------------------------------------------------------------------
@@ -341,18 +222,18 @@ def reference(case_id, method="lapack"):
     out = []
     for k in range(len(batch)):
         n = int(mps.n_qubits[k])
-        units = [tensors(mps, k, method, t, seed) for t in range(min(n_traj, shots))]
+        units = [mc.interpret(mps, k, method, t, seed) for t in range(min(n_traj, shots))]
         flip = batch.flip[int(mps.site_ptr[k]):int(mps.site_ptr[k]) + n]
         res = {"bits": [], "reported": [], "probs": [], "margin": math.inf, "flip_margin": math.inf,
-               "discarded": sum(u[1]["discarded"] for u in units) / len(units), "error_bound": sum(u[1]["error_bound"] for u in units) / len(units),
-               "bond": max(u[1]["bond"] for u in units), "mps_terms": contract_terms(mps, k, units[0][0])}
+               "discarded": sum(u["discarded"] for u in units) / len(units), "error_bound": sum(u["error_bound"] for u in units) / len(units),
+               "bond": max(u["bond"] for u in units), "mps_terms": mc.contract_terms(mps, k, units[0]["tensors"])}
         g0, g1 = int(batch.group_ptr[k]), int(batch.group_ptr[k + 1])
         for g in range(g0, g1):
             letters = batch.basis[int(batch.group_off[g]):int(batch.group_off[g]) + n]
             reported, probs = np.zeros((shots, n), dtype=np.int64), np.zeros((shots, n))
-            for t, (a, _) in enumerate(units):
+            for t, unit in enumerate(units):
                 ids = np.arange(t, shots, n_traj)
-                rep, pr, m, fm = sweep(a, letters, flip, g - g0, ids, seed, k)
+                rep, pr, m, fm = sweep(unit["tensors"], letters, flip, g - g0, ids, seed, k)
                 reported[ids], probs[ids] = rep, pr
                 res["margin"], res["flip_margin"] = min(res["margin"], m), min(res["flip_margin"], fm)
             res["reported"].append(reported)

@@ -7,8 +7,7 @@ run key lo, run key hi) under the seed: an integer, so there is no threshold and
 
 Write-out.  The contract (include/mlqem_hip.h) says a twirled program equals, per trajectory and bit for bit, the program in which
 every OPEN / CLOSE is written out as the ``U1`` records of its two letters: q0's, then q1's, identity letters left out, entries 0,
-+-1, +-i.  ``write_out`` builds that program for one (circuit, trajectory): it holds only kinds the interpreters of
-tests/mps_cases.py and tests/mps_relax_cases.py know, so they serve as they are (``mps_relax_cases.interpret`` knows all of them),
++-1, +-i.  ``write_out`` builds that program for one (circuit, trajectory): it holds only kinds that ``mps_cases.interpret`` knows, so it serves as it is,
 and the noise index is untouched (a ``U1`` is no noise record).  ``expand`` writes a folded run's schedule out as a plain program that
 still holds the twirl kinds (sizes 0 and 16), which ``run_mps`` runs and ``write_out`` writes out further.
 
@@ -248,7 +247,7 @@ def written(case_id, j, t):
 def reference(case_id, method="lapack"):
     """``[circuit][trajectory]`` of interpreter results on the written-out programs, computed once."""
     c, batch = case(case_id), lower(case_id)
-    return [[mr.interpret(written(case_id, j, t)[0], 0, method, t, c["seed"], run_key=j) for t in range(c["trajectories"])]
+    return [[mc.interpret(written(case_id, j, t)[0], 0, method, t, c["seed"], run_key=j) for t in range(c["trajectories"])]
             for j in range(len(batch))]
 
 
@@ -327,7 +326,7 @@ def channel_reference():
     oracle under the Pauli channel obtained independently: the ideal circuit's <P_i> times the diagonal of the error's transfer
     matrix (a Pauli channel after the ideal gate scales <P_i> by its transfer-matrix entry R_ii)."""
     batch = channel_batch()
-    rows = np.stack([mr.interpret(write_out(batch, 0, 0, forced=[code])[0], 0, "lapack")["terms"] for code in range(16)])
+    rows = np.stack([mc.interpret(write_out(batch, 0, 0, forced=[code])[0], 0, "lapack")["terms"] for code in range(16)])
     ideal = sc.simulate(channel_circuit(), [(label, 1.0) for label in PAIR_LABELS])[1]
     return rows, np.diag(error_transfer_matrix())[1:] * np.asarray(ideal)
 
@@ -378,7 +377,7 @@ def shots_reference(method="lapack"):
     batch = shots_case()
     mps, shots, seed, n_traj = batch.mps, SHOTS["shots"], SHOTS["seed"], SHOTS["trajectories"]
     n = int(mps.n_qubits[0])
-    units = [mr.interpret(write_out(mps, 0, t, seed, 0)[0], 0, method, t, seed, run_key=0)["tensors"] for t in range(n_traj)]
+    units = [mc.interpret(write_out(mps, 0, t, seed, 0)[0], 0, method, t, seed, run_key=0)["tensors"] for t in range(n_traj)]
     flip = batch.flip[:n]
     res = {"bits": [], "probs": [], "margin": math.inf, "flip_margin": math.inf}
     for g in range(int(batch.group_ptr[0]), int(batch.group_ptr[1])):

@@ -104,19 +104,13 @@ def test_refusals_name_the_offender():
     assert est._relaxation is True and sim.DeviceEstimator(noise, "cpu", method="mps")._relaxation is False
 
 
-# ---- the interpreter on the old kinds ---------------------------------------------------------------------------------------------------
-def test_the_interpreter_agrees_with_mps_cases_on_depolarising_batches():
-    """A model without relaxation lowers to today's batch under the keyword, and on the old kinds this module's interpreter is
-    ``mps_cases.interpret``."""
+# ---- the lowering on the old kinds ------------------------------------------------------------------------------------------------------
+def test_a_model_without_relaxation_lowers_to_the_same_batch_under_the_keyword():
     case = mc.case("noisy-overrot-T64")
     today = mc.lower(case)
     batch = compile_mps(case["circuits"], case["observables"], mc.noise_model(case["noise"], 11), case["trajectories"], case["max_bond"],
                         thermal_relaxation=True)
     assert np.array_equal(batch.ops, today.ops) and np.array_equal(batch.params, today.params) and batch.n_noise == today.n_noise
-    for j in range(len(batch)):
-        for t in (0, 5):
-            old, new = mc.interpret(batch, j, "lapack", t, case["seed"]), mr.interpret(batch, j, "lapack", t, case["seed"])
-            assert np.array_equal(old["terms"], new["terms"]) and old["error_bound"] == new["error_bound"] and old["margin"] == new["margin"]
 
 
 # ---- enumeration against the density-matrix oracle -------------------------------------------------------------------------------------
@@ -191,8 +185,8 @@ def test_forced_outcomes_against_a_dense_vector(case_id, j, method):
     """The outcomes a seeded run took, forced again: the same run; and its terms are those of a dense vector carried through the
     same operators (nothing is truncated at bond 32, so the dense vector stays normalised and equal to the state)."""
     case, batch = mr.case(case_id), mr.lower(case_id)
-    drawn = mr.interpret(batch, j, method, 3, case["seed"])
-    res = mr.interpret(batch, j, method, forced=drawn["outcomes"])
+    drawn = mc.interpret(batch, j, method, 3, case["seed"])
+    res = mc.interpret(batch, j, method, forced=drawn["outcomes"])
     assert res["outcomes"] == drawn["outcomes"] and np.array_equal(res["terms"], drawn["terms"])
     n = res["n"]
     psi = mr.dense_replay(n, res["operators"])
@@ -203,7 +197,7 @@ def test_forced_outcomes_against_a_dense_vector(case_id, j, method):
     # every alternative of the first relaxation draw that has a non-zero probability is a valid forced path too
     first = next(k for k, size in enumerate(mr._draw_sizes(batch, j)) if size == 6)
     try:
-        mr.interpret(batch, j, method, forced=drawn["outcomes"][:first])
+        mc.interpret(batch, j, method, forced=drawn["outcomes"][:first])
     except mr.NeedOutcome as need:
         assert abs(sum(need.probs) - 1.0) <= 1e-12 and len(need.probs) == 6
     else:
@@ -222,7 +216,7 @@ def test_the_certificate_bounds_the_distance_to_the_same_operators(program, bond
     circ, obs = mc.line_program(6, 40, seed=program), mc.terms_of(6, 6)
     noise = tc.model("corners")
     cut = compile_mps([circ], [obs], noise, 1, bond, thermal_relaxation=True)
-    res = mr.interpret(cut, 0, "lapack", 0, 1)
+    res = mc.interpret(cut, 0, "lapack", 0, 1)
     assert res["bond"] == bond and res["gap"] < math.inf, "the case truncates"
     big = res["error_bound"]
     psi = mr.dense_replay(6, res["operators"])
@@ -235,7 +229,7 @@ def test_the_certificate_bounds_the_distance_to_the_same_operators(program, bond
     assert abs(norm - 1.0) <= big + slack
     assert float(np.linalg.norm(psi / norm - phi)) <= 2.0 * big + slack
     full = compile_mps([circ], [obs], noise, 1, 32, thermal_relaxation=True)
-    exact = mr.interpret(full, 0, "lapack", forced=res["outcomes"])
+    exact = mc.interpret(full, 0, "lapack", forced=res["outcomes"])
     assert exact["error_bound"] <= mc.stat_floor(exact)[1] + slack, "bond 32 cuts nothing on six qubits"
     labels = [label for label, _ in obs]
     assert np.max(np.abs(mr.dense_terms(psi, labels, 6) - exact["terms"])) <= 1e-12, "the normalisers are scalars: the same ray"
@@ -311,7 +305,7 @@ def test_the_interpreters_trajectories_lie_within_five_standard_errors_of_the_or
     assert rows.shape == (mr.STAT["trajectories"], 4) and np.all(err > 1e-4), "every term has a standard error far above rounding"
     assert np.all(np.abs(mean - want) <= mr.STAT["sigmas"] * err)
     circ, obs, batch = mr.stat_case()
-    units = [mr.interpret(batch, 0, "lapack", t, mr.STAT["seed"]) for t in (0, 100, 255)]
+    units = [mc.interpret(batch, 0, "lapack", t, mr.STAT["seed"]) for t in (0, 100, 255)]
     assert min(r["margin"] for r in units) >= mr.MARGIN and any(o[0] == 11 for o in _ops(batch))
 
 

@@ -56,18 +56,6 @@ def test_lowering_groups_letters_masks_and_flip_table():
         assert math.isclose(1 - 2 * noisy.flip[q, 0], a + b) and math.isclose(-(1 - 2 * noisy.flip[q, 1]), -a + b)
 
 
-def test_the_restated_interpreter_is_the_interpreter():
-    """``mps_shots_cases.tensors`` gives the term values and statistics of ``mps_cases.interpret``, bit for bit."""
-    for case_id, traj in (("random-b3", 0), ("noisy-depol-T64", 5), ("noisy-overrot-T1", 0)):
-        c, batch = ms.case(case_id), ms.lower(case_id).mps
-        for method in ("lapack", "jacobi"):
-            for k in range(len(batch)):
-                a, stats = ms.tensors(batch, k, method, traj, c["seed"])
-                want = mc.interpret(batch, k, method, traj, c["seed"])
-                assert np.array_equal(ms.contract_terms(batch, k, a), want["terms"])
-                assert (stats["discarded"], stats["error_bound"], stats["bond"]) == (want["discarded"], want["error_bound"], want["bond"])
-
-
 # ---- the conditions of the device comparison ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("case_id", ms.IDS)
 def test_conditions_hold_and_recorded_differences_still_hold(case_id):

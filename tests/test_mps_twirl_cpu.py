@@ -210,8 +210,8 @@ def test_the_mean_over_the_codes_is_the_pauli_channel_of_the_error():
     assert np.max(np.abs(rows.mean(axis=0) - dense)) <= 1e-12
     # and untwirled the same circuit is somewhere else: the check above is no tautology
     plain = compile_mps([mt.channel_circuit()], [[(label, 1.0) for label in mt.PAIR_LABELS]], mt.model("overrot0"), 1)
-    assert np.max(np.abs(mr.interpret(plain, 0)["terms"] - dense)) > 1e-3
-    assert np.array_equal(rows[0], mr.interpret(plain, 0)["terms"]), "code 0 is the untwirled program"
+    assert np.max(np.abs(mc.interpret(plain, 0)["terms"] - dense)) > 1e-3
+    assert np.array_equal(rows[0], mc.interpret(plain, 0)["terms"]), "code 0 is the untwirled program"
 
 
 def test_the_write_out_follows_the_host_draw():
@@ -259,7 +259,7 @@ def test_every_gate_of_the_invariance_case_sees_all_sixteen_codes():
     assert not set(batch.ops[:, 0].tolist()) & {6, 7, 10, 11}, "no Pauli is drawn by the noise"
     plain = mt.lower("invariance", twirl=False)
     for j, per in enumerate(mt.reference("invariance")):   # on the host the invariance is exact up to the interpreter's rounding
-        want = mr.interpret(plain, j)["terms"]
+        want = mc.interpret(plain, j)["terms"]
         assert max(float(np.max(np.abs(r["terms"] - want))) for r in per) <= mt.tolerance("invariance")
 
 

@@ -46,6 +46,14 @@ template <int LPH> __device__ __forceinline__ float head_sum(float v) {
 }
 __device__ __forceinline__ float dot4(const f4u& a, const f4u& b) { return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x))); }
 
+// The score of an entry, in EVERY pass: the product by 1 / sqrt(C) rounded, never fused into the difference to the row's maximum that
+// follows it -- the backward passes recompute exp(score - m) / den from the forward's m and den, and with another rounding of the
+// score a row's weights do not sum to 1.
+__device__ __forceinline__ float attn_score(float dot, float scale) {
+#pragma clang fp contract(off)
+  return dot * scale;
+}
+
 // the lane's channels of a row segment that starts at p: `nv` of the four are real; `fits`: the 16 bytes lie inside the row's allocation
 __device__ __forceinline__ f4u load_channels(const float* __restrict__ p, int nv, bool fits) {
   f4u v = {0.f, 0.f, 0.f, 0.f};
@@ -175,7 +183,7 @@ template <bool TRAIN, int LPH, bool FAST = false> __device__ __forceinline__ voi
     float mys = -INFINITY;
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      const float s = head_sum<LPH>(dot4(q, kk[u])) * scale;
+      const float s = attn_score(head_sum<LPH>(dot4(q, kk[u])), scale);
       if (lu == u) mys = s;
     }
     if (lu >= k) mys = -INFINITY;

@@ -332,7 +332,7 @@ template <int LPH, bool FAST> __global__ __launch_bounds__(kBlock) void transfor
       if (lu == u) { mys = sd; mygv = gd; }
     }
     const int64_t pos = is_self ? a.E + row : (int64_t)beg + x;
-    const float alpha = expf(mys * scale - m) * inv_den * (is_self ? (float)n_self : 1.f);
+    const float alpha = expf(attn_score(mys, scale) - m) * inv_den * (is_self ? (float)n_self : 1.f);
     float dmask = 1.f;
     if (a.drop_p > 0.f) dmask = attn_dropped(seed, a.pair_key != 0, pos, H, h, row, j, a.drop_p) ? 0.f : keep;
     if (cnt <= 4) delta = quad_sum(lu < k ? alpha * dmask * mygv : 0.f);
@@ -439,7 +439,7 @@ template <int LPH, bool FAST> __global__ __launch_bounds__(kBlock) void transfor
       const float sd = head_sum<LPH>(dot4(qa[u], kown)), gd = head_sum<LPH>(dot4(ga[u], vown));
       if (lu == u) { mys = sd; mygv = gd; }
     }
-    const float alpha = expf(mys * scale - m_i) * inv_den * (is_self ? (float)n_self : 1.f);
+    const float alpha = expf(attn_score(mys, scale) - m_i) * inv_den * (is_self ? (float)n_self : 1.f);
     float dmask = 1.f;
     if (a.drop_p > 0.f) dmask = attn_dropped(seed, true, 0, H, h, i, row, a.drop_p) ? 0.f : keep;
     float gs = alpha * (mygv * dmask - delta_i) * scale, al = alpha * dmask;

@@ -8,7 +8,7 @@ from typing import Any, List, Optional, Tuple
 import numpy as np
 
 from ..data.backends import pauli_terms
-from .program import NoiseModel
+from .program import NoiseModel, upload, upload_fields
 from .template import BoundBatch, Template, compile_templates
 
 BOUND_BUFFER_BYTES = 256 << 20   # the per-run buffers of one call stay under this (``buffer_bytes=``)
@@ -72,16 +72,12 @@ def run_bound(batch: BoundBatch, theta, runs: np.ndarray, shift: np.ndarray, dev
     if int(buffer_bytes) < 1:
         raise ValueError(f"run_bound: buffer_bytes = {buffer_bytes!r}, want a positive number of bytes")
     form = ops.SIM_BOUND_TABLE if form is None else form
-
-    def up(a):
-        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
     runs = np.ascontiguousarray(runs, dtype=np.int32).reshape(-1, 4)
     shift = np.ascontiguousarray(shift, dtype=np.float64).reshape(-1)
     n_runs = int(runs.shape[0])
     width = int(np.diff(batch.term_ptr).max()) if len(batch) else 0
-    theta_d = theta.to(dev) if isinstance(theta, torch.Tensor) else up(np.asarray(theta, dtype=np.float64))
-    t = {k: up(getattr(batch, k)) for k in ("circ", "op_ptr", "ops", "params", "term_ptr", "terms", "coeff")} if n_runs else {}
+    theta_d = theta.to(dev) if isinstance(theta, torch.Tensor) else upload(np.asarray(theta, dtype=np.float64), dev)
+    t = upload_fields(batch, ("circ", "op_ptr", "ops", "params", "term_ptr", "terms", "coeff"), dev) if n_runs else {}
     values = torch.zeros(n_runs, dtype=torch.float64, device=dev)
     norm = torch.zeros(n_runs, dtype=torch.float64, device=dev)
     term_values = torch.zeros((n_runs, width), dtype=torch.float64, device=dev)
@@ -92,9 +88,9 @@ def run_bound(batch: BoundBatch, theta, runs: np.ndarray, shift: np.ndarray, dev
         hi = min(lo + step, n_runs)
         wave = is_wave[runs[lo:hi, 0]]
         ids = np.concatenate([np.flatnonzero(wave), np.flatnonzero(~wave)]).astype(np.int32)
-        ops.sim_run_bound(t["circ"], t["op_ptr"], t["ops"], t["params"], t["term_ptr"], t["terms"], t["coeff"], theta_d, up(runs[lo:hi]),
-                          up(shift[lo:hi]), up(ids), int(wave.sum()), int((~wave).sum()),
-                          up(np.arange(hi - lo + 1, dtype=np.int64) * width), (hi - lo) * width, form=form,
+        ops.sim_run_bound(t["circ"], t["op_ptr"], t["ops"], t["params"], t["term_ptr"], t["terms"], t["coeff"], theta_d,
+                          upload(runs[lo:hi], dev), upload(shift[lo:hi], dev), upload(ids, dev), int(wave.sum()), int((~wave).sum()),
+                          upload(np.arange(hi - lo + 1, dtype=np.int64) * width, dev), (hi - lo) * width, form=form,
                           term_values=term_values[lo:hi].reshape(-1), values=values[lo:hi], norm=norm[lo:hi])
     return values, term_values, norm
 
@@ -180,10 +176,6 @@ def parameter_shift(template, observable, parameter_values, noise: Optional[Nois
     width = max([0] + [t.num_parameters for t in tpls])
     values = torch.zeros(n_rows, dtype=torch.float64, device=dev)
     grads = torch.zeros((n_rows, width), dtype=torch.float64, device=dev)
-
-    def up(a):
-        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
     for c, rows, at, k in groups:
         b, p = int(rows.size), int(batch.num_parameters[c])
         ob = int(batch.occ_ptr[c])
@@ -191,11 +183,11 @@ def parameter_shift(template, observable, parameter_values, noise: Optional[Nois
         order = np.argsort(par, kind="stable").astype(np.int32)   # a parameter's occurrences, in circuit order
         occ_ptr = np.concatenate([[0], np.cumsum(np.bincount(par, minlength=p))]).astype(np.int64)
         v = all_values[at:at + b * (1 + 2 * k)]
-        g = ops.sim_shift_combine(v[b:b + k * b].reshape(k, b), v[b + k * b:].reshape(k, b), up(occ_ptr), up(order),
-                                  up(batch.occ_scale[ob:ob + k]))
+        g = ops.sim_shift_combine(v[b:b + k * b].reshape(k, b), v[b + k * b:].reshape(k, b), upload(occ_ptr, dev), upload(order, dev),
+                                  upload(batch.occ_scale[ob:ob + k], dev))
         if len(groups) == 1 and p == width and np.array_equal(rows, np.arange(n_rows)):
             return v[:b], g
-        idx = up(rows)
+        idx = upload(rows, dev)
         values[idx] = v[:b]
         grads[idx, :p] = g
     return values, grads

@@ -20,7 +20,8 @@ import numpy as np
 
 from ..data.backends import pauli_terms
 from ..data.circuit import Circuit
-from .program import (OP_CX, OP_CZ, OP_DIAG1, OP_SWAP, SUPPORTED_GATES, _N_PARAMS, _TWO_QUBIT, _one_qubit, _two_qubit)
+from .program import (OP_CX, OP_CZ, OP_DIAG1, OP_SWAP, SUPPORTED_GATES, _N_PARAMS, _TWO_QUBIT, _one_qubit, _two_qubit, upload,
+                      upload_fields)
 
 MAX_QUBITS_CLIFFORD = 512   # MLQEM_CLIFFORD_MAX_QUBITS
 REG_QUBITS = 128            # MLQEM_CLIFFORD_REG_QUBITS: units of circuits up to here keep their words in registers
@@ -180,13 +181,8 @@ class CliffordBatch:
 
     def to(self, device) -> Dict[str, Any]:
         """The arrays as tensors on ``device``, keyed as ``ops.clifford_run`` names them (uint32 words travel as int32)."""
-        import torch
-
-        dev = torch.device(device)
-        out = {k: torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(dev)
-               for k in ("n_qubits", "op_ptr", "pool", "units", "term_ptr", "coeff", "comb_ptr", "comb_unit", "comb_weight")}
-        out["ops"] = torch.from_numpy(np.ascontiguousarray(self.ops).view(np.int32)).to(dev)
-        out["masks"] = torch.from_numpy(np.ascontiguousarray(self.masks).view(np.int32)).to(dev)
+        out = upload_fields(self, ("n_qubits", "op_ptr", "pool", "units", "term_ptr", "coeff", "comb_ptr", "comb_unit", "comb_weight", "ops",
+                                   "masks"), device, view={"ops": np.int32, "masks": np.int32})
         out["n_reg"], out["n_lds"] = self.n_reg, self.n_lds
         return out
 
@@ -414,10 +410,8 @@ def clifford_expectation_values(circuits: Sequence[Any], observables: Sequence[A
     """Exact expectation values of ``observables[k]`` after the Clifford circuit ``circuits[k]``, at any width up to 512 qubits:
     ``(values, term_values, term_ptr)`` in the form of :func:`~blackwater.sim.expectation_values`, noisy under ``noise`` when it is
     given and ideal otherwise.  ``return_ideal=True`` appends ``(ideal_values, ideal_term_values)`` from the same call."""
-    import torch
-
     batch = compile_clifford(circuits, observables, noise)
     ideal_values, noisy_values, ideal_terms, noisy_terms, _, _ = run_clifford(batch, device)
-    term_ptr = torch.from_numpy(batch.term_ptr).to(ideal_values.device)
+    term_ptr = upload(batch.term_ptr, ideal_values.device)
     head = (ideal_values, ideal_terms, term_ptr) if noise is None else (noisy_values, noisy_terms, term_ptr)
     return head + (ideal_values, ideal_terms) if return_ideal else head

@@ -19,7 +19,7 @@ import numpy as np
 from ..data.backends import pauli_terms
 from ..data.circuit import Circuit
 from .clifford import _LETTER, PAD, REG_QUBITS, CliffordBatch, _words, compile_clifford
-from .program import MAX_SHOTS, check_seed, check_shots, measurement_groups
+from .program import MAX_SHOTS, _run_keys, check_seed, check_shots, measurement_groups, upload, upload_fields
 
 MAX_GROUPS = 4096            # MLQEM_CLIFFORD_MAX_GROUPS: measurement groups per circuit (12 bits of a counter word)
 DEPOL_BITS, READOUT_BITS = 60, 32
@@ -76,17 +76,10 @@ class FrameBatch:
     def to(self, device) -> Dict[str, Any]:
         """The arrays as tensors on ``device``, keyed as ``ops.clifford_sample`` names them (uint32 words travel as int32, the
         uint64 thresholds as int64: they are below 2^61)."""
-        import torch
-
-        dev = torch.device(device)
-        out = {k: torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(dev)
-               for k in ("ro_ptr", "group_ptr", "group_circ", "group_mask", "ids", "term_ptr", "coeff", "term_mask", "gterm_ptr", "gterm",
-                         "row_ptr", "ref_ptr")}
-        for k in ("n_qubits", "op_ptr"):
-            out[k] = torch.from_numpy(np.ascontiguousarray(getattr(self.clifford, k))).to(dev)
-        out["ops"] = torch.from_numpy(np.ascontiguousarray(self.clifford.ops).view(np.int32)).to(dev)
-        out["masks"] = torch.from_numpy(np.ascontiguousarray(self.masks).view(np.int32)).to(dev)
-        out["thresh"] = torch.from_numpy(np.ascontiguousarray(self.thresh).view(np.int64)).to(dev)
+        out = upload_fields(self, ("ro_ptr", "group_ptr", "group_circ", "group_mask", "ids", "term_ptr", "coeff", "term_mask", "gterm_ptr",
+                                   "gterm", "row_ptr", "ref_ptr"), device)
+        out.update(upload_fields(self.clifford, ("n_qubits", "op_ptr", "ops"), device, view={"ops": np.int32}))
+        out.update(upload_fields(self, ("masks", "thresh"), device, view={"masks": np.int32, "thresh": np.int64}))
         return out
 
 
@@ -203,25 +196,14 @@ class FrameResult:
     batch: Optional[FrameBatch] = None
 
 
-def _frame_run_keys(run_keys, n_runs: int, who: str) -> np.ndarray:
-    if run_keys is None:
-        return np.arange(n_runs, dtype=np.int64)
-    keys = np.asarray(run_keys)
-    if keys.shape != (n_runs,) or keys.dtype.kind not in "iu":
-        raise ValueError(f"{who}: run_keys must be {n_runs} integers (one per circuit), got shape {keys.shape} dtype {keys.dtype}")
-    return keys.astype(np.int64)
-
-
 def run_clifford_frames(batch: FrameBatch, shots: int, seed: int = 0, run_keys=None, return_bits: bool = False,
                         device="cuda") -> FrameResult:
     """Samples ``shots`` outcomes of every (circuit, group) of a lowered batch: one call, nothing read back.  ``run_keys``: one
     integer per circuit, by default its position in the batch; pass a circuit's batch key to draw the same shots for it alone."""
-    import torch
-
     from ..native import ops
 
     shots, seed = check_shots(shots, "run_clifford_frames"), check_seed(seed, "run_clifford_frames")
-    keys = torch.from_numpy(_frame_run_keys(run_keys, len(batch), "run_clifford_frames")).to(device)
+    keys = upload(_run_keys(run_keys, len(batch), "run_clifford_frames", per="circuit"), device)
     t = batch.to(device)
     values, variance, term_values, term_sums, reference, bits = ops.clifford_sample(
         t["n_qubits"], t["op_ptr"], t["ops"], t["thresh"], t["ro_ptr"], t["group_ptr"], t["group_circ"], t["group_mask"], t["ids"],

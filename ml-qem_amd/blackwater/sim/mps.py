@@ -28,7 +28,8 @@ import numpy as np
 
 from ..data.circuit import Circuit
 from .program import (_N_PARAMS, _TWO_QUBIT, OP_DIAG1, PARAM_PAD, SUPPORTED_GATES, NoiseModel, _check_coherent, _check_relaxation,
-                      _lower_terms, _one_qubit, _two_qubit, check_seed, check_trajectories, measurement_groups)
+                      _lower_terms, _one_qubit, _run_keys, _two_qubit, check_seed, check_trajectories, measurement_groups, upload,
+                      upload_fields)
 
 MAX_BOND = 32            # MLQEM_MPS_MAX_BOND: theta, (2 chi) x (2 chi) complex128 = 64 KiB, sits in LDS beside a second workgroup
 MAX_QUBITS_MPS = 512     # MLQEM_MPS_MAX_QUBITS
@@ -115,12 +116,8 @@ class MpsBatch:
         return int(self.n_qubits.shape[0])
 
     def to(self, device) -> Dict[str, Any]:
-        import torch
-
-        dev = torch.device(device)
-        return {k: torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(dev)
-                for k in ("n_qubits", "op_ptr", "ops", "params", "term_ptr", "term_circ", "term_off", "letters", "coeff", "site_ptr",
-                          "readout")}
+        return upload_fields(self, ("n_qubits", "op_ptr", "ops", "params", "term_ptr", "term_circ", "term_off", "letters", "coeff", "site_ptr",
+                                    "readout"), device)
 
 
 def is_line_circuit(circuit: Any) -> bool:
@@ -691,12 +688,6 @@ class MpsResult:
     batch: Optional[MpsBatch] = None
 
 
-def _upload(array, dev):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(array)).to(dev)
-
-
 def _mps_chunks(widths, max_bond: int, trajectories: int, buffer_bytes: int, unit_bytes=None):
     """``(unit range, trajectory range)`` pairs over the circuits (or runs) of the widths ``widths`` whose site-tensor workspace
     (n * chi * 2 * chi * 16 B per unit, plus the stash) stays under ``buffer_bytes``: whole circuits with all their trajectories
@@ -763,7 +754,6 @@ def run_mps(batch: MpsBatch, seed: int = 0, run_keys=None, device="cuda", keep_t
     import torch
 
     from ..native import ops
-    from .run import _run_keys
 
     seed = check_seed(seed, "run_mps")
     n_traj = 1 if batch.trajectories is None else check_trajectories(batch.trajectories, "run_mps")
@@ -777,7 +767,7 @@ def run_mps(batch: MpsBatch, seed: int = 0, run_keys=None, device="cuda", keep_t
                  for k in ("values", "term_values", "norm", "discarded", "error_bound", "std_error", "term_std_error")}
         empty["bond"] = torch.zeros(0, dtype=torch.int32, device=dev)
         return _mps_result(empty, t["term_ptr"], batch, seed, None, None, False, noisy)
-    keys_t = _upload(keys, dev)
+    keys_t = upload(keys, dev)
     traj_terms = torch.zeros((n_traj, n_terms), dtype=torch.float64, device=dev)
     traj_norm = torch.zeros((n_traj, b), dtype=torch.float64, device=dev)
     traj_stats = torch.zeros((n_traj, b, ops.MPS_STATS), dtype=torch.float64, device=dev)
@@ -817,8 +807,6 @@ class MpsBoundRun:
         import torch
 
         from ..native import ops
-        from .run import _run_keys
-
         who = "run_mps_bound"
         self.batch, self.seed = batch, check_seed(seed, who)
         refuse_relaxation_records(batch, who)
@@ -878,14 +866,14 @@ class MpsBoundRun:
                 chunks.append((range(lo, hi), tr))
                 lo = hi
         self.chunks = chunks
-        self.tpl = {k: _upload(getattr(batch, k), dev) for k in ("op_ptr", "ops", "params", "pool_ptr", "fac_ptr", "fac", "fac_val", "fpool",
-                                                                 "occ_ptr", "occ", "letters", "readout")}
-        self.theta = theta.to(dev).contiguous() if is_tensor else _upload(theta, dev)
-        self.runs, self.shift, self.keys = _upload(runs, dev), _upload(shift, dev), _upload(keys, dev)
-        self.widths = _upload(widths.astype(np.int32), dev)
-        self.term_off, self.coeff = _upload(batch.term_off[term_src], dev), _upload(batch.coeff[term_src], dev)
-        self.site_ptr = _upload(np.concatenate([batch.site_ptr[tpl], batch.site_ptr[-1:]]).astype(np.int64), dev)
-        self.term_ptr = _upload(self.run_term_ptr, dev)
+        self.tpl = upload_fields(batch, ("op_ptr", "ops", "params", "pool_ptr", "fac_ptr", "fac", "fac_val", "fpool", "occ_ptr", "occ", "letters",
+                                         "readout"), dev)
+        self.theta = theta.to(dev).contiguous() if is_tensor else upload(theta, dev)
+        self.runs, self.shift, self.keys = upload(runs, dev), upload(shift, dev), upload(keys, dev)
+        self.widths = upload(widths.astype(np.int32), dev)
+        self.term_off, self.coeff = upload(batch.term_off[term_src], dev), upload(batch.coeff[term_src], dev)
+        self.site_ptr = upload(np.concatenate([batch.site_ptr[tpl], batch.site_ptr[-1:]]).astype(np.int64), dev)
+        self.term_ptr = upload(self.run_term_ptr, dev)
         # per chunk, relative to its first run: op_ptr [n + 1], out_pool_ptr [n + 1] and the run of each of its terms
         rel_op, rel_pool, rel_term, self.where = [], [], [], []
         for cr, _ in chunks:
@@ -893,7 +881,7 @@ class MpsBoundRun:
             rel_op.append(run_op[cr.start:cr.stop + 1] - run_op[cr.start])
             rel_pool.append(run_pool[cr.start:cr.stop + 1] - run_pool[cr.start])
             rel_term.append(self.term_run[self.run_term_ptr[cr.start]:self.run_term_ptr[cr.stop]] - cr.start)
-        cat = lambda parts, dtype: _upload(np.concatenate(parts).astype(dtype) if parts else np.zeros(0, dtype=dtype), dev)   # noqa: E731
+        cat = lambda parts, dtype: upload(np.concatenate(parts).astype(dtype) if parts else np.zeros(0, dtype=dtype), dev)   # noqa: E731
         self.rel_op, self.rel_pool, self.rel_term = cat(rel_op, np.int64), cat(rel_pool, np.int64), cat(rel_term, np.int32)
         self.sizes = [(int(run_op[cr.stop] - run_op[cr.start]), int(run_pool[cr.stop] - run_pool[cr.start]),
                        int(self.run_term_ptr[cr.stop] - self.run_term_ptr[cr.start]), int(rec_n[cr.start:cr.stop].max()),
@@ -1015,7 +1003,6 @@ def mps_parameter_shift(template, observable, rows, noise: Optional[NoiseModel] 
     import torch
 
     from ..native import ops
-    from .run import _run_keys
 
     batch, pair, theta, n_rows = _mps_pairs(template, observable, rows, noise, trajectories, max_bond, cutoff, "parameter_shift")
     runs, shift, groups = mps_shift_runs(batch, pair)
@@ -1033,9 +1020,9 @@ def mps_parameter_shift(template, observable, rows, noise: Optional[NoiseModel] 
         order = np.argsort(par, kind="stable").astype(np.int32)   # a parameter's occurrences, in circuit order
         occ_ptr = np.concatenate([[0], np.cumsum(np.bincount(par, minlength=p))]).astype(np.int64)
         v = all_values[at:at + b * (1 + 2 * k)]
-        g = ops.sim_shift_combine(v[b:b + k * b].reshape(k, b), v[b + k * b:].reshape(k, b), _upload(occ_ptr, dev), _upload(order, dev),
-                                  _upload(batch.occ_scale[ob:ob + k], dev))
-        idx = _upload(rws, dev)
+        g = ops.sim_shift_combine(v[b:b + k * b].reshape(k, b), v[b + k * b:].reshape(k, b), upload(occ_ptr, dev), upload(order, dev),
+                                  upload(batch.occ_scale[ob:ob + k], dev))
+        idx = upload(rws, dev)
         values[idx] = v[:b]
         grads[idx, :p] = g
     return values, grads
@@ -1108,13 +1095,9 @@ class MpsShotsBatch:
         return self.mps.trajectories
 
     def to(self, device) -> Dict[str, Any]:
-        import torch
-
-        dev = torch.device(device)
-        out = self.mps.to(dev)
-        for k in ("group_ptr", "group_circ", "group_off", "basis", "flip", "ref_ptr", "gterm_ptr", "gterm", "term_mask"):
-            out[k] = torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(dev)
-        out["masks"] = torch.from_numpy(np.ascontiguousarray(self.masks).view(np.int32)).to(dev)
+        out = self.mps.to(device)
+        out.update(upload_fields(self, ("group_ptr", "group_circ", "group_off", "basis", "flip", "ref_ptr", "gterm_ptr", "gterm", "term_mask",
+                                        "masks"), device, view={"masks": np.int32}))
         return out
 
 
@@ -1215,7 +1198,6 @@ def run_mps_shots(batch: MpsShotsBatch, shots: int, seed: int = 0, run_keys=None
 
     from ..native import ops
     from .program import check_shots
-    from .run import _run_keys
 
     shots, seed = check_shots(shots, "run_mps_shots"), check_seed(seed, "run_mps_shots")
     mps = batch.mps
@@ -1233,7 +1215,7 @@ def run_mps_shots(batch: MpsShotsBatch, shots: int, seed: int = 0, run_keys=None
         return MpsShotsResult(zeros(0), zeros(0), zeros(0), t["term_ptr"], zeros(0, torch.int32), t["ref_ptr"], t["group_ptr"], zeros(0),
                               zeros(0), zeros(0, torch.int32), zeros(0, torch.int32) if return_bits else None, shots, seed,
                               mps.trajectories, batch)
-    keys_t = _upload(keys, dev)
+    keys_t = upload(keys, dev)
     traj_stats = zeros((n_traj, b, ops.MPS_STATS))
     term_sums = zeros(n_terms, torch.int32)
     bits = zeros(int(batch.ref_ptr[-1]) * shots, torch.int32) if return_bits else None

@@ -344,15 +344,10 @@ class SimBatch:
 
     def to(self, device) -> Dict[str, Any]:
         """The arrays as tensors on ``device``, keyed as ``ops.sim_run`` names them."""
-        import torch
-
-        dev = torch.device(device)
-        out = {k: torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(dev)
-               for k in ("circ", "op_ptr", "ops", "params", "term_ptr", "terms", "coeff", "ids")}
+        out = upload_fields(self, ("circ", "op_ptr", "ops", "params", "term_ptr", "terms", "coeff", "ids"), device)
         out["n_wave"], out["n_wg"] = self.n_wave, self.n_wg
         if self.group_ptr is not None:
-            for k in ("group_ptr", "term_group", "prob_ptr", "group_circ"):
-                out[k] = torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(dev)
+            out.update(upload_fields(self, ("group_ptr", "term_group", "prob_ptr", "group_circ"), device))
         return out
 
     def sample_units(self, n_factors: int = 1):
@@ -416,6 +411,38 @@ def check_seed(seed: Any, who: str) -> int:
     if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
         raise ValueError(f"{who}: seed = {seed!r}, want an int (it is reduced mod 2^64)")
     return int(seed) % 2 ** 64
+
+
+def default_run_keys(n_runs: int, offset: int = 0) -> np.ndarray:
+    """int64 [n_runs]: ``offset + r`` for run r = f * B + c, the counter words a run draws with unless the caller passes its own."""
+    return np.arange(int(n_runs), dtype=np.int64) + np.int64(offset)
+
+
+def _run_keys(run_keys, n_runs: int, who: str, per: str = "run") -> np.ndarray:
+    """``run_keys`` as int64 [n_runs] (None: :func:`default_run_keys`), or a ``ValueError`` that names ``who``."""
+    if run_keys is None:
+        return default_run_keys(n_runs)
+    keys = np.asarray(run_keys)
+    if keys.shape != (n_runs,) or keys.dtype.kind not in "iu":
+        raise ValueError(f"{who}: run_keys must be {n_runs} integers (one per {per}), got shape {keys.shape} dtype {keys.dtype}")
+    return keys.astype(np.int64)
+
+
+def upload(array, dev):
+    """A host array as a tensor on ``dev``: the one host-to-device copy of the package."""
+    import torch
+
+    return torch.from_numpy(np.ascontiguousarray(array)).to(dev)
+
+
+def upload_fields(obj: Any, names: Sequence[str], dev, view: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+    """``{name: upload(obj.name)}``; ``view`` names the dtype an array travels as (uint32 words as int32, uint64 as int64)."""
+    import torch
+
+    dev = torch.device(dev)
+    if not view:
+        return {k: upload(getattr(obj, k), dev) for k in names}
+    return {k: upload(np.ascontiguousarray(getattr(obj, k)).view(view[k]) if k in view else getattr(obj, k), dev) for k in names}
 
 
 def measurement_groups(term_rows: Sequence[Tuple[int, int, int, int]]):

@@ -3,6 +3,7 @@
 (``mlqem_sim_run_trajectories_f64``), and an Estimator-shaped primitive on all three."""
 from __future__ import annotations
 
+import functools
 from dataclasses import dataclass
 from typing import Any, Dict, List, Optional, Sequence
 
@@ -12,8 +13,8 @@ from ..library.primitives import make_estimator_result
 from ..data.circuit import Circuit
 from .clifford import clifford_expectation_values, is_clifford, refuse_non_pauli
 from .frames import sample_clifford_expectation_values
-from .program import (MAX_QUBITS_DENSITY, MAX_QUBITS_VECTOR, NoiseModel, SimBatch, check_seed, check_shots, check_trajectories,
-                      compile_programs)
+from .program import (MAX_QUBITS_DENSITY, MAX_QUBITS_VECTOR, NoiseModel, SimBatch, _run_keys, check_seed, check_shots, check_trajectories,
+                      compile_programs, default_run_keys, upload)
 from .bound import bound_expectation_values
 from .mps import (DEFAULT_CUTOFF, MAX_BOND, _check_bond, _check_cutoff, _check_twirl, bound_mps_expectation_values, mps_expectation_values,
                   sample_mps_expectation_values)
@@ -35,11 +36,9 @@ def expectation_values(circuits: Sequence[Any], observables: Sequence[Any], nois
     float64 [n_terms] and int64 [B + 1] tensors on ``device`` (``term_values[term_ptr[k] : term_ptr[k + 1]]`` are the Pauli terms
     of circuit k, without their coefficients).  ``noise=None`` simulates state vectors, a :class:`NoiseModel` density matrices;
     everything is lowered and validated on the host first (:func:`compile_programs`), then simulated in at most two launches."""
-    import torch
-
     batch = compile_programs(circuits, observables, noise)
     values, term_values, _ = run_batch(batch, device)
-    return values, term_values, torch.from_numpy(batch.term_ptr).to(values.device)
+    return values, term_values, upload(batch.term_ptr, values.device)
 
 
 @dataclass
@@ -64,31 +63,15 @@ class SampleResult:
     batch: Optional[SimBatch] = None
 
 
-def default_run_keys(n_runs: int, offset: int = 0) -> np.ndarray:
-    """int64 [n_runs]: ``offset + r`` for run r = f * B + c, the counter words a run draws with unless the caller passes its own."""
-    return np.arange(int(n_runs), dtype=np.int64) + np.int64(offset)
-
-
-def _run_keys(run_keys, n_runs: int, who: str) -> np.ndarray:
-    if run_keys is None:
-        return default_run_keys(n_runs)
-    keys = np.asarray(run_keys)
-    if keys.shape != (n_runs,) or keys.dtype.kind not in "iu":
-        raise ValueError(f"{who}: run_keys must be {n_runs} integers (one per run), got shape {keys.shape} dtype {keys.dtype}")
-    return keys.astype(np.int64)
-
-
 def sample_batch(batch: SimBatch, seed: int = 0, run_keys=None, device="cuda") -> SampleResult:
     """Simulates a batch lowered with ``shots`` and samples it: two calls (at most five launches), nothing read back."""
-    import torch
-
     from ..native import ops
 
     batch.refuse_trajectories("sample_batch")
     if batch.group_ptr is None:
         raise ValueError("sample_batch: the batch was lowered without shots (compile_programs(..., shots=))")
     seed = check_seed(seed, "sample_batch")
-    keys = torch.from_numpy(_run_keys(run_keys, len(batch), "sample_batch")).to(device)
+    keys = upload(_run_keys(run_keys, len(batch), "sample_batch"), device)
     t = batch.to(device)
     units, n_wave, n_wg = batch.sample_units(1)
     n_outcomes = int(batch.prob_ptr[-1])
@@ -97,7 +80,7 @@ def sample_batch(batch: SimBatch, seed: int = 0, run_keys=None, device="cuda") -
         t["ids"], t["n_wave"], t["n_wg"])
     s_values, variance, s_terms, counts = ops.sim_sample(
         t["circ"], t["term_ptr"], t["terms"], t["coeff"], t["group_ptr"], t["term_group"], t["prob_ptr"], t["group_circ"], probs, keys,
-        batch.shots, seed, torch.from_numpy(units).to(keys.device), n_wave, n_wg)
+        batch.shots, seed, upload(units, keys.device), n_wave, n_wg)
     return SampleResult(s_values, variance, s_terms, t["term_ptr"], counts, t["prob_ptr"], t["group_ptr"], probs, batch.shots, seed,
                         values, term_values, norm, batch)
 
@@ -172,11 +155,7 @@ def run_trajectories(batch: SimBatch, seed: int = 0, run_keys=None, device="cuda
     if int(buffer_bytes) < 1:
         raise ValueError(f"run_trajectories: buffer_bytes = {buffer_bytes!r}, want a positive number of bytes")
     dev = torch.device(device)
-
-    def up(a):
-        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-    params, term_ptr = up(batch.params), up(batch.term_ptr)
+    params, term_ptr = upload(batch.params, dev), upload(batch.term_ptr, dev)
     out = {k: [] for k in ("values", "std_error", "term_values", "term_std_error", "norm", "traj")}
     for chunk in _trajectory_chunks(batch, n_traj, buffer_bytes):
         lo, hi = chunk.start, chunk.stop
@@ -184,9 +163,9 @@ def run_trajectories(batch: SimBatch, seed: int = 0, run_keys=None, device="cuda
         wave = [k - lo for k in chunk if batch.variant[k] == "wave"]
         wg = [k - lo for k in chunk if batch.variant[k] != "wave"]
         values, std_error, term_values, term_std_error, norm, traj, _ = ops.sim_run_trajectories(
-            up(batch.circ[lo:hi]), up(batch.op_ptr[lo:hi + 1] - ob), up(batch.ops[ob:oe]), params, up(batch.term_ptr[lo:hi + 1] - tb),
-            up(batch.terms[tb:te]), up(batch.coeff[tb:te]), up(np.asarray(wave + wg, dtype=np.int32)), len(wave), len(wg),
-            up(keys[lo:hi]), n_traj, seed)
+            upload(batch.circ[lo:hi], dev), upload(batch.op_ptr[lo:hi + 1] - ob, dev), upload(batch.ops[ob:oe], dev), params,
+            upload(batch.term_ptr[lo:hi + 1] - tb, dev), upload(batch.terms[tb:te], dev), upload(batch.coeff[tb:te], dev),
+            upload(np.asarray(wave + wg, dtype=np.int32), dev), len(wave), len(wg), upload(keys[lo:hi], dev), n_traj, seed)
         for k, v in zip(out, (values, std_error, term_values, term_std_error, norm, traj if keep_trajectories else None)):
             out[k].append(v)
 
@@ -237,6 +216,10 @@ _TRAJECTORY_SHOTS = ("DeviceEstimator(method='trajectories'): shots= is not supp
                      "out of scope; the estimate's own standard error is in the metadata); run it without shots")
 
 
+_TRAJECTORY_NOISE = ("DeviceEstimator(method='trajectories'): noise=None; trajectories unravel a noise model (the noiseless values are "
+                     "method='exact')")
+
+
 _FRAMES_SHOTS = ("DeviceEstimator(method='frames'): shots=None; frame sampling draws measurement shots (pass shots=N; the exact "
                  "values of Clifford circuits are method='clifford')")
 
@@ -247,6 +230,10 @@ _MPS_SHOTS = ("DeviceEstimator(method='mps'): shots= is not supported with it (n
 
 _MPS_SHOTS_NONE = ("DeviceEstimator(method='mps_shots'): shots=None; it draws measurement shots from a matrix-product state (pass "
                    "shots=N; the values without shot noise are method='mps')")
+
+
+_CLIFFORD_SHOTS = ("DeviceEstimator: shots are not drawn on the Clifford path (method='clifford', or 'auto' on circuits over the exact "
+                   "simulator's cap); run it without shots")
 
 
 class SimulatedJob:
@@ -269,6 +256,131 @@ class SimulatedJob:
 
     def cancel(self) -> bool:
         return False
+
+
+def _shot_rows(variance, shots: int) -> List[dict]:
+    """The metadata of a sampled job: every circuit's per-shot variance and the shot count."""
+    return [{"variance": float(v), "shots": shots} for v in variance.cpu().numpy()]
+
+
+def _mps_rows(res, trajectories: Optional[int], rows: Optional[List[dict]] = None, std_error: bool = True) -> List[dict]:
+    """The metadata of a matrix-product-state job, added to ``rows`` (None: empty ones): every circuit's certificate and largest bond
+    and, under noise (``trajectories`` is then set), its standard error (``std_error=False``: the sampled path reports none) and the
+    trajectory count."""
+    bound, bond = res.error_bound.cpu().numpy(), res.bond.cpu().numpy()
+    rows = [{} for _ in bond] if rows is None else rows
+    for m, b, k in zip(rows, bound, bond):
+        m.update(truncation_error_bound=float(b), max_bond=int(k))
+    if trajectories is not None:
+        if std_error:
+            for m, e in zip(rows, res.std_error.cpu().numpy()):
+                m["std_error"] = float(e)
+        for m in rows:
+            m["trajectories"] = trajectories
+    return rows
+
+
+# ---- the runners of the method table: (estimator, circuits, observables, shots, seed, keys) -> (values on the device, metadata rows or None)
+def _exact(est, circuits, observables, shots, seed, keys):
+    if shots is None:
+        return expectation_values(circuits, observables, est._noise, est._device)[0], None
+    res = sample_expectation_values(circuits, observables, est._noise, shots=shots, seed=seed, run_keys=keys, device=est._device)
+    return res.values, _shot_rows(res.variance, shots)
+
+
+def _clifford(est, circuits, observables, shots, seed, keys):
+    return clifford_expectation_values(circuits, observables, est._noise, est._device)[0], None
+
+
+def _frames(est, circuits, observables, shots, seed, keys):
+    res = sample_clifford_expectation_values(circuits, observables, est._noise, shots=shots, seed=seed, run_keys=keys, device=est._device)
+    return res.values, _shot_rows(res.variance, shots)
+
+
+def _trajectories(est, circuits, observables, shots, seed, keys):
+    res = trajectory_expectation_values(circuits, observables, est._noise, trajectories=est._trajectories, seed=seed, run_keys=keys,
+                                        device=est._device)
+    return res.values, [{"std_error": float(e), "trajectories": est._trajectories} for e in res.std_error.cpu().numpy()]
+
+
+def _mps_trajectories(est) -> Optional[int]:
+    return None if est._noise is None else est._trajectories
+
+
+def _mps(est, circuits, observables, shots, seed, keys):
+    res = mps_expectation_values(circuits, observables, est._noise, max_bond=est._max_bond, cutoff=est._cutoff,
+                                 trajectories=_mps_trajectories(est), seed=seed, run_keys=keys, device=est._device,
+                                 thermal_relaxation=est._relaxation, pauli_twirl=est._twirl)
+    return res.values, _mps_rows(res, _mps_trajectories(est))
+
+
+def _mps_shots(est, circuits, observables, shots, seed, keys):
+    res = sample_mps_expectation_values(circuits, observables, est._noise, shots=shots, max_bond=est._max_bond, cutoff=est._cutoff,
+                                        trajectories=_mps_trajectories(est), seed=seed, run_keys=keys, device=est._device,
+                                        thermal_relaxation=est._relaxation, pauli_twirl=est._twirl)
+    return res.values, _mps_rows(res, _mps_trajectories(est), _shot_rows(res.variance, shots), std_error=False)
+
+
+def _bound_exact(est, circuits, observables, shots, seed, keys, parameter_values):
+    return bound_expectation_values(list(circuits), list(observables), list(parameter_values), est._noise, est._device)[0], None
+
+
+def _bound_mps(est, circuits, observables, shots, seed, keys, parameter_values):
+    values, _, res = bound_mps_expectation_values(list(circuits), list(observables), list(parameter_values), est._noise, _mps_trajectories(est),
+                                                  est._max_bond, est._cutoff, seed, keys, est._device, return_result=True)
+    return values, _mps_rows(res, _mps_trajectories(est))
+
+
+@dataclass(frozen=True)
+class _Method:
+    """One row of the method table: what ``DeviceEstimator(method=...)`` checks, at construction and per job, and what it runs."""
+
+    run: Any                               # the runner of a job of bound circuits
+    shots: str = "optional"                # "optional", "required" or "refused" ...
+    shots_message: Optional[str] = None    # ... with this text
+    draws: bool = False                    # draws without shots too: the seed is checked for every job
+    noise_message: Optional[str] = None    # ``noise=None`` is refused with this text (None: noise is optional)
+    pauli_noise_only: bool = False         # a model that is no Pauli channel is refused at construction
+    per_job: bool = False                  # ``use_clifford_path`` sends a job to the Clifford path (``_CLIFFORD_PATH``) or leaves it here
+    bound: Any = None                      # the runner of a job of templates (a runner with ``parameter_values``); None: refused
+    wide_options: bool = False             # ``thermal_relaxation`` and ``pauli_twirl`` apply
+
+    def check_shots_rule(self, shots) -> None:
+        if (self.shots == "required" and shots is None) or (self.shots == "refused" and shots is not None):
+            raise ValueError(self.shots_message)
+
+
+_CLIFFORD_PATH = _Method(_clifford, "refused", _CLIFFORD_SHOTS)   # not chosen at construction, so its shots rule holds per job alone
+_METHODS = {
+    "exact": _Method(_exact, bound=_bound_exact),
+    "clifford": _Method(_clifford, per_job=True),
+    "auto": _Method(_exact, per_job=True, bound=_bound_exact),
+    "trajectories": _Method(_trajectories, "refused", _TRAJECTORY_SHOTS, draws=True, noise_message=_TRAJECTORY_NOISE),
+    "frames": _Method(_frames, "required", _FRAMES_SHOTS, pauli_noise_only=True),
+    "mps": _Method(_mps, "refused", _MPS_SHOTS, draws=True, bound=_bound_mps, wide_options=True),
+    "mps_shots": _Method(_mps_shots, "required", _MPS_SHOTS_NONE, wide_options=True),
+}
+
+
+def use_clifford_path(method: str, noise: Optional[NoiseModel], circuits) -> bool:
+    """Whether a job under ``method`` ("clifford" or "auto") takes the Clifford path: always under ``"clifford"``; under ``"auto"``
+    when a circuit is over the exact simulator's cap and every circuit is a Clifford circuit (a ``ValueError`` names one that fits
+    neither path).  A noise model the Clifford path cannot carry is refused by name."""
+    if method == "clifford":
+        refuse_non_pauli(noise, "DeviceEstimator(method='clifford')")
+        return True
+    cap = MAX_QUBITS_VECTOR if noise is None else MAX_QUBITS_DENSITY
+    parsed = [Circuit.from_any(c) for c in circuits]
+    over = [k for k, c in enumerate(parsed) if c.num_qubits > cap]
+    if not over:
+        return False
+    why = (f"DeviceEstimator(method='auto'): circuit {over[0]} has {parsed[over[0]].num_qubits} qubits, over the exact simulator's cap of "
+           f"{cap} in this mode, so the job needs the Clifford path")
+    refuse_non_pauli(noise, why)
+    for k in over + [k for k in range(len(parsed)) if k not in over]:   # name a circuit that fits neither path first
+        if not is_clifford(parsed[k]):
+            raise ValueError(f"{why}, and circuit {k} is not a Clifford circuit")
+    return True
 
 
 class DeviceEstimator:
@@ -331,33 +443,27 @@ class DeviceEstimator:
         methods = self.METHODS + self.SAMPLED_METHODS + self.WIDE_METHODS + self.WIDE_SAMPLED_METHODS
         if method not in methods:
             raise ValueError(f"DeviceEstimator: method = {method!r}, want one of {', '.join(methods)}")
-        self._method = method
+        self._method, entry = method, _METHODS[method]
         self._max_bond, self._cutoff = _check_bond(max_bond, "DeviceEstimator"), _check_cutoff(cutoff, "DeviceEstimator")
         if not isinstance(thermal_relaxation, bool):
             raise ValueError(f"DeviceEstimator: thermal_relaxation = {thermal_relaxation!r}, want True or False")
-        if thermal_relaxation and method not in self.WIDE_METHODS + self.WIDE_SAMPLED_METHODS:
+        if thermal_relaxation and not entry.wide_options:
             raise ValueError(f"DeviceEstimator(method={method!r}): thermal_relaxation=True belongs to method='mps' and 'mps_shots' (the "
                              "exact and trajectory paths take a model with thermal relaxation as it is)")
         self._relaxation = thermal_relaxation
         self._twirl = _check_twirl(pauli_twirl, "DeviceEstimator") or None
-        if self._twirl and method not in self.WIDE_METHODS + self.WIDE_SAMPLED_METHODS:
+        if self._twirl and not entry.wide_options:
             raise ValueError(f"DeviceEstimator(method={method!r}): pauli_twirl= belongs to method='mps' and 'mps_shots' (the twirl is "
                              "drawn per trajectory on the matrix-product-state path)")
-        if method == "mps" and shots is not None:
-            raise ValueError(_MPS_SHOTS)
-        if method == "mps_shots" and shots is None:
-            raise ValueError(_MPS_SHOTS_NONE)
-        if method == "frames":
-            if shots is None:
-                raise ValueError(_FRAMES_SHOTS)
-            refuse_non_pauli(noise, "DeviceEstimator(method='frames')")
+        if entry.noise_message is None:   # the order of these checks is the one a call with two faults has always met
+            entry.check_shots_rule(shots)
+            if entry.pauli_noise_only:
+                refuse_non_pauli(noise, f"DeviceEstimator(method={method!r})")
         self._trajectories = check_trajectories(trajectories, "DeviceEstimator")
-        if method == "trajectories":
+        if entry.noise_message is not None:
             if noise is None:
-                raise ValueError("DeviceEstimator(method='trajectories'): noise=None; trajectories unravel a noise model (the "
-                                 "noiseless values are method='exact')")
-            if shots is not None:
-                raise ValueError(_TRAJECTORY_SHOTS)
+                raise ValueError(entry.noise_message)
+            entry.check_shots_rule(shots)
         self._noise, self._device, self._count = noise, device, 0
         self._shots = None if shots is None else check_shots(shots, "DeviceEstimator")
         self._seed = check_seed(seed, "DeviceEstimator")
@@ -375,78 +481,26 @@ class DeviceEstimator:
                 raise ValueError(f"DeviceEstimator: circuit {k} comes with {len(p)} parameter values; circuits must arrive bound")
         shots = run_options.pop("shots", self._shots)
         seed = run_options.pop("seed", self._seed)
+        entry = _METHODS[self._method]
         if any(free):
-            return self._run_templates(circuits, observables, parameter_values, free.index(True), shots, seed)
-        if self._method == "frames":
-            if shots is None:
-                raise ValueError(_FRAMES_SHOTS)
-            shots, seed = check_shots(shots, "DeviceEstimator.run"), check_seed(seed, "DeviceEstimator.run")
-            self._count += 1
-            res = sample_clifford_expectation_values(circuits, observables, self._noise, shots=shots, seed=seed,
-                                                     run_keys=default_run_keys(len(circuits), self._count << 32), device=self._device)
-            variance = res.variance.cpu().numpy()
-            return SimulatedJob(res.values.cpu().numpy(), f"sim-{self._count}", [{"variance": float(v), "shots": shots} for v in variance])
-        if self._method == "mps_shots":
-            if shots is None:
-                raise ValueError(_MPS_SHOTS_NONE)
-            shots, seed = check_shots(shots, "DeviceEstimator.run"), check_seed(seed, "DeviceEstimator.run")
-            self._count += 1
-            noisy = self._noise is not None
-            res = sample_mps_expectation_values(circuits, observables, self._noise, shots=shots, max_bond=self._max_bond,
-                                                cutoff=self._cutoff, trajectories=self._trajectories if noisy else None, seed=seed,
-                                                run_keys=default_run_keys(len(circuits), self._count << 32), device=self._device,
-                                                thermal_relaxation=self._relaxation, pauli_twirl=self._twirl)
-            metadata = [{"variance": float(v), "shots": shots, "truncation_error_bound": float(b), "max_bond": int(k)}
-                        for v, b, k in zip(res.variance.cpu().numpy(), res.error_bound.cpu().numpy(), res.bond.cpu().numpy())]
-            if noisy:
-                for m in metadata:
-                    m.update(trajectories=self._trajectories)
-            return SimulatedJob(res.values.cpu().numpy(), f"sim-{self._count}", metadata)
-        if self._method == "mps":
-            if shots is not None:
-                raise ValueError(_MPS_SHOTS)
-            self._count += 1
-            noisy = self._noise is not None
-            res = mps_expectation_values(circuits, observables, self._noise, max_bond=self._max_bond, cutoff=self._cutoff,
-                                         trajectories=self._trajectories if noisy else None, seed=check_seed(seed, "DeviceEstimator.run"),
-                                         run_keys=default_run_keys(len(circuits), self._count << 32), device=self._device,
-                                         thermal_relaxation=self._relaxation, pauli_twirl=self._twirl)
-            metadata = [{"truncation_error_bound": float(b), "max_bond": int(k)}
-                        for b, k in zip(res.error_bound.cpu().numpy(), res.bond.cpu().numpy())]
-            if noisy:
-                for m, e in zip(metadata, res.std_error.cpu().numpy()):
-                    m.update(std_error=float(e), trajectories=self._trajectories)
-            return SimulatedJob(res.values.cpu().numpy(), f"sim-{self._count}", metadata)
-        if self._method == "trajectories":
-            if shots is not None:
-                raise ValueError(_TRAJECTORY_SHOTS)
-            self._count += 1
-            res = trajectory_expectation_values(circuits, observables, self._noise, trajectories=self._trajectories,
-                                                seed=check_seed(seed, "DeviceEstimator.run"),
-                                                run_keys=default_run_keys(len(circuits), self._count << 32), device=self._device)
-            std_error = res.std_error.cpu().numpy()
-            return SimulatedJob(res.values.cpu().numpy(), f"sim-{self._count}",
-                                [{"std_error": float(e), "trajectories": self._trajectories} for e in std_error])
-        if self._method != "exact" and self._use_clifford(circuits):
-            if shots is not None:
-                raise ValueError("DeviceEstimator: shots are not drawn on the Clifford path (method='clifford', or 'auto' on circuits "
-                                 "over the exact simulator's cap); run it without shots")
-            self._count += 1
-            values = clifford_expectation_values(circuits, observables, self._noise, self._device)[0]
-            return SimulatedJob(values.cpu().numpy(), f"sim-{self._count}")
-        self._count += 1
-        if shots is None:
-            values, _, _ = expectation_values(circuits, observables, self._noise, self._device)
-            return SimulatedJob(values.cpu().numpy(), f"sim-{self._count}")
-        shots, seed = check_shots(shots, "DeviceEstimator.run"), check_seed(seed, "DeviceEstimator.run")
-        res = sample_expectation_values(circuits, observables, self._noise, shots=shots, seed=seed,
-                                        run_keys=default_run_keys(len(circuits), self._count << 32), device=self._device)
-        variance = res.variance.cpu().numpy()
-        return SimulatedJob(res.values.cpu().numpy(), f"sim-{self._count}",
-                            [{"variance": float(v), "shots": shots} for v in variance])
+            run = self._template_runner(entry, circuits, parameter_values, free.index(True), shots)
+        else:
+            if entry.per_job and self._use_clifford(circuits):
+                entry = _CLIFFORD_PATH
+            entry.check_shots_rule(shots)
+            run = entry.run
+        if shots is not None:
+            shots = check_shots(shots, "DeviceEstimator.run")
+        draws = entry.draws or shots is not None
+        if draws:
+            seed = check_seed(seed, "DeviceEstimator.run")
+        self._count += 1   # the call is accepted: job j = 1, 2, ... draws with the run keys j * 2^32 + k (a job that draws nothing has none)
+        keys = default_run_keys(len(circuits), self._count << 32) if draws else None
+        values, metadata = run(self, circuits, observables, shots, seed, keys)
+        return SimulatedJob(values.cpu().numpy(), f"sim-{self._count}", metadata)
 
-    def _run_templates(self, circuits, observables, parameter_values, first: int, shots, seed=0):
-        """A job with templates (or qiskit-like circuits with free parameters): the bound path, one lowering per distinct
+    def _template_runner(self, entry: _Method, circuits, parameter_values, first: int, shots):
+        """The runner of a job with templates (or qiskit-like circuits with free parameters): the bound path, one lowering per distinct
         (template, observable) pair and one run per row -- on the exact simulator, or under ``method="mps"`` on matrix-product
         states (:func:`bound_mps_expectation_values`).  Everything else is refused by name."""
         how = ("bind it first (Template.bind_parameters(values)) and pass the bound circuit, which takes that path as ever; "
@@ -455,57 +509,27 @@ class DeviceEstimator:
         if shots is not None:
             raise ValueError(f"DeviceEstimator: circuit {first} is a template with free parameters and shots= is set: shots are not "
                              f"drawn on the bound path; {how}")
-        if self._method in ("trajectories", "clifford", "frames", "mps_shots"):
+        if entry.bound is None:
             raise ValueError(f"DeviceEstimator(method={self._method!r}): circuit {first} is a template with free parameters; {how}")
         templates = [Template.from_any(c) for c in circuits]
         for k, (t, p) in enumerate(zip(templates, parameter_values)):
             if len(p) != t.num_parameters:
                 raise ValueError(f"DeviceEstimator: circuit {k} comes with {len(p)} parameter values, the template has "
                                  f"{t.num_parameters} parameters")
-        if self._method == "mps":
-            if self._relaxation:
-                raise ValueError(f"DeviceEstimator(method='mps', thermal_relaxation=True): circuit {first} is a template with free "
-                                 "parameters; thermal relaxation on templates is not built (bind the circuit first)")
-            if self._twirl:
-                raise ValueError(f"DeviceEstimator(method='mps', pauli_twirl=): circuit {first} is a template with free parameters; "
-                                 "twirled templates are not built (mlqem_mps_bind_f64 does not know the twirl records: bind the "
-                                 "circuit first)")
-            self._count += 1
-            noisy = self._noise is not None
-            values, _, res = bound_mps_expectation_values(
-                list(circuits), list(observables), list(parameter_values), self._noise, self._trajectories if noisy else None,
-                self._max_bond, self._cutoff, check_seed(seed, "DeviceEstimator.run"), default_run_keys(len(circuits), self._count << 32),
-                self._device, return_result=True)
-            metadata = [{"truncation_error_bound": float(b), "max_bond": int(k)}
-                        for b, k in zip(res.error_bound.cpu().numpy(), res.bond.cpu().numpy())]
-            if noisy:
-                for m, e in zip(metadata, res.std_error.cpu().numpy()):
-                    m.update(std_error=float(e), trajectories=self._trajectories)
-            return SimulatedJob(values.cpu().numpy(), f"sim-{self._count}", metadata)
+        if self._relaxation:
+            raise ValueError(f"DeviceEstimator(method='mps', thermal_relaxation=True): circuit {first} is a template with free "
+                             "parameters; thermal relaxation on templates is not built (bind the circuit first)")
+        if self._twirl:
+            raise ValueError(f"DeviceEstimator(method='mps', pauli_twirl=): circuit {first} is a template with free parameters; "
+                             "twirled templates are not built (mlqem_mps_bind_f64 does not know the twirl records: bind the "
+                             "circuit first)")
         if self._method == "auto":
             cap = MAX_QUBITS_VECTOR if self._noise is None else MAX_QUBITS_DENSITY
             for k, t in enumerate(templates):
                 if t.num_qubits > cap:
                     raise ValueError(f"DeviceEstimator(method='auto'): circuit {k} is a template of {t.num_qubits} qubits, over the "
                                      f"exact simulator's cap of {cap} in this mode; {how}")
-        self._count += 1
-        values, _ = bound_expectation_values(list(circuits), list(observables), list(parameter_values), self._noise, self._device)
-        return SimulatedJob(values.cpu().numpy(), f"sim-{self._count}")
+        return functools.partial(entry.bound, parameter_values=parameter_values)
 
     def _use_clifford(self, circuits) -> bool:
-        if self._method == "clifford":
-            refuse_non_pauli(self._noise, "DeviceEstimator(method='clifford')")
-            return True
-        cap = MAX_QUBITS_VECTOR if self._noise is None else MAX_QUBITS_DENSITY
-        parsed = [Circuit.from_any(c) for c in circuits]
-        over = [k for k, c in enumerate(parsed) if c.num_qubits > cap]
-        if not over:
-            return False
-        refuse_non_pauli(self._noise, f"DeviceEstimator(method='auto'): circuit {over[0]} has {parsed[over[0]].num_qubits} qubits, over the "
-                                      f"exact simulator's cap of {cap} in this mode, so the job needs the Clifford path")
-        for k in over + [k for k in range(len(parsed)) if k not in over]:   # name a circuit that fits neither path first
-            if not is_clifford(parsed[k]):
-                raise ValueError(f"DeviceEstimator(method='auto'): circuit {over[0]} has {parsed[over[0]].num_qubits} qubits, over the "
-                                 f"exact simulator's cap of {cap} in this mode, so the job needs the Clifford path, and circuit {k} "
-                                 "is not a Clifford circuit")
-        return True
+        return use_clifford_path(self._method, self._noise, circuits)

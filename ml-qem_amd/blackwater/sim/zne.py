@@ -60,7 +60,10 @@ import numpy as np
 from ..data.circuit import Circuit, CircuitOp
 from ..library.primitives import make_estimator_result
 from .clifford import CliffordBatch, compile_clifford, refuse_non_pauli
-from .program import _TWO_QUBIT, SUPPORTED_GATES, NoiseModel, SimBatch, check_seed, check_shots, compile_programs
+from .program import (_TWO_QUBIT, SUPPORTED_GATES, NoiseModel, SimBatch, _run_keys, check_seed, check_shots, check_trajectories, compile_programs,
+                      upload, upload_fields)
+from .run import _CLIFFORD_SHOTS, DeviceEstimator, use_clifford_path
+from .template import has_free_parameters
 
 _NOT_GATES = ("barrier", "measure")
 
@@ -273,10 +276,7 @@ class Schedules:
     achieved: np.ndarray      # float64 [F, B]: 1 + 2 m / N per run
 
     def to(self, device):
-        import torch
-
-        dev = torch.device(device)
-        return {k: torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(dev) for k in ("sched_ptr", "sched", "ids")}
+        return upload_fields(self, ("sched_ptr", "sched", "ids"), device)
 
 
 def _name_table(amplifier: _Amplifier) -> np.ndarray:
@@ -612,20 +612,26 @@ class ZNERun:
     traj_stats: Any = None            # float64 [T, F * B, 6] with it: MpsResult.traj_stats per run
 
 
-_CLIFFORD_SHOTS = ("DeviceEstimator: shots are not drawn on the Clifford path (method='clifford', or 'auto' on circuits over the exact "
-                   "simulator's cap); run it without shots")
-
-
 def _combine(strategy: "ZNEStrategy", weights: np.ndarray, term_values, term_ptr, coeff):
     """``(mitigated_values, mitigated_terms, fallback or None)`` by the strategy's extrapolator, in one launch."""
+    from ..native import ops
+
+    w = upload(weights, term_values.device)
+    if getattr(strategy.extrapolator, "exponential", False):
+        return ops.zne_combine_exp(term_values, w, term_ptr, coeff)
+    return ops.zne_combine(term_values, w, term_ptr, coeff) + (None,)
+
+
+def _combine_squared(weights: np.ndarray, per_factor):
+    """``sum_f w_f^2 x_f`` per circuit for ``per_factor`` [F, B] (variances of independently sampled factors, squared standard
+    errors): the same combine with the squared weights on one unit-coefficient "term" per circuit."""
     import torch
 
     from ..native import ops
 
-    w = torch.from_numpy(weights).to(term_values.device)
-    if getattr(strategy.extrapolator, "exponential", False):
-        return ops.zne_combine_exp(term_values, w, term_ptr, coeff)
-    return ops.zne_combine(term_values, w, term_ptr, coeff) + (None,)
+    b, dev = int(per_factor.shape[1]), per_factor.device
+    return ops.zne_combine(per_factor, upload(weights * weights, dev), torch.arange(b + 1, dtype=torch.int64, device=dev),
+                           torch.ones(b, dtype=torch.float64, device=dev))[1]
 
 
 def tile_mps_runs(batch: Any, n_factors: int) -> dict:
@@ -655,9 +661,7 @@ def run_mps_folded(batch: Any, schedules: Schedules, seed: int = 0, run_keys=Non
     import torch
 
     from ..native import ops
-    from .mps import _mps_plan, _mps_result, _upload, refuse_relaxation_records
-    from .program import check_trajectories
-    from .run import _run_keys
+    from .mps import _mps_plan, _mps_result, refuse_relaxation_records
 
     refuse_relaxation_records(batch, "run_mps_folded")
     if batch.trajectories is None:
@@ -674,8 +678,8 @@ def run_mps_folded(batch: Any, schedules: Schedules, seed: int = 0, run_keys=Non
     tiled = tile_mps_runs(batch, n_f)
     chunks, workspace, _ = _mps_plan(tiled["run_qubits"], batch.max_bond, n_traj, buffer_bytes, "run_mps_folded", dev)
     t, s = batch.to(dev), schedules.to(dev)
-    r = {k: _upload(v, dev) for k, v in tiled.items()}
-    keys_t = _upload(keys, dev)
+    r = {k: upload(v, dev) for k, v in tiled.items()}
+    keys_t = upload(keys, dev)
     traj_terms = torch.zeros((n_traj, n_f * n_terms), dtype=torch.float64, device=dev)
     traj_norm = torch.zeros((n_traj, n_runs), dtype=torch.float64, device=dev)
     traj_stats = torch.zeros((n_traj, n_runs, ops.MPS_STATS), dtype=torch.float64, device=dev)
@@ -691,11 +695,7 @@ def run_mps_folded(batch: Any, schedules: Schedules, seed: int = 0, run_keys=Non
 
 def _zne_run_mps(circuits, observables, noise, strategy, weights, device, shots, seed, run_keys, trajectories, max_bond, cutoff,
                  buffer_bytes, keep_trajectories, pauli_twirl=None) -> ZNERun:
-    import torch
-
-    from ..native import ops
     from .mps import DEFAULT_CUTOFF, MAX_BOND, compile_mps
-    from .program import check_trajectories
 
     if shots is not None:
         raise ValueError("zne_run(method='mps'): shots= is not supported with it (no shots are drawn from folded matrix-product-state "
@@ -710,17 +710,13 @@ def _zne_run_mps(circuits, observables, noise, strategy, weights, device, shots,
     sch = build_mps_schedules(batch, strategy.noise_factors, strategy.noise_amplifier)
     n_f, b, n_terms = len(sch.noise_factors), len(batch), int(batch.term_circ.shape[0])
     res = run_mps_folded(batch, sch, seed, run_keys, device, keep_trajectories, buffer_bytes)
-    dev = res.values.device
-    term_ptr, coeff = (torch.from_numpy(np.ascontiguousarray(v)).to(dev) for v in (batch.term_ptr, batch.coeff))
+    term_ptr, coeff = upload(batch.term_ptr, res.values.device), upload(batch.coeff, res.values.device)
     term_values = res.term_values.reshape(n_f, n_terms)
     mitigated_values, mitigated_terms, fallback = _combine(strategy, weights, term_values, term_ptr, coeff)
     std_error = res.std_error.reshape(n_f, b)
-    mitigated_std_error = None
+    mitigated_std_error = None   # sqrt(sum_f w_f^2 se_f^2), for the polynomial extrapolators
     if not getattr(strategy.extrapolator, "exponential", False):
-        # sqrt(sum_f w_f^2 se_f^2): the combine on the squared errors, squared weights, one unit-coefficient "term" per circuit
-        _, var = ops.zne_combine((std_error * std_error).contiguous(), torch.from_numpy(weights * weights).to(dev),
-                                 torch.arange(b + 1, dtype=torch.int64, device=dev), torch.ones(b, dtype=torch.float64, device=dev))
-        mitigated_std_error = torch.sqrt(var)
+        mitigated_std_error = _combine_squared(weights, (std_error * std_error).contiguous()).sqrt()
     return ZNERun(mitigated_values, mitigated_terms, term_ptr, res.values.reshape(n_f, b), term_values, res.norm.reshape(n_f, b), batch,
                   sch, weights, fallback_terms=fallback, std_error=std_error, term_std_error=res.term_std_error.reshape(n_f, n_terms),
                   mitigated_std_error=mitigated_std_error, error_bound=res.error_bound.reshape(n_f, b),
@@ -746,10 +742,7 @@ def zne_run(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional
     model with thermal relaxation is refused by name (folded runs do not take the ``thermal_relaxation=True`` of ``compile_mps``).
     ``pauli_twirl`` (``method="mps"`` alone) is ``compile_mps``'s: every pass of a folded gate draws its own twirl on the device, which
     turns a coherent gate error into the Pauli channel the extrapolators assume."""
-    import torch
-
     from ..native import ops
-    from .run import DeviceEstimator
 
     strategy = strategy or ZNEStrategy()
     weights = strategy.weights()
@@ -772,50 +765,43 @@ def zne_run(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional
                          f"not to method = {method!r}")
     if method not in DeviceEstimator.METHODS:
         raise ValueError(f"zne_run: method = {method!r}, want one of {', '.join(DeviceEstimator.METHODS + ('mps',))}")
-    if method != "exact" and DeviceEstimator(noise, device, method=method)._use_clifford(circuits):
+    clifford = method != "exact" and use_clifford_path(method, noise, circuits)
+    if clifford:
         if shots is not None:
             raise ValueError(_CLIFFORD_SHOTS)
         batch = compile_clifford(circuits, observables, noise)
         sch = build_clifford_schedules(batch, strategy.noise_factors, strategy.noise_amplifier, noise)
-        t, s = batch.to(device), sch.to(device)
-        ideal_values, noisy_values, ideal_terms, noisy_terms, _, _ = ops.clifford_run_folded(
-            t["n_qubits"], t["op_ptr"], t["ops"], t["pool"], t["units"], t["n_reg"], t["n_lds"], t["masks"], t["term_ptr"], t["coeff"],
-            t["comb_ptr"], t["comb_unit"], t["comb_weight"], s["sched_ptr"], s["sched"], len(sch.noise_factors))
-        values, term_values = (ideal_values, ideal_terms) if noise is None else (noisy_values, noisy_terms)
-        mitigated_values, mitigated_terms, fallback = _combine(strategy, weights, term_values, t["term_ptr"], t["coeff"])
-        return ZNERun(mitigated_values, mitigated_terms, t["term_ptr"], values, term_values, None, batch, sch, weights,
-                      ideal_values=ideal_values[0], ideal_terms=ideal_terms[0], fallback_terms=fallback)
-    if shots is not None:
-        from .run import _run_keys
-
-        shots, seed = check_shots(shots, "zne_run"), check_seed(seed, "zne_run")
+    else:
+        if shots is not None:
+            shots, seed = check_shots(shots, "zne_run"), check_seed(seed, "zne_run")
         batch = compile_programs(circuits, observables, noise, shots=shots)
         sch = build_schedules(batch, circuits, strategy.noise_factors, strategy.noise_amplifier)
-        t, s = batch.to(device), sch.to(device)
-        n_f, n_circ = len(sch.noise_factors), len(batch)
-        keys = torch.from_numpy(_run_keys(run_keys, n_f * n_circ, "zne_run")).to(device)
+    t, s = batch.to(device), sch.to(device)
+    n_f, extra = len(sch.noise_factors), {}
+    if clifford:
+        ideal_values, noisy_values, ideal_terms, noisy_terms, _, _ = ops.clifford_run_folded(
+            t["n_qubits"], t["op_ptr"], t["ops"], t["pool"], t["units"], t["n_reg"], t["n_lds"], t["masks"], t["term_ptr"], t["coeff"],
+            t["comb_ptr"], t["comb_unit"], t["comb_weight"], s["sched_ptr"], s["sched"], n_f)
+        values, term_values = (ideal_values, ideal_terms) if noise is None else (noisy_values, noisy_terms)
+        norm, extra = None, dict(ideal_values=ideal_values[0], ideal_terms=ideal_terms[0])
+    elif shots is not None:
+        keys = upload(_run_keys(run_keys, n_f * len(batch), "zne_run"), device)
         units, u_wave, u_wg = batch.sample_units(n_f)
         exact, _, norm, probs = ops.sim_run_folded_measured(
             t["circ"], t["op_ptr"], t["ops"], t["params"], t["term_ptr"], t["terms"], t["coeff"], t["group_ptr"], t["prob_ptr"],
             int(batch.prob_ptr[-1]), s["sched_ptr"], s["sched"], s["ids"], sch.n_wave, sch.n_wg, n_f)
         values, variance, term_values, counts = ops.sim_sample(
             t["circ"], t["term_ptr"], t["terms"], t["coeff"], t["group_ptr"], t["term_group"], t["prob_ptr"], t["group_circ"], probs,
-            keys, shots, seed, torch.from_numpy(units).to(keys.device), u_wave, u_wg)
-        w = torch.from_numpy(weights).to(values.device)
-        mitigated_values, mitigated_terms = ops.zne_combine(term_values, w, t["term_ptr"], t["coeff"])
-        # sum_f w_f^2 variance_f: the same combine, squared weights, one unit-coefficient "term" per circuit
-        _, mitigated_variance = ops.zne_combine(variance, torch.from_numpy(weights * weights).to(values.device), torch.arange(n_circ + 1, dtype=torch.int64, device=values.device),
-                                                torch.ones(n_circ, dtype=torch.float64, device=values.device))
-        return ZNERun(mitigated_values, mitigated_terms, t["term_ptr"], values, term_values, norm, batch, sch, weights, shots=shots,
-                      variance=variance, mitigated_variance=mitigated_variance, counts=counts, probs=probs, exact_values=exact)
-    batch = compile_programs(circuits, observables, noise)
-    sch = build_schedules(batch, circuits, strategy.noise_factors, strategy.noise_amplifier)
-    t, s = batch.to(device), sch.to(device)
-    values, term_values, norm = ops.sim_run_folded(t["circ"], t["op_ptr"], t["ops"], t["params"], t["term_ptr"], t["terms"], t["coeff"],
-                                                   s["sched_ptr"], s["sched"], s["ids"], sch.n_wave, sch.n_wg, len(sch.noise_factors))
+            keys, shots, seed, upload(units, keys.device), u_wave, u_wg)
+        extra = dict(shots=shots, variance=variance, counts=counts, probs=probs, exact_values=exact)
+    else:
+        values, term_values, norm = ops.sim_run_folded(t["circ"], t["op_ptr"], t["ops"], t["params"], t["term_ptr"], t["terms"], t["coeff"],
+                                                       s["sched_ptr"], s["sched"], s["ids"], sch.n_wave, sch.n_wg, n_f)
     mitigated_values, mitigated_terms, fallback = _combine(strategy, weights, term_values, t["term_ptr"], t["coeff"])
-    return ZNERun(mitigated_values, mitigated_terms, t["term_ptr"], values, term_values, norm, batch, sch, weights,
-                  fallback_terms=fallback)
+    if shots is not None:   # the factors are sampled independently
+        extra["mitigated_variance"] = _combine_squared(weights, variance)
+    return ZNERun(mitigated_values, mitigated_terms, t["term_ptr"], values, term_values, norm, batch, sch, weights, fallback_terms=fallback,
+                  **extra)
 
 
 def zne_expectation_values(circuits: Sequence[Any], observables: Sequence[Any], noise: Optional[NoiseModel] = None,
@@ -837,37 +823,51 @@ def _zne_metadata(strategy: ZNEStrategy, achieved: np.ndarray, per_factor: np.nd
             "extrapolator": repr(strategy.extrapolator)}
 
 
-class ZNEJob:
-    """The job of a ``zne(cls)`` run.  The fused path has its values when it is built; the generic path combines the F * B values of
-    the wrapped estimator's job when ``result()`` is asked for."""
+def _fused_rows(strategy: ZNEStrategy, run: ZNERun, n: int) -> List[Tuple[dict, dict]]:
+    """Per circuit, what a fused run puts into ``metadata[k]`` and into ``metadata[k]["zne"]`` (``zne(cls)`` has the keys)."""
+    values = run.values.cpu().numpy()
+    rows = [({}, _zne_metadata(strategy, run.schedules.achieved, values, k)) for k in range(n)]
+    if run.fallback_terms is not None:   # with ExponentialExtrapolator: the terms that fell back
+        ptr, flags = run.term_ptr.cpu().numpy(), run.fallback_terms.cpu().numpy()
+        for k, (_, z) in enumerate(rows):
+            z["fallback_terms"] = int(flags[ptr[k]:ptr[k + 1]].sum())
+    if run.trajectories is not None:   # the MPS path
+        se, bound = run.std_error.cpu().numpy(), run.error_bound.cpu().numpy()
+        mse = None if run.mitigated_std_error is None else run.mitigated_std_error.cpu().numpy()
+        for k, (m, z) in enumerate(rows):
+            m["trajectories"] = run.trajectories
+            if mse is not None:   # polynomial: |mitigated - exact ZNE| <= 2 * truncation_error_bound * sum|coeff|
+                m.update(std_error=float(mse[k]), truncation_error_bound=float(np.abs(run.weights) @ bound[:, k]))
+            z.update(std_errors=tuple(float(v) for v in se[:, k]), truncation_error_bounds=tuple(float(v) for v in bound[:, k]))
+    if run.shots is not None:   # the error bar of the mitigated value
+        variance, per_factor = run.mitigated_variance.cpu().numpy(), run.variance.cpu().numpy()
+        for k, (m, z) in enumerate(rows):
+            var = float(variance[k])
+            m.update(variance=var, shots=int(run.shots), std_error=math.sqrt(max(var, 0.0) / run.shots))
+            z["variances"] = tuple(float(v) for v in per_factor[:, k])
+    return rows
 
-    def __init__(self, strategy: ZNEStrategy, achieved: np.ndarray, n_circuits: int, job_id: str, values=None, per_factor=None,
-                 base_job=None, shots=None, variance=None, per_factor_variance=None, fallback=None, metadata=None, zne_metadata=None):
+
+class ZNEJob:
+    """The job of a ``zne(cls)`` run.  The fused path has its values and its metadata ``rows`` (per circuit: a dict merged into
+    ``metadata[k]`` and the finished ``metadata[k]["zne"]``) when it is built; the generic path combines the F * B values of the
+    wrapped estimator's job when ``result()`` is asked for."""
+
+    def __init__(self, strategy: ZNEStrategy, achieved: np.ndarray, n_circuits: int, job_id: str, values=None, rows=None, base_job=None):
         self._strategy, self._achieved, self._n, self._job_id = strategy, achieved, n_circuits, job_id
-        self._values, self._per_factor, self._base_job = values, per_factor, base_job
-        self._shots, self._variance, self._per_factor_variance = shots, variance, per_factor_variance
-        self._fallback = fallback   # with ExponentialExtrapolator on a fused path: per circuit, the terms that fell back
-        # the MPS path: per circuit, what goes into metadata[k] and into metadata[k]["zne"]
-        self._metadata, self._zne_metadata = metadata, zne_metadata
+        self._values, self._rows, self._base_job = values, rows, base_job
 
     def result(self):
         meta = [{} for _ in range(self._n)]
         if self._values is None:
             base = self._base_job.result()
-            self._per_factor = np.asarray(base.values, dtype=np.float64).reshape(len(self._strategy.noise_factors), self._n)
-            self._values = np.asarray(self._strategy.extrapolator.extrapolate(self._strategy.noise_factors, self._per_factor))
+            per_factor = np.asarray(base.values, dtype=np.float64).reshape(len(self._strategy.noise_factors), self._n)
+            self._values = np.asarray(self._strategy.extrapolator.extrapolate(self._strategy.noise_factors, per_factor))
+            self._rows = [({}, _zne_metadata(self._strategy, self._achieved, per_factor, k)) for k in range(self._n)]
             meta = [dict(m) for m in list(base.metadata)[:self._n]] if len(base.metadata) >= self._n else meta
-        for k in range(self._n):
-            meta[k]["zne"] = _zne_metadata(self._strategy, self._achieved, self._per_factor, k)
-            if self._fallback is not None:
-                meta[k]["zne"]["fallback_terms"] = int(self._fallback[k])
-            if self._metadata is not None:
-                meta[k].update(self._metadata[k])
-                meta[k]["zne"].update(self._zne_metadata[k])
-            if self._shots is not None:   # the fused path with shots: the error bar of the mitigated value
-                var = float(self._variance[k])
-                meta[k].update(variance=var, shots=int(self._shots), std_error=math.sqrt(max(var, 0.0) / self._shots))
-                meta[k]["zne"]["variances"] = tuple(float(v) for v in self._per_factor_variance[:, k])
+        for m, (row, zne_row) in zip(meta, self._rows):
+            m["zne"] = dict(zne_row)
+            m.update(row)
         return make_estimator_result(np.asarray(self._values, dtype=np.float64), meta)
 
     def job_id(self) -> str:
@@ -901,8 +901,6 @@ def zne(cls):
     counts the circuit's terms that fell back to the straight line.  Around any other
     estimator class it folds the IR (:func:`fold_circuit`), submits the F * B circuits through the wrapped ``_run`` in one job and
     combines with the same weights on the host; circuits must arrive bound there."""
-    from .run import DeviceEstimator
-
     fused = isinstance(cls, type) and issubclass(cls, DeviceEstimator)
 
     def __init__(self, *args, zne_strategy: Optional[ZNEStrategy] = None, **kwargs):
@@ -913,10 +911,7 @@ def zne(cls):
     def _run(self, circuits, observables, parameter_values, **run_options):
         strategy = run_options.pop("zne_strategy", None) or self._zne_strategy
         circuits, observables, parameter_values = list(circuits), list(observables), list(parameter_values)
-        self._zne_count += 1
         if fused:
-            from .template import has_free_parameters
-
             for k, c in enumerate(circuits):
                 if has_free_parameters(c):
                     raise ValueError(f"{type(self).__name__}: circuit {k} is a template with free parameters, which zne(DeviceEstimator) "
@@ -925,45 +920,20 @@ def zne(cls):
                 if len(p):
                     raise ValueError(f"{type(self).__name__}: circuit {k} comes with {len(p)} parameter values; circuits must arrive bound")
             shots, seed = run_options.pop("shots", self._shots), run_options.pop("seed", self._seed)
-            if self._method == "mps":   # job j's run r draws with the key j * 2^32 + r, as on the shots path
-                n_f, n = len(strategy.noise_factors), len(circuits)
-                keys = np.arange(n_f * n, dtype=np.int64) + (np.int64(self._zne_count) << 32)
-                run = zne_run(circuits, observables, self._noise, strategy, self._device, shots=shots, seed=seed, run_keys=keys,
-                              method="mps", trajectories=None if self._noise is None else self._trajectories, max_bond=self._max_bond,
-                              cutoff=self._cutoff, pauli_twirl=getattr(self, "_twirl", None))
-                se, bound = run.std_error.cpu().numpy(), run.error_bound.cpu().numpy()
-                polynomial = run.mitigated_std_error is not None
-                mse = run.mitigated_std_error.cpu().numpy() if polynomial else None
-                metadata, zne_metadata = [], []
-                for k in range(n):
-                    m = {"trajectories": run.trajectories}
-                    if polynomial:   # |mitigated - exact ZNE| <= 2 * truncation_error_bound * sum|coeff|
-                        m.update(std_error=float(mse[k]), truncation_error_bound=float(np.abs(run.weights) @ bound[:, k]))
-                    metadata.append(m)
-                    zne_metadata.append({"std_errors": tuple(float(v) for v in se[:, k]),
-                                         "truncation_error_bounds": tuple(float(v) for v in bound[:, k])})
-                fallback = None
-                if run.fallback_terms is not None:
-                    ptr, flags = run.term_ptr.cpu().numpy(), run.fallback_terms.cpu().numpy()
-                    fallback = [int(flags[ptr[k]:ptr[k + 1]].sum()) for k in range(n)]
-                return ZNEJob(strategy, run.schedules.achieved, n, f"zne-sim-{self._zne_count}", values=run.mitigated_values.cpu().numpy(),
-                              per_factor=run.values.cpu().numpy(), fallback=fallback, metadata=metadata, zne_metadata=zne_metadata)
-            if shots is not None and self._method != "exact" and self._use_clifford(circuits):
+            mps = {}
+            if self._method == "mps":
+                mps = dict(trajectories=None if self._noise is None else self._trajectories, max_bond=self._max_bond, cutoff=self._cutoff,
+                           pauli_twirl=self._twirl)
+            elif shots is not None and self._method != "exact" and self._use_clifford(circuits):
                 raise ValueError(_CLIFFORD_SHOTS)
-            if shots is not None:   # job j's run r draws with the key j * 2^32 + r: successive runs do not repeat their draws
-                keys = np.arange(len(strategy.noise_factors) * len(circuits), dtype=np.int64) + (np.int64(self._zne_count) << 32)
-                run = zne_run(circuits, observables, self._noise, strategy, self._device, shots=shots, seed=seed, run_keys=keys,
-                              method=self._method)
-                return ZNEJob(strategy, run.schedules.achieved, len(circuits), f"zne-sim-{self._zne_count}",
-                              values=run.mitigated_values.cpu().numpy(), per_factor=run.values.cpu().numpy(), shots=run.shots,
-                              variance=run.mitigated_variance.cpu().numpy(), per_factor_variance=run.variance.cpu().numpy())
-            run = zne_run(circuits, observables, self._noise, strategy, self._device, method=self._method)
-            fallback = None
-            if run.fallback_terms is not None:
-                ptr, flags = run.term_ptr.cpu().numpy(), run.fallback_terms.cpu().numpy()
-                fallback = [int(flags[ptr[k]:ptr[k + 1]].sum()) for k in range(len(circuits))]
-            return ZNEJob(strategy, run.schedules.achieved, len(circuits), f"zne-sim-{self._zne_count}",
-                          values=run.mitigated_values.cpu().numpy(), per_factor=run.values.cpu().numpy(), fallback=fallback)
+            # job j's run r draws with the key j * 2^32 + r, as on the shots path; a call that zne_run refuses is no job
+            job, n = self._zne_count + 1, len(circuits)
+            keys = np.arange(len(strategy.noise_factors) * n, dtype=np.int64) + (np.int64(job) << 32)
+            run = zne_run(circuits, observables, self._noise, strategy, self._device, shots=shots, seed=seed, run_keys=keys,
+                          method=self._method, **mps)
+            self._zne_count = job
+            return ZNEJob(strategy, run.schedules.achieved, n, f"zne-sim-{job}", values=run.mitigated_values.cpu().numpy(),
+                          rows=_fused_rows(strategy, run, n))
         parsed = [Circuit.from_any(c) for c in circuits]
         folded, achieved = [], []
         for lam in strategy.noise_factors:
@@ -972,6 +942,7 @@ def zne(cls):
                              for c in parsed])
         n_f = len(strategy.noise_factors)
         base = cls._run(self, folded, observables * n_f, parameter_values * n_f, **run_options)
+        self._zne_count += 1
         return ZNEJob(strategy, np.asarray(achieved, dtype=np.float64).reshape(n_f, len(parsed)), len(parsed),
                       f"zne-{self._zne_count}", base_job=base)
 

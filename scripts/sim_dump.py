@@ -11,10 +11,11 @@ bound_cases.grid in both forms with every shifted run, clifford_frames_cases' gr
 and mps_relax_cases.grid through run_mps, mps_shots_cases.grid through run_mps_shots with the bits, mps_zne_cases.grid through
 run_mps_folded, mps_bound_cases.grid through run_mps_bound (plain and shifted runs), mps_twirl_cases.grid through run_mps and
 run_mps_folded -- each once at the default buffer_bytes and once at the workspace of ONE unit of the case's widest circuit, which
-splits every circuit's trajectories over launches.
+splits every circuit's trajectories over launches.  The estimator section runs two successive jobs of DeviceEstimator under every
+method, and of zne(DeviceEstimator) where it folds, and keeps the values, every metadata field, the job ids and the key lists.
 
 --package-root DIR imports blackwater from another tree (a worktree of another commit, built in place) while the case modules
-stay this tree's: the MPS sections call only entry points of blackwater.sim.
+stay this tree's: the MPS and estimator sections call only public names of blackwater.sim.
 """
 import argparse
 import dataclasses
@@ -170,6 +171,51 @@ def dump(out):
         batch = sim.compile_clifford_frames([c for c, _ in cases], [t for _, t in cases], fc.GRID_NOISE[kind]())
         for shots in fc.GRID_SHOTS:
             put(f"frames/{kind}-{int(mixed)}-{shots}", sim.run_clifford_frames(batch, shots, fc.GRID_SEED, None, False, DEV))
+    section("estimator")
+    import json
+
+    def jobs(name, est, circuits, observables, rows=None):
+        """Two successive jobs of one estimator: the values, every metadata field as an array, the job id and the key lists."""
+        for j in (1, 2):
+            job = est.run(circuits, observables, rows)
+            res, tag = job.result(), f"estimator/{name}/job{j}"
+            arrays[f"{tag}/values"], arrays[f"{tag}/job_id"] = np.asarray(res.values), np.asarray(job.job_id())
+            arrays[f"{tag}/keys"] = np.asarray([",".join(m) for m in res.metadata])
+            for key in res.metadata[0]:
+                if key == "zne":
+                    arrays[f"{tag}/zne/keys"] = np.asarray([",".join(m["zne"]) for m in res.metadata])
+                    for k in res.metadata[0]["zne"]:
+                        arrays[f"{tag}/zne/{k}"] = np.asarray([m["zne"][k] for m in res.metadata])
+                else:
+                    arrays[f"{tag}/{key}"] = np.asarray([m[key] for m in res.metadata])
+
+    # the circuits come from the golden files and this tree's case modules, the estimators from blackwater.sim alone
+    with open(os.path.join(ROOT, "tests", "golden", "g1_circuits.json")) as fh:
+        g1 = list(json.load(fh)[:6])
+    g1_obs = [[("IIIIZ", 1.0)] if k % 2 else [("IIIZI", 0.5), ("IIZII", -2.0)] for k in range(6)]
+    lima = bc.lima_noise()
+    ideal, noisy = mc.case("tfim-cx-J1.9-s3-b4"), mc.case("noisy-readout-T64")   # lines: what the matrix-product-state methods take
+    line, line_obs, line_noise = noisy["circuits"], noisy["observables"], mc.noise_model("readout", 11)
+    cliffords, clifford_obs = zip(*(fc.grid_case(n, False) for n in (5, 33)))
+    clifford_noise = fc.GRID_NOISE["readout"]()
+    bound, bound_noisy = mbc.case("tfim-n12-s3-b4"), mbc.case("noisy-readout-T4")
+    per_row = [[bound_noisy[k][c] for c in bound_noisy["pair"]] for k in ("templates", "observables")]
+    theta = [row[:t.num_parameters] for row, t in zip(bound_noisy["rows"].tolist(), per_row[0])]
+    wide = dict(max_bond=4, trajectories=4)
+    for cls, tag in ((sim.DeviceEstimator, ""), (zne.zne(sim.DeviceEstimator), "zne-")):
+        jobs(f"{tag}exact", cls(lima, DEV), g1, g1_obs)
+        jobs(f"{tag}exact-shots", cls(lima, DEV, shots=1000, seed=3), g1, g1_obs)
+        jobs(f"{tag}clifford", cls(clifford_noise, DEV, method="clifford"), cliffords, clifford_obs)
+        jobs(f"{tag}mps-noise", cls(line_noise, DEV, method="mps", seed=5, **wide), line, line_obs)
+    jobs("frames", sim.DeviceEstimator(clifford_noise, DEV, method="frames", shots=64, seed=3), cliffords, clifford_obs)
+    jobs("trajectories", sim.DeviceEstimator(lima, DEV, method="trajectories", trajectories=16, seed=3), g1, g1_obs)
+    jobs("mps", sim.DeviceEstimator(None, DEV, method="mps", max_bond=4), ideal["circuits"], ideal["observables"])
+    jobs("mps_shots", sim.DeviceEstimator(None, DEV, method="mps_shots", shots=64, seed=3, max_bond=4), ideal["circuits"], ideal["observables"])
+    jobs("mps_shots-noise", sim.DeviceEstimator(line_noise, DEV, method="mps_shots", shots=64, seed=3, **wide), line, line_obs)
+    jobs("bound-exact", sim.DeviceEstimator(line_noise, DEV), *per_row, theta)
+    jobs("bound-mps", sim.DeviceEstimator(None, DEV, method="mps", max_bond=4), bound["templates"] * 2, bound["observables"] * 2,
+         bound["rows"].tolist())
+    jobs("bound-mps-noise", sim.DeviceEstimator(line_noise, DEV, method="mps", seed=5, **wide), *per_row, theta)
     torch.cuda.synchronize()
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     np.savez(out, **arrays)

@@ -87,8 +87,13 @@ int mlqem_graph_norms(const int32_t* in_ptr, const int32_t* out_ptr, const int32
  * CONTRACT: with 16-byte-aligned rows the columns C .. round_up(C,4)-1 of `out` ARE WRITTEN (scratch values).  A
  * caller whose `out` is a column slice of a wider matrix must pass an unaligned base / a leading dimension that is
  * not a multiple of 4, or use a padded buffer; the Python binding refuses such slices (ops._owns_pad_columns).
+ * Dropout mask (drop_p > 0): one splitmix64 hash per GROUP OF FOUR columns of a row, keyed by
+ * (seed [+ seed_counter], i * C + (c & ~3)); element (i, c) is dropped when 16-bit field (c & 3) of its group's hash is below
+ * floor(drop_p * 65536).  The mask of a (seed, row, column) depends on C alone: not on leading dimensions, alignment or the
+ * vector width the launcher picks for them.
  * seed_counter (may be NULL): a device-resident uint64 added (times an odd constant) to `seed` when the dropout mask is
- * drawn -- a launch captured in a hipGraph then draws a fresh mask on every replay as the caller bumps the counter.
+ * drawn -- a launch captured in a hipGraph then draws a fresh mask on every replay as the caller bumps the counter.  Every
+ * entry point that takes a seed_counter mixes it in this way; mlqem_linear_f32 takes none (see there).
  * ---------------------------------------------------------------------------------------------------- */
 int mlqem_csr_aggregate_f32(const float* x, int64_t ldx, const int32_t* ptr, const int32_t* idx, const int32_t* ell,
                             const float* cscale, const float* rscale, const float* dself, float alpha, float beta,
@@ -214,7 +219,8 @@ int mlqem_seq2_backward_f32(const float* gy, int64_t ldgy, const float* x, int64
 int mlqem_relu_dropout_bwd_f32(const float* g, int64_t ldg, const float* y, int64_t ldy, float scale, float* gx,
                                int64_t ldgx, int64_t N, int C, mlqem_stream_t stream);
 
-/* y = dropout(relu(x)) (inverted dropout, mask keyed by (seed [+ seed_counter], n*C + c)) and, when residual is given,
+/* y = dropout(relu(x)) (inverted dropout with the mask of mlqem_csr_aggregate_f32's epilogue: one hash per group of four columns,
+ * keyed by (seed [+ seed_counter], n*C + (c & ~3)), field c & 3 -- whatever the operands' layout) and, when residual is given,
  * sum = y + residual in the same pass -- the element-wise tail of an MLP2 / MLP3 trunk layer (docs/tutorials/mlp.py:60-66:
  * x1 = drop(relu(bn1(fc1 x))), x2 = drop(relu(bn2(fc2 x1))), x1 + x2) as ONE launch.  y is what the backward needs
  * (mlqem_relu_dropout_bwd_f32 recovers the mask from it); sum may be NULL; seed_counter as in mlqem_csr_aggregate_f32. */
@@ -231,7 +237,9 @@ int mlqem_relu_dropout_f32(const float* x, int64_t ldx, float drop_p, uint64_t s
  * stores it (transposed = 0), or the same with x @ W, W: [I,O] (transposed = 1: the data-gradient form gx = gy @ W).
  * b and rowscale may be NULL.  accumulate chains several calls into one sum of products (ChebConv's sum_k lins[k](T_k),
  * SAGEConv's lin_l(mean) + lin_r(x)); the activation belongs on the last call.  act bit 0 = ReLU; drop_p > 0 applies
- * inverted dropout keyed by (seed, n*O + o).  Column ranges: rowscale applies to outputs o < rs_cols and ReLU/dropout to
+ * inverted dropout keyed by (seed, n*O + o), one hash per ELEMENT (not the aggregation epilogue's mask).  This entry point takes NO
+ * seed_counter: a launch of it captured in a hipGraph repeats its mask on every replay (ChebConv with K = 1 or K > 3 puts its
+ * dropout here; the reference configuration, K = 3 / 2, does not).  Column ranges: rowscale applies to outputs o < rs_cols and ReLU/dropout to
  * outputs o >= act_from (-1, -1 = every column), so that one launch can serve several layers that read the same input
  * rows (the three first-layer projections of GCN | Cheb | SAGE).  gate (may be NULL), applied last:
  * y[n,o] = gate[n,o] > 0 ? y[n,o] * gate_scale : 0 -- the backward of a ReLU/dropout epilogue whose output `gate` is this
@@ -297,8 +305,9 @@ int mlqem_linear_parts_f32(const mlqem_col_parts* x, const float* const* w_block
  * (y[k]: [N, out_cols], padded rows) is
  *     Y_k = act((T[w_table[k]] (w[k] - w_minus[k])^T + T[w2_table[k]] (w2_scale[k] * w2[k])^T + bias[k]) * rowscale[k])
  * with the second term, w_minus, bias and rowscale optional (NULL); weights [out_cols, cols] row-major as the layers store them.
- * act[k] != 0: ReLU, then inverted dropout (drop_p > 0) with the mask of mlqem_csr_aggregate_f32's epilogue -- one hash per four
- * columns keyed by n * out_cols + column, seed + *seed_counter * 0xD1B54A32D192ED03 (seed_counter may be NULL).  At most
+ * act[k] != 0: ReLU, then inverted dropout (drop_p > 0) with the mask of mlqem_csr_aggregate_f32's epilogue for C = out_cols -- one
+ * hash per group of four columns keyed by n * out_cols + (column & ~3), field column & 3, seed + *seed_counter * 0xD1B54A32D192ED03
+ * (seed_counter may be NULL); the key uses the block's logical width, not its leading dimension.  At most
  * MLQEM_MAX_COL_PARTS blocks and as many terms in all; 17 <= cols <= 24, out_cols <= 16 (else MLQEM_ERR_UNSUPPORTED).  Blocks of
  * one term carry the values mlqem_linear_parts_f32 writes for them, bit for bit. */
 typedef struct mlqem_fanout_tables {

@@ -65,18 +65,22 @@ __device__ __forceinline__ float uniform01_edge(uint64_t seed, uint64_t idx) {
   return (float)(x >> 8) * (1.0f / 16777216.0f);
 }
 
-// Keep/drop decisions for V consecutive elements from ONE splitmix64 round keyed by the index of their first element:
-// element v is dropped when the v-th 16-bit field of the hash is < floor(p * 65536) (|P(drop) - p| < 1.6e-5).  The
-// aggregation epilogue draws a whole 16-byte slice at once: a quarter of the 64-bit multiplies of one hash per element.
-template <int V> __device__ __forceinline__ void dropout_keep(uint64_t seed, uint64_t first_idx, float p, bool (&keep)[V]) {
-  static_assert(V <= 4, "one 64-bit hash carries four 16-bit uniforms");
-  uint64_t z = seed + (first_idx + 1) * 0x9E3779B97F4A7C15ull;
+// Keep/drop decisions for the V consecutive elements col .. col + V - 1 of a row whose first element has index row_base
+// (= row * C): ONE splitmix64 round per GROUP OF FOUR columns, keyed row_base + (col & ~3); element (row, c) is dropped
+// when field (c & 3) of its group's hash is < floor(p * 65536) (|P(drop) - p| < 1.6e-5).  The mask of a (seed, row, column)
+// therefore does not depend on the vector width a launcher picks for the buffers it is handed: V = 4 (col a multiple of 4:
+// the aggregation epilogue draws a whole 16-byte slice at once, a quarter of the 64-bit multiplies of one hash per
+// element) reads fields 0..3, V = 2 (col even) fields 0, 1 or 2, 3, V = 1 the one field of its column.
+template <int V> __device__ __forceinline__ void dropout_keep(uint64_t seed, uint64_t row_base, int col, float p, bool (&keep)[V]) {
+  static_assert(V == 1 || V == 2 || V == 4, "one 64-bit hash carries four 16-bit uniforms; a slice never straddles two groups");
+  uint64_t z = seed + (row_base + (uint64_t)(V == 4 ? col : col & ~3) + 1) * 0x9E3779B97F4A7C15ull;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   z = z ^ (z >> 31);
   const unsigned thr = (unsigned)(p * 65536.f);
+  const int f0 = V == 4 ? 0 : (col & 3);
 #pragma unroll
-  for (int v = 0; v < V; ++v) keep[v] = (unsigned)((z >> (16 * v)) & 0xFFFFu) >= thr;
+  for (int v = 0; v < V; ++v) keep[v] = (unsigned)((z >> (16 * (f0 + v))) & 0xFFFFu) >= thr;
 }
 
 template <int V> struct VecT;

@@ -114,7 +114,7 @@ __device__ __forceinline__ unsigned finish_row(const AggArgs& a, int64_t row, in
     } else if (a.z) vload<VEC>(a.z + row * a.ldz + ch, zz);
     bool keep[VEC];
     if (a.drop_p > 0.f)
-      dropout_keep<VEC>(a.seed + (a.seed_counter ? *a.seed_counter * 0xD1B54A32D192ED03ull : 0ull), (uint64_t)(row * a.C + ch),
+      dropout_keep<VEC>(a.seed + (a.seed_counter ? *a.seed_counter * 0xD1B54A32D192ED03ull : 0ull), (uint64_t)(row * a.C), ch,
                         a.drop_p, keep);
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {
@@ -700,7 +700,7 @@ __global__ __launch_bounds__(kBlock) void relu_dropout_bwd_kernel(const float* _
 
 // y = dropout(relu(x)) and, with a residual, sum = y + residual in the same pass (the trunk of MLP2 / MLP3:
 // x1 + drop(relu(bn2(...))), docs/tutorials/mlp.py:60-66): one launch instead of three element-wise ones.  Masks: one hash
-// per 4 consecutive elements of a row (dropout_keep), keyed by (seed + counter, row * C + col).
+// per group of four columns of a row (dropout_keep), keyed by (seed + counter, row * C + (col & ~3)), whatever the operands' layout.
 template <int VEC>
 __global__ __launch_bounds__(kBlock) void relu_dropout_kernel(const float* __restrict__ x, int64_t ldx, float p, uint64_t seed,
                                                               const uint64_t* __restrict__ seed_counter,
@@ -717,7 +717,7 @@ __global__ __launch_bounds__(kBlock) void relu_dropout_kernel(const float* __res
   bool keep[VEC];
 #pragma unroll
   for (int v = 0; v < VEC; ++v) keep[v] = true;
-  if (p > 0.f) dropout_keep<VEC>(seed + (seed_counter ? *seed_counter * 0xD1B54A32D192ED03ull : 0ull), (uint64_t)(r * C + c), p, keep);
+  if (p > 0.f) dropout_keep<VEC>(seed + (seed_counter ? *seed_counter * 0xD1B54A32D192ED03ull : 0ull), (uint64_t)(r * C), c, p, keep);
 #pragma unroll
   for (int v = 0; v < VEC; ++v) {
     const float u = fmaxf(xv[v], 0.f);

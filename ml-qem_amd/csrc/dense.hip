@@ -928,7 +928,7 @@ __global__ __launch_bounds__(kBlock) void linear_fanout_tables_kernel(const FanT
         for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
         if (a.drop_p > 0.f) {
           bool keep[4];
-          dropout_keep<4>(seed, (uint64_t)(row * a.yc + 4 * lq), a.drop_p, keep);
+          dropout_keep<4>(seed, (uint64_t)(row * a.yc), 4 * lq, a.drop_p, keep);
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = keep[r] ? v[r] * keep_scale : 0.f;
         }
@@ -1140,7 +1140,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3, 3))) 
         if (drop_p > 0.f) {
           const float keep_scale = 1.f / (1.f - drop_p);
           bool keep[4];
-          dropout_keep<4>(a.seedk[blk] + ctr, (uint64_t)(row * a.yc + 4 * lq), drop_p, keep);
+          dropout_keep<4>(a.seedk[blk] + ctr, (uint64_t)(row * a.yc), 4 * lq, drop_p, keep);
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = keep[r] ? v[r] * keep_scale : 0.f;
         }

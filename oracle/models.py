@@ -140,16 +140,29 @@ class FamilyA(nn.Module):
         self.body_seq = nn.Sequential(nn.Linear(6, hc), nn.Linear(hc, 1))
         self.p_gcn, self.p_other = 0.1, 0.2
 
-    def forward(self, exp_value, observable, circuit_depth, nodes, edge_index, batch):
-        drop = lambda t, p: nn.functional.dropout(t, p=p, training=self.training)
+    def forward(self, exp_value, observable, circuit_depth, nodes, edge_index, batch, masks=None):
+        """``masks`` (optional): a mapping from ``conv1``, ``conv2``, ``cheb_conv1``, ``sage_conv1``, ``obs_seq`` to a keep tensor
+        of that layer's activation -- a present entry replaces the generator's dropout by ``t * keep / (1 - p)`` (a test hands in the
+        masks the device drew); an absent one leaves ``nn.functional.dropout``."""
+        masks = masks or {}
+
+        def drop(t, p, name):
+            if name in masks:
+                return t * masks[name].to(t.dtype) / (1.0 - p)
+            return nn.functional.dropout(t, p=p, training=self.training)
+
         b = exp_value.shape[0]
-        g = drop(self.conv1(nodes, edge_index).relu(), self.p_gcn)
-        g = drop(self.conv2(g, edge_index).relu(), self.p_gcn)
+        g = drop(self.conv1(nodes, edge_index).relu(), self.p_gcn, "conv1")
+        g = drop(self.conv2(g, edge_index).relu(), self.p_gcn, "conv2")
         g = global_mean_pool(self.conv3(g, edge_index), batch, b)
-        c = drop(self.cheb_conv1(nodes, edge_index).relu(), self.p_other)
+        c = drop(self.cheb_conv1(nodes, edge_index).relu(), self.p_other, "cheb_conv1")
         c = global_mean_pool(self.cheb_conv2(c, edge_index), batch, b)
-        s = drop(self.sage_conv1(nodes, edge_index).relu(), self.p_other)
+        s = drop(self.sage_conv1(nodes, edge_index).relu(), self.p_other, "sage_conv1")
         s = global_mean_pool(self.sage_conv2(s, edge_index), batch, b)
-        obs = torch.mean(self.obs_seq(observable), dim=1)
+        if "obs_seq" in masks:
+            lin1, mid, lin2 = self.obs_seq
+            obs = torch.mean(lin2(drop(lin1(observable), mid.p, "obs_seq")), dim=1)
+        else:
+            obs = torch.mean(self.obs_seq(observable), dim=1)
         merged = torch.cat((g, c, s, obs, circuit_depth, exp_value), dim=1)
         return self.body_seq(merged)

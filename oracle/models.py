@@ -34,13 +34,20 @@ class MLP2(nn.Module):
         self.fc3 = nn.Linear(hidden_size, output_size)
         self.drop = nn.Dropout(dropout_rate)
 
-    def trunk(self, x):
-        x1 = self.drop(torch.relu(self.bn1(self.fc1(x))))
-        x2 = self.drop(torch.relu(self.bn2(self.fc2(x1))))
+    def _drop(self, t, masks, name):
+        """``masks`` (optional): a mapping from ``block1``, ``block2``, ``tail`` to a keep tensor of that activation -- a present entry
+        replaces ``self.drop`` by ``t * keep / (1 - p)`` (a test hands in the masks the device drew), as FamilyA.forward's does."""
+        if masks and name in masks:
+            return t * masks[name].to(t.dtype) / (1.0 - self.drop.p)
+        return self.drop(t)
+
+    def trunk(self, x, masks=None):
+        x1 = self._drop(torch.relu(self.bn1(self.fc1(x))), masks, "block1")
+        x2 = self._drop(torch.relu(self.bn2(self.fc2(x1))), masks, "block2")
         return x1 + x2
 
-    def forward(self, x):
-        return self.fc3(self.trunk(x))
+    def forward(self, x, masks=None):
+        return self.fc3(self.trunk(x, masks))
 
 
 class MLP3(MLP2):
@@ -49,8 +56,8 @@ class MLP3(MLP2):
         self.fc3 = nn.Linear(hidden_size, hidden_size // 3)
         self.fc4 = nn.Linear(hidden_size // 3, output_size)
 
-    def forward(self, x):
-        return self.fc4(self.drop(torch.relu(self.fc3(self.trunk(x)))))
+    def forward(self, x, masks=None):
+        return self.fc4(self._drop(torch.relu(self.fc3(self.trunk(x, masks))), masks, "tail"))
 
 
 class _Identity2(nn.Module):

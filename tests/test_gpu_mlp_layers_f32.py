@@ -3,8 +3,9 @@ docs/tutorials/mlp.py:33-108 in torch's default dtype) -- ev
 SAME fp32 inputs, then the composed modules' train step against the CPU oracle in fp64.
 
 Stated tolerance: 1e-5 of the result's scale everywhere (fp32 products and sums against fp64; nothing is rounded to a shorter
-format in this mode).  Dropout masks are counter-based; what is checked of them is the keep rate and that the backward regenerates
-the forward's mask exactly."""
+format in this mode).  Dropout masks are counter-based; what is checked of them HERE is the keep rate and that the backward regenerates
+the forward's mask exactly -- test_gpu_mlp_dropout_reference.py holds the masks themselves, the backward's values and the train step
+with dropout on against fp64 with a host replica of the draw."""
 import pytest
 import torch
 
